@@ -11,9 +11,14 @@ HBM (normalised float32 NCHW).  Default workload = BASELINE.json configs[1]: bat
 refinement stage, fp32.  Frames shard across ranks with no data-path collective (weights are broadcast
 once over RCCL at start-up), so scaling is weak: every rank processes `--batch` frames per step.
 
-Timing protocol: W untimed warm-up steps, then BLOCKS of exactly K steps, each bracketed by a barrier +
-device synchronisation on both sides and reduced with MAX over the ranks; blocks repeat until >= --min-time
-seconds have been measured and `value` is the MEDIAN block (every block's figure is listed in `block_values`).
+Timing protocol: W untimed warm-up steps, then ONE block of exactly K timed steps, bracketed by a barrier +
+device synchronisation on both sides and reduced with MAX over the ranks; `value` = frames of the block / its time and
+`ms_per_step` = its time / K.  With --min-time S, blocks of K steps repeat until >= S seconds have been measured and
+`value` is the MEDIAN block (every block's figure is listed in `block_values`).
+
+A plain run measures only the headline.  --full adds, after the timed region, the replica / weight-digest check, serial
+latency, single-stream rate, device-only rates, per-class rooflines, the CPU baseline and the other BASELINE configs.
+--dump-outputs DIR writes the last timed step's results (what a caller of the step receives) as float64 .npy files.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields).
 """
@@ -197,11 +202,17 @@ def parse_args():
                     help="independent engine instances (own HIP streams and buffers) per GPU that take the steps round-robin; "
                          "every step is still one batch through the whole path.  At batch 1 one frame's kernels only half-fill "
                          "the chip, so frames in flight overlap (1 = single stream)")
-    ap.add_argument("--min-time", type=float, default=1.0, help="repeat the timed block of --steps steps until this many seconds are measured")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the timed block of --steps steps until this many seconds are measured (default: one block)")
     ap.add_argument("--max-blocks", type=int, default=400)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the replica check and the extra measurements (latency, single stream, "
+                         "rooflines, cpu_baseline, other_configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results as DIR/frame<i>_<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the short measurements of the other BASELINE configs reported under other_configs")
+                    help="with --full: skip the short measurements of the other BASELINE configs reported under other_configs")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--preroll", type=float, default=0.3, help="seconds of untimed passes before the warm-up steps (clock ramp)")
     return ap.parse_args()
@@ -345,8 +356,8 @@ def main():
 
     # every replica (engine streams of this rank; on ranks > 0 also engine 0, whose weights came over the broadcast) must give
     # engine 0's results on this rank's frames bit for bit, and every rank's packed weights must hash alike: a wrong replica
-    # would still print a frames/s line
-    if not rehearsal:
+    # would still print a frames/s line (--full)
+    if args.full and not rehearsal:
         ref_res = step()
         for e in engines[1:]:
             e.infer_poses_async(x, 4, True)
@@ -428,6 +439,8 @@ def main():
             break
     dt = sorted(blocks)[(len(blocks) - 1) // 2]          # median block (lower middle: an actual measurement)
 
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs, rank * args.batch, world)
     if _TRACE is not None:
         d = np.diff(np.array(_TRACE[-args.steps:])) * 1e3
         print("trace: first 24 iteration gaps (ms):", [round(float(v), 2) for v in d[:24]], "median", round(float(np.median(d)), 3),
@@ -456,12 +469,34 @@ def main():
             out["rehearsal"] = "stand-in engines from %s (no GPU touched): protocol check only, not a measurement" % factory
             out["roofline"] = None
             out["cpu_baseline"] = None
-        else:
+        elif args.full:
             measure_extras(out, args, eng, engines, net, sd, x, x_np, step, run_steps, local_rank, world)
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.barrier()              # rank 0 is still measuring its extra figures: leave together
         torch.distributed.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, frame0, world):
+    """The last timed step's results as its caller receives them, per frame (pose entries (P, 20), all key-points (K, 4),
+    key-points per type (18,)), as float64 DIR/frame<global frame index>_<name>.npy.  Above 64 MB in all (split over the
+    ranks) a fixed, seeded sample of the frames is written."""
+    os.makedirs(out_dir, exist_ok=True)
+    frames = [[np.asarray(a, dtype=np.float64) for a in r] for r in res]
+    order = range(len(frames))
+    if sum(a.nbytes for f in frames for a in f) > DUMP_LIMIT_BYTES // world:
+        order = np.random.default_rng(0).permutation(len(frames))
+    total = 0
+    for i in order:
+        nbytes = sum(a.nbytes for a in frames[i])
+        if total + nbytes > DUMP_LIMIT_BYTES // world:
+            continue
+        total += nbytes
+        for name, a in zip(("pose_entries", "keypoints", "type_counts"), frames[i]):
+            np.save(os.path.join(out_dir, "frame%04d_%s.npy" % (frame0 + i, name)), a)
 
 
 def measure_extras(out, args, eng, engines, net, sd, x, x_np, step, run_steps, local_rank, world):

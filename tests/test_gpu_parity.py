@@ -138,7 +138,8 @@ def test_net_matches_reference_golden_small():
 
 
 def test_net_mid_batch3_odd_maps_golden():
-    g = np.load(os.path.join(GOLDEN, "net_mid_nref1.npz"))
+    g = dict(np.load(os.path.join(GOLDEN, "net_mid_nref1.npz")))
+    g.update(np.load(os.path.join(GOLDEN, "net_mid_nref1_refinement.npz")))     # stored in two files of < 1 MiB each
     net, _ = get_net(1, 7)
     outs = net(net_input(3, 184, 328, seed=200))
     for i, o in enumerate(outs):

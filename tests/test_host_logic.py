@@ -400,6 +400,29 @@ def test_bench_multi_rank_protocol_over_gloo(tmp_path):
     assert out["block_spread"]["min"] <= out["value"] <= out["block_spread"]["max"]
 
 
+def test_bench_plain_run_times_one_block_of_steps_and_dumps_the_last_step(tmp_path):
+    """A plain bench.py run (no --full, no --min-time) times exactly --steps steps in one block, makes none of the extra
+    measurements, and --dump-outputs writes every frame's results of the last timed step as float64 .npy (stand-in engines)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "2",
+           "--preroll", "0", "--dump-outputs", str(tmp_path / "out")]
+    env = dict(os.environ, OMP_NUM_THREADS="1", LWP_BENCH_ENGINE_FACTORY="tests.stub_engine:make")
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    from tests.stub_engine import STEP_SECONDS
+    assert out["steps"] == 5 and out["timed_blocks"] == 1 and len(out["block_values"]) == 1
+    assert out["ms_per_step"] >= STEP_SECONDS * 1e3 * 0.98
+    assert abs(out["value"] - 2 / (out["ms_per_step"] / 1e3)) < 1e-6 * out["value"]
+    assert out["replica_check"] is None and "roofline_classes" not in out and "other_configs" not in out
+    names = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert names == sorted("frame%04d_%s.npy" % (f, n) for f in range(2) for n in ("pose_entries", "keypoints", "type_counts"))
+    e, k, c = (np.load(tmp_path / "out" / ("frame0001_%s.npy" % n)) for n in ("pose_entries", "keypoints", "type_counts"))
+    assert e.dtype == k.dtype == c.dtype == np.float64
+    assert e.shape == (2, 20) and k.shape == (5, 4) and c.shape == (18,)
+
+
 def test_pose_draw_marks_joints_and_limbs_and_stays_inside_the_image():
     """modules/pose.py:47-62 (`Pose.draw`: circles on the found key-points, a line per limb whose two ends were found).  The
     rasteriser is the product's own (cv2 is absent): joints and limbs must be painted in `Pose.color`, missing key-points

@@ -57,7 +57,8 @@ def test_net_small_all_stages_and_taps(nref):
 
 
 def test_net_mid_batch3():
-    g = np.load(os.path.join(GOLDEN, "net_mid_nref1.npz"))
+    g = dict(np.load(os.path.join(GOLDEN, "net_mid_nref1.npz")))
+    g.update(np.load(os.path.join(GOLDEN, "net_mid_nref1_refinement.npz")))     # stored in two files of < 1 MiB each
     x = net_input(3, 184, 328, seed=200)
     assert digest(x) == str(g["in_digest"])
     outs = net_ref.forward(synth.make_state_dict(1, seed=7), torch.from_numpy(x), 1)
