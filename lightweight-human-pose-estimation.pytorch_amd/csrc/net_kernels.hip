@@ -945,8 +945,12 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
     };
     constexpr int PF = AR_PF;                               // weight steps in flight per wave (register ring, static indices)
     f32x4 bv[PF][BK / 8];
+    // a group without blocks (1x1 layer with cin_pad / 32 < KS) prefetches nothing: its step 0 would be weight step g,
+    // past the layer's packed weights, and the weight descriptor does not bound the read (wave-uniform branch)
+    if (my_steps > 0) {
 #pragma unroll
-    for (int u = 0; u < PF - 1; ++u) load_b(u < my_steps ? u : (my_steps > 0 ? my_steps - 1 : 0), bv[u]);
+        for (int u = 0; u < PF - 1; ++u) load_b(u < my_steps ? u : my_steps - 1, bv[u]);
+    }
     __syncthreads();                                        // the windows of every group are complete
 
     f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};

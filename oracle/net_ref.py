@@ -1,7 +1,7 @@
 """ORACLE — test infrastructure, NOT product code.
 
 CPU restatement of the reference network forward, written as straight-line functional
-calls on a ``state_dict`` (no nn.Module), fp32, stock ``torch.nn.functional`` CPU kernels.
+calls on a ``state_dict`` (no nn.Module), fp32 (float64 through ``forward64``), stock ``torch.nn.functional`` CPU kernels.
 Only tests/, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg import it.
 
 Follows (reference file:line):
@@ -39,20 +39,50 @@ def _c3(x, sd, p, dil=1, bn=None):
     return F.relu(y)
 
 
-def _heads(x, sd, p):
-    h = _conv(F.relu(_conv(x, sd, p + ".heatmaps.0.0")), sd, p + ".heatmaps.1.0")
-    q = _conv(F.relu(_conv(x, sd, p + ".pafs.0.0")), sd, p + ".pafs.1.0")
+def _heads(x, sd, p, tap):
+    hh = tap(p + ".heatmaps.0", F.relu(_conv(x, sd, p + ".heatmaps.0.0")))
+    qh = tap(p + ".pafs.0", F.relu(_conv(x, sd, p + ".pafs.0.0")))
+    h = tap(p + ".heatmaps.1", _conv(hh, sd, p + ".heatmaps.1.0"))
+    q = tap(p + ".pafs.1", _conv(qh, sd, p + ".pafs.1.0"))
     return [h, q]
 
 
-def forward(sd, x, num_refinement_stages=1, taps=None):
+class _Stop(Exception):
+    pass
+
+
+def forward(sd, x, num_refinement_stages=1, taps=None, stop_after=None):
     """x: (N,3,H,W) f32 -> [heat0, paf0, heat1, paf1, ...] like the reference forward.
-    ``taps``: optional dict filled with intermediate activations (NCHW) for per-layer parity tests."""
+    ``taps``: optional dict filled with intermediate activations (NCHW) for per-layer parity tests.
+    ``stop_after``: name of a tap after which the forward ends (returns None; ``taps`` holds what was computed)."""
     def tap(name, t):
         if taps is not None:
             taps[name] = t
+        if name == stop_after:
+            raise _Stop
         return t
 
+    try:
+        return _forward(sd, x, num_refinement_stages, tap)
+    except _Stop:
+        return None
+
+
+def to_float64(sd, x):
+    """(state dict, input) cast to float64: ``forward`` on them is the float64 oracle the kernel-variant tests use.
+    Integer entries (num_batches_tracked) stay as they are."""
+    sd64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()}
+    x = torch.as_tensor(x)
+    return sd64, x.double()
+
+
+def forward64(sd, x, num_refinement_stages=1, taps=None, stop_after=None):
+    """``forward`` in float64 (``sd`` and ``x`` may be fp32 / numpy); taps and outputs are float64 tensors."""
+    sd64, x64 = to_float64(sd, x)
+    return forward(sd64, x64, num_refinement_stages, taps, stop_after)
+
+
+def _forward(sd, x, num_refinement_stages, tap):
     with torch.no_grad():
         x = F.relu(_bn(_conv(x, sd, "model.0.0", 2, 1), sd, "model.0.1"))
         tap("model.0", x)
@@ -79,17 +109,17 @@ def forward(sd, x, num_refinement_stages=1, taps=None):
         for j in range(3):
             t = _c3(t, sd, "initial_stage.trunk.%d.0" % j)
             tap("initial_stage.trunk.%d" % j, t)
-        outs = _heads(t, sd, "initial_stage")
+        outs = _heads(t, sd, "initial_stage", tap)
         # refinement stages
         for k in range(num_refinement_stages):
             p = "refinement_stages.%d" % k
             t = torch.cat([feat, outs[-2], outs[-1]], 1)
             for b in range(5):
                 q = "%s.trunk.%d" % (p, b)
-                ini = F.relu(_conv(t, sd, q + ".initial.0"))
-                u = _c3(ini, sd, q + ".trunk.0.0", 1, q + ".trunk.0.1")
+                ini = tap(q + ".initial", F.relu(_conv(t, sd, q + ".initial.0")))
+                u = tap(q + ".trunk.0", _c3(ini, sd, q + ".trunk.0.0", 1, q + ".trunk.0.1"))
                 u = _c3(u, sd, q + ".trunk.1.0", 2, q + ".trunk.1.1")
                 t = ini + u
                 tap(q, t)
-            outs.extend(_heads(t, sd, p))
+            outs.extend(_heads(t, sd, p, tap))
     return outs
