@@ -43,8 +43,10 @@ enum {
 
 enum { LWP_MEM_HOST = 0, LWP_MEM_DEVICE = 1 };
 enum { LWP_LAYOUT_NCHW = 0, LWP_LAYOUT_NHWC = 1 };
-enum { LWP_F32 = 0, LWP_BF16 = 1 };   /* storage/MFMA dtype of the conv stack; accumulation, bias,
-                                         activations and all post-processing are always f32/f64 */
+enum { LWP_F32 = 0, LWP_BF16 = 1, LWP_F16 = 2 };   /* storage/MFMA dtype of the conv stack; accumulation, bias, depthwise
+                                                       weights, activations and all post-processing are always f32/f64.
+                                                       LWP_F16 (IEEE half) is the bf16 graph with 3 more significand bits;
+                                                       a folded weight beyond +-65504 fails lwp_load_weights */
 
 /* role codes returned by lwp_param_spec */
 enum { LWP_ROLE_CONV_W = 0, LWP_ROLE_CONV_B = 1, LWP_ROLE_BN_W = 2, LWP_ROLE_BN_B = 3,
@@ -90,7 +92,8 @@ int lwp_load_weights(lwp_handle h, const char* const* names, const void* const* 
                      const int64_t* shapes, const int* ndims, int n);
 
 /* packed weight blob, for one-shot replication to other GPUs (RCCL broadcast done by the host side
- * on a device buffer; replaces nn.DataParallel's per-iteration replicate, train.py:74). */
+ * on a device buffer; replaces nn.DataParallel's per-iteration replicate, train.py:74).  An LWP_F16 blob ends in a 16-byte
+ * dtype tag; importing a blob of another dtype (or network) fails with LWP_ERR_ARG. */
 int lwp_weights_blob_bytes(lwp_handle h, size_t* bytes);
 int lwp_weights_blob_export(lwp_handle h, void* dst_device, size_t bytes);
 int lwp_weights_blob_import(lwp_handle h, const void* src_device, size_t bytes);
@@ -238,6 +241,9 @@ int lwp_debug_layer_output(lwp_handle h, const float* in, int N, int H, int W, i
  * pair reports the pair's kernel).  Lets a test prove that the kernel it means to cover is the one that ran: the launchers
  * choose by problem size, and the A/B switches (environment, read once per handle in lwp_create) only override that choice. */
 int lwp_debug_layer_variant(lwp_handle h, int layer_index, char* name, int name_cap);
+/* the host's f32 -> fp16 conversion of LWP_F16 weight packing (round to nearest even, subnormals kept, inf beyond 65520),
+ * n values; no handle, no GPU */
+int lwp_debug_f32_to_f16(const float* src, uint16_t* dst, int64_t n);
 /* frames one launch sequence of an N x 3 x H x W call takes (N unless a tensor of the pass would reach the kernels' 2 GiB
  * addressing range: lwp_forward / lwp_infer_poses* / lwp_pipeline_submit then walk the batch in equal chunks of this size) */
 int lwp_debug_frames_per_pass(lwp_handle h, int N, int H, int W);

@@ -8,7 +8,7 @@ LIB_PATH = os.path.join(PKG, "liblwpose_hip.so")
 
 LWP_OK, LWP_ERR_ARG, LWP_ERR_HIP, LWP_ERR_STATE, LWP_ERR_CAPACITY, LWP_ERR_NOGPU, LWP_ERR_UNBOUND = 0, -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2
 
 EXPORTS = [
     "lwp_version", "lwp_param_count", "lwp_param_spec", "lwp_create", "lwp_destroy", "lwp_last_error",
@@ -18,6 +18,7 @@ EXPORTS = [
     "lwp_synchronize", "lwp_poses_from_maps", "lwp_layer_count", "lwp_layer_info", "lwp_debug_layer_output",
     "lwp_profile_launches", "lwp_debug_time_layer", "lwp_pipeline_submit", "lwp_pipeline_fetch", "lwp_multiscale_accumulate",
     "lwp_preprocess_dims", "lwp_preprocess_u8", "lwp_scale_dims", "lwp_preprocess_scaled_u8", "lwp_debug_layer_variant", "lwp_set_stream", "lwp_preprocess_scaled_f32", "lwp_debug_frames_per_pass", "lwp_debug_post_counts",
+    "lwp_debug_f32_to_f16",
 ]
 
 
@@ -79,6 +80,7 @@ def lib():
     L.lwp_set_stream.argtypes = [vp, vp, C.c_int]
     L.lwp_debug_frames_per_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.lwp_debug_post_counts.argtypes = [vp, C.c_int] + [C.POINTER(C.c_int)] * 4
+    L.lwp_debug_f32_to_f16.argtypes = [vp, vp, C.c_int64]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

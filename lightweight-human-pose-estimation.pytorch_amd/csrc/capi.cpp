@@ -173,11 +173,11 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
     if (!out) return fail(nullptr, LWP_ERR_ARG, "out is null");
     *out = nullptr;
     if (nref < 0 || C <= 0 || C % 32 || NH <= 0 || NP <= 0) return fail(nullptr, LWP_ERR_ARG, "bad network shape (num_channels must be a multiple of 32)");
-    if (dtype != LWP_F32 && dtype != LWP_BF16) return fail(nullptr, LWP_ERR_ARG, "bad dtype");
-    // the bf16 graph has no stand-alone depthwise kernel and its GEMM walks K in 64-channel steps: cpm.trunk must fuse
-    // (C in {64, 128, 256, 512}); any other width would run f32 kernels on bf16-sized buffers
-    if (dtype == LWP_BF16 && !(C % 64 == 0 && dwpw_supported(C, C)))
-        return fail(nullptr, LWP_ERR_ARG, "bf16 path supports num_channels 64, 128, 256 or 512 only");
+    if (dtype != LWP_F32 && dtype != LWP_BF16 && dtype != LWP_F16) return fail(nullptr, LWP_ERR_ARG, "bad dtype");
+    // the 16-bit graph has no stand-alone depthwise kernel and its GEMM walks K in 64-channel steps: cpm.trunk must fuse
+    // (C in {64, 128, 256, 512}); any other width would run f32 kernels on 16-bit buffers
+    if (dtype != LWP_F32 && !(C % 64 == 0 && dwpw_supported(C, C)))
+        return fail(nullptr, LWP_ERR_ARG, std::string(dtype == LWP_F16 ? "fp16" : "bf16") + " path supports num_channels 64, 128, 256 or 512 only");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, LWP_ERR_NOGPU, "no HIP device available");
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, LWP_ERR_ARG, "device_id out of range");
@@ -300,22 +300,45 @@ extern "C" int lwp_load_weights(lwp_handle h, const char* const* names, const vo
     return LWP_OK;
 }
 
+// A bf16 and an fp16 blob of one network have the same packed size, so an fp16 blob carries a 16-byte trailer (tag + packed
+// size) that the import checks: a blob of another dtype is refused instead of being reinterpreted.  f32 and bf16 blobs are
+// the packed weights alone, as they always were.
+static void f16_blob_tag(const lwp_context* h, uint64_t tag[2]) {
+    std::memcpy(&tag[0], "lwpF16\0\1", 8);
+    tag[1] = (uint64_t)h->g.blob_floats;
+}
+static size_t blob_bytes(const lwp_context* h) {
+    return h->g.blob_floats * sizeof(float) + (h->dtype == LWP_F16 ? 2 * sizeof(uint64_t) : 0);
+}
 extern "C" int lwp_weights_blob_bytes(lwp_handle h, size_t* bytes) {
     if (!h || !bytes) return LWP_ERR_ARG;
-    *bytes = h->g.blob_floats * sizeof(float);
+    *bytes = blob_bytes(h);
     return LWP_OK;
 }
 extern "C" int lwp_weights_blob_export(lwp_handle h, void* dst, size_t bytes) {
-    if (!h || !dst || bytes != h->g.blob_floats * sizeof(float)) return fail(h, LWP_ERR_ARG, "bad blob size");
+    if (!h || !dst || bytes != blob_bytes(h)) return fail(h, LWP_ERR_ARG, "bad blob size");
     if (!h->weights_loaded) return fail(h, LWP_ERR_STATE, "weights not loaded");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpy(dst, h->d_blob, bytes, hipMemcpyDeviceToDevice));
+    const size_t packed = h->g.blob_floats * sizeof(float);
+    HIP_TRY(h, hipMemcpy(dst, h->d_blob, packed, hipMemcpyDeviceToDevice));
+    if (h->dtype == LWP_F16) {
+        uint64_t tag[2];
+        f16_blob_tag(h, tag);
+        HIP_TRY(h, hipMemcpy((char*)dst + packed, tag, sizeof(tag), hipMemcpyHostToDevice));
+    }
     return LWP_OK;
 }
 extern "C" int lwp_weights_blob_import(lwp_handle h, const void* src, size_t bytes) {
-    if (!h || !src || bytes != h->g.blob_floats * sizeof(float)) return fail(h, LWP_ERR_ARG, "bad blob size");
+    if (!h || !src || bytes != blob_bytes(h)) return fail(h, LWP_ERR_ARG, "bad blob size (a blob of another dtype or network?)");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpy(h->d_blob, src, bytes, hipMemcpyDeviceToDevice));
+    const size_t packed = h->g.blob_floats * sizeof(float);
+    if (h->dtype == LWP_F16) {
+        uint64_t want[2], got[2];
+        f16_blob_tag(h, want);
+        HIP_TRY(h, hipMemcpy(got, (const char*)src + packed, sizeof(got), hipMemcpyDeviceToHost));
+        if (std::memcmp(want, got, sizeof(want)) != 0) return fail(h, LWP_ERR_ARG, "not an fp16 weight blob of this network");
+    }
+    HIP_TRY(h, hipMemcpy(h->d_blob, src, packed, hipMemcpyDeviceToDevice));
     h->weights_loaded = true;
     return LWP_OK;
 }
@@ -336,7 +359,7 @@ static int ensure_activations(lwp_context* h, int N, int H, int W) {
     for (size_t i = 0; i < h->bufs.size(); ++i) {
         int bh, bw;
         level_dims(H, W, h->g.bufs[i].level, &bh, &bw);
-        const size_t bytes = (size_t)N * bh * bw * h->g.bufs[i].channels * (h->dtype == LWP_BF16 ? 2 : 4);
+        const size_t bytes = (size_t)N * bh * bw * h->g.bufs[i].channels * (h->dtype != LWP_F32 ? 2 : 4);
         if (bytes > h->buf_bytes[i]) {
             if (!synced) { HIP_TRY(h, hipStreamSynchronize(h->stream)); synced = true; }
             if (h->bufs[i]) { HIP_TRY(h, hipFree(h->bufs[i])); h->bufs[i] = nullptr; h->buf_bytes[i] = 0; }
@@ -443,7 +466,7 @@ static int frames_per_pass(lwp_context* h, int N, int H, int W) {
     for (const BufSpec& b : h->g.bufs) {
         int bh, bw;
         level_dims(H, W, b.level, &bh, &bw);
-        per = std::max(per, (size_t)bh * bw * b.channels * (h->dtype == LWP_BF16 ? 2 : 4));
+        per = std::max(per, (size_t)bh * bw * b.channels * (h->dtype != LWP_F32 ? 2 : 4));
     }
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);
@@ -476,15 +499,16 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
 }
 
 // ---------------------------------------------------------------------------------------------- forward
-// element-addressed window of an activation buffer (f32 or bf16 storage)
+// element-addressed window of an activation buffer (f32, bf16 or fp16 storage)
 static inline float* buf_at(lwp_context* h, const BufRef& r) {
-    return (float*)((char*)h->bufs[r.buf] + (size_t)r.coff * (h->dtype == LWP_BF16 ? 2 : 4));
+    return (float*)((char*)h->bufs[r.buf] + (size_t)r.coff * (h->dtype != LWP_F32 ? 2 : 4));
 }
 
 static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int N, int H, int W, float* const* d_outs_nchw,
                          const Layer* fold = nullptr, bool* folded = nullptr) {
     const Graph& g = h->g;
-    const bool h16 = h->dtype == LWP_BF16;
+    const bool h16 = h->dtype != LWP_F32;            // bf16 or fp16: the same launchers, the element type rides in the params
+    const int f16 = h->dtype == LWP_F16;
     const float* wts = h->d_blob + l.w_off;
     const float* bias = h->d_blob + l.b_off;
     int dh, dw;
@@ -493,14 +517,14 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
     char* vb = h->record_variants ? h->variant_buf : nullptr;
     if (vb) vb[0] = 0;
     if (l.kind == L_STEM) {
-        StemParams p{d_in, wts, bias, dst, N, H, W, dh, dw, h->d_zeros};
+        StemParams p{d_in, wts, bias, dst, N, H, W, dh, dw, f16, h->d_zeros};
         p.tune = &h->tune; p.variant = vb;
         LAUNCH(h, KC_STEM, h16 ? launch_stem_bf16(p, h->stream) : launch_stem(p, h->stream));
     } else if (l.kind == L_DWPW) {
         int sh, sw;
         level_dims(H, W, g.bufs[l.src.buf].level, &sh, &sw);
         DwPwParams p;
-        p.in = buf_at(h, l.src); p.in_ld = l.src.ld;
+        p.in = buf_at(h, l.src); p.in_ld = l.src.ld; p.f16 = f16;
         p.dw_w = wts; p.pw_w = h->d_blob + l.w2_off; p.pw_b = h->d_blob + l.b2_off;
         p.out = dst; p.out_ld = l.dst.ld;
         p.res = l.res.buf >= 0 ? buf_at(h, l.res) : nullptr; p.res_ld = l.res.ld;
@@ -517,7 +541,7 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
         LAUNCH(h, KC_DW, launch_dw(p, h->stream));
     } else {
         GemmParams p;
-        p.in = buf_at(h, l.src); p.in_ld = l.src.ld;
+        p.in = buf_at(h, l.src); p.in_ld = l.src.ld; p.f16 = f16;
         p.w = wts; p.bias = bias;
         p.wf = h16 ? nullptr : h->d_blob + l.w2_off;
         p.out = dst; p.out_ld = l.dst.ld;
@@ -553,14 +577,14 @@ static bool heads_pair_fusable(lwp_context* h, size_t i, int64_t M) {
     if (a.kind != L_GEMM || b.kind != L_GEMM || a.ks != 1 || b.ks != 1 || a.act != ACT_RELU || b.act != ACT_NONE) return false;
     if (a.res.buf >= 0 || b.res.buf >= 0 || a.out_index >= 0) return false;
     if (b.src.buf != a.dst.buf || b.src.coff != a.dst.coff || b.cin_pad != a.cout_pad || a.cout != a.cout_pad) return false;
-    return h->dtype == LWP_BF16 ? heads_bf16_supported(a.cin_pad, a.cout_pad, b.cout_pad) : heads_f32_supported(a.cin_pad, a.cout_pad, b.cout_pad, M, &h->tune);
+    return h->dtype != LWP_F32 ? heads_bf16_supported(a.cin_pad, a.cout_pad, b.cout_pad) : heads_f32_supported(a.cin_pad, a.cout_pad, b.cout_pad, M, &h->tune);
 }
 
 static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, int N, int H, int W, float* const* d_outs_nchw) {
     int dh, dw;
     level_dims(H, W, h->g.bufs[b.dst.buf].level, &dh, &dw);
     HeadsParams p;
-    p.in = buf_at(h, a.src); p.in_ld = a.src.ld;
+    p.in = buf_at(h, a.src); p.in_ld = a.src.ld; p.f16 = h->dtype == LWP_F16;
     p.w0 = h->d_blob + a.w_off; p.b0 = h->d_blob + a.b_off;
     p.w1 = h->d_blob + b.w_off; p.b1 = h->d_blob + b.b_off;
     p.out = buf_at(h, b.dst); p.out_ld = b.dst.ld;
@@ -571,7 +595,7 @@ static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, in
     char* vb = h->record_variants ? h->variant_buf : nullptr;
     if (vb) vb[0] = 0;
     p.tune = &h->tune; p.variant = vb;
-    LAUNCH(h, KC_PW, h->dtype == LWP_BF16 ? launch_heads_bf16(p, h->stream) : launch_heads_f32(p, h->stream));
+    LAUNCH(h, KC_PW, h->dtype != LWP_F32 ? launch_heads_bf16(p, h->stream) : launch_heads_f32(p, h->stream));
     if (vb && h->cur_layer >= 0 && h->cur_layer + 1 < (int)h->variants.size()) { h->variants[h->cur_layer] = vb; h->variants[h->cur_layer + 1] = vb; }
     return LWP_OK;
 }
@@ -591,10 +615,10 @@ static int enqueue_forward(lwp_context* h, const float* d_in, int N, int H, int 
             ++i;
             continue;
         }
-        // bf16: a dense 3x3 whose output feeds ONLY the next layer, a 1x1 128 -> 128 (refinement block b's last conv and block b+1's
+        // bf16 / fp16: a dense 3x3 whose output feeds ONLY the next layer, a 1x1 128 -> 128 (refinement block b's last conv and block b+1's
         // `initial`, with_mobilenet.py:57-60), hands that layer to its own epilogue when the window-resident kernel runs
         const Layer* fold = nullptr;
-        if (h->dtype == LWP_BF16 && (int)i + 1 < max_layers && i + 1 < ls.size()) {
+        if (h->dtype != LWP_F32 && (int)i + 1 < max_layers && i + 1 < ls.size()) {
             const Layer& a = ls[i];
             const Layer& b = ls[i + 1];
             const bool later_reader = [&]() {
@@ -1166,11 +1190,11 @@ static int enqueue_poses_chunk(lwp_context* h, const float* d_in, int N, int H, 
     level_dims(H, W, 3, &fh, &fw);
     const int cc = g.cat_channels;
     MapView heat, paf;
-    // bf16: the concat buffer is bf16, so the last stage's heads ALSO write f32 NCHW maps for the post-processing.  f32: the maps
+    // bf16 / fp16: the concat buffer is 16-bit, so the last stage's heads ALSO write f32 NCHW maps for the post-processing.  f32: the maps
     // could be read in place from the (NHWC) concat buffer, but the 4 x 4 footprint of a cubic sample is 4 cache lines in a
     // channel plane and 16 in channels-last rows: pair scoring at batch 32 runs 255 us on the concat buffer and ~80 on planes
     // (LWP_POST_NCHW=0: the in-place form, A/B)
-    if (h->dtype == LWP_BF16 || (with_post && h->tune.post_nchw != 0)) {
+    if (h->dtype != LWP_F32 || (with_post && h->tune.post_nchw != 0)) {
         const int nout = 2 * (1 + g.nref);
         std::vector<float*> outs(nout, nullptr);
         const size_t hb = (size_t)N * g.NH * fh * fw * sizeof(float), pb = (size_t)N * g.NP * fh * fw * sizeof(float);
@@ -1419,7 +1443,7 @@ extern "C" int lwp_debug_layer_output(lwp_handle h, const float* in, int N, int 
     rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, n * sizeof(float));
     if (rc) return rc;
     // NHWC window (ld, coff) -> compact NCHW
-    if (h->dtype == LWP_BF16) HIP_TRY(h, launch_nchw_from_nhwc_bf16(buf_at(h, l.dst), l.dst.ld, h->d_tmp, N, dh * dw, l.cout, h->stream));
+    if (h->dtype != LWP_F32) HIP_TRY(h, launch_nchw_from_nhwc_bf16(buf_at(h, l.dst), l.dst.ld, h->d_tmp, N, dh * dw, l.cout, h->stream, h->dtype == LWP_F16));
     else HIP_TRY(h, launch_nchw_from_nhwc(buf_at(h, l.dst), l.dst.ld, h->d_tmp, N, dh * dw, l.cout, h->stream));
     HIP_TRY(h, hipMemcpyAsync(dst, h->d_tmp, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1442,6 +1466,12 @@ extern "C" int lwp_debug_post_counts(lwp_handle h, int frame, int* peaks18, int*
     HIP_TRY(h, hipMemcpy(kpts18, h->ws.kpt_count + frame * 18, 18 * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(candidates19, h->ws.seen + frame * 37 + 18, 19 * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(picked19, h->ws.sel_count + frame * 19, 19 * sizeof(int), hipMemcpyDeviceToHost));
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_f32_to_f16(const float* src, uint16_t* dst, int64_t n) {
+    if ((!src || !dst) && n > 0) return fail(nullptr, LWP_ERR_ARG, "null argument");
+    for (int64_t i = 0; i < n; ++i) dst[i] = f32_to_f16_rne(src[i]);
     return LWP_OK;
 }
 

@@ -69,9 +69,12 @@ struct Graph {
     size_t blob_floats = 0;
     int cat_buf = -1;          // the [feat | heat | paf | pad] buffer
     int cat_channels = 0;
-    int dtype = LWP_F32;       // storage / MFMA dtype of the conv stack (weights packed accordingly)
+    int dtype = LWP_F32;       // storage / MFMA dtype of the conv stack (weights packed accordingly): LWP_F32, LWP_BF16, LWP_F16
 };
 Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bool merge_heads = true);
+// f32 -> IEEE binary16 / bfloat16 bits, round to nearest even (fp16: subnormals exact, overflow -> inf, NaN stays NaN)
+uint16_t f32_to_f16_rne(float f);
+uint16_t f32_to_bf16_rne(float f);
 
 struct HostTensor {
     const void* ptr;
@@ -79,6 +82,7 @@ struct HostTensor {
     int ndim;
 };
 // folds BN, packs into `blob` (size g.blob_floats); returns "" or an error message
+// (LWP_F16: also when a folded weight is beyond the fp16 range, |w| > 65504 — it would be stored as inf)
 std::string pack_weights(const Graph& g, const std::vector<std::string>& names,
                          const std::vector<HostTensor>& tensors, std::vector<float>& blob);
 
@@ -126,6 +130,7 @@ struct StemParams {       // (__restrict__: the weights stay scalar loads althou
     const float* __restrict__ bias;   // [32]
     float* __restrict__ out;          // N x Ho x Wo x 32
     int N, H, W, Ho, Wo;
+    int f16 = 0;                    // 16-bit path: output element type fp16 (else bf16); sits in the padding before `zeros`
     const float* zeros = nullptr;   // >= 16 bytes of zeros (source of out-of-image quads)
     const Tuning* tune = nullptr; char* variant = nullptr;
 };
@@ -139,6 +144,8 @@ struct DwParams {
 };
 struct GemmParams {
     const float* in; int in_ld;      // window start already applied to the pointer
+    int f16 = 0;                     // 16-bit path: element type fp16 (else bf16).  Here, and in the other structs, the field fills
+                                     // padding in front of the next pointer: the kernels' argument layout is that of the bf16 path
     const float* w;                  // [taps][cout_pad][cin_pad]
     const float* wf = nullptr;       // fp32 only: the same weights in fragment order [tap][k-step][32-ch tile][4][64][4]
     const float* bias;               // [cout_pad]
@@ -159,6 +166,7 @@ struct GemmParams {
 };
 struct DwPwParams {
     const float* in; int in_ld;          // depthwise input, NHWC
+    int f16 = 0;                         // 16-bit path: element type fp16 (else bf16)
     const float* dw_w;                   // [9][C] followed by [C] bias (contiguous)
     const float* pw_w;                   // fragment-packed pointwise weights [C/32][cout/32][4][64][4]
     const float* pw_b;                   // [cout]
@@ -174,14 +182,17 @@ hipError_t launch_dwpw(const DwPwParams& p, hipStream_t s);
 // LDS-tiled form of the front blocks at large batch (net_kernels_tiled.hip); *used = false: not applicable, the caller goes on
 hipError_t try_dwpw_tiled_f32(const DwPwParams& p, hipStream_t s, bool* used);
 hipError_t try_dwpw_tiled_bf16(const DwPwParams& p, hipStream_t s, bool* used);
-// bf16 storage path (net_kernels_bf16.hip): same parameter structs, activation / packed-weight pointers are bf16
+// 16-bit storage path (net_kernels_bf16.hip): same parameter structs, activation / packed-weight pointers are bf16, or fp16
+// when the struct's `f16` is set (LWP_F16: every launcher below and the LDS-tiled fused blocks instantiate their kernels for
+// either type)
 hipError_t launch_stem_bf16(const StemParams& p, hipStream_t s);
 hipError_t launch_dwpw_bf16(const DwPwParams& p, hipStream_t s);
 hipError_t launch_gemm_bf16(const GemmParams& p, hipStream_t s);
 // a stage's head pair (with_mobilenet.py:32-45, 1x1 C -> hidden, ReLU, 1x1 hidden -> NH + NP) as ONE kernel: the hidden tensor
 // (247 MB at batch 32 for the initial stage) never leaves the CU.  Weights in the plain [cout_pad][cin_pad] bf16 layout.
 struct HeadsParams {
-    const void* in; int in_ld;           // [M][128] bf16
+    const void* in; int in_ld;           // [M][128] bf16 / fp16
+    int f16 = 0;                         // element type fp16 (else bf16)
     const void* w0; const float* b0;     // [hidden][128] bf16, [hidden]
     const void* w1; const float* b1;     // [64][hidden] bf16 (rows >= cout are zero), [64]
     void* out; int out_ld;               // bf16 NHWC window (the concat buffer at the heat/PAF channels)
@@ -195,7 +206,7 @@ hipError_t launch_heads_bf16(const HeadsParams& p, hipStream_t s);
 // reduction of the partial outputs.  Pointers are f32 ([hidden][128], [64][hidden], NHWC f32 window).
 bool heads_f32_supported(int cin_pad, int hidden, int cout_pad, int64_t M, const Tuning* tune = nullptr);
 hipError_t launch_heads_f32(const HeadsParams& p, hipStream_t s);
-hipError_t launch_nchw_from_nhwc_bf16(const void* src, int src_ld, float* dst, int N, int HW, int C, hipStream_t s);
+hipError_t launch_nchw_from_nhwc_bf16(const void* src, int src_ld, float* dst, int N, int HW, int C, hipStream_t s, bool f16 = false);
 hipError_t launch_stem(const StemParams& p, hipStream_t s);
 hipError_t launch_dw(const DwParams& p, hipStream_t s);
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);

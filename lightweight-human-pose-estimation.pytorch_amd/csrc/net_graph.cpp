@@ -110,8 +110,8 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
     Builder b;
     Graph& g = b.g;
     g.nref = nref; g.C = C; g.NH = NH; g.NP = NP; g.dtype = dtype;
-    const bool h16 = dtype == LWP_BF16;
-    if (h16) fuse_dwpw = true;                    // the bf16 path has no stand-alone depthwise kernel
+    const bool h16 = dtype != LWP_F32;            // bf16 or fp16 storage: same graph, same blob layout
+    if (h16) fuse_dwpw = true;                    // the 16-bit path has no stand-alone depthwise kernel
     // level-1/2 buffers are single-use; level 3 ping-pongs two 512-channel slots and three C-channel slots
     int s1 = b.new_buf(1, 32), d1 = b.new_buf(1, 32), p1 = b.new_buf(1, 64);
     int d2 = b.new_buf(2, 64), p2 = b.new_buf(2, 128), d3 = b.new_buf(2, 128), p3 = b.new_buf(2, 128);
@@ -247,12 +247,35 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
     return g;
 }
 
-static inline uint16_t f32_to_bf16_rne(float f) {
+uint16_t f32_to_bf16_rne(float f) {
     uint32_t u;
     std::memcpy(&u, &f, 4);
     if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x0040u);   // NaN stays NaN
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
+}
+
+uint16_t f32_to_f16_rne(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    const uint32_t a = u & 0x7FFFFFFFu;
+    if (a >= 0x7F800000u) return sign | (a > 0x7F800000u ? 0x7E00u : 0x7C00u);    // NaN (quiet) / inf
+    if (a >= 0x477FF000u) return sign | 0x7C00u;                                  // >= 65520: rounds to inf
+    if (a >= 0x38800000u) {                                                       // normal: |f| >= 2^-14
+        uint32_t r = a - 0x38000000u;                                             // exponent bias 127 -> 15
+        r += 0xFFFu + ((r >> 13) & 1u);                                           // a carry moves into the exponent
+        return sign | (uint16_t)(r >> 13);
+    }
+    // subnormal: m * 2^-24 with m = |f| * 2^24 rounded to nearest even (m = 1024 is the smallest normal, same bits)
+    const int e = (int)(a >> 23);
+    if (e < 102) return sign;                                                     // |f| < 2^-25: zero
+    const uint32_t mant = (a & 0x007FFFFFu) | 0x00800000u;
+    const int shift = 126 - e;                                                    // 14 .. 24
+    uint32_t m = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (m & 1u))) ++m;
+    return sign | (uint16_t)m;
 }
 
 std::string pack_weights(const Graph& g, const std::vector<std::string>& names, const std::vector<HostTensor>& tensors,
@@ -273,6 +296,14 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names, 
     }
     auto f32 = [&](const std::string& k) { return (const float*)by_name[k]->ptr; };
     blob.assign(g.blob_floats, 0.0f);
+    // 16-bit MFMA operands: bf16 holds every finite f32; fp16 stops at 65504, and a larger folded weight is an error, never an inf
+    std::string range_err;
+    auto to16 = [&](float v, const std::string& key) -> uint16_t {
+        if (g.dtype == LWP_BF16) return f32_to_bf16_rne(v);
+        if (!(std::fabs(v) <= 65504.0f) && range_err.empty())
+            range_err = "folded weight of '" + key + "' is not finite in fp16 (|w| > 65504): use dtype fp32 or bf16";
+        return f32_to_f16_rne(v);
+    };
     auto fold = [&](const std::string& conv_key, const std::string& bn_key, bool has_bias, int co, std::vector<double>& scale,
                     std::vector<double>& shift) {   // y = conv*scale + shift
         scale.assign(co, 1.0); shift.assign(co, 0.0);
@@ -317,12 +348,12 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names, 
                     for (int ci = 0; ci < wb.cin; ++ci) {
                         const size_t idx = (size_t)(wb.out_off + o) * l.cin_pad + wb.in_off + ci;
                         const float v = ws[(size_t)o * wb.cin + ci];
-                        if (g.dtype == LWP_BF16) wh[idx] = f32_to_bf16_rne(v);
+                        if (g.dtype != LWP_F32) wh[idx] = to16(v, wb.conv_key);
                         else wp[idx] = v;
                     }
                 }
             }
-        } else {                                // OIHW -> [tap][cout_pad][cin_pad]  (f32 or bf16)
+        } else {                                // OIHW -> [tap][cout_pad][cin_pad]  (f32, bf16 or fp16)
             const int taps = l.ks * l.ks;
             uint16_t* wh = (uint16_t*)wp;
             for (int o = 0; o < co; ++o)
@@ -330,11 +361,11 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names, 
                     for (int t = 0; t < taps; ++t) {
                         const float v = (float)((double)w[((size_t)o * l.cin + ci) * taps + t] * scale[o]);
                         const size_t idx = ((size_t)t * l.cout_pad + o) * l.cin_pad + ci;
-                        if (g.dtype == LWP_BF16) wh[idx] = f32_to_bf16_rne(v);
+                        if (g.dtype != LWP_F32) wh[idx] = to16(v, l.conv_key);
                         else wp[idx] = v;
                     }
         }
-        if (l.kind == L_GEMM && g.dtype != LWP_BF16) {
+        if (l.kind == L_GEMM && g.dtype == LWP_F32) {
             // fragment order for v_mfma_f32_32x32x2_f32 as gemm_wp_kernel walks K: [tap][k-step 32][32-channel tile][s 0..3]
             // [lane 64][4]: lane (r = lane & 31, h = lane >> 5) holds W[tile*32 + r][step*32 + 8s + 4h + j], j = 0..3, so
             // one wave-wide 16-byte load is 1 KiB contiguous
@@ -361,8 +392,8 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names, 
             float* b2p = blob.data() + l.b2_off;
             for (int o = 0; o < l.cout; ++o) b2p[o] = (float)sh2[o];
             const int nw = l.cout / 32, C_ = l.cin;
-            if (g.dtype == LWP_BF16) {
-                // bf16: MFMA 16x16x32 operand order [C/32][cout/32][2 tiles][64 lanes][8]; lane (q = lane>>4, i = lane&15)
+            if (g.dtype != LWP_F32) {
+                // bf16 / fp16: MFMA 16x16x32 operand order [C/32][cout/32][2 tiles][64 lanes][8]; lane (q = lane>>4, i = lane&15)
                 // holds W[n = 32w + 8 (i >> 2) + 4 t + (i & 3)][k = 32s + 8q + j], j = 0..7
                 uint16_t* wh = (uint16_t*)w2p;
                 for (int s = 0; s < C_ / 32; ++s)
@@ -375,7 +406,7 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names, 
                                     const int i_ = lane & 15;
                                     const int k = 32 * s + 8 * (lane >> 4) + j, n = 32 * wv + 8 * (i_ >> 2) + 4 * t + (i_ & 3);
                                     wh[((((size_t)(s * nw + wv) * 2 + t) * 64 + lane) * 8) + j] =
-                                        f32_to_bf16_rne((float)((double)w2[(size_t)n * C_ + k] * sc2[n]));
+                                        to16((float)((double)w2[(size_t)n * C_ + k] * sc2[n]), l.conv2_key);
                                 }
             } else {
             for (int s = 0; s < C_ / 32; ++s)
@@ -390,7 +421,7 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names, 
             }
         }
     }
-    return "";
+    return range_err;
 }
 
 }  // namespace lwp

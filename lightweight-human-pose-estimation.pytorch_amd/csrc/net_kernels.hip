@@ -35,7 +35,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 }
 
 // ---------------------------------------------------------------------------------------- stem
-// conv 3x3 stride 2, 3 -> 32 (+folded BN, ReLU) from the NCHW float input to NHWC (f32 or bf16).
+// conv 3x3 stride 2, 3 -> 32 (+folded BN, ReLU) from the NCHW float input to NHWC (f32, bf16, or fp16 when F16).
 // One workgroup = 8 x 32 output pixels.  The (17 x 65) x 3 input region is loaded into LDS with coalesced row
 // loads (the first version gathered 27 scattered floats per thread and was bound by the texture addresser:
 // 62 % issue stalls in the PMC profile); one thread computes one pixel x all 32 channels with the weights
@@ -59,8 +59,9 @@ constexpr int ST_TX = 32;
 // WL: the 27 x 32 weights are staged in LDS and read back as broadcast vectors instead of arriving through scalar loads.  With
 // one or two waves per SIMD (batch 1: 1012 one-wave workgroups) nothing hides the 54 dependent s_load_dwordx16 round trips
 // of a pixel; with four or more (batch 32) the scalar form is the cheaper one (no extra LDS instructions).
-template <bool BF16, int ST_TY, int PY = 1, int DBG = 0, bool WL = false>
+template <bool BF16, int ST_TY, int PY = 1, int DBG = 0, bool WL = false, bool F16 = false>
 __global__ void __launch_bounds__(ST_TY * ST_TX) stem_kernel(StemParams p) {
+    typedef typename std::conditional<F16, _Float16, __bf16>::type h16;     // the 16-bit output type (BF16 true)
     constexpr int NT = ST_TY * ST_TX;
     constexpr int TROWS = ST_TY * PY;                              // output rows per tile
     constexpr int IR = 2 * TROWS + 1;                              // input rows per channel
@@ -174,9 +175,9 @@ __global__ void __launch_bounds__(ST_TY * ST_TX) stem_kernel(StemParams p) {
     for (int j = 0; j < PY; ++j) {
         __syncthreads();                                            // the tile (input, or the previous pass's output) is dead: the space is re-used
         if (BF16) {
-            __bf16* so = (__bf16*)s_out + tid * (OLD * 2);
+            h16* so = (h16*)s_out + tid * (OLD * 2);
 #pragma unroll
-            for (int o = 0; o < 32; ++o) so[o] = (__bf16)fmaxf(acc[j][o], 0.f);
+            for (int o = 0; o < 32; ++o) so[o] = (h16)fmaxf(acc[j][o], 0.f);
         } else {
             float* so = s_out + tid * OLD;
 #pragma unroll
@@ -195,7 +196,7 @@ __global__ void __launch_bounds__(ST_TY * ST_TX) stem_kernel(StemParams p) {
     }
 }
 
-template <bool BF16>
+template <bool BF16, bool F16 = false>
 static hipError_t launch_stem_t(const StemParams& p, hipStream_t s) {
     // tile height: 8 rows when that still gives every CU several workgroups, else 4 or 2 (batch 1: 253 -> 1012 workgroups)
     const Tuning& T = p.tune ? *p.tune : default_tuning();
@@ -203,24 +204,25 @@ static hipError_t launch_stem_t(const StemParams& p, hipStream_t s) {
     int ty = ((int64_t)tx * ((p.Ho + 7) / 8) * p.N >= 2048) ? 8 : (((int64_t)tx * ((p.Ho + 3) / 4) * p.N >= 2048) ? 4 : 2);
     if (T.stem_ty) ty = T.stem_ty;                            // LWP_STEM_TY
     const bool wl = T.stem_wl != 0;                           // LWP_STEM_WL "0" | "1": weights through scalar loads | LDS in the small-tile variants (A/B)
-    LWP_VARIANT(p, "stem<ty=%d,wl=%d>", ty, (ty == 4 || ty == 2) && wl ? 1 : 0);
+    if (F16) LWP_VARIANT(p, "%s<ty=%d,wl=%d>", "stem_f16", ty, (ty == 4 || ty == 2) && wl ? 1 : 0);
+    else LWP_VARIANT(p, "stem<ty=%d,wl=%d>", ty, (ty == 4 || ty == 2) && wl ? 1 : 0);
 #ifdef LWP_ABLATION
     const int d = T.stem_debug;
-#define ST_DBG(D_) if (ty == 8 && d == D_) { hipLaunchKernelGGL((stem_kernel<BF16, 8, 1, D_>), dim3(tx * ((p.Ho + 7) / 8), p.N), dim3(256), 0, s, p); return hipGetLastError(); }
+#define ST_DBG(D_) if (ty == 8 && d == D_) { hipLaunchKernelGGL((stem_kernel<BF16, 8, 1, D_, false, F16>), dim3(tx * ((p.Ho + 7) / 8), p.N), dim3(256), 0, s, p); return hipGetLastError(); }
     ST_DBG(1) ST_DBG(2) ST_DBG(4) ST_DBG(3) ST_DBG(5) ST_DBG(6) ST_DBG(7)
 #undef ST_DBG
 #endif
-    if (ty == 16) hipLaunchKernelGGL((stem_kernel<BF16, 8, 2>), dim3(tx * ((p.Ho + 15) / 16), p.N), dim3(256), 0, s, p);
-    else if (ty == 8) hipLaunchKernelGGL((stem_kernel<BF16, 8>), dim3(tx * ((p.Ho + 7) / 8), p.N), dim3(256), 0, s, p);
-    else if (ty == 4 && wl) hipLaunchKernelGGL((stem_kernel<BF16, 4, 1, 0, true>), dim3(tx * ((p.Ho + 3) / 4), p.N), dim3(128), 0, s, p);
-    else if (ty == 2 && wl) hipLaunchKernelGGL((stem_kernel<BF16, 2, 1, 0, true>), dim3(tx * ((p.Ho + 1) / 2), p.N), dim3(64), 0, s, p);
-    else if (ty == 4) hipLaunchKernelGGL((stem_kernel<BF16, 4>), dim3(tx * ((p.Ho + 3) / 4), p.N), dim3(128), 0, s, p);
-    else if (ty == 2) hipLaunchKernelGGL((stem_kernel<BF16, 2>), dim3(tx * ((p.Ho + 1) / 2), p.N), dim3(64), 0, s, p);
+    if (ty == 16) hipLaunchKernelGGL((stem_kernel<BF16, 8, 2, 0, false, F16>), dim3(tx * ((p.Ho + 15) / 16), p.N), dim3(256), 0, s, p);
+    else if (ty == 8) hipLaunchKernelGGL((stem_kernel<BF16, 8, 1, 0, false, F16>), dim3(tx * ((p.Ho + 7) / 8), p.N), dim3(256), 0, s, p);
+    else if (ty == 4 && wl) hipLaunchKernelGGL((stem_kernel<BF16, 4, 1, 0, true, F16>), dim3(tx * ((p.Ho + 3) / 4), p.N), dim3(128), 0, s, p);
+    else if (ty == 2 && wl) hipLaunchKernelGGL((stem_kernel<BF16, 2, 1, 0, true, F16>), dim3(tx * ((p.Ho + 1) / 2), p.N), dim3(64), 0, s, p);
+    else if (ty == 4) hipLaunchKernelGGL((stem_kernel<BF16, 4, 1, 0, false, F16>), dim3(tx * ((p.Ho + 3) / 4), p.N), dim3(128), 0, s, p);
+    else if (ty == 2) hipLaunchKernelGGL((stem_kernel<BF16, 2, 1, 0, false, F16>), dim3(tx * ((p.Ho + 1) / 2), p.N), dim3(64), 0, s, p);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_stem(const StemParams& p, hipStream_t s) { return launch_stem_t<false>(p, s); }
-hipError_t launch_stem_bf16(const StemParams& p, hipStream_t s) { return launch_stem_t<true>(p, s); }
+hipError_t launch_stem_bf16(const StemParams& p, hipStream_t s) { return p.f16 ? launch_stem_t<true, true>(p, s) : launch_stem_t<true>(p, s); }
 
 // ---------------------------------------------------------------------------------------- depthwise
 // one thread = PX consecutive output pixels (along x) x 4 channels; the 3 x (PX*stride + 2*dil) input

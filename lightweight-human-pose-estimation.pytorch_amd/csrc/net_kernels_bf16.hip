@@ -1,23 +1,21 @@
-// Network kernels for gfx950 (CDNA4), bf16 storage / bf16 MFMA / f32 accumulate path (BASELINE config 3).
-// Activations are NHWC bf16; biases, depthwise weights, accumulation, activations and residual adds are f32; the
+// Network kernels for gfx950 (CDNA4), 16-bit storage / 16-bit MFMA / f32 accumulate path (BASELINE config 3: bf16; and fp16).
+// Activations are NHWC bf16 or fp16; biases, depthwise weights, accumulation, activations and residual adds are f32; the
 // stage outputs handed to the post-processing / API are f32 NCHW.
+// Every kernel is a template over the element type E (__bf16 | _Float16, see h16.h); the launchers keep their bf16 names and
+// case lists and pick the instantiation from the params' `f16` field, so both types run the same set of configurations.
 //
 // MFMA orientation: the WEIGHTS are the A operand (rows = output channels) and the activations the B operand
 // (columns = pixels).  The accumulator then has the pixel on the lane and 4 consecutive channels in consecutive
-// registers, so the epilogue converts 4 values to bf16 and stores 8 bytes per lane, and NCHW f32 head outputs are
+// registers, so the epilogue converts 4 values to 16 bits and stores 8 bytes per lane, and NCHW f32 head outputs are
 // written with consecutive lanes on consecutive pixels.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
+#include "h16.h"
 #include "lwp_internal.h"
 
 namespace lwp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float act_f(float v, int act) {
     if (act == ACT_RELU) return fmaxf(v, 0.0f);
@@ -56,18 +54,20 @@ constexpr int DWPW_APAD = 16;
 // (The depthwise weights' reads — two 16-byte reads per lane, lanes 32 bytes apart — are two-way conflicted too; a split
 //  [low halves | high halves] layout removes that but needs a second run-time address per tap: +18 VGPRs, a wave of occupancy
 //  lost on the 4-wave kernels, spills on the dilation-2 one — measured slower and dropped.)
-template <int BM, int NW, int DBG = 0, int SDIL = 1, int ACT = -1>
+template <typename E, int BM, int NW, int DBG = 0, int SDIL = 1, int ACT = -1>
 __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
+    typedef typename H16<E>::x8 h16x8;
+    typedef typename H16<E>::x4 h16x4;
     // ACT >= 0: both activations known at compile time (ReLU for every conv_dw block) — with the run-time switch every output
     // vector walks a chain of scalar branches and the basic-block boundaries keep the loads from overlapping the arithmetic
     const int act_dw = ACT >= 0 ? ACT : p.act_dw, act_pw = ACT >= 0 ? ACT : p.act_pw;
     constexpr int NT = NW * 64;
     constexpr int RT = BM / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm_raw[];
-    __bf16* At = (__bf16*)dsm_raw;                   // [BM][C + DWPW_APAD]
+    E* At = (E*)dsm_raw;                             // [BM][C + DWPW_APAD]
     const int ldA = p.C + DWPW_APAD;
-    const __bf16* in = (const __bf16*)p.in;
-    const __bf16* pw = (const __bf16*)p.pw_w;
+    const E* in = (const E*)p.in;
+    const E* pw = (const E*)p.pw_w;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = blockIdx.y * NW + (tid >> 6);
@@ -87,15 +87,15 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
     // weight fragments: PF statically rotated register buffers (K loop unrolled by PF, no copies): PF-1 steps of the
     // weight stream stay in flight per wave — the bf16 MFMA phase is far too short to hide a 1-step prefetch
     constexpr int PF = 2;
-    bf16x8 bw[PF][2];
+    h16x8 bw[PF][2];
     // buffer loads: descriptor and step offset are wave-uniform (SGPRs), a lane supplies one 32-bit offset register — with a
     // 64-bit per-lane address (global_load) a request costs ~3x the issue time while the matrix pipes are busy
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)pw, 0, 0x7fffffff, 0x00020000);
-    auto load_b = [&](int step, bf16x8* dst) {
+    auto load_b = [&](int step, h16x8* dst) {
         const unsigned soff = (unsigned)(step * nwt + wave_u) * 2048u;
-        dst[0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, soff, 0));
-        dst[1] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16 + 1024, soff, 0));
+        dst[0] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, soff, 0));
+        dst[1] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16 + 1024, soff, 0));
     };
 #pragma unroll
     for (int j = 0; j < PF - 1; ++j) load_b(j < nsteps ? j : nsteps - 1, bw[j]);
@@ -118,17 +118,17 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
         const int c = (tid % cg) * 8;
         const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)((int64_t)p.N * p.Hi * p.Wi * p.in_ld * 2), 0x00020000);
         const int pix_b = p.in_ld * 2, row_b = p.Wi * pix_b;       // bytes per input pixel / input row
-        auto ldw = [&](unsigned off) { return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, 0)); };
+        auto ldw = [&](unsigned off) { return __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, 0)); };
         struct f32x8 { f32x4 lo, hi; };
         auto wtap = [&](int t) { return f32x8{*(const f32x4*)(Wd + t * p.C + c), *(const f32x4*)(Wd + t * p.C + c + 4)}; };
-        auto fma8 = [&](f32x8& a, const bf16x8& x, const f32x8& w) {
+        auto fma8 = [&](f32x8& a, const h16x8& x, const f32x8& w) {
             const f32x4 xl = {(float)x[0], (float)x[1], (float)x[2], (float)x[3]}, xh = {(float)x[4], (float)x[5], (float)x[6], (float)x[7]};
             a.lo += xl * w.lo; a.hi += xh * w.hi;
         };
         auto finish = [&](const f32x8& a, int row) {
-            const bf16x8 o = {(__bf16)act_f(a.lo.x, act_dw), (__bf16)act_f(a.lo.y, act_dw), (__bf16)act_f(a.lo.z, act_dw), (__bf16)act_f(a.lo.w, act_dw),
-                              (__bf16)act_f(a.hi.x, act_dw), (__bf16)act_f(a.hi.y, act_dw), (__bf16)act_f(a.hi.z, act_dw), (__bf16)act_f(a.hi.w, act_dw)};
-            *(bf16x8*)(At + row * ldA + c) = o;
+            const h16x8 o = {(E)act_f(a.lo.x, act_dw), (E)act_f(a.lo.y, act_dw), (E)act_f(a.lo.z, act_dw), (E)act_f(a.lo.w, act_dw),
+                              (E)act_f(a.hi.x, act_dw), (E)act_f(a.hi.y, act_dw), (E)act_f(a.hi.z, act_dw), (E)act_f(a.hi.w, act_dw)};
+            *(h16x8*)(At + row * ldA + c) = o;
         };
         // pixel coordinates are carried incrementally (32-bit; the host keeps every tensor below 2^31 bytes): one pair of
         // divisions per thread and tile instead of three 64-bit ones per pixel group (they were ~40 % of this phase's VALU work)
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
 #pragma unroll
                 for (int i = 0; i < PXG; ++i) a[i] = bias;
                 {
-                    bf16x8 win[3][NV];                  // the whole window in flight at once (18 loads at dilation 1), then the tap-vector FMAs
+                    h16x8 win[3][NV];                   // the whole window in flight at once (18 loads at dilation 1), then the tap-vector FMAs
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky) {
                         const int yy = yo + (ky - 1) * SDIL;
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
                     const bool ok = m + i < M32;
                     const int yc = yi * p.stride, xc = xi * p.stride;
                     const int base = ((im * p.Hi + yc) * p.Wi + xc) * pix_b + c * 2;
-                    bf16x8 x[9];
+                    h16x8 x[9];
 #pragma unroll
                     for (int t = 0; t < 9; ++t) {
                         const int dy = (t / 3 - 1) * p.dil, dx = (t % 3 - 1) * p.dil;
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
     f32x4 acc[RT][2];
 #pragma unroll
     for (int a = 0; a < RT; ++a) { acc[a][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[a][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    const __bf16* x_lane = At + i16 * ldA + 8 * q;
+    const E* x_lane = At + i16 * ldA + 8 * q;
     // one K step; the request for step + PF - 1 is UNCONDITIONAL (past the end: the last step again) and the ring index
     // static, so that the compiler counts the loads in flight instead of waiting for vmcnt(0)
     auto one = [&](int step, auto P_) {
@@ -217,10 +217,10 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
         __builtin_amdgcn_sched_barrier(0);           // keep the requests ahead of this step's MFMAs
 #pragma unroll
         for (int a = 0; a < RT; ++a) {
-            const bf16x8 xv = *(const bf16x8*)(x_lane + a * 16 * ldA + step * 32);
+            const h16x8 xv = *(const h16x8*)(x_lane + a * 16 * ldA + step * 32);
             if (DBG & 4) { asm volatile("" ::"v"(xv)); continue; }
-            acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[P][0], xv, acc[a][0], 0, 0, 0);
-            acc[a][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[P][1], xv, acc[a][1], 0, 0, 0);
+            acc[a][0] = H16<E>::mfma16(bw[P][0], xv, acc[a][0]);
+            acc[a][1] = H16<E>::mfma16(bw[P][1], xv, acc[a][1]);
         }
     };
     int s0 = 0;
@@ -232,13 +232,13 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
     if (s0 < nsteps) { one(s0, std::integral_constant<int, 0>{}); ++s0; }
     if (PF > 2 && s0 < nsteps) { one(s0, std::integral_constant<int, 1 % PF>{}); ++s0; }
     // epilogue
-    __bf16* out = (__bf16*)p.out;
-    const __bf16* res = (const __bf16*)p.res;
+    E* out = (E*)p.out;
+    const E* res = (const E*)p.res;
     if (DBG & 8) {
         float sum = 0.f;
 #pragma unroll
         for (int a = 0; a < RT; ++a) sum += acc[a][0][0] + acc[a][0][1] + acc[a][0][2] + acc[a][0][3] + acc[a][1][0] + acc[a][1][1] + acc[a][1][2] + acc[a][1][3];
-        if (sum == 12345.678f) out[0] = (__bf16)sum;
+        if (sum == 12345.678f) out[0] = (E)sum;
         return;
     }
     // The tile goes through LDS (the depthwise tile is dead once every wave has left the K loop) so that the write-out is
@@ -262,18 +262,18 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
             v1.x = act_f(v1.x, act_pw); v1.y = act_f(v1.y, act_pw); v1.z = act_f(v1.z, act_pw); v1.w = act_f(v1.w, act_pw);
             if (m < M) {
                 if (res) {
-                    const bf16x8 r = *(const bf16x8*)(res + m * p.res_ld + n);
+                    const h16x8 r = *(const h16x8*)(res + m * p.res_ld + n);
                     v0.x += (float)r[0]; v0.y += (float)r[1]; v0.z += (float)r[2]; v0.w += (float)r[3];
                     v1.x += (float)r[4]; v1.y += (float)r[5]; v1.z += (float)r[6]; v1.w += (float)r[7];
                 }
-                const bf16x8 o = {(__bf16)v0.x, (__bf16)v0.y, (__bf16)v0.z, (__bf16)v0.w, (__bf16)v1.x, (__bf16)v1.y, (__bf16)v1.z, (__bf16)v1.w};
-                *(bf16x8*)(out + m * p.out_ld + n) = o;
+                const h16x8 o = {(E)v0.x, (E)v0.y, (E)v0.z, (E)v0.w, (E)v1.x, (E)v1.y, (E)v1.z, (E)v1.w};
+                *(h16x8*)(out + m * p.out_ld + n) = o;
             }
         }
         return;
     }
     constexpr int OLD = WC + 8;                      // staged row stride (elements)
-    __bf16* Ot = (__bf16*)dsm_raw;                   // [BM][OLD]
+    E* Ot = (E*)dsm_raw;                             // [BM][OLD]
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -286,11 +286,11 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
             f32x4 v = acc[a][t] + bias;
             v.x = act_f(v.x, act_pw); v.y = act_f(v.y, act_pw); v.z = act_f(v.z, act_pw); v.w = act_f(v.w, act_pw);
             if (res && m < M) {                      // residual before the (single) rounding to bf16
-                const bf16x4 r = *(const bf16x4*)(res + m * p.res_ld + n);
+                const h16x4 r = *(const h16x4*)(res + m * p.res_ld + n);
                 v.x += (float)r[0]; v.y += (float)r[1]; v.z += (float)r[2]; v.w += (float)r[3];
             }
-            const bf16x4 o = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-            *(bf16x4*)(Ot + (a * 16 + i16) * OLD + nl) = o;
+            const h16x4 o = {(E)v.x, (E)v.y, (E)v.z, (E)v.w};
+            *(h16x4*)(Ot + (a * 16 + i16) * OLD + nl) = o;
         }
     }
     __syncthreads();
@@ -298,12 +298,12 @@ __global__ void __launch_bounds__(NW * 64) dwpw_bf16_kernel(DwPwParams p) {
     for (int ch = tid; ch < BM * CPR; ch += NT) {
         const int row = ch / CPR, col = (ch - row * CPR) * 8;
         const int64_t m = m0 + row;
-        if (m < M) *(bf16x8*)(out + m * p.out_ld + blockIdx.y * WC + col) = *(const bf16x8*)(Ot + row * OLD + col);
+        if (m < M) *(h16x8*)(out + m * p.out_ld + blockIdx.y * WC + col) = *(const h16x8*)(Ot + row * OLD + col);
     }
 }
 
-template <int BM, int NW, int DBG = 0, int SDIL = 1, int ACT = -1>
-static hipError_t launch_dwpw_bf16_t(const DwPwParams& p, hipStream_t s) {
+template <typename E, int BM, int NW, int DBG, int SDIL, int ACT>
+static hipError_t launch_dwpw_h16_t(const DwPwParams& p, hipStream_t s) {
     const int64_t M = (int64_t)p.N * p.Ho * p.Wo;
     size_t lds = (size_t)BM * (p.C + DWPW_APAD) * 2;
     const size_t lds_out = (size_t)BM * (NW * 32 + 8) * 2;          // the staged output tile re-uses the space
@@ -315,11 +315,15 @@ static hipError_t launch_dwpw_bf16_t(const DwPwParams& p, hipStream_t s) {
     const int nsplit = (p.cout / 32) / NW;
     static LdsAttrOnce attr;
     if (lds > 48 * 1024) {
-        hipError_t e = attr.ensure((const void*)dwpw_bf16_kernel<BM, NW, DBG, SDIL, ACT>, 160 * 1024);
+        hipError_t e = attr.ensure((const void*)dwpw_bf16_kernel<E, BM, NW, DBG, SDIL, ACT>, 160 * 1024);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((dwpw_bf16_kernel<BM, NW, DBG, SDIL, ACT>), dim3((unsigned)((M + BM - 1) / BM), nsplit), dim3(NW * 64), lds, s, p);
+    hipLaunchKernelGGL((dwpw_bf16_kernel<E, BM, NW, DBG, SDIL, ACT>), dim3((unsigned)((M + BM - 1) / BM), nsplit), dim3(NW * 64), lds, s, p);
     return hipGetLastError();
+}
+template <int BM, int NW, int DBG = 0, int SDIL = 1, int ACT = -1>
+static hipError_t launch_dwpw_bf16_t(const DwPwParams& p, hipStream_t s) {
+    return p.f16 ? launch_dwpw_h16_t<_Float16, BM, NW, DBG, SDIL, ACT>(p, s) : launch_dwpw_h16_t<__bf16, BM, NW, DBG, SDIL, ACT>(p, s);
 }
 
 // ---------------------------------------------------------------------------------------- fused depthwise -> pointwise, two half-tiles in flight
@@ -333,16 +337,17 @@ static hipError_t launch_dwpw_bf16_t(const DwPwParams& p, hipStream_t s) {
 // Epilogue without LDS: the pointwise weights are packed with a row permutation inside every 32-channel block (MFMA row 4q + r
 // of tile e <-> channel 8q + 4e + r), so a lane ends up with 8 CONSECUTIVE channels of a pixel in two accumulator tiles: one
 // 16-byte store per lane, 64 contiguous bytes per pixel and instruction.
-template <int NCT, int ACT, int SDIL>      // NCT: 16-channel column tiles per K-role wave (cout = 8 waves x 16 NCT)
+template <typename E, int NCT, int ACT, int SDIL>      // NCT: 16-channel column tiles per K-role wave (cout = 8 waves x 16 NCT)
 __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_half) {
+    typedef typename H16<E>::x8 h16x8;
     constexpr int HB = 64, RT = HB / 16, GT = 512;       // pixels per half-tile, row tiles, threads per wave group
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm_raw[];
     const int ldA = p.C + DWPW_APAD;
-    const __bf16* in = (const __bf16*)p.in;
+    const E* in = (const E*)p.in;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = wave >> 3, gw = wave & 7, gt = tid & (GT - 1);
-    __bf16* At = (__bf16*)dsm_raw + (size_t)g * HB * ldA;             // this group's tile [HB][C + 8]
+    E* At = (E*)dsm_raw + (size_t)g * HB * ldA;                       // this group's tile [HB][C + 8]
     float* Wd = (float*)(dsm_raw + (((size_t)2 * HB * ldA * 2 + 15) & ~(size_t)15));   // [10][C], shared
     for (int i = tid * 4; i < 10 * p.C; i += 1024 * 4) *(f32x4*)(Wd + i) = *(const f32x4*)(p.dw_w + i);
     const int i16 = lane & 15, q = lane >> 4;
@@ -364,12 +369,12 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
     const int c = (gt % cg) * 8;
     // K role: weights of this wave's NCT column tiles; block w32 = gw * NCT / 2 + (t >> 1) of 32 channels, tile e = t & 1
     constexpr int PF = 2;
-    bf16x8 bw[PF][NCT];
-    auto load_b = [&](int step, bf16x8* dst) {
+    h16x8 bw[PF][NCT];
+    auto load_b = [&](int step, h16x8* dst) {
 #pragma unroll
         for (int t = 0; t < NCT; ++t) {
             const unsigned soff = (unsigned)(step * nwt + gw * (NCT / 2) + (t >> 1)) * 2048u;
-            dst[t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16 + (t & 1) * 1024, soff, 0));
+            dst[t] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16 + (t & 1) * 1024, soff, 0));
         }
     };
     // run-time ablation switches (LWP_DWPWH_DEBUG, tools only; 0 in production): 1 no depthwise role, 2 no K role, 4 weights of
@@ -382,17 +387,17 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
             // ---------------- depthwise role: half-tile of round d / 2 into this group's tile
             const int h = 2 * (bid + (d >> 1) * G) + g;
             if (h < n_half && !(dbg & 1)) {
-                auto ldw = [&](unsigned off) { return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(irsrc, (dbg & 16) ? 0x80000000u : off, 0, 0)); };
+                auto ldw = [&](unsigned off) { return __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(irsrc, (dbg & 16) ? 0x80000000u : off, 0, 0)); };
                 struct f32x8 { f32x4 lo, hi; };
                 auto wtap = [&](int t) { return f32x8{*(const f32x4*)(Wd + t * p.C + c), *(const f32x4*)(Wd + t * p.C + c + 4)}; };
-                auto fma8 = [&](f32x8& a, const bf16x8& x, const f32x8& w) {
+                auto fma8 = [&](f32x8& a, const h16x8& x, const f32x8& w) {
                     const f32x4 xl = {(float)x[0], (float)x[1], (float)x[2], (float)x[3]}, xh = {(float)x[4], (float)x[5], (float)x[6], (float)x[7]};
                     a.lo += xl * w.lo; a.hi += xh * w.hi;
                 };
                 auto finish = [&](const f32x8& a, int row) {
-                    const bf16x8 o = {(__bf16)act_f(a.lo.x, ACT), (__bf16)act_f(a.lo.y, ACT), (__bf16)act_f(a.lo.z, ACT), (__bf16)act_f(a.lo.w, ACT),
-                                      (__bf16)act_f(a.hi.x, ACT), (__bf16)act_f(a.hi.y, ACT), (__bf16)act_f(a.hi.z, ACT), (__bf16)act_f(a.hi.w, ACT)};
-                    *(bf16x8*)(At + row * ldA + c) = o;
+                    const h16x8 o = {(E)act_f(a.lo.x, ACT), (E)act_f(a.lo.y, ACT), (E)act_f(a.lo.z, ACT), (E)act_f(a.lo.w, ACT),
+                                      (E)act_f(a.hi.x, ACT), (E)act_f(a.hi.y, ACT), (E)act_f(a.hi.z, ACT), (E)act_f(a.hi.w, ACT)};
+                    *(h16x8*)(At + row * ldA + c) = o;
                 };
                 constexpr int PXG = 2;
                 const int Wo = p.Wo, Ho = p.Ho;
@@ -416,7 +421,7 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
                         const f32x8 bias = wtap(9);
 #pragma unroll
                         for (int i = 0; i < PXG; ++i) a[i] = bias;
-                        bf16x8 win[3][NV];
+                        h16x8 win[3][NV];
 #pragma unroll
                         for (int ky = 0; ky < 3; ++ky) {
                             const int yy = yo + (ky - 1) * SDIL;
@@ -441,7 +446,7 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
                         for (int i = 0; i < PXG; ++i) {               // groups that cross an image row or the end of the tensor
                             const bool ok = m + i < M32;
                             const int base = ((im * p.Hi + yi) * p.Wi + xi) * pix_b + c * 2;
-                            bf16x8 x[9];
+                            h16x8 x[9];
 #pragma unroll
                             for (int t = 0; t < 9; ++t) {
                                 const int dy = (t / 3 - 1) * SDIL, dx = (t % 3 - 1) * SDIL;
@@ -471,7 +476,7 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
                 for (int a = 0; a < RT; ++a)
 #pragma unroll
                     for (int t = 0; t < NCT; ++t) acc[a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                const __bf16* x_lane = At + i16 * ldA + 8 * q;
+                const E* x_lane = At + i16 * ldA + 8 * q;
                 auto one = [&](int step, auto P_) {
                     constexpr int P = decltype(P_)::value;
                     const int nxt = step + PF - 1 < nsteps ? step + PF - 1 : nsteps - 1;
@@ -479,9 +484,9 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int a = 0; a < RT; ++a) {
-                        const bf16x8 xv = *(const bf16x8*)(x_lane + a * 16 * ldA + step * 32);
+                        const h16x8 xv = *(const h16x8*)(x_lane + a * 16 * ldA + step * 32);
 #pragma unroll
-                        for (int t = 0; t < NCT; ++t) acc[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[P][t], xv, acc[a][t], 0, 0, 0);
+                        for (int t = 0; t < NCT; ++t) acc[a][t] = H16<E>::mfma16(bw[P][t], xv, acc[a][t]);
                     }
                 };
                 int s0 = 0;
@@ -491,7 +496,7 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
                 }
                 if (s0 < nsteps) one(s0, std::integral_constant<int, 0>{});
                 // store: lane (pixel i16, q) holds channels n0 + 32 u + 8 q + 4 e + r in acc[a][2 u + e][r]
-                __bf16* out = (__bf16*)p.out;
+                E* out = (E*)p.out;
                 const int n0 = gw * 16 * NCT;
 #pragma unroll
                 for (int u = 0; u < NCT / 2; ++u) {
@@ -501,9 +506,9 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
                     for (int a = 0; a < RT; ++a) {
                         const int m = h * HB + a * 16 + i16;
                         const f32x4 v0 = acc[a][2 * u] + b0, v1 = acc[a][2 * u + 1] + b1;
-                        const bf16x8 o = {(__bf16)act_f(v0.x, ACT), (__bf16)act_f(v0.y, ACT), (__bf16)act_f(v0.z, ACT), (__bf16)act_f(v0.w, ACT),
-                                          (__bf16)act_f(v1.x, ACT), (__bf16)act_f(v1.y, ACT), (__bf16)act_f(v1.z, ACT), (__bf16)act_f(v1.w, ACT)};
-                        if (m < M32 && !(dbg & 8)) *(bf16x8*)(out + (int64_t)m * p.out_ld + n) = o;
+                        const h16x8 o = {(E)act_f(v0.x, ACT), (E)act_f(v0.y, ACT), (E)act_f(v0.z, ACT), (E)act_f(v0.w, ACT),
+                                          (E)act_f(v1.x, ACT), (E)act_f(v1.y, ACT), (E)act_f(v1.z, ACT), (E)act_f(v1.w, ACT)};
+                        if (m < M32 && !(dbg & 8)) *(h16x8*)(out + (int64_t)m * p.out_ld + n) = o;
                     }
                 }
             }
@@ -512,20 +517,24 @@ __global__ void __launch_bounds__(1024) dwpw_bf16_pp_kernel(DwPwParams p, int n_
     }
 }
 
-template <int NCT, int ACT, int SDIL>
-static hipError_t launch_dwpw_bf16_pp_t(const DwPwParams& p, hipStream_t s) {
+template <typename E, int NCT, int ACT, int SDIL>
+static hipError_t launch_dwpw_pp_h16_t(const DwPwParams& p, hipStream_t s) {
     const int64_t M = (int64_t)p.N * p.Ho * p.Wo;
     const int n_half = (int)((M + 63) / 64);
     const size_t lds = (((size_t)2 * 64 * (p.C + DWPW_APAD) * 2 + 15) & ~(size_t)15) + (size_t)10 * p.C * sizeof(float);
     static LdsAttrOnce attr;
-    hipError_t e = attr.ensure((const void*)dwpw_bf16_pp_kernel<NCT, ACT, SDIL>, 160 * 1024);
+    hipError_t e = attr.ensure((const void*)dwpw_bf16_pp_kernel<E, NCT, ACT, SDIL>, 160 * 1024);
     if (e != hipSuccess) return e;
     int grid = device_cu_count();
     const Tuning& T = p.tune ? *p.tune : default_tuning();
     if (T.dwpw_pp_grid > 0) grid = T.dwpw_pp_grid;
     if (grid > (n_half + 1) / 2) grid = (n_half + 1) / 2;
-    hipLaunchKernelGGL((dwpw_bf16_pp_kernel<NCT, ACT, SDIL>), dim3(grid), dim3(1024), lds, s, p, n_half);
+    hipLaunchKernelGGL((dwpw_bf16_pp_kernel<E, NCT, ACT, SDIL>), dim3(grid), dim3(1024), lds, s, p, n_half);
     return hipGetLastError();
+}
+template <int NCT, int ACT, int SDIL>
+static hipError_t launch_dwpw_bf16_pp_t(const DwPwParams& p, hipStream_t s) {
+    return p.f16 ? launch_dwpw_pp_h16_t<_Float16, NCT, ACT, SDIL>(p, s) : launch_dwpw_pp_h16_t<__bf16, NCT, ACT, SDIL>(p, s);
 }
 
 // two-half-tile form for the wide blocks at large M; *used = false: the caller takes the two-phase kernel
@@ -547,7 +556,8 @@ static hipError_t try_dwpw_bf16_pp(const DwPwParams& p, hipStream_t s, bool* use
     if (M >= (1ll << 31) - 128 || (int64_t)p.N * p.Hi * p.Wi * p.in_ld * 2 >= (1ll << 31)) return hipSuccess;
     if ((size_t)2 * 64 * (p.C + DWPW_APAD) * 2 + 16 + (size_t)40 * p.C > 160 * 1024) return hipSuccess;
     *used = true;
-    LWP_VARIANT(p, "dwpw_bf16_pp<%d,dil=%d>", p.cout / 128, p.dil);
+    if (p.f16) LWP_VARIANT(p, "dwpw_%s_pp<%d,dil=%d>", "f16", p.cout / 128, p.dil);
+    else LWP_VARIANT(p, "dwpw_bf16_pp<%d,dil=%d>", p.cout / 128, p.dil);
     DwPwParams q = p;
     q.debug = T.dwpwh_debug;
     if (p.cout == 512) return p.dil == 2 ? launch_dwpw_bf16_pp_t<4, ACT_RELU, 2>(q, s) : launch_dwpw_bf16_pp_t<4, ACT_RELU, 1>(q, s);
@@ -587,7 +597,8 @@ hipError_t launch_dwpw_bf16(const DwPwParams& p_in, hipStream_t s) {
     while (bm > 16 && (size_t)bm * (p.C + DWPW_APAD > p.cout + 8 ? p.C + DWPW_APAD : p.cout + 8) * 2 + (size_t)40 * p.C + 16 > 160 * 1024) bm >>= 1;
     if (bm == 128 && nw < 4) bm = 64;
     // every thread must own a whole 8-channel chunk column: NW*64 threads must be a multiple of C/8 (always true here)
-    LWP_VARIANT(p, "dwpw_bf16<%d,%d,dil=%d>", bm, nw, (nw == 16 && p.dil == 2 && p.stride == 1) ? 2 : 1);
+    if (p.f16) LWP_VARIANT(p, "dwpw_%s<%d,%d,dil=%d>", "f16", bm, nw, (nw == 16 && p.dil == 2 && p.stride == 1) ? 2 : 1);
+    else LWP_VARIANT(p, "dwpw_bf16<%d,%d,dil=%d>", bm, nw, (nw == 16 && p.dil == 2 && p.stride == 1) ? 2 : 1);
 #ifdef LWP_ABLATION
     const int d = T.dwpwh_debug;
 #define DPH_DBG(BM_, NW_, D_) if (bm == BM_ && nw == NW_ && d == D_) return launch_dwpw_bf16_t<BM_, NW_, D_>(p, s);
@@ -620,18 +631,20 @@ hipError_t launch_dwpw_bf16(const DwPwParams& p_in, hipStream_t s) {
 constexpr int HBK = 64;
 constexpr int HLD = HBK + 8;
 
-template <int BM, int BN, int RM, int RN>
+template <typename E, int BM, int BN, int RM, int RN>
 __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm_bf16_kernel(GemmParams p) {
+    typedef typename H16<E>::x8 h16x8;
+    typedef typename H16<E>::x4 h16x4;
     constexpr int WM = BM / (32 * RM), WN = BN / (32 * RN);
     constexpr int NT = WM * WN * 64;
     constexpr int A_CH = BM * 8, B_CH = BN * 8;       // 16-byte chunks per tile
     constexpr int A_PER = (A_CH + NT - 1) / NT, B_PER = (B_CH + NT - 1) / NT;
     static_assert(A_CH % NT == 0 && B_CH % NT == 0, "tile/threads mismatch");
     extern __shared__ __attribute__((aligned(16))) unsigned char hsm_raw[];
-    __bf16* As = (__bf16*)hsm_raw;                    // [2][BM][HLD]
-    __bf16* Bs = As + 2 * BM * HLD;                   // [2][BN][HLD]
-    const __bf16* in = (const __bf16*)p.in;
-    const __bf16* wgt = (const __bf16*)p.w;
+    E* As = (E*)hsm_raw;                              // [2][BM][HLD]
+    E* Bs = As + 2 * BM * HLD;                        // [2][BN][HLD]
+    const E* in = (const E*)p.in;
+    const E* wgt = (const E*)p.w;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -678,7 +691,7 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
     const int ksteps_per_tap = p.cin_pad / HBK;
     const int nsteps = p.ks * p.ks * ksteps_per_tap;
 
-    bf16x8 a_reg[A_PER], b_reg[B_PER];
+    h16x8 a_reg[A_PER], b_reg[B_PER];
     auto load_step = [&](int step) {
         const int tap = step / ksteps_per_tap;
         const int c0 = (step - tap * ksteps_per_tap) * HBK;
@@ -690,19 +703,19 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
             const int yy = a_y[i] + dy, xx = a_x[i] + dx;
             const bool ok = a_ok[i] && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
             const unsigned off = ok ? a_base[i] + (unsigned)shift : 0x80000000u;
-            a_reg[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(arsrc, off, 0, 0));
+            a_reg[i] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(arsrc, off, 0, 0));
         }
         const unsigned woff = (unsigned)__builtin_amdgcn_readfirstlane(((tap * p.cout_pad + n0) * p.cin_pad + c0) * 2);
 #pragma unroll
-        for (int i = 0; i < B_PER; ++i) b_reg[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, b_off[i], woff, 0));
+        for (int i = 0; i < B_PER; ++i) b_reg[i] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, b_off[i], woff, 0));
     };
     auto store_step = [&](int buf) {
-        __bf16* a = As + buf * BM * HLD;
-        __bf16* b = Bs + buf * BN * HLD;
+        E* a = As + buf * BM * HLD;
+        E* b = Bs + buf * BN * HLD;
 #pragma unroll
-        for (int i = 0; i < A_PER; ++i) *(bf16x8*)(a + a_lds[i]) = a_reg[i];
+        for (int i = 0; i < A_PER; ++i) *(h16x8*)(a + a_lds[i]) = a_reg[i];
 #pragma unroll
-        for (int i = 0; i < B_PER; ++i) *(bf16x8*)(b + b_lds[i]) = b_reg[i];
+        for (int i = 0; i < B_PER; ++i) *(h16x8*)(b + b_lds[i]) = b_reg[i];
     };
 
     f32x16 acc[RM][RN];
@@ -719,19 +732,19 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
     for (int step = 0; step < nsteps; ++step) {
         const int buf = step & 1;
         if (step + 1 < nsteps) load_step(step + 1);
-        const __bf16* a = As + buf * BM * HLD + (wm * 32 * RM + i32) * HLD + 8 * h;
-        const __bf16* b = Bs + buf * BN * HLD + (wn * 32 * RN + i32) * HLD + 8 * h;
+        const E* a = As + buf * BM * HLD + (wm * 32 * RM + i32) * HLD + 8 * h;
+        const E* b = Bs + buf * BN * HLD + (wn * 32 * RN + i32) * HLD + 8 * h;
 #pragma unroll
         for (int s = 0; s < HBK / 16; ++s) {
-            bf16x8 xv[RM], wv[RN];
+            h16x8 xv[RM], wv[RN];
 #pragma unroll
-            for (int i = 0; i < RM; ++i) xv[i] = *(const bf16x8*)(a + i * 32 * HLD + 16 * s);
+            for (int i = 0; i < RM; ++i) xv[i] = *(const h16x8*)(a + i * 32 * HLD + 16 * s);
 #pragma unroll
-            for (int j = 0; j < RN; ++j) wv[j] = *(const bf16x8*)(b + j * 32 * HLD + 16 * s);
+            for (int j = 0; j < RN; ++j) wv[j] = *(const h16x8*)(b + j * 32 * HLD + 16 * s);
 #pragma unroll
             for (int i = 0; i < RM; ++i)
 #pragma unroll
-                for (int j = 0; j < RN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[j], xv[i], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < RN; ++j) acc[i][j] = H16<E>::mfma32(wv[j], xv[i], acc[i][j]);
         }
         if (step + 1 < nsteps) store_step(buf ^ 1);
         __syncthreads();
@@ -742,12 +755,12 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
     // lines per store instruction (heads.0 at batch 32: 140 us for 247 MB).  The tile therefore goes through the (now free) LDS
     // tiles: bias + activation (+ residual, f32) in registers, bf16 into [BM][BN + 8], then 16 bytes per lane on consecutive
     // addresses — whole pixel rows of the workgroup's BN channels.  The NCHW stage outputs are pixel-major per channel already.
-    __bf16* out = (__bf16*)p.out;
-    const __bf16* res = (const __bf16*)p.res;
+    E* out = (E*)p.out;
+    const E* res = (const E*)p.res;
     const int64_t HW = (int64_t)p.H * p.W;
     constexpr int OLD_ = BN + 8;
     static_assert((size_t)BM * OLD_ * 2 <= (size_t)2 * (BM + BN) * HLD * 2, "the staged output tile must fit the operand tiles");
-    __bf16* Ot = (__bf16*)hsm_raw;                     // [BM][OLD_] (the last K step ended with a barrier: the tiles are free)
+    E* Ot = (E*)hsm_raw;                               // [BM][OLD_] (the last K step ended with a barrier: the tiles are free)
     const bool res_vec = res && ((p.res_ld & 3) == 0) && ((((uintptr_t)res) & 7) == 0);
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
@@ -773,7 +786,7 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
                 v.x = act_f(v.x, p.act); v.y = act_f(v.y, p.act); v.z = act_f(v.z, p.act); v.w = act_f(v.w, p.act);
                 if (res && mok) {                                     // residual before the (single) rounding to bf16
                     if (res_vec && n + 3 < p.cout) {
-                        const bf16x4 r = *(const bf16x4*)(res + m * p.res_ld + n);
+                        const h16x4 r = *(const h16x4*)(res + m * p.res_ld + n);
                         v.x += (float)r[0]; v.y += (float)r[1]; v.z += (float)r[2]; v.w += (float)r[3];
                     } else {
 #pragma unroll
@@ -784,8 +797,8 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
 #pragma unroll
                     for (int e = 0; e < 4; ++e) if (n + e < p.cout) store_nchw(n + e, v[e]);
                 }
-                const bf16x4 o = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-                *(bf16x4*)(Ot + lrow * OLD_ + lcol) = o;
+                const h16x4 o = {(E)v.x, (E)v.y, (E)v.z, (E)v.w};
+                *(h16x4*)(Ot + lrow * OLD_ + lcol) = o;
             }
         }
     }
@@ -797,8 +810,8 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
         const int64_t m = m0 + row;
         const int n = n0 + col;
         if (m >= M || n >= p.cout) continue;
-        const bf16x8 o = *(const bf16x8*)(Ot + row * OLD_ + col);
-        if (out_vec && n + 7 < p.cout) *(bf16x8*)(out + m * p.out_ld + n) = o;
+        const h16x8 o = *(const h16x8*)(Ot + row * OLD_ + col);
+        if (out_vec && n + 7 < p.cout) *(h16x8*)(out + m * p.out_ld + n) = o;
         else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) if (n + e < p.cout) out[m * p.out_ld + n + e] = o[e];
@@ -806,8 +819,8 @@ __global__ void __launch_bounds__((BM / (32 * RM)) * (BN / (32 * RN)) * 64) gemm
     }
 }
 
-template <int BM, int BN, int RM, int RN>
-static hipError_t launch_gemm_bf16_t(const GemmParams& p, hipStream_t s) {
+template <typename E, int BM, int BN, int RM, int RN>
+static hipError_t launch_gemm_h16_t(const GemmParams& p, hipStream_t s) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
     const int64_t tiles = ((M + BM - 1) / BM) * (p.cout_pad / BN);
     if (M * p.in_ld * 2 >= (1ll << 31)) return hipErrorInvalidValue;        // 32-bit buffer offsets (2 GiB of activations per launch)
@@ -815,11 +828,15 @@ static hipError_t launch_gemm_bf16_t(const GemmParams& p, hipStream_t s) {
     const size_t lds = (size_t)2 * (BM + BN) * HLD * 2;
     static LdsAttrOnce attr;
     if (lds > 48 * 1024) {
-        hipError_t e = attr.ensure((const void*)gemm_bf16_kernel<BM, BN, RM, RN>, (int)lds);
+        hipError_t e = attr.ensure((const void*)gemm_bf16_kernel<E, BM, BN, RM, RN>, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, RM, RN>), dim3((unsigned)tiles), dim3(NT), lds, s, p);
+    hipLaunchKernelGGL((gemm_bf16_kernel<E, BM, BN, RM, RN>), dim3((unsigned)tiles), dim3(NT), lds, s, p);
     return hipGetLastError();
+}
+template <int BM, int BN, int RM, int RN>
+static hipError_t launch_gemm_bf16_t(const GemmParams& p, hipStream_t s) {
+    return p.f16 ? launch_gemm_h16_t<_Float16, BM, BN, RM, RN>(p, s) : launch_gemm_h16_t<__bf16, BM, BN, RM, RN>(p, s);
 }
 
 // Measured and dropped: the heads kernel's structure for the single 1x1 convs to 128 channels (cpm.align, refinement `initial`):
@@ -841,12 +858,14 @@ static hipError_t launch_gemm_bf16_t(const GemmParams& p, hipStream_t s) {
 constexpr int HD_CH = 64, HD_K = 128;
 constexpr int HD_W0LD = HD_K + 8, HD_W1LD = HD_CH + 8;
 
-template <int RM>
+template <typename E, int RM>
 __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
+    typedef typename H16<E>::x8 h16x8;
+    typedef typename H16<E>::x4 h16x4;
     constexpr int HD_BM = 128 * RM;                                  // wave = 32 RM pixels: every weight fragment read from LDS feeds RM MFMAs
     extern __shared__ __attribute__((aligned(16))) unsigned char hd_raw[];
-    __bf16* W0s = (__bf16*)hd_raw;                                   // [2][64][HD_W0LD]
-    __bf16* W1s = W0s + 2 * HD_CH * HD_W0LD;                         // [2][64][HD_W1LD]
+    E* W0s = (E*)hd_raw;                                             // [2][64][HD_W0LD]
+    E* W1s = W0s + 2 * HD_CH * HD_W0LD;                              // [2][64][HD_W1LD]
     float* B0s = (float*)(W1s + 2 * 64 * HD_W1LD);                   // [hidden]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i32 = lane & 31, h = lane >> 5;
@@ -867,39 +886,39 @@ __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
     const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, 64 * p.hidden * 2, 0x00020000);
 
     // weight staging: W0 chunk = 64 rows x 256 B (4 x 16 B per thread), W1 chunk = 64 rows x 128 B (2 x 16 B per thread)
-    bf16x8 st0[4], st1[2];
+    h16x8 st0[4], st1[2];
     auto request = [&](int c) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int ch = tid + u * 256, row = ch >> 4, col = (ch & 15) * 8;
-            st0[u] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w0r, (row * HD_K + col) * 2, c * (HD_CH * HD_K * 2), 0));
+            st0[u] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(w0r, (row * HD_K + col) * 2, c * (HD_CH * HD_K * 2), 0));
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int ch = tid + u * 256, row = ch >> 3, col = (ch & 7) * 8;
-            st1[u] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w1r, (row * p.hidden + col) * 2, c * (HD_CH * 2), 0));
+            st1[u] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(w1r, (row * p.hidden + col) * 2, c * (HD_CH * 2), 0));
         }
     };
     auto land = [&](int buf) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int ch = tid + u * 256, row = ch >> 4, col = (ch & 15) * 8;
-            *(bf16x8*)(W0s + (buf * HD_CH + row) * HD_W0LD + col) = st0[u];
+            *(h16x8*)(W0s + (buf * HD_CH + row) * HD_W0LD + col) = st0[u];
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int ch = tid + u * 256, row = ch >> 3, col = (ch & 7) * 8;
-            *(bf16x8*)(W1s + (buf * 64 + row) * HD_W1LD + col) = st1[u];
+            *(h16x8*)(W1s + (buf * 64 + row) * HD_W1LD + col) = st1[u];
         }
     };
     request(0);
     // the wave's activations: k-slice s of pixel m = x[m][16 s + 8 h .. + 7]
-    bf16x8 xf[RM][HD_K / 16];
+    h16x8 xf[RM][HD_K / 16];
 #pragma unroll
     for (int i = 0; i < RM; ++i)
 #pragma unroll
         for (int s = 0; s < HD_K / 16; ++s)
-            xf[i][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xr, mok[i] ? (unsigned)((mr[i] * p.in_ld + 16 * s + 8 * h) * 2) : 0x80000000u, 0, 0));
+            xf[i][s] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(xr, mok[i] ? (unsigned)((mr[i] * p.in_ld + 16 * s + 8 * h) * 2) : 0x80000000u, 0, 0));
     for (int i = tid * 4; i < p.hidden; i += 256 * 4) *(f32x4*)(B0s + i) = *(const f32x4*)(p.b0 + i);
     land(0);
     __syncthreads();
@@ -915,9 +934,9 @@ __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
         const int buf = c & 1;
         request(c + 1 < nch ? c + 1 : c);                            // unconditional (the last chunk again): exact vmcnt counting
         __builtin_amdgcn_sched_barrier(0);                           // keep the requests ahead of the chunk's MFMAs
-        const __bf16* w0 = W0s + (buf * HD_CH + i32) * HD_W0LD + 8 * h;
-        const __bf16* w1 = W1s + (buf * 64 + i32) * HD_W1LD + 4 * h;
-        bf16x8 hf[RM][2][2];
+        const E* w0 = W0s + (buf * HD_CH + i32) * HD_W0LD + 8 * h;
+        const E* w1 = W1s + (buf * 64 + i32) * HD_W1LD + 4 * h;
+        h16x8 hf[RM][2][2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             f32x16 acc1[RM];
@@ -925,33 +944,33 @@ __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
             for (int i = 0; i < RM; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc1[i][e] = 0.f;
-            bf16x8 wv[HD_K / 16];                                    // all eight fragment reads in flight before the first MFMA
+            h16x8 wv[HD_K / 16];                                     // all eight fragment reads in flight before the first MFMA
 #pragma unroll
-            for (int s = 0; s < HD_K / 16; ++s) wv[s] = *(const bf16x8*)(w0 + j * 32 * HD_W0LD + 16 * s);
+            for (int s = 0; s < HD_K / 16; ++s) wv[s] = *(const h16x8*)(w0 + j * 32 * HD_W0LD + 16 * s);
             __builtin_amdgcn_sched_barrier(0);                       // (the scheduler otherwise pairs every read with its MFMA again)
 #pragma unroll
             for (int s = 0; s < HD_K / 16; ++s)
 #pragma unroll
-                for (int i = 0; i < RM; ++i) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[s], xf[i][s], acc1[i], 0, 0, 0);
+                for (int i = 0; i < RM; ++i) acc1[i] = H16<E>::mfma32(wv[s], xf[i][s], acc1[i]);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 b = *(const f32x4*)(B0s + c * HD_CH + j * 32 + 8 * g + 4 * h);
 #pragma unroll
                 for (int i = 0; i < RM; ++i)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) hf[i][j][g >> 1][(g & 1) * 4 + r] = (__bf16)fmaxf(acc1[i][4 * g + r] + b[r], 0.f);
+                    for (int r = 0; r < 4; ++r) hf[i][j][g >> 1][(g & 1) * 4 + r] = (E)fmaxf(acc1[i][4 * g + r] + b[r], 0.f);
             }
         }
-        bf16x8 w1v[2][2][2];                                         // the eight W1 fragments (hidden index permuted: see above)
+        h16x8 w1v[2][2][2];                                          // the eight W1 fragments (hidden index permuted: see above)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const __bf16* src = w1 + t * 32 * HD_W1LD + j * 32 + 16 * s;
-                    const bf16x4 lo = *(const bf16x4*)src, hi = *(const bf16x4*)(src + 8);
-                    w1v[t][j][s] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    const E* src = w1 + t * 32 * HD_W1LD + j * 32 + 16 * s;
+                    const h16x4 lo = *(const h16x4*)src, hi = *(const h16x4*)(src + 8);
+                    w1v[t][j][s] = h16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -961,13 +980,13 @@ __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
-                    for (int i = 0; i < RM; ++i) acc2[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1v[t][j][s], hf[i][j][s], acc2[i][t], 0, 0, 0);
+                    for (int i = 0; i < RM; ++i) acc2[i][t] = H16<E>::mfma32(w1v[t][j][s], hf[i][j][s], acc2[i][t]);
         if (c + 1 < nch) land(buf ^ 1);
         __syncthreads();
     }
 
     // epilogue: lane (pixel i32, half h) holds output channels 32 t + 8 g + 4 h + r
-    __bf16* out = (__bf16*)p.out;
+    E* out = (E*)p.out;
     const int HW = p.H * p.W;
     const int c0 = p.out_split > 0 ? p.out_split : p.cout;
     const bool out_vec = ((p.out_ld & 3) == 0) && ((((uintptr_t)out) & 7) == 0);
@@ -985,11 +1004,11 @@ __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
                 const f32x4 b = *(const f32x4*)(p.b1 + n);
                 const f32x4 v = {acc2[i][t][4 * g] + b[0], acc2[i][t][4 * g + 1] + b[1], acc2[i][t][4 * g + 2] + b[2], acc2[i][t][4 * g + 3] + b[3]};
                 if (out_vec && n + 3 < p.cout) {                 // 4 consecutive channels: one 8-byte store
-                    const bf16x4 o = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    *(bf16x4*)(out + (int64_t)m * p.out_ld + n) = o;
+                    const h16x4 o = {(E)v[0], (E)v[1], (E)v[2], (E)v[3]};
+                    *(h16x4*)(out + (int64_t)m * p.out_ld + n) = o;
                 } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) if (n + r < p.cout) out[(int64_t)m * p.out_ld + n + r] = (__bf16)v[r];
+                    for (int r = 0; r < 4; ++r) if (n + r < p.cout) out[(int64_t)m * p.out_ld + n + r] = (E)v[r];
                 }
                 if (p.out_nchw || p.out_nchw2) {
 #pragma unroll
@@ -1008,26 +1027,31 @@ bool heads_bf16_supported(int cin_pad, int hidden, int cout_pad) {
     return cin_pad == HD_K && hidden % HD_CH == 0 && hidden >= HD_CH && hidden <= 4096 && cout_pad == 64;
 }
 
-template <int RM>
-static hipError_t launch_heads_bf16_t(const HeadsParams& p, hipStream_t s) {
+template <typename E, int RM>
+static hipError_t launch_heads_h16_t(const HeadsParams& p, hipStream_t s) {
     constexpr int BM = 128 * RM;
     const int64_t M = (int64_t)p.N * p.H * p.W;
     if (M >= (1ll << 31) - BM || M * p.in_ld * 2 >= (1ll << 31) || (p.in_ld & 7)) return hipErrorInvalidValue;
     const size_t lds = (size_t)(2 * HD_CH * HD_W0LD + 2 * 64 * HD_W1LD) * 2 + (size_t)p.hidden * sizeof(float);
     static LdsAttrOnce attr;
     if (lds > 48 * 1024) {
-        hipError_t e = attr.ensure((const void*)heads_bf16_kernel<RM>, 96 * 1024);
+        hipError_t e = attr.ensure((const void*)heads_bf16_kernel<E, RM>, 96 * 1024);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(heads_bf16_kernel<RM>, dim3((unsigned)((M + BM - 1) / BM)), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((heads_bf16_kernel<E, RM>), dim3((unsigned)((M + BM - 1) / BM)), dim3(256), lds, s, p);
     return hipGetLastError();
+}
+template <int RM>
+static hipError_t launch_heads_bf16_t(const HeadsParams& p, hipStream_t s) {
+    return p.f16 ? launch_heads_h16_t<_Float16, RM>(p, s) : launch_heads_h16_t<__bf16, RM>(p, s);
 }
 hipError_t launch_heads_bf16(const HeadsParams& p, hipStream_t s) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
     const Tuning& T = p.tune ? *p.tune : default_tuning();
     const int rm = T.heads_rm ? T.heads_rm : 1;               // LWP_HEADS_RM (experiments): 64 rows per wave (198 VGPRs, 2 waves per SIMD) measured 12-23 % slower
     (void)M;
-    LWP_VARIANT(p, "heads_bf16<%d>", rm == 2 ? 2 : 1);
+    if (p.f16) LWP_VARIANT(p, "heads_%s<%d>", "f16", rm == 2 ? 2 : 1);
+    else LWP_VARIANT(p, "heads_bf16<%d>", rm == 2 ? 2 : 1);
     return rm == 2 ? launch_heads_bf16_t<2>(p, s) : launch_heads_bf16_t<1>(p, s);
 }
 
@@ -1049,8 +1073,9 @@ hipError_t launch_heads_bf16(const HeadsParams& p, hipStream_t s) {
 // 256-byte pixel rows (residual added from equally coalesced loads, rounded to bf16 once).
 // DBG (compile time, 0 in production; LWP_GEMMH_DEBUG selects an ablation build of the 256-row configuration):
 // 1 no epilogue, 2 no MFMA, 4 no window staging, 8 no weight stream, 16 no K loop
-template <int BM, int WM, int WN, int KSZ, int BD, int WCH, int DBG = 0, bool F2 = false>     // WCH: 16-byte window chunks per thread and channel block; F2: fused second conv
+template <typename E, int BM, int WM, int WN, int KSZ, int BD, int WCH, int DBG = 0, bool F2 = false>     // WCH: 16-byte window chunks per thread and channel block; F2: fused second conv
 __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p) {
+    typedef typename H16<E>::x8 h16x8;
     constexpr int NT = WM * WN * 64;
     constexpr int BN = 128, CIN = 128;
     constexpr int RM = BM / WM / 32, RN = BN / WN / 32;
@@ -1064,11 +1089,11 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
     extern __shared__ __attribute__((aligned(16))) unsigned char arm_raw[];
     const int halo = KSZ == 3 ? p.dil * (p.W + 1) : 0;
     const int R = BM + 2 * halo;                       // window rows
-    __bf16* Aw = (__bf16*)arm_raw;                     // [R + 1][CS]  (last row: zeros)
-    __bf16* zrow = Aw + (size_t)R * CS;
-    __bf16* Bs = zrow + CS;                            // [3][BN][HLD]: step k reads buffer k % 3 while step k + 2's tile is written
-    const __bf16* in = (const __bf16*)p.in;
-    const __bf16* wgt = (const __bf16*)p.w;
+    E* Aw = (E*)arm_raw;                               // [R + 1][CS]  (last row: zeros)
+    E* zrow = Aw + (size_t)R * CS;
+    E* Bs = zrow + CS;                                 // [3][BN][HLD]: step k reads buffer k % 3 while step k + 2's tile is written
+    const E* in = (const E*)p.in;
+    const E* wgt = (const E*)p.w;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1094,27 +1119,27 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
         b_off[i] = row * CIN + col;
         b_lds[i] = row * HLD + col;
     }
-    bf16x8 b_reg[BD][B_PER];
+    h16x8 b_reg[BD][B_PER];
     int n0 = 0;                                        // first output channel of the tile whose weights are being streamed
     // buffer loads: wave-uniform descriptor and tile/tap offset in SGPRs, one 32-bit offset register per lane (a 64-bit per-lane
     // address costs ~3x the issue time while the matrix pipes are busy)
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wgt, 0, 0x7fffffff, 0x00020000);
-    auto load_b = [&](int step, bf16x8* dst) {
+    auto load_b = [&](int step, h16x8* dst) {
         const int kb = step / taps, tap = step - kb * taps;
         const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(((tap * p.cout_pad + n0) * CIN + kb * HBK) * 2);
 #pragma unroll
-        for (int i = 0; i < B_PER; ++i) dst[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, b_off[i] * 2, soff, 0));
+        for (int i = 0; i < B_PER; ++i) dst[i] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, b_off[i] * 2, soff, 0));
     };
-    auto store_b = [&](int buf, const bf16x8* src) {
-        __bf16* b = Bs + buf * BN * HLD;
+    auto store_b = [&](int buf, const h16x8* src) {
+        E* b = Bs + buf * BN * HLD;
 #pragma unroll
-        for (int i = 0; i < B_PER; ++i) *(bf16x8*)(b + b_lds[i]) = src[i];
+        for (int i = 0; i < B_PER; ++i) *(h16x8*)(b + b_lds[i]) = src[i];
     };
 
     // ---- pixel window: row r <-> flat pixel m0 - halo + r.  Channel block 0 goes to LDS at the start of the tile; block 1 is
     // loaded behind it into registers (WCH 16-byte chunks per thread) and replaces block 0 in LDS after the ninth tap.
     const int wtotal = R * 8;                                    // chunks of one 64-channel block (<= WCH * NT: host check)
-    bf16x8 wreg[WCH];
+    h16x8 wreg[WCH];
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)((int64_t)M * p.in_ld * 2), 0x00020000);   // host: < 2^31 bytes
     auto win_load = [&](int m0_, int kb) {
 #pragma unroll
@@ -1123,14 +1148,14 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
             const int row = ch >> 3, col = (ch & 7) * 8 + kb * HBK;
             const int g = m0_ - halo + row;
             // buffer load: rows outside the tensor read offset 2^31 >= num_records and come back as zeros
-            wreg[u] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(irsrc, (ch < wtotal && g >= 0 && g < M) ? (unsigned)((g * p.in_ld + col) * 2) : 0x80000000u, 0, 0));
+            wreg[u] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(irsrc, (ch < wtotal && g >= 0 && g < M) ? (unsigned)((g * p.in_ld + col) * 2) : 0x80000000u, 0, 0));
         }
     };
     auto win_write = [&]() {
 #pragma unroll
         for (int u = 0; u < WCH; ++u) {
             const int ch = tid + u * NT;
-            if (ch < wtotal) *(bf16x8*)(Aw + (size_t)(ch >> 3) * CS + (ch & 7) * 8) = wreg[u];
+            if (ch < wtotal) *(h16x8*)(Aw + (size_t)(ch >> 3) * CS + (ch & 7) * 8) = wreg[u];
         }
     };
     // everything of the NEXT tile that can be requested early: its weights (ring) and block 0 of its window (registers)
@@ -1160,7 +1185,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
             win_write();
             win_load(m0, 1);                               // in flight during the first nine steps
         }
-        for (int c = tid * 8; c < CS; c += NT * 8) *(bf16x8*)(zrow + c) = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int c = tid * 8; c < CS; c += NT * 8) *(h16x8*)(zrow + c) = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
         if (!(DBG & 8)) {
             store_b(0, b_reg[0]);
             store_b(1, b_reg[1]);
@@ -1202,15 +1227,15 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
         // fragment registers, double-buffered over the 16-deep sub-steps
-        bf16x8 xa[2][RM], wb[2][RN];
+        h16x8 xa[2][RM], wb[2][RN];
         int ao[RM];
 #pragma unroll
         for (int i = 0; i < RM; ++i) ao[i] = a_off(0, i);
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < RM; ++i) xa[0][i] = *(const bf16x8*)(Aw + ao[i]);
+        for (int i = 0; i < RM; ++i) xa[0][i] = *(const h16x8*)(Aw + ao[i]);
 #pragma unroll
-        for (int j = 0; j < RN; ++j) wb[0][j] = *(const bf16x8*)(Bs + b_lane + j * 32 * HLD);
+        for (int j = 0; j < RN; ++j) wb[0][j] = *(const h16x8*)(Bs + b_lane + j * 32 * HLD);
 
         // one K step; JB (compile time) = position in the register ring, RESTAGE = the last step on channel block 0.
         // No data-dependent branch inside: look-ahead indices are clamped (the last steps reload / restore harmlessly), so the
@@ -1224,8 +1249,8 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
             // activation ones — are read ahead of the barrier and the MFMAs restart right behind it (with two buffers every step
             // began with an exposed LDS round trip: ~20 % of the loop).
             if (!(DBG & 8)) load_b(step + 4 < nsteps ? step + 4 : nsteps - 1, b_reg[(jb + 1) % 3]);
-            const __bf16* b = Bs + jb * BN * HLD + b_lane;
-            const __bf16* bnext = Bs + ((jb + 1) % 3) * BN * HLD + b_lane;
+            const E* b = Bs + jb * BN * HLD + b_lane;
+            const E* bnext = Bs + ((jb + 1) % 3) * BN * HLD + b_lane;
             int an[RM];                                          // next step's activation offsets
 #pragma unroll
             for (int i = 0; i < RM; ++i) an[i] = a_off(step + 1 < nsteps ? step + 1 : step, i);
@@ -1234,15 +1259,15 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                 const int c = s & 1, n = c ^ 1;
                 if (s + 1 < HBK / 16) {
 #pragma unroll
-                    for (int i = 0; i < RM; ++i) xa[n][i] = *(const bf16x8*)(Aw + ao[i] + 16 * (s + 1));
+                    for (int i = 0; i < RM; ++i) xa[n][i] = *(const h16x8*)(Aw + ao[i] + 16 * (s + 1));
 #pragma unroll
-                    for (int j = 0; j < RN; ++j) wb[n][j] = *(const bf16x8*)(b + j * 32 * HLD + 16 * (s + 1));
+                    for (int j = 0; j < RN; ++j) wb[n][j] = *(const h16x8*)(b + j * 32 * HLD + 16 * (s + 1));
                 } else {
 #pragma unroll
-                    for (int j = 0; j < RN; ++j) wb[n][j] = *(const bf16x8*)(bnext + j * 32 * HLD);   // next step, sub-step 0: before the barrier
+                    for (int j = 0; j < RN; ++j) wb[n][j] = *(const h16x8*)(bnext + j * 32 * HLD);    // next step, sub-step 0: before the barrier
                     if (!restage) {
 #pragma unroll
-                        for (int i = 0; i < RM; ++i) xa[n][i] = *(const bf16x8*)(Aw + an[i]);
+                        for (int i = 0; i < RM; ++i) xa[n][i] = *(const h16x8*)(Aw + an[i]);
                     }
                 }
                 if (DBG & 2) {
@@ -1254,7 +1279,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
 #pragma unroll
                     for (int i = 0; i < RM; ++i)
 #pragma unroll
-                        for (int j = 0; j < RN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[c][j], xa[c][i], acc[i][j], 0, 0, 0);
+                        for (int j = 0; j < RN; ++j) acc[i][j] = H16<E>::mfma32(wb[c][j], xa[c][i], acc[i][j]);
                 }
             }
 #pragma unroll
@@ -1265,7 +1290,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                 if (!(DBG & 4)) win_write();
                 __syncthreads();
 #pragma unroll
-                for (int i = 0; i < RM; ++i) xa[0][i] = *(const bf16x8*)(Aw + ao[i]);
+                for (int i = 0; i < RM; ++i) xa[0][i] = *(const h16x8*)(Aw + ao[i]);
             }
         };
         if (!(DBG & 16)) {
@@ -1301,7 +1326,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                 for (int j = 0; j < RN; ++j)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) sum += acc[i][j][e];
-            if (sum == 12345.678f) ((__bf16*)p.out)[0] = (__bf16)sum;
+            if (sum == 12345.678f) ((E*)p.out)[0] = (E)sum;
             continue;
         }
         constexpr int OS = BN + 4;                          // 528-byte rows: conflict-free ds_write_b128 for the accumulator layout
@@ -1322,8 +1347,8 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
             }
         }
         __syncthreads();
-        __bf16* out = (__bf16*)p.out;
-        const __bf16* res = (const __bf16*)p.res;
+        E* out = (E*)p.out;
+        const E* res = (const E*)p.res;
         constexpr int OCH = BM * (BN / 8) / NT;             // 16-byte output chunks per thread
         constexpr int OG = OCH >= 4 ? 4 : OCH;              // chunks per pass (bounds the residual registers)
         if (F2) {
@@ -1334,20 +1359,20 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
             // chunks of a row belong to 16 consecutive lanes of one wave, whose LDS reads of an iteration precede its LDS writes.
             // The second conv's weights W2 [128][128] go into the TAILS of the first 128 rows (bytes 272 .. 527 of a row are free once
             // the row has been converted): row n of W2 rides with tile row n, 16 bytes per lane of that row's chunk group.
-            __bf16* Tt = (__bf16*)arm_raw;
+            E* Tt = (E*)arm_raw;
             constexpr int TS = OS * 2;                           // row stride of the bf16 images in elements (528 B)
             constexpr int W2O = BN + 8;                          // element offset of a row's W2 slot (272 B)
             const __amdgpu_buffer_rsrc_t w2r = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, BN * CIN * 2, 0x00020000);
 #pragma unroll
             for (int u0 = 0; u0 < OCH; u0 += OG) {
-                bf16x8 rv[OG], w2v[OG];
+                h16x8 rv[OG], w2v[OG];
 #pragma unroll
                 for (int u = 0; u < OG; ++u) {
                     const int ch = tid + (u0 + u) * NT;
                     const int row = ch >> 4, col = (ch & 15) * 8;
                     const int m = m0 + row;
-                    if (res) rv[u] = (m < M) ? *(const bf16x8*)(res + (int64_t)m * p.res_ld + n0_cur + col) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                    w2v[u] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2r, row < BN ? (unsigned)((row * CIN + col) * 2) : 0x80000000u, 0, 0));
+                    if (res) rv[u] = (m < M) ? *(const h16x8*)(res + (int64_t)m * p.res_ld + n0_cur + col) : h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                    w2v[u] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(w2r, row < BN ? (unsigned)((row * CIN + col) * 2) : 0x80000000u, 0, 0));
                 }
                 f32x4 v0[OG], v1[OG];
 #pragma unroll
@@ -1362,11 +1387,11 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                     const int ch = tid + (u0 + u) * NT;
                     const int row = ch >> 4, col = (ch & 15) * 8;
                     const float f[8] = {v0[u].x, v0[u].y, v0[u].z, v0[u].w, v1[u].x, v1[u].y, v1[u].z, v1[u].w};
-                    bf16x8 o;
+                    h16x8 o;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = (__bf16)(res ? f[e] + (float)rv[u][e] : f[e]);
-                    *(bf16x8*)(Tt + row * TS + col) = o;
-                    if (row < BN) *(bf16x8*)(Tt + row * TS + W2O + col) = w2v[u];
+                    for (int e = 0; e < 8; ++e) o[e] = (E)(res ? f[e] + (float)rv[u][e] : f[e]);
+                    *(h16x8*)(Tt + row * TS + col) = o;
+                    if (row < BN) *(h16x8*)(Tt + row * TS + W2O + col) = w2v[u];
                 }
             }
             __syncthreads();
@@ -1380,16 +1405,16 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                     for (int e = 0; e < 16; ++e) acc2[i][j][e] = 0.f;
 #pragma unroll
             for (int s8 = 0; s8 < CIN / 16; ++s8) {
-                bf16x8 xt[RM];
+                h16x8 xt[RM];
 #pragma unroll
-                for (int i = 0; i < RM; ++i) xt[i] = *(const bf16x8*)(Tt + ((wm * RM + i) * 32 + i32) * TS + 16 * s8 + 8 * h);
-                bf16x8 w2f[RN];
+                for (int i = 0; i < RM; ++i) xt[i] = *(const h16x8*)(Tt + ((wm * RM + i) * 32 + i32) * TS + 16 * s8 + 8 * h);
+                h16x8 w2f[RN];
 #pragma unroll
-                for (int j = 0; j < RN; ++j) w2f[j] = *(const bf16x8*)(Tt + ((wn * RN + j) * 32 + i32) * TS + W2O + 16 * s8 + 8 * h);
+                for (int j = 0; j < RN; ++j) w2f[j] = *(const h16x8*)(Tt + ((wn * RN + j) * 32 + i32) * TS + W2O + 16 * s8 + 8 * h);
 #pragma unroll
                 for (int i = 0; i < RM; ++i)
 #pragma unroll
-                    for (int j = 0; j < RN; ++j) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[j], xt[i], acc2[i][j], 0, 0, 0);
+                    for (int j = 0; j < RN; ++j) acc2[i][j] = H16<E>::mfma32(w2f[j], xt[i], acc2[i][j]);
             }
             __syncthreads();                                     // every wave has read the bf16 image: the f32 tile may overwrite it
 #pragma unroll
@@ -1407,7 +1432,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                     }
             }
             __syncthreads();
-            __bf16* out2 = (__bf16*)p.out2;
+            E* out2 = (E*)p.out2;
 #pragma unroll
             for (int u = 0; u < OCH; ++u) {
                 const int ch = tid + u * NT;
@@ -1415,22 +1440,22 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                 const int m = m0 + row;
                 if (m >= M) continue;
                 const f32x4 a0 = *(const f32x4*)(Ot + row * OS + col), a1 = *(const f32x4*)(Ot + row * OS + col + 4);
-                const bf16x8 o = {(__bf16)a0.x, (__bf16)a0.y, (__bf16)a0.z, (__bf16)a0.w, (__bf16)a1.x, (__bf16)a1.y, (__bf16)a1.z, (__bf16)a1.w};
-                *(bf16x8*)(out2 + (int64_t)m * p.out2_ld + col) = o;
+                const h16x8 o = {(E)a0.x, (E)a0.y, (E)a0.z, (E)a0.w, (E)a1.x, (E)a1.y, (E)a1.z, (E)a1.w};
+                *(h16x8*)(out2 + (int64_t)m * p.out2_ld + col) = o;
             }
             __syncthreads();
             continue;
         }
 #pragma unroll
         for (int u0 = 0; u0 < OCH; u0 += OG) {
-            bf16x8 rv[OG];
+            h16x8 rv[OG];
             if (res) {
 #pragma unroll
                 for (int u = 0; u < OG; ++u) {
                     const int ch = tid + (u0 + u) * NT;
                     const int row = ch >> 4, col = (ch & 15) * 8;
                     const int m = m0 + row;
-                    rv[u] = (m < M && n0_cur + col < p.cout) ? *(const bf16x8*)(res + (int64_t)m * p.res_ld + n0_cur + col) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                    rv[u] = (m < M && n0_cur + col < p.cout) ? *(const h16x8*)(res + (int64_t)m * p.res_ld + n0_cur + col) : h16x8{0, 0, 0, 0, 0, 0, 0, 0};
                 }
             }
 #pragma unroll
@@ -1441,10 +1466,10 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_ar_kernel(GemmParams p
                 if (m >= M || n0_cur + col >= p.cout) continue;     // cout is a multiple of 8 here (host check)
                 const f32x4 v0 = *(const f32x4*)(Ot + row * OS + col), v1 = *(const f32x4*)(Ot + row * OS + col + 4);
                 float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                bf16x8 o;
+                h16x8 o;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (__bf16)(res ? f[e] + (float)rv[u][e] : f[e]);
-                *(bf16x8*)(out + (int64_t)m * p.out_ld + n0_cur + col) = o;
+                for (int e = 0; e < 8; ++e) o[e] = (E)(res ? f[e] + (float)rv[u][e] : f[e]);
+                *(h16x8*)(out + (int64_t)m * p.out_ld + n0_cur + col) = o;
             }
         }
         __syncthreads();                                    // the f32 tile has been read: the next tile's window may overwrite it
@@ -1458,12 +1483,12 @@ static size_t gemm_bf16_ar_lds(const GemmParams& p, int BM) {
     return loop > epi ? loop : epi;
 }
 
-template <int BM, int WM, int WN, int KSZ, int BD, int WCH, int DBG = 0, bool F2 = false>
-static hipError_t launch_gemm_bf16_ar_w(const GemmParams& p, hipStream_t s) {
+template <typename E, int BM, int WM, int WN, int KSZ, int BD, int WCH, int DBG, bool F2>
+static hipError_t launch_gemm_ar_h16_w(const GemmParams& p, hipStream_t s) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
     const int64_t tiles = ((M + BM - 1) / BM) * (p.cout_pad / 128);
     static LdsAttrOnce attr;
-    hipError_t e = attr.ensure((const void*)gemm_bf16_ar_kernel<BM, WM, WN, KSZ, BD, WCH, DBG, F2>, 160 * 1024);
+    hipError_t e = attr.ensure((const void*)gemm_bf16_ar_kernel<E, BM, WM, WN, KSZ, BD, WCH, DBG, F2>, 160 * 1024);
     if (e != hipSuccess) return e;
     // persistent workgroups: one per CU (or two when two fit), each walking tiles b, b + G, ...
     const Tuning& T = p.tune ? *p.tune : default_tuning();
@@ -1473,8 +1498,12 @@ static hipError_t launch_gemm_bf16_ar_w(const GemmParams& p, hipStream_t s) {
         const int64_t slots = (int64_t)device_cu_count() * (lds <= 80 * 1024 ? 2 : 1);
         if (grid > slots) grid = slots;
     }
-    hipLaunchKernelGGL((gemm_bf16_ar_kernel<BM, WM, WN, KSZ, BD, WCH, DBG, F2>), dim3((unsigned)grid), dim3(WM * WN * 64), lds, s, p);
+    hipLaunchKernelGGL((gemm_bf16_ar_kernel<E, BM, WM, WN, KSZ, BD, WCH, DBG, F2>), dim3((unsigned)grid), dim3(WM * WN * 64), lds, s, p);
     return hipGetLastError();
+}
+template <int BM, int WM, int WN, int KSZ, int BD, int WCH, int DBG = 0, bool F2 = false>
+static hipError_t launch_gemm_bf16_ar_w(const GemmParams& p, hipStream_t s) {
+    return p.f16 ? launch_gemm_ar_h16_w<_Float16, BM, WM, WN, KSZ, BD, WCH, DBG, F2>(p, s) : launch_gemm_ar_h16_w<__bf16, BM, WM, WN, KSZ, BD, WCH, DBG, F2>(p, s);
 }
 template <int BM, int WM, int WN, int KSZ, int BD, int DBG = 0, bool F2 = false>
 static hipError_t launch_gemm_bf16_ar_t(const GemmParams& p, hipStream_t s) {
@@ -1513,7 +1542,8 @@ static hipError_t try_gemm_bf16_ar(const GemmParams& p, hipStream_t s, bool* use
     }
     if (gemm_bf16_ar_lds(p, bm) > 160 * 1024) return hipSuccess;
     *used = true;
-    LWP_VARIANT(p, "gemm_bf16_ar<%d,%d,%d,%d>", bm, wm, wn, bd);
+    if (p.f16) LWP_VARIANT(p, "gemm_%s_ar<%d,%d,%d,%d>", "f16", bm, wm, wn, bd);
+    else LWP_VARIANT(p, "gemm_bf16_ar<%d,%d,%d,%d>", bm, wm, wn, bd);
 #ifdef LWP_ABLATION
     const int d = T.gemmh_debug;
 #define GAR_DBG(D_) if (bm == 256 && wm == 4 && wn == 2 && d == D_) return launch_gemm_bf16_ar_t<256, 4, 2, 3, 3, D_>(p, s); \
@@ -1525,7 +1555,8 @@ static hipError_t try_gemm_bf16_ar(const GemmParams& p, hipStream_t s, bool* use
     if (p.w2 && p.fused2 && T.gemmh_fold != 0 && bm == 256 && wm == 4 && wn == 2 && bd == 3 && p.cout_pad == 128 && p.cout == 128 &&
         !(p.out2_ld & 7) && !(((uintptr_t)p.out2) & 15)) {
         *p.fused2 = true;
-        LWP_VARIANT(p, "gemm_bf16_ar<256,4,2,3>+1x1");
+        if (p.f16) LWP_VARIANT(p, "gemm_%s_ar<256,4,2,3>+1x1", "f16");
+        else LWP_VARIANT(p, "gemm_bf16_ar<256,4,2,3>+1x1");
         return launch_gemm_bf16_ar_t<256, 4, 2, 3, 3, 0, true>(p, s);
     }
 #define GAR_CASE(BM_, WM_, WN_, BD_) if (bm == BM_ && wm == WM_ && wn == WN_ && bd == BD_) return launch_gemm_bf16_ar_t<BM_, WM_, WN_, 3, BD_>(p, s);
@@ -1554,7 +1585,8 @@ hipError_t launch_gemm_bf16(const GemmParams& p, hipStream_t s) {
     } else {
         bm = 64; bn = 64; rm = 1; rn = 1;             // 4 waves x (32 x 32): small problems
     }
-    LWP_VARIANT(p, "gemm_bf16<%d,%d,%d,%d>", bm, bn, rm, rn);
+    if (p.f16) LWP_VARIANT(p, "gemm_%s<%d,%d,%d,%d>", "f16", bm, bn, rm, rn);
+    else LWP_VARIANT(p, "gemm_bf16<%d,%d,%d,%d>", bm, bn, rm, rn);
 #define GH_CASE(BM_, BN_, RM_, RN_) if (bm == BM_ && bn == BN_ && rm == RM_ && rn == RN_) return launch_gemm_bf16_t<BM_, BN_, RM_, RN_>(p, s);
     GH_CASE(128, 128, 2, 2) GH_CASE(128, 64, 2, 1) GH_CASE(64, 64, 1, 1) GH_CASE(256, 128, 2, 2) GH_CASE(128, 128, 2, 1) GH_CASE(128, 128, 1, 1) GH_CASE(128, 64, 1, 1) GH_CASE(256, 128, 2, 1)
 #undef GH_CASE
@@ -1562,7 +1594,8 @@ hipError_t launch_gemm_bf16(const GemmParams& p, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------- layout helper
-__global__ void __launch_bounds__(256) nchw_from_nhwc_bf16_kernel(const __bf16* src, int src_ld, float* dst, int N, int HW, int C) {
+template <typename E>
+__global__ void __launch_bounds__(256) nchw_from_nhwc_bf16_kernel(const E* src, int src_ld, float* dst, int N, int HW, int C) {
     const int64_t total = (int64_t)N * C * HW;
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -1572,9 +1605,10 @@ __global__ void __launch_bounds__(256) nchw_from_nhwc_bf16_kernel(const __bf16* 
     const int n = (int)(t / C);
     dst[idx] = (float)src[((int64_t)n * HW + pix) * src_ld + c];
 }
-hipError_t launch_nchw_from_nhwc_bf16(const void* src, int src_ld, float* dst, int N, int HW, int C, hipStream_t s) {
+hipError_t launch_nchw_from_nhwc_bf16(const void* src, int src_ld, float* dst, int N, int HW, int C, hipStream_t s, bool f16) {
     const int64_t total = (int64_t)N * C * HW;
-    hipLaunchKernelGGL(nchw_from_nhwc_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const __bf16*)src, src_ld, dst, N, HW, C);
+    if (f16) hipLaunchKernelGGL(nchw_from_nhwc_bf16_kernel<_Float16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const _Float16*)src, src_ld, dst, N, HW, C);
+    else hipLaunchKernelGGL(nchw_from_nhwc_bf16_kernel<__bf16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const __bf16*)src, src_ld, dst, N, HW, C);
     return hipGetLastError();
 }
 

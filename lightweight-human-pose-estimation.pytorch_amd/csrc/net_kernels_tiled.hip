@@ -18,12 +18,11 @@
 // row-block kernels to the last bits of f32 rounding order (fp32: bit-identical accumulation chains per output).
 #include <type_traits>
 
+#include "h16.h"
 #include "lwp_internal.h"
 
 namespace lwp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct f32x8 { f32x4 lo, hi; };
 
@@ -34,8 +33,10 @@ __device__ __forceinline__ float tl_act(float v) {
     return v;
 }
 
-template <bool BF16, int C, int COUT, int S, int PH, int ACT = ACT_RELU>
+template <bool BF16, int C, int COUT, int S, int PH, int ACT = ACT_RELU, bool F16 = false>     // F16: fp16 instead of bf16 (BF16 true)
 __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int tiles_y, int tiles_x, int ntiles) {
+    typedef typename std::conditional<F16, _Float16, __bf16>::type h16;
+    typedef typename H16<h16>::x8 h16x8;
     constexpr int PW = 8;
     constexpr int VEC = BF16 ? 8 : 4;                  // channels per 16-byte vector
     constexpr int ESZ = BF16 ? 2 : 4;
@@ -55,7 +56,7 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
     static_assert(RT % WROWS == 0 && NU % WCOLS == 0, "tile / wave mismatch");
     constexpr int NSTEP = C / 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char tsm[];
-    typedef typename std::conditional<BF16, __bf16, float>::type elt;
+    typedef typename std::conditional<BF16, h16, float>::type elt;
     elt* win = (elt*)tsm;                               // [WR][WC][C]   (phase A / B)
     elt* til = (elt*)tsm;                               // [NPX][LDT]    (phase C, aliases the window)
 
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
     auto at = [&](int wy, int wx) -> f32x8 {
         f32x8 r;
         if (BF16) {
-            const bf16x8 v = *(const bf16x8*)((const __bf16*)win + (size_t)(wy * WC + wx) * C + c);
+            const h16x8 v = *(const h16x8*)((const h16*)win + (size_t)(wy * WC + wx) * C + c);
             r.lo = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
             r.hi = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
         } else {
@@ -185,8 +186,8 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
             const f32x4 lo = {tl_act<ACT>(res[i].lo.x), tl_act<ACT>(res[i].lo.y), tl_act<ACT>(res[i].lo.z), tl_act<ACT>(res[i].lo.w)};
             if (BF16) {
                 const f32x4 hi = {tl_act<ACT>(res[i].hi.x), tl_act<ACT>(res[i].hi.y), tl_act<ACT>(res[i].hi.z), tl_act<ACT>(res[i].hi.w)};
-                const bf16x8 o = {(__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w, (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w};
-                *(bf16x8*)((__bf16*)til + (size_t)pix * LDT + c) = o;
+                const h16x8 o = {(h16)lo.x, (h16)lo.y, (h16)lo.z, (h16)lo.w, (h16)hi.x, (h16)hi.y, (h16)hi.z, (h16)hi.w};
+                *(h16x8*)((h16*)til + (size_t)pix * LDT + c) = o;
             } else {
                 *(f32x4*)((float*)til + (size_t)pix * LDT + c) = lo;
             }
@@ -206,11 +207,11 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
                 // lane (pixel i16, q) reads k = 32 st + 8 q .. + 7; weights tile t: wreg[.][u][t]
 #pragma unroll
                 for (int a = 0; a < RTW; ++a) {
-                    const bf16x8 xv = *(const bf16x8*)((const __bf16*)til + (size_t)((wr + a * WROWS) * 16 + i16) * LDT + st * 32 + 8 * q);
+                    const h16x8 xv = *(const h16x8*)((const h16*)til + (size_t)((wr + a * WROWS) * 16 + i16) * LDT + st * 32 + 8 * q);
 #pragma unroll
                     for (int u = 0; u < UPW; ++u) {
-                        acc[u][a][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wreg[st & 1][u][0]), xv, acc[u][a][0], 0, 0, 0);
-                        acc[u][a][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wreg[st & 1][u][1]), xv, acc[u][a][1], 0, 0, 0);
+                        acc[u][a][0] = H16<h16>::mfma16(__builtin_bit_cast(h16x8, wreg[st & 1][u][0]), xv, acc[u][a][0]);
+                        acc[u][a][1] = H16<h16>::mfma16(__builtin_bit_cast(h16x8, wreg[st & 1][u][1]), xv, acc[u][a][1]);
                     }
                 }
             } else {
@@ -254,12 +255,12 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
                     v0 = f32x4{tl_act<ACT>(v0.x), tl_act<ACT>(v0.y), tl_act<ACT>(v0.z), tl_act<ACT>(v0.w)};
                     v1 = f32x4{tl_act<ACT>(v1.x), tl_act<ACT>(v1.y), tl_act<ACT>(v1.z), tl_act<ACT>(v1.w)};
                     if (p.res) {                              // residual (cpm: x + trunk(x)) before the single rounding to bf16
-                        const bf16x8 r = *(const bf16x8*)((const __bf16*)p.res + m * p.res_ld + nn);
+                        const h16x8 r = *(const h16x8*)((const h16*)p.res + m * p.res_ld + nn);
                         v0 += f32x4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
                         v1 += f32x4{(float)r[4], (float)r[5], (float)r[6], (float)r[7]};
                     }
-                    const bf16x8 o = {(__bf16)v0.x, (__bf16)v0.y, (__bf16)v0.z, (__bf16)v0.w, (__bf16)v1.x, (__bf16)v1.y, (__bf16)v1.z, (__bf16)v1.w};
-                    *(bf16x8*)((__bf16*)p.out + m * p.out_ld + nn) = o;
+                    const h16x8 o = {(h16)v0.x, (h16)v0.y, (h16)v0.z, (h16)v0.w, (h16)v1.x, (h16)v1.y, (h16)v1.z, (h16)v1.w};
+                    *(h16x8*)((h16*)p.out + m * p.out_ld + nn) = o;
                 } else {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
@@ -276,7 +277,7 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
     }
 }
 
-template <bool BF16, int C, int COUT, int S, int PH, int ACT = ACT_RELU>
+template <bool BF16, int C, int COUT, int S, int PH, int ACT = ACT_RELU, bool F16 = false>
 static hipError_t launch_tiled_t(const DwPwParams& p, hipStream_t s) {
     constexpr int ESZ = BF16 ? 2 : 4;
     constexpr int WR = (PH - 1) * S + 3, WC = 7 * S + 3;
@@ -286,7 +287,7 @@ static hipError_t launch_tiled_t(const DwPwParams& p, hipStream_t s) {
     const int64_t tiles = (int64_t)p.N * tiles_y * tiles_x;
     if (tiles >= (1ll << 31) - 1) return hipErrorInvalidValue;
     static LdsAttrOnce attr;
-    if (lds > 48 * 1024) { hipError_t e = attr.ensure((const void*)dwpw_tiled_kernel<BF16, C, COUT, S, PH, ACT>, 96 * 1024); if (e != hipSuccess) return e; }
+    if (lds > 48 * 1024) { hipError_t e = attr.ensure((const void*)dwpw_tiled_kernel<BF16, C, COUT, S, PH, ACT, F16>, 96 * 1024); if (e != hipSuccess) return e; }
     // persistent grid: as many workgroups as the chip holds at once (LDS- and register-limited), each walking patches b, b + G, ...
     const Tuning& T = p.tune ? *p.tune : default_tuning();
     int per_cu = (int)((160 * 1024) / (lds + 256));
@@ -300,12 +301,12 @@ static hipError_t launch_tiled_t(const DwPwParams& p, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) grid = (int64_t)cus * per_cu;
     }
     if (grid > tiles) grid = tiles;
-    hipLaunchKernelGGL((dwpw_tiled_kernel<BF16, C, COUT, S, PH, ACT>), dim3((unsigned)grid), dim3(256), lds, s, p, tiles_y, tiles_x, (int)tiles);
+    hipLaunchKernelGGL((dwpw_tiled_kernel<BF16, C, COUT, S, PH, ACT, F16>), dim3((unsigned)grid), dim3(256), lds, s, p, tiles_y, tiles_x, (int)tiles);
     return hipGetLastError();
 }
 
 // *used = false: the caller takes the row-block kernel
-template <bool BF16>
+template <bool BF16, bool F16 = false>
 static hipError_t try_tiled(const DwPwParams& p, hipStream_t s, bool* used) {
     *used = false;
     const Tuning& T = p.tune ? *p.tune : default_tuning();
@@ -319,8 +320,8 @@ static hipError_t try_tiled(const DwPwParams& p, hipStream_t s, bool* used) {
     const int64_t pixels = (int64_t)p.N * p.Ho * p.Wo;
     if (T.dwpw_tiled != 1 && pixels < (int64_t)96 * 1024) return hipSuccess;                // small maps: the row-block kernels fill the chip better
     *used = true;
-    LWP_VARIANT(p, "dwpw_tiled<%s,%d,%d,s=%d>", BF16 ? "bf16" : "f32", p.C, p.cout, p.stride);
-#define TL_CASE(C_, CO_, S_, PH_) if (relu && p.C == C_ && p.cout == CO_ && p.stride == S_) return launch_tiled_t<BF16, C_, CO_, S_, PH_>(p, s);
+    LWP_VARIANT(p, "dwpw_tiled<%s,%d,%d,s=%d>", F16 ? "f16" : BF16 ? "bf16" : "f32", p.C, p.cout, p.stride);
+#define TL_CASE(C_, CO_, S_, PH_) if (relu && p.C == C_ && p.cout == CO_ && p.stride == S_) return launch_tiled_t<BF16, C_, CO_, S_, PH_, ACT_RELU, F16>(p, s);
     const bool forced = T.dwpw_tiled == 1;
     TL_CASE(32, 64, 1, 16)
     // the wider blocks take 4-row patches: the NEXT patch's window is 4 - 8 sixteen-byte pieces per thread (8-row patches: 7 - 19,
@@ -333,12 +334,17 @@ static hipError_t try_tiled(const DwPwParams& p, hipStream_t s, bool* used) {
     if (!BF16 || forced) { TL_CASE(128, 128, 1, 4) }
 #undef TL_CASE
     if constexpr (BF16) {
-        if (forced && elu && p.C == 128 && p.cout == 128 && p.stride == 1) return launch_tiled_t<true, 128, 128, 1, 4, ACT_ELU>(p, s);   // cpm.trunk
+        if (forced && elu && p.C == 128 && p.cout == 128 && p.stride == 1) {     // cpm.trunk
+            if (F16) return launch_tiled_t<true, 128, 128, 1, 4, ACT_ELU, true>(p, s);
+            return launch_tiled_t<true, 128, 128, 1, 4, ACT_ELU>(p, s);
+        }
     }
     *used = false;
     return hipSuccess;
 }
 hipError_t try_dwpw_tiled_f32(const DwPwParams& p, hipStream_t s, bool* used) { return try_tiled<false>(p, s, used); }
-hipError_t try_dwpw_tiled_bf16(const DwPwParams& p, hipStream_t s, bool* used) { return try_tiled<true>(p, s, used); }
+hipError_t try_dwpw_tiled_bf16(const DwPwParams& p, hipStream_t s, bool* used) {
+    return p.f16 ? try_tiled<true, true>(p, s, used) : try_tiled<true>(p, s, used);
+}
 
 }  // namespace lwp

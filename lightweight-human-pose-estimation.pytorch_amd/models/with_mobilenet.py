@@ -19,7 +19,7 @@ class PoseEstimationWithMobileNet(object):
         import torch
         self.num_refinement_stages = num_refinement_stages
         self.num_channels, self.num_heatmaps, self.num_pafs = num_channels, num_heatmaps, num_pafs
-        self.dtype = {"fp32": _lib.F32, "bf16": _lib.BF16}[dtype]
+        self.dtype = {"fp32": _lib.F32, "bf16": _lib.BF16, "fp16": _lib.F16}[dtype]
         # parameters start from a deterministic random init (the reference starts from torch's default init)
         self._state = synth.make_state_dict(num_refinement_stages, seed=0, num_channels=num_channels,
                                             num_heatmaps=num_heatmaps, num_pafs=num_pafs)
