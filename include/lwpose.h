@@ -79,9 +79,29 @@ const char* lwp_last_error(lwp_handle h);
  *      queried first).  Host-memory results are complete on return in all modes. */
 int lwp_set_stream(lwp_handle h, void* caller_stream, int enable);
 
-/* capacities of the post-processing lists (defaults 2048 / 128 / 4096 / 256); overflow => LWP_ERR_CAPACITY */
+/* capacities of the post-processing lists (defaults 2048 / 128 / 4096 / 256); overflow => LWP_ERR_CAPACITY.  Refused while a
+ * pipeline slot is pending; discards the results of an unfetched lwp_infer_poses_async run (lwp_fetch_poses: LWP_ERR_STATE). */
 int lwp_set_capacity(lwp_handle h, int max_peaks_per_channel, int max_kpts_per_type,
                      int max_connections_per_limb, int max_pose_entries);
+
+/* ---- skeleton: the grouping tables of modules/keypoints.py:5-8 (BODY_PARTS_KPT_IDS, BODY_PARTS_PAF_IDS) and group_keypoints'
+ *      options (:51), for networks trained on another key-point set (TRAIN-ON-CUSTOM-DATASET.md: num_heatmaps = K + 1,
+ *      num_pafs = 2 L).  limb_kpts / limb_pafs: num_limbs x 2 int (key-point types a, b; PAF channels x, y), in grouping order.
+ *      limb_kpts == NULL restores the default (COCO tables, 18 types, pose_entry_size 20, min_paf_score 0.05).
+ *      Checks (LWP_ERR_ARG with a message): 1 <= K <= 64 and K <= num_heatmaps (only the first K heat-map channels are read,
+ *      like range(num_keypoints), demo.py:97); 1 <= L <= 320; 0 <= a, b < K, a != b; PAF ids < num_pafs (the two of a limb may
+ *      be equal); K + 2 <= pose_entry_size <= 256.  Deliberate divergence: the reference silently overwrites key-point columns
+ *      with the score and count when pose_entry_size < K + 2; this library refuses it.  min_paf_score: any double, used in
+ *      the reference's strict float64 '>'.  Host state of the handle (not part of the weight blob); the workspaces are
+ *      re-sized by K / L on the next call.  Every pose-producing export below uses the handle's skeleton: in their buffer
+ *      shapes 18 / 19 / 20 read K / L / E (pose_entry_size).  The default skeleton runs COCO-specialised kernels; any other
+ *      runs generic ones (LWP_POST_GENERIC=1 at lwp_create forces the generic kernels under the default skeleton too).
+ *      Refused while a pipeline slot is pending (LWP_ERR_STATE); the results of an lwp_infer_poses_async run not
+ *      yet fetched are discarded (lwp_fetch_poses then returns LWP_ERR_STATE), as after lwp_set_capacity.  lwp_get_skeleton: limb arrays of limb_cap rows (or NULL). */
+int lwp_set_skeleton(lwp_handle h, int num_kpt_types, int num_limbs, const int* limb_kpts, const int* limb_pafs,
+                     int pose_entry_size, double min_paf_score);
+int lwp_get_skeleton(lwp_handle h, int* num_kpt_types, int* num_limbs, int* limb_kpts, int* limb_pafs, int limb_cap,
+                     int* pose_entry_size, double* min_paf_score);
 
 /* ---- weights: replaces net.load_state_dict(...) at the end of load_state (modules/load_state.py:15).
  *      names[i] = state_dict key, ptrs[i] = host float32 data (int64 for num_batches_tracked, ignored),
@@ -165,10 +185,11 @@ int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int maps_mem, int
 int lwp_extract_keypoints(lwp_handle h, float* heatmap, int H, int W, int64_t row_stride, int64_t pix_stride,
                           int64_t* xs, int64_t* ys, float* scores, int cap, int* count);
 
-/* ---- group_keypoints: replaces modules/keypoints.py:51-201.
- *      kpts: K x 4 float64 rows (x, y, score, id) concatenated by type; type_counts[18].
+/* ---- group_keypoints: replaces modules/keypoints.py:51-201 (with the handle's skeleton: K types, E = pose_entry_size).
+ *      kpts: rows (x, y, score, id) float64 concatenated by type; type_counts[K] (18 by default).
  *      pafs: H x W x num_pafs float32 HWC (mem).  demo != 0 -> int() truncation, else round-half-even.
- *      pose_entries: cap_entries x 20 float64 out; *n_entries out. */
+ *      pose_entries: cap_entries x E float64 out (20 by default): ids in columns 0..K-1, -1 up to E-3, score at E-2, count at
+ *      E-1; *n_entries out. */
 int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* type_counts,
                         const float* pafs, int pafs_mem, int H, int W, int demo,
                         double* pose_entries, int cap_entries, int* n_entries);
@@ -177,9 +198,9 @@ int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* type_counts
  *      (demo.py:93-100: infer_fast -> 18 x extract_keypoints -> group_keypoints) for a batch.
  *      in: N x 3 x H x W float32, already normalised and padded (mem).  The up-sampled maps are never
  *      materialised: peaks and PAF samples are interpolated on the fly with the same arithmetic.
- *      Outputs (host): for frame f, kpt_counts[f*18 + t] key-points of type t; kpts rows
- *      (x, y, score, id) float64 at kpts + f*kpt_cap*4; entries at entries + f*entry_cap*20;
- *      n_entries[f]. */
+ *      Outputs (host): for frame f, kpt_counts[f*K + t] key-points of type t; kpts rows
+ *      (x, y, score, id) float64 at kpts + f*kpt_cap*4; entries at entries + f*entry_cap*E;
+ *      n_entries[f].  K / E: the handle's skeleton (18 / 20 by default, lwp_set_skeleton). */
 int lwp_infer_poses(lwp_handle h, const float* in, int in_mem, int N, int H, int W,
                     int upsample_ratio, int demo,
                     int* kpt_counts, double* kpts, int kpt_cap,
@@ -252,6 +273,12 @@ int lwp_debug_frames_per_pass(lwp_handle h, int N, int H, int W);
  * type after it [18], scored connection candidates per limb [19], connections picked per limb [19].  Tests / tools: which
  * form of nms_kernel / match_kernel (register form up to 64 candidates, LDS form beyond) a workload exercises. */
 int lwp_debug_post_counts(lwp_handle h, int frame, int* peaks18, int* kpts18, int* candidates19, int* picked19);
+/* the same for any skeleton: peaks[K], kpts[K], candidates[L], picked[L]; K and L must be the skeleton's (LWP_ERR_ARG otherwise).
+ * lwp_debug_post_counts itself keeps its [18] / [19] contract and returns LWP_ERR_STATE under a non-default skeleton. */
+int lwp_debug_post_counts_ex(lwp_handle h, int frame, int* peaks, int* kpts, int* candidates, int* picked, int K, int L);
+/* which grouping kernels the handle launches: 1 = the generic forms (a custom skeleton, or LWP_POST_GENERIC=1 at lwp_create),
+ * 0 = the COCO-specialised ones */
+int lwp_debug_post_generic(lwp_handle h);
 
 #ifdef __cplusplus
 }

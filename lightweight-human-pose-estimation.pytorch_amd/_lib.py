@@ -18,7 +18,8 @@ EXPORTS = [
     "lwp_synchronize", "lwp_poses_from_maps", "lwp_layer_count", "lwp_layer_info", "lwp_debug_layer_output",
     "lwp_profile_launches", "lwp_debug_time_layer", "lwp_pipeline_submit", "lwp_pipeline_fetch", "lwp_multiscale_accumulate",
     "lwp_preprocess_dims", "lwp_preprocess_u8", "lwp_scale_dims", "lwp_preprocess_scaled_u8", "lwp_debug_layer_variant", "lwp_set_stream", "lwp_preprocess_scaled_f32", "lwp_debug_frames_per_pass", "lwp_debug_post_counts",
-    "lwp_debug_f32_to_f16",
+    "lwp_debug_f32_to_f16", "lwp_set_skeleton", "lwp_get_skeleton", "lwp_debug_post_counts_ex",
+    "lwp_debug_post_generic",
 ]
 
 
@@ -81,6 +82,10 @@ def lib():
     L.lwp_debug_frames_per_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.lwp_debug_post_counts.argtypes = [vp, C.c_int] + [C.POINTER(C.c_int)] * 4
     L.lwp_debug_f32_to_f16.argtypes = [vp, vp, C.c_int64]
+    L.lwp_set_skeleton.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.c_int, C.c_double]
+    L.lwp_get_skeleton.argtypes = [vp, ip, ip, ip, ip, C.c_int, ip, dp]
+    L.lwp_debug_post_counts_ex.argtypes = [vp, C.c_int] + [ip] * 4 + [C.c_int, C.c_int]
+    L.lwp_debug_post_generic.argtypes = [vp]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -51,6 +51,9 @@ struct lwp_context {
     // post-processing
     PostCaps caps;
     PostWorkspace ws;
+    Skeleton skel = default_skeleton();    // grouping tables + options (lwp_set_skeleton); host state, not part of the weights
+    int* d_limbs = nullptr;                // [kMaxSkelLimbs][4] device copy of skel's limb table (the generic kernels read it)
+    bool post_generic = false;             // LWP_POST_GENERIC=1 at lwp_create: the generic grouping kernels under the default skeleton too
     // pinned host staging for results
     void* h_stage = nullptr; size_t h_stage_bytes = 0;
     int last_N = 0;
@@ -82,6 +85,19 @@ struct lwp_context {
 
 static std::string g_err;
 static std::mutex g_mu;
+
+namespace lwp {
+Skeleton default_skeleton() {              // modules/keypoints.py:5-8
+    static const int kpt[19][2] = {{1, 2}, {1, 5}, {2, 3}, {3, 4}, {5, 6}, {6, 7}, {1, 8}, {8, 9}, {9, 10}, {1, 11},
+                                   {11, 12}, {12, 13}, {1, 0}, {0, 14}, {14, 16}, {0, 15}, {15, 17}, {2, 16}, {5, 17}};
+    static const int paf[19][2] = {{12, 13}, {20, 21}, {14, 15}, {16, 17}, {22, 23}, {24, 25}, {0, 1}, {2, 3}, {4, 5}, {6, 7},
+                                   {8, 9}, {10, 11}, {28, 29}, {30, 31}, {34, 35}, {32, 33}, {36, 37}, {18, 19}, {26, 27}};
+    Skeleton s;
+    s.kpt.assign(&kpt[0][0], &kpt[0][0] + 38);
+    s.paf.assign(&paf[0][0], &paf[0][0] + 38);
+    return s;
+}
+}  // namespace lwp
 
 static int fail(lwp_context* h, int code, const std::string& msg) {
     if (h) h->err = msg;
@@ -199,6 +215,8 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
         h->fuse_heads = !(he && he[0] == '0');
         const char* pe = getenv("LWP_POST_STREAM");
         h->post_on_main = pe && pe[0] == '0';
+        const char* ge = getenv("LWP_POST_GENERIC");
+        h->post_generic = ge && ge[0] == '1';
         h->tune = tuning_from_env();
         h->variants.assign(h->g.layers.size(), std::string());
     }
@@ -211,6 +229,14 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
     e = hipMalloc((void**)&h->d_zeros, 4096);
     if (e == hipSuccess) e = hipMemset(h->d_zeros, 0, 4096);
     if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipMalloc(zeros): ") + hipGetErrorString(e)); }
+    {
+        std::vector<int> t(19 * 4);
+        for (int l = 0; l < 19; ++l)
+            for (int k = 0; k < 2; ++k) { t[l * 4 + k] = h->skel.kpt[l * 2 + k]; t[l * 4 + 2 + k] = h->skel.paf[l * 2 + k]; }
+        e = hipMalloc((void**)&h->d_limbs, (size_t)kMaxSkelLimbs * 4 * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(h->d_limbs, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipMalloc(limbs): ") + hipGetErrorString(e)); }
+    }
     h->bufs.assign(h->g.bufs.size(), nullptr);
     h->d_outs.assign(2 * (1 + nref), nullptr);
     h->d_outs_bytes.assign(2 * (1 + nref), 0);
@@ -249,6 +275,7 @@ extern "C" int lwp_destroy(lwp_handle h) {
     if (h->d_pre_tab) (void)hipFree(h->d_pre_tab);
     if (h->d_blob) (void)hipFree(h->d_blob);
     if (h->d_zeros) (void)hipFree(h->d_zeros);
+    if (h->d_limbs) (void)hipFree(h->d_limbs);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     free_ws(h);
     if (h->post_stream) (void)hipStreamSynchronize(h->post_stream);
@@ -272,11 +299,81 @@ extern "C" int lwp_set_capacity(lwp_handle h, int max_peaks, int max_kpts, int m
     if (max_peaks < 64 || max_peaks > 8192 || max_kpts < 1 || max_kpts > 1024 || max_conn < 1 || max_conn > (1 << 20) ||
         max_entries < 1 || max_entries > 65535)
         return fail(h, LWP_ERR_ARG, "capacity out of range (peaks 64..8192, kpts 1..1024, conns 1..2^20, entries 1..65535)");
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
     (void)hipSetDevice(h->device);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_ws(h);
-    for (auto& sl : h->slots) { if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending"); free_ws_obj(sl.ws); }
+    for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    h->last_N = 0;                                     // the results of an unfetched lwp_infer_poses_async went with the workspace
     h->caps.max_peaks = max_peaks; h->caps.max_kpts = max_kpts; h->caps.max_conn = max_conn; h->caps.max_entries = max_entries;
+    return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- skeleton
+extern "C" int lwp_set_skeleton(lwp_handle h, int num_kpt_types, int num_limbs, const int* limb_kpts, const int* limb_pafs,
+                                int pose_entry_size, double min_paf_score) {
+    if (!h) return LWP_ERR_ARG;
+    Skeleton sk = default_skeleton();
+    if (limb_kpts) {
+        const int K = num_kpt_types, L = num_limbs, E = pose_entry_size;
+        char msg[200];
+        if (K < 1 || K > kMaxSkelTypes) return fail(h, LWP_ERR_ARG, "num_kpt_types must be 1..64");
+        if (K > h->g.NH) {
+            snprintf(msg, sizeof msg, "num_kpt_types %d exceeds the network's %d heat-maps", K, h->g.NH);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        if (L < 1 || L > kMaxSkelLimbs) return fail(h, LWP_ERR_ARG, "num_limbs must be 1..320");
+        if (!limb_pafs) return fail(h, LWP_ERR_ARG, "limb_pafs is null");
+        if (E < K + 2 || E > kMaxEntrySize) {
+            snprintf(msg, sizeof msg, "pose_entry_size must be num_kpt_types + 2 .. 256 (got %d for %d key-point types)", E, K);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        for (int l = 0; l < L; ++l) {
+            const int a = limb_kpts[2 * l], b = limb_kpts[2 * l + 1], c0 = limb_pafs[2 * l], c1 = limb_pafs[2 * l + 1];
+            if (a < 0 || a >= K || b < 0 || b >= K || a == b) {
+                snprintf(msg, sizeof msg, "limb %d: key-point types (%d, %d) must be distinct and in 0..%d", l, a, b, K - 1);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+            if (c0 < 0 || c0 >= h->g.NP || c1 < 0 || c1 >= h->g.NP) {
+                snprintf(msg, sizeof msg, "limb %d: PAF channels (%d, %d) must be in 0..%d", l, c0, c1, h->g.NP - 1);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+        }
+        sk.K = K; sk.L = L; sk.E = E;
+        sk.min_paf = min_paf_score;
+        sk.kpt.assign(limb_kpts, limb_kpts + 2 * L);
+        sk.paf.assign(limb_pafs, limb_pafs + 2 * L);
+        const Skeleton d = default_skeleton();
+        sk.is_default = K == d.K && L == d.L && E == d.E && min_paf_score == d.min_paf && sk.kpt == d.kpt && sk.paf == d.paf;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    std::vector<int> t((size_t)sk.L * 4);
+    for (int l = 0; l < sk.L; ++l)
+        for (int k = 0; k < 2; ++k) { t[l * 4 + k] = sk.kpt[l * 2 + k]; t[l * 4 + 2 + k] = sk.paf[l * 2 + k]; }
+    HIP_TRY(h, hipMemcpy(h->d_limbs, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+    free_ws(h);                                        // every workspace is sized by K / L / E: re-allocated lazily
+    for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    h->last_N = 0;                                     // the results of an unfetched lwp_infer_poses_async went with the workspace
+    h->skel = sk;
+    return LWP_OK;
+}
+
+extern "C" int lwp_get_skeleton(lwp_handle h, int* num_kpt_types, int* num_limbs, int* limb_kpts, int* limb_pafs, int limb_cap,
+                                int* pose_entry_size, double* min_paf_score) {
+    if (!h) return LWP_ERR_ARG;
+    const Skeleton& sk = h->skel;
+    if (num_kpt_types) *num_kpt_types = sk.K;
+    if (num_limbs) *num_limbs = sk.L;
+    if (pose_entry_size) *pose_entry_size = sk.E;
+    if (min_paf_score) *min_paf_score = sk.min_paf;
+    if (limb_kpts || limb_pafs) {
+        if (limb_cap < sk.L) return fail(h, LWP_ERR_CAPACITY, "limb arrays too small");
+        if (limb_kpts) std::copy(sk.kpt.begin(), sk.kpt.end(), limb_kpts);
+        if (limb_pafs) std::copy(sk.paf.begin(), sk.paf.end(), limb_pafs);
+    }
     return LWP_OK;
 }
 
@@ -375,24 +472,35 @@ static int ensure_activations(lwp_context* h, int N, int H, int W) {
     return LWP_OK;
 }
 
+// the default skeleton reads 18 heat-maps and PAF channels up to 37; a custom one was checked against the network by lwp_set_skeleton
+static bool skeleton_fits(const lwp_context* h) {
+    if (!h->skel.is_default) return true;
+    return h->g.NH >= 18 && h->g.NP >= 38;
+}
+
 static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t stream) {
     if (w.N >= N && w.peak_count) return LWP_OK;
     HIP_TRY(h, hipStreamSynchronize(stream));
     free_ws_obj(w);
     w.caps = h->caps;
     const PostCaps& c = h->caps;
+    const int K = h->skel.K, L = h->skel.L, E = h->skel.E;
+    w.K = K; w.L = L; w.E = E;
+    w.min_paf = h->skel.min_paf;
+    w.generic = (!h->skel.is_default || h->post_generic) ? 1 : 0;
+    w.limbs = h->d_limbs;
 #define WS_ALLOC(field, count, type) HIP_TRY(h, hipMalloc((void**)&w.field, (size_t)(count) * sizeof(type)))
-    WS_ALLOC(peak_count, N * 18, int);
-    WS_ALLOC(peak_key, (size_t)N * 18 * c.max_peaks, uint32_t);
-    WS_ALLOC(peak_val, (size_t)N * 18 * c.max_peaks, float);
-    WS_ALLOC(kpt_xy, (size_t)N * 18 * c.max_kpts * 2, int);
-    WS_ALLOC(kpt_score, (size_t)N * 18 * c.max_kpts, float);
-    WS_ALLOC(conn_count, N * 19, int);
-    WS_ALLOC(conn_ij, (size_t)N * 19 * c.max_conn, int);
-    WS_ALLOC(conn_ratio, (size_t)N * 19 * c.max_conn, double);
-    {   // result block: [flags N*4 u64][kpts_out N*18*kcap*4 f64][entries N*ecap*20 f64][kpt_count N*18 i32][n_entries N i32]
-        const size_t b_fl = (size_t)N * 4 * 8, b_k = (size_t)N * 18 * c.max_kpts * 4 * 8, b_e = (size_t)N * c.max_entries * 20 * 8;
-        const size_t b_cnt = (size_t)N * 18 * 4, b_ne = (size_t)N * 4;
+    WS_ALLOC(peak_count, N * K, int);
+    WS_ALLOC(peak_key, (size_t)N * K * c.max_peaks, uint32_t);
+    WS_ALLOC(peak_val, (size_t)N * K * c.max_peaks, float);
+    WS_ALLOC(kpt_xy, (size_t)N * K * c.max_kpts * 2, int);
+    WS_ALLOC(kpt_score, (size_t)N * K * c.max_kpts, float);
+    WS_ALLOC(conn_count, N * L, int);
+    WS_ALLOC(conn_ij, (size_t)N * L * c.max_conn, int);
+    WS_ALLOC(conn_ratio, (size_t)N * L * c.max_conn, double);
+    {   // result block: [flags N*4 u64][kpts_out N*K*kcap*4 f64][entries N*ecap*E f64][kpt_count N*K i32][n_entries N i32]
+        const size_t b_fl = (size_t)N * 4 * 8, b_k = (size_t)N * K * c.max_kpts * 4 * 8, b_e = (size_t)N * c.max_entries * E * 8;
+        const size_t b_cnt = (size_t)N * K * 4, b_ne = (size_t)N * 4;
         w.result_bytes = b_fl + b_k + b_e + b_cnt + b_ne;
         HIP_TRY(h, hipMalloc((void**)&w.result_block, w.result_bytes));
         char* q = (char*)w.result_block;
@@ -402,13 +510,13 @@ static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t st
         w.kpt_count = (int*)q; q += b_cnt;
         w.n_entries = (int*)q;
     }
-    WS_ALLOC(entries_work, (size_t)N * c.max_entries * 20, double);
-    WS_ALLOC(sel_count, N * 19, int);
-    WS_ALLOC(seen, N * 37, int);
-    WS_ALLOC(sel_ij, (size_t)N * 19 * c.max_kpts, int);
-    WS_ALLOC(sel_r, (size_t)N * 19 * c.max_kpts, double);
-    WS_ALLOC(sel_sa, (size_t)N * 19 * c.max_kpts, float);
-    WS_ALLOC(sel_sb, (size_t)N * 19 * c.max_kpts, float);
+    WS_ALLOC(entries_work, (size_t)N * c.max_entries * E, double);
+    WS_ALLOC(sel_count, N * L, int);
+    WS_ALLOC(seen, N * (K + L), int);
+    WS_ALLOC(sel_ij, (size_t)N * L * c.max_kpts, int);
+    WS_ALLOC(sel_r, (size_t)N * L * c.max_kpts, double);
+    WS_ALLOC(sel_sa, (size_t)N * L * c.max_kpts, float);
+    WS_ALLOC(sel_sb, (size_t)N * L * c.max_kpts, float);
 #undef WS_ALLOC
     w.N = N;
     HIP_TRY(h, launch_reset_ws(N, w, stream));
@@ -486,15 +594,16 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
     const PostCaps& c = w.caps;
     const size_t f = (size_t)f0;
     v.N = w.N - f0;
-    v.peak_count += f * 18; v.peak_key += f * 18 * c.max_peaks; v.peak_val += f * 18 * c.max_peaks;
-    v.kpt_count += f * 18; v.kpt_xy += f * 18 * c.max_kpts * 2; v.kpt_score += f * 18 * c.max_kpts;
-    v.conn_count += f * 19; v.conn_ij += f * 19 * c.max_conn; v.conn_ratio += f * 19 * c.max_conn;
+    const size_t K = (size_t)w.K, L = (size_t)w.L, E = (size_t)w.E;
+    v.peak_count += f * K; v.peak_key += f * K * c.max_peaks; v.peak_val += f * K * c.max_peaks;
+    v.kpt_count += f * K; v.kpt_xy += f * K * c.max_kpts * 2; v.kpt_score += f * K * c.max_kpts;
+    v.conn_count += f * L; v.conn_ij += f * L * c.max_conn; v.conn_ratio += f * L * c.max_conn;
     v.flags += f * 4;
-    v.sel_count += f * 19; v.sel_ij += f * 19 * c.max_kpts; v.sel_r += f * 19 * c.max_kpts;
-    v.seen += f * 37;
-    v.sel_sa += f * 19 * c.max_kpts; v.sel_sb += f * 19 * c.max_kpts;
-    v.entries_work += f * c.max_entries * 20; v.entries += f * c.max_entries * 20;
-    v.n_entries += f; v.kpts_out += f * 18 * c.max_kpts * 4;
+    v.sel_count += f * L; v.sel_ij += f * L * c.max_kpts; v.sel_r += f * L * c.max_kpts;
+    v.seen += f * (K + L);
+    v.sel_sa += f * L * c.max_kpts; v.sel_sb += f * L * c.max_kpts;
+    v.entries_work += f * c.max_entries * E; v.entries += f * c.max_entries * E;
+    v.n_entries += f; v.kpts_out += f * K * c.max_kpts * 4;
     return v;
 }
 
@@ -1109,9 +1218,10 @@ static int parse_results(lwp_context* h, const PostWorkspace& ws, const void* ho
     const int WN = ws.N;                         // the block is laid out for the workspace's frame capacity
     const char* p = (const char*)host_block;
     const unsigned long long* h_fl = (const unsigned long long*)p; p += (size_t)WN * 4 * 8;
-    const double* h_k = (const double*)p; p += (size_t)WN * 18 * c.max_kpts * 4 * 8;
-    const double* h_e = (const double*)p; p += (size_t)WN * c.max_entries * 20 * 8;
-    const int* h_cnt = (const int*)p; p += (size_t)WN * 18 * 4;
+    const int K = ws.K, E = ws.E;
+    const double* h_k = (const double*)p; p += (size_t)WN * K * c.max_kpts * 4 * 8;
+    const double* h_e = (const double*)p; p += (size_t)WN * c.max_entries * E * 8;
+    const int* h_cnt = (const int*)p; p += (size_t)WN * K * 4;
     const int* h_ne = (const int*)p;
     for (int f = 0; f < N; ++f) {
         if (h_fl[f * 4 + 0]) {
@@ -1122,10 +1232,10 @@ static int parse_results(lwp_context* h, const PostWorkspace& ws, const void* ho
         if (h_fl[f * 4 + 1] < h_fl[f * 4 + 2])
             return fail(h, LWP_ERR_UNBOUND, "local variable 'ratio' referenced before assignment");
         int total = 0;
-        for (int t = 0; t < 18; ++t) { kpt_counts[f * 18 + t] = h_cnt[f * 18 + t]; total += h_cnt[f * 18 + t]; }
+        for (int t = 0; t < K; ++t) { kpt_counts[f * K + t] = h_cnt[f * K + t]; total += h_cnt[f * K + t]; }
         if (total > kpt_cap || h_ne[f] > entry_cap) return fail(h, LWP_ERR_CAPACITY, "result arrays too small");
-        std::memcpy(kpts + (size_t)f * kpt_cap * 4, h_k + (size_t)f * 18 * c.max_kpts * 4, (size_t)total * 4 * sizeof(double));
-        std::memcpy(entries + (size_t)f * entry_cap * 20, h_e + (size_t)f * c.max_entries * 20, (size_t)h_ne[f] * 20 * sizeof(double));
+        std::memcpy(kpts + (size_t)f * kpt_cap * 4, h_k + (size_t)f * K * c.max_kpts * 4, (size_t)total * 4 * sizeof(double));
+        std::memcpy(entries + (size_t)f * entry_cap * E, h_e + (size_t)f * c.max_entries * E, (size_t)h_ne[f] * E * sizeof(double));
         n_entries[f] = h_ne[f];
     }
     return LWP_OK;
@@ -1139,17 +1249,18 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
     int rc = ensure_ws(h, 1);
     if (rc) return rc;
     const PostCaps& c = h->ws.caps;
+    const int K = h->ws.K;
     int total = 0;
-    for (int t = 0; t < 18; ++t) {
+    for (int t = 0; t < K; ++t) {
         if (type_counts[t] < 0) return fail(h, LWP_ERR_ARG, "negative type count");
         if (type_counts[t] > c.max_kpts) return fail(h, LWP_ERR_CAPACITY, "group_keypoints: more key-points of one type than max_kpts_per_type");
         total += type_counts[t];
     }
     if (total > 0 && !kpts) return fail(h, LWP_ERR_ARG, "kpts is null");
-    std::vector<int> xy((size_t)18 * c.max_kpts * 2, 0), cnt(18);
-    std::vector<float> sc((size_t)18 * c.max_kpts, 0.f);
+    std::vector<int> xy((size_t)K * c.max_kpts * 2, 0), cnt(K);
+    std::vector<float> sc((size_t)K * c.max_kpts, 0.f);
     int r = 0;
-    for (int t = 0; t < 18; ++t) {
+    for (int t = 0; t < K; ++t) {
         cnt[t] = type_counts[t];
         for (int i = 0; i < type_counts[t]; ++i, ++r) {
             const double x = kpts[r * 4], y = kpts[r * 4 + 1];
@@ -1172,13 +1283,13 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
     LAUNCH(h, KC_POST, launch_reset_ws(1, h->ws, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_xy, xy.data(), xy.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_score, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_count, cnt.data(), 18 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_count, cnt.data(), K * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the host vectors above go out of scope
     MapView v{d_paf, 0, (int64_t)W * NPc, (int64_t)NPc, 1, H, W};
     LAUNCH(h, KC_POST, launch_score_pairs(v, 1, 1, demo, h->ws, h->stream));
     LAUNCH(h, KC_POST, launch_match(1, h->ws, h->stream));
     LAUNCH(h, KC_POST, launch_assemble(1, h->ws, h->stream));
-    std::vector<int> kc(18);
+    std::vector<int> kc(K);
     std::vector<double> kout((size_t)std::max(total, 1) * 4);
     return fetch_results(h, 1, kc.data(), kout.data(), std::max(total, 1), pose_entries, cap_entries, n_entries);
 }
@@ -1216,8 +1327,8 @@ static int enqueue_poses_chunk(lwp_context* h, const float* d_in, int N, int H, 
         heat = MapView{cat + g.C, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
         paf = MapView{cat + g.C + g.NH, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
     }
-    LAUNCH(h, KC_POST, launch_find_peaks(heat, N, 18, ratio, ws, h->stream, &h->tune));
-    LAUNCH(h, KC_POST, launch_nms(N, 18, fh * ratio, ws, h->stream));
+    LAUNCH(h, KC_POST, launch_find_peaks(heat, N, ws.K, ratio, ws, h->stream, &h->tune));
+    LAUNCH(h, KC_POST, launch_nms(N, ws.K, fh * ratio, ws, h->stream, true));
     LAUNCH(h, KC_POST, launch_score_pairs(paf, N, ratio, demo, ws, h->stream));
     LAUNCH(h, KC_POST, launch_match(N, ws, h->stream));
     LAUNCH(h, KC_POST, launch_assemble(N, ws, h->stream));
@@ -1241,7 +1352,7 @@ static int prepare_poses(lwp_context* h, int N, int H, int W, int ratio) {
     int rc = check_frame_shape(h, N, H, W);
     if (rc) return rc;
     if (ratio != 4 && ratio != 8) return fail(h, LWP_ERR_ARG, "upsample ratio must be 4 or 8");
-    if (h->g.NH < 18 || h->g.NP < 38) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs");
+    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
     if (((int64_t)H / 8 + 1) * ratio > 65535 || ((int64_t)W / 8 + 1) * ratio > 65535) return fail(h, LWP_ERR_ARG, "map too large");
     HIP_TRY(h, hipSetDevice(h->device));
     rc = ensure_activations(h, frames_per_pass(h, N, H, W), H, W);
@@ -1261,7 +1372,7 @@ extern "C" int lwp_infer_poses_async(lwp_handle h, const float* in_device, int N
 
 extern "C" int lwp_fetch_poses(lwp_handle h, int* kpt_counts, double* kpts, int kpt_cap, double* entries, int entry_cap, int* n_entries) {
     if (!h || !kpt_counts || !kpts || !entries || !n_entries) return fail(h, LWP_ERR_ARG, "null argument");
-    if (h->last_N <= 0) return fail(h, LWP_ERR_STATE, "no pipeline run to fetch");
+    if (h->last_N <= 0 || !h->ws.result_block || h->ws.N < h->last_N) return fail(h, LWP_ERR_STATE, "no pipeline run to fetch");
     HIP_TRY(h, hipSetDevice(h->device));
     return fetch_results(h, h->last_N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
 }
@@ -1287,7 +1398,7 @@ extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, 
     int rc = check_frame_shape(h, N, H, W);
     if (rc) return rc;
     if (ratio != 4 && ratio != 8) return fail(h, LWP_ERR_ARG, "upsample ratio must be 4 or 8");
-    if (h->g.NH < 18 || h->g.NP < 38) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs");
+    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
     HIP_TRY(h, hipSetDevice(h->device));
     lwp_context::Slot& sl = h->slots[slot];
     if (sl.pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
@@ -1338,8 +1449,8 @@ extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, 
     const int64_t hw = (int64_t)fh * fw;
     MapView heat{sl.maps[0], (int64_t)g.NH * hw, (int64_t)fw, 1, hw, fh, fw};
     MapView paf{sl.maps[1], (int64_t)g.NP * hw, (int64_t)fw, 1, hw, fh, fw};
-    HIP_TRY(h, launch_find_peaks(heat, N, 18, ratio, sl.ws, h->post_stream, &h->tune));
-    HIP_TRY(h, launch_nms(N, 18, fh * ratio, sl.ws, h->post_stream));
+    HIP_TRY(h, launch_find_peaks(heat, N, sl.ws.K, ratio, sl.ws, h->post_stream, &h->tune));
+    HIP_TRY(h, launch_nms(N, sl.ws.K, fh * ratio, sl.ws, h->post_stream, true));
     HIP_TRY(h, launch_score_pairs(paf, N, ratio, demo, sl.ws, h->post_stream));
     HIP_TRY(h, launch_match(N, sl.ws, h->post_stream));
     HIP_TRY(h, launch_assemble(N, sl.ws, h->post_stream));
@@ -1368,7 +1479,7 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
         return fail(h, LWP_ERR_ARG, "bad argument");
     if (ratio != 4 && ratio != 8 && ratio != 1) return fail(h, LWP_ERR_ARG, "upsample ratio must be 1, 4 or 8");
     if (layout != LWP_LAYOUT_NCHW && layout != LWP_LAYOUT_NHWC) return fail(h, LWP_ERR_ARG, "layout must be LWP_LAYOUT_NCHW or LWP_LAYOUT_NHWC");
-    if (h->g.NH < 18 || h->g.NP < 38) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs");
+    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
     if ((int64_t)hs * ratio > 65535 || (int64_t)ws * ratio > 65535) return fail(h, LWP_ERR_ARG, "map too large");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_ws(h, N);
@@ -1392,8 +1503,8 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
         hv.ys = (int64_t)ws * h->g.NH; hv.xs = h->g.NH; hv.cs = 1;
         pv.ys = (int64_t)ws * h->g.NP; pv.xs = h->g.NP; pv.cs = 1;
     }
-    LAUNCH(h, KC_POST, launch_find_peaks(hv, N, 18, ratio, h->ws, h->stream, &h->tune));
-    LAUNCH(h, KC_POST, launch_nms(N, 18, hs * ratio, h->ws, h->stream));
+    LAUNCH(h, KC_POST, launch_find_peaks(hv, N, h->ws.K, ratio, h->ws, h->stream, &h->tune));
+    LAUNCH(h, KC_POST, launch_nms(N, h->ws.K, hs * ratio, h->ws, h->stream, true));
     LAUNCH(h, KC_POST, launch_score_pairs(pv, N, ratio, demo, h->ws, h->stream));
     LAUNCH(h, KC_POST, launch_match(N, h->ws, h->stream));
     LAUNCH(h, KC_POST, launch_assemble(N, h->ws, h->stream));
@@ -1458,6 +1569,7 @@ extern "C" int lwp_debug_frames_per_pass(lwp_handle h, int N, int H, int W) {
 
 extern "C" int lwp_debug_post_counts(lwp_handle h, int frame, int* peaks18, int* kpts18, int* candidates19, int* picked19) {
     if (!h || !peaks18 || !kpts18 || !candidates19 || !picked19) return fail(h, LWP_ERR_ARG, "null argument");
+    if (!h->skel.is_default) return fail(h, LWP_ERR_STATE, "custom skeleton: use lwp_debug_post_counts_ex");
     if (frame < 0 || frame >= h->ws.N) return fail(h, LWP_ERR_ARG, "frame outside the last batch");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1467,6 +1579,26 @@ extern "C" int lwp_debug_post_counts(lwp_handle h, int frame, int* peaks18, int*
     HIP_TRY(h, hipMemcpy(candidates19, h->ws.seen + frame * 37 + 18, 19 * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(picked19, h->ws.sel_count + frame * 19, 19 * sizeof(int), hipMemcpyDeviceToHost));
     return LWP_OK;
+}
+
+extern "C" int lwp_debug_post_counts_ex(lwp_handle h, int frame, int* peaks, int* kpts, int* candidates, int* picked, int K, int L) {
+    if (!h || !peaks || !kpts || !candidates || !picked) return fail(h, LWP_ERR_ARG, "null argument");
+    if (K != h->ws.K || L != h->ws.L) return fail(h, LWP_ERR_ARG, "K / L do not match the skeleton of the last run");
+    if (frame < 0 || frame >= h->ws.N) return fail(h, LWP_ERR_ARG, "frame outside the last batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->post_stream && h->post_stream != h->stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    HIP_TRY(h, hipMemcpy(peaks, h->ws.seen + (size_t)frame * (K + L), K * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(kpts, h->ws.kpt_count + (size_t)frame * K, K * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(candidates, h->ws.seen + (size_t)frame * (K + L) + K, L * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(picked, h->ws.sel_count + (size_t)frame * L, L * sizeof(int), hipMemcpyDeviceToHost));
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_post_generic(lwp_handle h) {
+    if (!h) return LWP_ERR_ARG;
+    if (h->ws.N > 0) return h->ws.generic;             // the form the handle's current workspace launches
+    return (!h->skel.is_default || h->post_generic) ? 1 : 0;
 }
 
 extern "C" int lwp_debug_f32_to_f16(const float* src, uint16_t* dst, int64_t n) {

@@ -219,31 +219,47 @@ struct MapView {          // a float32 map set addressed as base[n*ns + y*ys + x
 };
 struct PostCaps { int max_peaks = 2048, max_kpts = 128, max_conn = 4096, max_entries = 256; };
 
-struct PostWorkspace {    // device buffers, sized for (N frames, caps)
+// The grouping tables (modules/keypoints.py:5-8) and group_keypoints' options (:51).  K key-point types, L limbs, pose rows of
+// E doubles.  The default (COCO: 18 / 19 / 20, min_paf_score 0.05) runs the specialised kernels; any other skeleton, or
+// LWP_POST_GENERIC=1, runs the generic forms, which read the tables at run time.
+constexpr int kMaxSkelTypes = 64, kMaxSkelLimbs = 320, kMaxEntrySize = 256;
+struct Skeleton {
+    int K = 18, L = 19, E = 20;
+    double min_paf = 0.05;
+    std::vector<int> kpt, paf;      // [L][2] each
+    bool is_default = true;
+};
+Skeleton default_skeleton();
+
+struct PostWorkspace {    // device buffers, sized for (N frames, caps, skeleton)
     int N = 0;
     PostCaps caps;
-    int* peak_count = nullptr;      // [N*18]
-    uint32_t* peak_key = nullptr;   // [N*18*max_peaks]  (x << 16 | y)
-    float* peak_val = nullptr;      // [N*18*max_peaks]
-    int* kpt_count = nullptr;       // [N*18]
-    int* kpt_xy = nullptr;          // [N*18*max_kpts*2]
-    float* kpt_score = nullptr;     // [N*18*max_kpts]
-    int* conn_count = nullptr;      // [N*19]
-    int* conn_ij = nullptr;         // [N*19*max_conn]   (i << 16 | j)
-    double* conn_ratio = nullptr;   // [N*19*max_conn]
+    int K = 18, L = 19, E = 20;     // key-point types, limbs, doubles per pose row (18 / 19 / 20 by default)
+    int generic = 0;                // 1: the generic kernels (runtime tables below) instead of the COCO-specialised ones
+    double min_paf = 0.05;
+    const int* limbs = nullptr;     // [L][4]: type a, type b, PAF channel x, PAF channel y (generic kernels only)
+    int* peak_count = nullptr;      // [N*K]
+    uint32_t* peak_key = nullptr;   // [N*K*max_peaks]  (x << 16 | y)
+    float* peak_val = nullptr;      // [N*K*max_peaks]
+    int* kpt_count = nullptr;       // [N*K]
+    int* kpt_xy = nullptr;          // [N*K*max_kpts*2]
+    float* kpt_score = nullptr;     // [N*K*max_kpts]
+    int* conn_count = nullptr;      // [N*L]
+    int* conn_ij = nullptr;         // [N*L*max_conn]   (i << 16 | j)
+    double* conn_ratio = nullptr;   // [N*L*max_conn]
     unsigned long long* flags = nullptr;  // [N*4]  0: overflow bits (1 peaks, 2 kpts, 4 conns/entries),
                                           //        1: min order of a pair whose mid-point test failed,
                                           //        2: min order of a pair whose mid-point test passed
-    int* sel_count = nullptr;       // [N*19]  connections picked by the greedy matching
-    int* seen = nullptr;            // [N*37]  debug: peaks per type nms_kernel saw [18], candidates per limb match_kernel saw [19] (the counters themselves are re-armed by assemble_kernel)
-    int* sel_ij = nullptr;          // [N*19*max_kpts]
-    double* sel_r = nullptr;        // [N*19*max_kpts]
-    float* sel_sa = nullptr;        // [N*19*max_kpts] score of the connection's first key-point
-    float* sel_sb = nullptr;        // [N*19*max_kpts] score of its second key-point
-    double* entries_work = nullptr; // [N*max_entries*20] scratch when the entries do not fit LDS
-    double* entries = nullptr;      // [N*max_entries*20]
+    int* sel_count = nullptr;       // [N*L]  connections picked by the greedy matching
+    int* seen = nullptr;            // [N*(K+L)]  debug: peaks per type nms_kernel saw [K], candidates per limb match_kernel saw [L] (the counters themselves are re-armed by assemble_kernel)
+    int* sel_ij = nullptr;          // [N*L*max_kpts]
+    double* sel_r = nullptr;        // [N*L*max_kpts]
+    float* sel_sa = nullptr;        // [N*L*max_kpts] score of the connection's first key-point
+    float* sel_sb = nullptr;        // [N*L*max_kpts] score of its second key-point
+    double* entries_work = nullptr; // [N*max_entries*E] scratch when the entries do not fit LDS
+    double* entries = nullptr;      // [N*max_entries*E]
     int* n_entries = nullptr;       // [N]
-    double* kpts_out = nullptr;     // [N*18*max_kpts*4]
+    double* kpts_out = nullptr;     // [N*K*max_kpts*4]
     void* result_block = nullptr;   // flags, kpts_out, entries, kpt_count, n_entries: one allocation, one D2H copy
     size_t result_bytes = 0;
 };
@@ -253,7 +269,8 @@ hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);
 hipError_t launch_upsample(const MapView& src, int N, int C, int ratio, float* dst, hipStream_t s, const Tuning* tune = nullptr);
 // threshold + strict 4-neighbour maximum on the (virtually) up-sampled heat-maps; ratio == 1: src is already full-res
 hipError_t launch_find_peaks(const MapView& heat, int N, int ntypes, int ratio, PostWorkspace& ws, hipStream_t s, const Tuning* tune = nullptr);
-hipError_t launch_nms(int N, int ntypes, int Hfull, PostWorkspace& ws, hipStream_t s);
+// record_seen: the debug read-out of peaks per type (ntypes == ws.K)
+hipError_t launch_nms(int N, int ntypes, int Hfull, PostWorkspace& ws, hipStream_t s, bool record_seen = false);
 hipError_t launch_score_pairs(const MapView& paf, int N, int ratio, int demo, PostWorkspace& ws, hipStream_t s);
 hipError_t launch_match(int N, PostWorkspace& ws, hipStream_t s);
 hipError_t launch_assemble(int N, PostWorkspace& ws, hipStream_t s);

@@ -704,15 +704,16 @@ hipError_t launch_threshold_inplace(float* map, int64_t n, hipStream_t s) {
 
 __global__ void __launch_bounds__(256) reset_ws_kernel(int N, PostWorkspace ws) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < N * 18) { ws.peak_count[i] = 0; ws.kpt_count[i] = 0; }
-    if (i < N * 19) { ws.conn_count[i] = 0; ws.sel_count[i] = 0; }
+    if (i < N * ws.K) { ws.peak_count[i] = 0; ws.kpt_count[i] = 0; }
+    if (i < N * ws.L) { ws.conn_count[i] = 0; ws.sel_count[i] = 0; }
     if (i < N) {
         ws.n_entries[i] = 0;
         ws.flags[i * 4 + 0] = 0ull; ws.flags[i * 4 + 1] = ~0ull; ws.flags[i * 4 + 2] = ~0ull; ws.flags[i * 4 + 3] = 0ull;
     }
 }
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s) {
-    hipLaunchKernelGGL(reset_ws_kernel, dim3((N * 19 + 255) / 256), dim3(256), 0, s, N, ws);
+    const int per = ws.K > ws.L ? ws.K : ws.L;
+    hipLaunchKernelGGL(reset_ws_kernel, dim3((N * per + 255) / 256), dim3(256), 0, s, N, ws);
     return hipGetLastError();
 }
 
@@ -856,25 +857,30 @@ __global__ __launch_bounds__(256) void publish_results_kernel(int N, PostWorkspa
     const PostCaps& c = ws.caps;
     const size_t WN = (size_t)ws.N;
     char* q = host;
+    const int K = ws.K, E = ws.E;               // E doubles per row: E * 8 bytes, a multiple of 16 only for even E
     unsigned long long* h_fl = (unsigned long long*)q; q += WN * 4 * 8;
-    double2* h_k = (double2*)q; q += WN * 18 * c.max_kpts * 4 * 8;
-    double2* h_e = (double2*)q; q += WN * c.max_entries * 20 * 8;
-    int* h_cnt = (int*)q; q += WN * 18 * 4;
+    double2* h_k = (double2*)q; q += WN * K * c.max_kpts * 4 * 8;
+    double* h_e = (double*)q; q += WN * c.max_entries * E * 8;
+    int* h_cnt = (int*)q; q += WN * K * 4;
     int* h_ne = (int*)q;
     int total = 0;
-    for (int t = 0; t < 18; ++t) total += ws.kpt_count[f * 18 + t];
-    total = min(max(total, 0), 18 * c.max_kpts);
+    for (int t = 0; t < K; ++t) total += ws.kpt_count[f * K + t];
+    total = min(max(total, 0), K * c.max_kpts);
     const int ne = min(max(ws.n_entries[f], 0), c.max_entries);
     const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
     if (tid < 4) h_fl[f * 4 + tid] = ws.flags[f * 4 + tid];
-    if (tid >= 32 && tid < 32 + 18) h_cnt[f * 18 + tid - 32] = ws.kpt_count[f * 18 + tid - 32];
+    if (tid >= 128 && tid < 128 + K) h_cnt[f * K + tid - 128] = ws.kpt_count[f * K + tid - 128];
     if (tid == 64) h_ne[f] = ws.n_entries[f];
-    const double2* sk = (const double2*)(ws.kpts_out + (size_t)f * 18 * c.max_kpts * 4);
-    double2* dk = h_k + (size_t)f * 18 * c.max_kpts * 2;
+    const double2* sk = (const double2*)(ws.kpts_out + (size_t)f * K * c.max_kpts * 4);
+    double2* dk = h_k + (size_t)f * K * c.max_kpts * 2;
     for (int i = tid; i < total * 2; i += nth) dk[i] = sk[i];
-    const double2* se = (const double2*)(ws.entries + (size_t)f * c.max_entries * 20);
-    double2* de = h_e + (size_t)f * c.max_entries * 10;
-    for (int i = tid; i < ne * 10; i += nth) de[i] = se[i];
+    const double* se = ws.entries + (size_t)f * c.max_entries * E;
+    double* de = h_e + (size_t)f * c.max_entries * E;
+    if ((E & 1) == 0) {
+        for (int i = tid; i < ne * E / 2; i += nth) ((double2*)de)[i] = ((const double2*)se)[i];
+    } else {
+        for (int i = tid; i < ne * E; i += nth) de[i] = se[i];
+    }
 }
 hipError_t launch_publish(int N, PostWorkspace& ws, void* host_block, hipStream_t s) {
     hipLaunchKernelGGL(publish_results_kernel, dim3(4, N), dim3(256), 0, s, N, ws, (char*)host_block);
@@ -1116,14 +1122,14 @@ hipError_t launch_find_peaks(const MapView& heat, int N, int ntypes, int ratio, 
 // keypoints.py:30-47: candidates ordered by x then y; an unsuppressed candidate suppresses every later
 // one closer than 6 px.  One wavefront per (frame, type): bitonic sort in LDS, then the greedy pass
 // (sequential in i, the 64 lanes sweep the j window; sorted by x, so the window ends at x_j - x_i >= 6).
-__global__ void __launch_bounds__(64) nms_kernel(int ntypes, PostWorkspace ws) {
+__global__ void __launch_bounds__(64) nms_kernel(int ntypes, int seen_stride, PostWorkspace ws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char nms_smem[];
     const int slot = blockIdx.x;                 // n * ntypes + t
     const int lane = threadIdx.x;
     const int cap = ws.caps.max_peaks;
     int cnt = ws.peak_count[slot];
     const int frame = slot / ntypes;
-    if (lane == 0 && ntypes == 18) ws.seen[frame * 37 + slot % 18] = cnt;      // debug read-out (lwp_debug_post_counts)
+    if (lane == 0 && seen_stride) ws.seen[frame * seen_stride + slot % ntypes] = cnt;   // debug read-out (lwp_debug_post_counts)
     if (cnt > cap) {
         if (lane == 0) atomicOr(&ws.flags[frame * 4 + 0], 1ull);
         cnt = cap;
@@ -1227,11 +1233,12 @@ __global__ void __launch_bounds__(64) nms_kernel(int ntypes, PostWorkspace ws) {
     }
     if (lane == 0) ws.kpt_count[slot] = kept < kcap ? kept : kcap;
 }
-hipError_t launch_nms(int N, int ntypes, int /*Hfull*/, PostWorkspace& ws, hipStream_t s) {
+hipError_t launch_nms(int N, int ntypes, int /*Hfull*/, PostWorkspace& ws, hipStream_t s, bool record_seen) {
     int n2 = 64;
     while (n2 < ws.caps.max_peaks) n2 <<= 1;
     const size_t lds = (size_t)n2 * 12;
-    hipLaunchKernelGGL(nms_kernel, dim3(N * ntypes), dim3(64), lds, s, ntypes, ws);
+    const int seen_stride = record_seen ? ws.K + ws.L : 0;
+    hipLaunchKernelGGL(nms_kernel, dim3(N * ntypes), dim3(64), lds, s, ntypes, seen_stride, ws);
     return hipGetLastError();
 }
 
@@ -1245,19 +1252,23 @@ __constant__ int c_limb_paf[19][2] = {{12, 13}, {20, 21}, {14, 15}, {16, 17}, {2
 // 16 lanes per pair: sub-lanes 0..9 evaluate the 10 line-integral samples, sub-lane 10 the mid-point test, in
 // parallel (each is two bicubic PAF samples = 32 gathers); sub-lane 0 then adds the passed samples in k order,
 // exactly the reference's sequential sum.
+// GENERIC: the handle's skeleton (limb table, K / L strides, min_paf_score) from the workspace instead of the COCO constants.
 constexpr int SP_BLOCKS = 16;
+template <bool GENERIC>
 __global__ void __launch_bounds__(256) score_pairs_kernel(MapView paf, int ratio, int demo, PostWorkspace ws) {
     const int limb = blockIdx.y, n = blockIdx.z;
-    const int ta = c_limb_kpt[limb][0], tb = c_limb_kpt[limb][1];
-    const int c0 = c_limb_paf[limb][0], c1 = c_limb_paf[limb][1];
+    const int NT = GENERIC ? ws.K : 18, NL = GENERIC ? ws.L : 19;
+    const double min_paf = GENERIC ? ws.min_paf : 0.05;
+    const int ta = GENERIC ? ws.limbs[limb * 4 + 0] : c_limb_kpt[limb][0], tb = GENERIC ? ws.limbs[limb * 4 + 1] : c_limb_kpt[limb][1];
+    const int c0 = GENERIC ? ws.limbs[limb * 4 + 2] : c_limb_paf[limb][0], c1 = GENERIC ? ws.limbs[limb * 4 + 3] : c_limb_paf[limb][1];
     const int kcap = ws.caps.max_kpts;
-    const int na = ws.kpt_count[n * 18 + ta], nb = ws.kpt_count[n * 18 + tb];
+    const int na = ws.kpt_count[n * NT + ta], nb = ws.kpt_count[n * NT + tb];
     const int npairs = na * nb;
     if (npairs == 0) return;
     const int Hf = paf.h * ratio;
     const double height_n = (double)(Hf / 2);
-    const int* xa = ws.kpt_xy + (int64_t)(n * 18 + ta) * kcap * 2;
-    const int* xb = ws.kpt_xy + (int64_t)(n * 18 + tb) * kcap * 2;
+    const int* xa = ws.kpt_xy + (int64_t)(n * NT + ta) * kcap * 2;
+    const int* xb = ws.kpt_xy + (int64_t)(n * NT + tb) * kcap * 2;
     unsigned long long* fl = ws.flags + n * 4;
     // 12 lanes per pair (11 used: ten samples + the mid-point), five pairs per wave, lanes 60-63 idle: 92 % of the lanes carry a
     // sample (16 lanes per pair: 69 %)
@@ -1303,7 +1314,7 @@ __global__ void __launch_bounds__(256) score_pairs_kernel(MapView paf, int ratio
 #pragma unroll
         for (int k = 0; k < 10; ++k) {
             const double s = __shfl(sc, grp0 + k);
-            if (s > 0.05) { acc = __dadd_rn(acc, s); ++cnt; }
+            if (s > min_paf) { acc = __dadd_rn(acc, s); ++cnt; }
         }
         if (live && sub == 0) {
             const unsigned long long order = ((unsigned long long)limb << 32) | (unsigned)p;
@@ -1315,7 +1326,7 @@ __global__ void __launch_bounds__(256) score_pairs_kernel(MapView paf, int ratio
                 const double pen = __dadd_rn(height_n / norm, -1.0);
                 rat = __dadd_rn(rat, pen < 0.0 ? pen : 0.0);
                 if (rat > 0.0 && cnt >= 9) {
-                    const int slot = n * 19 + limb;
+                    const int slot = n * NL + limb;
                     const int pos = atomicAdd(&ws.conn_count[slot], 1);
                     if (pos < ws.caps.max_conn) {
                         ws.conn_ij[(int64_t)slot * ws.caps.max_conn + pos] = (i << 16) | j;
@@ -1329,7 +1340,8 @@ __global__ void __launch_bounds__(256) score_pairs_kernel(MapView paf, int ratio
     if (threadIdx.x < 2 && s_min[threadIdx.x] != ~0ull) atomicMin(&fl[1 + threadIdx.x], s_min[threadIdx.x]);
 }
 hipError_t launch_score_pairs(const MapView& paf, int N, int ratio, int demo, PostWorkspace& ws, hipStream_t s) {
-    hipLaunchKernelGGL(score_pairs_kernel, dim3(SP_BLOCKS, 19, N), dim3(256), 0, s, paf, ratio, demo, ws);
+    if (ws.generic) hipLaunchKernelGGL(score_pairs_kernel<true>, dim3(SP_BLOCKS, ws.L, N), dim3(256), 0, s, paf, ratio, demo, ws);
+    else hipLaunchKernelGGL(score_pairs_kernel<false>, dim3(SP_BLOCKS, 19, N), dim3(256), 0, s, paf, ratio, demo, ws);
     return hipGetLastError();
 }
 
@@ -1356,39 +1368,47 @@ __device__ __forceinline__ void sort64_candidates(double& r, int& ij, int lane) 
         }
     }
 }
+// type t's rows of all_keypoints (K,4) f64: x, y, score, id (keypoints.py:53); t < 64
+__device__ __forceinline__ void write_type_rows(const PostWorkspace& ws, int n, int t, int NT, int kcap, int lane) {
+    const int c_t = ws.kpt_count[n * NT + t];
+    int below = (lane < t) ? ws.kpt_count[n * NT + lane] : 0;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) below += __shfl_xor(below, d);
+    double* ko = ws.kpts_out + (int64_t)n * NT * kcap * 4;
+    for (int i = lane; i < c_t; i += 64) {
+        const int64_t src = (int64_t)(n * NT + t) * kcap + i;
+        double* row = ko + (int64_t)(below + i) * 4;
+        row[0] = (double)ws.kpt_xy[src * 2];
+        row[1] = (double)ws.kpt_xy[src * 2 + 1];
+        row[2] = (double)ws.kpt_score[src];
+        row[3] = (double)(below + i);
+    }
+}
+// GENERIC: limbs and strides from the handle's skeleton; the grid covers max(K, L) waves (wave t < K writes type t's rows).
+template <bool GENERIC>
 __global__ void __launch_bounds__(64) match_kernel(PostWorkspace ws, int rounds_ok) {
     __shared__ double s_r[MATCH_LDS];
     __shared__ int s_ij[MATCH_LDS];
     extern __shared__ __attribute__((aligned(16))) int used[];     // [2 * kcap]
     const int limb = blockIdx.x, n = blockIdx.y, lane = threadIdx.x;
-    const int slot = n * 19 + limb;
+    const int NT = GENERIC ? ws.K : 18, NL = GENERIC ? ws.L : 19;
+    if constexpr (GENERIC) {
+        if (limb < NT) write_type_rows(ws, n, limb, NT, ws.caps.max_kpts, lane);
+        if (limb >= NL) return;
+    }
+    const int slot = n * NL + limb;
     const int kcap = ws.caps.max_kpts, ccap = ws.caps.max_conn;
-    const int ta = c_limb_kpt[limb][0], tb = c_limb_kpt[limb][1];
-    const int na = ws.kpt_count[n * 18 + ta], nb = ws.kpt_count[n * 18 + tb];
+    const int ta = GENERIC ? ws.limbs[limb * 4 + 0] : c_limb_kpt[limb][0], tb = GENERIC ? ws.limbs[limb * 4 + 1] : c_limb_kpt[limb][1];
+    const int na = ws.kpt_count[n * NT + ta], nb = ws.kpt_count[n * NT + tb];
     int m = ws.conn_count[slot];
-    if (lane == 0) ws.seen[n * 37 + 18 + limb] = m;                            // debug read-out (lwp_debug_post_counts)
+    if (lane == 0) ws.seen[n * (NT + NL) + NT + limb] = m;                    // debug read-out (lwp_debug_post_counts)
     if (m > ccap) {
         if (lane == 0) atomicOr(&ws.flags[n * 4 + 0], 4ull);
         m = ccap;
     }
     const int* cij = ws.conn_ij + (int64_t)slot * ccap;
     const double* crat = ws.conn_ratio + (int64_t)slot * ccap;
-    if (limb < 18) {   // this wave also writes type `limb`'s rows of all_keypoints (K,4) f64: x, y, score, id (keypoints.py:53)
-        const int t = limb;
-        const int c_t = ws.kpt_count[n * 18 + t];
-        int below = (lane < t) ? ws.kpt_count[n * 18 + lane] : 0;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) below += __shfl_xor(below, d);
-        double* ko = ws.kpts_out + (int64_t)n * 18 * kcap * 4;
-        for (int i = lane; i < c_t; i += 64) {
-            const int64_t src = (int64_t)(n * 18 + t) * kcap + i;
-            double* row = ko + (int64_t)(below + i) * 4;
-            row[0] = (double)ws.kpt_xy[src * 2];
-            row[1] = (double)ws.kpt_xy[src * 2 + 1];
-            row[2] = (double)ws.kpt_score[src];
-            row[3] = (double)(below + i);
-        }
-    }
+    if (!GENERIC && limb < 18) write_type_rows(ws, n, limb, 18, kcap, lane);   // this wave also writes type `limb`'s key-point rows
     const int want = na < nb ? na : nb;
     int nsel = 0;
     int* sel_ij = ws.sel_ij + (int64_t)slot * kcap;
@@ -1413,8 +1433,8 @@ __global__ void __launch_bounds__(64) match_kernel(PostWorkspace ws, int rounds_
         }
         if (my_rank >= 0) {                                  // the picked lanes write themselves out (and gather their end points' scores) in parallel
             sel_ij[my_rank] = ij; sel_r[my_rank] = r;
-            ws.sel_sa[(int64_t)slot * kcap + my_rank] = ws.kpt_score[(int64_t)(n * 18 + ta) * kcap + (ij >> 16)];
-            ws.sel_sb[(int64_t)slot * kcap + my_rank] = ws.kpt_score[(int64_t)(n * 18 + tb) * kcap + (ij & 0xFFFF)];
+            ws.sel_sa[(int64_t)slot * kcap + my_rank] = ws.kpt_score[(int64_t)(n * NT + ta) * kcap + (ij >> 16)];
+            ws.sel_sb[(int64_t)slot * kcap + my_rank] = ws.kpt_score[(int64_t)(n * NT + tb) * kcap + (ij & 0xFFFF)];
         }
         if (lane == 0) ws.sel_count[slot] = nsel;
         return;
@@ -1486,8 +1506,8 @@ __global__ void __launch_bounds__(64) match_kernel(PostWorkspace ws, int rounds_
         sort64_candidates(r, ij, lane);
         if (lane < nsel) {
             sel_ij[lane] = ij; sel_r[lane] = r;
-            ws.sel_sa[(int64_t)slot * kcap + lane] = ws.kpt_score[(int64_t)(n * 18 + ta) * kcap + (ij >> 16)];
-            ws.sel_sb[(int64_t)slot * kcap + lane] = ws.kpt_score[(int64_t)(n * 18 + tb) * kcap + (ij & 0xFFFF)];
+            ws.sel_sa[(int64_t)slot * kcap + lane] = ws.kpt_score[(int64_t)(n * NT + ta) * kcap + (ij >> 16)];
+            ws.sel_sb[(int64_t)slot * kcap + lane] = ws.kpt_score[(int64_t)(n * NT + tb) * kcap + (ij & 0xFFFF)];
         }
         if (lane == 0) ws.sel_count[slot] = nsel;
         return;
@@ -1517,15 +1537,17 @@ __global__ void __launch_bounds__(64) match_kernel(PostWorkspace ws, int rounds_
     // scores of the two end points, gathered here (all limbs in parallel) so the sequential assembly needs no gathers
     for (int q = lane; q < nsel; q += 64) {
         const int ij = sel_ij[q];
-        ws.sel_sa[(int64_t)slot * kcap + q] = ws.kpt_score[(int64_t)(n * 18 + ta) * kcap + (ij >> 16)];
-        ws.sel_sb[(int64_t)slot * kcap + q] = ws.kpt_score[(int64_t)(n * 18 + tb) * kcap + (ij & 0xFFFF)];
+        ws.sel_sa[(int64_t)slot * kcap + q] = ws.kpt_score[(int64_t)(n * NT + ta) * kcap + (ij >> 16)];
+        ws.sel_sb[(int64_t)slot * kcap + q] = ws.kpt_score[(int64_t)(n * NT + tb) * kcap + (ij & 0xFFFF)];
     }
     if (lane == 0) ws.sel_count[slot] = nsel;
 }
 hipError_t launch_match(int N, PostWorkspace& ws, hipStream_t s) {
     // dynamic LDS: used [2][kcap] int (+ best [2][kcap] u64 + tie [2][kcap] int for the rounds form while that stays small)
     const int rounds_ok = (size_t)ws.caps.max_kpts * 32 <= 32 * 1024;
-    hipLaunchKernelGGL(match_kernel, dim3(19, N), dim3(64), (size_t)ws.caps.max_kpts * (rounds_ok ? 32 : 8), s, ws, rounds_ok);
+    const size_t lds = (size_t)ws.caps.max_kpts * (rounds_ok ? 32 : 8);
+    if (ws.generic) hipLaunchKernelGGL(match_kernel<true>, dim3(ws.K > ws.L ? ws.K : ws.L, N), dim3(64), lds, s, ws, rounds_ok);
+    else hipLaunchKernelGGL(match_kernel<false>, dim3(19, N), dim3(64), lds, s, ws, rounds_ok);
     return hipGetLastError();
 }
 
@@ -1772,7 +1794,129 @@ __global__ void __launch_bounds__(64) assemble_kernel(PostWorkspace ws) {
                           stamps[2] - stamps[1], stamps[3] - stamps[2], c.n_ent);
 #endif
 }
+// Generic form (any skeleton, LWP_POST_GENERIC=1): the same walk with the tables read at run time.  A runtime K cannot live in
+// per-lane register arrays, so the entries are rows in memory — entries 0..63 in LDS, entries >= 64 spilled to the frame's
+// `entries_work` rows in global memory — each row [ids: Kp int][score: f64][count: int][pad] (Kp = K rounded up to even).  Row e
+// is only ever touched by lane e % 64 (appends included), so no barrier is needed anywhere; the wave-uniform decisions (any
+// entry matched?) are ballots.  Limbs in table order, connections in pick order, the fill-a-missing-end rule for limb
+// indices 17 and 18 (keypoints.py:166-175) whatever the table, the same f64 sums in the same order as the reference.
+constexpr int ASM_LDS_ROWS = 64;
+__global__ void __launch_bounds__(64) assemble_generic_kernel(PostWorkspace ws) {
+    __shared__ __attribute__((aligned(16))) int rows_lds[ASM_LDS_ROWS * (kMaxSkelTypes + 4)];
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int K = ws.K, L = ws.L, E = ws.E;
+    const int kcap = ws.caps.max_kpts, ecap = ws.caps.max_entries;
+    const int Kp = (K + 1) & ~1, RW = Kp + 4;                   // words per row
+    int* rows_gl = (int*)(ws.entries_work + (int64_t)n * ecap * E);   // (ecap - 64) rows of RW words fit: RW * 4 <= E * 8
+    // (explicit LDS / global accesses: one flat pointer that may point to either miscompiles here)
+    auto rd = [&](int e, int k) -> int { return e < ASM_LDS_ROWS ? rows_lds[e * RW + k] : rows_gl[(int64_t)(e - ASM_LDS_ROWS) * RW + k]; };
+    auto wr = [&](int e, int k, int v) {
+        if (e < ASM_LDS_ROWS) rows_lds[e * RW + k] = v;
+        else rows_gl[(int64_t)(e - ASM_LDS_ROWS) * RW + k] = v;
+    };
+    auto rd_score = [&](int e) -> double { return __hiloint2double(rd(e, Kp + 1), rd(e, Kp)); };
+    auto wr_score = [&](int e, double v) { wr(e, Kp, __double2loint(v)); wr(e, Kp + 1, __double2hiint(v)); };
+    const int my_cnt = lane < K ? ws.kpt_count[n * K + lane] : 0;
+    int incl = my_cnt;                                          // inclusive prefix over the K <= 64 lanes
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    const int my_off = incl - my_cnt;                           // lane t: first all_keypoints row of type t
+    int n_ent = 0;                                              // uniform
+    bool overflow = false;
+    auto append = [&](int ta, int ida, int tb, int idb, int cnt, double score) {   // uniform arguments; tb < 0: one key-point
+        if (n_ent >= ecap) { overflow = true; return; }
+        if (lane == (n_ent & 63)) {
+            for (int k = 0; k < K; ++k) wr(n_ent, k, k == ta ? ida : (k == tb ? idb : -1));
+            wr_score(n_ent, score);
+            wr(n_ent, Kp + 2, cnt);
+        }
+        ++n_ent;
+    };
+    for (int l = 0; l < L; ++l) {
+        const int ta = __builtin_amdgcn_readfirstlane(ws.limbs[l * 4 + 0]), tb = __builtin_amdgcn_readfirstlane(ws.limbs[l * 4 + 1]);
+        const int na = __builtin_amdgcn_readlane(my_cnt, ta), nb = __builtin_amdgcn_readlane(my_cnt, tb);
+        const int offa = __builtin_amdgcn_readlane(my_off, ta), offb = __builtin_amdgcn_readlane(my_off, tb);
+        if (na == 0 && nb == 0) continue;
+        if (na == 0 || nb == 0) {                               // one-sided limb (keypoints.py:65-92)
+            const int t = na == 0 ? tb : ta, cnt = na == 0 ? nb : na, off = na == 0 ? offb : offa;
+            for (int i = 0; i < cnt; ++i) {
+                const int id = off + i;
+                bool found = false;
+                for (int e = lane; e < n_ent; e += 64) found |= rd(e, t) == id;
+                if (!__any(found)) append(t, id, -1, 0, 1, (double)ws.kpt_score[(int64_t)(n * K + t) * kcap + i]);
+            }
+            continue;
+        }
+        const int nsel = __builtin_amdgcn_readfirstlane(ws.sel_count[n * L + l]);
+        if (nsel == 0) continue;
+        const int64_t gsel = (int64_t)(n * L + l) * kcap;
+        if (l == 0) n_ent = 0;                                  // keypoints.py:159-165
+        for (int q = 0; q < nsel; ++q) {
+            const int ij = ws.sel_ij[gsel + q];
+            const double r = ws.sel_r[gsel + q];
+            const float sa = ws.sel_sa[gsel + q], sb = ws.sel_sb[gsel + q];
+            const int ia = offa + (ij >> 16), ib = offb + (ij & 0xFFFF);
+            if (l == 0) {
+                append(ta, ia, tb, ib, 2, __dadd_rn(__dadd_rn((double)sa, (double)sb), r));
+            } else if (l == 17 || l == 18) {                    // keypoints.py:166-175: only fill a missing end point
+                for (int e = lane; e < n_ent; e += 64) {
+                    const int xa = rd(e, ta), xb = rd(e, tb);
+                    if (xa == ia && xb == -1) wr(e, tb, ib);
+                    else if (xb == ib && xa == -1) wr(e, ta, ia);
+                }
+            } else {                                            // keypoints.py:176-193
+                const double add = __dadd_rn((double)sb, r);
+                bool hit = false;
+                for (int e = lane; e < n_ent; e += 64) {
+                    if (rd(e, ta) == ia) {
+                        wr(e, tb, ib);
+                        wr(e, Kp + 2, rd(e, Kp + 2) + 1);
+                        wr_score(e, __dadd_rn(rd_score(e), add));
+                        hit = true;
+                    }
+                }
+                if (!__any(hit)) append(ta, ia, tb, ib, 2, __dadd_rn(__dadd_rn((double)sa, (double)sb), r));
+            }
+        }
+    }
+    // filter (keypoints.py:195-199), order preserved; rows of E doubles: ids, -1 up to E - 3, score, count
+    double* out = ws.entries + (int64_t)n * ecap * E;
+    int kept = 0;
+    for (int e0 = 0; e0 < n_ent; e0 += 64) {
+        const int e = e0 + lane;
+        double sc = 0.0, cntd = 0.0;
+        bool keep = false;
+        if (e < n_ent) {
+            sc = rd_score(e);
+            cntd = (double)rd(e, Kp + 2);
+            keep = !(cntd < 3.0 || sc / cntd < 0.2);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            double* o = out + (int64_t)(kept + __popcll(mask & ((1ull << lane) - 1ull))) * E;
+            for (int k = 0; k < K; ++k) o[k] = (double)rd(e, k);
+            for (int k = K; k < E - 2; ++k) o[k] = -1.0;
+            o[E - 2] = sc;
+            o[E - 1] = cntd;
+        }
+        kept += __popcll(mask);
+    }
+    if (lane == 0) {
+        ws.n_entries[n] = kept;
+        if (overflow) atomicOr(&ws.flags[n * 4 + 0], 4ull);
+    }
+    for (int t = lane; t < K; t += 64) ws.peak_count[n * K + t] = 0;     // re-arm the append counters (as assemble_kernel)
+    for (int l = lane; l < L; l += 64) ws.conn_count[n * L + l] = 0;
+}
+
 hipError_t launch_assemble(int N, PostWorkspace& ws, hipStream_t s) {
+    if (ws.generic) {
+        hipLaunchKernelGGL(assemble_generic_kernel, dim3(N), dim3(64), 0, s, ws);
+        return hipGetLastError();
+    }
     const size_t ext_bytes = ws.caps.max_entries > 64 ? (size_t)(ws.caps.max_entries - 64) * 20 * 8 : 16;
     if (ext_bytes <= 60 * 1024) hipLaunchKernelGGL(assemble_kernel<true>, dim3(N), dim3(64), ext_bytes, s, ws);
     else hipLaunchKernelGGL(assemble_kernel<false>, dim3(N), dim3(64), 16, s, ws);

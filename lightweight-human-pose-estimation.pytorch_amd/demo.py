@@ -48,7 +48,16 @@ def poses_from_entries(pose_entries, all_keypoints, scale, pad, stride=8, upsamp
 
 
 def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, draw=False):
-    """Generator over frames: yields (img, current_poses).  No GUI (cv2.imshow/waitKey are out of scope)."""
+    """Generator over frames: yields (img, current_poses).  No GUI (cv2.imshow/waitKey are out of scope).
+    Pose / tracking are COCO-18 (modules/pose.py), as in the reference: an engine with a custom skeleton raises ValueError."""
+    K = net.engine.skeleton["num_kpt_types"]
+    if K != Pose.num_kpts:
+        raise ValueError("run_demo draws and tracks COCO poses of %d key-points; the engine's skeleton has %d key-point types "
+                         "(use infer_poses / poses_from_maps for custom skeletons)" % (Pose.num_kpts, K))
+    return _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw)
+
+
+def _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw):
     net = net.eval()
     stride, upsample_ratio = 8, 4
     previous_poses = []

@@ -67,6 +67,48 @@ class Engine(object):
     def import_weights(self, device_tensor):
         check(lib().lwp_weights_blob_import(self.h.ptr, device_tensor.data_ptr(), device_tensor.numel() * device_tensor.element_size()), self.h.ptr)
 
+    # ------------------------------------------------------------------ skeleton (modules/keypoints.py:5-8, group_keypoints' options)
+    def set_skeleton(self, limb_kpts, limb_pafs, num_kpt_types=None, pose_entry_size=None, min_paf_score=0.05):
+        """Grouping tables for a network trained on another key-point set: limb_kpts / limb_pafs are the L (a, b) key-point
+        type pairs and their PAF channel pairs, in grouping order.  num_kpt_types defaults to num_heatmaps - 1,
+        pose_entry_size to max(20, K + 2).  ``limb_kpts=None`` restores the COCO default.  Bad tables raise ValueError."""
+        if limb_kpts is None:
+            check(lib().lwp_set_skeleton(self.h.ptr, 0, 0, None, None, 0, 0.0), self.h.ptr)
+            self._skel = None
+            return
+        kp = np.ascontiguousarray(np.asarray(limb_kpts, dtype=np.int64).reshape(-1, 2), dtype=np.int32)
+        pf = np.ascontiguousarray(np.asarray(limb_pafs, dtype=np.int64).reshape(-1, 2), dtype=np.int32)
+        if len(kp) == 0:                       # (an empty table is an error, not the default: that is limb_kpts=None)
+            raise ValueError("a skeleton needs 1..320 limbs, got none")
+        if len(kp) != len(pf):
+            raise ValueError("limb_kpts and limb_pafs must have the same number of limbs (%d != %d)" % (len(kp), len(pf)))
+        K = int(self.NH - 1 if num_kpt_types is None else num_kpt_types)
+        E = int(max(20, K + 2) if pose_entry_size is None else pose_entry_size)
+        check(lib().lwp_set_skeleton(self.h.ptr, K, len(kp), kp.ctypes.data_as(C.POINTER(C.c_int)), pf.ctypes.data_as(C.POINTER(C.c_int)),
+                                     E, float(min_paf_score)), self.h.ptr)
+        self._skel = None
+
+    @property
+    def skeleton(self):
+        """dict(num_kpt_types, limb_kpts (L,2), limb_pafs (L,2), pose_entry_size, min_paf_score) of the handle."""
+        if getattr(self, "_skel", None) is None:
+            K, L, E, mp = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+            check(lib().lwp_get_skeleton(self.h.ptr, C.byref(K), C.byref(L), None, None, 0, C.byref(E), C.byref(mp)), self.h.ptr)
+            kp = np.zeros((L.value, 2), np.int32)
+            pf = np.zeros((L.value, 2), np.int32)
+            check(lib().lwp_get_skeleton(self.h.ptr, None, None, kp.ctypes.data_as(C.POINTER(C.c_int)), pf.ctypes.data_as(C.POINTER(C.c_int)),
+                                         L.value, None, None), self.h.ptr)
+            self._skel = dict(num_kpt_types=K.value, limb_kpts=kp, limb_pafs=pf, pose_entry_size=E.value, min_paf_score=mp.value)
+        return self._skel
+
+    @property
+    def post_generic(self):
+        """True when the generic grouping kernels run (custom skeleton, or LWP_POST_GENERIC=1 at creation) — debug."""
+        rc = lib().lwp_debug_post_generic(self.h.ptr)
+        if rc < 0:
+            check(rc, self.h.ptr)
+        return rc == 1
+
     def set_capacity(self, max_peaks=2048, max_kpts=128, max_conn=4096, max_entries=256):
         check(lib().lwp_set_capacity(self.h.ptr, max_peaks, max_kpts, max_conn, max_entries), self.h.ptr)
         self._caps = (max_peaks, max_kpts, max_conn, max_entries)
@@ -242,15 +284,19 @@ class Engine(object):
         return xs[:n.value], ys[:n.value], sc[:n.value]
 
     def group_keypoints(self, kpts, type_counts, pafs, demo):
-        """kpts (K,4) float64, type_counts (18,), pafs (H,W,38) float32 -> (P,20) float64."""
+        """kpts (n,4) float64, type_counts (K,), pafs (H,W,num_pafs) float32 -> (P,E) float64 (K / E: the skeleton's, 18 / 20 by
+        default)."""
         pafs = np.ascontiguousarray(pafs, dtype=np.float32)
         H, W, NPc = pafs.shape
         if NPc != self.NP:
             raise ValueError("pafs must have %d channels" % self.NP)
         kp = np.ascontiguousarray(kpts, dtype=np.float64).reshape(-1, 4)
         tc = np.ascontiguousarray(type_counts, dtype=np.int32)
+        sk = self.skeleton
+        if tc.shape != (sk["num_kpt_types"],):
+            raise ValueError("type_counts must have %d entries (the skeleton's key-point types)" % sk["num_kpt_types"])
         cap = self.caps[3]
-        ent = np.empty((cap, 20), np.float64)
+        ent = np.empty((cap, sk["pose_entry_size"]), np.float64)
         n = C.c_int()
         check(lib().lwp_group_keypoints(self.h.ptr, kp.ctypes.data, tc.ctypes.data_as(C.POINTER(C.c_int)), pafs.ctypes.data,
                                         MEM_HOST, H, W, 1 if demo else 0, ent.ctypes.data, cap, C.byref(n)), self.h.ptr)
@@ -258,9 +304,11 @@ class Engine(object):
 
     # ------------------------------------------------------------------ fused pipeline
     def _result_buffers(self, N):
-        kcap = 18 * self.caps[1]
+        sk = self.skeleton
+        K, E = sk["num_kpt_types"], sk["pose_entry_size"]
+        kcap = K * self.caps[1]
         ecap = self.caps[3]
-        return (np.zeros((N, 18), np.int32), np.zeros((N, kcap, 4), np.float64), np.zeros((N, ecap, 20), np.float64),
+        return (np.zeros((N, K), np.int32), np.zeros((N, kcap, 4), np.float64), np.zeros((N, ecap, E), np.float64),
                 np.zeros(N, np.int32), kcap, ecap)
 
     @staticmethod
@@ -273,7 +321,8 @@ class Engine(object):
 
     def infer_poses(self, x, upsample_ratio=4, demo=True):
         """x: (N,3,H,W) float32 (numpy / cpu tensor / cuda tensor), already normalised and padded.
-        Returns per frame (pose_entries (P,20) f64, all_keypoints (K,4) f64, type_counts (18,))."""
+        Returns per frame (pose_entries (P,E) f64, all_keypoints (n,4) f64, type_counts (K,)); K / E of the skeleton (18 / 20 by
+        default)."""
         torch = _torch()
         t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
         t = t.detach().to(torch.float32).contiguous()
@@ -338,10 +387,12 @@ class Engine(object):
         return n
 
     def post_counts(self, frame=0):
-        """(peaks per type before the NMS [18], key-points per type [18], scored connection candidates per limb [19], picked
-        connections per limb [19]) of one frame of the last infer_poses / poses_from_maps call (debug)."""
-        arrs = [(C.c_int * n)() for n in (18, 18, 19, 19)]
-        check(lib().lwp_debug_post_counts(self.h.ptr, frame, *arrs), self.h.ptr)
+        """(peaks per type before the NMS [K], key-points per type [K], scored connection candidates per limb [L], picked
+        connections per limb [L]) of one frame of the last infer_poses / poses_from_maps call (debug; 18 / 19 by default)."""
+        sk = self.skeleton
+        K, L = sk["num_kpt_types"], len(sk["limb_kpts"])
+        arrs = [(C.c_int * n)() for n in (K, K, L, L)]
+        check(lib().lwp_debug_post_counts_ex(self.h.ptr, frame, *arrs, K, L), self.h.ptr)
         return tuple(np.array(list(a), dtype=np.int64) for a in arrs)
 
     def layer_variant(self, layer_index):

@@ -162,6 +162,57 @@ def make_pose_maps(n_people, h=46, w=82, seed=0, drop_prob=0.1, noise=0.01):
     return heat.astype(np.float32), paf.astype(np.float32), people
 
 
+def make_skeleton_maps(canon, limb_kpts, limb_pafs, num_pafs, n_people, h=46, w=82, seed=0, drop_prob=0.1, noise=0.01):
+    """make_pose_maps for any skeleton: ``canon`` (K,2) unit coordinates of the K key-point types (x right, y down, about
+    the COCO pose's extent), ``limb_kpts`` / ``limb_pafs`` the L (a, b) type pairs and their PAF channel pairs.  Returns
+    low-resolution heat-maps (K+1,h,w) (the last one background) and PAFs (num_pafs,h,w), float32, and the people ((K,2)
+    arrays of low-res (x, y), NaN where dropped).  Limbs whose channels repeat average their fields, as make_pose_maps does."""
+    canon = np.asarray(canon, dtype=np.float64)
+    K = len(canon)
+    s = fnv1a64("skeletonmaps", seed)
+    r = uniform((max(n_people, 1), 4 + 3 * K), s).astype(np.float64)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    heat = np.zeros((K + 1, h, w), np.float64)
+    paf = np.zeros((num_pafs, h, w), np.float64)
+    cnt = np.zeros((num_pafs, h, w), np.float64)
+    people = []
+    for i in range(n_people):
+        scale = (0.10 + 0.12 * r[i, 0]) * h
+        cx = (0.08 + 0.84 * r[i, 1]) * w
+        cy = (0.15 + 0.25 * r[i, 2]) * h
+        lean = (r[i, 3] - 0.5) * 0.5
+        pts = canon * scale
+        pts = np.stack([pts[:, 0] + lean * pts[:, 1] + cx, pts[:, 1] + cy], 1)
+        pts += (r[i, 4:4 + 2 * K].reshape(K, 2) - 0.5) * 0.15 * scale
+        keep = r[i, 4 + 2 * K:4 + 3 * K] > drop_prob
+        keep &= (pts[:, 0] > 1) & (pts[:, 0] < w - 2) & (pts[:, 1] > 1) & (pts[:, 1] < h - 2)
+        pts[~keep] = np.nan
+        people.append(pts)
+        for k in range(K):
+            if keep[k]:
+                g = np.exp(-((xx - pts[k, 0]) ** 2 + (yy - pts[k, 1]) ** 2) / (2 * 0.9 ** 2))
+                heat[k] = np.maximum(heat[k], g)
+        for (a, b), (c0, c1) in zip(limb_kpts, limb_pafs):
+            if not (keep[a] and keep[b]):
+                continue
+            v = pts[b] - pts[a]
+            n = np.hypot(*v)
+            if n < 1e-6:
+                continue
+            u = v / n
+            t = (xx - pts[a, 0]) * u[0] + (yy - pts[a, 1]) * u[1]
+            d = np.abs((xx - pts[a, 0]) * u[1] - (yy - pts[a, 1]) * u[0])
+            m = (t >= -0.5) & (t <= n + 0.5) & (d <= 1.0)
+            paf[c0][m] += u[0]; paf[c1][m] += u[1]
+            cnt[c0][m] += 1; cnt[c1][m] += 1
+    paf = np.where(cnt > 0, paf / np.maximum(cnt, 1), 0.0)
+    heat[K] = 1.0 - heat[:K].max(0)
+    nz = uniform((K + 1 + num_pafs, h, w), s ^ 0xABCDEF).astype(np.float64) - 0.5
+    heat = heat + noise * nz[:K + 1]
+    paf = paf + noise * nz[K + 1:]
+    return heat.astype(np.float32), paf.astype(np.float32), people
+
+
 def calibrate_heads(sd, heat_raw, paf_raw, num_refinement_stages=1, peaks_per_channel=10, score_scale=0.25,
                     paf_mean=0.3, paf_std=0.1):
     """Affine re-parameterisation of the LAST stage's final 1x1 convs so that random-init maps look like a

@@ -90,8 +90,9 @@ def infer_batch(net, imgs, scales, base_height, stride, pad_value=(0, 0, 0), img
 
 
 def poses_batch(net, avg_heatmaps, avg_pafs):
-    """val.py:129-134 for a batch on the device: extract_keypoints over the 18 key-point maps + group_keypoints
-    (demo=False rounding) -> per frame (pose_entries (P,20), all_keypoints (K,4), type_counts)."""
+    """val.py:129-134 for a batch on the device: extract_keypoints over the engine skeleton's K key-point maps + group_keypoints
+    (demo=False rounding) -> per frame (pose_entries (P,E), all_keypoints (n,4), type_counts (K,)); K / E are 18 / 20 unless
+    Engine.set_skeleton chose a custom skeleton."""
     return net.engine.poses_from_maps(avg_heatmaps, avg_pafs, 1, demo=False, layout="NHWC")
 
 
