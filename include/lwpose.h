@@ -230,6 +230,54 @@ int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, int H, int 
 int lwp_pipeline_fetch(lwp_handle h, int slot, int* kpt_counts, double* kpts, int kpt_cap,
                        double* entries, int entry_cap, int* n_entries);
 
+/* ---- pose tail on the device: replaces the rest of run_demo's loop body (demo.py:101-118: map the key-points back to image
+ *      coordinates, one Pose per entry, modules/pose.py:65-118 track_poses with its 1-Euro smoothing).  OFF by default: with
+ *      mode 0 every export launches, computes and returns exactly what it did before.  With mode != 0 two more kernels follow the
+ *      grouping kernels of lwp_infer_poses / lwp_infer_poses_async / lwp_poses_from_maps / lwp_pipeline_submit on the same
+ *      stream, and their results travel in the same result block; lwp_get_poses reads them on the host after the fetch.
+ *      (lwp_group_keypoints has no tail: it returns entries only.)
+ *      lwp_set_tracking: mode 0 off, 1 pose rows only (ids -1), 2 lanes (frame f of a batch is the next frame of lane f),
+ *      3 sequence (the N frames of a batch are N consecutive frames of lane 0; same results as N batch-1 calls).  A lane holds
+ *      the previous frame's poses, their ids and filter states and its own id counter, on the device.  match_threshold:
+ *      track_poses' `threshold` (3 in the reference; any int, <= 0 keeps the reference's corner case).  similarity_threshold:
+ *      get_similarity's (0.5), must lie inside (0, 1); the kernel decides exp(-q) > t as q < -ln t with -ln t computed here once.
+ *      smooth != 0: OneEuroFilter(freq 15, mincutoff 1, beta 0.05, dcutoff 1) per coordinate.  sigmas: K float32 values as
+ *      Pose.sigmas holds them (already divided by 10); NULL = the COCO table, an error unless K is 18 (n_sigmas 0 or 18);
+ *      otherwise n_sigmas must equal K.  The argument checks need no GPU and run with h == NULL against K = 18 (message via
+ *      lwp_last_error(NULL)).  Refused with LWP_ERR_STATE while a pipeline slot is pending.  Every call clears all lanes (ids
+ *      start at 0 again) and discards unfetched results; the workspaces are kept unless the tail goes on or off.  While
+ *      tracking is on (mode 2 / 3) the serial exports are refused with LWP_ERR_STATE as long as a pipeline slot is pending (the
+ *      lanes belong to one stream at a time), and EVERY pose-producing pass advances the lanes, lwp_time_pipeline and
+ *      lwp_profile_launches / lwp_profile_classes included (one step per repetition).  A NaN confidence ranks last (as -inf).  lwp_set_skeleton and lwp_set_capacity clear all lanes too;
+ *      lwp_set_skeleton with another K turns tracking off (the sigma table belonged to the old K).  The tail holds at most
+ *      256 poses per frame: with max_pose_entries above 256 a pose-producing call fails with LWP_ERR_ARG while it is on.
+ *      Pose rows: for entry n and type k, -1 if the entry column is -1.0, else (int)((x * stride / upsample_ratio - pad_left) /
+ *      scale) (y with pad_top), float64, truncation toward zero (values beyond int32 saturate; Python would raise); confidence =
+ *      entry column E - 2 (the reference writes the literal 18, which is E - 2 for its skeleton); poses keep entry order;
+ *      bbox = (min_x, min_y, max_x - min_x + 1, max_y - min_y + 1) over key-points with x != -1, (0,0,0,0) if none.
+ *      lwp_set_unmap: stride / scale / pad as lwp_preprocess_dims returns them (defaults 8, 1.0, 0, 0); used by the following calls.
+ *      lwp_reset_tracking: lane -1 = all lanes (and lanes created later); the lane forgets its poses and gives next_id out first.
+ *      lwp_get_poses: slot -1 = the last lwp_infer_poses / lwp_poses_from_maps / lwp_fetch_poses, 0 / 1 = a FETCHED pipeline
+ *      slot.  n_poses[N]; keypoints N x pose_cap x K x 2 int32; confidence N x pose_cap float64; bbox N x pose_cap x 4 int32;
+ *      ids N x pose_cap int32 (-1 in mode 1); last_ids (may be NULL) [N]: the lane's last given id after that frame (-1 in
+ *      mode 1).  LWP_ERR_STATE if the tail was off for that run; LWP_ERR_CAPACITY if pose_cap is below a frame's pose count.
+ *      lwp_track_poses: one tracking step of `lane` on poses the caller supplies (n x K x 2 int32 key-points, -1 = missing; n
+ *      float64 confidences, which must be finite: LWP_ERR_ARG otherwise), on the same kernels; outputs n x K x 2, n x 4, n, and
+ *      the lane's last given id.  Needs mode 2 or 3.  It uses frame 0 of the serial workspace: the results of an
+ *      lwp_infer_poses_async run not yet fetched are discarded (lwp_fetch_poses: LWP_ERR_STATE), and lwp_get_poses(-1) has
+ *      nothing to return until the next pose-producing call.
+ *      near_count (may be NULL), and lwp_debug_tracking_near per frame of a fetched run: similarity decisions whose q lay within
+ *      1e-12 (relative) of -ln t, i.e. where the device's compare could differ from NumPy's exp(-q) > t. */
+int lwp_set_tracking(lwp_handle h, int mode, int match_threshold, double similarity_threshold, int smooth,
+                     const float* sigmas, int n_sigmas);
+int lwp_set_unmap(lwp_handle h, int stride, double scale, int pad_top, int pad_left);
+int lwp_reset_tracking(lwp_handle h, int lane, int next_id);
+int lwp_get_poses(lwp_handle h, int slot, int* n_poses, int* keypoints, double* confidence, int* bbox, int* ids,
+                  int* last_ids, int pose_cap);
+int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoints, const double* confidence, int* out_keypoints,
+                    int* out_bbox, int* out_ids, int* last_id, unsigned* near_count);
+int lwp_debug_tracking_near(lwp_handle h, int slot, unsigned* counts, int cap);
+
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */
 int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio,

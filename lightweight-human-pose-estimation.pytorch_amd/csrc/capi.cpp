@@ -64,9 +64,17 @@ struct lwp_context {
         void* h_stage = nullptr; size_t h_stage_bytes = 0;
         hipEvent_t ev_maps = nullptr, ev_done = nullptr;
         int N = 0;
+        int tail_N = 0;                    // frames with pose rows in h_stage (0: submitted with the tail off)
         bool pending = false;
     } slots[2];
     hipStream_t post_stream = nullptr;
+    // pose tail (lwp_set_tracking): parameters, the lanes' device state, (2 sigma)^2 of the K key-point types
+    TailParams tail;
+    TailState tst;
+    float* d_vars = nullptr;
+    int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
+    int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
+    bool run_has_tail = false;             // the tail kernels ran behind the grouping whose results h->ws holds
     // caller-stream ordering (lwp_set_stream): work the caller queued on ITS stream is waited for with an event (no host
     // block), and the caller's stream is made to wait for the handle's results where they stay on the device
     hipStream_t caller_stream = nullptr;
@@ -253,6 +261,15 @@ static void free_ws_obj(PostWorkspace& w) {
     w = PostWorkspace();
 }
 static void free_ws(lwp_context* h) { free_ws_obj(h->ws); }
+static void free_tail_state(lwp_context* h, bool drop_results = true) {
+    TailState& t = h->tst;
+    void* ptrs[] = {t.hdr, t.kp, t.bbox, t.ids, t.f_xprev, t.f_init, t.f_dx, t.f_x, t.sim};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    t = TailState();
+    if (!drop_results) return;
+    h->stage_tail_N = 0;
+    for (auto& sl : h->slots) sl.tail_N = 0;
+}
 
 extern "C" int lwp_destroy(lwp_handle h) {
     if (!h) return LWP_OK;
@@ -276,6 +293,8 @@ extern "C" int lwp_destroy(lwp_handle h) {
     if (h->d_blob) (void)hipFree(h->d_blob);
     if (h->d_zeros) (void)hipFree(h->d_zeros);
     if (h->d_limbs) (void)hipFree(h->d_limbs);
+    if (h->d_vars) (void)hipFree(h->d_vars);
+    free_tail_state(h);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     free_ws(h);
     if (h->post_stream) (void)hipStreamSynchronize(h->post_stream);
@@ -304,6 +323,8 @@ extern "C" int lwp_set_capacity(lwp_handle h, int max_peaks, int max_kpts, int m
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_ws(h);
     for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    free_tail_state(h);                                // the lanes' state is sized by max_entries: every lane starts over
     h->last_N = 0;                                     // the results of an unfetched lwp_infer_poses_async went with the workspace
     h->caps.max_peaks = max_peaks; h->caps.max_kpts = max_kpts; h->caps.max_conn = max_conn; h->caps.max_entries = max_entries;
     return LWP_OK;
@@ -356,6 +377,8 @@ extern "C" int lwp_set_skeleton(lwp_handle h, int num_kpt_types, int num_limbs, 
     HIP_TRY(h, hipMemcpy(h->d_limbs, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
     free_ws(h);                                        // every workspace is sized by K / L / E: re-allocated lazily
     for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    free_tail_state(h);                                // the lanes' state is sized by K: every lane starts over
+    if (h->tail.mode >= 2 && sk.K != h->skel.K) h->tail.mode = 0;   // the sigma table was given for the old K: tracking is off until lwp_set_tracking
     h->last_N = 0;                                     // the results of an unfetched lwp_infer_poses_async went with the workspace
     h->skel = sk;
     return LWP_OK;
@@ -479,7 +502,9 @@ static bool skeleton_fits(const lwp_context* h) {
 }
 
 static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t stream) {
-    if (w.N >= N && w.peak_count) return LWP_OK;
+    if (w.N >= N && w.peak_count && (w.tail != 0) == (h->tail.mode != 0)) return LWP_OK;
+    if (h->tail.mode && h->caps.max_entries > kTailMaxPoses)
+        return fail(h, LWP_ERR_ARG, "the pose tail (lwp_set_tracking) holds at most 256 poses per frame: lower max_pose_entries or turn it off");
     HIP_TRY(h, hipStreamSynchronize(stream));
     free_ws_obj(w);
     w.caps = h->caps;
@@ -502,6 +527,10 @@ static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t st
         const size_t b_fl = (size_t)N * 4 * 8, b_k = (size_t)N * K * c.max_kpts * 4 * 8, b_e = (size_t)N * c.max_entries * E * 8;
         const size_t b_cnt = (size_t)N * K * 4, b_ne = (size_t)N * 4;
         w.result_bytes = b_fl + b_k + b_e + b_cnt + b_ne;
+        // pose tail: [t_conf N*P f64][t_bbox N*P*4 i32][t_kp N*P*K*2 i32][t_ids N*P i32][t_n N][t_near N][t_last N], 16-byte aligned
+        const size_t P = (size_t)c.max_entries, NP_ = (size_t)N * P;
+        const size_t tail_off = (w.result_bytes + 15) & ~(size_t)15;
+        if (h->tail.mode) w.result_bytes = tail_off + NP_ * 8 + NP_ * 16 + NP_ * K * 8 + NP_ * 4 + (size_t)N * 12;
         HIP_TRY(h, hipMalloc((void**)&w.result_block, w.result_bytes));
         char* q = (char*)w.result_block;
         w.flags = (unsigned long long*)q; q += b_fl;
@@ -509,6 +538,19 @@ static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t st
         w.entries = (double*)q; q += b_e;
         w.kpt_count = (int*)q; q += b_cnt;
         w.n_entries = (int*)q;
+        w.tail = h->tail.mode ? 1 : 0;
+        if (w.tail) {
+            w.tail_off = tail_off;
+            q = (char*)w.result_block + tail_off;
+            w.t_conf = (double*)q; q += NP_ * 8;
+            w.t_bbox = (int*)q; q += NP_ * 16;
+            w.t_kp = (int*)q; q += NP_ * K * 8;
+            w.t_ids = (int*)q; q += NP_ * 4;
+            w.t_n = (int*)q; q += (size_t)N * 4;
+            w.t_near = (unsigned*)q; q += (size_t)N * 4;
+            w.t_last = (int*)q;
+            HIP_TRY(h, hipMemsetAsync((char*)w.result_block + tail_off, 0, w.result_bytes - tail_off, stream));
+        }
     }
     WS_ALLOC(entries_work, (size_t)N * c.max_entries * E, double);
     WS_ALLOC(sel_count, N * L, int);
@@ -525,6 +567,7 @@ static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t st
 static int ensure_ws(lwp_context* h, int N) { return ensure_ws_obj(h, h->ws, N, h->stream); }
 
 static int ensure_host_stage(lwp_context* h, size_t bytes) {
+    h->stage_tail_N = 0;                               // every user of h_stage comes through here: the pose rows in it are gone
     if (h->h_stage_bytes >= bytes) return LWP_OK;
     if (h->h_stage) HIP_TRY(h, hipHostFree(h->h_stage));
     h->h_stage = nullptr; h->h_stage_bytes = 0;
@@ -604,6 +647,11 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
     v.sel_sa += f * L * c.max_kpts; v.sel_sb += f * L * c.max_kpts;
     v.entries_work += f * c.max_entries * E; v.entries += f * c.max_entries * E;
     v.n_entries += f; v.kpts_out += f * K * c.max_kpts * 4;
+    if (w.tail) {
+        const size_t P = (size_t)c.max_entries;
+        v.t_conf += f * P; v.t_bbox += f * P * 4; v.t_kp += f * P * K * 2; v.t_ids += f * P;
+        v.t_n += f; v.t_near += f; v.t_last += f;
+    }
     return v;
 }
 
@@ -1207,9 +1255,12 @@ static int parse_results(lwp_context* h, const PostWorkspace& ws, const void* ho
 static int fetch_results(lwp_context* h, int N, int* kpt_counts, double* kpts, int kpt_cap, double* entries, int entry_cap, int* n_entries) {
     int rc = ensure_host_stage(h, h->ws.result_bytes + 64);
     if (rc) return rc;
+    h->stage_tail_N = 0;
     HIP_TRY(h, launch_publish(N, h->ws, h->h_stage, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return parse_results(h, h->ws, h->h_stage, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
+    rc = parse_results(h, h->ws, h->h_stage, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
+    if (rc == LWP_OK && h->ws.tail && h->run_has_tail) h->stage_tail_N = N;
+    return rc;
 }
 
 static int parse_results(lwp_context* h, const PostWorkspace& ws, const void* host_block, int N, int* kpt_counts, double* kpts,
@@ -1280,6 +1331,7 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
         HIP_TRY(h, hipMemcpyAsync(h->d_tmp2, pafs, pb, hipMemcpyHostToDevice, h->stream));
         d_paf = h->d_tmp2;
     }
+    h->run_has_tail = false;                           // entries only: lwp_get_poses has nothing to return after this call
     LAUNCH(h, KC_POST, launch_reset_ws(1, h->ws, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_xy, xy.data(), xy.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_score, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -1292,6 +1344,52 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
     std::vector<int> kc(K);
     std::vector<double> kout((size_t)std::max(total, 1) * 4);
     return fetch_results(h, 1, kc.data(), kout.data(), std::max(total, 1), pose_entries, cap_entries, n_entries);
+}
+
+// ---------------------------------------------------------------------------------------------- pose tail
+// device state of `lanes` lanes (grow-only; the lanes that exist keep their state)
+static int ensure_tail_state(lwp_context* h, int lanes) {
+    TailState& t = h->tst;
+    const int P = h->caps.max_entries, K = h->skel.K;
+    if (t.lanes >= lanes && t.P == P && t.K == K) return LWP_OK;
+    if (P > kTailMaxPoses) return fail(h, LWP_ERR_ARG, "the pose tail (lwp_set_tracking) holds at most 256 poses per frame: lower max_pose_entries");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    const int keep = (t.P == P && t.K == K) ? t.lanes : 0;
+    TailState n;
+    n.lanes = std::max(lanes, keep); n.P = P; n.K = K; n.vars = h->d_vars;
+    const size_t L = (size_t)n.lanes, PK2 = (size_t)P * K * 2;
+    struct Arr { void** dst; void* src; size_t per_lane; };
+    Arr arrs[] = {{(void**)&n.hdr, t.hdr, sizeof(int4)}, {(void**)&n.kp, t.kp, 2 * PK2 * 4}, {(void**)&n.bbox, t.bbox, (size_t)2 * P * 16},
+                  {(void**)&n.ids, t.ids, (size_t)2 * P * 4}, {(void**)&n.f_xprev, t.f_xprev, 2 * PK2 * 4}, {(void**)&n.f_init, t.f_init, 2 * PK2 * 4},
+                  {(void**)&n.f_dx, t.f_dx, 2 * PK2 * 8}, {(void**)&n.f_x, t.f_x, 2 * PK2 * 8}, {(void**)&n.sim, t.sim, (size_t)P * P}};
+    for (Arr& a : arrs) {
+        HIP_TRY(h, hipMalloc(a.dst, L * a.per_lane));
+        HIP_TRY(h, hipMemset(*a.dst, 0, L * a.per_lane));
+        if (keep && a.src) HIP_TRY(h, hipMemcpy(*a.dst, a.src, (size_t)keep * a.per_lane, hipMemcpyDeviceToDevice));
+    }
+    free_tail_state(h, false);
+    h->tst = n;
+    HIP_TRY(h, launch_tail_reset(h->tst, keep, n.lanes - keep, h->tail_first_id, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+// the tail's launches for the N frames of `ws`, behind assemble_kernel on the same stream
+static int enqueue_tail(lwp_context* h, PostWorkspace& ws, int N, int ratio, hipStream_t s, bool profiled) {
+    if (profiled) h->run_has_tail = ws.tail != 0;      // (the serial path; a pipeline slot keeps its own tail_N)
+    if (!ws.tail) return LWP_OK;
+    TailParams p = h->tail;
+    p.ratio = ratio;
+    if (p.mode >= 2) { int rc = ensure_tail_state(h, p.mode == 2 ? N : 1); if (rc) return rc; }
+    if (profiled) {
+        LAUNCH(h, KC_POST, launch_tail_rows(N, ws, p, 0, s));
+        if (p.mode >= 2) LAUNCH(h, KC_POST, launch_tail_track(N, ws, h->tst, p, 0, s));
+    } else {
+        HIP_TRY(h, launch_tail_rows(N, ws, p, 0, s));
+        if (p.mode >= 2) HIP_TRY(h, launch_tail_track(N, ws, h->tst, p, 0, s));
+    }
+    return LWP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- fused pipeline
@@ -1345,11 +1443,21 @@ static int enqueue_poses(lwp_context* h, const float* d_in, int N, int H, int W,
         int rc = enqueue_poses_chunk(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, ratio, demo, with_post, ws_frames(h->ws, f0));
         if (rc) return rc;
     }
+    if (!with_post) { h->run_has_tail = false; return LWP_OK; }
+    return enqueue_tail(h, h->ws, N, ratio, h->stream, true);
+}
+
+// the lanes' state belongs to one stream at a time: the serial path runs the tail on the main stream, a pipeline slot on the post stream
+static int tail_serial_allowed(lwp_context* h) {
+    if (h->tail.mode >= 2)
+        for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "tracking is on and a pipeline slot is pending: fetch it first");
     return LWP_OK;
 }
 
 static int prepare_poses(lwp_context* h, int N, int H, int W, int ratio) {
     int rc = check_frame_shape(h, N, H, W);
+    if (rc) return rc;
+    rc = tail_serial_allowed(h);
     if (rc) return rc;
     if (ratio != 4 && ratio != 8) return fail(h, LWP_ERR_ARG, "upsample ratio must be 4 or 8");
     if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
@@ -1454,6 +1562,9 @@ extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, 
     HIP_TRY(h, launch_score_pairs(paf, N, ratio, demo, sl.ws, h->post_stream));
     HIP_TRY(h, launch_match(N, sl.ws, h->post_stream));
     HIP_TRY(h, launch_assemble(N, sl.ws, h->post_stream));
+    rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream, false);
+    if (rc) return rc;
+    sl.tail_N = sl.ws.tail ? N : 0;
     HIP_TRY(h, launch_publish(N, sl.ws, sl.h_stage, h->post_stream));
     HIP_TRY(h, hipEventRecord(sl.ev_done, h->post_stream));
     sl.pending = true;
@@ -1482,7 +1593,9 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
     if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
     if ((int64_t)hs * ratio > 65535 || (int64_t)ws * ratio > 65535) return fail(h, LWP_ERR_ARG, "map too large");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_ws(h, N);
+    int rc = tail_serial_allowed(h);
+    if (rc) return rc;
+    rc = ensure_ws(h, N);
     if (rc) return rc;
     if (mem == LWP_MEM_DEVICE) { rc = order_in(h); if (rc) return rc; }
     const size_t hb = (size_t)N * h->g.NH * hs * ws * sizeof(float), pb = (size_t)N * h->g.NP * hs * ws * sizeof(float);
@@ -1508,8 +1621,191 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
     LAUNCH(h, KC_POST, launch_score_pairs(pv, N, ratio, demo, h->ws, h->stream));
     LAUNCH(h, KC_POST, launch_match(N, h->ws, h->stream));
     LAUNCH(h, KC_POST, launch_assemble(N, h->ws, h->stream));
+    rc = enqueue_tail(h, h->ws, N, ratio, h->stream, true);
+    if (rc) return rc;
     h->last_N = N;
     return fetch_results(h, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
+}
+
+// ---------------------------------------------------------------------------------------------- pose tail: C ABI
+static const float kCocoSigmas[18] = {.26f, .79f, .79f, .72f, .62f, .79f, .72f, .62f, 1.07f, .87f, .89f, 1.07f, .87f, .89f, .25f, .25f, .35f, .35f};
+
+extern "C" int lwp_set_tracking(lwp_handle h, int mode, int match_threshold, double similarity_threshold, int smooth,
+                                const float* sigmas, int n_sigmas) {
+    const int K = h ? h->skel.K : 18;                  // the argument checks run without a handle too (against the default skeleton)
+    char msg[200];
+    if (mode < 0 || mode > 3) return fail(h, LWP_ERR_ARG, "tracking mode must be 0 (off), 1 (pose rows), 2 (lanes) or 3 (sequence)");
+    if (mode >= 2) {
+        if (!(similarity_threshold > 0.0 && similarity_threshold < 1.0))
+            return fail(h, LWP_ERR_ARG, "similarity_threshold must lie inside (0, 1)");
+        if (!sigmas) {
+            if (n_sigmas != 0 && n_sigmas != 18) {
+                snprintf(msg, sizeof msg, "sigmas is NULL (the COCO table of 18) but n_sigmas is %d", n_sigmas);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+            if (K != 18) {
+                snprintf(msg, sizeof msg, "sigmas is NULL (the COCO table of 18) but the skeleton has %d key-point types", K);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+        } else if (n_sigmas != K) {
+            snprintf(msg, sizeof msg, "n_sigmas is %d but the skeleton has %d key-point types", n_sigmas, K);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+    }
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    if (mode >= 2) {
+        // Pose.vars (pose.py:15-17): sigmas float32 / 10.0, then (sigmas * 2) ** 2, every step rounded to float32
+        float vars[kMaxSkelTypes] = {0};
+        for (int k = 0; k < K; ++k) {
+            volatile float sg = sigmas ? sigmas[k] : kCocoSigmas[k] / 10.0f;
+            volatile float t = sg * 2.0f;
+            vars[k] = t * t;
+            if (!(vars[k] > 0.f)) return fail(h, LWP_ERR_ARG, "sigmas must be positive");
+        }
+        if (!h->d_vars) HIP_TRY(h, hipMalloc((void**)&h->d_vars, kMaxSkelTypes * sizeof(float)));
+        HIP_TRY(h, hipMemcpy(h->d_vars, vars, sizeof vars, hipMemcpyHostToDevice));
+    }
+    if ((mode != 0) != (h->tail.mode != 0)) {          // the result block gains or loses its tail section: re-allocated lazily
+        free_ws(h);
+        for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    }
+    free_tail_state(h);                                // every lane starts over
+    h->last_N = 0;
+    h->tail_first_id = 0;
+    h->tail.mode = mode;
+    h->tail.match_threshold = match_threshold;
+    h->tail.smooth = smooth ? 1 : 0;
+    if (mode >= 2) h->tail.qmax = -std::log(similarity_threshold);
+    return LWP_OK;
+}
+
+extern "C" int lwp_set_unmap(lwp_handle h, int stride, double scale, int pad_top, int pad_left) {
+    if (stride <= 0) return fail(h, LWP_ERR_ARG, "stride must be positive");
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(h, LWP_ERR_ARG, "scale must be positive and finite");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    h->tail.stride = stride; h->tail.scale = scale; h->tail.pad_top = pad_top; h->tail.pad_left = pad_left;
+    return LWP_OK;
+}
+
+constexpr int kTailMaxLanes = 4096;
+
+extern "C" int lwp_reset_tracking(lwp_handle h, int lane, int next_id) {
+    if (lane < -1 || lane >= kTailMaxLanes) return fail(h, LWP_ERR_ARG, "lane must be -1 (all) or 0..4095");
+    if (next_id < 0) return fail(h, LWP_ERR_ARG, "next_id must not be negative");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (h->tail.mode < 2) return fail(h, LWP_ERR_STATE, "tracking is off (lwp_set_tracking mode 2 or 3)");
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (lane < 0) h->tail_first_id = next_id;
+    int rc = ensure_tail_state(h, lane < 0 ? std::max(h->tst.lanes, 1) : lane + 1);
+    if (rc) return rc;
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    HIP_TRY(h, launch_tail_reset(h->tst, lane < 0 ? 0 : lane, lane < 0 ? h->tst.lanes : 1, next_id, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+// host view of the tail section of a published result block
+struct TailHost { const int *n, *last, *ids, *bbox, *kp; const unsigned* near_; const double* conf; };
+static TailHost tail_host(const PostWorkspace& ws, const void* host_block) {
+    auto hp = [&](const void* q) { return (const char*)host_block + ((const char*)q - (const char*)ws.result_block); };
+    return TailHost{(const int*)hp(ws.t_n), (const int*)hp(ws.t_last), (const int*)hp(ws.t_ids), (const int*)hp(ws.t_bbox),
+                    (const int*)hp(ws.t_kp), (const unsigned*)hp(ws.t_near), (const double*)hp(ws.t_conf)};
+}
+static int tail_source(lwp_context* h, int slot, const PostWorkspace** ws, const void** block, int* N) {
+    if (slot < -1 || slot > 1) return fail(h, LWP_ERR_ARG, "slot must be -1 (the last serial call), 0 or 1");
+    if (slot < 0) { *ws = &h->ws; *block = h->h_stage; *N = h->stage_tail_N; }
+    else {
+        if (h->slots[slot].pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
+        *ws = &h->slots[slot].ws; *block = h->slots[slot].h_stage; *N = h->slots[slot].tail_N;
+    }
+    if (*N <= 0 || !(*ws)->tail || !*block) return fail(h, LWP_ERR_STATE, "no pose rows: the pose tail was off for that run (lwp_set_tracking), or nothing was fetched");
+    return LWP_OK;
+}
+
+extern "C" int lwp_get_poses(lwp_handle h, int slot, int* n_poses, int* keypoints, double* confidence, int* bbox, int* ids,
+                             int* last_ids, int pose_cap) {
+    if (!h || !n_poses || !keypoints || !confidence || !bbox || !ids || pose_cap < 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    const PostWorkspace* ws; const void* block; int N;
+    int rc = tail_source(h, slot, &ws, &block, &N);
+    if (rc) return rc;
+    const TailHost t = tail_host(*ws, block);
+    const size_t P = (size_t)ws->caps.max_entries, K = (size_t)ws->K;
+    for (int f = 0; f < N; ++f) {
+        if (t.n[f] < 0 || (size_t)t.n[f] > P) return fail(h, LWP_ERR_STATE, "the staged result block holds no valid pose rows");
+        if (t.n[f] > pose_cap) return fail(h, LWP_ERR_CAPACITY, "pose arrays too small (pose_cap)");
+    }
+    for (int f = 0; f < N; ++f) {
+        const size_t n = (size_t)t.n[f];
+        n_poses[f] = t.n[f];
+        std::memcpy(keypoints + (size_t)f * pose_cap * K * 2, t.kp + f * P * K * 2, n * K * 2 * sizeof(int));
+        std::memcpy(confidence + (size_t)f * pose_cap, t.conf + f * P, n * sizeof(double));
+        std::memcpy(bbox + (size_t)f * pose_cap * 4, t.bbox + f * P * 4, n * 4 * sizeof(int));
+        std::memcpy(ids + (size_t)f * pose_cap, t.ids + f * P, n * sizeof(int));
+        if (last_ids) last_ids[f] = t.last[f];
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_tracking_near(lwp_handle h, int slot, unsigned* counts, int cap) {
+    if (!h || !counts) return fail(h, LWP_ERR_ARG, "bad argument");
+    const PostWorkspace* ws; const void* block; int N;
+    int rc = tail_source(h, slot, &ws, &block, &N);
+    if (rc) return rc;
+    if (cap < N) return fail(h, LWP_ERR_CAPACITY, "counts array too small");
+    const TailHost t = tail_host(*ws, block);
+    for (int f = 0; f < N; ++f) counts[f] = t.near_[f];
+    return LWP_OK;
+}
+
+extern "C" int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoints, const double* confidence, int* out_keypoints,
+                               int* out_bbox, int* out_ids, int* last_id, unsigned* near_count) {
+    if (lane < 0 || lane >= kTailMaxLanes) return fail(h, LWP_ERR_ARG, "lane must be 0..4095");
+    if (n < 0) return fail(h, LWP_ERR_ARG, "negative pose count");
+    if (n > 0 && (!keypoints || !confidence || !out_keypoints || !out_bbox || !out_ids)) return fail(h, LWP_ERR_ARG, "null argument");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(confidence[i])) return fail(h, LWP_ERR_ARG, "confidences must be finite (sorting poses by a NaN has no defined order)");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (h->tail.mode < 2) return fail(h, LWP_ERR_STATE, "tracking is off (lwp_set_tracking mode 2 or 3)");
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
+    if (n > h->caps.max_entries) return fail(h, LWP_ERR_CAPACITY, "more poses than max_pose_entries");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_ws(h, 1);
+    if (rc) return rc;
+    rc = ensure_tail_state(h, lane + 1);
+    if (rc) return rc;
+    rc = ensure_host_stage(h, h->ws.result_bytes + 64);
+    if (rc) return rc;
+    h->stage_tail_N = 0;                               // frame 0 of the workspace is reused: the rows of the last run are gone,
+    h->run_has_tail = false;                           // and so is an lwp_infer_poses_async run that was not fetched yet
+    h->last_N = 0;
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    const size_t K = (size_t)h->ws.K;
+    if (n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(h->ws.t_kp, keypoints, (size_t)n * K * 2 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->ws.t_conf, confidence, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->ws.t_n, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    TailParams p = h->tail;
+    p.mode = 3;                                        // one frame of one lane
+    HIP_TRY(h, launch_tail_rows(1, h->ws, p, 1, h->stream));
+    HIP_TRY(h, launch_tail_track(1, h->ws, h->tst, p, lane, h->stream));
+    HIP_TRY(h, launch_publish(1, h->ws, h->h_stage, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const TailHost t = tail_host(h->ws, h->h_stage);
+    if (n > 0) {
+        std::memcpy(out_keypoints, t.kp, (size_t)n * K * 2 * sizeof(int));
+        std::memcpy(out_bbox, t.bbox, (size_t)n * 4 * sizeof(int));
+        std::memcpy(out_ids, t.ids, (size_t)n * sizeof(int));
+    }
+    if (last_id) *last_id = t.last[0];
+    if (near_count) *near_count = t.near_[0];
+    return LWP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- introspection

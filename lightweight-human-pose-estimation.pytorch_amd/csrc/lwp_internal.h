@@ -262,7 +262,46 @@ struct PostWorkspace {    // device buffers, sized for (N frames, caps, skeleton
     double* kpts_out = nullptr;     // [N*K*max_kpts*4]
     void* result_block = nullptr;   // flags, kpts_out, entries, kpt_count, n_entries: one allocation, one D2H copy
     size_t result_bytes = 0;
+    // pose tail (lwp_set_tracking mode != 0): one more section at the END of the result block, so the offsets above never move.
+    // P = caps.max_entries pose slots per frame.  All null / 0 with the tail off.
+    int tail = 0;                   // the tracking mode the block was laid out for (0: no tail section)
+    size_t tail_off = 0;            // byte offset of the tail section inside the result block
+    int* t_n = nullptr;             // [N]        poses of the frame
+    unsigned* t_near = nullptr;     // [N]        similarity decisions whose q lay within 1e-12 (relative) of -ln(similarity_threshold)
+    int* t_last = nullptr;          // [N]        the lane's id counter after the frame (last id given out)
+    int* t_ids = nullptr;           // [N*P]      -1 in mode 1
+    int* t_bbox = nullptr;          // [N*P*4]
+    int* t_kp = nullptr;            // [N*P*K*2]  -1 = key-point not found
+    double* t_conf = nullptr;       // [N*P]
 };
+
+// ---- pose tail (demo.py:101-118, modules/pose.py:65-118): tracking state of the handle's lanes, on the device
+constexpr int kTailMaxPoses = 256;  // pose slots per frame the greedy pass holds in registers (4 per lane of one wave)
+struct TailState {
+    int lanes = 0, P = 0, K = 0;
+    int4* hdr = nullptr;            // [lanes]  x: next id, y: parity (which of the two buffers holds the previous frame), z: poses in it
+    int* kp = nullptr;              // [lanes][2][P][K][2]  key-points after smoothing
+    int* bbox = nullptr;            // [lanes][2][P][4]
+    int* ids = nullptr;             // [lanes][2][P]
+    int* f_xprev = nullptr;         // [lanes][2][P][K][2]  1-Euro filter of each coordinate: last raw input,
+    int* f_init = nullptr;          //                      0 = never called,
+    double* f_dx = nullptr;         //                      low-passed derivative,
+    double* f_x = nullptr;          //                      low-passed value
+    unsigned char* sim = nullptr;   // [lanes][P][P]  similar key-points of (current pose, previous pose)
+    const float* vars = nullptr;    // [K]  (2 sigma)^2 in float32
+};
+struct TailParams {
+    int mode = 0;                   // 0 off, 1 pose rows only, 2 lanes (frame f -> lane f), 3 sequence (all frames -> lane 0, in order)
+    int match_threshold = 3, smooth = 0;
+    int stride = 8, ratio = 4, pad_top = 0, pad_left = 0;
+    double scale = 1.0;
+    double qmax = 0.6931471805599453;   // -ln(similarity_threshold), computed once on the host
+};
+// un-map + pose rows + confidence + bounding box of frames [0, N); from_rows != 0: the rows are already in ws.t_kp / t_conf / t_n
+hipError_t launch_tail_rows(int N, PostWorkspace& ws, const TailParams& p, int from_rows, hipStream_t s);
+// one tracking step per frame: lanes mode frame f -> lane lane0 + f (one workgroup each); sequence mode all N frames -> lane lane0, in order
+hipError_t launch_tail_track(int N, PostWorkspace& ws, const TailState& st, const TailParams& p, int lane0, hipStream_t s);
+hipError_t launch_tail_reset(const TailState& st, int lane0, int count, int next_id, hipStream_t s);
 
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);

@@ -881,6 +881,19 @@ __global__ __launch_bounds__(256) void publish_results_kernel(int N, PostWorkspa
     } else {
         for (int i = tid; i < ne * E; i += nth) de[i] = se[i];
     }
+    if (ws.tail) {                                     // the pose tail's section: same offsets in the pinned block, used rows only
+        const int P = c.max_entries, np = min(max(ws.t_n[f], 0), P);
+        auto hp = [&](auto* q) { return (decltype(q))(host + ((const char*)q - (const char*)ws.result_block)); };
+        if (tid == 0) { hp(ws.t_n)[f] = ws.t_n[f]; hp(ws.t_near)[f] = ws.t_near[f]; hp(ws.t_last)[f] = ws.t_last[f]; }
+        for (int i = tid; i < np; i += nth) {
+            hp(ws.t_ids)[(size_t)f * P + i] = ws.t_ids[(size_t)f * P + i];
+            hp(ws.t_conf)[(size_t)f * P + i] = ws.t_conf[(size_t)f * P + i];
+            ((int4*)hp(ws.t_bbox))[(size_t)f * P + i] = ((const int4*)ws.t_bbox)[(size_t)f * P + i];
+        }
+        const int2* sp = (const int2*)ws.t_kp + (size_t)f * P * K;
+        int2* dp = (int2*)hp(ws.t_kp) + (size_t)f * P * K;
+        for (int i = tid; i < np * K; i += nth) dp[i] = sp[i];
+    }
 }
 hipError_t launch_publish(int N, PostWorkspace& ws, void* host_block, hipStream_t s) {
     hipLaunchKernelGGL(publish_results_kernel, dim3(4, N), dim3(256), 0, s, N, ws, (char*)host_block);
@@ -1920,6 +1933,262 @@ hipError_t launch_assemble(int N, PostWorkspace& ws, hipStream_t s) {
     const size_t ext_bytes = ws.caps.max_entries > 64 ? (size_t)(ws.caps.max_entries - 64) * 20 * 8 : 16;
     if (ext_bytes <= 60 * 1024) hipLaunchKernelGGL(assemble_kernel<true>, dim3(N), dim3(64), ext_bytes, s, ws);
     else hipLaunchKernelGGL(assemble_kernel<false>, dim3(N), dim3(64), 16, s, ws);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ pose tail
+// demo.py:101-118 on the device, behind assemble_kernel: two launches.
+//   tail_rows_kernel   one workgroup per frame: un-map, int32 pose rows, confidence, bounding box (frames are independent)
+//   tail_track_kernel  one workgroup per LANE: similarity counts of all (current, previous) pairs, rank by confidence, the greedy
+//                      id hand-over by wave 0, 1-Euro filters, bounding boxes, and the lane's new state.  In sequence mode the one
+//                      workgroup walks the frames of the batch in order.
+// Every float64 operation below is an IEEE basic operation in the reference's order (this file is built with -ffp-contract=off).
+__global__ void __launch_bounds__(256) tail_rows_kernel(PostWorkspace ws, TailParams p, int from_rows) {
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int K = ws.K, E = ws.E, P = ws.caps.max_entries;
+    int* kp = ws.t_kp + (size_t)f * P * K * 2;
+    int n;
+    if (from_rows) {
+        n = min(max(ws.t_n[f], 0), P);
+    } else {
+        n = min(max(ws.n_entries[f], 0), P);
+        const double* ent = ws.entries + (size_t)f * P * E;
+        const double* rows = ws.kpts_out + (size_t)f * K * ws.caps.max_kpts * 4;
+        const int max_row = K * ws.caps.max_kpts;
+        const double stride = (double)p.stride, ratio = (double)p.ratio, pl = (double)p.pad_left, pt = (double)p.pad_top;
+        for (int i = tid; i < n * K; i += 256) {
+            const int e = i / K, k = i - e * K;
+            const double id = ent[(size_t)e * E + k];
+            int x = -1, y = -1;
+            if (id != -1.0) {
+                const int r = min(max((int)id, 0), max_row - 1);
+                // (x * stride / upsample_ratio - pad[1]) / scale, then Python's int(): truncation toward zero
+                x = (int)((rows[(size_t)r * 4] * stride / ratio - pl) / p.scale);
+                y = (int)((rows[(size_t)r * 4 + 1] * stride / ratio - pt) / p.scale);
+            }
+            kp[i * 2] = x;
+            kp[i * 2 + 1] = y;
+        }
+        for (int e = tid; e < n; e += 256) ws.t_conf[(size_t)f * P + e] = ent[(size_t)e * E + E - 2];
+        if (tid == 0) { ws.t_n[f] = n; ws.t_near[f] = 0u; ws.t_last[f] = -1; }
+    }
+    __syncthreads();                                   // the rows of this frame were written by this workgroup
+    for (int e = tid; e < n; e += 256) {
+        int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -0x7fffffff - 1, y1 = -0x7fffffff - 1, any = 0;
+        for (int k = 0; k < K; ++k) {
+            const int x = kp[(e * K + k) * 2], y = kp[(e * K + k) * 2 + 1];
+            if (x == -1) continue;                     // a real coordinate that truncated to -1 counts as missing, as in the reference
+            any = 1;
+            x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
+        }
+        int4 b = make_int4(0, 0, 0, 0);
+        if (any) b = make_int4(x0, y0, (int)((unsigned)x1 - (unsigned)x0 + 1u), (int)((unsigned)y1 - (unsigned)y0 + 1u));
+        *(int4*)(ws.t_bbox + ((size_t)f * P + e) * 4) = b;
+        ws.t_ids[(size_t)f * P + e] = -1;
+    }
+}
+
+// one_euro_filter.py:23-43 with freq 15, mincutoff 1, beta 0.05, dcutoff 1; x is an int32 key-point coordinate
+struct EuroState { int xprev, init; double dx, x; };
+__device__ __forceinline__ double euro_alpha(double cutoff) {          // get_alpha(rate = 15, cutoff)
+    const double tau = 1.0 / (2.0 * 3.141592653589793 * cutoff);
+    const double te = 1.0 / 15.0;
+    return 1.0 / (1.0 + tau / te);
+}
+__device__ __forceinline__ int euro_step(EuroState& s, int x) {
+    double dxs, xf;
+    if (!s.init) {                                     // dx = 0; both low-pass filters return their first input
+        dxs = 0.0;
+        xf = (double)x;
+    } else {
+        const int dx = (int)(((unsigned)x - (unsigned)s.xprev) * 15u);      // int32 arithmetic, as NumPy's scalars
+        const double a = euro_alpha(1.0);
+        dxs = a * (double)dx + (1.0 - a) * s.dx;
+        const double cutoff = 1.0 + 0.05 * fabs(dxs);
+        const double b = euro_alpha(cutoff);
+        xf = b * (double)x + (1.0 - b) * s.x;
+    }
+    s.dx = dxs; s.x = xf; s.xprev = x; s.init = 1;
+    return (int)xf;                                    // stored back into the int32 key-point array: truncation
+}
+
+__global__ void __launch_bounds__(256) tail_track_kernel(PostWorkspace ws, TailState st, TailParams p, int lane0, int frames) {
+    __shared__ int s_order[kTailMaxPoses];             // pose index by rank (descending confidence, stable)
+    __shared__ int s_match[kTailMaxPoses];             // donor: index of the previous pose whose id was inherited, -1 = fresh id
+    __shared__ int s_hdr[4];
+    __shared__ unsigned s_near;
+    const int tid = threadIdx.x, K = st.K, P = st.P;
+    const int lane = p.mode == 3 ? lane0 : lane0 + blockIdx.x;
+    const size_t PK2 = (size_t)P * K * 2;
+    unsigned char* sim = st.sim + (size_t)lane * P * P;
+    if (tid < 4) { const int4 h = st.hdr[lane]; s_hdr[tid] = tid == 0 ? h.x : tid == 1 ? h.y : tid == 2 ? h.z : 0; }
+    __syncthreads();
+    for (int fi = 0; fi < frames; ++fi) {
+        const int f = p.mode == 3 ? fi : (int)blockIdx.x;
+        const int next_id0 = s_hdr[0], par = s_hdr[1] & 1, np = s_hdr[2];
+        const int n = min(max(ws.t_n[f], 0), P);
+        int* ckp = ws.t_kp + (size_t)f * PK2;
+        int* cbb = ws.t_bbox + (size_t)f * P * 4;
+        int* cid = ws.t_ids + (size_t)f * P;
+        const double* conf = ws.t_conf + (size_t)f * P;
+        const size_t prev = (size_t)lane * 2 + par, cur = (size_t)lane * 2 + (par ^ 1);
+        const int* pkp = st.kp + prev * PK2;
+        const int* pbb = st.bbox + prev * P * 4;
+        const int* pid = st.ids + prev * P;
+        if (tid == 0) s_near = 0u;
+        __syncthreads();
+        // ---- similar key-points of every (current, previous) pair: pose.py:65-74
+        unsigned near = 0u;
+        for (int i = tid; i < n * np; i += 256) {
+            const int c = i / np, q = i - c * np;
+            const int4 ba = *(const int4*)(cbb + c * 4), bb = *(const int4*)(pbb + q * 4);
+            const long long area = max((long long)ba.z * ba.w, (long long)bb.z * bb.w);
+            const double den0 = 2.0 * ((double)area + 2.220446049250313e-16);      // 2 * (area + np.spacing(1))
+            int cnt = 0;
+            for (int k = 0; k < K; ++k) {
+                const int2 a = *(const int2*)(ckp + (c * K + k) * 2), b = *(const int2*)(pkp + ((size_t)q * K + k) * 2);
+                if (a.x == -1 || b.x == -1) continue;
+                const unsigned dx = (unsigned)a.x - (unsigned)b.x, dy = (unsigned)a.y - (unsigned)b.y;
+                const long long d = (long long)(int)(dx * dx) + (long long)(int)(dy * dy);   // int32 squares, np.sum in int64
+                const double qv = (double)d / (den0 * (double)st.vars[k]);
+                cnt += qv < p.qmax ? 1 : 0;                                    // exp(-q) > threshold
+                near += fabs(qv - p.qmax) <= 1e-12 * p.qmax ? 1u : 0u;
+            }
+            sim[(size_t)c * P + q] = (unsigned char)cnt;
+        }
+        if (near) atomicAdd(&s_near, near);
+        // ---- rank by confidence, descending, ties in input order (sorted(..., reverse=True) is stable)
+        // A NaN ranks as -inf, so the order is total and s_order is a permutation of 0..n-1 whatever the scores are (Python gives
+        // an arbitrary but in-bounds order there).
+        auto conf_key = [](double v) { return v != v ? -__builtin_huge_val() : v; };
+        for (int c = tid; c < n; c += 256) {
+            const double v = conf_key(conf[c]);
+            int r = 0;
+            for (int j = 0; j < n; ++j) { const double o = conf_key(conf[j]); r += (o > v || (o == v && j < c)) ? 1 : 0; }
+            s_order[r] = c;                            // r <= n - 1: at most n - 1 other poses rank before c
+        }
+        __threadfence_block();
+        __syncthreads();
+        // ---- greedy hand-over, pose.py:88-106: wave 0; lane l owns previous poses l, l + 64, l + 128, l + 192
+        if (tid < 64) {
+            unsigned free_mask = 0u;
+            for (int j = 0; j < 4; ++j) free_mask |= (tid + 64 * j < np) ? (1u << j) : 0u;
+            int next_id = next_id0;
+            unsigned cnts = 0u, cnts_next = 0u;
+            auto load_row = [&](int r) {
+                unsigned v = 0u;
+                if (r < n) {
+                    const unsigned char* row = sim + (size_t)s_order[r] * P;
+                    for (int j = 0; j < 4; ++j) if (tid + 64 * j < np) v |= (unsigned)row[tid + 64 * j] << (8 * j);
+                }
+                return v;
+            };
+            cnts_next = load_row(0);
+            for (int r = 0; r < n; ++r) {
+                cnts = cnts_next;
+                cnts_next = load_row(r + 1);           // independent of this round's outcome: its latency hides behind the reduction
+                // strict '>' scanning from index 0: the largest count, the smallest index among equals; a count of 0 never wins
+                int key = 0;
+                for (int j = 0; j < 4; ++j) {
+                    const int cnt = (int)((cnts >> (8 * j)) & 255u);
+                    if (((free_mask >> j) & 1u) && cnt > 0) key = max(key, (cnt << 16) | (0xffff - (tid + 64 * j)));
+                }
+                for (int d = 32; d > 0; d >>= 1) key = max(key, __shfl_xor(key, d));
+                const int best_n = key >> 16, best = key ? 0xffff - (key & 0xffff) : -1;
+                int donor = -1;
+                if (best_n >= p.match_threshold) {
+                    if (best < 0) free_mask = 0u;      // mask[None] = 0: every previous pose becomes unavailable
+                    else {
+                        if ((best & 63) == tid) free_mask &= ~(1u << (best >> 6));
+                        donor = best;
+                    }
+                }
+                if (tid == 0) {
+                    const int c = s_order[r];
+                    s_match[c] = donor;
+                    cid[c] = donor >= 0 ? pid[donor] : next_id;
+                }
+                next_id += donor >= 0 ? 0 : 1;
+            }
+            if (tid == 0) { s_hdr[0] = next_id; s_hdr[1] = par ^ 1; s_hdr[2] = n; }
+        }
+        __threadfence_block();
+        __syncthreads();
+        // ---- 1-Euro smoothing (pose.py:108-117) and the lane's new state
+        int* nkp = st.kp + cur * PK2;
+        int* nxp = st.f_xprev + cur * PK2; int* nin = st.f_init + cur * PK2;
+        double* ndx = st.f_dx + cur * PK2; double* nx = st.f_x + cur * PK2;
+        const int* oxp = st.f_xprev + prev * PK2; const int* oin = st.f_init + prev * PK2;
+        const double* odx = st.f_dx + prev * PK2; const double* ox = st.f_x + prev * PK2;
+        for (int i = tid; i < n * K; i += 256) {
+            const int c = i / K, k = i - c * K;
+            int2 v = *(const int2*)(ckp + i * 2);
+            if (p.smooth) {
+                EuroState sx = {0, 0, 0.0, 0.0}, sy = {0, 0, 0.0, 0.0};
+                if (v.x != -1) {
+                    const int m = s_match[c];
+                    if (m >= 0 && pkp[((size_t)m * K + k) * 2] != -1) {        // the donor had this key-point: its filter pair goes on
+                        const size_t o = ((size_t)m * K + k) * 2;
+                        sx = EuroState{oxp[o], oin[o], odx[o], ox[o]};
+                        sy = EuroState{oxp[o + 1], oin[o + 1], odx[o + 1], ox[o + 1]};
+                    }
+                    v.x = euro_step(sx, v.x);
+                    v.y = euro_step(sy, v.y);
+                    *(int2*)(ckp + i * 2) = v;
+                }
+                nxp[i * 2] = sx.xprev; nin[i * 2] = sx.init; ndx[i * 2] = sx.dx; nx[i * 2] = sx.x;
+                nxp[i * 2 + 1] = sy.xprev; nin[i * 2 + 1] = sy.init; ndx[i * 2 + 1] = sy.dx; nx[i * 2 + 1] = sy.x;
+            }
+            *(int2*)(nkp + i * 2) = v;
+        }
+        __threadfence_block();
+        __syncthreads();
+        for (int c = tid; c < n; c += 256) {
+            int4 b = *(const int4*)(cbb + c * 4);
+            if (p.smooth) {                            // Pose.get_bbox again on the smoothed key-points
+                int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -0x7fffffff - 1, y1 = -0x7fffffff - 1, any = 0;
+                for (int k = 0; k < K; ++k) {
+                    const int x = ckp[(c * K + k) * 2], y = ckp[(c * K + k) * 2 + 1];
+                    if (x == -1) continue;
+                    any = 1;
+                    x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
+                }
+                b = any ? make_int4(x0, y0, (int)((unsigned)x1 - (unsigned)x0 + 1u), (int)((unsigned)y1 - (unsigned)y0 + 1u)) : make_int4(0, 0, 0, 0);
+                *(int4*)(cbb + c * 4) = b;
+            }
+            *(int4*)(st.bbox + (cur * P + c) * 4) = b;
+            st.ids[cur * P + c] = cid[c];
+        }
+        if (tid == 0) { ws.t_near[f] = s_near; ws.t_last[f] = s_hdr[0] - 1; }
+        __threadfence_block();
+        __syncthreads();                               // the next frame of a sequence reads this state
+    }
+    if (tid == 0) st.hdr[lane] = make_int4(s_hdr[0], s_hdr[1], s_hdr[2], 0);
+}
+
+__global__ void __launch_bounds__(64) tail_reset_kernel(TailState st, int lane0, int count, int next_id) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < count) st.hdr[lane0 + i] = make_int4(next_id, 0, 0, 0);
+}
+
+hipError_t launch_tail_rows(int N, PostWorkspace& ws, const TailParams& p, int from_rows, hipStream_t s) {
+    hipLaunchKernelGGL(tail_rows_kernel, dim3(N), dim3(256), 0, s, ws, p, from_rows);
+    return hipGetLastError();
+}
+hipError_t launch_tail_track(int N, PostWorkspace& ws, const TailState& st, const TailParams& p, int lane0, hipStream_t s) {
+    if (st.P > kTailMaxPoses || ws.caps.max_entries != st.P || ws.K != st.K) return hipErrorInvalidValue;
+    if (p.mode == 3) {
+        if (lane0 < 0 || lane0 >= st.lanes) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(tail_track_kernel, dim3(1), dim3(256), 0, s, ws, st, p, lane0, N);
+    } else {
+        if (lane0 < 0 || lane0 + N > st.lanes) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(tail_track_kernel, dim3(N), dim3(256), 0, s, ws, st, p, lane0, 1);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_tail_reset(const TailState& st, int lane0, int count, int next_id, hipStream_t s) {
+    if (lane0 < 0 || count <= 0 || lane0 + count > st.lanes) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tail_reset_kernel, dim3((count + 63) / 64), dim3(64), 0, s, st, lane0, count, next_id);
     return hipGetLastError();
 }
 

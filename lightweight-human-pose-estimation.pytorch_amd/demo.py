@@ -8,7 +8,7 @@ uses the single fused C-ABI call (no up-sampled maps are materialised).
 import numpy as np
 
 from .modules.keypoints import extract_keypoints, group_keypoints
-from .modules.pose import Pose, track_poses
+from .modules.pose import Pose, poses_from_arrays, track_poses
 
 
 def _prepare(net, img, net_input_height_size, stride, pad_value, img_mean, img_scale):
@@ -47,14 +47,52 @@ def poses_from_entries(pose_entries, all_keypoints, scale, pad, stride=8, upsamp
     return poses
 
 
-def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, draw=False):
+def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, draw=False, device_tail=False, sigmas=None):
     """Generator over frames: yields (img, current_poses).  No GUI (cv2.imshow/waitKey are out of scope).
-    Pose / tracking are COCO-18 (modules/pose.py), as in the reference: an engine with a custom skeleton raises ValueError."""
+    Pose / tracking are COCO-18 (modules/pose.py), as in the reference: an engine with a custom skeleton raises ValueError,
+    unless ``device_tail=True`` and ``sigmas`` (K values, as ``Pose.sigmas`` holds them) are given.
+
+    ``device_tail=True`` (needs ``fused=True``) runs demo.py:101-118 on the GPU behind the grouping kernels: the un-map, the
+    int32 pose rows, ``track_poses`` and the 1-Euro smoothing.  The yielded ``Pose`` objects are filled from the returned arrays
+    (see ``poses_from_arrays``: their ``.filters`` is None, the filter state lives on the device).  Ids start at
+    ``Pose.last_id + 1`` and ``Pose.last_id`` is written back after every frame, so code that mixes both paths sees one
+    counter.  The engine's tracking setting is switched on for the run and off again when the generator ends."""
     K = net.engine.skeleton["num_kpt_types"]
-    if K != Pose.num_kpts:
+    if device_tail and not fused:
+        raise ValueError("run_demo(device_tail=True) needs fused=True: the pose tail runs behind the fused grouping kernels")
+    if K != Pose.num_kpts and (draw or not device_tail or sigmas is None):
         raise ValueError("run_demo draws and tracks COCO poses of %d key-points; the engine's skeleton has %d key-point types "
-                         "(use infer_poses / poses_from_maps for custom skeletons)" % (Pose.num_kpts, K))
+                         "(use infer_poses / poses_from_maps for custom skeletons, or device_tail=True with sigmas and draw=False)"
+                         % (Pose.num_kpts, K))
+    if device_tail:
+        return _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas)
     return _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw)
+
+
+def _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas):
+    net = net.eval()
+    eng = net.engine
+    stride, upsample_ratio = 8, 4
+    if sigmas is None:
+        sigmas = Pose.sigmas
+    eng.set_tracking(eng.TRACK_LANES if track else eng.TRACK_ROWS, smooth=smooth, sigmas=sigmas)
+    try:
+        if track:
+            eng.reset_tracking(0, Pose.last_id + 1)
+        for img in image_provider:
+            x, scale, pad = _prepare(net, img, height_size, stride, (0, 0, 0), (128, 128, 128), 1 / 256)
+            eng.set_unmap(stride, scale, pad)
+            eng.infer_poses(x, upsample_ratio, demo=True)
+            rows = eng.poses()[0]
+            current_poses = poses_from_arrays(rows["keypoints"], rows["confidence"], rows["bbox"], rows["ids"] if track else None)
+            if track:
+                Pose.last_id = rows["last_id"]
+            if draw:
+                for pose in current_poses:
+                    pose.draw(img)
+            yield img, current_poses
+    finally:
+        eng.set_tracking(eng.TRACK_OFF)
 
 
 def _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw):

@@ -71,6 +71,26 @@ class Pose:
                     stamp(int(q[0]), int(q[1]), 1)
 
 
+def poses_from_arrays(keypoints, confidence, bbox, ids=None):
+    """Pose objects over the arrays the device pose tail returns (Engine.poses / track_poses_device): keypoints (P,K,2) int32,
+    confidence (P,), bbox (P,4), ids (P,) or None.  No per-pose construction work: ``.keypoints`` is a view of row p, ``.bbox``
+    the row as a tuple, and ``.filters`` is None — the 1-Euro filter state of these poses lives on the device, in the lane that
+    tracked them, so they cannot be handed to the Python ``track_poses`` as previous poses with ``smooth=True``."""
+    boxes = bbox.tolist()
+    conf = confidence.tolist()
+    idl = ids.tolist() if ids is not None else None
+    out = []
+    for p in range(len(conf)):
+        pose = Pose.__new__(Pose)
+        pose.keypoints = keypoints[p]
+        pose.confidence = conf[p]
+        pose.bbox = tuple(boxes[p])
+        pose.id = idl[p] if idl is not None else None
+        pose.filters = None
+        out.append(pose)
+    return out
+
+
 def _similar_keypoints(a, b, threshold=0.5):
     """Number of key-points present in both poses whose OKS-like similarity exceeds ``threshold``."""
     both = (a.keypoints[:, 0] != -1) & (b.keypoints[:, 0] != -1)

@@ -333,6 +333,7 @@ class Engine(object):
         check(lib().lwp_infer_poses(self.h.ptr, t.data_ptr(), MEM_DEVICE if t.is_cuda else MEM_HOST, N, H, W, upsample_ratio,
                                     1 if demo else 0, counts.ctypes.data_as(C.POINTER(C.c_int)), kpts.ctypes.data, kcap,
                                     ent.ctypes.data, ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        self._last_N = N
         return self._unpack(N, counts, kpts, ent, ne)
 
     def poses_from_maps(self, heat, paf, upsample_ratio=4, demo=True, layout="NCHW"):
@@ -355,6 +356,7 @@ class Engine(object):
         check(lib().lwp_poses_from_maps(self.h.ptr, hp, pp, mem, lay, N, hs, ws, upsample_ratio,
                                         1 if demo else 0, counts.ctypes.data_as(C.POINTER(C.c_int)), kpts.ctypes.data, kcap,
                                         ent.ctypes.data, ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        self._last_N = N
         return self._unpack(N, counts, kpts, ent, ne)
 
     def layers(self):
@@ -447,6 +449,68 @@ class Engine(object):
                                        ent.ctypes.data, ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
         return self._unpack(N, counts, kpts, ent, ne)
 
+    # ------------------------------------------------------------------ pose tail on the device (demo.py:101-118)
+    TRACK_OFF, TRACK_ROWS, TRACK_LANES, TRACK_SEQUENCE = 0, 1, 2, 3
+
+    def set_tracking(self, mode, match_threshold=3, similarity_threshold=0.5, smooth=False, sigmas=None):
+        """Pose tail behind the grouping kernels: mode 0 off (default), 1 pose rows only, 2 lanes (frame f of a batch continues
+        lane f), 3 sequence (the frames of a batch are consecutive frames of lane 0).  ``sigmas``: K float32 values as
+        ``Pose.sigmas`` holds them; None = the COCO table (18 types only).  Clears every lane."""
+        mode = {"off": 0, "rows": 1, "lanes": 2, "sequence": 3}.get(mode, mode)
+        sg, n = None, 0
+        if sigmas is not None:
+            sg = np.ascontiguousarray(sigmas, dtype=np.float32)
+            n = int(sg.size)
+        check(lib().lwp_set_tracking(self.h.ptr, int(mode), int(match_threshold), float(similarity_threshold), 1 if smooth else 0,
+                                     sg.ctypes.data_as(C.POINTER(C.c_float)) if sg is not None else None, n), self.h.ptr)
+        self._tracking_mode = int(mode)
+
+    def set_unmap(self, stride, scale, pad):
+        """Geometry of the un-map (demo.py:101-103) for the following pose-producing calls; ``pad`` = [top, left, ...] as
+        ``preprocess_dims`` / ``infer_fast`` return it."""
+        check(lib().lwp_set_unmap(self.h.ptr, int(stride), float(scale), int(pad[0]), int(pad[1])), self.h.ptr)
+
+    def reset_tracking(self, lane=-1, next_id=0):
+        """Clears a lane (-1: all) and sets the first id it gives out."""
+        check(lib().lwp_reset_tracking(self.h.ptr, int(lane), int(next_id)), self.h.ptr)
+
+    def poses(self, slot=-1):
+        """Pose rows of the last infer_poses / poses_from_maps / fetch_poses (slot -1) or of a fetched pipeline slot: per frame a
+        dict of keypoints (P,K,2) int32, confidence (P,) f64, bbox (P,4) int32, ids (P,) int32 (-1 without tracking), last_id and
+        near (similarity decisions the device could round differently from NumPy; 0 on every fixture)."""
+        N = self._last_N if slot < 0 else self._keep_slot[slot][1]
+        K, cap = self.skeleton["num_kpt_types"], self.caps[3]
+        ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint)
+        n = np.zeros(N, np.int32)
+        kp = np.zeros((N, cap, K, 2), np.int32)
+        conf = np.zeros((N, cap), np.float64)
+        bbox = np.zeros((N, cap, 4), np.int32)
+        ids = np.zeros((N, cap), np.int32)
+        last = np.zeros(N, np.int32)
+        near = np.zeros(N, np.uint32)
+        check(lib().lwp_get_poses(self.h.ptr, slot, n.ctypes.data_as(ip), kp.ctypes.data_as(ip), conf.ctypes.data_as(C.POINTER(C.c_double)),
+                                  bbox.ctypes.data_as(ip), ids.ctypes.data_as(ip), last.ctypes.data_as(ip), cap), self.h.ptr)
+        check(lib().lwp_debug_tracking_near(self.h.ptr, slot, near.ctypes.data_as(up), N), self.h.ptr)
+        return [dict(keypoints=kp[f, :n[f]].copy(), confidence=conf[f, :n[f]].copy(), bbox=bbox[f, :n[f]].copy(),
+                     ids=ids[f, :n[f]].copy(), last_id=int(last[f]), near=int(near[f])) for f in range(N)]
+
+    def track_poses_device(self, keypoints, confidence, lane=0):
+        """One tracking step of ``lane`` on caller-supplied poses ((P,K,2) int32 key-points, (P,) confidences), on the kernels of
+        the pose tail.  Returns dict(keypoints, bbox, ids, last_id, near)."""
+        K = self.skeleton["num_kpt_types"]
+        kp = np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1, K, 2)
+        conf = np.ascontiguousarray(confidence, dtype=np.float64).reshape(-1)
+        n = len(kp)
+        if len(conf) != n:
+            raise ValueError("%d poses but %d confidences" % (n, len(conf)))
+        ip = C.POINTER(C.c_int)
+        okp, obb, oid = np.zeros((n, K, 2), np.int32), np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
+        last, near = C.c_int(), C.c_uint()
+        check(lib().lwp_track_poses(self.h.ptr, int(lane), n, kp.ctypes.data_as(ip), conf.ctypes.data_as(C.POINTER(C.c_double)),
+                                    okp.ctypes.data_as(ip), obb.ctypes.data_as(ip), oid.ctypes.data_as(ip), C.byref(last),
+                                    C.byref(near)), self.h.ptr)
+        return dict(keypoints=okp, bbox=obb, ids=oid, last_id=last.value, near=near.value)
+
     # ------------------------------------------------------------------ measurement
     def time_pipeline(self, x_cuda, iters, what=1, upsample_ratio=4, demo=True):
         """milliseconds for ``iters`` back-to-back passes (HIP events on the engine's stream)."""
@@ -472,7 +536,7 @@ class Engine(object):
         n = C.c_int()
         check(lib().lwp_profile_launches(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, reps, ms, kc, cap, C.byref(n)), self.h.ptr)
         layers = self.layers()
-        post = ["find_peaks", "nms", "score_pairs", "match", "assemble"]
+        post = ["find_peaks", "nms", "score_pairs", "match", "assemble", "tail_rows", "tail_track"]
         out, npost = [], 0
         for i in range(n.value):
             li = (kc[i] >> 8) - 1                      # first layer the launch covers (a fused head pair is one launch), -1: post kernel
