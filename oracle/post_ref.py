@@ -132,7 +132,9 @@ def multiscale_accumulate(avg, maps_chw, stride, pad, width, height, n_scales):
 
 
 # ----------------------------------------------------------------------------- extract
-def extract_keypoints(heatmap, all_keypoints, total_keypoint_num):
+def extract_keypoints(heatmap, all_keypoints, total_keypoint_num, counts=None):
+    """``counts``: optional dict; "peaks" / "kpts" get this map's strict maxima before the suppression and the key-points
+    kept appended (what Engine.post_counts reports per type).  It changes no result."""
     heatmap[heatmap < 0.1] = 0          # in place, like the reference (keypoints.py:17)
     h, w = heatmap.shape
     p = np.zeros((h + 2, w + 2), heatmap.dtype)
@@ -152,6 +154,9 @@ def extract_keypoints(heatmap, all_keypoints, total_keypoint_num):
         alive[i + 1:] &= d2 >= 36       # sqrt(d2) < 6  <=>  d2 < 36 for integers
         found.append((xs[i], ys[i], heatmap[ys[i], xs[i]], total_keypoint_num + len(found)))
     all_keypoints.append(found)
+    if counts is not None:
+        counts.setdefault("peaks", []).append(n)
+        counts.setdefault("kpts", []).append(len(found))
     return len(found)
 
 
@@ -211,8 +216,13 @@ def _fresh(size):
     return np.ones(size) * -1
 
 
-def group_keypoints(all_keypoints_by_type, pafs, pose_entry_size=20, min_paf_score=0.05, demo=False):
+def group_keypoints(all_keypoints_by_type, pafs, pose_entry_size=20, min_paf_score=0.05, demo=False, counts=None):
+    """``counts``: optional dict; "cand" / "picked" get per limb the scored candidates and the picked connections, "cands" the
+    candidate lists [i, j, ratio, score] in scoring order, "entries_before_filter" the entries the final filter saw (what
+    Engine.post_counts reports per limb).  It changes no result."""
     entries = []
+    if counts is not None:
+        counts.update(cand=[0] * len(KPT_IDS), picked=[0] * len(KPT_IDS), cands=[[] for _ in KPT_IDS], entries_before_filter=0)
     all_keypoints = np.array([kp for kps in all_keypoints_by_type for kp in kps])
     height_n = pafs.shape[0] // 2
     state = {"ratio_bound": False}
@@ -233,6 +243,9 @@ def group_keypoints(all_keypoints_by_type, pafs, pose_entry_size=20, min_paf_sco
             continue
 
         cand = score_pairs(ka, kb, pafs[:, :, chans], demo, height_n, min_paf_score, 10, state)
+        if counts is not None:
+            counts["cand"][part] = len(cand)
+            counts["cands"][part] = [list(c) for c in cand]
         cand.sort(key=lambda c: -c[2])   # stable, descending ratio (keypoints.py:141)
         used_a, used_b = np.zeros(na, bool), np.zeros(nb, bool)
         conns = []
@@ -242,6 +255,8 @@ def group_keypoints(all_keypoints_by_type, pafs, pose_entry_size=20, min_paf_sco
             if not used_a[i] and not used_b[j]:
                 conns.append([ka[i][3], kb[j][3], ratio])
                 used_a[i] = used_b[j] = True
+        if counts is not None:
+            counts["picked"][part] = len(conns)
         if not conns:
             continue
 
@@ -274,5 +289,7 @@ def group_keypoints(all_keypoints_by_type, pafs, pose_entry_size=20, min_paf_sco
                     e[-2] = np.sum(all_keypoints[[ia, ib], 2]) + ratio
                     entries.append(e)
 
+    if counts is not None:
+        counts["entries_before_filter"] = len(entries)
     kept = [e for e in entries if not (e[-1] < 3 or e[-2] / e[-1] < 0.2)]
     return np.asarray(kept), all_keypoints
