@@ -18,9 +18,7 @@ struct lwp_context {
     hipStream_t stream = nullptr;
     int dtype = LWP_F32;
     Graph g;
-    bool fuse_heads = true;                // head pairs as one kernel (LWP_FUSE_HEADS=0 at lwp_create: two GEMMs)
-    bool post_on_main = false;             // LWP_POST_STREAM=0 at lwp_create: grouping kernels follow the network on the same stream
-    Tuning tune;                           // kernel-selection A/B switches, read from the environment at lwp_create
+    Tuning tune;                           // every LWP_* A/B switch, read from the environment at lwp_create
     std::vector<std::string> variants;     // per layer: the kernel variant its last launch picked (debug / profiling entry points only)
     bool record_variants = false;
     char variant_buf[kVariantCap] = {0};
@@ -53,7 +51,6 @@ struct lwp_context {
     PostWorkspace ws;
     Skeleton skel = default_skeleton();    // grouping tables + options (lwp_set_skeleton); host state, not part of the weights
     int* d_limbs = nullptr;                // [kMaxSkelLimbs][4] device copy of skel's limb table (the generic kernels read it)
-    bool post_generic = false;             // LWP_POST_GENERIC=1 at lwp_create: the generic grouping kernels under the default skeleton too
     // pinned host staging for results
     void* h_stage = nullptr; size_t h_stage_bytes = 0;
     int last_N = 0;
@@ -215,19 +212,9 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
     lwp_context* h = new lwp_context();
     h->device = device_id;
     h->dtype = dtype;
-    {
-        const char* fe = getenv("LWP_FUSE_DWPW");   // "0" keeps depthwise and pointwise as separate launches (A/B, tests)
-        const char* me = getenv("LWP_MERGE_HEADS");   // "0": separate heat / PAF head GEMMs (A/B)
-        h->g = build_graph(nref, C, NH, NP, !(fe && fe[0] == '0'), dtype, !(me && me[0] == '0'));
-        const char* he = getenv("LWP_FUSE_HEADS");
-        h->fuse_heads = !(he && he[0] == '0');
-        const char* pe = getenv("LWP_POST_STREAM");
-        h->post_on_main = pe && pe[0] == '0';
-        const char* ge = getenv("LWP_POST_GENERIC");
-        h->post_generic = ge && ge[0] == '1';
-        h->tune = tuning_from_env();
-        h->variants.assign(h->g.layers.size(), std::string());
-    }
+    h->tune = tuning_from_env();
+    h->g = build_graph(nref, C, NH, NP, h->tune.fuse_dwpw != 0, dtype, h->tune.merge_heads != 0);
+    h->variants.assign(h->g.layers.size(), std::string());
     e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
     e = init_cubic_tables();
@@ -501,6 +488,17 @@ static bool skeleton_fits(const lwp_context* h) {
     return h->g.NH >= 18 && h->g.NP >= 38;
 }
 
+// the result-block pointers of `w`, from frame f0 on: the only place that turns the layout into pointers
+static void carve_result_block(PostWorkspace& w, const ResultLayout& l, size_t f0) {
+    char* b = (char*)w.result_block;
+    auto at = [&](const ResultLayout::Sec& s) { return b + s.off + f0 * s.stride; };
+    w.flags = (unsigned long long*)at(l.flags); w.kpts_out = (double*)at(l.kpts_out); w.entries = (double*)at(l.entries);
+    w.kpt_count = (int*)at(l.kpt_count); w.n_entries = (int*)at(l.n_entries);
+    if (!w.tail) return;
+    w.t_conf = (double*)at(l.t_conf); w.t_bbox = (int*)at(l.t_bbox); w.t_kp = (int*)at(l.t_kp); w.t_ids = (int*)at(l.t_ids);
+    w.t_n = (int*)at(l.t_n); w.t_near = (unsigned*)at(l.t_near); w.t_last = (int*)at(l.t_last);
+}
+
 static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t stream) {
     if (w.N >= N && w.peak_count && (w.tail != 0) == (h->tail.mode != 0)) return LWP_OK;
     if (h->tail.mode && h->caps.max_entries > kTailMaxPoses)
@@ -512,7 +510,7 @@ static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t st
     const int K = h->skel.K, L = h->skel.L, E = h->skel.E;
     w.K = K; w.L = L; w.E = E;
     w.min_paf = h->skel.min_paf;
-    w.generic = (!h->skel.is_default || h->post_generic) ? 1 : 0;
+    w.generic = (!h->skel.is_default || h->tune.post_generic == 1) ? 1 : 0;
     w.limbs = h->d_limbs;
 #define WS_ALLOC(field, count, type) HIP_TRY(h, hipMalloc((void**)&w.field, (size_t)(count) * sizeof(type)))
     WS_ALLOC(peak_count, N * K, int);
@@ -523,35 +521,11 @@ static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t st
     WS_ALLOC(conn_count, N * L, int);
     WS_ALLOC(conn_ij, (size_t)N * L * c.max_conn, int);
     WS_ALLOC(conn_ratio, (size_t)N * L * c.max_conn, double);
-    {   // result block: [flags N*4 u64][kpts_out N*K*kcap*4 f64][entries N*ecap*E f64][kpt_count N*K i32][n_entries N i32]
-        const size_t b_fl = (size_t)N * 4 * 8, b_k = (size_t)N * K * c.max_kpts * 4 * 8, b_e = (size_t)N * c.max_entries * E * 8;
-        const size_t b_cnt = (size_t)N * K * 4, b_ne = (size_t)N * 4;
-        w.result_bytes = b_fl + b_k + b_e + b_cnt + b_ne;
-        // pose tail: [t_conf N*P f64][t_bbox N*P*4 i32][t_kp N*P*K*2 i32][t_ids N*P i32][t_n N][t_near N][t_last N], 16-byte aligned
-        const size_t P = (size_t)c.max_entries, NP_ = (size_t)N * P;
-        const size_t tail_off = (w.result_bytes + 15) & ~(size_t)15;
-        if (h->tail.mode) w.result_bytes = tail_off + NP_ * 8 + NP_ * 16 + NP_ * K * 8 + NP_ * 4 + (size_t)N * 12;
-        HIP_TRY(h, hipMalloc((void**)&w.result_block, w.result_bytes));
-        char* q = (char*)w.result_block;
-        w.flags = (unsigned long long*)q; q += b_fl;
-        w.kpts_out = (double*)q; q += b_k;
-        w.entries = (double*)q; q += b_e;
-        w.kpt_count = (int*)q; q += b_cnt;
-        w.n_entries = (int*)q;
-        w.tail = h->tail.mode ? 1 : 0;
-        if (w.tail) {
-            w.tail_off = tail_off;
-            q = (char*)w.result_block + tail_off;
-            w.t_conf = (double*)q; q += NP_ * 8;
-            w.t_bbox = (int*)q; q += NP_ * 16;
-            w.t_kp = (int*)q; q += NP_ * K * 8;
-            w.t_ids = (int*)q; q += NP_ * 4;
-            w.t_n = (int*)q; q += (size_t)N * 4;
-            w.t_near = (unsigned*)q; q += (size_t)N * 4;
-            w.t_last = (int*)q;
-            HIP_TRY(h, hipMemsetAsync((char*)w.result_block + tail_off, 0, w.result_bytes - tail_off, stream));
-        }
-    }
+    w.tail = h->tail.mode ? 1 : 0;
+    const ResultLayout lay = result_layout(N, K, E, c, w.tail != 0);
+    HIP_TRY(h, hipMalloc(&w.result_block, lay.bytes));
+    carve_result_block(w, lay, 0);
+    if (w.tail) HIP_TRY(h, hipMemsetAsync((char*)w.result_block + lay.tail_off, 0, lay.bytes - lay.tail_off, stream));
     WS_ALLOC(entries_work, (size_t)N * c.max_entries * E, double);
     WS_ALLOC(sel_count, N * L, int);
     WS_ALLOC(seen, N * (K + L), int);
@@ -577,7 +551,7 @@ static int ensure_host_stage(lwp_context* h, size_t bytes) {
 }
 
 // ---------------------------------------------------------------------------------------------- profiling hooks
-static int prof_begin(lwp_context* h, int kclass) {
+static int prof_begin(lwp_context* h, hipStream_t s, int kclass) {
     if (!h->profiling) return LWP_OK;
     if (h->ev_used + 2 > h->ev.size()) {
         for (int i = 0; i < 2; ++i) {
@@ -590,23 +564,25 @@ static int prof_begin(lwp_context* h, int kclass) {
     }
     h->ev_class[h->ev_used / 2] = kclass;
     h->ev_layer[h->ev_used / 2] = h->cur_layer;
-    HIP_TRY(h, hipEventRecord(h->ev[h->ev_used], h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev[h->ev_used], s));
     return LWP_OK;
 }
-static int prof_end(lwp_context* h) {
+static int prof_end(lwp_context* h, hipStream_t s) {
     if (!h->profiling) return LWP_OK;
-    HIP_TRY(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev[h->ev_used + 1], s));
     h->ev_used += 2;
     return LWP_OK;
 }
-#define LAUNCH(h, kclass, expr)                    \
+// a launch on stream `s`, between two events of that stream while the handle is profiling (else a plain HIP_TRY)
+#define LAUNCH_ON(h, s, kclass, expr)              \
     do {                                           \
-        int rc_ = prof_begin(h, kclass);           \
+        int rc_ = prof_begin(h, s, kclass);        \
         if (rc_) return rc_;                       \
         HIP_TRY(h, expr);                          \
-        rc_ = prof_end(h);                         \
+        rc_ = prof_end(h, s);                      \
         if (rc_) return rc_;                       \
     } while (0)
+#define LAUNCH(h, kclass, expr) LAUNCH_ON(h, (h)->stream, kclass, expr)
 
 // ---------------------------------------------------------------------------------------------- batch split
 // The kernels address a tensor with 32-bit byte offsets (buffer loads), so one launch sequence takes at most as many frames
@@ -629,6 +605,41 @@ static int frames_per_pass(lwp_context* h, int N, int H, int W) {
     const int64_t chunks = (N + nmax - 1) / nmax;
     return (int)((N + chunks - 1) / chunks);
 }
+// fn(f0, n) for every pass of the batch, the activation buffers sized for the pass's n frames (the last one may be ragged)
+template <class F>
+static int for_each_pass(lwp_context* h, int N, int H, int W, F fn) {
+    const int Nc = frames_per_pass(h, N, H, W);
+    for (int f0 = 0; f0 < N; f0 += Nc) {
+        const int n = std::min(Nc, N - f0);
+        int rc = ensure_activations(h, n, H, W);
+        if (rc == LWP_OK) rc = fn(f0, n);
+        if (rc) return rc;
+    }
+    return LWP_OK;
+}
+
+// milliseconds the handle's stream spends on `iters` calls of fn; the two events do not outlive an error return
+template <class F>
+static int time_on_stream(lwp_context* h, int iters, F fn, float* ms) {
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } e;
+    HIP_TRY(h, hipEventCreate(&e.a));
+    HIP_TRY(h, hipEventCreate(&e.b));
+    HIP_TRY(h, hipEventRecord(e.a, h->stream));
+    for (int i = 0; i < iters; ++i) { int rc = fn(); if (rc) return rc; }
+    HIP_TRY(h, hipEventRecord(e.b, h->stream));
+    HIP_TRY(h, hipEventSynchronize(e.b));
+    HIP_TRY(h, hipEventElapsedTime(ms, e.a, e.b));
+    return LWP_OK;
+}
+
+// C channel planes of h x w per frame (NCHW)
+static MapView nchw_view(const float* base, int C, int h, int w) {
+    const int64_t hw = (int64_t)h * w;
+    return MapView{base, C * hw, (int64_t)w, 1, hw, h, w};
+}
 
 // the per-frame arrays of a post-processing workspace, seen from frame f0 on (every kernel indexes them by frame)
 static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
@@ -639,19 +650,13 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
     v.N = w.N - f0;
     const size_t K = (size_t)w.K, L = (size_t)w.L, E = (size_t)w.E;
     v.peak_count += f * K; v.peak_key += f * K * c.max_peaks; v.peak_val += f * K * c.max_peaks;
-    v.kpt_count += f * K; v.kpt_xy += f * K * c.max_kpts * 2; v.kpt_score += f * K * c.max_kpts;
+    v.kpt_xy += f * K * c.max_kpts * 2; v.kpt_score += f * K * c.max_kpts;
     v.conn_count += f * L; v.conn_ij += f * L * c.max_conn; v.conn_ratio += f * L * c.max_conn;
-    v.flags += f * 4;
     v.sel_count += f * L; v.sel_ij += f * L * c.max_kpts; v.sel_r += f * L * c.max_kpts;
     v.seen += f * (K + L);
     v.sel_sa += f * L * c.max_kpts; v.sel_sb += f * L * c.max_kpts;
-    v.entries_work += f * c.max_entries * E; v.entries += f * c.max_entries * E;
-    v.n_entries += f; v.kpts_out += f * K * c.max_kpts * 4;
-    if (w.tail) {
-        const size_t P = (size_t)c.max_entries;
-        v.t_conf += f * P; v.t_bbox += f * P * 4; v.t_kp += f * P * K * 2; v.t_ids += f * P;
-        v.t_n += f; v.t_near += f; v.t_last += f;
-    }
+    v.entries_work += f * c.max_entries * E;
+    carve_result_block(v, result_layout(w), f);
     return v;
 }
 
@@ -724,7 +729,7 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
 // a stage's merged head pair (".heads.0" 1x1 C -> hidden + ReLU, ".heads.1" 1x1 hidden -> NH + NP) runs as one kernel
 // that keeps the hidden tensor on the CU.  LWP_FUSE_HEADS=0 launches the two GEMMs (A/B, tests).
 static bool heads_pair_fusable(lwp_context* h, size_t i, int64_t M) {
-    if (!h->fuse_heads) return false;
+    if (h->tune.fuse_heads == 0) return false;
     const std::vector<Layer>& ls = h->g.layers;
     if (i + 1 >= ls.size()) return false;
     const Layer& a = ls[i];
@@ -823,8 +828,7 @@ extern "C" int lwp_forward(lwp_handle h, const float* in, int in_mem, int N, int
     int rc = check_frame_shape(h, N, H, W);
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const int Nc = frames_per_pass(h, N, H, W);          // frames per launch sequence (N unless a tensor would reach 2 GiB)
-    rc = ensure_activations(h, Nc, H, W);
+    rc = ensure_activations(h, frames_per_pass(h, N, H, W), H, W);   // frames per launch sequence: N unless a tensor would reach 2 GiB
     if (rc) return rc;
     if (in_mem == LWP_MEM_DEVICE || out_mem == LWP_MEM_DEVICE) { rc = order_in(h); if (rc) return rc; }
     const float* d_in = nullptr;
@@ -842,13 +846,11 @@ extern "C" int lwp_forward(lwp_handle h, const float* in, int in_mem, int N, int
         if (rc) return rc;
         d_outs[i] = h->d_outs[i];
     }
-    for (int f0 = 0; f0 < N; f0 += Nc) {
-        const int n = std::min(Nc, N - f0);
+    rc = for_each_pass(h, N, H, W, [&](int f0, int n) {
         for (int i = 0; i < nout; ++i) d_chunk[i] = d_outs[i] + (size_t)f0 * (i % 2 ? h->g.NP : h->g.NH) * fh * fw;
-        if (n != h->cur_N) { rc = ensure_activations(h, n, H, W); if (rc) return rc; }      // ragged last chunk
-        rc = enqueue_forward(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, d_chunk.data());
-        if (rc) return rc;
-    }
+        return enqueue_forward(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, d_chunk.data());
+    });
+    if (rc) return rc;
     if (out_mem == LWP_MEM_HOST) {
         for (int i = 0; i < nout; ++i) {
             const size_t bytes = (size_t)N * (i % 2 ? h->g.NP : h->g.NH) * fh * fw * sizeof(float);
@@ -883,7 +885,7 @@ extern "C" int lwp_upsample(lwp_handle h, const float* src, int src_mem, int N, 
         if (rc) return rc;
         d_dst = h->d_tmp2;
     }
-    MapView v{d_src, (int64_t)C * hs * ws, (int64_t)ws, 1, (int64_t)hs * ws, hs, ws};
+    const MapView v = nchw_view(d_src, C, hs, ws);
     LAUNCH(h, KC_POST, launch_upsample(v, N, C, ratio, d_dst, h->stream, &h->tune));
     if (dst_mem == LWP_MEM_HOST) {
         HIP_TRY(h, hipMemcpyAsync(dst, d_dst, db, hipMemcpyDeviceToHost, h->stream));
@@ -962,7 +964,7 @@ extern "C" int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int ma
     float* d_xw = (float*)t; t += nx * 4;
     int* d_yi = (int*)t; t += ny * 4;
     float* d_yw = (float*)t;
-    MapView v{d_src, (int64_t)C * hs * ws, (int64_t)ws, 1, (int64_t)hs * ws, hs, ws};
+    const MapView v = nchw_view(d_src, C, hs, ws);
     bool fused = false;
     if (h->tune.ms_fused != 0 && h->tune.ms_vec != 0) {      // four channels per lane (LWP_MS_VEC=0: the scalar fused kernel)
         LAUNCH(h, KC_POST, launch_multiscale_fused_v4(v, N, C, up_ratio, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
@@ -1253,7 +1255,7 @@ static int parse_results(lwp_context* h, const PostWorkspace& ws, const void* ho
                          int kpt_cap, double* entries, int entry_cap, int* n_entries);
 
 static int fetch_results(lwp_context* h, int N, int* kpt_counts, double* kpts, int kpt_cap, double* entries, int entry_cap, int* n_entries) {
-    int rc = ensure_host_stage(h, h->ws.result_bytes + 64);
+    int rc = ensure_host_stage(h, result_layout(h->ws).bytes + 64);
     if (rc) return rc;
     h->stage_tail_N = 0;
     HIP_TRY(h, launch_publish(N, h->ws, h->h_stage, h->stream));
@@ -1266,14 +1268,14 @@ static int fetch_results(lwp_context* h, int N, int* kpt_counts, double* kpts, i
 static int parse_results(lwp_context* h, const PostWorkspace& ws, const void* host_block, int N, int* kpt_counts, double* kpts,
                          int kpt_cap, double* entries, int entry_cap, int* n_entries) {
     const PostCaps& c = ws.caps;
-    const int WN = ws.N;                         // the block is laid out for the workspace's frame capacity
+    const ResultLayout l = result_layout(ws);    // the block is laid out for the workspace's frame capacity
     const char* p = (const char*)host_block;
-    const unsigned long long* h_fl = (const unsigned long long*)p; p += (size_t)WN * 4 * 8;
+    const unsigned long long* h_fl = (const unsigned long long*)(p + l.flags.off);
     const int K = ws.K, E = ws.E;
-    const double* h_k = (const double*)p; p += (size_t)WN * K * c.max_kpts * 4 * 8;
-    const double* h_e = (const double*)p; p += (size_t)WN * c.max_entries * E * 8;
-    const int* h_cnt = (const int*)p; p += (size_t)WN * K * 4;
-    const int* h_ne = (const int*)p;
+    const double* h_k = (const double*)(p + l.kpts_out.off);
+    const double* h_e = (const double*)(p + l.entries.off);
+    const int* h_cnt = (const int*)(p + l.kpt_count.off);
+    const int* h_ne = (const int*)(p + l.n_entries.off);
     for (int f = 0; f < N; ++f) {
         if (h_fl[f * 4 + 0]) {
             char msg[160];
@@ -1332,6 +1334,7 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
         d_paf = h->d_tmp2;
     }
     h->run_has_tail = false;                           // entries only: lwp_get_poses has nothing to return after this call
+    h->last_N = 1;                                     // the workspace holds this one frame now (lwp_debug_post_counts reads it)
     LAUNCH(h, KC_POST, launch_reset_ws(1, h->ws, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_xy, xy.data(), xy.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_score, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -1376,20 +1379,37 @@ static int ensure_tail_state(lwp_context* h, int lanes) {
 }
 
 // the tail's launches for the N frames of `ws`, behind assemble_kernel on the same stream
-static int enqueue_tail(lwp_context* h, PostWorkspace& ws, int N, int ratio, hipStream_t s, bool profiled) {
-    if (profiled) h->run_has_tail = ws.tail != 0;      // (the serial path; a pipeline slot keeps its own tail_N)
+static int enqueue_tail(lwp_context* h, PostWorkspace& ws, int N, int ratio, hipStream_t s) {
+    if (&ws == &h->ws) h->run_has_tail = ws.tail != 0; // (the serial path; a pipeline slot keeps its own tail_N)
     if (!ws.tail) return LWP_OK;
     TailParams p = h->tail;
     p.ratio = ratio;
     if (p.mode >= 2) { int rc = ensure_tail_state(h, p.mode == 2 ? N : 1); if (rc) return rc; }
-    if (profiled) {
-        LAUNCH(h, KC_POST, launch_tail_rows(N, ws, p, 0, s));
-        if (p.mode >= 2) LAUNCH(h, KC_POST, launch_tail_track(N, ws, h->tst, p, 0, s));
-    } else {
-        HIP_TRY(h, launch_tail_rows(N, ws, p, 0, s));
-        if (p.mode >= 2) HIP_TRY(h, launch_tail_track(N, ws, h->tst, p, 0, s));
-    }
+    LAUNCH_ON(h, s, KC_POST, launch_tail_rows(N, ws, p, 0, s));
+    if (p.mode >= 2) LAUNCH_ON(h, s, KC_POST, launch_tail_track(N, ws, h->tst, p, 0, s));
     return LWP_OK;
+}
+
+// the grouping kernels for N frames of stride-8 maps, on stream `s`; the tail follows once all frames of `ws` are grouped
+static int enqueue_grouping(lwp_context* h, const MapView& heat, const MapView& paf, int N, int ratio, int demo, PostWorkspace& ws, hipStream_t s) {
+    LAUNCH_ON(h, s, KC_POST, launch_find_peaks(heat, N, ws.K, ratio, ws, s, &h->tune));
+    LAUNCH_ON(h, s, KC_POST, launch_nms(N, ws.K, heat.h * ratio, ws, s, true));
+    LAUNCH_ON(h, s, KC_POST, launch_score_pairs(paf, N, ratio, demo, ws, s));
+    LAUNCH_ON(h, s, KC_POST, launch_match(N, ws, s));
+    LAUNCH_ON(h, s, KC_POST, launch_assemble(N, ws, s));
+    return LWP_OK;
+}
+
+static int check_pose_args(lwp_context* h, int ratio, bool allow_ratio1, int64_t full_h, int64_t full_w) {
+    if (ratio != 4 && ratio != 8 && !(allow_ratio1 && ratio == 1))
+        return fail(h, LWP_ERR_ARG, allow_ratio1 ? "upsample ratio must be 1, 4 or 8" : "upsample ratio must be 4 or 8");
+    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
+    if (full_h > 65535 || full_w > 65535) return fail(h, LWP_ERR_ARG, "map too large");   // peak coordinates are packed x << 16 | y
+    return LWP_OK;
+}
+// the same for the network's maps of an H x W frame (H / 8 + 1 bounds the stride-8 height from above)
+static int check_pose_frame(lwp_context* h, int H, int W, int ratio) {
+    return check_pose_args(h, ratio, false, ((int64_t)H / 8 + 1) * ratio, ((int64_t)W / 8 + 1) * ratio);
 }
 
 // ---------------------------------------------------------------------------------------------- fused pipeline
@@ -1415,9 +1435,8 @@ static int enqueue_poses_chunk(lwp_context* h, const float* d_in, int N, int H, 
         outs[nout - 1] = h->d_maps[1];
         rc = enqueue_forward(h, d_in, N, H, W, outs.data());
         if (rc || !with_post) return rc;
-        const int64_t hw = (int64_t)fh * fw;
-        heat = MapView{h->d_maps[0], (int64_t)g.NH * hw, (int64_t)fw, 1, hw, fh, fw};
-        paf = MapView{h->d_maps[1], (int64_t)g.NP * hw, (int64_t)fw, 1, hw, fh, fw};
+        heat = nchw_view(h->d_maps[0], g.NH, fh, fw);
+        paf = nchw_view(h->d_maps[1], g.NP, fh, fw);
     } else {
         int rc = enqueue_forward(h, d_in, N, H, W, nullptr);
         if (rc || !with_post) return rc;
@@ -1425,26 +1444,18 @@ static int enqueue_poses_chunk(lwp_context* h, const float* d_in, int N, int H, 
         heat = MapView{cat + g.C, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
         paf = MapView{cat + g.C + g.NH, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
     }
-    LAUNCH(h, KC_POST, launch_find_peaks(heat, N, ws.K, ratio, ws, h->stream, &h->tune));
-    LAUNCH(h, KC_POST, launch_nms(N, ws.K, fh * ratio, ws, h->stream, true));
-    LAUNCH(h, KC_POST, launch_score_pairs(paf, N, ratio, demo, ws, h->stream));
-    LAUNCH(h, KC_POST, launch_match(N, ws, h->stream));
-    LAUNCH(h, KC_POST, launch_assemble(N, ws, h->stream));
-    return LWP_OK;
+    return enqueue_grouping(h, heat, paf, N, ratio, demo, ws, h->stream);
 }
 
 // the whole batch, in as many equal launch sequences as keep every tensor below the 2 GiB addressing limit (one for any
 // batch the BASELINE configs use); the results of all frames land in h->ws
 static int enqueue_poses(lwp_context* h, const float* d_in, int N, int H, int W, int ratio, int demo, bool with_post) {
-    const int Nc = frames_per_pass(h, N, H, W);
-    for (int f0 = 0; f0 < N; f0 += Nc) {
-        const int n = std::min(Nc, N - f0);
-        if (n != h->cur_N) { int rc = ensure_activations(h, n, H, W); if (rc) return rc; }
-        int rc = enqueue_poses_chunk(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, ratio, demo, with_post, ws_frames(h->ws, f0));
-        if (rc) return rc;
-    }
+    int rc = for_each_pass(h, N, H, W, [&](int f0, int n) {
+        return enqueue_poses_chunk(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, ratio, demo, with_post, ws_frames(h->ws, f0));
+    });
+    if (rc) return rc;
     if (!with_post) { h->run_has_tail = false; return LWP_OK; }
-    return enqueue_tail(h, h->ws, N, ratio, h->stream, true);
+    return enqueue_tail(h, h->ws, N, ratio, h->stream);
 }
 
 // the lanes' state belongs to one stream at a time: the serial path runs the tail on the main stream, a pipeline slot on the post stream
@@ -1459,9 +1470,8 @@ static int prepare_poses(lwp_context* h, int N, int H, int W, int ratio) {
     if (rc) return rc;
     rc = tail_serial_allowed(h);
     if (rc) return rc;
-    if (ratio != 4 && ratio != 8) return fail(h, LWP_ERR_ARG, "upsample ratio must be 4 or 8");
-    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
-    if (((int64_t)H / 8 + 1) * ratio > 65535 || ((int64_t)W / 8 + 1) * ratio > 65535) return fail(h, LWP_ERR_ARG, "map too large");
+    rc = check_pose_frame(h, H, W, ratio);
+    if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     rc = ensure_activations(h, frames_per_pass(h, N, H, W), H, W);
     if (rc) return rc;
@@ -1504,22 +1514,20 @@ extern "C" int lwp_infer_poses(lwp_handle h, const float* in, int in_mem, int N,
 extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot) {
     if (!h || !in_device || slot < 0 || slot > 1) return fail(h, LWP_ERR_ARG, "bad argument");
     int rc = check_frame_shape(h, N, H, W);
+    if (rc == LWP_OK) rc = check_pose_frame(h, H, W, ratio);
     if (rc) return rc;
-    if (ratio != 4 && ratio != 8) return fail(h, LWP_ERR_ARG, "upsample ratio must be 4 or 8");
-    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
     HIP_TRY(h, hipSetDevice(h->device));
     lwp_context::Slot& sl = h->slots[slot];
     if (sl.pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
     if (!h->post_stream) {
-        if (h->post_on_main) h->post_stream = h->stream;
+        if (h->tune.post_stream == 0) h->post_stream = h->stream;
         else HIP_TRY(h, hipStreamCreateWithFlags(&h->post_stream, hipStreamNonBlocking));
     }
     if (!sl.ev_maps) {
         HIP_TRY(h, hipEventCreateWithFlags(&sl.ev_maps, hipEventDisableTiming));
         HIP_TRY(h, hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
     }
-    const int Nc = frames_per_pass(h, N, H, W);
-    rc = ensure_activations(h, Nc, H, W);
+    rc = ensure_activations(h, frames_per_pass(h, N, H, W), H, W);
     if (rc) return rc;
     rc = order_in(h);
     if (rc) return rc;
@@ -1534,35 +1542,27 @@ extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, 
     if (rc) return rc;
     rc = ensure_dev(h, &sl.maps[1], &sl.maps_bytes[1], pb);
     if (rc) return rc;
-    if (sl.h_stage_bytes < sl.ws.result_bytes) {
+    const size_t rb = result_layout(sl.ws).bytes;
+    if (sl.h_stage_bytes < rb) {
         if (sl.h_stage) HIP_TRY(h, hipHostFree(sl.h_stage));
         sl.h_stage = nullptr; sl.h_stage_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&sl.h_stage, sl.ws.result_bytes, hipHostMallocDefault));
-        sl.h_stage_bytes = sl.ws.result_bytes;
+        HIP_TRY(h, hipHostMalloc(&sl.h_stage, rb, hipHostMallocDefault));
+        sl.h_stage_bytes = rb;
     }
     // network on the main stream: the last stage's heads also write f32 NCHW maps into this slot
     const int nout = 2 * (1 + g.nref);
     std::vector<float*> outs(nout, nullptr);
-    for (int f0 = 0; f0 < N; f0 += Nc) {             // one launch sequence unless a tensor would reach 2 GiB
-        const int n = std::min(Nc, N - f0);
-        if (n != h->cur_N) { rc = ensure_activations(h, n, H, W); if (rc) return rc; }
+    rc = for_each_pass(h, N, H, W, [&](int f0, int n) {   // one launch sequence unless a tensor would reach 2 GiB
         outs[nout - 2] = sl.maps[0] + (size_t)f0 * g.NH * fh * fw;
         outs[nout - 1] = sl.maps[1] + (size_t)f0 * g.NP * fh * fw;
-        rc = enqueue_forward(h, in_device + (size_t)f0 * 3 * H * W, n, H, W, outs.data());
-        if (rc) return rc;
-    }
+        return enqueue_forward(h, in_device + (size_t)f0 * 3 * H * W, n, H, W, outs.data());
+    });
+    if (rc) return rc;
     HIP_TRY(h, hipEventRecord(sl.ev_maps, h->stream));
     // post-processing + result copy on the second stream
     if (h->post_stream != h->stream) HIP_TRY(h, hipStreamWaitEvent(h->post_stream, sl.ev_maps, 0));
-    const int64_t hw = (int64_t)fh * fw;
-    MapView heat{sl.maps[0], (int64_t)g.NH * hw, (int64_t)fw, 1, hw, fh, fw};
-    MapView paf{sl.maps[1], (int64_t)g.NP * hw, (int64_t)fw, 1, hw, fh, fw};
-    HIP_TRY(h, launch_find_peaks(heat, N, sl.ws.K, ratio, sl.ws, h->post_stream, &h->tune));
-    HIP_TRY(h, launch_nms(N, sl.ws.K, fh * ratio, sl.ws, h->post_stream, true));
-    HIP_TRY(h, launch_score_pairs(paf, N, ratio, demo, sl.ws, h->post_stream));
-    HIP_TRY(h, launch_match(N, sl.ws, h->post_stream));
-    HIP_TRY(h, launch_assemble(N, sl.ws, h->post_stream));
-    rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream, false);
+    rc = enqueue_grouping(h, nchw_view(sl.maps[0], g.NH, fh, fw), nchw_view(sl.maps[1], g.NP, fh, fw), N, ratio, demo, sl.ws, h->post_stream);
+    if (rc == LWP_OK) rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream);
     if (rc) return rc;
     sl.tail_N = sl.ws.tail ? N : 0;
     HIP_TRY(h, launch_publish(N, sl.ws, sl.h_stage, h->post_stream));
@@ -1588,12 +1588,11 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
                                    int* n_entries) {
     if (!h || !heat || !paf || !kpt_counts || !kpts || !entries || !n_entries || N <= 0 || hs <= 0 || ws <= 0)
         return fail(h, LWP_ERR_ARG, "bad argument");
-    if (ratio != 4 && ratio != 8 && ratio != 1) return fail(h, LWP_ERR_ARG, "upsample ratio must be 1, 4 or 8");
     if (layout != LWP_LAYOUT_NCHW && layout != LWP_LAYOUT_NHWC) return fail(h, LWP_ERR_ARG, "layout must be LWP_LAYOUT_NCHW or LWP_LAYOUT_NHWC");
-    if (!skeleton_fits(h)) return fail(h, LWP_ERR_ARG, "pose grouping needs >= 18 heat-maps and >= 38 PAFs (or a custom skeleton: lwp_set_skeleton)");
-    if ((int64_t)hs * ratio > 65535 || (int64_t)ws * ratio > 65535) return fail(h, LWP_ERR_ARG, "map too large");
+    int rc = check_pose_args(h, ratio, true, (int64_t)hs * ratio, (int64_t)ws * ratio);
+    if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = tail_serial_allowed(h);
+    rc = tail_serial_allowed(h);
     if (rc) return rc;
     rc = ensure_ws(h, N);
     if (rc) return rc;
@@ -1609,19 +1608,13 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
         HIP_TRY(h, hipMemcpyAsync(h->d_tmp2, paf, pb, hipMemcpyHostToDevice, h->stream));
         d_heat = h->d_tmp; d_paf = h->d_tmp2;
     }
-    const int64_t hw = (int64_t)hs * ws;
-    MapView hv{d_heat, (int64_t)h->g.NH * hw, (int64_t)ws, 1, hw, hs, ws};
-    MapView pv{d_paf, (int64_t)h->g.NP * hw, (int64_t)ws, 1, hw, hs, ws};
+    MapView hv = nchw_view(d_heat, h->g.NH, hs, ws), pv = nchw_view(d_paf, h->g.NP, hs, ws);
     if (layout == LWP_LAYOUT_NHWC) {                 // the averaged maps of val.infer are H x W x C
         hv.ys = (int64_t)ws * h->g.NH; hv.xs = h->g.NH; hv.cs = 1;
         pv.ys = (int64_t)ws * h->g.NP; pv.xs = h->g.NP; pv.cs = 1;
     }
-    LAUNCH(h, KC_POST, launch_find_peaks(hv, N, h->ws.K, ratio, h->ws, h->stream, &h->tune));
-    LAUNCH(h, KC_POST, launch_nms(N, h->ws.K, hs * ratio, h->ws, h->stream, true));
-    LAUNCH(h, KC_POST, launch_score_pairs(pv, N, ratio, demo, h->ws, h->stream));
-    LAUNCH(h, KC_POST, launch_match(N, h->ws, h->stream));
-    LAUNCH(h, KC_POST, launch_assemble(N, h->ws, h->stream));
-    rc = enqueue_tail(h, h->ws, N, ratio, h->stream, true);
+    rc = enqueue_grouping(h, hv, pv, N, ratio, demo, h->ws, h->stream);
+    if (rc == LWP_OK) rc = enqueue_tail(h, h->ws, N, ratio, h->stream);
     if (rc) return rc;
     h->last_N = N;
     return fetch_results(h, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
@@ -1712,9 +1705,10 @@ extern "C" int lwp_reset_tracking(lwp_handle h, int lane, int next_id) {
 // host view of the tail section of a published result block
 struct TailHost { const int *n, *last, *ids, *bbox, *kp; const unsigned* near_; const double* conf; };
 static TailHost tail_host(const PostWorkspace& ws, const void* host_block) {
-    auto hp = [&](const void* q) { return (const char*)host_block + ((const char*)q - (const char*)ws.result_block); };
-    return TailHost{(const int*)hp(ws.t_n), (const int*)hp(ws.t_last), (const int*)hp(ws.t_ids), (const int*)hp(ws.t_bbox),
-                    (const int*)hp(ws.t_kp), (const unsigned*)hp(ws.t_near), (const double*)hp(ws.t_conf)};
+    const ResultLayout l = result_layout(ws);
+    auto hp = [&](const ResultLayout::Sec& s) { return (const void*)((const char*)host_block + s.off); };
+    return TailHost{(const int*)hp(l.t_n), (const int*)hp(l.t_last), (const int*)hp(l.t_ids), (const int*)hp(l.t_bbox),
+                    (const int*)hp(l.t_kp), (const unsigned*)hp(l.t_near), (const double*)hp(l.t_conf)};
 }
 static int tail_source(lwp_context* h, int slot, const PostWorkspace** ws, const void** block, int* N) {
     if (slot < -1 || slot > 1) return fail(h, LWP_ERR_ARG, "slot must be -1 (the last serial call), 0 or 1");
@@ -1778,7 +1772,7 @@ extern "C" int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoin
     if (rc) return rc;
     rc = ensure_tail_state(h, lane + 1);
     if (rc) return rc;
-    rc = ensure_host_stage(h, h->ws.result_bytes + 64);
+    rc = ensure_host_stage(h, result_layout(h->ws).bytes + 64);
     if (rc) return rc;
     h->stage_tail_N = 0;                               // frame 0 of the workspace is reused: the rows of the last run are gone,
     h->run_has_tail = false;                           // and so is an lwp_infer_poses_async run that was not fetched yet
@@ -1863,24 +1857,10 @@ extern "C" int lwp_debug_frames_per_pass(lwp_handle h, int N, int H, int W) {
     return frames_per_pass(h, N, H, W);
 }
 
-extern "C" int lwp_debug_post_counts(lwp_handle h, int frame, int* peaks18, int* kpts18, int* candidates19, int* picked19) {
-    if (!h || !peaks18 || !kpts18 || !candidates19 || !picked19) return fail(h, LWP_ERR_ARG, "null argument");
-    if (!h->skel.is_default) return fail(h, LWP_ERR_STATE, "custom skeleton: use lwp_debug_post_counts_ex");
-    if (frame < 0 || frame >= h->ws.N) return fail(h, LWP_ERR_ARG, "frame outside the last batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->post_stream != h->stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
-    HIP_TRY(h, hipMemcpy(peaks18, h->ws.seen + frame * 37, 18 * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(kpts18, h->ws.kpt_count + frame * 18, 18 * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(candidates19, h->ws.seen + frame * 37 + 18, 19 * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(picked19, h->ws.sel_count + frame * 19, 19 * sizeof(int), hipMemcpyDeviceToHost));
-    return LWP_OK;
-}
-
 extern "C" int lwp_debug_post_counts_ex(lwp_handle h, int frame, int* peaks, int* kpts, int* candidates, int* picked, int K, int L) {
     if (!h || !peaks || !kpts || !candidates || !picked) return fail(h, LWP_ERR_ARG, "null argument");
     if (K != h->ws.K || L != h->ws.L) return fail(h, LWP_ERR_ARG, "K / L do not match the skeleton of the last run");
-    if (frame < 0 || frame >= h->ws.N) return fail(h, LWP_ERR_ARG, "frame outside the last batch");
+    if (frame < 0 || frame >= h->last_N) return fail(h, LWP_ERR_ARG, "frame outside the last batch");   // (last_N <= ws.N: whatever frees the workspace zeroes it)
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->post_stream && h->post_stream != h->stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
@@ -1891,10 +1871,16 @@ extern "C" int lwp_debug_post_counts_ex(lwp_handle h, int frame, int* peaks, int
     return LWP_OK;
 }
 
+extern "C" int lwp_debug_post_counts(lwp_handle h, int frame, int* peaks18, int* kpts18, int* candidates19, int* picked19) {
+    if (!h || !peaks18 || !kpts18 || !candidates19 || !picked19) return fail(h, LWP_ERR_ARG, "null argument");
+    if (!h->skel.is_default) return fail(h, LWP_ERR_STATE, "custom skeleton: use lwp_debug_post_counts_ex");
+    return lwp_debug_post_counts_ex(h, frame, peaks18, kpts18, candidates19, picked19, 18, 19);
+}
+
 extern "C" int lwp_debug_post_generic(lwp_handle h) {
     if (!h) return LWP_ERR_ARG;
     if (h->ws.N > 0) return h->ws.generic;             // the form the handle's current workspace launches
-    return (!h->skel.is_default || h->post_generic) ? 1 : 0;
+    return (!h->skel.is_default || h->tune.post_generic == 1) ? 1 : 0;
 }
 
 extern "C" int lwp_debug_f32_to_f16(const float* src, uint16_t* dst, int64_t n) {
@@ -1928,20 +1914,11 @@ extern "C" int lwp_debug_time_layer(lwp_handle h, int idx, int N, int H, int W, 
     const bool pair = heads_pair_fusable(h, (size_t)idx, M3);
     if (idx > 0 && heads_pair_fusable(h, (size_t)idx - 1, M3)) { *ms_avg = 0.f; return LWP_OK; }
     auto one = [&]() { return pair ? enqueue_heads_pair(h, l, h->g.layers[idx + 1], N, H, W, nullptr) : enqueue_layer(h, l, h->d_in, N, H, W, nullptr); };
-    hipEvent_t e0, e1;
-    HIP_TRY(h, hipEventCreate(&e0));
-    HIP_TRY(h, hipEventCreate(&e1));
     for (int i = 0; i < 3; ++i) { rc = one(); if (rc) return rc; }
-    HIP_TRY(h, hipEventRecord(e0, h->stream));
-    for (int i = 0; i < iters; ++i) { rc = one(); if (rc) return rc; }
-    HIP_TRY(h, hipEventRecord(e1, h->stream));
-    HIP_TRY(h, hipEventSynchronize(e1));
     float ms = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&ms, e0, e1));
+    rc = time_on_stream(h, iters, one, &ms);
     *ms_avg = ms / (float)iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return LWP_OK;
+    return rc;
 }
 
 extern "C" int lwp_synchronize(lwp_handle h) {
@@ -1959,20 +1936,7 @@ extern "C" int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, in
     int rc = prepare_poses(h, N, H, W, ratio);
     if (rc) return rc;
     h->last_N = N;
-    hipEvent_t e0, e1;
-    HIP_TRY(h, hipEventCreate(&e0));
-    HIP_TRY(h, hipEventCreate(&e1));
-    HIP_TRY(h, hipEventRecord(e0, h->stream));
-    for (int i = 0; i < iters; ++i) {
-        rc = enqueue_poses(h, in_device, N, H, W, ratio, demo, what != 0);
-        if (rc) return rc;
-    }
-    HIP_TRY(h, hipEventRecord(e1, h->stream));
-    HIP_TRY(h, hipEventSynchronize(e1));
-    HIP_TRY(h, hipEventElapsedTime(ms_total, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return LWP_OK;
+    return time_on_stream(h, iters, [&]() { return enqueue_poses(h, in_device, N, H, W, ratio, demo, what != 0); }, ms_total);
 }
 
 extern "C" int lwp_profile_launches(lwp_handle h, const float* in_device, int N, int H, int W, int ratio, int demo, int reps,

@@ -116,6 +116,8 @@ struct Tuning {
     int heads_f32_lds = -1;                                        // LWP_HEADS_F32_LDS ("0": the f32 stage heads above 4096 pixels as two GEMMs)
     int post_nchw = -1;                                            // LWP_POST_NCHW (f32: "0" = grouping reads the NHWC concat buffer in place)
     int heads_f32_max_m = 0;                                       // LWP_HEADS_F32_MAXM (tests: force the fused fp32 head pair at larger M)
+    int fuse_dwpw = -1, merge_heads = -1, fuse_heads = -1;         // LWP_FUSE_DWPW, LWP_MERGE_HEADS, LWP_FUSE_HEADS ("0": depthwise + pointwise / heat + PAF heads / a stage's head pair as separate launches)
+    int post_stream = -1, post_generic = -1;                       // LWP_POST_STREAM ("0": a pipeline slot's grouping follows the network on the main stream), LWP_POST_GENERIC ("1": the generic grouping kernels under the default skeleton too)
 };
 Tuning tuning_from_env();
 const Tuning& default_tuning();
@@ -260,12 +262,10 @@ struct PostWorkspace {    // device buffers, sized for (N frames, caps, skeleton
     double* entries = nullptr;      // [N*max_entries*E]
     int* n_entries = nullptr;       // [N]
     double* kpts_out = nullptr;     // [N*K*max_kpts*4]
-    void* result_block = nullptr;   // flags, kpts_out, entries, kpt_count, n_entries: one allocation, one D2H copy
-    size_t result_bytes = 0;
+    void* result_block = nullptr;   // flags, kpts_out, entries, kpt_count, n_entries (+ the tail): one allocation, laid out by result_layout()
     // pose tail (lwp_set_tracking mode != 0): one more section at the END of the result block, so the offsets above never move.
     // P = caps.max_entries pose slots per frame.  All null / 0 with the tail off.
     int tail = 0;                   // the tracking mode the block was laid out for (0: no tail section)
-    size_t tail_off = 0;            // byte offset of the tail section inside the result block
     int* t_n = nullptr;             // [N]        poses of the frame
     unsigned* t_near = nullptr;     // [N]        similarity decisions whose q lay within 1e-12 (relative) of -ln(similarity_threshold)
     int* t_last = nullptr;          // [N]        the lane's id counter after the frame (last id given out)
@@ -274,6 +274,31 @@ struct PostWorkspace {    // device buffers, sized for (N frames, caps, skeleton
     int* t_kp = nullptr;            // [N*P*K*2]  -1 = key-point not found
     double* t_conf = nullptr;       // [N*P]
 };
+
+// THE byte layout of the result block, on the device and in the pinned host copy alike: N frames of every section, back to
+// back in this order; the pose tail, 16-byte aligned, is appended so that the leading offsets never move.  A section of frame
+// f starts at off + f * stride.  With the tail off its sections are empty and `bytes` ends behind n_entries.
+struct ResultLayout {
+    struct Sec { size_t off, stride; };              // bytes: start of frame 0, distance between frames
+    Sec flags, kpts_out, entries, kpt_count, n_entries;
+    Sec t_conf, t_bbox, t_kp, t_ids, t_n, t_near, t_last;
+    size_t tail_off, bytes;
+};
+inline ResultLayout result_layout(int N, int K, int E, const PostCaps& c, bool tail) {
+    ResultLayout l{};
+    size_t q = 0;
+    auto sec = [&](ResultLayout::Sec& s, size_t stride) { s.off = q; s.stride = stride; q += (size_t)N * stride; };
+    const size_t P = (size_t)c.max_entries;          // pose slots per frame
+    sec(l.flags, 4 * 8); sec(l.kpts_out, (size_t)K * c.max_kpts * 4 * 8); sec(l.entries, P * E * 8); sec(l.kpt_count, (size_t)K * 4); sec(l.n_entries, 4);
+    l.bytes = q;
+    l.tail_off = (q + 15) & ~(size_t)15;
+    if (!tail) return l;
+    q = l.tail_off;
+    sec(l.t_conf, P * 8); sec(l.t_bbox, P * 4 * 4); sec(l.t_kp, P * K * 2 * 4); sec(l.t_ids, P * 4); sec(l.t_n, 4); sec(l.t_near, 4); sec(l.t_last, 4);
+    l.bytes = q;
+    return l;
+}
+inline ResultLayout result_layout(const PostWorkspace& w) { return result_layout(w.N, w.K, w.E, w.caps, w.tail != 0); }
 
 // ---- pose tail (demo.py:101-118, modules/pose.py:65-118): tracking state of the handle's lanes, on the device
 constexpr int kTailMaxPoses = 256;  // pose slots per frame the greedy pass holds in registers (4 per lane of one wave)

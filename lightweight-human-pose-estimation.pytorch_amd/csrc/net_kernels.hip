@@ -1937,6 +1937,8 @@ Tuning tuning_from_env() {
     digit("LWP_PEAK_TILE", &t.peak_tile); digit("LWP_PAIR_FORM", &t.pair_form); digit("LWP_POST_NCHW", &t.post_nchw); digit("LWP_HEADS_F32_LDS", &t.heads_f32_lds); digit("LWP_MS_FUSED", &t.ms_fused); digit("LWP_MS_VEC", &t.ms_vec); geti("LWP_MS_TX", &t.ms_tx); digit("LWP_HOST_FETCH_DMA", &t.host_fetch_dma); geti("LWP_DWPW_LDS_PAD", &t.dwpw_lds_pad_kb);
     geti("LWP_HEADS_F32_MAXM", &t.heads_f32_max_m);
     geti("LWP_MAX_FRAMES_PER_PASS", &t.max_frames_per_pass);
+    digit("LWP_FUSE_DWPW", &t.fuse_dwpw); digit("LWP_MERGE_HEADS", &t.merge_heads); digit("LWP_FUSE_HEADS", &t.fuse_heads);
+    digit("LWP_POST_STREAM", &t.post_stream); digit("LWP_POST_GENERIC", &t.post_generic);
     return t;
 }
 

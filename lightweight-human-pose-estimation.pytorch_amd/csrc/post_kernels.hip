@@ -852,51 +852,45 @@ hipError_t launch_preprocess_scaled(const PreScaleParams& p, hipStream_t s) {
 // n_entries pose rows of every frame) straight into pinned host memory at the same offsets, so the host parses
 // one block.  This replaces a hipMemcpyAsync of the whole block: the runtime may route that through an SDMA
 // queue, which stalls for milliseconds when it has to wake up, and it moves ~115 KB per frame instead of ~10 KB.
-__global__ __launch_bounds__(256) void publish_results_kernel(int N, PostWorkspace ws, char* __restrict__ host) {
+// `lay` is the block's layout (result_layout), the same on both sides: section x of frame f is at lay.x.off + f * lay.x.stride.
+__global__ __launch_bounds__(256) void publish_results_kernel(int N, PostWorkspace ws, ResultLayout lay, char* __restrict__ host) {
     const int f = blockIdx.y;
     const PostCaps& c = ws.caps;
-    const size_t WN = (size_t)ws.N;
-    char* q = host;
     const int K = ws.K, E = ws.E;               // E doubles per row: E * 8 bytes, a multiple of 16 only for even E
-    unsigned long long* h_fl = (unsigned long long*)q; q += WN * 4 * 8;
-    double2* h_k = (double2*)q; q += WN * K * c.max_kpts * 4 * 8;
-    double* h_e = (double*)q; q += WN * c.max_entries * E * 8;
-    int* h_cnt = (int*)q; q += WN * K * 4;
-    int* h_ne = (int*)q;
+    auto hp = [&](const ResultLayout::Sec& s) { return host + s.off + (size_t)f * s.stride; };
     int total = 0;
     for (int t = 0; t < K; ++t) total += ws.kpt_count[f * K + t];
     total = min(max(total, 0), K * c.max_kpts);
     const int ne = min(max(ws.n_entries[f], 0), c.max_entries);
     const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
-    if (tid < 4) h_fl[f * 4 + tid] = ws.flags[f * 4 + tid];
-    if (tid >= 128 && tid < 128 + K) h_cnt[f * K + tid - 128] = ws.kpt_count[f * K + tid - 128];
-    if (tid == 64) h_ne[f] = ws.n_entries[f];
+    if (tid < 4) ((unsigned long long*)hp(lay.flags))[tid] = ws.flags[f * 4 + tid];
+    if (tid >= 128 && tid < 128 + K) ((int*)hp(lay.kpt_count))[tid - 128] = ws.kpt_count[f * K + tid - 128];
+    if (tid == 64) *(int*)hp(lay.n_entries) = ws.n_entries[f];
     const double2* sk = (const double2*)(ws.kpts_out + (size_t)f * K * c.max_kpts * 4);
-    double2* dk = h_k + (size_t)f * K * c.max_kpts * 2;
+    double2* dk = (double2*)hp(lay.kpts_out);
     for (int i = tid; i < total * 2; i += nth) dk[i] = sk[i];
     const double* se = ws.entries + (size_t)f * c.max_entries * E;
-    double* de = h_e + (size_t)f * c.max_entries * E;
+    double* de = (double*)hp(lay.entries);
     if ((E & 1) == 0) {
         for (int i = tid; i < ne * E / 2; i += nth) ((double2*)de)[i] = ((const double2*)se)[i];
     } else {
         for (int i = tid; i < ne * E; i += nth) de[i] = se[i];
     }
-    if (ws.tail) {                                     // the pose tail's section: same offsets in the pinned block, used rows only
+    if (ws.tail) {                                     // the pose tail's section: used rows only
         const int P = c.max_entries, np = min(max(ws.t_n[f], 0), P);
-        auto hp = [&](auto* q) { return (decltype(q))(host + ((const char*)q - (const char*)ws.result_block)); };
-        if (tid == 0) { hp(ws.t_n)[f] = ws.t_n[f]; hp(ws.t_near)[f] = ws.t_near[f]; hp(ws.t_last)[f] = ws.t_last[f]; }
+        if (tid == 0) { *(int*)hp(lay.t_n) = ws.t_n[f]; *(unsigned*)hp(lay.t_near) = ws.t_near[f]; *(int*)hp(lay.t_last) = ws.t_last[f]; }
         for (int i = tid; i < np; i += nth) {
-            hp(ws.t_ids)[(size_t)f * P + i] = ws.t_ids[(size_t)f * P + i];
-            hp(ws.t_conf)[(size_t)f * P + i] = ws.t_conf[(size_t)f * P + i];
-            ((int4*)hp(ws.t_bbox))[(size_t)f * P + i] = ((const int4*)ws.t_bbox)[(size_t)f * P + i];
+            ((int*)hp(lay.t_ids))[i] = ws.t_ids[(size_t)f * P + i];
+            ((double*)hp(lay.t_conf))[i] = ws.t_conf[(size_t)f * P + i];
+            ((int4*)hp(lay.t_bbox))[i] = ((const int4*)ws.t_bbox)[(size_t)f * P + i];
         }
         const int2* sp = (const int2*)ws.t_kp + (size_t)f * P * K;
-        int2* dp = (int2*)hp(ws.t_kp) + (size_t)f * P * K;
+        int2* dp = (int2*)hp(lay.t_kp);
         for (int i = tid; i < np * K; i += nth) dp[i] = sp[i];
     }
 }
 hipError_t launch_publish(int N, PostWorkspace& ws, void* host_block, hipStream_t s) {
-    hipLaunchKernelGGL(publish_results_kernel, dim3(4, N), dim3(256), 0, s, N, ws, (char*)host_block);
+    hipLaunchKernelGGL(publish_results_kernel, dim3(4, N), dim3(256), 0, s, N, ws, result_layout(ws), (char*)host_block);
     return hipGetLastError();
 }
 

@@ -393,6 +393,22 @@ def test_capacity_overflow_is_reported():
         e2.poses_from_maps(heat[None], paf[None], 4, True)
 
 
+def test_post_counts_are_bounded_by_the_last_batch_not_the_workspace():
+    """The workspace only grows: after a batch of 4 it still holds 4 frames, but a following batch of 2 has frames 0 and 1
+    only.  include/lwpose.h: "frame outside the last batch" is LWP_ERR_ARG (ValueError)."""
+    e2 = Engine(0)
+    heat, paf, _ = synth.make_pose_maps(3, 46, 82, 2, 0.1, 0.02)
+    e2.poses_from_maps(np.repeat(heat[None], 4, 0), np.repeat(paf[None], 4, 0), 4, True)
+    four = [e2.post_counts(f) for f in range(4)]
+    assert four[3][1].sum() > 0
+    e2.poses_from_maps(np.repeat(heat[None], 2, 0), np.repeat(paf[None], 2, 0), 4, True)
+    for f in range(2):
+        assert all(np.array_equal(a, b) for a, b in zip(e2.post_counts(f), four[f]))
+    for f in (2, 3, -1):
+        with pytest.raises(ValueError, match="frame outside the last batch"):
+            e2.post_counts(f)
+
+
 def test_drop_in_run_demo_fused_equals_stepwise():
     from lwpose_amd.demo import run_demo
     from lwpose_amd import workload
