@@ -145,6 +145,17 @@ int lwp_preprocess_dims(int H, int W, int net_input_height, int stride, int* sca
 int lwp_preprocess_u8(lwp_handle h, const unsigned char* img, int img_mem, int H, int W, int net_input_height, int stride,
                       const double* pad_value, const double* img_mean, double img_scale, float* out_device);
 
+/* ---- the same for N same-sized frames in one launch: replaces demo.py:55-68's per-frame preparation for a batch of camera
+ *      frames (frame f of the batch is lane f of lwp_set_tracking mode 2).  imgs is N x H x W x 3 uint8 (mem), out a DEVICE
+ *      buffer of N*3*out_h*out_w float32 (out_h, out_w of lwp_preprocess_dims).  The arithmetic is lwp_preprocess_u8's (integer
+ *      resize, exact float64 normalise): every frame gets the bits a single-frame call gives it, N = 1 included.  Host frames go
+ *      through the same pinned staging and are free on return; the stream ordering is lwp_preprocess_u8's.  The resize tables of
+ *      a geometry are built once, kept on the device (up to 16 geometries) and never rewritten.  Checks (LWP_ERR_ARG with a
+ *      message; they need no GPU and run with h == NULL, message via lwp_last_error(NULL)): null pointers, img_mem, 1 <= N <=
+ *      65535, an empty scaled frame, negative padding, a padded frame below the network's 8 x 8 minimum. */
+int lwp_preprocess_u8_batch(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, int net_input_height,
+                            int stride, const double* pad_value, const double* img_mean, double img_scale, float* out_device);
+
 /* ---- image side of ONE scale of the multi-scale driver: replaces val.py:84-93 for N same-sized uint8 frames
  *      (normalize, val.py:30-33: float64 (u8 - mean) * scale;  cv2.resize(normed_img, (0,0), fx=fy=ratio, INTER_CUBIC) on
  *      the float64 image: float32 cubic coefficients (A = -0.75), float64 left-to-right sums, horizontal pass then vertical
@@ -229,6 +240,29 @@ int lwp_fetch_poses(lwp_handle h, int* kpt_counts, double* kpts, int kpt_cap,
 int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio, int demo, int slot);
 int lwp_pipeline_fetch(lwp_handle h, int slot, int* kpt_counts, double* kpts, int kpt_cap,
                        double* entries, int entry_cap, int* n_entries);
+
+/* ---- one-call video step: replaces demo.py:55-68 + demo.py:91-118 for a batch of N same-sized uint8 frames (mem).  One call
+ *      enqueues, in order: the upload of host frames, lwp_preprocess_u8_batch into an input tensor the handle owns, the
+ *      network on the main stream, and grouping + (if on) the pose tail + the result copy on the slot's stream, exactly as
+ *      lwp_pipeline_submit splits the work; it returns at once.  Host frames are free for reuse on return; DEVICE frames must
+ *      stay untouched until the slot is fetched (like in_device of lwp_pipeline_submit).  Results: lwp_pipeline_fetch(slot),
+ *      then lwp_get_poses(slot).  The tail's un-map of THIS submit is (stride, scale, pad_top, pad_left) as lwp_preprocess_dims
+ *      yields them for (H, W, net_input_height, stride), with upsample_ratio: it rides in the tail launch by value, so two
+ *      slots in flight may hold frames of different sizes, and the handle's lwp_set_unmap state is neither read nor written.
+ *      With the tail off the entries and key-points are those of lwp_preprocess_u8 + lwp_pipeline_submit.  lwp_pipeline_submit's
+ *      rules hold: a pending slot is LWP_ERR_STATE, a batch whose tensors would reach 2 GiB is walked in equal chunks, the lanes
+ *      of tracking modes 2 / 3 belong to the slot's stream while a slot is pending, the capacities and the 256-pose limit of
+ *      the tail apply.  A new frame geometry gets its own resize tables (never rewritten while another slot may read them).
+ *      The call returns without waiting in the steady state; it WAITS for the main stream (the other slot's network included)
+ *      when something has to grow or be built: a larger input tensor, a larger device frame buffer for host frames, and the
+ *      17th distinct geometry (the oldest tables are freed); a geometry seen for the first time also costs four small blocking
+ *      uploads of its tables.  The argument and slot checks (as lwp_preprocess_u8_batch, with h == NULL too, plus slot in
+ *      {0, 1} and upsample_ratio in {4, 8}) come before anything is enqueued; an allocation that fails later (activations,
+ *      grouping workspace, tracking state) is still reported after the upload and the pre-processing were enqueued — the slot
+ *      is then not pending and nothing of it can be fetched. */
+int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, int net_input_height,
+                           int stride, const double* pad_value, const double* img_mean, double img_scale, int upsample_ratio,
+                           int demo, int slot);
 
 /* ---- pose tail on the device: replaces the rest of run_demo's loop body (demo.py:101-118: map the key-points back to image
  *      coordinates, one Pose per entry, modules/pose.py:65-118 track_poses with its 1-Euro smoothing).  OFF by default: with

@@ -21,6 +21,7 @@ EXPORTS = [
     "lwp_debug_f32_to_f16", "lwp_set_skeleton", "lwp_get_skeleton", "lwp_debug_post_counts_ex",
     "lwp_debug_post_generic",
     "lwp_set_tracking", "lwp_set_unmap", "lwp_reset_tracking", "lwp_get_poses", "lwp_track_poses", "lwp_debug_tracking_near",
+    "lwp_preprocess_u8_batch", "lwp_pipeline_submit_u8",
 ]
 
 
@@ -93,6 +94,8 @@ def lib():
     L.lwp_get_poses.argtypes = [vp, C.c_int, ip, ip, dp, ip, ip, ip, C.c_int]
     L.lwp_track_poses.argtypes = [vp, C.c_int, C.c_int, ip, dp, ip, ip, ip, ip, C.POINTER(C.c_uint)]
     L.lwp_debug_tracking_near.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), C.c_int]
+    L.lwp_preprocess_u8_batch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, vp]
+    L.lwp_pipeline_submit_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -45,6 +45,9 @@ struct lwp_context {
     int pin_next = 0;
     float* d_pre_tab = nullptr; size_t d_pre_tab_bytes = 0;   // fixed-point resize tables, cached for (pre_H, pre_W, pre_net_h)
     int pre_H = 0, pre_W = 0, pre_net_h = 0;
+    std::vector<ResizeTab> pre_tabs;                     // the same tables for the batched entry points, one set per geometry (W, H, dw, dh, scale): never rewritten, so a
+                                                         // submit with a new frame size cannot race the launches of another slot that still read the old ones
+    float* d_pipe_in = nullptr; size_t d_pipe_in_bytes = 0;   // network input of lwp_pipeline_submit_u8 (written and read on the main stream only)
     float* d_maps[2] = {nullptr, nullptr}; size_t d_maps_bytes[2] = {0, 0};   // bf16 path: f32 NCHW heat / PAF of the last stage
     // post-processing
     PostCaps caps;
@@ -277,6 +280,8 @@ extern "C" int lwp_destroy(lwp_handle h) {
         if (h->pin_ev[k]) (void)hipEventDestroy(h->pin_ev[k]);
     }
     if (h->d_pre_tab) (void)hipFree(h->d_pre_tab);
+    for (auto& rt : h->pre_tabs) if (rt.d) (void)hipFree(rt.d);
+    if (h->d_pipe_in) (void)hipFree(h->d_pipe_in);
     if (h->d_blob) (void)hipFree(h->d_blob);
     if (h->d_zeros) (void)hipFree(h->d_zeros);
     if (h->d_limbs) (void)hipFree(h->d_limbs);
@@ -1379,10 +1384,11 @@ static int ensure_tail_state(lwp_context* h, int lanes) {
 }
 
 // the tail's launches for the N frames of `ws`, behind assemble_kernel on the same stream
-static int enqueue_tail(lwp_context* h, PostWorkspace& ws, int N, int ratio, hipStream_t s) {
+// (unmap: the geometry of THIS run, passed to the launch by value — lwp_pipeline_submit_u8; null: the handle's lwp_set_unmap state)
+static int enqueue_tail(lwp_context* h, PostWorkspace& ws, int N, int ratio, hipStream_t s, const TailParams* unmap = nullptr) {
     if (&ws == &h->ws) h->run_has_tail = ws.tail != 0; // (the serial path; a pipeline slot keeps its own tail_N)
     if (!ws.tail) return LWP_OK;
-    TailParams p = h->tail;
+    TailParams p = unmap ? *unmap : h->tail;
     p.ratio = ratio;
     if (p.mode >= 2) { int rc = ensure_tail_state(h, p.mode == 2 ? N : 1); if (rc) return rc; }
     LAUNCH_ON(h, s, KC_POST, launch_tail_rows(N, ws, p, 0, s));
@@ -1511,7 +1517,12 @@ extern "C" int lwp_infer_poses(lwp_handle h, const float* in, int in_mem, int N,
 }
 
 // ---------------------------------------------------------------------------------------------- pipelined streaming
+static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot, const TailParams* unmap);
 extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot) {
+    return pipeline_submit_impl(h, in_device, N, H, W, ratio, demo, slot, nullptr);
+}
+// unmap != null: the pose tail of this submit un-maps with these values instead of the handle's (lwp_pipeline_submit_u8)
+static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot, const TailParams* unmap) {
     if (!h || !in_device || slot < 0 || slot > 1) return fail(h, LWP_ERR_ARG, "bad argument");
     int rc = check_frame_shape(h, N, H, W);
     if (rc == LWP_OK) rc = check_pose_frame(h, H, W, ratio);
@@ -1562,7 +1573,7 @@ extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, 
     // post-processing + result copy on the second stream
     if (h->post_stream != h->stream) HIP_TRY(h, hipStreamWaitEvent(h->post_stream, sl.ev_maps, 0));
     rc = enqueue_grouping(h, nchw_view(sl.maps[0], g.NH, fh, fw), nchw_view(sl.maps[1], g.NP, fh, fw), N, ratio, demo, sl.ws, h->post_stream);
-    if (rc == LWP_OK) rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream);
+    if (rc == LWP_OK) rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream, unmap);
     if (rc) return rc;
     sl.tail_N = sl.ws.tail ? N : 0;
     HIP_TRY(h, launch_publish(N, sl.ws, sl.h_stage, h->post_stream));
@@ -1581,6 +1592,143 @@ extern "C" int lwp_pipeline_fetch(lwp_handle h, int slot, int* kpt_counts, doubl
     HIP_TRY(h, hipEventSynchronize(sl.ev_done));
     sl.pending = false;
     return parse_results(h, sl.ws, sl.h_stage, sl.N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
+}
+
+// ---------------------------------------------------------------------------------------------- batched uint8 front end
+struct PreGeom { int dh, dw, Hp, Wp, pad[4]; double sc; };
+
+// the argument checks of the two batched uint8 entry points: host arithmetic only, so they run with h == NULL too
+static int check_u8_batch_args(lwp_context* h, const void* imgs, int img_mem, int N, int H, int W, int net_input_height, int stride,
+                               const double* pad_value, const double* img_mean, PreGeom* g) {
+    if (!imgs) return fail(h, LWP_ERR_ARG, "imgs is null");
+    if (!pad_value || !img_mean) return fail(h, LWP_ERR_ARG, "pad_value / img_mean is null");
+    if (img_mem != LWP_MEM_HOST && img_mem != LWP_MEM_DEVICE) return fail(h, LWP_ERR_ARG, "img_mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+    if (N < 1) return fail(h, LWP_ERR_ARG, "N must be at least 1");
+    if (N > 65535) return fail(h, LWP_ERR_ARG, "at most 65535 frames per call");
+    int rc = lwp_preprocess_dims(H, W, net_input_height, stride, &g->dh, &g->dw, &g->Hp, &g->Wp, g->pad, &g->sc);
+    if (rc) return fail(h, rc, "bad frame / network size");
+    if (g->pad[0] < 0 || g->pad[1] < 0 || g->pad[2] < 0 || g->pad[3] < 0) return fail(h, LWP_ERR_ARG, "negative padding");
+    if (g->Hp < 8 || g->Wp < 8) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "frame too small: the padded network input is %d x %d, the network needs at least 8 x 8", g->Hp, g->Wp);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    return LWP_OK;
+}
+
+// device tables of a geometry, built and uploaded once and then only read
+static int pre_tables(lwp_context* h, int H, int W, const PreGeom& g, const int** tab) {
+    for (const auto& rt : h->pre_tabs)
+        if (rt.cw == W && rt.ch == H && rt.dw == g.dw && rt.dh == g.dh && rt.ratio == g.sc) { *tab = (const int*)rt.d; return LWP_OK; }
+    const size_t nx = (size_t)g.dw * 4, ny = (size_t)g.dh * 4;
+    std::vector<int> xi, xw, yi, yw;
+    build_resize_table_u8(W, g.dw, g.sc, xi, xw);
+    build_resize_table_u8(H, g.dh, g.sc, yi, yw);
+    if (h->pre_tabs.size() >= 16) {                      // bounded: drop the oldest geometry once nothing queued can read it
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->pre_tabs.front().d);
+        h->pre_tabs.erase(h->pre_tabs.begin());
+    }
+    void* d = nullptr;
+    HIP_TRY(h, hipMalloc(&d, (nx + ny) * 8));
+    int* t = (int*)d;
+    hipError_t e = hipMemcpy(t, xi.data(), nx * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t + nx, xw.data(), nx * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t + 2 * nx, yi.data(), ny * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t + 2 * nx + ny, yw.data(), ny * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(h, LWP_ERR_HIP, std::string("hipMemcpy(resize tables): ") + hipGetErrorString(e)); }
+    h->pre_tabs.push_back({W, H, g.dw, g.dh, d, g.sc});
+    *tab = t;
+    return LWP_OK;
+}
+
+// upload (host frames) + the batched kernel on the main stream; *consumed as upload_host reports it
+static int enqueue_u8_batch(lwp_context* h, const unsigned char* imgs, int img_mem, int N, int H, int W, const PreGeom& g,
+                            const double* pad_value, const double* img_mean, double img_scale, float* out, bool* consumed) {
+    *consumed = true;
+    const unsigned char* d_src = imgs;
+    if (img_mem == LWP_MEM_HOST) {
+        const size_t ib = (size_t)N * H * W * 3;
+        if (h->d_imgs_bytes < ib) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            if (h->d_imgs) HIP_TRY(h, hipFree(h->d_imgs));
+            h->d_imgs = nullptr; h->d_imgs_bytes = 0;
+            HIP_TRY(h, hipMalloc((void**)&h->d_imgs, ib));
+            h->d_imgs_bytes = ib;
+        }
+        int rc = upload_host(h, imgs, ib, h->d_imgs, consumed);
+        if (rc) return rc;
+        d_src = h->d_imgs;
+    }
+    const int* t = nullptr;
+    int rc = pre_tables(h, H, W, g, &t);
+    if (rc) return rc;
+    const size_t nx = (size_t)g.dw * 4, ny = (size_t)g.dh * 4;
+    PreprocParams p;
+    p.src = d_src; p.Hs = H; p.Ws = W;
+    p.xi = t; p.xw = t + nx; p.yi = t + 2 * nx; p.yw = t + 2 * nx + ny;
+    p.dh = g.dh; p.dw = g.dw; p.top = g.pad[0]; p.left = g.pad[1]; p.Hp = g.Hp; p.Wp = g.Wp;
+    for (int c = 0; c < 3; ++c) { p.mean[c] = img_mean[c]; p.pad_value[c] = (float)pad_value[c]; }
+    p.scale = img_scale;
+    p.out = out;
+    LAUNCH(h, KC_POST, launch_preprocess_u8_batch(p, N, h->tune.pre_batch_vec == 1, h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_preprocess_u8_batch(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, int net_input_height,
+                                       int stride, const double* pad_value, const double* img_mean, double img_scale, float* out_device) {
+    PreGeom g;
+    int rc = check_u8_batch_args(h, imgs, img_mem, N, H, W, net_input_height, stride, pad_value, img_mean, &g);
+    if (rc) return rc;
+    if (!out_device) return fail(h, LWP_ERR_ARG, "out_device is null");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);                                    // device frames produced / output buffer last used on the caller's stream
+    if (rc) return rc;
+    bool consumed = true;
+    rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, out_device, &consumed);
+    if (rc) return rc;
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (img_mem == LWP_MEM_HOST) {                       // as lwp_preprocess_u8: host frames are free on return
+        if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+        else if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, int net_input_height,
+                                      int stride, const double* pad_value, const double* img_mean, double img_scale, int ratio,
+                                      int demo, int slot) {
+    PreGeom g;
+    int rc = check_u8_batch_args(h, imgs, img_mem, N, H, W, net_input_height, stride, pad_value, img_mean, &g);
+    if (rc) return rc;
+    if (slot < 0 || slot > 1) return fail(h, LWP_ERR_ARG, "slot must be 0 or 1");
+    if (ratio != 4 && ratio != 8) return fail(h, LWP_ERR_ARG, "upsample ratio must be 4 or 8");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    rc = check_frame_shape(h, N, g.Hp, g.Wp);
+    if (rc == LWP_OK) rc = check_pose_frame(h, g.Hp, g.Wp, ratio);
+    if (rc) return rc;
+    if (h->slots[slot].pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
+    if (h->tail.mode && h->caps.max_entries > kTailMaxPoses)
+        return fail(h, LWP_ERR_ARG, "the pose tail (lwp_set_tracking) holds at most 256 poses per frame: lower max_pose_entries or turn it off");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    const size_t xb = (size_t)N * 3 * g.Hp * g.Wp * sizeof(float);
+    if (h->d_pipe_in_bytes < xb) {                       // the network of the other slot may still read the old tensor
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        rc = ensure_dev(h, &h->d_pipe_in, &h->d_pipe_in_bytes, xb);
+        if (rc) return rc;
+    }
+    bool consumed = true;
+    rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, h->d_pipe_in, &consumed);
+    if (rc) return rc;
+    if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));    // (batches beyond the pinned staging limit: the copy is waited for)
+    TailParams um = h->tail;                             // this submit's un-map, by value: the handle's lwp_set_unmap state is not touched
+    um.stride = stride; um.scale = g.sc; um.pad_top = g.pad[0]; um.pad_left = g.pad[1];
+    return pipeline_submit_impl(h, h->d_pipe_in, N, g.Hp, g.Wp, ratio, demo, slot, &um);
 }
 
 extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float* paf, int mem, int layout, int N, int hs, int ws, int ratio,

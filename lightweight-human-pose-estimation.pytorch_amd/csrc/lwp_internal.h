@@ -117,6 +117,7 @@ struct Tuning {
     int post_nchw = -1;                                            // LWP_POST_NCHW (f32: "0" = grouping reads the NHWC concat buffer in place)
     int heads_f32_max_m = 0;                                       // LWP_HEADS_F32_MAXM (tests: force the fused fp32 head pair at larger M)
     int fuse_dwpw = -1, merge_heads = -1, fuse_heads = -1;         // LWP_FUSE_DWPW, LWP_MERGE_HEADS, LWP_FUSE_HEADS ("0": depthwise + pointwise / heat + PAF heads / a stage's head pair as separate launches)
+    int pre_batch_vec = -1;                                        // LWP_PRE_BATCH_VEC ("1": the batched uint8 pre-processing with four pixels per thread; default: one thread per pixel)
     int post_stream = -1, post_generic = -1;                       // LWP_POST_STREAM ("0": a pipeline slot's grouping follows the network on the main stream), LWP_POST_GENERIC ("1": the generic grouping kernels under the default skeleton too)
 };
 Tuning tuning_from_env();
@@ -349,6 +350,9 @@ struct PreprocParams {
 };
 void build_resize_table_u8(int n_src, int n_dst, double inv_scale, std::vector<int>& idx, std::vector<int>& w);
 hipError_t launch_preprocess_u8(const PreprocParams& p, hipStream_t s);
+// N same-sized frames (src: N x Hs x Ws x 3, out: N x 3 x Hp x Wp), the tables shared; allow_vec: four pixels per thread with
+// 16-byte stores where the geometry permits (false: one thread per pixel)
+hipError_t launch_preprocess_u8_batch(const PreprocParams& p, int N, bool allow_vec, hipStream_t s);
 // N uint8 frames -> normalised float64 image, cubic resize by a ratio (f32 coefficients, f64 sums), pad, NCHW float32 (val.py:84-93)
 struct PreScaleParams {
     const void* src; int N, Hs, Ws;                  // N x Hs x Ws x 3 uint8 (float32 when src_f32)

@@ -1938,7 +1938,7 @@ Tuning tuning_from_env() {
     geti("LWP_HEADS_F32_MAXM", &t.heads_f32_max_m);
     geti("LWP_MAX_FRAMES_PER_PASS", &t.max_frames_per_pass);
     digit("LWP_FUSE_DWPW", &t.fuse_dwpw); digit("LWP_MERGE_HEADS", &t.merge_heads); digit("LWP_FUSE_HEADS", &t.fuse_heads);
-    digit("LWP_POST_STREAM", &t.post_stream); digit("LWP_POST_GENERIC", &t.post_generic);
+    digit("LWP_PRE_BATCH_VEC", &t.pre_batch_vec); digit("LWP_POST_STREAM", &t.post_stream); digit("LWP_POST_GENERIC", &t.post_generic);
     return t;
 }
 

@@ -782,6 +782,67 @@ hipError_t launch_preprocess_u8(const PreprocParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// The same for N same-sized frames in ONE launch (lwp_preprocess_u8_batch, lwp_pipeline_submit_u8): the arithmetic of
+// preprocess_u8_kernel, the frame index in blockIdx.z, the resize tables shared by the frames and read as int4 (a destination
+// index owns four taps and four weights, 16-byte aligned by construction).  PX = 1: one thread per output pixel, like the
+// single-frame kernel.  PX = 4: a thread owns four neighbouring pixels of a row — the row's y taps are read once and every
+// plane gets one 16-byte store (the launcher takes this form when Wp % 4 == 0 and the output is 16-byte aligned).
+template <int PX>
+__global__ void __launch_bounds__(256) preprocess_u8_batch_kernel(PreprocParams p) {
+    const int x0 = (blockIdx.x * 256 + threadIdx.x) * PX, y = blockIdx.y, n = blockIdx.z;
+    if (x0 >= p.Wp) return;
+    const int yy = y - p.top;
+    const int64_t plane = (int64_t)p.Hp * p.Wp;
+    float* o = p.out + (int64_t)n * 3 * plane + (int64_t)y * p.Wp + x0;
+    const unsigned char* img = p.src + (int64_t)n * p.Hs * p.Ws * 3;
+    const bool row_in = yy >= 0 && yy < p.dh;
+    int4 yi = make_int4(0, 0, 0, 0), yw = make_int4(0, 0, 0, 0);
+    if (row_in) { yi = ((const int4*)p.yi)[yy]; yw = ((const int4*)p.yw)[yy]; }
+    const int yo[4] = {yi.x, yi.y, yi.z, yi.w}, wyv[4] = {yw.x, yw.y, yw.z, yw.w};
+    float r[3][PX];
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+        const int xx = x0 + i - p.left;
+        if (!row_in || xx < 0 || xx >= p.dw) {
+            r[0][i] = p.pad_value[0]; r[1][i] = p.pad_value[1]; r[2][i] = p.pad_value[2];
+            continue;
+        }
+        const int4 xi = ((const int4*)p.xi)[xx], xw = ((const int4*)p.xw)[xx];
+        const int xo[4] = {xi.x * 3, xi.y * 3, xi.z * 3, xi.w * 3}, wx[4] = {xw.x, xw.y, xw.z, xw.w};
+        long long acc[3] = {0, 0, 0};
+#pragma unroll
+        for (int ky = 0; ky < 4; ++ky) {
+            const unsigned char* row = img + (int64_t)yo[ky] * p.Ws * 3;
+            const long long wy = wyv[ky];
+            int t0 = 0, t1 = 0, t2 = 0;
+#pragma unroll
+            for (int kx = 0; kx < 4; ++kx) {
+                const unsigned char* q = row + xo[kx];
+                t0 += (int)q[0] * wx[kx]; t1 += (int)q[1] * wx[kx]; t2 += (int)q[2] * wx[kx];
+            }
+            acc[0] += t0 * wy; acc[1] += t1 * wy; acc[2] += t2 * wy;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            long long v = (acc[c] + (1ll << 21)) >> 22;
+            v = v < 0 ? 0 : (v > 255 ? 255 : v);
+            r[c][i] = (float)__dmul_rn(__dsub_rn((double)v, p.mean[c]), p.scale);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if constexpr (PX == 4) *(float4*)(o + c * plane) = make_float4(r[c][0], r[c][1], r[c][2], r[c][3]);
+        else o[c * plane] = r[c][0];
+    }
+}
+hipError_t launch_preprocess_u8_batch(const PreprocParams& p, int N, bool allow_vec, hipStream_t s) {
+    if (N < 1 || N > 65535) return hipErrorInvalidValue;                 // the frame index is a grid dimension
+    const bool vec = allow_vec && p.Wp % 4 == 0 && ((uintptr_t)p.out & 15) == 0;
+    if (vec) hipLaunchKernelGGL(preprocess_u8_batch_kernel<4>, dim3((p.Wp / 4 + 255) / 256, p.Hp, N), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(preprocess_u8_batch_kernel<1>, dim3((p.Wp + 255) / 256, p.Hp, N), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ multi-scale image side
 // val.py:84-93 on the device for N same-sized uint8 frames and one scale ratio.  The normalised image is float64 in the
 // reference ((float32(u8) - mean) * scale with a Python tuple: NumPy promotes to float64), cv2.resize of a float64 image

@@ -47,7 +47,8 @@ def poses_from_entries(pose_entries, all_keypoints, scale, pad, stride=8, upsamp
     return poses
 
 
-def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, draw=False, device_tail=False, sigmas=None):
+def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, draw=False, device_tail=False, sigmas=None,
+             pipelined=False):
     """Generator over frames: yields (img, current_poses).  No GUI (cv2.imshow/waitKey are out of scope).
     Pose / tracking are COCO-18 (modules/pose.py), as in the reference: an engine with a custom skeleton raises ValueError,
     unless ``device_tail=True`` and ``sigmas`` (K values, as ``Pose.sigmas`` holds them) are given.
@@ -56,14 +57,26 @@ def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, 
     int32 pose rows, ``track_poses`` and the 1-Euro smoothing.  The yielded ``Pose`` objects are filled from the returned arrays
     (see ``poses_from_arrays``: their ``.filters`` is None, the filter state lives on the device).  Ids start at
     ``Pose.last_id + 1`` and ``Pose.last_id`` is written back after every frame, so code that mixes both paths sees one
-    counter.  The engine's tracking setting is switched on for the run and off again when the generator ends."""
+    counter.  The engine's tracking setting is switched on for the run and off again when the generator ends.
+
+    ``pipelined=True`` (needs ``device_tail=True``) drives the same loop through ``Engine.pipeline_submit_u8``: one call per
+    frame enqueues upload, pre-processing, network, grouping and tail, and frame k + 1 is submitted before frame k is fetched
+    (two alternating slots), so the host work of one frame overlaps the GPU work of the next.  The yielded sequence, the ids
+    and ``Pose.last_id`` are those of the serial device-tail run.  The provider is read ONE FRAME AHEAD: when frame k is
+    yielded, frame k + 1 has already been taken from it — a provider that hands out the same buffer again and again must
+    copy.  ``draw=True`` draws on the frame the poses belong to.  When the generator ends or is closed early, the slot still
+    in flight is fetched and tracking is switched off."""
     K = net.engine.skeleton["num_kpt_types"]
+    if pipelined and not device_tail:
+        raise ValueError("run_demo(pipelined=True) needs device_tail=True (and fused=True): the pipelined loop reads its poses from the device tail")
     if device_tail and not fused:
         raise ValueError("run_demo(device_tail=True) needs fused=True: the pose tail runs behind the fused grouping kernels")
     if K != Pose.num_kpts and (draw or not device_tail or sigmas is None):
         raise ValueError("run_demo draws and tracks COCO poses of %d key-points; the engine's skeleton has %d key-point types "
                          "(use infer_poses / poses_from_maps for custom skeletons, or device_tail=True with sigmas and draw=False)"
                          % (Pose.num_kpts, K))
+    if pipelined:
+        return _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, sigmas)
     if device_tail:
         return _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas)
     return _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw)
@@ -93,6 +106,124 @@ def _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigm
             yield img, current_poses
     finally:
         eng.set_tracking(eng.TRACK_OFF)
+
+
+def _drain(eng, in_flight):
+    """The end of a pipelined loop: every slot still in flight is fetched and tracking is switched off.  An error of such a
+    fetch is not lost: all slots are tried, tracking is switched off, and then the first error is raised."""
+    first = None
+    while in_flight:
+        _, slot = in_flight.pop(0)
+        try:
+            eng.pipeline_fetch(slot)
+        except Exception as e:
+            if first is None:
+                first = e
+    try:
+        eng.set_tracking(eng.TRACK_OFF)
+    finally:
+        if first is not None:
+            raise first
+
+
+def _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, sigmas):
+    net = net.eval()
+    eng = net.engine
+    stride, upsample_ratio = 8, 4
+    if sigmas is None:
+        sigmas = Pose.sigmas
+    eng.set_tracking(eng.TRACK_LANES if track else eng.TRACK_ROWS, smooth=smooth, sigmas=sigmas)
+    in_flight = []                                   # [(img, slot)], oldest first: at most two
+
+    def finish():
+        img, slot = in_flight.pop(0)
+        eng.pipeline_fetch(slot)
+        rows = eng.poses(slot)[0]
+        current_poses = poses_from_arrays(rows["keypoints"], rows["confidence"], rows["bbox"], rows["ids"] if track else None)
+        if track:
+            Pose.last_id = rows["last_id"]
+        if draw:
+            for pose in current_poses:
+                pose.draw(img)
+        return img, current_poses
+
+    try:
+        if track:
+            eng.reset_tracking(0, Pose.last_id + 1)
+        k = 0
+        for img in image_provider:
+            eng.pipeline_submit_u8(img, k % 2, height_size, stride, upsample_ratio=upsample_ratio, demo=True)
+            in_flight.append((img, k % 2))
+            k += 1
+            if len(in_flight) == 2:
+                yield finish()
+        while in_flight:
+            yield finish()
+    finally:
+        _drain(eng, in_flight)                       # closed early (or an error): no slot stays pending
+
+
+def run_cameras(net, providers, height_size, track, smooth, sigmas=None):
+    """N same-sized camera streams, one batch per step: yields a list of N (img, poses) per step and stops when the first
+    provider ends.  Frame f of every batch is lane f of the device tail (``Engine.TRACK_LANES``): each stream is tracked on its
+    own, with its own ids, and the results of stream f are those of ``run_demo(..., fused=True, device_tail=True)`` over
+    provider f alone — at the same number of frames per network pass: the fp32 network picks its kernels by the batch of a
+    pass, so a ``confidence`` (a sum of float32 map values) of a batch-N step may differ from the batch-1 run's in its last
+    bits (1e-6 level), while an engine that walks the batch one frame per pass gives the single-stream bits throughout.
+    Every lane gives out ids from ``Pose.last_id + 1`` on; ``Pose.last_id`` itself is left alone (the ids
+    are per lane, there is no single counter to write back).  Pipelined like ``run_demo(pipelined=True)``: the providers are read
+    one step ahead.  The arguments are checked at the call (ValueError), like ``run_demo``'s; a mismatch of frame sizes shows
+    at the step that meets it."""
+    net = net.eval()
+    eng = net.engine
+    stride, upsample_ratio = 8, 4
+    K = eng.skeleton["num_kpt_types"]
+    if K != Pose.num_kpts and sigmas is None:
+        raise ValueError("run_cameras tracks COCO poses of %d key-points; the engine's skeleton has %d key-point types (give sigmas)"
+                         % (Pose.num_kpts, K))
+    if sigmas is None:
+        sigmas = Pose.sigmas
+    providers = [iter(p) for p in providers]
+    if not providers:
+        raise ValueError("run_cameras needs at least one provider")
+    return _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, upsample_ratio)
+
+
+def _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, upsample_ratio):
+    eng.set_tracking(eng.TRACK_LANES if track else eng.TRACK_ROWS, smooth=smooth, sigmas=sigmas)
+    in_flight = []
+
+    def finish():
+        imgs, slot = in_flight.pop(0)
+        eng.pipeline_fetch(slot)
+        return [(img, poses_from_arrays(r["keypoints"], r["confidence"], r["bbox"], r["ids"] if track else None))
+                for img, r in zip(imgs, eng.poses(slot))]
+
+    try:
+        if track:
+            eng.reset_tracking(-1, Pose.last_id + 1)
+        k = 0
+        while True:
+            imgs = []
+            for p in providers:
+                try:
+                    imgs.append(next(p))
+                except StopIteration:
+                    break
+            if len(imgs) < len(providers):
+                break
+            shapes = set(np.shape(i) for i in imgs)
+            if len(shapes) != 1:
+                raise ValueError("run_cameras needs same-sized frames, got %s" % sorted(shapes))
+            eng.pipeline_submit_u8(np.stack(imgs), k % 2, height_size, stride, upsample_ratio=upsample_ratio, demo=True)
+            in_flight.append((imgs, k % 2))
+            k += 1
+            if len(in_flight) == 2:
+                yield finish()
+        while in_flight:
+            yield finish()
+    finally:
+        _drain(eng, in_flight)
 
 
 def _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw):

@@ -198,6 +198,38 @@ class Engine(object):
             x._lwp_stream_owner = self            # produced on this engine's stream, not visible to torch's stream
         return x, scale, pad
 
+    def _u8_frames(self, frames):
+        """(pointer, mem flag, N, H, W, the array kept alive) of a uint8 frame batch (N,H,W,3) or one frame (H,W,3), numpy or a
+        cuda tensor on this engine's GPU."""
+        torch = _torch()
+        on_dev = getattr(frames, "is_cuda", False)
+        a = frames.contiguous() if on_dev else np.ascontiguousarray(frames)
+        if a.dtype != (torch.uint8 if on_dev else np.uint8) or len(a.shape) not in (3, 4) or a.shape[-1] != 3:
+            raise TypeError("frames must be (N,)HxWx3 uint8")
+        shp = tuple(a.shape) if len(a.shape) == 4 else (1,) + tuple(a.shape)
+        if on_dev:
+            if a.device.index != self.device_id:
+                raise ValueError("frames are on cuda:%d but the engine lives on cuda:%d" % (a.device.index, self.device_id))
+            return a.data_ptr(), MEM_DEVICE, int(shp[0]), int(shp[1]), int(shp[2]), a
+        return a.ctypes.data, MEM_HOST, int(shp[0]), int(shp[1]), int(shp[2]), a
+
+    def preprocess_u8_batch(self, frames, net_input_height_size, stride, pad_value=(0, 0, 0), img_mean=(128, 128, 128), img_scale=1 / 256,
+                            hand_over=True):
+        """N same-sized uint8 frames (N,H,W,3) or one (H,W,3), numpy or cuda tensor -> (x: N x 3 x H' x W' float32 cuda tensor,
+        scale, pad): ``preprocess_u8`` for a batch in ONE launch (demo.py:55-64 per frame, same bits)."""
+        torch = _torch()
+        ptr, mem, N, H, W, a = self._u8_frames(frames)
+        _, _, oh, ow, pad, scale = self.preprocess_dims(H, W, net_input_height_size, stride)
+        x = torch.empty((N, 3, oh, ow), dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        pv = (C.c_double * 3)(*[float(v) for v in pad_value])
+        mv = (C.c_double * 3)(*[float(v) for v in img_mean])
+        self._order(hand_over=hand_over)
+        check(lib().lwp_preprocess_u8_batch(self.h.ptr, ptr, mem, N, H, W, net_input_height_size, stride, pv, mv, float(img_scale),
+                                            x.data_ptr()), self.h.ptr)
+        if not hand_over:
+            x._lwp_stream_owner = self
+        return x, scale, pad
+
     @staticmethod
     def scale_dims(height, width, ratio, base_height, stride):
         """(scaled_h, scaled_w, out_h, out_w, pad [top,left,bottom,right]) of val.py:89-91 for a height x width frame."""
@@ -441,6 +473,23 @@ class Engine(object):
         self._keep_slot = getattr(self, "_keep_slot", {})
         self._keep_slot[slot] = (x_cuda, N)
         check(lib().lwp_pipeline_submit(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, slot), self.h.ptr)
+
+    def pipeline_submit_u8(self, frames, slot, net_input_height_size, stride=8, pad_value=(0, 0, 0), img_mean=(128, 128, 128),
+                           img_scale=1 / 256, upsample_ratio=4, demo=True):
+        """One-call video step (demo.py:55-68 + 91-118): uint8 frames (N,H,W,3) or (H,W,3), numpy or cuda tensor -> upload,
+        batched pre-processing, network, grouping and (if ``set_tracking`` is on) the pose tail, all enqueued; returns at once.
+        Read the results with ``pipeline_fetch(slot)`` and ``poses(slot)``.  The tail un-maps with this submit's own stride,
+        scale and pad (``preprocess_dims`` of the frame size): ``set_unmap`` is neither used nor changed.  A numpy frame buffer
+        may be reused on return; a cuda tensor is kept alive until the slot is fetched."""
+        ptr, mem, N, H, W, a = self._u8_frames(frames)
+        pv = (C.c_double * 3)(*[float(v) for v in pad_value])
+        mv = (C.c_double * 3)(*[float(v) for v in img_mean])
+        if mem == MEM_DEVICE:
+            self._order(a.device)
+        check(lib().lwp_pipeline_submit_u8(self.h.ptr, ptr, mem, N, H, W, net_input_height_size, stride, pv, mv, float(img_scale),
+                                           upsample_ratio, 1 if demo else 0, slot), self.h.ptr)
+        self._keep_slot = getattr(self, "_keep_slot", {})
+        self._keep_slot[slot] = (a if mem == MEM_DEVICE else None, N)
 
     def pipeline_fetch(self, slot):
         _, N = self._keep_slot[slot]
