@@ -1591,19 +1591,25 @@ hipError_t launch_dwpw(const DwPwParams& p_in, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------- stage heads, both 1x1 convs in one kernel
 // out[m] = W1 . relu(W0 . x[m] + b0) + b1 (with_mobilenet.py:32-45, the merged heat / PAF pair) for small M (batch 1: 3772
-// pixels, where each of the two GEMM launches is mostly launch / ramp / tail).  Workgroup = 16 pixels x 8 waves; the hidden
-// dimension is split over the waves in tiles of 16 channels.  v_mfma_f32_16x16x4_f32 with the weights as the A operand:
+// pixels, where each of the two GEMM launches is mostly launch / ramp / tail).  Workgroup = 32 pixels of ONE head x 8 waves (the
+// second conv of a merged pair is block-diagonal: a head's outputs read its own half of the hidden vector only, so a workgroup
+// streams its own head's W0 rows and nothing of the other's; an un-merged pair is one head over the whole hidden dimension).  The
+// head's hidden channels are split over the waves in tiles of 16; every weight fragment feeds TWO 16-pixel column blocks, i.e.
+// two independent accumulator chains.  v_mfma_f32_16x16x4_f32 with the weights as the A operand:
 //   GEMM 1: D[hidden 16][pixel 16].  The summation index is free to permute: k-slot (step s = 4 u + c, lane group q) is read as
 //           input channel 32 q + 4 u + c, so a lane's operands are 128 contiguous bytes of its own row — eight 16-byte loads of
 //           the PLAIN [hidden][128] weight rows (fully coalesced, no packing), and of the pixel's own NHWC row, kept for all tiles.
 //   D leaves lane (pixel i, q) with hidden channels 4 q + r, r = 0..3: after bias + ReLU, register r IS the B operand of GEMM 2's
 //   step r if k-slot q of that step means hidden 4 q + r — i.e. the W1 fragment of lane (out channel i, q) is the 16-byte vector
 //   W1[out][16 tile + 4 q .. + 3].  The hidden values never leave the lane's registers.
-//   GEMM 2 accumulates all 64 (57 used) output channels per wave over its hidden tiles; the NW partial results are summed in the
-//   fixed order 0..NW-1 through LDS.  Weight loads are buffer loads with wave-uniform tile offsets, requested one tile ahead.
+//   GEMM 2 accumulates the head's own output tiles (2 or 3 of the 4 at 19 + 38 channels; a tile that straddles the split is
+//   computed by both heads' workgroups and each stores its own channels) per wave over its hidden tiles; the NW partial results
+//   are summed in the fixed order 0..NW-1 through LDS.  Weight loads are buffer loads with wave-uniform tile offsets, requested
+//   one tile ahead (two register buffers: the second pixel block's activations and accumulators take the third one's place).
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
-    extern __shared__ __attribute__((aligned(16))) float hsm[];     // [NW][4][64] f32x4 partial outputs
+    static_assert(NW == 8, "the reduction maps the 8 waves onto 2 pixel blocks x 4 output tiles");
+    extern __shared__ __attribute__((aligned(16))) float hsm[];     // [NW][2][4][64] f32x4 partial outputs
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i16 = lane & 15, q = lane >> 4;
@@ -1613,93 +1619,108 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
         const int nwg = gridDim.x, qq = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
         bid = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + (bid >> 3);
     }
-    const int m = bid * 16 + i16;
-    const bool mok = m < M;
+    // the two heads of a pixel tile are neighbours in the remapped order: same XCD, the activations come out of one L2
+    const int nheads = p.out_split > 0 ? 2 : 1;
+    const int head = nheads == 2 ? (bid & 1) : 0;
+    const int ptile = nheads == 2 ? (bid >> 1) : bid;
+    int mm[2];
+    bool mok[2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x) { mm[x] = ptile * 32 + x * 16 + i16; mok[x] = mm[x] < M; }
     const float* in = (const float*)p.in;
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)((int64_t)M * p.in_ld * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t w0r = __builtin_amdgcn_make_buffer_rsrc((void*)p.w0, 0, p.hidden * 128 * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, 64 * p.hidden * 4, 0x00020000);
     auto ld = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); };
 
-    const int ntiles = p.hidden / 16;
-    const int my = wave < ntiles ? (ntiles - wave + NW - 1) / NW : 0;            // tiles wave, wave + NW, ...
-    constexpr int HPF = 3;                              // weight tiles in registers: HPF - 1 requested ahead (a tile's MFMAs take ~0.8 us, an L2 round trip 1-2)
+    // this head's hidden tiles [ht0, ht0 + ntiles), output tiles [t_lo, t_lo + nt) and output channels [c_lo, c_hi)
+    const int ntiles = p.hidden / 16 / nheads;
+    const int ht0 = head * ntiles;
+    const int t_lo = head ? p.out_split / 16 : 0;
+    const int nt = (nheads == 2 && !head ? (p.out_split + 15) / 16 : 4) - t_lo;
+    const int c_lo = head ? p.out_split : 0, c_hi = (nheads == 2 && !head) ? p.out_split : p.cout;
+    const int my = wave < ntiles ? (ntiles - wave + NW - 1) / NW : 0;            // tiles wave, wave + NW, ... of the head
+    constexpr int HPF = 2;                              // weight tiles in registers: one requested ahead
     f32x4 w0v[HPF][8], w1v[HPF][4], b0v[HPF];
     const __amdgpu_buffer_rsrc_t b0r = __builtin_amdgcn_make_buffer_rsrc((void*)p.b0, 0, p.hidden * 4, 0x00020000);
     const unsigned w0_lane = (unsigned)(i16 * 128 + 32 * q) * 4u, w1_lane = (unsigned)(i16 * p.hidden + 4 * q) * 4u;
     auto request = [&](int k, f32x4* a, f32x4* b, f32x4* bias) {                               // k-th tile of this wave (clamped: no branch around loads)
-        const int ht = wave + (k < my ? k : (my > 0 ? my - 1 : 0)) * NW;
-        const int htc = ht < ntiles ? ht : 0;
+        const int hl = wave + (k < my ? k : (my > 0 ? my - 1 : 0)) * NW;
+        const int htc = ht0 + (hl < ntiles ? hl : 0);
 #pragma unroll
         for (int u = 0; u < 8; ++u) a[u] = ld(w0r, w0_lane + 16u * u, (unsigned)htc * (16u * 128u * 4u));
 #pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = ld(w1r, w1_lane + (unsigned)(t * 16 * p.hidden) * 4u, (unsigned)htc * 64u);
+        for (int t = 0; t < 4; ++t) {                                                // the head's own output tiles (past the last: the last again)
+            const int to = t_lo + (t < nt ? t : nt - 1);
+            b[t] = ld(w1r, w1_lane, (unsigned)htc * 64u + (unsigned)(to * 16 * p.hidden) * 4u);
+        }
         *bias = ld(b0r, 16u * q, (unsigned)htc * 64u);                               // the tile's bias rides with its weights (exact vmcnt counting)
     };
     request(0, w0v[0], w1v[0], &b0v[0]);
-    if (HPF > 2) request(1, w0v[1], w1v[1], &b0v[1]);
-    f32x4 xf[8];
+    f32x4 xf[2][8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) xf[u] = ld(xr, mok ? (unsigned)((m * p.in_ld + 32 * q + 4 * u) * 4) : 0x80000000u, 0);
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xf[x][u] = ld(xr, mok[x] ? (unsigned)((mm[x] * p.in_ld + 32 * q + 4 * u) * 4) : 0x80000000u, 0);
 
-    f32x4 acc2[4];
+    f32x4 acc2[2][4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // block-diagonal second conv (p.out_split > 0: merged heat / PAF pair): hidden channels < hsplit feed outputs < out_split only
-    const int hsplit = p.out_split > 0 ? p.hidden / 2 : p.hidden;
-    const int t_last_lo = p.out_split > 0 ? (p.out_split + 15) / 16 : 4;     // output tiles [0, t_last_lo) hold outputs of the first block
-    const int t_first_hi = p.out_split > 0 ? p.out_split / 16 : 0;          // output tiles [t_first_hi, 4) hold outputs of the second
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc2[x][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto one = [&](int k, auto P_) {
         constexpr int P = decltype(P_)::value;
         request(k + HPF - 1, w0v[(P + HPF - 1) % HPF], w1v[(P + HPF - 1) % HPF], &b0v[(P + HPF - 1) % HPF]);
         __builtin_amdgcn_sched_barrier(0);
         const f32x4 b0 = b0v[P];
-        f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int u = 0; u < 8; ++u)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0v[P][u][c], xf[u][c], acc1, 0, 0, 0);
-        f32x4 hv;
+            for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) hv[r] = fmaxf(acc1[r] + b0[r], 0.f);
-        // merged heads: W1 is block-diagonal (heat outputs [0, out_split) read the first half of the hidden vector, PAF outputs the
-        // second), so a hidden tile only feeds the output tiles its block touches: 2 (heat) or 3 (PAF) of the 4 at 19 + 38 channels
-        const int ht = wave + (k < my ? k : 0) * NW;                     // wave-uniform
-        const bool first_half = ht * 16 < hsplit;
-        const int t_lo = first_half ? 0 : t_first_hi, t_hi = first_half ? t_last_lo : 4;
+                for (int x = 0; x < 2; ++x) acc1[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0v[P][u][c], xf[x][u][c], acc1[x], 0, 0, 0);
+        f32x4 hv[2];
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hv[x][r] = fmaxf(acc1[x][r] + b0[r], 0.f);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            if (t < t_lo || t >= t_hi) continue;                         // scalar branch around whole MFMA groups
+            if (t >= nt) continue;                                       // scalar branch around whole MFMA groups
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1v[P][t][r], hv[r], acc2[t], 0, 0, 0);
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int x = 0; x < 2; ++x) acc2[x][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1v[P][t][r], hv[x][r], acc2[x][t], 0, 0, 0);
         }
     };
     int k = 0;
     for (; k + HPF <= my; k += HPF) {
         one(k, std::integral_constant<int, 0>{});
-        one(k + 1, std::integral_constant<int, 1 % HPF>{});
-        if (HPF > 2) one(k + 2, std::integral_constant<int, 2 % HPF>{});
+        one(k + 1, std::integral_constant<int, 1>{});
     }
-    if (k < my) { one(k, std::integral_constant<int, 0>{}); ++k; }
-    if (HPF > 2 && k < my) { one(k, std::integral_constant<int, 1 % HPF>{}); ++k; }
+    if (k < my) one(k, std::integral_constant<int, 0>{});
 
-    // fixed-order reduction of the NW partial tiles: [wave][t][lane] f32x4
+    // fixed-order reduction of the NW partial tiles: [wave][pixel block][t][lane] f32x4
 #pragma unroll
-    for (int t = 0; t < 4; ++t) *(f32x4*)(hsm + ((wave * 4 + t) * 64 + lane) * 4) = acc2[t];
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) *(f32x4*)(hsm + (((wave * 2 + x) * 4 + t) * 64 + lane) * 4) = acc2[x][t];
     __syncthreads();
-    if (tid >= 256) return;
-    const int t = tid >> 6;                                   // output-channel tile of this thread (its lane keeps pixel / q)
-    f32x4 v = *(const f32x4*)(hsm + ((0 * 4 + t) * 64 + lane) * 4);
+    const int x = wave >> 2, t = wave & 3;                    // pixel block and output tile of this thread (its lane keeps pixel / q)
+    if (t >= nt) return;
+    f32x4 v = *(const f32x4*)(hsm + (((0 * 2 + x) * 4 + t) * 64 + lane) * 4);
 #pragma unroll
-    for (int w = 1; w < NW; ++w) v += *(const f32x4*)(hsm + ((w * 4 + t) * 64 + lane) * 4);
-    const int n = 16 * t + 4 * q;                             // lane (pixel i16, q) holds output channels n .. n + 3
-    if (!mok || n >= p.cout) return;
+    for (int w = 1; w < NW; ++w) v += *(const f32x4*)(hsm + (((w * 2 + x) * 4 + t) * 64 + lane) * 4);
+    const int n = 16 * (t_lo + t) + 4 * q;                    // lane (pixel i16, q) holds output channels n .. n + 3
+    const int m = x ? mm[1] : mm[0];
+    if (!(x ? mok[1] : mok[0]) || n >= c_hi || n + 3 < c_lo) return;
     v += *(const f32x4*)(p.b1 + n);
     float* out = (float*)p.out;
-    if (((p.out_ld & 3) == 0) && ((((uintptr_t)out) & 15) == 0) && n + 3 < p.cout) *(f32x4*)(out + (int64_t)m * p.out_ld + n) = v;
+    if (((p.out_ld & 3) == 0) && ((((uintptr_t)out) & 15) == 0) && n >= c_lo && n + 3 < c_hi) *(f32x4*)(out + (int64_t)m * p.out_ld + n) = v;
     else {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) if (n + r < p.cout) out[(int64_t)m * p.out_ld + n + r] = v[r];
+        for (int r = 0; r < 4; ++r) if (n + r >= c_lo && n + r < c_hi) out[(int64_t)m * p.out_ld + n + r] = v[r];
     }
     if (p.out_nchw || p.out_nchw2) {
         const int HW = p.H * p.W;
@@ -1708,7 +1729,7 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int ch = n + r;
-            if (ch >= p.cout) continue;
+            if (ch < c_lo || ch >= c_hi) continue;
             if (ch < c0) { if (p.out_nchw) p.out_nchw[((int64_t)img * c0 + ch) * HW + pix] = v[r]; }
             else if (p.out_nchw2) p.out_nchw2[((int64_t)img * (p.cout - c0) + (ch - c0)) * HW + pix] = v[r];
         }
@@ -1878,9 +1899,9 @@ __global__ void __launch_bounds__(256) heads_f32_lds_kernel(HeadsParams p) {
 
 bool heads_f32_supported(int cin_pad, int hidden, int cout_pad, int64_t M, const Tuning* tune) {
     const int64_t max_m = (tune && tune->heads_f32_max_m > 0) ? tune->heads_f32_max_m : 4096;     // LWP_HEADS_F32_MAXM (tests)
-    // every 16-pixel workgroup streams all of W0 and W1 (768 KB for the initial stage): only while the grid is ONE round of the
-    // chip (measured at batch 2, 472 workgroups: 57 us against 27 + 17 for the two GEMMs; batch 1: 29.5 against 18.6 + 9.3 with
-    // two launch floors less)
+    // every 32-pixel workgroup streams its head's W0 rows and W1 tiles (at most ~340 KB for the initial stage): only while the
+    // grid is ONE round of the chip (the 16-pixel form that streamed both heads' weights measured at batch 2, 472 workgroups:
+    // 57 us against 27 + 17 for the two GEMMs; the threshold has not been re-measured for this form)
     if (!(cin_pad == 128 && hidden % 16 == 0 && hidden >= 128 && hidden <= 4096 && cout_pad == 64)) return false;
     if (M <= max_m) return true;
     // larger M: the LDS-staged form (LWP_HEADS_F32_LDS=0: the two GEMMs, A/B)
@@ -1903,9 +1924,15 @@ hipError_t launch_heads_f32(const HeadsParams& p, hipStream_t s) {
         hipLaunchKernelGGL(heads_f32_lds_kernel<PT>, dim3((unsigned)((M + 64 * PT - 1) / (64 * PT))), dim3(256), lds2, s, p);
         return hipGetLastError();
     }
-    const size_t lds = (size_t)NW * 4 * 64 * 4 * sizeof(float);
+    // 32 pixels of one head per workgroup (merged pair: pixel tiles x 2); 64 KiB of partial sums for the fixed-order reduction
+    const size_t lds = (size_t)NW * 2 * 4 * 64 * 4 * sizeof(float);
+    const unsigned nheads = p.out_split > 0 ? 2u : 1u;
+    if (p.out_split < 0 || p.out_split >= p.cout || (nheads == 2 && p.hidden % 32)) return hipErrorInvalidValue;
+    static LdsAttrOnce attr8;
+    hipError_t e = attr8.ensure((const void*)heads_f32_kernel<NW>, 64 * 1024);
+    if (e != hipSuccess) return e;
     LWP_VARIANT(p, "heads_f32<%d>", NW);
-    hipLaunchKernelGGL(heads_f32_kernel<NW>, dim3((unsigned)((M + 15) / 16)), dim3(NW * 64), lds, s, p);
+    hipLaunchKernelGGL(heads_f32_kernel<NW>, dim3((unsigned)((M + 31) / 32) * nheads), dim3(NW * 64), lds, s, p);
     return hipGetLastError();
 }
 
