@@ -312,6 +312,45 @@ int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoints, const d
                     int* out_bbox, int* out_ids, int* last_id, unsigned* near_count);
 int lwp_debug_tracking_near(lwp_handle h, int slot, unsigned* counts, int cap);
 
+/* ---- pose overlay on the device: replaces demo.py:119-124 (pose.draw(img) per pose, cv2.addWeighted(orig_img, 0.6, img, 0.4, 0),
+ *      one cv2.rectangle per pose) for H x W x 3 uint8 frames.  OFF by default: with mode 0 every export enqueues exactly what it
+ *      did before.  The arithmetic is integer except the limb parameter, and exact:
+ *        painted set  for each pose and each of the first n_draw_limbs limbs (a, b) of the handle's skeleton table (-1: all but the
+ *                     last two, BODY_PARTS_KPT_IDS[:-2]): a disc dx*dx + dy*dy <= 9 at every end whose x != -1; if both ends are
+ *                     present, steps = max(|bx - ax|, |by - ay|, 1) and for s = 0..steps a disc dx*dx + dy*dy <= 1 at
+ *                     (trunc(qx), trunc(qy)), q = a + (b - a) * (s / steps) in float64 — one division, one multiplication, one
+ *                     addition, each rounded (no fma), truncation toward zero; clipped to the frame.  This is what the package's
+ *                     host rasteriser Pose.draw paints, bit for bit while |coordinate| <= 2^20; beyond that (pose rows saturate at
+ *                     int32) the call still neither overflows nor reads or writes out of bounds, and a launch stays O(frame size)
+ *                     per limb: only the steps whose stamps can reach the frame are walked.
+ *        blend        painted pixel: out = (6 * src + 4 * color + 5) / 10 per channel, integer division (= addWeighted with
+ *                     round-to-nearest, for every byte pair); any other pixel: out = src.  out is written from src, never in place.
+ *        boxes        (boxes != 0) a one-pixel outline in box_color per pose, after the blend and not blended; corners (x, y) and
+ *                     (x + w, y + h) inclusive, clipped; a pose without key-points has box (0,0,0,0) and paints pixel (0,0).
+ *      OUT OF SCOPE: the id label (cv2.putText, demo.py:125-127) — there is no Hershey font data to pin it against; the ids are
+ *      returned next to the frame (lwp_get_poses).  cv2.circle / cv2.line themselves: the stand-in rasteriser above is the
+ *      contract, and it is not pinned against OpenCV (like the resizes).
+ *      lwp_set_overlay: mode 0 off, 1 annotated frames kept on the device, 2 additionally copied to pinned host memory with the
+ *      slot's results.  color / box_color: 3 bytes in the frame's channel order, NULL = (0, 224, 255) / (0, 255, 0).  The argument
+ *      checks need no GPU and run with h == NULL (against 19 limbs).  LWP_ERR_STATE while a pipeline slot is pending.  The
+ *      settings other than the mode also apply to lwp_draw_poses.
+ *      lwp_pipeline_submit_u8 with mode != 0 (needs lwp_set_tracking mode >= 1, else LWP_ERR_STATE): the overlay kernels follow the
+ *      pose tail on the slot's stream and read the frame's pose count, rows (the smoothed ones) and boxes from the slot's result
+ *      block on the device.  Host frames are uploaded into a frame buffer the SLOT owns (the shared staging would be overwritten by
+ *      the next submit while this slot has yet to read it); device frames are read in place until the fetch, as promised above.
+ *      lwp_get_overlay: the N x H x W x 3 annotated frames of a FETCHED slot into dst (mem): device-to-device on the handle's
+ *      stream (lwp_set_stream applies), or to host memory from the pinned copy (mode 2; mode 1: a blocking copy).  They stay valid
+ *      until that slot is submitted again.  LWP_ERR_STATE if the slot ran without the overlay, LWP_ERR_ARG on another N, H or W.
+ *      lwp_draw_poses: the same kernels on poses the caller supplies, the counterpart of lwp_track_poses: imgs N x H x W x 3 (mem),
+ *      n_poses[N], keypoints N x pose_cap x K x 2 int32, bbox N x pose_cap x 4 int32 (host, as lwp_get_poses returns them), out
+ *      N x H x W x 3 (mem), not overlapping imgs.  Needs no weights, no network and no tail; runs on the handle's stream and
+ *      honours lwp_set_stream; complete on return unless out is device memory handed to the caller's stream.  Checks without a GPU
+ *      (h == NULL too): null pointers, the mem flags, 1 <= N <= 65535, H, W >= 1, 0 <= n_poses[f] <= pose_cap <= 65535. */
+int lwp_set_overlay(lwp_handle h, int mode, const unsigned char* color, const unsigned char* box_color, int boxes, int n_draw_limbs);
+int lwp_get_overlay(lwp_handle h, int slot, unsigned char* dst, int dst_mem, int N, int H, int W);
+int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, const int* n_poses,
+                   const int* keypoints, const int* bbox, int pose_cap, unsigned char* out, int out_mem);
+
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */
 int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio,

@@ -22,6 +22,7 @@ EXPORTS = [
     "lwp_debug_post_generic",
     "lwp_set_tracking", "lwp_set_unmap", "lwp_reset_tracking", "lwp_get_poses", "lwp_track_poses", "lwp_debug_tracking_near",
     "lwp_preprocess_u8_batch", "lwp_pipeline_submit_u8",
+    "lwp_set_overlay", "lwp_get_overlay", "lwp_draw_poses",
 ]
 
 
@@ -96,6 +97,9 @@ def lib():
     L.lwp_debug_tracking_near.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), C.c_int]
     L.lwp_preprocess_u8_batch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, vp]
     L.lwp_pipeline_submit_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int]
+    L.lwp_set_overlay.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
+    L.lwp_get_overlay.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.lwp_draw_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, vp, C.c_int]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -66,12 +66,22 @@ struct lwp_context {
         int N = 0;
         int tail_N = 0;                    // frames with pose rows in h_stage (0: submitted with the tail off)
         bool pending = false;
+        // pose overlay (lwp_set_overlay): the slot OWNS the source pixels of host frames until its overlay has run (the shared
+        // d_imgs staging is overwritten by the next submit on the main stream while this slot's post stream still reads it)
+        unsigned char* frames = nullptr; size_t frames_bytes = 0;   // uploaded host frames of this slot
+        unsigned char* ov = nullptr; size_t ov_bytes = 0;           // annotated frames, device
+        void* h_ov = nullptr; size_t h_ov_bytes = 0;                // mode 2: their pinned host copy
+        int ov_N = 0, ov_H = 0, ov_W = 0, ov_mode = 0;              // ov_N == 0: the slot ran without the overlay
     } slots[2];
     hipStream_t post_stream = nullptr;
     // pose tail (lwp_set_tracking): parameters, the lanes' device state, (2 sigma)^2 of the K key-point types
     TailParams tail;
     TailState tst;
     float* d_vars = nullptr;
+    // pose overlay (lwp_set_overlay): settings, and the device staging of lwp_draw_poses (pose arrays; frames out for host `out`)
+    struct Overlay { int mode = 0, boxes = 1, n_draw_limbs = -1; unsigned char color[3] = {0, 224, 255}, box_color[3] = {0, 255, 0}; } ovl;
+    float* d_ov_pose = nullptr; size_t d_ov_pose_bytes = 0;
+    float* d_ov_out = nullptr; size_t d_ov_out_bytes = 0;
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
     bool run_has_tail = false;             // the tail kernels ran behind the grouping whose results h->ws holds
@@ -154,7 +164,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 101; }
+extern "C" int lwp_version(void) { return 102; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -286,6 +296,8 @@ extern "C" int lwp_destroy(lwp_handle h) {
     if (h->d_zeros) (void)hipFree(h->d_zeros);
     if (h->d_limbs) (void)hipFree(h->d_limbs);
     if (h->d_vars) (void)hipFree(h->d_vars);
+    if (h->d_ov_pose) (void)hipFree(h->d_ov_pose);
+    if (h->d_ov_out) (void)hipFree(h->d_ov_out);
     free_tail_state(h);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     free_ws(h);
@@ -294,6 +306,9 @@ extern "C" int lwp_destroy(lwp_handle h) {
         free_ws_obj(sl.ws);
         for (float* p : sl.maps) if (p) (void)hipFree(p);
         if (sl.h_stage) (void)hipHostFree(sl.h_stage);
+        if (sl.frames) (void)hipFree(sl.frames);
+        if (sl.ov) (void)hipFree(sl.ov);
+        if (sl.h_ov) (void)hipHostFree(sl.h_ov);
         if (sl.ev_maps) (void)hipEventDestroy(sl.ev_maps);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     }
@@ -1517,12 +1532,79 @@ extern "C" int lwp_infer_poses(lwp_handle h, const float* in, int in_mem, int N,
 }
 
 // ---------------------------------------------------------------------------------------------- pipelined streaming
-static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot, const TailParams* unmap);
+struct OverlayJob { const unsigned char* src; int H, W; };   // the uint8 frames a submit draws on (device memory the slot may read until it is fetched)
+static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot, const TailParams* unmap,
+                                const OverlayJob* overlay = nullptr);
 extern "C" int lwp_pipeline_submit(lwp_handle h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot) {
     return pipeline_submit_impl(h, in_device, N, H, W, ratio, demo, slot, nullptr);
 }
-// unmap != null: the pose tail of this submit un-maps with these values instead of the handle's (lwp_pipeline_submit_u8)
-static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot, const TailParams* unmap) {
+// the settings of lwp_set_overlay as launch parameters (the pose arrays are filled in by the caller)
+static OverlayParams overlay_params(const lwp_context* h, const unsigned char* src, unsigned char* out, int N, int H, int W) {
+    OverlayParams p{};
+    p.src = src; p.out = out; p.N = N; p.H = H; p.W = W;
+    p.K = h->skel.K;
+    p.limbs = h->d_limbs;
+    const int L = h->skel.L, nd = h->ovl.n_draw_limbs;
+    p.n_limbs = nd < 0 ? std::max(L - 2, 0) : std::min(nd, L);      // -1: BODY_PARTS_KPT_IDS[:-2] (pose.py:51); a later, shorter skeleton clamps
+    for (int c = 0; c < 3; ++c) { p.color[c] = h->ovl.color[c]; p.box_color[c] = h->ovl.box_color[c]; }
+    p.boxes = h->ovl.boxes;
+    return p;
+}
+
+// a slot's overlay buffers for `bytes` of frames.  Growing one waits for every stream that may still read the old one: the
+// post stream (this slot's last overlay) and the main stream (an lwp_get_overlay copy, the last upload)
+static int ensure_slot_overlay(lwp_context* h, lwp_context::Slot& sl, size_t bytes, bool host_frames) {
+    const bool pinned = h->ovl.mode == 2;
+    if (sl.ov_bytes >= bytes && (!host_frames || sl.frames_bytes >= bytes) && (!pinned || sl.h_ov_bytes >= bytes)) return LWP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
+    sl.ov_N = 0;
+    if (sl.ov_bytes < bytes) {
+        if (sl.ov) HIP_TRY(h, hipFree(sl.ov));
+        sl.ov = nullptr; sl.ov_bytes = 0;
+        HIP_TRY(h, hipMalloc((void**)&sl.ov, bytes));
+        sl.ov_bytes = bytes;
+    }
+    if (host_frames && sl.frames_bytes < bytes) {
+        if (sl.frames) HIP_TRY(h, hipFree(sl.frames));
+        sl.frames = nullptr; sl.frames_bytes = 0;
+        HIP_TRY(h, hipMalloc((void**)&sl.frames, bytes));
+        sl.frames_bytes = bytes;
+    }
+    if (pinned && sl.h_ov_bytes < bytes) {
+        if (sl.h_ov) HIP_TRY(h, hipHostFree(sl.h_ov));
+        sl.h_ov = nullptr; sl.h_ov_bytes = 0;
+        HIP_TRY(h, hipHostMalloc(&sl.h_ov, bytes, hipHostMallocDefault));
+        sl.h_ov_bytes = bytes;
+    }
+    return LWP_OK;
+}
+
+// the overlay of a slot's N frames behind its tail on stream `s`: the kernels read the frame's pose count, rows and boxes from
+// the slot's result block, so nothing returns to the host in between; mode 2 adds the copy into the slot's pinned frames
+static int enqueue_slot_overlay(lwp_context* h, lwp_context::Slot& sl, const OverlayJob& job, int N, hipStream_t s) {
+    const PostWorkspace& w = sl.ws;
+    const size_t bytes = (size_t)N * job.H * job.W * 3;
+    if (!w.tail || !sl.ov || sl.ov_bytes < bytes) return fail(h, LWP_ERR_STATE, "overlay without its buffers or the pose tail");
+    OverlayParams p = overlay_params(h, job.src, sl.ov, N, job.H, job.W);
+    const int P = w.caps.max_entries;
+    p.n_poses = w.t_n; p.kp = w.t_kp; p.bbox = w.t_bbox;
+    p.kp_stride = (int64_t)P * w.K * 2; p.bbox_stride = (int64_t)P * 4;
+    p.P = P; p.K = w.K;
+    LAUNCH_ON(h, s, KC_POST, launch_overlay(p, P, s));
+    if (h->ovl.mode == 2) {
+        void* mapped = nullptr;
+        HIP_TRY(h, hipHostGetDevicePointer(&mapped, sl.h_ov, 0));
+        HIP_TRY(h, launch_fetch_host(sl.ov, mapped, bytes, s));    // (the 16-byte copy kernel; here device -> pinned host)
+    }
+    sl.ov_N = N; sl.ov_H = job.H; sl.ov_W = job.W; sl.ov_mode = h->ovl.mode;
+    return LWP_OK;
+}
+
+// unmap != null: the pose tail of this submit un-maps with these values instead of the handle's (lwp_pipeline_submit_u8);
+// overlay != null: the overlay kernels follow the tail
+static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, int H, int W, int ratio, int demo, int slot, const TailParams* unmap,
+                                const OverlayJob* overlay) {
     if (!h || !in_device || slot < 0 || slot > 1) return fail(h, LWP_ERR_ARG, "bad argument");
     int rc = check_frame_shape(h, N, H, W);
     if (rc == LWP_OK) rc = check_pose_frame(h, H, W, ratio);
@@ -1530,6 +1612,7 @@ static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, i
     HIP_TRY(h, hipSetDevice(h->device));
     lwp_context::Slot& sl = h->slots[slot];
     if (sl.pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
+    sl.ov_N = 0;
     if (!h->post_stream) {
         if (h->tune.post_stream == 0) h->post_stream = h->stream;
         else HIP_TRY(h, hipStreamCreateWithFlags(&h->post_stream, hipStreamNonBlocking));
@@ -1574,6 +1657,7 @@ static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, i
     if (h->post_stream != h->stream) HIP_TRY(h, hipStreamWaitEvent(h->post_stream, sl.ev_maps, 0));
     rc = enqueue_grouping(h, nchw_view(sl.maps[0], g.NH, fh, fw), nchw_view(sl.maps[1], g.NP, fh, fw), N, ratio, demo, sl.ws, h->post_stream);
     if (rc == LWP_OK) rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream, unmap);
+    if (rc == LWP_OK && overlay) rc = enqueue_slot_overlay(h, sl, *overlay, N, h->post_stream);
     if (rc) return rc;
     sl.tail_N = sl.ws.tail ? N : 0;
     HIP_TRY(h, launch_publish(N, sl.ws, sl.h_stage, h->post_stream));
@@ -1642,23 +1726,32 @@ static int pre_tables(lwp_context* h, int H, int W, const PreGeom& g, const int*
     return LWP_OK;
 }
 
-// upload (host frames) + the batched kernel on the main stream; *consumed as upload_host reports it
+// the shared staging of host frames (read on the main stream only)
+static int ensure_imgs_staging(lwp_context* h, size_t ib) {
+    if (h->d_imgs_bytes >= ib) return LWP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->d_imgs) HIP_TRY(h, hipFree(h->d_imgs));
+    h->d_imgs = nullptr; h->d_imgs_bytes = 0;
+    HIP_TRY(h, hipMalloc((void**)&h->d_imgs, ib));
+    h->d_imgs_bytes = ib;
+    return LWP_OK;
+}
+
+// upload (host frames) + the batched kernel on the main stream; *consumed as upload_host reports it.  own_dst: a device buffer
+// of the caller's for the uploaded frames (a slot that draws on them later) instead of the shared staging
 static int enqueue_u8_batch(lwp_context* h, const unsigned char* imgs, int img_mem, int N, int H, int W, const PreGeom& g,
-                            const double* pad_value, const double* img_mean, double img_scale, float* out, bool* consumed) {
+                            const double* pad_value, const double* img_mean, double img_scale, float* out, bool* consumed,
+                            unsigned char* own_dst = nullptr) {
     *consumed = true;
     const unsigned char* d_src = imgs;
     if (img_mem == LWP_MEM_HOST) {
         const size_t ib = (size_t)N * H * W * 3;
-        if (h->d_imgs_bytes < ib) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            if (h->d_imgs) HIP_TRY(h, hipFree(h->d_imgs));
-            h->d_imgs = nullptr; h->d_imgs_bytes = 0;
-            HIP_TRY(h, hipMalloc((void**)&h->d_imgs, ib));
-            h->d_imgs_bytes = ib;
-        }
-        int rc = upload_host(h, imgs, ib, h->d_imgs, consumed);
+        int rc = own_dst ? LWP_OK : ensure_imgs_staging(h, ib);
         if (rc) return rc;
-        d_src = h->d_imgs;
+        unsigned char* dst = own_dst ? own_dst : h->d_imgs;
+        rc = upload_host(h, imgs, ib, dst, consumed);
+        if (rc) return rc;
+        d_src = dst;
     }
     const int* t = nullptr;
     int rc = pre_tables(h, H, W, g, &t);
@@ -1713,6 +1806,9 @@ extern "C" int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, i
     if (h->slots[slot].pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
     if (h->tail.mode && h->caps.max_entries > kTailMaxPoses)
         return fail(h, LWP_ERR_ARG, "the pose tail (lwp_set_tracking) holds at most 256 poses per frame: lower max_pose_entries or turn it off");
+    const bool overlay = h->ovl.mode != 0;
+    if (overlay && !h->tail.mode)
+        return fail(h, LWP_ERR_STATE, "the overlay (lwp_set_overlay) draws the pose tail's rows: lwp_set_tracking mode >= 1 first");
     HIP_TRY(h, hipSetDevice(h->device));
     rc = order_in(h);
     if (rc) return rc;
@@ -1722,13 +1818,22 @@ extern "C" int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, i
         rc = ensure_dev(h, &h->d_pipe_in, &h->d_pipe_in_bytes, xb);
         if (rc) return rc;
     }
+    // with the overlay on, host frames are uploaded into a buffer of the SLOT: its overlay reads them on the post stream after
+    // the next submit has overwritten the shared staging on the main stream
+    lwp_context::Slot& sl = h->slots[slot];
+    const bool own = overlay && img_mem == LWP_MEM_HOST;
+    if (overlay) {
+        rc = ensure_slot_overlay(h, sl, (size_t)N * H * W * 3, own);
+        if (rc) return rc;
+    }
     bool consumed = true;
-    rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, h->d_pipe_in, &consumed);
+    rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, h->d_pipe_in, &consumed, own ? sl.frames : nullptr);
     if (rc) return rc;
     if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));    // (batches beyond the pinned staging limit: the copy is waited for)
     TailParams um = h->tail;                             // this submit's un-map, by value: the handle's lwp_set_unmap state is not touched
     um.stride = stride; um.scale = g.sc; um.pad_top = g.pad[0]; um.pad_left = g.pad[1];
-    return pipeline_submit_impl(h, h->d_pipe_in, N, g.Hp, g.Wp, ratio, demo, slot, &um);
+    const OverlayJob job{own ? sl.frames : imgs, H, W};
+    return pipeline_submit_impl(h, h->d_pipe_in, N, g.Hp, g.Wp, ratio, demo, slot, &um, overlay ? &job : nullptr);
 }
 
 extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float* paf, int mem, int layout, int N, int hs, int ws, int ratio,
@@ -1947,6 +2052,124 @@ extern "C" int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoin
     }
     if (last_id) *last_id = t.last[0];
     if (near_count) *near_count = t.near_[0];
+    return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- pose overlay: C ABI
+extern "C" int lwp_set_overlay(lwp_handle h, int mode, const unsigned char* color, const unsigned char* box_color, int boxes,
+                               int n_draw_limbs) {
+    const int L = h ? h->skel.L : 19;                  // the argument checks run without a handle too (against the default skeleton)
+    char msg[160];
+    if (mode < 0 || mode > 2) return fail(h, LWP_ERR_ARG, "overlay mode must be 0 (off), 1 (frames on the device) or 2 (also copied to pinned host memory)");
+    if (n_draw_limbs < -1 || n_draw_limbs > L) {
+        snprintf(msg, sizeof msg, "n_draw_limbs must be -1 (all but the last two) or 0..%d (the skeleton's limbs), got %d", L, n_draw_limbs);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
+    static const unsigned char kColor[3] = {0, 224, 255}, kBoxColor[3] = {0, 255, 0};      // Pose.color (pose.py:21), demo.py:124
+    for (int c = 0; c < 3; ++c) { h->ovl.color[c] = (color ? color : kColor)[c]; h->ovl.box_color[c] = (box_color ? box_color : kBoxColor)[c]; }
+    h->ovl.mode = mode;
+    h->ovl.boxes = boxes ? 1 : 0;
+    h->ovl.n_draw_limbs = n_draw_limbs;
+    return LWP_OK;
+}
+
+extern "C" int lwp_get_overlay(lwp_handle h, int slot, unsigned char* dst, int dst_mem, int N, int H, int W) {
+    if (!dst) return fail(h, LWP_ERR_ARG, "dst is null");
+    if (dst_mem != LWP_MEM_HOST && dst_mem != LWP_MEM_DEVICE) return fail(h, LWP_ERR_ARG, "dst_mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+    if (slot < 0 || slot > 1) return fail(h, LWP_ERR_ARG, "slot must be 0 or 1");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    lwp_context::Slot& sl = h->slots[slot];
+    if (sl.pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
+    if (sl.ov_N <= 0) return fail(h, LWP_ERR_STATE, "no annotated frames: the slot ran without the overlay (lwp_set_overlay), or nothing was fetched");
+    if (N != sl.ov_N || H != sl.ov_H || W != sl.ov_W) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "the slot holds %d annotated frames of %d x %d, asked for %d of %d x %d", sl.ov_N, sl.ov_H, sl.ov_W, N, H, W);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    const size_t bytes = (size_t)N * H * W * 3;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (dst_mem == LWP_MEM_HOST) {                     // the fetch has waited for the slot's stream: both copies are complete
+        if (sl.ov_mode == 2) std::memcpy(dst, sl.h_ov, bytes);
+        else HIP_TRY(h, hipMemcpy(dst, sl.ov, bytes, hipMemcpyDeviceToHost));
+        return LWP_OK;
+    }
+    int rc = order_in(h);                              // dst last used on the caller's stream
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(dst, sl.ov, bytes, hipMemcpyDeviceToDevice, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, const int* n_poses,
+                              const int* keypoints, const int* bbox, int pose_cap, unsigned char* out, int out_mem) {
+    char msg[160];
+    if (!imgs || !out) return fail(h, LWP_ERR_ARG, "imgs / out is null");
+    if (imgs == out) return fail(h, LWP_ERR_ARG, "out must not be imgs: the blend reads the source pixels");
+    if ((img_mem != LWP_MEM_HOST && img_mem != LWP_MEM_DEVICE) || (out_mem != LWP_MEM_HOST && out_mem != LWP_MEM_DEVICE))
+        return fail(h, LWP_ERR_ARG, "img_mem / out_mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+    if (N < 1) return fail(h, LWP_ERR_ARG, "N must be at least 1");
+    if (N > 65535) return fail(h, LWP_ERR_ARG, "at most 65535 frames per call");
+    if (H < 1 || W < 1) return fail(h, LWP_ERR_ARG, "empty frame");
+    if (!n_poses) return fail(h, LWP_ERR_ARG, "n_poses is null");
+    if (pose_cap < 0 || pose_cap > 65535) return fail(h, LWP_ERR_ARG, "pose_cap must be 0..65535");
+    int most = 0;
+    for (int f = 0; f < N; ++f) {
+        if (n_poses[f] < 0 || n_poses[f] > pose_cap) {
+            snprintf(msg, sizeof msg, "frame %d has %d poses but pose_cap is %d", f, n_poses[f], pose_cap);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        most = std::max(most, n_poses[f]);
+    }
+    if (most > 0 && (!keypoints || !bbox)) return fail(h, LWP_ERR_ARG, "keypoints / bbox is null");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = LWP_OK;
+    if (img_mem == LWP_MEM_DEVICE || out_mem == LWP_MEM_DEVICE) { rc = order_in(h); if (rc) return rc; }
+    const size_t K = (size_t)h->skel.K, ib = (size_t)N * H * W * 3;
+    // the pose arrays in one device buffer: [n_poses | key-points | boxes], each section 16-byte aligned
+    const size_t nb = ((size_t)N * 4 + 15) & ~(size_t)15, kb = ((size_t)N * pose_cap * K * 2 * 4 + 15) & ~(size_t)15, bb = (size_t)N * pose_cap * 4 * 4;
+    if (h->d_ov_pose_bytes < nb + kb + bb + 16 || (out_mem == LWP_MEM_HOST && h->d_ov_out_bytes < ib)) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffers
+        rc = ensure_dev(h, &h->d_ov_pose, &h->d_ov_pose_bytes, nb + kb + bb + 16);
+        if (rc == LWP_OK && out_mem == LWP_MEM_HOST) rc = ensure_dev(h, &h->d_ov_out, &h->d_ov_out_bytes, ib);
+        if (rc) return rc;
+    }
+    char* dp = (char*)h->d_ov_pose;
+    HIP_TRY(h, hipMemcpyAsync(dp, n_poses, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+    if (most > 0) {
+        HIP_TRY(h, hipMemcpyAsync(dp + nb, keypoints, (size_t)N * pose_cap * K * 2 * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(dp + nb + kb, bbox, (size_t)N * pose_cap * 4 * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the caller's pose arrays are free from here on
+    const unsigned char* d_src = imgs;
+    if (img_mem == LWP_MEM_HOST) {
+        bool consumed = true;
+        rc = ensure_imgs_staging(h, ib);
+        if (rc == LWP_OK) rc = upload_host(h, imgs, ib, h->d_imgs, &consumed);
+        if (rc) return rc;
+        if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
+        d_src = h->d_imgs;
+    }
+    unsigned char* d_out = out_mem == LWP_MEM_HOST ? (unsigned char*)h->d_ov_out : out;
+    OverlayParams p = overlay_params(h, d_src, d_out, N, H, W);
+    p.n_poses = (const int*)dp; p.kp = (const int*)(dp + nb); p.bbox = (const int*)(dp + nb + kb);
+    p.kp_stride = (int64_t)pose_cap * (int64_t)K * 2; p.bbox_stride = (int64_t)pose_cap * 4;
+    p.P = pose_cap;
+    LAUNCH(h, KC_POST, launch_overlay(p, most, h->stream));
+    if (out_mem == LWP_MEM_HOST) {
+        HIP_TRY(h, hipMemcpyAsync(out, d_out, ib, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return LWP_OK;
+    }
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return LWP_OK;
 }
 

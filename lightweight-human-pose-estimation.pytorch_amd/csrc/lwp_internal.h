@@ -329,6 +329,25 @@ hipError_t launch_tail_rows(int N, PostWorkspace& ws, const TailParams& p, int f
 hipError_t launch_tail_track(int N, PostWorkspace& ws, const TailState& st, const TailParams& p, int lane0, hipStream_t s);
 hipError_t launch_tail_reset(const TailState& st, int lane0, int count, int next_id, hipStream_t s);
 
+// ---- pose overlay (demo.py:119-124): skeletons, blend and boxes of N uint8 frames, from pose rows that live on the device
+struct OverlayParams {
+    const unsigned char* src;       // N x H x W x 3, never written
+    unsigned char* out;             // N x H x W x 3, must not overlap src
+    int N, H, W;
+    const int* n_poses;             // [N]  (t_n of a result block, or rows the caller supplied)
+    const int* kp;                  // frame f, pose e, type k: kp[f * kp_stride + (e * K + k) * 2 + {0, 1}], x == -1: missing
+    const int* bbox;                // frame f, pose e: bbox[f * bbox_stride + e * 4 + {0..3}] = x, y, w, h
+    int64_t kp_stride, bbox_stride; // ints per frame
+    int P, K;                       // pose slots per frame (a frame's pose count is clamped to it), key-point types
+    const int* limbs;               // [L][4] as PostWorkspace::limbs; the first n_limbs rows are drawn
+    int n_limbs;
+    unsigned char color[3], box_color[3];
+    int boxes;
+};
+// three launches on `s`: the full-frame copy, one wave per (frame, pose slot, limb) for the stamps, one workgroup per
+// (frame, pose slot) for the boxes; `poses` bounds the pose slots the grid covers (<= P)
+hipError_t launch_overlay(const OverlayParams& p, int poses, hipStream_t s);
+
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);
 hipError_t launch_upsample(const MapView& src, int N, int C, int ratio, float* dst, hipStream_t s, const Tuning* tune = nullptr);

@@ -9,6 +9,7 @@
 //     fly (find_peaks / score_pairs) — so both routes give the same bits;
 //   * line-integral arithmetic is float64 exactly as NumPy does it (keypoints.py:11-13,104-136).
 #pragma clang fp contract(off)
+#include <algorithm>
 #include <type_traits>
 #include "lwp_internal.h"
 
@@ -2245,6 +2246,138 @@ hipError_t launch_tail_reset(const TailState& st, int lane0, int count, int next
     if (lane0 < 0 || count <= 0 || lane0 + count > st.lanes) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tail_reset_kernel, dim3((count + 63) / 64), dim3(64), 0, s, st, lane0, count, next_id);
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ pose overlay
+// demo.py:119-124 on the device: Pose.draw of every pose, addWeighted(orig, 0.6, img, 0.4, 0), one rectangle per pose.
+//   overlay_copy_kernel    out = src, the whole batch as one run of bytes (16 bytes per thread, byte tail)
+//   overlay_stamps_kernel  one wave per (frame, pose slot, limb): the two joint discs (radius 3), then the limb's steps over the
+//                          lanes, a radius-1 disc each.  A painted pixel is (6 src + 4 colour + 5) / 10 of the SOURCE pixel, so
+//                          every stamp that reaches a pixel stores the same three bytes: the stores may race, nothing else does.
+//   overlay_boxes_kernel   behind the stamps on the same stream: one workgroup per (frame, pose slot) walks the outline.
+// The pose count of a frame is read on the device (t_n of the result block): the grid covers the pose slots, and the
+// workgroups beyond the count leave at once.
+__global__ void __launch_bounds__(256) overlay_copy_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16,
+                                                          const unsigned char* __restrict__ src_tail, unsigned char* __restrict__ dst_tail, int ntail) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t k = i; k < n16; k += stride) dst[k] = src[k];
+    if (i < (size_t)ntail) dst_tail[i] = src_tail[i];
+}
+// either pointer off the 16-byte grid (a view into a caller's tensor)
+__global__ void __launch_bounds__(256) overlay_copy_bytes_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t k = i; k < n; k += stride) dst[k] = src[k];
+}
+
+__device__ __forceinline__ void overlay_paint(const OverlayParams& p, const unsigned char* __restrict__ src, unsigned char* __restrict__ out,
+                                              long long x, long long y) {
+    if (x < 0 || y < 0 || x >= p.W || y >= p.H) return;
+    const size_t i = ((size_t)y * p.W + (size_t)x) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[i + c] = (unsigned char)((6u * src[i + c] + 4u * p.color[c] + 5u) / 10u);
+}
+
+// Narrows [s0, s1] to the steps at which a + d * s / steps can lie inside [-2, size + 1] — outside it the radius-1 stamp at the
+// truncated coordinate cannot touch [0, size).  Real arithmetic in float64 plus two steps of margin on either side: the range
+// is a superset, the per-pixel clip decides.  Along the longer axis |d| == steps, so what is left is at most size + 8 steps.
+__device__ __forceinline__ void overlay_slab(int a, long long d, long long steps, int size, long long& s0, long long& s1) {
+    const double lo_c = -2.0 - (double)a, hi_c = (double)size + 1.0 - (double)a;      // bounds of d * s / steps
+    if (d == 0) {
+        if (lo_c > 0.0 || hi_c < 0.0) s1 = s0 - 1;
+        return;
+    }
+    const double st = (double)steps, dd = (double)d;
+    const double t0 = (d > 0 ? lo_c : hi_c) * st / dd, t1 = (d > 0 ? hi_c : lo_c) * st / dd;      // t0 <= t1
+    const double lo = fmin(fmax(floor(t0) - 2.0, 0.0), st + 1.0), hi = fmin(fmax(ceil(t1) + 2.0, -1.0), st);
+    s0 = max(s0, (long long)lo);
+    s1 = min(s1, (long long)hi);
+}
+
+__global__ void __launch_bounds__(64) overlay_stamps_kernel(OverlayParams p) {
+    const int l = blockIdx.x, e = blockIdx.y, f = blockIdx.z, lane = threadIdx.x;
+    if (e >= min(max(p.n_poses[f], 0), p.P)) return;
+    const size_t frame = (size_t)p.H * p.W * 3;
+    const unsigned char* __restrict__ src = p.src + (size_t)f * frame;
+    unsigned char* __restrict__ out = p.out + (size_t)f * frame;
+    const int ta = p.limbs[l * 4], tb = p.limbs[l * 4 + 1];
+    const int* kp = p.kp + (size_t)f * p.kp_stride + (size_t)e * p.K * 2;
+    const int ax = kp[ta * 2], ay = kp[ta * 2 + 1], bx = kp[tb * 2], by = kp[tb * 2 + 1];
+    const bool has_a = ax != -1, has_b = bx != -1;     // the reference tests x alone
+    if (lane < 49) {                                   // the joints: 7 x 7 offsets, 29 of them inside the radius-3 disc
+        const int ox = lane % 7 - 3, oy = lane / 7 - 3;
+        if (ox * ox + oy * oy <= 9) {
+            if (has_a) overlay_paint(p, src, out, (long long)ax + ox, (long long)ay + oy);
+            if (has_b) overlay_paint(p, src, out, (long long)bx + ox, (long long)by + oy);
+        }
+    }
+    if (!(has_a && has_b)) return;
+    const long long dx = (long long)bx - ax, dy = (long long)by - ay;
+    const long long steps = max(max(dx < 0 ? -dx : dx, dy < 0 ? -dy : dy), 1LL);
+    long long s0 = 0, s1 = steps;
+    overlay_slab(ax, dx, steps, p.W, s0, s1);
+    overlay_slab(ay, dy, steps, p.H, s0, s1);
+    const double fdx = (double)dx, fdy = (double)dy, fax = (double)ax, fay = (double)ay, fsteps = (double)steps;
+    for (long long s = s0 + lane; s <= s1; s += 64) {
+        // q = pa + (pb - pa) * (s / steps) as NumPy evaluates it: one division, one multiplication, one addition, each rounded
+        // (never an fma: 2.9999999999999996 and 3.0 truncate differently)
+        const double t = __ddiv_rn((double)s, fsteps);
+        const long long cx = (long long)__dadd_rn(fax, __dmul_rn(fdx, t)), cy = (long long)__dadd_rn(fay, __dmul_rn(fdy, t));
+        overlay_paint(p, src, out, cx, cy);
+        overlay_paint(p, src, out, cx - 1, cy);
+        overlay_paint(p, src, out, cx + 1, cy);
+        overlay_paint(p, src, out, cx, cy - 1);
+        overlay_paint(p, src, out, cx, cy + 1);
+    }
+}
+
+__global__ void __launch_bounds__(256) overlay_boxes_kernel(OverlayParams p) {
+    const int e = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    if (e >= min(max(p.n_poses[f], 0), p.P)) return;
+    unsigned char* __restrict__ out = p.out + (size_t)f * p.H * p.W * 3;
+    const int* b = p.bbox + (size_t)f * p.bbox_stride + (size_t)e * 4;
+    // corners (x, y) and (x + w, y + h), inclusive, in either order (cv2.rectangle); 64-bit: saturated rows must not wrap
+    const long long xa = b[0], xb = (long long)b[0] + b[2], ya = b[1], yb = (long long)b[1] + b[3];
+    const long long x0 = min(xa, xb), x1 = max(xa, xb), y0 = min(ya, yb), y1 = max(ya, yb);
+    auto put = [&](long long x, long long y) {
+        const size_t i = ((size_t)y * p.W + (size_t)x) * 3;
+        out[i] = p.box_color[0]; out[i + 1] = p.box_color[1]; out[i + 2] = p.box_color[2];
+    };
+    const bool top = y0 >= 0 && y0 < p.H, bottom = y1 >= 0 && y1 < p.H, left = x0 >= 0 && x0 < p.W, right = x1 >= 0 && x1 < p.W;
+    for (long long x = max(x0, 0LL) + tid; x <= min(x1, (long long)p.W - 1); x += 256) {
+        if (top) put(x, y0);
+        if (bottom) put(x, y1);
+    }
+    for (long long y = max(y0, 0LL) + tid; y <= min(y1, (long long)p.H - 1); y += 256) {
+        if (left) put(x0, y);
+        if (right) put(x1, y);
+    }
+}
+
+hipError_t launch_overlay(const OverlayParams& p, int poses, hipStream_t s) {
+    if (p.N < 1 || p.N > 65535 || p.H < 1 || p.W < 1 || poses < 0 || poses > p.P || poses > 65535 || p.n_limbs < 0 || p.n_limbs > kMaxSkelLimbs)
+        return hipErrorInvalidValue;
+    const size_t bytes = (size_t)p.N * p.H * p.W * 3;
+    if ((((uintptr_t)p.src | (uintptr_t)p.out) & 15) == 0) {
+        const size_t n16 = bytes / 16;
+        const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((n16 + 255) / 256, 1), 2048);
+        hipLaunchKernelGGL(overlay_copy_kernel, dim3(blocks), dim3(256), 0, s, (const uint4*)p.src, (uint4*)p.out, n16,
+                           p.src + n16 * 16, p.out + n16 * 16, (int)(bytes - n16 * 16));
+    } else {
+        const unsigned blocks = (unsigned)std::min<size_t>((bytes + 255) / 256, 2048);
+        hipLaunchKernelGGL(overlay_copy_bytes_kernel, dim3(blocks), dim3(256), 0, s, p.src, p.out, bytes);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || poses == 0) return e;
+    if (p.n_limbs > 0) {
+        hipLaunchKernelGGL(overlay_stamps_kernel, dim3(p.n_limbs, poses, p.N), dim3(64), 0, s, p);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (p.boxes) {
+        hipLaunchKernelGGL(overlay_boxes_kernel, dim3(poses, p.N), dim3(64 * 4), 0, s, p);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 }  // namespace lwp

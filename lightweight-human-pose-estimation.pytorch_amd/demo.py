@@ -47,8 +47,17 @@ def poses_from_entries(pose_entries, all_keypoints, scale, pad, stride=8, upsamp
     return poses
 
 
+def _overlay_options(overlay):
+    """``overlay=True`` or a dict of ``Engine.set_overlay`` keywords (color, box_color, boxes, n_draw_limbs)."""
+    opts = dict(overlay) if isinstance(overlay, dict) else {}
+    unknown = set(opts) - {"color", "box_color", "boxes", "n_draw_limbs"}
+    if unknown:
+        raise ValueError("unknown overlay option(s): %s" % ", ".join(sorted(unknown)))
+    return opts
+
+
 def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, draw=False, device_tail=False, sigmas=None,
-             pipelined=False):
+             pipelined=False, overlay=False):
     """Generator over frames: yields (img, current_poses).  No GUI (cv2.imshow/waitKey are out of scope).
     Pose / tracking are COCO-18 (modules/pose.py), as in the reference: an engine with a custom skeleton raises ValueError,
     unless ``device_tail=True`` and ``sigmas`` (K values, as ``Pose.sigmas`` holds them) are given.
@@ -65,24 +74,36 @@ def run_demo(net, image_provider, height_size, cpu, track, smooth, fused=False, 
     and ``Pose.last_id`` are those of the serial device-tail run.  The provider is read ONE FRAME AHEAD: when frame k is
     yielded, frame k + 1 has already been taken from it — a provider that hands out the same buffer again and again must
     copy.  ``draw=True`` draws on the frame the poses belong to.  When the generator ends or is closed early, the slot still
-    in flight is fetched and tracking is switched off."""
+    in flight is fetched and tracking is switched off.
+
+    ``overlay=True`` (needs ``fused=True, device_tail=True``; or a dict of ``Engine.set_overlay`` keywords) runs demo.py:119-124
+    on the GPU: the generator yields ``(annotated_img, poses)``, where the annotated frame is a NEW array holding the skeletons
+    blended 0.6 / 0.4 into the frame and one box per pose; the provider's frame is not modified.  Pipelined, the kernels follow
+    the pose tail inside the one-call submit and the frame comes back with the slot's results; serial, ``Engine.draw_poses``
+    runs them on the fetched rows.  Both give the same frames.  The kernels read the engine's limb table, so ``overlay=True``
+    is allowed under a custom skeleton (with ``sigmas``) where ``draw=True`` is not.  ``draw=True`` keeps its meaning: the host
+    ``Pose.draw`` into the provider's frame.  The id label (cv2.putText) is not drawn; the ids are in the poses.  The engine's
+    overlay setting is switched off again when the generator ends."""
     K = net.engine.skeleton["num_kpt_types"]
+    if overlay and not (fused and device_tail):
+        raise ValueError("run_demo(overlay=True) needs fused=True and device_tail=True: the overlay kernels draw the device tail's pose rows")
+    ov = _overlay_options(overlay) if overlay else None
     if pipelined and not device_tail:
         raise ValueError("run_demo(pipelined=True) needs device_tail=True (and fused=True): the pipelined loop reads its poses from the device tail")
     if device_tail and not fused:
         raise ValueError("run_demo(device_tail=True) needs fused=True: the pose tail runs behind the fused grouping kernels")
-    if K != Pose.num_kpts and (draw or not device_tail or sigmas is None):
+    if K != Pose.num_kpts and (draw or not device_tail or sigmas is None):       # (overlay=True is fine: the kernels read the engine's limb table)
         raise ValueError("run_demo draws and tracks COCO poses of %d key-points; the engine's skeleton has %d key-point types "
                          "(use infer_poses / poses_from_maps for custom skeletons, or device_tail=True with sigmas and draw=False)"
                          % (Pose.num_kpts, K))
     if pipelined:
-        return _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, sigmas)
+        return _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, sigmas, ov)
     if device_tail:
-        return _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas)
+        return _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas, ov)
     return _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw)
 
 
-def _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas):
+def _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigmas, ov=None):
     net = net.eval()
     eng = net.engine
     stride, upsample_ratio = 8, 4
@@ -90,6 +111,8 @@ def _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigm
         sigmas = Pose.sigmas
     eng.set_tracking(eng.TRACK_LANES if track else eng.TRACK_ROWS, smooth=smooth, sigmas=sigmas)
     try:
+        if ov is not None:
+            eng.set_overlay(eng.OVERLAY_OFF, **ov)       # the serial loop draws with draw_poses: only the options are set
         if track:
             eng.reset_tracking(0, Pose.last_id + 1)
         for img in image_provider:
@@ -103,14 +126,21 @@ def _run_demo_device(net, image_provider, height_size, track, smooth, draw, sigm
             if draw:
                 for pose in current_poses:
                     pose.draw(img)
-            yield img, current_poses
+            if ov is not None:
+                yield eng.draw_poses(img, rows["keypoints"], rows["bbox"], device_out=False), current_poses
+            else:
+                yield img, current_poses
     finally:
-        eng.set_tracking(eng.TRACK_OFF)
+        try:
+            if ov is not None:
+                eng.set_overlay(eng.OVERLAY_OFF)
+        finally:
+            eng.set_tracking(eng.TRACK_OFF)
 
 
-def _drain(eng, in_flight):
-    """The end of a pipelined loop: every slot still in flight is fetched and tracking is switched off.  An error of such a
-    fetch is not lost: all slots are tried, tracking is switched off, and then the first error is raised."""
+def _drain(eng, in_flight, overlay=False):
+    """The end of a pipelined loop: every slot still in flight is fetched and tracking (and the overlay) is switched off.  An
+    error of such a fetch is not lost: all slots are tried, tracking is switched off, and then the first error is raised."""
     first = None
     while in_flight:
         _, slot = in_flight.pop(0)
@@ -120,13 +150,17 @@ def _drain(eng, in_flight):
             if first is None:
                 first = e
     try:
-        eng.set_tracking(eng.TRACK_OFF)
+        if overlay:
+            eng.set_overlay(eng.OVERLAY_OFF)
     finally:
-        if first is not None:
-            raise first
+        try:
+            eng.set_tracking(eng.TRACK_OFF)
+        finally:
+            if first is not None:
+                raise first
 
 
-def _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, sigmas):
+def _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, sigmas, ov=None):
     net = net.eval()
     eng = net.engine
     stride, upsample_ratio = 8, 4
@@ -145,9 +179,13 @@ def _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, s
         if draw:
             for pose in current_poses:
                 pose.draw(img)
+        if ov is not None:
+            return eng.pipeline_overlay(slot)[0], current_poses
         return img, current_poses
 
     try:
+        if ov is not None:
+            eng.set_overlay(eng.OVERLAY_HOST, **ov)
         if track:
             eng.reset_tracking(0, Pose.last_id + 1)
         k = 0
@@ -160,10 +198,10 @@ def _run_demo_pipelined(net, image_provider, height_size, track, smooth, draw, s
         while in_flight:
             yield finish()
     finally:
-        _drain(eng, in_flight)                       # closed early (or an error): no slot stays pending
+        _drain(eng, in_flight, ov is not None)       # closed early (or an error): no slot stays pending
 
 
-def run_cameras(net, providers, height_size, track, smooth, sigmas=None):
+def run_cameras(net, providers, height_size, track, smooth, sigmas=None, overlay=False):
     """N same-sized camera streams, one batch per step: yields a list of N (img, poses) per step and stops when the first
     provider ends.  Frame f of every batch is lane f of the device tail (``Engine.TRACK_LANES``): each stream is tracked on its
     own, with its own ids, and the results of stream f are those of ``run_demo(..., fused=True, device_tail=True)`` over
@@ -173,7 +211,8 @@ def run_cameras(net, providers, height_size, track, smooth, sigmas=None):
     Every lane gives out ids from ``Pose.last_id + 1`` on; ``Pose.last_id`` itself is left alone (the ids
     are per lane, there is no single counter to write back).  Pipelined like ``run_demo(pipelined=True)``: the providers are read
     one step ahead.  The arguments are checked at the call (ValueError), like ``run_demo``'s; a mismatch of frame sizes shows
-    at the step that meets it."""
+    at the step that meets it.  ``overlay=True`` (or a dict of ``Engine.set_overlay`` keywords): every yielded ``img`` is the
+    annotated frame of that stream (a new array; the providers' frames are untouched), as ``run_demo(overlay=True)`` yields it."""
     net = net.eval()
     eng = net.engine
     stride, upsample_ratio = 8, 4
@@ -186,20 +225,25 @@ def run_cameras(net, providers, height_size, track, smooth, sigmas=None):
     providers = [iter(p) for p in providers]
     if not providers:
         raise ValueError("run_cameras needs at least one provider")
-    return _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, upsample_ratio)
+    ov = _overlay_options(overlay) if overlay else None
+    return _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, upsample_ratio, ov)
 
 
-def _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, upsample_ratio):
+def _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, upsample_ratio, ov=None):
     eng.set_tracking(eng.TRACK_LANES if track else eng.TRACK_ROWS, smooth=smooth, sigmas=sigmas)
     in_flight = []
 
     def finish():
         imgs, slot = in_flight.pop(0)
         eng.pipeline_fetch(slot)
+        if ov is not None:
+            imgs = list(eng.pipeline_overlay(slot))
         return [(img, poses_from_arrays(r["keypoints"], r["confidence"], r["bbox"], r["ids"] if track else None))
                 for img, r in zip(imgs, eng.poses(slot))]
 
     try:
+        if ov is not None:
+            eng.set_overlay(eng.OVERLAY_HOST, **ov)
         if track:
             eng.reset_tracking(-1, Pose.last_id + 1)
         k = 0
@@ -223,7 +267,7 @@ def _run_cameras(eng, providers, height_size, track, smooth, sigmas, stride, ups
         while in_flight:
             yield finish()
     finally:
-        _drain(eng, in_flight)
+        _drain(eng, in_flight, ov is not None)
 
 
 def _run_demo(net, image_provider, height_size, cpu, track, smooth, fused, draw):

@@ -91,6 +91,16 @@ def poses_from_arrays(keypoints, confidence, bbox, ids=None):
     return out
 
 
+def draw_poses(engine, img, poses):
+    """demo.py:119-124 on the GPU for one frame: the skeletons of ``poses`` (what ``Pose.draw`` paints), blended 0.6 / 0.4 into
+    ``img``, and one box per pose (``Engine.set_overlay`` holds colours, boxes on / off and the drawn limbs).  ``img``: (H,W,3)
+    uint8, numpy or cuda tensor.  Returns a NEW frame of the same kind; ``img`` is untouched.  The id label is not drawn."""
+    K = engine.skeleton["num_kpt_types"]
+    kp = np.stack([np.asarray(p.keypoints, dtype=np.int32) for p in poses]).reshape(-1, K, 2) if poses else np.zeros((0, K, 2), np.int32)
+    bb = np.array([p.bbox for p in poses], dtype=np.int32).reshape(-1, 4)
+    return engine.draw_poses(img, kp, bb)
+
+
 def _similar_keypoints(a, b, threshold=0.5):
     """Number of key-points present in both poses whose OKS-like similarity exceeds ``threshold``."""
     both = (a.keypoints[:, 0] != -1) & (b.keypoints[:, 0] != -1)

@@ -478,7 +478,7 @@ class Engine(object):
                            img_scale=1 / 256, upsample_ratio=4, demo=True):
         """One-call video step (demo.py:55-68 + 91-118): uint8 frames (N,H,W,3) or (H,W,3), numpy or cuda tensor -> upload,
         batched pre-processing, network, grouping and (if ``set_tracking`` is on) the pose tail, all enqueued; returns at once.
-        Read the results with ``pipeline_fetch(slot)`` and ``poses(slot)``.  The tail un-maps with this submit's own stride,
+        Read the results with ``pipeline_fetch(slot)`` and ``poses(slot)`` (and, with ``set_overlay`` on, ``pipeline_overlay(slot)``).  The tail un-maps with this submit's own stride,
         scale and pad (``preprocess_dims`` of the frame size): ``set_unmap`` is neither used nor changed.  A numpy frame buffer
         may be reused on return; a cuda tensor is kept alive until the slot is fetched."""
         ptr, mem, N, H, W, a = self._u8_frames(frames)
@@ -490,6 +490,8 @@ class Engine(object):
                                            upsample_ratio, 1 if demo else 0, slot), self.h.ptr)
         self._keep_slot = getattr(self, "_keep_slot", {})
         self._keep_slot[slot] = (a if mem == MEM_DEVICE else None, N)
+        self._overlay_shape = getattr(self, "_overlay_shape", {})
+        self._overlay_shape[slot] = (N, H, W, 3)
 
     def pipeline_fetch(self, slot):
         _, N = self._keep_slot[slot]
@@ -559,6 +561,90 @@ class Engine(object):
                                     okp.ctypes.data_as(ip), obb.ctypes.data_as(ip), oid.ctypes.data_as(ip), C.byref(last),
                                     C.byref(near)), self.h.ptr)
         return dict(keypoints=okp, bbox=obb, ids=oid, last_id=last.value, near=near.value)
+
+    # ------------------------------------------------------------------ pose overlay on the device (demo.py:119-124)
+    OVERLAY_OFF, OVERLAY_DEVICE, OVERLAY_HOST = 0, 1, 2
+
+    def set_overlay(self, mode, color=None, box_color=None, boxes=True, n_draw_limbs=-1):
+        """Skeletons, the 0.6 / 0.4 blend and the boxes of demo.py:119-124 drawn by kernels behind the pose tail of
+        ``pipeline_submit_u8``: mode 0 off (default), 1 annotated frames kept on the device, 2 also copied to pinned host memory
+        with the slot's results (``pipeline_overlay``).  ``color`` / ``box_color``: 3 bytes in the frame's channel order, None =
+        ``Pose.color`` / (0, 255, 0); ``n_draw_limbs``: the first rows of the engine's limb table that are drawn, -1 = all but
+        the last two.  Everything but the mode also applies to ``draw_poses``.  The id label (cv2.putText) is not drawn."""
+        mode = {"off": 0, "device": 1, "host": 2}.get(mode, mode)
+
+        def rgb(c):
+            if c is None:
+                return None
+            v = [int(x) for x in c]
+            if len(v) != 3 or min(v) < 0 or max(v) > 255:
+                raise ValueError("a colour is 3 values in 0..255, got %r" % (c,))
+            return (C.c_ubyte * 3)(*v)
+        check(lib().lwp_set_overlay(self.h.ptr, int(mode), rgb(color), rgb(box_color), 1 if boxes else 0, int(n_draw_limbs)), self.h.ptr)
+        self._overlay_mode = int(mode)
+
+    def draw_poses(self, imgs, keypoints, bbox, n_poses=None, device_out=None):
+        """The overlay kernels on poses the caller supplies.  ``imgs``: one frame (H,W,3) or a batch (N,H,W,3), uint8, numpy or
+        a cuda tensor.  One frame: ``keypoints`` (P,K,2) and ``bbox`` (P,4) int32.  A batch: padded arrays (N,cap,K,2) / (N,cap,4)
+        with ``n_poses`` (N,), or a list of N (P_f,K,2) arrays and a list of N (P_f,4) arrays.  Returns the annotated frames as a
+        NEW array of the input's shape; ``imgs`` is not modified.  ``device_out``: None = the kind of ``imgs``, True = a cuda
+        tensor, False = a numpy array."""
+        torch = _torch()
+        ptr, mem, N, H, W, a = self._u8_frames(imgs)
+        single = len(a.shape) == 3
+        K = self.skeleton["num_kpt_types"]
+        if single or n_poses is None:
+            kl = [keypoints] if single else list(keypoints)
+            bl = [bbox] if single else list(bbox)
+            if len(kl) != N or len(bl) != N:
+                raise ValueError("%d frames but %d key-point arrays and %d box arrays" % (N, len(kl), len(bl)))
+            kl = [np.asarray(k, dtype=np.int32).reshape(-1, K, 2) for k in kl]
+            bl = [np.asarray(b, dtype=np.int32).reshape(-1, 4) for b in bl]
+            for k, b in zip(kl, bl):
+                if len(k) != len(b):
+                    raise ValueError("%d poses but %d boxes" % (len(k), len(b)))
+            n = np.array([len(k) for k in kl], np.int32)
+            cap = int(n.max()) if N else 0
+            kp = np.full((N, cap, K, 2), -1, np.int32)
+            bb = np.zeros((N, cap, 4), np.int32)
+            for f in range(N):
+                kp[f, :n[f]] = kl[f]
+                bb[f, :n[f]] = bl[f]
+        else:
+            kp = np.ascontiguousarray(keypoints, dtype=np.int32)
+            bb = np.ascontiguousarray(bbox, dtype=np.int32)
+            n = np.ascontiguousarray(n_poses, dtype=np.int32).reshape(-1)
+            if kp.ndim != 4 or kp.shape[0] != N or kp.shape[2:] != (K, 2) or bb.shape != (N, kp.shape[1], 4) or n.shape != (N,):
+                raise ValueError("expected keypoints (N,cap,%d,2), bbox (N,cap,4) and n_poses (N,) for %d frames" % (K, N))
+            cap = int(kp.shape[1])
+        on_dev = (mem == MEM_DEVICE) if device_out is None else bool(device_out)
+        if on_dev:
+            out = torch.empty(tuple(a.shape), dtype=torch.uint8, device=torch.device("cuda", self.device_id))
+            optr, omem = out.data_ptr(), MEM_DEVICE
+        else:
+            out = np.empty(tuple(a.shape), np.uint8)
+            optr, omem = out.ctypes.data, MEM_HOST
+        if mem == MEM_DEVICE or omem == MEM_DEVICE:
+            self._order()
+        ip = C.POINTER(C.c_int)
+        check(lib().lwp_draw_poses(self.h.ptr, ptr, mem, N, H, W, n.ctypes.data_as(ip), kp.ctypes.data_as(ip), bb.ctypes.data_as(ip),
+                                   cap, optr, omem), self.h.ptr)
+        return out
+
+    def pipeline_overlay(self, slot, device=False):
+        """The annotated frames (N,H,W,3) uint8 of a fetched slot that was submitted with the overlay on: a numpy array (from the
+        pinned copy in mode 2), or with ``device=True`` a cuda tensor.  A new array each time."""
+        torch = _torch()
+        shape = self._overlay_shape[slot]
+        if device:
+            out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device_id))
+            self._order()
+            ptr, mem = out.data_ptr(), MEM_DEVICE
+        else:
+            out = np.empty(shape, np.uint8)
+            ptr, mem = out.ctypes.data, MEM_HOST
+        check(lib().lwp_get_overlay(self.h.ptr, slot, ptr, mem, shape[0], shape[1], shape[2]), self.h.ptr)
+        return out
 
     # ------------------------------------------------------------------ measurement
     def time_pipeline(self, x_cuda, iters, what=1, upsample_ratio=4, demo=True):
