@@ -351,6 +351,47 @@ int lwp_get_overlay(lwp_handle h, int slot, unsigned char* dst, int dst_mem, int
 int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, const int* n_poses,
                    const int* keypoints, const int* bbox, int pose_cap, unsigned char* out, int out_mem);
 
+/* ---- training targets and the per-stage masked L2 loss on the device: replaces datasets/coco.py:48-61,71-159 (the mask resize,
+ *      _generate_keypoint_maps / _add_gaussian, _generate_paf_maps / _set_paf) and modules/loss.py l2_loss as train.py:92-97
+ *      sums it per stage.  Targets and loss only: there is no backward, no optimiser and no augmentation.
+ *      lwp_train_targets: kpts is N x Pmax x K x 3 float64 (mem) holding (x, y, visibility) in image pixels, persons in label
+ *      order (the main person, then processed_other_annotations); n_persons[N] (host) says how many rows of a frame count.  K, L,
+ *      the limbs' key-point pairs and their PAF channel pairs are the handle's skeleton table (lwp_set_skeleton); the default
+ *      table writes limb [1, 2] to channels 12 / 13, which is coco.py's BODY_PARTS_KPT_IDS layout.  Outputs (DEVICE, float32):
+ *      keypoint_maps N x (K + 1) x h x w (last channel: 1 - max over the K), paf_maps N x 2L x h x w, h = H / stride, w = W / stride
+ *      (integer division).  A key-point counts iff visibility <= 1.  The arithmetic is the reference's, in double, statement by
+ *      statement (int() truncation, // on the clamped corners, exponent = d2 / 2 / sigma / sigma, cut at 4.6052, the increment
+ *      rounded to float32 before a float32 add as NumPy 2 does, clip to 1 after every add; the PAF of the last person in label
+ *      order wins a pixel), with two library calls in place of CPython's: exp() is the device's, and ** 0.5 is a correctly
+ *      rounded sqrt.  Checks (LWP_ERR_ARG): 1 <= N <= 65535, 0 <= n_persons[f] <= Pmax <= 65535, 1 <= stride <= H, W, sigma > 0,
+ *      paf_thickness >= 0, at most 2^28 map cells, PAF channel ids below 2L and each written by one limb only (the kernel
+ *      takes the limbs inside a chunk of persons, the reference limb by limb: the orders agree only then), and for host key-points that every value is finite (int() raises in the
+ *      reference; device key-points are not read by the host and must be finite).
+ *      lwp_mask_downsample: mask N x H x W float32 (mem) -> out N x (H / stride) x (W / stride) float32 (DEVICE), the mean of each
+ *      stride x stride block: cv2.resize(mask, fx = fy = 1 / stride, INTER_AREA) (coco.py:48) where the size divides — only
+ *      then (LWP_ERR_ARG otherwise; at most 2^28 output cells).  Exact for the 0 / 1 masks get_mask makes; not pinned against cv2 (like the other resizes).
+ *      lwp_stage_losses: outs = the n_outs = 2 * (num_refinement_stages + 1) tensors net(x) returned (DEVICE, contiguous NCHW
+ *      float32; even entries N x num_heatmaps x hs x ws against keypoint_maps, odd entries N x num_pafs x hs x ws against
+ *      paf_maps; a NULL entry is skipped and its loss is 0), mask N x hs x ws (DEVICE) broadcast over the channels.
+ *      losses_host[i] = sum(((outs[i] - target) * mask)^2 / 2 / batch_size), every term and every sum in float64, in a fixed
+ *      order without atomics: the same inputs give the same bits.  One launch reads the targets once for up to 16 tensors.
+ *      LWP_ERR_ARG when n_outs is not 2 * (num_refinement_stages + 1), or when the skeleton's K + 1 / 2L differ from the
+ *      network's num_heatmaps / num_pafs.  Complete on return (the sums are host memory).
+ *      All three run on the handle's stream and honour lwp_set_stream; none needs weights. */
+int lwp_train_targets(lwp_handle h, const double* kpts, int kpts_mem, const int* n_persons, int N, int Pmax, int H, int W,
+                      int stride, double sigma, double paf_thickness, float* keypoint_maps_device, float* paf_maps_device);
+int lwp_mask_downsample(lwp_handle h, const float* mask, int mem, int N, int H, int W, int stride, float* out_device);
+int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
+                     const float* mask, int N, int hs, int ws, int batch_size, double* losses_host);
+/* the kernels of the two calls alone (tools/targets_bench.py): the same arguments and checks, one upload, then `iters`
+ * back-to-back launches between two HIP events on the handle's stream, with no per-call synchronise and no copy-back of the
+ * sums.  ms_total out. */
+int lwp_time_train_targets(lwp_handle h, const double* kpts, int kpts_mem, const int* n_persons, int N, int Pmax, int H, int W,
+                           int stride, double sigma, double paf_thickness, float* keypoint_maps_device, float* paf_maps_device,
+                           int iters, float* ms_total);
+int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
+                          const float* mask, int N, int hs, int ws, int batch_size, int iters, float* ms_total);
+
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */
 int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio,

@@ -23,6 +23,7 @@ EXPORTS = [
     "lwp_set_tracking", "lwp_set_unmap", "lwp_reset_tracking", "lwp_get_poses", "lwp_track_poses", "lwp_debug_tracking_near",
     "lwp_preprocess_u8_batch", "lwp_pipeline_submit_u8",
     "lwp_set_overlay", "lwp_get_overlay", "lwp_draw_poses",
+    "lwp_train_targets", "lwp_mask_downsample", "lwp_stage_losses", "lwp_time_train_targets", "lwp_time_stage_losses",
 ]
 
 
@@ -100,6 +101,11 @@ def lib():
     L.lwp_set_overlay.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
     L.lwp_get_overlay.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.lwp_draw_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, vp, C.c_int]
+    L.lwp_train_targets.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
+    L.lwp_mask_downsample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.lwp_stage_losses.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    L.lwp_time_train_targets.argtypes = L.lwp_train_targets.argtypes + [C.c_int, fp]
+    L.lwp_time_stage_losses.argtypes = L.lwp_stage_losses.argtypes[:-1] + [C.c_int, fp]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -11,13 +11,15 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "liblwpose_hip.so")
-SOURCES = ["net_graph.cpp", "net_kernels.hip", "net_kernels_bf16.hip", "net_kernels_tiled.hip", "post_kernels.hip", "capi.cpp"]
+SOURCES = ["net_graph.cpp", "net_kernels.hip", "net_kernels_bf16.hip", "net_kernels_tiled.hip", "post_kernels.hip", "train_kernels.hip", "capi.cpp"]
 HEADERS = ["lwp_internal.h", "h16.h", os.path.join("..", "..", "include", "lwpose.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-result", "-DNDEBUG"]
 # the post-processing must reproduce NumPy's separately-rounded float32/float64 arithmetic bit for bit:
 # no FMA contraction anywhere in that translation unit (the in-source pragma alone is not honoured for
 # packed-math fusion by hipcc 7.2)
 EXTRA = {"post_kernels.hip": ["-ffp-contract=off"] + (["-DLWP_ASM_STAMPS"] if os.environ.get("LWP_ASM_STAMPS") else []),
+         # the training targets reproduce CPython's separately-rounded double arithmetic: same rule
+         "train_kernels.hip": ["-ffp-contract=off"],
          # LWP_ABLATION=1 at build time adds the ablation instantiations of the hot kernels (tools/ only; never shipped by default)
          "net_kernels_bf16.hip": (["-DLWP_ABLATION"] if os.environ.get("LWP_ABLATION") else []),
          "net_kernels.hip": (["-DLWP_ABLATION"] if os.environ.get("LWP_ABLATION") else []) +

@@ -82,6 +82,10 @@ struct lwp_context {
     struct Overlay { int mode = 0, boxes = 1, n_draw_limbs = -1; unsigned char color[3] = {0, 224, 255}, box_color[3] = {0, 255, 0}; } ovl;
     float* d_ov_pose = nullptr; size_t d_ov_pose_bytes = 0;
     float* d_ov_out = nullptr; size_t d_ov_out_bytes = 0;
+    // training targets and loss (lwp_train_targets / lwp_mask_downsample / lwp_stage_losses): staging of host key-points, person
+    // counts and host masks; the loss partials followed by the per-stage sums
+    float* d_train = nullptr; size_t d_train_bytes = 0;
+    float* d_loss = nullptr; size_t d_loss_bytes = 0;
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
     bool run_has_tail = false;             // the tail kernels ran behind the grouping whose results h->ws holds
@@ -298,6 +302,8 @@ extern "C" int lwp_destroy(lwp_handle h) {
     if (h->d_vars) (void)hipFree(h->d_vars);
     if (h->d_ov_pose) (void)hipFree(h->d_ov_pose);
     if (h->d_ov_out) (void)hipFree(h->d_ov_out);
+    if (h->d_train) (void)hipFree(h->d_train);
+    if (h->d_loss) (void)hipFree(h->d_loss);
     free_tail_state(h);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     free_ws(h);
@@ -2173,6 +2179,203 @@ extern "C" int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_m
     return LWP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- training targets and loss
+// argument checks, upload of the counts (and of host key-points) and the kernel's parameters: everything of lwp_train_targets
+// before its launch, shared with lwp_time_train_targets
+static int train_targets_prepare(lwp_handle h, const double* kpts, int kpts_mem, const int* n_persons, int N, int Pmax, int H, int W,
+                                 int stride, double sigma, double paf_thickness, float* keypoint_maps_device, float* paf_maps_device,
+                                 TrainTargetsParams* out) {
+    char msg[200];
+    if (!keypoint_maps_device || !paf_maps_device) return fail(h, LWP_ERR_ARG, "keypoint_maps_device / paf_maps_device is null");
+    if (kpts_mem != LWP_MEM_HOST && kpts_mem != LWP_MEM_DEVICE) return fail(h, LWP_ERR_ARG, "kpts_mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    if (Pmax < 0 || Pmax > 65535) return fail(h, LWP_ERR_ARG, "Pmax must be 0..65535");
+    if (stride < 1 || stride > 1024) return fail(h, LWP_ERR_ARG, "stride must be 1..1024");
+    if (H < stride || W < stride || H > (1 << 20) || W > (1 << 20)) return fail(h, LWP_ERR_ARG, "the frame must hold at least one stride x stride cell (and at most 2^20 pixels a side)");
+    if ((int64_t)(H / stride) * (W / stride) > (1 << 28)) return fail(h, LWP_ERR_ARG, "oversized map: more than 2^28 cells");
+    if (!(sigma > 0) || !std::isfinite(sigma)) return fail(h, LWP_ERR_ARG, "sigma must be positive and finite");
+    if (!(paf_thickness >= 0) || !std::isfinite(paf_thickness)) return fail(h, LWP_ERR_ARG, "paf_thickness must be finite and not negative");
+    if (!n_persons) return fail(h, LWP_ERR_ARG, "n_persons is null");
+    int most = 0;
+    for (int f = 0; f < N; ++f) {
+        if (n_persons[f] < 0 || n_persons[f] > Pmax) {
+            snprintf(msg, sizeof msg, "frame %d has %d persons but Pmax is %d", f, n_persons[f], Pmax);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        most = std::max(most, n_persons[f]);
+    }
+    if (most > 0 && !kpts) return fail(h, LWP_ERR_ARG, "kpts is null");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    const Skeleton& sk = h->skel;
+    const int K = sk.K, L = sk.L;
+    // the kernel walks the limbs inside each chunk of persons, the reference all persons of a limb before the next limb: the
+    // two orders agree only while no target channel belongs to two limbs
+    std::vector<char> used((size_t)2 * L, 0);
+    for (int l = 0; l < L; ++l)
+        for (int c = 0; c < 2; ++c) {
+            const int ch = sk.paf[2 * l + c];
+            if (ch < 0 || ch >= 2 * L) {
+                snprintf(msg, sizeof msg, "limb %d: PAF channels (%d, %d) lie outside the %d target channels (2 x num_limbs)", l, sk.paf[2 * l], sk.paf[2 * l + 1], 2 * L);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+            if (used[ch]) {
+                snprintf(msg, sizeof msg, "limb %d: PAF channel %d is already written by another limb", l, ch);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+            used[ch] = 1;
+        }
+    const size_t kd = (size_t)N * Pmax * K * 3;
+    if (kpts_mem == LWP_MEM_HOST)                      // int() of a NaN or an infinity raises in the reference
+        for (int f = 0; f < N; ++f)
+            for (size_t i = 0; i < (size_t)n_persons[f] * K * 3; ++i)
+                if (!std::isfinite(kpts[(size_t)f * Pmax * K * 3 + i])) {
+                    snprintf(msg, sizeof msg, "frame %d: a key-point value is not finite", f);
+                    return fail(h, LWP_ERR_ARG, msg);
+                }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = order_in(h);
+    if (rc) return rc;
+    // [n_persons | key-points]: the counts always travel, the key-points only from host memory
+    const size_t nb = ((size_t)N * 4 + 15) & ~(size_t)15, kb = kpts_mem == LWP_MEM_HOST ? kd * sizeof(double) : 0;
+    if (h->d_train_bytes < nb + kb + 16) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        rc = ensure_dev(h, &h->d_train, &h->d_train_bytes, nb + kb + 16);
+        if (rc) return rc;
+    }
+    char* dp = (char*)h->d_train;
+    HIP_TRY(h, hipMemcpyAsync(dp, n_persons, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+    if (kb && most > 0) HIP_TRY(h, hipMemcpyAsync(dp + nb, kpts, kb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the caller's arrays are free from here on
+    TrainTargetsParams p{};
+    p.kpts = kpts_mem == LWP_MEM_HOST ? (const double*)(dp + nb) : kpts;
+    p.n_persons = (const int*)dp;
+    p.Pmax = most > 0 ? Pmax : 0; p.K = K; p.L = L;
+    p.limbs = h->d_limbs;
+    p.h = H / stride; p.w = W / stride; p.stride = stride;
+    p.sigma = sigma; p.thickness = paf_thickness;
+    p.keypoint_maps = keypoint_maps_device; p.paf_maps = paf_maps_device;
+    *out = p;
+    return LWP_OK;
+}
+
+extern "C" int lwp_train_targets(lwp_handle h, const double* kpts, int kpts_mem, const int* n_persons, int N, int Pmax, int H, int W,
+                                 int stride, double sigma, double paf_thickness, float* keypoint_maps_device, float* paf_maps_device) {
+    TrainTargetsParams p{};
+    int rc = train_targets_prepare(h, kpts, kpts_mem, n_persons, N, Pmax, H, W, stride, sigma, paf_thickness, keypoint_maps_device,
+                                   paf_maps_device, &p);
+    if (rc) return rc;
+    LAUNCH(h, KC_OTHER, launch_train_targets(p, N, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_mask_downsample(lwp_handle h, const float* mask, int mem, int N, int H, int W, int stride, float* out_device) {
+    if (!mask || !out_device) return fail(h, LWP_ERR_ARG, "mask / out_device is null");
+    if (mem != LWP_MEM_HOST && mem != LWP_MEM_DEVICE) return fail(h, LWP_ERR_ARG, "mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    if (stride < 1 || stride > 1024) return fail(h, LWP_ERR_ARG, "stride must be 1..1024");
+    if (H < stride || W < stride || H > (1 << 20) || W > (1 << 20)) return fail(h, LWP_ERR_ARG, "the mask must hold at least one stride x stride block (and at most 2^20 pixels a side)");
+    if ((int64_t)(H / stride) * (W / stride) > (1 << 28)) return fail(h, LWP_ERR_ARG, "oversized map: more than 2^28 cells");
+    if (H % stride || W % stride) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "a %d x %d mask is not a whole number of %d x %d blocks: only exact block means are supported", H, W, stride, stride);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = order_in(h);
+    if (rc) return rc;
+    const float* d_src = mask;
+    if (mem == LWP_MEM_HOST) {
+        const size_t mb = (size_t)N * H * W * sizeof(float);
+        if (h->d_train_bytes < mb) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            rc = ensure_dev(h, &h->d_train, &h->d_train_bytes, mb);
+            if (rc) return rc;
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->d_train, mask, mb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        d_src = h->d_train;
+    }
+    LAUNCH(h, KC_OTHER, launch_mask_downsample(d_src, N, H, W, stride, out_device, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+// argument checks and the partials buffer: everything of lwp_stage_losses before its launches, shared with lwp_time_stage_losses
+static int stage_losses_prepare(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
+                                const float* mask, int N, int hs, int ws, int batch_size) {
+    char msg[200];
+    if (!outs || !mask) return fail(h, LWP_ERR_ARG, "outs / mask is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    if (hs < 1 || ws < 1 || (int64_t)hs * ws > (1 << 28)) return fail(h, LWP_ERR_ARG, "empty or oversized map");
+    if (batch_size < 1) return fail(h, LWP_ERR_ARG, "batch_size must be at least 1");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    const int S = 2 * (h->g.nref + 1);
+    if (n_outs != S) {
+        snprintf(msg, sizeof msg, "n_outs is %d but the network returns %d stage tensors (2 x (num_refinement_stages + 1))", n_outs, S);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    if (h->skel.K + 1 != h->g.NH || 2 * h->skel.L != h->g.NP) {
+        snprintf(msg, sizeof msg, "the skeleton's targets have %d + 1 heat-map and 2 x %d PAF channels, the network's tensors %d and %d",
+                 h->skel.K, h->skel.L, h->g.NH, h->g.NP);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    bool any[2] = {false, false};
+    for (int s = 0; s < S; ++s) if (outs[s]) any[s & 1] = true;
+    if ((any[0] && !keypoint_maps) || (any[1] && !paf_maps)) return fail(h, LWP_ERR_ARG, "keypoint_maps / paf_maps is null but a tensor of its kind is given");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = order_in(h);
+    if (rc) return rc;
+    const int blocks = stage_loss_blocks(N, hs * ws);
+    const size_t need = ((size_t)kLossMaxOuts * blocks + S) * sizeof(double);
+    if (h->d_loss_bytes < need) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        rc = ensure_dev(h, &h->d_loss, &h->d_loss_bytes, need);
+        if (rc) return rc;
+    }
+    return LWP_OK;
+}
+
+// the launches of one lwp_stage_losses call; the S sums land behind the partials in d_loss
+static int enqueue_stage_losses(lwp_handle h, const float* const* outs, const float* keypoint_maps, const float* paf_maps,
+                                const float* mask, int N, int hs, int ws, int batch_size) {
+    const int S = 2 * (h->g.nref + 1);
+    const int blocks = stage_loss_blocks(N, hs * ws);
+    double* d_partials = (double*)h->d_loss;
+    double* d_losses = d_partials + (size_t)kLossMaxOuts * blocks;
+    for (int s0 = 0; s0 < S; s0 += kLossMaxOuts) {       // one launch up to 16 tensors (7 refinement stages); each launch reads the targets once
+        StageLossParams p{};
+        p.S = std::min(kLossMaxOuts, S - s0);
+        for (int s = 0; s < p.S; ++s) p.outs[s] = outs[s0 + s];
+        p.keypoint_maps = keypoint_maps; p.paf_maps = paf_maps; p.mask = mask;
+        p.N = N; p.CH = h->g.NH; p.CP = h->g.NP; p.hw = hs * ws; p.batch = batch_size;
+        p.partials = d_partials;
+        LAUNCH(h, KC_OTHER, launch_stage_losses(p, d_losses + s0, h->stream));
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
+                                const float* mask, int N, int hs, int ws, int batch_size, double* losses_host) {
+    if (!losses_host) return fail(h, LWP_ERR_ARG, "losses_host is null");
+    int rc = stage_losses_prepare(h, outs, n_outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size);
+    if (rc) return rc;
+    rc = enqueue_stage_losses(h, outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size);
+    if (rc) return rc;
+    const int S = 2 * (h->g.nref + 1);
+    const double* d_losses = (const double*)h->d_loss + (size_t)kLossMaxOuts * stage_loss_blocks(N, hs * ws);
+    HIP_TRY(h, hipMemcpyAsync(losses_host, d_losses, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- introspection
 extern "C" int lwp_layer_count(lwp_handle h) { return h ? (int)h->g.layers.size() : LWP_ERR_ARG; }
 
@@ -2308,6 +2511,28 @@ extern "C" int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, in
     if (rc) return rc;
     h->last_N = N;
     return time_on_stream(h, iters, [&]() { return enqueue_poses(h, in_device, N, H, W, ratio, demo, what != 0); }, ms_total);
+}
+
+// the training kernels alone: ``iters`` back-to-back launches between two events, after one prepare (checks, uploads) and
+// without the per-call synchronise or the copy-back of the sums
+extern "C" int lwp_time_train_targets(lwp_handle h, const double* kpts, int kpts_mem, const int* n_persons, int N, int Pmax, int H,
+                                      int W, int stride, double sigma, double paf_thickness, float* keypoint_maps_device,
+                                      float* paf_maps_device, int iters, float* ms_total) {
+    if (!ms_total || iters <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    TrainTargetsParams p{};
+    int rc = train_targets_prepare(h, kpts, kpts_mem, n_persons, N, Pmax, H, W, stride, sigma, paf_thickness, keypoint_maps_device,
+                                   paf_maps_device, &p);
+    if (rc) return rc;
+    return time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_train_targets(p, N, h->stream)); return (int)LWP_OK; }, ms_total);
+}
+
+extern "C" int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps,
+                                     const float* paf_maps, const float* mask, int N, int hs, int ws, int batch_size, int iters,
+                                     float* ms_total) {
+    if (!ms_total || iters <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    int rc = stage_losses_prepare(h, outs, n_outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size);
+    if (rc) return rc;
+    return time_on_stream(h, iters, [&]() { return enqueue_stage_losses(h, outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size); }, ms_total);
 }
 
 extern "C" int lwp_profile_launches(lwp_handle h, const float* in_device, int N, int H, int W, int ratio, int demo, int reps,

@@ -348,6 +348,34 @@ struct OverlayParams {
 // (frame, pose slot) for the boxes; `poses` bounds the pose slots the grid covers (<= P)
 hipError_t launch_overlay(const OverlayParams& p, int poses, hipStream_t s);
 
+// ---- training targets and loss (train_kernels.hip; datasets/coco.py:48,71-159, modules/loss.py)
+constexpr int kTrainChunk = 8;      // persons of a frame staged in LDS at a time
+constexpr int kLossMaxOuts = 16;    // stage tensors one loss launch reads (more: further launches over the same targets)
+constexpr int kLossMaxBlocks = 1024;
+struct TrainTargetsParams {
+    const double* kpts;             // N x Pmax x K x 3: x, y, visibility
+    const int* n_persons;           // [N], clamped to 0..Pmax
+    int Pmax, K, L;
+    const int* limbs;               // [L][4] as PostWorkspace::limbs
+    int h, w, stride;               // map size, H // stride x W // stride
+    double sigma, thickness;
+    float* keypoint_maps;           // N x (K + 1) x h x w
+    float* paf_maps;                // N x 2L x h x w
+};
+hipError_t launch_train_targets(const TrainTargetsParams& p, int N, hipStream_t s);
+hipError_t launch_mask_downsample(const float* src, int N, int H, int W, int stride, float* dst, hipStream_t s);
+struct StageLossParams {
+    const float* outs[kLossMaxOuts];   // even: N x CH x hw heat-map tensors, odd: N x CP x hw PAF tensors; null = skipped
+    int S;
+    const float* keypoint_maps;     // N x CH x hw (null when no even tensor is given)
+    const float* paf_maps;          // N x CP x hw (null when no odd tensor is given)
+    const float* mask;              // N x hw, broadcast over the channels
+    int N, CH, CP, hw, batch;
+    double* partials;               // [S][stage_loss_blocks(N, hw)]
+};
+int stage_loss_blocks(int N, int hw);
+hipError_t launch_stage_losses(const StageLossParams& p, double* losses, hipStream_t s);   // losses: S doubles, device
+
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);
 hipError_t launch_upsample(const MapView& src, int N, int C, int ratio, float* dst, hipStream_t s, const Tuning* tune = nullptr);

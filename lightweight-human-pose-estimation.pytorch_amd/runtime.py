@@ -646,6 +646,108 @@ class Engine(object):
         check(lib().lwp_get_overlay(self.h.ptr, slot, ptr, mem, shape[0], shape[1], shape[2]), self.h.ptr)
         return out
 
+    # ------------------------------------------------------------------ training targets and loss (coco.py:48-61,71-159; loss.py)
+    def train_targets(self, kpts, n_persons, image_hw, stride=8, sigma=7, paf_thickness=1, time_iters=0):
+        """Key-point and PAF target maps rendered on the device.  ``kpts``: (N, Pmax, K, 3) float64 rows (x, y, visibility),
+        numpy or a cuda tensor, persons in label order; ``n_persons``: (N,) counts; ``image_hw``: (H, W) of the frames.
+        Returns float32 cuda tensors ``keypoint_maps`` (N, K + 1, H // stride, W // stride) and ``paf_maps`` (N, 2L, ...) for
+        the engine's skeleton (``set_skeleton``; the default gives coco.py's channel layout).  With ``time_iters`` > 0 the
+        kernel is launched that many times back to back and the call returns the milliseconds of all of them (HIP events)."""
+        torch = _torch()
+        H, W = int(image_hw[0]), int(image_hw[1])
+        sk = self.skeleton
+        K, L = sk["num_kpt_types"], len(sk["limb_kpts"])
+        if getattr(kpts, "is_cuda", False):
+            a = kpts.detach().to(torch.float64).contiguous()
+            ptr, mem = a.data_ptr(), MEM_DEVICE
+        else:
+            a = np.ascontiguousarray(kpts, dtype=np.float64)
+            ptr, mem = a.ctypes.data, MEM_HOST
+        if len(a.shape) != 4 or tuple(a.shape[2:]) != (K, 3):
+            raise ValueError("expected key-points of shape (N, Pmax, %d, 3), got %s" % (K, tuple(a.shape)))
+        N, Pmax = int(a.shape[0]), int(a.shape[1])
+        n = np.ascontiguousarray(n_persons, dtype=np.int32).reshape(-1)
+        if n.shape != (N,):
+            raise ValueError("expected %d person counts, got %s" % (N, n.shape))
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        dev = torch.device("cuda", self.device_id)
+        kmaps = torch.empty((N, K + 1, H // stride, W // stride), dtype=torch.float32, device=dev)
+        pmaps = torch.empty((N, 2 * L, H // stride, W // stride), dtype=torch.float32, device=dev)
+        self._order()
+        args = (self.h.ptr, ptr if Pmax else None, mem, n.ctypes.data_as(C.POINTER(C.c_int)), N, Pmax, H, W, stride, float(sigma),
+                float(paf_thickness), kmaps.data_ptr(), pmaps.data_ptr())
+        if time_iters:
+            ms = C.c_float()
+            check(lib().lwp_time_train_targets(*args, int(time_iters), C.byref(ms)), self.h.ptr)
+            return ms.value
+        check(lib().lwp_train_targets(*args), self.h.ptr)
+        return kmaps, pmaps
+
+    def mask_downsample(self, mask, stride=8):
+        """(N, H, W) or (H, W) float32 mask (numpy or cuda tensor) -> the mean of each stride x stride block as a float32 cuda
+        tensor (N, H // stride, W // stride): cv2.resize(mask, fx=fy=1/stride, INTER_AREA) of coco.py:48 where H and W are
+        multiples of the stride (ValueError otherwise)."""
+        torch = _torch()
+        if getattr(mask, "is_cuda", False):
+            a = mask.detach().to(torch.float32).contiguous()
+            ptr, mem = a.data_ptr(), MEM_DEVICE
+        else:
+            a = np.ascontiguousarray(mask, dtype=np.float32)
+            ptr, mem = a.ctypes.data, MEM_HOST
+        single = len(a.shape) == 2
+        if len(a.shape) not in (2, 3):
+            raise ValueError("expected a mask of shape (N, H, W) or (H, W), got %s" % (tuple(a.shape),))
+        N = 1 if single else int(a.shape[0])
+        H, W = int(a.shape[-2]), int(a.shape[-1])
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        out = torch.empty((N, H // stride, W // stride), dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        self._order()
+        check(lib().lwp_mask_downsample(self.h.ptr, ptr, mem, N, H, W, stride, out.data_ptr()), self.h.ptr)
+        return out[0] if single else out
+
+    def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
+        """train.py:92-97's per-stage sums: ``outs`` is the list net(x) returned (cuda tensors; an entry may be None),
+        ``keypoint_maps`` / ``paf_maps`` the targets, ``mask`` one (N, h, w) cuda tensor broadcast over the channels.
+        Returns 2 * (nref + 1) Python floats, loss[i] = sum(((outs[i] - target) * mask)**2 / 2 / batch_size) in float64;
+        two calls on the same inputs return the same bits.  Tensors are read as contiguous NCHW float32: a strided view is
+        copied first (``Engine.forward`` returns contiguous tensors, which are read in place).  With ``time_iters`` > 0 the
+        kernels are launched that many times back to back and the call returns the milliseconds of all of them (HIP events)."""
+        torch = _torch()
+
+        def dev32(t, what, shape):
+            if t is None:
+                return None
+            if not getattr(t, "is_cuda", False):
+                raise TypeError("%s must be a cuda tensor" % what)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s has shape %s, expected %s" % (what, tuple(t.shape), shape))
+            return t.detach().to(torch.float32).contiguous()
+        ref = next((o for o in outs if o is not None), None)
+        if ref is None:
+            raise ValueError("no stage tensor given")
+        N, _, hs, ws = (int(v) for v in ref.shape)
+        keep = [dev32(o, "outs[%d]" % i, (N, self.NP if i % 2 else self.NH, hs, ws)) for i, o in enumerate(outs)]
+        km = dev32(keypoint_maps, "keypoint_maps", (N, self.NH, hs, ws))
+        pm = dev32(paf_maps, "paf_maps", (N, self.NP, hs, ws))
+        m = dev32(mask, "mask", (N, hs, ws))
+        if m is None:
+            raise ValueError("mask is None")
+        ptrs = (C.c_void_p * max(len(keep), 1))(*[None if o is None else o.data_ptr() for o in keep])
+        losses = (C.c_double * max(len(keep), 1))()
+        self._order()
+        args = (self.h.ptr, ptrs, len(keep), None if km is None else km.data_ptr(), None if pm is None else pm.data_ptr(), m.data_ptr(),
+                N, hs, ws, int(N if batch_size is None else batch_size))
+        if time_iters:
+            ms = C.c_float()
+            check(lib().lwp_time_stage_losses(*args, int(time_iters), C.byref(ms)), self.h.ptr)
+            return ms.value
+        check(lib().lwp_stage_losses(*args, losses), self.h.ptr)
+        return [float(losses[i]) for i in range(len(keep))]
+
     # ------------------------------------------------------------------ measurement
     def time_pipeline(self, x_cuda, iters, what=1, upsample_ratio=4, demo=True):
         """milliseconds for ``iters`` back-to-back passes (HIP events on the engine's stream)."""

@@ -96,6 +96,26 @@ def poses_batch(net, avg_heatmaps, avg_pafs):
     return net.engine.poses_from_maps(avg_heatmaps, avg_pafs, 1, demo=False, layout="NHWC")
 
 
+# ---------------------------------------------------------------------------------------------- label-grounded loss
+def stage_losses(net, images, labels, masks=None, stride=8, sigma=7, paf_thickness=1, batch_size=None):
+    """The quantity the reference's training minimises (train.py:92-97), measured, not optimised: forward, targets and the
+    masked L2 loss of every stage on the GPU in one call.  ``images``: the network input (N, 3, H, W) float32 as
+    CocoTrainDataset yields it ((image - 128) / 256, CHW), numpy or torch; ``labels``: one label dict per frame
+    (prepare_train_labels.py's format); ``masks``: (N, H, W) float32 or None for all ones.  Returns the 2 * (nref + 1) floats
+    [heat0, paf0, heat1, paf1, ...] with batch_size = N unless given.  Works for every engine dtype; no gradients."""
+    import torch
+    from .datasets.coco import generate_targets
+    x = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)) if isinstance(images, np.ndarray) else images
+    eng = net.engine
+    x = x.to(torch.device("cuda", eng.device_id))
+    outs = net(x)
+    t = generate_targets(net, labels, (int(x.shape[2]), int(x.shape[3])), masks, stride, sigma, paf_thickness)
+    if tuple(outs[0].shape[2:]) != tuple(t["keypoint_maps"].shape[2:]):
+        raise ValueError("the network's maps are %s but the targets %s: the frame size must be a multiple of the stride"
+                         % (tuple(outs[0].shape[2:]), tuple(t["keypoint_maps"].shape[2:])))
+    return eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], t["keypoint_mask"][:, 0], batch_size)
+
+
 # ---------------------------------------------------------------------------------------------- COCO results
 # slot of each of the 18 network key-points in COCO's 17-key-point order (the neck, index 1, has none)
 _COCO_SLOT = (0, None, 6, 8, 10, 5, 7, 9, 12, 14, 16, 11, 13, 15, 2, 1, 4, 3)
