@@ -392,6 +392,48 @@ int lwp_time_train_targets(lwp_handle h, const double* kpts, int kpts_mem, const
 int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
                           const float* mask, int N, int hs, int ws, int batch_size, int iters, float* ms_total);
 
+/* ---- stage backward: the gradient of train.py:99-102's summed loss
+ *        L = loss_scale * sum_i l2_loss(stages_output[i], target_i, mask, batch_size)      (modules/loss.py: sum(((out - target) * mask)^2) / 2 / batch_size)
+ *      with respect to every parameter of initial_stage.* and refinement_stages.* (with_mobilenet.py:25-86) and to
+ *      backbone_features, the output of cpm.conv (with_mobilenet.py:117).  fp32 handles only; the backbone and the cpm are frozen,
+ *      and the refinement trunks' BatchNorms (modules/conv.py:8) stay at their running statistics: the result is what
+ *      loss.backward() gives on the reference network in eval() mode, NOT in train() mode (no batch statistics, running_mean /
+ *      running_var / num_batches_tracked get no gradient and are not updated).  There is no optimiser.
+ *      lwp_train_forward: with_mobilenet.py:114-123 on in_device (N x 3 x H x W float32, DEVICE) into outs_device[2 * (nref + 1)]
+ *      (DEVICE, NCHW float32) with the kernels, weights and reduction order of lwp_forward — the outputs are bit-identical —
+ *      while from cpm.conv's output onward every layer's output is kept in a buffer of its own (each refinement stage has its
+ *      own [features | heat | paf] concat input).  Where lwp_forward runs a stage's head pair as one kernel, the pair's hidden
+ *      tensor is computed once more by the plain 1x1 kernel for the retained copy.  N must fit one pass (lwp_debug_frames_per_pass).
+ *      lwp_stage_backward: keypoint_maps N x num_heatmaps x hs x ws, paf_maps N x num_pafs x hs x ws, mask N x hs x ws (DEVICE,
+ *      as lwp_stage_losses takes them).  d out_i = loss_scale * (out_i - target_i) * mask^2 / batch_size (loss_scale carries
+ *      train.py:102's 1 / batches_per_iter).  grads_device: ONE float32 DEVICE array of lwp_stage_grad_count's total; the
+ *      gradient of parameter `key` sits at lwp_stage_grad_spec's offset with lwp_param_spec's shape (OIHW weights, biases, BN
+ *      weight and BN bias), parameters in lwp_param_spec order.  accumulate != 0 adds to the array (train.py:96's
+ *      batches_per_iter), else it is overwritten.  d_features_device: NULL, or N x num_channels x hs x ws NCHW (DEVICE),
+ *      always overwritten.  All sums run in a fixed order without floating-point atomics: the same inputs give the same bits.
+ *      LWP_ERR_ARG with a message: no lwp_train_forward of the same N, hs, ws precedes the call; a bf16 / fp16 handle; no
+ *      weights loaded through lwp_load_weights (a weight blob has no raw parameters); the skeleton's K + 1 / 2L differ from
+ *      num_heatmaps / num_pafs (as in lwp_stage_losses); batch_size < 1.
+ *      Both run on the handle's stream and honour lwp_set_stream. */
+int lwp_train_forward(lwp_handle h, const float* in_device, int N, int H, int W, float* const* outs_device);
+int lwp_stage_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
+                       int batch_size, double loss_scale, int accumulate, float* grads_device, float* d_features_device);
+/* layout of the gradient array: lwp_stage_grad_count returns the number of parameters with a gradient (total_floats out, may be
+ * NULL); lwp_stage_grad_spec the state-dict key, shape and float offset of entry `index`.  No handle, no GPU. */
+int lwp_stage_grad_count(int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int64_t* total_floats);
+int lwp_stage_grad_spec(int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int index, char* name,
+                        int name_cap, int64_t shape[4], int* ndim, int64_t* offset);
+/* one backward per rep between HIP events around each launch (tools/backward_bench.py): ms[4], launches[4] by class:
+ * 0 = loss gradient / ReLU masks / sums, 1 = data gradient, 2 = weight gradient, 3 = partial-sum reduction and BatchNorm chain rule */
+int lwp_profile_stage_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
+                               int batch_size, double loss_scale, float* grads_device, float* d_features_device, int reps,
+                               float* ms, int* launches);
+/* tests: the output the last lwp_train_forward retained for layer `layer_index` (cpm.conv or a stage layer of lwp_layer_info's
+ * list; a refinement block's last conv holds relu(z) + residual, as the forward kernel writes it) as NCHW float32 in dst (HOST);
+ * and the number of pixel ranges the weight gradient of that layer was split into by the last lwp_stage_backward */
+int lwp_debug_train_activation(lwp_handle h, int layer_index, float* dst, size_t dst_floats, int out_dims[4]);
+int lwp_debug_backward_splits(lwp_handle h, int layer_index);
+
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */
 int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio,

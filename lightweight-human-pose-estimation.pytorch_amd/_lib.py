@@ -24,6 +24,8 @@ EXPORTS = [
     "lwp_preprocess_u8_batch", "lwp_pipeline_submit_u8",
     "lwp_set_overlay", "lwp_get_overlay", "lwp_draw_poses",
     "lwp_train_targets", "lwp_mask_downsample", "lwp_stage_losses", "lwp_time_train_targets", "lwp_time_stage_losses",
+    "lwp_train_forward", "lwp_stage_backward", "lwp_stage_grad_count", "lwp_stage_grad_spec", "lwp_profile_stage_backward",
+    "lwp_debug_train_activation", "lwp_debug_backward_splits",
 ]
 
 
@@ -106,6 +108,13 @@ def lib():
     L.lwp_stage_losses.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
     L.lwp_time_train_targets.argtypes = L.lwp_train_targets.argtypes + [C.c_int, fp]
     L.lwp_time_stage_losses.argtypes = L.lwp_stage_losses.argtypes[:-1] + [C.c_int, fp]
+    L.lwp_train_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.lwp_stage_backward.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]
+    L.lwp_stage_grad_count.argtypes = [C.c_int] * 4 + [i64p]
+    L.lwp_stage_grad_spec.argtypes = [C.c_int] * 5 + [C.c_char_p, C.c_int, i64p, ip, i64p]
+    L.lwp_profile_stage_backward.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, fp, ip]
+    L.lwp_debug_train_activation.argtypes = [vp, C.c_int, vp, C.c_size_t, ip]
+    L.lwp_debug_backward_splits.argtypes = [vp, C.c_int]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int
@@ -141,6 +150,23 @@ def param_spec(nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
         check(L.lwp_param_spec(nref, num_channels, num_heatmaps, num_pafs, i, name, 256, shape, C.byref(nd), C.byref(role)))
         out.append((name.value.decode(), tuple(shape[d] for d in range(nd.value)), role.value))
     return out
+
+
+def stage_grad_spec(nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
+    """([(key, shape tuple, float offset)], total floats) of lwp_stage_backward's gradient array (no GPU needed)."""
+    L = lib()
+    total = C.c_int64()
+    n = L.lwp_stage_grad_count(nref, num_channels, num_heatmaps, num_pafs, C.byref(total))
+    if n < 0:
+        raise ValueError("bad network shape")
+    out = []
+    name = C.create_string_buffer(256)
+    shape = (C.c_int64 * 4)()
+    nd, off = C.c_int(), C.c_int64()
+    for i in range(n):
+        check(L.lwp_stage_grad_spec(nref, num_channels, num_heatmaps, num_pafs, i, name, 256, shape, C.byref(nd), C.byref(off)))
+        out.append((name.value.decode(), tuple(shape[d] for d in range(nd.value)), off.value))
+    return out, total.value
 
 
 class Handle(object):

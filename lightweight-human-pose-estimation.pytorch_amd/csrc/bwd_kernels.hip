@@ -1,0 +1,314 @@
+// Stage backward (train.py:99-103 differentiated through initial_stage / refinement_stages, with_mobilenet.py:25-86), f32.
+//
+// Activations and gradients are NHWC windows (pointer + row stride), like the forward path.  Every GEMM here runs on
+// v_mfma_f32_16x16x4_f32 (lane l: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], C[i = 4 (l >> 4) + r][j = l & 15]):
+//   dgrad   dX[p][ci] = sum_tap sum_o dZ[p - off(tap)][o] * W[tap][o][ci]     M = pixels, N = cin, K = taps x cout
+//   wgrad   dW[tap][o][ci] = sum_p dZ[p][o] * X[p + off(tap)][ci]            M = cout, N = cin, K = pixels (split over workgroups)
+// A workgroup is 4 waves on a 64 x 64 output tile: wave w owns rows 16w .. 16w + 15 and four 16 x 16 accumulators (independent
+// chains, so the 40-cycle dependent latency of the instruction is covered).  Operand tiles go through LDS, 16 deep.
+// No floating-point atomics anywhere: wgrad writes per-split partial sums and a second kernel adds them in split order, so the
+// same inputs give the same bits.
+#include "lwp_internal.h"
+
+namespace lwp {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------------------------------- loss gradient
+// dL/d out = loss_scale * (out - target) * mask^2 / batch_size (modules/loss.py differentiated); targets NCHW, out and gradient NHWC
+__global__ void __launch_bounds__(256) loss_grad_kernel(LossGradParams p) {
+    const int s = blockIdx.y;
+    const int C = (s & 1) ? p.CP : p.CH;
+    const float* out = p.outs[s];
+    const float* tgt = (s & 1) ? p.paf_maps : p.keypoint_maps;
+    float* dst = p.dst[s];
+    const int64_t total = (int64_t)p.N * C * p.hw;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int px = (int)(i % p.hw);
+        const int64_t nc = i / p.hw;
+        const int c = (int)(nc % C);
+        const int64_t n = nc / C;
+        const float m = p.mask[n * p.hw + px];
+        const int64_t at = (n * p.hw + px) * p.ld + c;
+        const float d = out[at] - tgt[i];
+        dst[at] = d * m * m * p.scale;
+    }
+}
+
+hipError_t launch_loss_grad(const LossGradParams& p, hipStream_t s) {
+    if (p.S < 1 || p.S > kLossMaxOuts) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)p.N * (p.CH > p.CP ? p.CH : p.CP) * p.hw;
+    const unsigned bx = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(loss_grad_kernel, dim3(bx, (unsigned)p.S), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- element-wise pieces
+__global__ void __launch_bounds__(256) relu_mask_kernel(float* g, int g_ld, const float* y, int y_ld, const float* res, int res_ld,
+                                                        int64_t M, int C) {
+    const int64_t total = M * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t px = i / C;
+        const int c = (int)(i % C);
+        const float r = res ? res[px * res_ld + c] : 0.0f;
+        if (!(y[px * y_ld + c] > r)) g[px * g_ld + c] = 0.0f;
+    }
+}
+hipError_t launch_relu_mask(float* g, int g_ld, const float* y, int y_ld, const float* res, int res_ld, int64_t M, int C, hipStream_t s) {
+    const unsigned bx = (unsigned)std::min<int64_t>((M * C + 255) / 256, 8192);
+    hipLaunchKernelGGL(relu_mask_kernel, dim3(bx), dim3(256), 0, s, g, g_ld, y, y_ld, res, res_ld, M, C);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) grad_add_kernel(float* dst, int dst_ld, const float* src, int src_ld, int64_t M, int C, int beta) {
+    const int64_t total = M * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t px = i / C;
+        const int c = (int)(i % C);
+        const float v = src[px * src_ld + c];
+        float* d = dst + px * dst_ld + c;
+        *d = beta ? *d + v : v;
+    }
+}
+hipError_t launch_grad_add(float* dst, int dst_ld, const float* src, int src_ld, int64_t M, int C, int beta, hipStream_t s) {
+    const unsigned bx = (unsigned)std::min<int64_t>((M * C + 255) / 256, 8192);
+    hipLaunchKernelGGL(grad_add_kernel, dim3(bx), dim3(256), 0, s, dst, dst_ld, src, src_ld, M, C, beta);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- data gradient
+constexpr int BW_T = 64;       // output tile edge
+constexpr int BW_K = 16;       // K depth of one LDS stage
+constexpr int BW_APAD = 17;    // dgrad A tile [64 pixels][16 + 1]
+constexpr int BW_BPAD = 68;    // [16][64 + 4] tiles
+
+__global__ void __launch_bounds__(256) dgrad_kernel(DgradParams p) {
+    __shared__ float As[BW_T * BW_APAD];
+    __shared__ float Bs[BW_K * BW_BPAD];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int HW = p.H * p.W;
+    const int64_t M = (int64_t)p.N * HW;
+    const int64_t m0 = (int64_t)blockIdx.x * BW_T;
+    const int ci0 = blockIdx.y * BW_T;
+    // this thread's A-load row: one pixel of the tile, four consecutive k
+    const int arow = t >> 2, ak = (t & 3) * 4;
+    const int64_t am = m0 + arow;
+    const bool a_in = am < M;
+    int an = 0, ay = 0, ax = 0;
+    if (a_in) { an = (int)(am / HW); const int r = (int)(am % HW); ay = r / p.W; ax = r % p.W; }
+    // B-load: row k of the stage, four consecutive input channels
+    const int brow = t >> 4, bn = (t & 15) * 4;
+    const bool b_in = ci0 + bn < p.cin_pad;
+    f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    const int half = p.ks / 2;
+    for (int tap = 0; tap < p.ks * p.ks; ++tap) {
+        // forward: Y[q] takes X[q + (k - half) * dil], so dX[q] takes dZ[q - (k - half) * dil]
+        const int sy = ay - (tap / p.ks - half) * p.dil, sx = ax - (tap % p.ks - half) * p.dil;
+        const bool a_ok = a_in && sy >= 0 && sy < p.H && sx >= 0 && sx < p.W;
+        const float* arow_ptr = p.dz + ((int64_t)an * HW + (int64_t)sy * p.W + sx) * p.dz_ld;
+        const float* wt = p.w + (size_t)tap * p.cout_pad * p.cin_pad;
+        for (int o0 = 0; o0 < p.cout; o0 += BW_K) {
+            float av[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) av[j] = (a_ok && o0 + ak + j < p.cout) ? arow_ptr[o0 + ak + j] : 0.0f;
+            f32x4 bv = {0, 0, 0, 0};
+            if (b_in) bv = *(const f32x4*)(wt + (size_t)(o0 + brow) * p.cin_pad + ci0 + bn);   // rows < cout_pad (a multiple of 64), zero beyond cout
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) As[arow * BW_APAD + ak + j] = av[j];
+            *(f32x4*)(Bs + brow * BW_BPAD + bn) = bv;
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < BW_K; kk += 4) {
+                const float a = As[(16 * wv + (lane & 15)) * BW_APAD + kk + (lane >> 4)];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Bs[(kk + (lane >> 4)) * BW_BPAD + 16 * j + (lane & 15)], acc[j], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ci = ci0 + 16 * j + (lane & 15);
+        if (ci >= p.cin) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t m = m0 + 16 * wv + 4 * (lane >> 4) + r;
+            if (m >= M) continue;
+            float* d = p.dx + m * p.dx_ld + ci;
+            *d = ci >= p.acc_from ? *d + acc[j][r] : acc[j][r];
+        }
+    }
+}
+
+hipError_t launch_dgrad(const DgradParams& p, hipStream_t s) {
+    const int64_t M = (int64_t)p.N * p.H * p.W;
+    if (M < 1 || M >= (1ll << 31) - BW_T || p.cout < 1 || p.cin < 1 || p.cout > p.cout_pad || p.cin > p.cin_pad || (p.cin_pad & 3) ||
+        (p.cout_pad % BW_K) || (p.ks != 1 && p.ks != 3))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dgrad_kernel, dim3((unsigned)((M + BW_T - 1) / BW_T), (unsigned)((p.cin + BW_T - 1) / BW_T)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- weight and bias gradient
+// grid: x = cout tiles x cin tiles, y = tap (+ one extra row of workgroups for the bias column sums), z = pixel split
+__global__ void __launch_bounds__(256) wgrad_kernel(WgradParams p) {
+    __shared__ float As[BW_K * BW_BPAD];      // [pixel][cout channel]
+    __shared__ float Bs[BW_K * BW_BPAD];      // [pixel][cin channel]
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int taps = p.ks * p.ks;
+    const int co_p = wgrad_pad64(p.cout), ci_p = wgrad_pad64(p.cin);
+    const int ci_t = ci_p / BW_T;
+    const int o0 = (blockIdx.x / ci_t) * BW_T, c0 = (blockIdx.x % ci_t) * BW_T;
+    const int tap = blockIdx.y, z = blockIdx.z;
+    const int HW = p.H * p.W;
+    const int64_t M = (int64_t)p.N * HW;
+    const int64_t p_begin = (int64_t)z * p.chunk;
+    const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
+    if (tap == taps) {
+        // bias: db[o] = sum over the split's pixels of dZ[p][o]; 4 pixel lanes per channel, added in lane order
+        if (c0 != 0) return;
+        const int c = t & 63, pl = t >> 6;
+        float sum = 0.0f;
+        if (o0 + c < p.cout)
+            for (int64_t px = p_begin + pl; px < p_end; px += 4) sum += p.dz[px * p.dz_ld + o0 + c];
+        As[pl * 64 + c] = sum;
+        __syncthreads();
+        if (t < 64) {
+            float* bpart = p.partial + (size_t)p.splits * taps * co_p * ci_p;
+            bpart[(size_t)z * co_p + o0 + t] = ((As[t] + As[64 + t]) + As[128 + t]) + As[192 + t];
+        }
+        return;
+    }
+    const int half = p.ks / 2;
+    const int dy = (tap / p.ks - half) * p.dil, dx = (tap % p.ks - half) * p.dil;
+    const int lrow = t >> 4, lc = (t & 15) * 4;       // this thread's load: pixel lrow of the stage, four consecutive channels
+    f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    for (int64_t px0 = p_begin; px0 < p_end; px0 += BW_K) {
+        const int64_t px = px0 + lrow;
+        float av[4] = {0, 0, 0, 0}, bv[4] = {0, 0, 0, 0};
+        if (px < p_end) {
+            const float* zr = p.dz + px * p.dz_ld + o0 + lc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (o0 + lc + j < p.cout) av[j] = zr[j];
+            const int n = (int)(px / HW), r = (int)(px % HW);
+            const int sy = r / p.W + dy, sx = r % p.W + dx;
+            if (sy >= 0 && sy < p.H && sx >= 0 && sx < p.W) {
+                const float* xr = p.x + ((int64_t)n * HW + (int64_t)sy * p.W + sx) * p.x_ld + c0 + lc;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (c0 + lc + j < p.cin) bv[j] = xr[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { As[lrow * BW_BPAD + lc + j] = av[j]; Bs[lrow * BW_BPAD + lc + j] = bv[j]; }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < BW_K; kk += 4) {
+            const float a = As[(kk + (lane >> 4)) * BW_BPAD + 16 * wv + (lane & 15)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Bs[(kk + (lane >> 4)) * BW_BPAD + 16 * j + (lane & 15)], acc[j], 0, 0, 0);
+        }
+    }
+    float* part = p.partial + (((size_t)z * taps + tap) * co_p + o0) * ci_p + c0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            part[(size_t)(16 * wv + 4 * (lane >> 4) + r) * ci_p + 16 * j + (lane & 15)] = acc[j][r];
+}
+
+// pixel ranges of at least 64 pixels, as many as bring the grid to about four workgroups per CU
+void wgrad_plan(int64_t M, int cout, int cin, int ks, int* splits, int* chunk) {
+    const int64_t tiles = (int64_t)(wgrad_pad64(cout) / BW_T) * (wgrad_pad64(cin) / BW_T) * ks * ks;
+    int64_t sp = (1024 + tiles - 1) / tiles;
+    const int64_t max_sp = (M + 63) / 64;
+    if (sp > max_sp) sp = max_sp;
+    if (sp < 1) sp = 1;
+    int64_t ch = ((M + sp - 1) / sp + BW_K - 1) / BW_K * BW_K;
+    *chunk = (int)ch;
+    *splits = (int)((M + ch - 1) / ch);
+}
+
+hipError_t launch_wgrad(const WgradParams& p, hipStream_t s) {
+    const int64_t M = (int64_t)p.N * p.H * p.W;
+    if (M < 1 || M >= (1ll << 31) - BW_T || p.cout < 1 || p.cin < 1 || (p.ks != 1 && p.ks != 3) || p.splits < 1 || p.splits > 65535 ||
+        p.chunk < BW_K || (p.chunk % BW_K) || (int64_t)p.splits * p.chunk < M)
+        return hipErrorInvalidValue;
+    const unsigned tiles = (unsigned)((wgrad_pad64(p.cout) / BW_T) * (wgrad_pad64(p.cin) / BW_T));
+    hipLaunchKernelGGL(wgrad_kernel, dim3(tiles, (unsigned)(p.ks * p.ks + 1), (unsigned)p.splits), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(WgradParams p, float* dw, float* db, int accumulate) {
+    const int taps = p.ks * p.ks;
+    const int co_p = wgrad_pad64(p.cout), ci_p = wgrad_pad64(p.cin);
+    const int64_t nw = (int64_t)p.cout * p.cin * taps;
+    const int64_t total = nw + p.cout;
+    const float* bpart = p.partial + (size_t)p.splits * taps * co_p * ci_p;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        float sum = 0.0f;
+        float* d;
+        if (i < nw) {                                   // OIHW: ((o * cin) + ci) * taps + tap
+            const int tap = (int)(i % taps);
+            const int64_t oc = i / taps;
+            const int ci = (int)(oc % p.cin), o = (int)(oc / p.cin);
+            for (int z = 0; z < p.splits; ++z) sum += p.partial[(((size_t)z * taps + tap) * co_p + o) * ci_p + ci];
+            d = dw + i;
+        } else {
+            const int o = (int)(i - nw);
+            for (int z = 0; z < p.splits; ++z) sum += bpart[(size_t)z * co_p + o];
+            d = db + o;
+        }
+        *d = accumulate ? *d + sum : sum;
+    }
+}
+
+hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int accumulate, hipStream_t s) {
+    const int64_t total = (int64_t)p.cout * p.cin * p.ks * p.ks + p.cout;
+    const unsigned bx = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(bx), dim3(256), 0, s, p, dw, db, accumulate);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- BatchNorm at running statistics
+// z = s (W * x + b - mu) + beta, s = gamma / sqrt(var + 1e-5) (modules/conv.py:8 in eval()).  From G = dL/d(sW), g = dL/d(folded bias):
+//   dW = s G, db = s g, dbeta = g, dgamma = (<W, G> + g (b - mu)) / sqrt(var + 1e-5).  One workgroup per output channel, float64.
+__global__ void __launch_bounds__(256) bn_chain_kernel(BnChainParams p) {
+    __shared__ double red[256];
+    const int o = blockIdx.x, t = threadIdx.x;
+    const double inv = 1.0 / sqrt((double)p.var[o] + 1e-5);
+    const double sc = (double)p.gamma[o] * inv;
+    const float* G = p.G + (size_t)o * p.K;
+    const float* W = p.W + (size_t)o * p.K;
+    float* dW = p.dW + (size_t)o * p.K;
+    double dot = 0.0;
+    for (int k = t; k < p.K; k += 256) {
+        dot += (double)W[k] * (double)G[k];
+        const float v = (float)(sc * (double)G[k]);
+        dW[k] = p.accumulate ? dW[k] + v : v;
+    }
+    red[t] = dot;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (t < st) red[t] += red[t + st];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double g = (double)p.g[o];
+        const float vb = (float)(sc * g), vbeta = (float)g;
+        const float vg = (float)((red[0] + g * ((double)p.b[o] - (double)p.mean[o])) * inv);
+        p.db[o] = p.accumulate ? p.db[o] + vb : vb;
+        p.dbeta[o] = p.accumulate ? p.dbeta[o] + vbeta : vbeta;
+        p.dgamma[o] = p.accumulate ? p.dgamma[o] + vg : vg;
+    }
+}
+
+hipError_t launch_bn_chain(const BnChainParams& p, hipStream_t s) {
+    if (p.cout < 1 || p.K < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_chain_kernel, dim3((unsigned)p.cout), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace lwp

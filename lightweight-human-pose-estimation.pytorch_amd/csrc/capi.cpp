@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -86,6 +87,21 @@ struct lwp_context {
     // counts and host masks; the loss partials followed by the per-stage sums
     float* d_train = nullptr; size_t d_train_bytes = 0;
     float* d_loss = nullptr; size_t d_loss_bytes = 0;
+    // stage backward (lwp_train_forward / lwp_stage_backward; f32 handles): the retaining buffer plan, its activation and
+    // gradient buffers, the gradient array's layout, the raw stage parameters (the BatchNorm chain rule needs them unfolded)
+    TrainPlan tp;
+    std::vector<float*> tbufs, gbufs;
+    std::vector<size_t> tbuf_bytes;
+    int train_N = 0, train_H = 0, train_W = 0;      // frames of the last retaining forward (0: none)
+    struct GradSpec { std::string key; int64_t shape[4]; int ndim; size_t off; };
+    std::vector<GradSpec> gspec;
+    std::map<std::string, size_t> grad_off;          // state-dict key -> float offset in the gradient array
+    std::map<std::string, size_t> raw_off;           // the same keys, and the BatchNorm running statistics -> float offset in d_raw
+    size_t grad_floats = 0, raw_floats = 0;
+    float* d_raw = nullptr;
+    bool raw_loaded = false;                         // false after lwp_weights_blob_import: a blob holds folded weights only
+    float* d_bwd = nullptr; size_t d_bwd_bytes = 0; size_t bwd_fold_off = 0;  // wgrad partials, then the folded gradients of one BatchNorm layer
+    std::vector<int> bwd_splits;                     // per layer: pixel splits its last wgrad ran with
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
     bool run_has_tail = false;             // the tail kernels ran behind the grouping whose results h->ws holds
@@ -120,6 +136,24 @@ Skeleton default_skeleton() {              // modules/keypoints.py:5-8
     return s;
 }
 }  // namespace lwp
+
+// the stage parameters that receive a gradient, in lwp_param_spec order (running statistics and counters excluded)
+static bool is_stage_key(const std::string& k) { return k.rfind("initial_stage.", 0) == 0 || k.rfind("refinement_stages.", 0) == 0; }
+static std::vector<lwp_context::GradSpec> stage_grad_spec(int nref, int C, int NH, int NP, size_t* total) {
+    std::vector<lwp_context::GradSpec> v;
+    size_t off = 0;
+    for (const ParamSpec& p : param_table(nref, C, NH, NP)) {
+        if (!is_stage_key(p.key) || p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR || p.role == LWP_ROLE_BN_NBT) continue;
+        lwp_context::GradSpec s;
+        s.key = p.key; s.ndim = p.ndim; s.off = off;
+        size_t n = 1;
+        for (int d = 0; d < 4; ++d) { s.shape[d] = p.shape[d]; if (d < p.ndim) n *= (size_t)p.shape[d]; }
+        off += n;
+        v.push_back(s);
+    }
+    if (total) *total = off;
+    return v;
+}
 
 static int fail(lwp_context* h, int code, const std::string& msg) {
     if (h) h->err = msg;
@@ -250,6 +284,19 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
         if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipMalloc(limbs): ") + hipGetErrorString(e)); }
     }
     h->bufs.assign(h->g.bufs.size(), nullptr);
+    if (dtype == LWP_F32) {
+        h->tp = build_train_plan(h->g);
+        h->tbufs.assign(h->tp.bufs.size(), nullptr);
+        h->gbufs.assign(h->tp.bufs.size(), nullptr);
+        h->tbuf_bytes.assign(h->tp.bufs.size(), 0);
+        h->gspec = stage_grad_spec(nref, C, NH, NP, &h->grad_floats);
+        for (const auto& s : h->gspec) h->grad_off[s.key] = s.off;
+        h->raw_off = h->grad_off;
+        h->raw_floats = h->grad_floats;
+        for (const ParamSpec& p : param_table(nref, C, NH, NP))
+            if (is_stage_key(p.key) && (p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR)) { h->raw_off[p.key] = h->raw_floats; h->raw_floats += (size_t)p.shape[0]; }
+        h->bwd_splits.assign(h->g.layers.size(), 0);
+    }
     h->d_outs.assign(2 * (1 + nref), nullptr);
     h->d_outs_bytes.assign(2 * (1 + nref), 0);
     *out = h;
@@ -280,6 +327,10 @@ extern "C" int lwp_destroy(lwp_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (float* p : h->bufs) if (p) (void)hipFree(p);
+    for (float* p : h->tbufs) if (p) (void)hipFree(p);
+    for (float* p : h->gbufs) if (p) (void)hipFree(p);
+    if (h->d_raw) (void)hipFree(h->d_raw);
+    if (h->d_bwd) (void)hipFree(h->d_bwd);
     for (float* p : h->d_outs) if (p) (void)hipFree(p);
     if (h->d_in) (void)hipFree(h->d_in);
     if (h->d_tmp) (void)hipFree(h->d_tmp);
@@ -430,6 +481,20 @@ extern "C" int lwp_load_weights(lwp_handle h, const char* const* names, const vo
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpy(h->d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
     h->weights_loaded = true;
+    if (h->dtype == LWP_F32) {                           // the stage parameters as given: lwp_stage_backward's BatchNorm chain rule
+        std::vector<float> raw(h->raw_floats, 0.0f);
+        for (int i = 0; i < n; ++i) {
+            auto it = h->raw_off.find(nm[i]);
+            if (it == h->raw_off.end()) continue;
+            size_t cnt = 1;
+            for (int d = 0; d < ts[i].ndim; ++d) cnt *= (size_t)ts[i].shape[d];
+            std::memcpy(raw.data() + it->second, ts[i].ptr, cnt * sizeof(float));     // shapes were checked by pack_weights
+        }
+        if (!h->d_raw) HIP_TRY(h, hipMalloc((void**)&h->d_raw, std::max<size_t>(h->raw_floats, 1) * sizeof(float)));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipMemcpy(h->d_raw, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice));
+        h->raw_loaded = true;
+    }
     return LWP_OK;
 }
 
@@ -473,6 +538,7 @@ extern "C" int lwp_weights_blob_import(lwp_handle h, const void* src, size_t byt
     }
     HIP_TRY(h, hipMemcpy(h->d_blob, src, packed, hipMemcpyDeviceToDevice));
     h->weights_loaded = true;
+    h->raw_loaded = false;
     return LWP_OK;
 }
 
@@ -688,19 +754,22 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
 
 // ---------------------------------------------------------------------------------------------- forward
 // element-addressed window of an activation buffer (f32, bf16 or fp16 storage)
+// (an index past the graph's buffers is a buffer of the retaining plan, TrainPlan: f32, level 3)
 static inline float* buf_at(lwp_context* h, const BufRef& r) {
-    return (float*)((char*)h->bufs[r.buf] + (size_t)r.coff * (h->dtype != LWP_F32 ? 2 : 4));
+    const int nb = (int)h->g.bufs.size();
+    char* base = r.buf < nb ? (char*)h->bufs[r.buf] : (char*)h->tbufs[r.buf - nb];
+    return (float*)(base + (size_t)r.coff * (h->dtype != LWP_F32 ? 2 : 4));
 }
+static inline int buf_level(const lwp_context* h, int buf) { return buf < (int)h->g.bufs.size() ? h->g.bufs[buf].level : 3; }
 
 static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int N, int H, int W, float* const* d_outs_nchw,
                          const Layer* fold = nullptr, bool* folded = nullptr) {
-    const Graph& g = h->g;
     const bool h16 = h->dtype != LWP_F32;            // bf16 or fp16: the same launchers, the element type rides in the params
     const int f16 = h->dtype == LWP_F16;
     const float* wts = h->d_blob + l.w_off;
     const float* bias = h->d_blob + l.b_off;
     int dh, dw;
-    level_dims(H, W, g.bufs[l.dst.buf].level, &dh, &dw);
+    level_dims(H, W, buf_level(h, l.dst.buf), &dh, &dw);
     float* dst = buf_at(h, l.dst);
     char* vb = h->record_variants ? h->variant_buf : nullptr;
     if (vb) vb[0] = 0;
@@ -710,7 +779,7 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
         LAUNCH(h, KC_STEM, h16 ? launch_stem_bf16(p, h->stream) : launch_stem(p, h->stream));
     } else if (l.kind == L_DWPW) {
         int sh, sw;
-        level_dims(H, W, g.bufs[l.src.buf].level, &sh, &sw);
+        level_dims(H, W, buf_level(h, l.src.buf), &sh, &sw);
         DwPwParams p;
         p.in = buf_at(h, l.src); p.in_ld = l.src.ld; p.f16 = f16;
         p.dw_w = wts; p.pw_w = h->d_blob + l.w2_off; p.pw_b = h->d_blob + l.b2_off;
@@ -723,7 +792,7 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
         LAUNCH(h, KC_PW, h16 ? launch_dwpw_bf16(p, h->stream) : launch_dwpw(p, h->stream));
     } else if (l.kind == L_DW) {
         int sh, sw;
-        level_dims(H, W, g.bufs[l.src.buf].level, &sh, &sw);
+        level_dims(H, W, buf_level(h, l.src.buf), &sh, &sw);
         DwParams p{buf_at(h, l.src), l.src.ld, wts, bias, dst, l.dst.ld, N, sh, sw, dh, dw, l.cin, l.stride, l.dil, l.act};
         p.tune = &h->tune; p.variant = vb;
         LAUNCH(h, KC_DW, launch_dw(p, h->stream));
@@ -770,7 +839,7 @@ static bool heads_pair_fusable(lwp_context* h, size_t i, int64_t M) {
 
 static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, int N, int H, int W, float* const* d_outs_nchw) {
     int dh, dw;
-    level_dims(H, W, h->g.bufs[b.dst.buf].level, &dh, &dw);
+    level_dims(H, W, buf_level(h, b.dst.buf), &dh, &dw);
     HeadsParams p;
     p.in = buf_at(h, a.src); p.in_ld = a.src.ld; p.f16 = h->dtype == LWP_F16;
     p.w0 = h->d_blob + a.w_off; p.b0 = h->d_blob + a.b_off;
@@ -2374,6 +2443,327 @@ extern "C" int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_ou
     HIP_TRY(h, hipMemcpyAsync(losses_host, d_losses, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- stage backward
+// classes of the backward launches for lwp_profile_stage_backward (they share the forward's event table)
+enum BwdClass { BK_ELEMENTWISE = 0, BK_DGRAD = 1, BK_WGRAD = 2, BK_REDUCE = 3, BK_COUNT = 4 };
+
+static int ensure_train_buffers(lwp_context* h, int N, int H, int W) {
+    int fh, fw;
+    level_dims(H, W, 3, &fh, &fw);
+    bool synced = false;
+    for (size_t i = 0; i < h->tp.bufs.size(); ++i) {
+        const size_t bytes = (size_t)N * fh * fw * h->tp.bufs[i].channels * sizeof(float);
+        const bool grow = bytes > h->tbuf_bytes[i];
+        if (grow) {
+            if (!synced) { HIP_TRY(h, hipStreamSynchronize(h->stream)); synced = true; }
+            if (h->tbufs[i]) { HIP_TRY(h, hipFree(h->tbufs[i])); h->tbufs[i] = nullptr; }
+            if (h->gbufs[i]) { HIP_TRY(h, hipFree(h->gbufs[i])); h->gbufs[i] = nullptr; }
+            h->tbuf_bytes[i] = 0;
+            HIP_TRY(h, hipMalloc((void**)&h->tbufs[i], bytes));
+            HIP_TRY(h, hipMalloc((void**)&h->gbufs[i], bytes));
+            h->tbuf_bytes[i] = bytes;
+        }
+        // pad channels of a concat buffer are read with zero weights: finite at every geometry (as in ensure_activations)
+        if (h->tp.bufs[i].has_pad && (grow || N != h->train_N || H != h->train_H || W != h->train_W))
+            HIP_TRY(h, hipMemsetAsync(h->tbufs[i], 0, bytes, h->stream));
+    }
+    return LWP_OK;
+}
+
+static int train_handle_check(lwp_context* h) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (h->dtype != LWP_F32) return fail(h, LWP_ERR_ARG, "the stage backward runs on fp32 handles only (this one is bf16 / fp16)");
+    if (!h->weights_loaded) return fail(h, LWP_ERR_ARG, "weights not loaded (call lwp_load_weights first)");
+    if (!h->raw_loaded) return fail(h, LWP_ERR_ARG, "the stage backward needs the raw parameters: load them with lwp_load_weights (a weight blob holds folded weights only)");
+    return LWP_OK;
+}
+
+extern "C" int lwp_train_forward(lwp_handle h, const float* in_device, int N, int H, int W, float* const* outs_device) {
+    int rc = train_handle_check(h);
+    if (rc) return rc;
+    if (!in_device || !outs_device) return fail(h, LWP_ERR_ARG, "null argument");
+    rc = check_frame_shape(h, N, H, W);
+    if (rc) return rc;
+    const int nout = 2 * (1 + h->g.nref);
+    for (int i = 0; i < nout; ++i) if (!outs_device[i]) return fail(h, LWP_ERR_ARG, "null output pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (frames_per_pass(h, N, H, W) != N) return fail(h, LWP_ERR_ARG, "batch too large for one retaining pass (a tensor would reach 2 GiB)");
+    rc = ensure_activations(h, N, H, W);
+    if (rc) return rc;
+    rc = ensure_train_buffers(h, N, H, W);
+    if (rc) return rc;
+    h->train_N = 0;
+    rc = order_in(h);
+    if (rc) return rc;
+    // stem, backbone and cpm up to cpm.conv's input: the graph's own plan, nothing retained
+    const TrainPlan& tp = h->tp;
+    rc = enqueue_forward(h, in_device, N, H, W, nullptr, tp.cpm_conv);
+    if (rc) return rc;
+    int fh, fw;
+    level_dims(H, W, 3, &fh, &fw);
+    const int64_t M3 = (int64_t)N * fh * fw;
+    const int C = h->g.C, catc = h->g.cat_channels, nb = (int)h->g.bufs.size();
+    for (size_t i = (size_t)tp.cpm_conv; i < tp.layers.size(); ++i) {
+        h->cur_layer = (int)i;
+        if (heads_pair_fusable(h, i, M3)) {
+            // the pair's kernel keeps the hidden tensor on the CU: heads.0 runs once more on its own for the retained copy, the
+            // stage outputs come from the same kernel Engine.forward uses
+            rc = enqueue_layer(h, tp.layers[i], in_device, N, H, W, nullptr);
+            if (!rc) rc = enqueue_heads_pair(h, tp.layers[i], tp.layers[i + 1], N, H, W, outs_device);
+            ++i;
+        } else {
+            rc = enqueue_layer(h, tp.layers[i], in_device, N, H, W, outs_device);
+        }
+        if (rc) { h->cur_layer = -1; return rc; }
+        if ((int)i == tp.cpm_conv)             // every refinement stage reads [features | heat | paf] of a buffer of its own
+            for (int k = 1; k < h->g.nref; ++k)
+                LAUNCH(h, KC_OTHER, launch_grad_add(h->tbufs[tp.cats[k] - nb], catc, h->tbufs[tp.cats[0] - nb], catc, M3, C, 0, h->stream));
+    }
+    h->cur_layer = -1;
+    h->train_N = N; h->train_H = H; h->train_W = W;
+    bool ordered = false;
+    return order_out(h, h->stream, &ordered);
+}
+
+static float* grad_at(lwp_context* h, const BufRef& r) { return h->gbufs[r.buf - (int)h->g.bufs.size()] + r.coff; }
+
+struct BackwardArgs {
+    const float* keypoint_maps; const float* paf_maps; const float* mask;
+    int N, hs, ws, batch_size, accumulate;
+    double loss_scale;
+    float* grads; float* d_features;
+};
+
+static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
+    char msg[200];
+    int rc = train_handle_check(h);
+    if (rc) return rc;
+    if (!a.keypoint_maps || !a.paf_maps || !a.mask || !a.grads) return fail(h, LWP_ERR_ARG, "keypoint_maps / paf_maps / mask / grads_device is null");
+    if (a.batch_size < 1) return fail(h, LWP_ERR_ARG, "batch_size must be at least 1");
+    if (!std::isfinite(a.loss_scale)) return fail(h, LWP_ERR_ARG, "loss_scale must be finite");
+    if (h->skel.K + 1 != h->g.NH || 2 * h->skel.L != h->g.NP) {
+        snprintf(msg, sizeof msg, "the skeleton's targets have %d + 1 heat-map and 2 x %d PAF channels, the network's tensors %d and %d",
+                 h->skel.K, h->skel.L, h->g.NH, h->g.NP);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    int fh = 0, fw = 0;
+    if (h->train_N > 0) level_dims(h->train_H, h->train_W, 3, &fh, &fw);
+    if (h->train_N < 1 || h->train_N != a.N || fh != a.hs || fw != a.ws) {
+        snprintf(msg, sizeof msg, "no retaining forward of %d x %d x %d maps precedes this call (lwp_train_forward; the last one kept %d x %d x %d)",
+                 a.N, a.hs, a.ws, h->train_N, fh, fw);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    // workspace: the largest layer's wgrad partials + the folded gradients of the largest BatchNorm layer
+    const int64_t M = (int64_t)a.N * a.hs * a.ws;
+    size_t part = 0, fold = 0;
+    for (size_t i = (size_t)h->tp.cpm_conv + 1; i < h->tp.layers.size(); ++i) {
+        const Layer& l = h->tp.layers[i];
+        auto one = [&](int cout, int cin) {
+            WgradParams w{};
+            w.cout = cout; w.cin = cin; w.ks = l.ks;
+            wgrad_plan(M, cout, cin, l.ks, &w.splits, &w.chunk);
+            part = std::max(part, wgrad_partial_floats(w));
+        };
+        if (l.blocks.empty()) one(l.cout, l.cin);
+        else for (const WBlock& b : l.blocks) one(b.cout, b.cin);
+        if (!l.bn_key.empty()) fold = std::max(fold, (size_t)l.cout * l.cin * l.ks * l.ks + l.cout);
+    }
+    part = (part + 63) / 64 * 64;
+    h->bwd_fold_off = part;
+    const size_t need = (part + fold) * sizeof(float);
+    if (h->d_bwd_bytes < need) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        rc = ensure_dev(h, &h->d_bwd, &h->d_bwd_bytes, need);
+        if (rc) return rc;
+    }
+    return order_in(h);
+}
+
+// wgrad of one conv (a whole layer, or one source conv of a merged head layer): partials, fixed-order reduction, and the
+// BatchNorm chain rule where the layer has one
+static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const float* x, int x_ld, int cout, int cin,
+                         const std::string& conv_key, const BackwardArgs& a, size_t fold_off) {
+    WgradParams w{};
+    w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd;
+    w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = l.ks; w.dil = l.dil;
+    wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, l.ks, &w.splits, &w.chunk);
+    h->bwd_splits[layer_index] = w.splits;
+    LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream));
+    float* dw = a.grads + h->grad_off.at(conv_key + ".weight");
+    float* db = a.grads + h->grad_off.at(conv_key + ".bias");
+    if (l.bn_key.empty()) {
+        LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, dw, db, a.accumulate, h->stream));
+        return LWP_OK;
+    }
+    float* G = h->d_bwd + fold_off;
+    float* g = G + (size_t)cout * cin * l.ks * l.ks;
+    LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, G, g, 0, h->stream));
+    BnChainParams b{};
+    b.G = G; b.g = g;
+    b.W = h->d_raw + h->raw_off.at(conv_key + ".weight"); b.b = h->d_raw + h->raw_off.at(conv_key + ".bias");
+    b.gamma = h->d_raw + h->raw_off.at(l.bn_key + ".weight");
+    b.mean = h->d_raw + h->raw_off.at(l.bn_key + ".running_mean"); b.var = h->d_raw + h->raw_off.at(l.bn_key + ".running_var");
+    b.dW = dw; b.db = db;
+    b.dgamma = a.grads + h->grad_off.at(l.bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(l.bn_key + ".bias");
+    b.cout = cout; b.K = cin * l.ks * l.ks; b.accumulate = a.accumulate;
+    LAUNCH(h, BK_REDUCE, launch_bn_chain(b, h->stream));
+    return LWP_OK;
+}
+
+static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
+    const TrainPlan& tp = h->tp;
+    const Graph& g = h->g;
+    const int nb = (int)g.bufs.size();
+    const int C = g.C, NH = g.NH, NP = g.NP, catc = g.cat_channels;
+    const int64_t M = (int64_t)a.N * a.hs * a.ws;
+    const int S = 2 * (g.nref + 1);
+    const size_t fold_off = h->bwd_fold_off;
+    // 1. dL/d out of every stage, one launch per 16 tensors: from the [heat | paf] window of the stage's concat buffer (the very
+    //    values of the NCHW stage tensors) into the same window of its gradient buffer
+    for (int s0 = 0; s0 < S; s0 += kLossMaxOuts) {
+        LossGradParams p{};
+        p.S = std::min(kLossMaxOuts, S - s0);
+        for (int s = 0; s < p.S; ++s) {
+            const int st = (s0 + s) / 2;
+            const int coff = C + (((s0 + s) & 1) ? NH : 0);
+            p.outs[s] = h->tbufs[tp.cats[st] - nb] + coff;
+            p.dst[s] = h->gbufs[tp.cats[st] - nb] + coff;
+        }
+        p.ld = catc;
+        p.keypoint_maps = a.keypoint_maps; p.paf_maps = a.paf_maps; p.mask = a.mask;
+        p.N = a.N; p.CH = NH; p.CP = NP; p.hw = a.hs * a.ws;
+        p.scale = (float)(a.loss_scale / (double)a.batch_size);
+        LAUNCH(h, BK_ELEMENTWISE, launch_loss_grad(p, h->stream));
+    }
+    // 2. the layers in reverse.  A gradient buffer's first writer overwrites, later ones add: the launch order is the summation order.
+    std::vector<char> written(tp.bufs.size(), 0);
+    for (int i = (int)tp.layers.size() - 1; i > tp.cpm_conv; --i) {
+        const Layer& l = tp.layers[i];
+        h->cur_layer = i;
+        float* dy = grad_at(h, l.dst);
+        const float* y = buf_at(h, l.dst);
+        if (l.res.buf >= 0) {                  // out = relu(z) + res: the residual branch takes the gradient as it is
+            LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(grad_at(h, l.res), l.res.ld, dy, l.dst.ld, M, l.cout, written[l.res.buf - nb], h->stream));
+            written[l.res.buf - nb] = 1;
+        }
+        if (l.act == ACT_RELU)
+            LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(dy, l.dst.ld, y, l.dst.ld, l.res.buf >= 0 ? buf_at(h, l.res) : nullptr, l.res.ld, M, l.cout, h->stream));
+        const float* x = buf_at(h, l.src);
+        int rc = LWP_OK;
+        if (l.blocks.empty()) rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, x, l.src.ld, l.cout, l.cin, l.conv_key, a, fold_off);
+        else
+            for (const WBlock& b : l.blocks) {
+                rc = enqueue_wgrad(h, l, i, dy + b.out_off, l.dst.ld, x + b.in_off, l.src.ld, b.cout, b.cin, b.conv_key, a, fold_off);
+                if (rc) break;
+            }
+        if (rc) { h->cur_layer = -1; return rc; }
+        const bool is_cat = std::find(tp.cats.begin(), tp.cats.end(), l.src.buf) != tp.cats.end();
+        DgradParams d{};
+        d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->d_blob + l.w_off;
+        d.dx = grad_at(h, l.src); d.dx_ld = l.src.ld;
+        d.N = a.N; d.H = a.hs; d.W = a.ws;
+        d.cout = l.cout; d.cout_pad = l.cout_pad; d.cin = l.cin; d.cin_pad = l.cin_pad; d.ks = l.ks; d.dil = l.dil;
+        // a concat buffer's heat / PAF channels already hold the stage's loss gradient; its feature channels are summed over the stages
+        d.acc_from = written[l.src.buf - nb] ? 0 : (is_cat ? C : l.cin);
+        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+        written[l.src.buf - nb] = 1;
+    }
+    h->cur_layer = -1;
+    // 3. backbone_features feeds the initial stage and every refinement stage: stage order, then NCHW
+    if (a.d_features) {
+        float* g0 = h->gbufs[tp.cats[0] - nb];
+        for (int k = 1; k < g.nref; ++k)
+            LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(g0, catc, h->gbufs[tp.cats[k] - nb], catc, M, C, 1, h->stream));
+        LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(g0, catc, a.d_features, a.N, a.hs * a.ws, C, h->stream));
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
+                                  int batch_size, double loss_scale, int accumulate, float* grads_device, float* d_features_device) {
+    const BackwardArgs a{keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, accumulate, loss_scale, grads_device, d_features_device};
+    int rc = stage_backward_prepare(h, a);
+    if (rc) return rc;
+    rc = enqueue_stage_backward(h, a);
+    if (rc) return rc;
+    bool ordered = false;
+    return order_out(h, h->stream, &ordered);
+}
+
+extern "C" int lwp_profile_stage_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs,
+                                          int ws, int batch_size, double loss_scale, float* grads_device, float* d_features_device,
+                                          int reps, float* ms, int* launches) {
+    if (!ms || !launches || reps <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    const BackwardArgs a{keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, 0, loss_scale, grads_device, d_features_device};
+    int rc = stage_backward_prepare(h, a);
+    if (rc) return rc;
+    for (int k = 0; k < BK_COUNT; ++k) { ms[k] = 0.f; launches[k] = 0; }
+    for (int r = 0; r < reps; ++r) {
+        h->profiling = true;
+        h->ev_used = 0;
+        rc = enqueue_stage_backward(h, a);
+        h->profiling = false;
+        if (rc) return rc;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < h->ev_used; i += 2) {
+            float t = 0.f;
+            HIP_TRY(h, hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
+            const int k = h->ev_class[i / 2];
+            ms[k] += t / (float)reps;
+            if (r == 0) launches[k] += 1;
+        }
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_grad_count(int nref, int C, int NH, int NP, int64_t* total_floats) {
+    if (nref < 0 || C <= 0 || NH <= 0 || NP <= 0) return LWP_ERR_ARG;
+    size_t total = 0;
+    const int n = (int)stage_grad_spec(nref, C, NH, NP, &total).size();
+    if (total_floats) *total_floats = (int64_t)total;
+    return n;
+}
+
+extern "C" int lwp_stage_grad_spec(int nref, int C, int NH, int NP, int index, char* name, int name_cap, int64_t shape[4], int* ndim,
+                                   int64_t* offset) {
+    if (nref < 0 || C <= 0 || NH <= 0 || NP <= 0 || !name || !shape || !ndim || !offset) return fail(nullptr, LWP_ERR_ARG, "bad argument");
+    const auto t = stage_grad_spec(nref, C, NH, NP, nullptr);
+    if (index < 0 || index >= (int)t.size()) return fail(nullptr, LWP_ERR_ARG, "index out of range");
+    if ((int)t[index].key.size() + 1 > name_cap) return fail(nullptr, LWP_ERR_ARG, "name buffer too small");
+    std::strcpy(name, t[index].key.c_str());
+    for (int d = 0; d < 4; ++d) shape[d] = t[index].shape[d];
+    *ndim = t[index].ndim;
+    *offset = (int64_t)t[index].off;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_train_activation(lwp_handle h, int idx, float* dst, size_t dst_floats, int out_dims[4]) {
+    int rc = train_handle_check(h);
+    if (rc) return rc;
+    if (!dst || !out_dims) return fail(h, LWP_ERR_ARG, "bad argument");
+    if (idx < h->tp.cpm_conv || idx >= (int)h->tp.layers.size()) return fail(h, LWP_ERR_ARG, "layer_index is not cpm.conv or a stage layer");
+    if (h->train_N < 1) return fail(h, LWP_ERR_ARG, "no retaining forward precedes this call (lwp_train_forward)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const Layer& l = h->tp.layers[idx];
+    int dh, dw;
+    level_dims(h->train_H, h->train_W, 3, &dh, &dw);
+    const size_t n = (size_t)h->train_N * l.cout * dh * dw;
+    if (dst_floats < n) return fail(h, LWP_ERR_ARG, "dst too small");
+    rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, n * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(h, launch_nchw_from_nhwc(buf_at(h, l.dst), l.dst.ld, h->d_tmp, h->train_N, dh * dw, l.cout, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst, h->d_tmp, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    out_dims[0] = h->train_N; out_dims[1] = l.cout; out_dims[2] = dh; out_dims[3] = dw;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_backward_splits(lwp_handle h, int idx) {
+    if (!h || idx < 0 || idx >= (int)h->bwd_splits.size()) return LWP_ERR_ARG;
+    return h->bwd_splits[idx];
 }
 
 // ---------------------------------------------------------------------------------------------- introspection

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -72,6 +73,18 @@ struct Graph {
     int dtype = LWP_F32;       // storage / MFMA dtype of the conv stack (weights packed accordingly): LWP_F32, LWP_BF16, LWP_F16
 };
 Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bool merge_heads = true);
+
+// The retaining buffer plan of the stages (lwp_train_forward): the SAME layer list, but from cpm.conv's output onward every
+// layer writes a buffer of its own, and every stage has its own [feat | heat | paf | pad] concat buffer (cats[s]: stage s's
+// heads write its heat / PAF window, refinement stage s + 1 reads it).  Buffer indices below Graph::bufs.size() are the
+// graph's own buffers; index Graph::bufs.size() + i is train buffer i (all at level 3).
+struct TrainPlan {
+    std::vector<Layer> layers;     // Graph::layers with src / dst / res re-pointed
+    std::vector<BufSpec> bufs;     // the train buffers
+    std::vector<int> cats;         // nref + 1 concat buffers (plan indices)
+    int cpm_conv = -1;             // index of cpm.conv: layers before it run on the graph's own plan and retain nothing
+};
+TrainPlan build_train_plan(const Graph& g);
 // f32 -> IEEE binary16 / bfloat16 bits, round to nearest even (fp16: subnormals exact, overflow -> inf, NaN stays NaN)
 uint16_t f32_to_f16_rne(float f);
 uint16_t f32_to_bf16_rne(float f);
@@ -375,6 +388,51 @@ struct StageLossParams {
 };
 int stage_loss_blocks(int N, int hw);
 hipError_t launch_stage_losses(const StageLossParams& p, double* losses, hipStream_t s);   // losses: S doubles, device
+
+// ---- stage backward (bwd_kernels.hip; train.py:99-103 differentiated): f32, NHWC activations and gradients
+struct LossGradParams {
+    const float* outs[kLossMaxOuts];   // NHWC windows of the stage tensors, even: heat-maps, odd: PAFs, row stride ld
+    float* dst[kLossMaxOuts];          // NHWC gradient windows, row stride ld
+    int S, ld;
+    const float* keypoint_maps; const float* paf_maps; const float* mask;
+    int N, CH, CP, hw;
+    float scale;                       // loss_scale / batch_size
+};
+hipError_t launch_loss_grad(const LossGradParams& p, hipStream_t s);
+// g = (y > res ? g : 0) over an M x C window (res null: y > 0): the ReLU of a layer whose retained output is y (= relu(z) + res)
+hipError_t launch_relu_mask(float* g, int g_ld, const float* y, int y_ld, const float* res, int res_ld, int64_t M, int C, hipStream_t s);
+// dst = (beta ? dst : 0) + src over an M x C window
+hipError_t launch_grad_add(float* dst, int dst_ld, const float* src, int src_ld, int64_t M, int C, int beta, hipStream_t s);
+struct DgradParams {
+    const float* dz; int dz_ld;      // M x cout gradient of the layer's pre-activation output
+    const float* w;                  // the forward blob's [taps][cout_pad][cin_pad]
+    float* dx; int dx_ld;            // M x cin; channels >= acc_from are added to, the others overwritten
+    int N, H, W, cout, cout_pad, cin, cin_pad, ks, dil, acc_from;
+};
+hipError_t launch_dgrad(const DgradParams& p, hipStream_t s);
+struct WgradParams {
+    const float* dz; int dz_ld;      // M x cout
+    const float* x; int x_ld;        // M x cin, the layer's retained input
+    float* partial;                  // [splits][taps][co_pad][ci_pad] weight partials, then [splits][co_pad] bias partials
+    int N, H, W, cout, cin, ks, dil;
+    int splits, chunk;               // pixel ranges [z * chunk, (z + 1) * chunk), chunk a multiple of 16
+};
+__host__ __device__ inline int wgrad_pad64(int v) { return (v + 63) / 64 * 64; }
+void wgrad_plan(int64_t M, int cout, int cin, int ks, int* splits, int* chunk);
+inline size_t wgrad_partial_floats(const WgradParams& p) {
+    return (size_t)p.splits * wgrad_pad64(p.cout) * ((size_t)p.ks * p.ks * wgrad_pad64(p.cin) + 1);
+}
+hipError_t launch_wgrad(const WgradParams& p, hipStream_t s);
+// fixed-order sum of the partials into OIHW dw [cout][cin][taps] and db [cout]; accumulate: added to what is there
+hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int accumulate, hipStream_t s);
+struct BnChainParams {               // BatchNorm at running statistics behind a conv: folded gradients -> raw ones (float64 inside)
+    const float* G; const float* g;  // gradient of the folded weight [cout][K] and of the folded bias [cout]
+    const float* W; const float* b;  // raw conv weight [cout][K] and bias
+    const float* gamma; const float* mean; const float* var;
+    float *dW, *db, *dgamma, *dbeta;
+    int cout, K, accumulate;
+};
+hipError_t launch_bn_chain(const BnChainParams& p, hipStream_t s);
 
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);

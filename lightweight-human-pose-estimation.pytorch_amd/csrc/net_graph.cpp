@@ -247,6 +247,40 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
     return g;
 }
 
+TrainPlan build_train_plan(const Graph& g) {
+    TrainPlan t;
+    t.layers = g.layers;
+    const int nb = (int)g.bufs.size();
+    auto new_buf = [&](int ch, bool pad) {
+        BufSpec b{3, ch};
+        b.has_pad = pad;
+        t.bufs.push_back(b);
+        return nb + (int)t.bufs.size() - 1;
+    };
+    for (int s = 0; s <= g.nref; ++s) t.cats.push_back(new_buf(g.cat_channels, true));
+    for (size_t i = 0; i < t.layers.size(); ++i)
+        if (t.layers[i].name == "cpm.conv") t.cpm_conv = (int)i;
+    std::vector<int> cur(nb, -1);          // graph buffer -> the train buffer that holds its latest tensor
+    int read_cat = 0;                      // the concat buffer a reader of the graph's concat buffer means
+    for (size_t i = (size_t)t.cpm_conv; i < t.layers.size(); ++i) {
+        Layer& l = t.layers[i];
+        if ((int)i > t.cpm_conv) {
+            l.src.buf = l.src.buf == g.cat_buf ? t.cats[read_cat] : cur[l.src.buf];
+            if (l.res.buf >= 0) l.res.buf = cur[l.res.buf];
+        }
+        if (l.dst.buf == g.cat_buf) {
+            const int stage = l.out_index >= 0 ? l.out_index / 2 : 0;     // cpm.conv writes the features of stage 0's buffer
+            l.dst.buf = t.cats[stage];
+            read_cat = stage;
+        } else {
+            const int old = l.dst.buf;
+            l.dst.buf = new_buf(l.dst.ld, false);
+            cur[old] = l.dst.buf;
+        }
+    }
+    return t;
+}
+
 uint16_t f32_to_bf16_rne(float f) {
     uint32_t u;
     std::memcpy(&u, &f, 4);

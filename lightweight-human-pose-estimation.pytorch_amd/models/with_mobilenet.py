@@ -53,7 +53,7 @@ class PoseEstimationWithMobileNet(object):
 
     def train(self, mode=True):
         if mode:
-            raise NotImplementedError("lwpose_amd is an inference path; training is out of scope")
+            raise NotImplementedError("lwpose_amd has no training mode: val.stage_gradients gives the stage gradients of the eval() network (frozen backbone, BatchNorm at running statistics); there is no optimiser")
         return self
 
     def cuda(self, device=None):

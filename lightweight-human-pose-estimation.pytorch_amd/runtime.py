@@ -748,6 +748,111 @@ class Engine(object):
         check(lib().lwp_stage_losses(*args, losses), self.h.ptr)
         return [float(losses[i]) for i in range(len(keep))]
 
+    # ------------------------------------------------------------------ stage backward (train.py:99-103, fp32 engines)
+    def train_forward(self, x):
+        """``forward`` for a float32 cuda tensor (N, 3, H, W) that also keeps what ``stage_backward`` needs: every stage
+        layer's output from cpm.conv on.  Returns the same list of stage outputs, bit for bit."""
+        torch = _torch()
+        x = self._as_device_input(x)
+        N, _, H, W = (int(v) for v in x.shape)
+        fh, fw = H, W
+        for _ in range(3):
+            fh, fw = (fh - 1) // 2 + 1, (fw - 1) // 2 + 1
+        outs = [torch.empty((N, self.NP if i % 2 else self.NH, fh, fw), dtype=torch.float32, device=x.device) for i in range(2 * (1 + self.nref))]
+        ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        self._order(x.device)
+        check(lib().lwp_train_forward(self.h.ptr, x.data_ptr(), N, H, W, ptrs), self.h.ptr)
+        return outs
+
+    def grad_spec(self):
+        """([(state-dict key, shape, float offset)], total floats) of the flat gradient array."""
+        if getattr(self, "_gspec", None) is None:
+            self._gspec = _lib.stage_grad_spec(self.nref, self.C, self.NH, self.NP)
+        return self._gspec
+
+    def grad_views(self, flat):
+        """dict key -> view of ``flat`` (the array ``stage_backward`` fills) with that parameter's shape."""
+        return dict((k, flat[off:off + int(np.prod(shape))].view(shape)) for k, shape, off in self.grad_spec()[0])
+
+    def _backward_args(self, keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, want_features):
+        torch = _torch()
+        if not getattr(mask, "is_cuda", False) or mask.dim() != 3:
+            raise ValueError("mask must be an (N, h, w) cuda tensor")
+        N, hs, ws = (int(v) for v in mask.shape)
+
+        def dev32(t, what, shape):
+            if not getattr(t, "is_cuda", False):
+                raise TypeError("%s must be a cuda tensor" % what)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s has shape %s, expected %s" % (what, tuple(t.shape), shape))
+            return t.detach().to(torch.float32).contiguous()
+        km = dev32(keypoint_maps, "keypoint_maps", (N, self.NH, hs, ws))
+        pm = dev32(paf_maps, "paf_maps", (N, self.NP, hs, ws))
+        m = dev32(mask, "mask", (N, hs, ws))
+        dfeat = torch.empty((N, self.C, hs, ws), dtype=torch.float32, device=m.device) if want_features else None
+        self._keep = (km, pm, m)
+        return (self.h.ptr, km.data_ptr(), pm.data_ptr(), m.data_ptr(), N, hs, ws, int(N if batch_size is None else batch_size),
+                float(loss_scale)), flat, dfeat
+
+    def stage_backward(self, keypoint_maps, paf_maps, mask, batch_size=None, loss_scale=1.0, into=None, want_features=True):
+        """Gradients of L = loss_scale * sum of the per-stage masked L2 losses (train.py:99-102) of the last ``train_forward``:
+        returns (grads, d_features).  ``grads`` maps every initial_stage.* / refinement_stages.* state-dict key that has a
+        gradient to a cuda tensor of the parameter's shape, all views of one flat array (``flat_of(grads)``); ``d_features`` is dL / d backbone_features (N, num_channels, h, w).  ``into``: a flat array from an
+        earlier call (``Engine.flat_of(grads)``) to add to, like loss.backward() accumulates over train.py:96's batches.
+        The refinement BatchNorms stay at their running statistics: the reference network in eval() mode."""
+        torch = _torch()
+        total = self.grad_spec()[1]
+        dev = torch.device("cuda", self.device_id)
+        if into is not None and (not into.is_cuda or into.dtype != torch.float32 or into.numel() != total or not into.is_contiguous()):
+            raise ValueError("into must be the contiguous float32 cuda array of %d gradients an earlier call returned" % total)
+        flat = into if into is not None else torch.empty(total, dtype=torch.float32, device=dev)
+        args, flat, dfeat = self._backward_args(keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, want_features)
+        self._order()
+        check(lib().lwp_stage_backward(*args, 1 if into is not None else 0, flat.data_ptr(), None if dfeat is None else dfeat.data_ptr()), self.h.ptr)
+        return self.grad_views(flat), dfeat
+
+    def flat_of(self, grads):
+        """The flat array behind a dict ``stage_backward`` returned (to pass as ``into=``)."""
+        flat = getattr(next(iter(grads.values())), "_base", None)
+        if flat is None or flat.dim() != 1 or flat.numel() != self.grad_spec()[1]:
+            raise ValueError("not a gradient dict of this engine's stage_backward")
+        return flat
+
+    def profile_stage_backward(self, keypoint_maps, paf_maps, mask, batch_size=None, loss_scale=1.0, reps=3):
+        """Device milliseconds and launch counts of one backward by kernel class (HIP events around every launch)."""
+        torch = _torch()
+        flat = torch.empty(self.grad_spec()[1], dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        args, flat, dfeat = self._backward_args(keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, True)
+        ms, n = (C.c_float * 4)(), (C.c_int * 4)()
+        self._order()
+        check(lib().lwp_profile_stage_backward(*args, flat.data_ptr(), dfeat.data_ptr(), int(reps), ms, n), self.h.ptr)
+        names = ("elementwise", "dgrad", "wgrad", "reduce")
+        return dict((names[i], dict(ms=float(ms[i]), launches=int(n[i]))) for i in range(4))
+
+    def train_activation(self, layer_index):
+        """Retained output of a stage layer (or cpm.conv) from the last ``train_forward`` as NCHW float32 numpy (tests)."""
+        info = self.layers()[layer_index]
+        cap = 1 << 16
+        dims = (C.c_int * 4)()
+        while True:
+            buf = np.empty(cap, np.float32)
+            rc = lib().lwp_debug_train_activation(self.h.ptr, layer_index, buf.ctypes.data, buf.size, dims)
+            if rc == _lib.LWP_ERR_ARG and lib().lwp_last_error(self.h.ptr) == b"dst too small" and cap < (1 << 31):
+                cap *= 8
+                continue
+            check(rc, self.h.ptr)
+            break
+        n = dims[0] * dims[1] * dims[2] * dims[3]
+        assert dims[1] == info["cout"]
+        return buf[:n].reshape(dims[0], dims[1], dims[2], dims[3]).copy()
+
+    def backward_splits(self, layer_index):
+        """Pixel ranges the last ``stage_backward`` split this layer's weight gradient into (0: none ran)."""
+        n = lib().lwp_debug_backward_splits(self.h.ptr, layer_index)
+        if n < 0:
+            raise ValueError("bad layer index")
+        return n
+
     # ------------------------------------------------------------------ measurement
     def time_pipeline(self, x_cuda, iters, what=1, upsample_ratio=4, demo=True):
         """milliseconds for ``iters`` back-to-back passes (HIP events on the engine's stream)."""

@@ -116,6 +116,29 @@ def stage_losses(net, images, labels, masks=None, stride=8, sigma=7, paf_thickne
     return eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], t["keypoint_mask"][:, 0], batch_size)
 
 
+def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thickness=1, batch_size=None, loss_scale=1.0, into=None):
+    """``stage_losses`` plus the gradient of their sum (train.py:99-102, fp32 engines): retaining forward, targets, loss and
+    stage backward on the GPU in one call.  Returns (losses, grads, d_features): the 2 * (nref + 1) floats of ``stage_losses``,
+    the dict state-dict key -> gradient of every initial_stage.* / refinement_stages.* parameter, and the gradient at the
+    cpm output (N, num_channels, h, w).  ``loss_scale`` scales the gradients only (train.py:102's 1 / batches_per_iter);
+    ``into``: the flat array of an earlier call to add to.  The backbone and cpm are frozen and the BatchNorms stay at their
+    running statistics: this is loss.backward() of the reference network in eval() mode.  There is no optimiser."""
+    import torch
+    from .datasets.coco import generate_targets
+    x = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)) if isinstance(images, np.ndarray) else images
+    eng = net.engine
+    x = x.to(torch.device("cuda", eng.device_id)).to(torch.float32).contiguous()
+    outs = eng.train_forward(x)
+    t = generate_targets(net, labels, (int(x.shape[2]), int(x.shape[3])), masks, stride, sigma, paf_thickness)
+    if tuple(outs[0].shape[2:]) != tuple(t["keypoint_maps"].shape[2:]):
+        raise ValueError("the network's maps are %s but the targets %s: the frame size must be a multiple of the stride"
+                         % (tuple(outs[0].shape[2:]), tuple(t["keypoint_maps"].shape[2:])))
+    mask = t["keypoint_mask"][:, 0]
+    losses = eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], mask, batch_size)
+    grads, d_features = eng.stage_backward(t["keypoint_maps"], t["paf_maps"], mask, batch_size, loss_scale, into)
+    return losses, grads, d_features
+
+
 # ---------------------------------------------------------------------------------------------- COCO results
 # slot of each of the 18 network key-points in COCO's 17-key-point order (the neck, index 1, has none)
 _COCO_SLOT = (0, None, 6, 8, 10, 5, 7, 9, 12, 14, 16, 11, 13, 15, 2, 1, 4, 3)

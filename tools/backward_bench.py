@@ -1,0 +1,86 @@
+"""Times the stage backward at the reference's training shape (train.py: batch 80 of 368 x 368), for 1 and 3 refinement stages:
+
+  * the retaining forward (Engine.train_forward) against Engine.forward,
+  * the backward's kernels per class (HIP events around every launch, Engine.profile_stage_backward),
+  * torch-ROCm autograd over the same stages (tests/backward_cases.py's restatement in fp32 on the same GPU), as context.
+
+    python tools/backward_bench.py [--batch 80] [--size 368] [--reps 3] [--out profiles/train/backward_bench.json]
+
+Writes one JSON file; there is no parent figure for this path, so nothing is compared."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import lwpose_amd  # noqa: E402,F401
+from lwpose_amd import synth  # noqa: E402
+from lwpose_amd.runtime import Engine  # noqa: E402
+
+import backward_cases as bc  # noqa: E402
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def one(nref, batch, size, reps):
+    eng = Engine(0, nref=nref)
+    sd = synth.make_state_dict(nref, seed=1)
+    eng.load_state_dict(sd)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.rand((batch, 3, size, size), device="cuda", generator=g) - 0.5
+    hs = size // 8
+    km = torch.rand((batch, 19, hs, hs), device="cuda", generator=g)
+    pm = torch.rand((batch, 38, hs, hs), device="cuda", generator=g) - 0.5
+    mask = (torch.rand((batch, hs, hs), device="cuda", generator=g) > 0.1).float()
+    res = dict(nref=nref, batch=batch, size=size, reps=reps)
+    res["forward_ms"] = timed(lambda: eng.forward(x), reps)
+    res["train_forward_ms"] = timed(lambda: eng.train_forward(x), reps)
+    res["stage_backward_ms"] = timed(lambda: eng.stage_backward(km, pm, mask), reps)
+    res["backward_classes"] = eng.profile_stage_backward(km, pm, mask, reps=reps)
+    first = [i["index"] for i in eng.layers() if i["name"] == "cpm.conv"][0]
+    feat = torch.from_numpy(eng.train_activation(first)).cuda()
+    p = {k: v.cuda().requires_grad_(v.is_floating_point() and "running_" not in k) for k, v in sd.items()
+         if k.startswith("initial_stage.") or k.startswith("refinement_stages.")}
+    keys = bc.grad_keys(p)
+
+    def torch_step():
+        f = feat.detach().requires_grad_(True)
+        total = bc.loss(bc.stages(p, f, nref), km, pm, mask, batch)
+        torch.autograd.grad(total, [p[k] for k in keys] + [f])
+    res["torch_autograd_stages_fwd_bwd_ms"] = timed(torch_step, reps)
+    res["torch_stages_fwd_ms"] = timed(lambda: bc.stages({k: v.detach() for k, v in p.items()}, feat, nref), reps)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=80)
+    ap.add_argument("--size", type=int, default=368)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train", "backward_bench.json"))
+    a = ap.parse_args()
+    out = dict(device=torch.cuda.get_device_properties(0).gcnArchName, runs=[one(n, a.batch, a.size, a.reps) for n in (1, 3)])
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
