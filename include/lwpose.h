@@ -398,7 +398,7 @@ int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, co
  *      backbone_features, the output of cpm.conv (with_mobilenet.py:117).  fp32 handles only; the backbone and the cpm are frozen,
  *      and the refinement trunks' BatchNorms (modules/conv.py:8) stay at their running statistics: the result is what
  *      loss.backward() gives on the reference network in eval() mode, NOT in train() mode (no batch statistics, running_mean /
- *      running_var / num_batches_tracked get no gradient and are not updated).  There is no optimiser.
+ *      running_var / num_batches_tracked get no gradient and are not updated).  The optimiser step is lwp_stage_adam_step below.
  *      lwp_train_forward: with_mobilenet.py:114-123 on in_device (N x 3 x H x W float32, DEVICE) into outs_device[2 * (nref + 1)]
  *      (DEVICE, NCHW float32) with the kernels, weights and reduction order of lwp_forward — the outputs are bit-identical —
  *      while from cpm.conv's output onward every layer's output is kept in a buffer of its own (each refinement stage has its
@@ -433,6 +433,45 @@ int lwp_profile_stage_backward(lwp_handle h, const float* keypoint_maps, const f
  * and the number of pixel ranges the weight gradient of that layer was split into by the last lwp_stage_backward */
 int lwp_debug_train_activation(lwp_handle h, int layer_index, float* dst, size_t dst_floats, int out_dims[4]);
 int lwp_debug_backward_splits(lwp_handle h, int layer_index);
+
+/* ---- stage fine-tuning step: the reference's optimiser (train.py:41-55 and :106, torch.optim.Adam with its parameter groups)
+ *      for the parameters lwp_stage_backward differentiates, and the refold / repack of the changed layers into the forward's
+ *      weight blob, all on the handle's stream: train_forward -> stage_backward -> step lowers the loss with no host round
+ *      trip and no second copy of the weights.  fp32 handles whose weights came through lwp_load_weights only.
+ *      Out of scope: backward or updates for the backbone and cpm, BatchNorm train mode (the running statistics never move), a
+ *      16-bit optimiser, multi-GPU gradient reduction, amsgrad, loading torch's optimiser checkpoints.
+ *      lwp_stage_adam_group: the parameter group of gradient-spec entry `index` (no handle, no GPU): learning-rate multiplier
+ *      and weight-decay flag: initial_stage conv weight x1 / on, conv bias x2 / off; refinement_stages conv weight x4 / on,
+ *      conv bias x8 / off, BatchNorm weight x1 / off, BatchNorm bias x2 / off.
+ *      lwp_stage_adam_step: one step from grads_device (DEVICE, lwp_stage_grad_spec's layout).  The state (exp_avg, exp_avg_sq,
+ *      zero) is allocated on first use; the step count t goes up by one.  Per element, in float64 with ONE rounding to float32
+ *      at each of the three stores, in the order of torch's single-tensor Adam:
+ *        g' = g + weight_decay p (groups with decay);  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g';
+ *        denom = sqrt(v) / sqrt(1 - beta2^t) + eps;  p -= (lr_mult base_lr / (1 - beta1^t)) m / denom
+ *      (the bias corrections and learning rates are host doubles).  Then every stage layer is folded and packed on the device
+ *      exactly as lwp_load_weights packs it on the host: the blob afterwards has the very bits lwp_load_weights gives for the
+ *      new raw values, and the handle is as if that had been called; a later lwp_forward needs no synchronise in between to
+ *      see the new weights, and lwp_weights_blob_export / lwp_weights_blob_import / lwp_load_weights wait for the handle's
+ *      stream before they copy, so they are ordered behind a queued step as well.  No floating-point atomics: the same inputs give the same bits.  The retained lwp_train_forward is
+ *      invalidated (lwp_stage_backward then reports that no retaining forward precedes it).
+ *      LWP_ERR_ARG with a message: a bf16 / fp16 handle; no raw parameters (weights not loaded, or imported as a blob); base_lr
+ *      not finite or not positive; a beta outside [0, 1); eps or weight_decay negative or not finite.  LWP_ERR_STATE while a
+ *      pipeline slot or an lwp_infer_poses_async is pending.
+ *      lwp_stage_params_get: the current raw stage parameters into flat_device (DEVICE) in the gradient-spec layout.
+ *      lwp_stage_adam_state_get / _set: exp_avg, exp_avg_sq (DEVICE, gradient-spec layout) and the step count, for checkpoints
+ *      (before the first step: zeros and 0).  lwp_stage_adam_reset discards the state (zeros, step 0).
+ *      lwp_time_stage_adam_step: `iters` back-to-back launches of each kernel alone between HIP events, ms[0] the Adam kernel,
+ *      ms[1] the repack (totals, milliseconds), on scratch copies: the handle's weights and state do not move. */
+int lwp_stage_adam_group(int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int index, int* lr_mult,
+                         int* weight_decay_on);
+int lwp_stage_adam_step(lwp_handle h, const float* grads_device, double base_lr, double beta1, double beta2, double eps,
+                        double weight_decay);
+int lwp_stage_params_get(lwp_handle h, float* flat_device);
+int lwp_stage_adam_state_get(lwp_handle h, float* exp_avg_device, float* exp_avg_sq_device, int64_t* step);
+int lwp_stage_adam_state_set(lwp_handle h, const float* exp_avg_device, const float* exp_avg_sq_device, int64_t step);
+int lwp_stage_adam_reset(lwp_handle h);
+int lwp_time_stage_adam_step(lwp_handle h, const float* grads_device, double base_lr, double beta1, double beta2, double eps,
+                             double weight_decay, int iters, float* ms);
 
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */

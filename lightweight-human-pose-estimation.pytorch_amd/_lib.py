@@ -26,6 +26,8 @@ EXPORTS = [
     "lwp_train_targets", "lwp_mask_downsample", "lwp_stage_losses", "lwp_time_train_targets", "lwp_time_stage_losses",
     "lwp_train_forward", "lwp_stage_backward", "lwp_stage_grad_count", "lwp_stage_grad_spec", "lwp_profile_stage_backward",
     "lwp_debug_train_activation", "lwp_debug_backward_splits",
+    "lwp_stage_adam_group", "lwp_stage_adam_step", "lwp_stage_params_get", "lwp_stage_adam_state_get", "lwp_stage_adam_state_set",
+    "lwp_stage_adam_reset", "lwp_time_stage_adam_step",
 ]
 
 
@@ -115,6 +117,13 @@ def lib():
     L.lwp_profile_stage_backward.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, fp, ip]
     L.lwp_debug_train_activation.argtypes = [vp, C.c_int, vp, C.c_size_t, ip]
     L.lwp_debug_backward_splits.argtypes = [vp, C.c_int]
+    L.lwp_stage_adam_group.argtypes = [C.c_int] * 5 + [ip, ip]
+    L.lwp_stage_adam_step.argtypes = [vp, vp] + [C.c_double] * 5
+    L.lwp_stage_params_get.argtypes = [vp, vp]
+    L.lwp_stage_adam_state_get.argtypes = [vp, vp, vp, i64p]
+    L.lwp_stage_adam_state_set.argtypes = [vp, vp, vp, C.c_int64]
+    L.lwp_stage_adam_reset.argtypes = [vp]
+    L.lwp_time_stage_adam_step.argtypes = [vp, vp] + [C.c_double] * 5 + [C.c_int, fp]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int
@@ -167,6 +176,18 @@ def stage_grad_spec(nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
         check(L.lwp_stage_grad_spec(nref, num_channels, num_heatmaps, num_pafs, i, name, 256, shape, C.byref(nd), C.byref(off)))
         out.append((name.value.decode(), tuple(shape[d] for d in range(nd.value)), off.value))
     return out, total.value
+
+
+def stage_adam_groups(nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
+    """[(key, learning-rate multiplier, weight decay on)] of every gradient-spec entry under train.py:41-55 (no GPU needed)."""
+    L = lib()
+    spec, _ = stage_grad_spec(nref, num_channels, num_heatmaps, num_pafs)
+    mult, wd = C.c_int(), C.c_int()
+    out = []
+    for i, (key, _, _) in enumerate(spec):
+        check(L.lwp_stage_adam_group(nref, num_channels, num_heatmaps, num_pafs, i, C.byref(mult), C.byref(wd)))
+        out.append((key, mult.value, bool(wd.value)))
+    return out
 
 
 class Handle(object):

@@ -11,7 +11,7 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "liblwpose_hip.so")
-SOURCES = ["net_graph.cpp", "net_kernels.hip", "net_kernels_bf16.hip", "net_kernels_tiled.hip", "post_kernels.hip", "train_kernels.hip", "bwd_kernels.hip", "capi.cpp"]
+SOURCES = ["net_graph.cpp", "net_kernels.hip", "net_kernels_bf16.hip", "net_kernels_tiled.hip", "post_kernels.hip", "train_kernels.hip", "bwd_kernels.hip", "optim_kernels.hip", "capi.cpp"]
 HEADERS = ["lwp_internal.h", "h16.h", os.path.join("..", "..", "include", "lwpose.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-result", "-DNDEBUG"]
 # the post-processing must reproduce NumPy's separately-rounded float32/float64 arithmetic bit for bit:
@@ -20,6 +20,8 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-u
 EXTRA = {"post_kernels.hip": ["-ffp-contract=off"] + (["-DLWP_ASM_STAMPS"] if os.environ.get("LWP_ASM_STAMPS") else []),
          # the training targets reproduce CPython's separately-rounded double arithmetic: same rule
          "train_kernels.hip": ["-ffp-contract=off"],
+         # the optimiser step and the device repack restate torch's and pack_weights' double arithmetic: same rule
+         "optim_kernels.hip": ["-ffp-contract=off"],
          # LWP_ABLATION=1 at build time adds the ablation instantiations of the hot kernels (tools/ only; never shipped by default)
          "net_kernels_bf16.hip": (["-DLWP_ABLATION"] if os.environ.get("LWP_ABLATION") else []),
          "net_kernels.hip": (["-DLWP_ABLATION"] if os.environ.get("LWP_ABLATION") else []) +

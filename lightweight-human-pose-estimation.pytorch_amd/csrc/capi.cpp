@@ -102,6 +102,13 @@ struct lwp_context {
     bool raw_loaded = false;                         // false after lwp_weights_blob_import: a blob holds folded weights only
     float* d_bwd = nullptr; size_t d_bwd_bytes = 0; size_t bwd_fold_off = 0;  // wgrad partials, then the folded gradients of one BatchNorm layer
     std::vector<int> bwd_splits;                     // per layer: pixel splits its last wgrad ran with
+    // stage fine-tuning step (lwp_stage_adam_step): exp_avg then exp_avg_sq in one allocation, the step count, and the two
+    // device tables the host builds once per handle (parameter chunks of the Adam kernel, layer descriptors of the repack)
+    float* d_adam = nullptr; size_t adam_sq_off = 0;
+    int64_t adam_t = 0;
+    AdamChunk* d_adam_chunks = nullptr; int adam_chunks = 0;
+    RepackLayer* d_repack = nullptr; int repack_layers = 0, repack_blocks = 0;
+    bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
     bool run_has_tail = false;             // the tail kernels ran behind the grouping whose results h->ws holds
@@ -331,6 +338,9 @@ extern "C" int lwp_destroy(lwp_handle h) {
     for (float* p : h->gbufs) if (p) (void)hipFree(p);
     if (h->d_raw) (void)hipFree(h->d_raw);
     if (h->d_bwd) (void)hipFree(h->d_bwd);
+    if (h->d_adam) (void)hipFree(h->d_adam);
+    if (h->d_adam_chunks) (void)hipFree(h->d_adam_chunks);
+    if (h->d_repack) (void)hipFree(h->d_repack);
     for (float* p : h->d_outs) if (p) (void)hipFree(p);
     if (h->d_in) (void)hipFree(h->d_in);
     if (h->d_tmp) (void)hipFree(h->d_tmp);
@@ -389,7 +399,7 @@ extern "C" int lwp_set_capacity(lwp_handle h, int max_peaks, int max_kpts, int m
     for (auto& sl : h->slots) free_ws_obj(sl.ws);
     if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
     free_tail_state(h);                                // the lanes' state is sized by max_entries: every lane starts over
-    h->last_N = 0;                                     // the results of an unfetched lwp_infer_poses_async went with the workspace
+    h->last_N = 0; h->async_pending = false;   // the results of an unfetched lwp_infer_poses_async went with the workspace
     h->caps.max_peaks = max_peaks; h->caps.max_kpts = max_kpts; h->caps.max_conn = max_conn; h->caps.max_entries = max_entries;
     return LWP_OK;
 }
@@ -443,7 +453,7 @@ extern "C" int lwp_set_skeleton(lwp_handle h, int num_kpt_types, int num_limbs, 
     for (auto& sl : h->slots) free_ws_obj(sl.ws);
     free_tail_state(h);                                // the lanes' state is sized by K: every lane starts over
     if (h->tail.mode >= 2 && sk.K != h->skel.K) h->tail.mode = 0;   // the sigma table was given for the old K: tracking is off until lwp_set_tracking
-    h->last_N = 0;                                     // the results of an unfetched lwp_infer_poses_async went with the workspace
+    h->last_N = 0; h->async_pending = false;   // the results of an unfetched lwp_infer_poses_async went with the workspace
     h->skel = sk;
     return LWP_OK;
 }
@@ -479,6 +489,7 @@ extern "C" int lwp_load_weights(lwp_handle h, const char* const* names, const vo
     std::string msg = pack_weights(h->g, nm, ts, blob);
     if (!msg.empty()) return fail(h, LWP_ERR_ARG, msg);
     HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));         // a queued lwp_stage_adam_step still writes the blob and the raw parameters
     HIP_TRY(h, hipMemcpy(h->d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
     h->weights_loaded = true;
     if (h->dtype == LWP_F32) {                           // the stage parameters as given: lwp_stage_backward's BatchNorm chain rule
@@ -518,6 +529,7 @@ extern "C" int lwp_weights_blob_export(lwp_handle h, void* dst, size_t bytes) {
     if (!h->weights_loaded) return fail(h, LWP_ERR_STATE, "weights not loaded");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t packed = h->g.blob_floats * sizeof(float);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));         // the copy below is not stream-ordered: a queued lwp_stage_adam_step finishes first
     HIP_TRY(h, hipMemcpy(dst, h->d_blob, packed, hipMemcpyDeviceToDevice));
     if (h->dtype == LWP_F16) {
         uint64_t tag[2];
@@ -536,6 +548,7 @@ extern "C" int lwp_weights_blob_import(lwp_handle h, const void* src, size_t byt
         HIP_TRY(h, hipMemcpy(got, (const char*)src + packed, sizeof(got), hipMemcpyDeviceToHost));
         if (std::memcmp(want, got, sizeof(want)) != 0) return fail(h, LWP_ERR_ARG, "not an fp16 weight blob of this network");
     }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));         // a queued repack must not overwrite the imported stage layers
     HIP_TRY(h, hipMemcpy(h->d_blob, src, packed, hipMemcpyDeviceToDevice));
     h->weights_loaded = true;
     h->raw_loaded = false;
@@ -1429,7 +1442,7 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
         d_paf = h->d_tmp2;
     }
     h->run_has_tail = false;                           // entries only: lwp_get_poses has nothing to return after this call
-    h->last_N = 1;                                     // the workspace holds this one frame now (lwp_debug_post_counts reads it)
+    h->last_N = 1; h->async_pending = false;   // the workspace holds this one frame now (lwp_debug_post_counts reads it)
     LAUNCH(h, KC_POST, launch_reset_ws(1, h->ws, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_xy, xy.data(), xy.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->ws.kpt_score, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -1580,14 +1593,17 @@ extern "C" int lwp_infer_poses_async(lwp_handle h, const float* in_device, int N
     if (rc) return rc;
     rc = order_in(h);
     if (rc) return rc;
-    h->last_N = N;
-    return enqueue_poses(h, in_device, N, H, W, ratio, demo, true);
+    h->last_N = N; h->async_pending = false;
+    rc = enqueue_poses(h, in_device, N, H, W, ratio, demo, true);
+    h->async_pending = rc == LWP_OK;
+    return rc;
 }
 
 extern "C" int lwp_fetch_poses(lwp_handle h, int* kpt_counts, double* kpts, int kpt_cap, double* entries, int entry_cap, int* n_entries) {
     if (!h || !kpt_counts || !kpts || !entries || !n_entries) return fail(h, LWP_ERR_ARG, "null argument");
     if (h->last_N <= 0 || !h->ws.result_block || h->ws.N < h->last_N) return fail(h, LWP_ERR_STATE, "no pipeline run to fetch");
     HIP_TRY(h, hipSetDevice(h->device));
+    h->async_pending = false;
     return fetch_results(h, h->last_N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
 }
 
@@ -1600,7 +1616,7 @@ extern "C" int lwp_infer_poses(lwp_handle h, const float* in, int in_mem, int N,
     const float* d_in = nullptr;
     rc = stage_input(h, in, in_mem, (size_t)N * 3 * H * W * sizeof(float), &d_in);
     if (rc) return rc;
-    h->last_N = N;
+    h->last_N = N; h->async_pending = false;
     rc = enqueue_poses(h, d_in, N, H, W, ratio, demo, true);
     if (rc) return rc;
     return fetch_results(h, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
@@ -1944,7 +1960,7 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
     rc = enqueue_grouping(h, hv, pv, N, ratio, demo, h->ws, h->stream);
     if (rc == LWP_OK) rc = enqueue_tail(h, h->ws, N, ratio, h->stream);
     if (rc) return rc;
-    h->last_N = N;
+    h->last_N = N; h->async_pending = false;
     return fetch_results(h, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
 }
 
@@ -1995,7 +2011,7 @@ extern "C" int lwp_set_tracking(lwp_handle h, int mode, int match_threshold, dou
         for (auto& sl : h->slots) free_ws_obj(sl.ws);
     }
     free_tail_state(h);                                // every lane starts over
-    h->last_N = 0;
+    h->last_N = 0; h->async_pending = false;
     h->tail_first_id = 0;
     h->tail.mode = mode;
     h->tail.match_threshold = match_threshold;
@@ -2104,7 +2120,7 @@ extern "C" int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoin
     if (rc) return rc;
     h->stage_tail_N = 0;                               // frame 0 of the workspace is reused: the rows of the last run are gone,
     h->run_has_tail = false;                           // and so is an lwp_infer_poses_async run that was not fetched yet
-    h->last_N = 0;
+    h->last_N = 0; h->async_pending = false;
     if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
     const size_t K = (size_t)h->ws.K;
     if (n > 0) {
@@ -2766,6 +2782,285 @@ extern "C" int lwp_debug_backward_splits(lwp_handle h, int idx) {
     return h->bwd_splits[idx];
 }
 
+// ---------------------------------------------------------------------------------------------- stage fine-tuning step
+// train.py:41-55's parameter groups for the stage parameters: log2 of the learning-rate multiplier in bits 0-1, weight decay in bit 2
+static uint32_t stage_adam_group(const std::string& key, int role) {
+    const bool refine = key.rfind("refinement_stages.", 0) == 0;
+    switch (role) {
+    case LWP_ROLE_CONV_W: return (refine ? 2u : 0u) | 4u;
+    case LWP_ROLE_CONV_B: return refine ? 3u : 1u;
+    case LWP_ROLE_BN_W: return 0u;
+    default: return 1u;                            // LWP_ROLE_BN_B
+    }
+}
+static std::vector<uint32_t> stage_adam_groups(int nref, int C, int NH, int NP) {
+    std::vector<uint32_t> v;
+    for (const ParamSpec& p : param_table(nref, C, NH, NP))
+        if (is_stage_key(p.key) && p.role != LWP_ROLE_BN_MEAN && p.role != LWP_ROLE_BN_VAR && p.role != LWP_ROLE_BN_NBT)
+            v.push_back(stage_adam_group(p.key, p.role));
+    return v;
+}
+
+extern "C" int lwp_stage_adam_group(int nref, int C, int NH, int NP, int index, int* lr_mult, int* weight_decay_on) {
+    if (nref < 0 || C <= 0 || NH <= 0 || NP <= 0 || !lr_mult || !weight_decay_on) return fail(nullptr, LWP_ERR_ARG, "bad argument");
+    const auto g = stage_adam_groups(nref, C, NH, NP);
+    if (index < 0 || index >= (int)g.size()) return fail(nullptr, LWP_ERR_ARG, "index out of range");
+    *lr_mult = 1 << (g[index] & 3u);
+    *weight_decay_on = (g[index] & 4u) ? 1 : 0;
+    return LWP_OK;
+}
+
+static int adam_handle_check(lwp_context* h) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (h->dtype != LWP_F32) return fail(h, LWP_ERR_ARG, "the stage optimiser runs on fp32 handles only (this one is bf16 / fp16)");
+    if (!h->weights_loaded) return fail(h, LWP_ERR_ARG, "weights not loaded (call lwp_load_weights first)");
+    if (!h->raw_loaded) return fail(h, LWP_ERR_ARG, "the stage optimiser needs the raw parameters: load them with lwp_load_weights (a weight blob holds folded weights only)");
+    return LWP_OK;
+}
+
+// the two device tables, built once per handle: chunks of at most kAdamChunk elements that never cross a parameter (a parameter
+// that starts off the 16-byte grid gets a head chunk up to the grid), and one descriptor per stage layer
+static int ensure_adam_tables(lwp_context* h) {
+    if (h->d_adam_chunks) return LWP_OK;
+    const std::vector<uint32_t> groups = stage_adam_groups(h->g.nref, h->g.C, h->g.NH, h->g.NP);
+    std::vector<AdamChunk> chunks;
+    for (size_t i = 0; i < h->gspec.size(); ++i) {
+        const auto& s = h->gspec[i];
+        size_t n = 1;
+        for (int d = 0; d < s.ndim; ++d) n *= (size_t)s.shape[d];
+        const size_t roff = h->raw_off.at(s.key);
+        size_t done = 0;
+        while (done < n) {
+            size_t take = std::min<size_t>(kAdamChunk, n - done);
+            const size_t mis = (s.off + done) & 3;
+            if (mis && ((roff + done) & 3) == mis) take = std::min<size_t>(take, 4 - mis);
+            chunks.push_back(AdamChunk{(uint32_t)(s.off + done), (uint32_t)(roff + done), (uint32_t)take, groups[i]});
+            done += take;
+        }
+    }
+    auto raw_at = [&](const std::string& k) { auto it = h->raw_off.find(k); return it == h->raw_off.end() ? -1 : (int)it->second; };
+    std::vector<RepackLayer> tab;
+    uint32_t blocks = 0;
+    for (size_t i = (size_t)h->tp.cpm_conv + 1; i < h->g.layers.size(); ++i) {
+        const Layer& l = h->g.layers[i];
+        if (l.kind != L_GEMM || l.blocks.size() > 2 || (!l.blocks.empty() && l.ks != 1) || l.cin_pad % 32 || l.cout_pad % 32)
+            return fail(h, LWP_ERR_STATE, "stage layer '" + l.name + "' has no device repack");
+        RepackLayer r{};
+        r.block_begin = blocks;
+        r.w_off = (uint32_t)l.w_off; r.w2_off = (uint32_t)l.w2_off; r.b_off = (uint32_t)l.b_off;
+        r.cin = l.cin; r.cout = l.cout; r.cin_pad = l.cin_pad; r.cout_pad = l.cout_pad; r.taps = l.ks * l.ks;
+        r.w_raw = raw_at(l.conv_key + ".weight");
+        r.b_raw = l.has_bias ? raw_at(l.conv_key + ".bias") : -1;
+        r.gamma_raw = r.beta_raw = r.mean_raw = r.var_raw = -1;
+        if (!l.bn_key.empty()) {
+            r.gamma_raw = raw_at(l.bn_key + ".weight"); r.beta_raw = raw_at(l.bn_key + ".bias");
+            r.mean_raw = raw_at(l.bn_key + ".running_mean"); r.var_raw = raw_at(l.bn_key + ".running_var");
+            if (r.gamma_raw < 0 || r.beta_raw < 0 || r.mean_raw < 0 || r.var_raw < 0) return fail(h, LWP_ERR_STATE, "raw BatchNorm parameters of '" + l.name + "' missing");
+        }
+        r.n_blocks = (int)l.blocks.size();
+        for (int b = 0; b < r.n_blocks; ++b) {
+            const WBlock& wb = l.blocks[b];
+            r.blk[b] = RepackBlock{raw_at(wb.conv_key + ".weight"), raw_at(wb.conv_key + ".bias"), wb.out_off, wb.in_off, wb.cout, wb.cin};
+            if (r.blk[b].w_raw < 0 || r.blk[b].b_raw < 0 || wb.out_off + wb.cout > l.cout_pad || wb.in_off + wb.cin > l.cin_pad)
+                return fail(h, LWP_ERR_STATE, "source conv of '" + l.name + "' missing or out of range");
+        }
+        if (r.n_blocks == 0 && r.w_raw < 0) return fail(h, LWP_ERR_STATE, "raw weight of '" + l.name + "' missing");
+        blocks += (uint32_t)(r.taps * (l.cin_pad / 32) * (l.cout_pad / 32));
+        tab.push_back(r);
+    }
+    RepackLayer* d_tab = nullptr;
+    HIP_TRY(h, hipMalloc((void**)&d_tab, std::max<size_t>(tab.size(), 1) * sizeof(RepackLayer)));
+    hipError_t e = hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(RepackLayer), hipMemcpyHostToDevice);
+    AdamChunk* d_chunks = nullptr;
+    if (e == hipSuccess) e = hipMalloc((void**)&d_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(AdamChunk));
+    if (e == hipSuccess) e = hipMemcpy(d_chunks, chunks.data(), chunks.size() * sizeof(AdamChunk), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d_tab);
+        if (d_chunks) (void)hipFree(d_chunks);
+        return fail(h, LWP_ERR_HIP, std::string("stage optimiser tables: ") + hipGetErrorString(e));
+    }
+    h->d_repack = d_tab; h->repack_layers = (int)tab.size(); h->repack_blocks = (int)blocks;
+    h->d_adam_chunks = d_chunks; h->adam_chunks = (int)chunks.size();
+    return LWP_OK;
+}
+
+// exp_avg and exp_avg_sq, zeroed on the handle's stream when first needed
+static int ensure_adam_state(lwp_context* h) {
+    if (h->d_adam) return LWP_OK;
+    h->adam_sq_off = (h->grad_floats + 3) / 4 * 4;
+    const size_t bytes = std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float);
+    HIP_TRY(h, hipMalloc((void**)&h->d_adam, bytes));
+    HIP_TRY(h, hipMemsetAsync(h->d_adam, 0, bytes, h->stream));
+    h->adam_t = 0;
+    return LWP_OK;
+}
+
+struct AdamArgs { const float* grads; double base_lr, beta1, beta2, eps, weight_decay; };
+
+static int adam_args_check(lwp_context* h, const AdamArgs& a) {
+    if (!a.grads) return fail(h, LWP_ERR_ARG, "grads_device is null");
+    if (!std::isfinite(a.base_lr) || !(a.base_lr > 0.0)) return fail(h, LWP_ERR_ARG, "base_lr must be finite and positive");
+    if (!(a.beta1 >= 0.0 && a.beta1 < 1.0) || !(a.beta2 >= 0.0 && a.beta2 < 1.0)) return fail(h, LWP_ERR_ARG, "betas must lie in [0, 1)");
+    if (!std::isfinite(a.eps) || a.eps < 0.0) return fail(h, LWP_ERR_ARG, "eps must be finite and not negative");
+    if (!std::isfinite(a.weight_decay) || a.weight_decay < 0.0) return fail(h, LWP_ERR_ARG, "weight_decay must be finite and not negative");
+    return LWP_OK;
+}
+
+// launch parameters of step `t` on the given arrays; the bias corrections and the learning rates are host doubles
+static AdamParams adam_params(lwp_context* h, const AdamArgs& a, int64_t t, float* raw, float* state) {
+    AdamParams p{};
+    p.grads = a.grads; p.raw = raw; p.exp_avg = state; p.exp_avg_sq = state + h->adam_sq_off;
+    p.chunks = h->d_adam_chunks; p.n_chunks = h->adam_chunks;
+    p.vec_ok = (((uintptr_t)p.grads | (uintptr_t)p.raw | (uintptr_t)p.exp_avg | (uintptr_t)p.exp_avg_sq) & 15) == 0;
+    const double bc1 = 1.0 - std::pow(a.beta1, (double)t), bc2 = 1.0 - std::pow(a.beta2, (double)t);
+    for (int k = 0; k < 4; ++k) p.step_size[k] = a.base_lr * (double)(1 << k) / bc1;
+    p.one_minus_b1 = 1.0 - a.beta1; p.b2 = a.beta2; p.one_minus_b2 = 1.0 - a.beta2;
+    p.sqrt_bc2 = std::sqrt(bc2); p.eps = a.eps; p.weight_decay = a.weight_decay;
+    return p;
+}
+
+extern "C" int lwp_stage_adam_step(lwp_handle h, const float* grads_device, double base_lr, double beta1, double beta2, double eps,
+                                   double weight_decay) {
+    int rc = adam_handle_check(h);
+    if (rc) return rc;
+    const AdamArgs a{grads_device, base_lr, beta1, beta2, eps, weight_decay};
+    rc = adam_args_check(h, a);
+    if (rc) return rc;
+    // the blob is read by the network kernels, which all run on the main stream (a slot's post stream reads maps, never
+    // weights), and by the host-synchronous copies of lwp_load_weights / lwp_weights_blob_export / _import, which wait for the
+    // main stream first: a write on the main stream is ordered against every reader.  Work in flight whose results the caller has not
+    // taken yet would still see consistent weights, but a step between a submit and its fetch is a caller's mistake.
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending: fetch it before the optimiser step");
+    if (h->async_pending) return fail(h, LWP_ERR_STATE, "an lwp_infer_poses_async is pending: fetch it before the optimiser step");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = ensure_adam_tables(h);
+    if (!rc) rc = ensure_adam_state(h);
+    if (!rc) rc = order_in(h);
+    if (rc) return rc;
+    const AdamParams p = adam_params(h, a, h->adam_t + 1, h->d_raw, h->d_adam);
+    LAUNCH(h, KC_OTHER, launch_stage_adam(p, h->stream));
+    h->adam_t += 1;                                    // from here on the raw parameters and the state are those of step t
+    h->train_N = 0;                                    // the retained activations belong to the old weights
+    const hipError_t e = launch_stage_repack(h->d_repack, h->repack_layers, h->repack_blocks, h->d_raw, h->d_blob, h->stream);
+    if (e != hipSuccess) {                             // the blob no longer matches the raw parameters: no forward until lwp_load_weights
+        h->weights_loaded = false;
+        return fail(h, LWP_ERR_HIP, std::string("launch_stage_repack: ") + hipGetErrorString(e) + " (the weight blob is stale: load the weights again)");
+    }
+    bool ordered = false;
+    return order_out(h, h->stream, &ordered);
+}
+
+extern "C" int lwp_stage_params_get(lwp_handle h, float* flat_device) {
+    int rc = adam_handle_check(h);
+    if (rc) return rc;
+    if (!flat_device) return fail(h, LWP_ERR_ARG, "flat_device is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    for (const auto& s : h->gspec) {                   // gradient-spec offset <- raw offset, entry by entry
+        size_t n = 1;
+        for (int d = 0; d < s.ndim; ++d) n *= (size_t)s.shape[d];
+        HIP_TRY(h, hipMemcpyAsync(flat_device + s.off, h->d_raw + h->raw_off.at(s.key), n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_adam_state_get(lwp_handle h, float* exp_avg_device, float* exp_avg_sq_device, int64_t* step) {
+    int rc = adam_handle_check(h);
+    if (rc) return rc;
+    if (!exp_avg_device || !exp_avg_sq_device || !step) return fail(h, LWP_ERR_ARG, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    const size_t bytes = h->grad_floats * sizeof(float);
+    if (h->d_adam) {
+        HIP_TRY(h, hipMemcpyAsync(exp_avg_device, h->d_adam, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(exp_avg_sq_device, h->d_adam + h->adam_sq_off, bytes, hipMemcpyDeviceToDevice, h->stream));
+    } else {
+        HIP_TRY(h, hipMemsetAsync(exp_avg_device, 0, bytes, h->stream));
+        HIP_TRY(h, hipMemsetAsync(exp_avg_sq_device, 0, bytes, h->stream));
+    }
+    *step = h->d_adam ? h->adam_t : 0;
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_adam_state_set(lwp_handle h, const float* exp_avg_device, const float* exp_avg_sq_device, int64_t step) {
+    int rc = adam_handle_check(h);
+    if (rc) return rc;
+    if (!exp_avg_device || !exp_avg_sq_device) return fail(h, LWP_ERR_ARG, "null argument");
+    if (step < 0) return fail(h, LWP_ERR_ARG, "step must not be negative");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = ensure_adam_state(h);
+    if (!rc) rc = order_in(h);
+    if (rc) return rc;
+    const size_t bytes = h->grad_floats * sizeof(float);
+    HIP_TRY(h, hipMemcpyAsync(h->d_adam, exp_avg_device, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_adam + h->adam_sq_off, exp_avg_sq_device, bytes, hipMemcpyDeviceToDevice, h->stream));
+    h->adam_t = step;
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);            // the caller may free or overwrite its arrays once its stream gets here
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_adam_reset(lwp_handle h) {
+    int rc = adam_handle_check(h);
+    if (rc) return rc;
+    h->adam_t = 0;
+    if (!h->d_adam) return LWP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);                                  // the caller may still read an array lwp_stage_adam_state_get handed over
+    if (rc) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->d_adam, 0, std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float), h->stream));
+    return LWP_OK;
+}
+
+// the two kernels alone, `iters` back-to-back launches each between two events (ms[0]: Adam, ms[1]: repack), on scratch copies
+// of the raw parameters, the state and the blob: the handle's weights and optimiser state do not move
+extern "C" int lwp_time_stage_adam_step(lwp_handle h, const float* grads_device, double base_lr, double beta1, double beta2, double eps,
+                                        double weight_decay, int iters, float* ms) {
+    int rc = adam_handle_check(h);
+    if (rc) return rc;
+    if (!ms || iters <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    const AdamArgs a{grads_device, base_lr, beta1, beta2, eps, weight_decay};
+    rc = adam_args_check(h, a);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = ensure_adam_tables(h);
+    if (rc) return rc;
+    if (!h->adam_sq_off) h->adam_sq_off = (h->grad_floats + 3) / 4 * 4;
+    struct Scratch {
+        float *raw = nullptr, *state = nullptr, *blob = nullptr;
+        ~Scratch() { for (float* p : {raw, state, blob}) if (p) (void)hipFree(p); }
+    } sc;
+    const size_t state_bytes = std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float);
+    HIP_TRY(h, hipMalloc((void**)&sc.raw, std::max<size_t>(h->raw_floats, 1) * sizeof(float)));
+    HIP_TRY(h, hipMalloc((void**)&sc.state, state_bytes));
+    HIP_TRY(h, hipMalloc((void**)&sc.blob, h->g.blob_floats * sizeof(float)));
+    rc = order_in(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(sc.raw, h->d_raw, h->raw_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(sc.state, 0, state_bytes, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(sc.blob, h->d_blob, h->g.blob_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    const AdamParams p = adam_params(h, a, 1, sc.raw, sc.state);
+    rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_stage_adam(p, h->stream)); return (int)LWP_OK; }, &ms[0]);
+    if (!rc)
+        rc = time_on_stream(h, iters, [&]() {
+            LAUNCH(h, KC_OTHER, launch_stage_repack(h->d_repack, h->repack_layers, h->repack_blocks, sc.raw, sc.blob, h->stream));
+            return (int)LWP_OK; }, &ms[1]);
+    (void)hipStreamSynchronize(h->stream);             // the scratch arrays are freed on return
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------------------- introspection
 extern "C" int lwp_layer_count(lwp_handle h) { return h ? (int)h->g.layers.size() : LWP_ERR_ARG; }
 
@@ -2899,7 +3194,7 @@ extern "C" int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, in
     if (!h || !in_device || !ms_total || iters <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
     int rc = prepare_poses(h, N, H, W, ratio);
     if (rc) return rc;
-    h->last_N = N;
+    h->last_N = N; h->async_pending = false;
     return time_on_stream(h, iters, [&]() { return enqueue_poses(h, in_device, N, H, W, ratio, demo, what != 0); }, ms_total);
 }
 
@@ -2930,7 +3225,7 @@ extern "C" int lwp_profile_launches(lwp_handle h, const float* in_device, int N,
     if (!h || !in_device || !ms || !kclass || !n_launches || reps <= 0 || cap <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
     int rc = prepare_poses(h, N, H, W, ratio);
     if (rc) return rc;
-    h->last_N = N;
+    h->last_N = N; h->async_pending = false;
     for (int i = 0; i < cap; ++i) { ms[i] = 0.f; kclass[i] = -1; }
     size_t nl = 0;
     for (int r = 0; r < reps; ++r) {
@@ -2960,7 +3255,7 @@ extern "C" int lwp_profile_classes(lwp_handle h, const float* in_device, int N, 
     if (!h || !in_device || !ms || !launches || reps <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
     int rc = prepare_poses(h, N, H, W, ratio);
     if (rc) return rc;
-    h->last_N = N;
+    h->last_N = N; h->async_pending = false;
     for (int k = 0; k < KC_COUNT; ++k) { ms[k] = 0.f; launches[k] = 0; }
     for (int r = 0; r < reps; ++r) {
         h->profiling = true;

@@ -434,6 +434,33 @@ struct BnChainParams {               // BatchNorm at running statistics behind a
 };
 hipError_t launch_bn_chain(const BnChainParams& p, hipStream_t s);
 
+// ---- stage fine-tuning step (optim_kernels.hip; train.py:41-55, :106 and pack_weights for the stage layers)
+constexpr int kAdamChunk = 1024;     // elements of one parameter a workgroup updates
+struct AdamChunk {
+    uint32_t goff, roff, n;          // float offset in the gradient array (and in exp_avg / exp_avg_sq), in d_raw, elements
+    uint32_t group;                  // bits 0-1: log2 of the learning-rate multiplier (x1, x2, x4, x8), bit 2: weight decay on
+};
+struct AdamParams {
+    const float* grads;              // lwp_stage_grad_spec's layout
+    float* raw;                      // the handle's raw parameters
+    float* exp_avg; float* exp_avg_sq;
+    const AdamChunk* chunks; int n_chunks;
+    int vec_ok;                      // every base pointer is 16-byte aligned
+    double step_size[4];             // base_lr * {1, 2, 4, 8} / (1 - beta1^t), computed on the host
+    double one_minus_b1, b2, one_minus_b2, sqrt_bc2, eps, weight_decay;   // sqrt_bc2 = sqrt(1 - beta2^t)
+};
+hipError_t launch_stage_adam(const AdamParams& p, hipStream_t s);
+struct RepackBlock { int w_raw, b_raw, out_off, in_off, cout, cin; };    // one source conv of a merged head layer (WBlock)
+struct RepackLayer {                 // one fp32 L_GEMM layer: where its raw parameters are and where its packed forms go
+    uint32_t block_begin;            // first workgroup of the layer (one workgroup = 256 x 16 bytes of the fragment-order copy)
+    uint32_t w_off, w2_off, b_off;   // float offsets into the blob
+    int cin, cout, cin_pad, cout_pad, taps;
+    int w_raw, b_raw, gamma_raw, beta_raw, mean_raw, var_raw;   // float offsets into d_raw, -1: the layer has none
+    int n_blocks;                    // 0: a plain layer, else blk[0 .. n_blocks) are its source convs
+    RepackBlock blk[2];
+};
+hipError_t launch_stage_repack(const RepackLayer* tab_device, int n_layers, int n_blocks, const float* raw, float* blob, hipStream_t s);
+
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);
 hipError_t launch_upsample(const MapView& src, int N, int C, int ratio, float* dst, hipStream_t s, const Tuning* tune = nullptr);

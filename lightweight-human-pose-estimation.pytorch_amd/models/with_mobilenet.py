@@ -25,12 +25,23 @@ class PoseEstimationWithMobileNet(object):
                                             num_heatmaps=num_heatmaps, num_pafs=num_pafs)
         self._engine = None
         self._dirty = True
+        self._seen_steps = 0           # Engine.stage_steps when self._state last agreed with the engine's stage parameters
         self._device_id = None
         self.training = False
         self._torch = torch
 
     # ---- nn.Module-like surface used by the reference's callers (demo.py:82-84,156-158; val.py:114,174-178)
+    def _sync_from_engine(self):
+        """After an optimiser step (Engine.adam_step, however it was reached) the engine holds the current stage parameters:
+        copied back only when somebody asks."""
+        eng = self._engine
+        if eng is not None and eng.stage_steps != self._seen_steps:
+            for k, v in eng.stage_params().items():
+                self._state[k] = v.detach().cpu().to(self._state[k].dtype).reshape(self._state[k].shape).clone()
+            self._seen_steps = eng.stage_steps
+
     def state_dict(self):
+        self._sync_from_engine()
         return OrderedDict((k, v.clone()) for k, v in self._state.items())
 
     def load_state_dict(self, state_dict, strict=True):
@@ -38,6 +49,7 @@ class PoseEstimationWithMobileNet(object):
         unexpected = [k for k in state_dict if k not in self._state]
         if strict and (missing or unexpected):
             raise RuntimeError("Error(s) in loading state_dict: missing %s unexpected %s" % (missing, unexpected))
+        self._sync_from_engine()
         for k in self._state:
             if k in state_dict:
                 v = state_dict[k]
@@ -53,7 +65,7 @@ class PoseEstimationWithMobileNet(object):
 
     def train(self, mode=True):
         if mode:
-            raise NotImplementedError("lwpose_amd has no training mode: val.stage_gradients gives the stage gradients of the eval() network (frozen backbone, BatchNorm at running statistics); there is no optimiser")
+            raise NotImplementedError("lwpose_amd has no training mode (no BatchNorm batch statistics): val.train_step / optim.StageAdam fine-tune the stages of the eval() network (frozen backbone and cpm, BatchNorm at running statistics)")
         return self
 
     def cuda(self, device=None):
@@ -77,9 +89,11 @@ class PoseEstimationWithMobileNet(object):
 
     def _ensure(self, device_id):
         if self._engine is None or self._device_id != device_id:
+            self._sync_from_engine()
             self._engine = Engine(device_id, self.num_refinement_stages, self.num_channels, self.num_heatmaps,
                                   self.num_pafs, self.dtype)
             self._device_id = device_id
+            self._seen_steps = 0
             self._dirty = True
         if self._dirty:
             self._engine.load_state_dict(self._state)

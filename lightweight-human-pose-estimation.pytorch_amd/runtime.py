@@ -24,6 +24,7 @@ class Engine(object):
         self.nref, self.C, self.NH, self.NP = nref, num_channels, num_heatmaps, num_pafs
         self.device_id = device_id
         self._keep = None
+        self.stage_steps = 0                  # adam_step calls so far: the drop-in net reads its stage parameters back when this moves
 
     # ------------------------------------------------------------------ stream ordering
     def _order(self, device=None, hand_over=True):
@@ -852,6 +853,70 @@ class Engine(object):
         if n < 0:
             raise ValueError("bad layer index")
         return n
+
+    # ------------------------------------------------------------------ stage fine-tuning step (train.py:41-55, :106; fp32 engines)
+    def _flat32(self, flat, what):
+        torch = _torch()
+        total = self.grad_spec()[1]
+        if not getattr(flat, "is_cuda", False) or flat.dtype != torch.float32 or flat.numel() != total or not flat.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 cuda array of %d values in the gradient-spec layout" % (what, total))
+        return flat
+
+    def adam_groups(self):
+        """[(state-dict key, learning-rate multiplier, weight decay on)] per gradient-spec entry (train.py:41-55)."""
+        return _lib.stage_adam_groups(self.nref, self.C, self.NH, self.NP)
+
+    def adam_step(self, flat, base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4):
+        """One step of the reference's Adam (its parameter groups included) on the stage parameters from the flat gradient array
+        ``stage_backward`` filled (``flat_of(grads)``), then the device-side refold and repack of the stage layers: the engine
+        is afterwards as if ``load_state_dict`` had been called with the new values, with no host copy and no synchronise.
+        The retained ``train_forward`` is invalidated."""
+        flat = self._flat32(flat, "flat")
+        self._order()
+        check(lib().lwp_stage_adam_step(self.h.ptr, flat.data_ptr(), float(base_lr), float(betas[0]), float(betas[1]), float(eps),
+                                        float(weight_decay)), self.h.ptr)
+        self.stage_steps += 1
+
+    def stage_params(self):
+        """dict state-dict key -> current raw stage parameter (float32 cuda tensors, views of one flat array in the
+        gradient-spec layout: ``flat_of`` gives it)."""
+        torch = _torch()
+        flat = torch.empty(self.grad_spec()[1], dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        self._order()
+        check(lib().lwp_stage_params_get(self.h.ptr, flat.data_ptr()), self.h.ptr)
+        return self.grad_views(flat)
+
+    def adam_state(self):
+        """dict(step, exp_avg, exp_avg_sq): the step count and the two flat float32 cuda arrays (gradient-spec layout)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_id)
+        m = torch.empty(self.grad_spec()[1], dtype=torch.float32, device=dev)
+        v = torch.empty_like(m)
+        step = C.c_int64()
+        self._order()
+        check(lib().lwp_stage_adam_state_get(self.h.ptr, m.data_ptr(), v.data_ptr(), C.byref(step)), self.h.ptr)
+        return dict(step=int(step.value), exp_avg=m, exp_avg_sq=v)
+
+    def load_adam_state(self, state):
+        """Restores what ``adam_state`` returned (arrays on the host or the device); ``None`` discards the state."""
+        if state is None:
+            check(lib().lwp_stage_adam_reset(self.h.ptr), self.h.ptr)
+            return
+        torch = _torch()
+        dev = torch.device("cuda", self.device_id)
+        m = self._flat32(torch.as_tensor(state["exp_avg"]).to(dev, torch.float32).contiguous(), "exp_avg")
+        v = self._flat32(torch.as_tensor(state["exp_avg_sq"]).to(dev, torch.float32).contiguous(), "exp_avg_sq")
+        self._order()
+        check(lib().lwp_stage_adam_state_set(self.h.ptr, m.data_ptr(), v.data_ptr(), int(state["step"])), self.h.ptr)
+
+    def time_adam_step(self, flat, base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4, iters=20):
+        """(ms of ``iters`` Adam-kernel launches, ms of ``iters`` repack launches) on scratch copies (HIP events)."""
+        flat = self._flat32(flat, "flat")
+        ms = (C.c_float * 2)()
+        self._order()
+        check(lib().lwp_time_stage_adam_step(self.h.ptr, flat.data_ptr(), float(base_lr), float(betas[0]), float(betas[1]), float(eps),
+                                             float(weight_decay), int(iters), ms), self.h.ptr)
+        return float(ms[0]), float(ms[1])
 
     # ------------------------------------------------------------------ measurement
     def time_pipeline(self, x_cuda, iters, what=1, upsample_ratio=4, demo=True):

@@ -122,7 +122,7 @@ def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thic
     the dict state-dict key -> gradient of every initial_stage.* / refinement_stages.* parameter, and the gradient at the
     cpm output (N, num_channels, h, w).  ``loss_scale`` scales the gradients only (train.py:102's 1 / batches_per_iter);
     ``into``: the flat array of an earlier call to add to.  The backbone and cpm are frozen and the BatchNorms stay at their
-    running statistics: this is loss.backward() of the reference network in eval() mode.  There is no optimiser."""
+    running statistics: this is loss.backward() of the reference network in eval() mode.  ``train_step`` adds the optimiser."""
     import torch
     from .datasets.coco import generate_targets
     x = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)) if isinstance(images, np.ndarray) else images
@@ -137,6 +137,27 @@ def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thic
     losses = eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], mask, batch_size)
     grads, d_features = eng.stage_backward(t["keypoint_maps"], t["paf_maps"], mask, batch_size, loss_scale, into)
     return losses, grads, d_features
+
+
+def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=8, sigma=7, paf_thickness=1):
+    """One pass of train.py:85-110's loop body for one loader batch, all on the GPU: targets, retaining forward, stage losses,
+    stage backward with loss_scale = 1 / batches_per_iter, and, once ``batches_per_iter`` calls have added their gradients,
+    ``opt.step`` (an ``optim.StageAdam`` of this net; it is zeroed at the first batch of an iteration, train.py:87-88).
+    Returns the batch's stage losses as ``stage_losses`` does.  Only initial_stage.* / refinement_stages.* move."""
+    if opt.net is not net:
+        raise ValueError("opt is not an optimiser of this net")
+    batches_per_iter = int(batches_per_iter)
+    if batches_per_iter < 1:
+        raise ValueError("batches_per_iter must be at least 1")
+    if opt.batch_index == 0:
+        opt.zero_grad()
+    losses, grads, _ = stage_gradients(net, images, labels, masks, stride, sigma, paf_thickness, None, 1.0 / batches_per_iter, opt.accumulated)
+    opt.accumulated = net.engine.flat_of(grads)
+    opt.batch_index += 1
+    if opt.batch_index >= batches_per_iter:
+        opt.step(opt.accumulated)
+        opt.batch_index = 0
+    return losses
 
 
 # ---------------------------------------------------------------------------------------------- COCO results
