@@ -522,6 +522,9 @@ int lwp_debug_post_counts_ex(lwp_handle h, int frame, int* peaks, int* kpts, int
 /* which grouping kernels the handle launches: 1 = the generic forms (a custom skeleton, or LWP_POST_GENERIC=1 at lwp_create),
  * 0 = the COCO-specialised ones */
 int lwp_debug_post_generic(lwp_handle h);
+/* what the library holds right now, over all handles of the process: out[0] bytes of device memory, out[1] bytes of pinned
+ * host memory, out[2] events, out[3] streams.  A destroyed handle has given back everything it took.  No handle, no GPU. */
+int lwp_debug_live_resources(int64_t out[4]);
 
 #ifdef __cplusplus
 }

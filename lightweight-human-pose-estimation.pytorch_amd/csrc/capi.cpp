@@ -11,103 +11,107 @@
 #include <vector>
 
 #include "lwp_internal.h"
+#include "lwp_owners.h"
 
 using namespace lwp;
 
 struct lwp_context {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // The streams come before every buffer and event: members are destroyed in reverse order, so the streams go last.
+    Stream stream, post_own;
+    hipStream_t post_stream = nullptr;     // unset until the first submit; then post_own, or `stream` itself (LWP_POST_STREAM=0)
     int dtype = LWP_F32;
     Graph g;
     Tuning tune;                           // every LWP_* A/B switch, read from the environment at lwp_create
     std::vector<std::string> variants;     // per layer: the kernel variant its last launch picked (debug / profiling entry points only)
     bool record_variants = false;
     char variant_buf[kVariantCap] = {0};
-    float* d_blob = nullptr;
-    float* d_zeros = nullptr;
+    DevBuf d_blob, d_zeros;
     bool weights_loaded = false;
     // activations for the current (N, H, W)
     int cur_N = 0, cur_H = 0, cur_W = 0;
-    std::vector<float*> bufs;
-    std::vector<size_t> buf_bytes;         // allocated size of each activation buffer (grow-only)
-    float* d_in = nullptr; size_t d_in_bytes = 0;
-    std::vector<float*> d_outs;            // NCHW staging for host outputs
-    std::vector<size_t> d_outs_bytes;
-    float* d_tmp = nullptr; size_t d_tmp_bytes = 0;     // generic device staging (upsample / extract / group)
-    float* d_tmp2 = nullptr; size_t d_tmp2_bytes = 0;
-    struct ResizeTab { int cw, ch, dw, dh; void* d; double ratio; int uh_max = 0, uw_max = 0, tx = 0, up_ratio = 0, tx4 = 0, uh4 = 0, uw4 = 0; };   // cubic resize tables of the multi-scale path, kept on the device (+ the fused kernel's tile extents)
-    std::vector<ResizeTab> resize_tabs;                  // (a per-call upload went through SDMA queues: multi-ms stalls on some boxes)
-    std::vector<ResizeTab> scale_tabs;                   // image-side tables of lwp_preprocess_scaled_u8: (W, H, dw, dh, ratio)
-    unsigned char* d_imgs = nullptr; size_t d_imgs_bytes = 0;   // uint8 frame batch staging (host frames of the multi-scale path)
-    float* d_img = nullptr; size_t d_img_bytes = 0;     // uint8 frame staging (pre-processing of host frames)
+    std::vector<DevBuf> bufs;              // grow-only
+    DevBuf d_in;
+    std::vector<DevBuf> d_outs;            // NCHW staging for host outputs
+    DevBuf d_tmp, d_tmp2;                  // generic device staging (upsample / extract / group)
+    // resize tables of one geometry, kept on the device: the four host arrays back to back in one allocation
+    // (a per-call upload went through SDMA queues: multi-ms stalls on some boxes)
+    struct TabKey {
+        int cw, ch, dw, dh; double ratio; int up_ratio;
+        bool operator==(const TabKey& o) const { return cw == o.cw && ch == o.ch && dw == o.dw && dh == o.dh && ratio == o.ratio && up_ratio == o.up_ratio; }
+    };
+    struct MsPlan { int uh_max = 0, uw_max = 0, tx = 0, tx4 = 0, uh4 = 0, uw4 = 0; };   // the fused multi-scale kernels' tile extents
+    struct ResizeTab { TabKey key; DevBuf d; MsPlan plan; };
+    typedef std::vector<ResizeTab> TabCache;
+    TabCache resize_tabs;                  // cubic tables of the multi-scale path: (cw, ch, dst_w, dst_h, up_ratio)
+    TabCache scale_tabs;                   // image-side tables of lwp_preprocess_scaled_u8: (W, H, dw, dh, ratio)
+    DevBuf d_imgs;                         // uint8 frame batch staging (host frames of the multi-scale path)
+    DevBuf d_img;                          // uint8 frame staging (pre-processing of host frames)
     // host frames travel through one of two pinned buffers (upload_host): a copy from pageable memory is staged by the runtime
     // anyway, at ~100 us per 720 KB frame and with the calling thread blocked until the DMA has finished
-    void* pin_buf[2] = {nullptr, nullptr}; size_t pin_bytes[2] = {0, 0}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_busy[2] = {false, false};
+    PinBuf pin_buf[2]; Event pin_ev[2]; bool pin_busy[2] = {false, false};
     int pin_next = 0;
-    float* d_pre_tab = nullptr; size_t d_pre_tab_bytes = 0;   // fixed-point resize tables, cached for (pre_H, pre_W, pre_net_h)
+    DevBuf d_pre_tab;                      // fixed-point resize tables, cached for (pre_H, pre_W, pre_net_h)
     int pre_H = 0, pre_W = 0, pre_net_h = 0;
-    std::vector<ResizeTab> pre_tabs;                     // the same tables for the batched entry points, one set per geometry (W, H, dw, dh, scale): never rewritten, so a
-                                                         // submit with a new frame size cannot race the launches of another slot that still read the old ones
-    float* d_pipe_in = nullptr; size_t d_pipe_in_bytes = 0;   // network input of lwp_pipeline_submit_u8 (written and read on the main stream only)
-    float* d_maps[2] = {nullptr, nullptr}; size_t d_maps_bytes[2] = {0, 0};   // bf16 path: f32 NCHW heat / PAF of the last stage
+    TabCache pre_tabs;                     // the same tables for the batched entry points, one set per geometry (W, H, dw, dh, scale): never rewritten, so a
+                                           // submit with a new frame size cannot race the launches of another slot that still read the old ones
+    DevBuf d_pipe_in;                      // network input of lwp_pipeline_submit_u8 (written and read on the main stream only)
+    DevBuf d_maps[2];                      // bf16 path: f32 NCHW heat / PAF of the last stage
     // post-processing
     PostCaps caps;
-    PostWorkspace ws;
+    struct WsMem { DevBuf arena, block; };  // the memory behind a PostWorkspace: the scratch arrays (ws_sections), the result block
+    PostWorkspace ws; WsMem ws_mem;
     Skeleton skel = default_skeleton();    // grouping tables + options (lwp_set_skeleton); host state, not part of the weights
-    int* d_limbs = nullptr;                // [kMaxSkelLimbs][4] device copy of skel's limb table (the generic kernels read it)
+    DevBuf d_limbs;                        // [kMaxSkelLimbs][4] ints: device copy of skel's limb table (the generic kernels read it)
     // pinned host staging for results
-    void* h_stage = nullptr; size_t h_stage_bytes = 0;
+    PinBuf h_stage;
     int last_N = 0;
     // pipelined streaming mode: two result slots, post-processing + fetch of frame k overlap the network of frame k+1
     struct Slot {
-        PostWorkspace ws;
-        float* maps[2] = {nullptr, nullptr}; size_t maps_bytes[2] = {0, 0};
-        void* h_stage = nullptr; size_t h_stage_bytes = 0;
-        hipEvent_t ev_maps = nullptr, ev_done = nullptr;
+        PostWorkspace ws; WsMem ws_mem;
+        DevBuf maps[2];
+        PinBuf h_stage;
+        Event ev_maps, ev_done;
         int N = 0;
         int tail_N = 0;                    // frames with pose rows in h_stage (0: submitted with the tail off)
         bool pending = false;
         // pose overlay (lwp_set_overlay): the slot OWNS the source pixels of host frames until its overlay has run (the shared
         // d_imgs staging is overwritten by the next submit on the main stream while this slot's post stream still reads it)
-        unsigned char* frames = nullptr; size_t frames_bytes = 0;   // uploaded host frames of this slot
-        unsigned char* ov = nullptr; size_t ov_bytes = 0;           // annotated frames, device
-        void* h_ov = nullptr; size_t h_ov_bytes = 0;                // mode 2: their pinned host copy
+        DevBuf frames;                     // uploaded host frames of this slot
+        DevBuf ov;                         // annotated frames, device
+        PinBuf h_ov;                       // mode 2: their pinned host copy
         int ov_N = 0, ov_H = 0, ov_W = 0, ov_mode = 0;              // ov_N == 0: the slot ran without the overlay
     } slots[2];
-    hipStream_t post_stream = nullptr;
-    // pose tail (lwp_set_tracking): parameters, the lanes' device state, (2 sigma)^2 of the K key-point types
+    // pose tail (lwp_set_tracking): parameters, the lanes' device state and its memory, (2 sigma)^2 of the K key-point types
     TailParams tail;
-    TailState tst;
-    float* d_vars = nullptr;
+    TailState tst; DevBuf tst_mem[9];
+    DevBuf d_vars;
     // pose overlay (lwp_set_overlay): settings, and the device staging of lwp_draw_poses (pose arrays; frames out for host `out`)
     struct Overlay { int mode = 0, boxes = 1, n_draw_limbs = -1; unsigned char color[3] = {0, 224, 255}, box_color[3] = {0, 255, 0}; } ovl;
-    float* d_ov_pose = nullptr; size_t d_ov_pose_bytes = 0;
-    float* d_ov_out = nullptr; size_t d_ov_out_bytes = 0;
+    DevBuf d_ov_pose, d_ov_out;
     // training targets and loss (lwp_train_targets / lwp_mask_downsample / lwp_stage_losses): staging of host key-points, person
     // counts and host masks; the loss partials followed by the per-stage sums
-    float* d_train = nullptr; size_t d_train_bytes = 0;
-    float* d_loss = nullptr; size_t d_loss_bytes = 0;
+    DevBuf d_train, d_loss;
     // stage backward (lwp_train_forward / lwp_stage_backward; f32 handles): the retaining buffer plan, its activation and
     // gradient buffers, the gradient array's layout, the raw stage parameters (the BatchNorm chain rule needs them unfolded)
     TrainPlan tp;
-    std::vector<float*> tbufs, gbufs;
-    std::vector<size_t> tbuf_bytes;
+    std::vector<DevBuf> tbufs, gbufs;                // (a gradient buffer has the size of its activation buffer)
     int train_N = 0, train_H = 0, train_W = 0;      // frames of the last retaining forward (0: none)
     struct GradSpec { std::string key; int64_t shape[4]; int ndim; size_t off; };
     std::vector<GradSpec> gspec;
     std::map<std::string, size_t> grad_off;          // state-dict key -> float offset in the gradient array
     std::map<std::string, size_t> raw_off;           // the same keys, and the BatchNorm running statistics -> float offset in d_raw
     size_t grad_floats = 0, raw_floats = 0;
-    float* d_raw = nullptr;
+    DevBuf d_raw;
     bool raw_loaded = false;                         // false after lwp_weights_blob_import: a blob holds folded weights only
-    float* d_bwd = nullptr; size_t d_bwd_bytes = 0; size_t bwd_fold_off = 0;  // wgrad partials, then the folded gradients of one BatchNorm layer
+    DevBuf d_bwd; size_t bwd_fold_off = 0;           // wgrad partials, then the folded gradients of one BatchNorm layer
     std::vector<int> bwd_splits;                     // per layer: pixel splits its last wgrad ran with
     // stage fine-tuning step (lwp_stage_adam_step): exp_avg then exp_avg_sq in one allocation, the step count, and the two
     // device tables the host builds once per handle (parameter chunks of the Adam kernel, layer descriptors of the repack)
-    float* d_adam = nullptr; size_t adam_sq_off = 0;
+    DevBuf d_adam; size_t adam_sq_off = 0;
     int64_t adam_t = 0;
-    AdamChunk* d_adam_chunks = nullptr; int adam_chunks = 0;
-    RepackLayer* d_repack = nullptr; int repack_layers = 0, repack_blocks = 0;
+    DevBuf d_adam_chunks; int adam_chunks = 0;
+    DevBuf d_repack; int repack_layers = 0, repack_blocks = 0;
     bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
@@ -117,15 +121,18 @@ struct lwp_context {
     hipStream_t caller_stream = nullptr;
     bool caller_ordered = false;
     bool hand_over = true;                 // lwp_set_stream mode 1: device results are handed to the caller's stream; mode 2: not
-    hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_copy = nullptr;
+    Event ev_in, ev_out, ev_copy;
     // per-launch profiling
     bool profiling = false;
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     std::vector<int> ev_class;
     std::vector<int> ev_layer;             // index of the (first) layer a launch covers, -1: post-processing kernel
     int cur_layer = -1;
     size_t ev_used = 0;
     std::string err;
+
+    float* blob(size_t off) const { return d_blob.as<float>() + off; }   // weights at a float offset of the packed blob
+    float* raw(const std::string& key) const { return d_raw.as<float>() + raw_off.at(key); }
 };
 
 static std::string g_err;
@@ -174,15 +181,6 @@ static int fail(lwp_context* h, int code, const std::string& msg) {
             return fail(h, LWP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
     } while (0)
 
-static int ensure_dev(lwp_context* h, float** p, size_t* have, size_t need) {
-    if (*have >= need) return LWP_OK;
-    if (*p) HIP_TRY(h, hipFree(*p));
-    *p = nullptr; *have = 0;
-    HIP_TRY(h, hipMalloc((void**)p, need));
-    *have = need;
-    return LWP_OK;
-}
-
 // caller's stream -> handle's stream: everything the caller has queued so far (producers of our inputs, consumers of the
 // buffers we are about to overwrite) is ordered before our next launch.  No-op unless lwp_set_stream enabled it.
 static int order_in(lwp_context* h) {
@@ -214,9 +212,9 @@ extern "C" int lwp_version(void) { return 102; }
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (enable && !h->ev_in) {
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
+    if (enable) {
+        HIP_TRY(h, h->ev_in.ensure(hipEventDisableTiming));
+        HIP_TRY(h, h->ev_out.ensure(hipEventDisableTiming));
     }
     h->caller_stream = (hipStream_t)caller_stream;
     h->caller_ordered = enable != 0;
@@ -273,29 +271,28 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
     h->tune = tuning_from_env();
     h->g = build_graph(nref, C, NH, NP, h->tune.fuse_dwpw != 0, dtype, h->tune.merge_heads != 0);
     h->variants.assign(h->g.layers.size(), std::string());
-    e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
+    e = h->stream.ensure();
+    if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("stream: ") + hipGetErrorString(e)); }
     e = init_cubic_tables();
     if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("init_cubic_tables: ") + hipGetErrorString(e)); }
-    e = hipMalloc((void**)&h->d_blob, h->g.blob_floats * sizeof(float));
-    if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipMalloc(blob): ") + hipGetErrorString(e)); }
-    e = hipMalloc((void**)&h->d_zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(h->d_zeros, 0, 4096);
-    if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipMalloc(zeros): ") + hipGetErrorString(e)); }
+    e = h->d_blob.ensure(h->g.blob_floats * sizeof(float));
+    if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("blob: ") + hipGetErrorString(e)); }
+    e = h->d_zeros.ensure(4096);
+    if (e == hipSuccess) e = hipMemset(h->d_zeros.as<void>(), 0, 4096);
+    if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("zeros: ") + hipGetErrorString(e)); }
     {
         std::vector<int> t(19 * 4);
         for (int l = 0; l < 19; ++l)
             for (int k = 0; k < 2; ++k) { t[l * 4 + k] = h->skel.kpt[l * 2 + k]; t[l * 4 + 2 + k] = h->skel.paf[l * 2 + k]; }
-        e = hipMalloc((void**)&h->d_limbs, (size_t)kMaxSkelLimbs * 4 * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpy(h->d_limbs, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("hipMalloc(limbs): ") + hipGetErrorString(e)); }
+        e = h->d_limbs.ensure((size_t)kMaxSkelLimbs * 4 * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(h->d_limbs.as<void>(), t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { delete h; return fail(nullptr, LWP_ERR_HIP, std::string("limbs: ") + hipGetErrorString(e)); }
     }
-    h->bufs.assign(h->g.bufs.size(), nullptr);
+    h->bufs.resize(h->g.bufs.size());
     if (dtype == LWP_F32) {
         h->tp = build_train_plan(h->g);
-        h->tbufs.assign(h->tp.bufs.size(), nullptr);
-        h->gbufs.assign(h->tp.bufs.size(), nullptr);
-        h->tbuf_bytes.assign(h->tp.bufs.size(), 0);
+        h->tbufs.resize(h->tp.bufs.size());
+        h->gbufs.resize(h->tp.bufs.size());
         h->gspec = stage_grad_spec(nref, C, NH, NP, &h->grad_floats);
         for (const auto& s : h->gspec) h->grad_off[s.key] = s.off;
         h->raw_off = h->grad_off;
@@ -304,27 +301,24 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
             if (is_stage_key(p.key) && (p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR)) { h->raw_off[p.key] = h->raw_floats; h->raw_floats += (size_t)p.shape[0]; }
         h->bwd_splits.assign(h->g.layers.size(), 0);
     }
-    h->d_outs.assign(2 * (1 + nref), nullptr);
-    h->d_outs_bytes.assign(2 * (1 + nref), 0);
+    h->d_outs.resize(2 * (1 + nref));
     *out = h;
     return LWP_OK;
 }
 
-static void free_ws_obj(PostWorkspace& w) {
-    // flags / kpt_count / n_entries / kpts_out / entries live in ONE allocation (result_block) so the fetch is one copy
-    void* ptrs[] = {w.peak_count, w.peak_key, w.peak_val, w.kpt_xy, w.kpt_score, w.conn_count,
-                    w.conn_ij, w.conn_ratio, w.result_block, w.sel_count, w.sel_ij, w.sel_r,
-                    w.entries_work, w.sel_sa, w.sel_sb, w.seen};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+static void free_ws_obj(PostWorkspace& w, lwp_context::WsMem& m) {
+    (void)m.arena.reset();
+    (void)m.block.reset();
     w = PostWorkspace();
 }
-static void free_ws(lwp_context* h) { free_ws_obj(h->ws); }
-static void free_tail_state(lwp_context* h, bool drop_results = true) {
-    TailState& t = h->tst;
-    void* ptrs[] = {t.hdr, t.kp, t.bbox, t.ids, t.f_xprev, t.f_init, t.f_dx, t.f_x, t.sim};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    t = TailState();
-    if (!drop_results) return;
+// every workspace of the handle: its own and the two slots'
+static void free_workspaces(lwp_context* h) {
+    free_ws_obj(h->ws, h->ws_mem);
+    for (auto& sl : h->slots) free_ws_obj(sl.ws, sl.ws_mem);
+}
+static void free_tail_state(lwp_context* h) {
+    for (DevBuf& b : h->tst_mem) (void)b.reset();
+    h->tst = TailState();
     h->stage_tail_N = 0;
     for (auto& sl : h->slots) sl.tail_N = 0;
 }
@@ -333,57 +327,8 @@ extern "C" int lwp_destroy(lwp_handle h) {
     if (!h) return LWP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (float* p : h->bufs) if (p) (void)hipFree(p);
-    for (float* p : h->tbufs) if (p) (void)hipFree(p);
-    for (float* p : h->gbufs) if (p) (void)hipFree(p);
-    if (h->d_raw) (void)hipFree(h->d_raw);
-    if (h->d_bwd) (void)hipFree(h->d_bwd);
-    if (h->d_adam) (void)hipFree(h->d_adam);
-    if (h->d_adam_chunks) (void)hipFree(h->d_adam_chunks);
-    if (h->d_repack) (void)hipFree(h->d_repack);
-    for (float* p : h->d_outs) if (p) (void)hipFree(p);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_tmp) (void)hipFree(h->d_tmp);
-    if (h->d_tmp2) (void)hipFree(h->d_tmp2);
-    for (float* p : h->d_maps) if (p) (void)hipFree(p);
-    for (auto& rt : h->resize_tabs) if (rt.d) (void)hipFree(rt.d);
-    for (auto& rt : h->scale_tabs) if (rt.d) (void)hipFree(rt.d);
-    if (h->d_imgs) (void)hipFree(h->d_imgs);
-    if (h->d_img) (void)hipFree(h->d_img);
-    for (int k = 0; k < 2; ++k) {
-        if (h->pin_buf[k]) (void)hipHostFree(h->pin_buf[k]);
-        if (h->pin_ev[k]) (void)hipEventDestroy(h->pin_ev[k]);
-    }
-    if (h->d_pre_tab) (void)hipFree(h->d_pre_tab);
-    for (auto& rt : h->pre_tabs) if (rt.d) (void)hipFree(rt.d);
-    if (h->d_pipe_in) (void)hipFree(h->d_pipe_in);
-    if (h->d_blob) (void)hipFree(h->d_blob);
-    if (h->d_zeros) (void)hipFree(h->d_zeros);
-    if (h->d_limbs) (void)hipFree(h->d_limbs);
-    if (h->d_vars) (void)hipFree(h->d_vars);
-    if (h->d_ov_pose) (void)hipFree(h->d_ov_pose);
-    if (h->d_ov_out) (void)hipFree(h->d_ov_out);
-    if (h->d_train) (void)hipFree(h->d_train);
-    if (h->d_loss) (void)hipFree(h->d_loss);
-    free_tail_state(h);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    free_ws(h);
     if (h->post_stream) (void)hipStreamSynchronize(h->post_stream);
-    for (auto& sl : h->slots) {
-        free_ws_obj(sl.ws);
-        for (float* p : sl.maps) if (p) (void)hipFree(p);
-        if (sl.h_stage) (void)hipHostFree(sl.h_stage);
-        if (sl.frames) (void)hipFree(sl.frames);
-        if (sl.ov) (void)hipFree(sl.ov);
-        if (sl.h_ov) (void)hipHostFree(sl.h_ov);
-        if (sl.ev_maps) (void)hipEventDestroy(sl.ev_maps);
-        if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
-    }
-    if (h->post_stream && h->post_stream != h->stream) (void)hipStreamDestroy(h->post_stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_in, h->ev_out, h->ev_copy}) if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                          // every member releases what it owns; the streams go last
     return LWP_OK;
 }
 
@@ -395,8 +340,7 @@ extern "C" int lwp_set_capacity(lwp_handle h, int max_peaks, int max_kpts, int m
     for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending");
     (void)hipSetDevice(h->device);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_ws(h);
-    for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    free_workspaces(h);
     if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
     free_tail_state(h);                                // the lanes' state is sized by max_entries: every lane starts over
     h->last_N = 0; h->async_pending = false;   // the results of an unfetched lwp_infer_poses_async went with the workspace
@@ -448,9 +392,8 @@ extern "C" int lwp_set_skeleton(lwp_handle h, int num_kpt_types, int num_limbs, 
     std::vector<int> t((size_t)sk.L * 4);
     for (int l = 0; l < sk.L; ++l)
         for (int k = 0; k < 2; ++k) { t[l * 4 + k] = sk.kpt[l * 2 + k]; t[l * 4 + 2 + k] = sk.paf[l * 2 + k]; }
-    HIP_TRY(h, hipMemcpy(h->d_limbs, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
-    free_ws(h);                                        // every workspace is sized by K / L / E: re-allocated lazily
-    for (auto& sl : h->slots) free_ws_obj(sl.ws);
+    HIP_TRY(h, hipMemcpy(h->d_limbs.as<void>(), t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+    free_workspaces(h);                                // every workspace is sized by K / L / E: re-allocated lazily
     free_tail_state(h);                                // the lanes' state is sized by K: every lane starts over
     if (h->tail.mode >= 2 && sk.K != h->skel.K) h->tail.mode = 0;   // the sigma table was given for the old K: tracking is off until lwp_set_tracking
     h->last_N = 0; h->async_pending = false;   // the results of an unfetched lwp_infer_poses_async went with the workspace
@@ -490,7 +433,7 @@ extern "C" int lwp_load_weights(lwp_handle h, const char* const* names, const vo
     if (!msg.empty()) return fail(h, LWP_ERR_ARG, msg);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));         // a queued lwp_stage_adam_step still writes the blob and the raw parameters
-    HIP_TRY(h, hipMemcpy(h->d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_blob.as<float>(), blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
     h->weights_loaded = true;
     if (h->dtype == LWP_F32) {                           // the stage parameters as given: lwp_stage_backward's BatchNorm chain rule
         std::vector<float> raw(h->raw_floats, 0.0f);
@@ -501,9 +444,9 @@ extern "C" int lwp_load_weights(lwp_handle h, const char* const* names, const vo
             for (int d = 0; d < ts[i].ndim; ++d) cnt *= (size_t)ts[i].shape[d];
             std::memcpy(raw.data() + it->second, ts[i].ptr, cnt * sizeof(float));     // shapes were checked by pack_weights
         }
-        if (!h->d_raw) HIP_TRY(h, hipMalloc((void**)&h->d_raw, std::max<size_t>(h->raw_floats, 1) * sizeof(float)));
+        HIP_TRY(h, h->d_raw.ensure(std::max<size_t>(h->raw_floats, 1) * sizeof(float)));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipMemcpy(h->d_raw, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_raw.as<float>(), raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice));
         h->raw_loaded = true;
     }
     return LWP_OK;
@@ -530,7 +473,7 @@ extern "C" int lwp_weights_blob_export(lwp_handle h, void* dst, size_t bytes) {
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t packed = h->g.blob_floats * sizeof(float);
     HIP_TRY(h, hipStreamSynchronize(h->stream));         // the copy below is not stream-ordered: a queued lwp_stage_adam_step finishes first
-    HIP_TRY(h, hipMemcpy(dst, h->d_blob, packed, hipMemcpyDeviceToDevice));
+    HIP_TRY(h, hipMemcpy(dst, h->d_blob.as<float>(), packed, hipMemcpyDeviceToDevice));
     if (h->dtype == LWP_F16) {
         uint64_t tag[2];
         f16_blob_tag(h, tag);
@@ -549,7 +492,7 @@ extern "C" int lwp_weights_blob_import(lwp_handle h, const void* src, size_t byt
         if (std::memcmp(want, got, sizeof(want)) != 0) return fail(h, LWP_ERR_ARG, "not an fp16 weight blob of this network");
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));         // a queued repack must not overwrite the imported stage layers
-    HIP_TRY(h, hipMemcpy(h->d_blob, src, packed, hipMemcpyDeviceToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_blob.as<float>(), src, packed, hipMemcpyDeviceToDevice));
     h->weights_loaded = true;
     h->raw_loaded = false;
     return LWP_OK;
@@ -566,22 +509,19 @@ static int ensure_activations(lwp_context* h, int N, int H, int W) {
     if (h->cur_N == N && h->cur_H == H && h->cur_W == W) return LWP_OK;
     // Buffers only ever GROW: a caller that alternates shapes (the three scales of val.infer) would otherwise free and
     // re-allocate gigabytes on every call — hipFree / hipMalloc of that size took up to 600 ms on some boxes.
-    if (h->buf_bytes.size() != h->bufs.size()) h->buf_bytes.assign(h->bufs.size(), 0);
     bool synced = false;
     for (size_t i = 0; i < h->bufs.size(); ++i) {
         int bh, bw;
         level_dims(H, W, h->g.bufs[i].level, &bh, &bw);
         const size_t bytes = (size_t)N * bh * bw * h->g.bufs[i].channels * (h->dtype != LWP_F32 ? 2 : 4);
-        if (bytes > h->buf_bytes[i]) {
+        if (bytes > h->bufs[i].size()) {
             if (!synced) { HIP_TRY(h, hipStreamSynchronize(h->stream)); synced = true; }
-            if (h->bufs[i]) { HIP_TRY(h, hipFree(h->bufs[i])); h->bufs[i] = nullptr; h->buf_bytes[i] = 0; }
-            HIP_TRY(h, hipMalloc((void**)&h->bufs[i], bytes));
-            h->buf_bytes[i] = bytes;
+            HIP_TRY(h, h->bufs[i].ensure(bytes));
         }
         // the concat buffer's pad channels are read (with zero weights) but never written: they must hold finite values,
         // and a re-used buffer may hold anything at the new geometry's offsets -> cleared, stream-ordered.  Every other
         // buffer is completely overwritten by its producer before it is read.
-        if (h->g.bufs[i].has_pad) HIP_TRY(h, hipMemsetAsync(h->bufs[i], 0, bytes, h->stream));
+        if (h->g.bufs[i].has_pad) HIP_TRY(h, hipMemsetAsync(h->bufs[i].as<void>(), 0, bytes, h->stream));
     }
     h->cur_N = N; h->cur_H = H; h->cur_W = W;
     return LWP_OK;
@@ -604,54 +544,53 @@ static void carve_result_block(PostWorkspace& w, const ResultLayout& l, size_t f
     w.t_n = (int*)at(l.t_n); w.t_near = (unsigned*)at(l.t_near); w.t_last = (int*)at(l.t_last);
 }
 
-static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, int N, hipStream_t stream) {
+// THE layout of a workspace's scratch arena: f(field, bytes per frame) for every per-frame array outside the result block, in
+// arena order.  It sizes and carves the arena (ensure_ws_obj) and moves a view to a later frame (ws_frames).
+template <class F>
+static void ws_sections(PostWorkspace& w, F f) {
+    const PostCaps& c = w.caps;
+    const size_t K = (size_t)w.K, L = (size_t)w.L, E = (size_t)w.E;
+    f(w.peak_count, K * 4); f(w.peak_key, K * c.max_peaks * 4); f(w.peak_val, K * c.max_peaks * 4);
+    f(w.kpt_xy, K * c.max_kpts * 2 * 4); f(w.kpt_score, K * c.max_kpts * 4);
+    f(w.conn_count, L * 4); f(w.conn_ij, L * c.max_conn * 4); f(w.conn_ratio, L * c.max_conn * 8);
+    f(w.entries_work, (size_t)c.max_entries * E * 8); f(w.sel_count, L * 4); f(w.seen, (K + L) * 4);
+    f(w.sel_ij, L * c.max_kpts * 4); f(w.sel_r, L * c.max_kpts * 8); f(w.sel_sa, L * c.max_kpts * 4); f(w.sel_sb, L * c.max_kpts * 4);
+}
+// every section starts on a 256-byte boundary of the arena: frame 0 of an array is aligned as an allocation of its own was
+static size_t ws_section_bytes(int N, size_t per_frame) { return ((size_t)N * per_frame + 255) & ~(size_t)255; }
+
+static int ensure_ws_obj(lwp_context* h, PostWorkspace& w, lwp_context::WsMem& m, int N, hipStream_t stream) {
     if (w.N >= N && w.peak_count && (w.tail != 0) == (h->tail.mode != 0)) return LWP_OK;
     if (h->tail.mode && h->caps.max_entries > kTailMaxPoses)
         return fail(h, LWP_ERR_ARG, "the pose tail (lwp_set_tracking) holds at most 256 poses per frame: lower max_pose_entries or turn it off");
     HIP_TRY(h, hipStreamSynchronize(stream));
-    free_ws_obj(w);
+    free_ws_obj(w, m);
     w.caps = h->caps;
-    const PostCaps& c = h->caps;
-    const int K = h->skel.K, L = h->skel.L, E = h->skel.E;
-    w.K = K; w.L = L; w.E = E;
+    w.K = h->skel.K; w.L = h->skel.L; w.E = h->skel.E;
     w.min_paf = h->skel.min_paf;
     w.generic = (!h->skel.is_default || h->tune.post_generic == 1) ? 1 : 0;
-    w.limbs = h->d_limbs;
-#define WS_ALLOC(field, count, type) HIP_TRY(h, hipMalloc((void**)&w.field, (size_t)(count) * sizeof(type)))
-    WS_ALLOC(peak_count, N * K, int);
-    WS_ALLOC(peak_key, (size_t)N * K * c.max_peaks, uint32_t);
-    WS_ALLOC(peak_val, (size_t)N * K * c.max_peaks, float);
-    WS_ALLOC(kpt_xy, (size_t)N * K * c.max_kpts * 2, int);
-    WS_ALLOC(kpt_score, (size_t)N * K * c.max_kpts, float);
-    WS_ALLOC(conn_count, N * L, int);
-    WS_ALLOC(conn_ij, (size_t)N * L * c.max_conn, int);
-    WS_ALLOC(conn_ratio, (size_t)N * L * c.max_conn, double);
+    w.limbs = h->d_limbs.as<int>();
+    size_t arena = 0;
+    ws_sections(w, [&](auto*&, size_t per) { arena += ws_section_bytes(N, per); });
+    HIP_TRY(h, m.arena.ensure(arena));
+    char* at = m.arena.as<char>();
+    ws_sections(w, [&](auto*& p, size_t per) { p = reinterpret_cast<decltype(+p)>(at); at += ws_section_bytes(N, per); });
+    // flags / kpt_count / n_entries / kpts_out / entries live in ONE allocation (result_block) so the fetch is one copy
     w.tail = h->tail.mode ? 1 : 0;
-    const ResultLayout lay = result_layout(N, K, E, c, w.tail != 0);
-    HIP_TRY(h, hipMalloc(&w.result_block, lay.bytes));
+    const ResultLayout lay = result_layout(N, w.K, w.E, w.caps, w.tail != 0);
+    HIP_TRY(h, m.block.ensure(lay.bytes));
+    w.result_block = m.block.as<void>();
     carve_result_block(w, lay, 0);
     if (w.tail) HIP_TRY(h, hipMemsetAsync((char*)w.result_block + lay.tail_off, 0, lay.bytes - lay.tail_off, stream));
-    WS_ALLOC(entries_work, (size_t)N * c.max_entries * E, double);
-    WS_ALLOC(sel_count, N * L, int);
-    WS_ALLOC(seen, N * (K + L), int);
-    WS_ALLOC(sel_ij, (size_t)N * L * c.max_kpts, int);
-    WS_ALLOC(sel_r, (size_t)N * L * c.max_kpts, double);
-    WS_ALLOC(sel_sa, (size_t)N * L * c.max_kpts, float);
-    WS_ALLOC(sel_sb, (size_t)N * L * c.max_kpts, float);
-#undef WS_ALLOC
     w.N = N;
     HIP_TRY(h, launch_reset_ws(N, w, stream));
     return LWP_OK;
 }
-static int ensure_ws(lwp_context* h, int N) { return ensure_ws_obj(h, h->ws, N, h->stream); }
+static int ensure_ws(lwp_context* h, int N) { return ensure_ws_obj(h, h->ws, h->ws_mem, N, h->stream); }
 
 static int ensure_host_stage(lwp_context* h, size_t bytes) {
     h->stage_tail_N = 0;                               // every user of h_stage comes through here: the pose rows in it are gone
-    if (h->h_stage_bytes >= bytes) return LWP_OK;
-    if (h->h_stage) HIP_TRY(h, hipHostFree(h->h_stage));
-    h->h_stage = nullptr; h->h_stage_bytes = 0;
-    HIP_TRY(h, hipHostMalloc(&h->h_stage, bytes, hipHostMallocDefault));
-    h->h_stage_bytes = bytes;
+    HIP_TRY(h, h->h_stage.ensure(bytes));
     return LWP_OK;
 }
 
@@ -660,9 +599,9 @@ static int prof_begin(lwp_context* h, hipStream_t s, int kclass) {
     if (!h->profiling) return LWP_OK;
     if (h->ev_used + 2 > h->ev.size()) {
         for (int i = 0; i < 2; ++i) {
-            hipEvent_t e;
-            HIP_TRY(h, hipEventCreate(&e));
-            h->ev.push_back(e);
+            Event e;
+            HIP_TRY(h, e.ensure());
+            h->ev.push_back(std::move(e));
         }
         h->ev_class.resize(h->ev.size() / 2);
         h->ev_layer.resize(h->ev.size() / 2);
@@ -723,20 +662,17 @@ static int for_each_pass(lwp_context* h, int N, int H, int W, F fn) {
     return LWP_OK;
 }
 
-// milliseconds the handle's stream spends on `iters` calls of fn; the two events do not outlive an error return
+// milliseconds the handle's stream spends on `iters` calls of fn
 template <class F>
 static int time_on_stream(lwp_context* h, int iters, F fn, float* ms) {
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } e;
-    HIP_TRY(h, hipEventCreate(&e.a));
-    HIP_TRY(h, hipEventCreate(&e.b));
-    HIP_TRY(h, hipEventRecord(e.a, h->stream));
+    Event a, b;
+    HIP_TRY(h, a.ensure());
+    HIP_TRY(h, b.ensure());
+    HIP_TRY(h, hipEventRecord(a, h->stream));
     for (int i = 0; i < iters; ++i) { int rc = fn(); if (rc) return rc; }
-    HIP_TRY(h, hipEventRecord(e.b, h->stream));
-    HIP_TRY(h, hipEventSynchronize(e.b));
-    HIP_TRY(h, hipEventElapsedTime(ms, e.a, e.b));
+    HIP_TRY(h, hipEventRecord(b, h->stream));
+    HIP_TRY(h, hipEventSynchronize(b));
+    HIP_TRY(h, hipEventElapsedTime(ms, a, b));
     return LWP_OK;
 }
 
@@ -750,18 +686,9 @@ static MapView nchw_view(const float* base, int C, int h, int w) {
 static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
     if (f0 == 0) return w;
     PostWorkspace v = w;
-    const PostCaps& c = w.caps;
-    const size_t f = (size_t)f0;
     v.N = w.N - f0;
-    const size_t K = (size_t)w.K, L = (size_t)w.L, E = (size_t)w.E;
-    v.peak_count += f * K; v.peak_key += f * K * c.max_peaks; v.peak_val += f * K * c.max_peaks;
-    v.kpt_xy += f * K * c.max_kpts * 2; v.kpt_score += f * K * c.max_kpts;
-    v.conn_count += f * L; v.conn_ij += f * L * c.max_conn; v.conn_ratio += f * L * c.max_conn;
-    v.sel_count += f * L; v.sel_ij += f * L * c.max_kpts; v.sel_r += f * L * c.max_kpts;
-    v.seen += f * (K + L);
-    v.sel_sa += f * L * c.max_kpts; v.sel_sb += f * L * c.max_kpts;
-    v.entries_work += f * c.max_entries * E;
-    carve_result_block(v, result_layout(w), f);
+    ws_sections(v, [&](auto*& p, size_t per) { p = reinterpret_cast<decltype(+p)>((char*)p + (size_t)f0 * per); });
+    carve_result_block(v, result_layout(w), (size_t)f0);
     return v;
 }
 
@@ -770,7 +697,7 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
 // (an index past the graph's buffers is a buffer of the retaining plan, TrainPlan: f32, level 3)
 static inline float* buf_at(lwp_context* h, const BufRef& r) {
     const int nb = (int)h->g.bufs.size();
-    char* base = r.buf < nb ? (char*)h->bufs[r.buf] : (char*)h->tbufs[r.buf - nb];
+    char* base = (r.buf < nb ? h->bufs[r.buf] : h->tbufs[r.buf - nb]).as<char>();
     return (float*)(base + (size_t)r.coff * (h->dtype != LWP_F32 ? 2 : 4));
 }
 static inline int buf_level(const lwp_context* h, int buf) { return buf < (int)h->g.bufs.size() ? h->g.bufs[buf].level : 3; }
@@ -779,15 +706,15 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
                          const Layer* fold = nullptr, bool* folded = nullptr) {
     const bool h16 = h->dtype != LWP_F32;            // bf16 or fp16: the same launchers, the element type rides in the params
     const int f16 = h->dtype == LWP_F16;
-    const float* wts = h->d_blob + l.w_off;
-    const float* bias = h->d_blob + l.b_off;
+    const float* wts = h->blob(l.w_off);
+    const float* bias = h->blob(l.b_off);
     int dh, dw;
     level_dims(H, W, buf_level(h, l.dst.buf), &dh, &dw);
     float* dst = buf_at(h, l.dst);
     char* vb = h->record_variants ? h->variant_buf : nullptr;
     if (vb) vb[0] = 0;
     if (l.kind == L_STEM) {
-        StemParams p{d_in, wts, bias, dst, N, H, W, dh, dw, f16, h->d_zeros};
+        StemParams p{d_in, wts, bias, dst, N, H, W, dh, dw, f16, h->d_zeros.as<float>()};
         p.tune = &h->tune; p.variant = vb;
         LAUNCH(h, KC_STEM, h16 ? launch_stem_bf16(p, h->stream) : launch_stem(p, h->stream));
     } else if (l.kind == L_DWPW) {
@@ -795,10 +722,10 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
         level_dims(H, W, buf_level(h, l.src.buf), &sh, &sw);
         DwPwParams p;
         p.in = buf_at(h, l.src); p.in_ld = l.src.ld; p.f16 = f16;
-        p.dw_w = wts; p.pw_w = h->d_blob + l.w2_off; p.pw_b = h->d_blob + l.b2_off;
+        p.dw_w = wts; p.pw_w = h->blob(l.w2_off); p.pw_b = h->blob(l.b2_off);
         p.out = dst; p.out_ld = l.dst.ld;
         p.res = l.res.buf >= 0 ? buf_at(h, l.res) : nullptr; p.res_ld = l.res.ld;
-        p.zeros = h->d_zeros;
+        p.zeros = h->d_zeros.as<float>();
         p.N = N; p.Hi = sh; p.Wi = sw; p.Ho = dh; p.Wo = dw; p.C = l.cin; p.cout = l.cout;
         p.stride = l.stride; p.dil = l.dil; p.act_dw = l.act; p.act_pw = l.act2;
         p.tune = &h->tune; p.variant = vb;
@@ -813,18 +740,18 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
         GemmParams p;
         p.in = buf_at(h, l.src); p.in_ld = l.src.ld; p.f16 = f16;
         p.w = wts; p.bias = bias;
-        p.wf = h16 ? nullptr : h->d_blob + l.w2_off;
+        p.wf = h16 ? nullptr : h->blob(l.w2_off);
         p.out = dst; p.out_ld = l.dst.ld;
         p.res = l.res.buf >= 0 ? buf_at(h, l.res) : nullptr; p.res_ld = l.res.ld;
         p.out_nchw = (l.out_index >= 0 && d_outs_nchw) ? d_outs_nchw[l.out_index] : nullptr;
         p.out_nchw2 = (l.out_index2 >= 0 && d_outs_nchw) ? d_outs_nchw[l.out_index2] : nullptr;
         p.out_split = l.out_split;
-        p.zeros = h->d_zeros;
+        p.zeros = h->d_zeros.as<float>();
         p.N = N; p.H = dh; p.W = dw;
         p.cin_pad = l.cin_pad; p.cout = l.cout; p.cout_pad = l.cout_pad; p.ks = l.ks; p.dil = l.dil; p.act = l.act;
         p.tune = &h->tune; p.variant = vb;
         if (fold && folded && h16) {                    // the next 1x1 rides in this launch's epilogue if the launcher takes it
-            p.w2 = h->d_blob + fold->w_off; p.bias2 = h->d_blob + fold->b_off;
+            p.w2 = h->blob(fold->w_off); p.bias2 = h->blob(fold->b_off);
             p.out2 = buf_at(h, fold->dst); p.out2_ld = fold->dst.ld; p.act2 = fold->act;
             p.fused2 = folded;
         }
@@ -855,8 +782,8 @@ static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, in
     level_dims(H, W, buf_level(h, b.dst.buf), &dh, &dw);
     HeadsParams p;
     p.in = buf_at(h, a.src); p.in_ld = a.src.ld; p.f16 = h->dtype == LWP_F16;
-    p.w0 = h->d_blob + a.w_off; p.b0 = h->d_blob + a.b_off;
-    p.w1 = h->d_blob + b.w_off; p.b1 = h->d_blob + b.b_off;
+    p.w0 = h->blob(a.w_off); p.b0 = h->blob(a.b_off);
+    p.w1 = h->blob(b.w_off); p.b1 = h->blob(b.b_off);
     p.out = buf_at(h, b.dst); p.out_ld = b.dst.ld;
     p.out_nchw = (b.out_index >= 0 && d_outs_nchw) ? d_outs_nchw[b.out_index] : nullptr;
     p.out_nchw2 = (b.out_index2 >= 0 && d_outs_nchw) ? d_outs_nchw[b.out_index2] : nullptr;
@@ -924,10 +851,9 @@ static int check_frame_shape(lwp_context* h, int N, int H, int W) {
 
 static int stage_input(lwp_context* h, const float* in, int in_mem, size_t bytes, const float** d_in) {
     if (in_mem == LWP_MEM_DEVICE) { *d_in = in; return LWP_OK; }
-    int rc = ensure_dev(h, &h->d_in, &h->d_in_bytes, bytes);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_in, in, bytes, hipMemcpyHostToDevice, h->stream));
-    *d_in = h->d_in;
+    HIP_TRY(h, h->d_in.ensure(bytes));
+    HIP_TRY(h, hipMemcpyAsync(h->d_in.as<float>(), in, bytes, hipMemcpyHostToDevice, h->stream));
+    *d_in = h->d_in.as<float>();
     return LWP_OK;
 }
 
@@ -950,9 +876,8 @@ extern "C" int lwp_forward(lwp_handle h, const float* in, int in_mem, int N, int
         if (!outs[i]) return fail(h, LWP_ERR_ARG, "null output pointer");
         if (out_mem == LWP_MEM_DEVICE) { d_outs[i] = outs[i]; continue; }
         const size_t bytes = (size_t)N * (i % 2 ? h->g.NP : h->g.NH) * fh * fw * sizeof(float);
-        rc = ensure_dev(h, &h->d_outs[i], &h->d_outs_bytes[i], bytes);
-        if (rc) return rc;
-        d_outs[i] = h->d_outs[i];
+        HIP_TRY(h, h->d_outs[i].ensure(bytes));
+        d_outs[i] = h->d_outs[i].as<float>();
     }
     rc = for_each_pass(h, N, H, W, [&](int f0, int n) {
         for (int i = 0; i < nout; ++i) d_chunk[i] = d_outs[i] + (size_t)f0 * (i % 2 ? h->g.NP : h->g.NH) * fh * fw;
@@ -982,16 +907,14 @@ extern "C" int lwp_upsample(lwp_handle h, const float* src, int src_mem, int N, 
     const size_t sb = (size_t)N * C * hs * ws * sizeof(float), db = sb * ratio * ratio;
     const float* d_src = src;
     if (src_mem == LWP_MEM_HOST) {
-        int rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, sb);
-        if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_tmp, src, sb, hipMemcpyHostToDevice, h->stream));
-        d_src = h->d_tmp;
+        HIP_TRY(h, h->d_tmp.ensure(sb));
+        HIP_TRY(h, hipMemcpyAsync(h->d_tmp.as<float>(), src, sb, hipMemcpyHostToDevice, h->stream));
+        d_src = h->d_tmp.as<float>();
     }
     float* d_dst = dst;
     if (dst_mem == LWP_MEM_HOST) {
-        int rc = ensure_dev(h, &h->d_tmp2, &h->d_tmp2_bytes, db);
-        if (rc) return rc;
-        d_dst = h->d_tmp2;
+        HIP_TRY(h, h->d_tmp2.ensure(db));
+        d_dst = h->d_tmp2.as<float>();
     }
     const MapView v = nchw_view(d_src, C, hs, ws);
     LAUNCH(h, KC_POST, launch_upsample(v, N, C, ratio, d_dst, h->stream, &h->tune));
@@ -1003,6 +926,33 @@ extern "C" int lwp_upsample(lwp_handle h, const float* src, int src_mem, int N, 
         int rc1 = order_out(h, h->stream, &ordered);
         if (rc1) return rc1;
     }
+    return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- resize-table cache
+constexpr size_t kTabCacheMax = 16;
+static lwp_context::ResizeTab* find_tab(lwp_context::TabCache& cache, const lwp_context::TabKey& key) {
+    for (auto& rt : cache) if (rt.key == key) return &rt;
+    return nullptr;
+}
+// A new geometry's tables: the host arrays (4-byte elements), uploaded back to back into one allocation (blocking copies: a
+// steady-state call issues none).  The cache is bounded: the oldest geometry goes first, once nothing queued can read it.
+// The entry is inserted only after the upload succeeded.
+struct TabPart { const void* p; size_t n; };
+static int add_tab(lwp_context* h, lwp_context::TabCache& cache, const lwp_context::TabKey& key, const lwp_context::MsPlan& plan,
+                   std::initializer_list<TabPart> parts, lwp_context::ResizeTab** out) {
+    if (cache.size() >= kTabCacheMax) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        cache.erase(cache.begin());
+    }
+    size_t n = 0;
+    for (const TabPart& a : parts) n += a.n;
+    DevBuf d;
+    HIP_TRY(h, d.ensure(n * 4));
+    char* t = d.as<char>();
+    for (const TabPart& a : parts) { HIP_TRY(h, hipMemcpy(t, a.p, a.n * 4, hipMemcpyHostToDevice)); t += a.n * 4; }
+    cache.push_back(lwp_context::ResizeTab{key, std::move(d), plan});
+    *out = &cache.back();
     return LWP_OK;
 }
 
@@ -1021,53 +971,39 @@ extern "C" int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int ma
     int rc;
     if (maps_mem == LWP_MEM_DEVICE || accum_mem == LWP_MEM_DEVICE) { rc = order_in(h); if (rc) return rc; }
     if (maps_mem == LWP_MEM_HOST) {
-        rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, sb);
-        if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_tmp, maps, sb, hipMemcpyHostToDevice, h->stream));
-        d_src = h->d_tmp;
+        HIP_TRY(h, h->d_tmp.ensure(sb));
+        HIP_TRY(h, hipMemcpyAsync(h->d_tmp.as<float>(), maps, sb, hipMemcpyHostToDevice, h->stream));
+        d_src = h->d_tmp.as<float>();
     }
     float* d_acc = accum;
     if (accum_mem == LWP_MEM_HOST) {
-        rc = ensure_dev(h, &h->d_maps[0], &h->d_maps_bytes[0], ab);
-        if (rc) return rc;
-        if (!init) HIP_TRY(h, hipMemcpyAsync(h->d_maps[0], accum, ab, hipMemcpyHostToDevice, h->stream));
-        d_acc = h->d_maps[0];
+        HIP_TRY(h, h->d_maps[0].ensure(ab));
+        if (!init) HIP_TRY(h, hipMemcpyAsync(h->d_maps[0].as<float>(), accum, ab, hipMemcpyHostToDevice, h->stream));
+        d_acc = h->d_maps[0].as<float>();
     }
     // per-geometry tables, uploaded once (blocking copy) and kept: steady-state calls issue no host->device copy
     const size_t nx = (size_t)dst_w * 4, ny = (size_t)dst_h * 4;
-    void* d_tabs = nullptr;
-    int uh_max = 0, uw_max = 0, ms_tx = 0, tx4 = 0, uh4 = 0, uw4 = 0;
-    for (const auto& rt : h->resize_tabs)
-        if (rt.cw == cw && rt.ch == ch && rt.dw == dst_w && rt.dh == dst_h && rt.up_ratio == up_ratio) {
-            d_tabs = rt.d; uh_max = rt.uh_max; uw_max = rt.uw_max; ms_tx = rt.tx; tx4 = rt.tx4; uh4 = rt.uh4; uw4 = rt.uw4; break;
-        }
-    if (!d_tabs) {
+    const lwp_context::TabKey key{cw, ch, dst_w, dst_h, 0.0, up_ratio};
+    lwp_context::ResizeTab* tab = find_tab(h->resize_tabs, key);
+    if (!tab) {
         std::vector<int> xi, yi;
         std::vector<float> xw, yw;
         build_resize_table(cw, dst_w, xi, xw);
         build_resize_table(ch, dst_h, yi, yw);
+        lwp_context::MsPlan pl;
         if (h->tune.ms_tx >= 8 && h->tune.ms_tx <= 40) {   // LWP_MS_TX: a forced tile width (tests, A/B)
-            ms_tx = h->tune.ms_tx;
-            multiscale_fused_extent(xi.data(), yi.data(), dst_h, dst_w, ms_tx, &uh_max, &uw_max);
-            tx4 = ms_tx; uh4 = uh_max; uw4 = uw_max;
+            pl.tx = h->tune.ms_tx;
+            multiscale_fused_extent(xi.data(), yi.data(), dst_h, dst_w, pl.tx, &pl.uh_max, &pl.uw_max);
+            pl.tx4 = pl.tx; pl.uh4 = pl.uh_max; pl.uw4 = pl.uw_max;
         } else {
-            multiscale_fused_plan(xi.data(), yi.data(), dst_h, dst_w, up_ratio, &ms_tx, &uh_max, &uw_max);
-            multiscale_fused_plan_v4(xi.data(), yi.data(), dst_h, dst_w, up_ratio, &tx4, &uh4, &uw4);
+            multiscale_fused_plan(xi.data(), yi.data(), dst_h, dst_w, up_ratio, &pl.tx, &pl.uh_max, &pl.uw_max);
+            multiscale_fused_plan_v4(xi.data(), yi.data(), dst_h, dst_w, up_ratio, &pl.tx4, &pl.uh4, &pl.uw4);
         }
-        if (h->resize_tabs.size() >= 16) {               // bounded: drop the oldest geometry
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(h->resize_tabs.front().d);
-            h->resize_tabs.erase(h->resize_tabs.begin());
-        }
-        HIP_TRY(h, hipMalloc(&d_tabs, (nx + ny) * 8));
-        char* t0 = (char*)d_tabs;
-        HIP_TRY(h, hipMemcpy(t0, xi.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t0 + nx * 4, xw.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t0 + nx * 8, yi.data(), ny * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t0 + nx * 8 + ny * 4, yw.data(), ny * 4, hipMemcpyHostToDevice));
-        h->resize_tabs.push_back({cw, ch, dst_w, dst_h, d_tabs, 0.0, uh_max, uw_max, ms_tx, up_ratio, tx4, uh4, uw4});
+        rc = add_tab(h, h->resize_tabs, key, pl, {{xi.data(), nx}, {xw.data(), nx}, {yi.data(), ny}, {yw.data(), ny}}, &tab);
+        if (rc) return rc;
     }
-    char* t = (char*)d_tabs;
+    const lwp_context::MsPlan& pl = tab->plan;
+    char* t = tab->d.as<char>();
     int* d_xi = (int*)t; t += nx * 4;
     float* d_xw = (float*)t; t += nx * 4;
     int* d_yi = (int*)t; t += ny * 4;
@@ -1076,17 +1012,16 @@ extern "C" int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int ma
     bool fused = false;
     if (h->tune.ms_fused != 0 && h->tune.ms_vec != 0) {      // four channels per lane (LWP_MS_VEC=0: the scalar fused kernel)
         LAUNCH(h, KC_POST, launch_multiscale_fused_v4(v, N, C, up_ratio, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
-                                                      d_acc, tx4, uh4, uw4, h->stream, &fused));
+                                                      d_acc, pl.tx4, pl.uh4, pl.uw4, h->stream, &fused));
     }
     if (!fused && h->tune.ms_fused != 0) {                   // LWP_MS_FUSED=0: the two-kernel form (A/B, tests)
         LAUNCH(h, KC_POST, launch_multiscale_fused(v, N, C, up_ratio, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
-                                                   d_acc, ms_tx, uh_max, uw_max, h->stream, &fused));
+                                                   d_acc, pl.tx, pl.uh_max, pl.uw_max, h->stream, &fused));
     }
     if (!fused) {
-        rc = ensure_dev(h, &h->d_tmp2, &h->d_tmp2_bytes, ub);
-        if (rc) return rc;
-        LAUNCH(h, KC_POST, launch_upsample(v, N, C, up_ratio, h->d_tmp2, h->stream, &h->tune));
-        LAUNCH(h, KC_POST, launch_resize_accum(h->d_tmp2, N, Hs, Ws, C, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0, d_acc, h->stream));
+        HIP_TRY(h, h->d_tmp2.ensure(ub));
+        LAUNCH(h, KC_POST, launch_upsample(v, N, C, up_ratio, h->d_tmp2.as<float>(), h->stream, &h->tune));
+        LAUNCH(h, KC_POST, launch_resize_accum(h->d_tmp2.as<float>(), N, Hs, Ws, C, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0, d_acc, h->stream));
     }
     if (accum_mem == LWP_MEM_HOST) HIP_TRY(h, hipMemcpyAsync(accum, d_acc, ab, hipMemcpyDeviceToHost, h->stream));
     bool ordered = false;
@@ -1131,19 +1066,15 @@ static int upload_host(lwp_context* h, const void* src, size_t bytes, void* dst,
         const int k = h->pin_next;
         h->pin_next ^= 1;
         if (h->pin_busy[k]) { HIP_TRY(h, hipEventSynchronize(h->pin_ev[k])); h->pin_busy[k] = false; }
-        if (h->pin_bytes[k] < bytes) {
-            if (h->pin_buf[k]) HIP_TRY(h, hipHostFree(h->pin_buf[k]));
-            h->pin_buf[k] = nullptr; h->pin_bytes[k] = 0;
-            HIP_TRY(h, hipHostMalloc(&h->pin_buf[k], bytes, hipHostMallocDefault));
-            h->pin_bytes[k] = bytes;
-        }
-        if (!h->pin_ev[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->pin_ev[k], hipEventDisableTiming));
-        std::memcpy(h->pin_buf[k], src, bytes);
+        HIP_TRY(h, h->pin_buf[k].ensure(bytes));
+        HIP_TRY(h, h->pin_ev[k].ensure(hipEventDisableTiming));
+        void* pin = h->pin_buf[k].as<void>();
+        std::memcpy(pin, src, bytes);
         if (h->tune.host_fetch_dma == 1) {                   // LWP_HOST_FETCH_DMA=1: the copy engine instead of the fetch kernel (A/B)
-            HIP_TRY(h, hipMemcpyAsync(dst, h->pin_buf[k], bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, h->stream));
         } else {
             void* mapped = nullptr;
-            HIP_TRY(h, hipHostGetDevicePointer(&mapped, h->pin_buf[k], 0));
+            HIP_TRY(h, hipHostGetDevicePointer(&mapped, pin, 0));
             HIP_TRY(h, launch_fetch_host(mapped, dst, bytes, h->stream));
         }
         HIP_TRY(h, hipEventRecord(h->pin_ev[k], h->stream));
@@ -1151,9 +1082,17 @@ static int upload_host(lwp_context* h, const void* src, size_t bytes, void* dst,
         *consumed = true;
         return LWP_OK;
     }
-    if (!h->ev_copy) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
+    HIP_TRY(h, h->ev_copy.ensure(hipEventDisableTiming));
     HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(h->ev_copy, h->stream));
+    return LWP_OK;
+}
+
+// the shared staging of host frames (read on the main stream only)
+static int ensure_imgs_staging(lwp_context* h, size_t ib) {
+    if (h->d_imgs.size() >= ib) return LWP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, h->d_imgs.ensure(ib));
     return LWP_OK;
 }
 
@@ -1172,11 +1111,10 @@ extern "C" int lwp_preprocess_u8(lwp_handle h, const unsigned char* img, int img
     bool consumed = false;
     if (img_mem == LWP_MEM_HOST) {
         const size_t ib = (size_t)H * W * 3;
-        rc = ensure_dev(h, &h->d_img, &h->d_img_bytes, ib);
+        HIP_TRY(h, h->d_img.ensure(ib));
+        rc = upload_host(h, img, ib, h->d_img.as<unsigned char>(), &consumed);
         if (rc) return rc;
-        rc = upload_host(h, img, ib, h->d_img, &consumed);
-        if (rc) return rc;
-        d_src = (const unsigned char*)h->d_img;
+        d_src = h->d_img.as<unsigned char>();
     }
     const size_t nx = (size_t)dw * 4, ny = (size_t)dh * 4;
     if (h->pre_H != H || h->pre_W != W || h->pre_net_h != net_input_height) {   // tables depend on the geometry only
@@ -1184,16 +1122,15 @@ extern "C" int lwp_preprocess_u8(lwp_handle h, const unsigned char* img, int img
         build_resize_table_u8(W, dw, sc, xi, xw);
         build_resize_table_u8(H, dh, sc, yi, yw);
         HIP_TRY(h, hipStreamSynchronize(h->stream));                            // an earlier launch may still read the old tables
-        rc = ensure_dev(h, &h->d_pre_tab, &h->d_pre_tab_bytes, (nx + ny) * 8);
-        if (rc) return rc;
-        int* t = (int*)h->d_pre_tab;
+        HIP_TRY(h, h->d_pre_tab.ensure((nx + ny) * 8));
+        int* t = h->d_pre_tab.as<int>();
         HIP_TRY(h, hipMemcpy(t, xi.data(), nx * 4, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(t + nx, xw.data(), nx * 4, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(t + 2 * nx, yi.data(), ny * 4, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(t + 2 * nx + ny, yw.data(), ny * 4, hipMemcpyHostToDevice));
         h->pre_H = H; h->pre_W = W; h->pre_net_h = net_input_height;
     }
-    const int* t = (const int*)h->d_pre_tab;
+    const int* t = h->d_pre_tab.as<int>();
     PreprocParams p;
     p.src = d_src; p.Hs = H; p.Ws = W;
     p.xi = t; p.xw = t + nx; p.yi = t + 2 * nx; p.yw = t + 2 * nx + ny;
@@ -1266,40 +1203,24 @@ static int preprocess_scaled_impl(lwp_handle h, const void* imgs, int elem, int 
     bool consumed = false;
     if (img_mem == LWP_MEM_HOST) {
         const size_t ib = (size_t)N * H * W * 3 * elem;
-        if (h->d_imgs_bytes < ib) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            if (h->d_imgs) HIP_TRY(h, hipFree(h->d_imgs));
-            h->d_imgs = nullptr; h->d_imgs_bytes = 0;
-            HIP_TRY(h, hipMalloc((void**)&h->d_imgs, ib));
-            h->d_imgs_bytes = ib;
-        }
-        rc = upload_host(h, imgs, ib, h->d_imgs, &consumed);
+        rc = ensure_imgs_staging(h, ib);
         if (rc) return rc;
-        d_src = h->d_imgs;
+        rc = upload_host(h, imgs, ib, h->d_imgs.as<unsigned char>(), &consumed);
+        if (rc) return rc;
+        d_src = h->d_imgs.as<unsigned char>();
     }
     const size_t nx = (size_t)dw * 4, ny = (size_t)dh * 4;
-    void* d_tabs = nullptr;
-    for (const auto& rt : h->scale_tabs)
-        if (rt.cw == W && rt.ch == H && rt.dw == dw && rt.dh == dh && rt.ratio == ratio) { d_tabs = rt.d; break; }
-    if (!d_tabs) {                                       // per-geometry tables, uploaded once and kept
+    const lwp_context::TabKey key{W, H, dw, dh, ratio, 0};
+    lwp_context::ResizeTab* tab = find_tab(h->scale_tabs, key);
+    if (!tab) {                                          // per-geometry tables, uploaded once and kept
         std::vector<int> xi, yi;
         std::vector<float> xw, yw;
         build_resize_table_ratio(W, dw, ratio, xi, xw);
         build_resize_table_ratio(H, dh, ratio, yi, yw);
-        if (h->scale_tabs.size() >= 16) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(h->scale_tabs.front().d);
-            h->scale_tabs.erase(h->scale_tabs.begin());
-        }
-        HIP_TRY(h, hipMalloc(&d_tabs, (nx + ny) * 8));
-        char* t0 = (char*)d_tabs;
-        HIP_TRY(h, hipMemcpy(t0, xi.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t0 + nx * 4, xw.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t0 + nx * 8, yi.data(), ny * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t0 + nx * 8 + ny * 4, yw.data(), ny * 4, hipMemcpyHostToDevice));
-        h->scale_tabs.push_back({W, H, dw, dh, d_tabs, ratio});
+        rc = add_tab(h, h->scale_tabs, key, {}, {{xi.data(), nx}, {xw.data(), nx}, {yi.data(), ny}, {yw.data(), ny}}, &tab);
+        if (rc) return rc;
     }
-    char* t = (char*)d_tabs;
+    const char* t = tab->d.as<char>();
     PreScaleParams p;
     p.src = d_src; p.src_f32 = elem == 4; p.N = N; p.Hs = H; p.Ws = W;
     p.xi = (const int*)t; p.xw = (const float*)(t + nx * 4); p.yi = (const int*)(t + nx * 8); p.yw = (const float*)(t + nx * 8 + ny * 4);
@@ -1327,19 +1248,18 @@ extern "C" int lwp_extract_keypoints(lwp_handle h, float* heatmap, int H, int W,
     const size_t bytes = (size_t)H * W * sizeof(float);
     rc = ensure_host_stage(h, bytes + (size_t)h->caps.max_kpts * 12 + 64);
     if (rc) return rc;
-    rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, bytes);
-    if (rc) return rc;
-    float* hs = (float*)h->h_stage;
+    HIP_TRY(h, h->d_tmp.ensure(bytes));
+    float* hs = h->h_stage.as<float>();
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) hs[(size_t)y * W + x] = heatmap[y * row_stride + x * pix_stride];
-    HIP_TRY(h, hipMemcpyAsync(h->d_tmp, hs, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_tmp.as<float>(), hs, bytes, hipMemcpyHostToDevice, h->stream));
     LAUNCH(h, KC_POST, launch_reset_ws(1, h->ws, h->stream));
-    LAUNCH(h, KC_POST, launch_threshold_inplace(h->d_tmp, (int64_t)H * W, h->stream));
-    MapView v{h->d_tmp, 0, (int64_t)W, 1, 0, H, W};
+    LAUNCH(h, KC_POST, launch_threshold_inplace(h->d_tmp.as<float>(), (int64_t)H * W, h->stream));
+    MapView v{h->d_tmp.as<float>(), 0, (int64_t)W, 1, 0, H, W};
     LAUNCH(h, KC_POST, launch_find_peaks(v, 1, 1, 1, h->ws, h->stream, &h->tune));
     LAUNCH(h, KC_POST, launch_nms(1, 1, H, h->ws, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(hs, h->d_tmp, bytes, hipMemcpyDeviceToHost, h->stream));
-    int* h_xy = (int*)((char*)h->h_stage + bytes);
+    HIP_TRY(h, hipMemcpyAsync(hs, h->d_tmp.as<float>(), bytes, hipMemcpyDeviceToHost, h->stream));
+    int* h_xy = (int*)(h->h_stage.as<char>() + bytes);
     float* h_sc = (float*)(h_xy + (size_t)h->caps.max_kpts * 2);
     int n = 0;
     unsigned long long fl = 0;
@@ -1366,9 +1286,9 @@ static int fetch_results(lwp_context* h, int N, int* kpt_counts, double* kpts, i
     int rc = ensure_host_stage(h, result_layout(h->ws).bytes + 64);
     if (rc) return rc;
     h->stage_tail_N = 0;
-    HIP_TRY(h, launch_publish(N, h->ws, h->h_stage, h->stream));
+    HIP_TRY(h, launch_publish(N, h->ws, h->h_stage.as<void>(), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    rc = parse_results(h, h->ws, h->h_stage, N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
+    rc = parse_results(h, h->ws, h->h_stage.as<void>(), N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
     if (rc == LWP_OK && h->ws.tail && h->run_has_tail) h->stage_tail_N = N;
     return rc;
 }
@@ -1436,10 +1356,9 @@ extern "C" int lwp_group_keypoints(lwp_handle h, const double* kpts, const int* 
     const float* d_paf = pafs;
     if (pafs_mem == LWP_MEM_HOST) {
         const size_t pb = (size_t)H * W * NPc * sizeof(float);
-        rc = ensure_dev(h, &h->d_tmp2, &h->d_tmp2_bytes, pb);
-        if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_tmp2, pafs, pb, hipMemcpyHostToDevice, h->stream));
-        d_paf = h->d_tmp2;
+        HIP_TRY(h, h->d_tmp2.ensure(pb));
+        HIP_TRY(h, hipMemcpyAsync(h->d_tmp2.as<float>(), pafs, pb, hipMemcpyHostToDevice, h->stream));
+        d_paf = h->d_tmp2.as<float>();
     }
     h->run_has_tail = false;                           // entries only: lwp_get_poses has nothing to return after this call
     h->last_N = 1; h->async_pending = false;   // the workspace holds this one frame now (lwp_debug_post_counts reads it)
@@ -1468,18 +1387,21 @@ static int ensure_tail_state(lwp_context* h, int lanes) {
     if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
     const int keep = (t.P == P && t.K == K) ? t.lanes : 0;
     TailState n;
-    n.lanes = std::max(lanes, keep); n.P = P; n.K = K; n.vars = h->d_vars;
+    n.lanes = std::max(lanes, keep); n.P = P; n.K = K; n.vars = h->d_vars.as<float>();
     const size_t L = (size_t)n.lanes, PK2 = (size_t)P * K * 2;
-    struct Arr { void** dst; void* src; size_t per_lane; };
-    Arr arrs[] = {{(void**)&n.hdr, t.hdr, sizeof(int4)}, {(void**)&n.kp, t.kp, 2 * PK2 * 4}, {(void**)&n.bbox, t.bbox, (size_t)2 * P * 16},
-                  {(void**)&n.ids, t.ids, (size_t)2 * P * 4}, {(void**)&n.f_xprev, t.f_xprev, 2 * PK2 * 4}, {(void**)&n.f_init, t.f_init, 2 * PK2 * 4},
-                  {(void**)&n.f_dx, t.f_dx, 2 * PK2 * 8}, {(void**)&n.f_x, t.f_x, 2 * PK2 * 8}, {(void**)&n.sim, t.sim, (size_t)P * P}};
-    for (Arr& a : arrs) {
-        HIP_TRY(h, hipMalloc(a.dst, L * a.per_lane));
-        HIP_TRY(h, hipMemset(*a.dst, 0, L * a.per_lane));
-        if (keep && a.src) HIP_TRY(h, hipMemcpy(*a.dst, a.src, (size_t)keep * a.per_lane, hipMemcpyDeviceToDevice));
+    struct Arr { void** dst; size_t per_lane; };
+    Arr arrs[9] = {{(void**)&n.hdr, sizeof(int4)}, {(void**)&n.kp, 2 * PK2 * 4}, {(void**)&n.bbox, (size_t)2 * P * 16},
+                   {(void**)&n.ids, (size_t)2 * P * 4}, {(void**)&n.f_xprev, 2 * PK2 * 4}, {(void**)&n.f_init, 2 * PK2 * 4},
+                   {(void**)&n.f_dx, 2 * PK2 * 8}, {(void**)&n.f_x, 2 * PK2 * 8}, {(void**)&n.sim, (size_t)P * P}};
+    DevBuf fresh[9];                                   // the old arrays stay until all nine new ones exist
+    for (int i = 0; i < 9; ++i) {
+        const size_t bytes = L * arrs[i].per_lane;
+        HIP_TRY(h, fresh[i].ensure(bytes));
+        *arrs[i].dst = fresh[i].as<void>();
+        HIP_TRY(h, hipMemset(*arrs[i].dst, 0, bytes));
+        if (keep && h->tst_mem[i]) HIP_TRY(h, hipMemcpy(*arrs[i].dst, h->tst_mem[i].as<void>(), (size_t)keep * arrs[i].per_lane, hipMemcpyDeviceToDevice));
     }
-    free_tail_state(h, false);
+    for (int i = 0; i < 9; ++i) h->tst_mem[i] = std::move(fresh[i]);
     h->tst = n;
     HIP_TRY(h, launch_tail_reset(h->tst, keep, n.lanes - keep, h->tail_first_id, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1536,20 +1458,18 @@ static int enqueue_poses_chunk(lwp_context* h, const float* d_in, int N, int H, 
         const int nout = 2 * (1 + g.nref);
         std::vector<float*> outs(nout, nullptr);
         const size_t hb = (size_t)N * g.NH * fh * fw * sizeof(float), pb = (size_t)N * g.NP * fh * fw * sizeof(float);
-        int rc = ensure_dev(h, &h->d_maps[0], &h->d_maps_bytes[0], hb);
-        if (rc) return rc;
-        rc = ensure_dev(h, &h->d_maps[1], &h->d_maps_bytes[1], pb);
-        if (rc) return rc;
-        outs[nout - 2] = h->d_maps[0];
-        outs[nout - 1] = h->d_maps[1];
-        rc = enqueue_forward(h, d_in, N, H, W, outs.data());
+        HIP_TRY(h, h->d_maps[0].ensure(hb));
+        HIP_TRY(h, h->d_maps[1].ensure(pb));
+        outs[nout - 2] = h->d_maps[0].as<float>();
+        outs[nout - 1] = h->d_maps[1].as<float>();
+        const int rc = enqueue_forward(h, d_in, N, H, W, outs.data());
         if (rc || !with_post) return rc;
-        heat = nchw_view(h->d_maps[0], g.NH, fh, fw);
-        paf = nchw_view(h->d_maps[1], g.NP, fh, fw);
+        heat = nchw_view(h->d_maps[0].as<float>(), g.NH, fh, fw);
+        paf = nchw_view(h->d_maps[1].as<float>(), g.NP, fh, fw);
     } else {
         int rc = enqueue_forward(h, d_in, N, H, W, nullptr);
         if (rc || !with_post) return rc;
-        const float* cat = h->bufs[g.cat_buf];
+        const float* cat = h->bufs[g.cat_buf].as<float>();
         heat = MapView{cat + g.C, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
         paf = MapView{cat + g.C + g.NH, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
     }
@@ -1634,7 +1554,7 @@ static OverlayParams overlay_params(const lwp_context* h, const unsigned char* s
     OverlayParams p{};
     p.src = src; p.out = out; p.N = N; p.H = H; p.W = W;
     p.K = h->skel.K;
-    p.limbs = h->d_limbs;
+    p.limbs = h->d_limbs.as<int>();
     const int L = h->skel.L, nd = h->ovl.n_draw_limbs;
     p.n_limbs = nd < 0 ? std::max(L - 2, 0) : std::min(nd, L);      // -1: BODY_PARTS_KPT_IDS[:-2] (pose.py:51); a later, shorter skeleton clamps
     for (int c = 0; c < 3; ++c) { p.color[c] = h->ovl.color[c]; p.box_color[c] = h->ovl.box_color[c]; }
@@ -1646,28 +1566,13 @@ static OverlayParams overlay_params(const lwp_context* h, const unsigned char* s
 // post stream (this slot's last overlay) and the main stream (an lwp_get_overlay copy, the last upload)
 static int ensure_slot_overlay(lwp_context* h, lwp_context::Slot& sl, size_t bytes, bool host_frames) {
     const bool pinned = h->ovl.mode == 2;
-    if (sl.ov_bytes >= bytes && (!host_frames || sl.frames_bytes >= bytes) && (!pinned || sl.h_ov_bytes >= bytes)) return LWP_OK;
+    if (sl.ov.size() >= bytes && (!host_frames || sl.frames.size() >= bytes) && (!pinned || sl.h_ov.size() >= bytes)) return LWP_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->post_stream) HIP_TRY(h, hipStreamSynchronize(h->post_stream));
     sl.ov_N = 0;
-    if (sl.ov_bytes < bytes) {
-        if (sl.ov) HIP_TRY(h, hipFree(sl.ov));
-        sl.ov = nullptr; sl.ov_bytes = 0;
-        HIP_TRY(h, hipMalloc((void**)&sl.ov, bytes));
-        sl.ov_bytes = bytes;
-    }
-    if (host_frames && sl.frames_bytes < bytes) {
-        if (sl.frames) HIP_TRY(h, hipFree(sl.frames));
-        sl.frames = nullptr; sl.frames_bytes = 0;
-        HIP_TRY(h, hipMalloc((void**)&sl.frames, bytes));
-        sl.frames_bytes = bytes;
-    }
-    if (pinned && sl.h_ov_bytes < bytes) {
-        if (sl.h_ov) HIP_TRY(h, hipHostFree(sl.h_ov));
-        sl.h_ov = nullptr; sl.h_ov_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&sl.h_ov, bytes, hipHostMallocDefault));
-        sl.h_ov_bytes = bytes;
-    }
+    HIP_TRY(h, sl.ov.ensure(bytes));
+    if (host_frames) HIP_TRY(h, sl.frames.ensure(bytes));
+    if (pinned) HIP_TRY(h, sl.h_ov.ensure(bytes));
     return LWP_OK;
 }
 
@@ -1676,8 +1581,8 @@ static int ensure_slot_overlay(lwp_context* h, lwp_context::Slot& sl, size_t byt
 static int enqueue_slot_overlay(lwp_context* h, lwp_context::Slot& sl, const OverlayJob& job, int N, hipStream_t s) {
     const PostWorkspace& w = sl.ws;
     const size_t bytes = (size_t)N * job.H * job.W * 3;
-    if (!w.tail || !sl.ov || sl.ov_bytes < bytes) return fail(h, LWP_ERR_STATE, "overlay without its buffers or the pose tail");
-    OverlayParams p = overlay_params(h, job.src, sl.ov, N, job.H, job.W);
+    if (!w.tail || !sl.ov || sl.ov.size() < bytes) return fail(h, LWP_ERR_STATE, "overlay without its buffers or the pose tail");
+    OverlayParams p = overlay_params(h, job.src, sl.ov.as<unsigned char>(), N, job.H, job.W);
     const int P = w.caps.max_entries;
     p.n_poses = w.t_n; p.kp = w.t_kp; p.bbox = w.t_bbox;
     p.kp_stride = (int64_t)P * w.K * 2; p.bbox_stride = (int64_t)P * 4;
@@ -1685,8 +1590,8 @@ static int enqueue_slot_overlay(lwp_context* h, lwp_context::Slot& sl, const Ove
     LAUNCH_ON(h, s, KC_POST, launch_overlay(p, P, s));
     if (h->ovl.mode == 2) {
         void* mapped = nullptr;
-        HIP_TRY(h, hipHostGetDevicePointer(&mapped, sl.h_ov, 0));
-        HIP_TRY(h, launch_fetch_host(sl.ov, mapped, bytes, s));    // (the 16-byte copy kernel; here device -> pinned host)
+        HIP_TRY(h, hipHostGetDevicePointer(&mapped, sl.h_ov.as<void>(), 0));
+        HIP_TRY(h, launch_fetch_host(sl.ov.as<void>(), mapped, bytes, s));    // (the 16-byte copy kernel; here device -> pinned host)
     }
     sl.ov_N = N; sl.ov_H = job.H; sl.ov_W = job.W; sl.ov_mode = h->ovl.mode;
     return LWP_OK;
@@ -1705,53 +1610,43 @@ static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, i
     if (sl.pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
     sl.ov_N = 0;
     if (!h->post_stream) {
-        if (h->tune.post_stream == 0) h->post_stream = h->stream;
-        else HIP_TRY(h, hipStreamCreateWithFlags(&h->post_stream, hipStreamNonBlocking));
+        if (h->tune.post_stream != 0) HIP_TRY(h, h->post_own.ensure());
+        h->post_stream = h->tune.post_stream != 0 ? h->post_own : h->stream;
     }
-    if (!sl.ev_maps) {
-        HIP_TRY(h, hipEventCreateWithFlags(&sl.ev_maps, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
-    }
+    HIP_TRY(h, sl.ev_maps.ensure(hipEventDisableTiming));
+    HIP_TRY(h, sl.ev_done.ensure(hipEventDisableTiming));
     rc = ensure_activations(h, frames_per_pass(h, N, H, W), H, W);
     if (rc) return rc;
     rc = order_in(h);
     if (rc) return rc;
     if (sl.ws.caps.max_peaks != h->caps.max_peaks || sl.ws.caps.max_kpts != h->caps.max_kpts) sl.ws.N = 0;   // (re)allocate lazily
-    rc = ensure_ws_obj(h, sl.ws, N, h->post_stream);
+    rc = ensure_ws_obj(h, sl.ws, sl.ws_mem, N, h->post_stream);
     if (rc) return rc;
     const Graph& g = h->g;
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);               // three stride-2 stages: out = (in - 1) / 2 + 1 each
     const size_t hb = (size_t)N * g.NH * fh * fw * sizeof(float), pb = (size_t)N * g.NP * fh * fw * sizeof(float);
-    rc = ensure_dev(h, &sl.maps[0], &sl.maps_bytes[0], hb);
-    if (rc) return rc;
-    rc = ensure_dev(h, &sl.maps[1], &sl.maps_bytes[1], pb);
-    if (rc) return rc;
-    const size_t rb = result_layout(sl.ws).bytes;
-    if (sl.h_stage_bytes < rb) {
-        if (sl.h_stage) HIP_TRY(h, hipHostFree(sl.h_stage));
-        sl.h_stage = nullptr; sl.h_stage_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&sl.h_stage, rb, hipHostMallocDefault));
-        sl.h_stage_bytes = rb;
-    }
+    HIP_TRY(h, sl.maps[0].ensure(hb));
+    HIP_TRY(h, sl.maps[1].ensure(pb));
+    HIP_TRY(h, sl.h_stage.ensure(result_layout(sl.ws).bytes));
     // network on the main stream: the last stage's heads also write f32 NCHW maps into this slot
     const int nout = 2 * (1 + g.nref);
     std::vector<float*> outs(nout, nullptr);
     rc = for_each_pass(h, N, H, W, [&](int f0, int n) {   // one launch sequence unless a tensor would reach 2 GiB
-        outs[nout - 2] = sl.maps[0] + (size_t)f0 * g.NH * fh * fw;
-        outs[nout - 1] = sl.maps[1] + (size_t)f0 * g.NP * fh * fw;
+        outs[nout - 2] = sl.maps[0].as<float>() + (size_t)f0 * g.NH * fh * fw;
+        outs[nout - 1] = sl.maps[1].as<float>() + (size_t)f0 * g.NP * fh * fw;
         return enqueue_forward(h, in_device + (size_t)f0 * 3 * H * W, n, H, W, outs.data());
     });
     if (rc) return rc;
     HIP_TRY(h, hipEventRecord(sl.ev_maps, h->stream));
     // post-processing + result copy on the second stream
     if (h->post_stream != h->stream) HIP_TRY(h, hipStreamWaitEvent(h->post_stream, sl.ev_maps, 0));
-    rc = enqueue_grouping(h, nchw_view(sl.maps[0], g.NH, fh, fw), nchw_view(sl.maps[1], g.NP, fh, fw), N, ratio, demo, sl.ws, h->post_stream);
+    rc = enqueue_grouping(h, nchw_view(sl.maps[0].as<float>(), g.NH, fh, fw), nchw_view(sl.maps[1].as<float>(), g.NP, fh, fw), N, ratio, demo, sl.ws, h->post_stream);
     if (rc == LWP_OK) rc = enqueue_tail(h, sl.ws, N, ratio, h->post_stream, unmap);
     if (rc == LWP_OK && overlay) rc = enqueue_slot_overlay(h, sl, *overlay, N, h->post_stream);
     if (rc) return rc;
     sl.tail_N = sl.ws.tail ? N : 0;
-    HIP_TRY(h, launch_publish(N, sl.ws, sl.h_stage, h->post_stream));
+    HIP_TRY(h, launch_publish(N, sl.ws, sl.h_stage.as<void>(), h->post_stream));
     HIP_TRY(h, hipEventRecord(sl.ev_done, h->post_stream));
     sl.pending = true;
     sl.N = N;
@@ -1766,7 +1661,7 @@ extern "C" int lwp_pipeline_fetch(lwp_handle h, int slot, int* kpt_counts, doubl
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipEventSynchronize(sl.ev_done));
     sl.pending = false;
-    return parse_results(h, sl.ws, sl.h_stage, sl.N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
+    return parse_results(h, sl.ws, sl.h_stage.as<void>(), sl.N, kpt_counts, kpts, kpt_cap, entries, entry_cap, n_entries);
 }
 
 // ---------------------------------------------------------------------------------------------- batched uint8 front end
@@ -1793,38 +1688,17 @@ static int check_u8_batch_args(lwp_context* h, const void* imgs, int img_mem, in
 
 // device tables of a geometry, built and uploaded once and then only read
 static int pre_tables(lwp_context* h, int H, int W, const PreGeom& g, const int** tab) {
-    for (const auto& rt : h->pre_tabs)
-        if (rt.cw == W && rt.ch == H && rt.dw == g.dw && rt.dh == g.dh && rt.ratio == g.sc) { *tab = (const int*)rt.d; return LWP_OK; }
-    const size_t nx = (size_t)g.dw * 4, ny = (size_t)g.dh * 4;
-    std::vector<int> xi, xw, yi, yw;
-    build_resize_table_u8(W, g.dw, g.sc, xi, xw);
-    build_resize_table_u8(H, g.dh, g.sc, yi, yw);
-    if (h->pre_tabs.size() >= 16) {                      // bounded: drop the oldest geometry once nothing queued can read it
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->pre_tabs.front().d);
-        h->pre_tabs.erase(h->pre_tabs.begin());
+    const lwp_context::TabKey key{W, H, g.dw, g.dh, g.sc, 0};
+    lwp_context::ResizeTab* rt = find_tab(h->pre_tabs, key);
+    if (!rt) {
+        const size_t nx = (size_t)g.dw * 4, ny = (size_t)g.dh * 4;
+        std::vector<int> xi, xw, yi, yw;
+        build_resize_table_u8(W, g.dw, g.sc, xi, xw);
+        build_resize_table_u8(H, g.dh, g.sc, yi, yw);
+        int rc = add_tab(h, h->pre_tabs, key, {}, {{xi.data(), nx}, {xw.data(), nx}, {yi.data(), ny}, {yw.data(), ny}}, &rt);
+        if (rc) return rc;
     }
-    void* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, (nx + ny) * 8));
-    int* t = (int*)d;
-    hipError_t e = hipMemcpy(t, xi.data(), nx * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t + nx, xw.data(), nx * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t + 2 * nx, yi.data(), ny * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t + 2 * nx + ny, yw.data(), ny * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(h, LWP_ERR_HIP, std::string("hipMemcpy(resize tables): ") + hipGetErrorString(e)); }
-    h->pre_tabs.push_back({W, H, g.dw, g.dh, d, g.sc});
-    *tab = t;
-    return LWP_OK;
-}
-
-// the shared staging of host frames (read on the main stream only)
-static int ensure_imgs_staging(lwp_context* h, size_t ib) {
-    if (h->d_imgs_bytes >= ib) return LWP_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_imgs) HIP_TRY(h, hipFree(h->d_imgs));
-    h->d_imgs = nullptr; h->d_imgs_bytes = 0;
-    HIP_TRY(h, hipMalloc((void**)&h->d_imgs, ib));
-    h->d_imgs_bytes = ib;
+    *tab = rt->d.as<int>();
     return LWP_OK;
 }
 
@@ -1839,7 +1713,7 @@ static int enqueue_u8_batch(lwp_context* h, const unsigned char* imgs, int img_m
         const size_t ib = (size_t)N * H * W * 3;
         int rc = own_dst ? LWP_OK : ensure_imgs_staging(h, ib);
         if (rc) return rc;
-        unsigned char* dst = own_dst ? own_dst : h->d_imgs;
+        unsigned char* dst = own_dst ? own_dst : h->d_imgs.as<unsigned char>();
         rc = upload_host(h, imgs, ib, dst, consumed);
         if (rc) return rc;
         d_src = dst;
@@ -1904,10 +1778,9 @@ extern "C" int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, i
     rc = order_in(h);
     if (rc) return rc;
     const size_t xb = (size_t)N * 3 * g.Hp * g.Wp * sizeof(float);
-    if (h->d_pipe_in_bytes < xb) {                       // the network of the other slot may still read the old tensor
+    if (h->d_pipe_in.size() < xb) {                       // the network of the other slot may still read the old tensor
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        rc = ensure_dev(h, &h->d_pipe_in, &h->d_pipe_in_bytes, xb);
-        if (rc) return rc;
+        HIP_TRY(h, h->d_pipe_in.ensure(xb));
     }
     // with the overlay on, host frames are uploaded into a buffer of the SLOT: its overlay reads them on the post stream after
     // the next submit has overwritten the shared staging on the main stream
@@ -1918,13 +1791,13 @@ extern "C" int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, i
         if (rc) return rc;
     }
     bool consumed = true;
-    rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, h->d_pipe_in, &consumed, own ? sl.frames : nullptr);
+    rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, h->d_pipe_in.as<float>(), &consumed, own ? sl.frames.as<unsigned char>() : nullptr);
     if (rc) return rc;
     if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));    // (batches beyond the pinned staging limit: the copy is waited for)
     TailParams um = h->tail;                             // this submit's un-map, by value: the handle's lwp_set_unmap state is not touched
     um.stride = stride; um.scale = g.sc; um.pad_top = g.pad[0]; um.pad_left = g.pad[1];
-    const OverlayJob job{own ? sl.frames : imgs, H, W};
-    return pipeline_submit_impl(h, h->d_pipe_in, N, g.Hp, g.Wp, ratio, demo, slot, &um, overlay ? &job : nullptr);
+    const OverlayJob job{own ? sl.frames.as<unsigned char>() : imgs, H, W};
+    return pipeline_submit_impl(h, h->d_pipe_in.as<float>(), N, g.Hp, g.Wp, ratio, demo, slot, &um, overlay ? &job : nullptr);
 }
 
 extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float* paf, int mem, int layout, int N, int hs, int ws, int ratio,
@@ -1944,13 +1817,11 @@ extern "C" int lwp_poses_from_maps(lwp_handle h, const float* heat, const float*
     const size_t hb = (size_t)N * h->g.NH * hs * ws * sizeof(float), pb = (size_t)N * h->g.NP * hs * ws * sizeof(float);
     const float *d_heat = heat, *d_paf = paf;
     if (mem == LWP_MEM_HOST) {
-        rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, hb);
-        if (rc) return rc;
-        rc = ensure_dev(h, &h->d_tmp2, &h->d_tmp2_bytes, pb);
-        if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_tmp, heat, hb, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->d_tmp2, paf, pb, hipMemcpyHostToDevice, h->stream));
-        d_heat = h->d_tmp; d_paf = h->d_tmp2;
+        HIP_TRY(h, h->d_tmp.ensure(hb));
+        HIP_TRY(h, h->d_tmp2.ensure(pb));
+        HIP_TRY(h, hipMemcpyAsync(h->d_tmp.as<float>(), heat, hb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_tmp2.as<float>(), paf, pb, hipMemcpyHostToDevice, h->stream));
+        d_heat = h->d_tmp.as<float>(); d_paf = h->d_tmp2.as<float>();
     }
     MapView hv = nchw_view(d_heat, h->g.NH, hs, ws), pv = nchw_view(d_paf, h->g.NP, hs, ws);
     if (layout == LWP_LAYOUT_NHWC) {                 // the averaged maps of val.infer are H x W x C
@@ -2003,13 +1874,10 @@ extern "C" int lwp_set_tracking(lwp_handle h, int mode, int match_threshold, dou
             vars[k] = t * t;
             if (!(vars[k] > 0.f)) return fail(h, LWP_ERR_ARG, "sigmas must be positive");
         }
-        if (!h->d_vars) HIP_TRY(h, hipMalloc((void**)&h->d_vars, kMaxSkelTypes * sizeof(float)));
-        HIP_TRY(h, hipMemcpy(h->d_vars, vars, sizeof vars, hipMemcpyHostToDevice));
+        HIP_TRY(h, h->d_vars.ensure(kMaxSkelTypes * sizeof(float)));
+        HIP_TRY(h, hipMemcpy(h->d_vars.as<float>(), vars, sizeof vars, hipMemcpyHostToDevice));
     }
-    if ((mode != 0) != (h->tail.mode != 0)) {          // the result block gains or loses its tail section: re-allocated lazily
-        free_ws(h);
-        for (auto& sl : h->slots) free_ws_obj(sl.ws);
-    }
+    if ((mode != 0) != (h->tail.mode != 0)) free_workspaces(h);   // the result block gains or loses its tail section: re-allocated lazily
     free_tail_state(h);                                // every lane starts over
     h->last_N = 0; h->async_pending = false;
     h->tail_first_id = 0;
@@ -2056,10 +1924,10 @@ static TailHost tail_host(const PostWorkspace& ws, const void* host_block) {
 }
 static int tail_source(lwp_context* h, int slot, const PostWorkspace** ws, const void** block, int* N) {
     if (slot < -1 || slot > 1) return fail(h, LWP_ERR_ARG, "slot must be -1 (the last serial call), 0 or 1");
-    if (slot < 0) { *ws = &h->ws; *block = h->h_stage; *N = h->stage_tail_N; }
+    if (slot < 0) { *ws = &h->ws; *block = h->h_stage.as<void>(); *N = h->stage_tail_N; }
     else {
         if (h->slots[slot].pending) return fail(h, LWP_ERR_STATE, "slot still pending: call lwp_pipeline_fetch first");
-        *ws = &h->slots[slot].ws; *block = h->slots[slot].h_stage; *N = h->slots[slot].tail_N;
+        *ws = &h->slots[slot].ws; *block = h->slots[slot].h_stage.as<void>(); *N = h->slots[slot].tail_N;
     }
     if (*N <= 0 || !(*ws)->tail || !*block) return fail(h, LWP_ERR_STATE, "no pose rows: the pose tail was off for that run (lwp_set_tracking), or nothing was fetched");
     return LWP_OK;
@@ -2133,9 +2001,9 @@ extern "C" int lwp_track_poses(lwp_handle h, int lane, int n, const int* keypoin
     p.mode = 3;                                        // one frame of one lane
     HIP_TRY(h, launch_tail_rows(1, h->ws, p, 1, h->stream));
     HIP_TRY(h, launch_tail_track(1, h->ws, h->tst, p, lane, h->stream));
-    HIP_TRY(h, launch_publish(1, h->ws, h->h_stage, h->stream));
+    HIP_TRY(h, launch_publish(1, h->ws, h->h_stage.as<void>(), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const TailHost t = tail_host(h->ws, h->h_stage);
+    const TailHost t = tail_host(h->ws, h->h_stage.as<void>());
     if (n > 0) {
         std::memcpy(out_keypoints, t.kp, (size_t)n * K * 2 * sizeof(int));
         std::memcpy(out_bbox, t.bbox, (size_t)n * 4 * sizeof(int));
@@ -2182,13 +2050,13 @@ extern "C" int lwp_get_overlay(lwp_handle h, int slot, unsigned char* dst, int d
     const size_t bytes = (size_t)N * H * W * 3;
     HIP_TRY(h, hipSetDevice(h->device));
     if (dst_mem == LWP_MEM_HOST) {                     // the fetch has waited for the slot's stream: both copies are complete
-        if (sl.ov_mode == 2) std::memcpy(dst, sl.h_ov, bytes);
-        else HIP_TRY(h, hipMemcpy(dst, sl.ov, bytes, hipMemcpyDeviceToHost));
+        if (sl.ov_mode == 2) std::memcpy(dst, sl.h_ov.as<void>(), bytes);
+        else HIP_TRY(h, hipMemcpy(dst, sl.ov.as<void>(), bytes, hipMemcpyDeviceToHost));
         return LWP_OK;
     }
     int rc = order_in(h);                              // dst last used on the caller's stream
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dst, sl.ov, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst, sl.ov.as<void>(), bytes, hipMemcpyDeviceToDevice, h->stream));
     bool ordered = false;
     rc = order_out(h, h->stream, &ordered);
     if (rc) return rc;
@@ -2224,13 +2092,12 @@ extern "C" int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_m
     const size_t K = (size_t)h->skel.K, ib = (size_t)N * H * W * 3;
     // the pose arrays in one device buffer: [n_poses | key-points | boxes], each section 16-byte aligned
     const size_t nb = ((size_t)N * 4 + 15) & ~(size_t)15, kb = ((size_t)N * pose_cap * K * 2 * 4 + 15) & ~(size_t)15, bb = (size_t)N * pose_cap * 4 * 4;
-    if (h->d_ov_pose_bytes < nb + kb + bb + 16 || (out_mem == LWP_MEM_HOST && h->d_ov_out_bytes < ib)) {
+    if (h->d_ov_pose.size() < nb + kb + bb + 16 || (out_mem == LWP_MEM_HOST && h->d_ov_out.size() < ib)) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffers
-        rc = ensure_dev(h, &h->d_ov_pose, &h->d_ov_pose_bytes, nb + kb + bb + 16);
-        if (rc == LWP_OK && out_mem == LWP_MEM_HOST) rc = ensure_dev(h, &h->d_ov_out, &h->d_ov_out_bytes, ib);
-        if (rc) return rc;
+        HIP_TRY(h, h->d_ov_pose.ensure(nb + kb + bb + 16));
+        if (out_mem == LWP_MEM_HOST) HIP_TRY(h, h->d_ov_out.ensure(ib));
     }
-    char* dp = (char*)h->d_ov_pose;
+    char* dp = h->d_ov_pose.as<char>();
     HIP_TRY(h, hipMemcpyAsync(dp, n_poses, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
     if (most > 0) {
         HIP_TRY(h, hipMemcpyAsync(dp + nb, keypoints, (size_t)N * pose_cap * K * 2 * 4, hipMemcpyHostToDevice, h->stream));
@@ -2241,12 +2108,12 @@ extern "C" int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_m
     if (img_mem == LWP_MEM_HOST) {
         bool consumed = true;
         rc = ensure_imgs_staging(h, ib);
-        if (rc == LWP_OK) rc = upload_host(h, imgs, ib, h->d_imgs, &consumed);
+        if (rc == LWP_OK) rc = upload_host(h, imgs, ib, h->d_imgs.as<unsigned char>(), &consumed);
         if (rc) return rc;
         if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
-        d_src = h->d_imgs;
+        d_src = h->d_imgs.as<unsigned char>();
     }
-    unsigned char* d_out = out_mem == LWP_MEM_HOST ? (unsigned char*)h->d_ov_out : out;
+    unsigned char* d_out = out_mem == LWP_MEM_HOST ? h->d_ov_out.as<unsigned char>() : out;
     OverlayParams p = overlay_params(h, d_src, d_out, N, H, W);
     p.n_poses = (const int*)dp; p.kp = (const int*)(dp + nb); p.bbox = (const int*)(dp + nb + kb);
     p.kp_stride = (int64_t)pose_cap * (int64_t)K * 2; p.bbox_stride = (int64_t)pose_cap * 4;
@@ -2322,12 +2189,11 @@ static int train_targets_prepare(lwp_handle h, const double* kpts, int kpts_mem,
     if (rc) return rc;
     // [n_persons | key-points]: the counts always travel, the key-points only from host memory
     const size_t nb = ((size_t)N * 4 + 15) & ~(size_t)15, kb = kpts_mem == LWP_MEM_HOST ? kd * sizeof(double) : 0;
-    if (h->d_train_bytes < nb + kb + 16) {
+    if (h->d_train.size() < nb + kb + 16) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
-        rc = ensure_dev(h, &h->d_train, &h->d_train_bytes, nb + kb + 16);
-        if (rc) return rc;
+        HIP_TRY(h, h->d_train.ensure(nb + kb + 16));
     }
-    char* dp = (char*)h->d_train;
+    char* dp = h->d_train.as<char>();
     HIP_TRY(h, hipMemcpyAsync(dp, n_persons, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
     if (kb && most > 0) HIP_TRY(h, hipMemcpyAsync(dp + nb, kpts, kb, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // the caller's arrays are free from here on
@@ -2335,7 +2201,7 @@ static int train_targets_prepare(lwp_handle h, const double* kpts, int kpts_mem,
     p.kpts = kpts_mem == LWP_MEM_HOST ? (const double*)(dp + nb) : kpts;
     p.n_persons = (const int*)dp;
     p.Pmax = most > 0 ? Pmax : 0; p.K = K; p.L = L;
-    p.limbs = h->d_limbs;
+    p.limbs = h->d_limbs.as<int>();
     p.h = H / stride; p.w = W / stride; p.stride = stride;
     p.sigma = sigma; p.thickness = paf_thickness;
     p.keypoint_maps = keypoint_maps_device; p.paf_maps = paf_maps_device;
@@ -2376,14 +2242,13 @@ extern "C" int lwp_mask_downsample(lwp_handle h, const float* mask, int mem, int
     const float* d_src = mask;
     if (mem == LWP_MEM_HOST) {
         const size_t mb = (size_t)N * H * W * sizeof(float);
-        if (h->d_train_bytes < mb) {
+        if (h->d_train.size() < mb) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            rc = ensure_dev(h, &h->d_train, &h->d_train_bytes, mb);
-            if (rc) return rc;
+            HIP_TRY(h, h->d_train.ensure(mb));
         }
-        HIP_TRY(h, hipMemcpyAsync(h->d_train, mask, mb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_train.as<float>(), mask, mb, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        d_src = h->d_train;
+        d_src = h->d_train.as<float>();
     }
     LAUNCH(h, KC_OTHER, launch_mask_downsample(d_src, N, H, W, stride, out_device, h->stream));
     bool ordered = false;
@@ -2420,10 +2285,9 @@ static int stage_losses_prepare(lwp_handle h, const float* const* outs, int n_ou
     if (rc) return rc;
     const int blocks = stage_loss_blocks(N, hs * ws);
     const size_t need = ((size_t)kLossMaxOuts * blocks + S) * sizeof(double);
-    if (h->d_loss_bytes < need) {
+    if (h->d_loss.size() < need) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        rc = ensure_dev(h, &h->d_loss, &h->d_loss_bytes, need);
-        if (rc) return rc;
+        HIP_TRY(h, h->d_loss.ensure(need));
     }
     return LWP_OK;
 }
@@ -2433,7 +2297,7 @@ static int enqueue_stage_losses(lwp_handle h, const float* const* outs, const fl
                                 const float* mask, int N, int hs, int ws, int batch_size) {
     const int S = 2 * (h->g.nref + 1);
     const int blocks = stage_loss_blocks(N, hs * ws);
-    double* d_partials = (double*)h->d_loss;
+    double* d_partials = h->d_loss.as<double>();
     double* d_losses = d_partials + (size_t)kLossMaxOuts * blocks;
     for (int s0 = 0; s0 < S; s0 += kLossMaxOuts) {       // one launch up to 16 tensors (7 refinement stages); each launch reads the targets once
         StageLossParams p{};
@@ -2455,7 +2319,7 @@ extern "C" int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_ou
     rc = enqueue_stage_losses(h, outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size);
     if (rc) return rc;
     const int S = 2 * (h->g.nref + 1);
-    const double* d_losses = (const double*)h->d_loss + (size_t)kLossMaxOuts * stage_loss_blocks(N, hs * ws);
+    const double* d_losses = h->d_loss.as<double>() + (size_t)kLossMaxOuts * stage_loss_blocks(N, hs * ws);
     HIP_TRY(h, hipMemcpyAsync(losses_host, d_losses, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return LWP_OK;
@@ -2471,19 +2335,15 @@ static int ensure_train_buffers(lwp_context* h, int N, int H, int W) {
     bool synced = false;
     for (size_t i = 0; i < h->tp.bufs.size(); ++i) {
         const size_t bytes = (size_t)N * fh * fw * h->tp.bufs[i].channels * sizeof(float);
-        const bool grow = bytes > h->tbuf_bytes[i];
+        const bool grow = bytes > h->tbufs[i].size() || bytes > h->gbufs[i].size();
         if (grow) {
             if (!synced) { HIP_TRY(h, hipStreamSynchronize(h->stream)); synced = true; }
-            if (h->tbufs[i]) { HIP_TRY(h, hipFree(h->tbufs[i])); h->tbufs[i] = nullptr; }
-            if (h->gbufs[i]) { HIP_TRY(h, hipFree(h->gbufs[i])); h->gbufs[i] = nullptr; }
-            h->tbuf_bytes[i] = 0;
-            HIP_TRY(h, hipMalloc((void**)&h->tbufs[i], bytes));
-            HIP_TRY(h, hipMalloc((void**)&h->gbufs[i], bytes));
-            h->tbuf_bytes[i] = bytes;
+            HIP_TRY(h, h->tbufs[i].ensure(bytes));
+            HIP_TRY(h, h->gbufs[i].ensure(bytes));
         }
         // pad channels of a concat buffer are read with zero weights: finite at every geometry (as in ensure_activations)
         if (h->tp.bufs[i].has_pad && (grow || N != h->train_N || H != h->train_H || W != h->train_W))
-            HIP_TRY(h, hipMemsetAsync(h->tbufs[i], 0, bytes, h->stream));
+            HIP_TRY(h, hipMemsetAsync(h->tbufs[i].as<void>(), 0, bytes, h->stream));
     }
     return LWP_OK;
 }
@@ -2535,7 +2395,7 @@ extern "C" int lwp_train_forward(lwp_handle h, const float* in_device, int N, in
         if (rc) { h->cur_layer = -1; return rc; }
         if ((int)i == tp.cpm_conv)             // every refinement stage reads [features | heat | paf] of a buffer of its own
             for (int k = 1; k < h->g.nref; ++k)
-                LAUNCH(h, KC_OTHER, launch_grad_add(h->tbufs[tp.cats[k] - nb], catc, h->tbufs[tp.cats[0] - nb], catc, M3, C, 0, h->stream));
+                LAUNCH(h, KC_OTHER, launch_grad_add(h->tbufs[tp.cats[k] - nb].as<float>(), catc, h->tbufs[tp.cats[0] - nb].as<float>(), catc, M3, C, 0, h->stream));
     }
     h->cur_layer = -1;
     h->train_N = N; h->train_H = H; h->train_W = W;
@@ -2543,7 +2403,7 @@ extern "C" int lwp_train_forward(lwp_handle h, const float* in_device, int N, in
     return order_out(h, h->stream, &ordered);
 }
 
-static float* grad_at(lwp_context* h, const BufRef& r) { return h->gbufs[r.buf - (int)h->g.bufs.size()] + r.coff; }
+static float* grad_at(lwp_context* h, const BufRef& r) { return h->gbufs[r.buf - (int)h->g.bufs.size()].as<float>() + r.coff; }
 
 struct BackwardArgs {
     const float* keypoint_maps; const float* paf_maps; const float* mask;
@@ -2590,10 +2450,9 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     part = (part + 63) / 64 * 64;
     h->bwd_fold_off = part;
     const size_t need = (part + fold) * sizeof(float);
-    if (h->d_bwd_bytes < need) {
+    if (h->d_bwd.size() < need) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        rc = ensure_dev(h, &h->d_bwd, &h->d_bwd_bytes, need);
-        if (rc) return rc;
+        HIP_TRY(h, h->d_bwd.ensure(need));
     }
     return order_in(h);
 }
@@ -2603,7 +2462,7 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
 static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const float* x, int x_ld, int cout, int cin,
                          const std::string& conv_key, const BackwardArgs& a, size_t fold_off) {
     WgradParams w{};
-    w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd;
+    w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd.as<float>();
     w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = l.ks; w.dil = l.dil;
     wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, l.ks, &w.splits, &w.chunk);
     h->bwd_splits[layer_index] = w.splits;
@@ -2614,14 +2473,14 @@ static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const 
         LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, dw, db, a.accumulate, h->stream));
         return LWP_OK;
     }
-    float* G = h->d_bwd + fold_off;
+    float* G = h->d_bwd.as<float>() + fold_off;
     float* g = G + (size_t)cout * cin * l.ks * l.ks;
     LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, G, g, 0, h->stream));
     BnChainParams b{};
     b.G = G; b.g = g;
-    b.W = h->d_raw + h->raw_off.at(conv_key + ".weight"); b.b = h->d_raw + h->raw_off.at(conv_key + ".bias");
-    b.gamma = h->d_raw + h->raw_off.at(l.bn_key + ".weight");
-    b.mean = h->d_raw + h->raw_off.at(l.bn_key + ".running_mean"); b.var = h->d_raw + h->raw_off.at(l.bn_key + ".running_var");
+    b.W = h->raw(conv_key + ".weight"); b.b = h->raw(conv_key + ".bias");
+    b.gamma = h->raw(l.bn_key + ".weight");
+    b.mean = h->raw(l.bn_key + ".running_mean"); b.var = h->raw(l.bn_key + ".running_var");
     b.dW = dw; b.db = db;
     b.dgamma = a.grads + h->grad_off.at(l.bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(l.bn_key + ".bias");
     b.cout = cout; b.K = cin * l.ks * l.ks; b.accumulate = a.accumulate;
@@ -2645,8 +2504,8 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
         for (int s = 0; s < p.S; ++s) {
             const int st = (s0 + s) / 2;
             const int coff = C + (((s0 + s) & 1) ? NH : 0);
-            p.outs[s] = h->tbufs[tp.cats[st] - nb] + coff;
-            p.dst[s] = h->gbufs[tp.cats[st] - nb] + coff;
+            p.outs[s] = h->tbufs[tp.cats[st] - nb].as<float>() + coff;
+            p.dst[s] = h->gbufs[tp.cats[st] - nb].as<float>() + coff;
         }
         p.ld = catc;
         p.keypoint_maps = a.keypoint_maps; p.paf_maps = a.paf_maps; p.mask = a.mask;
@@ -2678,7 +2537,7 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
         if (rc) { h->cur_layer = -1; return rc; }
         const bool is_cat = std::find(tp.cats.begin(), tp.cats.end(), l.src.buf) != tp.cats.end();
         DgradParams d{};
-        d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->d_blob + l.w_off;
+        d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->blob(l.w_off);
         d.dx = grad_at(h, l.src); d.dx_ld = l.src.ld;
         d.N = a.N; d.H = a.hs; d.W = a.ws;
         d.cout = l.cout; d.cout_pad = l.cout_pad; d.cin = l.cin; d.cin_pad = l.cin_pad; d.ks = l.ks; d.dil = l.dil;
@@ -2690,9 +2549,9 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
     h->cur_layer = -1;
     // 3. backbone_features feeds the initial stage and every refinement stage: stage order, then NCHW
     if (a.d_features) {
-        float* g0 = h->gbufs[tp.cats[0] - nb];
+        float* g0 = h->gbufs[tp.cats[0] - nb].as<float>();
         for (int k = 1; k < g.nref; ++k)
-            LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(g0, catc, h->gbufs[tp.cats[k] - nb], catc, M, C, 1, h->stream));
+            LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(g0, catc, h->gbufs[tp.cats[k] - nb].as<float>(), catc, M, C, 1, h->stream));
         LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(g0, catc, a.d_features, a.N, a.hs * a.ws, C, h->stream));
     }
     return LWP_OK;
@@ -2768,10 +2627,9 @@ extern "C" int lwp_debug_train_activation(lwp_handle h, int idx, float* dst, siz
     level_dims(h->train_H, h->train_W, 3, &dh, &dw);
     const size_t n = (size_t)h->train_N * l.cout * dh * dw;
     if (dst_floats < n) return fail(h, LWP_ERR_ARG, "dst too small");
-    rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, n * sizeof(float));
-    if (rc) return rc;
-    HIP_TRY(h, launch_nchw_from_nhwc(buf_at(h, l.dst), l.dst.ld, h->d_tmp, h->train_N, dh * dw, l.cout, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dst, h->d_tmp, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, h->d_tmp.ensure(n * sizeof(float)));
+    HIP_TRY(h, launch_nchw_from_nhwc(buf_at(h, l.dst), l.dst.ld, h->d_tmp.as<float>(), h->train_N, dh * dw, l.cout, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst, h->d_tmp.as<float>(), n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     out_dims[0] = h->train_N; out_dims[1] = l.cout; out_dims[2] = dh; out_dims[3] = dw;
     return LWP_OK;
@@ -2868,19 +2726,13 @@ static int ensure_adam_tables(lwp_context* h) {
         blocks += (uint32_t)(r.taps * (l.cin_pad / 32) * (l.cout_pad / 32));
         tab.push_back(r);
     }
-    RepackLayer* d_tab = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d_tab, std::max<size_t>(tab.size(), 1) * sizeof(RepackLayer)));
-    hipError_t e = hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(RepackLayer), hipMemcpyHostToDevice);
-    AdamChunk* d_chunks = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void**)&d_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(AdamChunk));
-    if (e == hipSuccess) e = hipMemcpy(d_chunks, chunks.data(), chunks.size() * sizeof(AdamChunk), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d_tab);
-        if (d_chunks) (void)hipFree(d_chunks);
-        return fail(h, LWP_ERR_HIP, std::string("stage optimiser tables: ") + hipGetErrorString(e));
-    }
-    h->d_repack = d_tab; h->repack_layers = (int)tab.size(); h->repack_blocks = (int)blocks;
-    h->d_adam_chunks = d_chunks; h->adam_chunks = (int)chunks.size();
+    DevBuf d_tab, d_chunks;                            // the handle takes them once both are uploaded
+    HIP_TRY(h, d_tab.ensure(std::max<size_t>(tab.size(), 1) * sizeof(RepackLayer)));
+    HIP_TRY(h, hipMemcpy(d_tab.as<void>(), tab.data(), tab.size() * sizeof(RepackLayer), hipMemcpyHostToDevice));
+    HIP_TRY(h, d_chunks.ensure(std::max<size_t>(chunks.size(), 1) * sizeof(AdamChunk)));
+    HIP_TRY(h, hipMemcpy(d_chunks.as<void>(), chunks.data(), chunks.size() * sizeof(AdamChunk), hipMemcpyHostToDevice));
+    h->d_repack = std::move(d_tab); h->repack_layers = (int)tab.size(); h->repack_blocks = (int)blocks;
+    h->d_adam_chunks = std::move(d_chunks); h->adam_chunks = (int)chunks.size();
     return LWP_OK;
 }
 
@@ -2889,8 +2741,8 @@ static int ensure_adam_state(lwp_context* h) {
     if (h->d_adam) return LWP_OK;
     h->adam_sq_off = (h->grad_floats + 3) / 4 * 4;
     const size_t bytes = std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float);
-    HIP_TRY(h, hipMalloc((void**)&h->d_adam, bytes));
-    HIP_TRY(h, hipMemsetAsync(h->d_adam, 0, bytes, h->stream));
+    HIP_TRY(h, h->d_adam.ensure(bytes));
+    HIP_TRY(h, hipMemsetAsync(h->d_adam.as<float>(), 0, bytes, h->stream));
     h->adam_t = 0;
     return LWP_OK;
 }
@@ -2910,7 +2762,7 @@ static int adam_args_check(lwp_context* h, const AdamArgs& a) {
 static AdamParams adam_params(lwp_context* h, const AdamArgs& a, int64_t t, float* raw, float* state) {
     AdamParams p{};
     p.grads = a.grads; p.raw = raw; p.exp_avg = state; p.exp_avg_sq = state + h->adam_sq_off;
-    p.chunks = h->d_adam_chunks; p.n_chunks = h->adam_chunks;
+    p.chunks = h->d_adam_chunks.as<AdamChunk>(); p.n_chunks = h->adam_chunks;
     p.vec_ok = (((uintptr_t)p.grads | (uintptr_t)p.raw | (uintptr_t)p.exp_avg | (uintptr_t)p.exp_avg_sq) & 15) == 0;
     const double bc1 = 1.0 - std::pow(a.beta1, (double)t), bc2 = 1.0 - std::pow(a.beta2, (double)t);
     for (int k = 0; k < 4; ++k) p.step_size[k] = a.base_lr * (double)(1 << k) / bc1;
@@ -2937,11 +2789,11 @@ extern "C" int lwp_stage_adam_step(lwp_handle h, const float* grads_device, doub
     if (!rc) rc = ensure_adam_state(h);
     if (!rc) rc = order_in(h);
     if (rc) return rc;
-    const AdamParams p = adam_params(h, a, h->adam_t + 1, h->d_raw, h->d_adam);
+    const AdamParams p = adam_params(h, a, h->adam_t + 1, h->d_raw.as<float>(), h->d_adam.as<float>());
     LAUNCH(h, KC_OTHER, launch_stage_adam(p, h->stream));
     h->adam_t += 1;                                    // from here on the raw parameters and the state are those of step t
     h->train_N = 0;                                    // the retained activations belong to the old weights
-    const hipError_t e = launch_stage_repack(h->d_repack, h->repack_layers, h->repack_blocks, h->d_raw, h->d_blob, h->stream);
+    const hipError_t e = launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
     if (e != hipSuccess) {                             // the blob no longer matches the raw parameters: no forward until lwp_load_weights
         h->weights_loaded = false;
         return fail(h, LWP_ERR_HIP, std::string("launch_stage_repack: ") + hipGetErrorString(e) + " (the weight blob is stale: load the weights again)");
@@ -2960,7 +2812,7 @@ extern "C" int lwp_stage_params_get(lwp_handle h, float* flat_device) {
     for (const auto& s : h->gspec) {                   // gradient-spec offset <- raw offset, entry by entry
         size_t n = 1;
         for (int d = 0; d < s.ndim; ++d) n *= (size_t)s.shape[d];
-        HIP_TRY(h, hipMemcpyAsync(flat_device + s.off, h->d_raw + h->raw_off.at(s.key), n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(flat_device + s.off, h->raw(s.key), n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     }
     bool ordered = false;
     rc = order_out(h, h->stream, &ordered);
@@ -2978,8 +2830,8 @@ extern "C" int lwp_stage_adam_state_get(lwp_handle h, float* exp_avg_device, flo
     if (rc) return rc;
     const size_t bytes = h->grad_floats * sizeof(float);
     if (h->d_adam) {
-        HIP_TRY(h, hipMemcpyAsync(exp_avg_device, h->d_adam, bytes, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(exp_avg_sq_device, h->d_adam + h->adam_sq_off, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(exp_avg_device, h->d_adam.as<float>(), bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(exp_avg_sq_device, h->d_adam.as<float>() + h->adam_sq_off, bytes, hipMemcpyDeviceToDevice, h->stream));
     } else {
         HIP_TRY(h, hipMemsetAsync(exp_avg_device, 0, bytes, h->stream));
         HIP_TRY(h, hipMemsetAsync(exp_avg_sq_device, 0, bytes, h->stream));
@@ -3002,8 +2854,8 @@ extern "C" int lwp_stage_adam_state_set(lwp_handle h, const float* exp_avg_devic
     if (!rc) rc = order_in(h);
     if (rc) return rc;
     const size_t bytes = h->grad_floats * sizeof(float);
-    HIP_TRY(h, hipMemcpyAsync(h->d_adam, exp_avg_device, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_adam + h->adam_sq_off, exp_avg_sq_device, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_adam.as<float>(), exp_avg_device, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_adam.as<float>() + h->adam_sq_off, exp_avg_sq_device, bytes, hipMemcpyDeviceToDevice, h->stream));
     h->adam_t = step;
     bool ordered = false;
     rc = order_out(h, h->stream, &ordered);            // the caller may free or overwrite its arrays once its stream gets here
@@ -3020,7 +2872,7 @@ extern "C" int lwp_stage_adam_reset(lwp_handle h) {
     HIP_TRY(h, hipSetDevice(h->device));
     rc = order_in(h);                                  // the caller may still read an array lwp_stage_adam_state_get handed over
     if (rc) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->d_adam, 0, std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_adam.as<float>(), 0, std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float), h->stream));
     return LWP_OK;
 }
 
@@ -3038,24 +2890,21 @@ extern "C" int lwp_time_stage_adam_step(lwp_handle h, const float* grads_device,
     rc = ensure_adam_tables(h);
     if (rc) return rc;
     if (!h->adam_sq_off) h->adam_sq_off = (h->grad_floats + 3) / 4 * 4;
-    struct Scratch {
-        float *raw = nullptr, *state = nullptr, *blob = nullptr;
-        ~Scratch() { for (float* p : {raw, state, blob}) if (p) (void)hipFree(p); }
-    } sc;
+    DevBuf raw, state, blob;
     const size_t state_bytes = std::max<size_t>(2 * h->adam_sq_off, 4) * sizeof(float);
-    HIP_TRY(h, hipMalloc((void**)&sc.raw, std::max<size_t>(h->raw_floats, 1) * sizeof(float)));
-    HIP_TRY(h, hipMalloc((void**)&sc.state, state_bytes));
-    HIP_TRY(h, hipMalloc((void**)&sc.blob, h->g.blob_floats * sizeof(float)));
+    HIP_TRY(h, raw.ensure(std::max<size_t>(h->raw_floats, 1) * sizeof(float)));
+    HIP_TRY(h, state.ensure(state_bytes));
+    HIP_TRY(h, blob.ensure(h->g.blob_floats * sizeof(float)));
     rc = order_in(h);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(sc.raw, h->d_raw, h->raw_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(sc.state, 0, state_bytes, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(sc.blob, h->d_blob, h->g.blob_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    const AdamParams p = adam_params(h, a, 1, sc.raw, sc.state);
+    HIP_TRY(h, hipMemcpyAsync(raw.as<void>(), h->d_raw.as<float>(), h->raw_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(state.as<void>(), 0, state_bytes, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(blob.as<void>(), h->d_blob.as<float>(), h->g.blob_floats * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    const AdamParams p = adam_params(h, a, 1, raw.as<float>(), state.as<float>());
     rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_stage_adam(p, h->stream)); return (int)LWP_OK; }, &ms[0]);
     if (!rc)
         rc = time_on_stream(h, iters, [&]() {
-            LAUNCH(h, KC_OTHER, launch_stage_repack(h->d_repack, h->repack_layers, h->repack_blocks, sc.raw, sc.blob, h->stream));
+            LAUNCH(h, KC_OTHER, launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, raw.as<float>(), blob.as<float>(), h->stream));
             return (int)LWP_OK; }, &ms[1]);
     (void)hipStreamSynchronize(h->stream);             // the scratch arrays are freed on return
     return rc;
@@ -3100,12 +2949,11 @@ extern "C" int lwp_debug_layer_output(lwp_handle h, const float* in, int N, int 
     level_dims(H, W, h->g.bufs[l.dst.buf].level, &dh, &dw);
     const size_t n = (size_t)N * l.cout * dh * dw;
     if (dst_floats < n) return fail(h, LWP_ERR_ARG, "dst too small");
-    rc = ensure_dev(h, &h->d_tmp, &h->d_tmp_bytes, n * sizeof(float));
-    if (rc) return rc;
+    HIP_TRY(h, h->d_tmp.ensure(n * sizeof(float)));
     // NHWC window (ld, coff) -> compact NCHW
-    if (h->dtype != LWP_F32) HIP_TRY(h, launch_nchw_from_nhwc_bf16(buf_at(h, l.dst), l.dst.ld, h->d_tmp, N, dh * dw, l.cout, h->stream, h->dtype == LWP_F16));
-    else HIP_TRY(h, launch_nchw_from_nhwc(buf_at(h, l.dst), l.dst.ld, h->d_tmp, N, dh * dw, l.cout, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dst, h->d_tmp, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (h->dtype != LWP_F32) HIP_TRY(h, launch_nchw_from_nhwc_bf16(buf_at(h, l.dst), l.dst.ld, h->d_tmp.as<float>(), N, dh * dw, l.cout, h->stream, h->dtype == LWP_F16));
+    else HIP_TRY(h, launch_nchw_from_nhwc(buf_at(h, l.dst), l.dst.ld, h->d_tmp.as<float>(), N, dh * dw, l.cout, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst, h->d_tmp.as<float>(), n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     out_dims[0] = N; out_dims[1] = l.cout; out_dims[2] = dh; out_dims[3] = dw;
     return LWP_OK;
@@ -3142,6 +2990,13 @@ extern "C" int lwp_debug_post_generic(lwp_handle h) {
     return (!h->skel.is_default || h->tune.post_generic == 1) ? 1 : 0;
 }
 
+extern "C" int lwp_debug_live_resources(int64_t out[4]) {
+    if (!out) return fail(nullptr, LWP_ERR_ARG, "out is null");
+    const LiveResources& r = live_resources();
+    out[0] = r.dev_bytes; out[1] = r.pin_bytes; out[2] = r.events; out[3] = r.streams;
+    return LWP_OK;
+}
+
 extern "C" int lwp_debug_f32_to_f16(const float* src, uint16_t* dst, int64_t n) {
     if ((!src || !dst) && n > 0) return fail(nullptr, LWP_ERR_ARG, "null argument");
     for (int64_t i = 0; i < n; ++i) dst[i] = f32_to_f16_rne(src[i]);
@@ -3163,8 +3018,7 @@ extern "C" int lwp_debug_time_layer(lwp_handle h, int idx, int N, int H, int W, 
     HIP_TRY(h, hipSetDevice(h->device));
     rc = ensure_activations(h, N, H, W);
     if (rc) return rc;
-    rc = ensure_dev(h, &h->d_in, &h->d_in_bytes, (size_t)N * 3 * H * W * sizeof(float));
-    if (rc) return rc;
+    HIP_TRY(h, h->d_in.ensure((size_t)N * 3 * H * W * sizeof(float)));
     const Layer& l = h->g.layers[idx];
     // a fused head pair is timed at its first layer; its second layer has no launch of its own
     int fh, fw;
@@ -3172,7 +3026,7 @@ extern "C" int lwp_debug_time_layer(lwp_handle h, int idx, int N, int H, int W, 
     const int64_t M3 = (int64_t)N * fh * fw;
     const bool pair = heads_pair_fusable(h, (size_t)idx, M3);
     if (idx > 0 && heads_pair_fusable(h, (size_t)idx - 1, M3)) { *ms_avg = 0.f; return LWP_OK; }
-    auto one = [&]() { return pair ? enqueue_heads_pair(h, l, h->g.layers[idx + 1], N, H, W, nullptr) : enqueue_layer(h, l, h->d_in, N, H, W, nullptr); };
+    auto one = [&]() { return pair ? enqueue_heads_pair(h, l, h->g.layers[idx + 1], N, H, W, nullptr) : enqueue_layer(h, l, h->d_in.as<float>(), N, H, W, nullptr); };
     for (int i = 0; i < 3; ++i) { rc = one(); if (rc) return rc; }
     float ms = 0.f;
     rc = time_on_stream(h, iters, one, &ms);

@@ -450,3 +450,28 @@ def test_pose_draw_marks_joints_and_limbs_and_stays_inside_the_image():
     far[b] = (60, 50)                                  # outside the image: clipped, no exception
     Pose(far, 1.0).draw(img)
     assert (img[39, 47] == col).all()
+
+
+_RAW_RESOURCE_CALLS = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate", "hipEventDestroy",
+                       "hipStreamCreate", "hipStreamDestroy")
+
+
+def test_gpu_resources_are_held_by_owner_types_only():
+    """The C-ABI host code names no raw allocation / release call: device and pinned memory, events and streams are taken and
+    given back by the owner types of csrc/lwp_owners.h alone, which also keep the live-resource counters.  A process that
+    never created a handle holds nothing."""
+    csrc = os.path.join(ROOT, "lightweight-human-pose-estimation.pytorch_amd", "csrc")
+    capi = open(os.path.join(csrc, "capi.cpp")).read()
+    assert [c for c in _RAW_RESOURCE_CALLS if c in capi] == []
+    owners = open(os.path.join(csrc, "lwp_owners.h")).read()
+    assert [c for c in _RAW_RESOURCE_CALLS if c not in owners] == []      # ... and this is where they live
+    # a fresh process: handles of other tests in this one may be alive
+    code = ("import ctypes, sys\n"
+            "L = ctypes.CDLL(sys.argv[1])\n"
+            "out = (ctypes.c_int64 * 4)(-1, -1, -1, -1)\n"
+            "rc = L.lwp_debug_live_resources(out)\n"
+            "print(rc, list(out))\n"
+            "sys.exit(L.lwp_debug_live_resources(None) != %d)\n" % _lib.LWP_ERR_ARG)
+    r = subprocess.run([sys.executable, "-c", code, _lib.LIB_PATH], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.split("\n")[0] == "%d [0, 0, 0, 0]" % _lib.LWP_OK
