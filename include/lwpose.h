@@ -496,7 +496,9 @@ int lwp_synchronize(lwp_handle h);
 int lwp_layer_count(lwp_handle h);
 int lwp_layer_info(lwp_handle h, int layer_index, char* name, int name_cap, int* kind, int* cin, int* cout,
                    int* ksize, int* stride, int* dilation, int64_t* macs_per_pixel /* algorithmic multiply-adds */);
-/* average device time (ms) of `iters` back-to-back launches of one layer on the current buffers */
+/* average device time (ms) of `iters` back-to-back launches of one layer on the current buffers.  A head pair that lwp_forward
+ * runs as one kernel is timed at its first layer and its second layer reports 0; a folded 1x1 is NOT applied: a dense 3x3 is
+ * timed alone, and so is the 1x1 behind it */
 int lwp_debug_time_layer(lwp_handle h, int layer_index, int N, int H, int W, int iters, float* ms_avg);
 int lwp_debug_layer_output(lwp_handle h, const float* in, int N, int H, int W, int layer_index,
                            float* dst, size_t dst_floats, int out_dims[4]);
@@ -508,6 +510,16 @@ int lwp_debug_layer_variant(lwp_handle h, int layer_index, char* name, int name_
 /* the host's f32 -> fp16 conversion of LWP_F16 weight packing (round to nearest even, subnormals kept, inf beyond 65520),
  * n values; no handle, no GPU */
 int lwp_debug_f32_to_f16(const float* src, uint16_t* dst, int64_t n);
+/* which neighbouring layers of the layer list may share ONE launch, as the graph builder marks them once per graph (the
+ * handle's switches and the launchers' size limits decide at run time whether a marked step is taken): fuse[i] for layer i,
+ * its name at names + i * name_stride (names may be NULL).  LWP_MARK_HEADS_PAIR: layer i and i + 1 are a stage's merged head
+ * pair; LWP_MARK_FOLD_NEXT_1X1: layer i + 1, a 1x1, may ride in the epilogue of layer i, a dense 3x3 (16-bit graphs only).
+ * fuse_dwpw / merge_heads as LWP_FUSE_DWPW / LWP_MERGE_HEADS give them to lwp_create.  *n_layers out; LWP_ERR_CAPACITY when
+ * cap is below it or a name does not fit name_stride.  The retaining plan of lwp_train_forward is a copy of this list with
+ * the same marks at the same indices: for LWP_F32, fuse[i] from cpm.conv on is read from that copy.  No handle, no GPU. */
+enum { LWP_MARK_NONE = 0, LWP_MARK_HEADS_PAIR = 1, LWP_MARK_FOLD_NEXT_1X1 = 2 };
+int lwp_debug_graph_fusions(int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int dtype, int fuse_dwpw,
+                            int merge_heads, int* fuse, char* names, int name_stride, int cap, int* n_layers);
 /* frames one launch sequence of an N x 3 x H x W call takes (N unless a tensor of the pass would reach the kernels' 2 GiB
  * addressing range: lwp_forward / lwp_infer_poses* / lwp_pipeline_submit then walk the batch in equal chunks of this size) */
 int lwp_debug_frames_per_pass(lwp_handle h, int N, int H, int W);

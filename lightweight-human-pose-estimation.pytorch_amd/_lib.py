@@ -19,7 +19,7 @@ EXPORTS = [
     "lwp_profile_launches", "lwp_debug_time_layer", "lwp_pipeline_submit", "lwp_pipeline_fetch", "lwp_multiscale_accumulate",
     "lwp_preprocess_dims", "lwp_preprocess_u8", "lwp_scale_dims", "lwp_preprocess_scaled_u8", "lwp_debug_layer_variant", "lwp_set_stream", "lwp_preprocess_scaled_f32", "lwp_debug_frames_per_pass", "lwp_debug_post_counts",
     "lwp_debug_f32_to_f16", "lwp_set_skeleton", "lwp_get_skeleton", "lwp_debug_post_counts_ex",
-    "lwp_debug_post_generic", "lwp_debug_live_resources",
+    "lwp_debug_post_generic", "lwp_debug_live_resources", "lwp_debug_graph_fusions",
     "lwp_set_tracking", "lwp_set_unmap", "lwp_reset_tracking", "lwp_get_poses", "lwp_track_poses", "lwp_debug_tracking_near",
     "lwp_preprocess_u8_batch", "lwp_pipeline_submit_u8",
     "lwp_set_overlay", "lwp_get_overlay", "lwp_draw_poses",
@@ -95,6 +95,7 @@ def lib():
     L.lwp_debug_post_counts_ex.argtypes = [vp, C.c_int] + [ip] * 4 + [C.c_int, C.c_int]
     L.lwp_debug_post_generic.argtypes = [vp]
     L.lwp_debug_live_resources.argtypes = [i64p]
+    L.lwp_debug_graph_fusions.argtypes = [C.c_int] * 7 + [ip, C.c_char_p, C.c_int, C.c_int, ip]
     L.lwp_set_tracking.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, fp, C.c_int]
     L.lwp_set_unmap.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int]
     L.lwp_reset_tracking.argtypes = [vp, C.c_int, C.c_int]

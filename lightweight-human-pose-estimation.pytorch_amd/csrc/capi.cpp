@@ -41,20 +41,26 @@ struct lwp_context {
         bool operator==(const TabKey& o) const { return cw == o.cw && ch == o.ch && dw == o.dw && dh == o.dh && ratio == o.ratio && up_ratio == o.up_ratio; }
     };
     struct MsPlan { int uh_max = 0, uw_max = 0, tx = 0, tx4 = 0, uh4 = 0, uw4 = 0; };   // the fused multi-scale kernels' tile extents
-    struct ResizeTab { TabKey key; DevBuf d; MsPlan plan; };
+    template <class Wt> struct TabArrays { int* xi; Wt* xw; int* yi; Wt* yw; };   // device pointers
+    struct ResizeTab {
+        TabKey key; DevBuf d; MsPlan plan;
+        size_t nx = 0, ny = 0;             // elements of the x and of the y arrays (4 per destination column / row)
+        // the four arrays of the allocation, xi | xw | yi | yw; Wt: the weights' type (int: fixed point, float: cubic coefficients)
+        template <class Wt> TabArrays<Wt> arrays() const {
+            char* t = d.as<char>();
+            return {(int*)t, (Wt*)(t + nx * 4), (int*)(t + nx * 8), (Wt*)(t + nx * 8 + ny * 4)};
+        }
+    };
     typedef std::vector<ResizeTab> TabCache;
     TabCache resize_tabs;                  // cubic tables of the multi-scale path: (cw, ch, dst_w, dst_h, up_ratio)
     TabCache scale_tabs;                   // image-side tables of lwp_preprocess_scaled_u8: (W, H, dw, dh, ratio)
-    DevBuf d_imgs;                         // uint8 frame batch staging (host frames of the multi-scale path)
-    DevBuf d_img;                          // uint8 frame staging (pre-processing of host frames)
+    DevBuf d_imgs;                         // staging of host frames (uint8 pre-processing, multi-scale image side, lwp_draw_poses)
     // host frames travel through one of two pinned buffers (upload_host): a copy from pageable memory is staged by the runtime
     // anyway, at ~100 us per 720 KB frame and with the calling thread blocked until the DMA has finished
     PinBuf pin_buf[2]; Event pin_ev[2]; bool pin_busy[2] = {false, false};
     int pin_next = 0;
-    DevBuf d_pre_tab;                      // fixed-point resize tables, cached for (pre_H, pre_W, pre_net_h)
-    int pre_H = 0, pre_W = 0, pre_net_h = 0;
-    TabCache pre_tabs;                     // the same tables for the batched entry points, one set per geometry (W, H, dw, dh, scale): never rewritten, so a
-                                           // submit with a new frame size cannot race the launches of another slot that still read the old ones
+    TabCache pre_tabs;                     // fixed-point tables of the uint8 pre-processing, one set per geometry (W, H, dw, dh, scale): never rewritten, so a
+                                           // call with a new frame size cannot race the launches of another slot that still read the old ones
     DevBuf d_pipe_in;                      // network input of lwp_pipeline_submit_u8 (written and read on the main stream only)
     DevBuf d_maps[2];                      // bf16 path: f32 NCHW heat / PAF of the last stage
     // post-processing
@@ -237,6 +243,25 @@ extern "C" int lwp_param_spec(int nref, int C, int NH, int NP, int index, char* 
     for (int d = 0; d < 4; ++d) shape[d] = t[index].shape[d];
     *ndim = t[index].ndim;
     *role = t[index].role;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_graph_fusions(int nref, int C, int NH, int NP, int dtype, int fuse_dwpw, int merge_heads, int* fuse, char* names,
+                                       int name_stride, int cap, int* n_layers) {
+    if (nref < 0 || C <= 0 || C % 32 || NH <= 0 || NP <= 0 || !fuse || !n_layers || (names && name_stride <= 0)) return fail(nullptr, LWP_ERR_ARG, "bad argument");
+    if (dtype != LWP_F32 && dtype != LWP_BF16 && dtype != LWP_F16) return fail(nullptr, LWP_ERR_ARG, "bad dtype");
+    if (dtype != LWP_F32 && !(C % 64 == 0 && dwpw_supported(C, C))) return fail(nullptr, LWP_ERR_ARG, "the 16-bit paths support num_channels 64, 128, 256 or 512 only");
+    const Graph g = build_graph(nref, C, NH, NP, fuse_dwpw != 0, dtype, merge_heads != 0);
+    TrainPlan tp;                                      // fp32: from cpm.conv on, the marks the retaining plan's copy carries
+    if (dtype == LWP_F32) tp = build_train_plan(g);
+    *n_layers = (int)g.layers.size();
+    if (*n_layers > cap) return fail(nullptr, LWP_ERR_CAPACITY, "fuse array too small");
+    for (size_t i = 0; i < g.layers.size(); ++i) {
+        fuse[i] = (tp.cpm_conv >= 0 && (int)i >= tp.cpm_conv ? tp.layers[i] : g.layers[i]).fuse;
+        if (!names) continue;
+        if ((int)g.layers[i].name.size() + 1 > name_stride) return fail(nullptr, LWP_ERR_CAPACITY, "name stride too small");
+        std::strcpy(names + i * (size_t)name_stride, g.layers[i].name.c_str());
+    }
     return LWP_OK;
 }
 
@@ -750,7 +775,8 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
         p.N = N; p.H = dh; p.W = dw;
         p.cin_pad = l.cin_pad; p.cout = l.cout; p.cout_pad = l.cout_pad; p.ks = l.ks; p.dil = l.dil; p.act = l.act;
         p.tune = &h->tune; p.variant = vb;
-        if (fold && folded && h16) {                    // the next 1x1 rides in this launch's epilogue if the launcher takes it
+        if (fold) {                                     // the next 1x1 rides in this launch's epilogue if the launcher takes it.  Only the walk
+                                                        // passes one: from a fold mark (16-bit graphs only), with `folded` non-null
             p.w2 = h->blob(fold->w_off); p.bias2 = h->blob(fold->b_off);
             p.out2 = buf_at(h, fold->dst); p.out2_ld = fold->dst.ld; p.act2 = fold->act;
             p.fused2 = folded;
@@ -761,19 +787,10 @@ static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int 
     return LWP_OK;
 }
 
-// a stage's merged head pair (".heads.0" 1x1 C -> hidden + ReLU, ".heads.1" 1x1 hidden -> NH + NP) runs as one kernel
-// that keeps the hidden tensor on the CU.  LWP_FUSE_HEADS=0 launches the two GEMMs (A/B, tests).
-static bool heads_pair_fusable(lwp_context* h, size_t i, int64_t M) {
-    if (h->tune.fuse_heads == 0) return false;
-    const std::vector<Layer>& ls = h->g.layers;
-    if (i + 1 >= ls.size()) return false;
-    const Layer& a = ls[i];
-    const Layer& b = ls[i + 1];
-    auto ends_with = [](const std::string& s, const char* suf) { const size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; };
-    if (!ends_with(a.name, ".heads.0") || !ends_with(b.name, ".heads.1")) return false;
-    if (a.kind != L_GEMM || b.kind != L_GEMM || a.ks != 1 || b.ks != 1 || a.act != ACT_RELU || b.act != ACT_NONE) return false;
-    if (a.res.buf >= 0 || b.res.buf >= 0 || a.out_index >= 0) return false;
-    if (b.src.buf != a.dst.buf || b.src.coff != a.dst.coff || b.cin_pad != a.cout_pad || a.cout != a.cout_pad) return false;
+// The run-time half of a marked head pair (Layer::fuse == LWP_MARK_HEADS_PAIR on `a`, `b` the layer behind it): the handle's
+// switch (LWP_FUSE_HEADS=0 launches the two GEMMs: A/B, tests) and the head kernels' own size limits at M pixels.
+static bool heads_pair_runs(const lwp_context* h, const Layer& a, const Layer& b, int64_t M) {
+    if (a.fuse != LWP_MARK_HEADS_PAIR || h->tune.fuse_heads == 0) return false;
     return h->dtype != LWP_F32 ? heads_bf16_supported(a.cin_pad, a.cout_pad, b.cout_pad) : heads_f32_supported(a.cin_pad, a.cout_pad, b.cout_pad, M, &h->tune);
 }
 
@@ -797,49 +814,39 @@ static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, in
     return LWP_OK;
 }
 
-// enqueue every layer on the handle's stream.  d_outs_nchw: 2*(1+nref) device pointers or null.
-static int enqueue_forward(lwp_context* h, const float* d_in, int N, int H, int W, float* const* d_outs_nchw,
-                           int max_layers = 1 << 30) {
-    const std::vector<Layer>& ls = h->g.layers;
+// THE walk over a layer list: layers [begin, end) of `ls` (the graph's list, or the retaining plan's) on the handle's stream.
+// A step the graph marked as fusable (Layer::fuse) is taken as one launch only if all its layers lie inside the range.
+// d_outs_nchw: 2*(1+nref) device pointers or null.  retain (lwp_train_forward): a fused head pair is preceded by a stand-alone
+// launch of its first layer, whose hidden tensor the pair's kernel keeps on the CU, for the retained copy.
+static int enqueue_forward(lwp_context* h, const std::vector<Layer>& ls, int begin, int end, const float* d_in, int N, int H, int W,
+                           float* const* d_outs_nchw, bool retain = false) {
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);
     const int64_t M3 = (int64_t)N * fh * fw;                 // pixels of the stride-8 maps the heads work on
-    for (size_t i = 0; i < ls.size() && (int)i < max_layers; ++i) {
-        h->cur_layer = (int)i;
-        if ((int)i + 1 < max_layers && heads_pair_fusable(h, i, M3)) {
-            int rc = enqueue_heads_pair(h, ls[i], ls[i + 1], N, H, W, d_outs_nchw);
-            if (rc) { h->cur_layer = -1; return rc; }
+    int rc = LWP_OK;
+    for (int i = begin; i < end && rc == LWP_OK; ++i) {
+        h->cur_layer = i;
+        const bool inside = i + 1 < end;
+        if (inside && heads_pair_runs(h, ls[i], ls[i + 1], M3)) {
+            if (retain) rc = enqueue_layer(h, ls[i], d_in, N, H, W, nullptr);
+            if (!rc) rc = enqueue_heads_pair(h, ls[i], ls[i + 1], N, H, W, d_outs_nchw);
             ++i;
             continue;
         }
-        // bf16 / fp16: a dense 3x3 whose output feeds ONLY the next layer, a 1x1 128 -> 128 (refinement block b's last conv and block b+1's
-        // `initial`, with_mobilenet.py:57-60), hands that layer to its own epilogue when the window-resident kernel runs
-        const Layer* fold = nullptr;
-        if (h->dtype != LWP_F32 && (int)i + 1 < max_layers && i + 1 < ls.size()) {
-            const Layer& a = ls[i];
-            const Layer& b = ls[i + 1];
-            const bool later_reader = [&]() {
-                for (size_t k = i + 2; k < ls.size(); ++k) {
-                    if ((ls[k].src.buf == a.dst.buf && ls[k].src.coff == a.dst.coff) || (ls[k].res.buf == a.dst.buf)) return true;
-                    if (ls[k].dst.buf == a.dst.buf) return false;         // overwritten before anyone else reads it
-                }
-                return false;
-            }();
-            if (a.kind == L_GEMM && a.ks == 3 && b.kind == L_GEMM && b.ks == 1 && b.src.buf == a.dst.buf && b.src.coff == a.dst.coff &&
-                b.src.ld == a.dst.ld && b.res.buf < 0 && b.out_index < 0 && a.out_index < 0 && b.blocks.empty() && a.cout == 128 &&
-                b.cin_pad == 128 && b.cout_pad == 128 && b.cout == 128 && !later_reader)
-                fold = &b;
-        }
+        // a marked 1x1 rides in this 3x3's epilogue if the launcher takes it (GemmParams::fused2)
         bool folded = false;
-        int rc = enqueue_layer(h, ls[i], d_in, N, H, W, d_outs_nchw, fold, &folded);
-        if (rc) { h->cur_layer = -1; return rc; }
-        if (folded) {
-            if (h->record_variants && i + 1 < h->variants.size()) h->variants[i + 1] = h->variants[i];
+        rc = enqueue_layer(h, ls[i], d_in, N, H, W, d_outs_nchw, inside && ls[i].fuse == LWP_MARK_FOLD_NEXT_1X1 ? &ls[i + 1] : nullptr, &folded);
+        if (!rc && folded) {
+            if (h->record_variants && (size_t)i + 1 < h->variants.size()) h->variants[i + 1] = h->variants[i];
             ++i;
         }
     }
     h->cur_layer = -1;
-    return LWP_OK;
+    return rc;
+}
+// the whole network
+static int enqueue_network(lwp_context* h, const float* d_in, int N, int H, int W, float* const* d_outs_nchw) {
+    return enqueue_forward(h, h->g.layers, 0, (int)h->g.layers.size(), d_in, N, H, W, d_outs_nchw);
 }
 
 static int check_frame_shape(lwp_context* h, int N, int H, int W) {
@@ -881,7 +888,7 @@ extern "C" int lwp_forward(lwp_handle h, const float* in, int in_mem, int N, int
     }
     rc = for_each_pass(h, N, H, W, [&](int f0, int n) {
         for (int i = 0; i < nout; ++i) d_chunk[i] = d_outs[i] + (size_t)f0 * (i % 2 ? h->g.NP : h->g.NH) * fh * fw;
-        return enqueue_forward(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, d_chunk.data());
+        return enqueue_network(h, d_in + (size_t)f0 * 3 * H * W, n, H, W, d_chunk.data());
     });
     if (rc) return rc;
     if (out_mem == LWP_MEM_HOST) {
@@ -935,23 +942,23 @@ static lwp_context::ResizeTab* find_tab(lwp_context::TabCache& cache, const lwp_
     for (auto& rt : cache) if (rt.key == key) return &rt;
     return nullptr;
 }
-// A new geometry's tables: the host arrays (4-byte elements), uploaded back to back into one allocation (blocking copies: a
-// steady-state call issues none).  The cache is bounded: the oldest geometry goes first, once nothing queued can read it.
-// The entry is inserted only after the upload succeeded.
-struct TabPart { const void* p; size_t n; };
+// A new geometry's tables: the four host arrays (4-byte elements; nx = 4 * destination width, ny = 4 * destination height),
+// uploaded back to back into one allocation (blocking copies: a steady-state call issues none).  The cache is bounded: the
+// oldest geometry goes first, once nothing queued can read it.  The entry is inserted only after the upload succeeded.
 static int add_tab(lwp_context* h, lwp_context::TabCache& cache, const lwp_context::TabKey& key, const lwp_context::MsPlan& plan,
-                   std::initializer_list<TabPart> parts, lwp_context::ResizeTab** out) {
+                   size_t nx, size_t ny, const void* xi, const void* xw, const void* yi, const void* yw, lwp_context::ResizeTab** out) {
     if (cache.size() >= kTabCacheMax) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         cache.erase(cache.begin());
     }
-    size_t n = 0;
-    for (const TabPart& a : parts) n += a.n;
-    DevBuf d;
-    HIP_TRY(h, d.ensure(n * 4));
-    char* t = d.as<char>();
-    for (const TabPart& a : parts) { HIP_TRY(h, hipMemcpy(t, a.p, a.n * 4, hipMemcpyHostToDevice)); t += a.n * 4; }
-    cache.push_back(lwp_context::ResizeTab{key, std::move(d), plan});
+    lwp_context::ResizeTab rt{key, DevBuf(), plan, nx, ny};
+    HIP_TRY(h, rt.d.ensure((nx + ny) * 8));
+    const auto t = rt.arrays<int>();                     // (4-byte elements whatever the weights' type)
+    HIP_TRY(h, hipMemcpy(t.xi, xi, nx * 4, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(t.xw, xw, nx * 4, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(t.yi, yi, ny * 4, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(t.yw, yw, ny * 4, hipMemcpyHostToDevice));
+    cache.push_back(std::move(rt));
     *out = &cache.back();
     return LWP_OK;
 }
@@ -982,7 +989,6 @@ extern "C" int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int ma
         d_acc = h->d_maps[0].as<float>();
     }
     // per-geometry tables, uploaded once (blocking copy) and kept: steady-state calls issue no host->device copy
-    const size_t nx = (size_t)dst_w * 4, ny = (size_t)dst_h * 4;
     const lwp_context::TabKey key{cw, ch, dst_w, dst_h, 0.0, up_ratio};
     lwp_context::ResizeTab* tab = find_tab(h->resize_tabs, key);
     if (!tab) {
@@ -999,29 +1005,25 @@ extern "C" int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int ma
             multiscale_fused_plan(xi.data(), yi.data(), dst_h, dst_w, up_ratio, &pl.tx, &pl.uh_max, &pl.uw_max);
             multiscale_fused_plan_v4(xi.data(), yi.data(), dst_h, dst_w, up_ratio, &pl.tx4, &pl.uh4, &pl.uw4);
         }
-        rc = add_tab(h, h->resize_tabs, key, pl, {{xi.data(), nx}, {xw.data(), nx}, {yi.data(), ny}, {yw.data(), ny}}, &tab);
+        rc = add_tab(h, h->resize_tabs, key, pl, (size_t)dst_w * 4, (size_t)dst_h * 4, xi.data(), xw.data(), yi.data(), yw.data(), &tab);
         if (rc) return rc;
     }
     const lwp_context::MsPlan& pl = tab->plan;
-    char* t = tab->d.as<char>();
-    int* d_xi = (int*)t; t += nx * 4;
-    float* d_xw = (float*)t; t += nx * 4;
-    int* d_yi = (int*)t; t += ny * 4;
-    float* d_yw = (float*)t;
+    const auto t = tab->arrays<float>();
     const MapView v = nchw_view(d_src, C, hs, ws);
     bool fused = false;
     if (h->tune.ms_fused != 0 && h->tune.ms_vec != 0) {      // four channels per lane (LWP_MS_VEC=0: the scalar fused kernel)
-        LAUNCH(h, KC_POST, launch_multiscale_fused_v4(v, N, C, up_ratio, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
+        LAUNCH(h, KC_POST, launch_multiscale_fused_v4(v, N, C, up_ratio, pad[0], pad[1], t.xi, t.xw, t.yi, t.yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
                                                       d_acc, pl.tx4, pl.uh4, pl.uw4, h->stream, &fused));
     }
     if (!fused && h->tune.ms_fused != 0) {                   // LWP_MS_FUSED=0: the two-kernel form (A/B, tests)
-        LAUNCH(h, KC_POST, launch_multiscale_fused(v, N, C, up_ratio, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
+        LAUNCH(h, KC_POST, launch_multiscale_fused(v, N, C, up_ratio, pad[0], pad[1], t.xi, t.xw, t.yi, t.yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0,
                                                    d_acc, pl.tx, pl.uh_max, pl.uw_max, h->stream, &fused));
     }
     if (!fused) {
         HIP_TRY(h, h->d_tmp2.ensure(ub));
         LAUNCH(h, KC_POST, launch_upsample(v, N, C, up_ratio, h->d_tmp2.as<float>(), h->stream, &h->tune));
-        LAUNCH(h, KC_POST, launch_resize_accum(h->d_tmp2.as<float>(), N, Hs, Ws, C, pad[0], pad[1], d_xi, d_xw, d_yi, d_yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0, d_acc, h->stream));
+        LAUNCH(h, KC_POST, launch_resize_accum(h->d_tmp2.as<float>(), N, Hs, Ws, C, pad[0], pad[1], t.xi, t.xw, t.yi, t.yw, dst_h, dst_w, (float)n_scales, init ? 1 : 0, d_acc, h->stream));
     }
     if (accum_mem == LWP_MEM_HOST) HIP_TRY(h, hipMemcpyAsync(accum, d_acc, ab, hipMemcpyDeviceToHost, h->stream));
     bool ordered = false;
@@ -1032,6 +1034,21 @@ extern "C" int lwp_multiscale_accumulate(lwp_handle h, const float* maps, int ma
 }
 
 // ---------------------------------------------------------------------------------------------- pre-processing
+// THE padding rule, val.py:36-49 with min_dims = [base, max(dw, base)] (demo.py:61, val.py:90): the scaled dh x dw frame centred
+// in base x max(dw, base), both rounded up to the stride
+static void pad_rule(int dh, int dw, int base, int stride, int* pad, int* out_h, int* out_w) {
+    const int h = dh < base ? dh : base;
+    const int min0 = (int)ceil(base / (double)stride) * stride;
+    const int m1 = dw > base ? dw : base;
+    const int min1 = (int)ceil(m1 / (double)stride) * stride;
+    pad[0] = (int)floor((min0 - h) / 2.0);
+    pad[1] = (int)floor((min1 - dw) / 2.0);
+    pad[2] = min0 - h - pad[0];
+    pad[3] = min1 - dw - pad[1];
+    *out_h = dh + pad[0] + pad[2];
+    *out_w = dw + pad[1] + pad[3];
+}
+
 extern "C" int lwp_preprocess_dims(int H, int W, int net_input_height, int stride, int* scaled_h, int* scaled_w,
                                    int* out_h, int* out_w, int* pad, double* scale) {
     if (H <= 0 || W <= 0 || net_input_height <= 0 || stride <= 0 || !scaled_h || !scaled_w || !out_h || !out_w || !pad || !scale)
@@ -1039,18 +1056,8 @@ extern "C" int lwp_preprocess_dims(int H, int W, int net_input_height, int strid
     const double sc = (double)net_input_height / (double)H;                       // demo.py:57
     const int dw = (int)nearbyint((double)W * sc), dh = (int)nearbyint((double)H * sc);   // cv2 dsize: round half to even
     if (dw <= 0 || dh <= 0) return fail(nullptr, LWP_ERR_ARG, "scaled frame is empty");
-    // val.py:36-49 with min_dims = [net_input_height, max(dw, net_input_height)] (demo.py:61)
-    const int h = dh < net_input_height ? dh : net_input_height;
-    const int min0 = (int)ceil(net_input_height / (double)stride) * stride;
-    const int m1 = dw > net_input_height ? dw : net_input_height;
-    const int min1 = (int)ceil(m1 / (double)stride) * stride;
-    pad[0] = (int)floor((min0 - h) / 2.0);
-    pad[1] = (int)floor((min1 - dw) / 2.0);
-    pad[2] = min0 - h - pad[0];
-    pad[3] = min1 - dw - pad[1];
+    pad_rule(dh, dw, net_input_height, stride, pad, out_h, out_w);
     *scaled_h = dh; *scaled_w = dw;
-    *out_h = dh + pad[0] + pad[2];
-    *out_w = dw + pad[1] + pad[3];
     *scale = sc;
     return LWP_OK;
 }
@@ -1088,68 +1095,87 @@ static int upload_host(lwp_context* h, const void* src, size_t bytes, void* dst,
     return LWP_OK;
 }
 
-// the shared staging of host frames (read on the main stream only)
-static int ensure_imgs_staging(lwp_context* h, size_t ib) {
-    if (h->d_imgs.size() >= ib) return LWP_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, h->d_imgs.ensure(ib));
+// Frames for a kernel on the main stream: device frames are read where they are; host frames go through upload_host (which
+// reports *consumed) into the shared staging, read on the main stream only, or into own_dst, a device buffer of the caller's.
+// *consumed is written for host frames only: the caller initialises it to what its epilogue needs for device frames
+static int stage_frames(lwp_context* h, const void* imgs, int img_mem, size_t ib, const void** d_src, bool* consumed,
+                        unsigned char* own_dst = nullptr) {
+    *d_src = imgs;
+    if (img_mem != LWP_MEM_HOST) return LWP_OK;
+    if (!own_dst && h->d_imgs.size() < ib) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, h->d_imgs.ensure(ib));
+    }
+    unsigned char* dst = own_dst ? own_dst : h->d_imgs.as<unsigned char>();
+    *d_src = dst;
+    return upload_host(h, imgs, ib, dst, consumed);
+}
+
+// ---- the uint8 front end (demo.py:57-64): geometry, device tables, kernel parameters and epilogue of lwp_preprocess_u8,
+//      lwp_preprocess_u8_batch and lwp_pipeline_submit_u8
+struct PreGeom { int dh, dw, Hp, Wp, pad[4]; double sc; };
+
+// device tables of a geometry, built and uploaded once and then only read
+static int pre_tables(lwp_context* h, int H, int W, const PreGeom& g, const lwp_context::ResizeTab** tab) {
+    const lwp_context::TabKey key{W, H, g.dw, g.dh, g.sc, 0};
+    lwp_context::ResizeTab* rt = find_tab(h->pre_tabs, key);
+    if (!rt) {
+        std::vector<int> xi, xw, yi, yw;
+        build_resize_table_u8(W, g.dw, g.sc, xi, xw);
+        build_resize_table_u8(H, g.dh, g.sc, yi, yw);
+        int rc = add_tab(h, h->pre_tabs, key, {}, (size_t)g.dw * 4, (size_t)g.dh * 4, xi.data(), xw.data(), yi.data(), yw.data(), &rt);
+        if (rc) return rc;
+    }
+    *tab = rt;
+    return LWP_OK;
+}
+
+static PreprocParams preproc_params(const void* d_src, int H, int W, const PreGeom& g, const lwp_context::ResizeTab& tab,
+                                    const double* pad_value, const double* img_mean, double img_scale, float* out) {
+    const auto t = tab.arrays<int>();
+    PreprocParams p;
+    p.src = (const unsigned char*)d_src; p.Hs = H; p.Ws = W;
+    p.xi = t.xi; p.xw = t.xw; p.yi = t.yi; p.yw = t.yw;
+    p.dh = g.dh; p.dw = g.dw; p.top = g.pad[0]; p.left = g.pad[1]; p.Hp = g.Hp; p.Wp = g.Wp;
+    for (int c = 0; c < 3; ++c) { p.mean[c] = img_mean[c]; p.pad_value[c] = (float)pad_value[c]; }
+    p.scale = img_scale;
+    p.out = out;
+    return p;
+}
+
+// The caller may reuse its host frame buffer on return: it has been copied into the pinned staging buffer already (or, for
+// very large batches, the COPY is waited for); the kernel's output is stream-ordered (consumed by this handle's next call, or
+// by the caller's stream after the event hand-over).  Without a declared caller stream the call completes on return.
+static int finish_u8(lwp_context* h, int img_mem, bool consumed) {
+    bool ordered = false;
+    int rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (img_mem == LWP_MEM_HOST) {
+        if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+        else if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
+    }
     return LWP_OK;
 }
 
 extern "C" int lwp_preprocess_u8(lwp_handle h, const unsigned char* img, int img_mem, int H, int W, int net_input_height,
                                  int stride, const double* pad_value, const double* img_mean, double img_scale, float* out_device) {
     if (!h || !img || !pad_value || !img_mean || !out_device) return fail(h, LWP_ERR_ARG, "null argument");
-    int dh, dw, Hp, Wp, pad[4];
-    double sc;
-    int rc = lwp_preprocess_dims(H, W, net_input_height, stride, &dh, &dw, &Hp, &Wp, pad, &sc);
+    PreGeom g;
+    int rc = lwp_preprocess_dims(H, W, net_input_height, stride, &g.dh, &g.dw, &g.Hp, &g.Wp, g.pad, &g.sc);
     if (rc) return fail(h, rc, "bad frame / network size");
-    if (pad[0] < 0 || pad[1] < 0 || pad[2] < 0 || pad[3] < 0) return fail(h, LWP_ERR_ARG, "negative padding");
+    if (g.pad[0] < 0 || g.pad[1] < 0 || g.pad[2] < 0 || g.pad[3] < 0) return fail(h, LWP_ERR_ARG, "negative padding");
     HIP_TRY(h, hipSetDevice(h->device));
     rc = order_in(h);                                    // device frame produced / output buffer last used on the caller's stream
     if (rc) return rc;
-    const unsigned char* d_src = img;
+    const void* d_src = nullptr;
     bool consumed = false;
-    if (img_mem == LWP_MEM_HOST) {
-        const size_t ib = (size_t)H * W * 3;
-        HIP_TRY(h, h->d_img.ensure(ib));
-        rc = upload_host(h, img, ib, h->d_img.as<unsigned char>(), &consumed);
-        if (rc) return rc;
-        d_src = h->d_img.as<unsigned char>();
-    }
-    const size_t nx = (size_t)dw * 4, ny = (size_t)dh * 4;
-    if (h->pre_H != H || h->pre_W != W || h->pre_net_h != net_input_height) {   // tables depend on the geometry only
-        std::vector<int> xi, xw, yi, yw;
-        build_resize_table_u8(W, dw, sc, xi, xw);
-        build_resize_table_u8(H, dh, sc, yi, yw);
-        HIP_TRY(h, hipStreamSynchronize(h->stream));                            // an earlier launch may still read the old tables
-        HIP_TRY(h, h->d_pre_tab.ensure((nx + ny) * 8));
-        int* t = h->d_pre_tab.as<int>();
-        HIP_TRY(h, hipMemcpy(t, xi.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t + nx, xw.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t + 2 * nx, yi.data(), ny * 4, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(t + 2 * nx + ny, yw.data(), ny * 4, hipMemcpyHostToDevice));
-        h->pre_H = H; h->pre_W = W; h->pre_net_h = net_input_height;
-    }
-    const int* t = h->d_pre_tab.as<int>();
-    PreprocParams p;
-    p.src = d_src; p.Hs = H; p.Ws = W;
-    p.xi = t; p.xw = t + nx; p.yi = t + 2 * nx; p.yw = t + 2 * nx + ny;
-    p.dh = dh; p.dw = dw; p.top = pad[0]; p.left = pad[1]; p.Hp = Hp; p.Wp = Wp;
-    for (int c = 0; c < 3; ++c) { p.mean[c] = img_mean[c]; p.pad_value[c] = (float)pad_value[c]; }
-    p.scale = img_scale;
-    p.out = out_device;
-    LAUNCH(h, KC_POST, launch_preprocess_u8(p, h->stream));
-    bool ordered = false;
-    rc = order_out(h, h->stream, &ordered);
+    rc = stage_frames(h, img, img_mem, (size_t)H * W * 3, &d_src, &consumed);
     if (rc) return rc;
-    // the caller may reuse its host frame buffer on return: it has been copied into the pinned staging buffer already (or, for
-    // very large frames, the COPY is waited for); the kernel's output is stream-ordered (consumed by this handle's next call, or
-    // by the caller's stream after the event hand-over).  Without a declared caller stream the call completes on return.
-    if (img_mem == LWP_MEM_HOST) {
-        if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
-        else if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
-    }
-    return LWP_OK;
+    const lwp_context::ResizeTab* tab = nullptr;
+    rc = pre_tables(h, H, W, g, &tab);
+    if (rc) return rc;
+    LAUNCH(h, KC_POST, launch_preprocess_u8(preproc_params(d_src, H, W, g, *tab, pad_value, img_mean, img_scale, out_device), h->stream));
+    return finish_u8(h, img_mem, consumed);
 }
 
 // ---------------------------------------------------------------------------------------------- multi-scale image side
@@ -1160,18 +1186,8 @@ extern "C" int lwp_scale_dims(int H, int W, double ratio, int base_height, int s
     const double fw = nearbyint((double)W * ratio), fh = nearbyint((double)H * ratio);   // cv2 dsize: round half to even
     if (!(fw >= 1.0 && fh >= 1.0 && fw <= 65535.0 && fh <= 65535.0)) return fail(nullptr, LWP_ERR_ARG, "scaled frame is empty or too large");
     const int dw = (int)fw, dh = (int)fh;
-    // val.py:36-49 with min_dims = [base_height, max(dw, base_height)] (val.py:90)
-    const int hh = dh < base_height ? dh : base_height;
-    const int min0 = (int)ceil(base_height / (double)stride) * stride;
-    const int m1 = dw > base_height ? dw : base_height;
-    const int min1 = (int)ceil(m1 / (double)stride) * stride;
-    pad[0] = (int)floor((min0 - hh) / 2.0);
-    pad[1] = (int)floor((min1 - dw) / 2.0);
-    pad[2] = min0 - hh - pad[0];
-    pad[3] = min1 - dw - pad[1];
+    pad_rule(dh, dw, base_height, stride, pad, out_h, out_w);
     *scaled_h = dh; *scaled_w = dw;
-    *out_h = dh + pad[0] + pad[2];
-    *out_w = dw + pad[1] + pad[3];
     return LWP_OK;
 }
 
@@ -1199,17 +1215,10 @@ static int preprocess_scaled_impl(lwp_handle h, const void* imgs, int elem, int 
     HIP_TRY(h, hipSetDevice(h->device));
     rc = order_in(h);
     if (rc) return rc;
-    const void* d_src = imgs;
+    const void* d_src = nullptr;
     bool consumed = false;
-    if (img_mem == LWP_MEM_HOST) {
-        const size_t ib = (size_t)N * H * W * 3 * elem;
-        rc = ensure_imgs_staging(h, ib);
-        if (rc) return rc;
-        rc = upload_host(h, imgs, ib, h->d_imgs.as<unsigned char>(), &consumed);
-        if (rc) return rc;
-        d_src = h->d_imgs.as<unsigned char>();
-    }
-    const size_t nx = (size_t)dw * 4, ny = (size_t)dh * 4;
+    rc = stage_frames(h, imgs, img_mem, (size_t)N * H * W * 3 * elem, &d_src, &consumed);
+    if (rc) return rc;
     const lwp_context::TabKey key{W, H, dw, dh, ratio, 0};
     lwp_context::ResizeTab* tab = find_tab(h->scale_tabs, key);
     if (!tab) {                                          // per-geometry tables, uploaded once and kept
@@ -1217,13 +1226,13 @@ static int preprocess_scaled_impl(lwp_handle h, const void* imgs, int elem, int 
         std::vector<float> xw, yw;
         build_resize_table_ratio(W, dw, ratio, xi, xw);
         build_resize_table_ratio(H, dh, ratio, yi, yw);
-        rc = add_tab(h, h->scale_tabs, key, {}, {{xi.data(), nx}, {xw.data(), nx}, {yi.data(), ny}, {yw.data(), ny}}, &tab);
+        rc = add_tab(h, h->scale_tabs, key, {}, (size_t)dw * 4, (size_t)dh * 4, xi.data(), xw.data(), yi.data(), yw.data(), &tab);
         if (rc) return rc;
     }
-    const char* t = tab->d.as<char>();
+    const auto t = tab->arrays<float>();
     PreScaleParams p;
     p.src = d_src; p.src_f32 = elem == 4; p.N = N; p.Hs = H; p.Ws = W;
-    p.xi = (const int*)t; p.xw = (const float*)(t + nx * 4); p.yi = (const int*)(t + nx * 8); p.yw = (const float*)(t + nx * 8 + ny * 4);
+    p.xi = t.xi; p.xw = t.xw; p.yi = t.yi; p.yw = t.yw;
     p.dh = dh; p.dw = dw; p.top = pad[0]; p.left = pad[1]; p.Hp = Hp; p.Wp = Wp;
     for (int c = 0; c < 3; ++c) { p.mean[c] = img_mean[c]; p.pad_value[c] = (float)pad_value[c]; }
     p.scale = img_scale;
@@ -1462,12 +1471,12 @@ static int enqueue_poses_chunk(lwp_context* h, const float* d_in, int N, int H, 
         HIP_TRY(h, h->d_maps[1].ensure(pb));
         outs[nout - 2] = h->d_maps[0].as<float>();
         outs[nout - 1] = h->d_maps[1].as<float>();
-        const int rc = enqueue_forward(h, d_in, N, H, W, outs.data());
+        const int rc = enqueue_network(h, d_in, N, H, W, outs.data());
         if (rc || !with_post) return rc;
         heat = nchw_view(h->d_maps[0].as<float>(), g.NH, fh, fw);
         paf = nchw_view(h->d_maps[1].as<float>(), g.NP, fh, fw);
     } else {
-        int rc = enqueue_forward(h, d_in, N, H, W, nullptr);
+        int rc = enqueue_network(h, d_in, N, H, W, nullptr);
         if (rc || !with_post) return rc;
         const float* cat = h->bufs[g.cat_buf].as<float>();
         heat = MapView{cat + g.C, (int64_t)fh * fw * cc, (int64_t)fw * cc, (int64_t)cc, 1, fh, fw};
@@ -1635,7 +1644,7 @@ static int pipeline_submit_impl(lwp_context* h, const float* in_device, int N, i
     rc = for_each_pass(h, N, H, W, [&](int f0, int n) {   // one launch sequence unless a tensor would reach 2 GiB
         outs[nout - 2] = sl.maps[0].as<float>() + (size_t)f0 * g.NH * fh * fw;
         outs[nout - 1] = sl.maps[1].as<float>() + (size_t)f0 * g.NP * fh * fw;
-        return enqueue_forward(h, in_device + (size_t)f0 * 3 * H * W, n, H, W, outs.data());
+        return enqueue_network(h, in_device + (size_t)f0 * 3 * H * W, n, H, W, outs.data());
     });
     if (rc) return rc;
     HIP_TRY(h, hipEventRecord(sl.ev_maps, h->stream));
@@ -1665,8 +1674,6 @@ extern "C" int lwp_pipeline_fetch(lwp_handle h, int slot, int* kpt_counts, doubl
 }
 
 // ---------------------------------------------------------------------------------------------- batched uint8 front end
-struct PreGeom { int dh, dw, Hp, Wp, pad[4]; double sc; };
-
 // the argument checks of the two batched uint8 entry points: host arithmetic only, so they run with h == NULL too
 static int check_u8_batch_args(lwp_context* h, const void* imgs, int img_mem, int N, int H, int W, int net_input_height, int stride,
                                const double* pad_value, const double* img_mean, PreGeom* g) {
@@ -1686,50 +1693,19 @@ static int check_u8_batch_args(lwp_context* h, const void* imgs, int img_mem, in
     return LWP_OK;
 }
 
-// device tables of a geometry, built and uploaded once and then only read
-static int pre_tables(lwp_context* h, int H, int W, const PreGeom& g, const int** tab) {
-    const lwp_context::TabKey key{W, H, g.dw, g.dh, g.sc, 0};
-    lwp_context::ResizeTab* rt = find_tab(h->pre_tabs, key);
-    if (!rt) {
-        const size_t nx = (size_t)g.dw * 4, ny = (size_t)g.dh * 4;
-        std::vector<int> xi, xw, yi, yw;
-        build_resize_table_u8(W, g.dw, g.sc, xi, xw);
-        build_resize_table_u8(H, g.dh, g.sc, yi, yw);
-        int rc = add_tab(h, h->pre_tabs, key, {}, {{xi.data(), nx}, {xw.data(), nx}, {yi.data(), ny}, {yw.data(), ny}}, &rt);
-        if (rc) return rc;
-    }
-    *tab = rt->d.as<int>();
-    return LWP_OK;
-}
-
 // upload (host frames) + the batched kernel on the main stream; *consumed as upload_host reports it.  own_dst: a device buffer
 // of the caller's for the uploaded frames (a slot that draws on them later) instead of the shared staging
 static int enqueue_u8_batch(lwp_context* h, const unsigned char* imgs, int img_mem, int N, int H, int W, const PreGeom& g,
                             const double* pad_value, const double* img_mean, double img_scale, float* out, bool* consumed,
                             unsigned char* own_dst = nullptr) {
     *consumed = true;
-    const unsigned char* d_src = imgs;
-    if (img_mem == LWP_MEM_HOST) {
-        const size_t ib = (size_t)N * H * W * 3;
-        int rc = own_dst ? LWP_OK : ensure_imgs_staging(h, ib);
-        if (rc) return rc;
-        unsigned char* dst = own_dst ? own_dst : h->d_imgs.as<unsigned char>();
-        rc = upload_host(h, imgs, ib, dst, consumed);
-        if (rc) return rc;
-        d_src = dst;
-    }
-    const int* t = nullptr;
-    int rc = pre_tables(h, H, W, g, &t);
+    const void* d_src = nullptr;
+    int rc = stage_frames(h, imgs, img_mem, (size_t)N * H * W * 3, &d_src, consumed, own_dst);
     if (rc) return rc;
-    const size_t nx = (size_t)g.dw * 4, ny = (size_t)g.dh * 4;
-    PreprocParams p;
-    p.src = d_src; p.Hs = H; p.Ws = W;
-    p.xi = t; p.xw = t + nx; p.yi = t + 2 * nx; p.yw = t + 2 * nx + ny;
-    p.dh = g.dh; p.dw = g.dw; p.top = g.pad[0]; p.left = g.pad[1]; p.Hp = g.Hp; p.Wp = g.Wp;
-    for (int c = 0; c < 3; ++c) { p.mean[c] = img_mean[c]; p.pad_value[c] = (float)pad_value[c]; }
-    p.scale = img_scale;
-    p.out = out;
-    LAUNCH(h, KC_POST, launch_preprocess_u8_batch(p, N, h->tune.pre_batch_vec == 1, h->stream));
+    const lwp_context::ResizeTab* tab = nullptr;
+    rc = pre_tables(h, H, W, g, &tab);
+    if (rc) return rc;
+    LAUNCH(h, KC_POST, launch_preprocess_u8_batch(preproc_params(d_src, H, W, g, *tab, pad_value, img_mean, img_scale, out), N, h->tune.pre_batch_vec == 1, h->stream));
     return LWP_OK;
 }
 
@@ -1746,14 +1722,7 @@ extern "C" int lwp_preprocess_u8_batch(lwp_handle h, const unsigned char* imgs, 
     bool consumed = true;
     rc = enqueue_u8_batch(h, imgs, img_mem, N, H, W, g, pad_value, img_mean, img_scale, out_device, &consumed);
     if (rc) return rc;
-    bool ordered = false;
-    rc = order_out(h, h->stream, &ordered);
-    if (rc) return rc;
-    if (img_mem == LWP_MEM_HOST) {                       // as lwp_preprocess_u8: host frames are free on return
-        if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
-        else if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
-    }
-    return LWP_OK;
+    return finish_u8(h, img_mem, consumed);
 }
 
 extern "C" int lwp_pipeline_submit_u8(lwp_handle h, const unsigned char* imgs, int img_mem, int N, int H, int W, int net_input_height,
@@ -2104,17 +2073,13 @@ extern "C" int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_m
         HIP_TRY(h, hipMemcpyAsync(dp + nb + kb, bbox, (size_t)N * pose_cap * 4 * 4, hipMemcpyHostToDevice, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // the caller's pose arrays are free from here on
-    const unsigned char* d_src = imgs;
-    if (img_mem == LWP_MEM_HOST) {
-        bool consumed = true;
-        rc = ensure_imgs_staging(h, ib);
-        if (rc == LWP_OK) rc = upload_host(h, imgs, ib, h->d_imgs.as<unsigned char>(), &consumed);
-        if (rc) return rc;
-        if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
-        d_src = h->d_imgs.as<unsigned char>();
-    }
+    const void* d_src = nullptr;
+    bool consumed = true;
+    rc = stage_frames(h, imgs, img_mem, ib, &d_src, &consumed);
+    if (rc) return rc;
+    if (!consumed) HIP_TRY(h, hipEventSynchronize(h->ev_copy));
     unsigned char* d_out = out_mem == LWP_MEM_HOST ? h->d_ov_out.as<unsigned char>() : out;
-    OverlayParams p = overlay_params(h, d_src, d_out, N, H, W);
+    OverlayParams p = overlay_params(h, (const unsigned char*)d_src, d_out, N, H, W);
     p.n_poses = (const int*)dp; p.kp = (const int*)(dp + nb); p.bbox = (const int*)(dp + nb + kb);
     p.kp_stride = (int64_t)pose_cap * (int64_t)K * 2; p.bbox_stride = (int64_t)pose_cap * 4;
     p.P = pose_cap;
@@ -2373,31 +2338,19 @@ extern "C" int lwp_train_forward(lwp_handle h, const float* in_device, int N, in
     h->train_N = 0;
     rc = order_in(h);
     if (rc) return rc;
-    // stem, backbone and cpm up to cpm.conv's input: the graph's own plan, nothing retained
+    // stem, backbone and cpm up to cpm.conv's input: the graph's own plan, nothing retained; then the retaining plan, with
+    // the outputs of the kernels Engine.forward uses
     const TrainPlan& tp = h->tp;
-    rc = enqueue_forward(h, in_device, N, H, W, nullptr, tp.cpm_conv);
+    rc = enqueue_forward(h, h->g.layers, 0, tp.cpm_conv, in_device, N, H, W, nullptr);
+    if (!rc) rc = enqueue_forward(h, tp.layers, tp.cpm_conv, tp.cpm_conv + 1, in_device, N, H, W, outs_device, true);
     if (rc) return rc;
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);
-    const int64_t M3 = (int64_t)N * fh * fw;
     const int C = h->g.C, catc = h->g.cat_channels, nb = (int)h->g.bufs.size();
-    for (size_t i = (size_t)tp.cpm_conv; i < tp.layers.size(); ++i) {
-        h->cur_layer = (int)i;
-        if (heads_pair_fusable(h, i, M3)) {
-            // the pair's kernel keeps the hidden tensor on the CU: heads.0 runs once more on its own for the retained copy, the
-            // stage outputs come from the same kernel Engine.forward uses
-            rc = enqueue_layer(h, tp.layers[i], in_device, N, H, W, nullptr);
-            if (!rc) rc = enqueue_heads_pair(h, tp.layers[i], tp.layers[i + 1], N, H, W, outs_device);
-            ++i;
-        } else {
-            rc = enqueue_layer(h, tp.layers[i], in_device, N, H, W, outs_device);
-        }
-        if (rc) { h->cur_layer = -1; return rc; }
-        if ((int)i == tp.cpm_conv)             // every refinement stage reads [features | heat | paf] of a buffer of its own
-            for (int k = 1; k < h->g.nref; ++k)
-                LAUNCH(h, KC_OTHER, launch_grad_add(h->tbufs[tp.cats[k] - nb].as<float>(), catc, h->tbufs[tp.cats[0] - nb].as<float>(), catc, M3, C, 0, h->stream));
-    }
-    h->cur_layer = -1;
+    for (int k = 1; k < h->g.nref; ++k)        // every refinement stage reads [features | heat | paf] of a buffer of its own
+        LAUNCH(h, KC_OTHER, launch_grad_add(h->tbufs[tp.cats[k] - nb].as<float>(), catc, h->tbufs[tp.cats[0] - nb].as<float>(), catc, (int64_t)N * fh * fw, C, 0, h->stream));
+    rc = enqueue_forward(h, tp.layers, tp.cpm_conv + 1, (int)tp.layers.size(), in_device, N, H, W, outs_device, true);
+    if (rc) return rc;
     h->train_N = N; h->train_H = H; h->train_W = W;
     bool ordered = false;
     return order_out(h, h->stream, &ordered);
@@ -2941,7 +2894,7 @@ extern "C" int lwp_debug_layer_output(lwp_handle h, const float* in, int N, int 
     rc = stage_input(h, in, LWP_MEM_HOST, (size_t)N * 3 * H * W * sizeof(float), &d_in);
     if (rc) return rc;
     h->record_variants = true;
-    rc = enqueue_forward(h, d_in, N, H, W, nullptr, idx + 1);
+    rc = enqueue_forward(h, h->g.layers, 0, idx + 1, d_in, N, H, W, nullptr);
     h->record_variants = false;
     if (rc) return rc;
     const Layer& l = h->g.layers[idx];
@@ -3020,13 +2973,15 @@ extern "C" int lwp_debug_time_layer(lwp_handle h, int idx, int N, int H, int W, 
     if (rc) return rc;
     HIP_TRY(h, h->d_in.ensure((size_t)N * 3 * H * W * sizeof(float)));
     const Layer& l = h->g.layers[idx];
-    // a fused head pair is timed at its first layer; its second layer has no launch of its own
+    // a fused head pair is timed at its first layer; its second layer has no launch of its own.  A fold mark is not acted
+    // on: a dense 3x3 is timed alone
+    const std::vector<Layer>& ls = h->g.layers;
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);
     const int64_t M3 = (int64_t)N * fh * fw;
-    const bool pair = heads_pair_fusable(h, (size_t)idx, M3);
-    if (idx > 0 && heads_pair_fusable(h, (size_t)idx - 1, M3)) { *ms_avg = 0.f; return LWP_OK; }
-    auto one = [&]() { return pair ? enqueue_heads_pair(h, l, h->g.layers[idx + 1], N, H, W, nullptr) : enqueue_layer(h, l, h->d_in.as<float>(), N, H, W, nullptr); };
+    const bool pair = idx + 1 < (int)ls.size() && heads_pair_runs(h, l, ls[idx + 1], M3);
+    if (idx > 0 && heads_pair_runs(h, ls[idx - 1], l, M3)) { *ms_avg = 0.f; return LWP_OK; }
+    auto one = [&]() { return pair ? enqueue_heads_pair(h, l, ls[idx + 1], N, H, W, nullptr) : enqueue_layer(h, l, h->d_in.as<float>(), N, H, W, nullptr); };
     for (int i = 0; i < 3; ++i) { rc = one(); if (rc) return rc; }
     float ms = 0.f;
     rc = time_on_stream(h, iters, one, &ms);

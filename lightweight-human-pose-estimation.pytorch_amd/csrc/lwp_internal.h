@@ -48,6 +48,7 @@ struct Layer {
     int out_index2 = -1, out_split = 0;   // merged heads: channels >= out_split belong to stage output #out_index2
     std::vector<WBlock> blocks;           // non-empty: weight matrix assembled from these convs (zeros elsewhere)
     int64_t macs_per_pixel = 0;           // algorithmic multiply-adds per output pixel (zero blocks not counted)
+    int fuse = LWP_MARK_NONE;             // what the layer may share a launch with (LWP_MARK_*): set once by build_graph
     // packed weights (float offsets into the blob)
     size_t w_off = 0, b_off = 0;
     int cin_pad = 0, cout_pad = 0;

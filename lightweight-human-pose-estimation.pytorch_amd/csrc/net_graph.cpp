@@ -106,6 +106,41 @@ struct Builder {
 };
 }  // namespace
 
+// Which neighbouring layers may run as ONE launch: the structural half of the decision, taken once per graph when the layer
+// list and the padded sizes are final.  What depends on the handle or the call (LWP_FUSE_HEADS, the head kernels' size limits,
+// the 3x3 launcher's own answer) stays a run-time gate of the one walk over a layer list, enqueue_forward in capi.cpp.
+static void mark_fusions(Graph& g) {
+    std::vector<Layer>& ls = g.layers;
+    auto ends_with = [](const std::string& s, const char* suf) { const size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; };
+    for (size_t i = 0; i + 1 < ls.size(); ++i) {
+        Layer& a = ls[i];
+        const Layer& b = ls[i + 1];
+        // a stage's merged head pair (".heads.0" 1x1 C -> hidden + ReLU, ".heads.1" 1x1 hidden -> NH + NP): one kernel that
+        // keeps the hidden tensor on the CU
+        if (ends_with(a.name, ".heads.0") && ends_with(b.name, ".heads.1") &&
+            a.kind == L_GEMM && b.kind == L_GEMM && a.ks == 1 && b.ks == 1 && a.act == ACT_RELU && b.act == ACT_NONE &&
+            a.res.buf < 0 && b.res.buf < 0 && a.out_index < 0 &&
+            b.src.buf == a.dst.buf && b.src.coff == a.dst.coff && b.cin_pad == a.cout_pad && a.cout == a.cout_pad) {
+            a.fuse = LWP_MARK_HEADS_PAIR;
+            continue;
+        }
+        // bf16 / fp16: a dense 3x3 whose output feeds ONLY the next layer, a 1x1 128 -> 128 (refinement block b's last conv and
+        // block b+1's `initial`, with_mobilenet.py:57-60), may hand that layer to its own epilogue (the window-resident kernel)
+        if (g.dtype == LWP_F32) continue;
+        const bool later_reader = [&]() {
+            for (size_t k = i + 2; k < ls.size(); ++k) {
+                if ((ls[k].src.buf == a.dst.buf && ls[k].src.coff == a.dst.coff) || (ls[k].res.buf == a.dst.buf)) return true;
+                if (ls[k].dst.buf == a.dst.buf) return false;         // overwritten before anyone else reads it
+            }
+            return false;
+        }();
+        if (a.kind == L_GEMM && a.ks == 3 && b.kind == L_GEMM && b.ks == 1 && b.src.buf == a.dst.buf && b.src.coff == a.dst.coff &&
+            b.src.ld == a.dst.ld && b.res.buf < 0 && b.out_index < 0 && a.out_index < 0 && b.blocks.empty() && a.cout == 128 &&
+            b.cin_pad == 128 && b.cout_pad == 128 && b.cout == 128 && !later_reader)
+            a.fuse = LWP_MARK_FOLD_NEXT_1X1;
+    }
+}
+
 Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bool merge_heads) {
     Builder b;
     Graph& g = b.g;
@@ -244,6 +279,7 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
         off = (off + 63) / 64 * 64;
     }
     g.blob_floats = off;
+    mark_fusions(g);
     return g;
 }
 

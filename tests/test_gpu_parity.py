@@ -1093,6 +1093,29 @@ def test_fp32_fused_head_pair_matches_the_two_gemm_form(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_time_layer_times_a_fused_head_pair_at_its_first_layer(monkeypatch):
+    """lwp_debug_time_layer reads the graph's pair mark plus the run-time gate: fp32, nref 1, one 32 x 40 frame (stride-8 maps
+    4 x 5, M = 20: below the fused pair's 4096-pixel limit).  By default the pair's second layer has no launch of its own and
+    reports 0 while its first layer times the pair kernel; under LWP_FUSE_HEADS=0 both layers are launches."""
+    sd = synth.make_state_dict(1, seed=3)
+
+    def run(fuse):
+        if fuse is None:
+            monkeypatch.delenv("LWP_FUSE_HEADS", raising=False)
+        else:
+            monkeypatch.setenv("LWP_FUSE_HEADS", fuse)
+        net = PoseEstimationWithMobileNet(num_refinement_stages=1)
+        load_state(net, {"state_dict": sd})
+        net.eval().cuda()
+        idx = {i["name"]: i["index"] for i in net.engine.layers()}
+        return [net.engine.time_layer(idx["initial_stage.heads.%d" % k], 1, 32, 40, iters=5) for k in (0, 1)]
+    first, second = run(None)
+    assert second == 0.0 and first > 0
+    first, second = run("0")
+    assert first > 0 and second > 0
+
+
+@pytest.mark.gpu
 def test_fp32_lds_staged_head_pair_forced_at_small_ragged_sizes(monkeypatch):
     """heads_f32_lds_kernel (M > 4096: 128-pixel workgroups, the pair's weights staged once per workgroup in LDS in chunks of 32
     hidden channels, hidden values in registers, merged heat / PAF pair with the block-diagonal second conv) forced at

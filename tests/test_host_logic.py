@@ -28,6 +28,50 @@ def test_library_exports_every_declared_symbol():
     assert sorted(declared) == sorted(_lib.EXPORTS)
 
 
+def _graph_fusions(nref, C, dtype, merge_heads):
+    """[(layer name, fusion mark)] of the graph lwp_create would build (no handle, no GPU)."""
+    cap, stride = 256, 96
+    fuse, names, n = (ctypes.c_int * cap)(), ctypes.create_string_buffer(cap * stride), ctypes.c_int()
+    _lib.check(_lib.lib().lwp_debug_graph_fusions(nref, C, 19, 38, dtype, 1, merge_heads, fuse, names, stride, cap, ctypes.byref(n)))
+    return [(names.raw[i * stride:(i + 1) * stride].split(b"\0")[0].decode(), fuse[i]) for i in range(n.value)]
+
+
+@pytest.mark.parametrize("dtype", [_lib.F32, _lib.BF16, _lib.F16])
+@pytest.mark.parametrize("nref", [0, 1, 3])
+def test_graph_fusion_marks(nref, dtype):
+    """Which neighbouring layers may share a launch is marked once, on the graph: the pair mark on every stage's `heads.0`
+    (merged heads only), the fold mark on the dilated 3x3 that ends refinement blocks 0..3 (16-bit graphs at C = 128 only; block
+    4 feeds the heads).  The expectations are read off the structural conditions of mark_fusions (net_graph.cpp); 2 stages x
+    4 blocks is what test_bf16_folded_initial_1x1_matches_the_separate_launches counts on the GPU."""
+    NONE, PAIR, FOLD = 0, 1, 2
+    marks = _graph_fusions(nref, 128, dtype, 1)
+    assert [nm for nm, f in marks if f == PAIR] == [nm for nm, _ in marks if nm.endswith(".heads.0")]
+    assert len([nm for nm, f in marks if f == PAIR]) == nref + 1
+    assert all(f == NONE for nm, f in marks if nm.endswith(".heads.1"))
+    folds = [nm for nm, f in marks if f == FOLD]
+    if dtype == _lib.F32:
+        assert folds == []
+    else:
+        assert folds == ["refinement_stages.%d.trunk.%d.trunk.1" % (k, b) for k in range(nref) for b in range(4)]
+    assert {f for _, f in marks} <= {NONE, PAIR, FOLD}
+    # fp32: from cpm.conv on these ARE the marks of lwp_train_forward's retaining plan (the read-out takes them from the plan's
+    # copy of the list); its walk is cut before and behind cpm.conv, where no marked step may straddle the cut
+    names = [nm for nm, _ in marks]
+    assert all(f == NONE for _, f in marks[:names.index("cpm.conv") + 1])
+    split = _graph_fusions(nref, 128, dtype, 0)                        # LWP_MERGE_HEADS=0: four head GEMMs per stage, no pair
+    assert not [nm for nm, f in split if f == PAIR] and not [nm for nm, _ in split if ".heads." in nm]
+    assert [nm for nm, f in split if f == FOLD] == folds
+
+
+def test_graph_fusion_marks_need_128_channels_for_a_fold():
+    marks = _graph_fusions(1, 64, _lib.BF16, 1)
+    assert [f for _, f in marks if f == 2] == [] and len(marks) > 0
+    n = ctypes.c_int()
+    assert _lib.lib().lwp_debug_graph_fusions(1, 128, 19, 38, _lib.F32, 1, 1, (ctypes.c_int * 4)(), None, 0, 4, ctypes.byref(n)) == _lib.LWP_ERR_CAPACITY
+    assert n.value == len(_graph_fusions(1, 128, _lib.F32, 1))
+    assert _lib.lib().lwp_debug_graph_fusions(1, 100, 19, 38, _lib.F32, 1, 1, (ctypes.c_int * 4)(), None, 0, 4, ctypes.byref(n)) == _lib.LWP_ERR_ARG
+
+
 def test_no_gpu_fails_loudly():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
