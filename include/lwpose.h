@@ -395,7 +395,8 @@ int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, co
 /* ---- stage backward: the gradient of train.py:99-102's summed loss
  *        L = loss_scale * sum_i l2_loss(stages_output[i], target_i, mask, batch_size)      (modules/loss.py: sum(((out - target) * mask)^2) / 2 / batch_size)
  *      with respect to every parameter of initial_stage.* and refinement_stages.* (with_mobilenet.py:25-86) and to
- *      backbone_features, the output of cpm.conv (with_mobilenet.py:117).  fp32 handles only; the backbone and the cpm are frozen,
+ *      backbone_features, the output of cpm.conv (with_mobilenet.py:117).  fp32 handles only; the backbone is frozen, the cpm
+ *      too unless the train scope is LWP_TRAIN_CPM (lwp_set_train_scope below),
  *      and the refinement trunks' BatchNorms (modules/conv.py:8) stay at their running statistics: the result is what
  *      loss.backward() gives on the reference network in eval() mode, NOT in train() mode (no batch statistics, running_mean /
  *      running_var / num_batches_tracked get no gradient and are not updated).  The optimiser step is lwp_stage_adam_step below.
@@ -434,11 +435,61 @@ int lwp_profile_stage_backward(lwp_handle h, const float* keypoint_maps, const f
 int lwp_debug_train_activation(lwp_handle h, int layer_index, float* dst, size_t dst_floats, int out_dims[4]);
 int lwp_debug_backward_splits(lwp_handle h, int layer_index);
 
+/* ---- train scope: which parameters lwp_train_forward retains for, lwp_stage_backward / lwp_train_backward differentiate and
+ *      lwp_stage_adam_step updates.  LWP_TRAIN_STAGES (the default): initial_stage.* and refinement_stages.*, everything in
+ *      front of cpm.conv's output frozen.  LWP_TRAIN_CPM: the cpm (with_mobilenet.py:7-21) as well: cpm.align, the three
+ *      depthwise 3x3 + ELU / 1x1 + ELU trunk blocks and cpm.conv; the backbone stays frozen.  The cpm has no BatchNorm.
+ *      lwp_set_train_scope: LWP_ERR_ARG on a bf16 / fp16 handle or an unknown scope; LWP_ERR_STATE while a pipeline slot or
+ *      an lwp_infer_poses_async is pending, and while the Adam step count is above 0: the moments are laid out for the scope
+ *      they were taken in, so call lwp_stage_adam_reset first, or set the scope before the first step.  The call
+ *      invalidates the retained forward, as a step does, and releases the retaining plan's buffers and the optimiser state.
+ *      In scope LWP_TRAIN_CPM:
+ *      - the gradient array, lwp_stage_params_get and lwp_stage_adam_state_get / _set use lwp_train_grad_spec(LWP_TRAIN_CPM, ..)'s
+ *        layout: the ten cpm.* parameters in lwp_param_spec order (cpm.align.0.weight / .bias, cpm.trunk.{0,1,2}.0.weight of
+ *        shape (C, 1, 3, 3) and cpm.trunk.{0,1,2}.2.weight, cpm.conv.0.weight / .bias), then the stage layout as its unchanged
+ *        tail, shifted by the cpm total.  With LWP_TRAIN_STAGES the three lwp_train_* layout functions return exactly what
+ *        lwp_stage_grad_count / _spec / lwp_stage_adam_group return.  Parameter groups of the cpm (train.py:46-48): conv
+ *        weights with groups == 1 x1 with weight decay, conv biases x2 without, depthwise weights x1 without.
+ *      - lwp_train_forward keeps, each in a buffer of its own, the cpm's input (the backbone's last output), a = align(x),
+ *        every trunk block's depthwise output after ELU and pointwise output after ELU, and the sum a + trunk(a).  The forward
+ *        kernels, their variants and the blob are lwp_forward's, the stage outputs stay bit-identical.  Where the graph runs a
+ *        trunk block as one fused launch, the depthwise activation comes from one more stand-alone depthwise launch on the same
+ *        input (it may differ from the value inside the fused kernel in the last bit), and the last block's pointwise output in
+ *        front of the residual add from one more launch of the block without the residual.
+ *      - lwp_train_backward is lwp_stage_backward with one more optional output: d_backbone_device, NULL or N x 512 x hs x ws
+ *        NCHW (DEVICE), the gradient at the cpm's input, computed only when asked for (cpm.align's data gradient is 512 wide).
+ *        A non-NULL d_backbone_device in scope LWP_TRAIN_STAGES is LWP_ERR_ARG with a message.  lwp_stage_backward follows the
+ *        handle's scope for the gradient layout; d_features_device keeps its meaning, and the stage gradients and d_features
+ *        are bit-identical to those of scope LWP_TRAIN_STAGES.  New kernels: ELU gradient from the retained output
+ *        (dZ = dY * (y > 0 ? 1 : y + 1)), depthwise data gradient (one fmaf chain per output in tap order), depthwise weight
+ *        gradient (per-range partial sums in a fixed order, then a reduction in range order): no floating-point atomics.
+ *      - lwp_stage_adam_step also updates the cpm parameters and repacks the cpm layers into the blob bit for bit as
+ *        lwp_load_weights does.
+ *      - tests: lwp_debug_train_activation answers from the backbone's last layer on.  lwp_debug_train_copy is the same read-out
+ *        with the kind of retained tensor spelled out: LWP_KEPT_OUTPUT the layer's output (what lwp_debug_train_activation
+ *        returns), LWP_KEPT_DEPTHWISE the retained depthwise copy of a fused trunk block (cin channels), LWP_KEPT_NO_RESIDUAL
+ *        the retained output of a block in front of its residual add; LWP_ERR_ARG where the layer has no such copy.
+ *        lwp_debug_backward_dw_splits is the number of pixel ranges of the layer's depthwise weight gradient (a depthwise
+ *        layer or a fused block), lwp_debug_backward_splits that of its dense / pointwise one. */
+enum { LWP_TRAIN_STAGES = 0, LWP_TRAIN_CPM = 1 };
+enum { LWP_KEPT_OUTPUT = 0, LWP_KEPT_DEPTHWISE = 1, LWP_KEPT_NO_RESIDUAL = 2 };
+int lwp_debug_train_copy(lwp_handle h, int layer_index, int which, float* dst, size_t dst_floats, int out_dims[4]);
+int lwp_debug_backward_dw_splits(lwp_handle h, int layer_index);
+int lwp_set_train_scope(lwp_handle h, int scope);
+int lwp_train_grad_count(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int64_t* total_floats);
+int lwp_train_grad_spec(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int index, char* name,
+                        int name_cap, int64_t shape[4], int* ndim, int64_t* offset);
+int lwp_train_adam_group(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int index, int* lr_mult,
+                         int* weight_decay_on);
+int lwp_train_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
+                       int batch_size, double loss_scale, int accumulate, float* grads_device, float* d_features_device,
+                       float* d_backbone_device);
+
 /* ---- stage fine-tuning step: the reference's optimiser (train.py:41-55 and :106, torch.optim.Adam with its parameter groups)
  *      for the parameters lwp_stage_backward differentiates, and the refold / repack of the changed layers into the forward's
  *      weight blob, all on the handle's stream: train_forward -> stage_backward -> step lowers the loss with no host round
  *      trip and no second copy of the weights.  fp32 handles whose weights came through lwp_load_weights only.
- *      Out of scope: backward or updates for the backbone and cpm, BatchNorm train mode (the running statistics never move), a
+ *      Out of scope: backward or updates for the backbone (and for the cpm in scope LWP_TRAIN_STAGES), BatchNorm train mode (the running statistics never move), a
  *      16-bit optimiser, multi-GPU gradient reduction, amsgrad, loading torch's optimiser checkpoints.
  *      lwp_stage_adam_group: the parameter group of gradient-spec entry `index` (no handle, no GPU): learning-rate multiplier
  *      and weight-decay flag: initial_stage conv weight x1 / on, conv bias x2 / off; refinement_stages conv weight x4 / on,

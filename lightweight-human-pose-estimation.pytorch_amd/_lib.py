@@ -9,6 +9,9 @@ LIB_PATH = os.path.join(PKG, "liblwpose_hip.so")
 LWP_OK, LWP_ERR_ARG, LWP_ERR_HIP, LWP_ERR_STATE, LWP_ERR_CAPACITY, LWP_ERR_NOGPU, LWP_ERR_UNBOUND = 0, -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
 F32, BF16, F16 = 0, 1, 2
+TRAIN_STAGES, TRAIN_CPM = 0, 1
+TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM}
+KEPT_OUTPUT, KEPT_DEPTHWISE, KEPT_NO_RESIDUAL = 0, 1, 2
 
 EXPORTS = [
     "lwp_version", "lwp_param_count", "lwp_param_spec", "lwp_create", "lwp_destroy", "lwp_last_error",
@@ -28,6 +31,8 @@ EXPORTS = [
     "lwp_debug_train_activation", "lwp_debug_backward_splits",
     "lwp_stage_adam_group", "lwp_stage_adam_step", "lwp_stage_params_get", "lwp_stage_adam_state_get", "lwp_stage_adam_state_set",
     "lwp_stage_adam_reset", "lwp_time_stage_adam_step",
+    "lwp_set_train_scope", "lwp_train_grad_count", "lwp_train_grad_spec", "lwp_train_adam_group", "lwp_train_backward",
+    "lwp_debug_train_copy", "lwp_debug_backward_dw_splits",
 ]
 
 
@@ -126,6 +131,13 @@ def lib():
     L.lwp_stage_adam_state_set.argtypes = [vp, vp, vp, C.c_int64]
     L.lwp_stage_adam_reset.argtypes = [vp]
     L.lwp_time_stage_adam_step.argtypes = [vp, vp] + [C.c_double] * 5 + [C.c_int, fp]
+    L.lwp_set_train_scope.argtypes = [vp, C.c_int]
+    L.lwp_train_grad_count.argtypes = [C.c_int] * 5 + [i64p]
+    L.lwp_train_grad_spec.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_int, i64p, ip, i64p]
+    L.lwp_train_adam_group.argtypes = [C.c_int] * 6 + [ip, ip]
+    L.lwp_train_backward.argtypes = L.lwp_stage_backward.argtypes + [vp]
+    L.lwp_debug_train_copy.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, ip]
+    L.lwp_debug_backward_dw_splits.argtypes = [vp, C.c_int]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int
@@ -188,6 +200,52 @@ def stage_adam_groups(nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
     out = []
     for i, (key, _, _) in enumerate(spec):
         check(L.lwp_stage_adam_group(nref, num_channels, num_heatmaps, num_pafs, i, C.byref(mult), C.byref(wd)))
+        out.append((key, mult.value, bool(wd.value)))
+    return out
+
+
+def train_scope_name(scope):
+    """"stages" / "cpm" of a scope given by name or by its LWP_TRAIN_* number."""
+    sc = train_scope(scope)
+    return [k for k, v in TRAIN_SCOPES.items() if v == sc][0]
+
+
+def train_scope(scope):
+    """LWP_TRAIN_* of "stages" / "cpm" (or of the number itself)."""
+    if scope in TRAIN_SCOPES:
+        return TRAIN_SCOPES[scope]
+    if scope in TRAIN_SCOPES.values():
+        return int(scope)
+    raise ValueError("train scope must be 'stages' or 'cpm', got %r" % (scope,))
+
+
+def train_grad_spec(scope, nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
+    """``stage_grad_spec`` for a train scope ("stages" | "cpm"): in scope "cpm" the ten cpm.* parameters come first."""
+    L = lib()
+    sc = train_scope(scope)
+    total = C.c_int64()
+    n = L.lwp_train_grad_count(sc, nref, num_channels, num_heatmaps, num_pafs, C.byref(total))
+    if n < 0:
+        raise ValueError("bad network shape")
+    out = []
+    name = C.create_string_buffer(256)
+    shape = (C.c_int64 * 4)()
+    nd, off = C.c_int(), C.c_int64()
+    for i in range(n):
+        check(L.lwp_train_grad_spec(sc, nref, num_channels, num_heatmaps, num_pafs, i, name, 256, shape, C.byref(nd), C.byref(off)))
+        out.append((name.value.decode(), tuple(shape[d] for d in range(nd.value)), off.value))
+    return out, total.value
+
+
+def train_adam_groups(scope, nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
+    """``stage_adam_groups`` for a train scope: the cpm's conv weights x1 with decay, biases x2 and depthwise weights x1 without."""
+    L = lib()
+    sc = train_scope(scope)
+    spec, _ = train_grad_spec(sc, nref, num_channels, num_heatmaps, num_pafs)
+    mult, wd = C.c_int(), C.c_int()
+    out = []
+    for i, (key, _, _) in enumerate(spec):
+        check(L.lwp_train_adam_group(sc, nref, num_channels, num_heatmaps, num_pafs, i, C.byref(mult), C.byref(wd)))
         out.append((key, mult.value, bool(wd.value)))
     return out
 

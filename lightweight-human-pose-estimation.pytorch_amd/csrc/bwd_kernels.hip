@@ -237,7 +237,7 @@ hipError_t launch_wgrad(const WgradParams& p, hipStream_t s) {
         p.chunk < BW_K || (p.chunk % BW_K) || (int64_t)p.splits * p.chunk < M)
         return hipErrorInvalidValue;
     const unsigned tiles = (unsigned)((wgrad_pad64(p.cout) / BW_T) * (wgrad_pad64(p.cin) / BW_T));
-    hipLaunchKernelGGL(wgrad_kernel, dim3(tiles, (unsigned)(p.ks * p.ks + 1), (unsigned)p.splits), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(wgrad_kernel, dim3(tiles, (unsigned)(p.ks * p.ks + (p.no_bias ? 0 : 1)), (unsigned)p.splits), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(WgradParams p, float*
     const int taps = p.ks * p.ks;
     const int co_p = wgrad_pad64(p.cout), ci_p = wgrad_pad64(p.cin);
     const int64_t nw = (int64_t)p.cout * p.cin * taps;
-    const int64_t total = nw + p.cout;
+    const int64_t total = nw + (p.no_bias ? 0 : p.cout);
     const float* bpart = p.partial + (size_t)p.splits * taps * co_p * ci_p;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         float sum = 0.0f;
@@ -266,9 +266,168 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(WgradParams p, float*
 }
 
 hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int accumulate, hipStream_t s) {
-    const int64_t total = (int64_t)p.cout * p.cin * p.ks * p.ks + p.cout;
+    const int64_t total = (int64_t)p.cout * p.cin * p.ks * p.ks + (p.no_bias ? 0 : p.cout);
     const unsigned bx = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(bx), dim3(256), 0, s, p, dw, db, accumulate);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- cpm: ELU and depthwise 3x3
+// (with_mobilenet.py:7-21; modules/conv.py:24-32 with bn=False: depthwise 3x3 + ELU, 1x1 + ELU.)  Memory-bound element-wise and
+// reduction shapes: a lane owns four consecutive channels of a pixel, every access is 16 bytes, a wave covers whole rows.
+__global__ void __launch_bounds__(256) elu_grad_kernel(float* g, int g_ld, const float* y, int y_ld, int64_t M, int C4) {
+    const int64_t total = M * C4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t px = i / C4;
+        const int c = (int)(i % C4) * 4;
+        f32x4* gp = (f32x4*)(g + px * g_ld + c);
+        const f32x4 yv = *(const f32x4*)(y + px * y_ld + c);
+        f32x4 gv = *gp;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gv[k] = gv[k] * (yv[k] > 0.0f ? 1.0f : yv[k] + 1.0f);
+        *gp = gv;
+    }
+}
+static bool quad_ok(const void* p, int ld) { return p && ((uintptr_t)p & 15) == 0 && ld > 0 && (ld & 3) == 0; }
+hipError_t launch_elu_grad(float* g, int g_ld, const float* y, int y_ld, int64_t M, int C, hipStream_t s) {
+    if (M < 1 || C < 4 || (C & 3) || C > g_ld || C > y_ld || !quad_ok(g, g_ld) || !quad_ok(y, y_ld)) return hipErrorInvalidValue;
+    const unsigned bx = (unsigned)std::min<int64_t>((M * (C / 4) + 255) / 256, 8192);
+    hipLaunchKernelGGL(elu_grad_kernel, dim3(bx), dim3(256), 0, s, g, g_ld, y, y_ld, M, C / 4);
+    return hipGetLastError();
+}
+
+// dX[n, y, x, c] = sum over taps (ky, kx) of dZ[n, y + 1 - ky, x + 1 - kx, c] * w[ky][kx][c]: one fmaf chain per output in tap
+// order 0..8, a tap outside the map contributes a zero
+__global__ void __launch_bounds__(256) dw_dgrad_kernel(DwGradParams p) {
+    const int C4 = p.C / 4;
+    const int HW = p.H * p.W;
+    const int64_t total = (int64_t)p.N * HW * C4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t px = i / C4;
+        const int c = (int)(i % C4) * 4;
+        const int64_t n = px / HW;
+        const int r = (int)(px % HW);
+        const int y = r / p.W, x = r % p.W;
+        f32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int sy = y + 1 - tap / 3, sx = x + 1 - tap % 3;
+            f32x4 z = {0, 0, 0, 0};
+            if (sy >= 0 && sy < p.H && sx >= 0 && sx < p.W) z = *(const f32x4*)(p.dz + (n * HW + (int64_t)sy * p.W + sx) * p.dz_ld + c);
+            const f32x4 wv = *(const f32x4*)(p.w + tap * p.C + c);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = fmaf(z[k], wv[k], acc[k]);
+        }
+        f32x4* d = (f32x4*)(p.dx + px * p.dx_ld + c);
+        if (p.beta) {
+            const f32x4 old = *d;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = old[k] + acc[k];
+        }
+        *d = acc;
+    }
+}
+static bool dw_grad_shape_ok(const DwGradParams& p) {
+    const int64_t M = (int64_t)p.N * p.H * p.W;
+    return p.N >= 1 && p.H >= 1 && p.W >= 1 && M < (1ll << 31) - BW_T && p.C >= 4 && (p.C & 3) == 0 && p.C <= p.dz_ld && quad_ok(p.dz, p.dz_ld);
+}
+hipError_t launch_dw_dgrad(const DwGradParams& p, hipStream_t s) {
+    if (!dw_grad_shape_ok(p) || !quad_ok(p.w, 4) || !quad_ok(p.dx, p.dx_ld) || p.C > p.dx_ld) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)p.N * p.H * p.W * (p.C / 4);
+    hipLaunchKernelGGL(dw_dgrad_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// dW[c][tap] = sum over pixels p of dZ[p][c] * X[p + off(tap)][c], off(tap) = (tap / 3 - 1, tap % 3 - 1).  grid: x = 64-channel
+// group, y = pixel split.  Thread t owns channels 4 (t & 15) .. + 3 of the group and the pixels p_begin + (t >> 4) + 16 k of the
+// split, k ascending: 36 fmaf chains.  The 16 pixel lanes are then added through LDS in a fixed binary tree (lane i += lane
+// i + 8, + 4, + 2, + 1), and lane 0 writes the split's [9][C] partial.  A second launch adds the partials in split order.
+constexpr int DW_CG = 64;          // channels of a workgroup
+constexpr int DW_PL = 16;          // pixel lanes
+__global__ void __launch_bounds__(256) dw_wgrad_kernel(DwGradParams p) {
+    __shared__ float red[DW_PL * 9 * DW_CG];          // [pixel lane][tap][channel]: 36 KB
+    const int t = threadIdx.x, cq = (t & 15) * 4, pl = t >> 4;
+    const int c = blockIdx.x * DW_CG + cq;
+    const bool c_in = c < p.C;                         // C is a multiple of 4: a quad is inside or outside as a whole
+    const int HW = p.H * p.W;
+    const int64_t M = (int64_t)p.N * HW;
+    const int64_t p_begin = (int64_t)blockIdx.y * p.chunk;
+    const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
+    f32x4 acc[9];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) acc[tap] = f32x4{0, 0, 0, 0};
+    if (c_in)
+        for (int64_t px = p_begin + pl; px < p_end; px += DW_PL) {
+            const f32x4 z = *(const f32x4*)(p.dz + px * p.dz_ld + c);
+            const int64_t n = px / HW;
+            const int r = (int)(px % HW);
+            const int y = r / p.W, x = r % p.W;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const int sy = y + tap / 3 - 1, sx = x + tap % 3 - 1;
+                if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) continue;
+                const f32x4 xv = *(const f32x4*)(p.x + (n * HW + (int64_t)sy * p.W + sx) * p.x_ld + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[tap][k] = fmaf(z[k], xv[k], acc[tap][k]);
+            }
+        }
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) *(f32x4*)(red + (pl * 9 + tap) * DW_CG + cq) = acc[tap];
+    __syncthreads();
+    for (int st = DW_PL / 2; st > 0; st >>= 1) {
+        if (pl < st) {
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                f32x4* a = (f32x4*)(red + (pl * 9 + tap) * DW_CG + cq);
+                const f32x4 b = *(const f32x4*)(red + ((pl + st) * 9 + tap) * DW_CG + cq);
+                f32x4 v = *a;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = v[k] + b[k];
+                *a = v;
+            }
+        }
+        __syncthreads();
+    }
+    if (pl == 0 && c_in) {
+        float* part = p.partial + (size_t)blockIdx.y * 9 * p.C;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) *(f32x4*)(part + tap * p.C + c) = *(const f32x4*)(red + tap * DW_CG + cq);
+    }
+}
+
+// pixel ranges of at least 64 pixels, as many as bring the grid to about four workgroups per CU (as wgrad_plan)
+void dw_wgrad_plan(int64_t M, int C, int* splits, int* chunk) {
+    const int64_t groups = (C + DW_CG - 1) / DW_CG;
+    int64_t sp = (1024 + groups - 1) / groups;
+    const int64_t max_sp = (M + 63) / 64;
+    if (sp > max_sp) sp = max_sp;
+    if (sp < 1) sp = 1;
+    const int64_t ch = ((M + sp - 1) / sp + DW_PL - 1) / DW_PL * DW_PL;
+    *chunk = (int)ch;
+    *splits = (int)((M + ch - 1) / ch);
+}
+
+hipError_t launch_dw_wgrad(const DwGradParams& p, hipStream_t s) {
+    const int64_t M = (int64_t)p.N * p.H * p.W;
+    if (!dw_grad_shape_ok(p) || !quad_ok(p.x, p.x_ld) || p.C > p.x_ld || !quad_ok(p.partial, 4) || p.splits < 1 || p.splits > 65535 ||
+        p.chunk < DW_PL || (p.chunk % DW_PL) || (int64_t)p.splits * p.chunk < M)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dw_wgrad_kernel, dim3((unsigned)((p.C + DW_CG - 1) / DW_CG), (unsigned)p.splits), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) dw_wgrad_reduce_kernel(DwGradParams p, float* dw, int accumulate) {
+    const int i = blockIdx.x * 256 + threadIdx.x;      // thread i = tap * C + c: neighbouring lanes read neighbouring partials
+    if (i >= 9 * p.C) return;
+    const int tap = i / p.C, c = i % p.C;
+    float sum = 0.0f;
+    for (int z = 0; z < p.splits; ++z) sum += p.partial[(size_t)z * 9 * p.C + i];
+    float* d = dw + c * 9 + tap;                       // OIHW (C, 1, 3, 3)
+    *d = accumulate ? *d + sum : sum;
+}
+hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, int accumulate, hipStream_t s) {
+    if (p.C < 1 || p.splits < 1 || !p.partial || !dw) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((unsigned)((9 * p.C + 255) / 256)), dim3(256), 0, s, p, dw, accumulate);
     return hipGetLastError();
 }
 

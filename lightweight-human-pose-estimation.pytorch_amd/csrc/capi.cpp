@@ -101,6 +101,7 @@ struct lwp_context {
     // stage backward (lwp_train_forward / lwp_stage_backward; f32 handles): the retaining buffer plan, its activation and
     // gradient buffers, the gradient array's layout, the raw stage parameters (the BatchNorm chain rule needs them unfolded)
     TrainPlan tp;
+    int scope = LWP_TRAIN_STAGES;                    // lwp_set_train_scope: which parameters the plan, the gradient array and the optimiser cover
     std::vector<DevBuf> tbufs, gbufs;                // (a gradient buffer has the size of its activation buffer)
     int train_N = 0, train_H = 0, train_W = 0;      // frames of the last retaining forward (0: none)
     struct GradSpec { std::string key; int64_t shape[4]; int ndim; size_t off; };
@@ -112,6 +113,8 @@ struct lwp_context {
     bool raw_loaded = false;                         // false after lwp_weights_blob_import: a blob holds folded weights only
     DevBuf d_bwd; size_t bwd_fold_off = 0;           // wgrad partials, then the folded gradients of one BatchNorm layer
     std::vector<int> bwd_splits;                     // per layer: pixel splits its last wgrad ran with
+    std::vector<int> bwd_dw_splits;                  // per layer: pixel splits of its last depthwise wgrad (L_DW, L_DWPW)
+    std::vector<DwRepack> dw_repack;                 // the cpm trunk's depthwise / fused layers of the repack (LWP_TRAIN_CPM)
     // stage fine-tuning step (lwp_stage_adam_step): exp_avg then exp_avg_sq in one allocation, the step count, and the two
     // device tables the host builds once per handle (parameter chunks of the Adam kernel, layer descriptors of the repack)
     DevBuf d_adam; size_t adam_sq_off = 0;
@@ -159,20 +162,27 @@ Skeleton default_skeleton() {              // modules/keypoints.py:5-8
 
 // the stage parameters that receive a gradient, in lwp_param_spec order (running statistics and counters excluded)
 static bool is_stage_key(const std::string& k) { return k.rfind("initial_stage.", 0) == 0 || k.rfind("refinement_stages.", 0) == 0; }
-static std::vector<lwp_context::GradSpec> stage_grad_spec(int nref, int C, int NH, int NP, size_t* total) {
+static bool is_cpm_key(const std::string& k) { return k.rfind("cpm.", 0) == 0; }
+// LWP_TRAIN_CPM: the ten cpm.* parameters first, then the stage parameters (the unchanged tail, shifted by the cpm total)
+static std::vector<lwp_context::GradSpec> train_grad_spec(int scope, int nref, int C, int NH, int NP, size_t* total) {
     std::vector<lwp_context::GradSpec> v;
     size_t off = 0;
-    for (const ParamSpec& p : param_table(nref, C, NH, NP)) {
-        if (!is_stage_key(p.key) || p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR || p.role == LWP_ROLE_BN_NBT) continue;
-        lwp_context::GradSpec s;
-        s.key = p.key; s.ndim = p.ndim; s.off = off;
-        size_t n = 1;
-        for (int d = 0; d < 4; ++d) { s.shape[d] = p.shape[d]; if (d < p.ndim) n *= (size_t)p.shape[d]; }
-        off += n;
-        v.push_back(s);
-    }
+    const std::vector<ParamSpec> table = param_table(nref, C, NH, NP);
+    for (int part = scope == LWP_TRAIN_CPM ? 0 : 1; part < 2; ++part)
+        for (const ParamSpec& p : table) {
+            if (!(part == 0 ? is_cpm_key(p.key) : is_stage_key(p.key)) || p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR || p.role == LWP_ROLE_BN_NBT) continue;
+            lwp_context::GradSpec s;
+            s.key = p.key; s.ndim = p.ndim; s.off = off;
+            size_t n = 1;
+            for (int d = 0; d < 4; ++d) { s.shape[d] = p.shape[d]; if (d < p.ndim) n *= (size_t)p.shape[d]; }
+            off += n;
+            v.push_back(s);
+        }
     if (total) *total = off;
     return v;
+}
+static std::vector<lwp_context::GradSpec> stage_grad_spec(int nref, int C, int NH, int NP, size_t* total) {
+    return train_grad_spec(LWP_TRAIN_STAGES, nref, C, NH, NP, total);
 }
 
 static int fail(lwp_context* h, int code, const std::string& msg) {
@@ -271,6 +281,25 @@ extern "C" const char* lwp_last_error(lwp_handle h) {
     return g_err.c_str();
 }
 
+// the retaining plan, its (empty) buffers and the gradient layout of a scope; the caller has made sure nothing still runs on them
+static void apply_train_scope(lwp_context* h, int scope) {
+    const Graph& g = h->g;
+    h->scope = scope;
+    h->tp = build_train_plan(g, scope);
+    h->tbufs = std::vector<DevBuf>(h->tp.bufs.size());
+    h->gbufs = std::vector<DevBuf>(h->tp.bufs.size());
+    h->gspec = train_grad_spec(scope, g.nref, g.C, g.NH, g.NP, &h->grad_floats);
+    h->grad_off.clear();
+    for (const auto& s : h->gspec) h->grad_off[s.key] = s.off;
+    h->bwd_splits.assign(g.layers.size(), 0);
+    h->bwd_dw_splits.assign(g.layers.size(), 0);
+    h->train_N = h->train_H = h->train_W = 0;
+    h->d_adam = DevBuf(); h->adam_sq_off = 0; h->adam_t = 0;
+    h->d_adam_chunks = DevBuf(); h->adam_chunks = 0;
+    h->d_repack = DevBuf(); h->repack_layers = h->repack_blocks = 0;
+    h->dw_repack.clear();
+}
+
 extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dtype, lwp_handle* out) {
     if (!out) return fail(nullptr, LWP_ERR_ARG, "out is null");
     *out = nullptr;
@@ -315,16 +344,20 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
     }
     h->bufs.resize(h->g.bufs.size());
     if (dtype == LWP_F32) {
-        h->tp = build_train_plan(h->g);
-        h->tbufs.resize(h->tp.bufs.size());
-        h->gbufs.resize(h->tp.bufs.size());
-        h->gspec = stage_grad_spec(nref, C, NH, NP, &h->grad_floats);
-        for (const auto& s : h->gspec) h->grad_off[s.key] = s.off;
+        apply_train_scope(h, LWP_TRAIN_STAGES);
+        // the raw parameters do not move with the scope: the stage parameters in the stage gradient layout, the BatchNorm
+        // running statistics, then (16-byte aligned) the cpm parameters
         h->raw_off = h->grad_off;
         h->raw_floats = h->grad_floats;
         for (const ParamSpec& p : param_table(nref, C, NH, NP))
             if (is_stage_key(p.key) && (p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR)) { h->raw_off[p.key] = h->raw_floats; h->raw_floats += (size_t)p.shape[0]; }
-        h->bwd_splits.assign(h->g.layers.size(), 0);
+        h->raw_floats = (h->raw_floats + 3) / 4 * 4;
+        for (const auto& s : train_grad_spec(LWP_TRAIN_CPM, nref, C, NH, NP, nullptr)) {
+            if (!is_cpm_key(s.key)) continue;
+            size_t n = 1;
+            for (int d = 0; d < s.ndim; ++d) n *= (size_t)s.shape[d];
+            h->raw_off[s.key] = h->raw_floats; h->raw_floats += n;
+        }
     }
     h->d_outs.resize(2 * (1 + nref));
     *out = h;
@@ -814,6 +847,15 @@ static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, in
     return LWP_OK;
 }
 
+// the depthwise half of a level-3 L_DWPW block alone, into train buffer `buf` (the retained copy of lwp_train_forward)
+static int enqueue_dw_copy(lwp_context* h, const Layer& l, int buf, int N, int fh, int fw) {
+    DwParams p{buf_at(h, l.src), l.src.ld, h->blob(l.w_off), h->blob(l.b_off), h->tbufs[buf - (int)h->g.bufs.size()].as<float>(), l.cin,
+               N, fh, fw, fh, fw, l.cin, l.stride, l.dil, l.act};
+    p.tune = &h->tune;
+    LAUNCH(h, KC_DW, launch_dw(p, h->stream));
+    return LWP_OK;
+}
+
 // THE walk over a layer list: layers [begin, end) of `ls` (the graph's list, or the retaining plan's) on the handle's stream.
 // A step the graph marked as fusable (Layer::fuse) is taken as one launch only if all its layers lie inside the range.
 // d_outs_nchw: 2*(1+nref) device pointers or null.  retain (lwp_train_forward): a fused head pair is preceded by a stand-alone
@@ -832,6 +874,22 @@ static int enqueue_forward(lwp_context* h, const std::vector<Layer>& ls, int beg
             if (!rc) rc = enqueue_heads_pair(h, ls[i], ls[i + 1], N, H, W, d_outs_nchw);
             ++i;
             continue;
+        }
+        if (retain && &ls == &h->tp.layers) {
+            // cpm tensors a fused launch never stores (LWP_TRAIN_CPM): the depthwise half of an L_DWPW block from a stand-alone
+            // launch_dw on the block's input, the pointwise output in front of the residual add from the same launch without it
+            if (h->tp.dw_copy[i] >= 0) {
+                rc = enqueue_dw_copy(h, ls[i], h->tp.dw_copy[i], N, fh, fw);
+                if (rc) break;
+            }
+            if (h->tp.nores_copy[i] >= 0) {
+                Layer c = ls[i];
+                c.res = BufRef();
+                c.dst.buf = h->tp.nores_copy[i]; c.dst.coff = 0;
+                c.out_index = c.out_index2 = -1;
+                rc = enqueue_layer(h, c, d_in, N, H, W, nullptr);
+                if (rc) break;
+            }
         }
         // a marked 1x1 rides in this 3x3's epilogue if the launcher takes it (GemmParams::fused2)
         bool folded = false;
@@ -2300,11 +2358,12 @@ static int ensure_train_buffers(lwp_context* h, int N, int H, int W) {
     bool synced = false;
     for (size_t i = 0; i < h->tp.bufs.size(); ++i) {
         const size_t bytes = (size_t)N * fh * fw * h->tp.bufs[i].channels * sizeof(float);
-        const bool grow = bytes > h->tbufs[i].size() || bytes > h->gbufs[i].size();
+        const bool with_grad = h->tp.grad_mode[i] == TrainPlan::GRAD_ALWAYS;     // (GRAD_ON_DEMAND: stage_backward_prepare)
+        const bool grow = bytes > h->tbufs[i].size() || (with_grad && bytes > h->gbufs[i].size());
         if (grow) {
             if (!synced) { HIP_TRY(h, hipStreamSynchronize(h->stream)); synced = true; }
             HIP_TRY(h, h->tbufs[i].ensure(bytes));
-            HIP_TRY(h, h->gbufs[i].ensure(bytes));
+            if (with_grad) HIP_TRY(h, h->gbufs[i].ensure(bytes));
         }
         // pad channels of a concat buffer are read with zero weights: finite at every geometry (as in ensure_activations)
         if (h->tp.bufs[i].has_pad && (grow || N != h->train_N || H != h->train_H || W != h->train_W))
@@ -2338,11 +2397,11 @@ extern "C" int lwp_train_forward(lwp_handle h, const float* in_device, int N, in
     h->train_N = 0;
     rc = order_in(h);
     if (rc) return rc;
-    // stem, backbone and cpm up to cpm.conv's input: the graph's own plan, nothing retained; then the retaining plan, with
-    // the outputs of the kernels Engine.forward uses
+    // the layers in front of the plan's cut (cpm.conv, or the backbone's last layer in scope LWP_TRAIN_CPM): the graph's own
+    // plan, nothing retained; then the retaining plan, with the outputs of the kernels Engine.forward uses
     const TrainPlan& tp = h->tp;
-    rc = enqueue_forward(h, h->g.layers, 0, tp.cpm_conv, in_device, N, H, W, nullptr);
-    if (!rc) rc = enqueue_forward(h, tp.layers, tp.cpm_conv, tp.cpm_conv + 1, in_device, N, H, W, outs_device, true);
+    rc = enqueue_forward(h, h->g.layers, 0, tp.cut, in_device, N, H, W, nullptr);
+    if (!rc) rc = enqueue_forward(h, tp.layers, tp.cut, tp.cpm_conv + 1, in_device, N, H, W, outs_device, true);
     if (rc) return rc;
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);
@@ -2363,6 +2422,7 @@ struct BackwardArgs {
     int N, hs, ws, batch_size, accumulate;
     double loss_scale;
     float* grads; float* d_features;
+    float* d_backbone = nullptr;       // LWP_TRAIN_CPM: the gradient at the cpm's input, N x 512 x hs x ws, or null
 };
 
 static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
@@ -2371,6 +2431,8 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     if (rc) return rc;
     if (!a.keypoint_maps || !a.paf_maps || !a.mask || !a.grads) return fail(h, LWP_ERR_ARG, "keypoint_maps / paf_maps / mask / grads_device is null");
     if (a.batch_size < 1) return fail(h, LWP_ERR_ARG, "batch_size must be at least 1");
+    if (a.d_backbone && h->scope != LWP_TRAIN_CPM)
+        return fail(h, LWP_ERR_ARG, "d_backbone_device needs the train scope LWP_TRAIN_CPM (lwp_set_train_scope): in scope LWP_TRAIN_STAGES the cpm has no backward");
     if (!std::isfinite(a.loss_scale)) return fail(h, LWP_ERR_ARG, "loss_scale must be finite");
     if (h->skel.K + 1 != h->g.NH || 2 * h->skel.L != h->g.NP) {
         snprintf(msg, sizeof msg, "the skeleton's targets have %d + 1 heat-map and 2 x %d PAF channels, the network's tensors %d and %d",
@@ -2388,14 +2450,21 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     // workspace: the largest layer's wgrad partials + the folded gradients of the largest BatchNorm layer
     const int64_t M = (int64_t)a.N * a.hs * a.ws;
     size_t part = 0, fold = 0;
-    for (size_t i = (size_t)h->tp.cpm_conv + 1; i < h->tp.layers.size(); ++i) {
+    for (size_t i = (size_t)h->tp.cut + 1; i < h->tp.layers.size(); ++i) {
         const Layer& l = h->tp.layers[i];
+        const int ks = l.kind == L_DWPW ? 1 : l.ks;               // the pointwise half of a fused block
         auto one = [&](int cout, int cin) {
             WgradParams w{};
-            w.cout = cout; w.cin = cin; w.ks = l.ks;
-            wgrad_plan(M, cout, cin, l.ks, &w.splits, &w.chunk);
+            w.cout = cout; w.cin = cin; w.ks = ks;
+            wgrad_plan(M, cout, cin, ks, &w.splits, &w.chunk);
             part = std::max(part, wgrad_partial_floats(w));
         };
+        if (l.kind == L_DW || l.kind == L_DWPW) {
+            int sp = 0, ch = 0;
+            dw_wgrad_plan(M, l.cin, &sp, &ch);
+            part = std::max(part, (size_t)sp * 9 * l.cin);
+            if (l.kind == L_DW) continue;
+        }
         if (l.blocks.empty()) one(l.cout, l.cin);
         else for (const WBlock& b : l.blocks) one(b.cout, b.cin);
         if (!l.bn_key.empty()) fold = std::max(fold, (size_t)l.cout * l.cin * l.ks * l.ks + l.cout);
@@ -2407,22 +2476,32 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         HIP_TRY(h, h->d_bwd.ensure(need));
     }
+    if (a.d_backbone) {                                // the 512-channel gradient at the cpm's input exists only once it is asked for
+        const int xb = h->tp.layers[h->tp.cut].dst.buf - (int)h->g.bufs.size();
+        if (h->gbufs[xb].size() < h->tbufs[xb].size()) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, h->gbufs[xb].ensure(h->tbufs[xb].size()));
+        }
+    }
     return order_in(h);
 }
 
 // wgrad of one conv (a whole layer, or one source conv of a merged head layer): partials, fixed-order reduction, and the
 // BatchNorm chain rule where the layer has one
+// (pointwise: the 1x1 half of an L_DWPW block, conv_key its conv2_key; a conv without bias has no bias row and no db)
 static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const float* x, int x_ld, int cout, int cin,
-                         const std::string& conv_key, const BackwardArgs& a, size_t fold_off) {
+                         const std::string& conv_key, const BackwardArgs& a, size_t fold_off, bool pointwise = false) {
+    const bool has_bias = !pointwise && l.has_bias;
     WgradParams w{};
     w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd.as<float>();
-    w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = l.ks; w.dil = l.dil;
-    wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, l.ks, &w.splits, &w.chunk);
+    w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = pointwise ? 1 : l.ks; w.dil = pointwise ? 1 : l.dil;
+    w.no_bias = has_bias ? 0 : 1;
+    wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, w.ks, &w.splits, &w.chunk);
     h->bwd_splits[layer_index] = w.splits;
     LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream));
     float* dw = a.grads + h->grad_off.at(conv_key + ".weight");
-    float* db = a.grads + h->grad_off.at(conv_key + ".bias");
-    if (l.bn_key.empty()) {
+    float* db = has_bias ? a.grads + h->grad_off.at(conv_key + ".bias") : nullptr;
+    if (pointwise || l.bn_key.empty()) {
         LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, dw, db, a.accumulate, h->stream));
         return LWP_OK;
     }
@@ -2438,6 +2517,26 @@ static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const 
     b.dgamma = a.grads + h->grad_off.at(l.bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(l.bn_key + ".bias");
     b.cout = cout; b.K = cin * l.ks * l.ks; b.accumulate = a.accumulate;
     LAUNCH(h, BK_REDUCE, launch_bn_chain(b, h->stream));
+    return LWP_OK;
+}
+
+// depthwise 3x3 of the cpm trunk (an L_DW layer, or the first half of an L_DWPW block): dz is the gradient at its ELU output y
+static int enqueue_dw_backward(lwp_context* h, const Layer& l, int layer_index, float* dz, int dz_ld, const float* y, int y_ld,
+                               const BackwardArgs& a, std::vector<char>& written) {
+    const int nb = (int)h->g.bufs.size();
+    const int64_t M = (int64_t)a.N * a.hs * a.ws;
+    LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(dz, dz_ld, y, y_ld, M, l.cin, h->stream));
+    DwGradParams p{};
+    p.dz = dz; p.dz_ld = dz_ld; p.x = buf_at(h, l.src); p.x_ld = l.src.ld; p.w = h->blob(l.w_off);
+    p.dx = grad_at(h, l.src); p.dx_ld = l.src.ld; p.partial = h->d_bwd.as<float>();
+    p.N = a.N; p.H = a.hs; p.W = a.ws; p.C = l.cin; p.beta = written[l.src.buf - nb];
+    dw_wgrad_plan(M, l.cin, &p.splits, &p.chunk);
+    h->bwd_dw_splits[layer_index] = p.splits;
+    if (l.kind == L_DW) h->bwd_splits[layer_index] = p.splits;
+    LAUNCH(h, BK_WGRAD, launch_dw_wgrad(p, h->stream));
+    LAUNCH(h, BK_REDUCE, launch_dw_wgrad_reduce(p, a.grads + h->grad_off.at(l.conv_key + ".weight"), a.accumulate, h->stream));
+    LAUNCH(h, BK_DGRAD, launch_dw_dgrad(p, h->stream));
+    written[l.src.buf - nb] = 1;
     return LWP_OK;
 }
 
@@ -2468,15 +2567,48 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
     }
     // 2. the layers in reverse.  A gradient buffer's first writer overwrites, later ones add: the launch order is the summation order.
     std::vector<char> written(tp.bufs.size(), 0);
-    for (int i = (int)tp.layers.size() - 1; i > tp.cpm_conv; --i) {
+    for (int i = (int)tp.layers.size() - 1; i > tp.cut; --i) {
         const Layer& l = tp.layers[i];
         h->cur_layer = i;
         float* dy = grad_at(h, l.dst);
         const float* y = buf_at(h, l.dst);
-        if (l.res.buf >= 0) {                  // out = relu(z) + res: the residual branch takes the gradient as it is
+        if (i == tp.cpm_conv && tp.cut != tp.cpm_conv) {
+            // LWP_TRAIN_CPM: cpm.conv's output feeds the initial stage and every refinement stage; its gradient is their sum in
+            // stage order (step 3 below does the same for d_features, on the same values in the same order)
+            for (int k = 1; k < g.nref; ++k)
+                LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(dy, catc, h->gbufs[tp.cats[k] - nb].as<float>(), catc, M, C, 1, h->stream));
+            if (a.d_features) LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(dy, catc, a.d_features, a.N, a.hs * a.ws, C, h->stream));
+        }
+        if (l.res.buf >= 0) {                  // out = act(z) + res: the residual branch takes the gradient as it is
             LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(grad_at(h, l.res), l.res.ld, dy, l.dst.ld, M, l.cout, written[l.res.buf - nb], h->stream));
             written[l.res.buf - nb] = 1;
         }
+        // the ELU output in front of a residual add is the retained copy of the launch without it
+        const float* y_elu = tp.nores_copy[i] >= 0 ? h->tbufs[tp.nores_copy[i] - nb].as<float>() : y;
+        if (l.kind == L_DW) {
+            const int rc = enqueue_dw_backward(h, l, i, dy, l.dst.ld, y, l.dst.ld, a, written);
+            if (rc) { h->cur_layer = -1; return rc; }
+            continue;
+        }
+        if (l.kind == L_DWPW) {
+            // the pointwise half (raw (cout, C) weights: the blob holds them in fragment order only; without BatchNorm the raw
+            // values are the folded ones), then the depthwise half on the retained copy of its output
+            const float* dcopy = h->tbufs[tp.dw_copy[i] - nb].as<float>();
+            float* gd = h->gbufs[tp.dw_copy[i] - nb].as<float>();
+            LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(dy, l.dst.ld, y_elu, l.dst.ld, M, l.cout, h->stream));
+            int rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, dcopy, l.cin, l.cout, l.cin, l.conv2_key, a, fold_off, true);
+            if (rc) { h->cur_layer = -1; return rc; }
+            DgradParams d{};
+            d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->raw(l.conv2_key + ".weight");
+            d.dx = gd; d.dx_ld = l.cin;
+            d.N = a.N; d.H = a.hs; d.W = a.ws;
+            d.cout = l.cout; d.cout_pad = l.cout; d.cin = l.cin; d.cin_pad = l.cin; d.ks = 1; d.dil = 1; d.acc_from = l.cin;
+            LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+            rc = enqueue_dw_backward(h, l, i, gd, l.cin, dcopy, l.cin, a, written);
+            if (rc) { h->cur_layer = -1; return rc; }
+            continue;
+        }
+        if (l.act == ACT_ELU) LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(dy, l.dst.ld, y_elu, l.dst.ld, M, l.cout, h->stream));
         if (l.act == ACT_RELU)
             LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(dy, l.dst.ld, y, l.dst.ld, l.res.buf >= 0 ? buf_at(h, l.res) : nullptr, l.res.ld, M, l.cout, h->stream));
         const float* x = buf_at(h, l.src);
@@ -2488,6 +2620,7 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
                 if (rc) break;
             }
         if (rc) { h->cur_layer = -1; return rc; }
+        if (i == tp.cut + 1 && h->scope == LWP_TRAIN_CPM && !a.d_backbone) continue;      // cpm.align's dgrad is 512 wide: only when asked for
         const bool is_cat = std::find(tp.cats.begin(), tp.cats.end(), l.src.buf) != tp.cats.end();
         DgradParams d{};
         d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->blob(l.w_off);
@@ -2501,7 +2634,11 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
     }
     h->cur_layer = -1;
     // 3. backbone_features feeds the initial stage and every refinement stage: stage order, then NCHW
-    if (a.d_features) {
+    if (a.d_backbone) {
+        const BufRef& xin = tp.layers[tp.cut].dst;
+        LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(grad_at(h, xin), xin.ld, a.d_backbone, a.N, a.hs * a.ws, tp.layers[tp.cut].cout, h->stream));
+    }
+    if (a.d_features && tp.cut == tp.cpm_conv) {
         float* g0 = h->gbufs[tp.cats[0] - nb].as<float>();
         for (int k = 1; k < g.nref; ++k)
             LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(g0, catc, h->gbufs[tp.cats[k] - nb].as<float>(), catc, M, C, 1, h->stream));
@@ -2519,6 +2656,35 @@ extern "C" int lwp_stage_backward(lwp_handle h, const float* keypoint_maps, cons
     if (rc) return rc;
     bool ordered = false;
     return order_out(h, h->stream, &ordered);
+}
+
+extern "C" int lwp_train_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
+                                  int batch_size, double loss_scale, int accumulate, float* grads_device, float* d_features_device,
+                                  float* d_backbone_device) {
+    const BackwardArgs a{keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, accumulate, loss_scale, grads_device, d_features_device, d_backbone_device};
+    int rc = stage_backward_prepare(h, a);
+    if (rc) return rc;
+    rc = enqueue_stage_backward(h, a);
+    if (rc) return rc;
+    bool ordered = false;
+    return order_out(h, h->stream, &ordered);
+}
+
+extern "C" int lwp_set_train_scope(lwp_handle h, int scope) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (h->dtype != LWP_F32) return fail(h, LWP_ERR_ARG, "the train scope belongs to fp32 handles only (this one is bf16 / fp16)");
+    if (scope != LWP_TRAIN_STAGES && scope != LWP_TRAIN_CPM) return fail(h, LWP_ERR_ARG, "unknown train scope (LWP_TRAIN_STAGES or LWP_TRAIN_CPM)");
+    for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending: fetch it before changing the train scope");
+    if (h->async_pending) return fail(h, LWP_ERR_STATE, "an lwp_infer_poses_async is pending: fetch it before changing the train scope");
+    if (h->adam_t > 0)
+        return fail(h, LWP_ERR_STATE, "the optimiser has taken steps: the moments are laid out for the current scope (lwp_stage_adam_reset first, or set the scope before the first step)");
+    if (scope == h->scope) { h->train_N = 0; return LWP_OK; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = order_in(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the plan's buffers and the optimiser tables are released below
+    apply_train_scope(h, scope);
+    return LWP_OK;
 }
 
 extern "C" int lwp_profile_stage_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs,
@@ -2568,14 +2734,47 @@ extern "C" int lwp_stage_grad_spec(int nref, int C, int NH, int NP, int index, c
     return LWP_OK;
 }
 
+static bool train_shape_ok(int scope, int nref, int C, int NH, int NP) {
+    return (scope == LWP_TRAIN_STAGES || scope == LWP_TRAIN_CPM) && nref >= 0 && C > 0 && NH > 0 && NP > 0;
+}
+extern "C" int lwp_train_grad_count(int scope, int nref, int C, int NH, int NP, int64_t* total_floats) {
+    if (!train_shape_ok(scope, nref, C, NH, NP)) return LWP_ERR_ARG;
+    size_t total = 0;
+    const int n = (int)train_grad_spec(scope, nref, C, NH, NP, &total).size();
+    if (total_floats) *total_floats = (int64_t)total;
+    return n;
+}
+
+extern "C" int lwp_train_grad_spec(int scope, int nref, int C, int NH, int NP, int index, char* name, int name_cap, int64_t shape[4], int* ndim,
+                                   int64_t* offset) {
+    if (!train_shape_ok(scope, nref, C, NH, NP) || !name || !shape || !ndim || !offset) return fail(nullptr, LWP_ERR_ARG, "bad argument");
+    const auto t = train_grad_spec(scope, nref, C, NH, NP, nullptr);
+    if (index < 0 || index >= (int)t.size()) return fail(nullptr, LWP_ERR_ARG, "index out of range");
+    if ((int)t[index].key.size() + 1 > name_cap) return fail(nullptr, LWP_ERR_ARG, "name buffer too small");
+    std::strcpy(name, t[index].key.c_str());
+    for (int d = 0; d < 4; ++d) shape[d] = t[index].shape[d];
+    *ndim = t[index].ndim;
+    *offset = (int64_t)t[index].off;
+    return LWP_OK;
+}
+
 extern "C" int lwp_debug_train_activation(lwp_handle h, int idx, float* dst, size_t dst_floats, int out_dims[4]) {
+    return lwp_debug_train_copy(h, idx, LWP_KEPT_OUTPUT, dst, dst_floats, out_dims);
+}
+
+extern "C" int lwp_debug_train_copy(lwp_handle h, int idx, int which, float* dst, size_t dst_floats, int out_dims[4]) {
     int rc = train_handle_check(h);
     if (rc) return rc;
     if (!dst || !out_dims) return fail(h, LWP_ERR_ARG, "bad argument");
-    if (idx < h->tp.cpm_conv || idx >= (int)h->tp.layers.size()) return fail(h, LWP_ERR_ARG, "layer_index is not cpm.conv or a stage layer");
+    if (idx < h->tp.cut || idx >= (int)h->tp.layers.size()) return fail(h, LWP_ERR_ARG, "layer_index is not a layer of the retaining plan");
+    if (which != LWP_KEPT_OUTPUT && which != LWP_KEPT_DEPTHWISE && which != LWP_KEPT_NO_RESIDUAL) return fail(h, LWP_ERR_ARG, "unknown kind of retained tensor");
+    if ((which == LWP_KEPT_DEPTHWISE && h->tp.dw_copy[idx] < 0) || (which == LWP_KEPT_NO_RESIDUAL && h->tp.nores_copy[idx] < 0))
+        return fail(h, LWP_ERR_ARG, "the layer has no such retained copy");
     if (h->train_N < 1) return fail(h, LWP_ERR_ARG, "no retaining forward precedes this call (lwp_train_forward)");
     HIP_TRY(h, hipSetDevice(h->device));
-    const Layer& l = h->tp.layers[idx];
+    Layer l = h->tp.layers[idx];
+    if (which == LWP_KEPT_DEPTHWISE) { l.dst = BufRef(); l.dst.buf = h->tp.dw_copy[idx]; l.dst.ld = l.cin; l.cout = l.cin; }
+    if (which == LWP_KEPT_NO_RESIDUAL) { l.dst.buf = h->tp.nores_copy[idx]; l.dst.coff = 0; }
     int dh, dw;
     level_dims(h->train_H, h->train_W, 3, &dh, &dw);
     const size_t n = (size_t)h->train_N * l.cout * dh * dw;
@@ -2593,6 +2792,11 @@ extern "C" int lwp_debug_backward_splits(lwp_handle h, int idx) {
     return h->bwd_splits[idx];
 }
 
+extern "C" int lwp_debug_backward_dw_splits(lwp_handle h, int idx) {
+    if (!h || idx < 0 || idx >= (int)h->bwd_dw_splits.size()) return LWP_ERR_ARG;
+    return h->bwd_dw_splits[idx];
+}
+
 // ---------------------------------------------------------------------------------------------- stage fine-tuning step
 // train.py:41-55's parameter groups for the stage parameters: log2 of the learning-rate multiplier in bits 0-1, weight decay in bit 2
 static uint32_t stage_adam_group(const std::string& key, int role) {
@@ -2604,12 +2808,31 @@ static uint32_t stage_adam_group(const std::string& key, int role) {
     default: return 1u;                            // LWP_ROLE_BN_B
     }
 }
-static std::vector<uint32_t> stage_adam_groups(int nref, int C, int NH, int NP) {
+// train.py:46-48 with get_parameters.py for the cpm: conv weights with groups == 1 x1 with weight decay, conv biases x2
+// without, depthwise weights (cpm.trunk.j.0) x1 without
+static uint32_t cpm_adam_group(const std::string& key, int role) {
+    if (role == LWP_ROLE_CONV_B) return 1u;
+    const bool depthwise = key.rfind("cpm.trunk.", 0) == 0 && key.size() > 8 && key.compare(key.size() - 9, 9, ".0.weight") == 0;
+    return depthwise ? 0u : 4u;
+}
+static std::vector<uint32_t> train_adam_groups(int scope, int nref, int C, int NH, int NP) {
     std::vector<uint32_t> v;
-    for (const ParamSpec& p : param_table(nref, C, NH, NP))
-        if (is_stage_key(p.key) && p.role != LWP_ROLE_BN_MEAN && p.role != LWP_ROLE_BN_VAR && p.role != LWP_ROLE_BN_NBT)
-            v.push_back(stage_adam_group(p.key, p.role));
+    const std::vector<ParamSpec> table = param_table(nref, C, NH, NP);
+    for (int part = scope == LWP_TRAIN_CPM ? 0 : 1; part < 2; ++part)
+        for (const ParamSpec& p : table)
+            if ((part == 0 ? is_cpm_key(p.key) : is_stage_key(p.key)) && p.role != LWP_ROLE_BN_MEAN && p.role != LWP_ROLE_BN_VAR && p.role != LWP_ROLE_BN_NBT)
+                v.push_back(part == 0 ? cpm_adam_group(p.key, p.role) : stage_adam_group(p.key, p.role));
     return v;
+}
+static std::vector<uint32_t> stage_adam_groups(int nref, int C, int NH, int NP) { return train_adam_groups(LWP_TRAIN_STAGES, nref, C, NH, NP); }
+
+extern "C" int lwp_train_adam_group(int scope, int nref, int C, int NH, int NP, int index, int* lr_mult, int* weight_decay_on) {
+    if (!train_shape_ok(scope, nref, C, NH, NP) || !lr_mult || !weight_decay_on) return fail(nullptr, LWP_ERR_ARG, "bad argument");
+    const auto g = train_adam_groups(scope, nref, C, NH, NP);
+    if (index < 0 || index >= (int)g.size()) return fail(nullptr, LWP_ERR_ARG, "index out of range");
+    *lr_mult = 1 << (g[index] & 3u);
+    *weight_decay_on = (g[index] & 4u) ? 1 : 0;
+    return LWP_OK;
 }
 
 extern "C" int lwp_stage_adam_group(int nref, int C, int NH, int NP, int index, int* lr_mult, int* weight_decay_on) {
@@ -2633,7 +2856,7 @@ static int adam_handle_check(lwp_context* h) {
 // that starts off the 16-byte grid gets a head chunk up to the grid), and one descriptor per stage layer
 static int ensure_adam_tables(lwp_context* h) {
     if (h->d_adam_chunks) return LWP_OK;
-    const std::vector<uint32_t> groups = stage_adam_groups(h->g.nref, h->g.C, h->g.NH, h->g.NP);
+    const std::vector<uint32_t> groups = train_adam_groups(h->scope, h->g.nref, h->g.C, h->g.NH, h->g.NP);
     std::vector<AdamChunk> chunks;
     for (size_t i = 0; i < h->gspec.size(); ++i) {
         const auto& s = h->gspec[i];
@@ -2652,8 +2875,18 @@ static int ensure_adam_tables(lwp_context* h) {
     auto raw_at = [&](const std::string& k) { auto it = h->raw_off.find(k); return it == h->raw_off.end() ? -1 : (int)it->second; };
     std::vector<RepackLayer> tab;
     uint32_t blocks = 0;
-    for (size_t i = (size_t)h->tp.cpm_conv + 1; i < h->g.layers.size(); ++i) {
+    std::vector<DwRepack> dws;
+    for (size_t i = (size_t)h->tp.cut + 1; i < h->g.layers.size(); ++i) {
         const Layer& l = h->g.layers[i];
+        if ((l.kind == L_DW || l.kind == L_DWPW) && l.bn_key.empty() && l.bn2_key.empty()) {      // the cpm trunk (LWP_TRAIN_CPM)
+            DwRepack d{};
+            d.C = l.cin; d.cout = l.kind == L_DWPW ? l.cout : 0;
+            d.dw_raw = raw_at(l.conv_key + ".weight"); d.pw_raw = l.kind == L_DWPW ? raw_at(l.conv2_key + ".weight") : -1;
+            d.w_off = (uint32_t)l.w_off; d.b_off = (uint32_t)l.b_off; d.w2_off = (uint32_t)l.w2_off; d.b2_off = (uint32_t)l.b2_off;
+            if (d.dw_raw < 0 || (d.cout > 0 && d.pw_raw < 0)) return fail(h, LWP_ERR_STATE, "raw weights of '" + l.name + "' missing");
+            dws.push_back(d);
+            continue;
+        }
         if (l.kind != L_GEMM || l.blocks.size() > 2 || (!l.blocks.empty() && l.ks != 1) || l.cin_pad % 32 || l.cout_pad % 32)
             return fail(h, LWP_ERR_STATE, "stage layer '" + l.name + "' has no device repack");
         RepackLayer r{};
@@ -2686,6 +2919,7 @@ static int ensure_adam_tables(lwp_context* h) {
     HIP_TRY(h, hipMemcpy(d_chunks.as<void>(), chunks.data(), chunks.size() * sizeof(AdamChunk), hipMemcpyHostToDevice));
     h->d_repack = std::move(d_tab); h->repack_layers = (int)tab.size(); h->repack_blocks = (int)blocks;
     h->d_adam_chunks = std::move(d_chunks); h->adam_chunks = (int)chunks.size();
+    h->dw_repack = dws;
     return LWP_OK;
 }
 
@@ -2746,7 +2980,8 @@ extern "C" int lwp_stage_adam_step(lwp_handle h, const float* grads_device, doub
     LAUNCH(h, KC_OTHER, launch_stage_adam(p, h->stream));
     h->adam_t += 1;                                    // from here on the raw parameters and the state are those of step t
     h->train_N = 0;                                    // the retained activations belong to the old weights
-    const hipError_t e = launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
+    hipError_t e = launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
+    for (size_t k = 0; k < h->dw_repack.size() && e == hipSuccess; ++k) e = launch_dw_repack(h->dw_repack[k], h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
     if (e != hipSuccess) {                             // the blob no longer matches the raw parameters: no forward until lwp_load_weights
         h->weights_loaded = false;
         return fail(h, LWP_ERR_HIP, std::string("launch_stage_repack: ") + hipGetErrorString(e) + " (the weight blob is stale: load the weights again)");
@@ -2858,6 +3093,7 @@ extern "C" int lwp_time_stage_adam_step(lwp_handle h, const float* grads_device,
     if (!rc)
         rc = time_on_stream(h, iters, [&]() {
             LAUNCH(h, KC_OTHER, launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, raw.as<float>(), blob.as<float>(), h->stream));
+            for (const DwRepack& d : h->dw_repack) LAUNCH(h, KC_OTHER, launch_dw_repack(d, raw.as<float>(), blob.as<float>(), h->stream));
             return (int)LWP_OK; }, &ms[1]);
     (void)hipStreamSynchronize(h->stream);             // the scratch arrays are freed on return
     return rc;

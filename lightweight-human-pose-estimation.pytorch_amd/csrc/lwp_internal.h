@@ -79,13 +79,26 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
 // layer writes a buffer of its own, and every stage has its own [feat | heat | paf | pad] concat buffer (cats[s]: stage s's
 // heads write its heat / PAF window, refinement stage s + 1 reads it).  Buffer indices below Graph::bufs.size() are the
 // graph's own buffers; index Graph::bufs.size() + i is train buffer i (all at level 3).
+//
+// Scope LWP_TRAIN_CPM moves the cut from cpm.conv to the layer in front of cpm.align (the backbone's last layer, whose output
+// is the cpm's input): that layer and every cpm layer write buffers of their own too.  Two cpm tensors never leave a fused
+// launch and get a retained copy from a second launch (enqueue_forward): the depthwise output of an L_DWPW block
+// (dw_copy[i]: a buffer for a stand-alone launch_dw on the block's input) and the pointwise output of the block that adds
+// the residual `a` in its epilogue (nores_copy[i]: a buffer for the same launch without the residual).
 struct TrainPlan {
     std::vector<Layer> layers;     // Graph::layers with src / dst / res re-pointed
     std::vector<BufSpec> bufs;     // the train buffers
     std::vector<int> cats;         // nref + 1 concat buffers (plan indices)
-    int cpm_conv = -1;             // index of cpm.conv: layers before it run on the graph's own plan and retain nothing
+    int cpm_conv = -1;             // index of cpm.conv
+    int cut = -1;                  // layers before it run on the graph's own plan and retain nothing; the layers behind it have a
+                                   // backward.  LWP_TRAIN_STAGES: cpm.conv; LWP_TRAIN_CPM: the layer in front of cpm.align
+    std::vector<int> dw_copy, nores_copy;   // per layer: plan buffer index, -1: none
+    // per train buffer: does it have a gradient buffer?  GRAD_NEVER: a no-residual copy (only its values are read, as the
+    // ELU output); GRAD_ON_DEMAND: the cpm's 512-channel input, whose gradient exists only when lwp_train_backward is asked for it
+    enum { GRAD_ALWAYS = 0, GRAD_NEVER = 1, GRAD_ON_DEMAND = 2 };
+    std::vector<char> grad_mode;
 };
-TrainPlan build_train_plan(const Graph& g);
+TrainPlan build_train_plan(const Graph& g, int scope = LWP_TRAIN_STAGES);
 // f32 -> IEEE binary16 / bfloat16 bits, round to nearest even (fp16: subnormals exact, overflow -> inf, NaN stays NaN)
 uint16_t f32_to_f16_rne(float f);
 uint16_t f32_to_bf16_rne(float f);
@@ -417,6 +430,7 @@ struct WgradParams {
     float* partial;                  // [splits][taps][co_pad][ci_pad] weight partials, then [splits][co_pad] bias partials
     int N, H, W, cout, cin, ks, dil;
     int splits, chunk;               // pixel ranges [z * chunk, (z + 1) * chunk), chunk a multiple of 16
+    int no_bias;                     // != 0: a conv without bias (the cpm's pointwise layers): no bias row of workgroups, db not written
 };
 __host__ __device__ inline int wgrad_pad64(int v) { return (v + 63) / 64 * 64; }
 void wgrad_plan(int64_t M, int cout, int cin, int ks, int* splits, int* chunk);
@@ -426,6 +440,24 @@ inline size_t wgrad_partial_floats(const WgradParams& p) {
 hipError_t launch_wgrad(const WgradParams& p, hipStream_t s);
 // fixed-order sum of the partials into OIHW dw [cout][cin][taps] and db [cout]; accumulate: added to what is there
 hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int accumulate, hipStream_t s);
+// ---- cpm backward (with_mobilenet.py:7-21): ELU and depthwise 3x3 (stride 1, dilation 1, pad 1) gradients.  C is a multiple
+//      of 4, every row stride too, every pointer 16-byte aligned: a lane moves four consecutive channels of a pixel.
+// g = g * (y > 0 ? 1 : y + 1) over an M x C window, y the retained ELU output (alpha = 1: elu'(z) = exp(z) = y + 1 for z <= 0)
+hipError_t launch_elu_grad(float* g, int g_ld, const float* y, int y_ld, int64_t M, int C, hipStream_t s);
+struct DwGradParams {
+    const float* dz; int dz_ld;      // M x C gradient of the depthwise conv's pre-activation output
+    const float* x; int x_ld;        // wgrad: the retained input, M x C
+    const float* w;                  // dgrad: the forward blob's [9][C]
+    float* dx; int dx_ld;            // dgrad: M x C; beta != 0: added to, else overwritten
+    float* partial;                  // wgrad: [splits][9][C]
+    int N, H, W, C, beta;
+    int splits, chunk;               // wgrad: pixel ranges [z * chunk, (z + 1) * chunk), chunk a multiple of 16
+};
+void dw_wgrad_plan(int64_t M, int C, int* splits, int* chunk);
+hipError_t launch_dw_dgrad(const DwGradParams& p, hipStream_t s);
+hipError_t launch_dw_wgrad(const DwGradParams& p, hipStream_t s);
+// fixed-order sum of the partials into the OIHW (C, 1, 3, 3) gradient; accumulate: added to what is there
+hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, int accumulate, hipStream_t s);
 struct BnChainParams {               // BatchNorm at running statistics behind a conv: folded gradients -> raw ones (float64 inside)
     const float* G; const float* g;  // gradient of the folded weight [cout][K] and of the folded bias [cout]
     const float* W; const float* b;  // raw conv weight [cout][K] and bias
@@ -461,6 +493,12 @@ struct RepackLayer {                 // one fp32 L_GEMM layer: where its raw par
     RepackBlock blk[2];
 };
 hipError_t launch_stage_repack(const RepackLayer* tab_device, int n_layers, int n_blocks, const float* raw, float* blob, hipStream_t s);
+struct DwRepack {                    // one fp32 L_DW or L_DWPW layer without BatchNorm (the cpm trunk): float offsets into d_raw / the blob
+    int C, cout;                     // cout = 0: L_DW, no pointwise half
+    int dw_raw, pw_raw;
+    uint32_t w_off, b_off, w2_off, b2_off;
+};
+hipError_t launch_dw_repack(const DwRepack& l, const float* raw, float* blob, hipStream_t s);
 
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);

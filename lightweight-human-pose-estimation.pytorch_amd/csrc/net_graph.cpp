@@ -283,7 +283,7 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
     return g;
 }
 
-TrainPlan build_train_plan(const Graph& g) {
+TrainPlan build_train_plan(const Graph& g, int scope) {
     TrainPlan t;
     t.layers = g.layers;
     const int nb = (int)g.bufs.size();
@@ -294,13 +294,19 @@ TrainPlan build_train_plan(const Graph& g) {
         return nb + (int)t.bufs.size() - 1;
     };
     for (int s = 0; s <= g.nref; ++s) t.cats.push_back(new_buf(g.cat_channels, true));
-    for (size_t i = 0; i < t.layers.size(); ++i)
+    t.dw_copy.assign(t.layers.size(), -1);
+    t.nores_copy.assign(t.layers.size(), -1);
+    int align = -1;
+    for (size_t i = 0; i < t.layers.size(); ++i) {
         if (t.layers[i].name == "cpm.conv") t.cpm_conv = (int)i;
+        if (t.layers[i].name == "cpm.align") align = (int)i;
+    }
+    t.cut = scope == LWP_TRAIN_CPM ? align - 1 : t.cpm_conv;
     std::vector<int> cur(nb, -1);          // graph buffer -> the train buffer that holds its latest tensor
     int read_cat = 0;                      // the concat buffer a reader of the graph's concat buffer means
-    for (size_t i = (size_t)t.cpm_conv; i < t.layers.size(); ++i) {
+    for (size_t i = (size_t)t.cut; i < t.layers.size(); ++i) {
         Layer& l = t.layers[i];
-        if ((int)i > t.cpm_conv) {
+        if ((int)i > t.cut) {
             l.src.buf = l.src.buf == g.cat_buf ? t.cats[read_cat] : cur[l.src.buf];
             if (l.res.buf >= 0) l.res.buf = cur[l.res.buf];
         }
@@ -313,7 +319,14 @@ TrainPlan build_train_plan(const Graph& g) {
             l.dst.buf = new_buf(l.dst.ld, false);
             cur[old] = l.dst.buf;
         }
+        if ((int)i > t.cut && (int)i < t.cpm_conv) {                      // cpm layers with a backward (LWP_TRAIN_CPM only)
+            if (l.kind == L_DWPW) t.dw_copy[i] = new_buf(l.cin, false);
+            if (l.res.buf >= 0) t.nores_copy[i] = new_buf(l.dst.ld, false);
+        }
     }
+    t.grad_mode.assign(t.bufs.size(), TrainPlan::GRAD_ALWAYS);
+    for (int b : t.nores_copy) if (b >= 0) t.grad_mode[b - nb] = TrainPlan::GRAD_NEVER;
+    if (t.cut != t.cpm_conv) t.grad_mode[t.layers[t.cut].dst.buf - nb] = TrainPlan::GRAD_ON_DEMAND;
     return t;
 }
 

@@ -128,4 +128,37 @@ hipError_t launch_stage_repack(const RepackLayer* tab_device, int n_layers, int 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ repack, cpm trunk
+// An L_DW / L_DWPW layer without BatchNorm, as pack_weights writes it: the depthwise (C, 1, 3, 3) as [tap][C] with a zero bias
+// row, the pointwise (cout, C, 1, 1) in the f32 MFMA fragment order [C/32][cout/32][4][64 lanes][4] (lane (q = lane >> 4,
+// c = lane & 15) holds value v = 8 u + 2 j + t = W[n = 32 w + 16 t + c][k = 32 s + 16 u + 4 q + j]) with a zero bias row.  The
+// fold scale of a layer without BatchNorm is exactly 1.0, so pack_weights' float(double(w) * 1.0) is w itself: every element is
+// a plain copy of its raw value.  One thread per destination float.
+__global__ void __launch_bounds__(256) dw_repack_kernel(DwRepack l, const float* __restrict__ raw, float* __restrict__ blob) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned n_dw = 9u * l.C, n_pw = (unsigned)l.C * l.cout;
+    if (i < n_dw) {
+        const unsigned t = i / l.C, c = i % l.C;
+        blob[l.w_off + i] = raw[l.dw_raw + c * 9 + t];
+        if (t == 0) blob[l.b_off + c] = 0.f;
+        return;
+    }
+    const unsigned e = i - n_dw;
+    if (e >= n_pw) return;
+    const unsigned nw = l.cout / 32;
+    const unsigned v = ((e >> 8) & 3) * 4 + (e & 3), lane = (e >> 2) & 63;
+    const unsigned sw = e >> 10, s = sw / nw, wv = sw % nw;
+    const unsigned u = v >> 3, j = (v >> 1) & 3, t = v & 1, q = lane >> 4, c = lane & 15;
+    const unsigned k = 32 * s + 16 * u + 4 * q + j, n = 32 * wv + 16 * t + c;
+    blob[l.w2_off + e] = raw[l.pw_raw + (size_t)n * l.C + k];
+    if (e < (unsigned)l.cout) blob[l.b2_off + e] = 0.f;
+}
+
+hipError_t launch_dw_repack(const DwRepack& l, const float* raw, float* blob, hipStream_t s) {
+    if (l.C < 1 || l.dw_raw < 0 || (l.cout > 0 && (l.pw_raw < 0 || l.C % 32 || l.cout % 32))) return hipErrorInvalidValue;
+    const unsigned total = 9u * l.C + (unsigned)l.C * l.cout;
+    hipLaunchKernelGGL(dw_repack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, l, raw, blob);
+    return hipGetLastError();
+}
+
 }  // namespace lwp

@@ -2,7 +2,9 @@
 
 ``StageAdam(net)`` is ``torch.optim.Adam`` with train.py's parameter groups for every ``initial_stage.*`` /
 ``refinement_stages.*`` parameter of a drop-in net (fp32): conv weights x1 (initial) / x4 (refinement) with weight decay, conv
-biases x2 / x8, refinement BatchNorm weights x1 and biases x2 without.  The update and the refold / repack of the changed
+biases x2 / x8, refinement BatchNorm weights x1 and biases x2 without.  ``StageAdam(net, scope="cpm")`` also trains the cpm
+(train.py:46-48): its conv weights x1 with weight decay, its biases x2 and its depthwise weights x1 without; the engine's
+train scope is set on construction, ``val.train_step`` and the checkpoints below then cover the cpm.* keys too.  The update and the refold / repack of the changed
 layers into the forward's weight blob are HIP kernels behind ``lwp_stage_adam_step``: nothing travels through the host.
 
     opt = StageAdam(net, base_lr=4e-5, weight_decay=5e-4)
@@ -10,7 +12,7 @@ layers into the forward's weight blob are HIP kernels behind ``lwp_stage_adam_st
         losses = val.train_step(net, opt, images, labels, masks)
     opt.lr = opt.lr * 0.333            # MultiStepLR (train.py:60) is a line of Python
 
-Out of scope: the backbone and cpm (frozen: no backward, no update), BatchNorm train mode (running statistics never move), a
+Out of scope: the backbone (frozen: no backward, no update; so is the cpm in scope "stages"), BatchNorm train mode (running statistics never move), a
 16-bit optimiser, multi-GPU gradient reduction, amsgrad, and torch's optimiser checkpoints (``state_dict`` below has its own
 format, keyed by state-dict name; torch's is index-based and numbers the whole network).
 """
@@ -20,8 +22,12 @@ import numpy as np
 
 
 class StageAdam(object):
-    def __init__(self, net, base_lr=4e-5, weight_decay=5e-4, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, net, base_lr=4e-5, weight_decay=5e-4, betas=(0.9, 0.999), eps=1e-8, scope="stages"):
         self.net = net
+        from . import _lib
+        self.scope = _lib.train_scope_name(scope)
+        if net.engine.train_scope != self.scope:   # (refused once the engine's optimiser has taken a step: the moments have the old layout)
+            net.engine.set_train_scope(self.scope)
         self.lr = float(base_lr)              # the base learning rate; the groups' multipliers are applied by the kernel
         self.weight_decay = float(weight_decay)
         self.betas = (float(betas[0]), float(betas[1]))

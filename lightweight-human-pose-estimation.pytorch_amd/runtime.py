@@ -25,6 +25,9 @@ class Engine(object):
         self.device_id = device_id
         self._keep = None
         self.stage_steps = 0                  # adam_step calls so far: the drop-in net reads its stage parameters back when this moves
+        self.train_scope = "stages"           # set_train_scope: "stages" | "cpm"
+        self._scope_steps = 0                 # stage_steps when the current scope was set
+        self._left_params = {}                # parameters an earlier, wider scope trained and the current one does not cover
 
     # ------------------------------------------------------------------ stream ordering
     def _order(self, device=None, hand_over=True):
@@ -56,6 +59,8 @@ class Engine(object):
             shapes[i, :a.ndim] = a.shape
         check(lib().lwp_load_weights(self.h.ptr, c_names, c_ptrs, shapes.ctypes.data_as(C.POINTER(C.c_int64)),
                                      ndims.ctypes.data_as(C.POINTER(C.c_int)), n), self.h.ptr)
+        self._left_params = {}                # every parameter has just been replaced
+        self._scope_steps = self.stage_steps
 
     def weights_blob_bytes(self):
         n = C.c_size_t()
@@ -765,10 +770,30 @@ class Engine(object):
         check(lib().lwp_train_forward(self.h.ptr, x.data_ptr(), N, H, W, ptrs), self.h.ptr)
         return outs
 
+    def set_train_scope(self, scope):
+        """"stages" (the default): ``train_forward`` / ``stage_backward`` / ``adam_step`` cover initial_stage.* and
+        refinement_stages.*; "cpm": the cpm (cpm.align, cpm.trunk, cpm.conv) as well, its ten parameters in front of the stage
+        ones in every flat array.  The backbone stays frozen.  Raises RuntimeError once the optimiser has taken a step
+        (``load_adam_state(None)`` first, or set the scope before the first step).  The retained forward is invalidated.
+        Parameters the old scope has trained and the new one does not cover stay readable through ``trained_params``."""
+        name = _lib.train_scope_name(scope)
+        if name == self.train_scope:
+            check(lib().lwp_set_train_scope(self.h.ptr, _lib.train_scope(name)), self.h.ptr)
+            return
+        old = self.stage_params() if self.stage_steps != self._scope_steps else {}
+        check(lib().lwp_set_train_scope(self.h.ptr, _lib.train_scope(name)), self.h.ptr)
+        self.train_scope = name
+        self._gspec = None
+        self._scope_steps = self.stage_steps
+        covered = set(k for k, _, _ in self.grad_spec()[0])
+        self._left_params.update((k, v.clone()) for k, v in old.items() if k not in covered)
+        for k in covered:
+            self._left_params.pop(k, None)
+
     def grad_spec(self):
-        """([(state-dict key, shape, float offset)], total floats) of the flat gradient array."""
+        """([(state-dict key, shape, float offset)], total floats) of the flat gradient array, in the engine's train scope."""
         if getattr(self, "_gspec", None) is None:
-            self._gspec = _lib.stage_grad_spec(self.nref, self.C, self.NH, self.NP)
+            self._gspec = _lib.train_grad_spec(self.train_scope, self.nref, self.C, self.NH, self.NP)
         return self._gspec
 
     def grad_views(self, flat):
@@ -795,12 +820,14 @@ class Engine(object):
         return (self.h.ptr, km.data_ptr(), pm.data_ptr(), m.data_ptr(), N, hs, ws, int(N if batch_size is None else batch_size),
                 float(loss_scale)), flat, dfeat
 
-    def stage_backward(self, keypoint_maps, paf_maps, mask, batch_size=None, loss_scale=1.0, into=None, want_features=True):
+    def stage_backward(self, keypoint_maps, paf_maps, mask, batch_size=None, loss_scale=1.0, into=None, want_features=True, want_backbone=False):
         """Gradients of L = loss_scale * sum of the per-stage masked L2 losses (train.py:99-102) of the last ``train_forward``:
         returns (grads, d_features).  ``grads`` maps every initial_stage.* / refinement_stages.* state-dict key that has a
         gradient to a cuda tensor of the parameter's shape, all views of one flat array (``flat_of(grads)``); ``d_features`` is dL / d backbone_features (N, num_channels, h, w).  ``into``: a flat array from an
         earlier call (``Engine.flat_of(grads)``) to add to, like loss.backward() accumulates over train.py:96's batches.
-        The refinement BatchNorms stay at their running statistics: the reference network in eval() mode."""
+        The refinement BatchNorms stay at their running statistics: the reference network in eval() mode.
+        In train scope "cpm" the dict holds the cpm.* keys too, and ``want_backbone=True`` returns a third value: the gradient
+        at the cpm's input (N, 512, h, w)."""
         torch = _torch()
         total = self.grad_spec()[1]
         dev = torch.device("cuda", self.device_id)
@@ -809,6 +836,12 @@ class Engine(object):
         flat = into if into is not None else torch.empty(total, dtype=torch.float32, device=dev)
         args, flat, dfeat = self._backward_args(keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, want_features)
         self._order()
+        if want_backbone:
+            dback = torch.empty((dfeat.shape[0] if dfeat is not None else int(mask.shape[0]), 512) + tuple(int(v) for v in mask.shape[1:]),
+                                dtype=torch.float32, device=dev)
+            check(lib().lwp_train_backward(*args, 1 if into is not None else 0, flat.data_ptr(), None if dfeat is None else dfeat.data_ptr(),
+                                           dback.data_ptr()), self.h.ptr)
+            return self.grad_views(flat), dfeat, dback
         check(lib().lwp_stage_backward(*args, 1 if into is not None else 0, flat.data_ptr(), None if dfeat is None else dfeat.data_ptr()), self.h.ptr)
         return self.grad_views(flat), dfeat
 
@@ -830,26 +863,47 @@ class Engine(object):
         names = ("elementwise", "dgrad", "wgrad", "reduce")
         return dict((names[i], dict(ms=float(ms[i]), launches=int(n[i]))) for i in range(4))
 
-    def train_activation(self, layer_index):
-        """Retained output of a stage layer (or cpm.conv) from the last ``train_forward`` as NCHW float32 numpy (tests)."""
+    def cpm_activations(self):
+        """Train scope "cpm": the retained cpm tensors of the last ``train_forward`` as NCHW float32 numpy, by the oracle's tap
+        names: "model.11" (the cpm's input), "cpm.align", "cpm.trunk.j.dw", "cpm.trunk.j" (pointwise output after ELU, in front
+        of the residual add for j = 2), "cpm.sum" and "cpm" (tests)."""
+        layers = self.layers()
+        by = dict((i["name"], i["index"]) for i in layers)
+        out = {"model.11": self.train_activation(by["cpm.align"] - 1), "cpm.align": self.train_activation(by["cpm.align"]),
+               "cpm": self.train_activation(by["cpm.conv"])}
+        for j in range(3):
+            pw = by["cpm.trunk.%d.pw" % j]
+            dw = by.get("cpm.trunk.%d.dw" % j)
+            out["cpm.trunk.%d.dw" % j] = self.train_activation(dw) if dw is not None else self.train_activation(pw, _lib.KEPT_DEPTHWISE)
+            out["cpm.trunk.%d" % j] = self.train_activation(pw, _lib.KEPT_NO_RESIDUAL if j == 2 else _lib.KEPT_OUTPUT)
+        out["cpm.sum"] = self.train_activation(by["cpm.trunk.2.pw"])
+        return out
+
+    def train_activation(self, layer_index, which=_lib.KEPT_OUTPUT):
+        """Retained output of a layer from the last ``train_forward`` as NCHW float32 numpy (tests): a stage layer or cpm.conv,
+        in train scope "cpm" also a cpm layer or the backbone's last layer.  ``which``: ``_lib.KEPT_DEPTHWISE`` for the retained
+        depthwise copy of a fused cpm trunk block (``cin`` channels), ``_lib.KEPT_NO_RESIDUAL`` for the block's output in
+        front of its residual add."""
         info = self.layers()[layer_index]
+        channels = info["cin"] if which == _lib.KEPT_DEPTHWISE else info["cout"]
         cap = 1 << 16
         dims = (C.c_int * 4)()
         while True:
             buf = np.empty(cap, np.float32)
-            rc = lib().lwp_debug_train_activation(self.h.ptr, layer_index, buf.ctypes.data, buf.size, dims)
+            rc = lib().lwp_debug_train_copy(self.h.ptr, layer_index, which, buf.ctypes.data, buf.size, dims)
             if rc == _lib.LWP_ERR_ARG and lib().lwp_last_error(self.h.ptr) == b"dst too small" and cap < (1 << 31):
                 cap *= 8
                 continue
             check(rc, self.h.ptr)
             break
         n = dims[0] * dims[1] * dims[2] * dims[3]
-        assert dims[1] == info["cout"]
+        assert dims[1] == channels
         return buf[:n].reshape(dims[0], dims[1], dims[2], dims[3]).copy()
 
-    def backward_splits(self, layer_index):
-        """Pixel ranges the last ``stage_backward`` split this layer's weight gradient into (0: none ran)."""
-        n = lib().lwp_debug_backward_splits(self.h.ptr, layer_index)
+    def backward_splits(self, layer_index, depthwise=False):
+        """Pixel ranges the last ``stage_backward`` split this layer's weight gradient into (0: none ran); ``depthwise``: those
+        of the layer's depthwise weight gradient (a depthwise layer or a fused block of the cpm trunk, train scope "cpm")."""
+        n = (lib().lwp_debug_backward_dw_splits if depthwise else lib().lwp_debug_backward_splits)(self.h.ptr, layer_index)
         if n < 0:
             raise ValueError("bad layer index")
         return n
@@ -864,7 +918,7 @@ class Engine(object):
 
     def adam_groups(self):
         """[(state-dict key, learning-rate multiplier, weight decay on)] per gradient-spec entry (train.py:41-55)."""
-        return _lib.stage_adam_groups(self.nref, self.C, self.NH, self.NP)
+        return _lib.train_adam_groups(self.train_scope, self.nref, self.C, self.NH, self.NP)
 
     def adam_step(self, flat, base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4):
         """One step of the reference's Adam (its parameter groups included) on the stage parameters from the flat gradient array
@@ -885,6 +939,13 @@ class Engine(object):
         self._order()
         check(lib().lwp_stage_params_get(self.h.ptr, flat.data_ptr()), self.h.ptr)
         return self.grad_views(flat)
+
+    def trained_params(self):
+        """``stage_params`` plus what an earlier, wider train scope trained and the current one no longer covers (the cpm.*
+        parameters after "cpm" -> "stages"): every parameter whose value on the device may differ from what was loaded."""
+        out = dict(self._left_params)
+        out.update(self.stage_params())
+        return out
 
     def adam_state(self):
         """dict(step, exp_avg, exp_avg_sq): the step count and the two flat float32 cuda arrays (gradient-spec layout)."""

@@ -4,7 +4,11 @@
   * the backward's kernels per class (HIP events around every launch, Engine.profile_stage_backward),
   * torch-ROCm autograd over the same stages (tests/backward_cases.py's restatement in fp32 on the same GPU), as context.
 
-    python tools/backward_bench.py [--batch 80] [--size 368] [--reps 3] [--out profiles/train/backward_bench.json]
+    python tools/backward_bench.py [--batch 80] [--size 368] [--reps 3] [--scope stages|cpm] [--out profiles/train/backward_bench.json]
+
+--scope cpm times the same with the cpm trained too (Engine.set_train_scope("cpm"): retained cpm activations, ELU and depthwise
+gradient kernels, d_backbone not asked for); torch's autograd then starts at the cpm's input (tests/cpm_backward_cases.py).  Its
+default output is profiles/train/backward_bench_cpm.json.
 
 Writes one JSON file; there is no parent figure for this path, so nothing is compared."""
 import argparse
@@ -24,6 +28,7 @@ from lwpose_amd import synth  # noqa: E402
 from lwpose_amd.runtime import Engine  # noqa: E402
 
 import backward_cases as bc  # noqa: E402
+import cpm_backward_cases as cc  # noqa: E402
 
 
 def timed(fn, reps):
@@ -38,8 +43,9 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
-def one(nref, batch, size, reps):
+def one(nref, batch, size, reps, scope="stages"):
     eng = Engine(0, nref=nref)
+    eng.set_train_scope(scope)
     sd = synth.make_state_dict(nref, seed=1)
     eng.load_state_dict(sd)
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -48,23 +54,27 @@ def one(nref, batch, size, reps):
     km = torch.rand((batch, 19, hs, hs), device="cuda", generator=g)
     pm = torch.rand((batch, 38, hs, hs), device="cuda", generator=g) - 0.5
     mask = (torch.rand((batch, hs, hs), device="cuda", generator=g) > 0.1).float()
-    res = dict(nref=nref, batch=batch, size=size, reps=reps)
+    res = dict(nref=nref, batch=batch, size=size, reps=reps, scope=scope)
     res["forward_ms"] = timed(lambda: eng.forward(x), reps)
     res["train_forward_ms"] = timed(lambda: eng.train_forward(x), reps)
     res["stage_backward_ms"] = timed(lambda: eng.stage_backward(km, pm, mask), reps)
     res["backward_classes"] = eng.profile_stage_backward(km, pm, mask, reps=reps)
-    first = [i["index"] for i in eng.layers() if i["name"] == "cpm.conv"][0]
+    cpm = scope == "cpm"
+    first = [i["index"] for i in eng.layers() if i["name"] == ("cpm.align" if cpm else "cpm.conv")][0] - (1 if cpm else 0)
     feat = torch.from_numpy(eng.train_activation(first)).cuda()
     p = {k: v.cuda().requires_grad_(v.is_floating_point() and "running_" not in k) for k, v in sd.items()
-         if k.startswith("initial_stage.") or k.startswith("refinement_stages.")}
-    keys = bc.grad_keys(p)
+         if k.startswith("initial_stage.") or k.startswith("refinement_stages.") or (cpm and k.startswith("cpm."))}
+    keys = cc.grad_keys(p) if cpm else bc.grad_keys(p)
+
+    def net(q, f):
+        return bc.stages(q, cc.cpm(q, f) if cpm else f, nref)
 
     def torch_step():
         f = feat.detach().requires_grad_(True)
-        total = bc.loss(bc.stages(p, f, nref), km, pm, mask, batch)
+        total = bc.loss(net(p, f), km, pm, mask, batch)
         torch.autograd.grad(total, [p[k] for k in keys] + [f])
     res["torch_autograd_stages_fwd_bwd_ms"] = timed(torch_step, reps)
-    res["torch_stages_fwd_ms"] = timed(lambda: bc.stages({k: v.detach() for k, v in p.items()}, feat, nref), reps)
+    res["torch_stages_fwd_ms"] = timed(lambda: net({k: v.detach() for k, v in p.items()}, feat), reps)
     return res
 
 
@@ -73,9 +83,12 @@ def main():
     ap.add_argument("--batch", type=int, default=80)
     ap.add_argument("--size", type=int, default=368)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train", "backward_bench.json"))
+    ap.add_argument("--scope", choices=("stages", "cpm"), default="stages")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    out = dict(device=torch.cuda.get_device_properties(0).gcnArchName, runs=[one(n, a.batch, a.size, a.reps) for n in (1, 3)])
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "train", "backward_bench_cpm.json" if a.scope == "cpm" else "backward_bench.json")
+    out = dict(device=torch.cuda.get_device_properties(0).gcnArchName, runs=[one(n, a.batch, a.size, a.reps, a.scope) for n in (1, 3)])
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)

@@ -7,7 +7,10 @@
   * the loss over 50 steps on one batch of labelled synthetic frames (synthetic weights: the curve shows the loop closing, not a
     trained model).
 
-    python tools/finetune_bench.py [--batch 80] [--size 368] [--iters 50] [--steps 50] [--out profiles/train/finetune_bench.json]
+    python tools/finetune_bench.py [--batch 80] [--size 368] [--iters 50] [--steps 50] [--scope stages|cpm] [--out profiles/train/finetune_bench.json]
+
+--scope cpm runs every leg with the cpm trained too (optim.StageAdam(net, scope="cpm")) into profiles/train/finetune_bench_cpm.json;
+the repack's byte count then leaves the cpm layers out, so no share of the HBM figure is given for it.
 
 Writes one JSON file; the feature has no earlier form, so nothing is compared against a parent."""
 import argparse
@@ -29,7 +32,7 @@ from lwpose_amd.models.with_mobilenet import PoseEstimationWithMobileNet  # noqa
 from lwpose_amd.modules.load_state import load_state  # noqa: E402
 from lwpose_amd.runtime import Engine  # noqa: E402
 
-import optim_cases as oc  # noqa: E402
+import cpm_backward_cases as cc  # noqa: E402
 import train_cases as tc  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
@@ -52,8 +55,9 @@ def check_blob_rule():
     return dict(blob_growth_bytes=grown, rule_bytes=rule)
 
 
-def kernels(nref, iters):
+def kernels(nref, iters, scope):
     eng = Engine(0, nref=nref)
+    eng.set_train_scope(scope)
     eng.load_state_dict(synth.make_state_dict(nref, seed=1))
     spec, total = eng.grad_spec()
     g = torch.randn(total, device="cuda") * 1e-3
@@ -65,9 +69,11 @@ def kernels(nref, iters):
     adam_bytes = 7 * 4 * total
     blob_stage = stage_blob_bytes(eng)
     repack_bytes = 4 * total + blob_stage
-    return dict(nref=nref, num_channels=128, parameters=total, iters=iters,
-                adam_us=adam_us, adam_bytes=adam_bytes, adam_share_of_8TBs=adam_bytes / (adam_us * 1e-6) / HBM_BYTES_PER_S,
-                repack_us=repack_us, repack_bytes=repack_bytes, repack_share_of_8TBs=repack_bytes / (repack_us * 1e-6) / HBM_BYTES_PER_S)
+    res = dict(nref=nref, num_channels=128, scope=scope, parameters=total, iters=iters,
+               adam_us=adam_us, adam_bytes=adam_bytes, adam_share_of_8TBs=adam_bytes / (adam_us * 1e-6) / HBM_BYTES_PER_S, repack_us=repack_us)
+    if scope == "stages":
+        res.update(repack_bytes=repack_bytes, repack_share_of_8TBs=repack_bytes / (repack_us * 1e-6) / HBM_BYTES_PER_S)
+    return res
 
 
 def labelled(N, S, seed):
@@ -87,11 +93,11 @@ def make_net(nref=1):
     return net, sd
 
 
-def full_step(batch, size, reps):
+def full_step(batch, size, reps, scope):
     net, sd = make_net(1)
     x, labels = labelled(batch, size, 7)
     xc = torch.from_numpy(x).cuda()
-    opt = optim.StageAdam(net)
+    opt = optim.StageAdam(net, scope=scope)
     val.train_step(net, opt, xc, labels)                        # warm-up: buffers, tables, state
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -113,7 +119,7 @@ def full_step(batch, size, reps):
     params = {k: torch.nn.Parameter(sd[k].clone()) for k, _, _ in spec}
     groups = []
     for k, _, _ in spec:
-        mult, wd = oc.group_of(k)
+        mult, wd = cc.group_of(k)
         groups.append({"params": [params[k]], "lr": opt.lr * mult, "weight_decay": opt.weight_decay if wd else 0})
     topt = torch.optim.Adam(groups, lr=opt.lr)
     host = dict(sd)
@@ -135,13 +141,13 @@ def full_step(batch, size, reps):
                 host_route_step_ms=host_step * 1e3)
 
 
-def loss_curve(steps):
+def loss_curve(steps, scope):
     net, _ = make_net(1)
     x, labels = labelled(4, 128, 11)
-    opt = optim.StageAdam(net, base_lr=1e-3)
+    opt = optim.StageAdam(net, base_lr=1e-3, scope=scope)
     curve = [sum(val.train_step(net, opt, x, labels)) for _ in range(steps)]
     curve.append(sum(val.stage_losses(net, x, labels)))
-    return dict(frames=4, size=128, base_lr=1e-3, steps=steps, summed_stage_loss=curve)
+    return dict(frames=4, size=128, base_lr=1e-3, steps=steps, scope=scope, summed_stage_loss=curve)
 
 
 def main():
@@ -151,13 +157,16 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train", "finetune_bench.json"))
+    ap.add_argument("--scope", choices=("stages", "cpm"), default="stages")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "train", "finetune_bench_cpm.json" if a.scope == "cpm" else "finetune_bench.json")
     out = dict(device=torch.cuda.get_device_properties(0).gcnArchName,
-               kernels=[kernels(n, a.iters) for n in (1, 3)],
-               full_step=full_step(a.batch, a.size, a.reps),
+               kernels=[kernels(n, a.iters, a.scope) for n in (1, 3)],
+               full_step=full_step(a.batch, a.size, a.reps, a.scope),
                blob_rule=check_blob_rule(),
-               loss=loss_curve(a.steps))
+               loss=loss_curve(a.steps, a.scope))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
