@@ -396,7 +396,7 @@ int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, co
  *        L = loss_scale * sum_i l2_loss(stages_output[i], target_i, mask, batch_size)      (modules/loss.py: sum(((out - target) * mask)^2) / 2 / batch_size)
  *      with respect to every parameter of initial_stage.* and refinement_stages.* (with_mobilenet.py:25-86) and to
  *      backbone_features, the output of cpm.conv (with_mobilenet.py:117).  fp32 handles only; the backbone is frozen, the cpm
- *      too unless the train scope is LWP_TRAIN_CPM (lwp_set_train_scope below),
+ *      too unless the train scope is LWP_TRAIN_CPM; LWP_TRAIN_ALL trains both (lwp_set_train_scope below),
  *      and the refinement trunks' BatchNorms (modules/conv.py:8) stay at their running statistics: the result is what
  *      loss.backward() gives on the reference network in eval() mode, NOT in train() mode (no batch statistics, running_mean /
  *      running_var / num_batches_tracked get no gradient and are not updated).  The optimiser step is lwp_stage_adam_step below.
@@ -470,11 +470,38 @@ int lwp_debug_backward_splits(lwp_handle h, int layer_index);
  *        returns), LWP_KEPT_DEPTHWISE the retained depthwise copy of a fused trunk block (cin channels), LWP_KEPT_NO_RESIDUAL
  *        the retained output of a block in front of its residual add; LWP_ERR_ARG where the layer has no such copy.
  *        lwp_debug_backward_dw_splits is the number of pixel ranges of the layer's depthwise weight gradient (a depthwise
- *        layer or a fused block), lwp_debug_backward_splits that of its dense / pointwise one. */
-enum { LWP_TRAIN_STAGES = 0, LWP_TRAIN_CPM = 1 };
+ *        layer or a fused block), lwp_debug_backward_splits that of its dense / pointwise one.
+ *      LWP_TRAIN_ALL: the backbone model.* (with_mobilenet.py:92-105) as well, so every parameter train.py:41-55 hands to its
+ *      optimiser.  The rules are LWP_TRAIN_CPM's; what differs:
+ *      - layout: the 69 model.* parameters first, in lwp_param_spec order (model.0.0.weight, model.0.1.weight / .bias; for
+ *        i = 1..11 model.i.0.weight of shape (cin, 1, 3, 3), model.i.1.weight / .bias, model.i.3.weight, model.i.4.weight / .bias),
+ *        then the LWP_TRAIN_CPM layout as the unchanged tail, shifted by the backbone total.  Running mean, variance and
+ *        num_batches_tracked are not parameters and never move.  Groups (train.py:42-45): conv weights with groups == 1 (stem
+ *        and pointwise) x1 with weight decay, depthwise weights x1 without, BatchNorm weights x1 without, BatchNorm biases x2
+ *        without.
+ *      - lwp_train_forward keeps every backbone layer's output in a buffer of its own (and a copy of the image, which the stem's
+ *        weight gradient reads); a fused depthwise + pointwise backbone block gets its depthwise activation (after BatchNorm and
+ *        ReLU) from one more stand-alone depthwise launch, with the same last-bit caveat.  The stage outputs stay bit-identical
+ *        to lwp_forward's.  lwp_debug_train_activation answers from model.0 on, lwp_debug_train_copy(.., LWP_KEPT_DEPTHWISE, ..)
+ *        names a fused backbone block's copy.  None of this is allocated in the other scopes.
+ *      - lwp_train_backward covers the backbone: BatchNorm at its running statistics (eval mode), ReLU masks from the retained
+ *        outputs, depthwise gradients at stride 1 | 2 and dilation 1 | 2, the stem's weight gradient.  d_backbone_device keeps
+ *        its meaning (the gradient at the cpm's input, which this scope always computes).  No gradient at the image.
+ *      - lwp_stage_adam_step also updates model.* and refolds BatchNorm into the stem, depthwise, fused and pointwise forms of
+ *        the blob bit for bit as lwp_load_weights does. */
+enum { LWP_TRAIN_STAGES = 0, LWP_TRAIN_CPM = 1, LWP_TRAIN_ALL = 2 };
 enum { LWP_KEPT_OUTPUT = 0, LWP_KEPT_DEPTHWISE = 1, LWP_KEPT_NO_RESIDUAL = 2 };
 int lwp_debug_train_copy(lwp_handle h, int layer_index, int which, float* dst, size_t dst_floats, int out_dims[4]);
 int lwp_debug_backward_dw_splits(lwp_handle h, int layer_index);
+/* tests: the backbone's gradient kernels alone, on the handle's stream, synchronous.  All arrays DEVICE float32.
+ * lwp_debug_dw_grad_sd: depthwise 3x3, stride 1 | 2, dilation 1 | 2, padding = dilation.  dz N x Ho x Wo x C (NHWC, Ho = (H - 1) /
+ * stride + 1), x N x H x W x C, w [9][C]; out: dx N x H x W x C, G (C, 1, 3, 3), g (C) the per-channel sum of dz; C a multiple of 4.
+ * max_chunk > 0 caps the pixels of a range (a multiple of 16), so that small maps take several ranges; *splits: ranges taken.
+ * lwp_debug_stem_wgrad: the stem's weight gradient.  dz N x Ho x Wo x 32 (NHWC), x N x 3 x H x W (NCHW); out: G (32, 3, 3, 3),
+ * g (32) the column sums of dz. */
+int lwp_debug_dw_grad_sd(lwp_handle h, const float* dz, const float* x, const float* w, int N, int H, int W, int C, int stride, int dil,
+                         int max_chunk, float* dx, float* G, float* g, int* splits);
+int lwp_debug_stem_wgrad(lwp_handle h, const float* dz, const float* x, int N, int H, int W, int max_chunk, float* G, float* g, int* splits);
 int lwp_set_train_scope(lwp_handle h, int scope);
 int lwp_train_grad_count(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int64_t* total_floats);
 int lwp_train_grad_spec(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int index, char* name,
@@ -489,7 +516,7 @@ int lwp_train_backward(lwp_handle h, const float* keypoint_maps, const float* pa
  *      for the parameters lwp_stage_backward differentiates, and the refold / repack of the changed layers into the forward's
  *      weight blob, all on the handle's stream: train_forward -> stage_backward -> step lowers the loss with no host round
  *      trip and no second copy of the weights.  fp32 handles whose weights came through lwp_load_weights only.
- *      Out of scope: backward or updates for the backbone (and for the cpm in scope LWP_TRAIN_STAGES), BatchNorm train mode (the running statistics never move), a
+ *      Out of scope: BatchNorm train mode (the running statistics never move), a
  *      16-bit optimiser, multi-GPU gradient reduction, amsgrad, loading torch's optimiser checkpoints.
  *      lwp_stage_adam_group: the parameter group of gradient-spec entry `index` (no handle, no GPU): learning-rate multiplier
  *      and weight-decay flag: initial_stage conv weight x1 / on, conv bias x2 / off; refinement_stages conv weight x4 / on,

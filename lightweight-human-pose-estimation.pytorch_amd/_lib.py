@@ -9,8 +9,8 @@ LIB_PATH = os.path.join(PKG, "liblwpose_hip.so")
 LWP_OK, LWP_ERR_ARG, LWP_ERR_HIP, LWP_ERR_STATE, LWP_ERR_CAPACITY, LWP_ERR_NOGPU, LWP_ERR_UNBOUND = 0, -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
 F32, BF16, F16 = 0, 1, 2
-TRAIN_STAGES, TRAIN_CPM = 0, 1
-TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM}
+TRAIN_STAGES, TRAIN_CPM, TRAIN_ALL = 0, 1, 2
+TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM, "all": TRAIN_ALL}
 KEPT_OUTPUT, KEPT_DEPTHWISE, KEPT_NO_RESIDUAL = 0, 1, 2
 
 EXPORTS = [
@@ -32,7 +32,7 @@ EXPORTS = [
     "lwp_stage_adam_group", "lwp_stage_adam_step", "lwp_stage_params_get", "lwp_stage_adam_state_get", "lwp_stage_adam_state_set",
     "lwp_stage_adam_reset", "lwp_time_stage_adam_step",
     "lwp_set_train_scope", "lwp_train_grad_count", "lwp_train_grad_spec", "lwp_train_adam_group", "lwp_train_backward",
-    "lwp_debug_train_copy", "lwp_debug_backward_dw_splits",
+    "lwp_debug_train_copy", "lwp_debug_backward_dw_splits", "lwp_debug_dw_grad_sd", "lwp_debug_stem_wgrad",
 ]
 
 
@@ -138,6 +138,8 @@ def lib():
     L.lwp_train_backward.argtypes = L.lwp_stage_backward.argtypes + [vp]
     L.lwp_debug_train_copy.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, ip]
     L.lwp_debug_backward_dw_splits.argtypes = [vp, C.c_int]
+    L.lwp_debug_dw_grad_sd.argtypes = [vp, vp, vp, vp] + [C.c_int] * 7 + [vp, vp, vp, ip]
+    L.lwp_debug_stem_wgrad.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, vp, ip]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int
@@ -205,24 +207,24 @@ def stage_adam_groups(nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
 
 
 def train_scope_name(scope):
-    """"stages" / "cpm" of a scope given by name or by its LWP_TRAIN_* number."""
+    """"stages" / "cpm" / "all" of a scope given as ``train_scope`` takes it."""
     sc = train_scope(scope)
     return [k for k, v in TRAIN_SCOPES.items() if v == sc][0]
 
 
 def train_scope(scope):
-    """LWP_TRAIN_* of "stages" / "cpm" (or of the number itself)."""
+    """LWP_TRAIN_* of a scope.  A scope is given by name ("stages" | "cpm" | "all").  The first two may still be given by their
+    numbers (TRAIN_STAGES, TRAIN_CPM), as callers written before the scopes had names do; a scope added since has a name only:
+    a bare integer that was an error stays one (ValueError), whatever the C enumeration grows to."""
     if scope in TRAIN_SCOPES:
         return TRAIN_SCOPES[scope]
-    if scope in TRAIN_SCOPES.values():
+    if scope in (TRAIN_STAGES, TRAIN_CPM):
         return int(scope)
-    raise ValueError("train scope must be 'stages' or 'cpm', got %r" % (scope,))
+    raise ValueError("train scope must be 'stages', 'cpm' or 'all', got %r" % (scope,))
 
 
-def train_grad_spec(scope, nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
-    """``stage_grad_spec`` for a train scope ("stages" | "cpm"): in scope "cpm" the ten cpm.* parameters come first."""
+def _grad_spec_of(sc, nref, num_channels, num_heatmaps, num_pafs):
     L = lib()
-    sc = train_scope(scope)
     total = C.c_int64()
     n = L.lwp_train_grad_count(sc, nref, num_channels, num_heatmaps, num_pafs, C.byref(total))
     if n < 0:
@@ -237,11 +239,18 @@ def train_grad_spec(scope, nref=1, num_channels=128, num_heatmaps=19, num_pafs=3
     return out, total.value
 
 
+def train_grad_spec(scope, nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
+    """``stage_grad_spec`` for a train scope (``train_scope``): in scope "cpm" the ten cpm.* parameters come first, in scope
+    "all" the 69 model.* parameters in front of those."""
+    return _grad_spec_of(train_scope(scope), nref, num_channels, num_heatmaps, num_pafs)
+
+
 def train_adam_groups(scope, nref=1, num_channels=128, num_heatmaps=19, num_pafs=38):
-    """``stage_adam_groups`` for a train scope: the cpm's conv weights x1 with decay, biases x2 and depthwise weights x1 without."""
+    """``stage_adam_groups`` for a train scope: the cpm's conv weights x1 with decay, biases x2 and depthwise weights x1 without;
+    the backbone's stem and pointwise weights x1 with decay, depthwise and BatchNorm weights x1 and BatchNorm biases x2 without."""
     L = lib()
     sc = train_scope(scope)
-    spec, _ = train_grad_spec(sc, nref, num_channels, num_heatmaps, num_pafs)
+    spec, _ = _grad_spec_of(sc, nref, num_channels, num_heatmaps, num_pafs)
     mult, wd = C.c_int(), C.c_int()
     out = []
     for i, (key, _, _) in enumerate(spec):

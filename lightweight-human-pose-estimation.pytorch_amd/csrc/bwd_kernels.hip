@@ -431,9 +431,236 @@ hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, int accumula
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------- backbone: depthwise 3x3, stride 1 | 2, dilation 1 | 2
+// (with_mobilenet.py:94-104: conv_dw, padding = dilation, BatchNorm + ReLU behind it.)  The forward is
+// Z[n, oy, ox, c] = sum_k X[n, s oy + d (ky - 1), s ox + d (kx - 1), c] w[k][c] on an Ho x Wo map, Ho = (H - 1) / s + 1.  Same shapes
+// as the cpm's kernels above (a lane owns four channels of a pixel, 16 bytes per access); the cpm keeps its own statements.
+//
+// dX[n, y, x, c] = sum over taps of dZ[n, (y + d - d ky) / s, (x + d - d kx) / s, c] * w[tap][c], over the taps whose source
+// index is divisible by s and inside the Ho x Wo map: one fmaf chain per output in tap order 0..8
+__global__ void __launch_bounds__(256) dw_dgrad_sd_kernel(DwGradSdParams p) {
+    const int C4 = p.C / 4;
+    const int HW = p.H * p.W, HWo = p.Ho * p.Wo;
+    const int64_t total = (int64_t)p.N * HW * C4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t px = i / C4;
+        const int c = (int)(i % C4) * 4;
+        const int64_t n = px / HW;
+        const int r = (int)(px % HW);
+        const int y = r / p.W, x = r % p.W;
+        f32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ny = y + p.dil - p.dil * (tap / 3), nx = x + p.dil - p.dil * (tap % 3);
+            f32x4 z = {0, 0, 0, 0};
+            if (ny >= 0 && nx >= 0 && ny % p.stride == 0 && nx % p.stride == 0) {
+                const int sy = ny / p.stride, sx = nx / p.stride;
+                if (sy < p.Ho && sx < p.Wo) z = *(const f32x4*)(p.dz + (n * HWo + (int64_t)sy * p.Wo + sx) * p.dz_ld + c);
+            }
+            const f32x4 wv = *(const f32x4*)(p.w + tap * p.C + c);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = fmaf(z[k], wv[k], acc[k]);
+        }
+        f32x4* d = (f32x4*)(p.dx + px * p.dx_ld + c);
+        if (p.beta) {
+            const f32x4 old = *d;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = old[k] + acc[k];
+        }
+        *d = acc;
+    }
+}
+static bool dw_sd_shape_ok(const DwGradSdParams& p) {
+    const int64_t M = (int64_t)p.N * p.H * p.W;
+    return p.N >= 1 && p.H >= 1 && p.W >= 1 && M < (1ll << 31) - BW_T && (p.stride == 1 || p.stride == 2) && (p.dil == 1 || p.dil == 2) &&
+           p.Ho == (p.H - 1) / p.stride + 1 && p.Wo == (p.W - 1) / p.stride + 1 && p.C >= 4 && (p.C & 3) == 0 && p.C <= p.dz_ld &&
+           quad_ok(p.dz, p.dz_ld);
+}
+hipError_t launch_dw_dgrad_sd(const DwGradSdParams& p, hipStream_t s) {
+    if (!dw_sd_shape_ok(p) || !quad_ok(p.w, 4) || !quad_ok(p.dx, p.dx_ld) || p.C > p.dx_ld) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)p.N * p.H * p.W * (p.C / 4);
+    hipLaunchKernelGGL(dw_dgrad_sd_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// G[c][tap] = sum over output pixels q of dZ[q][c] * X[s q + d (k - 1)][c] and, as a tenth accumulator, g[c] = sum_q dZ[q][c] (the
+// gradient of the folded bias, which the BatchNorm chain rule needs).  The structure is dw_wgrad_kernel's: 64 channels of one
+// range of output pixels (dw_wgrad_plan over N Ho Wo) per workgroup, thread t on the pixels begin + (t >> 4) + 16 k, the 16 pixel
+// lanes added through LDS in the same fixed tree, [10][C] partials per range.
+__global__ void __launch_bounds__(256) dw_wgrad_sd_kernel(DwGradSdParams p) {
+    __shared__ float red[DW_PL * 10 * DW_CG];         // [pixel lane][tap, then the bias sum][channel]: 40 KB
+    const int t = threadIdx.x, cq = (t & 15) * 4, pl = t >> 4;
+    const int c = blockIdx.x * DW_CG + cq;
+    const bool c_in = c < p.C;
+    const int HW = p.H * p.W, HWo = p.Ho * p.Wo;
+    const int64_t M = (int64_t)p.N * HWo;
+    const int64_t p_begin = (int64_t)blockIdx.y * p.chunk;
+    const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
+    f32x4 acc[10];
+#pragma unroll
+    for (int tap = 0; tap < 10; ++tap) acc[tap] = f32x4{0, 0, 0, 0};
+    if (c_in)
+        for (int64_t px = p_begin + pl; px < p_end; px += DW_PL) {
+            const f32x4 z = *(const f32x4*)(p.dz + px * p.dz_ld + c);
+            const int64_t n = px / HWo;
+            const int r = (int)(px % HWo);
+            const int y = r / p.Wo, x = r % p.Wo;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const int sy = p.stride * y + p.dil * (tap / 3 - 1), sx = p.stride * x + p.dil * (tap % 3 - 1);
+                if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) continue;
+                const f32x4 xv = *(const f32x4*)(p.x + (n * HW + (int64_t)sy * p.W + sx) * p.x_ld + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[tap][k] = fmaf(z[k], xv[k], acc[tap][k]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[9][k] = acc[9][k] + z[k];
+        }
+#pragma unroll
+    for (int tap = 0; tap < 10; ++tap) *(f32x4*)(red + (pl * 10 + tap) * DW_CG + cq) = acc[tap];
+    __syncthreads();
+    for (int st = DW_PL / 2; st > 0; st >>= 1) {
+        if (pl < st) {
+#pragma unroll
+            for (int tap = 0; tap < 10; ++tap) {
+                f32x4* a = (f32x4*)(red + (pl * 10 + tap) * DW_CG + cq);
+                const f32x4 b = *(const f32x4*)(red + ((pl + st) * 10 + tap) * DW_CG + cq);
+                f32x4 v = *a;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = v[k] + b[k];
+                *a = v;
+            }
+        }
+        __syncthreads();
+    }
+    if (pl == 0 && c_in) {
+        float* part = p.partial + (size_t)blockIdx.y * 10 * p.C;
+#pragma unroll
+        for (int tap = 0; tap < 10; ++tap) *(f32x4*)(part + tap * p.C + c) = *(const f32x4*)(red + tap * DW_CG + cq);
+    }
+}
+hipError_t launch_dw_wgrad_sd(const DwGradSdParams& p, hipStream_t s) {
+    const int64_t M = (int64_t)p.N * p.Ho * p.Wo;
+    if (!dw_sd_shape_ok(p) || !quad_ok(p.x, p.x_ld) || p.C > p.x_ld || !quad_ok(p.partial, 4) || p.splits < 1 || p.splits > 65535 ||
+        p.chunk < DW_PL || (p.chunk % DW_PL) || (int64_t)p.splits * p.chunk < M)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dw_wgrad_sd_kernel, dim3((unsigned)((p.C + DW_CG - 1) / DW_CG), (unsigned)p.splits), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+// partials in range order -> G as OIHW (C, 1, 3, 3) and g (C); thread i = row * C + c, row 9 the bias sum
+__global__ void __launch_bounds__(256) dw_wgrad_sd_reduce_kernel(DwGradSdParams p, float* G, float* g) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 10 * p.C) return;
+    const int tap = i / p.C, c = i % p.C;
+    float sum = 0.0f;
+    for (int z = 0; z < p.splits; ++z) sum += p.partial[(size_t)z * 10 * p.C + i];
+    if (tap < 9) G[c * 9 + tap] = sum;
+    else g[c] = sum;
+}
+hipError_t launch_dw_wgrad_sd_reduce(const DwGradSdParams& p, float* G, float* g, hipStream_t s) {
+    if (p.C < 1 || p.splits < 1 || !p.partial || !G || !g) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dw_wgrad_sd_reduce_kernel, dim3((unsigned)((10 * p.C + 255) / 256)), dim3(256), 0, s, p, G, g);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- backbone: the stem's weight gradient
+// (with_mobilenet.py:93: conv 3 -> 32, 3x3, stride 2, pad 1, on the N x 3 x H x W input the stem kernel reads.)
+// G[o][k] = sum over output pixels q = (n, y, x) of dZ[q][o] * X[n, ci, 2 y + ky - 1, 2 x + kx - 1], k = ci * 9 + ky * 3 + kx (OIHW), and
+// g[o] = sum_q dZ[q][o].  A workgroup owns one range of output pixels; thread t owns output channel t & 31 and the rows
+// k = (t >> 5) + 8 j, j = 0..3, of the 28-row table (row 27 is the bias sum: its X is 1), one chain per row in pixel order.  The
+// 32 lanes of a k group read one X value (a broadcast) and 32 consecutive floats of dZ.  [28][32] partials per range, added in
+// range order by the reduce kernel.  No dgrad: there is no gradient at the image.
+constexpr int ST_ROWS = 28;
+__global__ void __launch_bounds__(256) stem_wgrad_kernel(StemWgradParams p) {
+    const int t = threadIdx.x, o = t & 31, kg = t >> 5;
+    const int HWo = p.Ho * p.Wo;
+    const int64_t plane = (int64_t)p.H * p.W;
+    const int64_t M = (int64_t)p.N * HWo;
+    const int64_t p_begin = (int64_t)blockIdx.x * p.chunk;
+    const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
+    int ci[4], dy[4], dx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = kg + 8 * j;
+        ci[j] = k / 9; dy[j] = (k % 9) / 3 - 1; dx[j] = k % 3 - 1;
+    }
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t px = p_begin; px < p_end; ++px) {
+        const float z = p.dz[px * p.dz_ld + o];
+        const int64_t n = px / HWo;
+        const int r = (int)(px % HWo);
+        const int y = r / p.Wo, x = r % p.Wo;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = kg + 8 * j;
+            if (k > 27) continue;
+            float xv = 1.0f;
+            if (k < 27) {
+                const int sy = 2 * y + dy[j], sx = 2 * x + dx[j];
+                xv = (sy >= 0 && sy < p.H && sx >= 0 && sx < p.W) ? p.x[(n * 3 + ci[j]) * plane + (int64_t)sy * p.W + sx] : 0.0f;
+            }
+            acc[j] = fmaf(z, xv, acc[j]);
+        }
+    }
+    float* part = p.partial + (size_t)blockIdx.x * ST_ROWS * 32;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = kg + 8 * j;
+        if (k < ST_ROWS) part[k * 32 + o] = acc[j];
+    }
+}
+// pixel ranges of at least 64 pixels, at most 1024 of them
+void stem_wgrad_plan(int64_t M, int* splits, int* chunk) {
+    int64_t sp = std::min<int64_t>(1024, (M + 63) / 64);
+    if (sp < 1) sp = 1;
+    const int64_t ch = (M + sp - 1) / sp;
+    *chunk = (int)ch;
+    *splits = (int)((M + ch - 1) / ch);
+}
+hipError_t launch_stem_wgrad(const StemWgradParams& p, hipStream_t s) {
+    const int64_t M = (int64_t)p.N * p.Ho * p.Wo;
+    if (p.N < 1 || p.H < 1 || p.W < 1 || p.Ho != (p.H - 1) / 2 + 1 || p.Wo != (p.W - 1) / 2 + 1 || (int64_t)p.N * 3 * p.H * p.W >= (1ll << 31) ||
+        !p.dz || !p.x || !p.partial || p.dz_ld < 32 || p.splits < 1 || p.splits > 65535 || p.chunk < 1 || (int64_t)p.splits * p.chunk < M)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)p.splits), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+__global__ void __launch_bounds__(256) stem_wgrad_reduce_kernel(StemWgradParams p, float* G, float* g) {
+    const int i = blockIdx.x * 256 + threadIdx.x;      // i = k * 32 + o
+    if (i >= ST_ROWS * 32) return;
+    const int k = i / 32, o = i % 32;
+    float sum = 0.0f;
+    for (int z = 0; z < p.splits; ++z) sum += p.partial[(size_t)z * ST_ROWS * 32 + i];
+    if (k < 27) G[o * 27 + k] = sum;
+    else g[o] = sum;
+}
+hipError_t launch_stem_wgrad_reduce(const StemWgradParams& p, float* G, float* g, hipStream_t s) {
+    if (p.splits < 1 || !p.partial || !G || !g) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((ST_ROWS * 32 + 255) / 256), dim3(256), 0, s, p, G, g);
+    return hipGetLastError();
+}
+
+// the folded pointwise weights of a fused backbone block as a plain [cout][cin] matrix, the B operand of its 1x1 dgrad (the blob
+// holds them in fragment order only): float(double(w) * gamma / sqrt(double(var) + 1e-5)), the very value pack_weights stores
+__global__ void __launch_bounds__(256) pw_fold_kernel(const float* w, const float* gamma, const float* var, float* out, int cout, int cin) {
+    const int64_t total = (int64_t)cout * cin;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int o = (int)(i / cin);
+        const double scale = (double)gamma[o] / sqrt((double)var[o] + 1e-5);
+        out[i] = (float)((double)w[i] * scale);
+    }
+}
+hipError_t launch_pw_fold(const float* w, const float* gamma, const float* var, float* out, int cout, int cin, hipStream_t s) {
+    if (!w || !gamma || !var || !out || cout < 1 || cin < 1) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)cout * cin;
+    hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, w, gamma, var, out, cout, cin);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------- BatchNorm at running statistics
 // z = s (W * x + b - mu) + beta, s = gamma / sqrt(var + 1e-5) (modules/conv.py:8 in eval()).  From G = dL/d(sW), g = dL/d(folded bias):
 //   dW = s G, db = s g, dbeta = g, dgamma = (<W, G> + g (b - mu)) / sqrt(var + 1e-5).  One workgroup per output channel, float64.
+// A conv without bias (the backbone's) passes a row of zeros as b and no db.
 __global__ void __launch_bounds__(256) bn_chain_kernel(BnChainParams p) {
     __shared__ double red[256];
     const int o = blockIdx.x, t = threadIdx.x;
@@ -458,7 +685,7 @@ __global__ void __launch_bounds__(256) bn_chain_kernel(BnChainParams p) {
         const double g = (double)p.g[o];
         const float vb = (float)(sc * g), vbeta = (float)g;
         const float vg = (float)((red[0] + g * ((double)p.b[o] - (double)p.mean[o])) * inv);
-        p.db[o] = p.accumulate ? p.db[o] + vb : vb;
+        if (p.db) p.db[o] = p.accumulate ? p.db[o] + vb : vb;     // (a conv without bias has no db)
         p.dbeta[o] = p.accumulate ? p.dbeta[o] + vbeta : vbeta;
         p.dgamma[o] = p.accumulate ? p.dgamma[o] + vg : vg;
     }

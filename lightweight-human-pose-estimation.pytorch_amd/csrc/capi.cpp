@@ -103,6 +103,7 @@ struct lwp_context {
     TrainPlan tp;
     int scope = LWP_TRAIN_STAGES;                    // lwp_set_train_scope: which parameters the plan, the gradient array and the optimiser cover
     std::vector<DevBuf> tbufs, gbufs;                // (a gradient buffer has the size of its activation buffer)
+    DevBuf d_train_in;                               // LWP_TRAIN_ALL: the image of the last retaining forward (the stem's weight gradient reads it)
     int train_N = 0, train_H = 0, train_W = 0;      // frames of the last retaining forward (0: none)
     struct GradSpec { std::string key; int64_t shape[4]; int ndim; size_t off; };
     std::vector<GradSpec> gspec;
@@ -111,10 +112,12 @@ struct lwp_context {
     size_t grad_floats = 0, raw_floats = 0;
     DevBuf d_raw;
     bool raw_loaded = false;                         // false after lwp_weights_blob_import: a blob holds folded weights only
-    DevBuf d_bwd; size_t bwd_fold_off = 0;           // wgrad partials, then the folded gradients of one BatchNorm layer
+    DevBuf d_bwd; size_t bwd_fold_off = 0;           // wgrad partials, then the folded gradients of one BatchNorm layer,
+    size_t bwd_pw_off = 0;                           // then (LWP_TRAIN_ALL) the folded pointwise matrix of one fused backbone block
     std::vector<int> bwd_splits;                     // per layer: pixel splits its last wgrad ran with
     std::vector<int> bwd_dw_splits;                  // per layer: pixel splits of its last depthwise wgrad (L_DW, L_DWPW)
-    std::vector<DwRepack> dw_repack;                 // the cpm trunk's depthwise / fused layers of the repack (LWP_TRAIN_CPM)
+    std::vector<DwRepack> dw_repack;                 // the depthwise / fused layers of the repack: the cpm trunk's, the backbone's (LWP_TRAIN_ALL)
+    StemRepack stem_repack{}; bool has_stem_repack = false;      // model.0 (LWP_TRAIN_ALL)
     // stage fine-tuning step (lwp_stage_adam_step): exp_avg then exp_avg_sq in one allocation, the step count, and the two
     // device tables the host builds once per handle (parameter chunks of the Adam kernel, layer descriptors of the repack)
     DevBuf d_adam; size_t adam_sq_off = 0;
@@ -163,14 +166,19 @@ Skeleton default_skeleton() {              // modules/keypoints.py:5-8
 // the stage parameters that receive a gradient, in lwp_param_spec order (running statistics and counters excluded)
 static bool is_stage_key(const std::string& k) { return k.rfind("initial_stage.", 0) == 0 || k.rfind("refinement_stages.", 0) == 0; }
 static bool is_cpm_key(const std::string& k) { return k.rfind("cpm.", 0) == 0; }
-// LWP_TRAIN_CPM: the ten cpm.* parameters first, then the stage parameters (the unchanged tail, shifted by the cpm total)
+static bool is_backbone_key(const std::string& k) { return k.rfind("model.", 0) == 0; }
+// parts of the layout: 0 backbone, 1 cpm, 2 stages; a scope's layout is its first part and everything behind it
+static int first_part(int scope) { return scope == LWP_TRAIN_ALL ? 0 : scope == LWP_TRAIN_CPM ? 1 : 2; }
+static bool in_part(int part, const std::string& k) { return part == 0 ? is_backbone_key(k) : part == 1 ? is_cpm_key(k) : is_stage_key(k); }
+// LWP_TRAIN_CPM: the ten cpm.* parameters first, then the stage parameters (the unchanged tail, shifted by the cpm total);
+// LWP_TRAIN_ALL: the 69 model.* parameters in front of that
 static std::vector<lwp_context::GradSpec> train_grad_spec(int scope, int nref, int C, int NH, int NP, size_t* total) {
     std::vector<lwp_context::GradSpec> v;
     size_t off = 0;
     const std::vector<ParamSpec> table = param_table(nref, C, NH, NP);
-    for (int part = scope == LWP_TRAIN_CPM ? 0 : 1; part < 2; ++part)
+    for (int part = first_part(scope); part < 3; ++part)
         for (const ParamSpec& p : table) {
-            if (!(part == 0 ? is_cpm_key(p.key) : is_stage_key(p.key)) || p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR || p.role == LWP_ROLE_BN_NBT) continue;
+            if (!in_part(part, p.key) || p.role == LWP_ROLE_BN_MEAN || p.role == LWP_ROLE_BN_VAR || p.role == LWP_ROLE_BN_NBT) continue;
             lwp_context::GradSpec s;
             s.key = p.key; s.ndim = p.ndim; s.off = off;
             size_t n = 1;
@@ -288,6 +296,7 @@ static void apply_train_scope(lwp_context* h, int scope) {
     h->tp = build_train_plan(g, scope);
     h->tbufs = std::vector<DevBuf>(h->tp.bufs.size());
     h->gbufs = std::vector<DevBuf>(h->tp.bufs.size());
+    h->d_train_in = DevBuf();
     h->gspec = train_grad_spec(scope, g.nref, g.C, g.NH, g.NP, &h->grad_floats);
     h->grad_off.clear();
     for (const auto& s : h->gspec) h->grad_off[s.key] = s.off;
@@ -298,6 +307,7 @@ static void apply_train_scope(lwp_context* h, int scope) {
     h->d_adam_chunks = DevBuf(); h->adam_chunks = 0;
     h->d_repack = DevBuf(); h->repack_layers = h->repack_blocks = 0;
     h->dw_repack.clear();
+    h->has_stem_repack = false;
 }
 
 extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dtype, lwp_handle* out) {
@@ -357,6 +367,14 @@ extern "C" int lwp_create(int device_id, int nref, int C, int NH, int NP, int dt
             size_t n = 1;
             for (int d = 0; d < s.ndim; ++d) n *= (size_t)s.shape[d];
             h->raw_off[s.key] = h->raw_floats; h->raw_floats += n;
+        }
+        // ... then (16-byte aligned) the backbone parameters (LWP_TRAIN_ALL) and their running statistics
+        h->raw_floats = (h->raw_floats + 3) / 4 * 4;
+        for (const ParamSpec& p : param_table(nref, C, NH, NP)) {
+            if (!is_backbone_key(p.key) || p.role == LWP_ROLE_BN_NBT) continue;
+            size_t n = 1;
+            for (int d = 0; d < p.ndim; ++d) n *= (size_t)p.shape[d];
+            h->raw_off[p.key] = h->raw_floats; h->raw_floats += n;
         }
     }
     h->d_outs.resize(2 * (1 + nref));
@@ -752,13 +770,16 @@ static PostWorkspace ws_frames(const PostWorkspace& w, int f0) {
 
 // ---------------------------------------------------------------------------------------------- forward
 // element-addressed window of an activation buffer (f32, bf16 or fp16 storage)
-// (an index past the graph's buffers is a buffer of the retaining plan, TrainPlan: f32, level 3)
+// (an index past the graph's buffers is a buffer of the retaining plan, TrainPlan: f32, at its BufSpec's level)
 static inline float* buf_at(lwp_context* h, const BufRef& r) {
     const int nb = (int)h->g.bufs.size();
     char* base = (r.buf < nb ? h->bufs[r.buf] : h->tbufs[r.buf - nb]).as<char>();
     return (float*)(base + (size_t)r.coff * (h->dtype != LWP_F32 ? 2 : 4));
 }
-static inline int buf_level(const lwp_context* h, int buf) { return buf < (int)h->g.bufs.size() ? h->g.bufs[buf].level : 3; }
+static inline int buf_level(const lwp_context* h, int buf) {
+    const int nb = (int)h->g.bufs.size();
+    return buf < 0 ? 0 : buf < nb ? h->g.bufs[buf].level : h->tp.bufs[buf - nb].level;
+}
 
 static int enqueue_layer(lwp_context* h, const Layer& l, const float* d_in, int N, int H, int W, float* const* d_outs_nchw,
                          const Layer* fold = nullptr, bool* folded = nullptr) {
@@ -847,10 +868,13 @@ static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, in
     return LWP_OK;
 }
 
-// the depthwise half of a level-3 L_DWPW block alone, into train buffer `buf` (the retained copy of lwp_train_forward)
-static int enqueue_dw_copy(lwp_context* h, const Layer& l, int buf, int N, int fh, int fw) {
+// the depthwise half of an L_DWPW block alone, into train buffer `buf` (the retained copy of lwp_train_forward)
+static int enqueue_dw_copy(lwp_context* h, const Layer& l, int buf, int N, int H, int W) {
+    int sh, sw, dh, dw;
+    level_dims(H, W, buf_level(h, l.src.buf), &sh, &sw);
+    level_dims(H, W, buf_level(h, buf), &dh, &dw);
     DwParams p{buf_at(h, l.src), l.src.ld, h->blob(l.w_off), h->blob(l.b_off), h->tbufs[buf - (int)h->g.bufs.size()].as<float>(), l.cin,
-               N, fh, fw, fh, fw, l.cin, l.stride, l.dil, l.act};
+               N, sh, sw, dh, dw, l.cin, l.stride, l.dil, l.act};
     p.tune = &h->tune;
     LAUNCH(h, KC_DW, launch_dw(p, h->stream));
     return LWP_OK;
@@ -879,7 +903,7 @@ static int enqueue_forward(lwp_context* h, const std::vector<Layer>& ls, int beg
             // cpm tensors a fused launch never stores (LWP_TRAIN_CPM): the depthwise half of an L_DWPW block from a stand-alone
             // launch_dw on the block's input, the pointwise output in front of the residual add from the same launch without it
             if (h->tp.dw_copy[i] >= 0) {
-                rc = enqueue_dw_copy(h, ls[i], h->tp.dw_copy[i], N, fh, fw);
+                rc = enqueue_dw_copy(h, ls[i], h->tp.dw_copy[i], N, H, W);
                 if (rc) break;
             }
             if (h->tp.nores_copy[i] >= 0) {
@@ -2353,10 +2377,10 @@ extern "C" int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_ou
 enum BwdClass { BK_ELEMENTWISE = 0, BK_DGRAD = 1, BK_WGRAD = 2, BK_REDUCE = 3, BK_COUNT = 4 };
 
 static int ensure_train_buffers(lwp_context* h, int N, int H, int W) {
-    int fh, fw;
-    level_dims(H, W, 3, &fh, &fw);
     bool synced = false;
     for (size_t i = 0; i < h->tp.bufs.size(); ++i) {
+        int fh, fw;
+        level_dims(H, W, h->tp.bufs[i].level, &fh, &fw);
         const size_t bytes = (size_t)N * fh * fw * h->tp.bufs[i].channels * sizeof(float);
         const bool with_grad = h->tp.grad_mode[i] == TrainPlan::GRAD_ALWAYS;     // (GRAD_ON_DEMAND: stage_backward_prepare)
         const bool grow = bytes > h->tbufs[i].size() || (with_grad && bytes > h->gbufs[i].size());
@@ -2368,6 +2392,13 @@ static int ensure_train_buffers(lwp_context* h, int N, int H, int W) {
         // pad channels of a concat buffer are read with zero weights: finite at every geometry (as in ensure_activations)
         if (h->tp.bufs[i].has_pad && (grow || N != h->train_N || H != h->train_H || W != h->train_W))
             HIP_TRY(h, hipMemsetAsync(h->tbufs[i].as<void>(), 0, bytes, h->stream));
+    }
+    if (h->tp.cut < 0) {                               // LWP_TRAIN_ALL: the stem's weight gradient reads the image
+        const size_t bytes = (size_t)N * 3 * H * W * sizeof(float);
+        if (bytes > h->d_train_in.size()) {
+            if (!synced) HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, h->d_train_in.ensure(bytes));
+        }
     }
     return LWP_OK;
 }
@@ -2397,11 +2428,12 @@ extern "C" int lwp_train_forward(lwp_handle h, const float* in_device, int N, in
     h->train_N = 0;
     rc = order_in(h);
     if (rc) return rc;
-    // the layers in front of the plan's cut (cpm.conv, or the backbone's last layer in scope LWP_TRAIN_CPM): the graph's own
-    // plan, nothing retained; then the retaining plan, with the outputs of the kernels Engine.forward uses
+    // the layers in front of the plan's cut (cpm.conv, or the backbone's last layer in scope LWP_TRAIN_CPM; none in scope
+    // LWP_TRAIN_ALL): the graph's own plan, nothing retained; then the retaining plan, with the outputs of the kernels Engine.forward uses
     const TrainPlan& tp = h->tp;
+    if (tp.cut < 0) HIP_TRY(h, hipMemcpyAsync(h->d_train_in.as<void>(), in_device, (size_t)N * 3 * H * W * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     rc = enqueue_forward(h, h->g.layers, 0, tp.cut, in_device, N, H, W, nullptr);
-    if (!rc) rc = enqueue_forward(h, tp.layers, tp.cut, tp.cpm_conv + 1, in_device, N, H, W, outs_device, true);
+    if (!rc) rc = enqueue_forward(h, tp.layers, std::max(tp.cut, 0), tp.cpm_conv + 1, in_device, N, H, W, outs_device, true);
     if (rc) return rc;
     int fh, fw;
     level_dims(H, W, 3, &fh, &fw);
@@ -2431,8 +2463,8 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     if (rc) return rc;
     if (!a.keypoint_maps || !a.paf_maps || !a.mask || !a.grads) return fail(h, LWP_ERR_ARG, "keypoint_maps / paf_maps / mask / grads_device is null");
     if (a.batch_size < 1) return fail(h, LWP_ERR_ARG, "batch_size must be at least 1");
-    if (a.d_backbone && h->scope != LWP_TRAIN_CPM)
-        return fail(h, LWP_ERR_ARG, "d_backbone_device needs the train scope LWP_TRAIN_CPM (lwp_set_train_scope): in scope LWP_TRAIN_STAGES the cpm has no backward");
+    if (a.d_backbone && h->scope == LWP_TRAIN_STAGES)
+        return fail(h, LWP_ERR_ARG, "d_backbone_device needs the train scope LWP_TRAIN_CPM or LWP_TRAIN_ALL (lwp_set_train_scope): in scope LWP_TRAIN_STAGES the cpm has no backward");
     if (!std::isfinite(a.loss_scale)) return fail(h, LWP_ERR_ARG, "loss_scale must be finite");
     if (h->skel.K + 1 != h->g.NH || 2 * h->skel.L != h->g.NP) {
         snprintf(msg, sizeof msg, "the skeleton's targets have %d + 1 heat-map and 2 x %d PAF channels, the network's tensors %d and %d",
@@ -2448,35 +2480,51 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     }
     HIP_TRY(h, hipSetDevice(h->device));
     // workspace: the largest layer's wgrad partials + the folded gradients of the largest BatchNorm layer
-    const int64_t M = (int64_t)a.N * a.hs * a.ws;
-    size_t part = 0, fold = 0;
-    for (size_t i = (size_t)h->tp.cut + 1; i < h->tp.layers.size(); ++i) {
+    size_t part = 0, fold = 0, pwf = 0;
+    for (size_t i = (size_t)(h->tp.cut + 1); i < h->tp.layers.size(); ++i) {
         const Layer& l = h->tp.layers[i];
         const int ks = l.kind == L_DWPW ? 1 : l.ks;               // the pointwise half of a fused block
+        int lh, lw;                                               // the layer's output map (a backbone layer's may be above level 3)
+        level_dims(h->train_H, h->train_W, buf_level(h, l.dst.buf), &lh, &lw);
+        const int64_t M = (int64_t)a.N * lh * lw;
         auto one = [&](int cout, int cin) {
             WgradParams w{};
             w.cout = cout; w.cin = cin; w.ks = ks;
             wgrad_plan(M, cout, cin, ks, &w.splits, &w.chunk);
             part = std::max(part, wgrad_partial_floats(w));
         };
+        if (l.kind == L_STEM) {                                   // (LWP_TRAIN_ALL)
+            int sp = 0, ch = 0;
+            stem_wgrad_plan(M, &sp, &ch);
+            part = std::max(part, (size_t)sp * 28 * 32);
+            fold = std::max(fold, (size_t)32 * 27 + 32);
+            continue;
+        }
         if (l.kind == L_DW || l.kind == L_DWPW) {
             int sp = 0, ch = 0;
             dw_wgrad_plan(M, l.cin, &sp, &ch);
-            part = std::max(part, (size_t)sp * 9 * l.cin);
+            part = std::max(part, (size_t)sp * (l.bn_key.empty() ? 9 : 10) * l.cin);      // (with BatchNorm: the sum of dZ too)
+            if (!l.bn_key.empty()) fold = std::max(fold, (size_t)10 * l.cin);
             if (l.kind == L_DW) continue;
+            if (!l.bn2_key.empty()) {
+                fold = std::max(fold, (size_t)l.cout * l.cin + l.cout);
+                pwf = std::max(pwf, (size_t)l.cout * l.cin);
+            }
         }
         if (l.blocks.empty()) one(l.cout, l.cin);
         else for (const WBlock& b : l.blocks) one(b.cout, b.cin);
-        if (!l.bn_key.empty()) fold = std::max(fold, (size_t)l.cout * l.cin * l.ks * l.ks + l.cout);
+        if (l.kind == L_GEMM && !l.bn_key.empty()) fold = std::max(fold, (size_t)l.cout * l.cin * l.ks * l.ks + l.cout);
     }
     part = (part + 63) / 64 * 64;
+    fold = (fold + 63) / 64 * 64;
     h->bwd_fold_off = part;
-    const size_t need = (part + fold) * sizeof(float);
+    h->bwd_pw_off = part + fold;
+    const size_t need = (part + fold + pwf) * sizeof(float);
     if (h->d_bwd.size() < need) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         HIP_TRY(h, h->d_bwd.ensure(need));
     }
-    if (a.d_backbone) {                                // the 512-channel gradient at the cpm's input exists only once it is asked for
+    if (a.d_backbone && h->tp.cut == h->tp.cpm_in) {   // LWP_TRAIN_CPM: the 512-channel gradient at the cpm's input exists only once it is asked for
         const int xb = h->tp.layers[h->tp.cut].dst.buf - (int)h->g.bufs.size();
         if (h->gbufs[xb].size() < h->tbufs[xb].size()) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2492,30 +2540,31 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
 static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const float* x, int x_ld, int cout, int cin,
                          const std::string& conv_key, const BackwardArgs& a, size_t fold_off, bool pointwise = false) {
     const bool has_bias = !pointwise && l.has_bias;
+    const std::string& bn_key = pointwise ? l.bn2_key : l.bn_key;
     WgradParams w{};
     w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd.as<float>();
     w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = pointwise ? 1 : l.ks; w.dil = pointwise ? 1 : l.dil;
-    w.no_bias = has_bias ? 0 : 1;
+    w.no_bias = (has_bias || !bn_key.empty()) ? 0 : 1;     // the BatchNorm chain rule needs the column sums of dZ, conv bias or not
     wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, w.ks, &w.splits, &w.chunk);
     h->bwd_splits[layer_index] = w.splits;
     LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream));
     float* dw = a.grads + h->grad_off.at(conv_key + ".weight");
     float* db = has_bias ? a.grads + h->grad_off.at(conv_key + ".bias") : nullptr;
-    if (pointwise || l.bn_key.empty()) {
+    if (bn_key.empty()) {
         LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, dw, db, a.accumulate, h->stream));
         return LWP_OK;
     }
     float* G = h->d_bwd.as<float>() + fold_off;
-    float* g = G + (size_t)cout * cin * l.ks * l.ks;
+    float* g = G + (size_t)cout * cin * w.ks * w.ks;
     LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, G, g, 0, h->stream));
     BnChainParams b{};
     b.G = G; b.g = g;
-    b.W = h->raw(conv_key + ".weight"); b.b = h->raw(conv_key + ".bias");
-    b.gamma = h->raw(l.bn_key + ".weight");
-    b.mean = h->raw(l.bn_key + ".running_mean"); b.var = h->raw(l.bn_key + ".running_var");
+    b.W = h->raw(conv_key + ".weight"); b.b = has_bias ? h->raw(conv_key + ".bias") : h->d_zeros.as<float>();   // (1024 zeros: the backbone's cout is at most 512)
+    b.gamma = h->raw(bn_key + ".weight");
+    b.mean = h->raw(bn_key + ".running_mean"); b.var = h->raw(bn_key + ".running_var");
     b.dW = dw; b.db = db;
-    b.dgamma = a.grads + h->grad_off.at(l.bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(l.bn_key + ".bias");
-    b.cout = cout; b.K = cin * l.ks * l.ks; b.accumulate = a.accumulate;
+    b.dgamma = a.grads + h->grad_off.at(bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(bn_key + ".bias");
+    b.cout = cout; b.K = cin * w.ks * w.ks; b.accumulate = a.accumulate;
     LAUNCH(h, BK_REDUCE, launch_bn_chain(b, h->stream));
     return LWP_OK;
 }
@@ -2538,6 +2587,95 @@ static int enqueue_dw_backward(lwp_context* h, const Layer& l, int layer_index, 
     LAUNCH(h, BK_DGRAD, launch_dw_dgrad(p, h->stream));
     written[l.src.buf - nb] = 1;
     return LWP_OK;
+}
+
+// BatchNorm chain rule of a backbone conv without bias: folded G, g in the workspace -> dW, dgamma, dbeta in the gradient array
+static int enqueue_bn_chain_nobias(lwp_context* h, const std::string& conv_key, const std::string& bn_key, float* G, float* g, int cout, int K,
+                                   const BackwardArgs& a) {
+    BnChainParams b{};
+    b.G = G; b.g = g;
+    b.W = h->raw(conv_key + ".weight"); b.b = h->d_zeros.as<float>();
+    b.gamma = h->raw(bn_key + ".weight");
+    b.mean = h->raw(bn_key + ".running_mean"); b.var = h->raw(bn_key + ".running_var");
+    b.dW = a.grads + h->grad_off.at(conv_key + ".weight"); b.db = nullptr;
+    b.dgamma = a.grads + h->grad_off.at(bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(bn_key + ".bias");
+    b.cout = cout; b.K = K; b.accumulate = a.accumulate;
+    LAUNCH(h, BK_REDUCE, launch_bn_chain(b, h->stream));
+    return LWP_OK;
+}
+
+// depthwise 3x3 of the backbone (an L_DW layer, or the first half of an L_DWPW block), stride 1 | 2, dilation 1 | 2, BatchNorm
+// behind it: dz is the gradient at its pre-activation output (the ReLU mask is applied), a.hs x a.ws its output map
+static int enqueue_dw_sd_backward(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const BackwardArgs& a,
+                                  std::vector<char>& written) {
+    const int nb = (int)h->g.bufs.size();
+    DwGradSdParams p{};
+    p.dz = dz; p.dz_ld = dz_ld; p.x = buf_at(h, l.src); p.x_ld = l.src.ld; p.w = h->blob(l.w_off);
+    p.dx = grad_at(h, l.src); p.dx_ld = l.src.ld; p.partial = h->d_bwd.as<float>();
+    level_dims(h->train_H, h->train_W, buf_level(h, l.src.buf), &p.H, &p.W);
+    p.N = a.N; p.Ho = a.hs; p.Wo = a.ws; p.C = l.cin; p.stride = l.stride; p.dil = l.dil; p.beta = written[l.src.buf - nb];
+    dw_wgrad_plan((int64_t)a.N * a.hs * a.ws, l.cin, &p.splits, &p.chunk);
+    h->bwd_dw_splits[layer_index] = p.splits;
+    if (l.kind == L_DW) h->bwd_splits[layer_index] = p.splits;
+    float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
+    float* g = G + (size_t)9 * l.cin;
+    LAUNCH(h, BK_WGRAD, launch_dw_wgrad_sd(p, h->stream));
+    LAUNCH(h, BK_REDUCE, launch_dw_wgrad_sd_reduce(p, G, g, h->stream));
+    const int rc = enqueue_bn_chain_nobias(h, l.conv_key, l.bn_key, G, g, l.cin, 9, a);
+    if (rc) return rc;
+    LAUNCH(h, BK_DGRAD, launch_dw_dgrad_sd(p, h->stream));
+    written[l.src.buf - nb] = 1;
+    return LWP_OK;
+}
+
+// one backbone layer (LWP_TRAIN_ALL; with_mobilenet.py:92-105): conv without bias, BatchNorm at its running statistics, ReLU
+static int enqueue_backbone_backward(lwp_context* h, const Layer& l, int i, const BackwardArgs& a, std::vector<char>& written) {
+    const TrainPlan& tp = h->tp;
+    const int nb = (int)h->g.bufs.size();
+    BackwardArgs al = a;                               // the layer's own output map
+    level_dims(h->train_H, h->train_W, buf_level(h, l.dst.buf), &al.hs, &al.ws);
+    const int64_t M = (int64_t)al.N * al.hs * al.ws;
+    float* dy = grad_at(h, l.dst);
+    LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(dy, l.dst.ld, buf_at(h, l.dst), l.dst.ld, nullptr, 0, M, l.cout, h->stream));
+    if (l.kind == L_STEM) {                            // weight gradient only: there is no gradient at the image
+        StemWgradParams p{};
+        p.dz = dy; p.dz_ld = l.dst.ld; p.x = h->d_train_in.as<float>(); p.partial = h->d_bwd.as<float>();
+        p.N = al.N; p.H = h->train_H; p.W = h->train_W; p.Ho = al.hs; p.Wo = al.ws;
+        stem_wgrad_plan(M, &p.splits, &p.chunk);
+        h->bwd_splits[i] = p.splits;
+        float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
+        float* g = G + 32 * 27;
+        LAUNCH(h, BK_WGRAD, launch_stem_wgrad(p, h->stream));
+        LAUNCH(h, BK_REDUCE, launch_stem_wgrad_reduce(p, G, g, h->stream));
+        return enqueue_bn_chain_nobias(h, l.conv_key, l.bn_key, G, g, 32, 27, al);
+    }
+    if (l.kind == L_DW) return enqueue_dw_sd_backward(h, l, i, dy, l.dst.ld, al, written);
+    DgradParams d{};
+    d.dz = dy; d.dz_ld = l.dst.ld;
+    d.N = al.N; d.H = al.hs; d.W = al.ws; d.cout = l.cout; d.cin = l.cin; d.ks = 1; d.dil = 1;
+    if (l.kind == L_GEMM) {                            // an unfused pointwise layer: the blob's [cout_pad][cin_pad] copy holds the folded weights
+        const int rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, buf_at(h, l.src), l.src.ld, l.cout, l.cin, l.conv_key, al, h->bwd_fold_off);
+        if (rc) return rc;
+        d.w = h->blob(l.w_off); d.cout_pad = l.cout_pad; d.cin_pad = l.cin_pad;
+        d.dx = grad_at(h, l.src); d.dx_ld = l.src.ld; d.acc_from = written[l.src.buf - nb] ? 0 : l.cin;
+        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+        written[l.src.buf - nb] = 1;
+        return LWP_OK;
+    }
+    // a fused block: the pointwise half on the retained depthwise copy (its folded weights exist in fragment order only, so the
+    // plain matrix is folded from the raw parameters for this launch), then the depthwise half
+    const float* dcopy = h->tbufs[tp.dw_copy[i] - nb].as<float>();
+    float* gd = h->gbufs[tp.dw_copy[i] - nb].as<float>();
+    int rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, dcopy, l.cin, l.cout, l.cin, l.conv2_key, al, h->bwd_fold_off, true);
+    if (rc) return rc;
+    float* wf = h->d_bwd.as<float>() + h->bwd_pw_off;
+    LAUNCH(h, BK_ELEMENTWISE, launch_pw_fold(h->raw(l.conv2_key + ".weight"), h->raw(l.bn2_key + ".weight"), h->raw(l.bn2_key + ".running_var"), wf,
+                                             l.cout, l.cin, h->stream));
+    d.w = wf; d.cout_pad = l.cout; d.cin_pad = l.cin;
+    d.dx = gd; d.dx_ld = l.cin; d.acc_from = l.cin;
+    LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+    LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(gd, l.cin, dcopy, l.cin, nullptr, 0, M, l.cin, h->stream));
+    return enqueue_dw_sd_backward(h, l, i, gd, l.cin, al, written);
 }
 
 static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
@@ -2570,6 +2708,13 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
     for (int i = (int)tp.layers.size() - 1; i > tp.cut; --i) {
         const Layer& l = tp.layers[i];
         h->cur_layer = i;
+        if (i <= tp.cpm_in) {                  // LWP_TRAIN_ALL: the backbone, below the cpm's input
+            if (i == tp.cpm_in && a.d_backbone)
+                LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(grad_at(h, l.dst), l.dst.ld, a.d_backbone, a.N, a.hs * a.ws, l.cout, h->stream));
+            const int rc = enqueue_backbone_backward(h, l, i, a, written);
+            if (rc) { h->cur_layer = -1; return rc; }
+            continue;
+        }
         float* dy = grad_at(h, l.dst);
         const float* y = buf_at(h, l.dst);
         if (i == tp.cpm_conv && tp.cut != tp.cpm_conv) {
@@ -2634,7 +2779,7 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
     }
     h->cur_layer = -1;
     // 3. backbone_features feeds the initial stage and every refinement stage: stage order, then NCHW
-    if (a.d_backbone) {
+    if (a.d_backbone && tp.cut == tp.cpm_in) {
         const BufRef& xin = tp.layers[tp.cut].dst;
         LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(grad_at(h, xin), xin.ld, a.d_backbone, a.N, a.hs * a.ws, tp.layers[tp.cut].cout, h->stream));
     }
@@ -2673,7 +2818,8 @@ extern "C" int lwp_train_backward(lwp_handle h, const float* keypoint_maps, cons
 extern "C" int lwp_set_train_scope(lwp_handle h, int scope) {
     if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
     if (h->dtype != LWP_F32) return fail(h, LWP_ERR_ARG, "the train scope belongs to fp32 handles only (this one is bf16 / fp16)");
-    if (scope != LWP_TRAIN_STAGES && scope != LWP_TRAIN_CPM) return fail(h, LWP_ERR_ARG, "unknown train scope (LWP_TRAIN_STAGES or LWP_TRAIN_CPM)");
+    if (scope != LWP_TRAIN_STAGES && scope != LWP_TRAIN_CPM && scope != LWP_TRAIN_ALL)
+        return fail(h, LWP_ERR_ARG, "unknown train scope (LWP_TRAIN_STAGES, LWP_TRAIN_CPM or LWP_TRAIN_ALL)");
     for (auto& sl : h->slots) if (sl.pending) return fail(h, LWP_ERR_STATE, "pipeline slot pending: fetch it before changing the train scope");
     if (h->async_pending) return fail(h, LWP_ERR_STATE, "an lwp_infer_poses_async is pending: fetch it before changing the train scope");
     if (h->adam_t > 0)
@@ -2735,7 +2881,7 @@ extern "C" int lwp_stage_grad_spec(int nref, int C, int NH, int NP, int index, c
 }
 
 static bool train_shape_ok(int scope, int nref, int C, int NH, int NP) {
-    return (scope == LWP_TRAIN_STAGES || scope == LWP_TRAIN_CPM) && nref >= 0 && C > 0 && NH > 0 && NP > 0;
+    return (scope == LWP_TRAIN_STAGES || scope == LWP_TRAIN_CPM || scope == LWP_TRAIN_ALL) && nref >= 0 && C > 0 && NH > 0 && NP > 0;
 }
 extern "C" int lwp_train_grad_count(int scope, int nref, int C, int NH, int NP, int64_t* total_floats) {
     if (!train_shape_ok(scope, nref, C, NH, NP)) return LWP_ERR_ARG;
@@ -2766,7 +2912,7 @@ extern "C" int lwp_debug_train_copy(lwp_handle h, int idx, int which, float* dst
     int rc = train_handle_check(h);
     if (rc) return rc;
     if (!dst || !out_dims) return fail(h, LWP_ERR_ARG, "bad argument");
-    if (idx < h->tp.cut || idx >= (int)h->tp.layers.size()) return fail(h, LWP_ERR_ARG, "layer_index is not a layer of the retaining plan");
+    if (idx < 0 || idx < h->tp.cut || idx >= (int)h->tp.layers.size()) return fail(h, LWP_ERR_ARG, "layer_index is not a layer of the retaining plan");
     if (which != LWP_KEPT_OUTPUT && which != LWP_KEPT_DEPTHWISE && which != LWP_KEPT_NO_RESIDUAL) return fail(h, LWP_ERR_ARG, "unknown kind of retained tensor");
     if ((which == LWP_KEPT_DEPTHWISE && h->tp.dw_copy[idx] < 0) || (which == LWP_KEPT_NO_RESIDUAL && h->tp.nores_copy[idx] < 0))
         return fail(h, LWP_ERR_ARG, "the layer has no such retained copy");
@@ -2776,7 +2922,7 @@ extern "C" int lwp_debug_train_copy(lwp_handle h, int idx, int which, float* dst
     if (which == LWP_KEPT_DEPTHWISE) { l.dst = BufRef(); l.dst.buf = h->tp.dw_copy[idx]; l.dst.ld = l.cin; l.cout = l.cin; }
     if (which == LWP_KEPT_NO_RESIDUAL) { l.dst.buf = h->tp.nores_copy[idx]; l.dst.coff = 0; }
     int dh, dw;
-    level_dims(h->train_H, h->train_W, 3, &dh, &dw);
+    level_dims(h->train_H, h->train_W, buf_level(h, l.dst.buf), &dh, &dw);
     const size_t n = (size_t)h->train_N * l.cout * dh * dw;
     if (dst_floats < n) return fail(h, LWP_ERR_ARG, "dst too small");
     HIP_TRY(h, h->d_tmp.ensure(n * sizeof(float)));
@@ -2797,6 +2943,50 @@ extern "C" int lwp_debug_backward_dw_splits(lwp_handle h, int idx) {
     return h->bwd_dw_splits[idx];
 }
 
+// the backbone's gradient kernels alone (tests): crafted tensors in, results out, the partials in a scratch allocation
+extern "C" int lwp_debug_dw_grad_sd(lwp_handle h, const float* dz, const float* x, const float* w, int N, int H, int W, int C, int stride, int dil,
+                                    int max_chunk, float* dx, float* G, float* g, int* splits) {
+    if (!h || !dz || !x || !w || !dx || !G || !g || !splits) return fail(h, LWP_ERR_ARG, "null argument");
+    if (N < 1 || H < 1 || W < 1 || C < 4 || (C & 3) || (stride != 1 && stride != 2) || (dil != 1 && dil != 2) || max_chunk < 0 || (max_chunk & 15))
+        return fail(h, LWP_ERR_ARG, "bad shape (C a multiple of 4, stride and dilation 1 or 2, max_chunk a multiple of 16)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    DwGradSdParams p{};
+    p.dz = dz; p.dz_ld = C; p.x = x; p.x_ld = C; p.w = w; p.dx = dx; p.dx_ld = C;
+    p.N = N; p.H = H; p.W = W; p.Ho = (H - 1) / stride + 1; p.Wo = (W - 1) / stride + 1; p.C = C; p.stride = stride; p.dil = dil; p.beta = 0;
+    const int64_t M = (int64_t)N * p.Ho * p.Wo;
+    dw_wgrad_plan(M, C, &p.splits, &p.chunk);
+    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    DevBuf part;
+    HIP_TRY(h, part.ensure((size_t)p.splits * 10 * C * sizeof(float)));
+    p.partial = part.as<float>();
+    HIP_TRY(h, launch_dw_wgrad_sd(p, h->stream));
+    HIP_TRY(h, launch_dw_wgrad_sd_reduce(p, G, g, h->stream));
+    HIP_TRY(h, launch_dw_dgrad_sd(p, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *splits = p.splits;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_stem_wgrad(lwp_handle h, const float* dz, const float* x, int N, int H, int W, int max_chunk, float* G, float* g, int* splits) {
+    if (!h || !dz || !x || !G || !g || !splits) return fail(h, LWP_ERR_ARG, "null argument");
+    if (N < 1 || H < 1 || W < 1 || max_chunk < 0) return fail(h, LWP_ERR_ARG, "bad shape");
+    HIP_TRY(h, hipSetDevice(h->device));
+    StemWgradParams p{};
+    p.dz = dz; p.dz_ld = 32; p.x = x;
+    p.N = N; p.H = H; p.W = W; p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
+    const int64_t M = (int64_t)N * p.Ho * p.Wo;
+    stem_wgrad_plan(M, &p.splits, &p.chunk);
+    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    DevBuf part;
+    HIP_TRY(h, part.ensure((size_t)p.splits * 28 * 32 * sizeof(float)));
+    p.partial = part.as<float>();
+    HIP_TRY(h, launch_stem_wgrad(p, h->stream));
+    HIP_TRY(h, launch_stem_wgrad_reduce(p, G, g, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *splits = p.splits;
+    return LWP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- stage fine-tuning step
 // train.py:41-55's parameter groups for the stage parameters: log2 of the learning-rate multiplier in bits 0-1, weight decay in bit 2
 static uint32_t stage_adam_group(const std::string& key, int role) {
@@ -2815,13 +3005,21 @@ static uint32_t cpm_adam_group(const std::string& key, int role) {
     const bool depthwise = key.rfind("cpm.trunk.", 0) == 0 && key.size() > 8 && key.compare(key.size() - 9, 9, ".0.weight") == 0;
     return depthwise ? 0u : 4u;
 }
+// train.py:42-45 with get_parameters.py for the backbone: conv weights with groups == 1 (the stem model.0.0 and the pointwise
+// model.i.3) x1 with weight decay, depthwise weights (model.i.0, i >= 1) x1 without, BatchNorm weights x1 without, biases x2 without
+static uint32_t backbone_adam_group(const std::string& key, int role) {
+    if (role == LWP_ROLE_BN_W) return 0u;
+    if (role == LWP_ROLE_BN_B) return 1u;
+    const bool depthwise = key.rfind("model.0.", 0) != 0 && key.size() > 8 && key.compare(key.size() - 9, 9, ".0.weight") == 0;
+    return depthwise ? 0u : 4u;
+}
 static std::vector<uint32_t> train_adam_groups(int scope, int nref, int C, int NH, int NP) {
     std::vector<uint32_t> v;
     const std::vector<ParamSpec> table = param_table(nref, C, NH, NP);
-    for (int part = scope == LWP_TRAIN_CPM ? 0 : 1; part < 2; ++part)
+    for (int part = first_part(scope); part < 3; ++part)
         for (const ParamSpec& p : table)
-            if ((part == 0 ? is_cpm_key(p.key) : is_stage_key(p.key)) && p.role != LWP_ROLE_BN_MEAN && p.role != LWP_ROLE_BN_VAR && p.role != LWP_ROLE_BN_NBT)
-                v.push_back(part == 0 ? cpm_adam_group(p.key, p.role) : stage_adam_group(p.key, p.role));
+            if (in_part(part, p.key) && p.role != LWP_ROLE_BN_MEAN && p.role != LWP_ROLE_BN_VAR && p.role != LWP_ROLE_BN_NBT)
+                v.push_back(part == 0 ? backbone_adam_group(p.key, p.role) : part == 1 ? cpm_adam_group(p.key, p.role) : stage_adam_group(p.key, p.role));
     return v;
 }
 static std::vector<uint32_t> stage_adam_groups(int nref, int C, int NH, int NP) { return train_adam_groups(LWP_TRAIN_STAGES, nref, C, NH, NP); }
@@ -2876,14 +3074,36 @@ static int ensure_adam_tables(lwp_context* h) {
     std::vector<RepackLayer> tab;
     uint32_t blocks = 0;
     std::vector<DwRepack> dws;
-    for (size_t i = (size_t)h->tp.cut + 1; i < h->g.layers.size(); ++i) {
+    StemRepack stem{};
+    bool has_stem = false;
+    for (size_t i = (size_t)(h->tp.cut + 1); i < h->g.layers.size(); ++i) {
         const Layer& l = h->g.layers[i];
-        if ((l.kind == L_DW || l.kind == L_DWPW) && l.bn_key.empty() && l.bn2_key.empty()) {      // the cpm trunk (LWP_TRAIN_CPM)
+        if (l.kind == L_STEM) {                            // model.0 (LWP_TRAIN_ALL)
+            stem.w_raw = raw_at(l.conv_key + ".weight");
+            stem.gamma = raw_at(l.bn_key + ".weight"); stem.beta = raw_at(l.bn_key + ".bias");
+            stem.mean = raw_at(l.bn_key + ".running_mean"); stem.var = raw_at(l.bn_key + ".running_var");
+            stem.w_off = (uint32_t)l.w_off; stem.b_off = (uint32_t)l.b_off;
+            if (stem.w_raw < 0 || stem.gamma < 0 || stem.beta < 0 || stem.mean < 0 || stem.var < 0) return fail(h, LWP_ERR_STATE, "raw parameters of '" + l.name + "' missing");
+            has_stem = true;
+            continue;
+        }
+        if (l.kind == L_DW || l.kind == L_DWPW) {          // the cpm trunk (no BatchNorm), the backbone's blocks (LWP_TRAIN_ALL: BatchNorm behind both halves)
             DwRepack d{};
             d.C = l.cin; d.cout = l.kind == L_DWPW ? l.cout : 0;
             d.dw_raw = raw_at(l.conv_key + ".weight"); d.pw_raw = l.kind == L_DWPW ? raw_at(l.conv2_key + ".weight") : -1;
             d.w_off = (uint32_t)l.w_off; d.b_off = (uint32_t)l.b_off; d.w2_off = (uint32_t)l.w2_off; d.b2_off = (uint32_t)l.b2_off;
             if (d.dw_raw < 0 || (d.cout > 0 && d.pw_raw < 0)) return fail(h, LWP_ERR_STATE, "raw weights of '" + l.name + "' missing");
+            d.dw_gamma = d.dw_beta = d.dw_mean = d.dw_var = d.pw_gamma = d.pw_beta = d.pw_mean = d.pw_var = -1;
+            if (!l.bn_key.empty()) {
+                d.dw_gamma = raw_at(l.bn_key + ".weight"); d.dw_beta = raw_at(l.bn_key + ".bias");
+                d.dw_mean = raw_at(l.bn_key + ".running_mean"); d.dw_var = raw_at(l.bn_key + ".running_var");
+                if (d.dw_gamma < 0 || d.dw_beta < 0 || d.dw_mean < 0 || d.dw_var < 0) return fail(h, LWP_ERR_STATE, "raw BatchNorm parameters of '" + l.name + "' missing");
+            }
+            if (l.kind == L_DWPW && !l.bn2_key.empty()) {
+                d.pw_gamma = raw_at(l.bn2_key + ".weight"); d.pw_beta = raw_at(l.bn2_key + ".bias");
+                d.pw_mean = raw_at(l.bn2_key + ".running_mean"); d.pw_var = raw_at(l.bn2_key + ".running_var");
+                if (d.pw_gamma < 0 || d.pw_beta < 0 || d.pw_mean < 0 || d.pw_var < 0) return fail(h, LWP_ERR_STATE, "raw BatchNorm parameters of '" + l.name + "' missing");
+            }
             dws.push_back(d);
             continue;
         }
@@ -2920,6 +3140,7 @@ static int ensure_adam_tables(lwp_context* h) {
     h->d_repack = std::move(d_tab); h->repack_layers = (int)tab.size(); h->repack_blocks = (int)blocks;
     h->d_adam_chunks = std::move(d_chunks); h->adam_chunks = (int)chunks.size();
     h->dw_repack = dws;
+    h->stem_repack = stem; h->has_stem_repack = has_stem;
     return LWP_OK;
 }
 
@@ -2982,6 +3203,7 @@ extern "C" int lwp_stage_adam_step(lwp_handle h, const float* grads_device, doub
     h->train_N = 0;                                    // the retained activations belong to the old weights
     hipError_t e = launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
     for (size_t k = 0; k < h->dw_repack.size() && e == hipSuccess; ++k) e = launch_dw_repack(h->dw_repack[k], h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
+    if (h->has_stem_repack && e == hipSuccess) e = launch_stem_repack(h->stem_repack, h->d_raw.as<float>(), h->d_blob.as<float>(), h->stream);
     if (e != hipSuccess) {                             // the blob no longer matches the raw parameters: no forward until lwp_load_weights
         h->weights_loaded = false;
         return fail(h, LWP_ERR_HIP, std::string("launch_stage_repack: ") + hipGetErrorString(e) + " (the weight blob is stale: load the weights again)");
@@ -3094,6 +3316,7 @@ extern "C" int lwp_time_stage_adam_step(lwp_handle h, const float* grads_device,
         rc = time_on_stream(h, iters, [&]() {
             LAUNCH(h, KC_OTHER, launch_stage_repack(h->d_repack.as<RepackLayer>(), h->repack_layers, h->repack_blocks, raw.as<float>(), blob.as<float>(), h->stream));
             for (const DwRepack& d : h->dw_repack) LAUNCH(h, KC_OTHER, launch_dw_repack(d, raw.as<float>(), blob.as<float>(), h->stream));
+            if (h->has_stem_repack) LAUNCH(h, KC_OTHER, launch_stem_repack(h->stem_repack, raw.as<float>(), blob.as<float>(), h->stream));
             return (int)LWP_OK; }, &ms[1]);
     (void)hipStreamSynchronize(h->stream);             // the scratch arrays are freed on return
     return rc;

@@ -85,13 +85,18 @@ Graph build_graph(int nref, int C, int NH, int NP, bool fuse_dwpw, int dtype, bo
 // launch and get a retained copy from a second launch (enqueue_forward): the depthwise output of an L_DWPW block
 // (dw_copy[i]: a buffer for a stand-alone launch_dw on the block's input) and the pointwise output of the block that adds
 // the residual `a` in its epilogue (nores_copy[i]: a buffer for the same launch without the residual).
+//
+// Scope LWP_TRAIN_ALL moves the cut to the network input: every backbone layer writes a buffer of its own at its own level
+// (BufSpec::level; the train buffers of the narrower scopes are all at level 3), and a fused backbone block gets a dw_copy too.
 struct TrainPlan {
     std::vector<Layer> layers;     // Graph::layers with src / dst / res re-pointed
     std::vector<BufSpec> bufs;     // the train buffers
     std::vector<int> cats;         // nref + 1 concat buffers (plan indices)
     int cpm_conv = -1;             // index of cpm.conv
+    int cpm_in = -1;               // index of the layer in front of cpm.align (the backbone's last layer: its output is the cpm's input)
     int cut = -1;                  // layers before it run on the graph's own plan and retain nothing; the layers behind it have a
-                                   // backward.  LWP_TRAIN_STAGES: cpm.conv; LWP_TRAIN_CPM: the layer in front of cpm.align
+                                   // backward.  LWP_TRAIN_STAGES: cpm.conv; LWP_TRAIN_CPM: cpm_in; LWP_TRAIN_ALL: -1 (every layer
+                                   // has a backward: the cut is the network input)
     std::vector<int> dw_copy, nores_copy;   // per layer: plan buffer index, -1: none
     // per train buffer: does it have a gradient buffer?  GRAD_NEVER: a no-residual copy (only its values are read, as the
     // ELU output); GRAD_ON_DEMAND: the cpm's 512-channel input, whose gradient exists only when lwp_train_backward is asked for it
@@ -458,6 +463,34 @@ hipError_t launch_dw_dgrad(const DwGradParams& p, hipStream_t s);
 hipError_t launch_dw_wgrad(const DwGradParams& p, hipStream_t s);
 // fixed-order sum of the partials into the OIHW (C, 1, 3, 3) gradient; accumulate: added to what is there
 hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, int accumulate, hipStream_t s);
+// ---- backbone backward (with_mobilenet.py:93-104): depthwise 3x3 with stride 1 | 2 and dilation 1 | 2 (padding = dilation), and
+//      the stem's weight gradient.  The depthwise wgrad also sums dZ per channel (the folded bias gradient of its BatchNorm).
+struct DwGradSdParams {
+    const float* dz; int dz_ld;      // N Ho Wo x C gradient of the depthwise conv's pre-activation output
+    const float* x; int x_ld;        // wgrad: the retained input, N H W x C
+    const float* w;                  // dgrad: the forward blob's [9][C] (folded)
+    float* dx; int dx_ld;            // dgrad: N H W x C; beta != 0: added to, else overwritten
+    float* partial;                  // wgrad: [splits][10][C], row 9 the sum of dZ
+    int N, H, W, Ho, Wo, C, stride, dil, beta;
+    int splits, chunk;               // wgrad: ranges of output pixels (dw_wgrad_plan over N Ho Wo)
+};
+hipError_t launch_dw_dgrad_sd(const DwGradSdParams& p, hipStream_t s);
+hipError_t launch_dw_wgrad_sd(const DwGradSdParams& p, hipStream_t s);
+// fixed-order sum of the partials into G, OIHW (C, 1, 3, 3), and g (C); both overwritten
+hipError_t launch_dw_wgrad_sd_reduce(const DwGradSdParams& p, float* G, float* g, hipStream_t s);
+struct StemWgradParams {
+    const float* dz; int dz_ld;      // N Ho Wo x 32 gradient of the stem's pre-activation output
+    const float* x;                  // N x 3 x H x W, the input the stem kernel read
+    float* partial;                  // [splits][28][32]: the 27 weight rows (ci, ky, kx), then the sum of dZ
+    int N, H, W, Ho, Wo;
+    int splits, chunk;               // ranges of output pixels (stem_wgrad_plan)
+};
+void stem_wgrad_plan(int64_t M, int* splits, int* chunk);
+hipError_t launch_stem_wgrad(const StemWgradParams& p, hipStream_t s);
+// fixed-order sum of the partials into G, OIHW (32, 3, 3, 3), and g (32); both overwritten
+hipError_t launch_stem_wgrad_reduce(const StemWgradParams& p, float* G, float* g, hipStream_t s);
+// out[o][ci] = float(double(w[o][ci]) * gamma[o] / sqrt(double(var[o]) + 1e-5)): a fused block's folded pointwise weights as a plain matrix
+hipError_t launch_pw_fold(const float* w, const float* gamma, const float* var, float* out, int cout, int cin, hipStream_t s);
 struct BnChainParams {               // BatchNorm at running statistics behind a conv: folded gradients -> raw ones (float64 inside)
     const float* G; const float* g;  // gradient of the folded weight [cout][K] and of the folded bias [cout]
     const float* W; const float* b;  // raw conv weight [cout][K] and bias
@@ -493,12 +526,19 @@ struct RepackLayer {                 // one fp32 L_GEMM layer: where its raw par
     RepackBlock blk[2];
 };
 hipError_t launch_stage_repack(const RepackLayer* tab_device, int n_layers, int n_blocks, const float* raw, float* blob, hipStream_t s);
-struct DwRepack {                    // one fp32 L_DW or L_DWPW layer without BatchNorm (the cpm trunk): float offsets into d_raw / the blob
+struct DwRepack {                    // one fp32 L_DW or L_DWPW layer (the cpm trunk; the backbone): float offsets into d_raw / the blob
     int C, cout;                     // cout = 0: L_DW, no pointwise half
     int dw_raw, pw_raw;
     uint32_t w_off, b_off, w2_off, b2_off;
+    int dw_gamma, dw_beta, dw_mean, dw_var;   // BatchNorm behind the depthwise half (the backbone), -1: none (the cpm trunk)
+    int pw_gamma, pw_beta, pw_mean, pw_var;   // ... behind the pointwise half
 };
 hipError_t launch_dw_repack(const DwRepack& l, const float* raw, float* blob, hipStream_t s);
+struct StemRepack {                  // model.0: float offsets into d_raw / the blob
+    int w_raw, gamma, beta, mean, var;
+    uint32_t w_off, b_off;
+};
+hipError_t launch_stem_repack(const StemRepack& l, const float* raw, float* blob, hipStream_t s);
 
 hipError_t init_cubic_tables();
 hipError_t launch_reset_ws(int N, PostWorkspace& ws, hipStream_t s);

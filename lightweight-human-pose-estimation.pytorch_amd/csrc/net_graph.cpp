@@ -8,6 +8,7 @@
 //           optional residual add after the activation             conv.py:4-10,19-21,30-31
 // torch.cat([features, heat, paf]) (with_mobilenet.py:121) is free: the producing layers write
 // channel windows of one [C | NH | NP | pad] buffer.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -287,13 +288,13 @@ TrainPlan build_train_plan(const Graph& g, int scope) {
     TrainPlan t;
     t.layers = g.layers;
     const int nb = (int)g.bufs.size();
-    auto new_buf = [&](int ch, bool pad) {
-        BufSpec b{3, ch};
+    auto new_buf = [&](int ch, bool pad, int level) {
+        BufSpec b{level, ch};
         b.has_pad = pad;
         t.bufs.push_back(b);
         return nb + (int)t.bufs.size() - 1;
     };
-    for (int s = 0; s <= g.nref; ++s) t.cats.push_back(new_buf(g.cat_channels, true));
+    for (int s = 0; s <= g.nref; ++s) t.cats.push_back(new_buf(g.cat_channels, true, 3));
     t.dw_copy.assign(t.layers.size(), -1);
     t.nores_copy.assign(t.layers.size(), -1);
     int align = -1;
@@ -301,12 +302,13 @@ TrainPlan build_train_plan(const Graph& g, int scope) {
         if (t.layers[i].name == "cpm.conv") t.cpm_conv = (int)i;
         if (t.layers[i].name == "cpm.align") align = (int)i;
     }
-    t.cut = scope == LWP_TRAIN_CPM ? align - 1 : t.cpm_conv;
+    t.cpm_in = align - 1;
+    t.cut = scope == LWP_TRAIN_ALL ? -1 : scope == LWP_TRAIN_CPM ? t.cpm_in : t.cpm_conv;
     std::vector<int> cur(nb, -1);          // graph buffer -> the train buffer that holds its latest tensor
     int read_cat = 0;                      // the concat buffer a reader of the graph's concat buffer means
-    for (size_t i = (size_t)t.cut; i < t.layers.size(); ++i) {
+    for (size_t i = (size_t)std::max(t.cut, 0); i < t.layers.size(); ++i) {
         Layer& l = t.layers[i];
-        if ((int)i > t.cut) {
+        if ((int)i > t.cut && l.src.buf >= 0) {                           // (the stem reads the caller's image: no buffer)
             l.src.buf = l.src.buf == g.cat_buf ? t.cats[read_cat] : cur[l.src.buf];
             if (l.res.buf >= 0) l.res.buf = cur[l.res.buf];
         }
@@ -316,17 +318,17 @@ TrainPlan build_train_plan(const Graph& g, int scope) {
             read_cat = stage;
         } else {
             const int old = l.dst.buf;
-            l.dst.buf = new_buf(l.dst.ld, false);
+            l.dst.buf = new_buf(l.dst.ld, false, g.bufs[old].level);
             cur[old] = l.dst.buf;
         }
-        if ((int)i > t.cut && (int)i < t.cpm_conv) {                      // cpm layers with a backward (LWP_TRAIN_CPM only)
-            if (l.kind == L_DWPW) t.dw_copy[i] = new_buf(l.cin, false);
-            if (l.res.buf >= 0) t.nores_copy[i] = new_buf(l.dst.ld, false);
+        if ((int)i > t.cut && (int)i < t.cpm_conv) {                      // backbone (LWP_TRAIN_ALL) and cpm layers with a backward
+            if (l.kind == L_DWPW) t.dw_copy[i] = new_buf(l.cin, false, t.bufs[l.dst.buf - nb].level);
+            if (l.res.buf >= 0) t.nores_copy[i] = new_buf(l.dst.ld, false, 3);
         }
     }
     t.grad_mode.assign(t.bufs.size(), TrainPlan::GRAD_ALWAYS);
     for (int b : t.nores_copy) if (b >= 0) t.grad_mode[b - nb] = TrainPlan::GRAD_NEVER;
-    if (t.cut != t.cpm_conv) t.grad_mode[t.layers[t.cut].dst.buf - nb] = TrainPlan::GRAD_ON_DEMAND;
+    if (t.cut == t.cpm_in) t.grad_mode[t.layers[t.cut].dst.buf - nb] = TrainPlan::GRAD_ON_DEMAND;
     return t;
 }
 

@@ -128,19 +128,27 @@ hipError_t launch_stage_repack(const RepackLayer* tab_device, int n_layers, int 
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------------ repack, cpm trunk
-// An L_DW / L_DWPW layer without BatchNorm, as pack_weights writes it: the depthwise (C, 1, 3, 3) as [tap][C] with a zero bias
+// ------------------------------------------------------------------------------------------------ repack, depthwise and fused layers
+// An L_DW / L_DWPW layer as pack_weights writes it.  Without BatchNorm (the cpm trunk): the depthwise (C, 1, 3, 3) as [tap][C] with a zero bias
 // row, the pointwise (cout, C, 1, 1) in the f32 MFMA fragment order [C/32][cout/32][4][64 lanes][4] (lane (q = lane >> 4,
 // c = lane & 15) holds value v = 8 u + 2 j + t = W[n = 32 w + 16 t + c][k = 32 s + 16 u + 4 q + j]) with a zero bias row.  The
 // fold scale of a layer without BatchNorm is exactly 1.0, so pack_weights' float(double(w) * 1.0) is w itself: every element is
-// a plain copy of its raw value.  One thread per destination float.
+// a plain copy of its raw value.  With BatchNorm (the backbone, LWP_TRAIN_ALL; a half whose gamma offset is >= 0): the fold of
+// pack_weights, scale = gamma / sqrt(double(var) + 1e-5) in double, float(double(w) * scale), and the bias row
+// float((0 - mu) * scale + beta) (these convs have no bias of their own).  One thread per destination float.
 __global__ void __launch_bounds__(256) dw_repack_kernel(DwRepack l, const float* __restrict__ raw, float* __restrict__ blob) {
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     const unsigned n_dw = 9u * l.C, n_pw = (unsigned)l.C * l.cout;
     if (i < n_dw) {
         const unsigned t = i / l.C, c = i % l.C;
-        blob[l.w_off + i] = raw[l.dw_raw + c * 9 + t];
-        if (t == 0) blob[l.b_off + c] = 0.f;
+        if (l.dw_gamma < 0) {
+            blob[l.w_off + i] = raw[l.dw_raw + c * 9 + t];
+            if (t == 0) blob[l.b_off + c] = 0.f;
+            return;
+        }
+        const double scale = (double)raw[l.dw_gamma + c] / sqrt((double)raw[l.dw_var + c] + 1e-5);
+        blob[l.w_off + i] = (float)((double)raw[l.dw_raw + c * 9 + t] * scale);
+        if (t == 0) blob[l.b_off + c] = (float)((0.0 - (double)raw[l.dw_mean + c]) * scale + (double)raw[l.dw_beta + c]);
         return;
     }
     const unsigned e = i - n_dw;
@@ -150,14 +158,44 @@ __global__ void __launch_bounds__(256) dw_repack_kernel(DwRepack l, const float*
     const unsigned sw = e >> 10, s = sw / nw, wv = sw % nw;
     const unsigned u = v >> 3, j = (v >> 1) & 3, t = v & 1, q = lane >> 4, c = lane & 15;
     const unsigned k = 32 * s + 16 * u + 4 * q + j, n = 32 * wv + 16 * t + c;
-    blob[l.w2_off + e] = raw[l.pw_raw + (size_t)n * l.C + k];
-    if (e < (unsigned)l.cout) blob[l.b2_off + e] = 0.f;
+    if (l.pw_gamma < 0) {
+        blob[l.w2_off + e] = raw[l.pw_raw + (size_t)n * l.C + k];
+        if (e < (unsigned)l.cout) blob[l.b2_off + e] = 0.f;
+        return;
+    }
+    const double scale = (double)raw[l.pw_gamma + n] / sqrt((double)raw[l.pw_var + n] + 1e-5);
+    blob[l.w2_off + e] = (float)((double)raw[l.pw_raw + (size_t)n * l.C + k] * scale);
+    if (e < (unsigned)l.cout) {
+        const double sc = (double)raw[l.pw_gamma + e] / sqrt((double)raw[l.pw_var + e] + 1e-5);
+        blob[l.b2_off + e] = (float)((0.0 - (double)raw[l.pw_mean + e]) * sc + (double)raw[l.pw_beta + e]);
+    }
 }
 
 hipError_t launch_dw_repack(const DwRepack& l, const float* raw, float* blob, hipStream_t s) {
     if (l.C < 1 || l.dw_raw < 0 || (l.cout > 0 && (l.pw_raw < 0 || l.C % 32 || l.cout % 32))) return hipErrorInvalidValue;
     const unsigned total = 9u * l.C + (unsigned)l.C * l.cout;
     hipLaunchKernelGGL(dw_repack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, l, raw, blob);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ repack, stem
+// model.0 (LWP_TRAIN_ALL): OIHW (32, 3, 3, 3) -> [(ky, kx, ci)][oc] with BatchNorm folded as above, and the bias row
+__global__ void __launch_bounds__(256) stem_repack_kernel(StemRepack l, const float* __restrict__ raw, float* __restrict__ blob) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;     // i = (t * 3 + ci) * 32 + o
+    if (i >= 27u * 32u + 32u) return;
+    const unsigned o = i & 31u;
+    const double scale = (double)raw[l.gamma + o] / sqrt((double)raw[l.var + o] + 1e-5);
+    if (i >= 27u * 32u) {
+        blob[l.b_off + o] = (float)((0.0 - (double)raw[l.mean + o]) * scale + (double)raw[l.beta + o]);
+        return;
+    }
+    const unsigned tc = i >> 5, t = tc / 3, ci = tc % 3;
+    blob[l.w_off + i] = (float)((double)raw[l.w_raw + (o * 3 + ci) * 9 + t] * scale);
+}
+
+hipError_t launch_stem_repack(const StemRepack& l, const float* raw, float* blob, hipStream_t s) {
+    if (l.w_raw < 0 || l.gamma < 0 || l.beta < 0 || l.mean < 0 || l.var < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stem_repack_kernel, dim3((27 * 32 + 32 + 255) / 256), dim3(256), 0, s, l, raw, blob);
     return hipGetLastError();
 }
 

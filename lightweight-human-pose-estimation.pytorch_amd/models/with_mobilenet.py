@@ -33,7 +33,8 @@ class PoseEstimationWithMobileNet(object):
     # ---- nn.Module-like surface used by the reference's callers (demo.py:82-84,156-158; val.py:114,174-178)
     def _sync_from_engine(self):
         """After an optimiser step (Engine.adam_step, however it was reached) the engine holds the current stage parameters
-        (and cpm parameters, where a train scope "cpm" has stepped, whatever the scope is now): copied back only when somebody asks."""
+        (and cpm / backbone parameters, where a train scope "cpm" / "all" has stepped, whatever the scope is now; the running
+        statistics stay as loaded): copied back only when somebody asks."""
         eng = self._engine
         if eng is not None and eng.stage_steps != self._seen_steps:
             for k, v in eng.trained_params().items():
@@ -65,7 +66,7 @@ class PoseEstimationWithMobileNet(object):
 
     def train(self, mode=True):
         if mode:
-            raise NotImplementedError("lwpose_amd has no training mode (no BatchNorm batch statistics): val.train_step / optim.StageAdam fine-tune the stages (and, in scope \"cpm\", the cpm) of the eval() network (frozen backbone, BatchNorm at running statistics)")
+            raise NotImplementedError("lwpose_amd has no training mode (no BatchNorm batch statistics): val.train_step / optim.StageAdam fine-tune the stages (in scope \"cpm\" the cpm too, in scope \"all\" the whole network) of the eval() network (BatchNorm at running statistics)")
         return self
 
     def cuda(self, device=None):

@@ -4,7 +4,9 @@
 ``refinement_stages.*`` parameter of a drop-in net (fp32): conv weights x1 (initial) / x4 (refinement) with weight decay, conv
 biases x2 / x8, refinement BatchNorm weights x1 and biases x2 without.  ``StageAdam(net, scope="cpm")`` also trains the cpm
 (train.py:46-48): its conv weights x1 with weight decay, its biases x2 and its depthwise weights x1 without; the engine's
-train scope is set on construction, ``val.train_step`` and the checkpoints below then cover the cpm.* keys too.  The update and the refold / repack of the changed
+train scope is set on construction, ``val.train_step`` and the checkpoints below then cover the cpm.* keys too.
+``StageAdam(net, scope="all")`` trains the backbone as well (train.py:42-45): stem and pointwise weights x1 with weight decay,
+depthwise and BatchNorm weights x1 and BatchNorm biases x2 without, which is every group of the reference's optimiser.  The update and the refold / repack of the changed
 layers into the forward's weight blob are HIP kernels behind ``lwp_stage_adam_step``: nothing travels through the host.
 
     opt = StageAdam(net, base_lr=4e-5, weight_decay=5e-4)
@@ -12,7 +14,7 @@ layers into the forward's weight blob are HIP kernels behind ``lwp_stage_adam_st
         losses = val.train_step(net, opt, images, labels, masks)
     opt.lr = opt.lr * 0.333            # MultiStepLR (train.py:60) is a line of Python
 
-Out of scope: the backbone (frozen: no backward, no update; so is the cpm in scope "stages"), BatchNorm train mode (running statistics never move), a
+Out of scope: BatchNorm train mode (running statistics never move), a
 16-bit optimiser, multi-GPU gradient reduction, amsgrad, and torch's optimiser checkpoints (``state_dict`` below has its own
 format, keyed by state-dict name; torch's is index-based and numbers the whole network).
 """

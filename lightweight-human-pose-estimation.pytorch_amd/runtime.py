@@ -25,7 +25,7 @@ class Engine(object):
         self.device_id = device_id
         self._keep = None
         self.stage_steps = 0                  # adam_step calls so far: the drop-in net reads its stage parameters back when this moves
-        self.train_scope = "stages"           # set_train_scope: "stages" | "cpm"
+        self.train_scope = "stages"           # set_train_scope: "stages" | "cpm" | "all"
         self._scope_steps = 0                 # stage_steps when the current scope was set
         self._left_params = {}                # parameters an earlier, wider scope trained and the current one does not cover
 
@@ -757,7 +757,7 @@ class Engine(object):
     # ------------------------------------------------------------------ stage backward (train.py:99-103, fp32 engines)
     def train_forward(self, x):
         """``forward`` for a float32 cuda tensor (N, 3, H, W) that also keeps what ``stage_backward`` needs: every stage
-        layer's output from cpm.conv on.  Returns the same list of stage outputs, bit for bit."""
+        layer's output from cpm.conv on (from the cpm's input on in train scope "cpm", from model.0 on in scope "all").  Returns the same list of stage outputs, bit for bit."""
         torch = _torch()
         x = self._as_device_input(x)
         N, _, H, W = (int(v) for v in x.shape)
@@ -773,7 +773,8 @@ class Engine(object):
     def set_train_scope(self, scope):
         """"stages" (the default): ``train_forward`` / ``stage_backward`` / ``adam_step`` cover initial_stage.* and
         refinement_stages.*; "cpm": the cpm (cpm.align, cpm.trunk, cpm.conv) as well, its ten parameters in front of the stage
-        ones in every flat array.  The backbone stays frozen.  Raises RuntimeError once the optimiser has taken a step
+        ones in every flat array, the backbone frozen; "all": the backbone model.* too (its 69 parameters in front of the cpm's;
+        BatchNorm at its running statistics, which never move).  Raises RuntimeError once the optimiser has taken a step
         (``load_adam_state(None)`` first, or set the scope before the first step).  The retained forward is invalidated.
         Parameters the old scope has trained and the new one does not cover stay readable through ``trained_params``."""
         name = _lib.train_scope_name(scope)
@@ -827,7 +828,7 @@ class Engine(object):
         earlier call (``Engine.flat_of(grads)``) to add to, like loss.backward() accumulates over train.py:96's batches.
         The refinement BatchNorms stay at their running statistics: the reference network in eval() mode.
         In train scope "cpm" the dict holds the cpm.* keys too, and ``want_backbone=True`` returns a third value: the gradient
-        at the cpm's input (N, 512, h, w)."""
+        at the cpm's input (N, 512, h, w).  Train scope "all" adds the model.* keys; there is no gradient at the image."""
         torch = _torch()
         total = self.grad_spec()[1]
         dev = torch.device("cuda", self.device_id)
@@ -881,8 +882,8 @@ class Engine(object):
 
     def train_activation(self, layer_index, which=_lib.KEPT_OUTPUT):
         """Retained output of a layer from the last ``train_forward`` as NCHW float32 numpy (tests): a stage layer or cpm.conv,
-        in train scope "cpm" also a cpm layer or the backbone's last layer.  ``which``: ``_lib.KEPT_DEPTHWISE`` for the retained
-        depthwise copy of a fused cpm trunk block (``cin`` channels), ``_lib.KEPT_NO_RESIDUAL`` for the block's output in
+        in train scope "cpm" also a cpm layer or the backbone's last layer, in scope "all" any layer.  ``which``: ``_lib.KEPT_DEPTHWISE`` for the retained
+        depthwise copy of a fused cpm trunk or backbone block (``cin`` channels), ``_lib.KEPT_NO_RESIDUAL`` for the block's output in
         front of its residual add."""
         info = self.layers()[layer_index]
         channels = info["cin"] if which == _lib.KEPT_DEPTHWISE else info["cout"]
@@ -899,6 +900,50 @@ class Engine(object):
         n = dims[0] * dims[1] * dims[2] * dims[3]
         assert dims[1] == channels
         return buf[:n].reshape(dims[0], dims[1], dims[2], dims[3]).copy()
+
+    def backbone_activations(self):
+        """Train scope "all": the retained backbone tensors of the last ``train_forward`` as NCHW float32 numpy, by the oracle's
+        tap names: "model.0", "model.i.dw" (a fused block's retained depthwise copy) and "model.i", i = 1..11 (tests)."""
+        by = dict((i["name"], i["index"]) for i in self.layers())
+        out = {"model.0": self.train_activation(by["model.0"])}
+        for i in range(1, 12):
+            pw = by["model.%d.pw" % i]
+            dw = by.get("model.%d.dw" % i)
+            out["model.%d.dw" % i] = self.train_activation(dw) if dw is not None else self.train_activation(pw, _lib.KEPT_DEPTHWISE)
+            out["model.%d" % i] = self.train_activation(pw)
+        return out
+
+    def debug_dw_grad(self, dz, x, w, stride, dil, max_chunk=0):
+        """The backbone's depthwise gradient kernels alone (tests): ``dz`` (N, C, Ho, Wo), ``x`` (N, C, H, W), ``w`` (C, 1, 3, 3)
+        float32 cuda tensors -> (dx (N, C, H, W), G (C, 1, 3, 3), g (C,), pixel ranges taken)."""
+        torch = _torch()
+        N, Cn, H, W = (int(v) for v in x.shape)
+        nhwc = lambda t: t.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        dzn, xn = nhwc(dz), nhwc(x)
+        wt = w.detach().to(torch.float32).reshape(Cn, 9).t().contiguous()
+        dx = torch.empty_like(xn)
+        G = torch.empty((Cn, 1, 3, 3), dtype=torch.float32, device=xn.device)
+        g = torch.empty(Cn, dtype=torch.float32, device=xn.device)
+        splits = C.c_int()
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_dw_grad_sd(self.h.ptr, dzn.data_ptr(), xn.data_ptr(), wt.data_ptr(), N, H, W, Cn, int(stride), int(dil), int(max_chunk),
+                                         dx.data_ptr(), G.data_ptr(), g.data_ptr(), C.byref(splits)), self.h.ptr)
+        return dx.permute(0, 3, 1, 2).contiguous(), G, g, splits.value
+
+    def debug_stem_wgrad(self, dz, x, max_chunk=0):
+        """The stem's weight gradient kernel alone (tests): ``dz`` (N, 32, Ho, Wo), ``x`` (N, 3, H, W) -> (G (32, 3, 3, 3), g (32,), ranges)."""
+        torch = _torch()
+        N, _, H, W = (int(v) for v in x.shape)
+        dzn = dz.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        xc = x.detach().to(torch.float32).contiguous()
+        G = torch.empty((32, 3, 3, 3), dtype=torch.float32, device=xc.device)
+        g = torch.empty(32, dtype=torch.float32, device=xc.device)
+        splits = C.c_int()
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_stem_wgrad(self.h.ptr, dzn.data_ptr(), xc.data_ptr(), N, H, W, int(max_chunk), G.data_ptr(), g.data_ptr(), C.byref(splits)), self.h.ptr)
+        return G, g, splits.value
 
     def backward_splits(self, layer_index, depthwise=False):
         """Pixel ranges the last ``stage_backward`` split this layer's weight gradient into (0: none ran); ``depthwise``: those
@@ -942,7 +987,7 @@ class Engine(object):
 
     def trained_params(self):
         """``stage_params`` plus what an earlier, wider train scope trained and the current one no longer covers (the cpm.*
-        parameters after "cpm" -> "stages"): every parameter whose value on the device may differ from what was loaded."""
+        parameters after "cpm" -> "stages", the model.* ones after "all" -> "cpm"): every parameter whose value on the device may differ from what was loaded."""
         out = dict(self._left_params)
         out.update(self.stage_params())
         return out

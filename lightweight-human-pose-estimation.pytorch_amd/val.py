@@ -121,8 +121,8 @@ def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thic
     stage backward on the GPU in one call.  Returns (losses, grads, d_features): the 2 * (nref + 1) floats of ``stage_losses``,
     the dict state-dict key -> gradient of every initial_stage.* / refinement_stages.* parameter, and the gradient at the
     cpm output (N, num_channels, h, w).  ``loss_scale`` scales the gradients only (train.py:102's 1 / batches_per_iter);
-    ``into``: the flat array of an earlier call to add to.  The backbone is frozen (the cpm too unless the engine's train scope
-    is "cpm": ``grads`` then holds the cpm.* keys as well) and the BatchNorms stay at their
+    ``into``: the flat array of an earlier call to add to.  The backbone is frozen (the cpm too) unless the engine's train scope
+    is "cpm" (``grads`` then holds the cpm.* keys as well) or "all" (the model.* keys too), and the BatchNorms stay at their
     running statistics: this is loss.backward() of the reference network in eval() mode.  ``train_step`` adds the optimiser."""
     import torch
     from .datasets.coco import generate_targets
@@ -144,7 +144,8 @@ def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=
     """One pass of train.py:85-110's loop body for one loader batch, all on the GPU: targets, retaining forward, stage losses,
     stage backward with loss_scale = 1 / batches_per_iter, and, once ``batches_per_iter`` calls have added their gradients,
     ``opt.step`` (an ``optim.StageAdam`` of this net; it is zeroed at the first batch of an iteration, train.py:87-88).
-    Returns the batch's stage losses as ``stage_losses`` does.  Only initial_stage.* / refinement_stages.* move, and cpm.* with ``optim.StageAdam(net, scope="cpm")``."""
+    Returns the batch's stage losses as ``stage_losses`` does.  Only initial_stage.* / refinement_stages.* move, and cpm.* with ``optim.StageAdam(net, scope="cpm")``,
+    every parameter with ``scope="all"``."""
     if opt.net is not net:
         raise ValueError("opt is not an optimiser of this net")
     batches_per_iter = int(batches_per_iter)

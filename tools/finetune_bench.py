@@ -7,10 +7,11 @@
   * the loss over 50 steps on one batch of labelled synthetic frames (synthetic weights: the curve shows the loop closing, not a
     trained model).
 
-    python tools/finetune_bench.py [--batch 80] [--size 368] [--iters 50] [--steps 50] [--scope stages|cpm] [--out profiles/train/finetune_bench.json]
+    python tools/finetune_bench.py [--batch 80] [--size 368] [--iters 50] [--steps 50] [--scope stages|cpm|all] [--out profiles/train/finetune_bench.json]
 
 --scope cpm runs every leg with the cpm trained too (optim.StageAdam(net, scope="cpm")) into profiles/train/finetune_bench_cpm.json;
-the repack's byte count then leaves the cpm layers out, so no share of the HBM figure is given for it.
+the repack's byte count then leaves the cpm layers out, so no share of the HBM figure is given for it.  --scope all trains the
+backbone as well (profiles/train/finetune_bench_all.json).
 
 Writes one JSON file; the feature has no earlier form, so nothing is compared against a parent."""
 import argparse
@@ -32,7 +33,7 @@ from lwpose_amd.models.with_mobilenet import PoseEstimationWithMobileNet  # noqa
 from lwpose_amd.modules.load_state import load_state  # noqa: E402
 from lwpose_amd.runtime import Engine  # noqa: E402
 
-import cpm_backward_cases as cc  # noqa: E402
+import backbone_backward_cases as bb  # noqa: E402
 import train_cases as tc  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
@@ -119,7 +120,7 @@ def full_step(batch, size, reps, scope):
     params = {k: torch.nn.Parameter(sd[k].clone()) for k, _, _ in spec}
     groups = []
     for k, _, _ in spec:
-        mult, wd = cc.group_of(k)
+        mult, wd = bb.group_of(k)
         groups.append({"params": [params[k]], "lr": opt.lr * mult, "weight_decay": opt.weight_decay if wd else 0})
     topt = torch.optim.Adam(groups, lr=opt.lr)
     host = dict(sd)
@@ -157,11 +158,11 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--scope", choices=("stages", "cpm"), default="stages")
+    ap.add_argument("--scope", choices=("stages", "cpm", "all"), default="stages")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "train", "finetune_bench_cpm.json" if a.scope == "cpm" else "finetune_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "train", "finetune_bench.json" if a.scope == "stages" else "finetune_bench_%s.json" % a.scope)
     out = dict(device=torch.cuda.get_device_properties(0).gcnArchName,
                kernels=[kernels(n, a.iters, a.scope) for n in (1, 3)],
                full_step=full_step(a.batch, a.size, a.reps, a.scope),
