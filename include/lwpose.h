@@ -502,6 +502,39 @@ int lwp_debug_backward_dw_splits(lwp_handle h, int layer_index);
 int lwp_debug_dw_grad_sd(lwp_handle h, const float* dz, const float* x, const float* w, int N, int H, int W, int C, int stride, int dil,
                          int max_chunk, float* dx, float* G, float* g, int* splits);
 int lwp_debug_stem_wgrad(lwp_handle h, const float* dz, const float* x, int N, int H, int W, int max_chunk, float* G, float* g, int* splits);
+/* tests: the stage and cpm gradient kernels alone, on the handle's stream, synchronous.  All arrays DEVICE float32 unless said
+ * otherwise.  A call that breaks a rule below returns LWP_ERR_ARG and launches nothing.
+ * lwp_debug_conv_grad: a dense conv (ks 1 | 3, dil 1 | 2, padding = dil * (ks / 2), stride 1): weight gradient, its fixed-order
+ *   reduction and data gradient.  dz (N H W rows of cout channels) and x (rows of cin channels) are NHWC windows: pointer, row
+ *   stride and channel offset, offset + channels <= row stride.  w is the raw OIHW weight (cout, cin, ks, ks); the call packs it
+ *   to the data gradient's [taps][cout_pad][cin_pad], zero-filled: LWP_PAD_GRAPH pads cout to a multiple of 64 and cin to a
+ *   multiple of 32 (the fp32 blob's form), LWP_PAD_RAW leaves both (a fused block's folded matrix) and needs cout a multiple
+ *   of 16 and cin a multiple of 4.  max_chunk > 0 caps the pixels of a range (a multiple of 16).  Channels >= acc_from (0..cin) of
+ *   the dx window are added to, the others overwritten.  no_bias: db is not touched.  accumulate: dw (OIHW) and db are added to.
+ *   *splits: pixel ranges taken.  Test sizes only: N H W < 2^24, cout and cin <= 4096.
+ * lwp_debug_dw_grad: the cpm's depthwise 3x3 (stride 1, dilation 1, pad 1).  dz, x and dx are N H W rows of C channels at row strides
+ *   that are multiples of 4, 16-byte aligned; w [9][C]; dw (C, 1, 3, 3).  beta: dx is added to.  accumulate: dw is added to.
+ * lwp_debug_loss_grad: dst[s] = scale (outs[s] - target) mask^2 for S <= 16 NHWC windows of one row stride ld (outs and dst are
+ *   HOST arrays of device pointers; even s: CH channels against keypoint_maps, odd s: CP against paf_maps, both NCHW; mask N x hw).
+ * lwp_debug_relu_mask: g = y > res ? g : 0 over M rows of C channels (res NULL: y > 0).  lwp_debug_grad_add: dst = (beta ? dst : 0)
+ *   + src.  lwp_debug_elu_grad: g *= y > 0 ? 1 : y + 1 (C and the row strides multiples of 4, pointers 16-byte aligned).
+ * lwp_debug_pw_fold: out[o][ci] = float(double(w[o][ci]) * (gamma[o] / sqrt(double(var[o]) + 1e-5))).
+ * lwp_debug_bn_chain: gradients G (cout, K) and g (cout) of a folded conv -> dW, db (NULL: none), dgamma, dbeta of the raw
+ *   parameters; accumulate: all four are added to. */
+enum { LWP_PAD_GRAPH = 0, LWP_PAD_RAW = 1 };
+int lwp_debug_conv_grad(lwp_handle h, const float* dz, int dz_ld, int dz_off, const float* x, int x_ld, int x_off, const float* w, int N,
+                        int H, int W, int cout, int cin, int ks, int dil, int pad_mode, int max_chunk, int acc_from, int no_bias,
+                        int accumulate, float* dx, int dx_ld, int dx_off, float* dw, float* db, int* splits);
+int lwp_debug_dw_grad(lwp_handle h, const float* dz, int dz_ld, const float* x, int x_ld, const float* w, int N, int H, int W, int C, int beta,
+                      int accumulate, int max_chunk, float* dx, int dx_ld, float* dw, int* splits);
+int lwp_debug_loss_grad(lwp_handle h, const float* const* outs, float* const* dst, int S, int ld, const float* keypoint_maps,
+                        const float* paf_maps, const float* mask, int N, int CH, int CP, int hw, float scale);
+int lwp_debug_relu_mask(lwp_handle h, float* g, int g_ld, const float* y, int y_ld, const float* res, int res_ld, int64_t M, int C);
+int lwp_debug_grad_add(lwp_handle h, float* dst, int dst_ld, const float* src, int src_ld, int64_t M, int C, int beta);
+int lwp_debug_elu_grad(lwp_handle h, float* g, int g_ld, const float* y, int y_ld, int64_t M, int C);
+int lwp_debug_pw_fold(lwp_handle h, const float* w, const float* gamma, const float* var, float* out, int cout, int cin);
+int lwp_debug_bn_chain(lwp_handle h, const float* G, const float* g, const float* W, const float* b, const float* gamma, const float* mean,
+                       const float* var, float* dW, float* db, float* dgamma, float* dbeta, int cout, int K, int accumulate);
 int lwp_set_train_scope(lwp_handle h, int scope);
 int lwp_train_grad_count(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int64_t* total_floats);
 int lwp_train_grad_spec(int scope, int num_refinement_stages, int num_channels, int num_heatmaps, int num_pafs, int index, char* name,

@@ -12,6 +12,8 @@ F32, BF16, F16 = 0, 1, 2
 TRAIN_STAGES, TRAIN_CPM, TRAIN_ALL = 0, 1, 2
 TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM, "all": TRAIN_ALL}
 KEPT_OUTPUT, KEPT_DEPTHWISE, KEPT_NO_RESIDUAL = 0, 1, 2
+PAD_GRAPH, PAD_RAW = 0, 1
+PAD_MODES = {"graph": PAD_GRAPH, "raw": PAD_RAW}
 
 EXPORTS = [
     "lwp_version", "lwp_param_count", "lwp_param_spec", "lwp_create", "lwp_destroy", "lwp_last_error",
@@ -33,6 +35,8 @@ EXPORTS = [
     "lwp_stage_adam_reset", "lwp_time_stage_adam_step",
     "lwp_set_train_scope", "lwp_train_grad_count", "lwp_train_grad_spec", "lwp_train_adam_group", "lwp_train_backward",
     "lwp_debug_train_copy", "lwp_debug_backward_dw_splits", "lwp_debug_dw_grad_sd", "lwp_debug_stem_wgrad",
+    "lwp_debug_conv_grad", "lwp_debug_dw_grad", "lwp_debug_loss_grad", "lwp_debug_relu_mask", "lwp_debug_grad_add", "lwp_debug_elu_grad",
+    "lwp_debug_pw_fold", "lwp_debug_bn_chain",
 ]
 
 
@@ -140,6 +144,14 @@ def lib():
     L.lwp_debug_backward_dw_splits.argtypes = [vp, C.c_int]
     L.lwp_debug_dw_grad_sd.argtypes = [vp, vp, vp, vp] + [C.c_int] * 7 + [vp, vp, vp, ip]
     L.lwp_debug_stem_wgrad.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, vp, ip]
+    L.lwp_debug_conv_grad.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp] + [C.c_int] * 12 + [vp, C.c_int, C.c_int, vp, vp, ip]
+    L.lwp_debug_dw_grad.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp] + [C.c_int] * 7 + [vp, C.c_int, vp, ip]
+    L.lwp_debug_loss_grad.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, vp, vp, vp] + [C.c_int] * 4 + [C.c_float]
+    L.lwp_debug_relu_mask.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int]
+    L.lwp_debug_grad_add.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int]
+    L.lwp_debug_elu_grad.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int]
+    L.lwp_debug_pw_fold.argtypes = [vp] * 5 + [C.c_int] * 2
+    L.lwp_debug_bn_chain.argtypes = [vp] * 12 + [C.c_int] * 3
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -2987,6 +2987,153 @@ extern "C" int lwp_debug_stem_wgrad(lwp_handle h, const float* dz, const float* 
     return LWP_OK;
 }
 
+// the stage and cpm gradient kernels alone (tests).  The argument rules of the launchers are checked here first, so that a
+// refused call is LWP_ERR_ARG and nothing is launched.
+static bool window_ok(const void* p, int ld, int off, int C) { return p && off >= 0 && C >= 1 && (int64_t)off + C <= ld; }
+
+extern "C" int lwp_debug_conv_grad(lwp_handle h, const float* dz, int dz_ld, int dz_off, const float* x, int x_ld, int x_off, const float* w,
+                                   int N, int H, int W, int cout, int cin, int ks, int dil, int pad_mode, int max_chunk, int acc_from,
+                                   int no_bias, int accumulate, float* dx, int dx_ld, int dx_off, float* dw, float* db, int* splits) {
+    if (!h || !w || !dw || !db || !splits) return fail(h, LWP_ERR_ARG, "null argument");
+    if (N < 1 || H < 1 || W < 1 || cout < 1 || cin < 1 || cout > 4096 || cin > 4096 || (int64_t)N * H * W >= (1ll << 24))
+        return fail(h, LWP_ERR_ARG, "bad shape");
+    if ((ks != 1 && ks != 3) || (dil != 1 && dil != 2)) return fail(h, LWP_ERR_ARG, "ks is 1 or 3, dil 1 or 2");
+    if (max_chunk < 0 || (max_chunk & 15)) return fail(h, LWP_ERR_ARG, "max_chunk is a multiple of 16");
+    if (pad_mode != LWP_PAD_GRAPH && pad_mode != LWP_PAD_RAW) return fail(h, LWP_ERR_ARG, "unknown pad mode");
+    if (pad_mode == LWP_PAD_RAW && ((cout & 15) || (cin & 3))) return fail(h, LWP_ERR_ARG, "raw weights need cout a multiple of 16 and cin a multiple of 4");
+    if (acc_from < 0 || acc_from > cin) return fail(h, LWP_ERR_ARG, "acc_from is in 0..cin");
+    if (!window_ok(dz, dz_ld, dz_off, cout) || !window_ok(x, x_ld, x_off, cin) || !window_ok(dx, dx_ld, dx_off, cin))
+        return fail(h, LWP_ERR_ARG, "a window does not fit its row stride");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int taps = ks * ks;
+    const int cout_pad = pad_mode == LWP_PAD_RAW ? cout : (cout + 63) / 64 * 64;
+    const int cin_pad = pad_mode == LWP_PAD_RAW ? cin : (cin + 31) / 32 * 32;
+    // OIHW -> [taps][cout_pad][cin_pad], zero-filled
+    std::vector<float> raw((size_t)cout * cin * taps), packed((size_t)taps * cout_pad * cin_pad, 0.0f);
+    HIP_TRY(h, hipMemcpy(raw.data(), w, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int o = 0; o < cout; ++o)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < taps; ++t) packed[((size_t)t * cout_pad + o) * cin_pad + ci] = raw[((size_t)o * cin + ci) * taps + t];
+    DevBuf wbuf, part;
+    HIP_TRY(h, wbuf.ensure(packed.size() * sizeof(float)));
+    HIP_TRY(h, hipMemcpy(wbuf.as<float>(), packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+    WgradParams p{};
+    p.dz = dz + dz_off; p.dz_ld = dz_ld; p.x = x + x_off; p.x_ld = x_ld;
+    p.N = N; p.H = H; p.W = W; p.cout = cout; p.cin = cin; p.ks = ks; p.dil = dil; p.no_bias = no_bias ? 1 : 0;
+    const int64_t M = (int64_t)N * H * W;
+    wgrad_plan(M, cout, cin, ks, &p.splits, &p.chunk);
+    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    if (p.splits > 65535) return fail(h, LWP_ERR_ARG, "too many pixel ranges");
+    HIP_TRY(h, part.ensure(wgrad_partial_floats(p) * sizeof(float)));
+    p.partial = part.as<float>();
+    DgradParams d{};
+    d.dz = p.dz; d.dz_ld = dz_ld; d.w = wbuf.as<float>(); d.dx = dx + dx_off; d.dx_ld = dx_ld;
+    d.N = N; d.H = H; d.W = W; d.cout = cout; d.cout_pad = cout_pad; d.cin = cin; d.cin_pad = cin_pad; d.ks = ks; d.dil = dil; d.acc_from = acc_from;
+    HIP_TRY(h, launch_wgrad(p, h->stream));
+    HIP_TRY(h, launch_wgrad_reduce(p, dw, db, accumulate ? 1 : 0, h->stream));
+    HIP_TRY(h, launch_dgrad(d, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *splits = p.splits;
+    return LWP_OK;
+}
+
+static bool quad_window_ok(const void* p, int ld, int C) { return p && ((uintptr_t)p & 15) == 0 && ld >= C && (ld & 3) == 0; }
+
+extern "C" int lwp_debug_dw_grad(lwp_handle h, const float* dz, int dz_ld, const float* x, int x_ld, const float* w, int N, int H, int W, int C,
+                                 int beta, int accumulate, int max_chunk, float* dx, int dx_ld, float* dw, int* splits) {
+    if (!h || !w || !dw || !splits) return fail(h, LWP_ERR_ARG, "null argument");
+    if (N < 1 || H < 1 || W < 1 || C < 4 || (C & 3) || (int64_t)N * H * W >= (1ll << 24) || max_chunk < 0 || (max_chunk & 15))
+        return fail(h, LWP_ERR_ARG, "bad shape (C a multiple of 4, max_chunk a multiple of 16)");
+    if (!quad_window_ok(dz, dz_ld, C) || !quad_window_ok(x, x_ld, C) || !quad_window_ok(dx, dx_ld, C) || ((uintptr_t)w & 15))
+        return fail(h, LWP_ERR_ARG, "row strides are multiples of 4 and at least C, pointers 16-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    DwGradParams p{};
+    p.dz = dz; p.dz_ld = dz_ld; p.x = x; p.x_ld = x_ld; p.w = w; p.dx = dx; p.dx_ld = dx_ld;
+    p.N = N; p.H = H; p.W = W; p.C = C; p.beta = beta ? 1 : 0;
+    const int64_t M = (int64_t)N * H * W;
+    dw_wgrad_plan(M, C, &p.splits, &p.chunk);
+    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    if (p.splits > 65535) return fail(h, LWP_ERR_ARG, "too many pixel ranges");
+    DevBuf part;
+    HIP_TRY(h, part.ensure((size_t)p.splits * 9 * C * sizeof(float)));
+    p.partial = part.as<float>();
+    HIP_TRY(h, launch_dw_wgrad(p, h->stream));
+    HIP_TRY(h, launch_dw_wgrad_reduce(p, dw, accumulate ? 1 : 0, h->stream));
+    HIP_TRY(h, launch_dw_dgrad(p, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *splits = p.splits;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_loss_grad(lwp_handle h, const float* const* outs, float* const* dst, int S, int ld, const float* keypoint_maps,
+                                   const float* paf_maps, const float* mask, int N, int CH, int CP, int hw, float scale) {
+    if (!h || !outs || !dst || !keypoint_maps || !paf_maps || !mask) return fail(h, LWP_ERR_ARG, "null argument");
+    if (S < 1 || S > kLossMaxOuts || N < 1 || CH < 1 || CP < 1 || hw < 1 || ld < std::max(CH, CP) || (int64_t)N * hw * ld >= (1ll << 31))
+        return fail(h, LWP_ERR_ARG, "bad shape");
+    LossGradParams p{};
+    for (int s = 0; s < S; ++s) {
+        if (!outs[s] || !dst[s]) return fail(h, LWP_ERR_ARG, "null argument");
+        p.outs[s] = outs[s]; p.dst[s] = dst[s];
+    }
+    p.S = S; p.ld = ld; p.keypoint_maps = keypoint_maps; p.paf_maps = paf_maps; p.mask = mask;
+    p.N = N; p.CH = CH; p.CP = CP; p.hw = hw; p.scale = scale;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_loss_grad(p, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+static bool rows_ok(int64_t M, int C, int ld) { return M >= 1 && C >= 1 && ld >= C && M * ld < (1ll << 32); }
+
+extern "C" int lwp_debug_relu_mask(lwp_handle h, float* g, int g_ld, const float* y, int y_ld, const float* res, int res_ld, int64_t M, int C) {
+    if (!h || !g || !y) return fail(h, LWP_ERR_ARG, "null argument");
+    if (!rows_ok(M, C, g_ld) || !rows_ok(M, C, y_ld) || (res && !rows_ok(M, C, res_ld))) return fail(h, LWP_ERR_ARG, "bad shape");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_relu_mask(g, g_ld, y, y_ld, res, res_ld, M, C, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_grad_add(lwp_handle h, float* dst, int dst_ld, const float* src, int src_ld, int64_t M, int C, int beta) {
+    if (!h || !dst || !src) return fail(h, LWP_ERR_ARG, "null argument");
+    if (!rows_ok(M, C, dst_ld) || !rows_ok(M, C, src_ld)) return fail(h, LWP_ERR_ARG, "bad shape");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_grad_add(dst, dst_ld, src, src_ld, M, C, beta ? 1 : 0, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_elu_grad(lwp_handle h, float* g, int g_ld, const float* y, int y_ld, int64_t M, int C) {
+    if (!h) return fail(h, LWP_ERR_ARG, "null argument");
+    if (C < 4 || (C & 3) || !rows_ok(M, C, g_ld) || !rows_ok(M, C, y_ld) || !quad_window_ok(g, g_ld, C) || !quad_window_ok(y, y_ld, C))
+        return fail(h, LWP_ERR_ARG, "bad shape (C and the row strides multiples of 4, pointers 16-byte aligned)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_elu_grad(g, g_ld, y, y_ld, M, C, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_pw_fold(lwp_handle h, const float* w, const float* gamma, const float* var, float* out, int cout, int cin) {
+    if (!h || !w || !gamma || !var || !out || cout < 1 || cin < 1) return fail(h, LWP_ERR_ARG, "bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_pw_fold(w, gamma, var, out, cout, cin, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_bn_chain(lwp_handle h, const float* G, const float* g, const float* W, const float* b, const float* gamma,
+                                  const float* mean, const float* var, float* dW, float* db, float* dgamma, float* dbeta, int cout, int K,
+                                  int accumulate) {
+    if (!h || !G || !g || !W || !b || !gamma || !mean || !var || !dW || !dgamma || !dbeta || cout < 1 || K < 1) return fail(h, LWP_ERR_ARG, "bad argument");
+    BnChainParams p{};
+    p.G = G; p.g = g; p.W = W; p.b = b; p.gamma = gamma; p.mean = mean; p.var = var;
+    p.dW = dW; p.db = db; p.dgamma = dgamma; p.dbeta = dbeta; p.cout = cout; p.K = K; p.accumulate = accumulate ? 1 : 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_bn_chain(p, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- stage fine-tuning step
 // train.py:41-55's parameter groups for the stage parameters: log2 of the learning-rate multiplier in bits 0-1, weight decay in bit 2
 static uint32_t stage_adam_group(const std::string& key, int role) {

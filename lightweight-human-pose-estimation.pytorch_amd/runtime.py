@@ -945,6 +945,133 @@ class Engine(object):
         check(lib().lwp_debug_stem_wgrad(self.h.ptr, dzn.data_ptr(), xc.data_ptr(), N, H, W, int(max_chunk), G.data_ptr(), g.data_ptr(), C.byref(splits)), self.h.ptr)
         return G, g, splits.value
 
+    # ------------------------------------------------------------------ the stage and cpm gradient kernels alone (tests)
+    # NCHW float32 cuda tensors in and out; the kernels see NHWC rows.  `fill` is what the rows hold outside the tensor's window
+    # (padding channels, GUARD_ROWS rows behind the last pixel); the rows come back whole so that a test can look there.
+    GUARD_ROWS = 3
+
+    @staticmethod
+    def _rows(t, ld=None, off=0, fill=0.0, guard=0):
+        torch = _torch()
+        N, Cn, H, W = (int(v) for v in t.shape)
+        rows = torch.full((N * H * W + guard, Cn if ld is None else int(ld)), float(fill), dtype=torch.float32, device=t.device)
+        rows[:N * H * W, off:off + Cn] = t.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(N * H * W, Cn)
+        return rows
+
+    @staticmethod
+    def _nchw(rows, shape, off=0):
+        N, Cn, H, W = (int(v) for v in shape)
+        return rows[:N * H * W, off:off + Cn].reshape(N, H, W, Cn).permute(0, 3, 1, 2).contiguous()
+
+    def debug_conv_grad(self, dz, x, w, dil=1, pad="graph", max_chunk=0, acc_from=None, no_bias=False, accumulate=False,
+                        dx0=None, dw0=None, db0=None, windows=None, fill=0.0):
+        """dgrad, wgrad and its reduction of a dense conv alone: ``dz`` (N, cout, H, W), ``x`` (N, cin, H, W), ``w`` (cout, cin, ks,
+        ks); ``dx0`` / ``dw0`` / ``db0`` are what dx / dw / db hold before the call (default zeros); ``acc_from`` defaults to cin
+        (overwrite); ``windows`` = ((dz_ld, dz_off), (x_ld, x_off), (dx_ld, dx_off)) puts the three tensors in wider rows.
+        -> (dx (N, cin, H, W), dw, db, pixel ranges taken, the dx rows whole)."""
+        torch = _torch()
+        N, cin, H, W = (int(v) for v in x.shape)
+        cout, ks = int(w.shape[0]), int(w.shape[2])
+        (zl, zo), (xl, xo), (dl, do) = windows if windows is not None else ((cout, 0), (cin, 0), (cin, 0))
+        dzr, xr = self._rows(dz, zl, zo, fill), self._rows(x, xl, xo, fill)
+        dxr = self._rows(dx0 if dx0 is not None else torch.zeros_like(x), dl, do, fill, self.GUARD_ROWS)
+        wc = w.detach().to(torch.float32).contiguous()
+        dw = (dw0 if dw0 is not None else torch.zeros_like(wc)).detach().to(torch.float32).clone().contiguous()
+        db = (db0 if db0 is not None else torch.zeros(cout, device=x.device)).detach().to(torch.float32).clone().contiguous()
+        splits = C.c_int()
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_conv_grad(self.h.ptr, dzr.data_ptr(), int(zl), int(zo), xr.data_ptr(), int(xl), int(xo), wc.data_ptr(), N, H, W, cout, cin,
+                                        ks, int(dil), _lib.PAD_MODES[pad], int(max_chunk), cin if acc_from is None else int(acc_from),
+                                        int(bool(no_bias)), int(bool(accumulate)), dxr.data_ptr(), int(dl), int(do), dw.data_ptr(), db.data_ptr(),
+                                        C.byref(splits)), self.h.ptr)
+        return self._nchw(dxr, x.shape, do), dw, db, splits.value, dxr
+
+    def debug_cpm_dw_grad(self, dz, x, w, beta=False, accumulate=False, max_chunk=0, dx0=None, dw0=None, ld=None, fill=0.0):
+        """The cpm's depthwise gradient kernels alone (stride 1, dilation 1): ``dz``, ``x`` (N, C, H, W), ``w`` (C, 1, 3, 3); ``ld``: the
+        row stride of all three windows (default C).  -> (dx, dw (C, 1, 3, 3), pixel ranges taken, the dx rows whole)."""
+        torch = _torch()
+        N, Cn, H, W = (int(v) for v in x.shape)
+        ld = Cn if ld is None else int(ld)
+        dzr, xr = self._rows(dz, ld, 0, fill), self._rows(x, ld, 0, fill)
+        dxr = self._rows(dx0 if dx0 is not None else torch.zeros_like(x), ld, 0, fill, self.GUARD_ROWS)
+        wt = w.detach().to(torch.float32).reshape(Cn, 9).t().contiguous()
+        dw = (dw0 if dw0 is not None else torch.zeros((Cn, 1, 3, 3), device=x.device)).detach().to(torch.float32).clone().contiguous()
+        splits = C.c_int()
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_dw_grad(self.h.ptr, dzr.data_ptr(), ld, xr.data_ptr(), ld, wt.data_ptr(), N, H, W, Cn, int(bool(beta)),
+                                      int(bool(accumulate)), int(max_chunk), dxr.data_ptr(), ld, dw.data_ptr(), C.byref(splits)), self.h.ptr)
+        return self._nchw(dxr, x.shape), dw, splits.value, dxr
+
+    def debug_loss_grad(self, outs, keypoint_maps, paf_maps, mask, scale, ld=None, off=0, fill=0.0):
+        """``loss_grad_kernel`` alone: ``outs`` alternate (N, CH, h, w) and (N, CP, h, w) tensors, ``mask`` (N, h, w), ``scale`` the
+        float32 factor loss_scale / batch.  -> ([gradient like outs[s]], [its rows whole])."""
+        torch = _torch()
+        N, CH, hh, ww = (int(v) for v in keypoint_maps.shape)
+        CP = int(paf_maps.shape[1])
+        ld = off + max(CH, CP) if ld is None else int(ld)
+        S = len(outs)
+        src = [self._rows(o, ld, off, fill) for o in outs]
+        dst = [self._rows(torch.zeros_like(o), ld, off, fill, self.GUARD_ROWS) for o in outs]
+        vp = C.c_void_p
+        a = (vp * S)(*[t.data_ptr() + 4 * off for t in src])
+        b = (vp * S)(*[t.data_ptr() + 4 * off for t in dst])
+        km, pm, mk = (t.detach().to(torch.float32).contiguous() for t in (keypoint_maps, paf_maps, mask))
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_loss_grad(self.h.ptr, a, b, S, ld, km.data_ptr(), pm.data_ptr(), mk.data_ptr(), N, CH, CP, hh * ww, float(scale)), self.h.ptr)
+        return [self._nchw(d, o.shape, off) for d, o in zip(dst, outs)], dst
+
+    def _debug_rows_op(self, call, g, others, ld, fill):
+        torch = _torch()
+        N, Cn, H, W = (int(v) for v in g.shape)
+        ld = Cn if ld is None else int(ld)
+        gr = self._rows(g, ld, 0, fill, self.GUARD_ROWS)
+        rs = [self._rows(o, ld, 0, fill) if o is not None else None for o in others]
+        self._order()
+        torch.cuda.synchronize()
+        check(call(gr, rs, ld, N * H * W, Cn), self.h.ptr)
+        return self._nchw(gr, g.shape), gr
+
+    def debug_relu_mask(self, g, y, res=None, ld=None, fill=0.0):
+        """g where y > res (``res`` None: y > 0), else 0; all (N, C, H, W).  -> (result, its rows whole)."""
+        return self._debug_rows_op(lambda gr, rs, ld, M, Cn: lib().lwp_debug_relu_mask(
+            self.h.ptr, gr.data_ptr(), ld, rs[0].data_ptr(), ld, rs[1].data_ptr() if rs[1] is not None else None, ld, M, Cn), g, [y, res], ld, fill)
+
+    def debug_grad_add(self, dst, src, beta, ld=None, fill=0.0):
+        """(beta ? dst : 0) + src.  -> (result, its rows whole)."""
+        return self._debug_rows_op(lambda gr, rs, ld, M, Cn: lib().lwp_debug_grad_add(
+            self.h.ptr, gr.data_ptr(), ld, rs[0].data_ptr(), ld, M, Cn, int(bool(beta))), dst, [src], ld, fill)
+
+    def debug_elu_grad(self, g, y, ld=None, fill=0.0):
+        """g * (y > 0 ? 1 : y + 1), y the ELU's output.  -> (result, its rows whole)."""
+        return self._debug_rows_op(lambda gr, rs, ld, M, Cn: lib().lwp_debug_elu_grad(
+            self.h.ptr, gr.data_ptr(), ld, rs[0].data_ptr(), ld, M, Cn), g, [y], ld, fill)
+
+    def debug_pw_fold(self, w, gamma, var):
+        """``pw_fold_kernel`` alone: ``w`` (cout, cin), ``gamma`` and ``var`` (cout,) -> the folded (cout, cin) matrix."""
+        torch = _torch()
+        w, gamma, var = (t.detach().to(torch.float32).contiguous() for t in (w, gamma, var))
+        out = torch.empty_like(w)
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_pw_fold(self.h.ptr, w.data_ptr(), gamma.data_ptr(), var.data_ptr(), out.data_ptr(), int(w.shape[0]), int(w.shape[1])), self.h.ptr)
+        return out
+
+    def debug_bn_chain(self, G, g, W, b, gamma, mean, var, into, accumulate=False):
+        """``bn_chain_kernel`` alone: ``G`` and ``W`` (cout, K), the others (cout,); ``into`` = (dW, db or None, dgamma, dbeta), contiguous
+        float32 cuda arrays written in place (they may be views into wider arrays)."""
+        torch = _torch()
+        ins = [t.detach().to(torch.float32).contiguous() for t in (G, g, W, b, gamma, mean, var)]
+        for t in into:
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("outputs must be contiguous float32 cuda arrays")
+        self._order()
+        torch.cuda.synchronize()
+        check(lib().lwp_debug_bn_chain(self.h.ptr, *([t.data_ptr() for t in ins] + [t.data_ptr() if t is not None else None for t in into]
+                                                    + [int(ins[0].shape[0]), int(ins[0].shape[1]), int(bool(accumulate))])), self.h.ptr)
+
     def backward_splits(self, layer_index, depthwise=False):
         """Pixel ranges the last ``stage_backward`` split this layer's weight gradient into (0: none ran); ``depthwise``: those
         of the layer's depthwise weight gradient (a depthwise layer or a fused block of the cpm trunk, train scope "cpm")."""
