@@ -23,6 +23,11 @@ CASES = {
     "b": dict(N=3, H=40, W=56, C=32, nref=2, skel="guide5", seed=12, frames=310, people=6),
     "c": dict(N=1, H=368, W=368, C=128, nref=1, skel="coco", seed=13, frames=320, people=7),
     "d": dict(N=1, H=32, W=40, C=32, nref=0, skel="coco", seed=14, frames=330, people=8),
+    # 8 refinement stages: 18 stage tensors, so the loss and its gradient take a second launch (16 tensors to a launch).  Its
+    # layers have 1920 elements or fewer, so MASK_FRACTION allows not one element off the float64 branch.  Of the two weight
+    # seeds tried on the CPU (31, 32: no deviation with either), 32 keeps every pre-activation further from zero: the
+    # smallest |z64| / max|z64| of any layer is 4.4e-7 against 4.0e-8, which is below float32's resolution.
+    "n8": dict(N=2, H=40, W=48, C=32, nref=8, skel="guide5", seed=32, frames=500, people=21),
 }
 MASK_FRACTION = 1e-4      # of a layer's elements may take another branch than the float64 forward ...
 MASK_MARGIN = 1e-4        # ... each within this fraction of the layer's max |z64| of zero

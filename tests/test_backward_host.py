@@ -40,7 +40,7 @@ def test_restatement_equals_the_oracle_forward(name):
         assert float((g - o).abs().max()) <= 1e-12 * float(o.max() - o.min())
 
 
-@pytest.mark.parametrize("name", ["a", "b", "d"])
+@pytest.mark.parametrize("name", ["a", "b", "d", "n8"])
 def test_own_masks_reproduce_plain_relu_autograd_and_fp32_stays_on_the_branch(name):
     c = bc.CASES[name]
     sd, x, feat, outs, km, pm, mask = case_inputs(name)

@@ -87,7 +87,7 @@ def run(name):
     return r
 
 
-CASE_NAMES = ["a", "b", "c", "d"]
+CASE_NAMES = ["a", "b", "c", "d", "n8"]
 
 
 @pytest.mark.parametrize("name", CASE_NAMES)
@@ -145,6 +145,41 @@ def test_gradients_against_float64(name):
         assert bc.err(got[k].cpu(), r["g64"][k]) <= 8 * r["e_ref"], k
     if name == "c":
         assert min(r["splits"].values()) > 1, r["splits"]                # more than one pixel range per weight gradient
+
+
+@pytest.mark.parametrize("name", ["c", "n8"])
+def test_rendered_targets_match_the_restatement(name):
+    """The targets every side of the comparisons above was handed are the device's own: 46 x 46 maps (nine workgroups a frame)
+    in case c, two frames of the guide5 table in n8.  Same bar as tests/test_gpu_train.py: touched sets identical, 1 float32 ulp."""
+    r = run(name)
+    c = r["c"]
+    K, lk, lp = tc.skeleton(c["skel"])
+    kp, n = bc.persons(c)
+    want = tc.targets(kp, n, c["H"], c["W"], 8, 7, 1, K, tc.limb_rows(lk, lp))
+    for what, got, w in (("keypoint_maps", r["km"], want[0]), ("paf_maps", r["pm"], want[1])):
+        got = got.cpu().numpy()
+        assert got.shape == w.shape and got.dtype == np.float32 and tc.touched(w).any()
+        assert np.array_equal(tc.touched(got), tc.touched(w)), (name, what)
+        u = tc.ulp_distance(got, w)
+        print("case %s %s: %d of %d elements not bit-identical" % (name, what, int((u > 0).sum()), u.size))
+        assert u.max() <= 1, (name, what)
+
+
+def test_losses_of_18_stage_tensors_match_float64():
+    """Engine.stage_losses on n8's own outputs: tensors 16 and 17 come from the second loss launch."""
+    r = run("n8")
+    N = r["c"]["N"]
+    assert len(r["outs"]) == 18
+    got = r["eng"].stage_losses(r["outs"], r["km"], r["pm"], r["mask"], N)
+    assert got == r["eng"].stage_losses(r["outs"], r["km"], r["pm"], r["mask"], N) and len(set(got)) == 18
+    km, pm, mask = r["km"].cpu().numpy(), r["pm"].cpu().numpy(), r["mask"].cpu().numpy()
+    worst = 0.0
+    for i, o in enumerate(r["outs"]):
+        o = o.cpu().numpy()
+        want = tc.l2_loss64(o, pm if i % 2 else km, mask, N)
+        worst = max(worst, abs(got[i] - want) / (o.size * 2.0 ** -52 * want))
+        assert got[i] > 0 and abs(got[i] - want) <= o.size * 2.0 ** -52 * want, (i, got[i], want)
+    print("case n8: worst loss error %.3g of its bar" % worst)
 
 
 @pytest.mark.parametrize("name", ["a", "b"])

@@ -4,7 +4,12 @@ Targets against what the reference's own statements produced (tests/golden/train
 identical, every value within 1 float32 ulp (the device's exp / sqrt stand in for CPython's exp / pow; a double that is off
 in its last bit moves a float32 rounding by one step at most); the count of non-identical elements is printed.  Mask: exact.
 Loss: relative error <= n * 2^-52 against the float64 restatement on the same float32 inputs (n non-negative terms summed in
-double), <= (n + 8) * 2^-24 against the reference's float32 l2_loss, and the same bits from two calls."""
+double), <= (n + 8) * 2^-24 against the reference's float32 l2_loss, and the same bits from two calls.
+
+train_targets_grid.npz, the mask cases of train_cases.MASK_CASES and the loss cases of train_cases.LOSS_GRID_CASES take the
+kernels past their smallest form at the same bars: more than one workgroup per frame, a second trip of the targets kernel's
+staging loop (K = 33, 64), a second trip of the loss grid (more than 262 144 positions) and a second loss launch (18 tensors).
+tests/test_train_host.py shows that a restatement without one of these forms fails on those cases."""
 import os
 
 import numpy as np
@@ -24,12 +29,13 @@ from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-CASES = tc.build_cases()
+CASES = tc.all_cases()
 _engines = {}
 
 
 def engine(skel="coco", nref=1):
-    """One engine per (skeleton, stage count); custom key-point sets get num_heatmaps = K + 1, num_pafs = 2L and their table."""
+    """One engine per (skeleton, stage count); custom key-point sets (the chains too: 34 + 64 and 65 + 126 channels) get
+    num_heatmaps = K + 1, num_pafs = 2L and their table."""
     if (skel, nref) not in _engines:
         K, lk, lp = tc.skeleton(skel)
         if skel == "coco":
@@ -43,7 +49,7 @@ def engine(skel="coco", nref=1):
 
 @pytest.fixture(scope="module")
 def golden():
-    return {f: np.load(os.path.join(GOLDEN, f + ".npz")) for f in ("train_targets", "train_targets_custom", "train_loss")}
+    return {f: np.load(os.path.join(GOLDEN, f + ".npz")) for f in list(tc.TARGET_FILES) + ["train_loss", "train_loss_grid"]}
 
 
 def check_targets(name, got, want):
@@ -56,7 +62,7 @@ def check_targets(name, got, want):
 
 
 # ------------------------------------------------------------------------------------------ targets
-@pytest.mark.parametrize("fname,name", [("train_targets", c) for c in tc.COCO_CASES] + [("train_targets_custom", c) for c in tc.CUSTOM_CASES])
+@pytest.mark.parametrize("fname,name", [(f, c) for f, names in tc.TARGET_FILES.items() for c in names])
 def test_targets_match_the_reference(golden, fname, name):
     skel, H, W, stride, sigma, thick, _ = CASES[name]
     g = golden[fname]
@@ -145,6 +151,23 @@ def test_mask_downsample_is_exact(stride):
     assert np.array_equal(eng.mask_downsample(mask[0], stride).cpu().numpy(), want[0])
 
 
+@pytest.mark.parametrize("kind", ["binary", "fraction"])
+@pytest.mark.parametrize("case", tc.MASK_CASES)
+def test_mask_downsample_is_exact_past_one_workgroup(case, kind):
+    """More than 256 cells per frame, frame offsets, a 1 x 257 map, an odd stride, stride 1 and 256-cell blocks, bit for bit
+    against the float64 block mean rounded once.  The ``fraction`` masks (multiples of 2^-8) go beyond what the reference ever
+    feeds, its masks being binary: they pin the kernel's own statement, the double sum of a block divided once, on inputs whose
+    sum is exact in any order (tests/test_train_host.py), so that the one correct rounding is the only answer."""
+    N, H, W, stride = case
+    mask = tc.mask_input(case, kind)
+    want = tc.mask_mean(mask, stride)
+    eng = engine()
+    got = eng.mask_downsample(mask, stride)
+    assert tuple(got.shape) == (N, H // stride, W // stride) and got.dtype == torch.float32
+    assert np.array_equal(got.cpu().numpy(), want)
+    assert np.array_equal(eng.mask_downsample(torch.from_numpy(mask).cuda(0), stride).cpu().numpy(), want)
+
+
 def test_mask_downsample_refuses_partial_blocks():
     for shape in ((1, 45, 40), (1, 48, 43)):
         with pytest.raises(ValueError, match="whole number"):
@@ -174,6 +197,58 @@ def test_stage_losses_bounds_and_determinism(golden, name, skel, nref):
     wide[..., 1:-2] = d[0]
     part = eng.stage_losses([wide[..., 1:-2]] + [None] * (len(d) - 1), dk, None, dm, N)
     assert part[0] == got[0] and part[1:] == [0.0] * (len(d) - 1)
+
+
+def _loss_case_on_device(name, n_stages):
+    outs, kt, pt, mask = tc.loss_inputs(name, n_stages)
+    d = [torch.from_numpy(o).cuda(0) for o in outs]
+    want = [tc.l2_loss64(o, pt if i % 2 else kt, mask, kt.shape[0]) for i, o in enumerate(outs)]
+    return outs, d, torch.from_numpy(kt).cuda(0), torch.from_numpy(pt).cuda(0), torch.from_numpy(mask).cuda(0), kt.shape[0], want
+
+
+def _check_losses(name, got, want, outs):
+    """|got - want64| <= n * 2^-52 * want64 per tensor; prints the worst error in units of that bar."""
+    worst = 0.0
+    for i, o in enumerate(outs):
+        bar = o.size * 2.0 ** -52 * want[i]
+        worst = max(worst, abs(got[i] - want[i]) / bar)
+        assert got[i] > 0 and abs(got[i] - want[i]) <= bar, (name, i, got[i], want[i])
+    print("%s: worst loss error %.3g of its bar" % (name, worst))
+
+
+@pytest.mark.parametrize("name", ["cap_exact", "one_past_cap", "second_trip"])
+def test_stage_losses_at_and_past_the_grid_cap(name):
+    """262 144 positions fill the capped grid's one trip exactly; 262 145 leave one position to the second trip, which carries an
+    error of 1 where every other error is of order 0.1 (its term alone is many times the bar); 2 x 363 x 363 is a second trip
+    of 1394 positions across a frame boundary."""
+    N, CH, CP, h, w, _ = tc.LOSS_GRID_CASES[name]
+    assert (N * h * w > tc.LOSS_CAP) == (name != "cap_exact")
+    outs, d, dk, dp, dm, N, want = _loss_case_on_device(name, 1)
+    eng = engine("guide5", 0)
+    got = eng.stage_losses(d, dk, dp, dm, N)
+    assert got == eng.stage_losses(d, dk, dp, dm, N)                                   # the same bits twice
+    _check_losses(name, got, want, outs)
+
+
+@pytest.mark.parametrize("name", ["s18", "s18_46"])
+def test_stage_losses_of_18_tensors_take_two_launches(golden, name):
+    """8 refinement stages: tensors 16 and 17 come from the second launch, which writes behind the first launch's sums and
+    reuses its partials (46 x 46: of more than one workgroup)."""
+    outs, d, dk, dp, dm, N, want = _loss_case_on_device(name, tc.LOSS_GRID_STAGES[name])
+    assert len(outs) == 18
+    eng = engine("guide5", 8)
+    got = eng.stage_losses(d, dk, dp, dm, N)
+    assert got == eng.stage_losses(d, dk, dp, dm, N)
+    _check_losses(name, got, want, outs)
+    assert len(set(got)) == 18                                                         # no sum landed in two places
+    if name == "s18":
+        g = golden["train_loss_grid"]
+        for i, o in enumerate(outs):
+            assert abs(got[i] - float(g["s18:losses_f32"][i])) <= (o.size + 8) * 2.0 ** -24 * got[i]
+    part = eng.stage_losses(d[:16] + [None, d[17]], dk, dp, dm, N)                     # a None entry in the second launch
+    assert part[:16] == got[:16] and part[16] == 0.0 and part[17] == got[17]
+    part = eng.stage_losses([None] * 16 + d[16:], dk, dp, dm, N)                       # nothing for the first launch to do
+    assert part[:16] == [0.0] * 16 and part[16:] == got[16:]
 
 
 def test_l2_loss_drop_in(golden):

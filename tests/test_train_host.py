@@ -15,18 +15,27 @@ from lwpose_amd.models.with_mobilenet import PoseEstimationWithMobileNet
 import train_cases as tc
 from conftest import GOLDEN
 
-TARGET_FILES = {"train_targets": tc.COCO_CASES, "train_targets_custom": tc.CUSTOM_CASES}
+TARGET_FILES = tc.TARGET_FILES
 ALL_CASES = [(f, c) for f, names in TARGET_FILES.items() for c in names]
+OLD_CASES = [(f, c) for f, c in ALL_CASES if f != "train_targets_grid"]
 
 
 @pytest.fixture(scope="module")
 def cases():
-    return tc.build_cases()
+    return tc.all_cases()
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return {f: np.load(os.path.join(GOLDEN, f + ".npz")) for f in list(TARGET_FILES) + ["train_loss"]}
+    return {f: np.load(os.path.join(GOLDEN, f + ".npz")) for f in list(TARGET_FILES) + ["train_loss", "train_loss_grid"]}
+
+
+def test_the_old_case_table_is_untouched_by_the_grid_cases(cases):
+    old = tc.build_cases()
+    assert sorted(old) == sorted(c for _, c in OLD_CASES) and sorted(cases) == sorted(c for _, c in ALL_CASES)
+    for name in old:
+        assert cases[name][:6] == old[name][:6]
+        assert all(np.array_equal(p, q) for f, g in zip(cases[name][6], old[name][6]) for p, q in zip(f, g))
 
 
 def test_fixture_inputs_are_the_case_table(cases, golden):
@@ -55,7 +64,8 @@ def test_vectorised_restatement_matches_the_reference(cases, golden, fname, name
         assert u.max() <= 1
 
 
-@pytest.mark.parametrize("fname,name", [("train_targets", "borders"), ("train_targets", "paf_t2"), ("train_targets_custom", "guide5")])
+@pytest.mark.parametrize("fname,name", [("train_targets", "borders"), ("train_targets", "paf_t2"), ("train_targets_custom", "guide5"),
+                                        ("train_targets_grid", "interior"), ("train_targets_grid", "chain33")])
 def test_pixel_loop_restatement_is_bit_identical(cases, golden, fname, name):
     skel, H, W, stride, sigma, thick, _ = cases[name]
     K, lk, lp = tc.skeleton(skel)
@@ -77,6 +87,84 @@ def test_goldens_hold_what_the_cases_are_for(golden):
     assert np.array_equal(g["cross_ab:kpts"][:, ::-1], g["cross_ba:kpts"])
 
 
+def test_grid_goldens_hold_what_the_cases_are_for(cases, golden):
+    g = golden["train_targets_grid"]
+    tc.check_grid_cases(cases, {name: (g[name + ":keypoint_maps"], g[name + ":paf_maps"]) for name in tc.GRID_CASES})
+    for name in ("chain33", "chain64"):
+        K, lk, lp = tc.skeleton(name)
+        assert K == int(name[5:]) and lk == [[j, j + 1] for j in range(K - 1)] and lp == [[2 * j, 2 * j + 1] for j in range(K - 1)]
+        assert g[name + ":keypoint_maps"].shape[1] == K + 1 and g[name + ":paf_maps"].shape[1] == 2 * (K - 1)
+        assert sorted(set(g[name + ":kpts"][..., 2].ravel().tolist())) == [0.0, 1.0, 2.0]
+        assert tc.CHUNK * K > 256                                         # a full chunk needs a second staging trip ...
+    assert tc.CHUNK * 32 <= 256                                           # ... and 33 is the smallest such K
+
+
+# ---- mutants of tc.targets: each is the restatement with one of the kernel's forms left out.  It must pass the fixture check on
+# every old case (the suite without the grid cases cannot tell it from the real thing) and fail it on the named new ones.
+def _agrees(got, want):
+    return all(np.array_equal(tc.touched(a), tc.touched(b)) and tc.ulp_distance(a, b).max() <= 1 for a, b in zip(got, want))
+
+
+def _restated(cases, g, name, kpts=None):
+    skel, H, W, stride, sigma, thick, _ = cases[name]
+    K, lk, lp = tc.skeleton(skel)
+    kpts = g[name + ":kpts"] if kpts is None else kpts
+    return tc.targets(kpts, g[name + ":n_persons"], H, W, stride, sigma, thick, K, tc.limb_rows(lk, lp))
+
+
+def mutant_one_workgroup(km, pm):
+    """Pixels of linear index 256 or above stay as an empty frame gives them: key-point channels 0, background 1, PAF 0."""
+    km, pm = km.copy(), pm.copy()
+    N, C, h, w = km.shape
+    fk, fp = km.reshape(N, C, h * w), pm.reshape(N, -1, h * w)
+    fk[:, :-1, 256:] = 0
+    fk[:, -1, 256:] = 1
+    fp[:, :, 256:] = 0
+    return km, pm
+
+
+def mutant_wrapped_index(km, pm):
+    """Pixel i at 256 or above takes pixel i - 256's value."""
+    out = []
+    for m in (km, pm):
+        N, C, h, w = m.shape
+        f = m.reshape(N, C, h * w).copy()
+        f[:, :, 256:] = m.reshape(N, C, h * w)[:, :, :max(h * w - 256, 0)]
+        out.append(f.reshape(m.shape))
+    return tuple(out)
+
+
+def mutant_one_staging_trip(kpts, K):
+    """Inside each chunk of CHUNK persons, entries q * K + k >= 256 were never staged: they count as visibility 2."""
+    kpts = kpts.copy()
+    q = np.arange(kpts.shape[1])[:, None] % tc.CHUNK
+    late = q * K + np.arange(K)[None, :] >= 256
+    kpts[:, late, 2] = 2.0
+    return kpts
+
+
+# not full256: 256 pixels exactly is what that case is for; the chains' scattered key-points reach their 17th map row as well
+PIXEL_MUTANT_DIFFERS = set(tc.PAST_256) | {"chain33", "chain64"}
+STAGING_MUTANT_DIFFERS = {"chain33", "chain64"}
+
+
+@pytest.mark.parametrize("fname,name", ALL_CASES)
+def test_mutants_pass_every_old_case_and_fail_the_named_new_ones(cases, golden, fname, name):
+    g = golden[fname]
+    want = (g[name + ":keypoint_maps"], g[name + ":paf_maps"])
+    km, pm = _restated(cases, g, name)
+    assert _agrees((km, pm), want)
+    K = tc.skeleton(cases[name][0])[0]
+    got = {"one workgroup": _agrees(mutant_one_workgroup(km, pm), want),
+           "wrapped index": _agrees(mutant_wrapped_index(km, pm), want),
+           "one staging trip": _agrees(_restated(cases, g, name, mutant_one_staging_trip(g[name + ":kpts"], K)), want)}
+    expect = {"one workgroup": name not in PIXEL_MUTANT_DIFFERS, "wrapped index": name not in PIXEL_MUTANT_DIFFERS,
+              "one staging trip": name not in STAGING_MUTANT_DIFFERS}
+    assert got == expect, name
+    if fname != "train_targets_grid":
+        assert all(got.values())
+
+
 def test_default_skeleton_gives_the_reference_channel_layout():
     K, lk, lp = tc.skeleton("coco")
     assert tc.train_limbs(lk, lp) == coco_mod.BODY_PARTS_KPT_IDS == tc.COCO_TRAIN_LIMBS
@@ -94,6 +182,46 @@ def test_mask_mean_is_exact_for_binary_masks():
     assert tc.mask_mean(m, 8)[1, 1, 1] == 0
 
 
+@pytest.mark.parametrize("case", tc.MASK_CASES)
+def test_mask_mean_sums_exactly_on_the_gpu_cases(case):
+    """The masks of tests/test_gpu_train.py: 0 / 1, and multiples of 2^-8 in [0, 1].  256 times a block's sum is an integer below
+    2^17, so the float64 sum of mask_mean is exact in any order and the mean is that sum divided once."""
+    N, H, W, s = case
+    for kind in ("binary", "fraction"):
+        m = tc.mask_input(case, kind)
+        scaled = m.astype(np.float64) * 256
+        assert m.dtype == np.float32 and m.min() >= 0 and m.max() <= 1 and np.array_equal(scaled, np.round(scaled))
+        assert (kind == "binary") == (set(np.unique(m).tolist()) <= {0.0, 1.0}) and len(np.unique(m)) > 1
+        isum = scaled.astype(np.int64).reshape(N, H // s, s, W // s, s).sum(axis=(2, 4))                  # integer block sums
+        assert isum.max() <= 256 * s * s <= 1 << 16
+        want = ((isum.astype(np.float64) / 256.0) / float(s * s)).astype(np.float32)
+        got = tc.mask_mean(m, s)
+        assert got.shape == (N, H // s, W // s) and np.array_equal(got, want)
+
+
+def test_a_loss_that_stops_at_the_grid_cap_passes_the_old_cases_only(golden):
+    """The mutant sums the first 262 144 positions (one trip of the capped grid).  n * 2^-52 relative is the GPU tests' bar."""
+    def miss(name, n_stages):
+        outs, kt, pt, mask = tc.loss_inputs(name, n_stages)
+        worst = 0.0
+        for i, o in enumerate(outs):
+            t = pt if i % 2 else kt
+            want = tc.l2_loss64(o, t, mask, kt.shape[0])
+            worst = max(worst, abs(tc.l2_loss64_first(o, t, mask, kt.shape[0], tc.LOSS_CAP) - want) / (o.size * 2.0 ** -52 * want))
+        return worst
+    for name in tc.LOSS_CASES:
+        assert miss(name, int(golden["train_loss"][name + ":n_stages"])) == 0.0
+    assert miss("cap_exact", 1) == 0.0 and miss("s18", 9) == 0.0
+    assert miss("one_past_cap", 1) > 1 and miss("second_trip", 1) > 1
+    N, CH, CP, h, w, _ = tc.LOSS_GRID_CASES["cap_exact"]
+    assert N * h * w == tc.LOSS_CAP
+    assert [c[0] * c[3] * c[4] for c in (tc.LOSS_GRID_CASES["one_past_cap"], tc.LOSS_GRID_CASES["second_trip"])] == [tc.LOSS_CAP + 1, 263538]
+    # one_past_cap: the last position alone carries more than the bar
+    outs, kt, pt, mask = tc.loss_inputs("one_past_cap", 1)
+    assert mask[-1, -1, -1] == 1 and np.array_equal(outs[0][-1, :, -1, -1], kt[-1, :, -1, -1] + np.float32(1))
+    assert np.abs(outs[0] - kt).reshape(-1, kt.shape[1], 52429)[..., :-1].max() < 0.75
+
+
 def test_float64_loss_matches_the_reference_float32_loss(golden):
     """(n + 8) * 2^-24 relative: any float32 summation order over n non-negative terms, plus the roundings of one term."""
     g = golden["train_loss"]
@@ -105,6 +233,14 @@ def test_float64_loss_matches_the_reference_float32_loss(golden):
             got = tc.l2_loss64(o, pt if i % 2 else kt, mask, kt.shape[0])
             print(name, i, got, want)
             assert abs(got - want) <= (o.size + 8) * 2.0 ** -24 * got
+    g = golden["train_loss_grid"]                         # 18 tensors on the 6 x 5 maps
+    assert list(g["cases"]) == ["s18"] and int(g["s18:n_stages"]) == tc.LOSS_GRID_STAGES["s18"] == 9
+    outs, kt, pt, mask = tc.loss_inputs("s18", 9)
+    assert len(outs) == 18 and np.array_equal(g["s18:digest"], [float(a.astype(np.float64).sum()) for a in outs + [kt, pt, mask]])
+    for i, o in enumerate(outs):
+        want = float(g["s18:losses_f32"][i])
+        got = tc.l2_loss64(o, pt if i % 2 else kt, mask, kt.shape[0])
+        assert abs(got - want) <= (o.size + 8) * 2.0 ** -24 * got
 
 
 def test_labels_to_arrays_keeps_label_order(cases):

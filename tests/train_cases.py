@@ -29,6 +29,9 @@ def skeleton(name):
         return 21, sc.HAND21_KPTS, sc.HAND21_PAFS
     if name == "guide5":
         return 5, sc.GUIDE5_KPTS, sc.GUIDE5_PAFS
+    if name in ("chain33", "chain64"):                   # synthetic: limb j joins types (j, j + 1) and owns PAF channels (2j, 2j + 1)
+        K = int(name[5:])
+        return K, [[j, j + 1] for j in range(K - 1)], [[2 * j, 2 * j + 1] for j in range(K - 1)]
     raise KeyError(name)
 
 
@@ -128,6 +131,141 @@ def build_cases():
 
 COCO_CASES = ["borders", "odd_45x43", "stride4_sigma3p5", "chunk", "two_chunks_plus", "paf_t1", "paf_t2", "cross_ab", "cross_ba"]
 CUSTOM_CASES = ["hand21", "hand21_stride4", "guide5"]
+
+
+# ------------------------------------------------------------------------------------------------ cases past one workgroup
+# The cases above never leave the targets kernel's smallest form: at most 120 map pixels (one workgroup of 256 threads), at
+# most 8 x 21 = 168 staged chunk entries (one trip of the 256-thread staging loop).  The ones below do; what each is for is
+# asserted by tools/make_train_golden.py and again, on the fixture, by tests/test_train_host.py.
+def _row257(rng):
+    a = _blank(18)
+    a[0] = (2046.0, 4.0, 0)                              # between the centres of pixels 255 (x = 2043.5) and 256 (2051.5)
+    a[1] = (2030.0, 4.0, 0); a[2] = (2054.0, 4.0, 1)     # limb [1,2]: 253.75 .. 256.75 map units, across the 255 / 256 boundary
+    a[3] = (2056.0, 3.5, 0)                              # x == W exactly
+    a[4] = (2051.5, 3.5, 1)                              # the centre of pixel 256, the last one: increment 1
+    a[5] = (2043.5, 3.5, 0)                              # the centre of pixel 255, the first workgroup's last thread
+    b = _blank(18)
+    b[:, 0] = rng.uniform(2000.0, 2070.0, 18)            # around the far end and up to 14 px beyond it
+    b[:, 1] = rng.uniform(-10.0, 18.0, 18)
+    b[:, 2] = rng.randint(0, 3, 18)
+    return [[a, b, _person(rng, "coco", 8, 2056)]]
+
+
+def _grid272(rng):
+    frames = _crowd(rng, "coco", 136, 128, [3, CHUNK + 2, 0])
+    frames[1][0][0] = (60.0, 130.0, 0)                   # persons 0 and 9 of frame 1, chunks 0 and 1, on one cell of the last map row
+    frames[1][CHUNK + 1][0] = (62.0, 128.0, 1)           # (pixel 16 * 16 + 7 = 263 of workgroup 1): 0.975 + 0.828, clipped to 1
+    return frames
+
+
+def _interior(rng):
+    a = _blank(18)
+    a[0] = (60.0, 90.0, 0)                               # x - 4 sigma == 32.0, a multiple of the stride: the box starts at cell 4
+    a[1] = (100.0, 64.0, 0); a[2] = (140.0, 64.0, 0)     # limb [1,2] along y = 8.0 map units: row 7 lies at d == thickness 1
+    a[5] = (40.0, 40.0, 0); a[6] = (90.0, 110.0, 1)      # limb [5,6], oblique
+    a[8] = (100.0, 100.0, 0); a[9] = (103.0, 101.0, 0)   # limb [8,9], 0.4 map units long
+    a[11] = (150.0, 40.0, 1); a[12] = (150.0, 120.0, 0)  # limb [11,12], vertical at x = 18.75 map units
+    b = _blank(18)
+    b[0] = (59.9, 130.0, 1)                              # a hair below: int(31.9) = 31, the box starts at cell 3
+    b[3] = (172.0, 156.0, 0)                             # x + 4 sigma == W, y + 4 sigma == H: the far clamps change nothing
+    b[4] = (28.0, 28.0, 0)                               # x - 4 sigma == 0, y - 4 sigma == 0
+    c = a.copy()                                         # a second person on the same spots: the clip to 1 fires mid-map
+    c[:, 2] = np.minimum(c[:, 2], 1.0)
+    return [[a, b, c], _crowd(rng, "coco", 184, 200, [2])[0]]          # frame 0 is hand-placed only, frame 1 two figures
+
+
+def _stride4_grid(rng):
+    frames = _crowd(rng, "coco", 72, 64, [3])
+    p = _blank(18)
+    p[0] = (30.0, 68.0, 0)                               # map row 17, pixels 272 and above
+    p[1] = (10.0, 66.0, 0); p[2] = (50.0, 70.0, 1)       # limb [1,2] across rows 16 and 17
+    frames[0].append(p)
+    return frames
+
+
+def _scatter(rng, K, H, W, counts):
+    """Key-points uniform over the frame and 20 px beyond it, visibility 0 / 1 / 2 in equal parts."""
+    def one():
+        p = np.zeros((K, 3))
+        p[:, 0] = rng.uniform(-20.0, W + 20.0, K)
+        p[:, 1] = rng.uniform(-20.0, H + 20.0, K)
+        p[:, 2] = rng.randint(0, 3, K)
+        return p
+    return [[one() for _ in range(n)] for n in counts]
+
+
+def _chain33(rng):
+    frames = _scatter(rng, 33, 136, 128, [CHUNK + 3])
+    frames[0][CHUNK - 1][25:, 2] = [0, 1, 0, 1, 2, 0, 1, 0]   # person 7, types 25 .. 32: chunk entries 256 .. 263, the second staging trip
+    return frames
+
+
+def build_grid_cases():
+    rng = np.random.RandomState(20261)
+    cases = {}
+    cases["row257"] = ("coco", 8, 2056, 8, 7, 1, _row257(rng))                 # 1 x 257: the second workgroup has one active thread
+    cases["full256"] = ("coco", 128, 128, 8, 7, 1, _crowd(rng, "coco", 128, 128, [3]))   # 16 x 16: one workgroup, no inactive thread
+    cases["grid272"] = ("coco", 136, 128, 8, 7, 1, _grid272(rng))              # 17 x 16, frames of 3 / CHUNK + 2 / 0 persons
+    cases["interior"] = ("coco", 184, 200, 8, 7, 1, _interior(rng))            # 23 x 25 = 575 pixels, three workgroups
+    cases["stride4_grid"] = ("coco", 72, 64, 4, 3.5, 2, _stride4_grid(rng))    # 18 x 16 = 288
+    cases["chain33"] = ("chain33", 136, 128, 8, 7, 1, _chain33(rng))           # 8 x 33 = 264 chunk entries
+    cases["chain64"] = ("chain64", 136, 128, 8, 7, 1, _scatter(rng, 64, 136, 128, [CHUNK, CHUNK + 3]))   # 512 entries, 20 KB of LDS
+    return cases
+
+
+GRID_CASES = ["row257", "full256", "grid272", "interior", "stride4_grid", "chain33", "chain64"]
+GRID_PIXELS = {"row257": 257, "full256": 256, "grid272": 272, "interior": 575, "stride4_grid": 288, "chain33": 272, "chain64": 272}
+PAST_256 = ["row257", "grid272", "interior", "stride4_grid"]      # coco cases that touch pixels of linear index 256 or above
+TARGET_FILES = {"train_targets": COCO_CASES, "train_targets_custom": CUSTOM_CASES, "train_targets_grid": GRID_CASES}
+
+
+def all_cases():
+    cases = build_cases()
+    cases.update(build_grid_cases())
+    return cases
+
+
+def gaussian_box(x, y, sigma, stride, h, w):
+    """_add_gaussian's cell range (x0, x1, y0, y1) and whether each of its four edges was clamped by the frame."""
+    tl = [int(x - 4 * sigma), int(y - 4 * sigma)]
+    br = [int(x + 4 * sigma), int(y + 4 * sigma)]
+    clamped = (tl[0] < 0, br[0] > w * stride, tl[1] < 0, br[1] > h * stride)
+    return (max(tl[0], 0) // stride, min(br[0], w * stride) // stride, max(tl[1], 0) // stride, min(br[1], h * stride) // stride), clamped
+
+
+def check_grid_cases(cases, maps):
+    """What every grid case is for, asserted on ``maps``: name -> (keypoint_maps, paf_maps) as the reference rendered them."""
+    for name in GRID_CASES:
+        skel, H, W, stride, sigma, thick, frames = cases[name]
+        k, p = maps[name]
+        assert k.shape[2] * k.shape[3] == GRID_PIXELS[name] == (H // stride) * (W // stride), name
+        K = skeleton(skel)[0]
+        flat_k, flat_p = k[:, :K].reshape(len(frames), K, -1), p.reshape(len(frames), p.shape[1], -1)
+        if name in PAST_256:
+            assert flat_k[..., 256:].any() and flat_p[..., 256:].any(), name
+    k, p = maps["row257"]
+    assert k.shape[2:] == (1, 257) and k[0, 0, 0, 255] != 0 and k[0, 0, 0, 256] != 0 and k[0, 4, 0, 256] == 1.0 and k[0, 5, 0, 255] == 1.0
+    assert (p[0, 12, 0, 252:257] != 0).all()                                           # limb [1,2] on both sides of the boundary
+    k, p = maps["grid272"]
+    assert [len(f) for f in cases["grid272"][6]] == [3, CHUNK + 2, 0]
+    assert k[1, 0, 16, 7] == 1.0 and not k[2, :18].any() and (k[2, 18] == 1).all() and not p[2].any()
+    skel, H, W, stride, sigma, thick, frames = cases["interior"]
+    k, p = maps["interior"]
+    h, w = H // stride, W // stride
+    boxes = [gaussian_box(x, y, sigma, stride, h, w) for person in frames[0] for x, y, v in person if v <= 1]
+    assert any(not any(c) and 0 < b[0] and b[1] < w and 0 < b[2] and b[3] < h for b, c in boxes)   # four unclamped edges inside the map
+    on, below = gaussian_box(*frames[0][0][0][:2], sigma, stride, h, w)[0], gaussian_box(*frames[0][1][0][:2], sigma, stride, h, w)[0]
+    assert frames[0][0][0][0] - 4 * sigma == 32.0 and on[0] == 4 and below[0] == 3      # the boundary pair lands in different cells
+    assert k[0, 0, 11, 7] == 1.0 and (k[0, :18, 2:-2, 2:-2] == 1.0).sum() > 3           # the clip fired away from every border
+    assert p[0, 12, 7, 14] == 1.0 and p[0, 12, 8, 14] == 1.0 and p[0, 12, 6, 14] == 0.0 and p[0, 12, 9, 14] == 0.0   # row 7: d == thickness
+    for c in (2, 22, 8):                                                                # short, oblique and vertical limbs, wholly inside
+        assert p[0, c:c + 2].any() and not p[0, c:c + 2, 0].any() and not p[0, c:c + 2, -1].any()
+        assert not p[0, c:c + 2, :, 0].any() and not p[0, c:c + 2, :, -1].any()
+    skel, H, W, stride, sigma, thick, frames = cases["chain33"]
+    assert len(frames[0]) == CHUNK + 3
+    late = [(x, y) for x, y, v in frames[0][CHUNK - 1][25:] if v <= 1]                  # chunk entries 7 * 33 + 25 = 256 and above
+    assert late and any(b[0] < b[1] and b[2] < b[3] for b in (gaussian_box(x, y, sigma, stride, H // stride, W // stride)[0] for x, y in late))
+    assert sorted(len(f) for f in cases["chain64"][6]) == [CHUNK, CHUNK + 3] and skeleton("chain64")[0] == 64
 
 
 def frames_to_arrays(frames, K):
@@ -275,13 +413,38 @@ def touched(m):
     return m != 0
 
 
+# ------------------------------------------------------------------------------------------------ mask cases
+# (N, H, W, stride): 272 cells in two workgroups with frame offsets; 1 x 257; an odd stride on 17 x 16; stride 1 (a copy, 300
+# cells); 256-cell blocks on a 4 x 3 map
+MASK_CASES = [(2, 136, 128, 8), (1, 8, 2056, 8), (3, 51, 48, 3), (1, 20, 15, 1), (2, 64, 48, 16)]
+
+
+def mask_input(case, kind):
+    """``binary``: 0 / 1.  ``fraction``: multiples of 2^-8 in [0, 1], so that a block of at most 256 cells sums exactly in double
+    (the sum times 256 is an integer below 2^17) and the one correct rounding of the mean is the only answer."""
+    N, H, W, stride = case
+    rng = np.random.RandomState(100 * H + W + stride)
+    if kind == "binary":
+        return (rng.rand(N, H, W) > 0.4).astype(np.float32)
+    assert kind == "fraction"
+    return (rng.randint(0, 257, size=(N, H, W)) / 256.0).astype(np.float32)
+
+
 # ------------------------------------------------------------------------------------------------ loss cases
 # name -> (N, heat-map channels, PAF channels, h, w, seed): synthetic stage tensors, targets and a mask with zeros
 LOSS_CASES = {"small": (2, 19, 38, 6, 5, 1), "multi_block": (3, 19, 38, 46, 46, 2), "guide5": (2, 6, 8, 6, 5, 3)}
+# past the loss grid's cap of 1024 workgroups x 256 positions = 262 144, and past 16 tensors (guide5 channels throughout)
+LOSS_CAP = 1024 * 256
+LOSS_GRID_CASES = {"cap_exact": (1, 6, 8, 512, 512, 11),         # 262 144 positions: 1024 workgroups, one trip
+                   "one_past_cap": (5, 6, 8, 1, 52429, 12),      # 262 145: the second trip is one position, and it carries the loss
+                   "second_trip": (2, 6, 8, 363, 363, 13),       # 263 538
+                   "s18": (2, 6, 8, 6, 5, 14),                   # 18 tensors (8 refinement stages): two launches
+                   "s18_46": (2, 6, 8, 46, 46, 15)}              # ... whose partials fill more than one workgroup
+LOSS_GRID_STAGES = {"cap_exact": 1, "one_past_cap": 1, "second_trip": 1, "s18": 9, "s18_46": 9}
 
 
 def loss_inputs(name, n_stages=2):
-    N, CH, CP, h, w, seed = LOSS_CASES[name]
+    N, CH, CP, h, w, seed = LOSS_CASES[name] if name in LOSS_CASES else LOSS_GRID_CASES[name]
     rng = np.random.RandomState(1000 + seed)
     kt = rng.rand(N, CH, h, w).astype(np.float32)
     pt = (rng.rand(N, CP, h, w).astype(np.float32) * 2 - 1) * (rng.rand(N, CP, h, w) < 0.2)
@@ -291,4 +454,17 @@ def loss_inputs(name, n_stages=2):
     for s in range(n_stages):
         outs.append((kt + rng.randn(N, CH, h, w) * 0.1).astype(np.float32))
         outs.append((pt + rng.randn(N, CP, h, w) * 0.1).astype(np.float32))
-    return outs, kt, pt.astype(np.float32), mask
+    pt = pt.astype(np.float32)
+    if name == "one_past_cap":                           # the very last position: an error of 1 in every channel, mask 1
+        mask[-1, -1, -1] = 1.0
+        for i, o in enumerate(outs):
+            o[-1, :, -1, -1] = (pt if i % 2 else kt)[-1, :, -1, -1] + np.float32(1)
+    return outs, kt, pt, mask
+
+
+def l2_loss64_first(out, target, mask, batch_size, positions):
+    """A wrong l2_loss64: the sum over the first ``positions`` (frame, pixel) positions only."""
+    N, C, h, w = out.shape
+    keep = (np.arange(N * h * w) < positions).reshape(N, 1, h, w)
+    d = (out.astype(np.float64) - target.astype(np.float64)) * mask.astype(np.float64)[:, None]
+    return float((d * d / 2 / batch_size * keep).sum())

@@ -1,5 +1,5 @@
-"""Generates tests/golden/train_targets.npz, train_targets_custom.npz and train_loss.npz: the reference's own target
-rendering (datasets/coco.py _generate_keypoint_maps / _add_gaussian / _generate_paf_maps / _set_paf) and its l2_loss
+"""Generates tests/golden/train_targets.npz, train_targets_custom.npz, train_targets_grid.npz, train_loss.npz and
+train_loss_grid.npz: the reference's own target rendering (datasets/coco.py _generate_keypoint_maps / _add_gaussian / _generate_paf_maps / _set_paf) and its l2_loss
 (modules/loss.py) on the cases of tests/train_cases.py.
 
 Run only where the reference checkout exists (never on the GPU machines):
@@ -10,7 +10,7 @@ The reference's statements are executed, not restated.  datasets/coco.py cannot 
 pycocotools), so the four methods are taken out of its syntax tree and compiled as plain functions whose ``self`` is a small
 object with ``_stride`` / ``_sigma`` / ``_paf_thickness``.  A custom key-point set is bound the way TRAIN-ON-CUSTOM-DATASET.md
 tells a user to edit the file: the module's ``BODY_PARTS_KPT_IDS`` is the new limb list (row j owns PAF channels 2j, 2j + 1),
-and the literal 18 assigned to ``n_keypoints`` becomes the new count.  ``l2_loss`` runs in torch float32 on the CPU.  The
+and the literal 18 assigned to ``n_keypoints`` becomes the new count (the synthetic chains of train_targets_grid.npz too).  ``l2_loss`` runs in torch float32 on the CPU.  The
 files hold data only: every case's inputs and the arrays the reference made of them."""
 import ast
 import io
@@ -86,8 +86,8 @@ def ref_l2_loss():
 
 
 def gen_targets():
-    cases = tc.build_cases()
-    files = {"train_targets": tc.COCO_CASES, "train_targets_custom": tc.CUSTOM_CASES}
+    cases = tc.all_cases()
+    files = tc.TARGET_FILES
     got = {}
     for fname, names in files.items():
         d = {"cases": np.array(names)}
@@ -99,6 +99,10 @@ def gen_targets():
                 ref_ns = ref_target_namespace(18, ref_limbs)
                 src = open(os.path.join(REF, "datasets", "coco.py")).read()
                 assert ref_limbs == ast.literal_eval(src[src.index("BODY_PARTS_KPT_IDS = ") + 21:src.index("\n\n\ndef get_mask")])
+            elif skel.startswith("chain"):              # synthetic chains: limb j = (j, j + 1), bound the same way
+                ref_limbs = tc.train_limbs(limb_kpts, limb_pafs)
+                assert ref_limbs == [[j, j + 1] for j in range(K - 1)]
+                ref_ns = ref_target_namespace(K, ref_limbs)
             else:                                       # the tables of the custom-skeleton fixtures, bound as the guide says
                 g = np.load(os.path.join(OUT, "skeleton_hand21.npz" if skel == "hand21" else "skeleton_guide5_r4.npz"))
                 assert g["limb_kpts"].tolist() == [list(p) for p in limb_kpts] and g["limb_pafs"].tolist() == [list(p) for p in limb_pafs]
@@ -140,13 +144,15 @@ def gen_targets():
     for name in ("chunk", "two_chunks_plus", "hand21"):
         assert max(len(f) for f in got[name][2]) > tc.CHUNK
     assert sorted(len(f) for f in got["chunk"][2]) == [tc.CHUNK - 1, tc.CHUNK, tc.CHUNK + 1]
+    tc.check_grid_cases(cases, {name: got[name][:2] for name in tc.GRID_CASES})
 
 
-def gen_loss():
+def gen_loss(fname, stages):
+    """``stages``: case name -> number of stages (two tensors each)."""
     l2 = ref_l2_loss()
-    d = {"cases": np.array(sorted(tc.LOSS_CASES))}
-    for name in sorted(tc.LOSS_CASES):
-        n_stages = 4 if name == "small" else 2
+    d = {"cases": np.array(sorted(stages))}
+    for name in sorted(stages):
+        n_stages = stages[name]
         outs, kt, pt, mask = tc.loss_inputs(name, n_stages)
         N = kt.shape[0]
         losses = []
@@ -159,9 +165,10 @@ def gen_loss():
         d[name + ":n_stages"] = np.array(n_stages, np.int32)
         d[name + ":losses_f32"] = np.array(losses, np.float32)
         d[name + ":digest"] = np.array([float(np.float64(o.astype(np.float64).sum())) for o in outs + [kt, pt, mask]])
-    save("train_loss", d)
+    save(fname, d)
 
 
 if __name__ == "__main__":
     gen_targets()
-    gen_loss()
+    gen_loss("train_loss", {name: 4 if name == "small" else 2 for name in tc.LOSS_CASES})
+    gen_loss("train_loss_grid", {"s18": tc.LOSS_GRID_STAGES["s18"]})
