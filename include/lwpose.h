@@ -353,7 +353,7 @@ int lwp_draw_poses(lwp_handle h, const unsigned char* imgs, int img_mem, int N, 
 
 /* ---- training targets and the per-stage masked L2 loss on the device: replaces datasets/coco.py:48-61,71-159 (the mask resize,
  *      _generate_keypoint_maps / _add_gaussian, _generate_paf_maps / _set_paf) and modules/loss.py l2_loss as train.py:92-97
- *      sums it per stage.  Targets and loss only: there is no backward, no optimiser and no augmentation.
+ *      sums it per stage.  Targets and loss only: backward, optimiser and augmentation are the sections below.
  *      lwp_train_targets: kpts is N x Pmax x K x 3 float64 (mem) holding (x, y, visibility) in image pixels, persons in label
  *      order (the main person, then processed_other_annotations); n_persons[N] (host) says how many rows of a frame count.  K, L,
  *      the limbs' key-point pairs and their PAF channel pairs are the handle's skeleton table (lwp_set_skeleton); the default
@@ -583,6 +583,54 @@ int lwp_stage_adam_state_set(lwp_handle h, const float* exp_avg_device, const fl
 int lwp_stage_adam_reset(lwp_handle h);
 int lwp_time_stage_adam_step(lwp_handle h, const float* grads_device, double base_lr, double beta1, double beta2, double eps,
                              double weight_decay, int iters, float* ms);
+
+/* ---- training augmentation on the device: the pixel half of datasets/transformations.py (Scale -> Rotate -> CropPad -> Flip,
+ *      train.py:33-38) and of coco.py:48,63-65, for a whole batch in one kernel launch.  The host half (the random draws, the
+ *      label arithmetic, the geometry below) is lwpose_amd.datasets.transformations.plan_batch; this call renders only the
+ *      pixels of the final crop, each straight from the source image: the warped-image pixel behind a crop pixel gives four
+ *      fixed-point taps in the resized image, and each tap is evaluated on demand from four source pixels.  No intermediate
+ *      image exists, and the result equals the staged resize -> warpAffine -> crop -> flip integer for integer.  The arithmetic
+ *      restates OpenCV's plain C path and is not pinned against cv2.
+ *      One record per sample:
+ *        image / mask   src_h x src_w x 3 uint8 (interleaved) and src_h x src_w float32 with values in [0, 1] (not checked), both
+ *                       in `mem` memory; mask == NULL means all ones (the mask taps are skipped, the result is 1 everywhere).
+ *                       Host sources of a batch are packed and uploaded with ONE copy; device sources are read in place.
+ *        rs_h, rs_w, rs_scale, area   cv2.resize(dsize = (0, 0), fx = fy = s): the rounded size, 1 / s, and 1 where OpenCV takes the
+ *                       2 x 2 area average instead (|1 / s - 2| < DBL_EPSILON)
+ *        m[6]           the INVERTED 2 x 3 matrix warpAffine walks (destination -> source), bound_h x bound_w its destination size
+ *        should_crop, dst_*, img_*   CropPad's slice assignment resolved: crop rows dst_y0..dst_y1-1 and columns dst_x0..dst_x1-1
+ *                       show warped pixel (img_y0 + y - dst_y0, img_x0 + x - dst_x0).  Everything else is crop_pad, mask 1.
+ *        flip           1: the crop is mirrored (cv2.flip(.., 1))
+ *        warp_pad, crop_pad   warpAffine's borderValue and CropPad's fill
+ *      Outputs (DEVICE): image_out N x 3 x crop_h x crop_w float32 = (float(v) - 128) / 256; mask_out N x crop_h x crop_w uint8
+ *      (the float mask TRUNCATED, as the reference's uint8 cropped_mask does: only 1.0 survives); mask_small_out
+ *      N x (crop_h / stride) x (crop_w / stride) float32 = rint(float(block sum) * float(1 / stride^2)), INTER_AREA on a uint8
+ *      image (lwp_mask_downsample, the float mean, is a different rule and is unchanged).
+ *      Checks without a GPU (h == NULL too, LWP_ERR_ARG): null pointers, 1 <= N <= 65535, 1 <= stride <= 1024, crop_h and crop_w
+ *      multiples of the stride, every size (source, resized, bound, crop) in 1..32767 (OpenCV saturates coordinates to short at
+ *      32768), a non-NULL image, the mem flag, finite rs_scale > 0 and matrix, the dst rectangle inside the crop and
+ *      its source inside the bound.  Runs on the handle's stream, honours lwp_set_stream, needs no weights. */
+typedef struct lwp_augment_plan {
+    const unsigned char* image;
+    const float* mask;
+    double rs_scale;
+    double m[6];
+    int mem;
+    int src_h, src_w;
+    int rs_h, rs_w, area;
+    int bound_h, bound_w;
+    int should_crop;
+    int dst_y0, dst_y1, dst_x0, dst_x1;
+    int img_y0, img_x0;
+    int flip;
+    unsigned char warp_pad[3], crop_pad[3];
+} lwp_augment_plan;
+int lwp_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride, float* image_out,
+                      unsigned char* mask_out, float* mask_small_out);
+/* the two kernels alone (tools/augment_bench.py): the same checks and the one upload, then `iters` back-to-back launch pairs
+ * between two HIP events.  ms_total out. */
+int lwp_time_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride, float* image_out,
+                           unsigned char* mask_out, float* mask_small_out, int iters, float* ms_total);
 
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */

@@ -37,7 +37,18 @@ EXPORTS = [
     "lwp_debug_train_copy", "lwp_debug_backward_dw_splits", "lwp_debug_dw_grad_sd", "lwp_debug_stem_wgrad",
     "lwp_debug_conv_grad", "lwp_debug_dw_grad", "lwp_debug_loss_grad", "lwp_debug_relu_mask", "lwp_debug_grad_add", "lwp_debug_elu_grad",
     "lwp_debug_pw_fold", "lwp_debug_bn_chain",
+    "lwp_augment_batch", "lwp_time_augment_batch",
 ]
+
+
+class AugmentPlan(C.Structure):
+    """lwp_augment_plan of include/lwpose.h: the geometry of one sample of lwp_augment_batch."""
+    _fields_ = [("image", C.c_void_p), ("mask", C.c_void_p), ("rs_scale", C.c_double), ("m", C.c_double * 6), ("mem", C.c_int),
+                ("src_h", C.c_int), ("src_w", C.c_int), ("rs_h", C.c_int), ("rs_w", C.c_int), ("area", C.c_int),
+                ("bound_h", C.c_int), ("bound_w", C.c_int), ("should_crop", C.c_int),
+                ("dst_y0", C.c_int), ("dst_y1", C.c_int), ("dst_x0", C.c_int), ("dst_x1", C.c_int),
+                ("img_y0", C.c_int), ("img_x0", C.c_int), ("flip", C.c_int),
+                ("warp_pad", C.c_ubyte * 3), ("crop_pad", C.c_ubyte * 3)]
 
 
 class CapacityError(RuntimeError):
@@ -152,6 +163,8 @@ def lib():
     L.lwp_debug_elu_grad.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int]
     L.lwp_debug_pw_fold.argtypes = [vp] * 5 + [C.c_int] * 2
     L.lwp_debug_bn_chain.argtypes = [vp] * 12 + [C.c_int] * 3
+    L.lwp_augment_batch.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [vp, vp, vp]
+    L.lwp_time_augment_batch.argtypes = L.lwp_augment_batch.argtypes + [C.c_int, fp]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

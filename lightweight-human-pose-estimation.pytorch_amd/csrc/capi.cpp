@@ -98,6 +98,9 @@ struct lwp_context {
     // training targets and loss (lwp_train_targets / lwp_mask_downsample / lwp_stage_losses): staging of host key-points, person
     // counts and host masks; the loss partials followed by the per-stage sums
     DevBuf d_train, d_loss;
+    // training augmentation (lwp_augment_batch): [plan records | host images and masks], packed on the host, one upload a batch
+    DevBuf d_augment;
+    std::vector<unsigned char> augment_stage;
     // stage backward (lwp_train_forward / lwp_stage_backward; f32 handles): the retaining buffer plan, its activation and
     // gradient buffers, the gradient array's layout, the raw stage parameters (the BatchNorm chain rule needs them unfolded)
     TrainPlan tp;
@@ -231,7 +234,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 102; }
+extern "C" int lwp_version(void) { return 103; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -2305,6 +2308,95 @@ extern "C" int lwp_mask_downsample(lwp_handle h, const float* mask, int mem, int
     return LWP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- training augmentation
+// argument checks, then the batch's one upload: the plan records (their pointers rewritten to device addresses) followed by
+// every host image and mask; shared by lwp_augment_batch and lwp_time_augment_batch
+static int augment_prepare(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride, float* image_out,
+                           unsigned char* mask_out, float* mask_small_out, const lwp_augment_plan** plans_device) {
+    char msg[200];
+    if (!plans || !image_out || !mask_out || !mask_small_out) return fail(h, LWP_ERR_ARG, "plans / image_out / mask_out / mask_small_out is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    if (stride < 1 || stride > 1024) return fail(h, LWP_ERR_ARG, "stride must be 1..1024");
+    if (crop_h < 1 || crop_w < 1 || crop_h >= 32768 || crop_w >= 32768) return fail(h, LWP_ERR_ARG, "the crop must be 1..32767 pixels a side");
+    if (crop_h % stride || crop_w % stride) {
+        snprintf(msg, sizeof msg, "a %d x %d crop is not a whole number of %d x %d blocks", crop_h, crop_w, stride, stride);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    auto bad = [&](int f, const char* what) {
+        snprintf(msg, sizeof msg, "sample %d: %s", f, what);
+        return fail(h, LWP_ERR_ARG, msg);
+    };
+    auto dim_ok = [](int v) { return v >= 1 && v < 32768; };
+    size_t bytes = ((size_t)N * sizeof(lwp_augment_plan) + 15) & ~(size_t)15;
+    for (int f = 0; f < N; ++f) {
+        const lwp_augment_plan& p = plans[f];
+        if (!p.image) return bad(f, "the image is null");
+        if (p.mem != LWP_MEM_HOST && p.mem != LWP_MEM_DEVICE) return bad(f, "mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+        if (!dim_ok(p.src_h) || !dim_ok(p.src_w) || !dim_ok(p.rs_h) || !dim_ok(p.rs_w) || !dim_ok(p.bound_h) || !dim_ok(p.bound_w))
+            return bad(f, "a source, resized or bound size is outside 1..32767 (OpenCV saturates coordinates to short at 32768)");
+        if (!(p.rs_scale > 0) || !std::isfinite(p.rs_scale)) return bad(f, "rs_scale must be positive and finite");
+        for (int i = 0; i < 6; ++i)
+            if (!std::isfinite(p.m[i])) return bad(f, "a matrix value is not finite");
+        if ((p.area != 0 && p.area != 1) || (p.flip != 0 && p.flip != 1) || (p.should_crop != 0 && p.should_crop != 1))
+            return bad(f, "area, flip and should_crop must be 0 or 1");
+        if (p.should_crop) {
+            if (p.dst_y0 < 0 || p.dst_y1 < p.dst_y0 || p.dst_y1 > crop_h || p.dst_x0 < 0 || p.dst_x1 < p.dst_x0 || p.dst_x1 > crop_w)
+                return bad(f, "the dst rectangle lies outside the crop");
+            const int ny = p.dst_y1 - p.dst_y0, nx = p.dst_x1 - p.dst_x0;
+            if (ny > 0 && nx > 0 &&
+                (p.img_y0 < 0 || p.img_x0 < 0 || p.img_y0 + ny > p.bound_h || p.img_x0 + nx > p.bound_w))
+                return bad(f, "the dst rectangle's source lies outside the bound");
+        }
+        if (p.mem == LWP_MEM_HOST) {
+            bytes += ((size_t)p.src_h * p.src_w * 3 + 15) & ~(size_t)15;
+            if (p.mask) bytes += ((size_t)p.src_h * p.src_w * sizeof(float) + 15) & ~(size_t)15;
+        }
+    }
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = order_in(h);
+    if (rc) return rc;
+    if (h->d_augment.size() < bytes) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        HIP_TRY(h, h->d_augment.ensure(bytes));
+    }
+    h->augment_stage.resize(bytes);
+    unsigned char* host = h->augment_stage.data();
+    unsigned char* dev = h->d_augment.as<unsigned char>();
+    lwp_augment_plan* recs = reinterpret_cast<lwp_augment_plan*>(host);
+    size_t at = ((size_t)N * sizeof(lwp_augment_plan) + 15) & ~(size_t)15;
+    for (int f = 0; f < N; ++f) {
+        recs[f] = plans[f];
+        if (plans[f].mem != LWP_MEM_HOST) continue;
+        const size_t ib = (size_t)plans[f].src_h * plans[f].src_w * 3, mb = (size_t)plans[f].src_h * plans[f].src_w * sizeof(float);
+        memcpy(host + at, plans[f].image, ib);
+        recs[f].image = dev + at;
+        at += (ib + 15) & ~(size_t)15;
+        if (plans[f].mask) {
+            memcpy(host + at, plans[f].mask, mb);
+            recs[f].mask = reinterpret_cast<const float*>(dev + at);
+            at += (mb + 15) & ~(size_t)15;
+        }
+    }
+    HIP_TRY(h, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the staging vector and the caller's arrays are free from here on
+    *plans_device = reinterpret_cast<const lwp_augment_plan*>(dev);
+    return LWP_OK;
+}
+
+extern "C" int lwp_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride,
+                                 float* image_out, unsigned char* mask_out, float* mask_small_out) {
+    const lwp_augment_plan* d_plans = nullptr;
+    int rc = augment_prepare(h, plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, &d_plans);
+    if (rc) return rc;
+    LAUNCH(h, KC_OTHER, launch_augment(d_plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
 // argument checks and the partials buffer: everything of lwp_stage_losses before its launches, shared with lwp_time_stage_losses
 static int stage_losses_prepare(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
                                 const float* mask, int N, int hs, int ws, int batch_size) {
@@ -3624,6 +3716,17 @@ extern "C" int lwp_time_train_targets(lwp_handle h, const double* kpts, int kpts
                                    paf_maps_device, &p);
     if (rc) return rc;
     return time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_train_targets(p, N, h->stream)); return (int)LWP_OK; }, ms_total);
+}
+
+extern "C" int lwp_time_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride,
+                                      float* image_out, unsigned char* mask_out, float* mask_small_out, int iters, float* ms_total) {
+    if (!ms_total || iters <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    const lwp_augment_plan* d_plans = nullptr;
+    int rc = augment_prepare(h, plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, &d_plans);
+    if (rc) return rc;
+    return time_on_stream(h, iters, [&]() {
+        LAUNCH(h, KC_OTHER, launch_augment(d_plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, h->stream));
+        return (int)LWP_OK; }, ms_total);
 }
 
 extern "C" int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps,

@@ -396,6 +396,10 @@ struct TrainTargetsParams {
 };
 hipError_t launch_train_targets(const TrainTargetsParams& p, int N, hipStream_t s);
 hipError_t launch_mask_downsample(const float* src, int N, int H, int W, int stride, float* dst, hipStream_t s);
+// ---- training augmentation (augment_kernels.hip; datasets/transformations.py): one thread per crop pixel, then the small mask;
+// plans_device: N records whose image / mask pointers are device addresses
+hipError_t launch_augment(const lwp_augment_plan* plans_device, int N, int crop_h, int crop_w, int stride, float* image,
+                          unsigned char* mask, float* mask_small, hipStream_t s);
 struct StageLossParams {
     const float* outs[kLossMaxOuts];   // even: N x CH x hw heat-map tensors, odd: N x CP x hw PAF tensors; null = skipped
     int S;

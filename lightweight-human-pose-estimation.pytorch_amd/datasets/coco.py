@@ -3,8 +3,10 @@ key-point and PAF target maps and the down-sampled mask of ``CocoTrainDataset.__
 batch by ``lwp_train_targets`` / ``lwp_mask_downsample`` instead of the per-pixel Python loops of ``_add_gaussian`` /
 ``_set_paf``.
 
-Out of scope: reading images and annotations (``cv2.imread``, ``pycocotools``), ``get_mask`` and the augmentations of
-``datasets/transformations.py``.  Labels arrive in ``scripts/prepare_train_labels.py``'s format, already transformed.
+Out of scope: reading images and annotations (``cv2.imread``, ``pycocotools``) and ``get_mask``.  Labels arrive in
+``scripts/prepare_train_labels.py``'s format, as ``datasets.transformations`` (the augmentations, host classes and the device
+batch path) leaves them; ``generate_targets`` takes the float mask mean, ``val.augmented_train_step`` the reference's rounded
+uint8 mask.
 """
 import numpy as np
 

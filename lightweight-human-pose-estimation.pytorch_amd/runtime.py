@@ -715,6 +715,71 @@ class Engine(object):
         check(lib().lwp_mask_downsample(self.h.ptr, ptr, mem, N, H, W, stride, out.data_ptr()), self.h.ptr)
         return out[0] if single else out
 
+    # ------------------------------------------------------------------ training augmentation (datasets/transformations.py)
+    def augment_batch(self, samples_or_plan, transforms=None, rng=None, stride=8, time_iters=0):
+        """The pixels of a batch of augmented training samples in one kernel launch.  ``samples_or_plan``: a
+        ``datasets.transformations.BatchPlan``, or the raw samples with ``transforms`` (and ``rng``) for ``plan_batch``.
+        Sources may be NumPy arrays (packed, one upload for the batch) or cuda uint8 / float32 tensors (read in place).
+        Returns four cuda tensors: ``image`` (N, 3, cy, cx) float32 = (pixel - 128) / 256, ``mask`` (N, cy, cx) uint8,
+        ``mask_small`` (N, cy // stride, cx // stride) float32 (coco.py:48 on the uint8 mask) and ``kpts`` (N, Pmax, 18, 3)
+        float64, the transformed key-points as ``train_targets`` takes them (person counts: the plan's ``n_persons``).  With
+        ``time_iters`` > 0 the kernels are launched that many times back to back and the call returns their milliseconds."""
+        torch = _torch()
+        from ._lib import AugmentPlan
+        from .datasets.transformations import BatchPlan, plan_batch
+        if not isinstance(samples_or_plan, BatchPlan) and transforms is None:
+            raise ValueError("raw samples need the transforms to plan them with")
+        plan = samples_or_plan if isinstance(samples_or_plan, BatchPlan) else plan_batch(samples_or_plan, transforms, rng)
+        N = len(plan)
+        cy, cx = plan.crop_hw
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        dev = torch.device("cuda", self.device_id)
+        recs = (AugmentPlan * N)()
+        keep = []                                      # the arrays the records point into, alive until the call returns
+        for n, g in enumerate(plan.records):
+            img, msk = plan.images[n], plan.masks[n]
+            on_device = getattr(img, "is_cuda", False)
+            if msk is not None and getattr(msk, "is_cuda", False) != on_device:
+                raise ValueError("sample %d: the image and its mask must both be host arrays or both cuda tensors" % n)
+            if on_device:
+                if img.dtype != torch.uint8 or (msk is not None and msk.dtype != torch.float32):
+                    raise TypeError("sample %d: cuda sources must be a uint8 image and a float32 mask" % n)
+                img = img.detach().contiguous()
+                msk = None if msk is None else msk.detach().contiguous()
+                ip, mp = img.data_ptr(), (None if msk is None else msk.data_ptr())
+            else:
+                if np.asarray(img).dtype != np.uint8:
+                    raise TypeError("sample %d: the image must be uint8, got %s" % (n, np.asarray(img).dtype))
+                img = np.ascontiguousarray(img, dtype=np.uint8)
+                msk = None if msk is None else np.ascontiguousarray(msk, dtype=np.float32)
+                ip, mp = img.ctypes.data, (None if msk is None else msk.ctypes.data)
+            keep.append((img, msk))
+            r = recs[n]
+            r.image, r.mask, r.mem = ip, mp, (MEM_DEVICE if on_device else MEM_HOST)
+            r.rs_scale = float(g["rs_scale"])
+            for i in range(6):
+                r.m[i] = float(g["minv"][i])
+            r.src_h, r.src_w, r.rs_h, r.rs_w, r.area = g["src_h"], g["src_w"], g["rs_h"], g["rs_w"], int(g["area"])
+            r.bound_h, r.bound_w, r.should_crop = g["bound_h"], g["bound_w"], int(g["should_crop"])
+            r.dst_y0, r.dst_y1, r.dst_x0, r.dst_x1 = g["dst"]
+            r.img_y0, r.img_x0 = g["src0"]
+            r.flip = int(g["flip"])
+            for c in range(3):
+                r.warp_pad[c], r.crop_pad[c] = int(g["warp_pad"][c]), int(g["crop_pad"][c])
+        image = torch.empty((N, 3, cy, cx), dtype=torch.float32, device=dev)
+        mask = torch.empty((N, cy, cx), dtype=torch.uint8, device=dev)
+        small = torch.empty((N, cy // stride, cx // stride), dtype=torch.float32, device=dev)
+        self._order()
+        args = (self.h.ptr, recs, N, cy, cx, stride, image.data_ptr(), mask.data_ptr(), small.data_ptr())
+        if time_iters:
+            ms = C.c_float()
+            check(lib().lwp_time_augment_batch(*args, int(time_iters), C.byref(ms)), self.h.ptr)
+            return ms.value
+        check(lib().lwp_augment_batch(*args), self.h.ptr)
+        return image, mask, small, torch.from_numpy(plan.kpts).to(dev)
+
     def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
         """train.py:92-97's per-stage sums: ``outs`` is the list net(x) returned (cuda tensors; an entry may be None),
         ``keypoint_maps`` / ``paf_maps`` the targets, ``mask`` one (N, h, w) cuda tensor broadcast over the channels.

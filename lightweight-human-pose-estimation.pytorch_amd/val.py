@@ -162,6 +162,38 @@ def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=
     return losses
 
 
+def augmented_train_step(net, opt, samples, augment, batches_per_iter=1, sigma=7, paf_thickness=1):
+    """``train_step`` from RAW samples (image uint8 (H, W, 3), mask float32 (H, W) or None, label dict): ``augment``, a
+    ``datasets.transformations.DeviceAugment``, draws the random numbers and moves the labels on the host and renders the
+    crops on the GPU; its ``image``, ``kpts`` and ``mask_small`` feed the same targets, retaining forward, losses, backward
+    and optimiser step as ``train_step``.  The small mask is the reference's (coco.py:48 on the uint8 mask CropPad leaves,
+    rounded to 0 / 1), not the float mean of ``Engine.mask_downsample``.  Returns the batch's stage losses."""
+    if opt.net is not net:
+        raise ValueError("opt is not an optimiser of this net")
+    batches_per_iter = int(batches_per_iter)
+    if batches_per_iter < 1:
+        raise ValueError("batches_per_iter must be at least 1")
+    eng = net.engine
+    batch = augment(samples, engine=eng)
+    x = batch["image"]
+    if opt.batch_index == 0:
+        opt.zero_grad()
+    outs = eng.train_forward(x)
+    kmaps, pmaps = eng.train_targets(batch["kpts"], batch["n_persons"], (int(x.shape[2]), int(x.shape[3])), augment.stride, sigma, paf_thickness)
+    if tuple(outs[0].shape[2:]) != tuple(kmaps.shape[2:]):
+        raise ValueError("the network's maps are %s but the targets %s: the crop must be a multiple of the network's stride"
+                         % (tuple(outs[0].shape[2:]), tuple(kmaps.shape[2:])))
+    mask = batch["mask_small"]
+    losses = eng.stage_losses(outs, kmaps, pmaps, mask, None)
+    grads, _ = eng.stage_backward(kmaps, pmaps, mask, None, 1.0 / batches_per_iter, opt.accumulated)
+    opt.accumulated = eng.flat_of(grads)
+    opt.batch_index += 1
+    if opt.batch_index >= batches_per_iter:
+        opt.step(opt.accumulated)
+        opt.batch_index = 0
+    return losses
+
+
 # ---------------------------------------------------------------------------------------------- COCO results
 # slot of each of the 18 network key-points in COCO's 17-key-point order (the neck, index 1, has none)
 _COCO_SLOT = (0, None, 6, 8, 10, 5, 7, 9, 12, 14, 16, 11, 13, 15, 2, 1, 4, 3)

@@ -1,0 +1,116 @@
+"""GPU: the augmentation kernel (csrc/augment_kernels.hip) through Engine.augment_batch against the recorded reference runs
+(tests/golden/augment_cases.npz) and against the staged NumPy route, bit for bit — everything is integer or fixed-order
+float32, so no differing element is allowed — and val.augmented_train_step against train_step fed the host-augmented batch."""
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import lwpose_amd  # noqa: F401
+from lwpose_amd import optim, synth, val
+from lwpose_amd.datasets import transformations as T
+from lwpose_amd.models.with_mobilenet import PoseEstimationWithMobileNet
+from lwpose_amd.modules.load_state import load_state
+from lwpose_amd.runtime import Engine
+
+import augment_cases as ac
+
+pytestmark = pytest.mark.gpu
+PAD = (128, 128, 128)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    return Engine(0, nref=1, num_channels=32)          # the augmentation needs no weights
+
+
+def assert_same(got, want):
+    """(image, mask, mask_small[, kpts]) cuda tensors against the host arrays: zero differing elements."""
+    for name, g, w in zip(("image", "mask", "mask_small"), got, want):
+        g = g.cpu().numpy()
+        assert g.dtype == w.dtype and g.shape == w.shape, name
+        assert int((g != w).sum()) == 0, "%s: %d elements differ" % (name, int((g != w).sum()))
+
+
+def test_every_fixture_case_is_bit_equal(eng):
+    for i in range(ac.n_cases()):
+        sample, transforms, seed, exp = ac.case(i)
+        random.seed(seed)
+        got = eng.augment_batch([sample], transforms)
+        assert_same(got, (ac.network_image(exp["image"])[None], exp["mask"][None], exp["mask_small"][None]))
+        assert got[3].dtype == torch.float64 and np.array_equal(got[3][0, :len(exp["kpts"])].cpu().numpy(), exp["kpts"])
+
+
+def test_a_mixed_batch_equals_the_host_path_sample_by_sample(eng):
+    """33 samples of different sizes, None and float masks, host and cuda sources, crop 40 x 72: more than one tile each way
+    and a ragged edge in both for any tile of 64 or fewer columns and fewer than 40 rows."""
+    g = np.random.default_rng(17)
+    samples = []
+    for n in range(33):
+        s = ac.synthetic_sample(500 + n, int(g.integers(9, 25)), int(g.integers(9, 25)), others=n % 3,
+                                scale_provided=float(g.uniform(0.12, 0.4)), with_mask=n % 3 != 1)
+        if n % 4 == 2:                                 # resident in device memory: read in place
+            s["image"] = torch.from_numpy(s["image"]).cuda()
+            s["mask"] = None if s["mask"] is None else torch.from_numpy(s["mask"]).cuda()
+        samples.append(s)
+    transforms = [T.ConvertKeypoints(), T.Scale(), T.Rotate(pad=PAD), T.CropPad(pad=(1, 2, 3), center_perterb_max=10, crop_x=72, crop_y=40),
+                  T.Flip()]
+    plan = T.plan_batch(samples, transforms, random.Random(33))
+    assert {bool(r["flip"]) for r in plan.records} == {False, True}
+    want = T.apply_plan_host(plan, 8)
+    assert 0 < int((want[1] == 0).sum()) and np.any(want[2] == 0) and np.any(want[2] == 1)
+    got = eng.augment_batch(plan)
+    assert tuple(got[0].shape) == (33, 3, 40, 72) and tuple(got[2].shape) == (33, 5, 9)
+    for n in range(33):
+        assert_same([t[n] for t in got[:3]], [w[n] for w in want])
+
+
+def test_a_six_fold_enlargement_equals_the_staged_host_path(eng):
+    """scale_provided = 0.1 with the multiplier off: fx = 6.  The staged route builds the 6 x image and warps all of it; the
+    kernel reads the source only."""
+    s = ac.synthetic_sample(77, 37, 52, others=1, scale_provided=0.1)
+    transforms = [T.ConvertKeypoints(), T.Scale(prob=0), T.Rotate(pad=PAD), T.CropPad(pad=PAD, crop_x=72, crop_y=40), T.Flip()]
+    plan = T.plan_batch([s], transforms, random.Random(6))
+    assert abs(plan.records[0]["scale"] - 6.0) < 1e-9 and (plan.records[0]["rs_h"], plan.records[0]["rs_w"]) == (222, 312)
+    want = T.apply_plan_host(plan, 8)
+    assert float(np.all(want[0][0] == 0, axis=0).mean()) < 0.5           # mostly picture, not pad
+    assert_same(eng.augment_batch(plan)[:3], want)
+
+
+def test_device_augment_front_end_and_the_time_twin(eng):
+    s = [ac.synthetic_sample(90 + n, 20, 26, scale_provided=0.3) for n in range(3)]
+    transforms = [T.ConvertKeypoints(), T.Scale(), T.Rotate(pad=PAD), T.CropPad(pad=PAD, center_perterb_max=4, crop_x=32, crop_y=24), T.Flip()]
+    out = T.DeviceAugment(transforms, eng, rng=random.Random(2))(s)
+    want = T.apply_plan_host(T.plan_batch(s, transforms, random.Random(2)), 8)
+    assert_same((out["image"], out["mask"], out["mask_small"]), want)
+    assert out["kpts"].shape == (3, 2, 18, 3) and out["n_persons"].tolist() == [2, 2, 2] and len(out["labels"]) == 3
+    ms = eng.augment_batch(out["plan"], time_iters=3)
+    assert ms > 0
+
+
+def make_net(seed=21):
+    sd = synth.make_state_dict(1, seed=seed, num_channels=32, num_heatmaps=19, num_pafs=38)
+    net = PoseEstimationWithMobileNet(num_refinement_stages=1, num_channels=32, num_heatmaps=19, num_pafs=38)
+    load_state(net, {"state_dict": sd})
+    net.eval().cuda()
+    return net
+
+
+def test_augmented_train_step_equals_train_step_on_the_host_augmented_batch():
+    samples = [ac.synthetic_sample(300 + n, 30 + 4 * n, 41 - 3 * n, others=n, scale_provided=0.5) for n in range(2)]
+    transforms = [T.ConvertKeypoints(), T.Scale(), T.Rotate(pad=PAD), T.CropPad(pad=PAD, center_perterb_max=5, crop_x=32, crop_y=32), T.Flip()]
+    net_a, net_b = make_net(), make_net()
+    opt_a, opt_b = optim.StageAdam(net_a, base_lr=1e-3), optim.StageAdam(net_b, base_lr=1e-3)
+    losses_a = val.augmented_train_step(net_a, opt_a, samples, T.DeviceAugment(transforms, rng=random.Random(9)))
+    plan = T.plan_batch(samples, transforms, random.Random(9))
+    image, mask, small = T.apply_plan_host(plan, 8)
+    assert np.any(small == 0) and np.any(small == 1)                     # the mask takes part in the loss
+    losses_b = val.train_step(net_b, opt_b, image, plan.labels, np.repeat(np.repeat(small, 8, 1), 8, 2))
+    assert losses_a == losses_b and all(np.isfinite(losses_a)) and sum(losses_a) > 0
+    assert opt_a.steps == opt_b.steps == 1
+    flat_a = net_a.engine.flat_of(net_a.engine.stage_params())
+    flat_b = net_b.engine.flat_of(net_b.engine.stage_params())
+    assert torch.equal(flat_a, flat_b)
+    start = make_net().engine
+    assert not torch.equal(flat_a, start.flat_of(start.stage_params()))  # the step moved the parameters
