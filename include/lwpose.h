@@ -632,6 +632,39 @@ int lwp_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int cr
 int lwp_time_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride, float* image_out,
                            unsigned char* mask_out, float* mask_small_out, int iters, float* ms_total);
 
+/* ---- COCO key-point evaluation: replaces pycocotools' COCOeval(gt, dt, 'keypoints') evaluate() + accumulate() behind
+ *      val.py:17-27, with COCOeval's default parameters (the 17 OKS sigmas, IoU thresholds 0.5:0.05:0.95, 101 recall
+ *      thresholds, maxDets 20, area ranges all [0, 1e10] / medium [32^2, 96^2] / large [96^2, 1e10], inclusive at both ends) and
+ *      ONE category.  All arithmetic is float64 on the GPU (csrc/eval_kernels.hip); summarize() is a mean over the
+ *      returned arrays and stays with the caller (val.run_coco_eval).
+ *      Inputs (HOST), CSR over n_images images in ascending image id: image i owns detections dt_off[i] .. dt_off[i + 1] - 1 and
+ *      ground truths gt_off[i] .. gt_off[i + 1] - 1, each in its file's order (ties in score keep it).
+ *        dt_kp [ND][17][3], dt_score [ND]      x, y and a third value that is not read; the detection's area is the box of all
+ *                       17 (x, y), zeros of missing key-points included, as loadRes computes it
+ *        gt_kp [NG][17][3]                     x, y, visibility (visible: > 0)
+ *        gt_area [NG], gt_bbox [NG][4], gt_iscrowd [NG], gt_ignore [NG]   gt_ignore is COCOeval's _prepare flag: iscrowd or
+ *                       num_keypoints == 0
+ *      Per image: the 20 best detections (stable), their OKS against every ground truth, and for each of the 3 x 10 (range,
+ *      threshold) pairs COCOeval's greedy matching.  Over the data set: the selected detections in descending score order
+ *      (stable), the running tp / fp counts, precision's running maximum from the end and the 101 recall look-ups.
+ *      Outputs (HOST): precision [10][101][3] and scores [10][101][3] indexed [threshold][recall][range], recall [10][3],
+ *      npig [3] (ground truths that count per range).  A range with npig == 0 holds -1 throughout.
+ *      Checks before any launch (h == NULL too, LWP_ERR_ARG): null pointers (an array with no element may be NULL),
+ *      n_images >= 1, offsets that start at 0 and never descend, fewer than 2^31 detections and ground truths, finite scores,
+ *      coordinates, areas and boxes.  One upload, the kernels on the handle's stream, one copy back; every byte of scratch is
+ *      released before the call returns.  Needs no weights.  Two calls on the same input return the same bits. */
+int lwp_coco_eval(lwp_handle h, int n_images, const int64_t* dt_off, const double* dt_kp, const double* dt_score,
+                  const int64_t* gt_off, const double* gt_kp, const double* gt_area, const double* gt_bbox, const int* gt_iscrowd,
+                  const int* gt_ignore, double* precision, double* recall, double* scores, int64_t* npig);
+/* the per-image half alone, for tests: the same inputs and checks, then for image `image`: n_sel = min(D, 20) and order[r], the
+ * index within the image of the detection at rank r; oks [n_sel][G] row-major, columns in input ground-truth order (oks_cap
+ * doubles available, LWP_ERR_CAPACITY below n_sel * G); matched / ignored [30][20] bytes indexed [range * 10 + threshold][rank]
+ * (ranks from n_sel on are 0); npig3 [3], the image's ground truths that count per range. */
+int lwp_debug_coco_oks(lwp_handle h, int n_images, const int64_t* dt_off, const double* dt_kp, const double* dt_score,
+                       const int64_t* gt_off, const double* gt_kp, const double* gt_area, const double* gt_bbox, const int* gt_iscrowd,
+                       const int* gt_ignore, int image, int* n_sel, int* order, double* oks, int64_t oks_cap, unsigned char* matched,
+                       unsigned char* ignored, int* npig3);
+
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */
 int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio,

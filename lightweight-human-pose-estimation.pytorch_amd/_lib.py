@@ -38,6 +38,7 @@ EXPORTS = [
     "lwp_debug_conv_grad", "lwp_debug_dw_grad", "lwp_debug_loss_grad", "lwp_debug_relu_mask", "lwp_debug_grad_add", "lwp_debug_elu_grad",
     "lwp_debug_pw_fold", "lwp_debug_bn_chain",
     "lwp_augment_batch", "lwp_time_augment_batch",
+    "lwp_coco_eval", "lwp_debug_coco_oks",
 ]
 
 
@@ -165,6 +166,9 @@ def lib():
     L.lwp_debug_bn_chain.argtypes = [vp] * 12 + [C.c_int] * 3
     L.lwp_augment_batch.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [vp, vp, vp]
     L.lwp_time_augment_batch.argtypes = L.lwp_augment_batch.argtypes + [C.c_int, fp]
+    coco_in = [vp, C.c_int, i64p, dp, dp, i64p, dp, dp, dp, ip, ip]
+    L.lwp_coco_eval.argtypes = coco_in + [dp, dp, dp, i64p]
+    L.lwp_debug_coco_oks.argtypes = coco_in + [C.c_int, ip, ip, dp, C.c_int64, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), ip]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -234,7 +234,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 103; }
+extern "C" int lwp_version(void) { return 104; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -2394,6 +2394,194 @@ extern "C" int lwp_augment_batch(lwp_handle h, const lwp_augment_plan* plans, in
     rc = order_out(h, h->stream, &ordered);
     if (rc) return rc;
     if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- COCO key-point evaluation
+// the device memory of one evaluation: released when it goes out of scope, whatever way the call ends
+struct CocoEvalRun {
+    DevBuf in, scratch;
+    CocoEvalParams p{};
+    std::vector<int64_t> sel_off, oks_off;
+    // the accumulation's order (not needed by the debug twin)
+    unsigned long long *keys = nullptr, *keys_out = nullptr;
+    unsigned int *vals = nullptr, *perm = nullptr;
+    void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
+};
+
+struct CocoEvalInput {
+    int n_images;
+    const int64_t* dt_off; const double* dt_kp; const double* dt_score;
+    const int64_t* gt_off; const double* gt_kp; const double* gt_area; const double* gt_bbox; const int* gt_iscrowd; const int* gt_ignore;
+};
+
+static int coco_eval_check(lwp_handle h, const CocoEvalInput& in) {
+    char msg[200];
+    if (!in.dt_off || !in.gt_off) return fail(h, LWP_ERR_ARG, "dt_off / gt_off is null");
+    if (in.n_images < 1) return fail(h, LWP_ERR_ARG, "n_images must be at least 1");
+    const int64_t lim = (int64_t)1 << 31;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int64_t* off = pass ? in.gt_off : in.dt_off;
+        const char* what = pass ? "gt_off" : "dt_off";
+        if (off[0] != 0) { snprintf(msg, sizeof msg, "%s[0] must be 0", what); return fail(h, LWP_ERR_ARG, msg); }
+        for (int i = 0; i < in.n_images; ++i)
+            if (off[i + 1] < off[i]) { snprintf(msg, sizeof msg, "%s descends at image %d", what, i); return fail(h, LWP_ERR_ARG, msg); }
+        if (off[in.n_images] >= lim) { snprintf(msg, sizeof msg, "%s: 2^31 rows or more", what); return fail(h, LWP_ERR_ARG, msg); }
+    }
+    const int64_t ND = in.dt_off[in.n_images], NG = in.gt_off[in.n_images];
+    if (ND > 0 && (!in.dt_kp || !in.dt_score)) return fail(h, LWP_ERR_ARG, "dt_kp / dt_score is null");
+    if (NG > 0 && (!in.gt_kp || !in.gt_area || !in.gt_bbox || !in.gt_iscrowd || !in.gt_ignore))
+        return fail(h, LWP_ERR_ARG, "gt_kp / gt_area / gt_bbox / gt_iscrowd / gt_ignore is null");
+    auto finite = [](const double* v, int64_t n) {
+        for (int64_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (!finite(in.dt_score, ND)) return fail(h, LWP_ERR_ARG, "a detection score is not finite");
+    if (!finite(in.dt_kp, ND * kEvalK * 3)) return fail(h, LWP_ERR_ARG, "a detection coordinate is not finite");
+    if (!finite(in.gt_kp, NG * kEvalK * 3)) return fail(h, LWP_ERR_ARG, "a ground-truth coordinate is not finite");
+    if (!finite(in.gt_area, NG)) return fail(h, LWP_ERR_ARG, "a ground-truth area is not finite");
+    if (!finite(in.gt_bbox, NG * 4)) return fail(h, LWP_ERR_ARG, "a ground-truth box is not finite");
+    return LWP_OK;
+}
+
+// checks, the one upload, scratch, and the per-image kernel; with_order: the sort buffers of the accumulation too
+static int coco_eval_match(lwp_handle h, const CocoEvalInput& in, bool with_order, CocoEvalRun* run) {
+    int rc = coco_eval_check(h, in);
+    if (rc) return rc;
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    const int n = in.n_images;
+    const int64_t ND = in.dt_off[n], NG = in.gt_off[n];
+    run->sel_off.assign((size_t)n + 1, 0);
+    run->oks_off.assign((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        const int64_t D = in.dt_off[i + 1] - in.dt_off[i], G = in.gt_off[i + 1] - in.gt_off[i];
+        const int64_t Ds = std::min<int64_t>(D, kEvalMaxDets);
+        run->sel_off[i + 1] = run->sel_off[i] + Ds;
+        run->oks_off[i + 1] = run->oks_off[i] + Ds * G;
+    }
+    const int64_t NS = run->sel_off[n], NO = run->oks_off[n];
+    CocoEvalParams& p = run->p;
+    coco_eval_defaults(&p);
+    p.n_images = n; p.NG = NG; p.NS = NS;
+
+    // sections of the two allocations, each 16-byte aligned
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
+    const size_t i_dt_off = take(nb), i_gt_off = take(nb), i_sel_off = take(nb), i_oks_off = take(nb);
+    const size_t i_dt_kp = take((size_t)ND * kEvalK * 3 * 8), i_dt_score = take((size_t)ND * 8);
+    const size_t i_gt_kp = take((size_t)NG * kEvalK * 3 * 8), i_gt_area = take((size_t)NG * 8), i_gt_bbox = take((size_t)NG * 4 * 8);
+    const size_t i_gt_crowd = take((size_t)NG * 4), i_gt_ignore = take((size_t)NG * 4);
+    const size_t in_bytes = std::max<size_t>(at, 16);
+    std::vector<unsigned char> stage(in_bytes);
+    auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(stage.data() + off, src, bytes); };
+    put(i_dt_off, in.dt_off, nb); put(i_gt_off, in.gt_off, nb); put(i_sel_off, run->sel_off.data(), nb); put(i_oks_off, run->oks_off.data(), nb);
+    put(i_dt_kp, in.dt_kp, (size_t)ND * kEvalK * 3 * 8); put(i_dt_score, in.dt_score, (size_t)ND * 8);
+    put(i_gt_kp, in.gt_kp, (size_t)NG * kEvalK * 3 * 8); put(i_gt_area, in.gt_area, (size_t)NG * 8); put(i_gt_bbox, in.gt_bbox, (size_t)NG * 4 * 8);
+    put(i_gt_crowd, in.gt_iscrowd, (size_t)NG * 4); put(i_gt_ignore, in.gt_ignore, (size_t)NG * 4);
+
+    at = 0;
+    const size_t s_gt_m = take((size_t)kEvalAT * NG);                       // first: the part that is zeroed
+    const size_t zero_bytes = at;
+    const size_t s_sel_idx = take((size_t)NS * 4), s_sel_score = take((size_t)NS * 8), s_oks = take((size_t)NO * 8);
+    const size_t s_gt_flag = take((size_t)NG), s_dt_m = take((size_t)kEvalAT * NS), s_dt_ig = take((size_t)kEvalAT * NS);
+    const size_t s_npig_img = take((size_t)n * kEvalA * 4);
+    const size_t s_out = take(((size_t)2 * kEvalT * kEvalR * kEvalA + kEvalT * kEvalA) * 8 + kEvalA * 8);
+    size_t s_keys = 0, s_keys_out = 0, s_vals = 0, s_perm = 0, s_tpfp = 0, s_pr = 0, s_tmp = 0;
+    if (with_order) {
+        HIP_TRY(h, coco_sort_temp_bytes(NS, &run->sort_tmp_bytes));
+        s_keys = take((size_t)NS * 8); s_keys_out = take((size_t)NS * 8); s_vals = take((size_t)NS * 4); s_perm = take((size_t)NS * 4);
+        s_tpfp = take((size_t)kEvalAT * NS * 8); s_pr = take((size_t)kEvalAT * NS * 8);
+        s_tmp = take(run->sort_tmp_bytes);
+    }
+    const size_t scratch_bytes = std::max<size_t>(at, 16);
+    HIP_TRY(h, run->in.ensure(in_bytes));
+    HIP_TRY(h, run->scratch.ensure(scratch_bytes));
+    unsigned char* di = run->in.as<unsigned char>();
+    unsigned char* ds = run->scratch.as<unsigned char>();
+    HIP_TRY(h, hipMemcpyAsync(di, stage.data(), in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (zero_bytes) HIP_TRY(h, hipMemsetAsync(ds + s_gt_m, 0, zero_bytes, h->stream));
+    p.dt_off = (const int64_t*)(di + i_dt_off); p.gt_off = (const int64_t*)(di + i_gt_off);
+    p.sel_off = (const int64_t*)(di + i_sel_off); p.oks_off = (const int64_t*)(di + i_oks_off);
+    p.dt_kp = (const double*)(di + i_dt_kp); p.dt_score = (const double*)(di + i_dt_score);
+    p.gt_kp = (const double*)(di + i_gt_kp); p.gt_area = (const double*)(di + i_gt_area); p.gt_bbox = (const double*)(di + i_gt_bbox);
+    p.gt_iscrowd = (const int*)(di + i_gt_crowd); p.gt_ignore = (const int*)(di + i_gt_ignore);
+    p.gt_m = ds + s_gt_m; p.sel_idx = (int*)(ds + s_sel_idx); p.sel_score = (double*)(ds + s_sel_score); p.oks = (double*)(ds + s_oks);
+    p.gt_flag = ds + s_gt_flag; p.dt_m = ds + s_dt_m; p.dt_ig = ds + s_dt_ig; p.npig_img = (int*)(ds + s_npig_img);
+    p.precision = (double*)(ds + s_out); p.scores = p.precision + kEvalT * kEvalR * kEvalA;
+    p.recall = p.scores + kEvalT * kEvalR * kEvalA; p.npig = (long long*)(p.recall + kEvalT * kEvalA);
+    if (with_order) {
+        run->keys = (unsigned long long*)(ds + s_keys); run->keys_out = (unsigned long long*)(ds + s_keys_out);
+        run->vals = (unsigned int*)(ds + s_vals); run->perm = (unsigned int*)(ds + s_perm);
+        run->sort_tmp = ds + s_tmp;
+        p.perm = run->perm; p.tpfp = (unsigned long long*)(ds + s_tpfp); p.pr = (double*)(ds + s_pr);
+    }
+    LAUNCH(h, KC_OTHER, launch_coco_match(p, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the staging vector is free from here on; a fault of the kernel is reported here
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_eval(lwp_handle h, int n_images, const int64_t* dt_off, const double* dt_kp, const double* dt_score,
+                             const int64_t* gt_off, const double* gt_kp, const double* gt_area, const double* gt_bbox,
+                             const int* gt_iscrowd, const int* gt_ignore, double* precision, double* recall, double* scores,
+                             int64_t* npig) {
+    if (!precision || !recall || !scores || !npig) return fail(h, LWP_ERR_ARG, "precision / recall / scores / npig is null");
+    const CocoEvalInput in{n_images, dt_off, dt_kp, dt_score, gt_off, gt_kp, gt_area, gt_bbox, gt_iscrowd, gt_ignore};
+    CocoEvalRun run;
+    int rc = coco_eval_match(h, in, true, &run);
+    if (rc) return rc;
+    const CocoEvalParams& p = run.p;
+    LAUNCH(h, KC_OTHER, launch_coco_sort(p.sel_score, p.NS, run.keys, run.keys_out, run.vals, run.perm, run.sort_tmp, run.sort_tmp_bytes, h->stream));
+    LAUNCH(h, KC_OTHER, launch_coco_accumulate(p, h->stream));
+    // precision | scores | recall | npig lie back to back
+    const size_t n_pr = (size_t)kEvalT * kEvalR * kEvalA, n_rc = (size_t)kEvalT * kEvalA;
+    std::vector<double> out(2 * n_pr + n_rc + kEvalA);
+    HIP_TRY(h, hipMemcpyAsync(out.data(), p.precision, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    memcpy(precision, out.data(), n_pr * sizeof(double));
+    memcpy(scores, out.data() + n_pr, n_pr * sizeof(double));
+    memcpy(recall, out.data() + 2 * n_pr, n_rc * sizeof(double));
+    long long np3[kEvalA];
+    memcpy(np3, out.data() + 2 * n_pr + n_rc, sizeof np3);
+    for (int a = 0; a < kEvalA; ++a) npig[a] = (int64_t)np3[a];
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_coco_oks(lwp_handle h, int n_images, const int64_t* dt_off, const double* dt_kp, const double* dt_score,
+                                  const int64_t* gt_off, const double* gt_kp, const double* gt_area, const double* gt_bbox,
+                                  const int* gt_iscrowd, const int* gt_ignore, int image, int* n_sel, int* order, double* oks,
+                                  int64_t oks_cap, unsigned char* matched, unsigned char* ignored, int* npig3) {
+    if (!n_sel || !order || !matched || !ignored || !npig3) return fail(h, LWP_ERR_ARG, "n_sel / order / matched / ignored / npig3 is null");
+    const CocoEvalInput in{n_images, dt_off, dt_kp, dt_score, gt_off, gt_kp, gt_area, gt_bbox, gt_iscrowd, gt_ignore};
+    int rc = coco_eval_check(h, in);
+    if (rc) return rc;
+    if (image < 0 || image >= n_images) return fail(h, LWP_ERR_ARG, "image out of range");
+    const int64_t D = dt_off[image + 1] - dt_off[image], G = gt_off[image + 1] - gt_off[image];
+    const int Ds = (int)std::min<int64_t>(D, kEvalMaxDets);
+    if (oks_cap < 0 || (int64_t)Ds * G > oks_cap) return fail(h, LWP_ERR_CAPACITY, "oks_cap is below n_sel * G");
+    if (Ds * G > 0 && !oks) return fail(h, LWP_ERR_ARG, "oks is null");
+    CocoEvalRun run;
+    rc = coco_eval_match(h, in, false, &run);
+    if (rc) return rc;
+    const CocoEvalParams& p = run.p;
+    const int64_t s0 = run.sel_off[image], o0 = run.oks_off[image];
+    *n_sel = Ds;
+    memset(matched, 0, (size_t)kEvalAT * kEvalMaxDets);
+    memset(ignored, 0, (size_t)kEvalAT * kEvalMaxDets);
+    for (int r = 0; r < kEvalMaxDets; ++r) order[r] = -1;
+    HIP_TRY(h, hipMemcpyAsync(npig3, p.npig_img + (size_t)image * kEvalA, kEvalA * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (Ds > 0) {
+        HIP_TRY(h, hipMemcpyAsync(order, p.sel_idx + s0, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (G > 0) HIP_TRY(h, hipMemcpyAsync(oks, p.oks + o0, (size_t)Ds * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        for (int at = 0; at < kEvalAT; ++at) {
+            HIP_TRY(h, hipMemcpyAsync(matched + at * kEvalMaxDets, p.dt_m + (size_t)at * p.NS + s0, (size_t)Ds, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(ignored + at * kEvalMaxDets, p.dt_ig + (size_t)at * p.NS + s0, (size_t)Ds, hipMemcpyDeviceToHost, h->stream));
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return LWP_OK;
 }
 

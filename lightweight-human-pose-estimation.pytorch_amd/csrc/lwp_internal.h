@@ -400,6 +400,46 @@ hipError_t launch_mask_downsample(const float* src, int N, int H, int W, int str
 // plans_device: N records whose image / mask pointers are device addresses
 hipError_t launch_augment(const lwp_augment_plan* plans_device, int N, int crop_h, int crop_w, int stride, float* image,
                           unsigned char* mask, float* mask_small, hipStream_t s);
+// ---- COCO key-point evaluation (eval_kernels.hip; COCOeval with iouType 'keypoints' and its default parameters): float64
+constexpr int kEvalK = 17;            // key-points of a person
+constexpr int kEvalMaxDets = 20;      // detections of an image that count (maxDets)
+constexpr int kEvalT = 10, kEvalR = 101, kEvalA = 3;      // IoU thresholds, recall thresholds, area ranges
+constexpr int kEvalAT = kEvalA * kEvalT;                  // independent matchings of an image; (range, threshold) = (at / 10, at % 10)
+constexpr int kEvalScanChunk = 256;   // detections one step of the accumulate kernel's scans covers (one per thread, then a carry)
+struct CocoEvalParams {
+    int n_images;
+    int64_t NG, NS;                   // ground truths and selected detections (at most 20 an image) of the dataset
+    // inputs, CSR over the images: detections [dt_off[i], dt_off[i + 1]), ground truths likewise
+    const int64_t *dt_off, *gt_off;
+    const int64_t *sel_off, *oks_off; // [n_images + 1]: first selected detection and first OKS entry of an image
+    const double *dt_kp, *dt_score;   // [ND][17][3], [ND]
+    const double *gt_kp, *gt_area, *gt_bbox;      // [NG][17][3], [NG], [NG][4]
+    const int *gt_iscrowd, *gt_ignore;            // [NG]
+    // per-image results
+    int* sel_idx;                     // [NS] index within its image of the detection at each rank
+    double* sel_score;                // [NS]
+    double* oks;                      // per image [min(D, 20)][G], columns in input GT order
+    unsigned char* gt_flag;           // [NG] bit 0: crowd, bit 1 + a: ignored in range a
+    unsigned char* gt_m;              // [30][NG] matched so far (zeroed before the launch)
+    unsigned char *dt_m, *dt_ig;      // [30][NS] matched / ignored
+    int* npig_img;                    // [n_images][3] GTs not ignored per range
+    // accumulate
+    const unsigned int* perm;         // [NS] selected detections by descending score, stable
+    unsigned long long* tpfp;         // [30][NS] inclusive counts: tp in the low, fp in the high 32 bits
+    double* pr;                       // [30][NS] precision, then its reverse running maximum
+    double *precision, *recall, *scores;          // [10][101][3], [10][3], [10][101][3]
+    long long* npig;                  // [3]
+    // COCOeval's default parameters, computed once on the host as NumPy does
+    double vars[kEvalK], iou_thr[kEvalT], rec_thr[kEvalR], area_lo[kEvalA], area_hi[kEvalA];
+};
+void coco_eval_defaults(CocoEvalParams* p);
+hipError_t launch_coco_match(const CocoEvalParams& p, hipStream_t s);
+// the order of the accumulation: keys and values in, sorted out; tmp / tmp_bytes as coco_sort_temp_bytes says
+hipError_t coco_sort_temp_bytes(int64_t NS, size_t* bytes);
+hipError_t launch_coco_sort(const double* sel_score, int64_t NS, unsigned long long* keys, unsigned long long* keys_out,
+                            unsigned int* vals, unsigned int* perm, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_coco_accumulate(const CocoEvalParams& p, hipStream_t s);
+
 struct StageLossParams {
     const float* outs[kLossMaxOuts];   // even: N x CH x hw heat-map tensors, odd: N x CP x hw PAF tensors; null = skipped
     int S;

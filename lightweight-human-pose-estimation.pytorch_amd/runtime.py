@@ -1263,6 +1263,112 @@ class Engine(object):
         return {n: {"ms": ms[i], "launches": ln[i]} for i, n in enumerate(names)}
 
 
+    # ------------------------------------------------------------------ COCO key-point evaluation (val.py:17-27)
+    @staticmethod
+    def _coco_args(packed):
+        i64p, dp, ip = C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int)
+
+        def ptr(a, t):
+            return a.ctypes.data_as(t) if a.size else None
+        return (int(packed["n_images"]), packed["dt_off"].ctypes.data_as(i64p), ptr(packed["dt_kp"], dp), ptr(packed["dt_score"], dp),
+                packed["gt_off"].ctypes.data_as(i64p), ptr(packed["gt_kp"], dp), ptr(packed["gt_area"], dp), ptr(packed["gt_bbox"], dp),
+                ptr(packed["gt_iscrowd"], ip), ptr(packed["gt_ignore"], ip))
+
+    def coco_eval(self, gt, detections=None):
+        """COCOeval(gt, loadRes(detections), 'keypoints') evaluate() + accumulate() on the GPU with COCOeval's default
+        parameters.  ``gt``: a COCO ground-truth dict ('images', 'annotations', 'categories') with ``detections`` the list of
+        result dicts (``val.coco_detections``), or the arrays ``coco_pack`` made of the two.  Returns a dict: ``precision``
+        (10, 101, 3) and ``scores`` (10, 101, 3) indexed [IoU threshold, recall threshold, area range], ``recall`` (10, 3),
+        ``npig`` (3,) and ``stats``, the ten numbers of summarize().  Two calls on the same input return the same bits."""
+        packed = gt if detections is None and "dt_off" in gt else coco_pack(gt, detections)
+        precision = np.empty((10, 101, 3), dtype=np.float64)
+        scores = np.empty((10, 101, 3), dtype=np.float64)
+        recall = np.empty((10, 3), dtype=np.float64)
+        npig = np.zeros(3, dtype=np.int64)
+        dp = C.POINTER(C.c_double)
+        check(lib().lwp_coco_eval(self.h.ptr, *self._coco_args(packed), precision.ctypes.data_as(dp), recall.ctypes.data_as(dp),
+                                  scores.ctypes.data_as(dp), npig.ctypes.data_as(C.POINTER(C.c_int64))), self.h.ptr)
+        return {"precision": precision, "recall": recall, "scores": scores, "npig": npig, "stats": coco_stats(precision, recall)}
+
+    def debug_coco_oks(self, gt, detections=None, image=0):
+        """The per-image half of ``coco_eval`` for image number ``image`` (position in ascending image-id order): ``order``, the
+        indices within the image of its up to 20 selected detections by rank; ``oks`` (len(order), G), columns in the ground
+        truths' input order; ``matched`` / ``ignored`` (3, 10, 20) bool by [area range, IoU threshold, rank]; ``npig`` (3,)."""
+        packed = gt if detections is None and "dt_off" in gt else coco_pack(gt, detections)
+        image = int(image)
+        if not 0 <= image < int(packed["n_images"]):
+            raise ValueError("image %d out of range" % image)
+        G = int(packed["gt_off"][image + 1] - packed["gt_off"][image])
+        n_sel, order, npig = C.c_int(), (C.c_int * 20)(), (C.c_int * 3)()
+        oks = np.zeros((20, max(G, 1)), dtype=np.float64)
+        matched, ignored = np.zeros((30, 20), dtype=np.uint8), np.zeros((30, 20), dtype=np.uint8)
+        ubp = C.POINTER(C.c_ubyte)
+        check(lib().lwp_debug_coco_oks(self.h.ptr, *self._coco_args(packed), image, C.byref(n_sel), order, oks.ctypes.data_as(C.POINTER(C.c_double)),
+                                       oks.size, matched.ctypes.data_as(ubp), ignored.ctypes.data_as(ubp), npig), self.h.ptr)
+        n = n_sel.value
+        return {"order": [order[r] for r in range(n)], "oks": oks.reshape(-1)[:n * G].reshape(n, G).copy(),
+                "matched": matched.reshape(3, 10, 20).astype(bool), "ignored": ignored.reshape(3, 10, 20).astype(bool),
+                "npig": np.array([npig[a] for a in range(3)], dtype=np.int64)}
+
+
+def coco_pack(gt, detections):
+    """The arrays ``lwp_coco_eval`` takes, from a COCO ground-truth dict and a list of result dicts, as COCO() / loadRes() /
+    COCOeval._prepare() arrange them: the images of ``gt`` in ascending id order, each with its annotations and detections in
+    input order; ``gt_ignore`` = iscrowd or num_keypoints == 0.  ValueError: a detection whose image_id is not in ``gt``
+    (loadRes asserts this), a non-positive annotation id (COCOeval reads a match to id 0 as no match), more than one category."""
+    cats = sorted({int(c["id"]) for c in gt["categories"]}) if gt.get("categories") else \
+        sorted({int(a["category_id"]) for a in gt.get("annotations", []) if "category_id" in a})
+    if len(cats) > 1:
+        raise ValueError("COCO evaluation supports one category, the ground truth has %d" % len(cats))
+    cat = cats[0] if cats else None
+    img_ids = sorted({int(im["id"]) for im in gt["images"]})
+    index = {v: i for i, v in enumerate(img_ids)}
+    n = len(img_ids)
+    if n < 1:
+        raise ValueError("the ground truth lists no image")
+    per_gt, per_dt = [[] for _ in range(n)], [[] for _ in range(n)]
+    for a in gt.get("annotations", []):
+        if int(a["id"]) <= 0:
+            raise ValueError("annotation id %r is not positive" % (a["id"],))
+        if cat is not None and int(a.get("category_id", cat)) != cat:
+            continue
+        if int(a["image_id"]) in index:
+            per_gt[index[int(a["image_id"])]].append(a)
+    for d in detections:
+        if int(d["image_id"]) not in index:
+            raise ValueError("detection for image %r, which the ground truth does not list" % (d["image_id"],))
+        if cat is not None and int(d.get("category_id", cat)) != cat:
+            continue
+        per_dt[index[int(d["image_id"])]].append(d)
+    gts = [a for lst in per_gt for a in lst]
+    dts = [d for lst in per_dt for d in lst]
+
+    def kp(rows):
+        a = np.array([r["keypoints"] for r in rows], dtype=np.float64).reshape(-1, 17, 3) if rows else np.zeros((0, 17, 3))
+        return np.ascontiguousarray(a)
+    crowd = np.array([1 if a.get("iscrowd", 0) else 0 for a in gts], dtype=np.int32)
+    nokp = np.array([1 if a["num_keypoints"] == 0 else 0 for a in gts], dtype=np.int32)
+    return {"n_images": n, "image_ids": img_ids,
+            "dt_off": np.cumsum([0] + [len(v) for v in per_dt], dtype=np.int64), "dt_kp": kp(dts),
+            "dt_score": np.array([d["score"] for d in dts], dtype=np.float64),
+            "gt_off": np.cumsum([0] + [len(v) for v in per_gt], dtype=np.int64), "gt_kp": kp(gts),
+            "gt_area": np.array([a["area"] for a in gts], dtype=np.float64),
+            "gt_bbox": np.ascontiguousarray(np.array([a["bbox"] for a in gts], dtype=np.float64).reshape(-1, 4)),
+            "gt_iscrowd": crowd, "gt_ignore": (crowd | nokp).astype(np.int32)}
+
+
+def coco_stats(precision, recall):
+    """COCOeval._summarizeKps on accumulate()'s arrays (precision (10, 101, 3), recall (10, 3); ranges all, medium, large): AP,
+    AP50, AP75, AP medium, AP large, then the same five of AR.  Each is the mean over the entries > -1, or -1 without any."""
+    def mean(s):
+        s = s[s > -1]
+        return -1.0 if s.size == 0 else float(np.mean(s))
+    out = []
+    for s in (precision, recall):
+        out += [mean(s[..., 0]), mean(s[0, ..., 0]), mean(s[5, ..., 0]), mean(s[..., 1]), mean(s[..., 2])]
+    return np.array(out, dtype=np.float64)
+
+
 _default = {}
 
 

@@ -240,3 +240,41 @@ def write_detections(output_name, coco_result):
     import json
     with open(output_name, 'w') as f:
         json.dump(coco_result, f, indent=4)
+
+
+# ---------------------------------------------------------------------------------------------- COCO evaluation
+def _print_summary(stats):
+    """COCOeval.summarize()'s ten lines for iouType 'keypoints', in its format."""
+    line = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'
+    rows = [(None, 'all'), (.5, 'all'), (.75, 'all'), (None, 'medium'), (None, 'large')]
+    for i, stat in enumerate(stats):
+        iou, area = rows[i % 5]
+        title, kind = ('Average Precision', '(AP)') if i < 5 else ('Average Recall', '(AR)')
+        iou_str = '{:0.2f}:{:0.2f}'.format(0.5, 0.95) if iou is None else '{:0.2f}'.format(iou)
+        print(line.format(title, kind, iou_str, area, 20, stat))
+
+
+def evaluate_detections(gt, results, engine=None):
+    """``run_coco_eval`` for in-memory data: ``gt`` a COCO ground-truth dict ('images', 'annotations', 'categories'),
+    ``results`` the list ``coco_detections`` returns.  OKS, matching and accumulation run on the GPU (``Engine.coco_eval``); the
+    ten summarize() numbers are printed and returned.  ValueError: a detection for an image ``gt`` does not list, a
+    non-positive annotation id, more than one category."""
+    from .runtime import default_engine
+    eng = default_engine() if engine is None else engine
+    stats = eng.coco_eval(gt, results)["stats"]
+    _print_summary(stats)
+    return stats
+
+
+def run_coco_eval(gt_file_path, dt_file_path):
+    """Drop-in for the reference's val.run_coco_eval (val.py:17-27) without pycocotools: COCOeval(gt, loadRes(dt), 'keypoints')
+    evaluate() / accumulate() / summarize() over the images of the ground-truth file in ascending id order.  Prints what the
+    reference prints and, unlike it, returns the ten stats."""
+    import json
+    annotation_type = 'keypoints'
+    print('Running test for {} results.'.format(annotation_type))
+    with open(gt_file_path) as f:
+        gt = json.load(f)
+    with open(dt_file_path) as f:
+        results = json.load(f)
+    return evaluate_detections(gt, results)
