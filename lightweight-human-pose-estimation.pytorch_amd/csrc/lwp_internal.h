@@ -126,6 +126,7 @@ struct Tuning {
     int stem_ty = 0, stem_wl = -1, stem_debug = 0;                 // LWP_STEM_TY, LWP_STEM_WL, LWP_STEM_DEBUG
     int dw_tiled = -1, dw_cc = 0, dw_ph = 0;                       // LWP_DW_TILED (0 never | 1 always), LWP_DW_CC, LWP_DW_PH
     int gemm_wp = -1;                                              // LWP_GEMM_WP (-1 unset, else first digit)
+    int gemm_debug = 0;                                            // LWP_GEMM_DEBUG (LWP_ABLATION builds: gemm_ar_kernel without 1 A staging, 2 weight requests, 4 MFMAs, 8 reduction + epilogue)
     bool has_c3 = false, has_pw = false; int c3[3] = {0, 0, 0}, pw[3] = {0, 0, 0};   // LWP_GEMM_C3 / LWP_GEMM_PW = "BM,BN,KS"
     int dwpw_bm = 0, dwpw_nw = 0, dwpw_debug = 0, dwpwh_debug = 0; // LWP_DWPW_BM, LWP_DWPW_NW, LWP_DWPW_DEBUG, LWP_DWPWH_DEBUG
     int dwpw_pipe = -1;                                            // LWP_DWPW_PIPE (f32 software-pipelined 512-output fused kernel: 0 off, 1 forced)

@@ -852,13 +852,24 @@ static hipError_t launch_gemm_wp_t(const GemmParams& p, hipStream_t s) {
 // ds_read_b128 at a tap-dependent row offset (taps outside the image: the lane reads a zero row instead), four
 // 1-KiB loads of fragment-packed weights (double-buffered in registers), sixteen MFMAs — no LDS store, no barrier, no
 // global A load inside the loop.  1x1 convs stage their (up to four) 32 x 32 tiles the same way.
+//
+// The fixed part of a launch is one memory round trip on either side of the K loop.  At entry a wave issues its A-window loads and
+// its first PF - 1 weight steps back to back (nothing in their addresses needs a run-time division: the dilation of the 3x3 is the
+// template's DIL, 1 or 2 — the values the graph produces; DIL = 0 reads p.dil and keeps the general index arithmetic — a window row
+// finds its segment by comparison, and the tile index is a shift when cout_pad / BN is a power of two), and computes the lane's
+// pixel and tap mask while they are in flight.  Bias and residual are requested after the K loop and arrive during the LDS
+// reduction; the EPG output values of a lane then leave as EPG buffer stores behind one wait (rows past M and channels past cout
+// store to an out-of-range offset, which the hardware drops), and the NCHW copies of the stage outputs follow in a branch of their own.
+// DBG (LWP_ABLATION builds, LWP_GEMM_DEBUG): 1 no A staging, 2 no weight requests, 4 no MFMAs, 8 no reduction + epilogue.
 #ifndef AR_PF
 #define AR_PF 2
 #endif
-template <int BN, int KS, int KSZ>
+template <int BN, int KS, int DIL, int DBG, int KSZ>
 __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams p) {
     constexpr int WN = BN / 32;
     constexpr int GT = WN * 64;                             // threads per K group
+    constexpr int RPT = GT / 8;                             // window rows per staging round (eight threads per 32-channel row)
+    constexpr unsigned OOB = 0x80000000u;                   // >= num_records of every descriptor here: loads return zero, stores are dropped
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -872,65 +883,58 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
         const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
         bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
     }
-    const int tile_m = bid / ntn, tile_n = bid % ntn;
+    int tile_m;
+    if ((ntn & (ntn - 1)) == 0) tile_m = bid >> __builtin_ctz(ntn); else tile_m = bid / ntn;
+    const int tile_n = bid - tile_m * ntn;
     const int m0 = tile_m * 32;
     const int n0 = tile_n * BN + wn * 32;
     const int n = n0 + r;
-    const float bias = n < p.cout ? p.bias[n] : 0.f;
 
     const int kpt = p.cin_pad / BK;                         // channel blocks
     const int nb = g < kpt ? (kpt - g + KS - 1) / KS : 0;   // blocks of this group
     const int nb_max = (kpt + KS - 1) / KS;
-    const int seg = KSZ == 3 ? 32 + 2 * p.dil : 32;         // rows per segment
+    const int dil = KSZ == 3 ? (DIL > 0 ? DIL : p.dil) : 0;
+    const int seg = KSZ == 3 ? 32 + 2 * dil : 32;           // rows per segment
     const int R = KSZ == 3 ? 3 * seg : 32;                  // rows per block
     float* Ag = smem + (size_t)g * (nb_max * R + 1) * LDS_LD;   // [nb][R][36] + one zero row
     float* zrow = Ag + (size_t)nb_max * R * LDS_LD;
 
     // ---- stage the group's A data: chunk = (block j, row, 16-byte column)
     const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)((int64_t)M * p.in_ld * 4), 0x00020000);   // host: < 2^31 bytes
-    {
-        const int t = tid - g * GT;                         // thread within the group
-        const int col = (t & 7) * 4;
-        const int total = nb * R;
-        for (int base = 0; base < total; base += 8 * (GT / 8)) {      // 8 independent loads in flight per thread, then the stores
-            f32x4 tmp[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int ch = base + (t >> 3) + u * (GT / 8);
-                const int chc = ch < total ? ch : 0;
-                const int j = chc / R, row = chc - j * R;
-                int64_t idx;
-                if (KSZ == 3) {
-                    const int sd = row / seg, rw = row - sd * seg;
-                    idx = (int64_t)m0 + (int64_t)(sd - 1) * p.dil * p.W - p.dil + rw;
-                } else {
-                    idx = (int64_t)m0 + row;
-                }
-                const bool ok = ch < total && idx >= 0 && idx < M;
-                // buffer load: rows outside the tensor read offset 2^31 >= num_records and come back as zeros
-                tmp[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, ok ? (unsigned)(((int)idx * p.in_ld + (g + j * KS) * BK + col) * 4) : 0x80000000u, 0, 0));
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int ch = base + (t >> 3) + u * (GT / 8);
-                if (ch < total) *(f32x4*)(Ag + (size_t)ch * LDS_LD + col) = tmp[u];
-            }
+    const int t = tid - g * GT;                             // thread within the group
+    const int col = (t & 7) * 4, trow = t >> 3;
+    const int total = nb * R;
+    // byte offset of chunk `ch` = row `row` of the group's block j (rows outside the group's chunks or the tensor: OOB, zeros)
+    auto a_off = [&](int ch, int j, int row) -> unsigned {
+        int idx = m0 + row;
+        if (KSZ == 3) {
+            const int sd = (row >= seg ? 1 : 0) + (row >= 2 * seg ? 1 : 0);     // segment dy = sd - 1
+            idx = m0 + (sd - 1) * dil * p.W - dil + (row - sd * seg);
         }
-        if (t < 9) *(f32x4*)(zrow + 4 * t) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+        const bool ok = ch < total && idx >= 0 && idx < M;
+        return ok ? ((unsigned)idx * (unsigned)p.in_ld + (unsigned)((g + j * KS) * BK + col)) * 4u : OOB;
+    };
+    // the workload's case: one block per group and a block that one round of at most eight loads per thread covers
+    constexpr int R_CT = KSZ == 1 ? 32 : (DIL > 0 ? 3 * (32 + 2 * DIL) : 0);
+    constexpr int NU1 = R_CT > 0 && (R_CT + RPT - 1) / RPT <= 8 ? (R_CT + RPT - 1) / RPT : 0;
+    const bool one_round = NU1 > 0 && nb == 1;
+    // there row = trow + u RPT, and the offset is one per-lane product plus wave-uniform terms: the round's u RPT pixels and the
+    // segment's shift (picked by comparison) times the pixel stride
+    auto a_off1 = [&](int u) -> unsigned {
+        const int row = trow + u * RPT;
+        const int pxb = p.in_ld * 4;                        // bytes per pixel
+        int shift = 0;                                      // pixels from m0 + row to the chunk's pixel
+        if (KSZ == 3) {
+            const int dw = dil * p.W;
+            shift = row >= 2 * seg ? dw - dil - 2 * seg : (row >= seg ? -dil - seg : -dw - dil);
+        }
+        const int idx = m0 + row + shift;
+        const bool ok = row < R_CT && idx >= 0 && idx < M;
+        const unsigned base = (unsigned)(m0 + trow) * (unsigned)pxb + (unsigned)((g * BK + col) * 4);
+        const int bshift = KSZ == 3 ? (row >= 2 * seg ? (dil * p.W - dil - 2 * seg) * pxb : (row >= seg ? (-dil - seg) * pxb : (-dil * p.W - dil) * pxb)) : 0;
+        return ok ? base + (unsigned)(u * RPT * pxb) + (unsigned)bshift : OOB;
+    };
 
-    // the lane's pixel and the taps that fall inside the image
-    const int mrow = m0 + r;
-    const bool row_ok = mrow < M;
-    const int mm = row_ok ? mrow : 0;
-    const int qy = mm / p.W;
-    const int x = mm - qy * p.W, y = qy % p.H;
-    unsigned valid = 0;
-#pragma unroll
-    for (int t = 0; t < KSZ * KSZ; ++t) {
-        const int yy = y + (KSZ == 3 ? (t / 3 - 1) * p.dil : 0), xx = x + (KSZ == 3 ? (t % 3 - 1) * p.dil : 0);
-        if (row_ok && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) valid |= 1u << t;
-    }
     constexpr int taps = KSZ * KSZ;
     const int my_steps = nb * taps;
     // B: fragment order [step = tap * kpt + block][32-channel tile][s][lane][4]
@@ -940,6 +944,7 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
     const unsigned b_tile = (unsigned)__builtin_amdgcn_readfirstlane(n0 >> 5) * 4096u;       // bytes
     const unsigned b_step = (unsigned)(p.cout_pad >> 5) * 4096u;
     auto load_b = [&](int i, f32x4* dst) {                  // i-th step of this group: block j = i / taps, tap = i % taps
+        if (DBG & 2) return;
         const int j = i / taps, tap = i - j * taps;
         const unsigned soff = (unsigned)(tap * kpt + g + j * KS) * b_step + b_tile;
 #pragma unroll
@@ -947,12 +952,76 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
     };
     constexpr int PF = AR_PF;                               // weight steps in flight per wave (register ring, static indices)
     f32x4 bv[PF][BK / 8];
-    // a group without blocks (1x1 layer with cin_pad / 32 < KS) prefetches nothing: its step 0 would be weight step g,
-    // past the layer's packed weights, and the weight descriptor does not bound the read (wave-uniform branch)
-    if (my_steps > 0) {
+    if (DBG & 2) {
 #pragma unroll
-        for (int u = 0; u < PF - 1; ++u) load_b(u < my_steps ? u : my_steps - 1, bv[u]);
+        for (int u = 0; u < PF; ++u)
+#pragma unroll
+            for (int s = 0; s < BK / 8; ++s) bv[u][s] = f32x4{1.f, 1.f, 1.f, 1.f};
     }
+    unsigned valid = 0;
+    // The prologue, once per form (ONE: the one-round case) so that neither waits for the other's requests: A loads, weight
+    // steps, then — with every request out — the lane's pixel and tap mask, then the window goes to LDS.
+    auto prologue = [&](auto ONE_) {
+        constexpr bool ONE = decltype(ONE_)::value;
+        constexpr int NU = ONE ? NU1 : 8;
+        f32x4 tmp[8];
+        auto round = [&](int base) {                        // general form: 8 independent loads in flight per thread
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int ch = base + trow + u * RPT;
+                const int chc = ch < total ? ch : 0;
+                const int j = chc / R;
+                tmp[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, a_off(ch, j, chc - j * R), 0, 0));
+            }
+        };
+        if (!(DBG & 1)) {
+            if (ONE) {
+#pragma unroll
+                for (int u = 0; u < NU; ++u) tmp[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, a_off1(u), 0, 0));
+            } else if (total > 0) {
+                round(0);
+            }
+        }
+        // a group without blocks (1x1 layer with cin_pad / 32 < KS) prefetches nothing: its step 0 would be weight step g,
+        // past the layer's packed weights, and the weight descriptor does not bound the read (wave-uniform branch)
+        if (ONE || my_steps > 0) {
+#pragma unroll
+            for (int u = 0; u < PF - 1; ++u) load_b(ONE ? (u < taps ? u : taps - 1) : (u < my_steps ? u : my_steps - 1), bv[u]);
+        }
+        __builtin_amdgcn_sched_barrier(0);                  // every request is out: nothing below moves in front of them
+
+        const int mrow = m0 + r;
+        const bool row_ok = mrow < M;
+        const int mm = row_ok ? mrow : 0;
+        const int qy = mm / p.W;
+        const int x = mm - qy * p.W, y = qy % p.H;
+#pragma unroll
+        for (int tp = 0; tp < KSZ * KSZ; ++tp) {
+            const int yy = y + (KSZ == 3 ? (tp / 3 - 1) * dil : 0), xx = x + (KSZ == 3 ? (tp % 3 - 1) * dil : 0);
+            if (row_ok && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) valid |= 1u << tp;
+        }
+
+        if (!(DBG & 1)) {
+            if (ONE) {
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+                    const int row = trow + u * RPT;
+                    if (row < R_CT) *(f32x4*)(Ag + (size_t)row * LDS_LD + col) = tmp[u];
+                }
+            } else {
+                for (int base = 0; base < total; base += 8 * RPT) {
+                    if (base > 0) round(base);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int ch = base + trow + u * RPT;
+                        if (ch < total) *(f32x4*)(Ag + (size_t)ch * LDS_LD + col) = tmp[u];
+                    }
+                }
+            }
+        }
+    };
+    if (one_round) prologue(std::true_type{}); else prologue(std::false_type{});
+    if (t < 9) *(f32x4*)(zrow + 4 * t) = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();                                        // the windows of every group are complete
 
     f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -964,17 +1033,21 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
         load_b(nxt, bv[(P + PF - 1) % PF]);
         const int j = i / taps, tap = i - j * taps;
         int roff = j * R;
-        if (KSZ == 3) roff += (tap / 3) * seg + (tap % 3) * p.dil;     // segment dy, shift dx (the segment starts at -dil)
+        if (KSZ == 3) roff += (tap / 3) * seg + (tap % 3) * dil;       // segment dy, shift dx (the segment starts at -dil)
         const float* a = (valid >> tap) & 1u ? a_lane + (size_t)roff * LDS_LD : z_lane;
         f32x4 av[BK / 8];
 #pragma unroll
         for (int s = 0; s < BK / 8; ++s) av[s] = *(const f32x4*)(a + 8 * s);
 #pragma unroll
-        for (int s = 0; s < BK / 8; ++s) {
+        for (int s = 0; s < ((DBG & 4) ? 0 : BK / 8); ++s) {
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].x, bv[P][s].x, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].y, bv[P][s].y, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].z, bv[P][s].z, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].w, bv[P][s].w, acc, 0, 0, 0);
+        }
+        if (DBG & 4) {                                                 // the operands still arrive
+#pragma unroll
+            for (int s = 0; s < BK / 8; ++s) asm volatile("" :: "v"(av[s]), "v"(bv[P][s]));
         }
     };
     int i = 0;
@@ -987,19 +1060,42 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
     if (i < my_steps) { one(i, std::integral_constant<int, 0>{}); ++i; }
     if (PF > 2 && i < my_steps) { one(i, std::integral_constant<int, 1 % PF>{}); ++i; }
     if (PF > 3 && i < my_steps) { one(i, std::integral_constant<int, 2 % PF>{}); ++i; }
+    if (DBG & 8) {                                  // the accumulators stay live behind a store no launch performs
+        if (p.debug == 0x7fffffff) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) p.out[e * 64 + lane] = acc[e];
+        }
+        return;
+    }
 
     // ---- reduction + epilogue, spread over ALL waves: every K group takes 16 / KS of the 16 accumulator registers
     // (= 8 / KS... rows) of its N half, sums the KS partials in the fixed order 0, 1, ..., KS-1 and stores those rows.
     constexpr int EPG = 16 / KS;                    // accumulator registers per group in the epilogue
     const int e0 = g * EPG;
+    // bias and residual: requested now without a branch per row, consumed after the reduction.  Descriptors bound the tensors
+    // (`out` and `res` may be windows of a concat buffer: the last row ends at its cout-th channel; host: < 2^31 bytes); a row
+    // past M or a channel past cout reads / writes the out-of-range offset.
+    const bool n_ok = n < p.cout;
+    const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, p.cout * 4, 0x00020000);
+    const float bias = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brsrc, n_ok ? (unsigned)n * 4u : OOB, 0, 0));
+    unsigned o_off[EPG];
+    bool m_ok[EPG];
+#pragma unroll
+    for (int u = 0; u < EPG; ++u) {
+        const int e = e0 + u;
+        const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        m_ok[u] = m < M && n_ok;
+        o_off[u] = m_ok[u] ? ((unsigned)m * (unsigned)p.out_ld + (unsigned)n) * 4u : OOB;
+    }
     float resv[EPG];
-    const bool has_res = p.res != nullptr && n < p.cout;
-    if (has_res) {                                  // requested now, consumed after the reduction
+    const bool has_res = p.res != nullptr;          // wave-uniform
+    if (has_res) {
+        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, ((M - 1) * p.res_ld + p.cout) * 4, 0x00020000);
 #pragma unroll
         for (int u = 0; u < EPG; ++u) {
             const int e = e0 + u;
             const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            resv[u] = m < M ? p.res[(int64_t)m * p.res_ld + n] : 0.f;
+            resv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, m_ok[u] ? ((unsigned)m * (unsigned)p.res_ld + (unsigned)n) * 4u : OOB, 0, 0));
         }
     }
     float outv[EPG];
@@ -1021,33 +1117,47 @@ __global__ void __launch_bounds__((BN / 32) * KS * 64) gemm_ar_kernel(GemmParams
         for (int u = 0; u < EPG; ++u) outv[u] = acc[u];
     }
 
-    if (n < p.cout) {
+    float v[EPG];
+#pragma unroll
+    for (int u = 0; u < EPG; ++u) {
+        v[u] = apply_act(outv[u] + bias, p.act);
+        if (has_res) v[u] += resv[u];
+    }
+    // the EPG stores of a lane, back to back behind the one wait for bias and residual
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, ((M - 1) * p.out_ld + p.cout) * 4, 0x00020000);
+#pragma unroll
+    for (int u = 0; u < EPG; ++u) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[u]), orsrc, o_off[u], 0, 0);
+    if (p.out_nchw || p.out_nchw2) {                // stage outputs (NCHW), wave-uniform; merged heads split at out_split
         const int HW = p.H * p.W;
+        const int c0 = p.out_split > 0 ? p.out_split : p.cout;
 #pragma unroll
         for (int u = 0; u < EPG; ++u) {
+            if (!m_ok[u]) continue;
             const int e = e0 + u;
             const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (m < M) {
-                float v = apply_act(outv[u] + bias, p.act);
-                if (has_res) v += resv[u];
-                p.out[(int64_t)m * p.out_ld + n] = v;
-                if (p.out_nchw || p.out_nchw2) {         // stage outputs (NCHW); merged heads split at out_split
-                    const int img = m / HW, pix = m - img * HW;
-                    const int c0 = p.out_split > 0 ? p.out_split : p.cout;
-                    if (n < c0) { if (p.out_nchw) p.out_nchw[((int64_t)img * c0 + n) * HW + pix] = v; }
-                    else if (p.out_nchw2) p.out_nchw2[((int64_t)img * (p.cout - c0) + (n - c0)) * HW + pix] = v;
-                }
-            }
+            const int img = m / HW, pix = m - img * HW;
+            if (n < c0) { if (p.out_nchw) p.out_nchw[((int64_t)img * c0 + n) * HW + pix] = v[u]; }
+            else if (p.out_nchw2) p.out_nchw2[((int64_t)img * (p.cout - c0) + (n - c0)) * HW + pix] = v[u];
         }
     }
 }
 
+template <int BN, int KS, int DIL, int DBG, int KSZ>
+static hipError_t launch_gemm_ar_i(const GemmParams& p, hipStream_t s, unsigned tiles, size_t lds) {
+    static LdsAttrOnce attr;
+    hipError_t e = attr.ensure((const void*)gemm_ar_kernel<BN, KS, DIL, DBG, KSZ>, 150 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((gemm_ar_kernel<BN, KS, DIL, DBG, KSZ>), dim3(tiles), dim3((BN / 32) * KS * 64), lds, s, p);
+    return hipGetLastError();
+}
 template <int BN, int KS, int KSZ>
 static hipError_t launch_gemm_ar_k(const GemmParams& p, hipStream_t s, bool* fits) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
     *fits = false;
     if (M >= (1ll << 31) - 64 || !p.wf) return hipSuccess;
     if (M * p.in_ld * 4 >= (1ll << 31)) return hipSuccess;       // 32-bit buffer offsets: larger inputs take the shared-tile kernel's path (and its check)
+    if (((M - 1) * p.out_ld + p.cout) * 4 >= (1ll << 31)) return hipSuccess;              // the same for the output window
+    if (p.res && ((M - 1) * p.res_ld + p.cout) * 4 >= (1ll << 31)) return hipSuccess;     // and the residual
     const int kpt = p.cin_pad / BK, nb_max = (kpt + KS - 1) / KS;
     const int R = KSZ == 3 ? 3 * (32 + 2 * p.dil) : 32;
     size_t lds = (size_t)KS * ((size_t)nb_max * R + 1) * LDS_LD * sizeof(float);
@@ -1055,15 +1165,22 @@ static hipError_t launch_gemm_ar_k(const GemmParams& p, hipStream_t s, bool* fit
     if (red > lds) lds = red;
     if (lds > 150 * 1024) return hipSuccess;                 // caller falls back to the per-step staging kernel
     *fits = true;
-    constexpr int NWV = (BN / 32) * KS;
-    const int64_t tiles = ((M + 31) / 32) * (p.cout_pad / BN);
-    static LdsAttrOnce attr;
-    {
-        hipError_t e = attr.ensure((const void*)gemm_ar_kernel<BN, KS, KSZ>, 150 * 1024);
-        if (e != hipSuccess) return e;
+    const unsigned tiles = (unsigned)(((M + 31) / 32) * (p.cout_pad / BN));
+    const int dil = KSZ == 3 && (p.dil == 1 || p.dil == 2) ? p.dil : 0;      // compile-time dilation of the 3x3 forms
+#ifdef LWP_ABLATION
+    const int d = (p.tune ? *p.tune : default_tuning()).gemm_debug;          // LWP_GEMM_DEBUG: the workload's configuration only
+    if (BN == 64 && KS == 4 && d) {
+#define AR_DBG(D_) if (d == D_) { \
+            if (KSZ == 1) return launch_gemm_ar_i<64, 4, 0, D_, 1>(p, s, tiles, lds); \
+            if (dil == 1) return launch_gemm_ar_i<64, 4, 1, D_, 3>(p, s, tiles, lds); \
+            if (dil == 2) return launch_gemm_ar_i<64, 4, 2, D_, 3>(p, s, tiles, lds); }
+        AR_DBG(1) AR_DBG(2) AR_DBG(4) AR_DBG(8) AR_DBG(7) AR_DBG(14) AR_DBG(15)
+#undef AR_DBG
     }
-    hipLaunchKernelGGL((gemm_ar_kernel<BN, KS, KSZ>), dim3((unsigned)tiles), dim3(NWV * 64), lds, s, p);
-    return hipGetLastError();
+#endif
+    if (dil == 1) return launch_gemm_ar_i<BN, KS, KSZ == 3 ? 1 : 0, 0, KSZ>(p, s, tiles, lds);
+    if (dil == 2) return launch_gemm_ar_i<BN, KS, KSZ == 3 ? 2 : 0, 0, KSZ>(p, s, tiles, lds);
+    return launch_gemm_ar_i<BN, KS, 0, 0, KSZ>(p, s, tiles, lds);
 }
 template <int BN, int KS>
 static hipError_t launch_gemm_ar_t(const GemmParams& p, hipStream_t s, bool* fits) {
@@ -1324,6 +1441,9 @@ __global__ void __launch_bounds__(NW * 64) dwpw_kernel(DwPwParams p) {
             }
         }
     };
+    f32x4 bias[2];                                   // in flight during the K loop
+#pragma unroll
+    for (int t = 0; t < 2; ++t) bias[t] = *(const f32x4*)(p.pw_b + wave * 32 + t * 16 + 4 * q);
     int s0 = 0;
     for (; s0 + PF <= nsteps; s0 += PF) {
         one(s0, std::integral_constant<int, 0>{});
@@ -1332,19 +1452,29 @@ __global__ void __launch_bounds__(NW * 64) dwpw_kernel(DwPwParams p) {
     }
     if (s0 < nsteps) { one(s0, std::integral_constant<int, 0>{}); ++s0; }
     if (PF > 2 && s0 < nsteps) { one(s0, std::integral_constant<int, 1 % PF>{}); ++s0; }
-    // epilogue: D layout row (channel) = (lane>>4)*4 + reg, col (pixel) = lane&15
+    // epilogue: D layout row (channel) = (lane>>4)*4 + reg, col (pixel) = lane&15.  The residual rows of both column halves are
+    // requested together (the biases went out before the K loop): one round trip, then the stores with no wait between them
+    f32x4 resv[RT][2];
+    if (p.res) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int a = 0; a < RT; ++a) {
+                const int64_t m = m0 + a * 16 + r16;
+                resv[a][t] = m < M ? *(const f32x4*)(p.res + m * p.res_ld + wave * 32 + t * 16 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+    }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = wave * 32 + t * 16 + 4 * q;
-        const f32x4 bias = *(const f32x4*)(p.pw_b + n);
 #pragma unroll
         for (int a = 0; a < RT; ++a) {
             const int64_t m = m0 + a * 16 + r16;
             if (m < M) {
-                f32x4 v = acc[a][t] + bias;
+                f32x4 v = acc[a][t] + bias[t];
                 v.x = apply_act(v.x, act_pw); v.y = apply_act(v.y, act_pw);
                 v.z = apply_act(v.z, act_pw); v.w = apply_act(v.w, act_pw);
-                if (p.res) v += *(const f32x4*)(p.res + m * p.res_ld + n);
+                if (p.res) v += resv[a][t];
                 *(f32x4*)(p.out + m * p.out_ld + n) = v;
             }
         }
@@ -1958,7 +2088,7 @@ Tuning tuning_from_env() {
         else t.has_gemmh_ar = sscanf(e, "%d,%d,%d,%d", &t.gemmh_ar[0], &t.gemmh_ar[1], &t.gemmh_ar[2], &t.gemmh_ar[3]) == 4;
     }
     if (const char* e = getenv("LWP_GEMMH_AR_FORCE")) t.gemmh_ar_force = e[0] == '1';
-    geti("LWP_GEMMH_DEBUG", &t.gemmh_debug);
+    geti("LWP_GEMMH_DEBUG", &t.gemmh_debug); geti("LWP_GEMM_DEBUG", &t.gemm_debug);
     if (const char* e = getenv("LWP_GEMMH")) t.has_gemmh = sscanf(e, "%d,%d,%d,%d", &t.gemmh[0], &t.gemmh[1], &t.gemmh[2], &t.gemmh[3]) == 4;
     digit("LWP_UPSAMPLE_TILED", &t.upsample_tiled);
     digit("LWP_PEAK_TILE", &t.peak_tile); digit("LWP_PAIR_FORM", &t.pair_form); digit("LWP_POST_NCHW", &t.post_nchw); digit("LWP_HEADS_F32_LDS", &t.heads_f32_lds); digit("LWP_MS_FUSED", &t.ms_fused); digit("LWP_MS_VEC", &t.ms_vec); geti("LWP_MS_TX", &t.ms_tx); digit("LWP_HOST_FETCH_DMA", &t.host_fetch_dma); geti("LWP_DWPW_LDS_PAD", &t.dwpw_lds_pad_kb);
