@@ -632,6 +632,37 @@ int lwp_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int cr
 int lwp_time_augment_batch(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride, float* image_out,
                            unsigned char* mask_out, float* mask_small_out, int iters, float* ms_total);
 
+/* ---- crowd masks on the device: datasets/coco.py:17-21 (get_mask) for a batch, from the uncompressed RLE dicts
+ *      {"counts": [c0, c1, ..], "size": [h, w]} that scripts/prepare_train_labels.py collects from iscrowd annotations.  The runs
+ *      alternate between zeros and ones, start with zeros and walk the image column by column: pixel (y, x) is position
+ *      x * h + y.  A zero-length run is legal anywhere; positions past the last run are zeros.  The arithmetic restates
+ *      maskApi.c's rleDecode and is not pinned against pycocotools.
+ *      Inputs (HOST), CSR: image n of N owns segmentations image_seg_off[n] .. image_seg_off[n + 1] - 1, segmentation s the counts
+ *      counts[seg_off[s]] .. counts[seg_off[s + 1] - 1]; heights / widths [N].  The host turns the counts into run ends and
+ *      uploads [run ends | segment offsets | image records] with ONE copy; one kernel launch renders every image.
+ *      Output (DEVICE): image n's heights[n] x widths[n] row-major float32 mask at masks_device + out_off[n] (out_off [N + 1],
+ *      in floats): 1.0f where no segmentation of the image covers the pixel, 0.0f where any does.  An image without
+ *      segmentations is all ones.
+ *      Checks without a GPU (h == NULL too, LWP_ERR_ARG, each naming the sample): null pointers (counts may be NULL when there is
+ *      no count), 1 <= N <= 65535, offsets that start at 0 and never descend, sizes in 1..32767, no negative count, the counts of
+ *      a segmentation summing to at most height * width (in 64 bits), out_off leaving height * width floats an image.
+ *      Runs on the handle's stream, honours lwp_set_stream, needs no weights. */
+int lwp_crowd_masks(lwp_handle h, const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off, const int* heights,
+                    const int* widths, int N, const int64_t* out_off, float* masks_device);
+/* the kernel alone (tools/crowd_mask_bench.py): the same checks and the one upload, then `iters` back-to-back launches between
+ * two HIP events.  ms_total out. */
+int lwp_time_crowd_masks(lwp_handle h, const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off,
+                         const int* heights, const int* widths, int N, const int64_t* out_off, float* masks_device, int iters,
+                         float* ms_total);
+/* lwp_augment_batch whose float masks come from crowd RLEs: sample n's mask is rendered from its segmentations (CSR as above)
+ * at plans[n].src_h x src_w into a workspace the handle owns, behind the batch's one upload, in which the run tables ride;
+ * the augment kernel then reads it in place.  A sample with segmentations must have plans[n].mask == NULL (LWP_ERR_ARG); one
+ * without keeps its mask as given: NULL stays all ones with the mask taps skipped.  Everything else, the checks of both calls
+ * included, is as lwp_augment_batch and lwp_crowd_masks say. */
+int lwp_augment_batch_crowd(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride,
+                            const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off, float* image_out,
+                            unsigned char* mask_out, float* mask_small_out);
+
 /* ---- COCO key-point evaluation: replaces pycocotools' COCOeval(gt, dt, 'keypoints') evaluate() + accumulate() behind
  *      val.py:17-27, with COCOeval's default parameters (the 17 OKS sigmas, IoU thresholds 0.5:0.05:0.95, 101 recall
  *      thresholds, maxDets 20, area ranges all [0, 1e10] / medium [32^2, 96^2] / large [96^2, 1e10], inclusive at both ends) and

@@ -38,6 +38,7 @@ EXPORTS = [
     "lwp_debug_conv_grad", "lwp_debug_dw_grad", "lwp_debug_loss_grad", "lwp_debug_relu_mask", "lwp_debug_grad_add", "lwp_debug_elu_grad",
     "lwp_debug_pw_fold", "lwp_debug_bn_chain",
     "lwp_augment_batch", "lwp_time_augment_batch",
+    "lwp_crowd_masks", "lwp_time_crowd_masks", "lwp_augment_batch_crowd",
     "lwp_coco_eval", "lwp_debug_coco_oks",
 ]
 
@@ -166,6 +167,9 @@ def lib():
     L.lwp_debug_bn_chain.argtypes = [vp] * 12 + [C.c_int] * 3
     L.lwp_augment_batch.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [vp, vp, vp]
     L.lwp_time_augment_batch.argtypes = L.lwp_augment_batch.argtypes + [C.c_int, fp]
+    L.lwp_crowd_masks.argtypes = [vp, i64p, i64p, i64p, ip, ip, C.c_int, i64p, vp]
+    L.lwp_time_crowd_masks.argtypes = L.lwp_crowd_masks.argtypes + [C.c_int, fp]
+    L.lwp_augment_batch_crowd.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [i64p, i64p, i64p, vp, vp, vp]
     coco_in = [vp, C.c_int, i64p, dp, dp, i64p, dp, dp, dp, ip, ip]
     L.lwp_coco_eval.argtypes = coco_in + [dp, dp, dp, i64p]
     L.lwp_debug_coco_oks.argtypes = coco_in + [C.c_int, ip, ip, dp, C.c_int64, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), ip]

@@ -98,7 +98,8 @@ struct lwp_context {
     // training targets and loss (lwp_train_targets / lwp_mask_downsample / lwp_stage_losses): staging of host key-points, person
     // counts and host masks; the loss partials followed by the per-stage sums
     DevBuf d_train, d_loss;
-    // training augmentation (lwp_augment_batch): [plan records | host images and masks], packed on the host, one upload a batch
+    // training augmentation (lwp_augment_batch): [plan records | host images and masks], packed on the host, one upload a batch;
+    // lwp_augment_batch_crowd: [.. | run tables] and, behind the upload, the rendered crowd masks; lwp_crowd_masks: [run tables]
     DevBuf d_augment;
     std::vector<unsigned char> augment_stage;
     // stage backward (lwp_train_forward / lwp_stage_backward; f32 handles): the retaining buffer plan, its activation and
@@ -2308,11 +2309,150 @@ extern "C" int lwp_mask_downsample(lwp_handle h, const float* mask, int mem, int
     return LWP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- crowd masks
+// the RLEs of a batch as the entry points take them: image n owns segmentations image_seg_off[n] .. image_seg_off[n + 1] - 1,
+// segmentation s the counts seg_off[s] .. seg_off[s + 1] - 1
+struct CrowdRuns { const int64_t *counts, *seg_off, *image_seg_off; };
+// what crowd_check leaves for crowd_pack: the sizes, and the layout of [run ends | segment offsets | image records]
+struct CrowdTables {
+    int64_t S = 0, runs = 0;
+    int n_rec = 0, max_h = 0, max_w = 0;
+    size_t segs_at = 0, recs_at = 0, bytes = 0;
+};
+
+// every check that needs no GPU.  size_of(n, &h, &w): the image's size; rendered(n): whether image n gets a record
+template <class SizeOf, class Rendered>
+static int crowd_check(lwp_context* h, const CrowdRuns& r, int N, SizeOf size_of, Rendered rendered, CrowdTables* t) {
+    char msg[200];
+    if (!r.seg_off || !r.image_seg_off) return fail(h, LWP_ERR_ARG, "seg_off / image_seg_off is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    auto bad = [&](int f, const char* what) {
+        snprintf(msg, sizeof msg, "sample %d: %s", f, what);
+        return fail(h, LWP_ERR_ARG, msg);
+    };
+    if (r.image_seg_off[0] != 0) return fail(h, LWP_ERR_ARG, "image_seg_off must start at 0");
+    for (int f = 0; f < N; ++f)
+        if (r.image_seg_off[f + 1] < r.image_seg_off[f]) return bad(f, "image_seg_off descends");
+    const int64_t S = r.image_seg_off[N];
+    if (S >= ((int64_t)1 << 31)) return fail(h, LWP_ERR_ARG, "2^31 segmentations or more");
+    if (r.seg_off[0] != 0) return fail(h, LWP_ERR_ARG, "seg_off must start at 0");
+    for (int f = 0; f < N; ++f)
+        for (int64_t s = r.image_seg_off[f]; s < r.image_seg_off[f + 1]; ++s)
+            if (r.seg_off[s + 1] < r.seg_off[s]) return bad(f, "seg_off descends");
+    const int64_t runs = r.seg_off[S];
+    if (runs >= ((int64_t)1 << 31)) return fail(h, LWP_ERR_ARG, "2^31 counts or more");
+    if (runs > 0 && !r.counts) return fail(h, LWP_ERR_ARG, "counts is null");
+    *t = CrowdTables();
+    for (int f = 0; f < N; ++f) {
+        int ih = 0, iw = 0;
+        size_of(f, &ih, &iw);
+        if (ih < 1 || iw < 1 || ih >= 32768 || iw >= 32768) return bad(f, "the image size is outside 1..32767");
+        const int64_t hw = (int64_t)ih * iw;
+        for (int64_t s = r.image_seg_off[f]; s < r.image_seg_off[f + 1]; ++s) {
+            int64_t sum = 0;
+            for (int64_t i = r.seg_off[s]; i < r.seg_off[s + 1]; ++i) {
+                const int64_t c = r.counts[i];
+                if (c < 0) return bad(f, "a segmentation holds a negative count");
+                if (c > hw - sum) return bad(f, "the counts of a segmentation sum to more than height * width");
+                sum += c;
+            }
+        }
+        if (!rendered(f)) continue;
+        t->n_rec += 1;
+        t->max_h = std::max(t->max_h, ih);
+        t->max_w = std::max(t->max_w, iw);
+    }
+    t->S = S; t->runs = runs;
+    t->segs_at = ((size_t)runs * sizeof(unsigned) + 15) & ~(size_t)15;
+    t->recs_at = t->segs_at + ((((size_t)S + 1) * sizeof(unsigned) + 15) & ~(size_t)15);
+    t->bytes = t->recs_at + (((size_t)t->n_rec * sizeof(CrowdImage) + 15) & ~(size_t)15);
+    return LWP_OK;
+}
+
+// the tables at `host`, which will live at `dev`: the counts become run ends (h * w < 2^30, so a running sum fits 32 bits);
+// out_of(n): the float offset of image n's mask in `masks`
+template <class SizeOf, class Rendered, class OutOf>
+static CrowdLaunch crowd_pack(const CrowdTables& t, const CrowdRuns& r, int N, SizeOf size_of, Rendered rendered, OutOf out_of,
+                              unsigned char* host, unsigned char* dev, float* masks) {
+    unsigned* ends = reinterpret_cast<unsigned*>(host);
+    unsigned* segs = reinterpret_cast<unsigned*>(host + t.segs_at);
+    CrowdImage* recs = reinterpret_cast<CrowdImage*>(host + t.recs_at);
+    for (int64_t s = 0; s < t.S; ++s) {
+        unsigned e = 0;
+        for (int64_t i = r.seg_off[s]; i < r.seg_off[s + 1]; ++i) ends[i] = (e += (unsigned)r.counts[i]);
+    }
+    for (int64_t s = 0; s <= t.S; ++s) segs[s] = (unsigned)r.seg_off[s];
+    int k = 0;
+    for (int f = 0; f < N; ++f) {
+        if (!rendered(f)) continue;
+        CrowdImage& im = recs[k++];
+        size_of(f, &im.h, &im.w);
+        im.seg0 = (unsigned)r.image_seg_off[f];
+        im.n_seg = (unsigned)(r.image_seg_off[f + 1] - r.image_seg_off[f]);
+        im.out = (long long)out_of(f);
+    }
+    CrowdLaunch c;
+    c.ends = reinterpret_cast<const unsigned*>(dev);
+    c.seg_off = reinterpret_cast<const unsigned*>(dev + t.segs_at);
+    c.images = reinterpret_cast<const CrowdImage*>(dev + t.recs_at);
+    c.masks = masks;
+    c.n_images = t.n_rec; c.max_h = t.max_h; c.max_w = t.max_w;
+    return c;
+}
+
+// argument checks and the one upload of lwp_crowd_masks and its timing twin; the tables share the augmentation's staging
+static int crowd_masks_prepare(lwp_handle h, const CrowdRuns& r, const int* heights, const int* widths, int N, const int64_t* out_off,
+                               float* masks_device, CrowdLaunch* launch) {
+    char msg[200];
+    if (!heights || !widths || !out_off || !masks_device) return fail(h, LWP_ERR_ARG, "heights / widths / out_off / masks_device is null");
+    auto size_of = [&](int f, int* ih, int* iw) { *ih = heights[f]; *iw = widths[f]; };
+    auto every = [](int) { return true; };            // an image without segmentations is all ones
+    CrowdTables t;
+    int rc = crowd_check(h, r, N, size_of, every, &t);
+    if (rc) return rc;
+    if (out_off[0] != 0) return fail(h, LWP_ERR_ARG, "out_off must start at 0");
+    for (int f = 0; f < N; ++f)
+        if (out_off[f + 1] - out_off[f] < (int64_t)heights[f] * widths[f]) {
+            snprintf(msg, sizeof msg, "sample %d: out_off leaves fewer than height * width floats", f);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    if (h->d_augment.size() < t.bytes) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        HIP_TRY(h, h->d_augment.ensure(t.bytes));
+    }
+    h->augment_stage.resize(t.bytes);
+    unsigned char* dev = h->d_augment.as<unsigned char>();
+    *launch = crowd_pack(t, r, N, size_of, every, [&](int f) { return out_off[f]; }, h->augment_stage.data(), dev, masks_device);
+    HIP_TRY(h, hipMemcpyAsync(dev, h->augment_stage.data(), t.bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the staging vector and the caller's arrays are free from here on
+    return LWP_OK;
+}
+
+extern "C" int lwp_crowd_masks(lwp_handle h, const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off,
+                               const int* heights, const int* widths, int N, const int64_t* out_off, float* masks_device) {
+    CrowdLaunch c{};
+    int rc = crowd_masks_prepare(h, CrowdRuns{counts, seg_off, image_seg_off}, heights, widths, N, out_off, masks_device, &c);
+    if (rc) return rc;
+    LAUNCH(h, KC_OTHER, launch_crowd_masks(c, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- training augmentation
 // argument checks, then the batch's one upload: the plan records (their pointers rewritten to device addresses) followed by
-// every host image and mask; shared by lwp_augment_batch and lwp_time_augment_batch
+// every host image and mask; shared by lwp_augment_batch and lwp_time_augment_batch.  With `crowd` (lwp_augment_batch_crowd)
+// the run tables of the crowd masks ride in the same upload, the masks' workspace lies behind it in the same allocation, and
+// the records of the samples that have segmentations point into it
 static int augment_prepare(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride, float* image_out,
-                           unsigned char* mask_out, float* mask_small_out, const lwp_augment_plan** plans_device) {
+                           unsigned char* mask_out, float* mask_small_out, const lwp_augment_plan** plans_device,
+                           const CrowdRuns* crowd = nullptr, CrowdLaunch* crowd_launch = nullptr) {
     char msg[200];
     if (!plans || !image_out || !mask_out || !mask_small_out) return fail(h, LWP_ERR_ARG, "plans / image_out / mask_out / mask_small_out is null");
     if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
@@ -2352,21 +2492,43 @@ static int augment_prepare(lwp_handle h, const lwp_augment_plan* plans, int N, i
             if (p.mask) bytes += ((size_t)p.src_h * p.src_w * sizeof(float) + 15) & ~(size_t)15;
         }
     }
+    auto size_of = [&](int f, int* ih, int* iw) { *ih = plans[f].src_h; *iw = plans[f].src_w; };
+    auto has_segs = [&](int f) { return crowd->image_seg_off[f + 1] > crowd->image_seg_off[f]; };
+    CrowdTables tab;
+    std::vector<int64_t> ws_off;                       // float offset of a sample's rendered mask in the workspace
+    const size_t tab_at = bytes;
+    size_t ws_at = bytes, total = bytes;
+    if (crowd) {
+        int rc = crowd_check(h, *crowd, N, size_of, has_segs, &tab);
+        if (rc) return rc;
+        ws_off.assign((size_t)N + 1, 0);
+        for (int f = 0; f < N; ++f) {
+            if (has_segs(f) && plans[f].mask) return bad(f, "a sample with segmentations must have a null mask");
+            ws_off[f + 1] = ws_off[f] + (has_segs(f) ? (int64_t)plans[f].src_h * plans[f].src_w : 0);
+        }
+        bytes += tab.bytes;
+        ws_at = (bytes + 255) & ~(size_t)255;
+        total = ws_at + (size_t)ws_off[N] * sizeof(float);
+    }
     if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = order_in(h);
     if (rc) return rc;
-    if (h->d_augment.size() < bytes) {
+    if (h->d_augment.size() < total) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
-        HIP_TRY(h, h->d_augment.ensure(bytes));
+        HIP_TRY(h, h->d_augment.ensure(total));
     }
     h->augment_stage.resize(bytes);
     unsigned char* host = h->augment_stage.data();
     unsigned char* dev = h->d_augment.as<unsigned char>();
     lwp_augment_plan* recs = reinterpret_cast<lwp_augment_plan*>(host);
     size_t at = ((size_t)N * sizeof(lwp_augment_plan) + 15) & ~(size_t)15;
+    if (crowd)
+        *crowd_launch = crowd_pack(tab, *crowd, N, size_of, has_segs, [&](int f) { return ws_off[f]; }, host + tab_at, dev + tab_at,
+                                   reinterpret_cast<float*>(dev + ws_at));
     for (int f = 0; f < N; ++f) {
         recs[f] = plans[f];
+        if (crowd && has_segs(f)) recs[f].mask = reinterpret_cast<const float*>(dev + ws_at) + ws_off[f];
         if (plans[f].mem != LWP_MEM_HOST) continue;
         const size_t ib = (size_t)plans[f].src_h * plans[f].src_w * 3, mb = (size_t)plans[f].src_h * plans[f].src_w * sizeof(float);
         memcpy(host + at, plans[f].image, ib);
@@ -2389,6 +2551,23 @@ extern "C" int lwp_augment_batch(lwp_handle h, const lwp_augment_plan* plans, in
     const lwp_augment_plan* d_plans = nullptr;
     int rc = augment_prepare(h, plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, &d_plans);
     if (rc) return rc;
+    LAUNCH(h, KC_OTHER, launch_augment(d_plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_augment_batch_crowd(lwp_handle h, const lwp_augment_plan* plans, int N, int crop_h, int crop_w, int stride,
+                                       const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off, float* image_out,
+                                       unsigned char* mask_out, float* mask_small_out) {
+    const lwp_augment_plan* d_plans = nullptr;
+    const CrowdRuns runs{counts, seg_off, image_seg_off};
+    CrowdLaunch c{};
+    int rc = augment_prepare(h, plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, &d_plans, &runs, &c);
+    if (rc) return rc;
+    LAUNCH(h, KC_OTHER, launch_crowd_masks(c, h->stream));           // the same stream: the augment kernel reads finished masks
     LAUNCH(h, KC_OTHER, launch_augment(d_plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, h->stream));
     bool ordered = false;
     rc = order_out(h, h->stream, &ordered);
@@ -3915,6 +4094,16 @@ extern "C" int lwp_time_augment_batch(lwp_handle h, const lwp_augment_plan* plan
     return time_on_stream(h, iters, [&]() {
         LAUNCH(h, KC_OTHER, launch_augment(d_plans, N, crop_h, crop_w, stride, image_out, mask_out, mask_small_out, h->stream));
         return (int)LWP_OK; }, ms_total);
+}
+
+extern "C" int lwp_time_crowd_masks(lwp_handle h, const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off,
+                                    const int* heights, const int* widths, int N, const int64_t* out_off, float* masks_device,
+                                    int iters, float* ms_total) {
+    if (!ms_total || iters <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    CrowdLaunch c{};
+    int rc = crowd_masks_prepare(h, CrowdRuns{counts, seg_off, image_seg_off}, heights, widths, N, out_off, masks_device, &c);
+    if (rc) return rc;
+    return time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_crowd_masks(c, h->stream)); return (int)LWP_OK; }, ms_total);
 }
 
 extern "C" int lwp_time_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps,

@@ -401,6 +401,22 @@ hipError_t launch_mask_downsample(const float* src, int N, int H, int W, int str
 // plans_device: N records whose image / mask pointers are device addresses
 hipError_t launch_augment(const lwp_augment_plan* plans_device, int N, int crop_h, int crop_w, int stride, float* image,
                           unsigned char* mask, float* mask_small, hipStream_t s);
+// ---- crowd masks (crowd_kernels.hip; datasets/coco.py:17-21): the float32 loss masks of a batch from uncompressed RLEs
+constexpr int kCrowdRunsLds = 4096;   // run ends of one image (all its segmentations) a workgroup stages in LDS; more: searched in global memory
+constexpr int kCrowdStrip = 8;        // rows of one column a thread renders: consecutive positions of the column-major runs
+struct CrowdImage {
+    unsigned seg0, n_seg;             // its segmentations: seg_off[seg0] .. seg_off[seg0 + n_seg] bound their run ends
+    int h, w;
+    long long out;                    // float offset of its h x w row-major mask
+};
+struct CrowdLaunch {
+    const unsigned* ends;             // running sums of the counts, per segmentation
+    const unsigned* seg_off;          // [S + 1] first run end of a segmentation
+    const CrowdImage* images;         // the images that are rendered
+    float* masks;
+    int n_images, max_h, max_w;
+};
+hipError_t launch_crowd_masks(const CrowdLaunch& c, hipStream_t s);
 // ---- COCO key-point evaluation (eval_kernels.hip; COCOeval with iouType 'keypoints' and its default parameters): float64
 constexpr int kEvalK = 17;            // key-points of a person
 constexpr int kEvalMaxDets = 20;      // detections of an image that count (maxDets)

@@ -1,17 +1,89 @@
 """Drop-in for the target side of the reference's ``datasets.coco`` (reference: datasets/coco.py:13-14, 48-61, 71-159): the
 key-point and PAF target maps and the down-sampled mask of ``CocoTrainDataset.__getitem__``, rendered on the GPU for a whole
 batch by ``lwp_train_targets`` / ``lwp_mask_downsample`` instead of the per-pixel Python loops of ``_add_gaussian`` /
-``_set_paf``.
+``_set_paf``.  Together with ``get_mask`` below (reference: datasets/coco.py:17-21, 38-39) and ``datasets.transformations`` this
+covers ``__getitem__`` from the mask on.
 
-Out of scope: reading images and annotations (``cv2.imread``, ``pycocotools``) and ``get_mask``.  Labels arrive in
+``get_mask`` is the reference's function in NumPy, the CPU path: it zeroes the crowd regions of a float mask from the
+``segmentations`` of a label, which ``scripts/prepare_train_labels.py`` collects from ``iscrowd`` annotations.  In scope is what
+COCO stores there, the uncompressed RLE dict ``{"counts": [c0, c1, ..], "size": [h, w]}``; a compressed ``counts`` string, a
+polygon or a box is a ValueError.  On the GPU the same masks come from ``Engine.crowd_masks`` (``pack_crowd_runs`` makes the
+arrays of the C call), and a sample of ``plan_batch`` / ``DeviceAugment`` / ``val.augmented_train_step`` may carry
+``"segmentations"`` instead of a float ``"mask"``: the mask is then rendered on the device and never crosses PCIe.  Both restate
+``maskApi.c``'s ``rleDecode`` and are unpinned against pycocotools itself.
+
+Out of scope: reading images and annotations (``cv2.imread``, ``pycocotools``).  Labels arrive in
 ``scripts/prepare_train_labels.py``'s format, as ``datasets.transformations`` (the augmentations, host classes and the device
 batch path) leaves them; ``generate_targets`` takes the float mask mean, ``val.augmented_train_step`` the reference's rounded
 uint8 mask.
 """
+import numbers
+
 import numpy as np
 
 BODY_PARTS_KPT_IDS = [[1, 8], [8, 9], [9, 10], [1, 11], [11, 12], [12, 13], [1, 2], [2, 3], [3, 4], [2, 16],
                       [1, 5], [5, 6], [6, 7], [5, 17], [1, 0], [0, 14], [0, 15], [14, 16], [15, 17]]
+
+
+def _rle_counts(segmentation, h, w, where):
+    """The counts of one uncompressed RLE dict as an int64 array, checked against an ``h`` x ``w`` image.  ``where`` names the
+    sample in the ValueError."""
+    if not isinstance(segmentation, dict) or "counts" not in segmentation or "size" not in segmentation:
+        raise ValueError("%s: expected an uncompressed RLE dict {'counts': [...], 'size': [h, w]}, got %s (polygons and boxes are "
+                         "out of scope)" % (where, type(segmentation).__name__))
+    counts = segmentation["counts"]
+    if isinstance(counts, (str, bytes)):
+        raise ValueError("%s: compressed RLE counts (a string) are out of scope" % where)
+    size = list(segmentation["size"])
+    if size != [h, w]:
+        raise ValueError("%s: an RLE of size %s does not belong to a %d x %d image" % (where, size, h, w))
+    try:
+        arr = np.asarray(counts)
+    except (ValueError, OverflowError):
+        arr = None
+    if arr is not None and arr.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if arr is None or arr.ndim != 1 or arr.dtype.kind not in "iu":       # find the value to name
+        for c in counts:
+            if isinstance(c, bool) or not isinstance(c, (numbers.Integral, np.integer)):
+                raise ValueError("%s: the count %r is not an integer" % (where, c))
+        arr = np.asarray([int(c) for c in counts], dtype=object)
+    if (arr < 0).any():
+        raise ValueError("%s: the count %r is negative" % (where, arr[arr < 0][0]))
+    total = int(arr.sum(dtype=object)) if arr.dtype != object else int(arr.sum())
+    if total > h * w:
+        raise ValueError("%s: the counts sum to %d, more than %d x %d" % (where, total, h, w))
+    return arr.astype(np.int64)
+
+
+def get_mask(segmentations, mask):
+    """coco.py:17-21: zeroes, in place, the pixels of ``mask`` (H, W) that any of the RLE dicts covers, and returns ``mask``.
+    The runs alternate between zeros and ones, start with zeros and walk the image column by column; what lies past the last
+    run is zeros.  Nothing is written when a segmentation is refused."""
+    h, w = int(mask.shape[0]), int(mask.shape[1])
+    runs = [_rle_counts(seg, h, w, "segmentation %d" % k) for k, seg in enumerate(segmentations)]
+    for counts in runs:
+        flat = np.zeros(h * w, dtype=bool)
+        flat[:int(counts.sum())] = np.repeat(np.arange(len(counts)) & 1, counts).astype(bool)
+        mask[flat.reshape(w, h).T] = 0
+    return mask
+
+
+def pack_crowd_runs(segmentations_per_image, sizes):
+    """The three host arrays of ``lwp_crowd_masks`` / ``lwp_augment_batch_crowd`` for a batch: ``counts`` (all counts, back to
+    back), ``seg_off`` (S + 1) and ``image_seg_off`` (N + 1), int64.  ``segmentations_per_image``: per image a list of RLE dicts
+    (``None`` counts as empty); ``sizes``: per image (height, width).  Raises the ValueErrors of ``get_mask``, naming the
+    sample."""
+    if len(segmentations_per_image) != len(sizes):
+        raise ValueError("%d lists of segmentations for %d sizes" % (len(segmentations_per_image), len(sizes)))
+    counts, seg_off, image_seg_off = [], [0], [0]
+    for n, (segs, (h, w)) in enumerate(zip(segmentations_per_image, sizes)):
+        for k, seg in enumerate(segs or []):
+            counts.append(_rle_counts(seg, int(h), int(w), "sample %d, segmentation %d" % (n, k)))
+            seg_off.append(seg_off[-1] + len(counts[-1]))
+        image_seg_off.append(len(seg_off) - 1)
+    flat = np.concatenate(counts) if counts else np.zeros(0, dtype=np.int64)
+    return flat.astype(np.int64), np.asarray(seg_off, dtype=np.int64), np.asarray(image_seg_off, dtype=np.int64)
 
 
 def labels_to_arrays(labels, K=18):

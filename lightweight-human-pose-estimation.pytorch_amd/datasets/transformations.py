@@ -17,7 +17,7 @@ import random
 
 import numpy as np
 
-from .coco import labels_to_arrays
+from .coco import _rle_counts, get_mask, labels_to_arrays, pack_crowd_runs
 
 MAX_DIM = 32768                      # OpenCV's remap coordinates saturate to short there: refused instead
 _F32 = np.float32
@@ -417,10 +417,16 @@ class BatchPlan(object):
     """What ``plan_batch`` returns.  ``records``: per sample the geometry dict (src_h, src_w, scale, rs_h, rs_w, rs_scale,
     area, minv (6 float64), bound_h, bound_w, warp_pad, crop_pad, should_crop, dst, src0, flip); ``images`` /
     ``masks``: the sources, untouched; ``labels``: the transformed label dicts; ``kpts`` (N, Pmax, 18, 3) float64 and
-    ``n_persons`` (N,) int32 in ``labels_to_arrays``' layout; ``crop_hw``."""
+    ``n_persons`` (N,) int32 in ``labels_to_arrays``' layout; ``crop_hw``; ``segmentations``: per sample its list of crowd RLE
+    dicts, or None where the sample came with a float mask or with neither (None for the whole batch: no sample has any);
+    ``crowd_runs``: ``pack_crowd_runs`` of them, made at construction (None when no sample has a segmentation)."""
 
-    def __init__(self, records, images, masks, labels, crop_hw):
+    def __init__(self, records, images, masks, labels, crop_hw, segmentations=None):
         self.records, self.images, self.masks, self.labels, self.crop_hw = records, images, masks, labels, crop_hw
+        self.segmentations = segmentations
+        self.crowd_runs = None                         # the arrays of the C call, packed once: the host half of the crowd masks
+        if segmentations is not None and any(segmentations):
+            self.crowd_runs = pack_crowd_runs(segmentations, [(g["src_h"], g["src_w"]) for g in records])
         self.kpts, self.n_persons = labels_to_arrays(labels)
 
     def __len__(self):
@@ -432,7 +438,10 @@ def plan_batch(samples, transforms, rng=None):
     ``random`` when None), its label arithmetic and its geometry.  ``transforms``: instances of the five classes in the
     reference's order; ``CropPad`` is required (it fixes the output size), the others may be left out.  No pixel is touched
     and the samples are not modified (labels are deep-copied).  A sample whose crop the reference cannot assign raises
-    ValueError here as it does there."""
+    ValueError here as it does there.  A sample may carry ``"segmentations"`` (a list of uncompressed RLE dicts, possibly
+    empty: ``label['segmentations']``) instead of a float ``"mask"``: its mask is ``get_mask`` of all ones, decoded by
+    ``apply_plan_host`` on the host and rendered by ``Engine.augment_batch`` on the device.  Both at once is a ValueError, and
+    so is an RLE that ``get_mask`` refuses."""
     rng = random if rng is None else rng
     kinds = [type(t) for t in transforms]
     places = [_ORDER.index(k) if k in _ORDER else -1 for k in kinds]
@@ -442,15 +451,22 @@ def plan_batch(samples, transforms, rng=None):
         raise ValueError("a batch needs a CropPad: it fixes the size every sample ends with")
     if len(samples) == 0:
         raise ValueError("no samples")
-    records, images, masks, labels = [], [], [], []
-    for sample in samples:
-        image, mask = sample["image"], sample.get("mask")
+    records, images, masks, labels, segmentations = [], [], [], [], []
+    for n, sample in enumerate(samples):
+        image, mask, segs = sample["image"], sample.get("mask"), sample.get("segmentations")
+        if mask is not None and segs is not None:
+            raise ValueError("sample %d carries both a mask and segmentations" % n)
         if len(image.shape) != 3 or image.shape[2] != 3:
             raise ValueError("expected an image of shape (H, W, 3), got %s" % (tuple(image.shape),))
         h, w = int(image.shape[0]), int(image.shape[1])
         if mask is not None and tuple(mask.shape) != (h, w):
             raise ValueError("a mask of shape %s does not belong to a %d x %d image" % (tuple(mask.shape), h, w))
         _check_dims(h, w)
+        if segs is not None:
+            segs = list(segs)
+            for k, seg in enumerate(segs):             # the checks of get_mask, before anything is planned
+                _rle_counts(seg, h, w, "sample %d, segmentation %d" % (n, k))
+        segmentations.append(segs)
         label = copy.deepcopy(sample["label"])
         g = {"src_h": h, "src_w": w, "scale": 1.0, "rs_h": h, "rs_w": w, "R": None, "bound_h": None, "warp_pad": (0, 0, 0),
              "flip": False}
@@ -471,7 +487,9 @@ def plan_batch(samples, transforms, rng=None):
         masks.append(mask)
         labels.append(label)
     crops = set((g["crop_h"], g["crop_w"]) for g in records)
-    return BatchPlan(records, images, masks, labels, crops.pop())
+    if all(segs is None for segs in segmentations):
+        segmentations = None
+    return BatchPlan(records, images, masks, labels, crops.pop(), segmentations)
 
 
 def _to_numpy(a, dtype):
@@ -490,6 +508,8 @@ def apply_plan_host(plan, stride=8):
     for n, g in enumerate(plan.records):
         img = _to_numpy(plan.images[n], np.uint8)
         m = np.ones(img.shape[:2], dtype=np.float32) if plan.masks[n] is None else _to_numpy(plan.masks[n], np.float32)
+        if plan.segmentations is not None and plan.segmentations[n]:
+            m = get_mask(plan.segmentations[n], m)
         img, m = resize_linear(img, g["scale"]), resize_linear(m, g["scale"])
         dsize = (g["bound_w"], g["bound_h"])
         img = warp_affine(img, g["minv"], dsize, g["warp_pad"], inverse=True)

@@ -722,7 +722,9 @@ class Engine(object):
         Sources may be NumPy arrays (packed, one upload for the batch) or cuda uint8 / float32 tensors (read in place).
         Returns four cuda tensors: ``image`` (N, 3, cy, cx) float32 = (pixel - 128) / 256, ``mask`` (N, cy, cx) uint8,
         ``mask_small`` (N, cy // stride, cx // stride) float32 (coco.py:48 on the uint8 mask) and ``kpts`` (N, Pmax, 18, 3)
-        float64, the transformed key-points as ``train_targets`` takes them (person counts: the plan's ``n_persons``).  With
+        float64, the transformed key-points as ``train_targets`` takes them (person counts: the plan's ``n_persons``).  Where a
+        sample carries ``"segmentations"`` (crowd RLE dicts) instead of a float mask, its mask is rendered on the device from the
+        runs (``lwp_augment_batch_crowd``) and read in place; a batch without any takes ``lwp_augment_batch``.  With
         ``time_iters`` > 0 the kernels are launched that many times back to back and the call returns their milliseconds."""
         torch = _torch()
         from ._lib import AugmentPlan
@@ -773,12 +775,47 @@ class Engine(object):
         small = torch.empty((N, cy // stride, cx // stride), dtype=torch.float32, device=dev)
         self._order()
         args = (self.h.ptr, recs, N, cy, cx, stride, image.data_ptr(), mask.data_ptr(), small.data_ptr())
+        if getattr(plan, "crowd_runs", None) is not None:
+            if time_iters:
+                raise ValueError("a batch with segmentations has no timing twin: time crowd_masks, and augment_batch without them")
+            counts, seg_off, image_seg_off = plan.crowd_runs
+            i64p = C.POINTER(C.c_int64)
+            check(lib().lwp_augment_batch_crowd(*args[:6], counts.ctypes.data_as(i64p), seg_off.ctypes.data_as(i64p),
+                                                image_seg_off.ctypes.data_as(i64p), *args[6:]), self.h.ptr)
+            return image, mask, small, torch.from_numpy(plan.kpts).to(dev)
         if time_iters:
             ms = C.c_float()
             check(lib().lwp_time_augment_batch(*args, int(time_iters), C.byref(ms)), self.h.ptr)
             return ms.value
         check(lib().lwp_augment_batch(*args), self.h.ptr)
         return image, mask, small, torch.from_numpy(plan.kpts).to(dev)
+
+    def crowd_masks(self, segmentations_per_image, sizes, time_iters=0):
+        """``get_mask`` (coco.py:17-21) of all-ones masks for a batch, in one kernel launch.  ``segmentations_per_image``: per
+        image a list of uncompressed RLE dicts (possibly empty); ``sizes``: per image (height, width).  Returns a list of
+        (H, W) float32 cuda tensors, views of ONE buffer: 1 where no segmentation covers the pixel, 0 where any does.  With
+        ``time_iters`` > 0 the kernel is launched that many times back to back and the call returns the milliseconds of all of
+        them (HIP events)."""
+        torch = _torch()
+        from .datasets.coco import pack_crowd_runs
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        counts, seg_off, image_seg_off = pack_crowd_runs(segmentations_per_image, sizes)
+        N = len(sizes)
+        heights = np.array([h for h, _ in sizes], dtype=np.int32)
+        widths = np.array([w for _, w in sizes], dtype=np.int32)
+        out_off = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(heights.astype(np.int64) * widths, out=out_off[1:])
+        buf = torch.empty((max(int(out_off[-1]), 1),), dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        self._order()
+        i64p, ip = C.POINTER(C.c_int64), C.POINTER(C.c_int)
+        args = (self.h.ptr, counts.ctypes.data_as(i64p), seg_off.ctypes.data_as(i64p), image_seg_off.ctypes.data_as(i64p),
+                heights.ctypes.data_as(ip), widths.ctypes.data_as(ip), N, out_off.ctypes.data_as(i64p), buf.data_ptr())
+        if time_iters:
+            ms = C.c_float()
+            check(lib().lwp_time_crowd_masks(*args, int(time_iters), C.byref(ms)), self.h.ptr)
+            return ms.value
+        check(lib().lwp_crowd_masks(*args), self.h.ptr)
+        return [buf[int(out_off[n]):int(out_off[n + 1])].view(h, w) for n, (h, w) in enumerate(sizes)]
 
     def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
         """train.py:92-97's per-stage sums: ``outs`` is the list net(x) returned (cuda tensors; an entry may be None),

@@ -163,7 +163,8 @@ def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=
 
 
 def augmented_train_step(net, opt, samples, augment, batches_per_iter=1, sigma=7, paf_thickness=1):
-    """``train_step`` from RAW samples (image uint8 (H, W, 3), mask float32 (H, W) or None, label dict): ``augment``, a
+    """``train_step`` from RAW samples (image uint8 (H, W, 3), label dict, and a mask float32 (H, W), or ``"segmentations"``,
+    the label's crowd RLE dicts, from which the mask is rendered on the device, or neither): ``augment``, a
     ``datasets.transformations.DeviceAugment``, draws the random numbers and moves the labels on the host and renders the
     crops on the GPU; its ``image``, ``kpts`` and ``mask_small`` feed the same targets, retaining forward, losses, backward
     and optimiser step as ``train_step``.  The small mask is the reference's (coco.py:48 on the uint8 mask CropPad leaves,
