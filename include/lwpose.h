@@ -696,6 +696,59 @@ int lwp_debug_coco_oks(lwp_handle h, int n_images, const int64_t* dt_off, const 
                        const int* gt_ignore, int image, int* n_sel, int* order, double* oks, int64_t oks_cap, unsigned char* matched,
                        unsigned char* ignored, int* npig3);
 
+/* ---- device-resident validation: the detection loop of val.py:113-160 without a fetch.  A DETECTION STORE on the device takes
+ *      the poses of every validated image straight from the grouping's result block (val.py:52-78 restated by an append
+ *      kernel), the ground truth is uploaded once per data set, and lwp_coco_finish runs the kernels of lwp_coco_eval on the
+ *      store: no per-image synchronise, no Python object between the grouping and AP / AR.
+ *      lwp_coco_open: the ground-truth arrays exactly as lwp_coco_eval takes them (HOST; the same checks, with a NULL handle too),
+ *      uploaded once, and a store of row_cap >= 0 detection rows ([17][3] float64 key-points, a float64 score, the image index)
+ *      with per-image start / count tables, a row cursor and a sticky status word, all on the device.  A second open replaces
+ *      the first; lwp_coco_release frees everything (so does lwp_destroy; a release without a store is LWP_OK).  The memory
+ *      shows in lwp_debug_live_resources.  lwp_coco_reset forgets the detections and the status and keeps the ground truth.
+ *      lwp_coco_add_maps: arguments and checks of lwp_poses_from_maps for DEVICE maps; image_index[N] (HOST) is frame f's
+ *      position in the ground truth's ascending image-id order.  Enqueues the grouping on the serial workspace and the append
+ *      kernel behind it and RETURNS WITHOUT SYNCHRONISING: under lwp_set_stream the caller's stream is ordered before and behind
+ *      it, as for lwp_infer_poses_async.  Frame f's rows follow frame f - 1's, in entry order (no atomic places a row; COCOeval
+ *      breaks score ties by this order).  A pose row is 17 x (x + 0.5, y + 0.5, 1.0) in COCO's key-point order, (0, 0, 0) for a
+ *      key-point that was not found (the neck has no slot); its score is entry[18] * max(0, entry[19] - 1), one float64
+ *      multiply.  Checked on the host before anything is enqueued: LWP_ERR_STATE without a store, for an image that was
+ *      already added (the message names it), under a custom skeleton (COCO's mapping is defined for the default 18 / 19 / 20
+ *      only) and with tracking mode 2 or 3 on (no lane may advance on validation frames); LWP_ERR_ARG for an index outside
+ *      0 .. n_images - 1.  The serial workspace then holds nothing to fetch: a following lwp_fetch_poses is LWP_ERR_STATE.
+ *      lwp_coco_add_rows: n >= 0 ready-made rows (HOST, finite) of one image through the same cursor; enqueue only.
+ *      Host arrays of both add calls (the image indices, the rows) reach the kernels through a pinned ring of 1 MiB, grown to the
+ *      largest single request: the ONE exception to "no synchronise" is that a call which finds the ring full waits for the
+ *      stream once before it reuses the ring from its start (about every 2500 rows of lwp_coco_add_rows, every 65 000 calls of
+ *      lwp_coco_add_maps with a few frames each).
+ *      STATUS: what a fetch would have reported is kept on the device, the first error wins, and lwp_coco_counts / lwp_coco_rows /
+ *      lwp_coco_finish return it until lwp_coco_reset: a frame whose grouping overflowed a capacity is LWP_ERR_CAPACITY (the
+ *      message names the image and the bits), the reference's unbound 'ratio' LWP_ERR_UNBOUND, a non-finite value
+ *      LWP_ERR_ARG.  Rows beyond row_cap are not written while the cursor keeps counting: LWP_ERR_CAPACITY, and the message
+ *      names the row_cap that would have fitted.
+ *      lwp_coco_counts: *n_rows and, unless NULL, per_image_counts[n_images].  lwp_coco_rows: the rows IN THE EVALUATION'S ORDER
+ *      (images ascending, within an image the order they were added): dt_image [n], dt_kp [n][17][3], dt_score [n] for the n
+ *      rows lwp_coco_counts reported; row_cap is what the arrays hold (LWP_ERR_CAPACITY below n).  Each of the two synchronises
+ *      once: lwp_coco_rows forms the offsets on the device, so the tables and the gathered rows come back together.
+ *      lwp_coco_finish: one copy of the tables (counts and status), the host forms the offsets, a gather kernel compacts the store
+ *      into lwp_coco_eval's layout in scratch, then the same match / sort / accumulate launches and one copy back: outputs as
+ *      lwp_coco_eval's, bit for bit equal to it on the same rows.  The store is left intact: finish twice returns the same
+ *      bits, and finish, more adds, finish is allowed. */
+int lwp_coco_open(lwp_handle h, int n_images, const int64_t* gt_off, const double* gt_kp, const double* gt_area, const double* gt_bbox,
+                  const int* gt_iscrowd, const int* gt_ignore, int row_cap);
+int lwp_coco_release(lwp_handle h);
+int lwp_coco_reset(lwp_handle h);
+int lwp_coco_add_maps(lwp_handle h, const float* heat, const float* paf, int layout, int N, int hs, int ws, int upsample_ratio,
+                      int demo, const int* image_index);
+int lwp_coco_add_rows(lwp_handle h, int image_index, int n, const double* dt_kp, const double* dt_score);
+int lwp_coco_counts(lwp_handle h, int64_t* n_rows, int* per_image_counts);
+int lwp_coco_rows(lwp_handle h, int* dt_image, double* dt_kp, double* dt_score, int64_t row_cap);
+int lwp_coco_finish(lwp_handle h, double* precision, double* recall, double* scores, int64_t* npig);
+/* the append kernel alone, for tests: N frames of host pose entries (frame f's n_entries[f] rows of 20 doubles, back to back)
+ * and key-point rows (kpt_counts[f] rows of 4 doubles, back to back) are loaded into the serial workspace's result block, then
+ * appended as image_index[N] like the frames of lwp_coco_add_maps; synchronises. */
+int lwp_debug_coco_rows(lwp_handle h, int N, const double* entries, const int* n_entries, const double* kpts, const int* kpt_counts,
+                        const int* image_index);
+
 /* ---- measurement helpers (bench.py): time `iters` back-to-back enqueues with HIP events on the
  *      handle's own stream.  what: 0 = forward only, 1 = full infer_poses.  ms_total out. */
 int lwp_time_pipeline(lwp_handle h, const float* in_device, int N, int H, int W, int upsample_ratio,

@@ -40,6 +40,8 @@ EXPORTS = [
     "lwp_augment_batch", "lwp_time_augment_batch",
     "lwp_crowd_masks", "lwp_time_crowd_masks", "lwp_augment_batch_crowd",
     "lwp_coco_eval", "lwp_debug_coco_oks",
+    "lwp_coco_open", "lwp_coco_release", "lwp_coco_reset", "lwp_coco_add_maps", "lwp_coco_add_rows", "lwp_coco_counts",
+    "lwp_coco_rows", "lwp_coco_finish", "lwp_debug_coco_rows",
 ]
 
 
@@ -173,6 +175,15 @@ def lib():
     coco_in = [vp, C.c_int, i64p, dp, dp, i64p, dp, dp, dp, ip, ip]
     L.lwp_coco_eval.argtypes = coco_in + [dp, dp, dp, i64p]
     L.lwp_debug_coco_oks.argtypes = coco_in + [C.c_int, ip, ip, dp, C.c_int64, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), ip]
+    L.lwp_coco_open.argtypes = [vp, C.c_int, i64p, dp, dp, dp, ip, ip, C.c_int]
+    L.lwp_coco_release.argtypes = [vp]
+    L.lwp_coco_reset.argtypes = [vp]
+    L.lwp_coco_add_maps.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [ip]
+    L.lwp_coco_add_rows.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    L.lwp_coco_counts.argtypes = [vp, i64p, ip]
+    L.lwp_coco_rows.argtypes = [vp, ip, dp, dp, C.c_int64]
+    L.lwp_coco_finish.argtypes = [vp, dp, dp, dp, i64p]
+    L.lwp_debug_coco_rows.argtypes = [vp, C.c_int, dp, ip, dp, ip, ip]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

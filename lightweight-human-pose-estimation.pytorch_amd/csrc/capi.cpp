@@ -128,6 +128,19 @@ struct lwp_context {
     int64_t adam_t = 0;
     DevBuf d_adam_chunks; int adam_chunks = 0;
     DevBuf d_repack; int repack_layers = 0, repack_blocks = 0;
+    // detection store (lwp_coco_open): the resident ground truth [gt_off | gt_kp | gt_area | gt_bbox | gt_iscrowd | gt_ignore],
+    // the rows [kp | score | image], the tables [control words | count | start], and a pinned ring through which host rows and
+    // image indices reach the append kernels without a synchronise
+    struct CocoStoreMem {
+        bool open = false;
+        DevBuf gt, rows, meta;
+        PinBuf ring; size_t ring_used = 0;
+        CocoStore st{};
+        int64_t NG = 0;
+        size_t o_kp = 0, o_area = 0, o_bbox = 0, o_crowd = 0, o_ignore = 0;     // byte offsets into gt (gt_off is at 0)
+        std::vector<int64_t> gt_off;                 // host copy: the OKS offsets of an evaluation need G per image
+        std::vector<char> added;                     // per image: rows were appended since the last reset
+    } coco;
     bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
@@ -235,7 +248,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 104; }
+extern "C" int lwp_version(void) { return 105; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -2582,6 +2595,7 @@ struct CocoEvalRun {
     DevBuf in, scratch;
     CocoEvalParams p{};
     std::vector<int64_t> sel_off, oks_off;
+    std::vector<unsigned char> stage;                  // host side of the upload: alive until the run has synchronised
     // the accumulation's order (not needed by the debug twin)
     unsigned long long *keys = nullptr, *keys_out = nullptr;
     unsigned int *vals = nullptr, *perm = nullptr;
@@ -2594,12 +2608,13 @@ struct CocoEvalInput {
     const int64_t* gt_off; const double* gt_kp; const double* gt_area; const double* gt_bbox; const int* gt_iscrowd; const int* gt_ignore;
 };
 
-static int coco_eval_check(lwp_handle h, const CocoEvalInput& in) {
+// gt_only: the ground-truth half alone (lwp_coco_open), same rules and wording
+static int coco_eval_check(lwp_handle h, const CocoEvalInput& in, bool gt_only = false) {
     char msg[200];
-    if (!in.dt_off || !in.gt_off) return fail(h, LWP_ERR_ARG, "dt_off / gt_off is null");
+    if (gt_only ? !in.gt_off : (!in.dt_off || !in.gt_off)) return fail(h, LWP_ERR_ARG, gt_only ? "gt_off is null" : "dt_off / gt_off is null");
     if (in.n_images < 1) return fail(h, LWP_ERR_ARG, "n_images must be at least 1");
     const int64_t lim = (int64_t)1 << 31;
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = gt_only ? 1 : 0; pass < 2; ++pass) {
         const int64_t* off = pass ? in.gt_off : in.dt_off;
         const char* what = pass ? "gt_off" : "dt_off";
         if (off[0] != 0) { snprintf(msg, sizeof msg, "%s[0] must be 0", what); return fail(h, LWP_ERR_ARG, msg); }
@@ -2607,7 +2622,7 @@ static int coco_eval_check(lwp_handle h, const CocoEvalInput& in) {
             if (off[i + 1] < off[i]) { snprintf(msg, sizeof msg, "%s descends at image %d", what, i); return fail(h, LWP_ERR_ARG, msg); }
         if (off[in.n_images] >= lim) { snprintf(msg, sizeof msg, "%s: 2^31 rows or more", what); return fail(h, LWP_ERR_ARG, msg); }
     }
-    const int64_t ND = in.dt_off[in.n_images], NG = in.gt_off[in.n_images];
+    const int64_t ND = gt_only ? 0 : in.dt_off[in.n_images], NG = in.gt_off[in.n_images];
     if (ND > 0 && (!in.dt_kp || !in.dt_score)) return fail(h, LWP_ERR_ARG, "dt_kp / dt_score is null");
     if (NG > 0 && (!in.gt_kp || !in.gt_area || !in.gt_bbox || !in.gt_iscrowd || !in.gt_ignore))
         return fail(h, LWP_ERR_ARG, "gt_kp / gt_area / gt_bbox / gt_iscrowd / gt_ignore is null");
@@ -2623,7 +2638,26 @@ static int coco_eval_check(lwp_handle h, const CocoEvalInput& in) {
     return LWP_OK;
 }
 
-// checks, the one upload, scratch, and the per-image kernel; with_order: the sort buffers of the accumulation too
+// first selected detection and first OKS entry of every image, the defaults and the sizes: what both ways of staging share
+static void coco_eval_offsets(int n, const int64_t* dt_off, const int64_t* gt_off, CocoEvalRun* run) {
+    run->sel_off.assign((size_t)n + 1, 0);
+    run->oks_off.assign((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        const int64_t D = dt_off[i + 1] - dt_off[i], G = gt_off[i + 1] - gt_off[i];
+        const int64_t Ds = std::min<int64_t>(D, kEvalMaxDets);
+        run->sel_off[i + 1] = run->sel_off[i] + Ds;
+        run->oks_off[i + 1] = run->oks_off[i] + Ds * G;
+    }
+    coco_eval_defaults(&run->p);
+    run->p.n_images = n; run->p.NG = gt_off[n]; run->p.NS = run->sel_off[n];
+}
+
+static int coco_eval_launch(lwp_handle h, bool with_order, CocoEvalRun* run);
+static int coco_eval_accumulate(lwp_handle h, const CocoEvalRun& run, double* precision, double* recall, double* scores, int64_t* npig);
+
+// "stage the inputs" of lwp_coco_eval and its debug twin: checks and the one upload of host arrays; then "scratch + launch"
+// (coco_eval_launch: scratch and the per-image kernel; with_order: the sort buffers of the accumulation too), which
+// lwp_coco_finish shares
 static int coco_eval_match(lwp_handle h, const CocoEvalInput& in, bool with_order, CocoEvalRun* run) {
     int rc = coco_eval_check(h, in);
     if (rc) return rc;
@@ -2633,20 +2667,10 @@ static int coco_eval_match(lwp_handle h, const CocoEvalInput& in, bool with_orde
     if (rc) return rc;
     const int n = in.n_images;
     const int64_t ND = in.dt_off[n], NG = in.gt_off[n];
-    run->sel_off.assign((size_t)n + 1, 0);
-    run->oks_off.assign((size_t)n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        const int64_t D = in.dt_off[i + 1] - in.dt_off[i], G = in.gt_off[i + 1] - in.gt_off[i];
-        const int64_t Ds = std::min<int64_t>(D, kEvalMaxDets);
-        run->sel_off[i + 1] = run->sel_off[i] + Ds;
-        run->oks_off[i + 1] = run->oks_off[i] + Ds * G;
-    }
-    const int64_t NS = run->sel_off[n], NO = run->oks_off[n];
+    coco_eval_offsets(n, in.dt_off, in.gt_off, run);
     CocoEvalParams& p = run->p;
-    coco_eval_defaults(&p);
-    p.n_images = n; p.NG = NG; p.NS = NS;
 
-    // sections of the two allocations, each 16-byte aligned
+    // sections of the allocation, each 16-byte aligned
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
     const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
@@ -2655,14 +2679,31 @@ static int coco_eval_match(lwp_handle h, const CocoEvalInput& in, bool with_orde
     const size_t i_gt_kp = take((size_t)NG * kEvalK * 3 * 8), i_gt_area = take((size_t)NG * 8), i_gt_bbox = take((size_t)NG * 4 * 8);
     const size_t i_gt_crowd = take((size_t)NG * 4), i_gt_ignore = take((size_t)NG * 4);
     const size_t in_bytes = std::max<size_t>(at, 16);
-    std::vector<unsigned char> stage(in_bytes);
+    std::vector<unsigned char>& stage = run->stage;
+    stage.assign(in_bytes, 0);
     auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(stage.data() + off, src, bytes); };
     put(i_dt_off, in.dt_off, nb); put(i_gt_off, in.gt_off, nb); put(i_sel_off, run->sel_off.data(), nb); put(i_oks_off, run->oks_off.data(), nb);
     put(i_dt_kp, in.dt_kp, (size_t)ND * kEvalK * 3 * 8); put(i_dt_score, in.dt_score, (size_t)ND * 8);
     put(i_gt_kp, in.gt_kp, (size_t)NG * kEvalK * 3 * 8); put(i_gt_area, in.gt_area, (size_t)NG * 8); put(i_gt_bbox, in.gt_bbox, (size_t)NG * 4 * 8);
     put(i_gt_crowd, in.gt_iscrowd, (size_t)NG * 4); put(i_gt_ignore, in.gt_ignore, (size_t)NG * 4);
+    HIP_TRY(h, run->in.ensure(in_bytes));
+    unsigned char* di = run->in.as<unsigned char>();
+    HIP_TRY(h, hipMemcpyAsync(di, stage.data(), in_bytes, hipMemcpyHostToDevice, h->stream));
+    p.dt_off = (const int64_t*)(di + i_dt_off); p.gt_off = (const int64_t*)(di + i_gt_off);
+    p.sel_off = (const int64_t*)(di + i_sel_off); p.oks_off = (const int64_t*)(di + i_oks_off);
+    p.dt_kp = (const double*)(di + i_dt_kp); p.dt_score = (const double*)(di + i_dt_score);
+    p.gt_kp = (const double*)(di + i_gt_kp); p.gt_area = (const double*)(di + i_gt_area); p.gt_bbox = (const double*)(di + i_gt_bbox);
+    p.gt_iscrowd = (const int*)(di + i_gt_crowd); p.gt_ignore = (const int*)(di + i_gt_ignore);
+    return coco_eval_launch(h, with_order, run);
+}
 
-    at = 0;
+// run->p holds the sizes and the input pointers (host arrays staged by coco_eval_match, or the store's by lwp_coco_finish)
+static int coco_eval_launch(lwp_handle h, bool with_order, CocoEvalRun* run) {
+    CocoEvalParams& p = run->p;
+    const int n = p.n_images;
+    const int64_t NG = p.NG, NS = p.NS, NO = run->oks_off[n];
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
     const size_t s_gt_m = take((size_t)kEvalAT * NG);                       // first: the part that is zeroed
     const size_t zero_bytes = at;
     const size_t s_sel_idx = take((size_t)NS * 4), s_sel_score = take((size_t)NS * 8), s_oks = take((size_t)NO * 8);
@@ -2677,17 +2718,9 @@ static int coco_eval_match(lwp_handle h, const CocoEvalInput& in, bool with_orde
         s_tmp = take(run->sort_tmp_bytes);
     }
     const size_t scratch_bytes = std::max<size_t>(at, 16);
-    HIP_TRY(h, run->in.ensure(in_bytes));
     HIP_TRY(h, run->scratch.ensure(scratch_bytes));
-    unsigned char* di = run->in.as<unsigned char>();
     unsigned char* ds = run->scratch.as<unsigned char>();
-    HIP_TRY(h, hipMemcpyAsync(di, stage.data(), in_bytes, hipMemcpyHostToDevice, h->stream));
     if (zero_bytes) HIP_TRY(h, hipMemsetAsync(ds + s_gt_m, 0, zero_bytes, h->stream));
-    p.dt_off = (const int64_t*)(di + i_dt_off); p.gt_off = (const int64_t*)(di + i_gt_off);
-    p.sel_off = (const int64_t*)(di + i_sel_off); p.oks_off = (const int64_t*)(di + i_oks_off);
-    p.dt_kp = (const double*)(di + i_dt_kp); p.dt_score = (const double*)(di + i_dt_score);
-    p.gt_kp = (const double*)(di + i_gt_kp); p.gt_area = (const double*)(di + i_gt_area); p.gt_bbox = (const double*)(di + i_gt_bbox);
-    p.gt_iscrowd = (const int*)(di + i_gt_crowd); p.gt_ignore = (const int*)(di + i_gt_ignore);
     p.gt_m = ds + s_gt_m; p.sel_idx = (int*)(ds + s_sel_idx); p.sel_score = (double*)(ds + s_sel_score); p.oks = (double*)(ds + s_oks);
     p.gt_flag = ds + s_gt_flag; p.dt_m = ds + s_dt_m; p.dt_ig = ds + s_dt_ig; p.npig_img = (int*)(ds + s_npig_img);
     p.precision = (double*)(ds + s_out); p.scores = p.precision + kEvalT * kEvalR * kEvalA;
@@ -2712,6 +2745,11 @@ extern "C" int lwp_coco_eval(lwp_handle h, int n_images, const int64_t* dt_off, 
     CocoEvalRun run;
     int rc = coco_eval_match(h, in, true, &run);
     if (rc) return rc;
+    return coco_eval_accumulate(h, run, precision, recall, scores, npig);
+}
+
+// the order of the selected detections, accumulate, and the one copy back: behind coco_eval_launch(with_order = true)
+static int coco_eval_accumulate(lwp_handle h, const CocoEvalRun& run, double* precision, double* recall, double* scores, int64_t* npig) {
     const CocoEvalParams& p = run.p;
     LAUNCH(h, KC_OTHER, launch_coco_sort(p.sel_score, p.NS, run.keys, run.keys_out, run.vals, run.perm, run.sort_tmp, run.sort_tmp_bytes, h->stream));
     LAUNCH(h, KC_OTHER, launch_coco_accumulate(p, h->stream));
@@ -2761,6 +2799,420 @@ extern "C" int lwp_debug_coco_oks(lwp_handle h, int n_images, const int64_t* dt_
         }
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- detection store
+static void coco_store_free(lwp_context* h) {
+    auto& c = h->coco;
+    (void)c.gt.reset(); (void)c.rows.reset(); (void)c.meta.reset(); (void)c.ring.reset();
+    c.open = false; c.ring_used = 0; c.st = CocoStore(); c.NG = 0;
+    c.gt_off.clear(); c.added.clear();
+}
+
+extern "C" int lwp_coco_open(lwp_handle h, int n_images, const int64_t* gt_off, const double* gt_kp, const double* gt_area,
+                             const double* gt_bbox, const int* gt_iscrowd, const int* gt_ignore, int row_cap) {
+    const CocoEvalInput in{n_images, nullptr, nullptr, nullptr, gt_off, gt_kp, gt_area, gt_bbox, gt_iscrowd, gt_ignore};
+    int rc = coco_eval_check(h, in, true);
+    if (rc) return rc;
+    if (row_cap < 0) return fail(h, LWP_ERR_ARG, "row_cap must not be negative");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // a second open replaces the first: nothing reads the old store any more
+    coco_store_free(h);
+    auto& c = h->coco;
+    const int n = n_images;
+    const int64_t NG = gt_off[n];
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
+    const size_t o_off = take(nb);
+    c.o_kp = take((size_t)NG * kEvalK * 3 * 8); c.o_area = take((size_t)NG * 8); c.o_bbox = take((size_t)NG * 4 * 8);
+    c.o_crowd = take((size_t)NG * 4); c.o_ignore = take((size_t)NG * 4);
+    std::vector<unsigned char> stage(std::max<size_t>(at, 16));
+    auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(stage.data() + off, src, bytes); };
+    put(o_off, gt_off, nb); put(c.o_kp, gt_kp, (size_t)NG * kEvalK * 3 * 8); put(c.o_area, gt_area, (size_t)NG * 8);
+    put(c.o_bbox, gt_bbox, (size_t)NG * 4 * 8); put(c.o_crowd, gt_iscrowd, (size_t)NG * 4); put(c.o_ignore, gt_ignore, (size_t)NG * 4);
+    // rows: kp | score | image; tables: control words | count | start
+    const size_t R = (size_t)row_cap;
+    const size_t r_score = (R * kEvalK * 3 * 8 + 15) & ~(size_t)15, r_image = r_score + ((R * 8 + 15) & ~(size_t)15);
+    const size_t rows_bytes = std::max<size_t>(r_image + R * 4, 16);
+    const size_t m_count = 4 * sizeof(long long), m_start = m_count + (size_t)n * 4, meta_bytes = m_start + (size_t)n * 4;
+    hipError_t e = c.gt.ensure(stage.size());
+    if (e == hipSuccess) e = c.rows.ensure(rows_bytes);
+    if (e == hipSuccess) e = c.meta.ensure(meta_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.gt.as<void>(), stage.data(), stage.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c.meta.as<void>(), 0, meta_bytes, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the staging vector goes out of scope
+    if (e != hipSuccess) { coco_store_free(h); return fail(h, LWP_ERR_HIP, std::string("lwp_coco_open: ") + hipGetErrorString(e)); }
+    char* r = c.rows.as<char>();
+    char* m = c.meta.as<char>();
+    c.st.kp = (double*)r; c.st.score = (double*)(r + r_score); c.st.image = (int*)(r + r_image);
+    c.st.ctl = (long long*)m; c.st.count = (int*)(m + m_count); c.st.start = (int*)(m + m_start);
+    c.st.row_cap = row_cap; c.st.n_images = n;
+    c.NG = NG;
+    c.gt_off.assign(gt_off, gt_off + n + 1);
+    c.added.assign((size_t)n, 0);
+    c.open = true;
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_release(lwp_handle h) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (!h->coco.open) return LWP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    coco_store_free(h);
+    return LWP_OK;
+}
+
+static int coco_need_store(lwp_context* h) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (!h->coco.open) return fail(h, LWP_ERR_STATE, "no detection store is open (lwp_coco_open)");
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_reset(lwp_handle h) {
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    auto& c = h->coco;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemsetAsync(c.meta.as<void>(), 0, 4 * sizeof(long long) + (size_t)c.st.n_images * 8, h->stream));   // cursor, status, count, start
+    c.added.assign(c.added.size(), 0);
+    return LWP_OK;
+}
+
+// host bytes -> pinned ring -> *dev, the address the kernels of this stream read them at.  The ring is reused from its start
+// once it is full, after one synchronise: everything queued so far has read its part by then.
+static int coco_ring_put(lwp_context* h, const void* src, size_t bytes, const void** dev) {
+    auto& c = h->coco;
+    *dev = nullptr;
+    if (bytes == 0) return LWP_OK;                     // nothing to carry (an image without a detection): the kernel reads nothing
+    const size_t need = (bytes + 15) & ~(size_t)15;
+    if (c.ring.size() < need || c.ring_used + need > c.ring.size()) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, c.ring.ensure(std::max<size_t>(need, (size_t)1 << 20)));
+        c.ring_used = 0;
+    }
+    memcpy(c.ring.as<char>() + c.ring_used, src, bytes);
+    void* mapped = nullptr;
+    HIP_TRY(h, hipHostGetDevicePointer(&mapped, c.ring.as<void>(), 0));
+    *dev = (const char*)mapped + c.ring_used;
+    c.ring_used += need;
+    return LWP_OK;
+}
+
+// the image indices of one call: in range, not added before, no index twice
+static int coco_add_check(lwp_context* h, int N, const int* image_index) {
+    auto& c = h->coco;
+    char msg[200];
+    for (int f = 0; f < N; ++f) {
+        const int i = image_index[f];
+        if (i < 0 || i >= c.st.n_images) {
+            snprintf(msg, sizeof msg, "image_index[%d] = %d is outside the ground truth's 0..%d", f, i, c.st.n_images - 1);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+    }
+    for (int f = 0; f < N; ++f) {
+        const int i = image_index[f];
+        bool twice = c.added[i] != 0;
+        for (int g = 0; g < f && !twice; ++g) twice = image_index[g] == i;
+        if (twice) {
+            snprintf(msg, sizeof msg, "image %d was already added (lwp_coco_reset forgets the detections)", i);
+            return fail(h, LWP_ERR_STATE, msg);
+        }
+    }
+    return LWP_OK;
+}
+
+// the serial workspace holds frames nobody may fetch: as after lwp_track_poses
+static void coco_claim_serial_ws(lwp_context* h) {
+    h->stage_tail_N = 0; h->run_has_tail = false;
+    h->last_N = 0; h->async_pending = false;
+}
+
+// the append kernel on the N frames the grouping (or lwp_debug_coco_rows) left in the serial workspace
+static int coco_enqueue_append(lwp_context* h, int N, const int* image_index) {
+    auto& c = h->coco;
+    const void* d_index = nullptr;
+    int rc = coco_ring_put(h, image_index, (size_t)N * sizeof(int), &d_index);
+    if (rc) return rc;
+    const PostWorkspace& w = h->ws;
+    CocoAppendParams p{};
+    p.flags = w.flags; p.kpts_out = w.kpts_out; p.entries = w.entries; p.n_entries = w.n_entries;
+    p.image_index = (const int*)d_index;
+    p.N = N; p.max_entries = w.caps.max_entries; p.max_rows = w.K * w.caps.max_kpts;
+    LAUNCH(h, KC_POST, launch_coco_append(c.st, p, h->stream));
+    for (int f = 0; f < N; ++f) c.added[image_index[f]] = 1;
+    return LWP_OK;
+}
+
+static int coco_default_skeleton(lwp_context* h) {
+    if (!h->skel.is_default || h->skel.K != kCocoTypes || h->skel.E != kCocoEntry)
+        return fail(h, LWP_ERR_STATE, "the detection store maps the default skeleton (18 key-point types, rows of 20) to COCO's 17 key-points: a custom skeleton has no mapping");
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_add_maps(lwp_handle h, const float* heat, const float* paf, int layout, int N, int hs, int ws, int ratio,
+                                 int demo, const int* image_index) {
+    if (!heat || !paf || !image_index || N <= 0 || hs <= 0 || ws <= 0) return fail(h, LWP_ERR_ARG, "bad argument");
+    if (layout != LWP_LAYOUT_NCHW && layout != LWP_LAYOUT_NHWC) return fail(h, LWP_ERR_ARG, "layout must be LWP_LAYOUT_NCHW or LWP_LAYOUT_NHWC");
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    rc = check_pose_args(h, ratio, true, (int64_t)hs * ratio, (int64_t)ws * ratio);
+    if (rc) return rc;
+    rc = coco_add_check(h, N, image_index);
+    if (rc) return rc;
+    rc = coco_default_skeleton(h);
+    if (rc) return rc;
+    // the store takes detections, not tracks: the lanes of modes 2 / 3 must not advance on validation frames
+    if (h->tail.mode >= 2) return fail(h, LWP_ERR_STATE, "tracking is on (lwp_set_tracking mode 2 or 3): the detection store takes untracked frames only");
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = ensure_ws(h, N);
+    if (rc) return rc;
+    rc = order_in(h);
+    if (rc) return rc;
+    MapView hv = nchw_view(heat, h->g.NH, hs, ws), pv = nchw_view(paf, h->g.NP, hs, ws);
+    if (layout == LWP_LAYOUT_NHWC) {
+        hv.ys = (int64_t)ws * h->g.NH; hv.xs = h->g.NH; hv.cs = 1;
+        pv.ys = (int64_t)ws * h->g.NP; pv.xs = h->g.NP; pv.cs = 1;
+    }
+    coco_claim_serial_ws(h);
+    rc = enqueue_grouping(h, hv, pv, N, ratio, demo, h->ws, h->stream);
+    if (rc == LWP_OK) rc = coco_enqueue_append(h, N, image_index);
+    if (rc) return rc;
+    bool ordered = false;
+    return order_out(h, h->stream, &ordered);          // enqueue only: no synchronise, no fetch
+}
+
+extern "C" int lwp_coco_add_rows(lwp_handle h, int image_index, int n, const double* dt_kp, const double* dt_score) {
+    if (n < 0) return fail(h, LWP_ERR_ARG, "negative row count");
+    if (n > 0 && (!dt_kp || !dt_score)) return fail(h, LWP_ERR_ARG, "dt_kp / dt_score is null");
+    for (int64_t i = 0; i < n; ++i) if (!std::isfinite(dt_score[i])) return fail(h, LWP_ERR_ARG, "a detection score is not finite");
+    for (int64_t i = 0; i < (int64_t)n * kEvalK * 3; ++i) if (!std::isfinite(dt_kp[i])) return fail(h, LWP_ERR_ARG, "a detection coordinate is not finite");
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    rc = coco_add_check(h, 1, &image_index);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    // key-points and scores travel as one section of the ring
+    const size_t kb = (size_t)n * kEvalK * 3 * 8;
+    std::vector<double> both((size_t)n * (kEvalK * 3 + 1));
+    if (n > 0) { memcpy(both.data(), dt_kp, kb); memcpy(both.data() + (size_t)n * kEvalK * 3, dt_score, (size_t)n * 8); }
+    const void* d = nullptr;
+    rc = coco_ring_put(h, both.data(), both.size() * 8, &d);
+    if (rc) return rc;
+    const double* dk = (const double*)d;
+    LAUNCH(h, KC_OTHER, launch_coco_append_rows(h->coco.st, image_index, n, dk, dk + (size_t)n * kEvalK * 3, h->stream));
+    h->coco.added[image_index] = 1;
+    return LWP_OK;
+}
+
+// the tables after everything queued so far: ONE copy (control words | counts) and one synchronise; a sticky status is the error
+static int coco_tables_parse(lwp_context* h, const std::vector<long long>& buf, std::vector<int>* counts, long long* cursor);
+static int coco_tables_copy(lwp_context* h, std::vector<long long>* buf) {
+    auto& c = h->coco;
+    const int n = c.st.n_images;
+    buf->assign(4 + ((size_t)n + 1) / 2, 0);
+    HIP_TRY(h, hipMemcpyAsync(buf->data(), c.meta.as<void>(), 4 * sizeof(long long) + (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    return LWP_OK;
+}
+static int coco_fetch_tables(lwp_context* h, std::vector<int>* counts, long long* cursor) {
+    std::vector<long long> buf;
+    int rc = coco_tables_copy(h, &buf);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return coco_tables_parse(h, buf, counts, cursor);
+}
+static int coco_tables_parse(lwp_context* h, const std::vector<long long>& buf, std::vector<int>* counts, long long* cursor) {
+    auto& c = h->coco;
+    const int n = c.st.n_images;
+    const long long* ctl = buf.data();
+    if (cursor) *cursor = ctl[0];
+    char msg[240];
+    switch ((int)ctl[1]) {
+    case COCO_ST_OK: break;
+    case COCO_ST_FLAGS:
+        snprintf(msg, sizeof msg, "image %d: post-processing capacity exceeded (bits 0x%llx: 1 peaks, 2 key-points, 4 connections/entries)", (int)ctl[2], (unsigned long long)ctl[3]);
+        return fail(h, LWP_ERR_CAPACITY, msg);
+    case COCO_ST_UNBOUND:
+        return fail(h, LWP_ERR_UNBOUND, "local variable 'ratio' referenced before assignment");
+    case COCO_ST_ROWS:
+        snprintf(msg, sizeof msg, "the detection store holds %d rows and %lld were added (image %d was the first without room): open it with row_cap >= %lld",
+                 c.st.row_cap, ctl[0], (int)ctl[2], ctl[0]);
+        return fail(h, LWP_ERR_CAPACITY, msg);
+    case COCO_ST_NONFINITE:
+        snprintf(msg, sizeof msg, "image %d: a detection coordinate or score is not finite", (int)ctl[2]);
+        return fail(h, LWP_ERR_ARG, msg);
+    default:
+        return fail(h, LWP_ERR_STATE, "the detection store's status word is damaged");
+    }
+    const int* cnt = (const int*)(buf.data() + 4);
+    counts->resize((size_t)n);
+    for (int i = 0; i < n; ++i) (*counts)[i] = std::min(std::max(cnt[i], 0), c.st.row_cap);
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_counts(lwp_handle h, int64_t* n_rows, int* per_image_counts) {
+    if (!n_rows) return fail(h, LWP_ERR_ARG, "n_rows is null");
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    std::vector<int> counts;
+    rc = coco_fetch_tables(h, &counts, nullptr);
+    if (rc) return rc;
+    int64_t total = 0;
+    for (size_t i = 0; i < counts.size(); ++i) { total += counts[i]; if (per_image_counts) per_image_counts[i] = counts[i]; }
+    *n_rows = total;
+    return LWP_OK;
+}
+
+// "stage the inputs" of lwp_coco_finish: the tables, the offsets formed on the host, and the store gathered into CSR order in
+// run->in: [dt_off | sel_off | oks_off | dt_kp | dt_score]; the ground truth is the resident one
+static int coco_gather_rows(lwp_context* h, CocoEvalRun* run) {
+    auto& c = h->coco;
+    const int n = c.st.n_images;
+    std::vector<int> counts;
+    int rc = coco_fetch_tables(h, &counts, nullptr);
+    if (rc) return rc;
+    std::vector<int64_t> dt_off((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) dt_off[i + 1] = dt_off[i] + counts[i];
+    const int64_t ND = dt_off[n];
+    if (ND > c.st.row_cap) return fail(h, LWP_ERR_STATE, "the detection store's counts exceed its rows");
+    coco_eval_offsets(n, dt_off.data(), c.gt_off.data(), run);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
+    const size_t i_dt_off = take(nb), i_sel_off = take(nb), i_oks_off = take(nb);
+    const size_t up_bytes = at;
+    const size_t i_dt_kp = take((size_t)ND * kEvalK * 3 * 8), i_dt_score = take((size_t)ND * 8);
+    run->stage.assign(up_bytes, 0);
+    memcpy(run->stage.data() + i_dt_off, dt_off.data(), nb);
+    memcpy(run->stage.data() + i_sel_off, run->sel_off.data(), nb);
+    memcpy(run->stage.data() + i_oks_off, run->oks_off.data(), nb);
+    HIP_TRY(h, run->in.ensure(std::max<size_t>(at, 16)));
+    unsigned char* di = run->in.as<unsigned char>();
+    HIP_TRY(h, hipMemcpyAsync(di, run->stage.data(), up_bytes, hipMemcpyHostToDevice, h->stream));
+    CocoEvalParams& p = run->p;
+    const char* g = c.gt.as<char>();
+    p.dt_off = (const int64_t*)(di + i_dt_off); p.sel_off = (const int64_t*)(di + i_sel_off); p.oks_off = (const int64_t*)(di + i_oks_off);
+    p.dt_kp = (const double*)(di + i_dt_kp); p.dt_score = (const double*)(di + i_dt_score);
+    p.gt_off = (const int64_t*)g; p.gt_kp = (const double*)(g + c.o_kp); p.gt_area = (const double*)(g + c.o_area);
+    p.gt_bbox = (const double*)(g + c.o_bbox); p.gt_iscrowd = (const int*)(g + c.o_crowd); p.gt_ignore = (const int*)(g + c.o_ignore);
+    LAUNCH(h, KC_OTHER, launch_coco_gather(c.st, p.dt_off, ND, (double*)(di + i_dt_kp), (double*)(di + i_dt_score), nullptr, h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_rows(lwp_handle h, int* dt_image, double* dt_kp, double* dt_score, int64_t row_cap) {
+    if (row_cap < 0) return fail(h, LWP_ERR_ARG, "row_cap must not be negative");
+    if (row_cap > 0 && (!dt_image || !dt_kp || !dt_score)) return fail(h, LWP_ERR_ARG, "dt_image / dt_kp / dt_score is null");
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    // the offsets are formed on the device here, so that the tables and the rows come back behind ONE synchronise: the first
+    // `cap` rows of the evaluation's order are gathered and copied, and the counts say afterwards how many of them there are
+    auto& c = h->coco;
+    const int n = c.st.n_images;
+    const size_t cap = (size_t)std::min<int64_t>(row_cap, c.st.row_cap);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t s_off = take(((size_t)n + 1) * 8), s_kp = take(cap * kEvalK * 3 * 8), s_score = take(cap * 8), s_image = take(cap * 4);
+    DevBuf scratch;
+    HIP_TRY(h, scratch.ensure(std::max<size_t>(at, 16)));
+    char* ds = scratch.as<char>();
+    LAUNCH(h, KC_OTHER, launch_coco_offsets(c.st, (int64_t*)(ds + s_off), h->stream));
+    LAUNCH(h, KC_OTHER, launch_coco_gather(c.st, (const int64_t*)(ds + s_off), (int64_t)cap, (double*)(ds + s_kp), (double*)(ds + s_score),
+                                           (int*)(ds + s_image), h->stream));
+    std::vector<long long> tables;
+    rc = coco_tables_copy(h, &tables);
+    if (rc) return rc;
+    std::vector<double> h_kp(cap * kEvalK * 3), h_score(cap);
+    std::vector<int> h_image(cap);
+    if (cap > 0) {
+        HIP_TRY(h, hipMemcpyAsync(h_kp.data(), ds + s_kp, cap * kEvalK * 3 * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h_score.data(), ds + s_score, cap * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h_image.data(), ds + s_image, cap * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<int> counts;
+    rc = coco_tables_parse(h, tables, &counts, nullptr);
+    if (rc) return rc;
+    int64_t ND = 0;
+    for (int v : counts) ND += v;
+    if (ND > row_cap) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "the detection store holds %lld rows, the arrays %lld", (long long)ND, (long long)row_cap);
+        return fail(h, LWP_ERR_CAPACITY, msg);
+    }
+    if (ND > 0) {
+        memcpy(dt_kp, h_kp.data(), (size_t)ND * kEvalK * 3 * 8);
+        memcpy(dt_score, h_score.data(), (size_t)ND * 8);
+        memcpy(dt_image, h_image.data(), (size_t)ND * 4);
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_coco_finish(lwp_handle h, double* precision, double* recall, double* scores, int64_t* npig) {
+    if (!precision || !recall || !scores || !npig) return fail(h, LWP_ERR_ARG, "precision / recall / scores / npig is null");
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = order_in(h);
+    if (rc) return rc;
+    CocoEvalRun run;
+    rc = coco_gather_rows(h, &run);
+    if (rc) return rc;
+    rc = coco_eval_launch(h, true, &run);
+    if (rc) return rc;
+    return coco_eval_accumulate(h, run, precision, recall, scores, npig);
+}
+
+extern "C" int lwp_debug_coco_rows(lwp_handle h, int N, const double* entries, const int* n_entries, const double* kpts,
+                                   const int* kpt_counts, const int* image_index) {
+    if (N <= 0 || !n_entries || !kpt_counts || !image_index) return fail(h, LWP_ERR_ARG, "bad argument");
+    int rc = coco_need_store(h);
+    if (rc) return rc;
+    rc = coco_default_skeleton(h);
+    if (rc) return rc;
+    const int max_rows = h->skel.K * h->caps.max_kpts;
+    int64_t te = 0, tk = 0;
+    for (int f = 0; f < N; ++f) {
+        if (n_entries[f] < 0 || kpt_counts[f] < 0) return fail(h, LWP_ERR_ARG, "negative count");
+        if (n_entries[f] > h->caps.max_entries || kpt_counts[f] > max_rows) return fail(h, LWP_ERR_CAPACITY, "more rows than the workspace's capacity (lwp_set_capacity)");
+        te += n_entries[f]; tk += kpt_counts[f];
+    }
+    if ((te > 0 && !entries) || (tk > 0 && !kpts)) return fail(h, LWP_ERR_ARG, "entries / kpts is null");
+    rc = coco_add_check(h, N, image_index);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = ensure_ws(h, N);
+    if (rc) return rc;
+    rc = order_in(h);
+    if (rc) return rc;
+    coco_claim_serial_ws(h);
+    const PostWorkspace& w = h->ws;
+    std::vector<unsigned long long> fl((size_t)N * 4);
+    // the copies below read `fl` and the caller's pageable arrays: whatever way the call ends, it ends synchronised (the guard
+    // is declared behind the vector, so it runs before the vector is released)
+    struct SyncAtExit { hipStream_t s; ~SyncAtExit() { (void)hipStreamSynchronize(s); } } sync_at_exit{h->stream};
+    for (int f = 0; f < N; ++f) { fl[f * 4] = 0; fl[f * 4 + 1] = ~0ull; fl[f * 4 + 2] = ~0ull; fl[f * 4 + 3] = 0; }   // as find_peaks leaves them
+    HIP_TRY(h, hipMemcpyAsync(w.flags, fl.data(), fl.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w.n_entries, n_entries, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    const double *e = entries, *k = kpts;
+    for (int f = 0; f < N; ++f) {                      // frame f's rows lie back to back in the caller's arrays
+        if (n_entries[f]) HIP_TRY(h, hipMemcpyAsync(w.entries + (size_t)f * w.caps.max_entries * w.E, e, (size_t)n_entries[f] * w.E * 8, hipMemcpyHostToDevice, h->stream));
+        if (kpt_counts[f]) HIP_TRY(h, hipMemcpyAsync(w.kpts_out + (size_t)f * max_rows * 4, k, (size_t)kpt_counts[f] * 4 * 8, hipMemcpyHostToDevice, h->stream));
+        e += (size_t)n_entries[f] * w.E; k += (size_t)kpt_counts[f] * 4;
+    }
+    rc = coco_enqueue_append(h, N, image_index);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the caller's arrays and the vector above are free
     return LWP_OK;
 }
 

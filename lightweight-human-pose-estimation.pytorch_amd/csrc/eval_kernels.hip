@@ -296,4 +296,151 @@ hipError_t launch_coco_accumulate(const CocoEvalParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------- detection store
+// val.py:52-78 on the result block of the grouping: slot of each of the 18 network key-points in COCO's order (the neck has none)
+__constant__ int c_coco_slot[kCocoTypes] = {0, -1, 6, 8, 10, 5, 7, 9, 12, 14, 16, 11, 13, 15, 2, 1, 4, 3};
+
+// The control words after one more image: the first error stays.  Every thread of the workgroup carries the same values.
+struct CocoCtl { long long cursor, status, image, detail; };
+__device__ inline void coco_ctl_note(CocoCtl& c, int code, int image, long long detail) {
+    if (c.status == COCO_ST_OK) { c.status = code; c.image = image; c.detail = detail; }
+}
+// rows [c.cursor, c.cursor + n) of `image`; returns how many of them lie inside the store (the others are not written)
+__device__ inline int coco_ctl_claim(const CocoStore& st, CocoCtl& c, int image, int n, long long* base) {
+    *base = c.cursor < (long long)st.row_cap ? c.cursor : (long long)st.row_cap;
+    const long long room = (long long)st.row_cap - *base;
+    const int w = (int)(room < (long long)n ? room : (long long)n);
+    if (threadIdx.x == 0) { st.start[image] = (int)*base; st.count[image] = w; }
+    c.cursor += n;
+    return w;
+}
+
+// One workgroup for the N frames of a call, in frame order: frame f's rows start where frame f - 1's end, a row's place is its
+// entry's place.  The cursor and the status are read by every thread before the loop and written by thread 0 behind it.
+__global__ void __launch_bounds__(kEvalThreads) coco_append_kernel(const CocoStore st, const CocoAppendParams p) {
+    const int tid = threadIdx.x;
+    CocoCtl c{st.ctl[0], st.ctl[1], st.ctl[2], st.ctl[3]};
+    for (int f = 0; f < p.N; ++f) {
+        const int img = p.image_index[f];
+        if (img < 0 || img >= st.n_images) continue;   // (checked by the host; uniform)
+        const int ne = p.n_entries[f];
+        const int n = ne < 0 ? 0 : (ne > p.max_entries ? p.max_entries : ne);
+        long long base;
+        const int w = coco_ctl_claim(st, c, img, n, &base);
+        const double* ent = p.entries + (size_t)f * p.max_entries * kCocoEntry;
+        const double* rows = p.kpts_out + (size_t)f * p.max_rows * 4;
+        int bad = 0;
+        for (int e = tid; e < w; e += kEvalThreads) {
+            const double* en = ent + (size_t)e * kCocoEntry;
+            double* kp = st.kp + (size_t)(base + e) * kEvalK * 3;
+            for (int k = 0; k < kEvalK * 3; ++k) kp[k] = 0.0;
+            for (int t = 0; t < kCocoTypes; ++t) {
+                const int slot = c_coco_slot[t];
+                const double id = en[t];
+                if (slot < 0 || id == -1.0) continue;
+                int r = (int)id;                       // the rows of a frame are stored compact and in id order
+                r = r < 0 ? 0 : (r > p.max_rows - 1 ? p.max_rows - 1 : r);
+                const double x = rows[(size_t)r * 4] + 0.5, y = rows[(size_t)r * 4 + 1] + 0.5;
+                if (!isfinite(x) || !isfinite(y)) bad = 1;
+                kp[slot * 3] = x; kp[slot * 3 + 1] = y; kp[slot * 3 + 2] = 1.0;
+            }
+            const double m = en[kCocoEntry - 1] - 1.0;                     // max(0, count - 1): the neck does not count
+            const double s = en[kCocoEntry - 2] * (m > 0.0 ? m : 0.0);
+            if (!isfinite(s)) bad = 1;
+            st.score[base + e] = s;
+            st.image[base + e] = img;
+        }
+        const int any_bad = __syncthreads_or(bad);
+        const unsigned long long* fl = p.flags + (size_t)f * 4;
+        if (fl[0]) coco_ctl_note(c, COCO_ST_FLAGS, img, (long long)fl[0]);
+        else if (fl[1] < fl[2]) coco_ctl_note(c, COCO_ST_UNBOUND, img, 0);
+        else if (w < n) coco_ctl_note(c, COCO_ST_ROWS, img, 0);
+        else if (any_bad) coco_ctl_note(c, COCO_ST_NONFINITE, img, 0);
+    }
+    __syncthreads();
+    if (tid == 0) { st.ctl[0] = c.cursor; st.ctl[1] = c.status; st.ctl[2] = c.image; st.ctl[3] = c.detail; }
+}
+
+hipError_t launch_coco_append(const CocoStore& st, const CocoAppendParams& p, hipStream_t s) {
+    if (p.N < 1) return hipSuccess;
+    hipLaunchKernelGGL(coco_append_kernel, dim3(1), dim3(kEvalThreads), 0, s, st, p);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(kEvalThreads) coco_append_rows_kernel(const CocoStore st, int img, int n, const double* __restrict__ kp,
+                                                                        const double* __restrict__ score) {
+    const int tid = threadIdx.x;
+    CocoCtl c{st.ctl[0], st.ctl[1], st.ctl[2], st.ctl[3]};
+    long long base;
+    const int w = coco_ctl_claim(st, c, img, n, &base);
+    for (int64_t i = tid; i < (int64_t)w * kEvalK * 3; i += kEvalThreads) st.kp[(int64_t)base * kEvalK * 3 + i] = kp[i];
+    for (int e = tid; e < w; e += kEvalThreads) { st.score[base + e] = score[e]; st.image[base + e] = img; }
+    if (w < n) coco_ctl_note(c, COCO_ST_ROWS, img, 0);
+    __syncthreads();
+    if (tid == 0) { st.ctl[0] = c.cursor; st.ctl[1] = c.status; st.ctl[2] = c.image; st.ctl[3] = c.detail; }
+}
+
+hipError_t launch_coco_append_rows(const CocoStore& st, int image, int n, const double* kp, const double* score, hipStream_t s) {
+    hipLaunchKernelGGL(coco_append_rows_kernel, dim3(1), dim3(kEvalThreads), 0, s, st, image, n, kp, score);
+    return hipGetLastError();
+}
+
+// dt_off[0 .. n_images] from the counts, on the device (lwp_coco_rows, which reads tables and rows behind one synchronise): one
+// workgroup, a chunk of kEvalScanChunk images at a time with a carry
+__global__ void __launch_bounds__(kEvalThreads) coco_offsets_kernel(const CocoStore st, int64_t* __restrict__ dt_off) {
+    __shared__ unsigned long long s_cnt[2][kEvalThreads];
+    const int tid = threadIdx.x;
+    unsigned long long carry = 0;
+    if (tid == 0) dt_off[0] = 0;
+    for (int base = 0; base < st.n_images; base += kEvalScanChunk) {
+        const int i = base + tid;
+        int v = i < st.n_images ? st.count[i] : 0;
+        v = v < 0 ? 0 : (v > st.row_cap ? st.row_cap : v);
+        const unsigned long long incl = block_scan((unsigned long long)v, s_cnt, [](unsigned long long x, unsigned long long y) { return x + y; }) + carry;
+        if (i < st.n_images) dt_off[i + 1] = (int64_t)incl;
+        carry += s_cnt[0][kEvalThreads - 1];
+        __syncthreads();
+    }
+}
+
+hipError_t launch_coco_offsets(const CocoStore& st, int64_t* dt_off, hipStream_t s) {
+    hipLaunchKernelGGL(coco_offsets_kernel, dim3(1), dim3(kEvalThreads), 0, s, st, dt_off);
+    return hipGetLastError();
+}
+
+// one wave per destination row: lanes 0..50 move the key-points, lane 51 the score and the image index.  Rows [0, min(ND,
+// dt_off[n_images])): ND bounds the destination arrays.
+__global__ void __launch_bounds__(kEvalThreads) coco_gather_kernel(const CocoStore st, const int64_t* __restrict__ dt_off, int64_t ND,
+                                                                   double* __restrict__ dt_kp, double* __restrict__ dt_score,
+                                                                   int* __restrict__ dt_image) {
+    const int lane = threadIdx.x & 63;
+    const int64_t total = dt_off[st.n_images];
+    if (total < ND) ND = total;
+    const int64_t waves = (int64_t)gridDim.x * (kEvalThreads / 64);
+    for (int64_t r = (int64_t)blockIdx.x * (kEvalThreads / 64) + (threadIdx.x >> 6); r < ND; r += waves) {
+        int lo = 0, hi = st.n_images;                  // the image with dt_off[i] <= r < dt_off[i + 1]
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (dt_off[mid] <= r) lo = mid;
+            else hi = mid;
+        }
+        int64_t src = (int64_t)st.start[lo] + (r - dt_off[lo]);
+        src = src < 0 ? 0 : (src > (int64_t)st.row_cap - 1 ? (int64_t)st.row_cap - 1 : src);
+        if (lane < kEvalK * 3) dt_kp[r * kEvalK * 3 + lane] = st.kp[src * kEvalK * 3 + lane];
+        else if (lane == kEvalK * 3) {
+            dt_score[r] = st.score[src];
+            if (dt_image) dt_image[r] = lo;
+        }
+    }
+}
+
+hipError_t launch_coco_gather(const CocoStore& st, const int64_t* dt_off, int64_t ND, double* dt_kp, double* dt_score, int* dt_image,
+                              hipStream_t s) {
+    if (ND < 1) return hipSuccess;
+    const int64_t want = (ND + kEvalThreads / 64 - 1) / (kEvalThreads / 64);
+    hipLaunchKernelGGL(coco_gather_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(kEvalThreads), 0, s, st, dt_off, ND, dt_kp, dt_score,
+                       dt_image);
+    return hipGetLastError();
+}
+
 }  // namespace lwp

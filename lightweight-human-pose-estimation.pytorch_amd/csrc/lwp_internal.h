@@ -456,6 +456,38 @@ hipError_t coco_sort_temp_bytes(int64_t NS, size_t* bytes);
 hipError_t launch_coco_sort(const double* sel_score, int64_t NS, unsigned long long* keys, unsigned long long* keys_out,
                             unsigned int* vals, unsigned int* perm, void* tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_coco_accumulate(const CocoEvalParams& p, hipStream_t s);
+// ---- detection store (eval_kernels.hip; val.py:52-78,136-145): the detections of a validation run, kept on the device between
+//      the grouping and the evaluation.  Rows lie in the order they were added; an image's rows are [start, start + count).
+constexpr int kCocoTypes = 18, kCocoEntry = 20;       // key-point types and doubles per pose row of the default skeleton
+enum CocoStatus { COCO_ST_OK = 0, COCO_ST_FLAGS = 1, COCO_ST_UNBOUND = 2, COCO_ST_ROWS = 3, COCO_ST_NONFINITE = 4 };
+struct CocoStore {
+    double* kp;                       // [row_cap][17][3]
+    double* score;                    // [row_cap]
+    int* image;                       // [row_cap] position of the row's image in ascending id order
+    int* start;                       // [n_images]
+    int* count;                       // [n_images] rows written (0: never added, or added without a pose)
+    long long* ctl;                   // [4] 0: cursor (rows asked for; beyond row_cap nothing is written), 1: sticky CocoStatus,
+                                      //     2: the image index it names, 3: its detail (the overflow bits of a frame)
+    int row_cap, n_images;
+};
+struct CocoAppendParams {             // the result block enqueue_grouping leaves for N frames (ResultLayout, default skeleton)
+    const unsigned long long* flags;  // [N][4]
+    const double* kpts_out;           // [N][max_rows][4] rows in id order
+    const double* entries;            // [N][max_entries][20]
+    const int* n_entries;             // [N]
+    const int* image_index;           // [N] device
+    int N, max_entries, max_rows;
+};
+// one workgroup walks the N frames in order: no atomic decides a row's position
+hipError_t launch_coco_append(const CocoStore& st, const CocoAppendParams& p, hipStream_t s);
+// n ready-made rows of one image through the same cursor
+hipError_t launch_coco_append_rows(const CocoStore& st, int image, int n, const double* kp, const double* score, hipStream_t s);
+// dt_off [n_images + 1] (device) from the store's counts
+hipError_t launch_coco_offsets(const CocoStore& st, int64_t* dt_off, hipStream_t s);
+// the store in CSR order: destination row r of image i comes from start[i] + (r - dt_off[i]); rows [0, min(ND, dt_off[n_images]));
+// dt_image may be null
+hipError_t launch_coco_gather(const CocoStore& st, const int64_t* dt_off, int64_t ND, double* dt_kp, double* dt_score, int* dt_image,
+                              hipStream_t s);
 
 struct StageLossParams {
     const float* outs[kLossMaxOuts];   // even: N x CH x hw heat-map tensors, odd: N x CP x hw PAF tensors; null = skipped

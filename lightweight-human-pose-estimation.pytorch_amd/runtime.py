@@ -28,6 +28,8 @@ class Engine(object):
         self.train_scope = "stages"           # set_train_scope: "stages" | "cpm" | "all"
         self._scope_steps = 0                 # stage_steps when the current scope was set
         self._left_params = {}                # parameters an earlier, wider scope trained and the current one does not cover
+        self._coco_n = 0                      # images of the open detection store (coco_open); 0: none, the library reports it
+        self._val_store = None
 
     # ------------------------------------------------------------------ stream ordering
     def _order(self, device=None, hand_over=True):
@@ -1311,6 +1313,16 @@ class Engine(object):
                 packed["gt_off"].ctypes.data_as(i64p), ptr(packed["gt_kp"], dp), ptr(packed["gt_area"], dp), ptr(packed["gt_bbox"], dp),
                 ptr(packed["gt_iscrowd"], ip), ptr(packed["gt_ignore"], ip))
 
+    @staticmethod
+    def _coco_gt_args(packed):
+        """n_images and the ground-truth pointers of ``_coco_args``: what lwp_coco_open takes."""
+        i64p, dp, ip = C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int)
+
+        def ptr(a, t):
+            return a.ctypes.data_as(t) if a.size else None
+        return (int(packed["n_images"]), packed["gt_off"].ctypes.data_as(i64p), ptr(packed["gt_kp"], dp), ptr(packed["gt_area"], dp),
+                ptr(packed["gt_bbox"], dp), ptr(packed["gt_iscrowd"], ip), ptr(packed["gt_ignore"], ip))
+
     def coco_eval(self, gt, detections=None):
         """COCOeval(gt, loadRes(detections), 'keypoints') evaluate() + accumulate() on the GPU with COCOeval's default
         parameters.  ``gt``: a COCO ground-truth dict ('images', 'annotations', 'categories') with ``detections`` the list of
@@ -1347,12 +1359,131 @@ class Engine(object):
                 "matched": matched.reshape(3, 10, 20).astype(bool), "ignored": ignored.reshape(3, 10, 20).astype(bool),
                 "npig": np.array([npig[a] for a in range(3)], dtype=np.int64)}
 
+    # ------------------------------------------------------------------ device-resident validation (val.py:113-160)
+    def coco_open(self, gt_or_packed, row_cap=None):
+        """Upload a data set's ground truth once and open a detection store of ``row_cap`` rows on the device (default: 32 an
+        image).  ``gt_or_packed``: a COCO ground-truth dict, or what ``coco_pack_gt`` / ``coco_pack`` made of one.  A second
+        call replaces the store.  Returns the packed ground truth (``image_ids`` gives an image's index)."""
+        g = gt_or_packed if "gt_off" in gt_or_packed else coco_pack_gt(gt_or_packed)
+        n = int(g["n_images"])
+        row_cap = 32 * n if row_cap is None else int(row_cap)
+        check(lib().lwp_coco_open(self.h.ptr, *self._coco_gt_args(g), row_cap), self.h.ptr)
+        self._coco_n = n
+        self._val_store = None                # (val.evaluate(store=True) notes here which labels the store belongs to)
+        return g
+
+    def coco_release(self):
+        self._val_store = None
+        check(lib().lwp_coco_release(self.h.ptr), self.h.ptr)
+
+    def coco_reset(self):
+        """Forget the detections and the status, keep the ground truth: the next validation of the same data set."""
+        check(lib().lwp_coco_reset(self.h.ptr), self.h.ptr)
+
+    def coco_add_maps(self, heat, paf, image_index, upsample_ratio=4, demo=False, layout="NCHW"):
+        """``poses_from_maps`` for cuda tensors whose poses go into the detection store instead of to the host: grouping and the
+        append kernel are enqueued and the call returns; nothing is synchronised or fetched.  ``image_index``: per frame its
+        image's position in the ground truth's ascending id order."""
+        lay = {"NCHW": 0, "NHWC": 1}[layout]
+        if not getattr(heat, "is_cuda", False) or not getattr(paf, "is_cuda", False):
+            raise TypeError("coco_add_maps takes cuda tensors (the maps stay on the device)")
+        heat, paf = heat.detach().contiguous(), paf.detach().contiguous()
+        if lay == 0:
+            N, _, hs, ws = heat.shape
+        else:
+            N, hs, ws, _ = heat.shape
+        idx = np.ascontiguousarray(np.atleast_1d(image_index), dtype=np.int32)
+        if idx.shape != (N,):
+            raise ValueError("image_index must hold one index per frame (%d), got %s" % (N, idx.shape))
+        self._order(heat.device)
+        check(lib().lwp_coco_add_maps(self.h.ptr, heat.data_ptr(), paf.data_ptr(), lay, N, hs, ws, upsample_ratio, 1 if demo else 0,
+                                      idx.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+
+    def coco_add_rows(self, image_index, keypoints, scores):
+        """Append ready-made detections of one image: ``keypoints`` (n, 17, 3) or (n, 51), ``scores`` (n,); enqueue only."""
+        kp = np.ascontiguousarray(keypoints, dtype=np.float64).reshape(-1, 17, 3)
+        sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        if len(kp) != len(sc):
+            raise ValueError("%d key-point rows but %d scores" % (len(kp), len(sc)))
+        dp = C.POINTER(C.c_double)
+        check(lib().lwp_coco_add_rows(self.h.ptr, int(image_index), len(sc), kp.ctypes.data_as(dp) if len(sc) else None,
+                                      sc.ctypes.data_as(dp) if len(sc) else None), self.h.ptr)
+
+    def coco_counts(self):
+        """(rows in the store, rows per image (n_images,) int32) after everything queued so far; raises the store's status."""
+        total = C.c_int64()
+        per = np.zeros(self._coco_n, dtype=np.int32)
+        check(lib().lwp_coco_counts(self.h.ptr, C.byref(total), per.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        return int(total.value), per
+
+    def coco_rows(self):
+        """The store's rows in the evaluation's order (images ascending, within an image as added): ``image`` (n,) int32,
+        ``keypoints`` (n, 17, 3) and ``score`` (n,) float64.  Two library calls, one synchronise each: ``coco_counts`` sizes
+        the arrays (sizing them by the store's capacity instead would copy every unused row back), lwp_coco_rows fills them."""
+        n, _ = self.coco_counts()
+        img = np.zeros(n, dtype=np.int32)
+        kp = np.zeros((n, 17, 3), dtype=np.float64)
+        sc = np.zeros(n, dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(lib().lwp_coco_rows(self.h.ptr, img.ctypes.data_as(C.POINTER(C.c_int)), kp.ctypes.data_as(dp), sc.ctypes.data_as(dp), n), self.h.ptr)
+        return {"image": img, "keypoints": kp, "score": sc}
+
+    def coco_finish(self):
+        """``coco_eval`` on the store's rows against the resident ground truth: the same dict, bit for bit what ``coco_eval``
+        returns for the same rows.  The store stays as it is."""
+        precision = np.empty((10, 101, 3), dtype=np.float64)
+        scores = np.empty((10, 101, 3), dtype=np.float64)
+        recall = np.empty((10, 3), dtype=np.float64)
+        npig = np.zeros(3, dtype=np.int64)
+        dp = C.POINTER(C.c_double)
+        check(lib().lwp_coco_finish(self.h.ptr, precision.ctypes.data_as(dp), recall.ctypes.data_as(dp), scores.ctypes.data_as(dp),
+                                    npig.ctypes.data_as(C.POINTER(C.c_int64))), self.h.ptr)
+        return {"precision": precision, "recall": recall, "scores": scores, "npig": npig, "stats": coco_stats(precision, recall)}
+
+    def debug_coco_rows(self, frames, image_index):
+        """The append kernel alone: ``frames`` is a list of (pose_entries (P, 20), all_keypoints (n, 4)) as ``poses_from_maps``
+        returns them, loaded into the serial result block and appended as images ``image_index``."""
+        N = len(frames)
+        ne = np.array([len(f[0]) for f in frames], dtype=np.int32)
+        nk = np.array([len(f[1]) for f in frames], dtype=np.int32)
+        ent = np.ascontiguousarray(np.concatenate([np.asarray(f[0], dtype=np.float64).reshape(-1, 20) for f in frames]))
+        kpt = np.ascontiguousarray(np.concatenate([np.asarray(f[1], dtype=np.float64).reshape(-1, 4) for f in frames]))
+        idx = np.ascontiguousarray(image_index, dtype=np.int32)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        check(lib().lwp_debug_coco_rows(self.h.ptr, N, ent.ctypes.data_as(dp) if ent.size else None, ne.ctypes.data_as(ip),
+                                        kpt.ctypes.data_as(dp) if kpt.size else None, nk.ctypes.data_as(ip), idx.ctypes.data_as(ip)), self.h.ptr)
+
 
 def coco_pack(gt, detections):
     """The arrays ``lwp_coco_eval`` takes, from a COCO ground-truth dict and a list of result dicts, as COCO() / loadRes() /
     COCOeval._prepare() arrange them: the images of ``gt`` in ascending id order, each with its annotations and detections in
     input order; ``gt_ignore`` = iscrowd or num_keypoints == 0.  ValueError: a detection whose image_id is not in ``gt``
     (loadRes asserts this), a non-positive annotation id (COCOeval reads a match to id 0 as no match), more than one category."""
+    g, index, cat = _coco_gt(gt)
+    n = g["n_images"]
+    per_dt = [[] for _ in range(n)]
+    for d in detections:
+        if int(d["image_id"]) not in index:
+            raise ValueError("detection for image %r, which the ground truth does not list" % (d["image_id"],))
+        if cat is not None and int(d.get("category_id", cat)) != cat:
+            continue
+        per_dt[index[int(d["image_id"])]].append(d)
+    dts = [d for lst in per_dt for d in lst]
+    return {"n_images": n, "image_ids": g["image_ids"],
+            "dt_off": np.cumsum([0] + [len(v) for v in per_dt], dtype=np.int64), "dt_kp": _coco_kp(dts),
+            "dt_score": np.array([d["score"] for d in dts], dtype=np.float64),
+            "gt_off": g["gt_off"], "gt_kp": g["gt_kp"], "gt_area": g["gt_area"], "gt_bbox": g["gt_bbox"],
+            "gt_iscrowd": g["gt_iscrowd"], "gt_ignore": g["gt_ignore"]}
+
+
+def _coco_kp(rows):
+    a = np.array([r["keypoints"] for r in rows], dtype=np.float64).reshape(-1, 17, 3) if rows else np.zeros((0, 17, 3))
+    return np.ascontiguousarray(a)
+
+
+def _coco_gt(gt):
+    """(the ground-truth arrays, image id -> position, the one category id or None): the half of ``coco_pack`` that does not
+    change while a data set is validated again and again."""
     cats = sorted({int(c["id"]) for c in gt["categories"]}) if gt.get("categories") else \
         sorted({int(a["category_id"]) for a in gt.get("annotations", []) if "category_id" in a})
     if len(cats) > 1:
@@ -1363,7 +1494,7 @@ def coco_pack(gt, detections):
     n = len(img_ids)
     if n < 1:
         raise ValueError("the ground truth lists no image")
-    per_gt, per_dt = [[] for _ in range(n)], [[] for _ in range(n)]
+    per_gt = [[] for _ in range(n)]
     for a in gt.get("annotations", []):
         if int(a["id"]) <= 0:
             raise ValueError("annotation id %r is not positive" % (a["id"],))
@@ -1371,27 +1502,20 @@ def coco_pack(gt, detections):
             continue
         if int(a["image_id"]) in index:
             per_gt[index[int(a["image_id"])]].append(a)
-    for d in detections:
-        if int(d["image_id"]) not in index:
-            raise ValueError("detection for image %r, which the ground truth does not list" % (d["image_id"],))
-        if cat is not None and int(d.get("category_id", cat)) != cat:
-            continue
-        per_dt[index[int(d["image_id"])]].append(d)
     gts = [a for lst in per_gt for a in lst]
-    dts = [d for lst in per_dt for d in lst]
-
-    def kp(rows):
-        a = np.array([r["keypoints"] for r in rows], dtype=np.float64).reshape(-1, 17, 3) if rows else np.zeros((0, 17, 3))
-        return np.ascontiguousarray(a)
     crowd = np.array([1 if a.get("iscrowd", 0) else 0 for a in gts], dtype=np.int32)
     nokp = np.array([1 if a["num_keypoints"] == 0 else 0 for a in gts], dtype=np.int32)
-    return {"n_images": n, "image_ids": img_ids,
-            "dt_off": np.cumsum([0] + [len(v) for v in per_dt], dtype=np.int64), "dt_kp": kp(dts),
-            "dt_score": np.array([d["score"] for d in dts], dtype=np.float64),
-            "gt_off": np.cumsum([0] + [len(v) for v in per_gt], dtype=np.int64), "gt_kp": kp(gts),
-            "gt_area": np.array([a["area"] for a in gts], dtype=np.float64),
-            "gt_bbox": np.ascontiguousarray(np.array([a["bbox"] for a in gts], dtype=np.float64).reshape(-1, 4)),
-            "gt_iscrowd": crowd, "gt_ignore": (crowd | nokp).astype(np.int32)}
+    return ({"n_images": n, "image_ids": img_ids,
+             "gt_off": np.cumsum([0] + [len(v) for v in per_gt], dtype=np.int64), "gt_kp": _coco_kp(gts),
+             "gt_area": np.array([a["area"] for a in gts], dtype=np.float64),
+             "gt_bbox": np.ascontiguousarray(np.array([a["bbox"] for a in gts], dtype=np.float64).reshape(-1, 4)),
+             "gt_iscrowd": crowd, "gt_ignore": (crowd | nokp).astype(np.int32)}, index, cat)
+
+
+def coco_pack_gt(gt):
+    """The ground-truth half of ``coco_pack``: ``n_images``, ``image_ids`` (ascending) and the ``gt_*`` arrays, the same
+    values under the same keys.  This is what ``Engine.coco_open`` uploads once per data set."""
+    return _coco_gt(gt)[0]
 
 
 def coco_stats(precision, recall):

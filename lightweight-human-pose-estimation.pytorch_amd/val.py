@@ -1,6 +1,6 @@
 """Drop-ins for the reference's ``val`` helpers (reference: val.py:30-147): ``normalize`` / ``pad_width`` (host, for callers
-that use them directly), the multi-scale driver ``infer`` (all of it on the GPU), ``convert_to_coco_format`` and the
-detection loop.
+that use them directly), the multi-scale driver ``infer`` (all of it on the GPU), ``convert_to_coco_format``, the
+detection loop, and ``evaluate`` with the detections resident on the device.
 
 OpenCV is not a dependency: ``cv2.copyMakeBorder(BORDER_CONSTANT)`` is a constant fill + copy.  The cubic resizes
 (uint8 fixed point of demo.py:59, float64 of val.py:89, float32 of val.py:98-107) run on the GPU with OpenCV's published
@@ -263,6 +263,71 @@ def evaluate_detections(gt, results, engine=None):
     from .runtime import default_engine
     eng = default_engine() if engine is None else engine
     stats = eng.coco_eval(gt, results)["stats"]
+    _print_summary(stats)
+    return stats
+
+
+def evaluate(labels, output_name, samples, net, multiscale=False, visualize=False, store=False, base_height=368, stride=8):
+    """The reference's val.evaluate (val.py:113-160) with the results resident on the device: per sample ``infer_batch`` and
+    ``Engine.coco_add_maps`` are enqueued (the poses go from the grouping's result block into the engine's detection store;
+    the host reads nothing in the loop), then ``output_name`` is written from the store's rows, the evaluation runs on the
+    store (``Engine.coco_finish``), the reference's lines are printed and the ten stats returned.
+
+    One difference from the reference: the third argument is an iterable of ``{'file_name': '<image id>.jpg', 'img': uint8
+    HxWx3}`` samples, not an images folder (image decoding is not part of this package).  ``labels``: the ground-truth file's
+    path, or the dict itself.  ``output_name`` None: no file is written.  The file holds the list ``coco_detections`` returns
+    for the same samples.  ``store=True`` keeps the ground truth and the store on the engine for the next call with the same
+    ``labels`` (the same dict object, or the same path; a training run that validates every ``val_after`` iterations);
+    otherwise they are released."""
+    if isinstance(samples, (str, bytes)):
+        raise TypeError("evaluate takes an iterable of {'file_name', 'img'} samples as its third argument, not an images "
+                        "folder: image decoding is not part of this package")
+    if visualize:
+        raise NotImplementedError("visualize needs cv2.imshow, which this package does not depend on")
+    eng = net.engine
+    kept = getattr(eng, "_val_store", None)
+    if kept is not None and (kept[0] is labels or (isinstance(labels, str) and kept[0] == labels)):
+        packed = kept[1]
+        eng.coco_reset()
+    else:
+        if isinstance(labels, dict):
+            gt = labels
+        else:
+            import json
+            with open(labels) as f:
+                gt = json.load(f)
+        packed = eng.coco_open(gt)
+    eng._val_store = None
+    try:
+        index = {v: i for i, v in enumerate(packed["image_ids"])}
+        scales = [0.5, 1.0, 1.5, 2.0] if multiscale else [1]
+        order = []
+        for sample in samples:
+            file_name, img = sample['file_name'], sample['img']
+            image_id = int(file_name[0:file_name.rfind('.')])
+            if image_id not in index:
+                raise ValueError("sample %r: image %d is not in the ground truth" % (file_name, image_id))
+            avg_heatmaps, avg_pafs = infer_batch(net, [img], scales, base_height, stride)
+            eng.coco_add_maps(avg_heatmaps, avg_pafs, [index[image_id]], 1, demo=False, layout="NHWC")
+            order.append(index[image_id])
+        if output_name is not None:
+            rows = eng.coco_rows()
+            first = np.concatenate([[0], np.cumsum(np.bincount(rows["image"], minlength=len(index)))])
+            coco_result = []
+            for i in order:                            # the file lists the images in sample order, as the reference's loop does
+                for r in range(first[i], first[i + 1]):
+                    coco_result.append({'image_id': packed["image_ids"][i], 'category_id': 1,
+                                        'keypoints': rows["keypoints"][r].reshape(-1).tolist(), 'score': float(rows["score"][r])})
+            write_detections(output_name, coco_result)
+        print('Running test for {} results.'.format('keypoints'))
+        stats = eng.coco_finish()["stats"]
+    except BaseException:
+        eng.coco_release()
+        raise
+    if store:
+        eng._val_store = (labels, packed)
+    else:
+        eng.coco_release()
     _print_summary(stats)
     return stats
 
