@@ -871,6 +871,7 @@ static int enqueue_heads_pair(lwp_context* h, const Layer& a, const Layer& b, in
     HeadsParams p;
     p.in = buf_at(h, a.src); p.in_ld = a.src.ld; p.f16 = h->dtype == LWP_F16;
     p.w0 = h->blob(a.w_off); p.b0 = h->blob(a.b_off);
+    if (h->dtype == LWP_F32) p.w0f = h->blob(a.w2_off);
     p.w1 = h->blob(b.w_off); p.b1 = h->blob(b.b_off);
     p.out = buf_at(h, b.dst); p.out_ld = b.dst.ld;
     p.out_nchw = (b.out_index >= 0 && d_outs_nchw) ? d_outs_nchw[b.out_index] : nullptr;

@@ -146,6 +146,7 @@ struct Tuning {
     int ms_tx = 0;                                                 // LWP_MS_TX (8..40: tile width of the fused multi-scale kernel; 0 = the geometry's plan)
     int ms_vec = -1;                                               // LWP_MS_VEC ("0": the scalar fused multi-scale kernel)
     int ms_fused = -1;                                             // LWP_MS_FUSED ("0": multi-scale step as up-sample + resize kernels)
+    int heads_debug = 0;                                           // LWP_HEADS_DEBUG (LWP_ABLATION builds: heads_f32_kernel<8> without 1 pixel-row loads, 2 weight requests, 4 MFMAs, 8 reduction + epilogue)
     int heads_f32_lds = -1;                                        // LWP_HEADS_F32_LDS ("0": the f32 stage heads above 4096 pixels as two GEMMs)
     int post_nchw = -1;                                            // LWP_POST_NCHW (f32: "0" = grouping reads the NHWC concat buffer in place)
     int heads_f32_max_m = 0;                                       // LWP_HEADS_F32_MAXM (tests: force the fused fp32 head pair at larger M)
@@ -230,6 +231,7 @@ struct HeadsParams {
     const void* in; int in_ld;           // [M][128] bf16 / fp16
     int f16 = 0;                         // element type fp16 (else bf16)
     const void* w0; const float* b0;     // [hidden][128] bf16, [hidden]
+    const float* w0f = nullptr;          // fp32: w0 again in the layer's fragment-order copy ([k-step 4][32-row tile][s 4][lane 64][4])
     const void* w1; const float* b1;     // [64][hidden] bf16 (rows >= cout are zero), [64]
     void* out; int out_ld;               // bf16 NHWC window (the concat buffer at the heat/PAF channels)
     float* out_nchw; float* out_nchw2;   // may be null: stage outputs, split at out_split

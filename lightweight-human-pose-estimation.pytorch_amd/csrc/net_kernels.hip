@@ -1727,19 +1727,28 @@ hipError_t launch_dwpw(const DwPwParams& p_in, hipStream_t s) {
 // head's hidden channels are split over the waves in tiles of 16; every weight fragment feeds TWO 16-pixel column blocks, i.e.
 // two independent accumulator chains.  v_mfma_f32_16x16x4_f32 with the weights as the A operand:
 //   GEMM 1: D[hidden 16][pixel 16].  The summation index is free to permute: k-slot (step s = 4 u + c, lane group q) is read as
-//           input channel 32 q + 4 u + c, so a lane's operands are 128 contiguous bytes of its own row — eight 16-byte loads of
-//           the PLAIN [hidden][128] weight rows (fully coalesced, no packing), and of the pixel's own NHWC row, kept for all tiles.
+//           input channel 32 q + 4 u + c, so a lane's operands are eight 16-byte pieces (u = 0..7) of its own weight row and of
+//           its pixel's NHWC row.  Read from the plain [hidden][128] rows, one wave instruction is 64 pieces in 64 different
+//           128-byte lines (row i16, byte 128 q + 16 u).  So W0 comes from the layer's fragment-order copy (the one gemm_ar
+//           streams: [k-step 32][32-row tile][s][lane][4], pack_weights): piece (row r, channels 32 q + 4 u) is k-step q, tile
+//           r >> 5, s = u >> 1, lane (r & 31) + 32 (u & 1) — the 16 rows of a lane group are 256 contiguous bytes and a wave
+//           instruction touches 8 lines.  The 32 pixel rows are loaded once per workgroup (two whole rows per wave instruction),
+//           handed to the waves through LDS and kept in registers for all tiles.
 //   D leaves lane (pixel i, q) with hidden channels 4 q + r, r = 0..3: after bias + ReLU, register r IS the B operand of GEMM 2's
 //   step r if k-slot q of that step means hidden 4 q + r — i.e. the W1 fragment of lane (out channel i, q) is the 16-byte vector
 //   W1[out][16 tile + 4 q .. + 3].  The hidden values never leave the lane's registers.
 //   GEMM 2 accumulates the head's own output tiles (2 or 3 of the 4 at 19 + 38 channels; a tile that straddles the split is
 //   computed by both heads' workgroups and each stores its own channels) per wave over its hidden tiles; the NW partial results
 //   are summed in the fixed order 0..NW-1 through LDS.  Weight loads are buffer loads with wave-uniform tile offsets, requested
-//   one tile ahead (two register buffers: the second pixel block's activations and accumulators take the third one's place).
-template <int NW>
+//   one tile ahead (two register buffers: the second pixel block's activations and accumulators take the third one's place);
+//   a wave's last tile requests nothing.
+// DBG (LWP_ABLATION builds, LWP_HEADS_DEBUG): 1 no pixel-row loads, 2 no weight requests, 4 no MFMAs, 8 no reduction + epilogue.
+constexpr int HX_LD = 32 + 4, HX_QS = 32 * HX_LD;       // pixel tile in LDS: [channel group q 4][pixel 32][32 channels + 4]
+template <int NW, int DBG = 0>
 __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
     static_assert(NW == 8, "the reduction maps the 8 waves onto 2 pixel blocks x 4 output tiles");
-    extern __shared__ __attribute__((aligned(16))) float hsm[];     // [NW][2][4][64] f32x4 partial outputs
+    extern __shared__ __attribute__((aligned(16))) float hsm[];     // [NW][2][4][64] f32x4 partial outputs, then the pixel tile [4][32][HX_LD]
+    float* const xs = hsm + NW * 2 * 4 * 64 * 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i16 = lane & 15, q = lane >> 4;
@@ -1759,7 +1768,7 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
     for (int x = 0; x < 2; ++x) { mm[x] = ptile * 32 + x * 16 + i16; mok[x] = mm[x] < M; }
     const float* in = (const float*)p.in;
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)((int64_t)M * p.in_ld * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t w0r = __builtin_amdgcn_make_buffer_rsrc((void*)p.w0, 0, p.hidden * 128 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w0fr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w0f, 0, p.hidden * 128 * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, 64 * p.hidden * 4, 0x00020000);
     auto ld = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); };
 
@@ -1773,12 +1782,22 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
     constexpr int HPF = 2;                              // weight tiles in registers: one requested ahead
     f32x4 w0v[HPF][8], w1v[HPF][4], b0v[HPF];
     const __amdgpu_buffer_rsrc_t b0r = __builtin_amdgcn_make_buffer_rsrc((void*)p.b0, 0, p.hidden * 4, 0x00020000);
-    const unsigned w0_lane = (unsigned)(i16 * 128 + 32 * q) * 4u, w1_lane = (unsigned)(i16 * p.hidden + 4 * q) * 4u;
+    const unsigned w0f_lane = (unsigned)q * (unsigned)(p.hidden / 32) * 4096u + 16u * i16, w1_lane = (unsigned)(i16 * p.hidden + 4 * q) * 4u;
+    // the workgroup's 32 pixel rows, once: thread (row = idx >> 5, 16-byte chunk idx & 31), a wave instruction is two whole rows
+    f32x4 xg[2];
+    if (!(DBG & 1)) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int idx = tid + j * NW * 64, m = ptile * 32 + (idx >> 5);
+            xg[j] = ld(xr, m < M ? (unsigned)((m * p.in_ld + 4 * (idx & 31)) * 4) : 0x80000000u, 0);
+        }
+    }
     auto request = [&](int k, f32x4* a, f32x4* b, f32x4* bias) {                               // k-th tile of this wave (clamped: no branch around loads)
+        if (DBG & 2) return;
         const int hl = wave + (k < my ? k : (my > 0 ? my - 1 : 0)) * NW;
         const int htc = ht0 + (hl < ntiles ? hl : 0);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) a[u] = ld(w0r, w0_lane + 16u * u, (unsigned)htc * (16u * 128u * 4u));
+        for (int u = 0; u < 8; ++u) a[u] = ld(w0fr, w0f_lane + 512u * u, (unsigned)(htc >> 1) * 4096u + (unsigned)(htc & 1) * 256u);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {                                                // the head's own output tiles (past the last: the last again)
             const int to = t_lo + (t < nt ? t : nt - 1);
@@ -1786,24 +1805,61 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
         }
         *bias = ld(b0r, 16u * q, (unsigned)htc * 64u);                               // the tile's bias rides with its weights (exact vmcnt counting)
     };
+    if (DBG & 2) {
+#pragma unroll
+        for (int b = 0; b < HPF; ++b) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) w0v[b][u] = f32x4{1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) w1v[b][t] = f32x4{1.f, 1.f, 1.f, 1.f};
+            b0v[b] = f32x4{1.f, 1.f, 1.f, 1.f};
+        }
+    }
     request(0, w0v[0], w1v[0], &b0v[0]);
     f32x4 xf[2][8];
+    if (DBG & 1) {
 #pragma unroll
-    for (int x = 0; x < 2; ++x)
+        for (int x = 0; x < 2; ++x)
 #pragma unroll
-        for (int u = 0; u < 8; ++u) xf[x][u] = ld(xr, mok[x] ? (unsigned)((mm[x] * p.in_ld + 32 * q + 4 * u) * 4) : 0x80000000u, 0);
+            for (int u = 0; u < 8; ++u) xf[x][u] = f32x4{1.f, 1.f, 1.f, 1.f};
+    } else {
+        // through LDS as [q][pixel][HX_LD]: the fragment read below (pixel i16, 16 bytes at channel 32 q + 4 u) is 16-byte slot
+        // 9 x pixel + u (mod 16; a q block is 288 slots) and a lane group of ds_read_b128 holds 16 different pixels (eight of
+        // q, the other eight of q + 1): conflict-free
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int idx = tid + j * NW * 64, c4 = idx & 31;
+            *(f32x4*)(xs + (c4 >> 3) * HX_QS + (idx >> 5) * HX_LD + 4 * (c4 & 7)) = xg[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) xf[x][u] = *(const f32x4*)(xs + q * HX_QS + (16 * x + i16) * HX_LD + 4 * u);
+    }
 
     f32x4 acc2[2][4];
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc2[x][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto one = [&](int k, auto P_) {
+    // LAST: the wave's final tile.  It requests nothing (the clamped repeat would be 13 loads nobody reads, and a wait for them
+    // in front of GEMM 2), so its waits count only what is in flight.
+    auto one = [&](int k, auto P_, auto LAST_) {
         constexpr int P = decltype(P_)::value;
-        request(k + HPF - 1, w0v[(P + HPF - 1) % HPF], w1v[(P + HPF - 1) % HPF], &b0v[(P + HPF - 1) % HPF]);
+        constexpr bool LAST = decltype(LAST_)::value;
+        if constexpr (!LAST) request(k + HPF - 1, w0v[(P + HPF - 1) % HPF], w1v[(P + HPF - 1) % HPF], &b0v[(P + HPF - 1) % HPF]);
         __builtin_amdgcn_sched_barrier(0);
         const f32x4 b0 = b0v[P];
         f32x4 acc1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        if (DBG & 4) {                                                   // the operands still arrive
+#pragma unroll
+            for (int u = 0; u < 8; ++u) asm volatile("" :: "v"(w0v[P][u]), "v"(xf[0][u]), "v"(xf[1][u]));
+#pragma unroll
+            for (int t = 0; t < 4; ++t) asm volatile("" :: "v"(w1v[P][t]));
+            asm volatile("" :: "v"(b0));
+            return;
+        }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
 #pragma unroll
@@ -1825,11 +1881,23 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
         }
     };
     int k = 0;
-    for (; k + HPF <= my; k += HPF) {
-        one(k, std::integral_constant<int, 0>{});
-        one(k + 1, std::integral_constant<int, 1>{});
+    for (; k + HPF < my; k += HPF) {                          // pairs with a tile behind them
+        one(k, std::integral_constant<int, 0>{}, std::false_type{});
+        one(k + 1, std::integral_constant<int, 1>{}, std::false_type{});
     }
-    if (k < my) one(k, std::integral_constant<int, 0>{});
+    if (k + HPF == my) {
+        one(k, std::integral_constant<int, 0>{}, std::false_type{});
+        one(k + 1, std::integral_constant<int, 1>{}, std::true_type{});
+    } else if (k < my) one(k, std::integral_constant<int, 0>{}, std::true_type{});
+    if (DBG & 8) {                                            // the accumulators stay live behind a store no launch performs
+        if (p.out_split == 0x7fffffff) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) *(f32x4*)((float*)p.out + ((x * 4 + t) * 64 + lane) * 4) = acc2[x][t];
+        }
+        return;
+    }
 
     // fixed-order reduction of the NW partial tiles: [wave][pixel block][t][lane] f32x4
 #pragma unroll
@@ -2038,6 +2106,15 @@ bool heads_f32_supported(int cin_pad, int hidden, int cout_pad, int64_t M, const
     return hidden % HL_HC == 0 && !(tune && tune->heads_f32_lds == 0);
 }
 
+template <int NW, int DBG>
+static hipError_t launch_heads_f32_i(const HeadsParams& p, hipStream_t s, unsigned grid, size_t lds) {
+    static LdsAttrOnce attr;
+    hipError_t e = attr.ensure((const void*)heads_f32_kernel<NW, DBG>, 96 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((heads_f32_kernel<NW, DBG>), dim3(grid), dim3(NW * 64), lds, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_heads_f32(const HeadsParams& p, hipStream_t s) {
     constexpr int NW = 8;
     const int64_t M = (int64_t)p.N * p.H * p.W;
@@ -2055,15 +2132,19 @@ hipError_t launch_heads_f32(const HeadsParams& p, hipStream_t s) {
         return hipGetLastError();
     }
     // 32 pixels of one head per workgroup (merged pair: pixel tiles x 2); 64 KiB of partial sums for the fixed-order reduction
-    const size_t lds = (size_t)NW * 2 * 4 * 64 * 4 * sizeof(float);
+    // and 18 KiB for the pixel tile
+    const size_t lds = ((size_t)NW * 2 * 4 * 64 * 4 + 4 * HX_QS) * sizeof(float);
     const unsigned nheads = p.out_split > 0 ? 2u : 1u;
-    if (p.out_split < 0 || p.out_split >= p.cout || (nheads == 2 && p.hidden % 32)) return hipErrorInvalidValue;
-    static LdsAttrOnce attr8;
-    hipError_t e = attr8.ensure((const void*)heads_f32_kernel<NW>, 64 * 1024);
-    if (e != hipSuccess) return e;
+    if (p.out_split < 0 || p.out_split >= p.cout || p.hidden % 32 || !p.w0f) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((M + 31) / 32) * nheads;
     LWP_VARIANT(p, "heads_f32<%d>", NW);
-    hipLaunchKernelGGL(heads_f32_kernel<NW>, dim3((unsigned)((M + 31) / 32) * nheads), dim3(NW * 64), lds, s, p);
-    return hipGetLastError();
+#ifdef LWP_ABLATION
+    const int d = (p.tune ? *p.tune : default_tuning()).heads_debug;         // LWP_HEADS_DEBUG
+#define HD_DBG(D_) if (d == D_) return launch_heads_f32_i<NW, D_>(p, s, grid, lds);
+    HD_DBG(1) HD_DBG(2) HD_DBG(4) HD_DBG(8) HD_DBG(7) HD_DBG(15)
+#undef HD_DBG
+#endif
+    return launch_heads_f32_i<NW, 0>(p, s, grid, lds);
 }
 
 // ---------------------------------------------------------------------------------------- switches
@@ -2092,7 +2173,7 @@ Tuning tuning_from_env() {
     if (const char* e = getenv("LWP_GEMMH")) t.has_gemmh = sscanf(e, "%d,%d,%d,%d", &t.gemmh[0], &t.gemmh[1], &t.gemmh[2], &t.gemmh[3]) == 4;
     digit("LWP_UPSAMPLE_TILED", &t.upsample_tiled);
     digit("LWP_PEAK_TILE", &t.peak_tile); digit("LWP_PAIR_FORM", &t.pair_form); digit("LWP_POST_NCHW", &t.post_nchw); digit("LWP_HEADS_F32_LDS", &t.heads_f32_lds); digit("LWP_MS_FUSED", &t.ms_fused); digit("LWP_MS_VEC", &t.ms_vec); geti("LWP_MS_TX", &t.ms_tx); digit("LWP_HOST_FETCH_DMA", &t.host_fetch_dma); geti("LWP_DWPW_LDS_PAD", &t.dwpw_lds_pad_kb);
-    geti("LWP_HEADS_F32_MAXM", &t.heads_f32_max_m);
+    geti("LWP_HEADS_F32_MAXM", &t.heads_f32_max_m); geti("LWP_HEADS_DEBUG", &t.heads_debug);
     geti("LWP_MAX_FRAMES_PER_PASS", &t.max_frames_per_pass);
     digit("LWP_FUSE_DWPW", &t.fuse_dwpw); digit("LWP_MERGE_HEADS", &t.merge_heads); digit("LWP_FUSE_HEADS", &t.fuse_heads);
     digit("LWP_PRE_BATCH_VEC", &t.pre_batch_vec); digit("LWP_POST_STREAM", &t.post_stream); digit("LWP_POST_GENERIC", &t.post_generic);
