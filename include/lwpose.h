@@ -663,6 +663,58 @@ int lwp_augment_batch_crowd(lwp_handle h, const lwp_augment_plan* plans, int N, 
                             const int64_t* counts, const int64_t* seg_off, const int64_t* image_seg_off, float* image_out,
                             unsigned char* mask_out, float* mask_small_out);
 
+/* ---- JPEG files: replaces cv2.imread(path, cv2.IMREAD_COLOR) in front of the sample path (datasets/coco.py:33, val.py:124,
+ *      demo.py:20) for baseline files.  The host parses the markers and decodes the Huffman data (csrc/jpeg_host.cpp, no GPU);
+ *      the device dequantises, runs libjpeg's default integer inverse DCT (jidctint.c's slow-but-accurate form: column pass
+ *      descaled by 11, then row pass descaled by 18), fancy up-sampling and the table-driven YCbCr conversion, and stores
+ *      interleaved BGR (csrc/jpeg_kernels.hip).  Every step is integer arithmetic, restated from libjpeg and pinned
+ *      bit for bit against libjpeg-turbo as Pillow bundles it; agreement with cv2 itself is NOT pinned (cv2 is not a
+ *      dependency).  The Exif orientation is reported and never applied, unlike cv2.imread from version 3.1 on.
+ *      IN SCOPE: SOF0 (baseline sequential Huffman, 8-bit), one interleaved scan, 1 component (grey; B = G = R = Y) or 3
+ *      (YCbCr), luma sampling 1x1 / 2x1 / 2x2 with both chroma components at 1x1, 8-bit quantisation tables, up to 4 + 4
+ *      Huffman tables, DRI / RSTn, 0xFF fill bytes in front of markers, APPn / COM skipped, APP14 Adobe with transform 1 or
+ *      none.  REFUSED with LWP_ERR_ARG, the message naming the reason and the byte offset: SOF1 / SOF2 (progressive) / SOF3
+ *      and above, arithmetic coding, 12-bit samples, 4 components, Adobe transform 0 or 2, any other sampling, several scans,
+ *      DNL, 16-bit quantisation tables, a missing table, a width or height of 0, and every malformed or truncated stream (a
+ *      segment length past the end, entropy data that ends before the last MCU, a Huffman code that matches no symbol, a DC
+ *      category above 11, an AC size above 10, a run past coefficient 63, a wrong or missing RSTn, a missing EOI).  libjpeg
+ *      warns and carries on in several of these cases; this library refuses them.
+ *      lwp_jpeg_header: blocks_w / blocks_h are each component's block-padded grid (mcus_x * h_samp by mcus_y * v_samp 8x8
+ *      blocks); a single-component file reports sampling 1x1 whatever its frame header states.
+ *      COEFFICIENT LAYOUT (lwp_debug_jpeg_blocks; what a device entropy decoder would fill): int16, 64 per block in natural
+ *      (de-zig-zagged, row-major) order, DC prediction undone, not dequantised; blocks in plane order, component by component,
+ *      each component's blocks row-major over its block-padded grid; qtables: 4 slots of 64 uint16 in natural order, component
+ *      c using slot quant_table[c]. */
+typedef struct lwp_jpeg_header {
+    int width, height, components;
+    int h_samp[3], v_samp[3], quant_table[3];
+    int restart_interval;                  /* MCUs between restart markers, 0: none */
+    int mcus_x, mcus_y;
+    int orientation;                       /* Exif tag 0x0112 of APP1 (1..8), 0: none; reported only */
+    int blocks_w[3], blocks_h[3];
+    int64_t total_blocks;                  /* 64 coefficients each */
+} lwp_jpeg_header;
+/* the header of one file (HOST bytes): parsed up to its scan header.  No handle, no GPU; message via lwp_last_error(NULL). */
+int lwp_jpeg_info(const unsigned char* data, size_t len, lwp_jpeg_header* out);
+/* the host half alone, for tests: coefficients (coef_cap int16 available; LWP_ERR_CAPACITY below 64 * total_blocks of
+ * lwp_jpeg_info) and quantisation tables (qtables[256]) of one file.  No handle, no GPU; safe to call from several threads. */
+int lwp_debug_jpeg_blocks(const unsigned char* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtables);
+/* N files (HOST bytes data[i], len[i]) -> out[i], a DEVICE pointer to height * width * 3 bytes of row-major BGR that the caller
+ * sized from lwp_jpeg_info.  1 <= N <= 65535.  All N files are parsed and entropy-decoded before anything is enqueued: a
+ * refused file fails the whole call with its index in the message (the lowest, if several are) and no output is written.  From
+ * 256 KiB of input on, the files' entropy decode is shared among up to 16 host threads that live for the call; the result does
+ * not depend on it.  Coefficients, tables and the
+ * per-image descriptors go up in ONE copy through pinned staging; two launches (inverse DCT into block-padded uint8 planes
+ * in a workspace of the handle; up-sample + colour + store) cover the whole batch, files of different sizes and samplings
+ * mixed.  Runs on the handle's stream and honours lwp_set_stream like the other device-returning calls; the staging is not
+ * rewritten while the copy of an earlier call may be pending.  Workspace and staging show in lwp_debug_live_resources and go
+ * with lwp_destroy.  Needs no weights.  Two calls on the same bytes return the same bits. */
+int lwp_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out);
+/* the two kernels alone (tools/jpeg_bench.py): the same checks, decode and upload, then `iters` back-to-back launches of each
+ * stage between HIP events.  ms_total[2] out: stage A, stage B. */
+int lwp_time_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out,
+                               int iters, float* ms_total);
+
 /* ---- COCO key-point evaluation: replaces pycocotools' COCOeval(gt, dt, 'keypoints') evaluate() + accumulate() behind
  *      val.py:17-27, with COCOeval's default parameters (the 17 OKS sigmas, IoU thresholds 0.5:0.05:0.95, 101 recall
  *      thresholds, maxDets 20, area ranges all [0, 1e10] / medium [32^2, 96^2] / large [96^2, 1e10], inclusive at both ends) and

@@ -42,6 +42,7 @@ EXPORTS = [
     "lwp_coco_eval", "lwp_debug_coco_oks",
     "lwp_coco_open", "lwp_coco_release", "lwp_coco_reset", "lwp_coco_add_maps", "lwp_coco_add_rows", "lwp_coco_counts",
     "lwp_coco_rows", "lwp_coco_finish", "lwp_debug_coco_rows",
+    "lwp_jpeg_info", "lwp_debug_jpeg_blocks", "lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch",
 ]
 
 
@@ -53,6 +54,14 @@ class AugmentPlan(C.Structure):
                 ("dst_y0", C.c_int), ("dst_y1", C.c_int), ("dst_x0", C.c_int), ("dst_x1", C.c_int),
                 ("img_y0", C.c_int), ("img_x0", C.c_int), ("flip", C.c_int),
                 ("warp_pad", C.c_ubyte * 3), ("crop_pad", C.c_ubyte * 3)]
+
+
+class JpegHeader(C.Structure):
+    """lwp_jpeg_header of include/lwpose.h: what lwp_jpeg_info reports of one file."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int),
+                ("h_samp", C.c_int * 3), ("v_samp", C.c_int * 3), ("quant_table", C.c_int * 3),
+                ("restart_interval", C.c_int), ("mcus_x", C.c_int), ("mcus_y", C.c_int), ("orientation", C.c_int),
+                ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3), ("total_blocks", C.c_int64)]
 
 
 class CapacityError(RuntimeError):
@@ -184,6 +193,10 @@ def lib():
     L.lwp_coco_rows.argtypes = [vp, ip, dp, dp, C.c_int64]
     L.lwp_coco_finish.argtypes = [vp, dp, dp, dp, i64p]
     L.lwp_debug_coco_rows.argtypes = [vp, C.c_int, dp, ip, dp, ip, ip]
+    L.lwp_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(JpegHeader)]
+    L.lwp_debug_jpeg_blocks.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.lwp_jpeg_decode_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
+    L.lwp_time_jpeg_decode_batch.argtypes = L.lwp_jpeg_decode_batch.argtypes + [C.c_int, fp]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

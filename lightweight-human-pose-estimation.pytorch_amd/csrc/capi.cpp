@@ -8,8 +8,11 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <system_error>
+#include <thread>
 #include <vector>
 
+#include "jpeg_host.h"
 #include "lwp_internal.h"
 #include "lwp_owners.h"
 
@@ -141,6 +144,10 @@ struct lwp_context {
         std::vector<int64_t> gt_off;                 // host copy: the OKS offsets of an evaluation need G per image
         std::vector<char> added;                     // per image: rows were appended since the last reset
     } coco;
+    // JPEG decode (lwp_jpeg_decode_batch): the device workspace [upload: coefficients | tables | descriptors][component planes],
+    // the pinned staging of the upload and the event behind its last copy (the staging is not rewritten before it)
+    DevBuf d_jpeg;
+    PinBuf jpeg_stage; Event jpeg_ev; bool jpeg_copy_pending = false;
     bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
@@ -248,7 +255,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 105; }
+extern "C" int lwp_version(void) { return 106; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -2457,6 +2464,172 @@ extern "C" int lwp_crowd_masks(lwp_handle h, const int64_t* counts, const int64_
     if (rc) return rc;
     if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return LWP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- JPEG decode
+extern "C" int lwp_jpeg_info(const unsigned char* data, size_t len, lwp_jpeg_header* out) {
+    if (!data || !out) return fail(nullptr, LWP_ERR_ARG, "data / out is null");
+    char msg[256] = {0};
+    if (jpeg_parse_header(data, len, out, msg, sizeof msg) != JPEG_OK) return fail(nullptr, LWP_ERR_ARG, msg);
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_jpeg_blocks(const unsigned char* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtables) {
+    if (!data || !coef || !qtables) return fail(nullptr, LWP_ERR_ARG, "data / coef / qtables is null");
+    char msg[256] = {0};
+    lwp_jpeg_header hd;
+    const int rc = jpeg_decode_blocks(data, len, &hd, coef, coef_cap, qtables, msg, sizeof msg);
+    if (rc == JPEG_CAPACITY) return fail(nullptr, LWP_ERR_CAPACITY, msg);
+    if (rc != JPEG_OK) return fail(nullptr, LWP_ERR_ARG, msg);
+    return LWP_OK;
+}
+
+// checks, the host half of every file and the batch's one upload [coefficients | tables | plane records | plane starts | image
+// records | image starts]; the component planes lie behind it in the same allocation.  Nothing is enqueued before every file
+// has been decoded: a refusal leaves the outputs untouched.
+static int jpeg_prepare(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out, JpegLaunch* launch) {
+    char msg[400], why[256];
+    if (!data || !len || !out) return fail(h, LWP_ERR_ARG, "data / len / out is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    std::vector<lwp_jpeg_header> hd((size_t)N);
+    uint64_t blocks = 0, units = 0;
+    int n_planes = 0;
+    for (int i = 0; i < N; ++i) {
+        if (!data[i] || !out[i]) { snprintf(msg, sizeof msg, "image %d: data / out is null", i); return fail(h, LWP_ERR_ARG, msg); }
+        why[0] = 0;
+        if (jpeg_parse_header(data[i], len[i], &hd[i], why, sizeof why) != JPEG_OK) {
+            snprintf(msg, sizeof msg, "image %d: %s", i, why);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        blocks += (uint64_t)hd[i].total_blocks;
+        units += (uint64_t)hd[i].height * (uint64_t)((hd[i].width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
+        n_planes += hd[i].components;
+    }
+    if (blocks > 0x7fffffffu || units > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^31 or more blocks or pixel groups: decode it in parts");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_coef = 0, o_qt = align16((size_t)blocks * 128), o_planes = o_qt + (size_t)N * kJpegQuantSlots * 128;
+    const size_t o_pstart = align16(o_planes + (size_t)n_planes * sizeof(JpegPlane)), o_images = align16(o_pstart + ((size_t)n_planes + 1) * 4);
+    const size_t o_istart = align16(o_images + (size_t)N * sizeof(JpegImage));
+    const size_t upload = (o_istart + ((size_t)N + 1) * 4 + 255) & ~(size_t)255;
+    const size_t total = upload + (size_t)blocks * 64;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->jpeg_copy_pending) {                        // the copy of the call before may still read the staging
+        HIP_TRY(h, hipEventSynchronize(h->jpeg_ev));
+        h->jpeg_copy_pending = false;
+    }
+    HIP_TRY(h, h->jpeg_stage.ensure(upload));
+    unsigned char* host = h->jpeg_stage.as<unsigned char>();
+    JpegPlane* planes = reinterpret_cast<JpegPlane*>(host + o_planes);
+    unsigned* pstart = reinterpret_cast<unsigned*>(host + o_pstart);
+    JpegImage* images = reinterpret_cast<JpegImage*>(host + o_images);
+    unsigned* istart = reinterpret_cast<unsigned*>(host + o_istart);
+    // the entropy decode of the files: independent of each other, each into its own part of the staging, so a large batch is
+    // shared among up to kJpegHostThreads threads (file i goes to thread i mod T; the result does not depend on T).  The
+    // first refused file in index order is the one reported.
+    std::vector<uint64_t> first_block((size_t)N + 1, 0);
+    size_t in_bytes = 0;
+    for (int i = 0; i < N; ++i) { first_block[i + 1] = first_block[i] + (uint64_t)hd[i].total_blocks; in_bytes += len[i]; }
+    std::vector<int> bad((size_t)N, 0);
+    std::vector<std::string> bad_why((size_t)N);
+    auto decode_file = [&](int i) {
+        lwp_jpeg_header now;
+        char w[256] = {0};
+        const int rc = jpeg_decode_blocks(data[i], len[i], &now, reinterpret_cast<int16_t*>(host + o_coef) + first_block[i] * 64,
+                                          (size_t)hd[i].total_blocks * 64, reinterpret_cast<uint16_t*>(host + o_qt) + (size_t)i * kJpegQuantSlots * 64,
+                                          w, sizeof w);
+        if (rc != JPEG_OK || now.total_blocks != hd[i].total_blocks) { bad[i] = 1; bad_why[i] = rc != JPEG_OK ? w : "the file changed during the call"; }
+    };
+    int T = std::min({kJpegHostThreads, N, (int)std::max(1u, std::thread::hardware_concurrency())});
+    if (in_bytes < kJpegThreadedFromBytes) T = 1;
+    if (T > 1) {
+        std::vector<std::thread> pool;
+        int started = 1;                               // this thread is the first
+        try {
+            for (; started < T; ++started) pool.emplace_back([&, t = started]() { for (int i = t; i < N; i += T) decode_file(i); });
+        } catch (const std::system_error&) {}          // no more threads to be had: this one takes the rest below
+        for (int i = 0; i < N; i += T) decode_file(i);
+        for (std::thread& th : pool) th.join();
+        for (int t = started; t < T; ++t)
+            for (int i = t; i < N; i += T) decode_file(i);
+    } else {
+        for (int i = 0; i < N && !(i && bad[i - 1]); ++i) decode_file(i);
+    }
+    for (int i = 0; i < N; ++i)
+        if (bad[i]) {
+            snprintf(msg, sizeof msg, "image %d: %s", i, bad_why[i].c_str());
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+    uint64_t b0 = 0, u0 = 0;
+    int p = 0;
+    for (int i = 0; i < N; ++i) {
+        const lwp_jpeg_header& f = hd[i];
+        JpegImage& im = images[i];
+        memset(&im, 0, sizeof im);
+        im.unit0 = (unsigned)u0; istart[i] = (unsigned)u0;
+        im.width = f.width; im.height = f.height;
+        im.mode = f.components == 1 ? 0 : f.h_samp[0] == 1 ? 1 : f.v_samp[0] == 1 ? 2 : 3;
+        im.chroma_w = f.components == 1 ? 0 : (f.width + f.h_samp[0] - 1) / f.h_samp[0];
+        im.chroma_h = f.components == 1 ? 0 : (f.height + f.v_samp[0] - 1) / f.v_samp[0];
+        im.out = out[i];
+        for (int c = 0; c < f.components; ++c) {
+            JpegPlane& pl = planes[p];
+            pl.block0 = (unsigned)b0; pstart[p] = (unsigned)b0;
+            pl.blocks_w = f.blocks_w[c];
+            pl.qt = (unsigned)(((size_t)i * kJpegQuantSlots + (size_t)f.quant_table[c]) * 64);
+            pl.pad_ = 0;
+            pl.plane = (long long)(upload + b0 * 64);
+            im.plane[c] = pl.plane; im.stride[c] = f.blocks_w[c] * 8;
+            b0 += (uint64_t)f.blocks_w[c] * f.blocks_h[c];
+            ++p;
+        }
+        u0 += (uint64_t)f.height * (uint64_t)((f.width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
+    }
+    pstart[n_planes] = (unsigned)b0; istart[N] = (unsigned)u0;
+    int rc = order_in(h);
+    if (rc) return rc;
+    if (h->d_jpeg.size() < total) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        HIP_TRY(h, h->d_jpeg.ensure(total));
+    }
+    unsigned char* dev = h->d_jpeg.as<unsigned char>();
+    HIP_TRY(h, h->jpeg_ev.ensure(hipEventDisableTiming));
+    HIP_TRY(h, hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->jpeg_ev, h->stream));
+    h->jpeg_copy_pending = true;
+    JpegLaunch j{};
+    j.coef = reinterpret_cast<const int16_t*>(dev + o_coef); j.qtables = reinterpret_cast<const uint16_t*>(dev + o_qt);
+    j.planes = reinterpret_cast<const JpegPlane*>(dev + o_planes); j.plane_block0 = reinterpret_cast<const unsigned*>(dev + o_pstart);
+    j.images = reinterpret_cast<const JpegImage*>(dev + o_images); j.image_unit0 = reinterpret_cast<const unsigned*>(dev + o_istart);
+    j.workspace = dev;
+    j.n_planes = n_planes; j.n_images = N;
+    j.total_blocks = (unsigned)b0; j.total_units = (unsigned)u0;
+    *launch = j;
+    return LWP_OK;
+}
+
+extern "C" int lwp_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out) {
+    JpegLaunch j{};
+    int rc = jpeg_prepare(h, N, data, len, out, &j);
+    if (rc) return rc;
+    LAUNCH(h, KC_OTHER, launch_jpeg_idct(j, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_color(j, h->stream));
+    bool ordered = false;
+    rc = order_out(h, h->stream, &ordered);
+    if (rc) return rc;
+    if (!ordered) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_time_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len,
+                                          unsigned char* const* out, int iters, float* ms_total) {
+    if (iters < 1 || !ms_total) return fail(h, LWP_ERR_ARG, "iters must be at least 1 and ms_total non-null");
+    JpegLaunch j{};
+    int rc = jpeg_prepare(h, N, data, len, out, &j);
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_idct(j, h->stream)); return (int)LWP_OK; }, &ms_total[0]);
+    if (rc) return rc;
+    return time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_color(j, h->stream)); return (int)LWP_OK; }, &ms_total[1]);
 }
 
 // ---------------------------------------------------------------------------------------------- training augmentation

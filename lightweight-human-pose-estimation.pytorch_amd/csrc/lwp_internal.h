@@ -419,6 +419,38 @@ struct CrowdLaunch {
     int n_images, max_h, max_w;
 };
 hipError_t launch_crowd_masks(const CrowdLaunch& c, hipStream_t s);
+// ---- JPEG decode, device half (jpeg_kernels.hip; libjpeg's default path: jidctint.c, fancy up-sampling, jdcolor.c): stage A
+// turns the coefficient blocks of a batch into block-padded uint8 component planes, stage B up-samples, converts and stores BGR
+constexpr int kJpegBlocksPerGroup = 32;   // stage A: 8 lanes a block, 256 threads a workgroup
+constexpr int kJpegPixelsPerThread = 4;   // stage B: horizontally adjacent output pixels of one thread
+constexpr int kJpegUnitsPerGroup = 256;   // stage B: threads (pixel groups) a workgroup
+struct JpegPlane {                        // one component of one image
+    unsigned block0;                      // its first block in the batch's plane-ordered coefficient array
+    int blocks_w;                         // blocks a block row (the plane is blocks_w * 8 bytes wide)
+    unsigned qt;                          // uint16 offset of its quantisation table (natural order) in the batch's table array
+    unsigned pad_;
+    long long plane;                      // byte offset of the plane in the workspace
+};
+struct JpegImage {
+    unsigned unit0;                       // its first pixel group in the batch (a row holds ceil(width / kJpegPixelsPerThread))
+    int width, height;
+    int mode;                             // 0 grey, 1 4:4:4, 2 4:2:2 (h2v1), 3 4:2:0 (h2v2)
+    int chroma_w, chroma_h;               // TRUE size of the chroma planes: the edges the up-sampling replicates
+    int stride[3];                        // bytes a row of each plane
+    int pad_;
+    long long plane[3];                   // byte offsets of the planes in the workspace
+    unsigned char* out;                   // height * width * 3 bytes, BGR
+};
+struct JpegLaunch {
+    const int16_t* coef; const uint16_t* qtables;
+    const JpegPlane* planes; const unsigned* plane_block0;    // [n_planes] records; [n_planes + 1] their block0, then the total
+    const JpegImage* images; const unsigned* image_unit0;     // [n_images]; [n_images + 1]
+    unsigned char* workspace;
+    int n_planes, n_images;
+    unsigned total_blocks, total_units;
+};
+hipError_t launch_jpeg_idct(const JpegLaunch& j, hipStream_t s);
+hipError_t launch_jpeg_color(const JpegLaunch& j, hipStream_t s);
 // ---- COCO key-point evaluation (eval_kernels.hip; COCOeval with iouType 'keypoints' and its default parameters): float64
 constexpr int kEvalK = 17;            // key-points of a person
 constexpr int kEvalMaxDets = 20;      // detections of an image that count (maxDets)

@@ -12,12 +12,16 @@ arrays of the C call), and a sample of ``plan_batch`` / ``DeviceAugment`` / ``va
 ``"segmentations"`` instead of a float ``"mask"``: the mask is then rendered on the device and never crosses PCIe.  Both restate
 ``maskApi.c``'s ``rleDecode`` and are unpinned against pycocotools itself.
 
-Out of scope: reading images and annotations (``cv2.imread``, ``pycocotools``).  Labels arrive in
+Images are read by ``imread`` / ``CocoTrainDataset`` / ``CocoValDataset`` at the end of this file: baseline JPEG files, the
+Huffman data decoded on the host and everything behind it on the GPU (``Engine.decode_jpeg_batch``), pinned against
+libjpeg-turbo and not against ``cv2.imread`` itself.  Out of scope: reading annotations (``pycocotools``).  Labels arrive in
 ``scripts/prepare_train_labels.py``'s format, as ``datasets.transformations`` (the augmentations, host classes and the device
 batch path) leaves them; ``generate_targets`` takes the float mask mean, ``val.augmented_train_step`` the reference's rounded
 uint8 mask.
 """
 import numbers
+import os
+import re
 
 import numpy as np
 
@@ -128,3 +132,126 @@ def generate_targets(net, labels, image_hw, mask=None, stride=8, sigma=7, paf_th
     return {"keypoint_maps": kmaps, "paf_maps": pmaps,
             "keypoint_mask": small[:, None].expand(-1, kmaps.shape[1], -1, -1),
             "paf_mask": small[:, None].expand(-1, pmaps.shape[1], -1, -1)}
+
+
+# ---------------------------------------------------------------------------------------------- reading the files
+def _file_bytes(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes), "<bytes>"
+    with open(path_or_bytes, "rb") as f:
+        return f.read(), str(path_or_bytes)
+
+
+def imread(path_or_bytes, engine):
+    """``cv2.imread(path, cv2.IMREAD_COLOR)`` for a baseline JPEG file, decoded by ``Engine.decode_jpeg_batch``: a cuda uint8
+    (H, W, 3) BGR tensor.  In scope: baseline (SOF0) files, grey or YCbCr at 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan;
+    progressive, arithmetic-coded, 12-bit and CMYK files, and every malformed one, are a ValueError that names the file and the
+    reason.  The arithmetic is libjpeg's default integer path, pinned bit for bit against libjpeg-turbo as Pillow bundles it and
+    NOT against cv2 itself.  The Exif orientation is not applied (``Engine.jpeg_info`` reports it), unlike
+    ``cv2.imread`` from OpenCV 3.1 on."""
+    data, name = _file_bytes(path_or_bytes)
+    try:
+        return engine.decode_jpeg_batch([data])[0]
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, re.sub(r"^image 0: ", "", str(e)))) from None
+
+
+class _JpegFolder(object):
+    """What the two datasets share: the folder, the engine, and the optional ``fallback(path) -> uint8 HxWx3 BGR`` for files
+    the decoder refuses (``fallbacks`` counts its calls).  The package imports no decoder of its own accord."""
+
+    def __init__(self, images_folder, engine, fallback=None):
+        self._images_folder = images_folder
+        self._engine = getattr(engine, "engine", engine)
+        self._fallback = fallback
+        self.fallbacks = 0
+
+    def _read_batch(self, file_names):
+        """The images of ``file_names`` as cuda uint8 (H, W, 3) tensors: every file the decoder takes in ONE device call."""
+        import torch
+        eng = self._engine
+        paths = [os.path.join(self._images_folder, f) for f in file_names]
+        images, datas = [None] * len(paths), []
+        for path in paths:
+            with open(path, "rb") as f:
+                datas.append(f.read())
+        todo = list(range(len(paths)))
+        while todo:
+            try:
+                for i, img in zip(todo, eng.decode_jpeg_batch([datas[i] for i in todo])):
+                    images[i] = img
+                break
+            except ValueError as e:                    # "image k: reason", k indexing this call's list; nothing was written
+                m = re.match(r"image (\d+): (.*)", str(e), re.S)
+                if m is None:
+                    raise
+                k = int(m.group(1))
+                if self._fallback is None:
+                    raise ValueError("%s: %s" % (paths[todo[k]], m.group(2))) from None
+                del todo[k]                            # the fallback takes it below; the others are decoded again, without it
+        for i, path in enumerate(paths):
+            if images[i] is None:
+                a = np.ascontiguousarray(self._fallback(path))
+                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError("%s: the fallback must return a uint8 (H, W, 3) BGR array" % path)
+                self.fallbacks += 1
+                images[i] = torch.from_numpy(a).to(torch.device("cuda", eng.device_id))
+        return images
+
+
+class CocoValDataset(_JpegFolder):
+    """The validation images of a COCO ground-truth file (reference: datasets/coco.py:162-178), for ``val.evaluate``: iterable
+    and indexable, one ``{'file_name', 'img'}`` per entry of ``labels['images']`` with ``img`` a cuda uint8 (H, W, 3) BGR
+    tensor.  ``labels``: the file's path or the dict."""
+
+    def __init__(self, labels, images_folder, engine, fallback=None):
+        super().__init__(images_folder, engine, fallback)
+        if isinstance(labels, dict):
+            self._labels = labels
+        else:
+            import json
+            with open(labels) as f:
+                self._labels = json.load(f)
+
+    def __len__(self):
+        return len(self._labels["images"])
+
+    def __getitem__(self, idx):
+        file_name = self._labels["images"][idx]["file_name"]
+        return {"file_name": file_name, "img": self._read_batch([file_name])[0]}
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
+class CocoTrainDataset(_JpegFolder):
+    """The training samples of ``scripts/prepare_train_labels.py``'s label list (reference: datasets/coco.py:24-44) up to the
+    transform: ``samples(indices)`` decodes the images of a batch in ONE device call and returns the dicts ``DeviceAugment`` /
+    ``val.augmented_train_step`` take, ``'image'`` a cuda uint8 tensor the augment kernel reads in place, ``'label'`` a deep copy
+    and ``'segmentations'`` the label's crowd RLEs (the mask is rendered on the device).  ``labels``: the pickle's path or the
+    list itself."""
+
+    def __init__(self, labels, images_folder, engine, fallback=None):
+        super().__init__(images_folder, engine, fallback)
+        if isinstance(labels, (list, tuple)):
+            self._labels = list(labels)
+        else:
+            import pickle
+            with open(labels, "rb") as f:
+                self._labels = pickle.load(f)
+
+    def __len__(self):
+        return len(self._labels)
+
+    def samples(self, indices):
+        import copy
+        labels = [copy.deepcopy(self._labels[i]) for i in indices]
+        images = self._read_batch([label["img_paths"] for label in labels])
+        for label, image in zip(labels, images):
+            if (int(image.shape[0]), int(image.shape[1])) != (label["img_height"], label["img_width"]):
+                raise ValueError("%s is %d x %d but its label says %d x %d" % (label["img_paths"], image.shape[1], image.shape[0],
+                                                                             label["img_width"], label["img_height"]))
+        return [{"image": image, "label": label, "segmentations": label.get("segmentations", [])} for label, image in zip(labels, images)]
+
+    def __getitem__(self, idx):
+        return self.samples([idx])[0]

@@ -11,6 +11,29 @@ from .modules.keypoints import extract_keypoints, group_keypoints
 from .modules.pose import Pose, poses_from_arrays, track_poses
 
 
+class ImageReader(object):
+    """The reference's image provider (demo.py:14-30) for baseline JPEG files: iterating yields one cuda uint8 (H, W, 3) BGR
+    frame per file name, read by ``datasets.coco.imread`` (a file outside its scope is a ValueError naming the file; an
+    unreadable path an OSError).  ``engine``: an ``Engine`` or a net that has one."""
+
+    def __init__(self, file_names, engine):
+        self.file_names = list(file_names)
+        self.max_idx = len(self.file_names)
+        self._engine = getattr(engine, "engine", engine)
+
+    def __iter__(self):
+        self.idx = 0
+        return self
+
+    def __next__(self):
+        from .datasets.coco import imread
+        if self.idx == self.max_idx:
+            raise StopIteration
+        img = imread(self.file_names[self.idx], self._engine)
+        self.idx += 1
+        return img
+
+
 def _prepare(net, img, net_input_height_size, stride, pad_value, img_mean, img_scale):
     """demo.py:55-64 (resize by height, normalize, pad, to tensor) as one GPU kernel: uint8 frame -> cuda tensor.  The tensor never
     leaves infer_fast / run_demo, so it stays on the engine's stream (no hand-over to torch's current stream)."""

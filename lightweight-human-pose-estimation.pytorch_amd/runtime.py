@@ -819,6 +819,66 @@ class Engine(object):
         check(lib().lwp_crowd_masks(*args), self.h.ptr)
         return [buf[int(out_off[n]):int(out_off[n + 1])].view(h, w) for n, (h, w) in enumerate(sizes)]
 
+    # ------------------------------------------------------------------ JPEG files (cv2.imread's place)
+    @staticmethod
+    def jpeg_info(data):
+        """The header of one baseline JPEG file (``bytes``): a dict of lwp_jpeg_header's fields (width, height, components,
+        per-component sampling and quantisation table, restart interval, MCU and block counts, the Exif orientation or 0).
+        Needs no GPU.  ValueError, naming the reason and the byte offset, for a file outside the scope (include/lwpose.h)."""
+        data = bytes(data)
+        hd = _lib.JpegHeader()
+        check(lib().lwp_jpeg_info(data, len(data), C.byref(hd)))
+        n = hd.components
+        return {"width": hd.width, "height": hd.height, "components": n, "h_samp": list(hd.h_samp)[:n], "v_samp": list(hd.v_samp)[:n],
+                "quant_table": list(hd.quant_table)[:n], "restart_interval": hd.restart_interval, "mcus_x": hd.mcus_x,
+                "mcus_y": hd.mcus_y, "orientation": hd.orientation, "blocks_w": list(hd.blocks_w)[:n],
+                "blocks_h": list(hd.blocks_h)[:n], "total_blocks": hd.total_blocks}
+
+    @staticmethod
+    def debug_jpeg_blocks(data):
+        """The host half alone (tests; no GPU): (header dict, coefficients int16 (total_blocks, 64) in natural order and plane
+        order, quantisation tables uint16 (4, 64) in natural order)."""
+        data = bytes(data)
+        hd = Engine.jpeg_info(data)
+        coef = np.empty((hd["total_blocks"], 64), dtype=np.int16)
+        qt = np.empty((4, 64), dtype=np.uint16)
+        check(lib().lwp_debug_jpeg_blocks(data, len(data), coef.ctypes.data, coef.size, qt.ctypes.data))
+        return hd, coef, qt
+
+    def decode_jpeg_batch(self, files, time_iters=0):
+        """``cv2.imread(.., IMREAD_COLOR)`` of a batch of baseline JPEG files (a list of ``bytes``), decoded in ONE device call:
+        the Huffman data on the host, inverse DCT, up-sampling, colour conversion and the BGR store on the GPU, files of different
+        sizes and samplings mixed.  Returns a list of cuda uint8 (H, W, 3) tensors, views of one allocation.  ValueError with the
+        file's index for one outside the scope; nothing is written then.  The Exif orientation is not applied.  With
+        ``time_iters`` > 0 each of the two kernels is launched that many times back to back and the call returns their
+        milliseconds (stage A, stage B)."""
+        torch = _torch()
+        files = [bytes(f) for f in files]
+        N = len(files)
+        if N == 0:
+            return []
+        sizes = []
+        for i, f in enumerate(files):
+            hd = _lib.JpegHeader()
+            rc = lib().lwp_jpeg_info(f, len(f), C.byref(hd))
+            if rc:
+                raise ValueError("image %d: %s" % (i, lib().lwp_last_error(None).decode("utf-8", "replace")))
+            sizes.append((hd.height, hd.width))
+        off = np.zeros(N + 1, dtype=np.int64)           # every image starts on a 16-byte boundary of the allocation
+        for i, (h, w) in enumerate(sizes):
+            off[i + 1] = (off[i] + h * w * 3 + 15) // 16 * 16
+        buf = torch.empty((int(off[-1]),), dtype=torch.uint8, device=torch.device("cuda", self.device_id))
+        data = (C.c_void_p * N)(*[C.cast(C.c_char_p(f), C.c_void_p) for f in files])
+        lens = (C.c_size_t * N)(*[len(f) for f in files])
+        outs = (C.c_void_p * N)(*[buf.data_ptr() + int(off[i]) for i in range(N)])
+        self._order()
+        if time_iters:
+            ms = (C.c_float * 2)()
+            check(lib().lwp_time_jpeg_decode_batch(self.h.ptr, N, data, lens, outs, int(time_iters), ms), self.h.ptr)
+            return ms[0], ms[1]
+        check(lib().lwp_jpeg_decode_batch(self.h.ptr, N, data, lens, outs), self.h.ptr)
+        return [buf[int(off[i]):int(off[i]) + h * w * 3].view(h, w, 3) for i, (h, w) in enumerate(sizes)]
+
     def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
         """train.py:92-97's per-stage sums: ``outs`` is the list net(x) returned (cuda tensors; an entry may be None),
         ``keypoint_maps`` / ``paf_maps`` the targets, ``mask`` one (N, h, w) cuda tensor broadcast over the channels.

@@ -83,7 +83,11 @@ def accumulate_scales(net, inputs, height, width, stride):
 
 
 def infer_batch(net, imgs, scales, base_height, stride, pad_value=(0, 0, 0), img_mean=(128, 128, 128), img_scale=1/256):
-    """``infer`` (val.py:81-110) for N same-sized uint8 frames at once; returns cuda tensors (N,H,W,19), (N,H,W,38)."""
+    """``infer`` (val.py:81-110) for N same-sized uint8 frames at once; returns cuda tensors (N,H,W,19), (N,H,W,38).  A list may
+    hold NumPy arrays or cuda tensors (``datasets.coco.imread`` / ``CocoValDataset`` yield those), not a mix."""
+    if isinstance(imgs, (list, tuple)) and len(imgs) and all(getattr(a, "is_cuda", False) for a in imgs):
+        import torch
+        imgs = torch.stack(list(imgs))
     imgs = _as_frames(np.stack(list(imgs)) if isinstance(imgs, (list, tuple)) else imgs)
     inputs = scaled_inputs(net, imgs, scales, base_height, stride, pad_value, img_mean, img_scale)
     return accumulate_scales(net, inputs, int(imgs.shape[1]), int(imgs.shape[2]), stride)
@@ -274,14 +278,15 @@ def evaluate(labels, output_name, samples, net, multiscale=False, visualize=Fals
     store (``Engine.coco_finish``), the reference's lines are printed and the ten stats returned.
 
     One difference from the reference: the third argument is an iterable of ``{'file_name': '<image id>.jpg', 'img': uint8
-    HxWx3}`` samples, not an images folder (image decoding is not part of this package).  ``labels``: the ground-truth file's
+    HxWx3}`` samples (NumPy arrays or cuda tensors), not an images folder; ``datasets.coco.CocoValDataset(labels, images_folder,
+    engine)`` yields them from a folder of baseline JPEG files.  ``labels``: the ground-truth file's
     path, or the dict itself.  ``output_name`` None: no file is written.  The file holds the list ``coco_detections`` returns
     for the same samples.  ``store=True`` keeps the ground truth and the store on the engine for the next call with the same
     ``labels`` (the same dict object, or the same path; a training run that validates every ``val_after`` iterations);
     otherwise they are released."""
     if isinstance(samples, (str, bytes)):
         raise TypeError("evaluate takes an iterable of {'file_name', 'img'} samples as its third argument, not an images "
-                        "folder: image decoding is not part of this package")
+                        "folder: datasets.coco.CocoValDataset(labels, images_folder, engine) makes one from a folder")
     if visualize:
         raise NotImplementedError("visualize needs cv2.imshow, which this package does not depend on")
     eng = net.engine
