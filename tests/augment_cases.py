@@ -63,3 +63,12 @@ def synthetic_sample(seed, h, w, others=1, scale_provided=0.6, with_mask=True):
         mask[h // 4:h // 2, w // 3:w // 3 + max(w // 4, 1)] = 0
         mask[0, 0] = 0.5
     return {"image": g.integers(0, 256, size=(h, w, 3), dtype=np.uint8), "mask": mask, "label": label}
+
+
+def crop_sample(h, w, objpos, mask_value=1.0, seed=None):
+    """A sample for CropPad alone: pixels in 0..99 (never a pad value used by the tests), 18 key-points, a constant mask."""
+    g = np.random.default_rng(h * 100 + w if seed is None else seed)
+    image = g.integers(0, 100, size=(h, w, 3), dtype=np.uint8)           # never the pad value
+    label = {"keypoints": [[1.0, 2.0, 1] for _ in range(18)], "objpos": list(objpos), "img_width": w, "img_height": h,
+             "processed_other_annotations": []}
+    return {"image": image, "mask": np.full((h, w), mask_value, dtype=np.float32), "label": label}

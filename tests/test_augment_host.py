@@ -2,7 +2,8 @@
 against what the reference's own Python produced (tests/golden/augment_cases.npz, tools/make_augment_golden.py): labels,
 sizes, crop geometry, the order of the random draws and the dtype conversions are pinned bit for bit.  The pixel routines
 restate OpenCV and cannot be pinned here; they get hand-derived checks that do not depend on the restatement being
-self-consistent.  And the argument checks of the two new exports that need no GPU."""
+self-consistent.  And the argument checks of the two new exports that need no GPU, and what the batches of
+augment_branch_cases.py are: the conditions under which each reaches the kernel path it is named for."""
 import copy
 import ctypes as C
 import random
@@ -14,6 +15,7 @@ import lwpose_amd  # noqa: F401
 from lwpose_amd import _lib
 from lwpose_amd.datasets import transformations as T
 
+import augment_branch_cases as bc
 import augment_cases as ac
 
 CASES = list(range(ac.n_cases()))
@@ -100,12 +102,7 @@ def test_the_fixture_set_keeps_its_coverage():
 
 
 # ------------------------------------------------------------------------------------------ 2. crop quirks
-def crop_sample(h, w, objpos, mask_value=1.0):
-    g = np.random.default_rng(h * 100 + w)
-    image = g.integers(0, 100, size=(h, w, 3), dtype=np.uint8)           # never the pad value
-    label = {"keypoints": [[1.0, 2.0, 1] for _ in range(18)], "objpos": list(objpos), "img_width": w, "img_height": h,
-             "processed_other_annotations": []}
-    return {"image": image, "mask": np.full((h, w), mask_value, dtype=np.float32), "label": label}
+crop_sample = ac.crop_sample                                             # shared with the branch cases (augment_branch_cases.py)
 
 
 def crop_both_ways(sample, crop=16):
@@ -333,3 +330,173 @@ def test_augment_exports_check_their_arguments_without_a_gpu():
     assert rc == _lib.LWP_ERR_ARG and b"sample 1" in msg
     assert L.lwp_time_augment_batch(None, recs, 1, 8, 16, 8, out, out, out, 0, C.byref(ms)) == _lib.LWP_ERR_ARG
     assert L.lwp_time_augment_batch(None, recs, 1, 8, 16, 8, out, out, out, 3, C.byref(ms)) == _lib.LWP_ERR_ARG and b"handle" in L.lwp_last_error(None)
+
+
+# ------------------------------------------------------------------------------------------ 5. the branch cases
+# augment_branch_cases.py: what each batch is, and that it reaches the kernel path it is named for
+def same_as_closed_form(b, result):
+    """Every sample of the batch that has a closed form equals it in (image, mask) of ``result``; returns how many had one."""
+    n_closed = 0
+    for n, exp in enumerate(bc.closed_form(b)):
+        if exp is None:
+            continue
+        n_closed += 1
+        assert np.array_equal(result[0][n], ac.network_image(exp[0])), (b["name"], n)
+        assert np.array_equal(result[1][n], exp[1]), (b["name"], n)
+    return n_closed
+
+
+def test_area_batches_plan_the_area_branch_with_and_without_the_clamp():
+    b = bc.area_batch()
+    plan, want = bc.plan_of(b), bc.host_result("area")
+    assert [(g["src_h"], g["src_w"]) for g in plan.records[::3]] == list(bc.AREA_SOURCES)
+    assert [(g["rs_h"], g["rs_w"]) for g in plan.records[::3]] == [(20, 28), (18, 26), (1, 1), (2, 2)]
+    for n, g in enumerate(plan.records):
+        assert g["scale"] == 0.5 and g["area"] is True and g["should_crop"]
+        assert (plan.masks[n] is None) == (b["kinds"][n] == "none")
+    assert {bool(g["flip"]) for g in plan.records[:6]} == {False, True}  # both flips among the samples that show picture
+    shown = bc.picture(want[0]).reshape(len(plan), -1).mean(axis=1)
+    assert np.all(shown[:6] >= 0.5), shown                               # 39 x 55 and 36 x 52: at least half the crop is picture
+    for n in range(6):
+        if b["kinds"][n] != "none":
+            assert np.any(want[1][n] == 0) and np.any(want[1][n] == 1)
+    fractions = b["samples"][0]["mask"]
+    assert np.any((fractions > 0) & (fractions < 1))
+
+
+def test_the_area_closed_form_holds_on_the_host_route():
+    b = bc.area_closed_batch()
+    plan, want = bc.plan_of(b), bc.host_result("area_closed")
+    for n, g in enumerate(plan.records):
+        assert g["scale"] == 0.5 and g["area"] is True and (g["rs_h"], g["rs_w"]) == (20, 28) and not g["flip"]
+        assert g["dst"] == (10, 30, 22, 50) and g["src0"] == (0, 0)
+        image, mask = bc.area_closed_expected(b["samples"][n])
+        assert np.array_equal(image[10:30, 22:50], T.resize_linear(b["samples"][n]["image"], 0.5))
+        outside = np.ones((40, 72), dtype=bool)
+        outside[10:30, 22:50] = False
+        assert np.all(image[outside] == np.array(bc.CROP_PAD, np.uint8)) and np.all(mask[outside] == 1)
+    assert same_as_closed_form(b, want) == 2
+    assert np.any(want[1][0] == 0) and np.any(want[1][0][10:30, 22:50] == 1) and np.all(want[1][1] == 1)
+
+
+@pytest.mark.parametrize("name", ["area", "area_closed", "area_crowd_decoded"])
+def test_the_bilinear_branch_at_a_step_of_two_gives_the_area_average(name, monkeypatch):
+    """uint8: every weight is 1024, so >> 4, >> 16 and (.. + 2) >> 2 reduce to (a + b + c + d + 2) >> 2; a {0, 1} mask: every
+    float operation is exact.  Fractional masks associate their sums differently and are left out."""
+    b = bc.named(name)
+    plan, want = bc.plan_of(b), bc.host_result(name)
+    assert all(g["area"] is False for g in bc.with_area(plan, False).records) and all(g["area"] is True for g in plan.records)
+    monkeypatch.setattr(T, "is_area_scale", lambda scale: False)
+    linear = T.apply_plan_host(plan, b["stride"])
+    exact = [n for n, kind in enumerate(b["kinds"]) if kind != "float"]
+    assert len(exact) >= 2
+    for n in exact:
+        for got, exp in zip(linear, want):
+            assert np.array_equal(got[n], exp[n]), (name, n)
+
+
+def test_the_area_crowd_sample_equals_its_decoded_float_mask():
+    with_segs, decoded = bc.area_crowd_batches()
+    plan, plan_decoded = bc.plan_of(with_segs), bc.plan_of(decoded)
+    assert [bool(s) for s in plan.segmentations] == [False, True, False] and plan.masks[1] is None and plan.crowd_runs is not None
+    assert plan_decoded.segmentations is None and all(g["area"] for g in plan.records)
+    want, want_decoded = bc.host_result("area_crowd"), bc.host_result("area_crowd_decoded")
+    assert all(np.array_equal(a, d) for a, d in zip(want, want_decoded))
+    assert 0 < int((want[1][1] == 0).sum()) < want[1][1].size and np.any(want[2][1] == 0)
+
+
+def test_the_nothing_to_copy_batch_is_what_it_claims():
+    b = bc.nothing_batch()
+    plan, want = bc.plan_of(b), bc.host_result("nothing")
+    g = plan.records
+    assert [r["should_crop"] for r in g] == [True, False, True, True, True, True, True]
+    assert g[3]["dst"] == (0, 0, 0, 16) and g[4]["dst"] == (0, 16, 16, 16) and g[5]["dst"] == (0, 13, 0, 16) and g[5]["src0"] == (17, 12)
+    assert np.all(b["samples"][1]["mask"] == 0)                          # and it must not show
+    assert all(int(s["image"].max()) < 100 for s in b["samples"])        # never a pad value in all three channels
+    assert same_as_closed_form(b, want) == 7
+    pad = ((np.array(bc.CROP_PAD, np.float32) - 128) / 256).reshape(3, 1, 1)
+    for n in bc.NOTHING_ALL_PAD:
+        assert np.all(want[0][n] == pad) and np.all(want[1][n] == 1) and np.all(want[2][n] == 1)
+    assert np.all(want[1][5][:13] == 0) and np.all(want[1][5][13:] == 1) and np.all(want[2][5] == 0)
+
+
+def test_the_identity_batches_plan_the_identity_warp_and_copy_the_window():
+    for b in bc.identity_batches():
+        plan, want = bc.plan_of(b), bc.host_result(b["name"])
+        flipped = b["name"] == "identity_unit_scale_flipped"
+        for g in plan.records:
+            assert g["scale"] == 1.0 and not g["area"] and (g["rs_h"], g["rs_w"]) == (g["bound_h"], g["bound_w"]) == (30, 41)
+            assert np.array_equal(g["minv"], [1, 0, 0, 0, 1, 0]) and bool(g["flip"]) == flipped
+        assert [g["dst"] + g["src0"] for g in plan.records] == [(0, 16, 0, 18, 2, 23), (0, 11, 7, 24, 19, 0)]
+        assert same_as_closed_form(b, want) == 2
+        assert all(np.any(want[1][n] == 0) and np.any(want[1][n] == 1) for n in range(2))
+        assert set(np.unique(b["samples"][0]["mask"]).tolist()) == {0.0, 0.5, 1.0}
+    plain, mirrored = bc.host_result("identity_crop_only"), bc.host_result("identity_unit_scale_flipped")
+    assert np.array_equal(mirrored[0], plain[0][..., ::-1]) and np.array_equal(mirrored[1], plain[1][..., ::-1])
+    assert not np.array_equal(mirrored[1], plain[1])
+
+
+@pytest.mark.parametrize("stride", bc.STRIDES)
+def test_the_small_mask_batches_hold_ties_that_only_round_half_even_gets_right(stride):
+    b = bc.small_mask_batch(stride)
+    plan = bc.plan_of(b)
+    image, mask, small = bc.host_result(b["name"])
+    assert plan.crop_hw == bc.SMALL_CROP and b["stride"] == stride
+    assert [g["dst"] + g["src0"] for g in plan.records] == [(0, 144, 0, 192, 3, 4), (0, 144, 0, 192, 5, 7), (52, 92, 71, 121, 0, 0)]
+    assert np.array_equal(mask[0], bc.band_mask(stride, 1).astype(np.uint8))          # the design arrives in crop coordinates
+    assert float(bc.picture(image)[2].mean()) < 0.1                      # mostly pad
+    hs, ws = 144 // stride, 192 // stride
+    assert small.shape == (3, hs, ws) and {4: 1728, 8: 432, 16: 108, 24: 48}[stride] == hs * ws
+    ties, sums = bc.tie_blocks(mask, stride)
+    inv = np.float32(1.0 / (stride * stride))
+    assert np.float32(stride * stride // 2) * inv == np.float32(0.5)     # the tie is exact in float32 at this stride
+    half_up = np.floor(sums.astype(np.float32) * inv + np.float32(0.5)).astype(np.float32)
+    print("stride %d: %d tie blocks of %d" % (stride, int(ties.sum()), ties.size))
+    assert int(ties[0].sum()) > 0 and int(ties[1].sum()) > 0
+    assert np.array_equal(half_up != small, ties) and np.all(small[ties] == 0)
+    for n in range(2):
+        assert np.any(small[n] == 0) and np.any(small[n] == 1)
+        assert not np.array_equal(small[n].reshape(ws, hs).T, small[n])  # h and w exchanged is another array
+        shifted = np.roll(mask[n], 1, axis=1)
+        assert not np.array_equal(T.mask_small_u8(shifted, stride), small[n])
+
+
+def test_the_one_pixel_sides_show_picture_and_the_single_pixel_survives():
+    b = bc.thin_batch()
+    plan, want = bc.plan_of(b), bc.host_result("thin")
+    assert [(g["src_h"], g["src_w"], g["rs_h"], g["rs_w"]) for g in plan.records] == [(1, 1, 6, 6), (1, 7, 6, 42), (7, 1, 21, 3)]
+    shown = bc.picture(want[0]).reshape(3, -1).sum(axis=1)
+    print("picture pixels:", shown.tolist())
+    assert np.all(shown > 0) and all(np.any(want[1][n] == 0) for n in range(3))
+    inside = bc.one_pixel_interior(want[0][0])
+    pixel = ((np.array(bc.ONE_PIXEL, np.float32) - 128) / 256).reshape(3, 1)
+    assert int(inside.sum()) > 0 and np.all(want[0][0][:, inside] == pixel)
+
+
+def test_the_branch_table_keeps_its_coverage():
+    area, clamped, crops, empty_y, empty_x, identity, flips, kinds, strides, outputs, ties, sides = set(), set(), set(), 0, 0, 0, set(), set(), set(), set(), 0, set()
+    names = []
+    for b in bc.all_batches():
+        names.append(b["name"])
+        plan = bc.plan_of(b)
+        strides.add(b["stride"])
+        kinds.update(b["kinds"])
+        outputs.add((plan.crop_hw[0] // b["stride"]) * (plan.crop_hw[1] // b["stride"]))
+        if b["name"].startswith("small_mask"):
+            ties += int(bc.tie_blocks(bc.host_result(b["name"])[1], b["stride"])[0].sum())
+        for g in plan.records:
+            area.add(g["area"])
+            if g["area"]:
+                clamped.add(2 * g["rs_h"] > g["src_h"] and 2 * g["rs_w"] > g["src_w"])
+            crops.add(g["should_crop"])
+            dy0, dy1, dx0, dx1 = g["dst"]
+            empty_y += g["should_crop"] and dy0 == dy1 and dx0 < dx1
+            empty_x += g["should_crop"] and dx0 == dx1 and dy0 < dy1
+            identity += not any(isinstance(t, (T.Scale, T.Rotate)) for t in b["transforms"])
+            flips.add(bool(g["flip"]))
+            sides.add(min(g["src_h"], g["src_w"]))
+    assert tuple(names) == bc.NAMES and len(set(names)) == len(names)
+    assert area == {False, True} and clamped == {False, True} and crops == {False, True} and empty_y and empty_x and identity
+    assert flips == {False, True} and kinds == {"none", "binary", "float", "segmentations"} and strides == set(bc.STRIDES)
+    assert any(n > 256 and n % 256 for n in outputs) and ties > 0 and 1 in sides
+    assert {b["route"] for b in bc.all_batches()} == {"plan", "samples", "device_augment"}

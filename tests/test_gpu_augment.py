@@ -1,6 +1,7 @@
 """GPU: the augmentation kernel (csrc/augment_kernels.hip) through Engine.augment_batch against the recorded reference runs
 (tests/golden/augment_cases.npz) and against the staged NumPy route, bit for bit — everything is integer or fixed-order
-float32, so no differing element is allowed — and val.augmented_train_step against train_step fed the host-augmented batch."""
+float32, so no differing element is allowed — and val.augmented_train_step against train_step fed the host-augmented batch.
+The second half runs the batches of augment_branch_cases.py, which reach the kernel paths that random draws never take."""
 import random
 
 import numpy as np
@@ -14,6 +15,7 @@ from lwpose_amd.models.with_mobilenet import PoseEstimationWithMobileNet
 from lwpose_amd.modules.load_state import load_state
 from lwpose_amd.runtime import Engine
 
+import augment_branch_cases as bc
 import augment_cases as ac
 
 pytestmark = pytest.mark.gpu
@@ -114,3 +116,111 @@ def test_augmented_train_step_equals_train_step_on_the_host_augmented_batch():
     assert torch.equal(flat_a, flat_b)
     start = make_net().engine
     assert not torch.equal(flat_a, start.flat_of(start.stage_params()))  # the step moved the parameters
+
+
+# ------------------------------------------------------------------------------------------ the branch cases
+# augment_branch_cases.py: the area branch, nothing to copy, the identity warp, the small mask past one workgroup at four
+# strides, one-pixel sides.  Each batch runs from host sources and from the same arrays as cuda tensors, through the entry
+# point its ``route`` names, against the staged host route (computed once per batch) and its closed form where it has one.
+def on_device(samples):
+    out = []
+    for s in samples:
+        mask = s.get("mask")
+        out.append(dict(s, image=torch.from_numpy(s["image"]).cuda(), mask=None if mask is None else torch.from_numpy(mask).cuda()))
+    return out
+
+
+def run_route(eng, b, samples):
+    if b["route"] == "samples":
+        return eng.augment_batch(samples, b["transforms"], random.Random(b["seed"]), stride=b["stride"])[:3]
+    if b["route"] == "device_augment":
+        out = T.DeviceAugment(b["transforms"], eng, stride=b["stride"], rng=random.Random(b["seed"]))(samples)
+        return out["image"], out["mask"], out["mask_small"]
+    return eng.augment_batch(bc.plan_of(b, samples), stride=b["stride"])[:3]
+
+
+def assert_batch_same(got, want):
+    assert all(int(g.shape[0]) == len(w) for g, w in zip(got, want))
+    for n in range(len(want[0])):
+        assert_same([t[n] for t in got], [w[n] for w in want])
+
+
+def both_sources(eng, b):
+    """The batch's result from host sources and from cuda sources, each already held to the host route."""
+    want = bc.host_result(b["name"])
+    results = []
+    for samples in (b["samples"], on_device(b["samples"])):
+        got = run_route(eng, b, samples)
+        assert_batch_same(got, want)
+        results.append([t.cpu().numpy() for t in got])
+    return results
+
+
+@pytest.mark.parametrize("name", bc.NAMES)
+def test_every_branch_batch_is_bit_equal_to_the_host_route_and_its_closed_form(eng, name):
+    b = bc.named(name)
+    closed = bc.closed_form(b)
+    for image, mask, small in both_sources(eng, b):
+        for n, exp in enumerate(closed):
+            if exp is None:
+                continue
+            want = (ac.network_image(exp[0]), exp[1], T.mask_small_u8(exp[1], b["stride"]))
+            for what, g, w in zip(("image", "mask", "mask_small"), (image[n], mask[n], small[n]), want):
+                assert g.dtype == w.dtype and g.shape == w.shape, what
+                assert int((g != w).sum()) == 0, "%s of sample %d against the closed form: %d elements differ" % (what, n, int((g != w).sum()))
+
+
+def test_nothing_to_copy_is_all_crop_pad_with_a_mask_of_ones(eng):
+    b = bc.nothing_batch()
+    pad = ((np.array(bc.CROP_PAD, np.float32) - 128) / 256).reshape(3, 1, 1)
+    for image, mask, small in both_sources(eng, b):
+        for n in bc.NOTHING_ALL_PAD:                   # should_crop == 0 (over a source mask of zeros), empty in y, empty in x
+            assert np.all(image[n] == pad) and np.all(mask[n] == 1) and np.all(small[n] == 1)
+        assert np.all(mask[5][:13] == 0) and np.all(mask[5][13:] == 1) and np.all(image[5][:, 13:] == pad)
+
+
+@pytest.mark.parametrize("name", ["area", "area_closed", "area_crowd_decoded"])
+def test_the_kernels_bilinear_branch_at_a_step_of_two_equals_its_area_branch(eng, name):
+    """The same plan with ``area`` cleared: for the uint8 image, a {0, 1} mask and no mask the two branches give the same bits
+    (test_augment_host.py states why); samples with fractional masks are compared with the host route only, above."""
+    b = bc.named(name)
+    want = bc.host_result(name)
+    exact = [n for n, kind in enumerate(b["kinds"]) if kind != "float"]
+    for samples in (b["samples"], on_device(b["samples"])):
+        linear = eng.augment_batch(bc.with_area(bc.plan_of(b, samples), False), stride=b["stride"])[:3]
+        for n in exact:
+            assert_same([t[n] for t in linear], [w[n] for w in want])
+        if len(exact) < len(b["kinds"]):               # the image does not depend on the mask: exact for every sample
+            assert_same(linear[:1], want[:1])
+
+
+def test_the_area_crowd_sample_equals_its_decoded_float_mask_on_the_device(eng):
+    with_segs, decoded = bc.area_crowd_batches()
+    for a, d in zip(both_sources(eng, with_segs), both_sources(eng, decoded)):
+        assert all(np.array_equal(x, y) for x, y in zip(a, d))
+        assert 0 < int((a[1][1] == 0).sum())
+
+
+def test_device_augment_at_stride_four_runs_seven_workgroups_a_sample(eng):
+    b = bc.small_mask_batch(4)
+    out = T.DeviceAugment(b["transforms"], eng, stride=4, rng=random.Random(b["seed"]))(on_device(b["samples"]))
+    assert tuple(out["mask_small"].shape) == (3, 36, 48)              # 1728 outputs: six workgroups of 256 and one of 192
+    assert_batch_same((out["image"], out["mask"], out["mask_small"]), bc.host_result(b["name"]))
+
+
+def test_the_small_mask_refuses_a_crop_that_is_not_whole_blocks(eng):
+    b = bc.small_mask_batch(8)
+    plan = bc.plan_of(b)
+    for stride in (5, 10):                             # 144 = 28 * 5 + 4; 192 = 19 * 10 + 2
+        with pytest.raises(ValueError, match="not a whole number of"):
+            eng.augment_batch(plan, stride=stride)
+    assert_batch_same(eng.augment_batch(plan, stride=8)[:3], bc.host_result(b["name"]))    # and the engine is still usable
+
+
+def test_the_single_pixel_survives_on_the_device(eng):
+    b = bc.thin_batch()
+    pixel = ((np.array(bc.ONE_PIXEL, np.float32) - 128) / 256).reshape(3, 1)
+    for image, mask, small in both_sources(eng, b):
+        inside = bc.one_pixel_interior(image[0])
+        assert int(inside.sum()) > 0 and np.all(image[0][:, inside] == pixel)
+        assert np.all(bc.picture(image).reshape(3, -1).sum(axis=1) > 0)
