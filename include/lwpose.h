@@ -38,7 +38,8 @@ enum {
     LWP_ERR_STATE = -3,     /* call order (e.g. forward before load_weights)       */
     LWP_ERR_CAPACITY = -4,  /* a peak / key-point / connection list overflowed its configured capacity */
     LWP_ERR_NOGPU = -5,     /* no usable HIP device                                */
-    LWP_ERR_UNBOUND = -6    /* the reference would raise UnboundLocalError here (keypoints.py:116,137) */
+    LWP_ERR_UNBOUND = -6,   /* the reference would raise UnboundLocalError here (keypoints.py:116,137) */
+    LWP_ERR_INTERNAL = -7   /* two parts of the library that must agree do not (the message names both verdicts) */
 };
 
 enum { LWP_MEM_HOST = 0, LWP_MEM_DEVICE = 1 };
@@ -681,7 +682,7 @@ int lwp_augment_batch_crowd(lwp_handle h, const lwp_augment_plan* plans, int N, 
  *      warns and carries on in several of these cases; this library refuses them.
  *      lwp_jpeg_header: blocks_w / blocks_h are each component's block-padded grid (mcus_x * h_samp by mcus_y * v_samp 8x8
  *      blocks); a single-component file reports sampling 1x1 whatever its frame header states.
- *      COEFFICIENT LAYOUT (lwp_debug_jpeg_blocks; what a device entropy decoder would fill): int16, 64 per block in natural
+ *      COEFFICIENT LAYOUT (lwp_debug_jpeg_blocks; what the device entropy decoder below fills too): int16, 64 per block in natural
  *      (de-zig-zagged, row-major) order, DC prediction undone, not dequantised; blocks in plane order, component by component,
  *      each component's blocks row-major over its block-padded grid; qtables: 4 slots of 64 uint16 in natural order, component
  *      c using slot quant_table[c]. */
@@ -714,6 +715,45 @@ int lwp_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data,
  * stage between HIP events.  ms_total[2] out: stage A, stage B. */
 int lwp_time_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out,
                                int iters, float* ms_total);
+
+/* ---- JPEG files, entropy decode on the device (csrc/jpeg_entropy_kernels.hip).  An opt-in mode of
+ *      lwp_jpeg_decode_batch / lwp_time_jpeg_decode_batch: the default stays the host decode, and the pixels, the refusals and
+ *      their messages are the same in both modes.  In device mode the host only parses the headers and walks each scan once
+ *      (csrc/jpeg_host.cpp's jpeg_scan_segments: FF 00 un-stuffed into the pinned staging, the scan cut at the RSTn markers, RST
+ *      numbering / count and the trailer checked, the Huffman tables flattened); the call then issues ONE upload [un-stuffed
+ *      scans | Huffman tables | quantisation tables | records], zero-fills the coefficients and runs self-synchronising
+ *      parallel Huffman decoding (one lane a subsequence of subseq_bytes of one restart interval; decoder state = bit position,
+ *      block in MCU, coefficient index; sync inside a workgroup, then across workgroups, both with round caps that make the
+ *      result exact for any stream; write pass; DC scan in stream order), which fills exactly the COEFFICIENT LAYOUT above.
+ *      The N status words are copied back and the call WAITS for them (the one host wait host mode does not have) before
+ *      stage A is enqueued, so a refused file still fails the whole call with its index (the lowest) and nothing is written.
+ *      The message of a refusal is the host decoder's, which is run on the refused file; a file the device refuses and the
+ *      host accepts is LWP_ERR_INTERNAL naming the file and both verdicts.  A scan of 2^28 or more un-stuffed bytes is
+ *      LWP_ERR_CAPACITY in device mode.  Staging event, lwp_set_stream ordering, lwp_debug_live_resources and lwp_destroy as
+ *      for host mode. */
+enum { LWP_JPEG_ENTROPY_HOST = 0, LWP_JPEG_ENTROPY_DEVICE = 1 };
+/* subseq_bytes: 0 (the default, 128) or a multiple of 4 from 4 to 1024; 32 bits hold the longest symbol (16 code bits and 11
+ * magnitude bits).  LWP_ERR_ARG for any other value or mode. */
+int lwp_set_jpeg_entropy(lwp_handle h, int mode, int subseq_bytes);
+/* the pre-pass and the entropy kernels alone, for tests: status_out[i] 0 accepted, non-zero refused (by the header, the
+ * pre-pass or the kernels) without failing the call; an accepted file's coefficients (64 * total_blocks int16) go to the HOST
+ * buffer coef_out[i] and its tables to qtables_out[i][256].  subseq_bytes 0: the handle's setting. */
+int lwp_debug_jpeg_entropy_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, int subseq_bytes,
+                                 int16_t* const* coef_out, uint16_t* const* qtables_out, int* status_out);
+/* the pre-pass alone.  No handle, no GPU.  bytes_out (bytes_cap available; len suffices): the un-stuffed scan; segs_out
+ * (segs_cap segments available): four uint32 a segment (un-stuffed byte offset, byte length, first MCU, MCU count); tables_out
+ * (may be NULL): 6 * 1488 bytes, the DC tables of components 0..2 and then their AC tables as the kernels read them (512 uint16
+ * of 9-bit look-up, 17 int32 each of maxcode / mincode / valptr, 256 symbols, 4 bytes of padding); qtables_out (may be NULL):
+ * 256 uint16.  *status_out: 0 accepted so far, 1 refused, 2 the scan is too long for device mode.  LWP_ERR_ARG if the header
+ * itself is refused. */
+int lwp_debug_jpeg_scan(const unsigned char* data, size_t len, unsigned char* bytes_out, size_t bytes_cap, size_t* n_bytes,
+                        uint32_t* segs_out, size_t segs_cap, size_t* n_segs, unsigned char* tables_out, uint16_t* qtables_out,
+                        int* status_out);
+/* the entropy kernels alone (tools/jpeg_entropy_bench.py): the checks, pre-pass and upload of device mode, then `iters`
+ * back-to-back runs of the memset and the four kernels between HIP events.  rounds[2] out: the most sync rounds a workgroup
+ * took, and the most rounds across workgroups. */
+int lwp_time_jpeg_entropy_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, int subseq_bytes,
+                                int iters, float* ms_total, int* rounds);
 
 /* ---- COCO key-point evaluation: replaces pycocotools' COCOeval(gt, dt, 'keypoints') evaluate() + accumulate() behind
  *      val.py:17-27, with COCOeval's default parameters (the 17 OKS sigmas, IoU thresholds 0.5:0.05:0.95, 101 recall

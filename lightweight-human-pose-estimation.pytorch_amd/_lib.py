@@ -6,8 +6,10 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "liblwpose_hip.so")
 
-LWP_OK, LWP_ERR_ARG, LWP_ERR_HIP, LWP_ERR_STATE, LWP_ERR_CAPACITY, LWP_ERR_NOGPU, LWP_ERR_UNBOUND = 0, -1, -2, -3, -4, -5, -6
+LWP_OK, LWP_ERR_ARG, LWP_ERR_HIP, LWP_ERR_STATE, LWP_ERR_CAPACITY, LWP_ERR_NOGPU, LWP_ERR_UNBOUND, LWP_ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7
 MEM_HOST, MEM_DEVICE = 0, 1
+JPEG_ENTROPY_HOST, JPEG_ENTROPY_DEVICE = 0, 1
+JPEG_ENTROPY_MODES = {"host": JPEG_ENTROPY_HOST, "device": JPEG_ENTROPY_DEVICE}
 F32, BF16, F16 = 0, 1, 2
 TRAIN_STAGES, TRAIN_CPM, TRAIN_ALL = 0, 1, 2
 TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM, "all": TRAIN_ALL}
@@ -43,6 +45,7 @@ EXPORTS = [
     "lwp_coco_open", "lwp_coco_release", "lwp_coco_reset", "lwp_coco_add_maps", "lwp_coco_add_rows", "lwp_coco_counts",
     "lwp_coco_rows", "lwp_coco_finish", "lwp_debug_coco_rows",
     "lwp_jpeg_info", "lwp_debug_jpeg_blocks", "lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch",
+    "lwp_set_jpeg_entropy", "lwp_debug_jpeg_entropy_batch", "lwp_debug_jpeg_scan", "lwp_time_jpeg_entropy_batch",
 ]
 
 
@@ -197,6 +200,10 @@ def lib():
     L.lwp_debug_jpeg_blocks.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
     L.lwp_jpeg_decode_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
     L.lwp_time_jpeg_decode_batch.argtypes = L.lwp_jpeg_decode_batch.argtypes + [C.c_int, fp]
+    L.lwp_set_jpeg_entropy.argtypes = [vp, C.c_int, C.c_int]
+    L.lwp_debug_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(vp), C.POINTER(vp), ip]
+    L.lwp_debug_jpeg_scan.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, ip]
+    L.lwp_time_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_int, fp, ip]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -148,6 +148,7 @@ struct lwp_context {
     // the pinned staging of the upload and the event behind its last copy (the staging is not rewritten before it)
     DevBuf d_jpeg;
     PinBuf jpeg_stage; Event jpeg_ev; bool jpeg_copy_pending = false;
+    int jpeg_entropy_mode = LWP_JPEG_ENTROPY_HOST, jpeg_subseq = kJpegSubseqDefault;     // lwp_set_jpeg_entropy
     bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
@@ -2484,6 +2485,39 @@ extern "C" int lwp_debug_jpeg_blocks(const unsigned char* data, size_t len, int1
     return LWP_OK;
 }
 
+// the plane and image records of a batch whose headers are hd (a file of no components takes none); plane_base: where the
+// component planes start in the workspace
+static void jpeg_fill_records(const std::vector<lwp_jpeg_header>& hd, int N, unsigned char* const* out, size_t plane_base, JpegPlane* planes,
+                              unsigned* pstart, JpegImage* images, unsigned* istart, uint64_t* blocks, uint64_t* units) {
+    uint64_t b0 = 0, u0 = 0;
+    int p = 0;
+    for (int i = 0; i < N; ++i) {
+        const lwp_jpeg_header& f = hd[i];
+        JpegImage& im = images[i];
+        memset(&im, 0, sizeof im);
+        im.unit0 = (unsigned)u0; istart[i] = (unsigned)u0;
+        im.width = f.width; im.height = f.height;
+        im.mode = f.components == 1 ? 0 : f.h_samp[0] == 1 ? 1 : f.v_samp[0] == 1 ? 2 : 3;
+        im.chroma_w = f.components == 1 ? 0 : (f.width + f.h_samp[0] - 1) / f.h_samp[0];
+        im.chroma_h = f.components == 1 ? 0 : (f.height + f.v_samp[0] - 1) / f.v_samp[0];
+        im.out = out ? out[i] : nullptr;
+        for (int c = 0; c < f.components; ++c) {
+            JpegPlane& pl = planes[p];
+            pl.block0 = (unsigned)b0; pstart[p] = (unsigned)b0;
+            pl.blocks_w = f.blocks_w[c];
+            pl.qt = (unsigned)(((size_t)i * kJpegQuantSlots + (size_t)f.quant_table[c]) * 64);
+            pl.pad_ = 0;
+            pl.plane = (long long)(plane_base + b0 * 64);
+            im.plane[c] = pl.plane; im.stride[c] = f.blocks_w[c] * 8;
+            b0 += (uint64_t)f.blocks_w[c] * f.blocks_h[c];
+            ++p;
+        }
+        u0 += (uint64_t)f.height * (uint64_t)((f.width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
+    }
+    pstart[p] = (unsigned)b0; istart[N] = (unsigned)u0;
+    *blocks = b0; *units = u0;
+}
+
 // checks, the host half of every file and the batch's one upload [coefficients | tables | plane records | plane starts | image
 // records | image starts]; the component planes lie behind it in the same allocation.  Nothing is enqueued before every file
 // has been decoded: a refusal leaves the outputs untouched.
@@ -2561,31 +2595,7 @@ static int jpeg_prepare(lwp_handle h, int N, const unsigned char* const* data, c
             return fail(h, LWP_ERR_ARG, msg);
         }
     uint64_t b0 = 0, u0 = 0;
-    int p = 0;
-    for (int i = 0; i < N; ++i) {
-        const lwp_jpeg_header& f = hd[i];
-        JpegImage& im = images[i];
-        memset(&im, 0, sizeof im);
-        im.unit0 = (unsigned)u0; istart[i] = (unsigned)u0;
-        im.width = f.width; im.height = f.height;
-        im.mode = f.components == 1 ? 0 : f.h_samp[0] == 1 ? 1 : f.v_samp[0] == 1 ? 2 : 3;
-        im.chroma_w = f.components == 1 ? 0 : (f.width + f.h_samp[0] - 1) / f.h_samp[0];
-        im.chroma_h = f.components == 1 ? 0 : (f.height + f.v_samp[0] - 1) / f.v_samp[0];
-        im.out = out[i];
-        for (int c = 0; c < f.components; ++c) {
-            JpegPlane& pl = planes[p];
-            pl.block0 = (unsigned)b0; pstart[p] = (unsigned)b0;
-            pl.blocks_w = f.blocks_w[c];
-            pl.qt = (unsigned)(((size_t)i * kJpegQuantSlots + (size_t)f.quant_table[c]) * 64);
-            pl.pad_ = 0;
-            pl.plane = (long long)(upload + b0 * 64);
-            im.plane[c] = pl.plane; im.stride[c] = f.blocks_w[c] * 8;
-            b0 += (uint64_t)f.blocks_w[c] * f.blocks_h[c];
-            ++p;
-        }
-        u0 += (uint64_t)f.height * (uint64_t)((f.width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
-    }
-    pstart[n_planes] = (unsigned)b0; istart[N] = (unsigned)u0;
+    jpeg_fill_records(hd, N, out, upload, planes, pstart, images, istart, &b0, &u0);
     int rc = order_in(h);
     if (rc) return rc;
     if (h->d_jpeg.size() < total) {
@@ -2608,9 +2618,316 @@ static int jpeg_prepare(lwp_handle h, int N, const unsigned char* const* data, c
     return LWP_OK;
 }
 
+// ---- device entropy mode (lwp_set_jpeg_entropy; jpeg_entropy_kernels.hip)
+static bool jpeg_subseq_ok(int v) { return v >= 4 && v <= 1024 && v % 4 == 0; }
+
+extern "C" int lwp_set_jpeg_entropy(lwp_handle h, int mode, int subseq_bytes) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (mode != LWP_JPEG_ENTROPY_HOST && mode != LWP_JPEG_ENTROPY_DEVICE) return fail(h, LWP_ERR_ARG, "mode must be LWP_JPEG_ENTROPY_HOST or LWP_JPEG_ENTROPY_DEVICE");
+    if (subseq_bytes != 0 && !jpeg_subseq_ok(subseq_bytes)) return fail(h, LWP_ERR_ARG, "subseq_bytes must be 0 (the default) or a multiple of 4 from 4 to 1024");
+    h->jpeg_entropy_mode = mode;
+    h->jpeg_subseq = subseq_bytes ? subseq_bytes : kJpegSubseqDefault;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_jpeg_scan(const unsigned char* data, size_t len, unsigned char* bytes_out, size_t bytes_cap, size_t* n_bytes,
+                                   uint32_t* segs_out, size_t segs_cap, size_t* n_segs, unsigned char* tables_out, uint16_t* qtables_out,
+                                   int* status_out) {
+    if (!data || !bytes_out || !n_bytes || !segs_out || !n_segs || !status_out) return fail(nullptr, LWP_ERR_ARG, "data / bytes_out / n_bytes / segs_out / n_segs / status_out is null");
+    char msg[256] = {0};
+    lwp_jpeg_header hd;
+    if (jpeg_parse_header(data, len, &hd, msg, sizeof msg) != JPEG_OK) return fail(nullptr, LWP_ERR_ARG, msg);
+    if (jpeg_expected_segments(hd) > segs_cap) return fail(nullptr, LWP_ERR_CAPACITY, "jpeg: segs_cap is below the segments the header promises");
+    std::vector<JpegHuffFlat> tables(kJpegHuffPerFile);
+    uint16_t qt[kJpegQuantSlots * 64];
+    static_assert(sizeof(JpegScanSeg) == 4 * sizeof(uint32_t), "segs_out is four uint32 a segment");
+    *status_out = jpeg_scan_segments(data, len, &hd, bytes_out, bytes_cap, n_bytes, reinterpret_cast<JpegScanSeg*>(segs_out), segs_cap, n_segs,
+                                     tables.data(), qt);
+    if (tables_out) memcpy(tables_out, tables.data(), kJpegHuffPerFile * sizeof(JpegHuffFlat));
+    if (qtables_out) memcpy(qtables_out, qt, sizeof qt);
+    return LWP_OK;
+}
+
+// files shared among up to kJpegHostThreads threads, as the host entropy decode shares them
+template <class F>
+static void jpeg_share_files(int N, size_t in_bytes, F per_file) {
+    int T = std::min({kJpegHostThreads, N, (int)std::max(1u, std::thread::hardware_concurrency())});
+    if (in_bytes < kJpegThreadedFromBytes) T = 1;
+    std::vector<std::thread> pool;
+    int started = 1;                                   // this thread is the first
+    try {
+        for (; started < T; ++started) pool.emplace_back([&, t = started]() { for (int i = t; i < N; i += T) per_file(i); });
+    } catch (const std::system_error&) {}              // no more threads to be had: this one takes the rest below
+    for (int i = 0; i < N; i += T) per_file(i);
+    for (std::thread& th : pool) th.join();
+    for (int t = started; t < T; ++t)
+        for (int i = t; i < N; i += T) per_file(i);
+}
+
+// the call's error for file i, which the pre-pass (by_kernels false) or the kernels refused: the host decoder's message, so
+// both modes word a refusal alike; a file the host accepts is an internal error, never a silent repair
+static int jpeg_device_refusal(lwp_handle h, int i, const unsigned char* data, size_t len, const lwp_jpeg_header& hd, int verdict, bool by_kernels) {
+    char msg[400], why[256] = {0};
+    if (verdict == JPEG_CAPACITY) {
+        snprintf(msg, sizeof msg, "image %d: jpeg: the scan's un-stuffed length is 2^28 bytes or more, which the device entropy mode does not take: decode it in host mode", i);
+        return fail(h, LWP_ERR_CAPACITY, msg);
+    }
+    std::vector<int16_t> coef((size_t)hd.total_blocks * 64);
+    uint16_t qt[kJpegQuantSlots * 64];
+    lwp_jpeg_header now;
+    if (jpeg_decode_blocks(data, len, &now, coef.data(), coef.size(), qt, why, sizeof why) != JPEG_OK) {
+        snprintf(msg, sizeof msg, "image %d: %s", i, why);
+        return fail(h, LWP_ERR_ARG, msg);
+    }
+    snprintf(msg, sizeof msg, "image %d: the device entropy decoder's %s refused a file that the host decoder accepts", i, by_kernels ? "kernels" : "pre-pass");
+    return fail(h, LWP_ERR_INTERNAL, msg);
+}
+
+struct JpegDeviceBatch {
+    std::vector<lwp_jpeg_header> hd;
+    std::vector<int> verdict;                          // per file: JPEG_OK, or why it takes no part (tolerant calls only)
+    JpegLaunch j{};
+    JpegEntropyLaunch e{};
+    const uint16_t* qt_host = nullptr;                 // the quantisation tables in the staging
+    int* status_host = nullptr;                        // [N + 2] in the staging, filled by jpeg_device_entropy
+    size_t memset_bytes = 0;                           // coefficients and status words, from e.coef on
+};
+
+// Device mode's front half: headers, the pre-pass on the host threads, the one upload [un-stuffed scans | Huffman tables |
+// quantisation tables | records].  `tolerant` (lwp_debug_jpeg_entropy_batch): a refused file takes no part instead of failing
+// the call.  Device layout behind the upload: [coefficients | status][subsequence records][positions][workgroup entries][planes].
+static int jpeg_device_prepare(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out,
+                               int subseq, bool tolerant, JpegDeviceBatch* B) {
+    char msg[400], why[256];
+    if (!data || !len) return fail(h, LWP_ERR_ARG, "data / len is null");        // out: null where the call writes no pixels
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    std::vector<lwp_jpeg_header>& hd = B->hd;
+    hd.assign((size_t)N, lwp_jpeg_header{});
+    B->verdict.assign((size_t)N, JPEG_OK);
+    uint64_t blocks = 0, units = 0, n_segs_cap = 0, byte_cap = 0;
+    int n_planes = 0;
+    size_t in_bytes = 0;
+    std::vector<uint64_t> seg_at((size_t)N + 1, 0), byte_at((size_t)N + 1, 0);
+    for (int i = 0; i < N; ++i) {
+        if (!data[i] || (out && !out[i])) { snprintf(msg, sizeof msg, "image %d: data / out is null", i); return fail(h, LWP_ERR_ARG, msg); }
+        why[0] = 0;
+        if (jpeg_parse_header(data[i], len[i], &hd[i], why, sizeof why) != JPEG_OK) {
+            if (!tolerant) { snprintf(msg, sizeof msg, "image %d: %s", i, why); return fail(h, LWP_ERR_ARG, msg); }
+            hd[i] = lwp_jpeg_header{};
+            hd[i].h_samp[0] = hd[i].v_samp[0] = 1;
+            B->verdict[i] = JPEG_REFUSED;
+        }
+        blocks += (uint64_t)hd[i].total_blocks;
+        units += (uint64_t)hd[i].height * (uint64_t)((hd[i].width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
+        n_planes += hd[i].components;
+        seg_at[i + 1] = seg_at[i] + (B->verdict[i] ? 0 : (uint64_t)jpeg_expected_segments(hd[i]));
+        byte_at[i + 1] = byte_at[i] + (B->verdict[i] ? 0 : (((uint64_t)len[i] + 3) & ~(uint64_t)3) + 8);
+        in_bytes += len[i];
+    }
+    n_segs_cap = seg_at[N]; byte_cap = byte_at[N];
+    if (blocks > 0x7fffffffu || units > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^31 or more blocks or pixel groups: decode it in parts");
+    if (byte_cap > 0xfffffff0u || n_segs_cap > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^32 or more bytes or 2^31 or more restart intervals: decode it in parts");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_bytes = 0, o_tab = align16((size_t)byte_cap + 8), o_qt = o_tab + (size_t)N * kJpegHuffPerFile * sizeof(JpegHuffFlat);
+    const size_t o_files = o_qt + (size_t)N * kJpegQuantSlots * 128, o_fwg = align16(o_files + (size_t)N * sizeof(JpegEntFile));
+    const size_t o_segs = align16(o_fwg + ((size_t)N + 1) * 4), o_ssub = align16(o_segs + (size_t)n_segs_cap * sizeof(JpegEntSeg));
+    const size_t o_planes = align16(o_ssub + ((size_t)n_segs_cap + 1) * 4);
+    const size_t o_pstart = align16(o_planes + (size_t)n_planes * sizeof(JpegPlane)), o_images = align16(o_pstart + ((size_t)n_planes + 1) * 4);
+    const size_t o_istart = align16(o_images + (size_t)N * sizeof(JpegImage));
+    const size_t upload = (o_istart + ((size_t)N + 1) * 4 + 255) & ~(size_t)255;
+    const size_t stage_bytes = upload + align16(((size_t)N + 2) * 4);     // the status words come back behind the upload
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->jpeg_copy_pending) {                        // the copy of the call before may still read the staging
+        HIP_TRY(h, hipEventSynchronize(h->jpeg_ev));
+        h->jpeg_copy_pending = false;
+    }
+    HIP_TRY(h, h->jpeg_stage.ensure(stage_bytes));
+    unsigned char* host = h->jpeg_stage.as<unsigned char>();
+    JpegHuffFlat* tables = reinterpret_cast<JpegHuffFlat*>(host + o_tab);
+    uint16_t* qt = reinterpret_cast<uint16_t*>(host + o_qt);
+    std::vector<JpegScanSeg> scan((size_t)n_segs_cap + 1);
+    std::vector<size_t> n_scan((size_t)N, 0);
+    jpeg_share_files(N, in_bytes, [&](int i) {
+        if (B->verdict[i]) {
+            memset(tables + (size_t)i * kJpegHuffPerFile, 0, kJpegHuffPerFile * sizeof(JpegHuffFlat));
+            memset(qt + (size_t)i * kJpegQuantSlots * 64, 0, kJpegQuantSlots * 128);
+            return;
+        }
+        size_t nb = 0;
+        B->verdict[i] = jpeg_scan_segments(data[i], len[i], &hd[i], host + o_bytes + byte_at[i], (size_t)(byte_at[i + 1] - byte_at[i]), &nb,
+                                           scan.data() + seg_at[i], (size_t)(seg_at[i + 1] - seg_at[i]), &n_scan[i],
+                                           tables + (size_t)i * kJpegHuffPerFile, qt + (size_t)i * kJpegQuantSlots * 64);
+    });
+    memset(host + o_bytes + byte_cap, 0, o_tab - byte_cap);
+    if (!tolerant)
+        for (int i = 0; i < N; ++i)
+            if (B->verdict[i]) {
+                // the call names the LOWEST refused file, and a file in front of this one may be one the kernels would refuse:
+                // nothing has been enqueued yet, so the host decoder gives their verdicts (this path is a failing call's only)
+                for (int j = 0; j < i; ++j) {
+                    std::vector<int16_t> coef((size_t)hd[j].total_blocks * 64);
+                    uint16_t q[kJpegQuantSlots * 64];
+                    lwp_jpeg_header now;
+                    why[0] = 0;
+                    if (jpeg_decode_blocks(data[j], len[j], &now, coef.data(), coef.size(), q, why, sizeof why) != JPEG_OK) {
+                        snprintf(msg, sizeof msg, "image %d: %s", j, why);
+                        return fail(h, LWP_ERR_ARG, msg);
+                    }
+                }
+                return jpeg_device_refusal(h, i, data[i], len[i], hd[i], B->verdict[i], false);
+            }
+    // the records: files, segments (of the files that take part), their first subsequences and workgroups
+    JpegEntFile* files = reinterpret_cast<JpegEntFile*>(host + o_files);
+    unsigned* fwg = reinterpret_cast<unsigned*>(host + o_fwg);
+    JpegEntSeg* segs = reinterpret_cast<JpegEntSeg*>(host + o_segs);
+    unsigned* ssub = reinterpret_cast<unsigned*>(host + o_ssub);
+    uint64_t n_subs = 0, n_wgs = 0, b0 = 0;
+    size_t n_segs = 0;
+    for (int i = 0; i < N; ++i) {
+        const lwp_jpeg_header& f = hd[i];
+        JpegEntFile& ef = files[i];
+        memset(&ef, 0, sizeof ef);
+        fwg[i] = (unsigned)n_wgs;
+        ef.seg0 = (unsigned)n_segs; ef.sub0 = (unsigned)n_subs; ef.wg0 = (unsigned)n_wgs;
+        ef.block0 = (unsigned)b0; ef.total_blocks = (unsigned)f.total_blocks;
+        ef.components = f.components; ef.mcus_x = std::max(f.mcus_x, 1);
+        ef.h0 = std::max(f.h_samp[0], 1); ef.v0 = std::max(f.v_samp[0], 1);
+        ef.blocks_per_mcu = f.components == 3 ? ef.h0 * ef.v0 + 2 : 1;
+        unsigned pb = 0;
+        for (int c = 0; c < f.components; ++c) { ef.plane_block[c] = pb; ef.blocks_w[c] = f.blocks_w[c]; pb += (unsigned)(f.blocks_w[c] * f.blocks_h[c]); }
+        b0 += (uint64_t)f.total_blocks;
+        if (B->verdict[i]) continue;
+        for (size_t k = 0; k < n_scan[i]; ++k) {
+            const JpegScanSeg& sc = scan[seg_at[i] + k];
+            JpegEntSeg& sg = segs[n_segs];
+            sg.byte0 = (unsigned)(byte_at[i] + sc.byte0); sg.n_bytes = sc.n_bytes;
+            sg.first_block = sc.first_mcu * (unsigned)ef.blocks_per_mcu; sg.n_blocks = sc.n_mcus * (unsigned)ef.blocks_per_mcu;
+            sg.sub0 = (unsigned)n_subs; sg.file = (unsigned)i;
+            ssub[n_segs++] = (unsigned)n_subs;
+            n_subs += std::max<uint64_t>(1, ((uint64_t)sc.n_bytes + (uint64_t)subseq - 1) / (uint64_t)subseq);
+            if (n_subs > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^31 or more subsequences: decode it in parts or with larger subsequences");
+        }
+        ef.n_segs = (unsigned)(n_segs - ef.seg0); ef.n_subs = (unsigned)(n_subs - ef.sub0);
+        ef.n_wgs = (ef.n_subs + kJpegEntropyGroup - 1) / kJpegEntropyGroup;
+        n_wgs += ef.n_wgs;
+    }
+    fwg[N] = (unsigned)n_wgs; ssub[n_segs] = (unsigned)n_subs;
+    auto align256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t d_coef = upload, coef_status = align256((size_t)blocks * 128 + ((size_t)N + 2) * 4);
+    const size_t d_rec = d_coef + coef_status, d_subpos = d_rec + align256((size_t)n_subs * 8), d_wge = d_subpos + align256((size_t)n_subs * 4);
+    const size_t d_wgd = d_wge + align256((size_t)n_wgs * 8), d_planes = d_wgd + align256((size_t)n_wgs * 4);
+    const size_t total = d_planes + (size_t)blocks * 64;
+    uint64_t fb = 0, fu = 0;
+    jpeg_fill_records(hd, N, out, d_planes, reinterpret_cast<JpegPlane*>(host + o_planes), reinterpret_cast<unsigned*>(host + o_pstart),
+                      reinterpret_cast<JpegImage*>(host + o_images), reinterpret_cast<unsigned*>(host + o_istart), &fb, &fu);
+    int rc = order_in(h);
+    if (rc) return rc;
+    if (h->d_jpeg.size() < total) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        HIP_TRY(h, h->d_jpeg.ensure(total));
+    }
+    unsigned char* dev = h->d_jpeg.as<unsigned char>();
+    HIP_TRY(h, h->jpeg_ev.ensure(hipEventDisableTiming));
+    HIP_TRY(h, hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->jpeg_ev, h->stream));
+    h->jpeg_copy_pending = true;
+    JpegLaunch& j = B->j;
+    j.coef = reinterpret_cast<const int16_t*>(dev + d_coef); j.qtables = reinterpret_cast<const uint16_t*>(dev + o_qt);
+    j.planes = reinterpret_cast<const JpegPlane*>(dev + o_planes); j.plane_block0 = reinterpret_cast<const unsigned*>(dev + o_pstart);
+    j.images = reinterpret_cast<const JpegImage*>(dev + o_images); j.image_unit0 = reinterpret_cast<const unsigned*>(dev + o_istart);
+    j.workspace = dev;
+    j.n_planes = n_planes; j.n_images = N;
+    j.total_blocks = (unsigned)fb; j.total_units = (unsigned)fu;
+    JpegEntropyLaunch& e = B->e;
+    e.words = reinterpret_cast<const unsigned*>(dev + o_bytes); e.n_words = (unsigned)(o_tab / 4);
+    e.tables = reinterpret_cast<const JpegHuffFlat*>(dev + o_tab);
+    e.files = reinterpret_cast<const JpegEntFile*>(dev + o_files); e.file_wg0 = reinterpret_cast<const unsigned*>(dev + o_fwg);
+    e.segs = reinterpret_cast<const JpegEntSeg*>(dev + o_segs); e.seg_sub0 = reinterpret_cast<const unsigned*>(dev + o_ssub);
+    e.rec = reinterpret_cast<uint2*>(dev + d_rec); e.subpos = reinterpret_cast<unsigned*>(dev + d_subpos);
+    e.wg_entry = reinterpret_cast<uint2*>(dev + d_wge); e.wg_dirty = reinterpret_cast<unsigned*>(dev + d_wgd);
+    e.coef = reinterpret_cast<int16_t*>(dev + d_coef); e.status = reinterpret_cast<int*>(dev + d_coef + (size_t)blocks * 128);
+    e.n_files = N; e.n_segs = (unsigned)n_segs; e.n_subs = (unsigned)n_subs; e.n_wgs = (unsigned)n_wgs;
+    e.subseq_bytes = subseq;
+    B->qt_host = qt;
+    B->status_host = reinterpret_cast<int*>(host + upload);
+    B->memset_bytes = (size_t)blocks * 128 + ((size_t)N + 2) * 4;
+    return LWP_OK;
+}
+
+// the memset, the four entropy kernels, the status words back to the host, and the wait for them
+static int jpeg_device_entropy(lwp_handle h, JpegDeviceBatch& B) {
+    HIP_TRY(h, hipMemsetAsync(B.e.coef, 0, B.memset_bytes, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_entropy(B.e, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(B.status_host, B.e.status, ((size_t)B.e.n_files + 2) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+// device mode up to the coefficients: fails the call for the lowest refused file before stage A is enqueued
+static int jpeg_prepare_device(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out, JpegLaunch* launch) {
+    if (!data || !len || !out) return fail(h, LWP_ERR_ARG, "data / len / out is null");
+    JpegDeviceBatch B;
+    int rc = jpeg_device_prepare(h, N, data, len, out, h->jpeg_subseq, false, &B);
+    if (rc) return rc;
+    rc = jpeg_device_entropy(h, B);
+    if (rc) return rc;
+    for (int i = 0; i < N; ++i)
+        if (B.status_host[i]) return jpeg_device_refusal(h, i, data[i], len[i], B.hd[i], JPEG_REFUSED, true);
+    *launch = B.j;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_jpeg_entropy_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, int subseq_bytes,
+                                            int16_t* const* coef_out, uint16_t* const* qtables_out, int* status_out) {
+    if (!coef_out || !qtables_out || !status_out) return fail(h, LWP_ERR_ARG, "coef_out / qtables_out / status_out is null");
+    if (subseq_bytes != 0 && !jpeg_subseq_ok(subseq_bytes)) return fail(h, LWP_ERR_ARG, "subseq_bytes must be 0 (the default) or a multiple of 4 from 4 to 1024");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    JpegDeviceBatch B;
+    int rc = jpeg_device_prepare(h, N, data, len, nullptr, subseq_bytes ? subseq_bytes : h->jpeg_subseq, true, &B);
+    if (rc) return rc;
+    rc = jpeg_device_entropy(h, B);
+    if (rc) return rc;
+    size_t b0 = 0;
+    for (int i = 0; i < N; ++i) {
+        const size_t n = (size_t)B.hd[i].total_blocks;
+        status_out[i] = B.verdict[i] ? B.verdict[i] : B.status_host[i] ? JPEG_REFUSED : JPEG_OK;
+        if (!status_out[i]) {
+            if (!coef_out[i] || !qtables_out[i]) return fail(h, LWP_ERR_ARG, "coef_out[i] / qtables_out[i] is null");
+            HIP_TRY(h, hipMemcpyAsync(coef_out[i], B.j.coef + b0 * 64, n * 128, hipMemcpyDeviceToHost, h->stream));
+            memcpy(qtables_out[i], B.qt_host + (size_t)i * kJpegQuantSlots * 64, kJpegQuantSlots * 128);
+        }
+        b0 += n;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_time_jpeg_entropy_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, int subseq_bytes,
+                                           int iters, float* ms_total, int* rounds) {
+    if (iters < 1 || !ms_total || !rounds) return fail(h, LWP_ERR_ARG, "iters must be at least 1 and ms_total / rounds non-null");
+    if (subseq_bytes != 0 && !jpeg_subseq_ok(subseq_bytes)) return fail(h, LWP_ERR_ARG, "subseq_bytes must be 0 (the default) or a multiple of 4 from 4 to 1024");
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    JpegDeviceBatch B;
+    int rc = jpeg_device_prepare(h, N, data, len, nullptr, subseq_bytes ? subseq_bytes : h->jpeg_subseq, false, &B);
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() {
+        HIP_TRY(h, hipMemsetAsync(B.e.coef, 0, B.memset_bytes, h->stream));
+        LAUNCH(h, KC_OTHER, launch_jpeg_entropy(B.e, h->stream));
+        return (int)LWP_OK;
+    }, ms_total);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(B.status_host, B.e.status, ((size_t)N + 2) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < N; ++i)
+        if (B.status_host[i]) return jpeg_device_refusal(h, i, data[i], len[i], B.hd[i], JPEG_REFUSED, true);
+    rounds[0] = B.status_host[N]; rounds[1] = B.status_host[N + 1];
+    return LWP_OK;
+}
+
 extern "C" int lwp_jpeg_decode_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out) {
     JpegLaunch j{};
-    int rc = jpeg_prepare(h, N, data, len, out, &j);
+    int rc = h && h->jpeg_entropy_mode == LWP_JPEG_ENTROPY_DEVICE ? jpeg_prepare_device(h, N, data, len, out, &j) : jpeg_prepare(h, N, data, len, out, &j);
     if (rc) return rc;
     LAUNCH(h, KC_OTHER, launch_jpeg_idct(j, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_color(j, h->stream));
@@ -2625,7 +2942,7 @@ extern "C" int lwp_time_jpeg_decode_batch(lwp_handle h, int N, const unsigned ch
                                           unsigned char* const* out, int iters, float* ms_total) {
     if (iters < 1 || !ms_total) return fail(h, LWP_ERR_ARG, "iters must be at least 1 and ms_total non-null");
     JpegLaunch j{};
-    int rc = jpeg_prepare(h, N, data, len, out, &j);
+    int rc = h && h->jpeg_entropy_mode == LWP_JPEG_ENTROPY_DEVICE ? jpeg_prepare_device(h, N, data, len, out, &j) : jpeg_prepare(h, N, data, len, out, &j);
     if (rc) return rc;
     rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_idct(j, h->stream)); return (int)LWP_OK; }, &ms_total[0]);
     if (rc) return rc;

@@ -472,4 +472,84 @@ int jpeg_decode_blocks(const unsigned char* data, size_t len, lwp_jpeg_header* o
     }
 }
 
+namespace {
+
+void flatten(const HuffTable& t, JpegHuffFlat* f) {
+    memset(f, 0, sizeof *f);
+    memcpy(f->look, t.look, sizeof f->look);
+    for (int l = 1; l <= 16; ++l) { f->maxcode[l] = t.maxcode[l]; f->mincode[l] = t.mincode[l]; f->valptr[l] = t.valptr[l]; }
+    f->maxcode[0] = -1;
+    memcpy(f->vals, t.vals, sizeof f->vals);
+}
+
+}  // namespace
+
+int jpeg_scan_segments(const unsigned char* data, size_t len, const lwp_jpeg_header* hd, unsigned char* bytes, size_t bytes_cap,
+                       size_t* n_bytes, JpegScanSeg* segs, size_t segs_cap, size_t* n_segs, JpegHuffFlat* tables, uint16_t* qtables) {
+    const Refuse quiet{nullptr, 0};
+    if (!data || !hd || !bytes || !n_bytes || !segs || !n_segs || !tables || !qtables) return JPEG_REFUSED;
+    *n_bytes = 0; *n_segs = 0;
+    Parsed P;
+    if (parse(data, len, P, quiet)) return JPEG_REFUSED;
+    const lwp_jpeg_header& h = P.hd;
+    if (h.width != hd->width || h.height != hd->height || h.components != hd->components || h.h_samp[0] != hd->h_samp[0] ||
+        h.v_samp[0] != hd->v_samp[0] || h.restart_interval != hd->restart_interval || h.total_blocks != hd->total_blocks)
+        return JPEG_REFUSED;                           // not the file the caller sized its buffers for
+    if ((uint64_t)h.total_blocks > 4 * (uint64_t)(len - P.scan_at)) return JPEG_REFUSED;
+    memcpy(qtables, P.qt, sizeof P.qt);
+    for (int c = 0; c < kJpegHuffPerFile; ++c) memset(&tables[c], 0, sizeof tables[c]);
+    for (int c = 0; c < h.components; ++c) { flatten(P.dc[P.td[c]], &tables[c]); flatten(P.ac[P.ta[c]], &tables[3 + c]); }
+    const uint64_t n_mcus = (uint64_t)h.mcus_x * (uint64_t)h.mcus_y;
+    const size_t expected = jpeg_expected_segments(h);
+    if (expected > segs_cap) return JPEG_REFUSED;
+    size_t pos = P.scan_at, out = 0, seg_out = 0, n = 0;
+    int next_rst = 0;
+    auto close_segment = [&]() {
+        JpegScanSeg& s = segs[n];
+        const uint64_t first = (uint64_t)n * (uint64_t)(h.restart_interval ? h.restart_interval : 0);
+        s.byte0 = (uint32_t)seg_out; s.n_bytes = (uint32_t)(out - seg_out);
+        s.first_mcu = (uint32_t)first;
+        s.n_mcus = (uint32_t)(h.restart_interval ? (n_mcus - first < (uint64_t)h.restart_interval ? n_mcus - first : (uint64_t)h.restart_interval) : n_mcus);
+        seg_out = out;
+        ++n;
+    };
+    for (;;) {                                         // every turn moves pos forward
+        const void* hit = pos < len ? memchr(data + pos, 0xFF, len - pos) : nullptr;
+        const size_t stop = hit ? (size_t)(static_cast<const unsigned char*>(hit) - data) : len;
+        const size_t run = stop - pos;
+        if (out + run + 1 >= kJpegDeviceScanLimit) return JPEG_CAPACITY;
+        if (out + run + 1 > bytes_cap) return JPEG_REFUSED;
+        memcpy(bytes + out, data + pos, run);
+        out += run; pos = stop;
+        if (pos + 1 >= len) return JPEG_REFUSED;       // the stream stops inside the scan or inside a marker: no EOI
+        if (data[pos + 1] == 0) { bytes[out++] = 0xFF; pos += 2; continue; }
+        size_t q = pos;                                // a marker, fill bytes in front of it allowed
+        while (q < len && data[q] == 0xFF) ++q;
+        if (q >= len) return JPEG_REFUSED;
+        const int m = data[q];
+        if (m >= 0xD0 && m <= 0xD7) {
+            if (!h.restart_interval || n + 1 >= expected || m != 0xD0 + next_rst) return JPEG_REFUSED;
+            close_segment();
+            next_rst = (next_rst + 1) & 7;
+            pos = q + 1;
+            continue;
+        }
+        close_segment();
+        if (n != expected) return JPEG_REFUSED;
+        break;
+    }
+    *n_bytes = out; *n_segs = n;
+    // behind the scan: markers up to EOI, as jpeg_decode_blocks walks them
+    for (;;) {
+        int m = 0;
+        if (pos >= len || data[pos] != 0xFF) return JPEG_REFUSED;
+        if (next_marker(data, len, pos, &m, quiet)) return JPEG_REFUSED;
+        if (m == 0xD9) return JPEG_OK;
+        if (m == 0xDA || m == 0xDC || (m >= 0xD0 && m <= 0xD7) || m == 0x00 || m == 0x01 || m == 0xD8) return JPEG_REFUSED;
+        const unsigned char* p = nullptr;
+        size_t sn = 0;
+        if (segment(data, len, pos, &p, &sn, quiet)) return JPEG_REFUSED;
+    }
+}
+
 }  // namespace lwp

@@ -451,6 +451,42 @@ struct JpegLaunch {
 };
 hipError_t launch_jpeg_idct(const JpegLaunch& j, hipStream_t s);
 hipError_t launch_jpeg_color(const JpegLaunch& j, hipStream_t s);
+// ---- JPEG entropy decode on the device (jpeg_entropy_kernels.hip): fills JpegLaunch::coef from the un-stuffed scan
+// bytes, segments and flattened tables that jpeg_scan_segments (jpeg_host.h) left.  One lane owns one subsequence of
+// subseq_bytes bytes of one segment; a workgroup takes kJpegEntropyGroup consecutive subsequences of ONE file.
+struct JpegHuffFlat;                      // jpeg_host.h
+constexpr int kJpegEntropyGroup = 256;
+constexpr int kJpegSubseqDefault = 128;   // bytes; lwp_set_jpeg_entropy's subseq_bytes 0
+struct JpegEntFile {
+    unsigned seg0, n_segs;                // its segments in the batch's segment array
+    unsigned sub0, n_subs;                // its subsequences in the batch's numbering (0: the file is skipped)
+    unsigned wg0, n_wgs;                  // its workgroups of the sync and the write pass
+    unsigned block0, total_blocks;        // its blocks in the batch's plane-ordered coefficient array
+    int components, blocks_per_mcu, mcus_x;
+    int h0, v0;                           // sampling of component 0 (the others are 1x1)
+    unsigned plane_block[3];              // first block of each plane, file-relative
+    int blocks_w[3];
+};
+struct JpegEntSeg {
+    unsigned byte0, n_bytes;              // un-stuffed bytes, byte0 from the start of the batch's byte area
+    unsigned first_block, n_blocks;       // stream index (MCU order, file-relative) of its first block; MCUs times blocks per MCU
+    unsigned sub0;                        // its first subsequence in the batch's numbering
+    unsigned file;
+};
+struct JpegEntropyLaunch {
+    const unsigned* words; unsigned n_words;          // the byte area as dwords
+    const JpegHuffFlat* tables;                       // [n_files][kJpegHuffPerFile]
+    const JpegEntFile* files; const unsigned* file_wg0;   // [n_files]; [n_files + 1] first workgroups, then the total
+    const JpegEntSeg* segs; const unsigned* seg_sub0;     // [n_segs]; [n_segs + 1] first subsequences, then the total
+    uint2* rec;                                       // [n_subs] x: exit bit position, y: block starts << 16 | block in MCU << 8 | k
+    unsigned* subpos;                                 // [n_subs] block starts in front of the subsequence, counted from the file's first
+    uint2* wg_entry; unsigned* wg_dirty;              // [n_wgs] the entry a workgroup's first lane last used; whether it changed
+    int16_t* coef;
+    int* status;                                      // [n_files] non-zero: refused; then [2] sync rounds taken (in a workgroup, across)
+    int n_files; unsigned n_segs, n_subs, n_wgs;
+    int subseq_bytes;
+};
+hipError_t launch_jpeg_entropy(const JpegEntropyLaunch& e, hipStream_t s);
 // ---- COCO key-point evaluation (eval_kernels.hip; COCOeval with iouType 'keypoints' and its default parameters): float64
 constexpr int kEvalK = 17;            // key-points of a person
 constexpr int kEvalMaxDets = 20;      // detections of an image that count (maxDets)

@@ -142,25 +142,28 @@ def _file_bytes(path_or_bytes):
         return f.read(), str(path_or_bytes)
 
 
-def imread(path_or_bytes, engine):
+def imread(path_or_bytes, engine, entropy="host"):
     """``cv2.imread(path, cv2.IMREAD_COLOR)`` for a baseline JPEG file, decoded by ``Engine.decode_jpeg_batch``: a cuda uint8
     (H, W, 3) BGR tensor.  In scope: baseline (SOF0) files, grey or YCbCr at 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan;
     progressive, arithmetic-coded, 12-bit and CMYK files, and every malformed one, are a ValueError that names the file and the
     reason.  The arithmetic is libjpeg's default integer path, pinned bit for bit against libjpeg-turbo as Pillow bundles it and
     NOT against cv2 itself.  The Exif orientation is not applied (``Engine.jpeg_info`` reports it), unlike
-    ``cv2.imread`` from OpenCV 3.1 on."""
+    ``cv2.imread`` from OpenCV 3.1 on.  ``entropy``: ``"host"`` (the default) or ``"device"``, where the Huffman data is decoded
+    (DESIGN §3p); the pixels and the refusals are the same."""
     data, name = _file_bytes(path_or_bytes)
     try:
-        return engine.decode_jpeg_batch([data])[0]
+        return engine.decode_jpeg_batch([data], entropy=entropy)[0]
     except ValueError as e:
         raise ValueError("%s: %s" % (name, re.sub(r"^image 0: ", "", str(e)))) from None
 
 
 class _JpegFolder(object):
     """What the two datasets share: the folder, the engine, and the optional ``fallback(path) -> uint8 HxWx3 BGR`` for files
-    the decoder refuses (``fallbacks`` counts its calls).  The package imports no decoder of its own accord."""
+    the decoder refuses (``fallbacks`` counts its calls).  The package imports no decoder of its own accord.  ``entropy``:
+    ``"host"`` (the default) or ``"device"``, passed to ``Engine.decode_jpeg_batch``."""
 
-    def __init__(self, images_folder, engine, fallback=None):
+    def __init__(self, images_folder, engine, fallback=None, entropy="host"):
+        self._entropy = entropy
         self._images_folder = images_folder
         self._engine = getattr(engine, "engine", engine)
         self._fallback = fallback
@@ -178,7 +181,7 @@ class _JpegFolder(object):
         todo = list(range(len(paths)))
         while todo:
             try:
-                for i, img in zip(todo, eng.decode_jpeg_batch([datas[i] for i in todo])):
+                for i, img in zip(todo, eng.decode_jpeg_batch([datas[i] for i in todo], entropy=self._entropy)):
                     images[i] = img
                 break
             except ValueError as e:                    # "image k: reason", k indexing this call's list; nothing was written
@@ -204,8 +207,8 @@ class CocoValDataset(_JpegFolder):
     and indexable, one ``{'file_name', 'img'}`` per entry of ``labels['images']`` with ``img`` a cuda uint8 (H, W, 3) BGR
     tensor.  ``labels``: the file's path or the dict."""
 
-    def __init__(self, labels, images_folder, engine, fallback=None):
-        super().__init__(images_folder, engine, fallback)
+    def __init__(self, labels, images_folder, engine, fallback=None, entropy="host"):
+        super().__init__(images_folder, engine, fallback, entropy)
         if isinstance(labels, dict):
             self._labels = labels
         else:
@@ -231,8 +234,8 @@ class CocoTrainDataset(_JpegFolder):
     and ``'segmentations'`` the label's crowd RLEs (the mask is rendered on the device).  ``labels``: the pickle's path or the
     list itself."""
 
-    def __init__(self, labels, images_folder, engine, fallback=None):
-        super().__init__(images_folder, engine, fallback)
+    def __init__(self, labels, images_folder, engine, fallback=None, entropy="host"):
+        super().__init__(images_folder, engine, fallback, entropy)
         if isinstance(labels, (list, tuple)):
             self._labels = list(labels)
         else:

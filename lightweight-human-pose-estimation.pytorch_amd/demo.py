@@ -14,9 +14,11 @@ from .modules.pose import Pose, poses_from_arrays, track_poses
 class ImageReader(object):
     """The reference's image provider (demo.py:14-30) for baseline JPEG files: iterating yields one cuda uint8 (H, W, 3) BGR
     frame per file name, read by ``datasets.coco.imread`` (a file outside its scope is a ValueError naming the file; an
-    unreadable path an OSError).  ``engine``: an ``Engine`` or a net that has one."""
+    unreadable path an OSError).  ``engine``: an ``Engine`` or a net that has one.  ``entropy``: ``"host"`` (the default) or
+    ``"device"``, as ``imread`` takes it."""
 
-    def __init__(self, file_names, engine):
+    def __init__(self, file_names, engine, entropy="host"):
+        self._entropy = entropy
         self.file_names = list(file_names)
         self.max_idx = len(self.file_names)
         self._engine = getattr(engine, "engine", engine)
@@ -29,7 +31,7 @@ class ImageReader(object):
         from .datasets.coco import imread
         if self.idx == self.max_idx:
             raise StopIteration
-        img = imread(self.file_names[self.idx], self._engine)
+        img = imread(self.file_names[self.idx], self._engine, self._entropy)
         self.idx += 1
         return img
 

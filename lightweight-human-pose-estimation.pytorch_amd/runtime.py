@@ -845,14 +845,86 @@ class Engine(object):
         check(lib().lwp_debug_jpeg_blocks(data, len(data), coef.ctypes.data, coef.size, qt.ctypes.data))
         return hd, coef, qt
 
-    def decode_jpeg_batch(self, files, time_iters=0):
+    def set_jpeg_entropy(self, mode, subseq_bytes=0):
+        """Where ``decode_jpeg_batch`` decodes the Huffman data: ``"host"`` (the default) or ``"device"`` (the same
+        pixels, refusals and messages).  ``subseq_bytes``: the bytes of a scan one lane owns, 0 (the default) or a multiple of 4
+        from 4 to 1024.  ValueError for anything else."""
+        if mode not in _lib.JPEG_ENTROPY_MODES:
+            raise ValueError("entropy mode must be 'host' or 'device', not %r" % (mode,))
+        check(lib().lwp_set_jpeg_entropy(self.h.ptr, _lib.JPEG_ENTROPY_MODES[mode], int(subseq_bytes)), self.h.ptr)
+        self._jpeg_entropy, self._jpeg_subseq = mode, int(subseq_bytes)
+
+    @staticmethod
+    def _jpeg_args(files):
+        N = len(files)
+        data = (C.c_void_p * N)(*[C.cast(C.c_char_p(f), C.c_void_p) for f in files])
+        lens = (C.c_size_t * N)(*[len(f) for f in files])
+        return data, lens
+
+    def debug_jpeg_entropy(self, files, subseq_bytes=0, time_iters=0):
+        """The device entropy decoder alone (tests): ``[(status, coef or None, qtables or None)]`` per file, status 0 for an
+        accepted file, whose coefficients and tables are laid out as ``debug_jpeg_blocks`` returns them; a refused file does not
+        fail the call.  With ``time_iters`` > 0: (milliseconds of that many back-to-back runs of the kernels, the most sync rounds
+        inside a workgroup, the most across workgroups)."""
+        files = [bytes(f) for f in files]
+        N = len(files)
+        if N == 0:
+            return []
+        data, lens = self._jpeg_args(files)
+        self._order()
+        if time_iters:
+            ms, rounds = C.c_float(), (C.c_int * 2)()
+            check(lib().lwp_time_jpeg_entropy_batch(self.h.ptr, N, data, lens, int(subseq_bytes), int(time_iters), C.byref(ms), rounds), self.h.ptr)
+            return ms.value, rounds[0], rounds[1]
+        coefs, qts = [], []
+        for f in files:
+            hd = _lib.JpegHeader()
+            blocks = 0 if lib().lwp_jpeg_info(f, len(f), C.byref(hd)) else hd.total_blocks
+            coefs.append(np.zeros((max(blocks, 1), 64), dtype=np.int16))
+            qts.append(np.zeros((4, 64), dtype=np.uint16))
+        cp = (C.c_void_p * N)(*[c.ctypes.data for c in coefs])
+        qp = (C.c_void_p * N)(*[q.ctypes.data for q in qts])
+        status = (C.c_int * N)()
+        check(lib().lwp_debug_jpeg_entropy_batch(self.h.ptr, N, data, lens, int(subseq_bytes), cp, qp, status), self.h.ptr)
+        return [(int(status[i]), None, None) if status[i] else (0, coefs[i], qts[i]) for i in range(N)]
+
+    @staticmethod
+    def debug_jpeg_scan(data):
+        """The host pre-pass of the device entropy decoder alone (tests; no GPU): a dict of ``status`` (0 accepted so far,
+        1 refused, 2 too long for device mode), ``bytes`` (the un-stuffed scan), ``segments`` (uint32 (n, 4): byte offset, byte
+        length, first MCU, MCU count), ``tables`` (the six flattened Huffman tables, uint8 (6, 1488)) and ``qtables`` (uint16
+        (4, 64)).  ValueError if the header itself is refused."""
+        data = bytes(data)
+        hd = Engine.jpeg_info(data)
+        n_mcus = hd["mcus_x"] * hd["mcus_y"]
+        cap = -(-n_mcus // hd["restart_interval"]) if hd["restart_interval"] else 1
+        out = np.zeros(len(data) + 8, dtype=np.uint8)
+        segs = np.zeros((cap, 4), dtype=np.uint32)
+        tables = np.zeros((6, 1488), dtype=np.uint8)
+        qt = np.zeros((4, 64), dtype=np.uint16)
+        nb, ns, status = C.c_size_t(), C.c_size_t(), C.c_int()
+        check(lib().lwp_debug_jpeg_scan(data, len(data), out.ctypes.data, out.size, C.byref(nb), segs.ctypes.data, cap, C.byref(ns),
+                                        tables.ctypes.data, qt.ctypes.data, C.byref(status)))
+        return {"status": status.value, "bytes": out[:nb.value].tobytes(), "segments": segs[:ns.value].copy(), "tables": tables, "qtables": qt}
+
+    def decode_jpeg_batch(self, files, time_iters=0, entropy=None):
         """``cv2.imread(.., IMREAD_COLOR)`` of a batch of baseline JPEG files (a list of ``bytes``), decoded in ONE device call:
         the Huffman data on the host, inverse DCT, up-sampling, colour conversion and the BGR store on the GPU, files of different
         sizes and samplings mixed.  Returns a list of cuda uint8 (H, W, 3) tensors, views of one allocation.  ValueError with the
         file's index for one outside the scope; nothing is written then.  The Exif orientation is not applied.  With
         ``time_iters`` > 0 each of the two kernels is launched that many times back to back and the call returns their
-        milliseconds (stage A, stage B)."""
+        milliseconds (stage A, stage B).  ``entropy``: ``"host"`` or ``"device"`` for this call, None for the engine's setting
+        (``set_jpeg_entropy``; the host unless set)."""
         torch = _torch()
+        if entropy is not None and entropy != getattr(self, "_jpeg_entropy", "host"):
+            if entropy not in _lib.JPEG_ENTROPY_MODES:
+                raise ValueError("entropy mode must be 'host' or 'device', not %r" % (entropy,))
+            before = getattr(self, "_jpeg_entropy", "host")
+            check(lib().lwp_set_jpeg_entropy(self.h.ptr, _lib.JPEG_ENTROPY_MODES[entropy], getattr(self, "_jpeg_subseq", 0)), self.h.ptr)
+            try:
+                return self.decode_jpeg_batch(files, time_iters)
+            finally:
+                check(lib().lwp_set_jpeg_entropy(self.h.ptr, _lib.JPEG_ENTROPY_MODES[before], getattr(self, "_jpeg_subseq", 0)), self.h.ptr)
         files = [bytes(f) for f in files]
         N = len(files)
         if N == 0:
