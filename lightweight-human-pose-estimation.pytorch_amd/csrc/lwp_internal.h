@@ -125,6 +125,7 @@ std::string pack_weights(const Graph& g, const std::vector<std::string>& names,
 struct Tuning {
     int stem_ty = 0, stem_wl = -1, stem_debug = 0;                 // LWP_STEM_TY, LWP_STEM_WL, LWP_STEM_DEBUG
     int dw_tiled = -1, dw_cc = 0, dw_ph = 0;                       // LWP_DW_TILED (0 never | 1 always), LWP_DW_CC, LWP_DW_PH
+    int dw_px = 0;                                                 // LWP_DW_PX (tests: 1 | 2 output pixels per thread of the per-thread depthwise kernel at every size)
     int gemm_wp = -1;                                              // LWP_GEMM_WP (-1 unset, else first digit)
     int gemm_debug = 0;                                            // LWP_GEMM_DEBUG (LWP_ABLATION builds: gemm_ar_kernel without 1 A staging, 2 weight requests, 4 MFMAs, 8 reduction + epilogue)
     bool has_c3 = false, has_pw = false; int c3[3] = {0, 0, 0}, pw[3] = {0, 0, 0};   // LWP_GEMM_C3 / LWP_GEMM_PW = "BM,BN,KS"
@@ -156,6 +157,11 @@ struct Tuning {
 };
 Tuning tuning_from_env();
 const Tuning& default_tuning();
+#ifdef __HIPCC__
+// ReLU of the conv kernels.  Not fmaxf: that returns its other operand for a NaN, so the NaN of an inf x 0 behind an fp16
+// overflow would read as 0 in the next layer; this keeps it, as torch's ReLU does (tests/exact_cases.py, the f16ovf fixtures).
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+#endif
 // name of the kernel variant a launcher picked, written when the caller supplies a buffer (debug / profiling entry points)
 constexpr int kVariantCap = 64;
 #define LWP_VARIANT(p, ...) do { if ((p).variant) snprintf((p).variant, lwp::kVariantCap, __VA_ARGS__); } while (0)

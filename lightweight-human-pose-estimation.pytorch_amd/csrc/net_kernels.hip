@@ -29,7 +29,7 @@ __device__ __forceinline__ float elu_negative(float v) {
     return v > -0.5f ? p : __expf(v) - 1.0f;
 }
 __device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == ACT_RELU) return fmaxf(v, 0.0f);
+    if (act == ACT_RELU) return relu_f(v);
     if (act == ACT_ELU) return v > 0.0f ? v : elu_negative(v);
     return v;
 }
@@ -177,11 +177,11 @@ __global__ void __launch_bounds__(ST_TY * ST_TX) stem_kernel(StemParams p) {
         if (BF16) {
             h16* so = (h16*)s_out + tid * (OLD * 2);
 #pragma unroll
-            for (int o = 0; o < 32; ++o) so[o] = (h16)fmaxf(acc[j][o], 0.f);
+            for (int o = 0; o < 32; ++o) so[o] = (h16)relu_f(acc[j][o]);
         } else {
             float* so = s_out + tid * OLD;
 #pragma unroll
-            for (int o = 0; o < 32; o += 4) *(f32x4*)(so + o) = f32x4{fmaxf(acc[j][o], 0.f), fmaxf(acc[j][o + 1], 0.f), fmaxf(acc[j][o + 2], 0.f), fmaxf(acc[j][o + 3], 0.f)};
+            for (int o = 0; o < 32; o += 4) *(f32x4*)(so + o) = f32x4{relu_f(acc[j][o]), relu_f(acc[j][o + 1]), relu_f(acc[j][o + 2]), relu_f(acc[j][o + 3])};
         }
         __syncthreads();
         for (int qd = tid; qd < ((DBG & 4) ? 0 : NT * CPP); qd += NT) {
@@ -438,8 +438,11 @@ hipError_t launch_dw(const DwParams& p, hipStream_t s) {
     const int cg = p.C >> 2;
     // few pixels per thread when the map is small (keep the chip full), more when it is large
     const int64_t pixels = (int64_t)p.N * p.Ho * p.Wo;
-    LWP_VARIANT(p, "dw<px=%d>", pixels * cg >= (int64_t)256 * 256 * 16 ? 2 : 1);
-    if (pixels * cg >= (int64_t)256 * 256 * 16) {
+    // LWP_DW_PX "1" | "2": that form at every size (tests; dw_kernel<2> has no precondition: an odd Wo ends its last pair early)
+    const Tuning& T = p.tune ? *p.tune : default_tuning();
+    const bool px2 = T.dw_px == 1 || T.dw_px == 2 ? T.dw_px == 2 : pixels * cg >= (int64_t)256 * 256 * 16;
+    LWP_VARIANT(p, "dw<px=%d>", px2 ? 2 : 1);
+    if (px2) {
         const int64_t total = (int64_t)p.N * p.Ho * ((p.Wo + 1) / 2) * cg;
         hipLaunchKernelGGL(dw_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
     } else {
@@ -1566,7 +1569,7 @@ __global__ void __launch_bounds__(1024) dwpw_pipe_kernel(DwPwParams p, int ntile
             for (int t = 4; t < 9; ++t) pacc += win[t] * *(const f32x4*)(Wd + t * C + c);
         } else {
             f32x4 v = pacc;
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
             *(f32x4*)(Adst + (it * PAR + prow) * ldA + c) = v;
         }
     };
@@ -1623,7 +1626,7 @@ __global__ void __launch_bounds__(1024) dwpw_pipe_kernel(DwPwParams p, int ntile
                 const int m = tile * BM + a * 16 + r16;
                 if (m < M32) {
                     f32x4 v = acc[a][t] + bias;
-                    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                    v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
                     *(f32x4*)(p.out + (int64_t)m * p.out_ld + n) = v;
                 }
             }
@@ -1870,7 +1873,7 @@ __global__ void __launch_bounds__(NW * 64) heads_f32_kernel(HeadsParams p) {
 #pragma unroll
         for (int x = 0; x < 2; ++x)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) hv[x][r] = fmaxf(acc1[x][r] + b0[r], 0.f);
+            for (int r = 0; r < 4; ++r) hv[x][r] = relu_f(acc1[x][r] + b0[r]);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t >= nt) continue;                                       // scalar branch around whole MFMA groups
@@ -2047,7 +2050,7 @@ __global__ void __launch_bounds__(256) heads_f32_lds_kernel(HeadsParams p) {
 #pragma unroll
             for (int i = 0; i < PT; ++i)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) hv[i][r] = fmaxf(acc1[i][r] + b0[r], 0.f);
+                for (int r = 0; r < 4; ++r) hv[i][r] = relu_f(acc1[i][r] + b0[r]);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if (t < t_lo || t >= t_hi) continue;                 // scalar branch around whole MFMA groups
@@ -2154,7 +2157,7 @@ Tuning tuning_from_env() {
     auto geti = [](const char* name, int* dst) { const char* e = getenv(name); if (e && e[0]) *dst = atoi(e); };
     auto digit = [](const char* name, int* dst) { const char* e = getenv(name); if (e && e[0]) *dst = e[0] - '0'; };
     geti("LWP_STEM_TY", &t.stem_ty); digit("LWP_STEM_WL", &t.stem_wl); geti("LWP_STEM_DEBUG", &t.stem_debug);
-    digit("LWP_DW_TILED", &t.dw_tiled); geti("LWP_DW_CC", &t.dw_cc); geti("LWP_DW_PH", &t.dw_ph);
+    digit("LWP_DW_TILED", &t.dw_tiled); geti("LWP_DW_CC", &t.dw_cc); geti("LWP_DW_PH", &t.dw_ph); geti("LWP_DW_PX", &t.dw_px);
     digit("LWP_GEMM_WP", &t.gemm_wp);
     if (const char* e = getenv("LWP_GEMM_C3")) t.has_c3 = sscanf(e, "%d,%d,%d", &t.c3[0], &t.c3[1], &t.c3[2]) == 3;
     if (const char* e = getenv("LWP_GEMM_PW")) t.has_pw = sscanf(e, "%d,%d,%d", &t.pw[0], &t.pw[1], &t.pw[2]) == 3;

@@ -18,7 +18,7 @@
 namespace lwp {
 
 __device__ __forceinline__ float act_f(float v, int act) {
-    if (act == ACT_RELU) return fmaxf(v, 0.0f);
+    if (act == ACT_RELU) return relu_f(v);
     // bf16 path: the result is rounded to 8 significant bits, so the hardware exp (abs error ~1e-7 on (-1, 0]) replaces
     // expm1f, which cost ~30 us per cpm.trunk block at batch 32
     if (act == ACT_ELU) return v > 0.0f ? v : __expf(v) - 1.0f;
@@ -958,7 +958,7 @@ __global__ void __launch_bounds__(256) heads_bf16_kernel(HeadsParams p) {
 #pragma unroll
                 for (int i = 0; i < RM; ++i)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) hf[i][j][g >> 1][(g & 1) * 4 + r] = (E)fmaxf(acc1[i][4 * g + r] + b[r], 0.f);
+                    for (int r = 0; r < 4; ++r) hf[i][j][g >> 1][(g & 1) * 4 + r] = (E)relu_f(acc1[i][4 * g + r] + b[r]);
             }
         }
         h16x8 w1v[2][2][2];                                          // the eight W1 fragments (hidden index permuted: see above)

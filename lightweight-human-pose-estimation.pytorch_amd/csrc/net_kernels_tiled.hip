@@ -28,8 +28,10 @@ struct f32x8 { f32x4 lo, hi; };
 
 template <int ACT>
 __device__ __forceinline__ float tl_act(float v) {
-    if (ACT == ACT_RELU) return fmaxf(v, 0.f);
-    if (ACT == ACT_ELU) return v > 0.f ? v : __expf(v) - 1.f;      // (bf16 path only: the f32 path keeps expm1f, see launcher)
+    if (ACT == ACT_RELU) return relu_f(v);
+    // 16-bit paths only (the kernel asserts it): exp(v) - 1 cancels near 0, which the 16-bit store hides (within one step of the
+    // rounded expm1 plus 2^-22); the f32 path's ELU is net_kernels.hip's elu_negative (polynomial above -0.5), see launcher
+    if (ACT == ACT_ELU) return v > 0.f ? v : __expf(v) - 1.f;
     return v;
 }
 
@@ -43,6 +45,7 @@ __global__ void __launch_bounds__(256, 3) dwpw_tiled_kernel(DwPwParams p, int ti
     constexpr int QN = C / VEC;                         // channel vectors per pixel
     constexpr int GRP = 256 / (QN * PW);               // row groups of the patch handled in parallel
     static_assert(GRP >= 1 && PH % GRP == 0, "patch / thread mismatch");
+    static_assert(BF16 || ACT != ACT_ELU, "tl_act's ELU is the cancelling exp(v) - 1: 16-bit stores only");
     constexpr int RPT = PH / GRP;                       // patch rows per thread
     constexpr int WR = (PH - 1) * S + 3, WC = (PW - 1) * S + 3;
     constexpr int NPX = PH * PW;                        // output pixels of the patch
@@ -313,7 +316,7 @@ static hipError_t try_tiled(const DwPwParams& p, hipStream_t s, bool* used) {
     if (T.dwpw_tiled == 0) return hipSuccess;                  // LWP_DWPW_TILED "0": off (A/B); "1": at every size (tests)
     constexpr int ESZ = BF16 ? 2 : 4;
     const bool relu = p.act_dw == ACT_RELU && p.act_pw == ACT_RELU, elu = p.act_dw == ACT_ELU && p.act_pw == ACT_ELU;
-    if (p.dil != 1 || !(relu || (elu && BF16))) return hipSuccess;       // (ELU blocks: bf16 only — the f32 path's ELU is expm1f)
+    if (p.dil != 1 || !(relu || (elu && BF16))) return hipSuccess;       // (ELU blocks: 16-bit only — the f32 path's ELU is elu_negative)
     if (p.res && (!elu || (p.res_ld % 8) || (((uintptr_t)p.res) & 15))) return hipSuccess;
     if (p.in_ld != p.C || (p.out_ld % (BF16 ? 8 : 4)) || (((uintptr_t)p.out) & 15) || (((uintptr_t)p.in) & 15)) return hipSuccess;
     if ((int64_t)p.N * p.Hi * p.Wi * p.in_ld * ESZ >= (1ll << 31)) return hipSuccess;      // 32-bit buffer offsets

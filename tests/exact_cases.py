@@ -18,9 +18,18 @@ Rounding points of the 16-bit paths (tools/bf16_budget.py):
 that is stored or handed to an MFMA; accumulation, bias, activation functions and residual adds are f32; depthwise weights
 and the stem stay f32.  Stage outputs are f32; their copy in the concat buffer is 16-bit.
 
-Not covered here (they stay with the tolerance tests): ELU's negative branch (a polynomial / the hardware exponential: not
-exact; the cpm trunk fixtures keep every ELU operand >= 0, which ``exactness`` checks), fp16 subnormals and overflow, and
-the dw<px=2> kernel, which only a 720 x 1280 frame reaches.
+ELU's negative branch (a polynomial / the hardware exponential) is not exact: the fixtures above keep every ELU operand >= 0,
+which ``exactness`` checks, and the ``elu:*`` fixtures at the end of this file pin the branch by a derived bound instead:
+an exactly known negative operand per element, fp32 within 1e-6 relative of float64 expm1, bf16 / fp16 within one step of the
+format + 2^-22 of the rounded expm1 (which says nothing below |z| of about 2^-22, where the 16-bit form cancels).  The
+dw<px=2> kernel runs every depthwise fixture through LWP_DW_PX=2 (tests/variant_matrix.py).
+
+fp16 subnormals: the ``f16sub:*`` fixtures (bit exact like the others; plain fixtures at fp32 and bf16) store and consume
+values below 2^-14 at fp16 in every kernel family: gradual underflow, round to nearest even on the subnormal grid, no flush.
+
+fp16 overflow: the ``f16ovf:*`` fixtures (again plain exact fixtures at fp32 and bf16) store 65504, values in (65504, 65520),
+the tie 65520 and larger values at fp16 in every kernel family and read one consumer behind them: round to nearest even to
+inf, no saturation; inf x 0 is NaN and stays NaN through ReLU, as in the float64 reference.
 """
 from collections import OrderedDict
 
@@ -220,7 +229,7 @@ NORMAL = {"fp32": (2.0 ** -126, 3.4e38), "bf16": (2.0 ** -126, 3.38e38), "fp16":
 def _lowbit(t):
     """Smallest set bit (as a power of two) over the non-zero entries of a float64 tensor; inf if all are zero."""
     a = t.detach().numpy().ravel()
-    a = a[a != 0]
+    a = a[(a != 0) & np.isfinite(a)]
     if a.size == 0:
         return float("inf")
     m, e = np.frexp(np.abs(a))
@@ -253,10 +262,10 @@ def reference(sd, x, nref=1, dtype="fp32", base=None, round16=None, stop_after=N
     block output).  ``base`` = (state dict, result) of an earlier call on the same input, dtype and rounding: layers up to the
     first one whose parameters differ are taken from it.  ``round16`` replaces the dtype's rounding (tests flip it to
     truncation).  ``probe``: also record, under "_exact", per reduction (headroom bits, smallest ELU operand) and under
-    "_stored" per rounding point (smallest, largest non-zero stored magnitude)."""
+    "_stored" per rounding point (smallest, largest non-zero stored magnitude) and under "_z" the operand tensor of every ELU."""
     h16 = dtype != "fp32"
     r16 = round16 or ROUND[dtype]
-    taps, exact, stored = OrderedDict(), OrderedDict(), OrderedDict()
+    taps, exact, stored, zs = OrderedDict(), OrderedDict(), OrderedDict(), OrderedDict()
     st = {"dirty": base is None, "elu_min": float("inf")}
     x = torch.as_tensor(np.asarray(x)).double()
 
@@ -280,8 +289,9 @@ def reference(sd, x, nref=1, dtype="fp32", base=None, round16=None, stop_after=N
             note_stored(name + "/w", w)
         y = F.conv2d(xin, w, b, stride, pad, dil, groups)
         if probe:
-            s = float(F.conv2d(xin.abs(), w.abs(), b.abs(), stride, pad, dil, groups).max())
-            q = min(_lowbit(xin) * _lowbit(w), _lowbit(b))
+            xf = torch.where(torch.isfinite(xin), xin, torch.zeros_like(xin))        # (the f16ovf fixtures: the finite part)
+            s = float(F.conv2d(xf.abs(), w.abs(), b.abs(), stride, pad, dil, groups).max())
+            q = min(_lowbit(xf) * _lowbit(w), _lowbit(b))
             exact[name] = 24.0 - float(np.log2(s / q)) if s > 0 and np.isfinite(q) else 24.0
         return y
 
@@ -293,7 +303,8 @@ def reference(sd, x, nref=1, dtype="fp32", base=None, round16=None, stop_after=N
 
     def elu(name, t):
         if probe:
-            exact[name + "/elu_min"] = float(t.min())
+            exact[name + "/elu_min"] = float(t[torch.isfinite(t)].min())      # (the f16ovf fixtures: of the finite operands)
+            zs[name] = t                                  # the ELU's operand, element by element (the bounded ELU fixtures)
         return F.elu(t)
 
     def keys(ck, bn=None):
@@ -307,7 +318,7 @@ def reference(sd, x, nref=1, dtype="fp32", base=None, round16=None, stop_after=N
         if not st["dirty"] and all(sd[k] is base[0][k] for k in ks) and all(n in base[1] for n in names):
             for n in names:
                 taps[n] = base[1][n]
-            for src, dst in ((base[1].get("_exact", {}), exact), (base[1].get("_stored", {}), stored)):
+            for src, dst in ((base[1].get("_exact", {}), exact), (base[1].get("_stored", {}), stored), (base[1].get("_z", {}), zs)):
                 for k, v in src.items():
                     if k.split("/")[0] in names:
                         dst[k] = v
@@ -375,7 +386,7 @@ def reference(sd, x, nref=1, dtype="fp32", base=None, round16=None, stop_after=N
     res = _Result(out)
     res.tensors = taps
     if probe:
-        res["_exact"], res["_stored"] = exact, stored
+        res["_exact"], res["_stored"], res["_z"] = exact, stored, zs
     return res
 
 
@@ -387,7 +398,7 @@ class _Result(OrderedDict):
 def as_base(sd, res):
     """(sd, {name: tensor}) for ``reference(base=...)``."""
     d = dict(res.tensors)
-    for k in ("_exact", "_stored"):
+    for k in ("_exact", "_stored", "_z"):
         if k in res:
             d[k] = res[k]
     return sd, d
@@ -472,15 +483,170 @@ def build_fixtures():
     return fx
 
 
+# ------------------------------------------------------------------------------------------------------------ fp16 subnormals
+# Plain exact fixtures at fp32 and bf16; at fp16 the stored activations of the layers between ``down`` and ``up`` are subnormal
+# (the "stored values are normal" rule is lifted for them at fp16 only: ``subnormal_ok``), and the oracle is torch's CPU half
+# rounding: IEEE gradual underflow, round to nearest even.  ``down`` (one or two convs) is scaled by 2^-17, so what it stores
+# are the multiples n 2^-25 of HALF the subnormal spacing: odd n are exact ties (3 -> 4 rounds to even upwards, 5 -> 4 downwards,
+# 1 -> 0 is a non-zero value that rounds to 0); its bias, which is what a pixel with a zero input stores, cycles through
+# F16SUB_BIAS: 2^-24, the ties, the largest subnormal 1023 2^-24 and the smallest normal 2^-14.  The convs in ``mid`` lose
+# their bias (it would be 2^17 times too large) and pass the subnormals on: depthwise unpack, MFMA activation operand, residual
+# and concat copies.  ``up`` multiplies by 2^13 (2^16 is no fp16 weight), back to normal numbers k 2^-12: the subnormals are
+# consumed and not only stored.  2^-17 is itself a subnormal packed GEMM weight where ``down`` is a GEMM.
+F16SUB_DOWN, F16SUB_UP = 2.0 ** -17, 2.0 ** 13
+F16SUB_BIAS = (0, 2, 1, 3, 5, 7, 2046, 2048)          # in units of 2^-25
+F16SUB = [
+    dict(name="model.0>model.1", down=["model.0.0"], mid=[], up="model.1.0"),                    # stem store -> depthwise unpack
+    dict(name="model.1>model.2", down=["model.1.3"], mid=[], up="model.2.0"),                    # fused block store -> stride-2 depthwise
+    dict(name="model.4>model.5", down=["model.4.3"], mid=[], up="model.5.0"),
+    dict(name="model.6>model.7", down=["model.6.3"], mid=[], up="model.7.0"),                    # 512 outputs -> dilation 2
+    dict(name="model.5.dw>pw", down=["model.5.0"], mid=[], up="model.5.3"),                      # a 2^-17 f32 tap: subnormal MFMA operand inside one kernel
+    dict(name="cpm", down=["cpm.align.0"], mid=["cpm.trunk.%d.%d" % (j, k) for j in range(3) for k in (0, 2)], up="cpm.conv.0"),
+    # feature and stage maps both subnormal: the f32 stage outputs stay normal f32 numbers, their 16-bit concat copy is subnormal
+    dict(name="cpm.conv>concat", down=["cpm.conv.0"],
+         mid=["initial_stage.trunk.%d.0" % j for j in range(3)] + ["initial_stage.%s.%d.0" % (n, k) for k in (0, 1) for n in ("heatmaps", "pafs")],
+         up="refinement_stages.0.trunk.0.initial.0"),
+    dict(name="refinement", down=["refinement_stages.0.trunk.0.initial.0"],
+         mid=["refinement_stages.0.trunk.0.trunk.0.0", "refinement_stages.0.trunk.0.trunk.1.0"], up="refinement_stages.0.trunk.1.initial.0"),
+]
+
+
+def _set(out, key, arr, like):
+    out[key] = torch.from_numpy(np.ascontiguousarray(np.asarray(arr, np.float32))).reshape(tuple(like.shape))
+
+
+def f16sub_state_dict(sd, spec, down=None, up=None, bias=None):
+    """``spec``'s ``down`` convs scaled by ``down`` (a power of two, or one per output channel) with the folded bias
+    ``bias(co)``, its ``mid`` convs without bias, its ``up`` conv scaled by ``up`` (defaults: the f16sub values)."""
+    out = OrderedDict(sd)
+    down = F16SUB_DOWN if down is None else down
+    up = F16SUB_UP if up is None else up
+    bias = bias or (lambda co: np.asarray(F16SUB_BIAS, np.float64)[np.arange(co) % len(F16SUB_BIAS)] * 2.0 ** -25)
+
+    def rebias(conv, scale, bias):
+        """Scale the conv's output by ``scale`` and make its (folded) bias ``bias``."""
+        w = sd[conv + ".weight"]
+        bn = _bn_of(conv)
+        if bn:
+            cb = sd[conv + ".bias"].numpy() if conv + ".bias" in sd else np.zeros(w.shape[0], np.float32)
+            _set(out, bn + ".weight", sd[bn + ".weight"].numpy() * np.asarray(scale, np.float32), sd[bn + ".weight"])
+            _set(out, bn + ".running_mean", cb, sd[bn + ".running_mean"])
+            _set(out, bn + ".bias", bias, sd[bn + ".bias"])
+        else:
+            _set(out, conv + ".weight", w.numpy() * np.asarray(scale, np.float32).reshape(-1, 1, 1, 1), w)
+            if conv + ".bias" in sd:
+                _set(out, conv + ".bias", bias, sd[conv + ".bias"])
+    for conv in spec["down"]:
+        co = sd[conv + ".weight"].shape[0]
+        rebias(conv, down(co) if callable(down) else down, bias(co))
+    for conv in spec["mid"]:
+        rebias(conv, 1.0, np.zeros(sd[conv + ".weight"].shape[0]))
+    _set(out, spec["up"] + ".weight", sd[spec["up"] + ".weight"].numpy() * np.float32(up), sd[spec["up"] + ".weight"])
+    return out
+
+
+def build_f16sub_fixtures():
+    fx = []
+    for spec in F16SUB:
+        f = _fixture("f16sub:" + spec["name"], spec["down"] + spec["mid"] + [spec["up"]])
+        f.update(f16sub=spec, subnormal_ok=True)
+        fx.append(f)
+    return fx
+
+
+F16SUB_FIXTURES = build_f16sub_fixtures()
+
+
+# ------------------------------------------------------------------------------------------------------------ fp16 overflow
+# Plain exact fixtures at fp32 and bf16 (65520 is a finite number there); at fp16 the oracle is torch's CPU half rounding:
+# round to nearest even to inf, no saturation.  ``down`` is scaled by 2^5, so it stores k 2^-3 with k < 532, and one channel
+# gets the bias 65504 and one 65512 on top (``_ovf_channels`` picks them by the selector network's batch-1 activations): a pixel with a zero input stores 65504 (or 65512, which rounds to 65504), small
+# inputs land in (65504, 65520) and round to 65504, 65504 + 16 and 65512 + 8 are the tie 65520, which rounds to even = inf,
+# and everything above is inf.  The stage heads have no ReLU: there two more channels are the same, negated (weight and bias),
+# which gives the negative twins; the f32 stage outputs stay finite while their 16-bit concat copy is +-inf.  ``up`` (the only
+# consumer that is read) multiplies by 2^-5: inf stays inf, and inf x 0, a zero weight or tap on an inf, is NaN, in the float64
+# reference as on the device; ``check`` treats NaN at the same place and inf of the same sign as equal for these fixtures only.
+F16OVF_UP, F16OVF_DOWN = 2.0 ** 5, 2.0 ** -5
+F16OVF = [
+    dict(name="model.0>model.1", down=["model.0.0"], mid=[], up="model.1.0"),
+    dict(name="model.1>model.2", down=["model.1.3"], mid=[], up="model.2.0"),
+    dict(name="model.4>model.5", down=["model.4.3"], mid=[], up="model.5.0"),
+    dict(name="model.6>model.7", down=["model.6.3"], mid=[], up="model.7.0"),
+    dict(name="model.5.dw>pw", down=["model.5.0"], mid=[], up="model.5.3"),
+    dict(name="cpm.align>trunk", down=["cpm.align.0"], mid=[], up="cpm.trunk.0.0"),
+    dict(name="cpm.conv>trunk", down=["cpm.conv.0"], mid=[], up="initial_stage.trunk.0.0"),
+    dict(name="heads>concat", down=["initial_stage.heatmaps.1.0", "initial_stage.pafs.1.0"], mid=[], up="refinement_stages.0.trunk.0.initial.0", twins=True),
+    dict(name="refinement", down=["refinement_stages.0.trunk.0.initial.0"], mid=[], up="refinement_stages.0.trunk.0.trunk.0.0"),
+    dict(name="refinement.3x3>3x3", down=["refinement_stages.0.trunk.0.trunk.0.0"], mid=[], up="refinement_stages.0.trunk.0.trunk.1.0"),
+    # (the 1x1 that the window-resident 3x3 in front of it can carry in its epilogue)
+    dict(name="refinement.1", down=["refinement_stages.0.trunk.1.initial.0"], mid=[], up="refinement_stages.0.trunk.1.trunk.0.0"),
+]
+
+
+def _first_tensor(spec):
+    """reference() name of the tensor the first ``down`` conv of an f16sub / f16ovf spec writes."""
+    c = spec["down"][0]
+    p = c.split(".")
+    return "model.%s.dw" % p[1] if p[0] == "model" and p[1] != "0" and p[2] == "0" else layer_of(c)
+
+
+def _ovf_channels(y, twins):
+    """Channels of ``y`` (N, C, H, W; the scaled tensor without the special bias, multiples of 2^-3) for the biases 65504, 65512
+    (and, with ``twins``, -65504, -65512): the first holds 0, values in (0, 16), 16 (65504 + 16 is the tie 65520) and more,
+    the second 8 (65512 + 8 is that tie again)."""
+    rows = y.transpose(1, 0, 2, 3).reshape(y.shape[1], -1)
+    ok = [c for c, r in enumerate(rows) if (r == 0).any() and ((r > 0) & (r < 16)).any()]
+    full = [c for c in ok if (rows[c] == 16).any() and (rows[c] > 16).any()] or ok       # (the stem's scaled values end below 16)
+    rest = [c for c in range(len(rows)) if c not in full[:2] and (rows[c] > 8).any()]
+    half = [c for c in rest if (rows[c] == 8).any()] or [c for c in rest if (rows[c] == 0).any()]
+    need = 2 if twins else 1
+    assert len(full) >= need and len(half) >= need, (len(full), len(half))
+    return [full[0], half[0]] + ([full[1], half[1]] if twins else [])
+
+
+def f16ovf_state_dict(sd, spec):
+    tw = bool(spec.get("twins"))
+    big = spec.get("scale", F16OVF_UP)
+    plain = f16sub_state_dict(sd, spec, down=big, up=1.0, bias=lambda co: np.zeros(co))
+    y = reference(plain, frame_of(FRAMES[1]), 1, "fp32", base=selector_run(FRAMES[1], "fp32"), stop_after=layer_of(spec["down"][0]))[_first_tensor(spec)]
+    at, chosen = 0, {}
+    for conv in spec["down"]:                              # (the two head convs write one tensor: [heat | paf])
+        co = sd[conv + ".weight"].shape[0]
+        chosen[co] = _ovf_channels(y[:, at:at + co], tw)
+        at += co
+
+    def sign(co):
+        v = np.ones(co)
+        v[chosen[co][2:]] = -1.0
+        return v
+
+    def bias(co):
+        v = np.zeros(co)
+        v[chosen[co][0::2]], v[chosen[co][1::2]] = 65504.0, 65512.0
+        return v * sign(co)
+    return f16sub_state_dict(sd, spec, down=lambda co: big * sign(co), up=1.0 / big, bias=bias)
+
+
+def build_f16ovf_fixtures():
+    fx = []
+    for spec in F16OVF:
+        f = _fixture("f16ovf:" + spec["name"], spec["down"] + [spec["up"]])
+        f.update(f16ovf=spec, nonfinite_ok=True)
+        fx.append(f)
+    return fx
+
+
+F16OVF_FIXTURES = build_f16ovf_fixtures()
 FIXTURES = build_fixtures()
-BY_NAME = {f["name"]: f for f in FIXTURES}
+ALL_EXACT = FIXTURES + F16SUB_FIXTURES + F16OVF_FIXTURES        # everything that is compared bit for bit on the device
+BY_NAME = {f["name"]: f for f in ALL_EXACT}
 
 
 def fixtures_for(layer, nref=1):
     """Fixtures whose layers under test include engine layer ``layer`` ("model.N.dw" counts as "model.N.pw")."""
     if layer.endswith(".dw"):
         layer = layer[:-3] + ".pw"
-    return [f for f in FIXTURES if f["nref"] == nref and layer in f["layers"]]
+    return [f for f in ALL_EXACT if f["nref"] == nref and layer in f["layers"]]
 
 
 _SEL, _FRAME, _DENSE, _BASE = {}, {}, {}, {}
@@ -499,6 +665,12 @@ def frame_of(shape):
 
 
 def dense_sd(fx):
+    if fx["name"] not in _DENSE and fx.get("f16ovf"):
+        _DENSE[fx["name"]] = f16ovf_state_dict(selector(fx["nref"]), fx["f16ovf"])
+    if fx["name"] not in _DENSE and fx.get("f16sub"):
+        _DENSE[fx["name"]] = f16sub_state_dict(selector(fx["nref"]), fx["f16sub"])
+    if fx["name"] not in _DENSE and fx.get("elu"):
+        _DENSE[fx["name"]] = elu_state_dict(selector(fx["nref"]), fx["j"], fx["elu"])
     if fx["name"] not in _DENSE:
         _DENSE[fx["name"]] = with_dense(selector(fx["nref"]), fx["convs"], seed=fx["seed"], opts=fx["opts"])
     return _DENSE[fx["name"]]
@@ -561,3 +733,187 @@ def tap_of(name, taps):
     if name.startswith("refinement_stages.") and name.endswith(".trunk.1") and name.count(".trunk.") == 2:
         return taps[name[:-len(".trunk.1")]]
     return taps[name]
+
+
+# ------------------------------------------------------------------------------------------------------------ ELU below zero
+# Bounded, not exact: the operand z of one ELU of the cpm trunk is exactly known in f32 (a single product of an input k 2^-8
+# with a weight -2^e, no bias), negative, and swept from -2^-22 (.pw) or -2^-30 (.dw) down to about -132; the reference is
+# expm1(z) in float64 (``reference`` through F.elu).  Everything else is the selector network, so the positive elements of
+# the same tensors (one channel in every cycle keeps its weight +1) and every z = 0 stay bit exact.
+#
+#   fp32         |got - E| <= 1e-6 |E|: Taylor truncation 2.5e-7 at -0.5 plus at most nine roundings of 2^-24 is 7.9e-7; below
+#                -0.5 |E| >= 0.39 and the error is at most 2 ulp of exp.  Behind a residual add: + half an f32 ulp of the sum.
+#   bf16 / fp16  |got - r16(E)| <= step16(E) + 2^-22: the step (the format's spacing at |E|, the subnormal spacing below the
+#                smallest normal) covers the two half-step roundings of the device and of the reference; 2^-22 covers __expf near 1
+#                (<= 2 ulp of 2^-24) and a subtraction that is exact or off by half an ulp.  Behind a residual add the stored
+#                sum is rounded once more: the step is taken at |E + a|, and where E was rounded before the add (the .dw
+#                fixtures: the depthwise result is an MFMA operand) both steps count.
+#                Below |z| of about 2^-22 this bound says NOTHING about the 16-bit ELU: exp(z) - 1 in f32 cancels there (at
+#                z = -2.9e-8 the bf16 result is 248 bf16 steps off, absolutely 3e-8), and 2^-22 is larger than |E| itself.
+#                The .dw fixtures reach that region (they have to: their fp32 form is held to 1e-6 relative down to 2^-30).
+ELU_PW_EXP = tuple(range(-14, 7))        # cpm.trunk.J.2 is a packed GEMM weight: 2^-14 is the smallest normal fp16 (exact in bf16)
+ELU_DW_EXP = tuple(range(-22, 7))        # depthwise weights stay f32 on every path
+ELU_F32_REL = 1e-6
+ELU_16_ABS = 2.0 ** -22
+
+
+def _elu_scale(x, exps, ends=6):
+    """Per channel of the tensor ``x`` (N, C, H, W; multiples of 2^-8) the conv under test reads: -2^e, or +1 for the bit-exact
+    positive elements.  The ``ends`` channels with the largest values take the largest exponent (one channel in 128 carries
+    values up to 531 / 256, a dozen reach 1: only there does |z| pass 2^6 and 104) and the ``ends`` channels with the most
+    distinct small odd multiples k 2^-8 (k < 16) the smallest (the lowest binades hold few grid points: all of them are wanted);
+    the others cycle through the exponents in between and +1."""
+    k = np.rint(x.transpose(1, 0, 2, 3).reshape(x.shape[1], -1) * 256).astype(np.int64)
+    n = k.shape[0]
+    sc = np.zeros(n)
+    top = np.argsort(-k.max(axis=1), kind="stable")[:ends]
+    sc[top] = -2.0 ** exps[-1]
+    odd = np.array([len({int(v) for v in row if v < 16 and v % 2 == 1}) for row in k], np.int64)
+    odd[top] = -1
+    low = np.argsort(-odd, kind="stable")[:ends]
+    sc[low] = -2.0 ** exps[0]
+    rest = np.flatnonzero(sc == 0)
+    mid = np.asarray([-2.0 ** e for e in exps[1:-1]] + [1.0])
+    sc[rest] = mid[np.arange(rest.size) % mid.size]
+    return sc
+
+
+def elu_state_dict(sd, j, kind):
+    """The selector network with the ELU operand of cpm.trunk.J's pointwise ("pw") or depthwise ("dw") conv swept below zero.
+
+    "pw": row o of cpm.trunk.J.2 keeps its one (permuted) input channel with weight -2^e(o).  "dw": the tap of channel c of
+    cpm.trunk.J.0 becomes -2^e(c), and cpm.trunk.J.2 copies a negative channel with weight -1: the fused layer then stores
+    -(the 16-bit ELU value) >= 0, which the second ELU passes unchanged.  Which channel takes which exponent follows the
+    selector network's fp32 activations on the batch-1 frame (the first image of the batch-2 frame), see ``_elu_scale``."""
+    out = OrderedDict(sd)
+    dwk, pwk = "cpm.trunk.%d.0.weight" % j, "cpm.trunk.%d.2.weight" % j
+    acts = selector_run(FRAMES[1], "fp32")[1]
+    wp = sd[pwk].numpy().astype(np.float64).reshape(128, 128)
+    pick = np.abs(wp).argmax(axis=1)
+    if kind == "pw":
+        wp = wp * _elu_scale(acts["cpm.trunk.%d.dw" % j].numpy()[:, pick], ELU_PW_EXP)[:, None]
+    else:
+        sc = _elu_scale(acts["cpm.align" if j == 0 else "cpm.trunk.%d.pw" % (j - 1)].numpy(), ELU_DW_EXP)
+        wd = sd[dwk].numpy().astype(np.float64).reshape(128, 9) * sc[:, None]
+        out[dwk] = torch.from_numpy(wd.astype(np.float32).reshape(tuple(sd[dwk].shape)))
+        wp = wp * np.where(sc[pick] < 0, -1.0, 1.0)[:, None]
+    out[pwk] = torch.from_numpy(wp.astype(np.float32).reshape(tuple(sd[pwk].shape)))
+    return out
+
+
+def build_elu_fixtures():
+    fx = []
+    for j in range(3):
+        for kind, conv in (("pw", "cpm.trunk.%d.2" % j), ("dw", "cpm.trunk.%d.0" % j)):
+            f = _fixture("elu:cpm.trunk.%d.%s" % (j, kind), [conv])
+            f.update(elu=kind, j=j)
+            fx.append(f)
+    return fx
+
+
+ELU_FIXTURES = build_elu_fixtures()          # kept apart from FIXTURES: those are compared bit for bit on every element
+
+
+def elu_fixtures_for(layer):
+    """ELU fixtures that engine layer ``layer`` ("cpm.trunk.J.pw", or "cpm.trunk.J.dw" of the unfused graph) runs."""
+    return [f for f in ELU_FIXTURES if f["layers"][0][:-3] == layer[:-3]]
+
+
+def step16(dtype, a):
+    """Spacing of the 16-bit format at |a| (the subnormal spacing below its smallest normal number)."""
+    mant, emin = (7, -126) if dtype == "bf16" else (10, -14)
+    e = np.frexp(np.maximum(np.abs(a), 2.0 ** emin))[1] - 1
+    return np.exp2((np.maximum(e, emin) - mant).astype(np.float64))
+
+
+def _ulp32(a):
+    return np.exp2((np.maximum(np.frexp(np.maximum(np.abs(a), 2.0 ** -126))[1] - 1, -126) - 23).astype(np.float64))
+
+
+def elu_reference(fx, shape, dtype):
+    """fixture_reference with the ELU operands recorded (``["_z"]``)."""
+    return fixture_reference(fx, shape, dtype, probe=True)
+
+
+def elu_expect(fx, ref, layer, dtype):
+    """What engine layer ``layer`` must hold on an ELU fixture: dict(want = the float64 reference of the stored tensor, bound =
+    the allowed |got - want| per element (0: bit exact), neg = the elements behind a negative ELU operand, z = that operand,
+    lo / hi = the interval the stored value of a ``neg`` element lies in because the ELU value is in [-1, 0])."""
+    j, kind = fx["j"], fx["elu"]
+    n_dw, n_pw = "cpm.trunk.%d.dw" % j, "cpm.trunk.%d.pw" % j
+    assert layer in (n_dw, n_pw), layer
+    want = ref[layer]
+    if kind == "pw" and layer == n_dw:                   # the selector depthwise in front of it: operands >= 0, identity
+        zero = np.zeros_like(want)
+        return dict(want=want, bound=zero, neg=zero.astype(bool), z=ref["_z"][n_dw].numpy(), lo=zero, hi=zero)
+    z = ref["_z"][n_pw if kind == "pw" else n_dw].numpy()
+    sign = 1.0
+    if kind == "dw" and layer == n_pw:                   # read through the +-1 selector behind it
+        w2 = dense_sd(fx)["cpm.trunk.%d.2.weight" % j].numpy().astype(np.float64).reshape(128, 128)
+        pick = np.abs(w2).argmax(axis=1)
+        z = z[:, pick]
+        sign = w2[np.arange(128), pick].reshape(1, 128, 1, 1)
+    neg = z < 0
+    e = np.where(neg, np.expm1(np.minimum(z, 0.0)), z)
+    res = layer == n_pw and j == 2
+    a = ref["cpm.align"] if res else np.zeros_like(z)
+    s = sign * e + a
+    if dtype == "fp32":
+        bound = ELU_F32_REL * np.abs(e) + (0.5 * _ulp32(s) if res else 0.0)
+    else:
+        bound = step16(dtype, e) + ELU_16_ABS
+        if res:
+            bound = step16(dtype, s) + ELU_16_ABS + (step16(dtype, e) if kind == "dw" else 0.0)
+    r = ROUND[dtype]
+    ends = [r(torch.from_numpy(np.ascontiguousarray(sign * v + a))).numpy() for v in (-1.0, 0.0)]
+    return dict(want=want, bound=np.where(neg, bound, 0.0), neg=neg, z=z, lo=np.minimum(*ends), hi=np.maximum(*ends))
+
+
+def elu_compare(got, exp):
+    """(problems, worst error / bound over the elements behind a negative operand) of a device tensor against ``elu_expect``."""
+    g = got.astype(np.float64)
+    err = np.abs(g - exp["want"])
+    neg = exp["neg"]
+    bad = []
+    exact = ~neg & (g != exp["want"])                     # z = 0 gives 0, positive elements bit for bit (a NaN differs)
+    if exact.any():
+        bad.append("%d of %d identity / zero elements differ" % (int(exact.sum()), int((~neg).sum())))
+    over = neg & ~(err <= exp["bound"])
+    if over.any():
+        at = tuple(int(v) for v in np.argwhere(over)[0])
+        bad.append("%d of %d beyond the bound; first at %s: z %.9g got %.9g want %.9g bound %.3g" % (
+            int(over.sum()), int(neg.sum()), at, exp["z"][at], g[at], exp["want"][at], exp["bound"][at]))
+    out = neg & ~((g >= exp["lo"]) & (g <= exp["hi"]))
+    if out.any():
+        at = tuple(int(v) for v in np.argwhere(out)[0])
+        bad.append("%d elements outside the image of [-1, 0]; first at %s: got %.9g" % (int(out.sum()), at, g[at]))
+    ratio = float((err[neg] / exp["bound"][neg]).max()) if neg.any() else 0.0
+    return bad, ratio
+
+
+# the two device forms restated in float32 NumPy (no fma; exp correctly rounded), and the faults the bounds must bite on
+_ELU_COEF = (1.0, 0.5, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040)
+
+
+def elu_f32_form(z, coef=_ELU_COEF, switch=-0.5):
+    """net_kernels.hip's elu_negative on float32 operands <= 0: the degree-7 polynomial above ``switch``, exp - 1 below."""
+    v = np.asarray(z, np.float32)
+    c = [np.float32(x) for x in coef]
+    p = c[6]
+    for k in range(5, -1, -1):
+        p = (c[k] + (v * p).astype(np.float32)).astype(np.float32)
+    p = (v * p).astype(np.float32)
+    return np.where(v > np.float32(switch), p, elu_cancelling_form(v))
+
+
+def elu_cancelling_form(z):
+    """The 16-bit paths' __expf(v) - 1 in float32 (before the 16-bit store)."""
+    v = np.asarray(z, np.float32)
+    return (np.exp(v.astype(np.float64)).astype(np.float32) - np.float32(1)).astype(np.float32)
+
+
+ELU_MUTANTS = {
+    "1/720 in place of 1/5040": lambda z: elu_f32_form(z, coef=_ELU_COEF[:6] + (1.0 / 720,)),
+    "switch point at -5": lambda z: elu_f32_form(z, switch=-5.0),
+    "the cancelling form at fp32": elu_cancelling_form,
+}

@@ -7,9 +7,22 @@ nearest even where the path stores 16 bits.  ``np.array_equal`` on every element
   * default kernels: every fixture x {fp32, bf16, fp16} x {2, 1} frames; a fused group is read at its last layer and at every
     member ``debug_layer_output`` exposes; stage outputs are read twice, as the f32 maps ``forward`` returns and as their
     (16-bit) copy in the concat buffer;
-  * every row of tests/variant_matrix.py, forced with the row's switches (bf16 rows also at fp16): the row's variant string is
-    asserted and each of its layers runs every fixture that has it under test, the joint ones of its fused group included.
-    Not run: dw<px=2>, which only a 720 x 1280 frame reaches (a workload-size frame).
+  * every row of tests/variant_matrix.py at the fixture frame, forced with the row's switches (bf16 rows also at fp16): the
+    row's variant string is asserted and each of its layers runs every fixture that has it under test, the joint ones of its
+    fused group included.  dw<px=2> runs here too (LWP_DW_PX=2, odd output widths); no variant of the matrix is left out.
+
+The ``f16sub:*`` fixtures are among them: at fp16 they store and consume subnormals (2^-14, the largest subnormal, 2^-24, ties
+of the subnormal grid, non-zero values that round to 0) in every kernel family; the oracle is torch's CPU half rounding, so a
+flush at a store or at an MFMA / depthwise operand differs.  The ``f16ovf:*`` fixtures store 65504, values that round to it,
+the tie 65520 and larger values (fp16: inf, never saturated) and read one consumer; for them alone a NaN (inf x 0) at the same
+place as in the reference counts as equal, and inf equals inf of the same sign as always.
+
+ELU below zero is pinned by a bound, not bit for bit (the ``elu:*`` fixtures of tests/exact_cases.py, which states the bounds
+and their derivation): per element behind an exactly known negative operand, fp32 within 1e-6 relative of float64 expm1, bf16
+and fp16 within one step of the format + 2^-22 of the rounded expm1; the result lies in [-1, 0]; z = 0 gives 0 and the positive
+elements of the same tensors are bit exact.  Default engines (three dtypes x both frames) and every row that lists a
+cpm.trunk layer; behind a forced stand-alone depthwise the f32 GEMM's ELU epilogue is read as well.  The worst error / bound
+per dtype and variant is printed and lands in the report under "elu_worst".
 
 LWP_EXACT_REPORT=path dumps per comparison the variant seen, the elements compared and the elements differing."""
 import json
@@ -30,9 +43,8 @@ pytestmark = pytest.mark.gpu
 DT = {"fp32": _lib.F32, "bf16": _lib.BF16, "fp16": _lib.F16}
 # every kernel-choice switch a row may set: cleared before each engine so that one row's switch never leaks into another's
 SWITCHES = sorted({k for r in vm.ROWS for k in r["env"]} | {k for u in vm.UPSAMPLE_ROWS for k in u["env"]} | {"LWP_MS_TX"})
-SKIPPED_VARIANT = "dw<px=2>"             # no switch: pixels * C / 4 >= 2^20, a 720 x 1280 frame
 
-REPORT = {"cases": [], "variants_seen": {}}
+REPORT = {"cases": [], "variants_seen": {}, "elu": [], "elu_worst": {}}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -88,6 +100,8 @@ def check(case, eng, fx, shape, dtype, layers, bad, expect_variant=None):
     def note(layer, variant, got, want):
         assert got.shape == want.shape, (fx["name"], layer, got.shape, want.shape)
         differ = got.astype(np.float64) != want                   # as numbers: -0 == 0; a NaN differs
+        if fx.get("nonfinite_ok"):                                # the f16ovf fixtures only: NaN at the same place is equal (inf of
+            differ &= ~(np.isnan(got) & np.isnan(want))           # the same sign already is: inf == inf, inf != -inf)
         n = int(differ.sum())
         REPORT["cases"].append(dict(case=case, dtype=dtype, frame=list(shape), fixture=fx["name"], layer=layer, variant=variant,
                                     compared=int(want.size), differing=n))
@@ -124,7 +138,7 @@ def _layers_in(eng, fx):
     return out
 
 
-_CASES = [(dtype, shape, fx) for dtype in ec.DTYPES for shape in ec.FRAMES for fx in ec.FIXTURES]
+_CASES = [(dtype, shape, fx) for dtype in ec.DTYPES for shape in ec.FRAMES for fx in ec.ALL_EXACT]
 
 
 @pytest.mark.parametrize("dtype,shape,fx", _CASES, ids=["%s-b%d-%s" % (d, s[0], f["name"]) for d, s, f in _CASES])
@@ -140,13 +154,18 @@ def _row_id(r, dtype):
     return "%s-%s-%s-%s" % (dtype, r["variant"], env or "default", r["layers"][0])
 
 
-_ROWS = [(r, dt) for r in vm.ROWS if r["variant"] != SKIPPED_VARIANT for dt in ([r["dtype"]] + (["fp16"] if r["dtype"] == "bf16" else []))]
+_ROWS = [(r, dt) for r in vm.ROWS if r["frame"] == vm.FRAME for dt in ([r["dtype"]] + (["fp16"] if r["dtype"] == "bf16" else []))]
 
 
-def test_only_the_workload_size_depthwise_row_is_left_out():
-    left = [r for r in vm.ROWS if r["variant"] == SKIPPED_VARIANT]
-    assert len(left) == 1 and left[0]["frame"] == (1, 720, 1280)
-    assert all(r["frame"] == vm.FRAME for r, _ in _ROWS) and vm.FRAME == ec.FRAMES[0]
+def test_no_variant_of_the_matrix_is_left_out():
+    """Every (variant, dtype) of the matrix runs here at the fixture frame; the only row at another size (the 720 x 1280 frame
+    at which the heuristic itself takes dw<px=2>: tests/test_kernel_variants.py) repeats a variant that a forced row has."""
+    assert vm.FRAME == ec.FRAMES[0]
+    ran = {(r["variant"], r["dtype"]) for r, _ in _ROWS}
+    assert ran == {(r["variant"], r["dtype"]) for r in vm.ROWS} and ("dw<px=2>", "fp32") in ran
+    other = [r for r in vm.ROWS if r["frame"] != vm.FRAME]
+    assert [(r["variant"], r["frame"]) for r in other] == [("dw<px=2>", (1, 720, 1280))]
+    assert {dt for r, dt in _ROWS if r["dtype"] == "bf16"} == {"bf16", "fp16"}
 
 
 @pytest.mark.parametrize("row,dtype", _ROWS, ids=[_row_id(r, dt) for r, dt in _ROWS])
@@ -161,3 +180,77 @@ def test_forced_variant_bit_for_bit(monkeypatch, row, dtype):
             check(_row_id(row, dtype), eng, fx, row["frame"], dtype, [layer], bad, expect_variant=want)
             ran += 1
     assert ran >= len(row["layers"]) and not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------------------ ELU below zero
+_ELU_REF = {}
+
+
+def elu_reference(fx, shape, dtype):
+    key = (fx["name"], shape, dtype)
+    if key not in _ELU_REF:
+        _ELU_REF[key] = ec.elu_reference(fx, shape, dtype)
+    return _ELU_REF[key]
+
+
+def check_elu(case, eng, fx, shape, dtype, layers, bad, expect=None):
+    """Load the ELU fixture and hold each of ``layers`` to ``ec.elu_expect``; ``expect`` = {layer: variant it must record}."""
+    x = ec.frame_of(shape)
+    ref = elu_reference(fx, shape, dtype)
+    idx = {l["name"]: l["index"] for l in eng.layers()}
+    eng.load_state_dict(ec.dense_sd(fx))
+    for layer in sorted(layers, key=lambda n: idx[n]):
+        got = eng.debug_layer_output(x, idx[layer])
+        variant = eng.layer_variant(idx[layer])
+        if expect and layer in expect and variant != expect[layer]:
+            bad.append((fx["name"], layer, "variant", variant, expect[layer]))
+        exp = ec.elu_expect(fx, ref, layer, dtype)
+        assert got.shape == exp["want"].shape, (fx["name"], layer, got.shape)
+        problems, ratio = ec.elu_compare(got, exp)
+        print("%s %s b%d %s %s [%s]: worst error / bound %.4f over %d negative operands" % (
+            case, dtype, shape[0], fx["name"], layer, variant, ratio, int(exp["neg"].sum())))
+        REPORT["elu"].append(dict(case=case, dtype=dtype, frame=list(shape), fixture=fx["name"], layer=layer, variant=variant,
+                                  negative_operands=int(exp["neg"].sum()), exact_elements=int((~exp["neg"]).sum()),
+                                  worst_error_over_bound=ratio, problems=problems))
+        worst = REPORT["elu_worst"].setdefault(dtype, {})
+        worst[str(variant)] = max(worst.get(str(variant), 0.0), ratio)
+        bad += [(fx["name"], layer, variant, p) for p in problems]
+
+
+_ELU_CASES = [(dtype, shape, fx) for dtype in ec.DTYPES for shape in ec.FRAMES for fx in ec.ELU_FIXTURES]
+
+
+@pytest.mark.parametrize("dtype,shape,fx", _ELU_CASES, ids=["%s-b%d-%s" % (d, s[0], f["name"]) for d, s, f in _ELU_CASES])
+def test_default_kernels_elu_below_zero(monkeypatch, dtype, shape, fx):
+    eng = default_engine(monkeypatch, dtype, fx["nref"])
+    bad = []
+    check_elu("default", eng, fx, shape, dtype, _layers_in(eng, fx), bad)
+    assert not bad, bad
+
+
+_ELU_ROWS = [(r, dt) for r, dt in _ROWS if any(l.startswith("cpm.trunk.") for l in r["layers"])]
+
+
+def test_elu_rows_cover_every_kernel_family_that_runs_the_cpm_trunk():
+    fam = {(r["family"], dt) for r, dt in _ELU_ROWS}
+    assert fam == {("dw", "fp32"), ("dw_tiled", "fp32"), ("dwpw", "fp32"), ("dwpw_bf16", "bf16"), ("dwpw_bf16", "fp16"),
+                   ("dwpw_tiled", "bf16"), ("dwpw_tiled", "fp16")}, fam
+    assert {r["variant"] for r, _ in _ELU_ROWS if r["family"] == "dw"} == {"dw<px=1>", "dw<px=2>"}
+
+
+@pytest.mark.parametrize("row,dtype", _ELU_ROWS, ids=[_row_id(r, dt) for r, dt in _ELU_ROWS])
+def test_forced_variant_elu_below_zero(monkeypatch, row, dtype):
+    eng = make_engine(monkeypatch, row["env"], dtype)
+    want = f16_twin(row["variant"]) if dtype == "fp16" else row["variant"]
+    bad, ran = [], 0
+    for layer in row["layers"]:
+        if not layer.startswith("cpm.trunk."):
+            continue
+        fixtures = ec.elu_fixtures_for(layer)
+        assert len(fixtures) == 2, layer
+        # behind a stand-alone depthwise the pointwise conv is a GEMM with an ELU epilogue of its own: read it as well
+        layers = [layer, layer[:-3] + ".pw"] if layer.endswith(".dw") else [layer]
+        for fx in fixtures:
+            check_elu(_row_id(row, dtype), eng, fx, row["frame"], dtype, layers, bad, expect={layer: want})
+            ran += 1
+    assert ran and not bad, bad

@@ -132,6 +132,28 @@ def test_every_instantiation_has_a_row_or_a_reason():
     assert not missing, "kernel configurations without a row in tests/variant_matrix.py: %s" % missing
 
 
+def test_per_thread_depthwise_forms_are_forced_at_the_default_frame():
+    """``LWP_DW_PX`` is parsed into ``Tuning`` and decides launch_dw's branch, and every dw_kernel<PX> has a row at the default
+    frame (PX = 2: forced by the switch, with an odd output width among its layers) next to the workload-size row."""
+    f32 = _src("net_kernels.hip")
+    assert re.search(r'geti\("LWP_DW_PX", &t\.dw_px\)', _body(f32, "Tuning tuning_from_env("))
+    assert "int dw_px = 0;" in _src("lwp_internal.h")
+    body = _body(f32, "hipError_t launch_dw(")
+    assert re.search(r"T\.dw_px == 1 \|\| T\.dw_px == 2 \? T\.dw_px == 2 :", body)
+    pxs = set(re.findall(r"hipLaunchKernelGGL\(dw_kernel<(\d+)>", body))
+    assert pxs == {"1", "2"}
+    rows = [r for r in vm.ROWS if r["family"] == "dw"]
+    for px in pxs:
+        at_frame = [r for r in rows if r["variant"] == "dw<px=%s>" % px and r["frame"] == vm.FRAME]
+        assert at_frame, px
+        assert all(r["env"].get("LWP_DW_TILED") == "0" and r["env"].get("LWP_FUSE_DWPW") == "0" for r in at_frame)
+    forced = [r for r in rows if r["variant"] == "dw<px=2>" and r["frame"] == vm.FRAME]
+    assert all(r["env"].get("LWP_DW_PX") == "2" for r in forced)
+    # widths of the default frame's maps (variant_matrix's header): model.1 has 75 columns, model.4 on 19
+    assert any(l in ("model.1.dw", "model.4.dw", "model.7.dw", "cpm.trunk.0.dw") for r in forced for l in r["layers"])
+    assert any(r["variant"] == "dw<px=2>" and r["frame"] == (1, 720, 1280) and "LWP_DW_PX" not in r["env"] for r in rows)
+
+
 def test_unreachable_entries_name_real_instantiations_with_reasons():
     inst = expected_instantiations()
     known = set(inst) | {v if isinstance(v, str) else v[0] for vs in inst.values() for v in vs}

@@ -81,8 +81,12 @@ _row("dw_tiled", dict(_DW, LWP_DW_CC="128"), "fp32", ["model.3.dw"], "dw_tiled<c
 _row("dw_tiled", dict(_DW, LWP_DW_CC="128"), "fp32", ["model.7.dw"], "dw_tiled<cc=128,s=1,d=2,ph=8>")
 _row("dw_tiled", dict(_DW, LWP_DW_CC="128", LWP_DW_PH="16"), "fp32", ["model.7.dw"], "dw_tiled<cc=128,s=1,d=2,ph=16>")
 _row("dw", {"LWP_FUSE_DWPW": "0", "LWP_DW_TILED": "0"}, "fp32", ["model.1.dw", "model.2.dw", "model.7.dw", "cpm.trunk.0.dw"], "dw<px=1>")
-# dw<px=2> has no switch: pixels * C / 4 >= 2^20 (one 720 x 1280 frame: model.1.dw is 360 x 640 x 32); backbone taps only
+# dw<px=2>: the heuristic takes it at pixels * C / 4 >= 2^20 (one 720 x 1280 frame: model.1.dw is 360 x 640 x 32; backbone taps
+# only), LWP_DW_PX=2 at every size.  At the default frame: Wo = 75 (model.1) and 19 (model.4 on) are odd, so the last thread of a
+# row stores one pixel of its pair; model.2 / model.4 have stride 2, model.7 dilation 2, cpm.trunk.0 ELU
 _row("dw", {"LWP_FUSE_DWPW": "0", "LWP_DW_TILED": "0"}, "fp32", ["model.1.dw", "model.3.dw"], "dw<px=2>", frame=(1, 720, 1280))
+_row("dw", {"LWP_FUSE_DWPW": "0", "LWP_DW_TILED": "0", "LWP_DW_PX": "2"}, "fp32",
+     ["model.1.dw", "model.2.dw", "model.4.dw", "model.7.dw", "cpm.trunk.0.dw"], "dw<px=2>")
 
 # ---------------------------------------------------------------- f32 fused depthwise + pointwise (launch_dwpw): DP_CASE(bm, waves)
 # waves per workgroup = cout / 32 unless LWP_DWPW_NW splits the columns: model.1 -> 2, model.2/3 + cpm.trunk -> 4, model.4/5 -> 8, model.6..11 -> 16
