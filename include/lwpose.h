@@ -546,12 +546,41 @@ int lwp_train_backward(lwp_handle h, const float* keypoint_maps, const float* pa
                        int batch_size, double loss_scale, int accumulate, float* grads_device, float* d_features_device,
                        float* d_backbone_device);
 
+/* ---- backward precision: the operand type of the two matrix products of the dense-conv gradients (data gradient and weight
+ *      gradient of every 1x1 / 3x3 conv: stage convs, the cpm's 1x1s, the backbone's folded pointwise matrices).  LWP_F32 (the
+ *      default) runs v_mfma_f32_16x16x4_f32 and gives the bits it always gave.  LWP_BF16 / LWP_F16 run
+ *      v_mfma_f32_16x16x32_{bf16,f16} on the SAME f32 arrays: the handle stays fp32, and so do the forward, the retained
+ *      activations, every gradient buffer, the parameters and the optimiser.  There is no 16-bit copy of anything in memory, so
+ *      nothing can go stale: a backward after lwp_stage_adam_step or lwp_load_weights reads the new weights.
+ *      Rounding points: each operand element is converted once, f32 -> 16 bits, round to nearest even, fp16 subnormals kept, while
+ *      it is staged into LDS: dZ after its multiplication by grad_scale, the retained input x, and the folded weight (the blob's
+ *      [tap][cout_pad][cin_pad] copy or the folded pointwise matrix).  Products are exact and are accumulated in f32; the
+ *      accumulator is multiplied by 1 / grad_scale before it is stored or added.  (LWP_F16: subnormal operands reach the MFMA
+ *      as normal numbers times 2^-10, in products of their own, because the instruction would add them with fewer bits.)
+ *      grad_scale is a power of two in [1, 2^24], so
+ *      both multiplications are exact; with LWP_F32 it must be 1.
+ *      What stays f32 and bit-identical to LWP_F32 mode for the same inputs: the pixel ranges (lwp_debug_backward_splits), the
+ *      partial-sum layout and the fixed-order reduction, the bias column sums (an f32 sum of the unrounded, unscaled dZ), the
+ *      accumulate / overwrite rules, the launch order; and every other kernel: depthwise gradients, the stem's weight gradient,
+ *      the element-wise kernels, the BatchNorm chain rule, the pointwise fold, the loss gradient.  No floating-point atomics:
+ *      the same inputs give the same bits.
+ *      A value whose scaled magnitude passes the format's largest number (65504 for LWP_F16) becomes infinite, as the IEEE
+ *      conversion does, and such infinities (or the NaNs they breed) reach the gradient array; a scaled value below the
+ *      format's smallest subnormal becomes zero.  Choosing or adapting grad_scale (dynamic loss scaling) is the caller's.
+ *      Out of scope: a 16-bit forward in training, a 16-bit optimiser, dynamic loss scaling.
+ *      The setting may change between any two calls and changes no layout.  It is honoured by lwp_stage_backward,
+ *      lwp_train_backward (all three scopes), lwp_profile_stage_backward and lwp_debug_conv_grad.
+ *      LWP_ERR_ARG with a message: a bf16 / fp16 handle, an unknown dtype, a grad_scale that is no power of two or outside
+ *      [1, 2^24], LWP_F32 with a grad_scale other than 1.  A refused call leaves the setting as it was. */
+int lwp_set_backward_precision(lwp_handle h, int dtype, double grad_scale);
+int lwp_get_backward_precision(lwp_handle h, int* dtype, double* grad_scale);
+
 /* ---- stage fine-tuning step: the reference's optimiser (train.py:41-55 and :106, torch.optim.Adam with its parameter groups)
  *      for the parameters lwp_stage_backward differentiates, and the refold / repack of the changed layers into the forward's
  *      weight blob, all on the handle's stream: train_forward -> stage_backward -> step lowers the loss with no host round
  *      trip and no second copy of the weights.  fp32 handles whose weights came through lwp_load_weights only.
- *      Out of scope: BatchNorm train mode (the running statistics never move), a
- *      16-bit optimiser, multi-GPU gradient reduction, amsgrad, loading torch's optimiser checkpoints.
+ *      Out of scope: BatchNorm train mode (the running statistics never move), a 16-bit forward in training, a
+ *      16-bit optimiser, dynamic loss scaling, multi-GPU gradient reduction, amsgrad, loading torch's optimiser checkpoints.
  *      lwp_stage_adam_group: the parameter group of gradient-spec entry `index` (no handle, no GPU): learning-rate multiplier
  *      and weight-decay flag: initial_stage conv weight x1 / on, conv bias x2 / off; refinement_stages conv weight x4 / on,
  *      conv bias x8 / off, BatchNorm weight x1 / off, BatchNorm bias x2 / off.

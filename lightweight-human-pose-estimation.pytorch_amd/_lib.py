@@ -16,6 +16,7 @@ TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM, "all": TRAIN_ALL}
 KEPT_OUTPUT, KEPT_DEPTHWISE, KEPT_NO_RESIDUAL = 0, 1, 2
 PAD_GRAPH, PAD_RAW = 0, 1
 PAD_MODES = {"graph": PAD_GRAPH, "raw": PAD_RAW}
+BACKWARD_PRECISIONS = {"fp32": F32, "bf16": BF16, "fp16": F16}
 
 EXPORTS = [
     "lwp_version", "lwp_param_count", "lwp_param_spec", "lwp_create", "lwp_destroy", "lwp_last_error",
@@ -46,6 +47,7 @@ EXPORTS = [
     "lwp_coco_rows", "lwp_coco_finish", "lwp_debug_coco_rows",
     "lwp_jpeg_info", "lwp_debug_jpeg_blocks", "lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch",
     "lwp_set_jpeg_entropy", "lwp_debug_jpeg_entropy_batch", "lwp_debug_jpeg_scan", "lwp_time_jpeg_entropy_batch",
+    "lwp_set_backward_precision", "lwp_get_backward_precision",
 ]
 
 
@@ -204,6 +206,8 @@ def lib():
     L.lwp_debug_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(vp), C.POINTER(vp), ip]
     L.lwp_debug_jpeg_scan.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, ip]
     L.lwp_time_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_int, fp, ip]
+    L.lwp_set_backward_precision.argtypes = [vp, C.c_int, C.c_double]
+    L.lwp_get_backward_precision.argtypes = [vp, ip, dp]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

@@ -6,13 +6,14 @@
 //   wgrad   dW[tap][o][ci] = sum_p dZ[p][o] * X[p + off(tap)][ci]            M = cout, N = cin, K = pixels (split over workgroups)
 // A workgroup is 4 waves on a 64 x 64 output tile: wave w owns rows 16w .. 16w + 15 and four 16 x 16 accumulators (independent
 // chains, so the 40-cycle dependent latency of the instruction is covered).  Operand tiles go through LDS, 16 deep.
+// lwp_set_backward_precision puts dgrad and wgrad on v_mfma_f32_16x16x32_{bf16,f16} instead (dgrad_h16_kernel, wgrad_h16_kernel
+// below: the same arrays, tiles, ranges and partials, operands rounded on their way into LDS); everything else stays f32.
 // No floating-point atomics anywhere: wgrad writes per-split partial sums and a second kernel adds them in split order, so the
 // same inputs give the same bits.
 #include "lwp_internal.h"
+#include "h16.h"
 
 namespace lwp {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------- loss gradient
 // dL/d out = loss_scale * (out - target) * mask^2 / batch_size (modules/loss.py differentiated); targets NCHW, out and gradient NHWC
@@ -141,16 +142,169 @@ __global__ void __launch_bounds__(256) dgrad_kernel(DgradParams p) {
     }
 }
 
-hipError_t launch_dgrad(const DgradParams& p, hipStream_t s) {
+// ---------------------------------------------------------------------------------------- 16-bit operands (lwp_set_backward_precision)
+// The same tiles, grids, windows and pixel ranges on v_mfma_f32_16x16x32_{bf16,f16}: lane l holds A[i = l & 15][k = 8 (l >> 4) .. + 7]
+// and B[k = 8 (l >> 4) .. + 7][j = l & 15], C as above.  The operands stay f32 in memory; each is rounded once, (T)v, on its way
+// into LDS, dZ after its multiplication by grad_scale; the f32 accumulator is multiplied by 1 / grad_scale before it is stored or
+// added (both exact: the scale is a power of two).  A stage is 32 deep.  Both LDS tiles are [64 rows][32 k] of 16 bits, k along the
+// row whatever the operand's order in memory: thread t stages row t >> 2, k = 8 (t & 3) .. + 7, eight dword loads (along the
+// memory row where k runs along it: dgrad's dZ; one per memory row where k runs across: dgrad's W, both operands of wgrad) and
+// one 16-byte LDS store, so the transposition costs nothing beyond the address.  A lane then reads its 8 k with one ds_read_b128.
+// Rows are 64 bytes, four 16-byte chunks; chunk q of row r sits at q ^ f(r >> 2 & 3), f = (0, 2, 3, 1): the 16 lanes a
+// ds_read_b128 serves together ({0-3, 12-15, 20-27}, ...: eight rows at one chunk, eight at its neighbour) then fall on 16
+// different 16-byte slots of the 256-byte bank row, and the 8 lanes of a store (two rows, four chunks) on 128 contiguous bytes.
+constexpr int BH_K = 32;
+__device__ __forceinline__ int bh_at(int row, int q) { return row * BH_K + 8 * (q ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)); }
+template <typename T> __device__ __forceinline__ void bh_store(T* tile, int row, int q, const float (&v)[8]) {
+    typename H16<T>::x8 h;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) h[j] = (T)v[j];
+    *(typename H16<T>::x8*)(tile + bh_at(row, q)) = h;
+}
+// fp16 subnormals.  The MFMA aligns its 32 products to the largest NOMINAL exponent, a subnormal operand counting with the
+// exponent field of 2^-14, and keeps 24 bits below that: a product with a subnormal operand loses as many bits as the operand
+// has leading zeros (measured: DESIGN 3q).  So a stage whose tiles hold a subnormal (bh_subnormal, or-ed over the workgroup by the
+// stage's second barrier) runs four products instead of one: each fragment is split into its normal elements and its subnormal
+// ones times 2^10 (exact: m 2^-24 -> m 2^-14, now normal), normal x normal goes to the accumulator, the two mixed products to a
+// second one that stands for 2^-10 of its value, subnormal x subnormal to a third (2^-20).  The same operands, the same exact
+// products, no further rounding point; a stage without subnormals (every stage of the integer fixtures) runs as before.  bf16's
+// subnormals lie below 2^-126, where the f32 operands are subnormal themselves: no split there.
+template <typename T> struct H16Split { static constexpr bool on = false; };
+template <> struct H16Split<_Float16> { static constexpr bool on = true; };
+template <typename T> __device__ __forceinline__ int bh_subnormal(const float (&v)[8]) {
+    if constexpr (!H16Split<T>::on) return 0;
+    int any = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float a = fabsf((float)(T)v[j]);
+        any |= (a != 0.0f && a < 6.103515625e-05f) ? 1 : 0;      // below 2^-14
+    }
+    return any;
+}
+template <typename X8> __device__ __forceinline__ void bh_split(const X8& v, X8& normal, X8& sub) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const _Float16 h = v[j];
+        const bool s = (__builtin_bit_cast(unsigned short, h) & 0x7C00) == 0;      // exponent field 0: a subnormal or a zero
+        normal[j] = s ? (_Float16)0 : h;
+        sub[j] = s ? h * (_Float16)1024 : (_Float16)0;
+    }
+}
+// one stage of a wave's four 16 x 16 tiles: a and the four b fragments come from LDS
+template <typename T> __device__ __forceinline__ void bh_products(const T* As, const T* Bs, int wv, int lane, int sub, f32x4 (&acc)[4],
+                                                                 f32x4 (&acc1)[4], f32x4 (&acc2)[4]) {
+    typedef typename H16<T>::x8 x8;
+    const x8 a = *(const x8*)(As + bh_at(16 * wv + (lane & 15), lane >> 4));
+    if constexpr (H16Split<T>::on) {
+        if (sub) {
+            x8 an, as;
+            bh_split(a, an, as);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x8 bn, bs;
+                bh_split(*(const x8*)(Bs + bh_at(16 * j + (lane & 15), lane >> 4)), bn, bs);
+                acc[j] = H16<T>::mfma16(an, bn, acc[j]);
+                acc1[j] = H16<T>::mfma16(as, bn, acc1[j]);
+                acc1[j] = H16<T>::mfma16(an, bs, acc1[j]);
+                acc2[j] = H16<T>::mfma16(as, bs, acc2[j]);
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = H16<T>::mfma16(a, *(const x8*)(Bs + bh_at(16 * j + (lane & 15), lane >> 4)), acc[j]);
+}
+// the value of an accumulator element: acc + 2^-10 acc1 + 2^-20 acc2 (the last two are zero without the split)
+template <typename T> __device__ __forceinline__ float bh_value(float a, float a1, float a2) {
+    if constexpr (H16Split<T>::on) return (a + a1 * 0.0009765625f) + a2 * 9.5367431640625e-07f;
+    return a;
+}
+
+template <typename T> __global__ void __launch_bounds__(256) dgrad_h16_kernel(DgradParams p, float scale, float inv_scale) {
+    __shared__ __attribute__((aligned(16))) T As[BW_T * BH_K];      // [pixel][cout channel]
+    __shared__ __attribute__((aligned(16))) T Bs[BW_T * BH_K];      // [cin channel][cout channel]
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int HW = p.H * p.W;
+    const int64_t M = (int64_t)p.N * HW;
+    const int64_t m0 = (int64_t)blockIdx.x * BW_T;
+    const int ci0 = blockIdx.y * BW_T;
+    const int row = t >> 2, q = t & 3;
+    const int64_t am = m0 + row;
+    const bool a_in = am < M;
+    int an = 0, ay = 0, ax = 0;
+    if (a_in) { an = (int)(am / HW); const int r = (int)(am % HW); ay = r / p.W; ax = r % p.W; }
+    const bool b_in = ci0 + row < p.cin;
+    f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    f32x4 acc1[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}, acc2[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    const int half = p.ks / 2;
+    for (int tap = 0; tap < p.ks * p.ks; ++tap) {
+        const int sy = ay - (tap / p.ks - half) * p.dil, sx = ax - (tap % p.ks - half) * p.dil;
+        const bool a_ok = a_in && sy >= 0 && sy < p.H && sx >= 0 && sx < p.W;
+        const float* arow_ptr = p.dz + ((int64_t)an * HW + (int64_t)sy * p.W + sx) * p.dz_ld;
+        const float* wt = p.w + (size_t)tap * p.cout_pad * p.cin_pad + ci0 + row;
+        for (int o0 = 0; o0 < p.cout; o0 += BH_K) {
+            float av[8], bv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int o = o0 + 8 * q + j;
+                av[j] = (a_ok && o < p.cout) ? arow_ptr[o] * scale : 0.0f;
+                bv[j] = (b_in && o < p.cout) ? wt[(size_t)o * p.cin_pad] : 0.0f;
+            }
+            __syncthreads();
+            bh_store(As, row, q, av);
+            bh_store(Bs, row, q, bv);
+            const int sub = H16Split<T>::on ? __syncthreads_or(bh_subnormal<T>(av) | bh_subnormal<T>(bv)) : (__syncthreads(), 0);
+            bh_products<T>(As, Bs, wv, lane, sub, acc, acc1, acc2);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ci = ci0 + 16 * j + (lane & 15);
+        if (ci >= p.cin) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t m = m0 + 16 * wv + 4 * (lane >> 4) + r;
+            if (m >= M) continue;
+            float* d = p.dx + m * p.dx_ld + ci;
+            const float v = bh_value<T>(acc[j][r], acc1[j][r], acc2[j][r]) * inv_scale;
+            *d = ci >= p.acc_from ? *d + v : v;
+        }
+    }
+}
+
+static bool bwd_precision_ok(const BwdPrecision& bp) {
+    return bp.dtype == LWP_F32 ? bp.scale == 1.0f : ((bp.dtype == LWP_BF16 || bp.dtype == LWP_F16) && bp.scale >= 1.0f && bp.scale <= 16777216.0f);
+}
+
+hipError_t launch_dgrad(const DgradParams& p, hipStream_t s, BwdPrecision bp) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
     if (M < 1 || M >= (1ll << 31) - BW_T || p.cout < 1 || p.cin < 1 || p.cout > p.cout_pad || p.cin > p.cin_pad || (p.cin_pad & 3) ||
-        (p.cout_pad % BW_K) || (p.ks != 1 && p.ks != 3))
+        (p.cout_pad % BW_K) || (p.ks != 1 && p.ks != 3) || !bwd_precision_ok(bp))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dgrad_kernel, dim3((unsigned)((M + BW_T - 1) / BW_T), (unsigned)((p.cin + BW_T - 1) / BW_T)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)((M + BW_T - 1) / BW_T), (unsigned)((p.cin + BW_T - 1) / BW_T));
+    if (bp.dtype == LWP_BF16) hipLaunchKernelGGL(dgrad_h16_kernel<__bf16>, grid, dim3(256), 0, s, p, bp.scale, 1.0f / bp.scale);
+    else if (bp.dtype == LWP_F16) hipLaunchKernelGGL(dgrad_h16_kernel<_Float16>, grid, dim3(256), 0, s, p, bp.scale, 1.0f / bp.scale);
+    else hipLaunchKernelGGL(dgrad_kernel, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------- weight and bias gradient
+// bias: db[o] = sum over the split's pixels of dZ[p][o]; 4 pixel lanes per channel, added in lane order (red: 256 floats of LDS).
+// The 16-bit kernel runs the same statement: the column sums read the unrounded, unscaled dZ in either mode.
+__device__ __forceinline__ void wgrad_bias_sums(const WgradParams& p, float* red, int o0, int z, int64_t p_begin, int64_t p_end) {
+    const int t = threadIdx.x, c = t & 63, pl = t >> 6;
+    const int co_p = wgrad_pad64(p.cout), ci_p = wgrad_pad64(p.cin);
+    float sum = 0.0f;
+    if (o0 + c < p.cout)
+        for (int64_t px = p_begin + pl; px < p_end; px += 4) sum += p.dz[px * p.dz_ld + o0 + c];
+    red[pl * 64 + c] = sum;
+    __syncthreads();
+    if (t < 64) {
+        float* bpart = p.partial + (size_t)p.splits * p.ks * p.ks * co_p * ci_p;
+        bpart[(size_t)z * co_p + o0 + t] = ((red[t] + red[64 + t]) + red[128 + t]) + red[192 + t];
+    }
+}
+
 // grid: x = cout tiles x cin tiles, y = tap (+ one extra row of workgroups for the bias column sums), z = pixel split
 __global__ void __launch_bounds__(256) wgrad_kernel(WgradParams p) {
     __shared__ float As[BW_K * BW_BPAD];      // [pixel][cout channel]
@@ -166,18 +320,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradParams p) {
     const int64_t p_begin = (int64_t)z * p.chunk;
     const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
     if (tap == taps) {
-        // bias: db[o] = sum over the split's pixels of dZ[p][o]; 4 pixel lanes per channel, added in lane order
-        if (c0 != 0) return;
-        const int c = t & 63, pl = t >> 6;
-        float sum = 0.0f;
-        if (o0 + c < p.cout)
-            for (int64_t px = p_begin + pl; px < p_end; px += 4) sum += p.dz[px * p.dz_ld + o0 + c];
-        As[pl * 64 + c] = sum;
-        __syncthreads();
-        if (t < 64) {
-            float* bpart = p.partial + (size_t)p.splits * taps * co_p * ci_p;
-            bpart[(size_t)z * co_p + o0 + t] = ((As[t] + As[64 + t]) + As[128 + t]) + As[192 + t];
-        }
+        if (c0 == 0) wgrad_bias_sums(p, As, o0, z, p_begin, p_end);
         return;
     }
     const int half = p.ks / 2;
@@ -231,13 +374,71 @@ void wgrad_plan(int64_t M, int cout, int cin, int ks, int* splits, int* chunk) {
     *splits = (int)((M + ch - 1) / ch);
 }
 
-hipError_t launch_wgrad(const WgradParams& p, hipStream_t s) {
+// wgrad_kernel's grid, ranges and partial layout on 16-bit operands (the rules are above dgrad_h16_kernel).  K is the pixel axis,
+// across the memory rows of both operands; a range need not be a multiple of the 32-deep stage (pixels past p_end are zeros).
+template <typename T> __global__ void __launch_bounds__(256) wgrad_h16_kernel(WgradParams p, float scale, float inv_scale) {
+    __shared__ __attribute__((aligned(16))) T As[BW_T * BH_K];      // [cout channel][pixel]
+    __shared__ __attribute__((aligned(16))) T Bs[BW_T * BH_K];      // [cin channel][pixel]
+    __shared__ float red[256];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int taps = p.ks * p.ks;
+    const int co_p = wgrad_pad64(p.cout), ci_p = wgrad_pad64(p.cin);
+    const int ci_t = ci_p / BW_T;
+    const int o0 = (blockIdx.x / ci_t) * BW_T, c0 = (blockIdx.x % ci_t) * BW_T;
+    const int tap = blockIdx.y, z = blockIdx.z;
+    const int HW = p.H * p.W;
+    const int64_t M = (int64_t)p.N * HW;
+    const int64_t p_begin = (int64_t)z * p.chunk;
+    const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
+    if (tap == taps) {
+        if (c0 == 0) wgrad_bias_sums(p, red, o0, z, p_begin, p_end);
+        return;
+    }
+    const int half = p.ks / 2;
+    const int dy = (tap / p.ks - half) * p.dil, dx = (tap % p.ks - half) * p.dil;
+    const int row = t >> 2, q = t & 3;
+    const bool a_in = o0 + row < p.cout, b_in = c0 + row < p.cin;
+    const float* zc = p.dz + o0 + row;
+    const float* xc = p.x + c0 + row;
+    f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    f32x4 acc1[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}, acc2[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    for (int64_t px0 = p_begin; px0 < p_end; px0 += BH_K) {
+        const int64_t pf = px0 + 8 * q;                 // this thread's first pixel of the stage; (n, y, x) walks on from it
+        int n = 0, y = 0, x = 0;
+        if (pf < p_end) { n = (int)(pf / HW); const int r = (int)(pf % HW); y = r / p.W; x = r % p.W; }
+        float av[8], bv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool in = pf + j < p_end;
+            const int sy = y + dy, sx = x + dx;
+            av[j] = (in && a_in) ? zc[(pf + j) * p.dz_ld] * scale : 0.0f;
+            bv[j] = (in && b_in && sy >= 0 && sy < p.H && sx >= 0 && sx < p.W) ? xc[((int64_t)n * HW + (int64_t)sy * p.W + sx) * p.x_ld] : 0.0f;
+            if (++x == p.W) { x = 0; if (++y == p.H) { y = 0; ++n; } }
+        }
+        __syncthreads();
+        bh_store(As, row, q, av);
+        bh_store(Bs, row, q, bv);
+        const int sub = H16Split<T>::on ? __syncthreads_or(bh_subnormal<T>(av) | bh_subnormal<T>(bv)) : (__syncthreads(), 0);
+        bh_products<T>(As, Bs, wv, lane, sub, acc, acc1, acc2);
+    }
+    float* part = p.partial + (((size_t)z * taps + tap) * co_p + o0) * ci_p + c0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            part[(size_t)(16 * wv + 4 * (lane >> 4) + r) * ci_p + 16 * j + (lane & 15)] = bh_value<T>(acc[j][r], acc1[j][r], acc2[j][r]) * inv_scale;
+}
+
+hipError_t launch_wgrad(const WgradParams& p, hipStream_t s, BwdPrecision bp) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
     if (M < 1 || M >= (1ll << 31) - BW_T || p.cout < 1 || p.cin < 1 || (p.ks != 1 && p.ks != 3) || p.splits < 1 || p.splits > 65535 ||
-        p.chunk < BW_K || (p.chunk % BW_K) || (int64_t)p.splits * p.chunk < M)
+        p.chunk < BW_K || (p.chunk % BW_K) || (int64_t)p.splits * p.chunk < M || !bwd_precision_ok(bp))
         return hipErrorInvalidValue;
     const unsigned tiles = (unsigned)((wgrad_pad64(p.cout) / BW_T) * (wgrad_pad64(p.cin) / BW_T));
-    hipLaunchKernelGGL(wgrad_kernel, dim3(tiles, (unsigned)(p.ks * p.ks + (p.no_bias ? 0 : 1)), (unsigned)p.splits), dim3(256), 0, s, p);
+    const dim3 grid(tiles, (unsigned)(p.ks * p.ks + (p.no_bias ? 0 : 1)), (unsigned)p.splits);
+    if (bp.dtype == LWP_BF16) hipLaunchKernelGGL(wgrad_h16_kernel<__bf16>, grid, dim3(256), 0, s, p, bp.scale, 1.0f / bp.scale);
+    else if (bp.dtype == LWP_F16) hipLaunchKernelGGL(wgrad_h16_kernel<_Float16>, grid, dim3(256), 0, s, p, bp.scale, 1.0f / bp.scale);
+    else hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

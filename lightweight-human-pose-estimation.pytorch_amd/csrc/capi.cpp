@@ -121,6 +121,7 @@ struct lwp_context {
     bool raw_loaded = false;                         // false after lwp_weights_blob_import: a blob holds folded weights only
     DevBuf d_bwd; size_t bwd_fold_off = 0;           // wgrad partials, then the folded gradients of one BatchNorm layer,
     size_t bwd_pw_off = 0;                           // then (LWP_TRAIN_ALL) the folded pointwise matrix of one fused backbone block
+    BwdPrecision bwd_prec;                           // lwp_set_backward_precision: operand type and dZ scale of dgrad / wgrad
     std::vector<int> bwd_splits;                     // per layer: pixel splits its last wgrad ran with
     std::vector<int> bwd_dw_splits;                  // per layer: pixel splits of its last depthwise wgrad (L_DW, L_DWPW)
     std::vector<DwRepack> dw_repack;                 // the depthwise / fused layers of the repack: the cpm trunk's, the backbone's (LWP_TRAIN_ALL)
@@ -256,7 +257,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 106; }
+extern "C" int lwp_version(void) { return 107; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -3949,7 +3950,7 @@ static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const 
     w.no_bias = (has_bias || !bn_key.empty()) ? 0 : 1;     // the BatchNorm chain rule needs the column sums of dZ, conv bias or not
     wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, w.ks, &w.splits, &w.chunk);
     h->bwd_splits[layer_index] = w.splits;
-    LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream));
+    LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream, h->bwd_prec));
     float* dw = a.grads + h->grad_off.at(conv_key + ".weight");
     float* db = has_bias ? a.grads + h->grad_off.at(conv_key + ".bias") : nullptr;
     if (bn_key.empty()) {
@@ -4060,7 +4061,7 @@ static int enqueue_backbone_backward(lwp_context* h, const Layer& l, int i, cons
         if (rc) return rc;
         d.w = h->blob(l.w_off); d.cout_pad = l.cout_pad; d.cin_pad = l.cin_pad;
         d.dx = grad_at(h, l.src); d.dx_ld = l.src.ld; d.acc_from = written[l.src.buf - nb] ? 0 : l.cin;
-        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
         written[l.src.buf - nb] = 1;
         return LWP_OK;
     }
@@ -4075,7 +4076,7 @@ static int enqueue_backbone_backward(lwp_context* h, const Layer& l, int i, cons
                                              l.cout, l.cin, h->stream));
     d.w = wf; d.cout_pad = l.cout; d.cin_pad = l.cin;
     d.dx = gd; d.dx_ld = l.cin; d.acc_from = l.cin;
-    LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+    LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
     LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(gd, l.cin, dcopy, l.cin, nullptr, 0, M, l.cin, h->stream));
     return enqueue_dw_sd_backward(h, l, i, gd, l.cin, al, written);
 }
@@ -4150,7 +4151,7 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
             d.dx = gd; d.dx_ld = l.cin;
             d.N = a.N; d.H = a.hs; d.W = a.ws;
             d.cout = l.cout; d.cout_pad = l.cout; d.cin = l.cin; d.cin_pad = l.cin; d.ks = 1; d.dil = 1; d.acc_from = l.cin;
-            LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+            LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
             rc = enqueue_dw_backward(h, l, i, gd, l.cin, dcopy, l.cin, a, written);
             if (rc) { h->cur_layer = -1; return rc; }
             continue;
@@ -4176,7 +4177,7 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
         d.cout = l.cout; d.cout_pad = l.cout_pad; d.cin = l.cin; d.cin_pad = l.cin_pad; d.ks = l.ks; d.dil = l.dil;
         // a concat buffer's heat / PAF channels already hold the stage's loss gradient; its feature channels are summed over the stages
         d.acc_from = written[l.src.buf - nb] ? 0 : (is_cat ? C : l.cin);
-        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream));
+        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
         written[l.src.buf - nb] = 1;
     }
     h->cur_layer = -1;
@@ -4232,6 +4233,26 @@ extern "C" int lwp_set_train_scope(lwp_handle h, int scope) {
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // the plan's buffers and the optimiser tables are released below
     apply_train_scope(h, scope);
+    return LWP_OK;
+}
+
+extern "C" int lwp_set_backward_precision(lwp_handle h, int dtype, double grad_scale) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (h->dtype != LWP_F32) return fail(h, LWP_ERR_ARG, "the backward precision belongs to fp32 handles only (this one is bf16 / fp16)");
+    if (dtype != LWP_F32 && dtype != LWP_BF16 && dtype != LWP_F16) return fail(h, LWP_ERR_ARG, "unknown backward precision (LWP_F32, LWP_BF16 or LWP_F16)");
+    int e = 0;
+    if (!(grad_scale >= 1.0 && grad_scale <= 16777216.0) || std::frexp(grad_scale, &e) != 0.5)
+        return fail(h, LWP_ERR_ARG, "grad_scale must be a power of two in [1, 2^24]");
+    if (dtype == LWP_F32 && grad_scale != 1.0) return fail(h, LWP_ERR_ARG, "grad_scale must be 1 with LWP_F32 (the fp32 kernels do not scale)");
+    h->bwd_prec.dtype = dtype;
+    h->bwd_prec.scale = (float)grad_scale;
+    return LWP_OK;
+}
+
+extern "C" int lwp_get_backward_precision(lwp_handle h, int* dtype, double* grad_scale) {
+    if (!h || !dtype || !grad_scale) return fail(h, LWP_ERR_ARG, "null argument");
+    *dtype = h->bwd_prec.dtype;
+    *grad_scale = (double)h->bwd_prec.scale;
     return LWP_OK;
 }
 
@@ -4431,9 +4452,9 @@ extern "C" int lwp_debug_conv_grad(lwp_handle h, const float* dz, int dz_ld, int
     DgradParams d{};
     d.dz = p.dz; d.dz_ld = dz_ld; d.w = wbuf.as<float>(); d.dx = dx + dx_off; d.dx_ld = dx_ld;
     d.N = N; d.H = H; d.W = W; d.cout = cout; d.cout_pad = cout_pad; d.cin = cin; d.cin_pad = cin_pad; d.ks = ks; d.dil = dil; d.acc_from = acc_from;
-    HIP_TRY(h, launch_wgrad(p, h->stream));
+    HIP_TRY(h, launch_wgrad(p, h->stream, h->bwd_prec));
     HIP_TRY(h, launch_wgrad_reduce(p, dw, db, accumulate ? 1 : 0, h->stream));
-    HIP_TRY(h, launch_dgrad(d, h->stream));
+    HIP_TRY(h, launch_dgrad(d, h->stream, h->bwd_prec));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *splits = p.splits;
     return LWP_OK;

@@ -597,7 +597,10 @@ struct DgradParams {
     float* dx; int dx_ld;            // M x cin; channels >= acc_from are added to, the others overwritten
     int N, H, W, cout, cout_pad, cin, cin_pad, ks, dil, acc_from;
 };
-hipError_t launch_dgrad(const DgradParams& p, hipStream_t s);
+// lwp_set_backward_precision: the operand type of the two MFMA products (LWP_F32: the f32 kernels) and the power of two dZ is
+// multiplied by in front of its rounding (the accumulator by its inverse)
+struct BwdPrecision { int dtype = LWP_F32; float scale = 1.0f; };
+hipError_t launch_dgrad(const DgradParams& p, hipStream_t s, BwdPrecision bp = BwdPrecision());
 struct WgradParams {
     const float* dz; int dz_ld;      // M x cout
     const float* x; int x_ld;        // M x cin, the layer's retained input
@@ -611,7 +614,7 @@ void wgrad_plan(int64_t M, int cout, int cin, int ks, int* splits, int* chunk);
 inline size_t wgrad_partial_floats(const WgradParams& p) {
     return (size_t)p.splits * wgrad_pad64(p.cout) * ((size_t)p.ks * p.ks * wgrad_pad64(p.cin) + 1);
 }
-hipError_t launch_wgrad(const WgradParams& p, hipStream_t s);
+hipError_t launch_wgrad(const WgradParams& p, hipStream_t s, BwdPrecision bp = BwdPrecision());
 // fixed-order sum of the partials into OIHW dw [cout][cin][taps] and db [cout]; accumulate: added to what is there
 hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int accumulate, hipStream_t s);
 // ---- cpm backward (with_mobilenet.py:7-21): ELU and depthwise 3x3 (stride 1, dilation 1, pad 1) gradients.  C is a multiple

@@ -14,8 +14,11 @@ layers into the forward's weight blob are HIP kernels behind ``lwp_stage_adam_st
         losses = val.train_step(net, opt, images, labels, masks)
     opt.lr = opt.lr * 0.333            # MultiStepLR (train.py:60) is a line of Python
 
-Out of scope: BatchNorm train mode (running statistics never move), a
-16-bit optimiser, multi-GPU gradient reduction, amsgrad, and torch's optimiser checkpoints (``state_dict`` below has its own
+``StageAdam(net, backward_precision="bf16")`` (or ``"fp16"``, with ``grad_scale`` a power of two) switches the engine's dense-conv
+gradients to 16-bit MFMA operands (``Engine.set_backward_precision``); the parameters, the moments and the step stay fp32.
+
+Out of scope: BatchNorm train mode (running statistics never move), no 16-bit forward in training, no 16-bit optimiser, no dynamic
+loss scaling, multi-GPU gradient reduction, amsgrad, and torch's optimiser checkpoints (``state_dict`` below has its own
 format, keyed by state-dict name; torch's is index-based and numbers the whole network).
 """
 from collections import OrderedDict
@@ -24,12 +27,16 @@ import numpy as np
 
 
 class StageAdam(object):
-    def __init__(self, net, base_lr=4e-5, weight_decay=5e-4, betas=(0.9, 0.999), eps=1e-8, scope="stages"):
+    def __init__(self, net, base_lr=4e-5, weight_decay=5e-4, betas=(0.9, 0.999), eps=1e-8, scope="stages", backward_precision=None,
+                 grad_scale=None):
         self.net = net
         from . import _lib
         self.scope = _lib.train_scope_name(scope)
         if net.engine.train_scope != self.scope:   # (refused once the engine's optimiser has taken a step: the moments have the old layout)
             net.engine.set_train_scope(self.scope)
+        if backward_precision is not None or grad_scale is not None:      # an argument left out keeps what the engine has
+            name, scale = net.engine.backward_precision
+            net.engine.set_backward_precision(name if backward_precision is None else backward_precision, scale if grad_scale is None else grad_scale)
         self.lr = float(base_lr)              # the base learning rate; the groups' multipliers are applied by the kernel
         self.weight_decay = float(weight_decay)
         self.betas = (float(betas[0]), float(betas[1]))

@@ -1006,6 +1006,22 @@ class Engine(object):
         check(lib().lwp_train_forward(self.h.ptr, x.data_ptr(), N, H, W, ptrs), self.h.ptr)
         return outs
 
+    def set_backward_precision(self, precision="fp32", grad_scale=1.0):
+        """The operand type of the dense-conv gradients' two MFMA products: ``"fp32"`` (the default: the f32 kernels and their
+        bits), ``"bf16"`` or ``"fp16"`` (include/lwpose.h, "backward precision").  dZ is multiplied by ``grad_scale``, a
+        power of two in [1, 2^24] (1 with "fp32"), in front of its rounding and the f32 accumulator by its inverse.  Everything
+        else, the engine included, stays fp32; the setting may change between any two calls.  ValueError for anything else."""
+        if precision not in _lib.BACKWARD_PRECISIONS:
+            raise ValueError("backward precision must be 'fp32', 'bf16' or 'fp16', not %r" % (precision,))
+        check(lib().lwp_set_backward_precision(self.h.ptr, _lib.BACKWARD_PRECISIONS[precision], float(grad_scale)), self.h.ptr)
+
+    @property
+    def backward_precision(self):
+        """(name, grad_scale) as the handle holds them."""
+        dt, sc = C.c_int(), C.c_double()
+        check(lib().lwp_get_backward_precision(self.h.ptr, C.byref(dt), C.byref(sc)), self.h.ptr)
+        return [k for k, v in _lib.BACKWARD_PRECISIONS.items() if v == dt.value][0], sc.value
+
     def set_train_scope(self, scope):
         """"stages" (the default): ``train_forward`` / ``stage_backward`` / ``adam_step`` cover initial_stage.* and
         refinement_stages.*; "cpm": the cpm (cpm.align, cpm.trunk, cpm.conv) as well, its ten parameters in front of the stage

@@ -12,6 +12,13 @@ default output is profiles/train/backward_bench_cpm.json.  --scope all trains th
 dilated depthwise gradients, the stem's weight gradient, BatchNorm chain rule); torch's autograd then starts at the image
 (tests/backbone_backward_cases.py) and the output is profiles/train/backward_bench_all.json.
 
+--precision bf16|fp16 [--grad-scale S] compares the backward's 16-bit mode (Engine.set_backward_precision) with fp32 mode instead:
+one engine, one process, alternating windows of --reps backwards each (fp32, 16-bit, fp32, ...), the median over --windows per
+mode of the per-class times, of the whole backward and of a step (train_forward + stage_backward + adam_step); the number of
+non-finite elements of the 16-bit gradient; and, from one torch-ROCm fp32 autograd pass over the same restatement, the share of
+the non-zero dZ elements of the dense convs that round to zero in the format at the scale.  Output:
+profiles/train/backward_bench_h16.json (nref 1 only).
+
 Writes one JSON file; there is no parent figure for this path, so nothing is compared."""
 import argparse
 import json
@@ -31,6 +38,7 @@ from lwpose_amd.runtime import Engine  # noqa: E402
 
 import backward_cases as bc  # noqa: E402
 import backbone_backward_cases as bb  # noqa: E402
+import backward_h16_cases as hc  # noqa: E402
 import cpm_backward_cases as cc  # noqa: E402
 
 
@@ -83,6 +91,65 @@ def one(nref, batch, size, reps, scope="stages"):
     return res
 
 
+def h16_compare(nref, batch, size, reps, scope, precision, scale, windows):
+    eng = Engine(0, nref=nref)
+    eng.set_train_scope(scope)
+    sd = synth.make_state_dict(nref, seed=1)
+    eng.load_state_dict(sd)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.rand((batch, 3, size, size), device="cuda", generator=g) - 0.5
+    hs = size // 8
+    km = torch.rand((batch, 19, hs, hs), device="cuda", generator=g)
+    pm = torch.rand((batch, 38, hs, hs), device="cuda", generator=g) - 0.5
+    mask = (torch.rand((batch, hs, hs), device="cuda", generator=g) > 0.1).float()
+    res = dict(nref=nref, batch=batch, size=size, reps=reps, windows=windows, scope=scope, precision=precision, grad_scale=scale)
+    eng.train_forward(x)
+    modes = (("fp32", 1.0), (precision, scale))
+    # the gradient and the dZ statistics first: the timed steps below move the weights
+    eng.set_backward_precision(precision, scale)
+    flat = eng.flat_of(eng.stage_backward(km, pm, mask)[0])
+    res["gradient_elements"] = int(flat.numel())
+    res["nonfinite_gradient_elements"] = int((~torch.isfinite(flat)).sum())
+    cpm, whole = scope != "stages", scope == "all"
+    first = [i["index"] for i in eng.layers() if i["name"] == ("cpm.align" if cpm else "cpm.conv")][0] - (1 if cpm else 0)
+    feat = x if whole else torch.from_numpy(eng.train_activation(first)).cuda()
+    p = {k: v.cuda().requires_grad_(v.is_floating_point() and "running_" not in k) for k, v in sd.items()}
+    keys = bb.grad_keys(p) if whole else cc.grad_keys(p) if cpm else bc.grad_keys(p)
+    sim = hc.Sim("fp32", scale, count_as=precision)
+    with hc.installed(sim):
+        f = feat.detach().requires_grad_(not whole)
+        if whole:
+            f = bb.backbone(p, f)
+        total = bc.loss(bc.stages(p, cc.cpm(p, f) if cpm else f, nref), km, pm, mask, batch)
+        torch.autograd.grad(total, [p[k] for k in keys])
+    res["dz_max"] = sim.stats["max_dz"]
+    res["dz_nonzero"] = sim.stats["nonzero"]
+    res["dz_rounded_to_zero_share"] = sim.stats["flushed"] / max(1, sim.stats["nonzero"])
+    del p, f, total
+
+    def step():
+        eng.train_forward(x)
+        eng.adam_step(eng.flat_of(eng.stage_backward(km, pm, mask)[0]), 4e-5, (0.9, 0.999), 1e-8, 5e-4)
+    names = ("elementwise", "dgrad", "wgrad", "reduce")
+    samples = dict((m[0], dict(backward=[], step=[], classes=dict((n, []) for n in names))) for m in modes)
+    for _ in range(windows):
+        for name, sc in modes:
+            eng.set_backward_precision(name, sc)
+            eng.train_forward(x)
+            samples[name]["backward"].append(timed(lambda: eng.stage_backward(km, pm, mask), reps))
+            cls = eng.profile_stage_backward(km, pm, mask, reps=reps)
+            for n in names:
+                samples[name]["classes"][n].append(cls[n]["ms"])
+            samples[name]["step"].append(timed(step, reps))
+    med = lambda v: float(np.median(v))
+    for name, _ in modes:
+        sm = samples[name]
+        res[name] = dict(stage_backward_ms=med(sm["backward"]), step_ms=med(sm["step"]), backward_classes_ms=dict((n, med(sm["classes"][n])) for n in names),
+                         stage_backward_ms_windows=sm["backward"])
+    eng.set_backward_precision("fp32", 1.0)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=80)
@@ -90,7 +157,19 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--scope", choices=("stages", "cpm", "all"), default="stages")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precision", choices=("fp32", "bf16", "fp16"), default="fp32")
+    ap.add_argument("--grad-scale", type=float, default=1.0)
+    ap.add_argument("--windows", type=int, default=5)
     a = ap.parse_args()
+    if a.precision != "fp32":
+        a.out = a.out or os.path.join(ROOT, "profiles", "train", "backward_bench_h16.json")
+        out = dict(device=torch.cuda.get_device_properties(0).gcnArchName,
+                   runs=[h16_compare(1, a.batch, a.size, a.reps, a.scope, a.precision, a.grad_scale, a.windows)])
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+        print(json.dumps(out))
+        return
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "train", "backward_bench.json" if a.scope == "stages" else "backward_bench_%s.json" % a.scope)
     out = dict(device=torch.cuda.get_device_properties(0).gcnArchName, runs=[one(n, a.batch, a.size, a.reps, a.scope) for n in (1, 3)])
