@@ -384,6 +384,18 @@ int lwp_train_targets(lwp_handle h, const double* kpts, int kpts_mem, const int*
 int lwp_mask_downsample(lwp_handle h, const float* mask, int mem, int N, int H, int W, int stride, float* out_device);
 int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
                      const float* mask, int N, int hs, int ws, int batch_size, double* losses_host);
+/* ---- the loss log: train.py:78,96-97,112-119's total_losses on the device.  lwp_stage_losses_log takes lwp_stage_losses'
+ *      arguments with `divisor` in place of losses_host: it enqueues the same launches on the handle's stream and, in the kernel
+ *      that forms the S = 2 * (num_refinement_stages + 1) sums, log[i] += losses[i] / divisor in float64, one thread per entry, in
+ *      launch order, without atomics; the call is counted in an add count.  With more than 16 tensors there are two launches and
+ *      each adds its own range.  It returns WITHOUT a host wait (the one wait left is that of a growing partials buffer, as in
+ *      lwp_stage_losses); under lwp_set_stream the caller's stream is ordered behind the launches, otherwise the caller keeps the
+ *      tensors untouched until a call that waits.  The log belongs to the handle and is zero at creation.  Checks: those of
+ *      lwp_stage_losses, and divisor finite and > 0 (LWP_ERR_ARG).
+ *      lwp_loss_log_read waits for the stream and copies the S sums and the add count; reset != 0 zeroes both behind the copy. */
+int lwp_stage_losses_log(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
+                         const float* mask, int N, int hs, int ws, int batch_size, double divisor);
+int lwp_loss_log_read(lwp_handle h, double* sums_host, int64_t* adds, int reset);
 /* the kernels of the two calls alone (tools/targets_bench.py): the same arguments and checks, one upload, then `iters`
  * back-to-back launches between two HIP events on the handle's stream, with no per-call synchronise and no copy-back of the
  * sums.  ms_total out. */

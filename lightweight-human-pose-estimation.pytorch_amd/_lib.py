@@ -48,6 +48,7 @@ EXPORTS = [
     "lwp_jpeg_info", "lwp_debug_jpeg_blocks", "lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch",
     "lwp_set_jpeg_entropy", "lwp_debug_jpeg_entropy_batch", "lwp_debug_jpeg_scan", "lwp_time_jpeg_entropy_batch",
     "lwp_set_backward_precision", "lwp_get_backward_precision",
+    "lwp_stage_losses_log", "lwp_loss_log_read",
 ]
 
 
@@ -208,6 +209,8 @@ def lib():
     L.lwp_time_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_int, fp, ip]
     L.lwp_set_backward_precision.argtypes = [vp, C.c_int, C.c_double]
     L.lwp_get_backward_precision.argtypes = [vp, ip, dp]
+    L.lwp_stage_losses_log.argtypes = L.lwp_stage_losses.argtypes[:-1] + [C.c_double]
+    L.lwp_loss_log_read.argtypes = [vp, dp, i64p, C.c_int]
     for name in EXPORTS:
         if name not in ("lwp_last_error",):
             getattr(L, name).restype = C.c_int

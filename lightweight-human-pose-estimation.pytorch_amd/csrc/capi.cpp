@@ -101,6 +101,8 @@ struct lwp_context {
     // training targets and loss (lwp_train_targets / lwp_mask_downsample / lwp_stage_losses): staging of host key-points, person
     // counts and host masks; the loss partials followed by the per-stage sums
     DevBuf d_train, d_loss;
+    // the running loss log of lwp_stage_losses_log / lwp_loss_log_read: S doubles and, behind them, the int64 add count
+    DevBuf d_loss_log;
     // training augmentation (lwp_augment_batch): [plan records | host images and masks], packed on the host, one upload a batch;
     // lwp_augment_batch_crowd: [.. | run tables] and, behind the upload, the rendered crowd masks; lwp_crowd_masks: [run tables]
     DevBuf d_augment;
@@ -257,7 +259,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 107; }
+extern "C" int lwp_version(void) { return 108; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -3742,9 +3744,11 @@ static int stage_losses_prepare(lwp_handle h, const float* const* outs, int n_ou
     return LWP_OK;
 }
 
-// the launches of one lwp_stage_losses call; the S sums land behind the partials in d_loss
+// the launches of one lwp_stage_losses call; the S sums land behind the partials in d_loss.  With `log` each launch also adds
+// its own range of sums / divisor to log[s0 ...], and the first one counts the call in `adds`.
 static int enqueue_stage_losses(lwp_handle h, const float* const* outs, const float* keypoint_maps, const float* paf_maps,
-                                const float* mask, int N, int hs, int ws, int batch_size) {
+                                const float* mask, int N, int hs, int ws, int batch_size, double* log = nullptr, double divisor = 1.0,
+                                int64_t* adds = nullptr) {
     const int S = 2 * (h->g.nref + 1);
     const int blocks = stage_loss_blocks(N, hs * ws);
     double* d_partials = h->d_loss.as<double>();
@@ -3756,8 +3760,17 @@ static int enqueue_stage_losses(lwp_handle h, const float* const* outs, const fl
         p.keypoint_maps = keypoint_maps; p.paf_maps = paf_maps; p.mask = mask;
         p.N = N; p.CH = h->g.NH; p.CP = h->g.NP; p.hw = hs * ws; p.batch = batch_size;
         p.partials = d_partials;
-        LAUNCH(h, KC_OTHER, launch_stage_losses(p, d_losses + s0, h->stream));
+        LAUNCH(h, KC_OTHER, launch_stage_losses(p, d_losses + s0, h->stream, log ? log + s0 : nullptr, divisor, s0 == 0 ? adds : nullptr));
     }
+    return LWP_OK;
+}
+
+// the log buffer, zeroed on the handle's stream when it is made: a handle's log is zero until its first add
+static int ensure_loss_log(lwp_handle h) {
+    if (h->d_loss_log) return LWP_OK;
+    const size_t bytes = (size_t)(2 * (h->g.nref + 1)) * sizeof(double) + sizeof(int64_t);
+    HIP_TRY(h, h->d_loss_log.ensure(bytes));
+    HIP_TRY(h, hipMemsetAsync(h->d_loss_log.as<char>(), 0, bytes, h->stream));
     return LWP_OK;
 }
 
@@ -3772,6 +3785,38 @@ extern "C" int lwp_stage_losses(lwp_handle h, const float* const* outs, int n_ou
     const double* d_losses = h->d_loss.as<double>() + (size_t)kLossMaxOuts * stage_loss_blocks(N, hs * ws);
     HIP_TRY(h, hipMemcpyAsync(losses_host, d_losses, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_stage_losses_log(lwp_handle h, const float* const* outs, int n_outs, const float* keypoint_maps, const float* paf_maps,
+                                    const float* mask, int N, int hs, int ws, int batch_size, double divisor) {
+    if (!(divisor > 0.0) || !std::isfinite(divisor)) return fail(h, LWP_ERR_ARG, "divisor must be finite and greater than 0");
+    int rc = stage_losses_prepare(h, outs, n_outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size);
+    if (rc) return rc;
+    rc = ensure_loss_log(h);
+    if (rc) return rc;
+    const int S = 2 * (h->g.nref + 1);
+    double* log = h->d_loss_log.as<double>();
+    rc = enqueue_stage_losses(h, outs, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, log, divisor, (int64_t*)(log + S));
+    if (rc) return rc;
+    bool ordered = false;                              // the caller's next work on the tensors waits for the launches; the host does not
+    return order_out(h, h->stream, &ordered);
+}
+
+extern "C" int lwp_loss_log_read(lwp_handle h, double* sums_host, int64_t* adds, int reset) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (!sums_host || !adds) return fail(h, LWP_ERR_ARG, "sums_host / adds is null");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_loss_log(h);
+    if (rc) return rc;
+    const int S = 2 * (h->g.nref + 1);
+    const size_t bytes = (size_t)S * sizeof(double) + sizeof(int64_t);
+    std::vector<char> host(bytes);
+    HIP_TRY(h, hipMemcpyAsync(host.data(), h->d_loss_log.as<char>(), bytes, hipMemcpyDeviceToHost, h->stream));
+    if (reset) HIP_TRY(h, hipMemsetAsync(h->d_loss_log.as<char>(), 0, bytes, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    memcpy(sums_host, host.data(), (size_t)S * sizeof(double));
+    memcpy(adds, host.data() + (size_t)S * sizeof(double), sizeof(int64_t));
     return LWP_OK;
 }
 

@@ -575,7 +575,9 @@ struct StageLossParams {
     double* partials;               // [S][stage_loss_blocks(N, hw)]
 };
 int stage_loss_blocks(int N, int hw);
-hipError_t launch_stage_losses(const StageLossParams& p, double* losses, hipStream_t s);   // losses: S doubles, device
+// losses: p.S doubles, device.  log (or null): p.S doubles that get losses[i] / divisor added; adds (or null): one counter, + 1
+hipError_t launch_stage_losses(const StageLossParams& p, double* losses, hipStream_t s, double* log = nullptr, double divisor = 1.0,
+                               int64_t* adds = nullptr);
 
 // ---- stage backward (bwd_kernels.hip; train.py:99-103 differentiated): f32, NHWC activations and gradients
 struct LossGradParams {

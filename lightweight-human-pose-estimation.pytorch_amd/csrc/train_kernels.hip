@@ -179,12 +179,18 @@ __global__ void __launch_bounds__(256) stage_loss_kernel(StageLossParams p) {
     }
 }
 
-__global__ void __launch_bounds__(64) stage_loss_reduce_kernel(const double* __restrict__ partials, int blocks, int S, double* __restrict__ losses) {
+// With `log` the same thread also adds its stage's sum / divisor to the handle's running log (lwp_stage_losses_log), in float64,
+// and thread 0 counts the add when `adds` is given: one thread per entry, launches in stream order, no atomics.  The sum stored
+// in `losses` is the same with or without a log.
+__global__ void __launch_bounds__(64) stage_loss_reduce_kernel(const double* __restrict__ partials, int blocks, int S, double* __restrict__ losses,
+                                                               double* __restrict__ log, double divisor, int64_t* __restrict__ adds) {
     const int s = threadIdx.x;
     if (s >= S) return;
     double sum = 0.0;
     for (int b = 0; b < blocks; ++b) sum += partials[(size_t)s * blocks + b];
     losses[s] = sum;
+    if (log) log[s] += sum / divisor;
+    if (adds && s == 0) adds[0] += 1;
 }
 
 int stage_loss_blocks(int N, int hw) {
@@ -192,12 +198,12 @@ int stage_loss_blocks(int N, int hw) {
     return (int)(need < 1 ? 1 : (need > kLossMaxBlocks ? kLossMaxBlocks : need));
 }
 
-hipError_t launch_stage_losses(const StageLossParams& p, double* losses, hipStream_t s) {
+hipError_t launch_stage_losses(const StageLossParams& p, double* losses, hipStream_t s, double* log, double divisor, int64_t* adds) {
     const int blocks = stage_loss_blocks(p.N, p.hw);
     hipLaunchKernelGGL(stage_loss_kernel, dim3(blocks), dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(stage_loss_reduce_kernel, dim3(1), dim3(64), 0, s, (const double*)p.partials, blocks, p.S, losses);
+    hipLaunchKernelGGL(stage_loss_reduce_kernel, dim3(1), dim3(64), 0, s, (const double*)p.partials, blocks, p.S, losses, log, divisor, adds);
     return hipGetLastError();
 }
 

@@ -958,6 +958,18 @@ class Engine(object):
         two calls on the same inputs return the same bits.  Tensors are read as contiguous NCHW float32: a strided view is
         copied first (``Engine.forward`` returns contiguous tensors, which are read in place).  With ``time_iters`` > 0 the
         kernels are launched that many times back to back and the call returns the milliseconds of all of them (HIP events)."""
+        args, n = self._loss_args(outs, keypoint_maps, paf_maps, mask, batch_size)
+        if time_iters:
+            ms = C.c_float()
+            check(lib().lwp_time_stage_losses(*args, int(time_iters), C.byref(ms)), self.h.ptr)
+            return ms.value
+        losses = (C.c_double * max(n, 1))()
+        check(lib().lwp_stage_losses(*args, losses), self.h.ptr)
+        return [float(losses[i]) for i in range(n)]
+
+    def _loss_args(self, outs, keypoint_maps, paf_maps, mask, batch_size):
+        """The leading arguments of lwp_stage_losses / lwp_stage_losses_log and the number of stage tensors; the contiguous
+        tensors behind the pointers are kept on the engine until the next loss call."""
         torch = _torch()
 
         def dev32(t, what, shape):
@@ -979,16 +991,25 @@ class Engine(object):
         if m is None:
             raise ValueError("mask is None")
         ptrs = (C.c_void_p * max(len(keep), 1))(*[None if o is None else o.data_ptr() for o in keep])
-        losses = (C.c_double * max(len(keep), 1))()
+        self._loss_keep = (keep, km, pm, m, ptrs)
         self._order()
-        args = (self.h.ptr, ptrs, len(keep), None if km is None else km.data_ptr(), None if pm is None else pm.data_ptr(), m.data_ptr(),
-                N, hs, ws, int(N if batch_size is None else batch_size))
-        if time_iters:
-            ms = C.c_float()
-            check(lib().lwp_time_stage_losses(*args, int(time_iters), C.byref(ms)), self.h.ptr)
-            return ms.value
-        check(lib().lwp_stage_losses(*args, losses), self.h.ptr)
-        return [float(losses[i]) for i in range(len(keep))]
+        return (self.h.ptr, ptrs, len(keep), None if km is None else km.data_ptr(), None if pm is None else pm.data_ptr(), m.data_ptr(),
+                N, hs, ws, int(N if batch_size is None else batch_size)), len(keep)
+
+    def log_stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, divisor=1.0):
+        """``stage_losses`` without the read: the same launches, and behind them, on the device, ``log[i] += loss[i] / divisor``
+        in float64 (train.py:96-97's total_losses with divisor = batches_per_iter).  Returns None and does not wait for the
+        GPU; ``read_loss_log`` fetches the running sums.  ``divisor`` must be finite and > 0 (ValueError)."""
+        args, _ = self._loss_args(outs, keypoint_maps, paf_maps, mask, batch_size)
+        check(lib().lwp_stage_losses_log(*args, float(divisor)), self.h.ptr)
+
+    def read_loss_log(self, reset=True):
+        """(the 2 * (nref + 1) running sums of ``log_stage_losses`` as Python floats, the number of adds since the last reset).
+        Waits for the engine's stream: the one wait of a logged training loop.  ``reset`` zeroes both behind the read."""
+        S = 2 * (self.nref + 1)
+        sums, adds = (C.c_double * S)(), C.c_int64()
+        check(lib().lwp_loss_log_read(self.h.ptr, sums, C.byref(adds), 1 if reset else 0), self.h.ptr)
+        return [float(sums[i]) for i in range(S)], int(adds.value)
 
     # ------------------------------------------------------------------ stage backward (train.py:99-103, fp32 engines)
     def train_forward(self, x):

@@ -120,14 +120,17 @@ def stage_losses(net, images, labels, masks=None, stride=8, sigma=7, paf_thickne
     return eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], t["keypoint_mask"][:, 0], batch_size)
 
 
-def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thickness=1, batch_size=None, loss_scale=1.0, into=None):
+def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thickness=1, batch_size=None, loss_scale=1.0, into=None,
+                    log_divisor=None):
     """``stage_losses`` plus the gradient of their sum (train.py:99-102, fp32 engines): retaining forward, targets, loss and
     stage backward on the GPU in one call.  Returns (losses, grads, d_features): the 2 * (nref + 1) floats of ``stage_losses``,
     the dict state-dict key -> gradient of every initial_stage.* / refinement_stages.* parameter, and the gradient at the
     cpm output (N, num_channels, h, w).  ``loss_scale`` scales the gradients only (train.py:102's 1 / batches_per_iter);
     ``into``: the flat array of an earlier call to add to.  The backbone is frozen (the cpm too) unless the engine's train scope
     is "cpm" (``grads`` then holds the cpm.* keys as well) or "all" (the model.* keys too), and the BatchNorms stay at their
-    running statistics: this is loss.backward() of the reference network in eval() mode.  ``train_step`` adds the optimiser."""
+    running statistics: this is loss.backward() of the reference network in eval() mode.  ``train_step`` adds the optimiser.
+    ``log_divisor``: the losses are added to the engine's loss log (``Engine.log_stage_losses``) instead of being fetched,
+    and ``losses`` is None."""
     import torch
     from .datasets.coco import generate_targets
     x = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)) if isinstance(images, np.ndarray) else images
@@ -139,17 +142,21 @@ def stage_gradients(net, images, labels, masks=None, stride=8, sigma=7, paf_thic
         raise ValueError("the network's maps are %s but the targets %s: the frame size must be a multiple of the stride"
                          % (tuple(outs[0].shape[2:]), tuple(t["keypoint_maps"].shape[2:])))
     mask = t["keypoint_mask"][:, 0]
-    losses = eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], mask, batch_size)
+    if log_divisor is None:
+        losses = eng.stage_losses(outs, t["keypoint_maps"], t["paf_maps"], mask, batch_size)
+    else:
+        losses = eng.log_stage_losses(outs, t["keypoint_maps"], t["paf_maps"], mask, batch_size, log_divisor)
     grads, d_features = eng.stage_backward(t["keypoint_maps"], t["paf_maps"], mask, batch_size, loss_scale, into)
     return losses, grads, d_features
 
 
-def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=8, sigma=7, paf_thickness=1):
+def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=8, sigma=7, paf_thickness=1, log=False):
     """One pass of train.py:85-110's loop body for one loader batch, all on the GPU: targets, retaining forward, stage losses,
     stage backward with loss_scale = 1 / batches_per_iter, and, once ``batches_per_iter`` calls have added their gradients,
     ``opt.step`` (an ``optim.StageAdam`` of this net; it is zeroed at the first batch of an iteration, train.py:87-88).
     Returns the batch's stage losses as ``stage_losses`` does.  Only initial_stage.* / refinement_stages.* move, and cpm.* with ``optim.StageAdam(net, scope="cpm")``,
-    every parameter with ``scope="all"``."""
+    every parameter with ``scope="all"``.  ``log=True``: the losses, divided by ``batches_per_iter``, are added to the engine's loss
+    log on the device (train.py:96-97's total_losses; ``Engine.read_loss_log``); nothing is fetched and the call returns None."""
     if opt.net is not net:
         raise ValueError("opt is not an optimiser of this net")
     batches_per_iter = int(batches_per_iter)
@@ -157,7 +164,8 @@ def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=
         raise ValueError("batches_per_iter must be at least 1")
     if opt.batch_index == 0:
         opt.zero_grad()
-    losses, grads, _ = stage_gradients(net, images, labels, masks, stride, sigma, paf_thickness, None, 1.0 / batches_per_iter, opt.accumulated)
+    losses, grads, _ = stage_gradients(net, images, labels, masks, stride, sigma, paf_thickness, None, 1.0 / batches_per_iter, opt.accumulated,
+                                       float(batches_per_iter) if log else None)
     opt.accumulated = net.engine.flat_of(grads)
     opt.batch_index += 1
     if opt.batch_index >= batches_per_iter:
@@ -166,13 +174,14 @@ def train_step(net, opt, images, labels, masks=None, batches_per_iter=1, stride=
     return losses
 
 
-def augmented_train_step(net, opt, samples, augment, batches_per_iter=1, sigma=7, paf_thickness=1):
+def augmented_train_step(net, opt, samples, augment, batches_per_iter=1, sigma=7, paf_thickness=1, log=False):
     """``train_step`` from RAW samples (image uint8 (H, W, 3), label dict, and a mask float32 (H, W), or ``"segmentations"``,
     the label's crowd RLE dicts, from which the mask is rendered on the device, or neither): ``augment``, a
     ``datasets.transformations.DeviceAugment``, draws the random numbers and moves the labels on the host and renders the
     crops on the GPU; its ``image``, ``kpts`` and ``mask_small`` feed the same targets, retaining forward, losses, backward
     and optimiser step as ``train_step``.  The small mask is the reference's (coco.py:48 on the uint8 mask CropPad leaves,
-    rounded to 0 / 1), not the float mean of ``Engine.mask_downsample``.  Returns the batch's stage losses."""
+    rounded to 0 / 1), not the float mean of ``Engine.mask_downsample``.  Returns the batch's stage losses, or with
+    ``log=True`` adds them to the engine's loss log as ``train_step`` does and returns None."""
     if opt.net is not net:
         raise ValueError("opt is not an optimiser of this net")
     batches_per_iter = int(batches_per_iter)
@@ -189,7 +198,10 @@ def augmented_train_step(net, opt, samples, augment, batches_per_iter=1, sigma=7
         raise ValueError("the network's maps are %s but the targets %s: the crop must be a multiple of the network's stride"
                          % (tuple(outs[0].shape[2:]), tuple(kmaps.shape[2:])))
     mask = batch["mask_small"]
-    losses = eng.stage_losses(outs, kmaps, pmaps, mask, None)
+    if log:
+        losses = eng.log_stage_losses(outs, kmaps, pmaps, mask, None, float(batches_per_iter))
+    else:
+        losses = eng.stage_losses(outs, kmaps, pmaps, mask, None)
     grads, _ = eng.stage_backward(kmaps, pmaps, mask, None, 1.0 / batches_per_iter, opt.accumulated)
     opt.accumulated = eng.flat_of(grads)
     opt.batch_index += 1
