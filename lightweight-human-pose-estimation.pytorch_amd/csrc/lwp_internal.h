@@ -131,6 +131,7 @@ struct Tuning {
     bool has_c3 = false, has_pw = false; int c3[3] = {0, 0, 0}, pw[3] = {0, 0, 0};   // LWP_GEMM_C3 / LWP_GEMM_PW = "BM,BN,KS"
     int dwpw_bm = 0, dwpw_nw = 0, dwpw_debug = 0, dwpwh_debug = 0; // LWP_DWPW_BM, LWP_DWPW_NW, LWP_DWPW_DEBUG, LWP_DWPWH_DEBUG
     int dwpw_pipe = -1;                                            // LWP_DWPW_PIPE (f32 software-pipelined 512-output fused kernel: 0 off, 1 forced)
+    int dwpw_lean = -1;                                            // LWP_DWPW_LEAN (f32 two-phase fused kernel <16,16>: 0 the classic phase 1, 1 the row-stepped one in 80 VGPRs; unset: 1)
     int dwpw_tiled_wgs = 0;                                        // LWP_DWPW_TILED_WGS (experiments: persistent workgroups per CU)
     int dwpw_tiled = -1;                                           // LWP_DWPW_TILED (front blocks, LDS-tiled fused kernel: 0 off, 1 forced)
     int dwpw_pp_grid = 0;                                          // LWP_DWPW_PP_GRID (tests: persistent grid size, to walk several rounds at small M)

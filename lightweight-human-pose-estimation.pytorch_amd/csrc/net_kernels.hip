@@ -1276,8 +1276,17 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
 // f32 blocks do not care (the f32 MFMA leaves the LDS idle most of the time): 26.9 against 26.2 us at batch 1 with C + 8, the
 // same at batch 32.  The bf16 kernels take the conflict-free stride (DWPW_APAD, net_kernels_bf16.hip).
 constexpr int DWPW_F32_APAD = 4;
-template <int BM, int NW, int DBG = 0, int ACT = -1>
-__global__ void __launch_bounds__(NW * 64) dwpw_kernel(DwPwParams p) {
+constexpr int DWPW_LEAN_DEFAULT = 1;                 // what an unset LWP_DWPW_LEAN means
+// LEAN (BM = 16, NW = 16, C <= 512: every thread has at most ONE depthwise item): phase 1 in row steps.  The classic register
+// peak (9 weight vectors + a 3 x 4 window + the first weight step of the K loop: 120 VGPRs, 480 of a SIMD's 512 for the
+// workgroup's 4 waves) becomes 80 with no scratch (amdgpu_waves_per_eu(6, 6) is the check: it makes the compiler spill instead
+// of exceeding 80), so that a dense-3x3 workgroup of another stream (72 VGPRs, 2 waves per SIMD) fits on the CU beside it.
+// Same arithmetic: every output keeps its chain acc = bias; acc += x[t] * w[t], t = 0..8; K loop and epilogue are the classic
+// ones.  The other instantiations keep their code and their registers (amdgpu_waves_per_eu(0, 0) sets nothing).  Measured
+// (profiles/r7_dwpw_lean): 0.2 us per launch faster alone, 1.2 us beside a dense 3x3 of another stream.
+template <int BM, int NW, int DBG = 0, int ACT = -1, int LEAN = 0>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 0, LEAN ? 6 : 0))) dwpw_kernel(DwPwParams p) {
+    static_assert(!LEAN || (BM == 16 && NW == 16 && DBG == 0), "the lean phase 1 is written for one item per thread");
     // ACT >= 0: both activations known at compile time (ReLU for every conv_dw block): no chain of scalar branches per vector
     const int act_dw = ACT >= 0 ? ACT : p.act_dw, act_pw = ACT >= 0 ? ACT : p.act_pw;
     constexpr int NT = NW * 64;
@@ -1318,8 +1327,11 @@ __global__ void __launch_bounds__(NW * 64) dwpw_kernel(DwPwParams p) {
         for (int j = 0; j < 4; ++j)
             dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16 + j * 1024, soff, 0));
     };
+    auto first_b = [&]() {
 #pragma unroll
-    for (int j = 0; j < PF - 1; ++j) load_b(j < nsteps ? j : nsteps - 1, bw[j]);   // in flight during phase 1
+        for (int j = 0; j < PF - 1; ++j) load_b(j < nsteps ? j : nsteps - 1, bw[j]);
+    };
+    if constexpr (!LEAN) first_b();                  // in flight during phase 1 (LEAN: requested behind its last row)
 
     // ---- phase 1: depthwise row block.  A thread keeps ONE 4-channel chunk (its 9 weight vectors + bias are loaded
     // once; NT is a multiple of C/4 for every layer shape) and walks groups of PXG consecutive output pixels.  When the
@@ -1328,7 +1340,125 @@ __global__ void __launch_bounds__(NW * 64) dwpw_kernel(DwPwParams p) {
     constexpr int PXG = 2;
     static_assert(BM % PXG == 0, "row block must hold whole pixel groups");
     const int cg = p.C >> 2;
-    if (!(DBG & 1)) {
+    if constexpr (LEAN) {
+        // Row steps.  A request is a row's 3 weight vectors and its input vectors; at most two rows are in flight or live at a
+        // time and the K loop's first weight step goes out behind the last row's requests.  sched_barrier: without them the
+        // scheduler hoists every request to the top and the peak is the classic one.
+        const int c = (tid % cg) * 4, grp = tid / cg;
+        if (grp < BM / PXG) {
+            const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)((int64_t)p.N * p.Hi * p.Wi * p.in_ld * 4), 0x00020000);
+            const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.dw_w, 0, 10 * p.C * 4, 0x00020000);
+            const int pix_b = p.in_ld * 4, row_b = p.Wi * pix_b;
+            auto ldw = [&](unsigned off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, 0)); };
+            // depthwise weights [9][C] + bias [C]: the lane's channel offset in a register, the tap's row in a scalar
+            auto ldd = [&](int t) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(drsrc, c * 4, t * p.C * 4, 0)); };
+            auto reqw = [&](int ky, f32x4* wr) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) wr[j] = ldd(ky * 3 + j);
+            };
+            const int M32 = (int)M, Wo = p.Wo, Ho = p.Ho;
+            const int m = (int)m0 + grp * PXG;
+            int xo, yo, img;
+            {
+                const unsigned q1 = (unsigned)m / (unsigned)Wo;
+                xo = m - (int)q1 * Wo;
+                img = (int)(q1 / (unsigned)Ho);
+                yo = (int)q1 - img * Ho;
+            }
+            f32x4 acc[PXG];
+            acc[0] = ldd(9);
+            if (p.stride == 1 && p.dil == 1 && m + PXG <= M32 && xo + PXG <= Wo) {
+                // the pixels share a 3 x (PXG + 2) window: two row slots of 3 weight + PXG + 2 input vectors
+                const int base = ((img * p.Hi + yo) * p.Wi + xo) * pix_b + c * 4;
+                f32x4 wb[2][3], xb[2][PXG + 2];
+                auto req = [&](int ky, f32x4* wr, f32x4* xr) {
+                    reqw(ky, wr);
+                    const int yy = yo + ky - 1;
+                    const bool rok = (unsigned)yy < (unsigned)p.Hi;
+#pragma unroll
+                    for (int j = 0; j < PXG + 2; ++j) {
+                        const int xx = xo + j - 1;
+                        xr[j] = ldw((rok & ((unsigned)xx < (unsigned)p.Wi)) ? (unsigned)(base + (ky - 1) * row_b + (j - 1) * pix_b) : 0x80000000u);
+                    }
+                };
+                req(0, wb[0], xb[0]);
+                req(1, wb[1], xb[1]);
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (ky == 0) {
+#pragma unroll
+                        for (int i = 1; i < PXG; ++i) acc[i] = acc[0];
+                    }
+#pragma unroll
+                    for (int i = 0; i < PXG; ++i)
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) acc[i] += xb[ky & 1][i + j] * wb[ky & 1][j];
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (ky == 0) req(2, wb[0], xb[0]);
+                    if (ky == 1) first_b();
+                }
+            } else {
+                // general path (borders of the row block, stride 2, dilation 2): units (row ky, pixel i) of 3 input vectors; two
+                // weight-row slots and one input slot per pixel, i.e. four requests in flight
+                int bs[PXG], ycs[PXG], xcs[PXG];
+                bool oks[PXG];
+                {
+                    int xi = xo, yi = yo, im = img;
+#pragma unroll
+                    for (int i = 0; i < PXG; ++i) {
+                        oks[i] = m + i < M32;
+                        ycs[i] = yi * p.stride; xcs[i] = xi * p.stride;
+                        bs[i] = ((im * p.Hi + ycs[i]) * p.Wi + xcs[i]) * pix_b + c * 4;
+                        if (++xi == Wo) { xi = 0; if (++yi == Ho) { yi = 0; ++im; } }
+                    }
+                }
+                f32x4 wb[2][3], xb[PXG][3];
+                auto reqx = [&](int ky, int i, f32x4* xr) {
+                    const int dy = (ky - 1) * p.dil;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        const int dx = (j - 1) * p.dil;
+                        // (no short-circuit: a chain of && becomes branches here, and every vector in flight is spilled around them)
+                        const bool in = oks[i] & ((unsigned)(ycs[i] + dy) < (unsigned)p.Hi) & ((unsigned)(xcs[i] + dx) < (unsigned)p.Wi);
+                        xr[j] = ldw(in ? (unsigned)(bs[i] + dy * row_b + dx * pix_b) : 0x80000000u);
+                    }
+                };
+                reqw(0, wb[0]);
+#pragma unroll
+                for (int i = 0; i < PXG; ++i) reqx(0, i, xb[i]);
+                reqw(1, wb[1]);
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+                    for (int i = 0; i < PXG; ++i) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (ky == 0 && i == 0) {
+#pragma unroll
+                            for (int k = 1; k < PXG; ++k) acc[k] = acc[0];
+                        }
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) acc[i] += xb[i][j] * wb[ky & 1][j];
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (ky < 2) reqx(ky + 1, i, xb[i]);
+                        if (i == PXG - 1 && ky == 0) reqw(2, wb[0]);
+                        if (i == PXG - 1 && ky == 1) first_b();
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const int row0 = grp * PXG;
+#pragma unroll
+            for (int i = 0; i < PXG; ++i) {
+                f32x4 v = acc[i];
+                v.x = apply_act(v.x, act_dw); v.y = apply_act(v.y, act_dw);
+                v.z = apply_act(v.z, act_dw); v.w = apply_act(v.w, act_dw);
+                *(f32x4*)(At + (row0 + i) * ldA + c) = v;
+            }
+        } else {
+            first_b();                               // C = 256: waves 8 .. 15 have no depthwise item
+        }
+    } else if (!(DBG & 1)) {
         const int c = (tid % cg) * 4;
         f32x4 wv[9];
 #pragma unroll
@@ -1490,6 +1620,14 @@ static hipError_t launch_dwpw_t(const DwPwParams& p, hipStream_t s) {
     const size_t lds = (size_t)BM * (p.C + DWPW_F32_APAD) * sizeof(float);
     if ((int64_t)p.N * p.Hi * p.Wi * p.in_ld * 4 >= (1ll << 31)) return hipErrorInvalidValue;     // 32-bit buffer offsets (2 GiB of input per launch)
     const int nsplit = (p.cout / 32) / NW;
+    if constexpr (BM == 16 && NW == 16 && DBG == 0 && ACT == ACT_RELU) {
+        // LWP_DWPW_LEAN: the row-stepped phase 1 (one depthwise item per thread: C <= 512, so the tile is 33 KB of LDS at most)
+        const Tuning& T = p.tune ? *p.tune : default_tuning();
+        if ((T.dwpw_lean < 0 ? DWPW_LEAN_DEFAULT : T.dwpw_lean) != 0 && p.C <= 512) {
+            hipLaunchKernelGGL((dwpw_kernel<BM, NW, DBG, ACT, 1>), dim3((unsigned)((M + BM - 1) / BM), nsplit), dim3(NW * 64), lds, s, p);
+            return hipGetLastError();
+        }
+    }
     static LdsAttrOnce attr;
     if (lds > 48 * 1024) {
         hipError_t e = attr.ensure((const void*)dwpw_kernel<BM, NW, DBG, ACT>, 160 * 1024);
@@ -2162,7 +2300,7 @@ Tuning tuning_from_env() {
     if (const char* e = getenv("LWP_GEMM_C3")) t.has_c3 = sscanf(e, "%d,%d,%d", &t.c3[0], &t.c3[1], &t.c3[2]) == 3;
     if (const char* e = getenv("LWP_GEMM_PW")) t.has_pw = sscanf(e, "%d,%d,%d", &t.pw[0], &t.pw[1], &t.pw[2]) == 3;
     geti("LWP_DWPW_BM", &t.dwpw_bm); geti("LWP_DWPW_NW", &t.dwpw_nw); geti("LWP_DWPW_DEBUG", &t.dwpw_debug); geti("LWP_DWPWH_DEBUG", &t.dwpwh_debug);
-    digit("LWP_DWPW_PIPE", &t.dwpw_pipe);
+    digit("LWP_DWPW_PIPE", &t.dwpw_pipe); digit("LWP_DWPW_LEAN", &t.dwpw_lean);
     digit("LWP_DWPW_TILED", &t.dwpw_tiled); geti("LWP_DWPW_TILED_WGS", &t.dwpw_tiled_wgs);
     digit("LWP_DWPW_PP", &t.dwpw_pp); geti("LWP_DWPW_PP_GRID", &t.dwpw_pp_grid);
     geti("LWP_HEADS_RM", &t.heads_rm);
