@@ -12,6 +12,7 @@
 // same inputs give the same bits.
 #include "lwp_internal.h"
 #include "h16.h"
+#include <type_traits>
 
 namespace lwp {
 
@@ -473,9 +474,10 @@ hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int a
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------- cpm: ELU and depthwise 3x3
-// (with_mobilenet.py:7-21; modules/conv.py:24-32 with bn=False: depthwise 3x3 + ELU, 1x1 + ELU.)  Memory-bound element-wise and
-// reduction shapes: a lane owns four consecutive channels of a pixel, every access is 16 bytes, a wave covers whole rows.
+// ---------------------------------------------------------------------------------------- cpm: ELU
+// (with_mobilenet.py:7-21; modules/conv.py:24-32 with bn=False: depthwise 3x3 + ELU, 1x1 + ELU.)  This and the depthwise family
+// below are memory-bound element-wise and reduction shapes: a lane owns four consecutive channels of a pixel, every access is 16
+// bytes, a wave covers whole rows.
 __global__ void __launch_bounds__(256) elu_grad_kernel(float* g, int g_ld, const float* y, int y_ld, int64_t M, int C4) {
     const int64_t total = M * C4;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -497,11 +499,24 @@ hipError_t launch_elu_grad(float* g, int g_ld, const float* y, int y_ld, int64_t
     return hipGetLastError();
 }
 
-// dX[n, y, x, c] = sum over taps (ky, kx) of dZ[n, y + 1 - ky, x + 1 - kx, c] * w[ky][kx][c]: one fmaf chain per output in tap
-// order 0..8, a tap outside the map contributes a zero
-__global__ void __launch_bounds__(256) dw_dgrad_kernel(DwGradParams p) {
+// ---------------------------------------------------------------------------------------- depthwise 3x3, stride 1 | 2, dilation 1 | 2
+// One family for the cpm's depthwise convs (stride 1, dilation 1, ELU behind them) and the backbone's (with_mobilenet.py:94-104:
+// conv_dw, BatchNorm + ReLU behind it).  The forward is Z[n, oy, ox, c] = sum_k X[n, s oy + d (ky - 1), s ox + d (kx - 1), c] w[k][c]
+// on an Ho x Wo map, Ho = (H - 1) / s + 1 (padding = dilation).  Stride and dilation are template arguments: the index arithmetic
+// of a pair is compile-time, and at (1, 1) Ho x Wo is H x W itself.
+template <typename F> static void dw_for_sd(int stride, int dil, F&& launch) {      // both 1 or 2 (dw_grad_shape_ok)
+    typedef std::integral_constant<int, 1> I1;
+    typedef std::integral_constant<int, 2> I2;
+    if (stride == 1) { if (dil == 1) launch(I1(), I1()); else launch(I1(), I2()); }
+    else { if (dil == 1) launch(I2(), I1()); else launch(I2(), I2()); }
+}
+
+// dX[n, y, x, c] = sum over taps of dZ[n, (y + d - d ky) / s, (x + d - d kx) / s, c] * w[tap][c]: one fmaf chain per output in tap
+// order 0..8; a tap whose source index is not divisible by s or lies outside the Ho x Wo map contributes a zero
+template <int S, int D> __global__ void __launch_bounds__(256) dw_dgrad_kernel(DwGradParams p) {
     const int C4 = p.C / 4;
-    const int HW = p.H * p.W;
+    const int Ho = S == 1 ? p.H : p.Ho, Wo = S == 1 ? p.W : p.Wo;
+    const int HW = p.H * p.W, HWo = Ho * Wo;
     const int64_t total = (int64_t)p.N * HW * C4;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t px = i / C4;
@@ -512,9 +527,11 @@ __global__ void __launch_bounds__(256) dw_dgrad_kernel(DwGradParams p) {
         f32x4 acc = {0, 0, 0, 0};
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int sy = y + 1 - tap / 3, sx = x + 1 - tap % 3;
+            const int ny = y + D - D * (tap / 3), nx = x + D - D * (tap % 3);
+            const int sy = ny / S, sx = nx / S;
             f32x4 z = {0, 0, 0, 0};
-            if (sy >= 0 && sy < p.H && sx >= 0 && sx < p.W) z = *(const f32x4*)(p.dz + (n * HW + (int64_t)sy * p.W + sx) * p.dz_ld + c);
+            if (ny >= 0 && nx >= 0 && ny % S == 0 && nx % S == 0 && sy < Ho && sx < Wo)
+                z = *(const f32x4*)(p.dz + (n * HWo + (int64_t)sy * Wo + sx) * p.dz_ld + c);
             const f32x4 wv = *(const f32x4*)(p.w + tap * p.C + c);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = fmaf(z[k], wv[k], acc[k]);
@@ -530,57 +547,70 @@ __global__ void __launch_bounds__(256) dw_dgrad_kernel(DwGradParams p) {
 }
 static bool dw_grad_shape_ok(const DwGradParams& p) {
     const int64_t M = (int64_t)p.N * p.H * p.W;
-    return p.N >= 1 && p.H >= 1 && p.W >= 1 && M < (1ll << 31) - BW_T && p.C >= 4 && (p.C & 3) == 0 && p.C <= p.dz_ld && quad_ok(p.dz, p.dz_ld);
+    return p.N >= 1 && p.H >= 1 && p.W >= 1 && M < (1ll << 31) - BW_T && (p.stride == 1 || p.stride == 2) && (p.dil == 1 || p.dil == 2) &&
+           p.Ho == (p.H - 1) / p.stride + 1 && p.Wo == (p.W - 1) / p.stride + 1 && p.C >= 4 && (p.C & 3) == 0 && p.C <= p.dz_ld &&
+           quad_ok(p.dz, p.dz_ld);
 }
 hipError_t launch_dw_dgrad(const DwGradParams& p, hipStream_t s) {
     if (!dw_grad_shape_ok(p) || !quad_ok(p.w, 4) || !quad_ok(p.dx, p.dx_ld) || p.C > p.dx_ld) return hipErrorInvalidValue;
     const int64_t total = (int64_t)p.N * p.H * p.W * (p.C / 4);
-    hipLaunchKernelGGL(dw_dgrad_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 8192));
+    dw_for_sd(p.stride, p.dil, [&](auto S, auto D) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(dw_dgrad_kernel<decltype(S)::value, decltype(D)::value>), grid, dim3(256), 0, s, p);
+    });
     return hipGetLastError();
 }
 
-// dW[c][tap] = sum over pixels p of dZ[p][c] * X[p + off(tap)][c], off(tap) = (tap / 3 - 1, tap % 3 - 1).  grid: x = 64-channel
-// group, y = pixel split.  Thread t owns channels 4 (t & 15) .. + 3 of the group and the pixels p_begin + (t >> 4) + 16 k of the
-// split, k ascending: 36 fmaf chains.  The 16 pixel lanes are then added through LDS in a fixed binary tree (lane i += lane
-// i + 8, + 4, + 2, + 1), and lane 0 writes the split's [9][C] partial.  A second launch adds the partials in split order.
+// dW[c][tap] = sum over output pixels q of dZ[q][c] * X[s q + d off(tap)][c], off(tap) = (tap / 3 - 1, tap % 3 - 1), and, with SUM, a
+// tenth accumulator row g[c] = sum_q dZ[q][c] (the gradient of the folded bias, which the BatchNorm chain rule needs).  grid:
+// x = 64-channel group, y = range of output pixels (dw_wgrad_plan over N Ho Wo).  Thread t owns channels 4 (t & 15) .. + 3 of the
+// group and the pixels p_begin + (t >> 4) + 16 k of the range, k ascending: 36 fmaf chains (and 4 sums).  The 16 pixel lanes are
+// then added through LDS in a fixed binary tree (lane i += lane i + 8, + 4, + 2, + 1), and lane 0 writes the range's [rows][C]
+// partial.  A second launch adds the partials in range order.
 constexpr int DW_CG = 64;          // channels of a workgroup
 constexpr int DW_PL = 16;          // pixel lanes
-__global__ void __launch_bounds__(256) dw_wgrad_kernel(DwGradParams p) {
-    __shared__ float red[DW_PL * 9 * DW_CG];          // [pixel lane][tap][channel]: 36 KB
+template <bool SUM, int S, int D> __global__ void __launch_bounds__(256) dw_wgrad_kernel(DwGradParams p) {
+    constexpr int ROWS = SUM ? 10 : 9;
+    __shared__ float red[DW_PL * ROWS * DW_CG];       // [pixel lane][tap, then the sum of dZ][channel]: 36 KB, 40 KB with SUM
     const int t = threadIdx.x, cq = (t & 15) * 4, pl = t >> 4;
     const int c = blockIdx.x * DW_CG + cq;
     const bool c_in = c < p.C;                         // C is a multiple of 4: a quad is inside or outside as a whole
-    const int HW = p.H * p.W;
-    const int64_t M = (int64_t)p.N * HW;
+    const int Ho = S == 1 ? p.H : p.Ho, Wo = S == 1 ? p.W : p.Wo;
+    const int HW = p.H * p.W, HWo = Ho * Wo;
+    const int64_t M = (int64_t)p.N * HWo;
     const int64_t p_begin = (int64_t)blockIdx.y * p.chunk;
     const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
-    f32x4 acc[9];
+    f32x4 acc[ROWS];
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) acc[tap] = f32x4{0, 0, 0, 0};
+    for (int row = 0; row < ROWS; ++row) acc[row] = f32x4{0, 0, 0, 0};
     if (c_in)
         for (int64_t px = p_begin + pl; px < p_end; px += DW_PL) {
             const f32x4 z = *(const f32x4*)(p.dz + px * p.dz_ld + c);
-            const int64_t n = px / HW;
-            const int r = (int)(px % HW);
-            const int y = r / p.W, x = r % p.W;
+            const int64_t n = px / HWo;
+            const int r = (int)(px % HWo);
+            const int y0 = S * (r / Wo) - D, x0 = S * (r % Wo) - D;      // the source of tap 0
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                const int sy = y + tap / 3 - 1, sx = x + tap % 3 - 1;
-                if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) continue;
+                const int sy = y0 + D * (tap / 3), sx = x0 + D * (tap % 3);
+                if ((unsigned)sy >= (unsigned)p.H || (unsigned)sx >= (unsigned)p.W) continue;      // outside the map, below 0 too
                 const f32x4 xv = *(const f32x4*)(p.x + (n * HW + (int64_t)sy * p.W + sx) * p.x_ld + c);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc[tap][k] = fmaf(z[k], xv[k], acc[tap][k]);
             }
+            if constexpr (SUM) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[9][k] = acc[9][k] + z[k];
+            }
         }
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) *(f32x4*)(red + (pl * 9 + tap) * DW_CG + cq) = acc[tap];
+    for (int row = 0; row < ROWS; ++row) *(f32x4*)(red + (pl * ROWS + row) * DW_CG + cq) = acc[row];
     __syncthreads();
     for (int st = DW_PL / 2; st > 0; st >>= 1) {
         if (pl < st) {
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                f32x4* a = (f32x4*)(red + (pl * 9 + tap) * DW_CG + cq);
-                const f32x4 b = *(const f32x4*)(red + ((pl + st) * 9 + tap) * DW_CG + cq);
+            for (int row = 0; row < ROWS; ++row) {
+                f32x4* a = (f32x4*)(red + (pl * ROWS + row) * DW_CG + cq);
+                const f32x4 b = *(const f32x4*)(red + ((pl + st) * ROWS + row) * DW_CG + cq);
                 f32x4 v = *a;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = v[k] + b[k];
@@ -590,9 +620,9 @@ __global__ void __launch_bounds__(256) dw_wgrad_kernel(DwGradParams p) {
         __syncthreads();
     }
     if (pl == 0 && c_in) {
-        float* part = p.partial + (size_t)blockIdx.y * 9 * p.C;
+        float* part = p.partial + (size_t)blockIdx.y * ROWS * p.C;
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) *(f32x4*)(part + tap * p.C + c) = *(const f32x4*)(red + tap * DW_CG + cq);
+        for (int row = 0; row < ROWS; ++row) *(f32x4*)(part + row * p.C + c) = *(const f32x4*)(red + row * DW_CG + cq);
     }
 }
 
@@ -608,159 +638,36 @@ void dw_wgrad_plan(int64_t M, int C, int* splits, int* chunk) {
     *splits = (int)((M + ch - 1) / ch);
 }
 
-hipError_t launch_dw_wgrad(const DwGradParams& p, hipStream_t s) {
-    const int64_t M = (int64_t)p.N * p.H * p.W;
+hipError_t launch_dw_wgrad(const DwGradParams& p, bool sum_dz, hipStream_t s) {
+    const int64_t M = (int64_t)p.N * p.Ho * p.Wo;
     if (!dw_grad_shape_ok(p) || !quad_ok(p.x, p.x_ld) || p.C > p.x_ld || !quad_ok(p.partial, 4) || p.splits < 1 || p.splits > 65535 ||
-        p.chunk < DW_PL || (p.chunk % DW_PL) || (int64_t)p.splits * p.chunk < M)
+        p.chunk < DW_PL || (p.chunk % DW_PL) || (int64_t)p.splits * p.chunk < M ||
+        (!sum_dz && (p.stride != 1 || p.dil != 1)))      // nine rows: the cpm's form only, the one network layer kind without BatchNorm
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dw_wgrad_kernel, dim3((unsigned)((p.C + DW_CG - 1) / DW_CG), (unsigned)p.splits), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)((p.C + DW_CG - 1) / DW_CG), (unsigned)p.splits);
+    if (!sum_dz) hipLaunchKernelGGL(HIP_KERNEL_NAME(dw_wgrad_kernel<false, 1, 1>), grid, dim3(256), 0, s, p);
+    else
+        dw_for_sd(p.stride, p.dil, [&](auto S, auto D) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(dw_wgrad_kernel<true, decltype(S)::value, decltype(D)::value>), grid, dim3(256), 0, s, p);
+        });
     return hipGetLastError();
 }
 
-__global__ void __launch_bounds__(256) dw_wgrad_reduce_kernel(DwGradParams p, float* dw, int accumulate) {
-    const int i = blockIdx.x * 256 + threadIdx.x;      // thread i = tap * C + c: neighbouring lanes read neighbouring partials
-    if (i >= 9 * p.C) return;
-    const int tap = i / p.C, c = i % p.C;
+// partials in range order -> dw as OIHW (C, 1, 3, 3) and, where g is given, their tenth row -> g (C); thread i = row * C + c:
+// neighbouring lanes read neighbouring partials
+__global__ void __launch_bounds__(256) dw_wgrad_reduce_kernel(DwGradParams p, float* dw, float* g, int accumulate) {
+    const int rows = g ? 10 : 9;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * p.C) return;
+    const int row = i / p.C, c = i % p.C;
     float sum = 0.0f;
-    for (int z = 0; z < p.splits; ++z) sum += p.partial[(size_t)z * 9 * p.C + i];
-    float* d = dw + c * 9 + tap;                       // OIHW (C, 1, 3, 3)
+    for (int z = 0; z < p.splits; ++z) sum += p.partial[(size_t)z * rows * p.C + i];
+    float* d = row < 9 ? dw + c * 9 + row : g + c;
     *d = accumulate ? *d + sum : sum;
 }
-hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, int accumulate, hipStream_t s) {
+hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, float* g, int accumulate, hipStream_t s) {
     if (p.C < 1 || p.splits < 1 || !p.partial || !dw) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((unsigned)((9 * p.C + 255) / 256)), dim3(256), 0, s, p, dw, accumulate);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------- backbone: depthwise 3x3, stride 1 | 2, dilation 1 | 2
-// (with_mobilenet.py:94-104: conv_dw, padding = dilation, BatchNorm + ReLU behind it.)  The forward is
-// Z[n, oy, ox, c] = sum_k X[n, s oy + d (ky - 1), s ox + d (kx - 1), c] w[k][c] on an Ho x Wo map, Ho = (H - 1) / s + 1.  Same shapes
-// as the cpm's kernels above (a lane owns four channels of a pixel, 16 bytes per access); the cpm keeps its own statements.
-//
-// dX[n, y, x, c] = sum over taps of dZ[n, (y + d - d ky) / s, (x + d - d kx) / s, c] * w[tap][c], over the taps whose source
-// index is divisible by s and inside the Ho x Wo map: one fmaf chain per output in tap order 0..8
-__global__ void __launch_bounds__(256) dw_dgrad_sd_kernel(DwGradSdParams p) {
-    const int C4 = p.C / 4;
-    const int HW = p.H * p.W, HWo = p.Ho * p.Wo;
-    const int64_t total = (int64_t)p.N * HW * C4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t px = i / C4;
-        const int c = (int)(i % C4) * 4;
-        const int64_t n = px / HW;
-        const int r = (int)(px % HW);
-        const int y = r / p.W, x = r % p.W;
-        f32x4 acc = {0, 0, 0, 0};
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ny = y + p.dil - p.dil * (tap / 3), nx = x + p.dil - p.dil * (tap % 3);
-            f32x4 z = {0, 0, 0, 0};
-            if (ny >= 0 && nx >= 0 && ny % p.stride == 0 && nx % p.stride == 0) {
-                const int sy = ny / p.stride, sx = nx / p.stride;
-                if (sy < p.Ho && sx < p.Wo) z = *(const f32x4*)(p.dz + (n * HWo + (int64_t)sy * p.Wo + sx) * p.dz_ld + c);
-            }
-            const f32x4 wv = *(const f32x4*)(p.w + tap * p.C + c);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = fmaf(z[k], wv[k], acc[k]);
-        }
-        f32x4* d = (f32x4*)(p.dx + px * p.dx_ld + c);
-        if (p.beta) {
-            const f32x4 old = *d;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = old[k] + acc[k];
-        }
-        *d = acc;
-    }
-}
-static bool dw_sd_shape_ok(const DwGradSdParams& p) {
-    const int64_t M = (int64_t)p.N * p.H * p.W;
-    return p.N >= 1 && p.H >= 1 && p.W >= 1 && M < (1ll << 31) - BW_T && (p.stride == 1 || p.stride == 2) && (p.dil == 1 || p.dil == 2) &&
-           p.Ho == (p.H - 1) / p.stride + 1 && p.Wo == (p.W - 1) / p.stride + 1 && p.C >= 4 && (p.C & 3) == 0 && p.C <= p.dz_ld &&
-           quad_ok(p.dz, p.dz_ld);
-}
-hipError_t launch_dw_dgrad_sd(const DwGradSdParams& p, hipStream_t s) {
-    if (!dw_sd_shape_ok(p) || !quad_ok(p.w, 4) || !quad_ok(p.dx, p.dx_ld) || p.C > p.dx_ld) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)p.N * p.H * p.W * (p.C / 4);
-    hipLaunchKernelGGL(dw_dgrad_sd_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-// G[c][tap] = sum over output pixels q of dZ[q][c] * X[s q + d (k - 1)][c] and, as a tenth accumulator, g[c] = sum_q dZ[q][c] (the
-// gradient of the folded bias, which the BatchNorm chain rule needs).  The structure is dw_wgrad_kernel's: 64 channels of one
-// range of output pixels (dw_wgrad_plan over N Ho Wo) per workgroup, thread t on the pixels begin + (t >> 4) + 16 k, the 16 pixel
-// lanes added through LDS in the same fixed tree, [10][C] partials per range.
-__global__ void __launch_bounds__(256) dw_wgrad_sd_kernel(DwGradSdParams p) {
-    __shared__ float red[DW_PL * 10 * DW_CG];         // [pixel lane][tap, then the bias sum][channel]: 40 KB
-    const int t = threadIdx.x, cq = (t & 15) * 4, pl = t >> 4;
-    const int c = blockIdx.x * DW_CG + cq;
-    const bool c_in = c < p.C;
-    const int HW = p.H * p.W, HWo = p.Ho * p.Wo;
-    const int64_t M = (int64_t)p.N * HWo;
-    const int64_t p_begin = (int64_t)blockIdx.y * p.chunk;
-    const int64_t p_end = p_begin + p.chunk < M ? p_begin + p.chunk : M;
-    f32x4 acc[10];
-#pragma unroll
-    for (int tap = 0; tap < 10; ++tap) acc[tap] = f32x4{0, 0, 0, 0};
-    if (c_in)
-        for (int64_t px = p_begin + pl; px < p_end; px += DW_PL) {
-            const f32x4 z = *(const f32x4*)(p.dz + px * p.dz_ld + c);
-            const int64_t n = px / HWo;
-            const int r = (int)(px % HWo);
-            const int y = r / p.Wo, x = r % p.Wo;
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int sy = p.stride * y + p.dil * (tap / 3 - 1), sx = p.stride * x + p.dil * (tap % 3 - 1);
-                if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) continue;
-                const f32x4 xv = *(const f32x4*)(p.x + (n * HW + (int64_t)sy * p.W + sx) * p.x_ld + c);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[tap][k] = fmaf(z[k], xv[k], acc[tap][k]);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[9][k] = acc[9][k] + z[k];
-        }
-#pragma unroll
-    for (int tap = 0; tap < 10; ++tap) *(f32x4*)(red + (pl * 10 + tap) * DW_CG + cq) = acc[tap];
-    __syncthreads();
-    for (int st = DW_PL / 2; st > 0; st >>= 1) {
-        if (pl < st) {
-#pragma unroll
-            for (int tap = 0; tap < 10; ++tap) {
-                f32x4* a = (f32x4*)(red + (pl * 10 + tap) * DW_CG + cq);
-                const f32x4 b = *(const f32x4*)(red + ((pl + st) * 10 + tap) * DW_CG + cq);
-                f32x4 v = *a;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = v[k] + b[k];
-                *a = v;
-            }
-        }
-        __syncthreads();
-    }
-    if (pl == 0 && c_in) {
-        float* part = p.partial + (size_t)blockIdx.y * 10 * p.C;
-#pragma unroll
-        for (int tap = 0; tap < 10; ++tap) *(f32x4*)(part + tap * p.C + c) = *(const f32x4*)(red + tap * DW_CG + cq);
-    }
-}
-hipError_t launch_dw_wgrad_sd(const DwGradSdParams& p, hipStream_t s) {
-    const int64_t M = (int64_t)p.N * p.Ho * p.Wo;
-    if (!dw_sd_shape_ok(p) || !quad_ok(p.x, p.x_ld) || p.C > p.x_ld || !quad_ok(p.partial, 4) || p.splits < 1 || p.splits > 65535 ||
-        p.chunk < DW_PL || (p.chunk % DW_PL) || (int64_t)p.splits * p.chunk < M)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dw_wgrad_sd_kernel, dim3((unsigned)((p.C + DW_CG - 1) / DW_CG), (unsigned)p.splits), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-// partials in range order -> G as OIHW (C, 1, 3, 3) and g (C); thread i = row * C + c, row 9 the bias sum
-__global__ void __launch_bounds__(256) dw_wgrad_sd_reduce_kernel(DwGradSdParams p, float* G, float* g) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 10 * p.C) return;
-    const int tap = i / p.C, c = i % p.C;
-    float sum = 0.0f;
-    for (int z = 0; z < p.splits; ++z) sum += p.partial[(size_t)z * 10 * p.C + i];
-    if (tap < 9) G[c * 9 + tap] = sum;
-    else g[c] = sum;
-}
-hipError_t launch_dw_wgrad_sd_reduce(const DwGradSdParams& p, float* G, float* g, hipStream_t s) {
-    if (p.C < 1 || p.splits < 1 || !p.partial || !G || !g) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dw_wgrad_sd_reduce_kernel, dim3((unsigned)((10 * p.C + 255) / 256)), dim3(256), 0, s, p, G, g);
+    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((unsigned)(((g ? 10 : 9) * p.C + 255) / 256)), dim3(256), 0, s, p, dw, g, accumulate);
     return hipGetLastError();
 }
 

@@ -731,6 +731,27 @@ static int prof_end(lwp_context* h, hipStream_t s) {
         if (rc_) return rc_;                       \
     } while (0)
 #define LAUNCH(h, kclass, expr) LAUNCH_ON(h, (h)->stream, kclass, expr)
+// reps profiled runs of enqueue(): per class of its launches, their time per run and (from the first run) their number
+template <typename F> static int profile_by_class(lwp_context* h, int n_classes, int reps, float* ms, int* launches, F&& enqueue) {
+    for (int k = 0; k < n_classes; ++k) { ms[k] = 0.f; launches[k] = 0; }
+    for (int r = 0; r < reps; ++r) {
+        h->profiling = true;
+        h->ev_used = 0;
+        const int rc = enqueue();
+        h->profiling = false;
+        if (rc) return rc;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < h->ev_used; i += 2) {
+            float t = 0.f;
+            HIP_TRY(h, hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
+            const int k = h->ev_class[i / 2];
+            ms[k] += t;
+            if (r == 0) launches[k] += 1;
+        }
+    }
+    for (int k = 0; k < n_classes; ++k) ms[k] /= (float)reps;
+    return LWP_OK;
+}
 
 // ---------------------------------------------------------------------------------------------- batch split
 // The kernels address a tensor with 32-bit byte offsets (buffer loads), so one launch sequence takes at most as many frames
@@ -3905,6 +3926,53 @@ struct BackwardArgs {
     float* d_backbone = nullptr;       // LWP_TRAIN_CPM: the gradient at the cpm's input, N x 512 x hs x ws, or null
 };
 
+// What the backward of one layer of the retaining plan launches with, on its output map of M = N x h x w pixels: the pixel ranges
+// of every weight-gradient launch and the floats of the workspace d_bwd they need.  stage_backward_prepare sizes d_bwd from the
+// maxima over the layers and the walk launches from the same values, so the sizes and the launches cannot drift apart.
+struct PixelRanges { int splits = 0, chunk = 0; };
+struct LayerBackwardPlan {
+    std::vector<PixelRanges> w;        // dense weight gradients: the layer's own (the pointwise half's of an L_DWPW block), or one per
+                                       // source conv of a merged head layer; L_STEM: the stem kernel's
+    PixelRanges dw;                    // L_DW, L_DWPW: the depthwise weight gradient
+    size_t part = 0;                   // partials of the largest of these launches
+    size_t fold = 0;                   // folded G | g in front of the largest BatchNorm chain rule
+    size_t pwf = 0;                    // the folded pointwise matrix of a fused block with BatchNorm
+};
+static LayerBackwardPlan backward_plan(const Layer& l, int64_t M) {
+    LayerBackwardPlan bp;
+    if (l.kind == L_STEM) {                                       // (LWP_TRAIN_ALL) [28][32] partials per range, G (32, 27) | g (32)
+        PixelRanges r;
+        stem_wgrad_plan(M, &r.splits, &r.chunk);
+        bp.w.push_back(r);
+        bp.part = (size_t)r.splits * 28 * 32;
+        bp.fold = (size_t)32 * 27 + 32;
+        return bp;
+    }
+    if (l.kind == L_DW || l.kind == L_DWPW) {
+        const bool bn = !l.bn_key.empty();                        // with BatchNorm: the sum of dZ as a tenth row
+        dw_wgrad_plan(M, l.cin, &bp.dw.splits, &bp.dw.chunk);
+        bp.part = (size_t)bp.dw.splits * (bn ? 10 : 9) * l.cin;
+        if (bn) bp.fold = (size_t)10 * l.cin;
+        if (l.kind == L_DW) return bp;
+        if (!l.bn2_key.empty()) {
+            bp.fold = std::max(bp.fold, (size_t)l.cout * l.cin + l.cout);
+            bp.pwf = (size_t)l.cout * l.cin;
+        }
+    }
+    const int ks = l.kind == L_DWPW ? 1 : l.ks;                   // the pointwise half of a fused block
+    auto one = [&](int cout, int cin) {
+        WgradParams w{};
+        w.cout = cout; w.cin = cin; w.ks = ks;
+        wgrad_plan(M, cout, cin, ks, &w.splits, &w.chunk);
+        bp.w.push_back({w.splits, w.chunk});
+        bp.part = std::max(bp.part, wgrad_partial_floats(w));
+    };
+    if (l.blocks.empty()) one(l.cout, l.cin);
+    else for (const WBlock& b : l.blocks) one(b.cout, b.cin);
+    if (l.kind == L_GEMM && !l.bn_key.empty()) bp.fold = std::max(bp.fold, (size_t)l.cout * l.cin * l.ks * l.ks + l.cout);
+    return bp;
+}
+
 static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     char msg[200];
     int rc = train_handle_check(h);
@@ -3927,41 +3995,16 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
         return fail(h, LWP_ERR_ARG, msg);
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    // workspace: the largest layer's wgrad partials + the folded gradients of the largest BatchNorm layer
+    // workspace: the largest partials of a layer + the folded gradients of the largest BatchNorm layer + the largest folded pointwise matrix
     size_t part = 0, fold = 0, pwf = 0;
     for (size_t i = (size_t)(h->tp.cut + 1); i < h->tp.layers.size(); ++i) {
         const Layer& l = h->tp.layers[i];
-        const int ks = l.kind == L_DWPW ? 1 : l.ks;               // the pointwise half of a fused block
         int lh, lw;                                               // the layer's output map (a backbone layer's may be above level 3)
         level_dims(h->train_H, h->train_W, buf_level(h, l.dst.buf), &lh, &lw);
-        const int64_t M = (int64_t)a.N * lh * lw;
-        auto one = [&](int cout, int cin) {
-            WgradParams w{};
-            w.cout = cout; w.cin = cin; w.ks = ks;
-            wgrad_plan(M, cout, cin, ks, &w.splits, &w.chunk);
-            part = std::max(part, wgrad_partial_floats(w));
-        };
-        if (l.kind == L_STEM) {                                   // (LWP_TRAIN_ALL)
-            int sp = 0, ch = 0;
-            stem_wgrad_plan(M, &sp, &ch);
-            part = std::max(part, (size_t)sp * 28 * 32);
-            fold = std::max(fold, (size_t)32 * 27 + 32);
-            continue;
-        }
-        if (l.kind == L_DW || l.kind == L_DWPW) {
-            int sp = 0, ch = 0;
-            dw_wgrad_plan(M, l.cin, &sp, &ch);
-            part = std::max(part, (size_t)sp * (l.bn_key.empty() ? 9 : 10) * l.cin);      // (with BatchNorm: the sum of dZ too)
-            if (!l.bn_key.empty()) fold = std::max(fold, (size_t)10 * l.cin);
-            if (l.kind == L_DW) continue;
-            if (!l.bn2_key.empty()) {
-                fold = std::max(fold, (size_t)l.cout * l.cin + l.cout);
-                pwf = std::max(pwf, (size_t)l.cout * l.cin);
-            }
-        }
-        if (l.blocks.empty()) one(l.cout, l.cin);
-        else for (const WBlock& b : l.blocks) one(b.cout, b.cin);
-        if (l.kind == L_GEMM && !l.bn_key.empty()) fold = std::max(fold, (size_t)l.cout * l.cin * l.ks * l.ks + l.cout);
+        const LayerBackwardPlan bp = backward_plan(l, (int64_t)a.N * lh * lw);
+        part = std::max(part, bp.part);
+        fold = std::max(fold, bp.fold);
+        pwf = std::max(pwf, bp.pwf);
     }
     part = (part + 63) / 64 * 64;
     fold = (fold + 63) / 64 * 64;
@@ -3982,148 +4025,182 @@ static int stage_backward_prepare(lwp_handle h, const BackwardArgs& a) {
     return order_in(h);
 }
 
-// wgrad of one conv (a whole layer, or one source conv of a merged head layer): partials, fixed-order reduction, and the
-// BatchNorm chain rule where the layer has one
-// (pointwise: the 1x1 half of an L_DWPW block, conv_key its conv2_key; a conv without bias has no bias row and no db)
-static int enqueue_wgrad(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const float* x, int x_ld, int cout, int cin,
-                         const std::string& conv_key, const BackwardArgs& a, size_t fold_off, bool pointwise = false) {
-    const bool has_bias = !pointwise && l.has_bias;
-    const std::string& bn_key = pointwise ? l.bn2_key : l.bn_key;
-    WgradParams w{};
-    w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd.as<float>();
-    w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = pointwise ? 1 : l.ks; w.dil = pointwise ? 1 : l.dil;
-    w.no_bias = (has_bias || !bn_key.empty()) ? 0 : 1;     // the BatchNorm chain rule needs the column sums of dZ, conv bias or not
-    wgrad_plan((int64_t)a.N * a.hs * a.ws, cout, cin, w.ks, &w.splits, &w.chunk);
-    h->bwd_splits[layer_index] = w.splits;
-    LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream, h->bwd_prec));
-    float* dw = a.grads + h->grad_off.at(conv_key + ".weight");
-    float* db = has_bias ? a.grads + h->grad_off.at(conv_key + ".bias") : nullptr;
-    if (bn_key.empty()) {
-        LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, dw, db, a.accumulate, h->stream));
-        return LWP_OK;
+// the gradient buffers of one backward walk: a buffer's first writer overwrites, later ones add (the launch order is the summation order)
+struct GradBuffers {
+    std::vector<char> written;
+    int nb;
+    int adds(const BufRef& r) {                        // for the launch that writes r next: 1 = add to what is there
+        char& w = written[r.buf - nb];
+        const int had = w;
+        w = 1;
+        return had;
     }
-    float* G = h->d_bwd.as<float>() + fold_off;
-    float* g = G + (size_t)cout * cin * w.ks * w.ks;
-    LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, G, g, 0, h->stream));
+};
+
+// g = g * act'(z) from the retained output y: ELU from y itself, ReLU as the mask y > res (res null: y > 0)
+static int enqueue_act_grad(lwp_context* h, int act, float* g, int g_ld, const float* y, int y_ld, const float* res, int res_ld, int64_t M, int C) {
+    if (act == ACT_ELU) LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(g, g_ld, y, y_ld, M, C, h->stream));
+    if (act == ACT_RELU) LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(g, g_ld, y, y_ld, res, res_ld, M, C, h->stream));
+    return LWP_OK;
+}
+
+// BatchNorm chain rule behind a conv: folded G, g in the workspace -> dW, db (with a conv bias), dgamma, dbeta in the gradient array
+static int enqueue_bn_chain(lwp_context* h, const std::string& conv_key, const std::string& bn_key, bool has_bias, const float* G, const float* g,
+                            int cout, int K, const BackwardArgs& a) {
     BnChainParams b{};
     b.G = G; b.g = g;
     b.W = h->raw(conv_key + ".weight"); b.b = has_bias ? h->raw(conv_key + ".bias") : h->d_zeros.as<float>();   // (1024 zeros: the backbone's cout is at most 512)
     b.gamma = h->raw(bn_key + ".weight");
     b.mean = h->raw(bn_key + ".running_mean"); b.var = h->raw(bn_key + ".running_var");
-    b.dW = dw; b.db = db;
-    b.dgamma = a.grads + h->grad_off.at(bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(bn_key + ".bias");
-    b.cout = cout; b.K = cin * w.ks * w.ks; b.accumulate = a.accumulate;
-    LAUNCH(h, BK_REDUCE, launch_bn_chain(b, h->stream));
-    return LWP_OK;
-}
-
-// depthwise 3x3 of the cpm trunk (an L_DW layer, or the first half of an L_DWPW block): dz is the gradient at its ELU output y
-static int enqueue_dw_backward(lwp_context* h, const Layer& l, int layer_index, float* dz, int dz_ld, const float* y, int y_ld,
-                               const BackwardArgs& a, std::vector<char>& written) {
-    const int nb = (int)h->g.bufs.size();
-    const int64_t M = (int64_t)a.N * a.hs * a.ws;
-    LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(dz, dz_ld, y, y_ld, M, l.cin, h->stream));
-    DwGradParams p{};
-    p.dz = dz; p.dz_ld = dz_ld; p.x = buf_at(h, l.src); p.x_ld = l.src.ld; p.w = h->blob(l.w_off);
-    p.dx = grad_at(h, l.src); p.dx_ld = l.src.ld; p.partial = h->d_bwd.as<float>();
-    p.N = a.N; p.H = a.hs; p.W = a.ws; p.C = l.cin; p.beta = written[l.src.buf - nb];
-    dw_wgrad_plan(M, l.cin, &p.splits, &p.chunk);
-    h->bwd_dw_splits[layer_index] = p.splits;
-    if (l.kind == L_DW) h->bwd_splits[layer_index] = p.splits;
-    LAUNCH(h, BK_WGRAD, launch_dw_wgrad(p, h->stream));
-    LAUNCH(h, BK_REDUCE, launch_dw_wgrad_reduce(p, a.grads + h->grad_off.at(l.conv_key + ".weight"), a.accumulate, h->stream));
-    LAUNCH(h, BK_DGRAD, launch_dw_dgrad(p, h->stream));
-    written[l.src.buf - nb] = 1;
-    return LWP_OK;
-}
-
-// BatchNorm chain rule of a backbone conv without bias: folded G, g in the workspace -> dW, dgamma, dbeta in the gradient array
-static int enqueue_bn_chain_nobias(lwp_context* h, const std::string& conv_key, const std::string& bn_key, float* G, float* g, int cout, int K,
-                                   const BackwardArgs& a) {
-    BnChainParams b{};
-    b.G = G; b.g = g;
-    b.W = h->raw(conv_key + ".weight"); b.b = h->d_zeros.as<float>();
-    b.gamma = h->raw(bn_key + ".weight");
-    b.mean = h->raw(bn_key + ".running_mean"); b.var = h->raw(bn_key + ".running_var");
-    b.dW = a.grads + h->grad_off.at(conv_key + ".weight"); b.db = nullptr;
+    b.dW = a.grads + h->grad_off.at(conv_key + ".weight"); b.db = has_bias ? a.grads + h->grad_off.at(conv_key + ".bias") : nullptr;
     b.dgamma = a.grads + h->grad_off.at(bn_key + ".weight"); b.dbeta = a.grads + h->grad_off.at(bn_key + ".bias");
     b.cout = cout; b.K = K; b.accumulate = a.accumulate;
     LAUNCH(h, BK_REDUCE, launch_bn_chain(b, h->stream));
     return LWP_OK;
 }
 
-// depthwise 3x3 of the backbone (an L_DW layer, or the first half of an L_DWPW block), stride 1 | 2, dilation 1 | 2, BatchNorm
-// behind it: dz is the gradient at its pre-activation output (the ReLU mask is applied), a.hs x a.ws its output map
-static int enqueue_dw_sd_backward(lwp_context* h, const Layer& l, int layer_index, const float* dz, int dz_ld, const BackwardArgs& a,
-                                  std::vector<char>& written) {
-    const int nb = (int)h->g.bufs.size();
-    DwGradSdParams p{};
+static DgradParams dgrad_params(const float* dz, int dz_ld, const float* w, int cout_pad, int cin_pad, float* dx, int dx_ld, int acc_from,
+                                int N, int H, int W, int cout, int cin, int ks, int dil) {
+    DgradParams d{};
+    d.dz = dz; d.dz_ld = dz_ld; d.w = w; d.dx = dx; d.dx_ld = dx_ld;
+    d.N = N; d.H = H; d.W = W; d.cout = cout; d.cout_pad = cout_pad; d.cin = cin; d.cin_pad = cin_pad; d.ks = ks; d.dil = dil; d.acc_from = acc_from;
+    return d;
+}
+
+// wgrad of one conv (a whole layer, or one source conv of a merged head layer) over the plan's pixel ranges: partials, fixed-order
+// reduction, and the BatchNorm chain rule where the layer has one
+// (pointwise: the 1x1 half of an L_DWPW block, conv_key its conv2_key; a conv without bias has no bias row and no db)
+static int enqueue_wgrad(lwp_context* h, const Layer& l, const float* dz, int dz_ld, const float* x, int x_ld, int cout, int cin,
+                         const std::string& conv_key, const BackwardArgs& a, PixelRanges r, bool pointwise = false) {
+    const bool has_bias = !pointwise && l.has_bias;
+    const std::string& bn_key = pointwise ? l.bn2_key : l.bn_key;
+    WgradParams w{};
+    w.dz = dz; w.dz_ld = dz_ld; w.x = x; w.x_ld = x_ld; w.partial = h->d_bwd.as<float>();
+    w.N = a.N; w.H = a.hs; w.W = a.ws; w.cout = cout; w.cin = cin; w.ks = pointwise ? 1 : l.ks; w.dil = pointwise ? 1 : l.dil;
+    w.no_bias = (has_bias || !bn_key.empty()) ? 0 : 1;     // the BatchNorm chain rule needs the column sums of dZ, conv bias or not
+    w.splits = r.splits; w.chunk = r.chunk;
+    LAUNCH(h, BK_WGRAD, launch_wgrad(w, h->stream, h->bwd_prec));
+    if (bn_key.empty()) {
+        float* db = has_bias ? a.grads + h->grad_off.at(conv_key + ".bias") : nullptr;
+        LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, a.grads + h->grad_off.at(conv_key + ".weight"), db, a.accumulate, h->stream));
+        return LWP_OK;
+    }
+    float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
+    float* g = G + (size_t)cout * cin * w.ks * w.ks;
+    LAUNCH(h, BK_REDUCE, launch_wgrad_reduce(w, G, g, 0, h->stream));
+    return enqueue_bn_chain(h, conv_key, bn_key, has_bias, G, g, cout, cin * w.ks * w.ks, a);
+}
+
+// the stem (LWP_TRAIN_ALL): its weight gradient only, there is no gradient at the image.  dz: the gradient at its pre-activation output
+static int enqueue_stem_wgrad(lwp_context* h, const Layer& l, const float* dz, const BackwardArgs& a, PixelRanges r) {
+    StemWgradParams p{};
+    p.dz = dz; p.dz_ld = l.dst.ld; p.x = h->d_train_in.as<float>(); p.partial = h->d_bwd.as<float>();
+    p.N = a.N; p.H = h->train_H; p.W = h->train_W; p.Ho = a.hs; p.Wo = a.ws;
+    p.splits = r.splits; p.chunk = r.chunk;
+    float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
+    float* g = G + 32 * 27;
+    LAUNCH(h, BK_WGRAD, launch_stem_wgrad(p, h->stream));
+    LAUNCH(h, BK_REDUCE, launch_stem_wgrad_reduce(p, G, g, h->stream));
+    return enqueue_bn_chain(h, l.conv_key, l.bn_key, false, G, g, 32, 27, a);
+}
+
+// depthwise 3x3 (an L_DW layer, or the first half of an L_DWPW block): dz is the gradient at its activation output y, on the
+// layer's a.hs x a.ws output map.  The cpm's has an ELU behind it and no BatchNorm: its weight gradient goes straight to the
+// gradient array.  The backbone's (stride 1 | 2, dilation 1 | 2) has BatchNorm + ReLU: folded G | g, then the chain rule.
+static int enqueue_dw_backward(lwp_context* h, const Layer& l, float* dz, int dz_ld, const float* y, int y_ld, const BackwardArgs& a,
+                               PixelRanges r, GradBuffers& gb) {
+    int rc = enqueue_act_grad(h, l.act, dz, dz_ld, y, y_ld, nullptr, 0, (int64_t)a.N * a.hs * a.ws, l.cin);
+    if (rc) return rc;
+    DwGradParams p{};
     p.dz = dz; p.dz_ld = dz_ld; p.x = buf_at(h, l.src); p.x_ld = l.src.ld; p.w = h->blob(l.w_off);
     p.dx = grad_at(h, l.src); p.dx_ld = l.src.ld; p.partial = h->d_bwd.as<float>();
     level_dims(h->train_H, h->train_W, buf_level(h, l.src.buf), &p.H, &p.W);
-    p.N = a.N; p.Ho = a.hs; p.Wo = a.ws; p.C = l.cin; p.stride = l.stride; p.dil = l.dil; p.beta = written[l.src.buf - nb];
-    dw_wgrad_plan((int64_t)a.N * a.hs * a.ws, l.cin, &p.splits, &p.chunk);
-    h->bwd_dw_splits[layer_index] = p.splits;
-    if (l.kind == L_DW) h->bwd_splits[layer_index] = p.splits;
-    float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
-    float* g = G + (size_t)9 * l.cin;
-    LAUNCH(h, BK_WGRAD, launch_dw_wgrad_sd(p, h->stream));
-    LAUNCH(h, BK_REDUCE, launch_dw_wgrad_sd_reduce(p, G, g, h->stream));
-    const int rc = enqueue_bn_chain_nobias(h, l.conv_key, l.bn_key, G, g, l.cin, 9, a);
-    if (rc) return rc;
-    LAUNCH(h, BK_DGRAD, launch_dw_dgrad_sd(p, h->stream));
-    written[l.src.buf - nb] = 1;
+    p.N = a.N; p.Ho = a.hs; p.Wo = a.ws; p.C = l.cin; p.stride = l.stride; p.dil = l.dil; p.beta = gb.adds(l.src);
+    p.splits = r.splits; p.chunk = r.chunk;
+    const bool bn = !l.bn_key.empty();
+    LAUNCH(h, BK_WGRAD, launch_dw_wgrad(p, bn, h->stream));
+    if (bn) {
+        float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
+        float* g = G + (size_t)9 * l.cin;
+        LAUNCH(h, BK_REDUCE, launch_dw_wgrad_reduce(p, G, g, 0, h->stream));
+        rc = enqueue_bn_chain(h, l.conv_key, l.bn_key, false, G, g, l.cin, 9, a);
+        if (rc) return rc;
+    } else
+        LAUNCH(h, BK_REDUCE, launch_dw_wgrad_reduce(p, a.grads + h->grad_off.at(l.conv_key + ".weight"), nullptr, a.accumulate, h->stream));
+    LAUNCH(h, BK_DGRAD, launch_dw_dgrad(p, h->stream));
     return LWP_OK;
 }
 
-// one backbone layer (LWP_TRAIN_ALL; with_mobilenet.py:92-105): conv without bias, BatchNorm at its running statistics, ReLU
-static int enqueue_backbone_backward(lwp_context* h, const Layer& l, int i, const BackwardArgs& a, std::vector<char>& written) {
+// a fused block, dy the gradient at its pre-activation output: the pointwise half on the retained copy of the depthwise half's
+// output, then the depthwise half.  The blob holds the pointwise weights in fragment order only, so the 1x1 dgrad reads the raw
+// (cout, cin) matrix: without BatchNorm (the cpm) the raw values are the folded ones, with it (the backbone) the folded matrix
+// is made from the raw parameters for this launch.
+static int enqueue_dwpw_backward(lwp_context* h, const Layer& l, int i, const float* dy, const BackwardArgs& a, const LayerBackwardPlan& bp,
+                                 GradBuffers& gb) {
+    const float* dcopy = h->tbufs[h->tp.dw_copy[i] - gb.nb].as<float>();
+    float* gd = h->gbufs[h->tp.dw_copy[i] - gb.nb].as<float>();
+    const int rc = enqueue_wgrad(h, l, dy, l.dst.ld, dcopy, l.cin, l.cout, l.cin, l.conv2_key, a, bp.w[0], true);
+    if (rc) return rc;
+    const float* w = h->raw(l.conv2_key + ".weight");
+    if (!l.bn2_key.empty()) {
+        float* wf = h->d_bwd.as<float>() + h->bwd_pw_off;
+        LAUNCH(h, BK_ELEMENTWISE, launch_pw_fold(w, h->raw(l.bn2_key + ".weight"), h->raw(l.bn2_key + ".running_var"), wf, l.cout, l.cin, h->stream));
+        w = wf;
+    }
+    const DgradParams d = dgrad_params(dy, l.dst.ld, w, l.cout, l.cin, gd, l.cin, l.cin, a.N, a.hs, a.ws, l.cout, l.cin, 1, 1);
+    LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
+    return enqueue_dw_backward(h, l, gd, l.cin, dcopy, l.cin, a, bp.dw, gb);
+}
+
+// one layer of the walk.  a: the call's arguments, its hs x ws the level-3 map of the stages and the cpm
+static int enqueue_layer_backward(lwp_context* h, int i, const BackwardArgs& a, GradBuffers& gb) {
     const TrainPlan& tp = h->tp;
-    const int nb = (int)h->g.bufs.size();
-    BackwardArgs al = a;                               // the layer's own output map
+    const Graph& g = h->g;
+    const Layer& l = tp.layers[i];
+    const int nb = gb.nb, C = g.C, catc = g.cat_channels;
+    BackwardArgs al = a;                               // the layer's own output map (a backbone layer's may be above level 3)
     level_dims(h->train_H, h->train_W, buf_level(h, l.dst.buf), &al.hs, &al.ws);
     const int64_t M = (int64_t)al.N * al.hs * al.ws;
+    const LayerBackwardPlan bp = backward_plan(l, M);
+    h->bwd_splits[i] = bp.w.empty() ? bp.dw.splits : bp.w.back().splits;
+    h->bwd_dw_splits[i] = bp.dw.splits;
     float* dy = grad_at(h, l.dst);
-    LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(dy, l.dst.ld, buf_at(h, l.dst), l.dst.ld, nullptr, 0, M, l.cout, h->stream));
-    if (l.kind == L_STEM) {                            // weight gradient only: there is no gradient at the image
-        StemWgradParams p{};
-        p.dz = dy; p.dz_ld = l.dst.ld; p.x = h->d_train_in.as<float>(); p.partial = h->d_bwd.as<float>();
-        p.N = al.N; p.H = h->train_H; p.W = h->train_W; p.Ho = al.hs; p.Wo = al.ws;
-        stem_wgrad_plan(M, &p.splits, &p.chunk);
-        h->bwd_splits[i] = p.splits;
-        float* G = h->d_bwd.as<float>() + h->bwd_fold_off;
-        float* g = G + 32 * 27;
-        LAUNCH(h, BK_WGRAD, launch_stem_wgrad(p, h->stream));
-        LAUNCH(h, BK_REDUCE, launch_stem_wgrad_reduce(p, G, g, h->stream));
-        return enqueue_bn_chain_nobias(h, l.conv_key, l.bn_key, G, g, 32, 27, al);
+    const float* y = buf_at(h, l.dst);
+    if (i == tp.cpm_in && a.d_backbone)                // LWP_TRAIN_ALL: the backbone's last layer (in LWP_TRAIN_CPM the walk ends above it: step 3)
+        LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(dy, l.dst.ld, a.d_backbone, a.N, a.hs * a.ws, l.cout, h->stream));
+    if (i == tp.cpm_conv && tp.cut != tp.cpm_conv) {
+        // LWP_TRAIN_CPM: cpm.conv's output feeds the initial stage and every refinement stage; its gradient is their sum in
+        // stage order (step 3 below does the same for d_features, on the same values in the same order)
+        for (int k = 1; k < g.nref; ++k)
+            LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(dy, catc, h->gbufs[tp.cats[k] - nb].as<float>(), catc, M, C, 1, h->stream));
+        if (a.d_features) LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(dy, catc, a.d_features, a.N, a.hs * a.ws, C, h->stream));
     }
-    if (l.kind == L_DW) return enqueue_dw_sd_backward(h, l, i, dy, l.dst.ld, al, written);
-    DgradParams d{};
-    d.dz = dy; d.dz_ld = l.dst.ld;
-    d.N = al.N; d.H = al.hs; d.W = al.ws; d.cout = l.cout; d.cin = l.cin; d.ks = 1; d.dil = 1;
-    if (l.kind == L_GEMM) {                            // an unfused pointwise layer: the blob's [cout_pad][cin_pad] copy holds the folded weights
-        const int rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, buf_at(h, l.src), l.src.ld, l.cout, l.cin, l.conv_key, al, h->bwd_fold_off);
-        if (rc) return rc;
-        d.w = h->blob(l.w_off); d.cout_pad = l.cout_pad; d.cin_pad = l.cin_pad;
-        d.dx = grad_at(h, l.src); d.dx_ld = l.src.ld; d.acc_from = written[l.src.buf - nb] ? 0 : l.cin;
-        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
-        written[l.src.buf - nb] = 1;
-        return LWP_OK;
-    }
-    // a fused block: the pointwise half on the retained depthwise copy (its folded weights exist in fragment order only, so the
-    // plain matrix is folded from the raw parameters for this launch), then the depthwise half
-    const float* dcopy = h->tbufs[tp.dw_copy[i] - nb].as<float>();
-    float* gd = h->gbufs[tp.dw_copy[i] - nb].as<float>();
-    int rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, dcopy, l.cin, l.cout, l.cin, l.conv2_key, al, h->bwd_fold_off, true);
+    if (l.res.buf >= 0)                                // out = act(z) + res: the residual branch takes the gradient as it is
+        LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(grad_at(h, l.res), l.res.ld, dy, l.dst.ld, M, l.cout, gb.adds(l.res), h->stream));
+    if (l.kind == L_DW) return enqueue_dw_backward(h, l, dy, l.dst.ld, y, l.dst.ld, al, bp.dw, gb);
+    // the activation behind the layer's last conv; the ELU output in front of a residual add is the retained copy of the launch without it
+    const int act = l.kind == L_DWPW ? l.act2 : l.act;
+    const float* y_act = act == ACT_ELU && tp.nores_copy[i] >= 0 ? h->tbufs[tp.nores_copy[i] - nb].as<float>() : y;
+    int rc = enqueue_act_grad(h, act, dy, l.dst.ld, y_act, l.dst.ld, l.res.buf >= 0 ? buf_at(h, l.res) : nullptr, l.res.ld, M, l.cout);
     if (rc) return rc;
-    float* wf = h->d_bwd.as<float>() + h->bwd_pw_off;
-    LAUNCH(h, BK_ELEMENTWISE, launch_pw_fold(h->raw(l.conv2_key + ".weight"), h->raw(l.bn2_key + ".weight"), h->raw(l.bn2_key + ".running_var"), wf,
-                                             l.cout, l.cin, h->stream));
-    d.w = wf; d.cout_pad = l.cout; d.cin_pad = l.cin;
-    d.dx = gd; d.dx_ld = l.cin; d.acc_from = l.cin;
+    if (l.kind == L_STEM) return enqueue_stem_wgrad(h, l, dy, al, bp.w[0]);
+    if (l.kind == L_DWPW) return enqueue_dwpw_backward(h, l, i, dy, al, bp, gb);
+    const float* x = buf_at(h, l.src);
+    if (l.blocks.empty()) rc = enqueue_wgrad(h, l, dy, l.dst.ld, x, l.src.ld, l.cout, l.cin, l.conv_key, al, bp.w[0]);
+    else
+        for (size_t k = 0; k < l.blocks.size() && !rc; ++k) {
+            const WBlock& b = l.blocks[k];
+            rc = enqueue_wgrad(h, l, dy + b.out_off, l.dst.ld, x + b.in_off, l.src.ld, b.cout, b.cin, b.conv_key, al, bp.w[k]);
+        }
+    if (rc) return rc;
+    if (i == tp.cut + 1 && h->scope == LWP_TRAIN_CPM && !a.d_backbone) return LWP_OK;      // cpm.align's dgrad is 512 wide: only when asked for
+    // a concat buffer's heat / PAF channels already hold the stage's loss gradient; its feature channels are summed over the stages
+    const bool is_cat = std::find(tp.cats.begin(), tp.cats.end(), l.src.buf) != tp.cats.end();
+    const int acc_from = gb.adds(l.src) ? 0 : (is_cat ? C : l.cin);
+    const DgradParams d = dgrad_params(dy, l.dst.ld, h->blob(l.w_off), l.cout_pad, l.cin_pad, grad_at(h, l.src), l.src.ld, acc_from, al.N, al.hs, al.ws,
+                                       l.cout, l.cin, l.ks, l.dil);
     LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
-    LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(gd, l.cin, dcopy, l.cin, nullptr, 0, M, l.cin, h->stream));
-    return enqueue_dw_sd_backward(h, l, i, gd, l.cin, al, written);
+    return LWP_OK;
 }
 
 static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
@@ -4133,7 +4210,6 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
     const int C = g.C, NH = g.NH, NP = g.NP, catc = g.cat_channels;
     const int64_t M = (int64_t)a.N * a.hs * a.ws;
     const int S = 2 * (g.nref + 1);
-    const size_t fold_off = h->bwd_fold_off;
     // 1. dL/d out of every stage, one launch per 16 tensors: from the [heat | paf] window of the stage's concat buffer (the very
     //    values of the NCHW stage tensors) into the same window of its gradient buffer
     for (int s0 = 0; s0 < S; s0 += kLossMaxOuts) {
@@ -4151,81 +4227,14 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
         p.scale = (float)(a.loss_scale / (double)a.batch_size);
         LAUNCH(h, BK_ELEMENTWISE, launch_loss_grad(p, h->stream));
     }
-    // 2. the layers in reverse.  A gradient buffer's first writer overwrites, later ones add: the launch order is the summation order.
-    std::vector<char> written(tp.bufs.size(), 0);
+    // 2. the layers in reverse
+    GradBuffers gb{std::vector<char>(tp.bufs.size(), 0), nb};
     for (int i = (int)tp.layers.size() - 1; i > tp.cut; --i) {
-        const Layer& l = tp.layers[i];
         h->cur_layer = i;
-        if (i <= tp.cpm_in) {                  // LWP_TRAIN_ALL: the backbone, below the cpm's input
-            if (i == tp.cpm_in && a.d_backbone)
-                LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(grad_at(h, l.dst), l.dst.ld, a.d_backbone, a.N, a.hs * a.ws, l.cout, h->stream));
-            const int rc = enqueue_backbone_backward(h, l, i, a, written);
-            if (rc) { h->cur_layer = -1; return rc; }
-            continue;
-        }
-        float* dy = grad_at(h, l.dst);
-        const float* y = buf_at(h, l.dst);
-        if (i == tp.cpm_conv && tp.cut != tp.cpm_conv) {
-            // LWP_TRAIN_CPM: cpm.conv's output feeds the initial stage and every refinement stage; its gradient is their sum in
-            // stage order (step 3 below does the same for d_features, on the same values in the same order)
-            for (int k = 1; k < g.nref; ++k)
-                LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(dy, catc, h->gbufs[tp.cats[k] - nb].as<float>(), catc, M, C, 1, h->stream));
-            if (a.d_features) LAUNCH(h, BK_ELEMENTWISE, launch_nchw_from_nhwc(dy, catc, a.d_features, a.N, a.hs * a.ws, C, h->stream));
-        }
-        if (l.res.buf >= 0) {                  // out = act(z) + res: the residual branch takes the gradient as it is
-            LAUNCH(h, BK_ELEMENTWISE, launch_grad_add(grad_at(h, l.res), l.res.ld, dy, l.dst.ld, M, l.cout, written[l.res.buf - nb], h->stream));
-            written[l.res.buf - nb] = 1;
-        }
-        // the ELU output in front of a residual add is the retained copy of the launch without it
-        const float* y_elu = tp.nores_copy[i] >= 0 ? h->tbufs[tp.nores_copy[i] - nb].as<float>() : y;
-        if (l.kind == L_DW) {
-            const int rc = enqueue_dw_backward(h, l, i, dy, l.dst.ld, y, l.dst.ld, a, written);
-            if (rc) { h->cur_layer = -1; return rc; }
-            continue;
-        }
-        if (l.kind == L_DWPW) {
-            // the pointwise half (raw (cout, C) weights: the blob holds them in fragment order only; without BatchNorm the raw
-            // values are the folded ones), then the depthwise half on the retained copy of its output
-            const float* dcopy = h->tbufs[tp.dw_copy[i] - nb].as<float>();
-            float* gd = h->gbufs[tp.dw_copy[i] - nb].as<float>();
-            LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(dy, l.dst.ld, y_elu, l.dst.ld, M, l.cout, h->stream));
-            int rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, dcopy, l.cin, l.cout, l.cin, l.conv2_key, a, fold_off, true);
-            if (rc) { h->cur_layer = -1; return rc; }
-            DgradParams d{};
-            d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->raw(l.conv2_key + ".weight");
-            d.dx = gd; d.dx_ld = l.cin;
-            d.N = a.N; d.H = a.hs; d.W = a.ws;
-            d.cout = l.cout; d.cout_pad = l.cout; d.cin = l.cin; d.cin_pad = l.cin; d.ks = 1; d.dil = 1; d.acc_from = l.cin;
-            LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
-            rc = enqueue_dw_backward(h, l, i, gd, l.cin, dcopy, l.cin, a, written);
-            if (rc) { h->cur_layer = -1; return rc; }
-            continue;
-        }
-        if (l.act == ACT_ELU) LAUNCH(h, BK_ELEMENTWISE, launch_elu_grad(dy, l.dst.ld, y_elu, l.dst.ld, M, l.cout, h->stream));
-        if (l.act == ACT_RELU)
-            LAUNCH(h, BK_ELEMENTWISE, launch_relu_mask(dy, l.dst.ld, y, l.dst.ld, l.res.buf >= 0 ? buf_at(h, l.res) : nullptr, l.res.ld, M, l.cout, h->stream));
-        const float* x = buf_at(h, l.src);
-        int rc = LWP_OK;
-        if (l.blocks.empty()) rc = enqueue_wgrad(h, l, i, dy, l.dst.ld, x, l.src.ld, l.cout, l.cin, l.conv_key, a, fold_off);
-        else
-            for (const WBlock& b : l.blocks) {
-                rc = enqueue_wgrad(h, l, i, dy + b.out_off, l.dst.ld, x + b.in_off, l.src.ld, b.cout, b.cin, b.conv_key, a, fold_off);
-                if (rc) break;
-            }
-        if (rc) { h->cur_layer = -1; return rc; }
-        if (i == tp.cut + 1 && h->scope == LWP_TRAIN_CPM && !a.d_backbone) continue;      // cpm.align's dgrad is 512 wide: only when asked for
-        const bool is_cat = std::find(tp.cats.begin(), tp.cats.end(), l.src.buf) != tp.cats.end();
-        DgradParams d{};
-        d.dz = dy; d.dz_ld = l.dst.ld; d.w = h->blob(l.w_off);
-        d.dx = grad_at(h, l.src); d.dx_ld = l.src.ld;
-        d.N = a.N; d.H = a.hs; d.W = a.ws;
-        d.cout = l.cout; d.cout_pad = l.cout_pad; d.cin = l.cin; d.cin_pad = l.cin_pad; d.ks = l.ks; d.dil = l.dil;
-        // a concat buffer's heat / PAF channels already hold the stage's loss gradient; its feature channels are summed over the stages
-        d.acc_from = written[l.src.buf - nb] ? 0 : (is_cat ? C : l.cin);
-        LAUNCH(h, BK_DGRAD, launch_dgrad(d, h->stream, h->bwd_prec));
-        written[l.src.buf - nb] = 1;
+        const int rc = enqueue_layer_backward(h, i, a, gb);
+        h->cur_layer = -1;
+        if (rc) return rc;
     }
-    h->cur_layer = -1;
     // 3. backbone_features feeds the initial stage and every refinement stage: stage order, then NCHW
     if (a.d_backbone && tp.cut == tp.cpm_in) {
         const BufRef& xin = tp.layers[tp.cut].dst;
@@ -4242,13 +4251,7 @@ static int enqueue_stage_backward(lwp_context* h, const BackwardArgs& a) {
 
 extern "C" int lwp_stage_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
                                   int batch_size, double loss_scale, int accumulate, float* grads_device, float* d_features_device) {
-    const BackwardArgs a{keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, accumulate, loss_scale, grads_device, d_features_device};
-    int rc = stage_backward_prepare(h, a);
-    if (rc) return rc;
-    rc = enqueue_stage_backward(h, a);
-    if (rc) return rc;
-    bool ordered = false;
-    return order_out(h, h->stream, &ordered);
+    return lwp_train_backward(h, keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, loss_scale, accumulate, grads_device, d_features_device, nullptr);
 }
 
 extern "C" int lwp_train_backward(lwp_handle h, const float* keypoint_maps, const float* paf_maps, const float* mask, int N, int hs, int ws,
@@ -4308,23 +4311,7 @@ extern "C" int lwp_profile_stage_backward(lwp_handle h, const float* keypoint_ma
     const BackwardArgs a{keypoint_maps, paf_maps, mask, N, hs, ws, batch_size, 0, loss_scale, grads_device, d_features_device};
     int rc = stage_backward_prepare(h, a);
     if (rc) return rc;
-    for (int k = 0; k < BK_COUNT; ++k) { ms[k] = 0.f; launches[k] = 0; }
-    for (int r = 0; r < reps; ++r) {
-        h->profiling = true;
-        h->ev_used = 0;
-        rc = enqueue_stage_backward(h, a);
-        h->profiling = false;
-        if (rc) return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i < h->ev_used; i += 2) {
-            float t = 0.f;
-            HIP_TRY(h, hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-            const int k = h->ev_class[i / 2];
-            ms[k] += t / (float)reps;
-            if (r == 0) launches[k] += 1;
-        }
-    }
-    return LWP_OK;
+    return profile_by_class(h, BK_COUNT, reps, ms, launches, [&]() { return enqueue_stage_backward(h, a); });
 }
 
 extern "C" int lwp_stage_grad_count(int nref, int C, int NH, int NP, int64_t* total_floats) {
@@ -4411,28 +4398,45 @@ extern "C" int lwp_debug_backward_dw_splits(lwp_handle h, int idx) {
     return h->bwd_dw_splits[idx];
 }
 
-// the backbone's gradient kernels alone (tests): crafted tensors in, results out, the partials in a scratch allocation
+// the gradient kernels alone (tests): crafted tensors in, results out, the partials in a scratch allocation.
+// Ranges of at most max_chunk pixels (0: the plan's own), so that a small tensor runs several of them
+static void clamp_chunk(int64_t M, int max_chunk, int* splits, int* chunk) {
+    if (max_chunk > 0 && *chunk > max_chunk) { *chunk = max_chunk; *splits = (int)((M + max_chunk - 1) / max_chunk); }
+}
+
+// the depthwise family (lwp_debug_dw_grad: the cpm's form, windows, beta, accumulate; lwp_debug_dw_grad_sd: the backbone's, with
+// stride, dilation and the sum of dZ): the entry points check their arguments, fill the parameters here and run them below
+static DwGradParams debug_dw_params(const float* dz, int dz_ld, const float* x, int x_ld, const float* w, float* dx, int dx_ld, int N, int H, int W,
+                                    int C, int stride, int dil, int beta, int max_chunk) {
+    DwGradParams p{};
+    p.dz = dz; p.dz_ld = dz_ld; p.x = x; p.x_ld = x_ld; p.w = w; p.dx = dx; p.dx_ld = dx_ld;
+    p.N = N; p.H = H; p.W = W; p.Ho = (H - 1) / stride + 1; p.Wo = (W - 1) / stride + 1; p.C = C; p.stride = stride; p.dil = dil; p.beta = beta;
+    const int64_t M = (int64_t)N * p.Ho * p.Wo;
+    dw_wgrad_plan(M, C, &p.splits, &p.chunk);
+    clamp_chunk(M, max_chunk, &p.splits, &p.chunk);
+    return p;
+}
+// g null: nine rows of partials, dw written with `accumulate`; else ten, the tenth summed into g
+static int debug_dw_grad(lwp_context* h, DwGradParams p, float* dw, float* g, int accumulate, int* splits) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    DevBuf part;
+    HIP_TRY(h, part.ensure((size_t)p.splits * (g ? 10 : 9) * p.C * sizeof(float)));
+    p.partial = part.as<float>();
+    HIP_TRY(h, launch_dw_wgrad(p, g != nullptr, h->stream));
+    HIP_TRY(h, launch_dw_wgrad_reduce(p, dw, g, accumulate, h->stream));
+    HIP_TRY(h, launch_dw_dgrad(p, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *splits = p.splits;
+    return LWP_OK;
+}
+
 extern "C" int lwp_debug_dw_grad_sd(lwp_handle h, const float* dz, const float* x, const float* w, int N, int H, int W, int C, int stride, int dil,
                                     int max_chunk, float* dx, float* G, float* g, int* splits) {
     if (!h || !dz || !x || !w || !dx || !G || !g || !splits) return fail(h, LWP_ERR_ARG, "null argument");
     if (N < 1 || H < 1 || W < 1 || C < 4 || (C & 3) || (stride != 1 && stride != 2) || (dil != 1 && dil != 2) || max_chunk < 0 || (max_chunk & 15))
         return fail(h, LWP_ERR_ARG, "bad shape (C a multiple of 4, stride and dilation 1 or 2, max_chunk a multiple of 16)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    DwGradSdParams p{};
-    p.dz = dz; p.dz_ld = C; p.x = x; p.x_ld = C; p.w = w; p.dx = dx; p.dx_ld = C;
-    p.N = N; p.H = H; p.W = W; p.Ho = (H - 1) / stride + 1; p.Wo = (W - 1) / stride + 1; p.C = C; p.stride = stride; p.dil = dil; p.beta = 0;
-    const int64_t M = (int64_t)N * p.Ho * p.Wo;
-    dw_wgrad_plan(M, C, &p.splits, &p.chunk);
-    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
-    DevBuf part;
-    HIP_TRY(h, part.ensure((size_t)p.splits * 10 * C * sizeof(float)));
-    p.partial = part.as<float>();
-    HIP_TRY(h, launch_dw_wgrad_sd(p, h->stream));
-    HIP_TRY(h, launch_dw_wgrad_sd_reduce(p, G, g, h->stream));
-    HIP_TRY(h, launch_dw_dgrad_sd(p, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *splits = p.splits;
-    return LWP_OK;
+    const DwGradParams p = debug_dw_params(dz, C, x, C, w, dx, C, N, H, W, C, stride, dil, 0, max_chunk);
+    return debug_dw_grad(h, p, G, g, 0, splits);
 }
 
 extern "C" int lwp_debug_stem_wgrad(lwp_handle h, const float* dz, const float* x, int N, int H, int W, int max_chunk, float* G, float* g, int* splits) {
@@ -4444,7 +4448,7 @@ extern "C" int lwp_debug_stem_wgrad(lwp_handle h, const float* dz, const float* 
     p.N = N; p.H = H; p.W = W; p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
     const int64_t M = (int64_t)N * p.Ho * p.Wo;
     stem_wgrad_plan(M, &p.splits, &p.chunk);
-    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    clamp_chunk(M, max_chunk, &p.splits, &p.chunk);
     DevBuf part;
     HIP_TRY(h, part.ensure((size_t)p.splits * 28 * 32 * sizeof(float)));
     p.partial = part.as<float>();
@@ -4490,13 +4494,11 @@ extern "C" int lwp_debug_conv_grad(lwp_handle h, const float* dz, int dz_ld, int
     p.N = N; p.H = H; p.W = W; p.cout = cout; p.cin = cin; p.ks = ks; p.dil = dil; p.no_bias = no_bias ? 1 : 0;
     const int64_t M = (int64_t)N * H * W;
     wgrad_plan(M, cout, cin, ks, &p.splits, &p.chunk);
-    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    clamp_chunk(M, max_chunk, &p.splits, &p.chunk);
     if (p.splits > 65535) return fail(h, LWP_ERR_ARG, "too many pixel ranges");
     HIP_TRY(h, part.ensure(wgrad_partial_floats(p) * sizeof(float)));
     p.partial = part.as<float>();
-    DgradParams d{};
-    d.dz = p.dz; d.dz_ld = dz_ld; d.w = wbuf.as<float>(); d.dx = dx + dx_off; d.dx_ld = dx_ld;
-    d.N = N; d.H = H; d.W = W; d.cout = cout; d.cout_pad = cout_pad; d.cin = cin; d.cin_pad = cin_pad; d.ks = ks; d.dil = dil; d.acc_from = acc_from;
+    const DgradParams d = dgrad_params(p.dz, dz_ld, wbuf.as<float>(), cout_pad, cin_pad, dx + dx_off, dx_ld, acc_from, N, H, W, cout, cin, ks, dil);
     HIP_TRY(h, launch_wgrad(p, h->stream, h->bwd_prec));
     HIP_TRY(h, launch_wgrad_reduce(p, dw, db, accumulate ? 1 : 0, h->stream));
     HIP_TRY(h, launch_dgrad(d, h->stream, h->bwd_prec));
@@ -4514,23 +4516,9 @@ extern "C" int lwp_debug_dw_grad(lwp_handle h, const float* dz, int dz_ld, const
         return fail(h, LWP_ERR_ARG, "bad shape (C a multiple of 4, max_chunk a multiple of 16)");
     if (!quad_window_ok(dz, dz_ld, C) || !quad_window_ok(x, x_ld, C) || !quad_window_ok(dx, dx_ld, C) || ((uintptr_t)w & 15))
         return fail(h, LWP_ERR_ARG, "row strides are multiples of 4 and at least C, pointers 16-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    DwGradParams p{};
-    p.dz = dz; p.dz_ld = dz_ld; p.x = x; p.x_ld = x_ld; p.w = w; p.dx = dx; p.dx_ld = dx_ld;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.beta = beta ? 1 : 0;
-    const int64_t M = (int64_t)N * H * W;
-    dw_wgrad_plan(M, C, &p.splits, &p.chunk);
-    if (max_chunk > 0 && p.chunk > max_chunk) { p.chunk = max_chunk; p.splits = (int)((M + max_chunk - 1) / max_chunk); }
+    const DwGradParams p = debug_dw_params(dz, dz_ld, x, x_ld, w, dx, dx_ld, N, H, W, C, 1, 1, beta ? 1 : 0, max_chunk);
     if (p.splits > 65535) return fail(h, LWP_ERR_ARG, "too many pixel ranges");
-    DevBuf part;
-    HIP_TRY(h, part.ensure((size_t)p.splits * 9 * C * sizeof(float)));
-    p.partial = part.as<float>();
-    HIP_TRY(h, launch_dw_wgrad(p, h->stream));
-    HIP_TRY(h, launch_dw_wgrad_reduce(p, dw, accumulate ? 1 : 0, h->stream));
-    HIP_TRY(h, launch_dw_dgrad(p, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *splits = p.splits;
-    return LWP_OK;
+    return debug_dw_grad(h, p, dw, nullptr, accumulate ? 1 : 0, splits);
 }
 
 extern "C" int lwp_debug_loss_grad(lwp_handle h, const float* const* outs, float* const* dst, int S, int ld, const float* keypoint_maps,
@@ -5160,22 +5148,5 @@ extern "C" int lwp_profile_classes(lwp_handle h, const float* in_device, int N, 
     int rc = prepare_poses(h, N, H, W, ratio);
     if (rc) return rc;
     h->last_N = N; h->async_pending = false;
-    for (int k = 0; k < KC_COUNT; ++k) { ms[k] = 0.f; launches[k] = 0; }
-    for (int r = 0; r < reps; ++r) {
-        h->profiling = true;
-        h->ev_used = 0;
-        rc = enqueue_poses(h, in_device, N, H, W, ratio, demo, true);
-        h->profiling = false;
-        if (rc) return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i + 1 < h->ev_used + 1 && i < h->ev_used; i += 2) {
-            float t = 0.f;
-            HIP_TRY(h, hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-            const int k = h->ev_class[i / 2];
-            ms[k] += t;
-            if (r == 0) launches[k] += 1;
-        }
-    }
-    for (int k = 0; k < KC_COUNT; ++k) ms[k] /= (float)reps;
-    return LWP_OK;
+    return profile_by_class(h, KC_COUNT, reps, ms, launches, [&]() { return enqueue_poses(h, in_device, N, H, W, ratio, demo, true); });
 }

@@ -620,39 +620,29 @@ inline size_t wgrad_partial_floats(const WgradParams& p) {
 hipError_t launch_wgrad(const WgradParams& p, hipStream_t s, BwdPrecision bp = BwdPrecision());
 // fixed-order sum of the partials into OIHW dw [cout][cin][taps] and db [cout]; accumulate: added to what is there
 hipError_t launch_wgrad_reduce(const WgradParams& p, float* dw, float* db, int accumulate, hipStream_t s);
-// ---- cpm backward (with_mobilenet.py:7-21): ELU and depthwise 3x3 (stride 1, dilation 1, pad 1) gradients.  C is a multiple
-//      of 4, every row stride too, every pointer 16-byte aligned: a lane moves four consecutive channels of a pixel.
+// ---- depthwise backward: the ELU gradient of the cpm (with_mobilenet.py:7-21) and the gradients of a depthwise 3x3 with stride
+//      1 | 2 and dilation 1 | 2, padding = dilation (the cpm's: 1, 1; the backbone's, with_mobilenet.py:94-104: all four).  C is a
+//      multiple of 4, every row stride too, every pointer 16-byte aligned: a lane moves four consecutive channels of a pixel.
 // g = g * (y > 0 ? 1 : y + 1) over an M x C window, y the retained ELU output (alpha = 1: elu'(z) = exp(z) = y + 1 for z <= 0)
 hipError_t launch_elu_grad(float* g, int g_ld, const float* y, int y_ld, int64_t M, int C, hipStream_t s);
 struct DwGradParams {
-    const float* dz; int dz_ld;      // M x C gradient of the depthwise conv's pre-activation output
-    const float* x; int x_ld;        // wgrad: the retained input, M x C
-    const float* w;                  // dgrad: the forward blob's [9][C]
-    float* dx; int dx_ld;            // dgrad: M x C; beta != 0: added to, else overwritten
-    float* partial;                  // wgrad: [splits][9][C]
-    int N, H, W, C, beta;
-    int splits, chunk;               // wgrad: pixel ranges [z * chunk, (z + 1) * chunk), chunk a multiple of 16
-};
-void dw_wgrad_plan(int64_t M, int C, int* splits, int* chunk);
-hipError_t launch_dw_dgrad(const DwGradParams& p, hipStream_t s);
-hipError_t launch_dw_wgrad(const DwGradParams& p, hipStream_t s);
-// fixed-order sum of the partials into the OIHW (C, 1, 3, 3) gradient; accumulate: added to what is there
-hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, int accumulate, hipStream_t s);
-// ---- backbone backward (with_mobilenet.py:93-104): depthwise 3x3 with stride 1 | 2 and dilation 1 | 2 (padding = dilation), and
-//      the stem's weight gradient.  The depthwise wgrad also sums dZ per channel (the folded bias gradient of its BatchNorm).
-struct DwGradSdParams {
     const float* dz; int dz_ld;      // N Ho Wo x C gradient of the depthwise conv's pre-activation output
     const float* x; int x_ld;        // wgrad: the retained input, N H W x C
-    const float* w;                  // dgrad: the forward blob's [9][C] (folded)
+    const float* w;                  // dgrad: the forward blob's [9][C]
     float* dx; int dx_ld;            // dgrad: N H W x C; beta != 0: added to, else overwritten
-    float* partial;                  // wgrad: [splits][10][C], row 9 the sum of dZ
-    int N, H, W, Ho, Wo, C, stride, dil, beta;
-    int splits, chunk;               // wgrad: ranges of output pixels (dw_wgrad_plan over N Ho Wo)
+    float* partial;                  // wgrad: [splits][rows][C], rows = 9 taps, or 10 with the sum of dZ behind them
+    int N, H, W, Ho, Wo, C, stride, dil, beta;       // Ho = (H - 1) / stride + 1
+    int splits, chunk;               // wgrad: ranges of output pixels [z * chunk, (z + 1) * chunk), chunk a multiple of 16
 };
-hipError_t launch_dw_dgrad_sd(const DwGradSdParams& p, hipStream_t s);
-hipError_t launch_dw_wgrad_sd(const DwGradSdParams& p, hipStream_t s);
-// fixed-order sum of the partials into G, OIHW (C, 1, 3, 3), and g (C); both overwritten
-hipError_t launch_dw_wgrad_sd_reduce(const DwGradSdParams& p, float* G, float* g, hipStream_t s);
+void dw_wgrad_plan(int64_t M, int C, int* splits, int* chunk);      // M = N Ho Wo
+hipError_t launch_dw_dgrad(const DwGradParams& p, hipStream_t s);
+// sum_dz: the partials carry a tenth row, the sum of dZ per channel (the folded bias gradient a BatchNorm chain rule needs);
+// without it stride and dilation are 1 (the cpm's form, the one without BatchNorm)
+hipError_t launch_dw_wgrad(const DwGradParams& p, bool sum_dz, hipStream_t s);
+// fixed-order sum of the partials into the OIHW (C, 1, 3, 3) gradient and, where g is given, of their tenth row into g (C);
+// accumulate: added to what is there
+hipError_t launch_dw_wgrad_reduce(const DwGradParams& p, float* dw, float* g, int accumulate, hipStream_t s);
+// ---- backbone backward (with_mobilenet.py:93-104): the stem's weight gradient, folded pointwise weights, BatchNorm chain rule
 struct StemWgradParams {
     const float* dz; int dz_ld;      // N Ho Wo x 32 gradient of the stem's pre-activation output
     const float* x;                  // N x 3 x H x W, the input the stem kernel read

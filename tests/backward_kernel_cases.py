@@ -17,6 +17,7 @@ import functools
 import numpy as np
 import torch
 
+import backbone_backward_cases as bb
 import backward_cases as bc
 
 U = 2.0 ** -24
@@ -45,6 +46,14 @@ DW_SHAPES = [
     (1, 132, 1, 17),     # M = 17; three channel groups, the last ragged; a one-row map
     (3, 8, 2, 3),        # frames inside one range
 ]
+# the depthwise 3x3 at stride 1 | 2, dilation 1 | 2 (the backbone's forms), ranges of 16 output pixels: (N, C, H, W)
+DW_SD_SHAPES = [
+    (2, 8, 5, 7),        # an odd map; 2 frames, their boundary inside a range
+    (1, 68, 9, 6),       # an even width; a ragged second channel group
+    (1, 4, 2, 3),        # a map smaller than the dilated kernel; a single range
+    (3, 4, 8, 8),        # an even map; 3 frames, 12 ranges (3 at stride 2)
+]
+DW_SD_PAIRS = [(1, 1), (2, 1), (1, 2), (2, 2)]      # (stride, dilation)
 # the second trip of the capped grid-stride loops: the smallest size past each cap
 CAP_8192 = 8192 * 256        # relu_mask, grad_add, elu_grad (quads), dw_dgrad (quads): threads of the capped grid
 CAP_4096 = 4096 * 256        # loss_grad, wgrad_reduce, pw_fold
@@ -287,6 +296,27 @@ def dw_fixture(shape, kind, bound=8, x_bound=8):
         return dict((k, _ints(rs, s, 64 if k.endswith("0") else (x_bound if k == "x" else bound))) for k, s in sizes.items())
     small = dict(dz=1, x=1, w=0, dx0=1, dw0=0)
     return dict((k, _normal(("dw", shape, k), s, small[k])) for k, s in sizes.items())
+
+
+@functools.lru_cache(maxsize=None)
+def dw_sd_fixture(shape, s):
+    """dict(dz, x, w) of a depthwise shape at stride ``s``: the integer fixture of the shape, its dz cut to the Ho x Wo map."""
+    N, C, H, W = shape
+    f = dw_fixture(shape, "int")
+    return dict(dz=np.ascontiguousarray(f["dz"][:, :, :(H - 1) // s + 1, :(W - 1) // s + 1]), x=f["x"], w=f["w"])
+
+
+@functools.lru_cache(maxsize=None)
+def dw_sd_reference(shape, s, d):
+    """(dict(dx, G, g), sum|terms| of each) of dw_sd_fixture by the pixel loops of backbone_backward_cases, int64.  Computed once
+    and shared: do not write to the arrays."""
+    N, C, H, W = shape
+    f = dw_sd_fixture(shape, s)
+    a = np.abs
+    G, g = bb.dw_sd_wgrad_loops(f["dz"], f["x"], s, d)
+    Ga, ga = bb.dw_sd_wgrad_loops(a(f["dz"]), a(f["x"]), s, d)
+    return (dict(dx=bb.dw_sd_dgrad_loops(f["dz"], f["w"], H, W, s, d), G=G, g=g),
+            dict(dx=bb.dw_sd_dgrad_loops(a(f["dz"]), a(f["w"]), H, W, s, d), G=Ga, g=ga))
 
 
 @functools.lru_cache(maxsize=None)

@@ -144,6 +144,36 @@ def test_depthwise_integer_fixtures_are_exact_and_shapes_obey_the_launchers(shap
     assert C >= 4 and C % 4 == 0 and (N * H * W + 15) // 16 <= 65535
 
 
+@pytest.mark.parametrize("s,d", kc.DW_SD_PAIRS)
+@pytest.mark.parametrize("shape", kc.DW_SD_SHAPES, ids=ids(kc.DW_SD_SHAPES))
+def test_strided_depthwise_integer_fixtures_are_exact_and_the_loops_are_float64_autograd(shape, s, d):
+    N, C, H, W = shape
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    f = kc.dw_sd_fixture(shape, s)
+    assert f["dz"].shape == (N, C, Ho, Wo) and f["dz"].dtype == np.int64
+    assert max(np.abs(f[k]).max() for k in ("dz", "x", "w")) <= 8
+    want, terms = kc.dw_sd_reference(shape, s, d)
+    # every sum of |terms| is below 2^24: each partial sum, in any order and any split into ranges, is an exact float32 integer
+    assert kc.max_terms(terms) < kc.EXACT_LIMIT
+    assert all(v.dtype == np.int64 for v in want.values())
+    assert C >= 4 and C % 4 == 0 and (N * Ho * Wo + 15) // 16 <= 65535
+    x, w = T(f["x"].astype(np.float64)).requires_grad_(), T(f["w"].astype(np.float64)).requires_grad_()
+    F.conv2d(x, w, None, s, d, d, C).backward(T(f["dz"].astype(np.float64)))
+    assert np.array_equal(x.grad.numpy(), want["dx"]) and np.array_equal(w.grad.numpy(), want["G"])
+    assert np.array_equal(f["dz"].sum(axis=(0, 2, 3)), want["g"])
+    if (s, d) == (1, 1):                               # the cpm's statements on the same tensors
+        assert np.array_equal(kc.dw_dgrad(f["dz"], f["w"]), want["dx"]) and np.array_equal(kc.dw_wgrad(f["dz"], f["x"]), want["G"])
+
+
+def test_strided_depthwise_shapes_reach_the_edges_they_name():
+    (a, b, c, e), ranges = kc.DW_SD_SHAPES, lambda sh, s: (sh[0] * ((sh[2] - 1) // s + 1) * ((sh[3] - 1) // s + 1) + 15) // 16
+    assert a[2] % 2 and a[3] % 2 and a[0] == 2 and (a[2] * a[3]) % 16            # odd map; the frame boundary is inside a range
+    assert b[3] % 2 == 0 and 64 < b[1] < 128                                     # even width; a ragged second channel group
+    assert c[2] < 3 and c[3] <= 3 and ranges(c, 1) == 1                          # smaller than the kernel at dilation 2 (span 5)
+    assert e[2] % 2 == 0 and e[3] % 2 == 0 and (ranges(e, 1), ranges(e, 2)) == (12, 3)
+    assert all(ranges(sh, 1) > 1 for sh in (a, b, e)) and all(ranges(sh, 2) > 1 for sh in (a, e))
+
+
 def test_second_trip_fixtures_are_exact():
     f = kc.dw_fixture(kc.TRIP_QUADS, "int", 4, 1)
     assert np.abs(f["x"]).max() == 1 and np.abs(f["dz"]).max() == 4

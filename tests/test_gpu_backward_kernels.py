@@ -180,6 +180,30 @@ def test_depthwise_second_trip():
     assert kc.exact_failures(got, want) == []
 
 
+# ---------------------------------------------------------------------------------------------- the same family at stride 1 | 2, dilation 1 | 2
+@pytest.mark.parametrize("s,d", kc.DW_SD_PAIRS)
+@pytest.mark.parametrize("shape", kc.DW_SD_SHAPES, ids=ids(kc.DW_SD_SHAPES))
+def test_strided_depthwise_integer_fixtures_bit_for_bit_against_the_pixel_loops(shape, s, d):
+    """lwp_debug_dw_grad_sd (the backbone's form: dz on the Ho x Wo map, the sum of dZ as a tenth row) in ranges of 16 output
+    pixels: dx, G and g equal the int64 pixel loops on every element.  At (1, 1) the cpm's entry point returns the same bits on
+    the same tensors, integer and normal ones: one kernel family, one order of summation."""
+    N, C, H, W = shape
+    M = N * ((H - 1) // s + 1) * ((W - 1) // s + 1)
+    f = kc.dw_sd_fixture(shape, s)
+    want, _ = kc.dw_sd_reference(shape, s, d)
+    dz, x, w = dev(f["dz"]), dev(f["x"]), dev(f["w"])
+    dx, G, g, splits = twice(lambda: engine().debug_dw_grad(dz, x, w, s, d, max_chunk=16))
+    assert splits == (M + 15) // 16
+    assert kc.exact_failures(dict(dx=host(dx), G=host(G), g=host(g)), want) == [], (shape, s, d)
+    if (s, d) != (1, 1):
+        return
+    fn = kc.dw_fixture(shape, "normal")
+    for dz, x, w in ((dz, x, w), (dev(fn["dz"]), dev(fn["x"]), dev(fn["w"]))):
+        dx, G, _, splits = engine().debug_dw_grad(dz, x, w, 1, 1, max_chunk=16)
+        dx1, dw1, splits1, _ = engine().debug_cpm_dw_grad(dz, x, w, max_chunk=16)
+        assert splits1 == splits and torch.equal(dx1, dx) and torch.equal(dw1, G), shape
+
+
 # ---------------------------------------------------------------------------------------------- element-wise kernels
 ROW_SHAPES = [(2, 8, 3, 5), (1, 68, 1, 7), (1, 4, 1, 1)]
 TRIP_ROW_SHAPE = (1, kc.TRIP_ROWS[1], kc.TRIP_ROWS[0], 1)
