@@ -86,8 +86,11 @@ def lib():
             "lwpose_amd: %s is missing — build it first (python __graft_entry__.py build, or "
             "python lightweight-human-pose-estimation.pytorch_amd/build.py). There is no CPU fallback." % LIB_PATH)
     L = C.CDLL(LIB_PATH)
+    # Array parameters that callers fill from numpy / torch buffers are c_void_p (they pass the address); scalars keep their exact
+    # types and small out-parameters their typed pointers.  tests/test_abi_closure.py holds every list against include/lwpose.h.
     vp, ip, i64p, fp, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
     L.lwp_version.restype = C.c_int
+    results = [vp, vp, C.c_int, vp, C.c_int, vp]          # counts, key-points and their capacity, entries and theirs, entry counts
     L.lwp_param_count.argtypes = [C.c_int] * 4
     L.lwp_param_spec.argtypes = [C.c_int] * 5 + [C.c_char_p, C.c_int, i64p, ip, ip]
     L.lwp_create.argtypes = [C.c_int] * 6 + [C.POINTER(vp)]
@@ -95,27 +98,26 @@ def lib():
     L.lwp_last_error.argtypes = [vp]
     L.lwp_last_error.restype = C.c_char_p
     L.lwp_set_capacity.argtypes = [vp] + [C.c_int] * 4
-    L.lwp_load_weights.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(vp), i64p, ip, C.c_int]
+    L.lwp_load_weights.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(vp), vp, vp, C.c_int]
     L.lwp_weights_blob_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.lwp_weights_blob_export.argtypes = [vp, vp, C.c_size_t]
     L.lwp_weights_blob_import.argtypes = [vp, vp, C.c_size_t]
     L.lwp_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.c_int]
     L.lwp_upsample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
-    L.lwp_extract_keypoints.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int64, i64p, i64p, fp, C.c_int, ip]
-    L.lwp_group_keypoints.argtypes = [vp, vp, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
-    L.lwp_infer_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, vp, C.c_int, vp, C.c_int, ip]
+    L.lwp_extract_keypoints.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, ip]
+    L.lwp_group_keypoints.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
+    L.lwp_infer_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + results
     L.lwp_infer_poses_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.lwp_fetch_poses.argtypes = [vp, ip, vp, C.c_int, vp, C.c_int, ip]
+    L.lwp_fetch_poses.argtypes = [vp] + results
     L.lwp_time_pipeline.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.lwp_profile_classes.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, ip]
     L.lwp_synchronize.argtypes = [vp]
-    L.lwp_poses_from_maps.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, vp, C.c_int, vp, C.c_int, ip]
+    L.lwp_poses_from_maps.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + results
     L.lwp_profile_launches.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, ip, C.c_int, ip]
     L.lwp_debug_time_layer.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.lwp_pipeline_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.lwp_pipeline_fetch.argtypes = [vp, C.c_int, ip, vp, C.c_int, vp, C.c_int, ip]
+    L.lwp_pipeline_fetch.argtypes = [vp, C.c_int] + results
     L.lwp_multiscale_accumulate.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int]
-    dp = C.POINTER(C.c_double)
     L.lwp_preprocess_dims.argtypes = [C.c_int] * 4 + [ip] * 5 + [dp]
     L.lwp_preprocess_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, vp]
     L.lwp_scale_dims.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [ip] * 5
@@ -129,24 +131,24 @@ def lib():
     L.lwp_debug_frames_per_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.lwp_debug_post_counts.argtypes = [vp, C.c_int] + [C.POINTER(C.c_int)] * 4
     L.lwp_debug_f32_to_f16.argtypes = [vp, vp, C.c_int64]
-    L.lwp_set_skeleton.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.c_int, C.c_double]
-    L.lwp_get_skeleton.argtypes = [vp, ip, ip, ip, ip, C.c_int, ip, dp]
+    L.lwp_set_skeleton.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double]
+    L.lwp_get_skeleton.argtypes = [vp, ip, ip, vp, vp, C.c_int, ip, dp]
     L.lwp_debug_post_counts_ex.argtypes = [vp, C.c_int] + [ip] * 4 + [C.c_int, C.c_int]
     L.lwp_debug_post_generic.argtypes = [vp]
     L.lwp_debug_live_resources.argtypes = [i64p]
     L.lwp_debug_graph_fusions.argtypes = [C.c_int] * 7 + [ip, C.c_char_p, C.c_int, C.c_int, ip]
-    L.lwp_set_tracking.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, fp, C.c_int]
+    L.lwp_set_tracking.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.c_int]
     L.lwp_set_unmap.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int]
     L.lwp_reset_tracking.argtypes = [vp, C.c_int, C.c_int]
-    L.lwp_get_poses.argtypes = [vp, C.c_int, ip, ip, dp, ip, ip, ip, C.c_int]
-    L.lwp_track_poses.argtypes = [vp, C.c_int, C.c_int, ip, dp, ip, ip, ip, ip, C.POINTER(C.c_uint)]
-    L.lwp_debug_tracking_near.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), C.c_int]
+    L.lwp_get_poses.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int]
+    L.lwp_track_poses.argtypes = [vp, C.c_int, C.c_int] + [vp] * 5 + [ip, C.POINTER(C.c_uint)]
+    L.lwp_debug_tracking_near.argtypes = [vp, C.c_int, vp, C.c_int]
     L.lwp_preprocess_u8_batch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, vp]
     L.lwp_pipeline_submit_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int]
     L.lwp_set_overlay.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
     L.lwp_get_overlay.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.lwp_draw_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, vp, C.c_int]
-    L.lwp_train_targets.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
+    L.lwp_draw_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int]
+    L.lwp_train_targets.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
     L.lwp_mask_downsample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.lwp_stage_losses.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
     L.lwp_time_train_targets.argtypes = L.lwp_train_targets.argtypes + [C.c_int, fp]
@@ -184,21 +186,21 @@ def lib():
     L.lwp_debug_bn_chain.argtypes = [vp] * 12 + [C.c_int] * 3
     L.lwp_augment_batch.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [vp, vp, vp]
     L.lwp_time_augment_batch.argtypes = L.lwp_augment_batch.argtypes + [C.c_int, fp]
-    L.lwp_crowd_masks.argtypes = [vp, i64p, i64p, i64p, ip, ip, C.c_int, i64p, vp]
+    L.lwp_crowd_masks.argtypes = [vp] * 6 + [C.c_int, vp, vp]
     L.lwp_time_crowd_masks.argtypes = L.lwp_crowd_masks.argtypes + [C.c_int, fp]
-    L.lwp_augment_batch_crowd.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [i64p, i64p, i64p, vp, vp, vp]
-    coco_in = [vp, C.c_int, i64p, dp, dp, i64p, dp, dp, dp, ip, ip]
-    L.lwp_coco_eval.argtypes = coco_in + [dp, dp, dp, i64p]
-    L.lwp_debug_coco_oks.argtypes = coco_in + [C.c_int, ip, ip, dp, C.c_int64, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), ip]
-    L.lwp_coco_open.argtypes = [vp, C.c_int, i64p, dp, dp, dp, ip, ip, C.c_int]
+    L.lwp_augment_batch_crowd.argtypes = [vp, C.POINTER(AugmentPlan)] + [C.c_int] * 4 + [vp] * 6
+    coco_in = [vp, C.c_int] + [vp] * 9
+    L.lwp_coco_eval.argtypes = coco_in + [vp] * 4
+    L.lwp_debug_coco_oks.argtypes = coco_in + [C.c_int, ip, ip, vp, C.c_int64, vp, vp, ip]
+    L.lwp_coco_open.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int]
     L.lwp_coco_release.argtypes = [vp]
     L.lwp_coco_reset.argtypes = [vp]
-    L.lwp_coco_add_maps.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [ip]
-    L.lwp_coco_add_rows.argtypes = [vp, C.c_int, C.c_int, dp, dp]
-    L.lwp_coco_counts.argtypes = [vp, i64p, ip]
-    L.lwp_coco_rows.argtypes = [vp, ip, dp, dp, C.c_int64]
-    L.lwp_coco_finish.argtypes = [vp, dp, dp, dp, i64p]
-    L.lwp_debug_coco_rows.argtypes = [vp, C.c_int, dp, ip, dp, ip, ip]
+    L.lwp_coco_add_maps.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [vp]
+    L.lwp_coco_add_rows.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.lwp_coco_counts.argtypes = [vp, i64p, vp]
+    L.lwp_coco_rows.argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.lwp_coco_finish.argtypes = [vp] * 5
+    L.lwp_debug_coco_rows.argtypes = [vp, C.c_int] + [vp] * 5
     L.lwp_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(JpegHeader)]
     L.lwp_debug_jpeg_blocks.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
     L.lwp_jpeg_decode_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]

@@ -18,12 +18,45 @@ def _torch():
     return torch
 
 
+def _triple(values):
+    """The three doubles of a ``pad_value`` / ``img_mean`` argument."""
+    return (C.c_double * 3)(*[float(v) for v in values])
+
+
+def _stride(stride):
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be at least 1")
+    return stride
+
+
+def _data_or_null(a):
+    """The address of a numpy array's data, None (a null pointer) for an empty one."""
+    return a.ctypes.data if a.size else None
+
+
+def _is_dtype(a, dtype):
+    """``a`` (numpy array or torch tensor) holds elements of the numpy type ``dtype``."""
+    return a.dtype == (dtype if isinstance(a, np.ndarray) else getattr(_torch(), np.dtype(dtype).name))
+
+
 class Engine(object):
     def __init__(self, device_id=0, nref=1, num_channels=128, num_heatmaps=19, num_pafs=38, dtype=_lib.F32):
         self.h = _lib.Handle(device_id, nref, num_channels, num_heatmaps, num_pafs, dtype)
         self.nref, self.C, self.NH, self.NP = nref, num_channels, num_heatmaps, num_pafs
         self.device_id = device_id
-        self._keep = None
+        self._device = None                   # torch.device of the engine's GPU (``_gpu``)
+        self._keep = None                     # tensors behind the raw pointers of the last asynchronous call
+        self._keep_slot = {}                  # pipeline slot -> (cuda tensor kept alive until the slot is fetched, frames)
+        self._overlay_shape = {}              # pipeline slot -> (N, H, W, 3) of the frames pipeline_submit_u8 took
+        self._loss_keep = None                # tensors behind the pointers of the last loss call
+        self._last_N = None                   # frames of the last serial pose-producing call
+        self._skel = None                     # ``skeleton``, read back from the handle on demand
+        self._caps = (2048, 128, 4096, 256)   # set_capacity: the library's defaults
+        self._tracking_mode = 0
+        self._overlay_mode = 0
+        self._jpeg_entropy, self._jpeg_subseq = "host", 0
+        self._gspec = None                    # ``grad_spec`` of the current train scope
         self.stage_steps = 0                  # adam_step calls so far: the drop-in net reads its stage parameters back when this moves
         self.train_scope = "stages"           # set_train_scope: "stages" | "cpm" | "all"
         self._scope_steps = 0                 # stage_steps when the current scope was set
@@ -31,15 +64,79 @@ class Engine(object):
         self._coco_n = 0                      # images of the open detection store (coco_open); 0: none, the library reports it
         self._val_store = None
 
+    # ------------------------------------------------------------------ the library boundary
+    def _call(self, name, *args):
+        """``name(handle, *args)`` of the library; a failure raises what ``check`` makes of the return code and the handle's
+        message.  Every entry point that takes the handle goes through here, but for the few that read the return code."""
+        check(getattr(lib(), name)(self.h.ptr, *args), self.h.ptr)
+
+    def _timed(self, run_name, time_name, args, iters, n_ms=1, tail=()):
+        """``run_name(*args, *tail)``, returning None; or with ``iters`` > 0 its timing twin ``time_name(*args, iters, ms)``,
+        returning the ``n_ms`` millisecond figures it wrote (one float, or a tuple)."""
+        if not iters:
+            self._call(run_name, *args, *tail)
+            return None
+        ms = (C.c_float * n_ms)()
+        self._call(time_name, *args, int(iters), ms)
+        return ms[0] if n_ms == 1 else tuple(ms)
+
+    @property
+    def _gpu(self):
+        if self._device is None:
+            torch = _torch()
+            self._device = torch.device("cuda", self.device_id)
+        return self._device
+
+    def _empty(self, shape, dtype=None):
+        """An uninitialised tensor on the engine's GPU; float32 unless ``dtype`` (a torch dtype) says otherwise."""
+        torch = _torch()
+        return torch.empty(shape, dtype=torch.float32 if dtype is None else dtype, device=self._gpu)
+
+    def _ptr(self, x, dtype=None, what="input", convert=True):
+        """(pointer, MEM_HOST or MEM_DEVICE, the contiguous object behind the pointer) of a numpy array, a cpu tensor or a cuda
+        tensor: the one place a caller's buffer becomes an address.  The caller keeps the third value alive for as long as the
+        library may read the pointer.  ``dtype`` (a numpy type) is the element type the library reads; None leaves the
+        elements as they are, for callers that check the type themselves.  Host data is converted to ``dtype``; a cuda tensor
+        of another type is converted too, or with ``convert=False`` refused (TypeError).  A cuda tensor on another GPU than
+        the engine's is refused (ValueError).  A copy is made only of what is not contiguous or is converted."""
+        if getattr(x, "is_cuda", False):
+            if x.device.index != self.device_id:
+                raise ValueError("%s %s on cuda:%d but the engine lives on cuda:%d"
+                                 % (what, "are" if what.endswith("s") else "is", x.device.index, self.device_id))
+            if dtype is not None and not _is_dtype(x, dtype):
+                if not convert:
+                    raise TypeError("%s must be a %s cuda tensor, got %s" % (what, np.dtype(dtype).name, x.dtype))
+                x = x.to(getattr(_torch(), np.dtype(dtype).name))
+            a = x.detach().contiguous()
+            return a.data_ptr(), MEM_DEVICE, a
+        a = np.ascontiguousarray(x.detach().numpy() if hasattr(x, "detach") else x, dtype=dtype)
+        return a.ctypes.data, MEM_HOST, a
+
+    def _dev32(self, t, what, shape, optional=False):
+        """``t`` as a contiguous float32 cuda tensor of ``shape`` on the engine's GPU (the targets, masks and stage tensors of
+        the loss and the backward); ``optional``: None stays None."""
+        if t is None and optional:
+            return None
+        if not getattr(t, "is_cuda", False):
+            raise TypeError("%s must be a cuda tensor" % what)
+        if tuple(t.shape) != shape:
+            raise ValueError("%s has shape %s, expected %s" % (what, tuple(t.shape), shape))
+        return self._ptr(t, np.float32, what)[2]
+
+    def _stage_shapes(self, N, H, W):
+        """Shapes of the 2 (1 + nref) stage outputs for an (N, 3, H, W) input: three stride-2 layers, out = (in - 1) // 2 + 1."""
+        for _ in range(3):
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        return [(N, self.NP if i % 2 else self.NH, H, W) for i in range(2 * (1 + self.nref))]
+
     # ------------------------------------------------------------------ stream ordering
     def _order(self, device=None, hand_over=True):
         """Order the library's stream against torch's CURRENT stream on this GPU with events (lwp_set_stream): no host block.
         The reference's net(x) runs on the current stream (demo.py:64-68); this gives device tensors the same semantics —
         inputs written by queued torch work are waited for, and torch work queued after the call sees the device results.
         ``hand_over=False``: results left on the device stay on the library's stream (for its own next call)."""
-        torch = _torch()
-        st = torch.cuda.current_stream(torch.device("cuda", self.device_id) if device is None else device)
-        check(lib().lwp_set_stream(self.h.ptr, C.c_void_p(st.cuda_stream), 1 if hand_over else 2), self.h.ptr)
+        st = _torch().cuda.current_stream(self._gpu if device is None else device)
+        self._call("lwp_set_stream", C.c_void_p(st.cuda_stream), 1 if hand_over else 2)
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict):
@@ -59,21 +156,20 @@ class Engine(object):
         for i, a in enumerate(arrs):
             ndims[i] = a.ndim
             shapes[i, :a.ndim] = a.shape
-        check(lib().lwp_load_weights(self.h.ptr, c_names, c_ptrs, shapes.ctypes.data_as(C.POINTER(C.c_int64)),
-                                     ndims.ctypes.data_as(C.POINTER(C.c_int)), n), self.h.ptr)
+        self._call("lwp_load_weights", c_names, c_ptrs, shapes.ctypes.data, ndims.ctypes.data, n)
         self._left_params = {}                # every parameter has just been replaced
         self._scope_steps = self.stage_steps
 
     def weights_blob_bytes(self):
         n = C.c_size_t()
-        check(lib().lwp_weights_blob_bytes(self.h.ptr, C.byref(n)), self.h.ptr)
+        self._call("lwp_weights_blob_bytes", C.byref(n))
         return n.value
 
     def export_weights(self, device_tensor):
-        check(lib().lwp_weights_blob_export(self.h.ptr, device_tensor.data_ptr(), device_tensor.numel() * device_tensor.element_size()), self.h.ptr)
+        self._call("lwp_weights_blob_export", device_tensor.data_ptr(), device_tensor.numel() * device_tensor.element_size())
 
     def import_weights(self, device_tensor):
-        check(lib().lwp_weights_blob_import(self.h.ptr, device_tensor.data_ptr(), device_tensor.numel() * device_tensor.element_size()), self.h.ptr)
+        self._call("lwp_weights_blob_import", device_tensor.data_ptr(), device_tensor.numel() * device_tensor.element_size())
 
     # ------------------------------------------------------------------ skeleton (modules/keypoints.py:5-8, group_keypoints' options)
     def set_skeleton(self, limb_kpts, limb_pafs, num_kpt_types=None, pose_entry_size=None, min_paf_score=0.05):
@@ -81,7 +177,7 @@ class Engine(object):
         type pairs and their PAF channel pairs, in grouping order.  num_kpt_types defaults to num_heatmaps - 1,
         pose_entry_size to max(20, K + 2).  ``limb_kpts=None`` restores the COCO default.  Bad tables raise ValueError."""
         if limb_kpts is None:
-            check(lib().lwp_set_skeleton(self.h.ptr, 0, 0, None, None, 0, 0.0), self.h.ptr)
+            self._call("lwp_set_skeleton", 0, 0, None, None, 0, 0.0)
             self._skel = None
             return
         kp = np.ascontiguousarray(np.asarray(limb_kpts, dtype=np.int64).reshape(-1, 2), dtype=np.int32)
@@ -92,20 +188,18 @@ class Engine(object):
             raise ValueError("limb_kpts and limb_pafs must have the same number of limbs (%d != %d)" % (len(kp), len(pf)))
         K = int(self.NH - 1 if num_kpt_types is None else num_kpt_types)
         E = int(max(20, K + 2) if pose_entry_size is None else pose_entry_size)
-        check(lib().lwp_set_skeleton(self.h.ptr, K, len(kp), kp.ctypes.data_as(C.POINTER(C.c_int)), pf.ctypes.data_as(C.POINTER(C.c_int)),
-                                     E, float(min_paf_score)), self.h.ptr)
+        self._call("lwp_set_skeleton", K, len(kp), kp.ctypes.data, pf.ctypes.data, E, float(min_paf_score))
         self._skel = None
 
     @property
     def skeleton(self):
         """dict(num_kpt_types, limb_kpts (L,2), limb_pafs (L,2), pose_entry_size, min_paf_score) of the handle."""
-        if getattr(self, "_skel", None) is None:
+        if self._skel is None:
             K, L, E, mp = C.c_int(), C.c_int(), C.c_int(), C.c_double()
-            check(lib().lwp_get_skeleton(self.h.ptr, C.byref(K), C.byref(L), None, None, 0, C.byref(E), C.byref(mp)), self.h.ptr)
+            self._call("lwp_get_skeleton", C.byref(K), C.byref(L), None, None, 0, C.byref(E), C.byref(mp))
             kp = np.zeros((L.value, 2), np.int32)
             pf = np.zeros((L.value, 2), np.int32)
-            check(lib().lwp_get_skeleton(self.h.ptr, None, None, kp.ctypes.data_as(C.POINTER(C.c_int)), pf.ctypes.data_as(C.POINTER(C.c_int)),
-                                         L.value, None, None), self.h.ptr)
+            self._call("lwp_get_skeleton", None, None, kp.ctypes.data, pf.ctypes.data, L.value, None, None)
             self._skel = dict(num_kpt_types=K.value, limb_kpts=kp, limb_pafs=pf, pose_entry_size=E.value, min_paf_score=mp.value)
         return self._skel
 
@@ -118,56 +212,42 @@ class Engine(object):
         return rc == 1
 
     def set_capacity(self, max_peaks=2048, max_kpts=128, max_conn=4096, max_entries=256):
-        check(lib().lwp_set_capacity(self.h.ptr, max_peaks, max_kpts, max_conn, max_entries), self.h.ptr)
+        self._call("lwp_set_capacity", max_peaks, max_kpts, max_conn, max_entries)
         self._caps = (max_peaks, max_kpts, max_conn, max_entries)
 
     @property
     def caps(self):
-        return getattr(self, "_caps", (2048, 128, 4096, 256))
+        return self._caps
 
     # ------------------------------------------------------------------ network
     def forward(self, x):
         """x: (N,3,H,W) float32 torch tensor (cpu or cuda) or numpy array -> list of 2(1+nref) outputs of the
         same kind (NCHW), like PoseEstimationWithMobileNet.forward (with_mobilenet.py:114-123)."""
         torch = _torch()
-        is_np = isinstance(x, np.ndarray)
-        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if is_np else x
-        if t.dim() != 4 or t.shape[1] != 3:
-            raise ValueError("expected input of shape (N, 3, H, W), got %s" % (tuple(t.shape),))
-        t = t.detach().to(torch.float32).contiguous()
-        N, _, H, W = t.shape
-        on_dev = t.is_cuda
-        if on_dev and t.device.index != self.device_id:
-            raise ValueError("input is on cuda:%d but the engine lives on cuda:%d" % (t.device.index, self.device_id))
-        fh, fw = H, W
-        for _ in range(3):                       # three stride-2 stages: out = (in - 1) // 2 + 1
-            fh, fw = (fh - 1) // 2 + 1, (fw - 1) // 2 + 1
-        shapes = [(N, self.NP if i % 2 else self.NH, fh, fw) for i in range(2 * (1 + self.nref))]
-        outs = [torch.empty(s, dtype=torch.float32, device=t.device) for s in shapes]
+        if len(x.shape) != 4 or x.shape[1] != 3:
+            raise ValueError("expected input of shape (N, 3, H, W), got %s" % (tuple(x.shape),))
+        ptr, mem, a = self._ptr(x, np.float32)
+        N, _, H, W = a.shape
+        outs = [torch.empty(s, dtype=torch.float32, device=a.device if mem == MEM_DEVICE else "cpu") for s in self._stage_shapes(N, H, W)]
         ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-        if on_dev:
-            self._order(t.device)                 # events both ways: the outputs are valid for work queued on torch's current stream
+        if mem == MEM_DEVICE:
+            self._order(a.device)                 # events both ways: the outputs are valid for work queued on torch's current stream
             # (a frame from preprocess_u8(hand_over=False) is in order on the engine's stream; the outputs still need the hand-over)
-        mem = MEM_DEVICE if on_dev else MEM_HOST
-        check(lib().lwp_forward(self.h.ptr, t.data_ptr(), mem, N, H, W, ptrs, mem), self.h.ptr)
-        return [o.numpy() for o in outs] if is_np else outs
+        self._call("lwp_forward", ptr, mem, N, H, W, ptrs, mem)
+        return [o.numpy() for o in outs] if isinstance(x, np.ndarray) else outs
 
     def synchronize(self):
-        check(lib().lwp_synchronize(self.h.ptr), self.h.ptr)
+        self._call("lwp_synchronize")
 
     # ------------------------------------------------------------------ post-processing pieces
     def upsample(self, maps_nchw, ratio=4):
         """(N,C,h,w) float32 numpy -> (N, h*r, w*r, C) float32 numpy (cv2.resize INTER_CUBIC, demo.py:72,76)."""
-        if getattr(maps_nchw, "is_cuda", False):
-            a = maps_nchw.detach().contiguous()
+        ptr, mem, a = self._ptr(maps_nchw, np.float32, "maps", convert=False)
+        if mem == MEM_DEVICE:
             self._order(a.device)
-            ptr, mem = a.data_ptr(), MEM_DEVICE
-        else:
-            a = np.ascontiguousarray(maps_nchw.numpy() if hasattr(maps_nchw, "numpy") else maps_nchw, dtype=np.float32)
-            ptr, mem = a.ctypes.data, MEM_HOST
         N, Cc, h, w = a.shape
         out = np.empty((N, h * ratio, w * ratio, Cc), dtype=np.float32)
-        check(lib().lwp_upsample(self.h.ptr, ptr, mem, N, Cc, h, w, ratio, out.ctypes.data, MEM_HOST), self.h.ptr)
+        self._call("lwp_upsample", ptr, mem, N, Cc, h, w, ratio, out.ctypes.data, MEM_HOST)
         return out
 
     @staticmethod
@@ -184,56 +264,38 @@ class Engine(object):
         """uint8 HxWx3 frame (numpy or cuda tensor) -> (x: 1x3xH'xW' float32 cuda tensor, scale, pad): the cubic resize,
         normalize and pad_width of demo.py:55-64 in one kernel.  ``hand_over=False`` (infer_fast's internal use): x is only meant
         for this engine's next call — it stays on the engine's stream and that call skips the stream ordering (no events)."""
-        torch = _torch()
-        if getattr(img, "is_cuda", False):
-            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-                raise TypeError("frame must be HxWx3 uint8")
-            a = img.contiguous()
-            ptr, mem = a.data_ptr(), MEM_DEVICE
-        else:
-            a = np.ascontiguousarray(img)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise TypeError("frame must be HxWx3 uint8")
-            ptr, mem = a.ctypes.data, MEM_HOST
+        ptr, mem, a = self._ptr(img, what="frame")
+        if not _is_dtype(a, np.uint8) or len(a.shape) != 3 or a.shape[2] != 3:
+            raise TypeError("frame must be HxWx3 uint8")
         H, W = int(a.shape[0]), int(a.shape[1])
         _, _, oh, ow, pad, scale = self.preprocess_dims(H, W, net_input_height_size, stride)
-        x = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=torch.device("cuda", self.device_id))
-        pv = (C.c_double * 3)(*[float(v) for v in pad_value])
-        mv = (C.c_double * 3)(*[float(v) for v in img_mean])
+        x = self._empty((1, 3, oh, ow))
         self._order(hand_over=hand_over)          # x is handed to torch's current stream by event; a host frame may be reused on return
-        check(lib().lwp_preprocess_u8(self.h.ptr, ptr, mem, H, W, net_input_height_size, stride, pv, mv, float(img_scale), x.data_ptr()), self.h.ptr)
+        self._call("lwp_preprocess_u8", ptr, mem, H, W, net_input_height_size, stride, _triple(pad_value), _triple(img_mean),
+                   float(img_scale), x.data_ptr())
         if not hand_over:
             x._lwp_stream_owner = self            # produced on this engine's stream, not visible to torch's stream
         return x, scale, pad
 
-    def _u8_frames(self, frames):
+    def _u8_frames(self, frames, dtypes=(np.uint8,), kinds="uint8"):
         """(pointer, mem flag, N, H, W, the array kept alive) of a uint8 frame batch (N,H,W,3) or one frame (H,W,3), numpy or a
         cuda tensor on this engine's GPU."""
-        torch = _torch()
-        on_dev = getattr(frames, "is_cuda", False)
-        a = frames.contiguous() if on_dev else np.ascontiguousarray(frames)
-        if a.dtype != (torch.uint8 if on_dev else np.uint8) or len(a.shape) not in (3, 4) or a.shape[-1] != 3:
-            raise TypeError("frames must be (N,)HxWx3 uint8")
+        ptr, mem, a = self._ptr(frames, what="frames")
+        if not any(_is_dtype(a, t) for t in dtypes) or len(a.shape) not in (3, 4) or a.shape[-1] != 3:
+            raise TypeError("frames must be (N,)HxWx3 %s" % kinds)
         shp = tuple(a.shape) if len(a.shape) == 4 else (1,) + tuple(a.shape)
-        if on_dev:
-            if a.device.index != self.device_id:
-                raise ValueError("frames are on cuda:%d but the engine lives on cuda:%d" % (a.device.index, self.device_id))
-            return a.data_ptr(), MEM_DEVICE, int(shp[0]), int(shp[1]), int(shp[2]), a
-        return a.ctypes.data, MEM_HOST, int(shp[0]), int(shp[1]), int(shp[2]), a
+        return ptr, mem, int(shp[0]), int(shp[1]), int(shp[2]), a
 
     def preprocess_u8_batch(self, frames, net_input_height_size, stride, pad_value=(0, 0, 0), img_mean=(128, 128, 128), img_scale=1 / 256,
                             hand_over=True):
         """N same-sized uint8 frames (N,H,W,3) or one (H,W,3), numpy or cuda tensor -> (x: N x 3 x H' x W' float32 cuda tensor,
         scale, pad): ``preprocess_u8`` for a batch in ONE launch (demo.py:55-64 per frame, same bits)."""
-        torch = _torch()
         ptr, mem, N, H, W, a = self._u8_frames(frames)
         _, _, oh, ow, pad, scale = self.preprocess_dims(H, W, net_input_height_size, stride)
-        x = torch.empty((N, 3, oh, ow), dtype=torch.float32, device=torch.device("cuda", self.device_id))
-        pv = (C.c_double * 3)(*[float(v) for v in pad_value])
-        mv = (C.c_double * 3)(*[float(v) for v in img_mean])
+        x = self._empty((N, 3, oh, ow))
         self._order(hand_over=hand_over)
-        check(lib().lwp_preprocess_u8_batch(self.h.ptr, ptr, mem, N, H, W, net_input_height_size, stride, pv, mv, float(img_scale),
-                                            x.data_ptr()), self.h.ptr)
+        self._call("lwp_preprocess_u8_batch", ptr, mem, N, H, W, net_input_height_size, stride, _triple(pad_value), _triple(img_mean),
+                   float(img_scale), x.data_ptr())
         if not hand_over:
             x._lwp_stream_owner = self
         return x, scale, pad
@@ -249,42 +311,19 @@ class Engine(object):
     def preprocess_scaled_u8(self, imgs, ratio, base_height, stride, pad_value=(0, 0, 0), img_mean=(128, 128, 128), img_scale=1 / 256):
         """N same-sized frames (N,H,W,3) or one (H,W,3), numpy or cuda tensor, uint8 or float32 -> (x: N x 3 x H' x W' float32
         cuda tensor, pad): normalize + cubic resize by ``ratio`` + pad_width of val.py:84-93 in one kernel."""
-        torch = _torch()
-        on_dev = getattr(imgs, "is_cuda", False)
-        a = imgs.contiguous() if on_dev else np.ascontiguousarray(imgs)
-        is_u8 = a.dtype == (torch.uint8 if on_dev else np.uint8)
-        is_f32 = a.dtype == (torch.float32 if on_dev else np.float32)
-        if not (is_u8 or is_f32) or len(a.shape) not in (3, 4) or a.shape[-1] != 3:
-            raise TypeError("frames must be (N,)HxWx3 uint8 or float32")
-        shp = tuple(a.shape) if len(a.shape) == 4 else (1,) + tuple(a.shape)
-        N, H, W = int(shp[0]), int(shp[1]), int(shp[2])
+        ptr, mem, N, H, W, a = self._u8_frames(imgs, (np.uint8, np.float32), "uint8 or float32")
         _, _, oh, ow, pad = self.scale_dims(H, W, ratio, base_height, stride)
-        if on_dev:
-            if a.device.index != self.device_id:
-                raise ValueError("frames are on cuda:%d but the engine lives on cuda:%d" % (a.device.index, self.device_id))
-            ptr, mem = a.data_ptr(), MEM_DEVICE
-        else:
-            ptr, mem = a.ctypes.data, MEM_HOST
         self._order()
-        x = torch.empty((N, 3, oh, ow), dtype=torch.float32, device=torch.device("cuda", self.device_id))
-        pv = (C.c_double * 3)(*[float(v) for v in pad_value])
-        mv = (C.c_double * 3)(*[float(v) for v in img_mean])
-        fn = lib().lwp_preprocess_scaled_u8 if is_u8 else lib().lwp_preprocess_scaled_f32
-        check(fn(self.h.ptr, ptr, mem, N, H, W, float(ratio), base_height, stride, pv, mv, float(img_scale), x.data_ptr()), self.h.ptr)
+        x = self._empty((N, 3, oh, ow))
+        self._call("lwp_preprocess_scaled_u8" if _is_dtype(a, np.uint8) else "lwp_preprocess_scaled_f32", ptr, mem, N, H, W, float(ratio),
+                   base_height, stride, _triple(pad_value), _triple(img_mean), float(img_scale), x.data_ptr())
         return x, pad
 
     def multiscale_accumulate(self, accum, maps, up_ratio, pad, n_scales, init=False):
         """accum (H,W,C) or (N,H,W,C) float32 [numpy or cuda tensor, updated in place] += resize(crop(upsample(maps))) / n_scales
         (val.py:96-101).  maps: (C,h,w) or (N,C,h,w) float32 numpy / cuda tensor; the N frames share pad and size.
         init=True: accum is treated as zero (first scale), so it may be uninitialised memory."""
-        def ptr_mem(a):
-            if getattr(a, "is_cuda", False):
-                return a.data_ptr(), MEM_DEVICE
-            return a.ctypes.data, MEM_HOST
-        if getattr(maps, "is_cuda", False):
-            maps = maps.detach().contiguous()
-        else:
-            maps = np.ascontiguousarray(maps, dtype=np.float32)
+        mp, mm, maps = self._ptr(maps, np.float32, "maps", convert=False)
         shp = tuple(maps.shape)
         ashp = tuple(accum.shape)
         N = shp[0] if len(shp) == 4 else 1
@@ -298,12 +337,11 @@ class Engine(object):
                 raise TypeError("accum must be a contiguous float32 tensor")
         elif accum.dtype != np.float32 or not accum.flags.c_contiguous:
             raise TypeError("accum must be a C-contiguous float32 array")
-        mp, mm = ptr_mem(maps)
-        ap, am = ptr_mem(accum)
+        ap, am, _ = self._ptr(accum, what="accum")     # contiguous, so this is accum itself: updated in place
         if mm == MEM_DEVICE or am == MEM_DEVICE:
             self._order()
         padv = (C.c_int * 4)(*[int(v) for v in pad])
-        check(lib().lwp_multiscale_accumulate(self.h.ptr, mp, mm, N, shp[-3], shp[-2], shp[-1], up_ratio, padv, H, W, n_scales, ap, am, 1 if init else 0), self.h.ptr)
+        self._call("lwp_multiscale_accumulate", mp, mm, N, shp[-3], shp[-2], shp[-1], up_ratio, padv, H, W, n_scales, ap, am, 1 if init else 0)
         return accum
 
     def extract_keypoints(self, heatmap):
@@ -318,9 +356,8 @@ class Engine(object):
         cap = self.caps[1]
         xs = np.empty(cap, np.int64); ys = np.empty(cap, np.int64); sc = np.empty(cap, np.float32)
         n = C.c_int()
-        check(lib().lwp_extract_keypoints(self.h.ptr, heatmap.ctypes.data, H, W, heatmap.strides[0] // 4, heatmap.strides[1] // 4,
-                                          xs.ctypes.data_as(C.POINTER(C.c_int64)), ys.ctypes.data_as(C.POINTER(C.c_int64)),
-                                          sc.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(n)), self.h.ptr)
+        self._call("lwp_extract_keypoints", heatmap.ctypes.data, H, W, heatmap.strides[0] // 4, heatmap.strides[1] // 4,
+                   xs.ctypes.data, ys.ctypes.data, sc.ctypes.data, cap, C.byref(n))
         return xs[:n.value], ys[:n.value], sc[:n.value]
 
     def group_keypoints(self, kpts, type_counts, pafs, demo):
@@ -338,23 +375,34 @@ class Engine(object):
         cap = self.caps[3]
         ent = np.empty((cap, sk["pose_entry_size"]), np.float64)
         n = C.c_int()
-        check(lib().lwp_group_keypoints(self.h.ptr, kp.ctypes.data, tc.ctypes.data_as(C.POINTER(C.c_int)), pafs.ctypes.data,
-                                        MEM_HOST, H, W, 1 if demo else 0, ent.ctypes.data, cap, C.byref(n)), self.h.ptr)
+        self._call("lwp_group_keypoints", kp.ctypes.data, tc.ctypes.data, pafs.ctypes.data, MEM_HOST, H, W, 1 if demo else 0,
+                   ent.ctypes.data, cap, C.byref(n))
         return ent[:n.value].copy()
 
     # ------------------------------------------------------------------ fused pipeline
+    def _frames_of(self, slot=-1):
+        """Frames of the last serial pose-producing call (slot < 0) or of a submitted pipeline slot."""
+        if slot < 0:
+            if self._last_N is None:
+                raise RuntimeError("no poses yet: call infer_poses, infer_poses_async or poses_from_maps first")
+            return self._last_N
+        if slot not in self._keep_slot:
+            raise RuntimeError("slot %r holds nothing: call pipeline_submit or pipeline_submit_u8 for it first" % (slot,))
+        return self._keep_slot[slot][1]
+
     def _result_buffers(self, N):
+        """(the four host arrays a pose-producing call fills for N frames, the argument tail that hands them to the library)."""
         sk = self.skeleton
         K, E = sk["num_kpt_types"], sk["pose_entry_size"]
         kcap = K * self.caps[1]
         ecap = self.caps[3]
-        return (np.zeros((N, K), np.int32), np.zeros((N, kcap, 4), np.float64), np.zeros((N, ecap, E), np.float64),
-                np.zeros(N, np.int32), kcap, ecap)
+        counts, kpts, ent, ne = np.zeros((N, K), np.int32), np.zeros((N, kcap, 4), np.float64), np.zeros((N, ecap, E), np.float64), np.zeros(N, np.int32)
+        return (counts, kpts, ent, ne), (counts.ctypes.data, kpts.ctypes.data, kcap, ent.ctypes.data, ecap, ne.ctypes.data)
 
     @staticmethod
-    def _unpack(N, counts, kpts, ent, ne):
+    def _unpack(counts, kpts, ent, ne):
         out = []
-        for f in range(N):
+        for f in range(len(ne)):
             K = int(counts[f].sum())
             out.append((ent[f, :ne[f]].copy(), kpts[f, :K].copy(), counts[f].copy()))
         return out
@@ -363,41 +411,36 @@ class Engine(object):
         """x: (N,3,H,W) float32 (numpy / cpu tensor / cuda tensor), already normalised and padded.
         Returns per frame (pose_entries (P,E) f64, all_keypoints (n,4) f64, type_counts (K,)); K / E of the skeleton (18 / 20 by
         default)."""
-        torch = _torch()
-        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if isinstance(x, np.ndarray) else x
-        t = t.detach().to(torch.float32).contiguous()
+        ptr, mem, t = self._ptr(x, np.float32)
         N, _, H, W = t.shape
-        counts, kpts, ent, ne, kcap, ecap = self._result_buffers(N)
-        if t.is_cuda and getattr(x, "_lwp_stream_owner", None) is not self:
+        bufs, tail = self._result_buffers(N)
+        if mem == MEM_DEVICE and getattr(x, "_lwp_stream_owner", None) is not self:
             self._order(t.device)
-        check(lib().lwp_infer_poses(self.h.ptr, t.data_ptr(), MEM_DEVICE if t.is_cuda else MEM_HOST, N, H, W, upsample_ratio,
-                                    1 if demo else 0, counts.ctypes.data_as(C.POINTER(C.c_int)), kpts.ctypes.data, kcap,
-                                    ent.ctypes.data, ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        self._call("lwp_infer_poses", ptr, mem, N, H, W, upsample_ratio, 1 if demo else 0, *tail)
         self._last_N = N
-        return self._unpack(N, counts, kpts, ent, ne)
+        return self._unpack(*bufs)
+
+    def _maps(self, heat, paf, layout):
+        """(heat pointer, paf pointer, mem flag, layout code, N, h, w, the two arrays kept alive) of a pair of float32 maps, both
+        numpy or both cuda tensors; device maps are ordered behind torch's current stream."""
+        lay = {"NCHW": 0, "NHWC": 1}[layout]
+        hp, mem, heat = self._ptr(heat, np.float32, "heat", convert=False)
+        pp, pmem, paf = self._ptr(paf, np.float32, "paf", convert=False)
+        if pmem != mem:
+            raise TypeError("heat and paf must both be numpy arrays or both cuda tensors")
+        if mem == MEM_DEVICE:
+            self._order(heat.device)
+        N, hs, ws = (heat.shape[0], heat.shape[2], heat.shape[3]) if lay == 0 else heat.shape[:3]
+        return hp, pp, mem, lay, N, hs, ws, (heat, paf)
 
     def poses_from_maps(self, heat, paf, upsample_ratio=4, demo=True, layout="NCHW"):
         """Post-processing only.  layout "NCHW": the low-res stage outputs (N,19,h,w) / (N,38,h,w); layout "NHWC": full-res
         averaged maps (N,H,W,19) / (N,H,W,38) of the multi-scale path with upsample_ratio=1.  float32 numpy or cuda tensors."""
-        lay = {"NCHW": 0, "NHWC": 1}[layout]
-        if getattr(heat, "is_cuda", False):
-            heat, paf = heat.detach().contiguous(), paf.detach().contiguous()
-            self._order(heat.device)
-            hp, pp, mem = heat.data_ptr(), paf.data_ptr(), MEM_DEVICE
-        else:
-            heat = np.ascontiguousarray(heat, dtype=np.float32)
-            paf = np.ascontiguousarray(paf, dtype=np.float32)
-            hp, pp, mem = heat.ctypes.data, paf.ctypes.data, MEM_HOST
-        if lay == 0:
-            N, _, hs, ws = heat.shape
-        else:
-            N, hs, ws, _ = heat.shape
-        counts, kpts, ent, ne, kcap, ecap = self._result_buffers(N)
-        check(lib().lwp_poses_from_maps(self.h.ptr, hp, pp, mem, lay, N, hs, ws, upsample_ratio,
-                                        1 if demo else 0, counts.ctypes.data_as(C.POINTER(C.c_int)), kpts.ctypes.data, kcap,
-                                        ent.ctypes.data, ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        hp, pp, mem, lay, N, hs, ws, _ = self._maps(heat, paf, layout)
+        bufs, tail = self._result_buffers(N)
+        self._call("lwp_poses_from_maps", hp, pp, mem, lay, N, hs, ws, upsample_ratio, 1 if demo else 0, *tail)
         self._last_N = N
-        return self._unpack(N, counts, kpts, ent, ne)
+        return self._unpack(*bufs)
 
     def layers(self):
         out = []
@@ -405,7 +448,7 @@ class Engine(object):
         v = [C.c_int() for _ in range(6)]
         macs = C.c_int64()
         for i in range(lib().lwp_layer_count(self.h.ptr)):
-            check(lib().lwp_layer_info(self.h.ptr, i, name, 128, *[C.byref(x) for x in v], C.byref(macs)), self.h.ptr)
+            self._call("lwp_layer_info", i, name, 128, *[C.byref(x) for x in v], C.byref(macs))
             out.append(dict(index=i, name=name.value.decode(), kind=v[0].value, cin=v[1].value, cout=v[2].value,
                             ksize=v[3].value, stride=v[4].value, dilation=v[5].value, macs_per_pixel=macs.value))
         return out
@@ -417,7 +460,7 @@ class Engine(object):
         info = self.layers()[layer_index]
         buf = np.empty(N * info["cout"] * ((H + 1) // 2) * ((W + 1) // 2), np.float32)
         dims = (C.c_int * 4)()
-        check(lib().lwp_debug_layer_output(self.h.ptr, x.ctypes.data, N, H, W, layer_index, buf.ctypes.data, buf.size, dims), self.h.ptr)
+        self._call("lwp_debug_layer_output", x.ctypes.data, N, H, W, layer_index, buf.ctypes.data, buf.size, dims)
         n = dims[0] * dims[1] * dims[2] * dims[3]
         return buf[:n].reshape(dims[0], dims[1], dims[2], dims[3]).copy()
 
@@ -434,13 +477,13 @@ class Engine(object):
         sk = self.skeleton
         K, L = sk["num_kpt_types"], len(sk["limb_kpts"])
         arrs = [(C.c_int * n)() for n in (K, K, L, L)]
-        check(lib().lwp_debug_post_counts_ex(self.h.ptr, frame, *arrs, K, L), self.h.ptr)
+        self._call("lwp_debug_post_counts_ex", frame, *arrs, K, L)
         return tuple(np.array(list(a), dtype=np.int64) for a in arrs)
 
     def layer_variant(self, layer_index):
         """Kernel variant the last debug_layer_output / profile_launches pass picked for a layer ("" before any)."""
         name = C.create_string_buffer(96)
-        check(lib().lwp_debug_layer_variant(self.h.ptr, layer_index, name, 96), self.h.ptr)
+        self._call("lwp_debug_layer_variant", layer_index, name, 96)
         return name.value.decode()
 
     def _as_device_input(self, x):
@@ -464,23 +507,20 @@ class Engine(object):
         x_cuda = self._as_device_input(x_cuda)
         N, _, H, W = x_cuda.shape
         self._keep = x_cuda
-        check(lib().lwp_infer_poses_async(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0), self.h.ptr)
+        self._call("lwp_infer_poses_async", x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0)
         self._last_N = N
 
     def fetch_poses(self):
-        N = self._last_N
-        counts, kpts, ent, ne, kcap, ecap = self._result_buffers(N)
-        check(lib().lwp_fetch_poses(self.h.ptr, counts.ctypes.data_as(C.POINTER(C.c_int)), kpts.ctypes.data, kcap, ent.ctypes.data,
-                                    ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
-        return self._unpack(N, counts, kpts, ent, ne)
+        bufs, tail = self._result_buffers(self._frames_of())
+        self._call("lwp_fetch_poses", *tail)
+        return self._unpack(*bufs)
 
     # ------------------------------------------------------------------ pipelined streaming (two slots)
     def pipeline_submit(self, x_cuda, slot, upsample_ratio=4, demo=True):
         x_cuda = self._as_device_input(x_cuda)
         N, _, H, W = x_cuda.shape
-        self._keep_slot = getattr(self, "_keep_slot", {})
         self._keep_slot[slot] = (x_cuda, N)
-        check(lib().lwp_pipeline_submit(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, slot), self.h.ptr)
+        self._call("lwp_pipeline_submit", x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, slot)
 
     def pipeline_submit_u8(self, frames, slot, net_input_height_size, stride=8, pad_value=(0, 0, 0), img_mean=(128, 128, 128),
                            img_scale=1 / 256, upsample_ratio=4, demo=True):
@@ -490,23 +530,17 @@ class Engine(object):
         scale and pad (``preprocess_dims`` of the frame size): ``set_unmap`` is neither used nor changed.  A numpy frame buffer
         may be reused on return; a cuda tensor is kept alive until the slot is fetched."""
         ptr, mem, N, H, W, a = self._u8_frames(frames)
-        pv = (C.c_double * 3)(*[float(v) for v in pad_value])
-        mv = (C.c_double * 3)(*[float(v) for v in img_mean])
         if mem == MEM_DEVICE:
             self._order(a.device)
-        check(lib().lwp_pipeline_submit_u8(self.h.ptr, ptr, mem, N, H, W, net_input_height_size, stride, pv, mv, float(img_scale),
-                                           upsample_ratio, 1 if demo else 0, slot), self.h.ptr)
-        self._keep_slot = getattr(self, "_keep_slot", {})
+        self._call("lwp_pipeline_submit_u8", ptr, mem, N, H, W, net_input_height_size, stride, _triple(pad_value), _triple(img_mean),
+                   float(img_scale), upsample_ratio, 1 if demo else 0, slot)
         self._keep_slot[slot] = (a if mem == MEM_DEVICE else None, N)
-        self._overlay_shape = getattr(self, "_overlay_shape", {})
         self._overlay_shape[slot] = (N, H, W, 3)
 
     def pipeline_fetch(self, slot):
-        _, N = self._keep_slot[slot]
-        counts, kpts, ent, ne, kcap, ecap = self._result_buffers(N)
-        check(lib().lwp_pipeline_fetch(self.h.ptr, slot, counts.ctypes.data_as(C.POINTER(C.c_int)), kpts.ctypes.data, kcap,
-                                       ent.ctypes.data, ecap, ne.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
-        return self._unpack(N, counts, kpts, ent, ne)
+        bufs, tail = self._result_buffers(self._frames_of(slot))
+        self._call("lwp_pipeline_fetch", slot, *tail)
+        return self._unpack(*bufs)
 
     # ------------------------------------------------------------------ pose tail on the device (demo.py:101-118)
     TRACK_OFF, TRACK_ROWS, TRACK_LANES, TRACK_SEQUENCE = 0, 1, 2, 3
@@ -520,26 +554,25 @@ class Engine(object):
         if sigmas is not None:
             sg = np.ascontiguousarray(sigmas, dtype=np.float32)
             n = int(sg.size)
-        check(lib().lwp_set_tracking(self.h.ptr, int(mode), int(match_threshold), float(similarity_threshold), 1 if smooth else 0,
-                                     sg.ctypes.data_as(C.POINTER(C.c_float)) if sg is not None else None, n), self.h.ptr)
+        self._call("lwp_set_tracking", int(mode), int(match_threshold), float(similarity_threshold), 1 if smooth else 0,
+                   None if sg is None else sg.ctypes.data, n)
         self._tracking_mode = int(mode)
 
     def set_unmap(self, stride, scale, pad):
         """Geometry of the un-map (demo.py:101-103) for the following pose-producing calls; ``pad`` = [top, left, ...] as
         ``preprocess_dims`` / ``infer_fast`` return it."""
-        check(lib().lwp_set_unmap(self.h.ptr, int(stride), float(scale), int(pad[0]), int(pad[1])), self.h.ptr)
+        self._call("lwp_set_unmap", int(stride), float(scale), int(pad[0]), int(pad[1]))
 
     def reset_tracking(self, lane=-1, next_id=0):
         """Clears a lane (-1: all) and sets the first id it gives out."""
-        check(lib().lwp_reset_tracking(self.h.ptr, int(lane), int(next_id)), self.h.ptr)
+        self._call("lwp_reset_tracking", int(lane), int(next_id))
 
     def poses(self, slot=-1):
         """Pose rows of the last infer_poses / poses_from_maps / fetch_poses (slot -1) or of a fetched pipeline slot: per frame a
         dict of keypoints (P,K,2) int32, confidence (P,) f64, bbox (P,4) int32, ids (P,) int32 (-1 without tracking), last_id and
         near (similarity decisions the device could round differently from NumPy; 0 on every fixture)."""
-        N = self._last_N if slot < 0 else self._keep_slot[slot][1]
+        N = self._frames_of(slot)
         K, cap = self.skeleton["num_kpt_types"], self.caps[3]
-        ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint)
         n = np.zeros(N, np.int32)
         kp = np.zeros((N, cap, K, 2), np.int32)
         conf = np.zeros((N, cap), np.float64)
@@ -547,9 +580,9 @@ class Engine(object):
         ids = np.zeros((N, cap), np.int32)
         last = np.zeros(N, np.int32)
         near = np.zeros(N, np.uint32)
-        check(lib().lwp_get_poses(self.h.ptr, slot, n.ctypes.data_as(ip), kp.ctypes.data_as(ip), conf.ctypes.data_as(C.POINTER(C.c_double)),
-                                  bbox.ctypes.data_as(ip), ids.ctypes.data_as(ip), last.ctypes.data_as(ip), cap), self.h.ptr)
-        check(lib().lwp_debug_tracking_near(self.h.ptr, slot, near.ctypes.data_as(up), N), self.h.ptr)
+        self._call("lwp_get_poses", slot, n.ctypes.data, kp.ctypes.data, conf.ctypes.data, bbox.ctypes.data, ids.ctypes.data,
+                   last.ctypes.data, cap)
+        self._call("lwp_debug_tracking_near", slot, near.ctypes.data, N)
         return [dict(keypoints=kp[f, :n[f]].copy(), confidence=conf[f, :n[f]].copy(), bbox=bbox[f, :n[f]].copy(),
                      ids=ids[f, :n[f]].copy(), last_id=int(last[f]), near=int(near[f])) for f in range(N)]
 
@@ -562,12 +595,10 @@ class Engine(object):
         n = len(kp)
         if len(conf) != n:
             raise ValueError("%d poses but %d confidences" % (n, len(conf)))
-        ip = C.POINTER(C.c_int)
         okp, obb, oid = np.zeros((n, K, 2), np.int32), np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
         last, near = C.c_int(), C.c_uint()
-        check(lib().lwp_track_poses(self.h.ptr, int(lane), n, kp.ctypes.data_as(ip), conf.ctypes.data_as(C.POINTER(C.c_double)),
-                                    okp.ctypes.data_as(ip), obb.ctypes.data_as(ip), oid.ctypes.data_as(ip), C.byref(last),
-                                    C.byref(near)), self.h.ptr)
+        self._call("lwp_track_poses", int(lane), n, kp.ctypes.data, conf.ctypes.data, okp.ctypes.data, obb.ctypes.data, oid.ctypes.data,
+                   C.byref(last), C.byref(near))
         return dict(keypoints=okp, bbox=obb, ids=oid, last_id=last.value, near=near.value)
 
     # ------------------------------------------------------------------ pose overlay on the device (demo.py:119-124)
@@ -588,7 +619,7 @@ class Engine(object):
             if len(v) != 3 or min(v) < 0 or max(v) > 255:
                 raise ValueError("a colour is 3 values in 0..255, got %r" % (c,))
             return (C.c_ubyte * 3)(*v)
-        check(lib().lwp_set_overlay(self.h.ptr, int(mode), rgb(color), rgb(box_color), 1 if boxes else 0, int(n_draw_limbs)), self.h.ptr)
+        self._call("lwp_set_overlay", int(mode), rgb(color), rgb(box_color), 1 if boxes else 0, int(n_draw_limbs))
         self._overlay_mode = int(mode)
 
     def draw_poses(self, imgs, keypoints, bbox, n_poses=None, device_out=None):
@@ -597,7 +628,6 @@ class Engine(object):
         with ``n_poses`` (N,), or a list of N (P_f,K,2) arrays and a list of N (P_f,4) arrays.  Returns the annotated frames as a
         NEW array of the input's shape; ``imgs`` is not modified.  ``device_out``: None = the kind of ``imgs``, True = a cuda
         tensor, False = a numpy array."""
-        torch = _torch()
         ptr, mem, N, H, W, a = self._u8_frames(imgs)
         single = len(a.shape) == 3
         K = self.skeleton["num_kpt_types"]
@@ -625,33 +655,26 @@ class Engine(object):
             if kp.ndim != 4 or kp.shape[0] != N or kp.shape[2:] != (K, 2) or bb.shape != (N, kp.shape[1], 4) or n.shape != (N,):
                 raise ValueError("expected keypoints (N,cap,%d,2), bbox (N,cap,4) and n_poses (N,) for %d frames" % (K, N))
             cap = int(kp.shape[1])
-        on_dev = (mem == MEM_DEVICE) if device_out is None else bool(device_out)
-        if on_dev:
-            out = torch.empty(tuple(a.shape), dtype=torch.uint8, device=torch.device("cuda", self.device_id))
-            optr, omem = out.data_ptr(), MEM_DEVICE
-        else:
-            out = np.empty(tuple(a.shape), np.uint8)
-            optr, omem = out.ctypes.data, MEM_HOST
+        optr, omem, out = self._u8_out(tuple(a.shape), (mem == MEM_DEVICE) if device_out is None else bool(device_out))
         if mem == MEM_DEVICE or omem == MEM_DEVICE:
             self._order()
-        ip = C.POINTER(C.c_int)
-        check(lib().lwp_draw_poses(self.h.ptr, ptr, mem, N, H, W, n.ctypes.data_as(ip), kp.ctypes.data_as(ip), bb.ctypes.data_as(ip),
-                                   cap, optr, omem), self.h.ptr)
+        self._call("lwp_draw_poses", ptr, mem, N, H, W, n.ctypes.data, kp.ctypes.data, bb.ctypes.data, cap, optr, omem)
         return out
+
+    def _u8_out(self, shape, on_device):
+        """(pointer, mem flag, the array) of a new uint8 array of ``shape``: a cuda tensor or a numpy array."""
+        return self._ptr(self._empty(shape, _torch().uint8) if on_device else np.empty(shape, np.uint8))
 
     def pipeline_overlay(self, slot, device=False):
         """The annotated frames (N,H,W,3) uint8 of a fetched slot that was submitted with the overlay on: a numpy array (from the
         pinned copy in mode 2), or with ``device=True`` a cuda tensor.  A new array each time."""
-        torch = _torch()
+        if slot not in self._overlay_shape:
+            raise RuntimeError("slot %r holds no frames: call pipeline_submit_u8 for it first" % (slot,))
         shape = self._overlay_shape[slot]
+        ptr, mem, out = self._u8_out(shape, device)
         if device:
-            out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device_id))
             self._order()
-            ptr, mem = out.data_ptr(), MEM_DEVICE
-        else:
-            out = np.empty(shape, np.uint8)
-            ptr, mem = out.ctypes.data, MEM_HOST
-        check(lib().lwp_get_overlay(self.h.ptr, slot, ptr, mem, shape[0], shape[1], shape[2]), self.h.ptr)
+        self._call("lwp_get_overlay", slot, ptr, mem, shape[0], shape[1], shape[2])
         return out
 
     # ------------------------------------------------------------------ training targets and loss (coco.py:48-61,71-159; loss.py)
@@ -661,60 +684,39 @@ class Engine(object):
         Returns float32 cuda tensors ``keypoint_maps`` (N, K + 1, H // stride, W // stride) and ``paf_maps`` (N, 2L, ...) for
         the engine's skeleton (``set_skeleton``; the default gives coco.py's channel layout).  With ``time_iters`` > 0 the
         kernel is launched that many times back to back and the call returns the milliseconds of all of them (HIP events)."""
-        torch = _torch()
         H, W = int(image_hw[0]), int(image_hw[1])
         sk = self.skeleton
         K, L = sk["num_kpt_types"], len(sk["limb_kpts"])
-        if getattr(kpts, "is_cuda", False):
-            a = kpts.detach().to(torch.float64).contiguous()
-            ptr, mem = a.data_ptr(), MEM_DEVICE
-        else:
-            a = np.ascontiguousarray(kpts, dtype=np.float64)
-            ptr, mem = a.ctypes.data, MEM_HOST
+        ptr, mem, a = self._ptr(kpts, np.float64, "kpts")
         if len(a.shape) != 4 or tuple(a.shape[2:]) != (K, 3):
             raise ValueError("expected key-points of shape (N, Pmax, %d, 3), got %s" % (K, tuple(a.shape)))
         N, Pmax = int(a.shape[0]), int(a.shape[1])
         n = np.ascontiguousarray(n_persons, dtype=np.int32).reshape(-1)
         if n.shape != (N,):
             raise ValueError("expected %d person counts, got %s" % (N, n.shape))
-        stride = int(stride)
-        if stride < 1:
-            raise ValueError("stride must be at least 1")
-        dev = torch.device("cuda", self.device_id)
-        kmaps = torch.empty((N, K + 1, H // stride, W // stride), dtype=torch.float32, device=dev)
-        pmaps = torch.empty((N, 2 * L, H // stride, W // stride), dtype=torch.float32, device=dev)
+        stride = _stride(stride)
+        kmaps = self._empty((N, K + 1, H // stride, W // stride))
+        pmaps = self._empty((N, 2 * L, H // stride, W // stride))
         self._order()
-        args = (self.h.ptr, ptr if Pmax else None, mem, n.ctypes.data_as(C.POINTER(C.c_int)), N, Pmax, H, W, stride, float(sigma),
-                float(paf_thickness), kmaps.data_ptr(), pmaps.data_ptr())
-        if time_iters:
-            ms = C.c_float()
-            check(lib().lwp_time_train_targets(*args, int(time_iters), C.byref(ms)), self.h.ptr)
-            return ms.value
-        check(lib().lwp_train_targets(*args), self.h.ptr)
-        return kmaps, pmaps
+        args = (ptr if Pmax else None, mem, n.ctypes.data, N, Pmax, H, W, stride, float(sigma), float(paf_thickness),
+                kmaps.data_ptr(), pmaps.data_ptr())
+        ms = self._timed("lwp_train_targets", "lwp_time_train_targets", args, time_iters)
+        return (kmaps, pmaps) if ms is None else ms
 
     def mask_downsample(self, mask, stride=8):
         """(N, H, W) or (H, W) float32 mask (numpy or cuda tensor) -> the mean of each stride x stride block as a float32 cuda
         tensor (N, H // stride, W // stride): cv2.resize(mask, fx=fy=1/stride, INTER_AREA) of coco.py:48 where H and W are
         multiples of the stride (ValueError otherwise)."""
-        torch = _torch()
-        if getattr(mask, "is_cuda", False):
-            a = mask.detach().to(torch.float32).contiguous()
-            ptr, mem = a.data_ptr(), MEM_DEVICE
-        else:
-            a = np.ascontiguousarray(mask, dtype=np.float32)
-            ptr, mem = a.ctypes.data, MEM_HOST
+        ptr, mem, a = self._ptr(mask, np.float32, "mask")
         single = len(a.shape) == 2
         if len(a.shape) not in (2, 3):
             raise ValueError("expected a mask of shape (N, H, W) or (H, W), got %s" % (tuple(a.shape),))
         N = 1 if single else int(a.shape[0])
         H, W = int(a.shape[-2]), int(a.shape[-1])
-        stride = int(stride)
-        if stride < 1:
-            raise ValueError("stride must be at least 1")
-        out = torch.empty((N, H // stride, W // stride), dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        stride = _stride(stride)
+        out = self._empty((N, H // stride, W // stride))
         self._order()
-        check(lib().lwp_mask_downsample(self.h.ptr, ptr, mem, N, H, W, stride, out.data_ptr()), self.h.ptr)
+        self._call("lwp_mask_downsample", ptr, mem, N, H, W, stride, out.data_ptr())
         return out[0] if single else out
 
     # ------------------------------------------------------------------ training augmentation (datasets/transformations.py)
@@ -736,10 +738,7 @@ class Engine(object):
         plan = samples_or_plan if isinstance(samples_or_plan, BatchPlan) else plan_batch(samples_or_plan, transforms, rng)
         N = len(plan)
         cy, cx = plan.crop_hw
-        stride = int(stride)
-        if stride < 1:
-            raise ValueError("stride must be at least 1")
-        dev = torch.device("cuda", self.device_id)
+        stride = _stride(stride)
         recs = (AugmentPlan * N)()
         keep = []                                      # the arrays the records point into, alive until the call returns
         for n, g in enumerate(plan.records):
@@ -750,18 +749,12 @@ class Engine(object):
             if on_device:
                 if img.dtype != torch.uint8 or (msk is not None and msk.dtype != torch.float32):
                     raise TypeError("sample %d: cuda sources must be a uint8 image and a float32 mask" % n)
-                img = img.detach().contiguous()
-                msk = None if msk is None else msk.detach().contiguous()
-                ip, mp = img.data_ptr(), (None if msk is None else msk.data_ptr())
-            else:
-                if np.asarray(img).dtype != np.uint8:
-                    raise TypeError("sample %d: the image must be uint8, got %s" % (n, np.asarray(img).dtype))
-                img = np.ascontiguousarray(img, dtype=np.uint8)
-                msk = None if msk is None else np.ascontiguousarray(msk, dtype=np.float32)
-                ip, mp = img.ctypes.data, (None if msk is None else msk.ctypes.data)
-            keep.append((img, msk))
+            elif np.asarray(img).dtype != np.uint8:
+                raise TypeError("sample %d: the image must be uint8, got %s" % (n, np.asarray(img).dtype))
             r = recs[n]
-            r.image, r.mask, r.mem = ip, mp, (MEM_DEVICE if on_device else MEM_HOST)
+            r.image, r.mem, img = self._ptr(img, np.uint8, "sample %d: the image" % n)
+            r.mask, _, msk = (None, None, None) if msk is None else self._ptr(msk, np.float32, "sample %d: the mask" % n)
+            keep.append((img, msk))
             r.rs_scale = float(g["rs_scale"])
             for i in range(6):
                 r.m[i] = float(g["minv"][i])
@@ -772,25 +765,19 @@ class Engine(object):
             r.flip = int(g["flip"])
             for c in range(3):
                 r.warp_pad[c], r.crop_pad[c] = int(g["warp_pad"][c]), int(g["crop_pad"][c])
-        image = torch.empty((N, 3, cy, cx), dtype=torch.float32, device=dev)
-        mask = torch.empty((N, cy, cx), dtype=torch.uint8, device=dev)
-        small = torch.empty((N, cy // stride, cx // stride), dtype=torch.float32, device=dev)
+        image = self._empty((N, 3, cy, cx))
+        mask = self._empty((N, cy, cx), torch.uint8)
+        small = self._empty((N, cy // stride, cx // stride))
         self._order()
-        args = (self.h.ptr, recs, N, cy, cx, stride, image.data_ptr(), mask.data_ptr(), small.data_ptr())
+        args = (recs, N, cy, cx, stride, image.data_ptr(), mask.data_ptr(), small.data_ptr())
+        ms = None
         if getattr(plan, "crowd_runs", None) is not None:
             if time_iters:
                 raise ValueError("a batch with segmentations has no timing twin: time crowd_masks, and augment_batch without them")
-            counts, seg_off, image_seg_off = plan.crowd_runs
-            i64p = C.POINTER(C.c_int64)
-            check(lib().lwp_augment_batch_crowd(*args[:6], counts.ctypes.data_as(i64p), seg_off.ctypes.data_as(i64p),
-                                                image_seg_off.ctypes.data_as(i64p), *args[6:]), self.h.ptr)
-            return image, mask, small, torch.from_numpy(plan.kpts).to(dev)
-        if time_iters:
-            ms = C.c_float()
-            check(lib().lwp_time_augment_batch(*args, int(time_iters), C.byref(ms)), self.h.ptr)
-            return ms.value
-        check(lib().lwp_augment_batch(*args), self.h.ptr)
-        return image, mask, small, torch.from_numpy(plan.kpts).to(dev)
+            self._call("lwp_augment_batch_crowd", *args[:5], *[a.ctypes.data for a in plan.crowd_runs], *args[5:])
+        else:
+            ms = self._timed("lwp_augment_batch", "lwp_time_augment_batch", args, time_iters)
+        return (image, mask, small, torch.from_numpy(plan.kpts).to(self._gpu)) if ms is None else ms
 
     def crowd_masks(self, segmentations_per_image, sizes, time_iters=0):
         """``get_mask`` (coco.py:17-21) of all-ones masks for a batch, in one kernel launch.  ``segmentations_per_image``: per
@@ -798,7 +785,6 @@ class Engine(object):
         (H, W) float32 cuda tensors, views of ONE buffer: 1 where no segmentation covers the pixel, 0 where any does.  With
         ``time_iters`` > 0 the kernel is launched that many times back to back and the call returns the milliseconds of all of
         them (HIP events)."""
-        torch = _torch()
         from .datasets.coco import pack_crowd_runs
         sizes = [(int(h), int(w)) for h, w in sizes]
         counts, seg_off, image_seg_off = pack_crowd_runs(segmentations_per_image, sizes)
@@ -807,16 +793,13 @@ class Engine(object):
         widths = np.array([w for _, w in sizes], dtype=np.int32)
         out_off = np.zeros(N + 1, dtype=np.int64)
         np.cumsum(heights.astype(np.int64) * widths, out=out_off[1:])
-        buf = torch.empty((max(int(out_off[-1]), 1),), dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        buf = self._empty((max(int(out_off[-1]), 1),))
         self._order()
-        i64p, ip = C.POINTER(C.c_int64), C.POINTER(C.c_int)
-        args = (self.h.ptr, counts.ctypes.data_as(i64p), seg_off.ctypes.data_as(i64p), image_seg_off.ctypes.data_as(i64p),
-                heights.ctypes.data_as(ip), widths.ctypes.data_as(ip), N, out_off.ctypes.data_as(i64p), buf.data_ptr())
-        if time_iters:
-            ms = C.c_float()
-            check(lib().lwp_time_crowd_masks(*args, int(time_iters), C.byref(ms)), self.h.ptr)
-            return ms.value
-        check(lib().lwp_crowd_masks(*args), self.h.ptr)
+        args = (counts.ctypes.data, seg_off.ctypes.data, image_seg_off.ctypes.data, heights.ctypes.data, widths.ctypes.data, N,
+                out_off.ctypes.data, buf.data_ptr())
+        ms = self._timed("lwp_crowd_masks", "lwp_time_crowd_masks", args, time_iters)
+        if ms is not None:
+            return ms
         return [buf[int(out_off[n]):int(out_off[n + 1])].view(h, w) for n, (h, w) in enumerate(sizes)]
 
     # ------------------------------------------------------------------ JPEG files (cv2.imread's place)
@@ -851,7 +834,7 @@ class Engine(object):
         from 4 to 1024.  ValueError for anything else."""
         if mode not in _lib.JPEG_ENTROPY_MODES:
             raise ValueError("entropy mode must be 'host' or 'device', not %r" % (mode,))
-        check(lib().lwp_set_jpeg_entropy(self.h.ptr, _lib.JPEG_ENTROPY_MODES[mode], int(subseq_bytes)), self.h.ptr)
+        self._call("lwp_set_jpeg_entropy", _lib.JPEG_ENTROPY_MODES[mode], int(subseq_bytes))
         self._jpeg_entropy, self._jpeg_subseq = mode, int(subseq_bytes)
 
     @staticmethod
@@ -874,7 +857,7 @@ class Engine(object):
         self._order()
         if time_iters:
             ms, rounds = C.c_float(), (C.c_int * 2)()
-            check(lib().lwp_time_jpeg_entropy_batch(self.h.ptr, N, data, lens, int(subseq_bytes), int(time_iters), C.byref(ms), rounds), self.h.ptr)
+            self._call("lwp_time_jpeg_entropy_batch", N, data, lens, int(subseq_bytes), int(time_iters), C.byref(ms), rounds)
             return ms.value, rounds[0], rounds[1]
         coefs, qts = [], []
         for f in files:
@@ -885,7 +868,7 @@ class Engine(object):
         cp = (C.c_void_p * N)(*[c.ctypes.data for c in coefs])
         qp = (C.c_void_p * N)(*[q.ctypes.data for q in qts])
         status = (C.c_int * N)()
-        check(lib().lwp_debug_jpeg_entropy_batch(self.h.ptr, N, data, lens, int(subseq_bytes), cp, qp, status), self.h.ptr)
+        self._call("lwp_debug_jpeg_entropy_batch", N, data, lens, int(subseq_bytes), cp, qp, status)
         return [(int(status[i]), None, None) if status[i] else (0, coefs[i], qts[i]) for i in range(N)]
 
     @staticmethod
@@ -915,16 +898,14 @@ class Engine(object):
         ``time_iters`` > 0 each of the two kernels is launched that many times back to back and the call returns their
         milliseconds (stage A, stage B).  ``entropy``: ``"host"`` or ``"device"`` for this call, None for the engine's setting
         (``set_jpeg_entropy``; the host unless set)."""
-        torch = _torch()
-        if entropy is not None and entropy != getattr(self, "_jpeg_entropy", "host"):
+        if entropy is not None and entropy != self._jpeg_entropy:
             if entropy not in _lib.JPEG_ENTROPY_MODES:
                 raise ValueError("entropy mode must be 'host' or 'device', not %r" % (entropy,))
-            before = getattr(self, "_jpeg_entropy", "host")
-            check(lib().lwp_set_jpeg_entropy(self.h.ptr, _lib.JPEG_ENTROPY_MODES[entropy], getattr(self, "_jpeg_subseq", 0)), self.h.ptr)
+            self._call("lwp_set_jpeg_entropy", _lib.JPEG_ENTROPY_MODES[entropy], self._jpeg_subseq)
             try:
                 return self.decode_jpeg_batch(files, time_iters)
             finally:
-                check(lib().lwp_set_jpeg_entropy(self.h.ptr, _lib.JPEG_ENTROPY_MODES[before], getattr(self, "_jpeg_subseq", 0)), self.h.ptr)
+                self._call("lwp_set_jpeg_entropy", _lib.JPEG_ENTROPY_MODES[self._jpeg_entropy], self._jpeg_subseq)
         files = [bytes(f) for f in files]
         N = len(files)
         if N == 0:
@@ -939,16 +920,13 @@ class Engine(object):
         off = np.zeros(N + 1, dtype=np.int64)           # every image starts on a 16-byte boundary of the allocation
         for i, (h, w) in enumerate(sizes):
             off[i + 1] = (off[i] + h * w * 3 + 15) // 16 * 16
-        buf = torch.empty((int(off[-1]),), dtype=torch.uint8, device=torch.device("cuda", self.device_id))
-        data = (C.c_void_p * N)(*[C.cast(C.c_char_p(f), C.c_void_p) for f in files])
-        lens = (C.c_size_t * N)(*[len(f) for f in files])
+        buf = self._empty((int(off[-1]),), _torch().uint8)
+        data, lens = self._jpeg_args(files)
         outs = (C.c_void_p * N)(*[buf.data_ptr() + int(off[i]) for i in range(N)])
         self._order()
-        if time_iters:
-            ms = (C.c_float * 2)()
-            check(lib().lwp_time_jpeg_decode_batch(self.h.ptr, N, data, lens, outs, int(time_iters), ms), self.h.ptr)
-            return ms[0], ms[1]
-        check(lib().lwp_jpeg_decode_batch(self.h.ptr, N, data, lens, outs), self.h.ptr)
+        ms = self._timed("lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch", (N, data, lens, outs), time_iters, n_ms=2)
+        if ms is not None:
+            return ms
         return [buf[int(off[i]):int(off[i]) + h * w * 3].view(h, w, 3) for i, (h, w) in enumerate(sizes)]
 
     def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
@@ -959,41 +937,27 @@ class Engine(object):
         copied first (``Engine.forward`` returns contiguous tensors, which are read in place).  With ``time_iters`` > 0 the
         kernels are launched that many times back to back and the call returns the milliseconds of all of them (HIP events)."""
         args, n = self._loss_args(outs, keypoint_maps, paf_maps, mask, batch_size)
-        if time_iters:
-            ms = C.c_float()
-            check(lib().lwp_time_stage_losses(*args, int(time_iters), C.byref(ms)), self.h.ptr)
-            return ms.value
         losses = (C.c_double * max(n, 1))()
-        check(lib().lwp_stage_losses(*args, losses), self.h.ptr)
-        return [float(losses[i]) for i in range(n)]
+        ms = self._timed("lwp_stage_losses", "lwp_time_stage_losses", args, time_iters, tail=(losses,))
+        return [float(losses[i]) for i in range(n)] if ms is None else ms
 
     def _loss_args(self, outs, keypoint_maps, paf_maps, mask, batch_size):
         """The leading arguments of lwp_stage_losses / lwp_stage_losses_log and the number of stage tensors; the contiguous
         tensors behind the pointers are kept on the engine until the next loss call."""
-        torch = _torch()
-
-        def dev32(t, what, shape):
-            if t is None:
-                return None
-            if not getattr(t, "is_cuda", False):
-                raise TypeError("%s must be a cuda tensor" % what)
-            if tuple(t.shape) != shape:
-                raise ValueError("%s has shape %s, expected %s" % (what, tuple(t.shape), shape))
-            return t.detach().to(torch.float32).contiguous()
         ref = next((o for o in outs if o is not None), None)
         if ref is None:
             raise ValueError("no stage tensor given")
         N, _, hs, ws = (int(v) for v in ref.shape)
-        keep = [dev32(o, "outs[%d]" % i, (N, self.NP if i % 2 else self.NH, hs, ws)) for i, o in enumerate(outs)]
-        km = dev32(keypoint_maps, "keypoint_maps", (N, self.NH, hs, ws))
-        pm = dev32(paf_maps, "paf_maps", (N, self.NP, hs, ws))
-        m = dev32(mask, "mask", (N, hs, ws))
+        keep = [self._dev32(o, "outs[%d]" % i, (N, self.NP if i % 2 else self.NH, hs, ws), True) for i, o in enumerate(outs)]
+        km = self._dev32(keypoint_maps, "keypoint_maps", (N, self.NH, hs, ws), True)
+        pm = self._dev32(paf_maps, "paf_maps", (N, self.NP, hs, ws), True)
+        m = self._dev32(mask, "mask", (N, hs, ws), True)
         if m is None:
             raise ValueError("mask is None")
         ptrs = (C.c_void_p * max(len(keep), 1))(*[None if o is None else o.data_ptr() for o in keep])
         self._loss_keep = (keep, km, pm, m, ptrs)
         self._order()
-        return (self.h.ptr, ptrs, len(keep), None if km is None else km.data_ptr(), None if pm is None else pm.data_ptr(), m.data_ptr(),
+        return (ptrs, len(keep), None if km is None else km.data_ptr(), None if pm is None else pm.data_ptr(), m.data_ptr(),
                 N, hs, ws, int(N if batch_size is None else batch_size)), len(keep)
 
     def log_stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, divisor=1.0):
@@ -1001,30 +965,26 @@ class Engine(object):
         in float64 (train.py:96-97's total_losses with divisor = batches_per_iter).  Returns None and does not wait for the
         GPU; ``read_loss_log`` fetches the running sums.  ``divisor`` must be finite and > 0 (ValueError)."""
         args, _ = self._loss_args(outs, keypoint_maps, paf_maps, mask, batch_size)
-        check(lib().lwp_stage_losses_log(*args, float(divisor)), self.h.ptr)
+        self._call("lwp_stage_losses_log", *args, float(divisor))
 
     def read_loss_log(self, reset=True):
         """(the 2 * (nref + 1) running sums of ``log_stage_losses`` as Python floats, the number of adds since the last reset).
         Waits for the engine's stream: the one wait of a logged training loop.  ``reset`` zeroes both behind the read."""
         S = 2 * (self.nref + 1)
         sums, adds = (C.c_double * S)(), C.c_int64()
-        check(lib().lwp_loss_log_read(self.h.ptr, sums, C.byref(adds), 1 if reset else 0), self.h.ptr)
+        self._call("lwp_loss_log_read", sums, C.byref(adds), 1 if reset else 0)
         return [float(sums[i]) for i in range(S)], int(adds.value)
 
     # ------------------------------------------------------------------ stage backward (train.py:99-103, fp32 engines)
     def train_forward(self, x):
         """``forward`` for a float32 cuda tensor (N, 3, H, W) that also keeps what ``stage_backward`` needs: every stage
         layer's output from cpm.conv on (from the cpm's input on in train scope "cpm", from model.0 on in scope "all").  Returns the same list of stage outputs, bit for bit."""
-        torch = _torch()
         x = self._as_device_input(x)
         N, _, H, W = (int(v) for v in x.shape)
-        fh, fw = H, W
-        for _ in range(3):
-            fh, fw = (fh - 1) // 2 + 1, (fw - 1) // 2 + 1
-        outs = [torch.empty((N, self.NP if i % 2 else self.NH, fh, fw), dtype=torch.float32, device=x.device) for i in range(2 * (1 + self.nref))]
+        outs = [self._empty(s) for s in self._stage_shapes(N, H, W)]
         ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
         self._order(x.device)
-        check(lib().lwp_train_forward(self.h.ptr, x.data_ptr(), N, H, W, ptrs), self.h.ptr)
+        self._call("lwp_train_forward", x.data_ptr(), N, H, W, ptrs)
         return outs
 
     def set_backward_precision(self, precision="fp32", grad_scale=1.0):
@@ -1034,13 +994,13 @@ class Engine(object):
         else, the engine included, stays fp32; the setting may change between any two calls.  ValueError for anything else."""
         if precision not in _lib.BACKWARD_PRECISIONS:
             raise ValueError("backward precision must be 'fp32', 'bf16' or 'fp16', not %r" % (precision,))
-        check(lib().lwp_set_backward_precision(self.h.ptr, _lib.BACKWARD_PRECISIONS[precision], float(grad_scale)), self.h.ptr)
+        self._call("lwp_set_backward_precision", _lib.BACKWARD_PRECISIONS[precision], float(grad_scale))
 
     @property
     def backward_precision(self):
         """(name, grad_scale) as the handle holds them."""
         dt, sc = C.c_int(), C.c_double()
-        check(lib().lwp_get_backward_precision(self.h.ptr, C.byref(dt), C.byref(sc)), self.h.ptr)
+        self._call("lwp_get_backward_precision", C.byref(dt), C.byref(sc))
         return [k for k, v in _lib.BACKWARD_PRECISIONS.items() if v == dt.value][0], sc.value
 
     def set_train_scope(self, scope):
@@ -1052,10 +1012,10 @@ class Engine(object):
         Parameters the old scope has trained and the new one does not cover stay readable through ``trained_params``."""
         name = _lib.train_scope_name(scope)
         if name == self.train_scope:
-            check(lib().lwp_set_train_scope(self.h.ptr, _lib.train_scope(name)), self.h.ptr)
+            self._call("lwp_set_train_scope", _lib.train_scope(name))
             return
         old = self.stage_params() if self.stage_steps != self._scope_steps else {}
-        check(lib().lwp_set_train_scope(self.h.ptr, _lib.train_scope(name)), self.h.ptr)
+        self._call("lwp_set_train_scope", _lib.train_scope(name))
         self.train_scope = name
         self._gspec = None
         self._scope_steps = self.stage_steps
@@ -1066,7 +1026,7 @@ class Engine(object):
 
     def grad_spec(self):
         """([(state-dict key, shape, float offset)], total floats) of the flat gradient array, in the engine's train scope."""
-        if getattr(self, "_gspec", None) is None:
+        if self._gspec is None:
             self._gspec = _lib.train_grad_spec(self.train_scope, self.nref, self.C, self.NH, self.NP)
         return self._gspec
 
@@ -1075,23 +1035,15 @@ class Engine(object):
         return dict((k, flat[off:off + int(np.prod(shape))].view(shape)) for k, shape, off in self.grad_spec()[0])
 
     def _backward_args(self, keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, want_features):
-        torch = _torch()
         if not getattr(mask, "is_cuda", False) or mask.dim() != 3:
             raise ValueError("mask must be an (N, h, w) cuda tensor")
         N, hs, ws = (int(v) for v in mask.shape)
-
-        def dev32(t, what, shape):
-            if not getattr(t, "is_cuda", False):
-                raise TypeError("%s must be a cuda tensor" % what)
-            if tuple(t.shape) != shape:
-                raise ValueError("%s has shape %s, expected %s" % (what, tuple(t.shape), shape))
-            return t.detach().to(torch.float32).contiguous()
-        km = dev32(keypoint_maps, "keypoint_maps", (N, self.NH, hs, ws))
-        pm = dev32(paf_maps, "paf_maps", (N, self.NP, hs, ws))
-        m = dev32(mask, "mask", (N, hs, ws))
-        dfeat = torch.empty((N, self.C, hs, ws), dtype=torch.float32, device=m.device) if want_features else None
+        km = self._dev32(keypoint_maps, "keypoint_maps", (N, self.NH, hs, ws))
+        pm = self._dev32(paf_maps, "paf_maps", (N, self.NP, hs, ws))
+        m = self._dev32(mask, "mask", (N, hs, ws))
+        dfeat = self._empty((N, self.C, hs, ws)) if want_features else None
         self._keep = (km, pm, m)
-        return (self.h.ptr, km.data_ptr(), pm.data_ptr(), m.data_ptr(), N, hs, ws, int(N if batch_size is None else batch_size),
+        return (km.data_ptr(), pm.data_ptr(), m.data_ptr(), N, hs, ws, int(N if batch_size is None else batch_size),
                 float(loss_scale)), flat, dfeat
 
     def stage_backward(self, keypoint_maps, paf_maps, mask, batch_size=None, loss_scale=1.0, into=None, want_features=True, want_backbone=False):
@@ -1104,19 +1056,17 @@ class Engine(object):
         at the cpm's input (N, 512, h, w).  Train scope "all" adds the model.* keys; there is no gradient at the image."""
         torch = _torch()
         total = self.grad_spec()[1]
-        dev = torch.device("cuda", self.device_id)
         if into is not None and (not into.is_cuda or into.dtype != torch.float32 or into.numel() != total or not into.is_contiguous()):
             raise ValueError("into must be the contiguous float32 cuda array of %d gradients an earlier call returned" % total)
-        flat = into if into is not None else torch.empty(total, dtype=torch.float32, device=dev)
+        flat = into if into is not None else self._empty(total)
         args, flat, dfeat = self._backward_args(keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, want_features)
+        args += (1 if into is not None else 0, flat.data_ptr(), None if dfeat is None else dfeat.data_ptr())
         self._order()
         if want_backbone:
-            dback = torch.empty((dfeat.shape[0] if dfeat is not None else int(mask.shape[0]), 512) + tuple(int(v) for v in mask.shape[1:]),
-                                dtype=torch.float32, device=dev)
-            check(lib().lwp_train_backward(*args, 1 if into is not None else 0, flat.data_ptr(), None if dfeat is None else dfeat.data_ptr(),
-                                           dback.data_ptr()), self.h.ptr)
+            dback = self._empty((int(mask.shape[0]), 512) + tuple(int(v) for v in mask.shape[1:]))
+            self._call("lwp_train_backward", *args, dback.data_ptr())
             return self.grad_views(flat), dfeat, dback
-        check(lib().lwp_stage_backward(*args, 1 if into is not None else 0, flat.data_ptr(), None if dfeat is None else dfeat.data_ptr()), self.h.ptr)
+        self._call("lwp_stage_backward", *args)
         return self.grad_views(flat), dfeat
 
     def flat_of(self, grads):
@@ -1128,12 +1078,10 @@ class Engine(object):
 
     def profile_stage_backward(self, keypoint_maps, paf_maps, mask, batch_size=None, loss_scale=1.0, reps=3):
         """Device milliseconds and launch counts of one backward by kernel class (HIP events around every launch)."""
-        torch = _torch()
-        flat = torch.empty(self.grad_spec()[1], dtype=torch.float32, device=torch.device("cuda", self.device_id))
-        args, flat, dfeat = self._backward_args(keypoint_maps, paf_maps, mask, batch_size, loss_scale, flat, True)
+        args, flat, dfeat = self._backward_args(keypoint_maps, paf_maps, mask, batch_size, loss_scale, self._empty(self.grad_spec()[1]), True)
         ms, n = (C.c_float * 4)(), (C.c_int * 4)()
         self._order()
-        check(lib().lwp_profile_stage_backward(*args, flat.data_ptr(), dfeat.data_ptr(), int(reps), ms, n), self.h.ptr)
+        self._call("lwp_profile_stage_backward", *args, flat.data_ptr(), dfeat.data_ptr(), int(reps), ms, n)
         names = ("elementwise", "dgrad", "wgrad", "reduce")
         return dict((names[i], dict(ms=float(ms[i]), launches=int(n[i]))) for i in range(4))
 
@@ -1200,8 +1148,8 @@ class Engine(object):
         splits = C.c_int()
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_dw_grad_sd(self.h.ptr, dzn.data_ptr(), xn.data_ptr(), wt.data_ptr(), N, H, W, Cn, int(stride), int(dil), int(max_chunk),
-                                         dx.data_ptr(), G.data_ptr(), g.data_ptr(), C.byref(splits)), self.h.ptr)
+        self._call("lwp_debug_dw_grad_sd", dzn.data_ptr(), xn.data_ptr(), wt.data_ptr(), N, H, W, Cn, int(stride), int(dil), int(max_chunk),
+                   dx.data_ptr(), G.data_ptr(), g.data_ptr(), C.byref(splits))
         return dx.permute(0, 3, 1, 2).contiguous(), G, g, splits.value
 
     def debug_stem_wgrad(self, dz, x, max_chunk=0):
@@ -1215,7 +1163,7 @@ class Engine(object):
         splits = C.c_int()
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_stem_wgrad(self.h.ptr, dzn.data_ptr(), xc.data_ptr(), N, H, W, int(max_chunk), G.data_ptr(), g.data_ptr(), C.byref(splits)), self.h.ptr)
+        self._call("lwp_debug_stem_wgrad", dzn.data_ptr(), xc.data_ptr(), N, H, W, int(max_chunk), G.data_ptr(), g.data_ptr(), C.byref(splits))
         return G, g, splits.value
 
     # ------------------------------------------------------------------ the stage and cpm gradient kernels alone (tests)
@@ -1254,10 +1202,9 @@ class Engine(object):
         splits = C.c_int()
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_conv_grad(self.h.ptr, dzr.data_ptr(), int(zl), int(zo), xr.data_ptr(), int(xl), int(xo), wc.data_ptr(), N, H, W, cout, cin,
-                                        ks, int(dil), _lib.PAD_MODES[pad], int(max_chunk), cin if acc_from is None else int(acc_from),
-                                        int(bool(no_bias)), int(bool(accumulate)), dxr.data_ptr(), int(dl), int(do), dw.data_ptr(), db.data_ptr(),
-                                        C.byref(splits)), self.h.ptr)
+        self._call("lwp_debug_conv_grad", dzr.data_ptr(), int(zl), int(zo), xr.data_ptr(), int(xl), int(xo), wc.data_ptr(), N, H, W, cout, cin,
+                   ks, int(dil), _lib.PAD_MODES[pad], int(max_chunk), cin if acc_from is None else int(acc_from),
+                   int(bool(no_bias)), int(bool(accumulate)), dxr.data_ptr(), int(dl), int(do), dw.data_ptr(), db.data_ptr(), C.byref(splits))
         return self._nchw(dxr, x.shape, do), dw, db, splits.value, dxr
 
     def debug_cpm_dw_grad(self, dz, x, w, beta=False, accumulate=False, max_chunk=0, dx0=None, dw0=None, ld=None, fill=0.0):
@@ -1273,8 +1220,8 @@ class Engine(object):
         splits = C.c_int()
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_dw_grad(self.h.ptr, dzr.data_ptr(), ld, xr.data_ptr(), ld, wt.data_ptr(), N, H, W, Cn, int(bool(beta)),
-                                      int(bool(accumulate)), int(max_chunk), dxr.data_ptr(), ld, dw.data_ptr(), C.byref(splits)), self.h.ptr)
+        self._call("lwp_debug_dw_grad", dzr.data_ptr(), ld, xr.data_ptr(), ld, wt.data_ptr(), N, H, W, Cn, int(bool(beta)),
+                   int(bool(accumulate)), int(max_chunk), dxr.data_ptr(), ld, dw.data_ptr(), C.byref(splits))
         return self._nchw(dxr, x.shape), dw, splits.value, dxr
 
     def debug_loss_grad(self, outs, keypoint_maps, paf_maps, mask, scale, ld=None, off=0, fill=0.0):
@@ -1293,10 +1240,12 @@ class Engine(object):
         km, pm, mk = (t.detach().to(torch.float32).contiguous() for t in (keypoint_maps, paf_maps, mask))
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_loss_grad(self.h.ptr, a, b, S, ld, km.data_ptr(), pm.data_ptr(), mk.data_ptr(), N, CH, CP, hh * ww, float(scale)), self.h.ptr)
+        self._call("lwp_debug_loss_grad", a, b, S, ld, km.data_ptr(), pm.data_ptr(), mk.data_ptr(), N, CH, CP, hh * ww, float(scale))
         return [self._nchw(d, o.shape, off) for d, o in zip(dst, outs)], dst
 
-    def _debug_rows_op(self, call, g, others, ld, fill):
+    def _debug_rows_op(self, name, g, others, ld, fill, *tail):
+        """``name(g rows, ld, [other rows, ld]..., pixels, channels, *tail)`` on NHWC rows of width ``ld``; a None among
+        ``others`` is passed as a null pointer.  -> (result like g, its rows whole)."""
         torch = _torch()
         N, Cn, H, W = (int(v) for v in g.shape)
         ld = Cn if ld is None else int(ld)
@@ -1304,23 +1253,23 @@ class Engine(object):
         rs = [self._rows(o, ld, 0, fill) if o is not None else None for o in others]
         self._order()
         torch.cuda.synchronize()
-        check(call(gr, rs, ld, N * H * W, Cn), self.h.ptr)
+        args = [gr.data_ptr(), ld]
+        for r in rs:
+            args += [None if r is None else r.data_ptr(), ld]
+        self._call(name, *args, N * H * W, Cn, *tail)
         return self._nchw(gr, g.shape), gr
 
     def debug_relu_mask(self, g, y, res=None, ld=None, fill=0.0):
         """g where y > res (``res`` None: y > 0), else 0; all (N, C, H, W).  -> (result, its rows whole)."""
-        return self._debug_rows_op(lambda gr, rs, ld, M, Cn: lib().lwp_debug_relu_mask(
-            self.h.ptr, gr.data_ptr(), ld, rs[0].data_ptr(), ld, rs[1].data_ptr() if rs[1] is not None else None, ld, M, Cn), g, [y, res], ld, fill)
+        return self._debug_rows_op("lwp_debug_relu_mask", g, [y, res], ld, fill)
 
     def debug_grad_add(self, dst, src, beta, ld=None, fill=0.0):
         """(beta ? dst : 0) + src.  -> (result, its rows whole)."""
-        return self._debug_rows_op(lambda gr, rs, ld, M, Cn: lib().lwp_debug_grad_add(
-            self.h.ptr, gr.data_ptr(), ld, rs[0].data_ptr(), ld, M, Cn, int(bool(beta))), dst, [src], ld, fill)
+        return self._debug_rows_op("lwp_debug_grad_add", dst, [src], ld, fill, int(bool(beta)))
 
     def debug_elu_grad(self, g, y, ld=None, fill=0.0):
         """g * (y > 0 ? 1 : y + 1), y the ELU's output.  -> (result, its rows whole)."""
-        return self._debug_rows_op(lambda gr, rs, ld, M, Cn: lib().lwp_debug_elu_grad(
-            self.h.ptr, gr.data_ptr(), ld, rs[0].data_ptr(), ld, M, Cn), g, [y], ld, fill)
+        return self._debug_rows_op("lwp_debug_elu_grad", g, [y], ld, fill)
 
     def debug_pw_fold(self, w, gamma, var):
         """``pw_fold_kernel`` alone: ``w`` (cout, cin), ``gamma`` and ``var`` (cout,) -> the folded (cout, cin) matrix."""
@@ -1329,7 +1278,7 @@ class Engine(object):
         out = torch.empty_like(w)
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_pw_fold(self.h.ptr, w.data_ptr(), gamma.data_ptr(), var.data_ptr(), out.data_ptr(), int(w.shape[0]), int(w.shape[1])), self.h.ptr)
+        self._call("lwp_debug_pw_fold", w.data_ptr(), gamma.data_ptr(), var.data_ptr(), out.data_ptr(), int(w.shape[0]), int(w.shape[1]))
         return out
 
     def debug_bn_chain(self, G, g, W, b, gamma, mean, var, into, accumulate=False):
@@ -1342,8 +1291,8 @@ class Engine(object):
                 raise ValueError("outputs must be contiguous float32 cuda arrays")
         self._order()
         torch.cuda.synchronize()
-        check(lib().lwp_debug_bn_chain(self.h.ptr, *([t.data_ptr() for t in ins] + [t.data_ptr() if t is not None else None for t in into]
-                                                    + [int(ins[0].shape[0]), int(ins[0].shape[1]), int(bool(accumulate))])), self.h.ptr)
+        self._call("lwp_debug_bn_chain", *[t.data_ptr() for t in ins], *[None if t is None else t.data_ptr() for t in into],
+                   int(ins[0].shape[0]), int(ins[0].shape[1]), int(bool(accumulate)))
 
     def backward_splits(self, layer_index, depthwise=False):
         """Pixel ranges the last ``stage_backward`` split this layer's weight gradient into (0: none ran); ``depthwise``: those
@@ -1372,17 +1321,15 @@ class Engine(object):
         The retained ``train_forward`` is invalidated."""
         flat = self._flat32(flat, "flat")
         self._order()
-        check(lib().lwp_stage_adam_step(self.h.ptr, flat.data_ptr(), float(base_lr), float(betas[0]), float(betas[1]), float(eps),
-                                        float(weight_decay)), self.h.ptr)
+        self._call("lwp_stage_adam_step", flat.data_ptr(), float(base_lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
         self.stage_steps += 1
 
     def stage_params(self):
         """dict state-dict key -> current raw stage parameter (float32 cuda tensors, views of one flat array in the
         gradient-spec layout: ``flat_of`` gives it)."""
-        torch = _torch()
-        flat = torch.empty(self.grad_spec()[1], dtype=torch.float32, device=torch.device("cuda", self.device_id))
+        flat = self._empty(self.grad_spec()[1])
         self._order()
-        check(lib().lwp_stage_params_get(self.h.ptr, flat.data_ptr()), self.h.ptr)
+        self._call("lwp_stage_params_get", flat.data_ptr())
         return self.grad_views(flat)
 
     def trained_params(self):
@@ -1394,34 +1341,30 @@ class Engine(object):
 
     def adam_state(self):
         """dict(step, exp_avg, exp_avg_sq): the step count and the two flat float32 cuda arrays (gradient-spec layout)."""
-        torch = _torch()
-        dev = torch.device("cuda", self.device_id)
-        m = torch.empty(self.grad_spec()[1], dtype=torch.float32, device=dev)
-        v = torch.empty_like(m)
+        m, v = self._empty(self.grad_spec()[1]), self._empty(self.grad_spec()[1])
         step = C.c_int64()
         self._order()
-        check(lib().lwp_stage_adam_state_get(self.h.ptr, m.data_ptr(), v.data_ptr(), C.byref(step)), self.h.ptr)
+        self._call("lwp_stage_adam_state_get", m.data_ptr(), v.data_ptr(), C.byref(step))
         return dict(step=int(step.value), exp_avg=m, exp_avg_sq=v)
 
     def load_adam_state(self, state):
         """Restores what ``adam_state`` returned (arrays on the host or the device); ``None`` discards the state."""
         if state is None:
-            check(lib().lwp_stage_adam_reset(self.h.ptr), self.h.ptr)
+            self._call("lwp_stage_adam_reset")
             return
         torch = _torch()
-        dev = torch.device("cuda", self.device_id)
-        m = self._flat32(torch.as_tensor(state["exp_avg"]).to(dev, torch.float32).contiguous(), "exp_avg")
-        v = self._flat32(torch.as_tensor(state["exp_avg_sq"]).to(dev, torch.float32).contiguous(), "exp_avg_sq")
+        m = self._flat32(torch.as_tensor(state["exp_avg"]).to(self._gpu, torch.float32).contiguous(), "exp_avg")
+        v = self._flat32(torch.as_tensor(state["exp_avg_sq"]).to(self._gpu, torch.float32).contiguous(), "exp_avg_sq")
         self._order()
-        check(lib().lwp_stage_adam_state_set(self.h.ptr, m.data_ptr(), v.data_ptr(), int(state["step"])), self.h.ptr)
+        self._call("lwp_stage_adam_state_set", m.data_ptr(), v.data_ptr(), int(state["step"]))
 
     def time_adam_step(self, flat, base_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4, iters=20):
         """(ms of ``iters`` Adam-kernel launches, ms of ``iters`` repack launches) on scratch copies (HIP events)."""
         flat = self._flat32(flat, "flat")
         ms = (C.c_float * 2)()
         self._order()
-        check(lib().lwp_time_stage_adam_step(self.h.ptr, flat.data_ptr(), float(base_lr), float(betas[0]), float(betas[1]), float(eps),
-                                             float(weight_decay), int(iters), ms), self.h.ptr)
+        self._call("lwp_time_stage_adam_step", flat.data_ptr(), float(base_lr), float(betas[0]), float(betas[1]), float(eps),
+                   float(weight_decay), int(iters), ms)
         return float(ms[0]), float(ms[1])
 
     # ------------------------------------------------------------------ measurement
@@ -1430,13 +1373,13 @@ class Engine(object):
         x_cuda = self._as_device_input(x_cuda)
         N, _, H, W = x_cuda.shape
         ms = C.c_float()
-        check(lib().lwp_time_pipeline(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, what, iters, C.byref(ms)), self.h.ptr)
+        self._call("lwp_time_pipeline", x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, what, iters, C.byref(ms))
         self._last_N = N
         return ms.value
 
     def time_layer(self, layer_index, N, H, W, iters=50):
         ms = C.c_float()
-        check(lib().lwp_debug_time_layer(self.h.ptr, layer_index, N, H, W, iters, C.byref(ms)), self.h.ptr)
+        self._call("lwp_debug_time_layer", layer_index, N, H, W, iters, C.byref(ms))
         return ms.value
 
     def profile_launches(self, x_cuda, reps=5, upsample_ratio=4, demo=True):
@@ -1447,7 +1390,7 @@ class Engine(object):
         ms = (C.c_float * cap)()
         kc = (C.c_int * cap)()
         n = C.c_int()
-        check(lib().lwp_profile_launches(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, reps, ms, kc, cap, C.byref(n)), self.h.ptr)
+        self._call("lwp_profile_launches", x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, reps, ms, kc, cap, C.byref(n))
         layers = self.layers()
         post = ["find_peaks", "nms", "score_pairs", "match", "assemble", "tail_rows", "tail_track"]
         out, npost = [], 0
@@ -1466,7 +1409,7 @@ class Engine(object):
         N, _, H, W = x_cuda.shape
         ms = (C.c_float * 6)()
         ln = (C.c_int * 6)()
-        check(lib().lwp_profile_classes(self.h.ptr, x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, reps, ms, ln), self.h.ptr)
+        self._call("lwp_profile_classes", x_cuda.data_ptr(), N, H, W, upsample_ratio, 1 if demo else 0, reps, ms, ln)
         names = ["stem", "depthwise", "pointwise_1x1", "dense_3x3", "post", "other"]
         return {n: {"ms": ms[i], "launches": ln[i]} for i, n in enumerate(names)}
 
@@ -1474,23 +1417,16 @@ class Engine(object):
     # ------------------------------------------------------------------ COCO key-point evaluation (val.py:17-27)
     @staticmethod
     def _coco_args(packed):
-        i64p, dp, ip = C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int)
-
-        def ptr(a, t):
-            return a.ctypes.data_as(t) if a.size else None
-        return (int(packed["n_images"]), packed["dt_off"].ctypes.data_as(i64p), ptr(packed["dt_kp"], dp), ptr(packed["dt_score"], dp),
-                packed["gt_off"].ctypes.data_as(i64p), ptr(packed["gt_kp"], dp), ptr(packed["gt_area"], dp), ptr(packed["gt_bbox"], dp),
-                ptr(packed["gt_iscrowd"], ip), ptr(packed["gt_ignore"], ip))
+        """n_images, the detection pointers and the ground-truth pointers of ``coco_pack``'s arrays, which ``packed`` keeps alive:
+        what lwp_coco_eval takes.  An empty array is passed as a null pointer."""
+        gt = Engine._coco_gt_args(packed)
+        return gt[:1] + (packed["dt_off"].ctypes.data, _data_or_null(packed["dt_kp"]), _data_or_null(packed["dt_score"])) + gt[1:]
 
     @staticmethod
     def _coco_gt_args(packed):
         """n_images and the ground-truth pointers of ``_coco_args``: what lwp_coco_open takes."""
-        i64p, dp, ip = C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int)
-
-        def ptr(a, t):
-            return a.ctypes.data_as(t) if a.size else None
-        return (int(packed["n_images"]), packed["gt_off"].ctypes.data_as(i64p), ptr(packed["gt_kp"], dp), ptr(packed["gt_area"], dp),
-                ptr(packed["gt_bbox"], dp), ptr(packed["gt_iscrowd"], ip), ptr(packed["gt_ignore"], ip))
+        return (int(packed["n_images"]), packed["gt_off"].ctypes.data) + tuple(
+            _data_or_null(packed[k]) for k in ("gt_kp", "gt_area", "gt_bbox", "gt_iscrowd", "gt_ignore"))
 
     def coco_eval(self, gt, detections=None):
         """COCOeval(gt, loadRes(detections), 'keypoints') evaluate() + accumulate() on the GPU with COCOeval's default
@@ -1499,13 +1435,15 @@ class Engine(object):
         (10, 101, 3) and ``scores`` (10, 101, 3) indexed [IoU threshold, recall threshold, area range], ``recall`` (10, 3),
         ``npig`` (3,) and ``stats``, the ten numbers of summarize().  Two calls on the same input return the same bits."""
         packed = gt if detections is None and "dt_off" in gt else coco_pack(gt, detections)
+        return self._coco_result("lwp_coco_eval", *self._coco_args(packed))
+
+    def _coco_result(self, name, *args):
+        """``name(*args, precision, recall, scores, npig)`` and the dict ``coco_eval`` returns of the four arrays it filled."""
         precision = np.empty((10, 101, 3), dtype=np.float64)
         scores = np.empty((10, 101, 3), dtype=np.float64)
         recall = np.empty((10, 3), dtype=np.float64)
         npig = np.zeros(3, dtype=np.int64)
-        dp = C.POINTER(C.c_double)
-        check(lib().lwp_coco_eval(self.h.ptr, *self._coco_args(packed), precision.ctypes.data_as(dp), recall.ctypes.data_as(dp),
-                                  scores.ctypes.data_as(dp), npig.ctypes.data_as(C.POINTER(C.c_int64))), self.h.ptr)
+        self._call(name, *args, precision.ctypes.data, recall.ctypes.data, scores.ctypes.data, npig.ctypes.data)
         return {"precision": precision, "recall": recall, "scores": scores, "npig": npig, "stats": coco_stats(precision, recall)}
 
     def debug_coco_oks(self, gt, detections=None, image=0):
@@ -1520,9 +1458,8 @@ class Engine(object):
         n_sel, order, npig = C.c_int(), (C.c_int * 20)(), (C.c_int * 3)()
         oks = np.zeros((20, max(G, 1)), dtype=np.float64)
         matched, ignored = np.zeros((30, 20), dtype=np.uint8), np.zeros((30, 20), dtype=np.uint8)
-        ubp = C.POINTER(C.c_ubyte)
-        check(lib().lwp_debug_coco_oks(self.h.ptr, *self._coco_args(packed), image, C.byref(n_sel), order, oks.ctypes.data_as(C.POINTER(C.c_double)),
-                                       oks.size, matched.ctypes.data_as(ubp), ignored.ctypes.data_as(ubp), npig), self.h.ptr)
+        self._call("lwp_debug_coco_oks", *self._coco_args(packed), image, C.byref(n_sel), order, oks.ctypes.data, oks.size,
+                   matched.ctypes.data, ignored.ctypes.data, npig)
         n = n_sel.value
         return {"order": [order[r] for r in range(n)], "oks": oks.reshape(-1)[:n * G].reshape(n, G).copy(),
                 "matched": matched.reshape(3, 10, 20).astype(bool), "ignored": ignored.reshape(3, 10, 20).astype(bool),
@@ -1536,37 +1473,30 @@ class Engine(object):
         g = gt_or_packed if "gt_off" in gt_or_packed else coco_pack_gt(gt_or_packed)
         n = int(g["n_images"])
         row_cap = 32 * n if row_cap is None else int(row_cap)
-        check(lib().lwp_coco_open(self.h.ptr, *self._coco_gt_args(g), row_cap), self.h.ptr)
+        self._call("lwp_coco_open", *self._coco_gt_args(g), row_cap)
         self._coco_n = n
         self._val_store = None                # (val.evaluate(store=True) notes here which labels the store belongs to)
         return g
 
     def coco_release(self):
         self._val_store = None
-        check(lib().lwp_coco_release(self.h.ptr), self.h.ptr)
+        self._call("lwp_coco_release")
 
     def coco_reset(self):
         """Forget the detections and the status, keep the ground truth: the next validation of the same data set."""
-        check(lib().lwp_coco_reset(self.h.ptr), self.h.ptr)
+        self._call("lwp_coco_reset")
 
     def coco_add_maps(self, heat, paf, image_index, upsample_ratio=4, demo=False, layout="NCHW"):
         """``poses_from_maps`` for cuda tensors whose poses go into the detection store instead of to the host: grouping and the
         append kernel are enqueued and the call returns; nothing is synchronised or fetched.  ``image_index``: per frame its
         image's position in the ground truth's ascending id order."""
-        lay = {"NCHW": 0, "NHWC": 1}[layout]
         if not getattr(heat, "is_cuda", False) or not getattr(paf, "is_cuda", False):
             raise TypeError("coco_add_maps takes cuda tensors (the maps stay on the device)")
-        heat, paf = heat.detach().contiguous(), paf.detach().contiguous()
-        if lay == 0:
-            N, _, hs, ws = heat.shape
-        else:
-            N, hs, ws, _ = heat.shape
+        hp, pp, _, lay, N, hs, ws, _ = self._maps(heat, paf, layout)
         idx = np.ascontiguousarray(np.atleast_1d(image_index), dtype=np.int32)
         if idx.shape != (N,):
             raise ValueError("image_index must hold one index per frame (%d), got %s" % (N, idx.shape))
-        self._order(heat.device)
-        check(lib().lwp_coco_add_maps(self.h.ptr, heat.data_ptr(), paf.data_ptr(), lay, N, hs, ws, upsample_ratio, 1 if demo else 0,
-                                      idx.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        self._call("lwp_coco_add_maps", hp, pp, lay, N, hs, ws, upsample_ratio, 1 if demo else 0, idx.ctypes.data)
 
     def coco_add_rows(self, image_index, keypoints, scores):
         """Append ready-made detections of one image: ``keypoints`` (n, 17, 3) or (n, 51), ``scores`` (n,); enqueue only."""
@@ -1574,15 +1504,13 @@ class Engine(object):
         sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
         if len(kp) != len(sc):
             raise ValueError("%d key-point rows but %d scores" % (len(kp), len(sc)))
-        dp = C.POINTER(C.c_double)
-        check(lib().lwp_coco_add_rows(self.h.ptr, int(image_index), len(sc), kp.ctypes.data_as(dp) if len(sc) else None,
-                                      sc.ctypes.data_as(dp) if len(sc) else None), self.h.ptr)
+        self._call("lwp_coco_add_rows", int(image_index), len(sc), _data_or_null(kp), _data_or_null(sc))
 
     def coco_counts(self):
         """(rows in the store, rows per image (n_images,) int32) after everything queued so far; raises the store's status."""
         total = C.c_int64()
         per = np.zeros(self._coco_n, dtype=np.int32)
-        check(lib().lwp_coco_counts(self.h.ptr, C.byref(total), per.ctypes.data_as(C.POINTER(C.c_int))), self.h.ptr)
+        self._call("lwp_coco_counts", C.byref(total), per.ctypes.data)
         return int(total.value), per
 
     def coco_rows(self):
@@ -1593,21 +1521,13 @@ class Engine(object):
         img = np.zeros(n, dtype=np.int32)
         kp = np.zeros((n, 17, 3), dtype=np.float64)
         sc = np.zeros(n, dtype=np.float64)
-        dp = C.POINTER(C.c_double)
-        check(lib().lwp_coco_rows(self.h.ptr, img.ctypes.data_as(C.POINTER(C.c_int)), kp.ctypes.data_as(dp), sc.ctypes.data_as(dp), n), self.h.ptr)
+        self._call("lwp_coco_rows", img.ctypes.data, kp.ctypes.data, sc.ctypes.data, n)
         return {"image": img, "keypoints": kp, "score": sc}
 
     def coco_finish(self):
         """``coco_eval`` on the store's rows against the resident ground truth: the same dict, bit for bit what ``coco_eval``
         returns for the same rows.  The store stays as it is."""
-        precision = np.empty((10, 101, 3), dtype=np.float64)
-        scores = np.empty((10, 101, 3), dtype=np.float64)
-        recall = np.empty((10, 3), dtype=np.float64)
-        npig = np.zeros(3, dtype=np.int64)
-        dp = C.POINTER(C.c_double)
-        check(lib().lwp_coco_finish(self.h.ptr, precision.ctypes.data_as(dp), recall.ctypes.data_as(dp), scores.ctypes.data_as(dp),
-                                    npig.ctypes.data_as(C.POINTER(C.c_int64))), self.h.ptr)
-        return {"precision": precision, "recall": recall, "scores": scores, "npig": npig, "stats": coco_stats(precision, recall)}
+        return self._coco_result("lwp_coco_finish")
 
     def debug_coco_rows(self, frames, image_index):
         """The append kernel alone: ``frames`` is a list of (pose_entries (P, 20), all_keypoints (n, 4)) as ``poses_from_maps``
@@ -1618,9 +1538,7 @@ class Engine(object):
         ent = np.ascontiguousarray(np.concatenate([np.asarray(f[0], dtype=np.float64).reshape(-1, 20) for f in frames]))
         kpt = np.ascontiguousarray(np.concatenate([np.asarray(f[1], dtype=np.float64).reshape(-1, 4) for f in frames]))
         idx = np.ascontiguousarray(image_index, dtype=np.int32)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
-        check(lib().lwp_debug_coco_rows(self.h.ptr, N, ent.ctypes.data_as(dp) if ent.size else None, ne.ctypes.data_as(ip),
-                                        kpt.ctypes.data_as(dp) if kpt.size else None, nk.ctypes.data_as(ip), idx.ctypes.data_as(ip)), self.h.ptr)
+        self._call("lwp_debug_coco_rows", N, _data_or_null(ent), ne.ctypes.data, _data_or_null(kpt), nk.ctypes.data, idx.ctypes.data)
 
 
 def coco_pack(gt, detections):
