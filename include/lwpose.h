@@ -796,6 +796,58 @@ int lwp_debug_jpeg_scan(const unsigned char* data, size_t len, unsigned char* by
 int lwp_time_jpeg_entropy_batch(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, int subseq_bytes,
                                 int iters, float* ms_total, int* rounds);
 
+/* ---- JPEG files, written: replaces cv2.imwrite(path.jpg, img) and, behind demo.VideoWriter, a Motion-JPEG cv2.VideoWriter
+ *      (the reference only shows its result, demo.py:128-166).  The whole encoder runs on the device
+ *      (csrc/jpeg_encode_kernels.hip); what crosses to the host is the compressed scan, not pixels.  Every step is
+ *      libjpeg's default compression path in integer arithmetic, restated and pinned byte for byte against the files Pillow
+ *      (libjpeg-turbo) writes of the same pixels; agreement with cv2.imwrite itself is NOT pinned (cv2 is not a dependency).
+ *        colour        jccolor.c, 16-bit fixed point: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb and Cr likewise
+ *        sampling      4:4:4, 4:2:2 (h2v1, bias 0, 1, 0, 1 .. along the columns), 4:2:0 (h2v2, bias 1, 2, 1, 2 ..); no smoothing
+ *        edges         a component has ceil(ceil(W h / hmax) / 8) by ceil(ceil(H v / vmax) / 8) REAL blocks; the right edge repeats
+ *                      the last pixel up to them; the bottom edge repeats the last pixel row up to a multiple of vmax rows only,
+ *                      and the last DOWN-SAMPLED row from there; the other blocks of the MCU-padded grids are DUMMY blocks: 63
+ *                      zeros and the DC of the block before them in MCU order (jccoefct.c)
+ *        forward DCT   jfdctint.c (CONST_BITS 13, PASS1_BITS 2) on sample - 128, rows then columns
+ *        quantiser     sign(c) * ((|c| + (8 q >> 1)) / (8 q)); q from jpeg_quality_scaling of Annex K's two tables, clamped to 1..255
+ *        entropy code  Annex K's four Huffman tables; the last byte of the scan and of every restart interval padded with one-bits;
+ *                      00 stuffed behind every FF; RSTn between the intervals
+ *      The stage in front of the entropy code leaves its coefficients in exactly the COEFFICIENT LAYOUT of the decoder above.
+ *      FILE LAYOUT (Pillow's): SOI, APP0 JFIF 1.1 (units 0, density 1 x 1), DQT 0, DQT 1, SOF0 (components 1, 2, 3 with tables
+ *      0, 1, 1), DHT DC 0, AC 0, DC 1, AC 1, DRI if restart_interval > 0, SOS, the scan, EOI.
+ *      OUT OF SCOPE: grey output, optimised Huffman tables, progressive and arithmetic coding, 4:4:0 / 4:1:1, custom
+ *      quantisation tables, Exif.  A height or width outside 1..65535 is LWP_ERR_ARG with the image's index. */
+enum { LWP_JPEG_444 = 0, LWP_JPEG_422 = 1, LWP_JPEG_420 = 2 };     /* Pillow's subsampling numbers */
+/* bytes that hold the file of a height x width frame whatever its pixels: the header, every block at its longest code with
+ * every byte stuffed, a marker an interval.  Far above what pictures take (about 416 bytes a block).  No handle, no GPU. */
+int lwp_jpeg_encode_bound(int height, int width, int subsampling, int restart_interval, size_t* bound_out);
+/* N frames (frames[i]: heights[i] x widths[i] x 3 bytes of row-major BGR, all in HOST memory or all in DEVICE memory as mem says;
+ * host frames go up in ONE copy with the per-image records, device frames are read in place) -> N whole files.  1 <= N <= 65535,
+ * sizes mixed; quality 1..100, subsampling LWP_JPEG_444 / 422 / 420 and restart_interval (MCUs, 0..65535) hold for the batch.
+ * Six launches and one memset cover the batch; the call enqueues everything, WAITS once for the N scan lengths, checks the
+ * capacities and then copies the scans out through pinned staging.  out[i]: HOST memory of cap[i] bytes that receives file i,
+ * or NULL: then only len_out[i] is reported (a sizing call; the scan stays in the handle's workspace until the next call and is
+ * not fetched).  len_out[i]: the length of file i.  cap[i] below that is LWP_ERR_CAPACITY with the image's index (the lowest) in
+ * the message, and NO out[i] is written; lwp_jpeg_encode_bound always suffices.  Runs on the handle's stream and waits for the
+ * caller's stream as lwp_set_stream says; workspace and staging show in lwp_debug_live_resources and go with lwp_destroy.  Needs
+ * no weights.  The same frames give the same bytes. */
+int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights, const int* widths,
+                          int quality, int subsampling, int restart_interval, unsigned char* const* out, const size_t* cap,
+                          size_t* len_out);
+/* the first stage alone, for tests: the quantised coefficients of frame i (64 * total_blocks int16 in the COEFFICIENT LAYOUT;
+ * total_blocks as lwp_jpeg_info reports it of the header) to the HOST buffer coef_out[i], the batch's tables to qtables_out[256]
+ * (slots 0 and 1). */
+int lwp_debug_jpeg_encode_blocks(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights,
+                                 const int* widths, int quality, int subsampling, int16_t* const* coef_out, uint16_t* qtables_out);
+/* the header bytes alone, SOI up to and including SOS (at most 640 bytes; LWP_ERR_CAPACITY if cap is below them).  No handle,
+ * no GPU. */
+int lwp_debug_jpeg_encode_header(int height, int width, int quality, int subsampling, int restart_interval, unsigned char* out,
+                                 size_t cap, size_t* n_out);
+/* the kernels alone (tools/jpeg_encode_bench.py): the checks and the upload, one run of all stages, then `iters` back-to-back
+ * launches of each stage between HIP events.  ms_total[6] out: A colour / sampling / DCT / quantiser, B bit counts, C offsets,
+ * D memset and code write, E FF counts, F stuffing. */
+int lwp_time_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights,
+                               const int* widths, int quality, int subsampling, int restart_interval, int iters, float* ms_total);
+
 /* ---- COCO key-point evaluation: replaces pycocotools' COCOeval(gt, dt, 'keypoints') evaluate() + accumulate() behind
  *      val.py:17-27, with COCOeval's default parameters (the 17 OKS sigmas, IoU thresholds 0.5:0.05:0.95, 101 recall
  *      thresholds, maxDets 20, area ranges all [0, 1e10] / medium [32^2, 96^2] / large [96^2, 1e10], inclusive at both ends) and

@@ -10,6 +10,7 @@ LWP_OK, LWP_ERR_ARG, LWP_ERR_HIP, LWP_ERR_STATE, LWP_ERR_CAPACITY, LWP_ERR_NOGPU
 MEM_HOST, MEM_DEVICE = 0, 1
 JPEG_ENTROPY_HOST, JPEG_ENTROPY_DEVICE = 0, 1
 JPEG_ENTROPY_MODES = {"host": JPEG_ENTROPY_HOST, "device": JPEG_ENTROPY_DEVICE}
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
 F32, BF16, F16 = 0, 1, 2
 TRAIN_STAGES, TRAIN_CPM, TRAIN_ALL = 0, 1, 2
 TRAIN_SCOPES = {"stages": TRAIN_STAGES, "cpm": TRAIN_CPM, "all": TRAIN_ALL}
@@ -47,6 +48,8 @@ EXPORTS = [
     "lwp_coco_rows", "lwp_coco_finish", "lwp_debug_coco_rows",
     "lwp_jpeg_info", "lwp_debug_jpeg_blocks", "lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch",
     "lwp_set_jpeg_entropy", "lwp_debug_jpeg_entropy_batch", "lwp_debug_jpeg_scan", "lwp_time_jpeg_entropy_batch",
+    "lwp_jpeg_encode_bound", "lwp_jpeg_encode_batch", "lwp_debug_jpeg_encode_blocks", "lwp_debug_jpeg_encode_header",
+    "lwp_time_jpeg_encode_batch",
     "lwp_set_backward_precision", "lwp_get_backward_precision",
     "lwp_stage_losses_log", "lwp_loss_log_read",
 ]
@@ -209,6 +212,12 @@ def lib():
     L.lwp_debug_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(vp), C.POINTER(vp), ip]
     L.lwp_debug_jpeg_scan.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, ip]
     L.lwp_time_jpeg_entropy_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_int, fp, ip]
+    jpeg_frames = [vp, C.c_int, C.POINTER(vp), C.c_int, ip, ip]          # handle, N, frames, mem, heights, widths
+    L.lwp_jpeg_encode_bound.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)]
+    L.lwp_jpeg_encode_batch.argtypes = jpeg_frames + [C.c_int] * 3 + [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.lwp_debug_jpeg_encode_blocks.argtypes = jpeg_frames + [C.c_int] * 2 + [C.POINTER(vp), vp]
+    L.lwp_debug_jpeg_encode_header.argtypes = [C.c_int] * 5 + [vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lwp_time_jpeg_encode_batch.argtypes = jpeg_frames + [C.c_int] * 4 + [fp]
     L.lwp_set_backward_precision.argtypes = [vp, C.c_int, C.c_double]
     L.lwp_get_backward_precision.argtypes = [vp, ip, dp]
     L.lwp_stage_losses_log.argtypes = L.lwp_stage_losses.argtypes[:-1] + [C.c_double]

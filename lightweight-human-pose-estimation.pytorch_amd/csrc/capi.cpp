@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "jpeg_encode_host.h"
 #include "jpeg_host.h"
 #include "lwp_internal.h"
 #include "lwp_owners.h"
@@ -152,6 +153,11 @@ struct lwp_context {
     DevBuf d_jpeg;
     PinBuf jpeg_stage; Event jpeg_ev; bool jpeg_copy_pending = false;
     int jpeg_entropy_mode = LWP_JPEG_ENTROPY_HOST, jpeg_subseq = kJpegSubseqDefault;     // lwp_set_jpeg_entropy
+    // JPEG encode (lwp_jpeg_encode_batch): the device workspace [upload: records | tables | host frames][coefficients | bit
+    // counts | offsets | interval starts | lengths | un-stuffed scans | chunk counts | stuffed scans] and the pinned staging the
+    // upload leaves through and the scans come back through; every call ends synchronised, so neither outlives it in use
+    DevBuf d_jpeg_enc;
+    PinBuf jpeg_enc_stage;
     bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
@@ -259,7 +265,7 @@ static int order_out(lwp_context* h, hipStream_t from, bool* ordered) {
     return LWP_OK;
 }
 
-extern "C" int lwp_version(void) { return 108; }
+extern "C" int lwp_version(void) { return 109; }
 
 extern "C" int lwp_set_stream(lwp_handle h, void* caller_stream, int enable) {
     if (!h) return LWP_ERR_ARG;
@@ -2971,6 +2977,259 @@ extern "C" int lwp_time_jpeg_decode_batch(lwp_handle h, int N, const unsigned ch
     rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_idct(j, h->stream)); return (int)LWP_OK; }, &ms_total[0]);
     if (rc) return rc;
     return time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_color(j, h->stream)); return (int)LWP_OK; }, &ms_total[1]);
+}
+
+// ---------------------------------------------------------------------------------------------- JPEG encode
+extern "C" int lwp_jpeg_encode_bound(int height, int width, int subsampling, int restart_interval, size_t* bound_out) {
+    JpegEncGeom g;
+    if (!bound_out) return fail(nullptr, LWP_ERR_ARG, "bound_out is null");
+    if (!jpeg_enc_geometry(height, width, subsampling, restart_interval, &g))
+        return fail(nullptr, LWP_ERR_ARG, "jpeg encode: height and width must be 1..65535, subsampling 0..2, restart_interval 0..65535");
+    *bound_out = kJpegEncHeaderMax + jpeg_enc_scan_bound(g) + 2;
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_jpeg_encode_header(int height, int width, int quality, int subsampling, int restart_interval, unsigned char* out,
+                                            size_t cap, size_t* n_out) {
+    JpegEncGeom g;
+    if (!out || !n_out) return fail(nullptr, LWP_ERR_ARG, "out / n_out is null");
+    if (quality < 1 || quality > 100) return fail(nullptr, LWP_ERR_ARG, "jpeg encode: quality must be 1..100");
+    if (!jpeg_enc_geometry(height, width, subsampling, restart_interval, &g))
+        return fail(nullptr, LWP_ERR_ARG, "jpeg encode: height and width must be 1..65535, subsampling 0..2, restart_interval 0..65535");
+    unsigned char hd[kJpegEncHeaderMax];
+    const size_t n = jpeg_enc_header(height, width, quality, subsampling, restart_interval, hd);
+    if (n > cap) return fail(nullptr, LWP_ERR_CAPACITY, "jpeg encode: the header does not fit cap (640 bytes always suffice)");
+    memcpy(out, hd, n);
+    *n_out = n;
+    return LWP_OK;
+}
+
+struct JpegEncBatch {
+    JpegEncLaunch e{};
+    std::vector<JpegEncGeom> geom;
+    size_t o_ubytes = 0, ubytes_total = 0;             // the un-stuffed scans of the batch: one region, zeroed in front of stage D
+    std::vector<size_t> sbytes;                        // where each stuffed scan starts in the workspace
+};
+
+// checks, the per-image records and the batch's one upload [records | block starts | chunk starts | quantisation tables | Huffman
+// codes | host frames]; the arrays the kernels fill lie behind it in the same allocation.  Nothing is enqueued before every
+// image has been checked.
+static int jpeg_enc_prepare(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights, const int* widths,
+                            int quality, int subsampling, int restart_interval, JpegEncBatch* B) {
+    char msg[200];
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (!frames || !heights || !widths) return fail(h, LWP_ERR_ARG, "frames / heights / widths is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    if (mem != LWP_MEM_HOST && mem != LWP_MEM_DEVICE) return fail(h, LWP_ERR_ARG, "mem must be LWP_MEM_HOST or LWP_MEM_DEVICE");
+    if (quality < 1 || quality > 100) return fail(h, LWP_ERR_ARG, "jpeg encode: quality must be 1..100");
+    if (subsampling < 0 || subsampling > 2) return fail(h, LWP_ERR_ARG, "jpeg encode: subsampling must be LWP_JPEG_444, LWP_JPEG_422 or LWP_JPEG_420");
+    if (restart_interval < 0 || restart_interval > 65535) return fail(h, LWP_ERR_ARG, "jpeg encode: restart_interval must be 0..65535 MCUs");
+    B->geom.assign((size_t)N, JpegEncGeom{});
+    uint64_t blocks = 0, chunks = 0, intervals = 0, pixels = 0, scan_bytes = 0;
+    for (int i = 0; i < N; ++i) {
+        if (!frames[i]) { snprintf(msg, sizeof msg, "image %d: the frame is null", i); return fail(h, LWP_ERR_ARG, msg); }
+        JpegEncGeom& g = B->geom[i];
+        if (!jpeg_enc_geometry(heights[i], widths[i], subsampling, restart_interval, &g)) {
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: %d x %d: height and width must be 1..65535", i, heights[i], widths[i]);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        if ((uint64_t)g.total_blocks * kJpegEncBlockBytes * 8 >= ((uint64_t)1 << 32)) {       // bit offsets are 32-bit
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: %d x %d has too many blocks for one scan: encode it in tiles", i, heights[i], widths[i]);
+            return fail(h, LWP_ERR_CAPACITY, msg);
+        }
+        blocks += (uint64_t)g.total_blocks;
+        intervals += (uint64_t)g.intervals;
+        chunks += (jpeg_enc_unstuffed_bound(g) + kJpegEncChunk - 1) / kJpegEncChunk;
+        pixels += (uint64_t)heights[i] * (uint64_t)widths[i] * 3;
+        scan_bytes += 3 * jpeg_enc_unstuffed_bound(g);
+    }
+    if (blocks > 0x7fffffffu || chunks > 0x7fffffffu || scan_bytes + blocks * 136 + pixels > ((uint64_t)1 << 36))
+        return fail(h, LWP_ERR_CAPACITY, "jpeg encode: the batch needs more than 64 GiB of workspace: encode it in parts");
+    auto align = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+    const size_t o_images = 0, o_bstart = align((size_t)N * sizeof(JpegEncImage), 16), o_cstart = align(o_bstart + ((size_t)N + 1) * 4, 16);
+    const size_t o_qt = align(o_cstart + ((size_t)N + 1) * 4, 16), o_huff = o_qt + 2 * 64 * sizeof(uint16_t);
+    size_t upload = align(o_huff + sizeof(JpegEncHuff), 256);
+    std::vector<size_t> o_frame((size_t)N, 0);
+    if (mem == LWP_MEM_HOST)
+        for (int i = 0; i < N; ++i) { o_frame[i] = upload; upload = align(upload + (size_t)heights[i] * widths[i] * 3, 256); }
+    const size_t o_coef = upload, o_bits = o_coef + (size_t)blocks * 128, o_offs = o_bits + (size_t)blocks * 4;
+    const size_t o_istart = o_offs + (size_t)blocks * 4, o_ulen = o_istart + (size_t)intervals * 4, o_slen = o_ulen + (size_t)N * 4;
+    const size_t o_ffbase = o_slen + (size_t)N * 4;
+    size_t at = align(o_ffbase + (size_t)chunks * 4, 256);
+    B->o_ubytes = at;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, h->jpeg_enc_stage.ensure(upload));
+    unsigned char* host = h->jpeg_enc_stage.as<unsigned char>();
+    JpegEncImage* images = reinterpret_cast<JpegEncImage*>(host + o_images);
+    unsigned* bstart = reinterpret_cast<unsigned*>(host + o_bstart);
+    unsigned* cstart = reinterpret_cast<unsigned*>(host + o_cstart);
+    uint64_t b0 = 0, c0 = 0, i0 = 0;
+    for (int i = 0; i < N; ++i) {                      // the un-stuffed scans, back to back, whole chunks each
+        const JpegEncGeom& g = B->geom[i];
+        JpegEncImage& im = images[i];
+        memset(&im, 0, sizeof im);
+        const size_t n_chunks = (jpeg_enc_unstuffed_bound(g) + kJpegEncChunk - 1) / kJpegEncChunk;
+        im.ubytes = (long long)at; im.ucap = (unsigned)(n_chunks * kJpegEncChunk);
+        at += n_chunks * kJpegEncChunk;
+        im.width = widths[i]; im.height = heights[i]; im.hs = g.hs; im.vs = g.vs; im.mcus_x = g.mcus_x; im.mcus_y = g.mcus_y;
+        unsigned p0 = 0;
+        for (int c = 0; c < 3; ++c) {
+            im.blocks_w[c] = g.blocks_w[c]; im.real_w[c] = g.real_w[c]; im.real_h[c] = g.real_h[c];
+            im.plane0[c] = p0;
+            p0 += (unsigned)(g.blocks_w[c] * g.blocks_h[c]);
+        }
+        im.block0 = (unsigned)b0; im.n_blocks = (unsigned)g.total_blocks;
+        im.per_mcu = (unsigned)(g.hs * g.vs + 2); im.ri_blocks = im.per_mcu * (unsigned)restart_interval;
+        im.int0 = (unsigned)i0; im.n_int = (unsigned)g.intervals;
+        im.chunk0 = (unsigned)c0; im.n_chunks = (unsigned)n_chunks;
+        bstart[i] = (unsigned)b0; cstart[i] = (unsigned)c0;
+        b0 += (uint64_t)g.total_blocks; c0 += n_chunks; i0 += (uint64_t)g.intervals;
+    }
+    bstart[N] = (unsigned)b0; cstart[N] = (unsigned)c0;
+    B->ubytes_total = at - B->o_ubytes;
+    B->sbytes.assign((size_t)N, 0);
+    for (int i = 0; i < N; ++i) {
+        at = align(at, 16);
+        B->sbytes[i] = at;
+        images[i].sbytes = (long long)at; images[i].scap = (unsigned)jpeg_enc_scan_bound(B->geom[i]);
+        at += images[i].scap;
+    }
+    const size_t total = align(at, 256);
+    jpeg_enc_quant_tables(quality, reinterpret_cast<uint16_t(*)[64]>(host + o_qt));
+    jpeg_enc_huffman(reinterpret_cast<JpegEncHuff*>(host + o_huff));
+    int rc = order_in(h);
+    if (rc) return rc;
+    if (h->d_jpeg_enc.size() < total) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        HIP_TRY(h, h->d_jpeg_enc.ensure(total));
+    }
+    unsigned char* dev = h->d_jpeg_enc.as<unsigned char>();
+    for (int i = 0; i < N; ++i) {
+        if (mem == LWP_MEM_HOST) {
+            memcpy(host + o_frame[i], frames[i], (size_t)heights[i] * widths[i] * 3);
+            images[i].src = dev + o_frame[i];
+        } else {
+            images[i].src = frames[i];
+        }
+    }
+    HIP_TRY(h, hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, h->stream));
+    JpegEncLaunch& e = B->e;
+    e.images = reinterpret_cast<const JpegEncImage*>(dev + o_images);
+    e.block_start = reinterpret_cast<const unsigned*>(dev + o_bstart); e.chunk_start = reinterpret_cast<const unsigned*>(dev + o_cstart);
+    e.qtables = reinterpret_cast<const uint16_t*>(dev + o_qt); e.huff = reinterpret_cast<const unsigned*>(dev + o_huff);
+    e.coef = reinterpret_cast<int16_t*>(dev + o_coef);
+    e.bits = reinterpret_cast<unsigned*>(dev + o_bits); e.offs = reinterpret_cast<unsigned*>(dev + o_offs);
+    e.istart = reinterpret_cast<unsigned*>(dev + o_istart);
+    e.ulen = reinterpret_cast<unsigned*>(dev + o_ulen); e.slen = reinterpret_cast<unsigned*>(dev + o_slen);
+    e.ffbase = reinterpret_cast<unsigned*>(dev + o_ffbase);
+    e.workspace = dev;
+    e.n_images = N; e.total_blocks = (unsigned)b0; e.total_chunks = (unsigned)c0;
+    return LWP_OK;
+}
+
+// the six stages, in order, on the handle's stream
+static int jpeg_enc_enqueue(lwp_handle h, const JpegEncBatch& B) {
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_lengths(B.e, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_offsets(B.e, h->stream));
+    HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.o_ubytes, 0, B.ubytes_total, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_write(B.e, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_stuff_scan(B.e, h->stream));
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_stuff(B.e, h->stream));
+    return LWP_OK;
+}
+
+extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights, const int* widths,
+                                     int quality, int subsampling, int restart_interval, unsigned char* const* out, const size_t* cap,
+                                     size_t* len_out) {
+    if (!out || !cap || !len_out) return fail(h, LWP_ERR_ARG, "out / cap / len_out is null");
+    JpegEncBatch B;
+    int rc = jpeg_enc_prepare(h, N, frames, mem, heights, widths, quality, subsampling, restart_interval, &B);
+    if (rc) return rc;
+    rc = jpeg_enc_enqueue(h, B);
+    if (rc) return rc;
+    // the one wait of the call: the N lengths.  The staging's front part is free again: the upload ran in front of the kernels
+    unsigned* lens = h->jpeg_enc_stage.as<unsigned>();
+    HIP_TRY(h, hipMemcpyAsync(lens, B.e.slen, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<size_t> scan((size_t)N), at((size_t)N);
+    unsigned char hd[kJpegEncHeaderMax];
+    const size_t hd_len = jpeg_enc_header(heights[0], widths[0], quality, subsampling, restart_interval, hd);      // the same for every size
+    size_t stage = 0;
+    for (int i = 0; i < N; ++i) {
+        scan[i] = lens[i];
+        if (scan[i] > jpeg_enc_scan_bound(B.geom[i])) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: a scan of %zu bytes where %zu is the most possible", i, scan[i], jpeg_enc_scan_bound(B.geom[i]));
+            return fail(h, LWP_ERR_INTERNAL, msg);
+        }
+        at[i] = stage;
+        if (out[i]) stage += (scan[i] + 15) & ~(size_t)15;
+    }
+    for (int i = 0; i < N; ++i)
+        if (out[i] && cap[i] < hd_len + scan[i] + 2) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: the file takes %zu bytes, cap is %zu", i, hd_len + scan[i] + 2, cap[i]);
+            return fail(h, LWP_ERR_CAPACITY, msg);
+        }
+    HIP_TRY(h, h->jpeg_enc_stage.ensure(stage));
+    unsigned char* host = h->jpeg_enc_stage.as<unsigned char>();
+    for (int i = 0; i < N; ++i)
+        if (out[i] && scan[i]) HIP_TRY(h, hipMemcpyAsync(host + at[i], B.e.workspace + B.sbytes[i], scan[i], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < N; ++i) {
+        len_out[i] = hd_len + scan[i] + 2;
+        if (!out[i]) continue;
+        jpeg_enc_header(heights[i], widths[i], quality, subsampling, restart_interval, out[i]);
+        memcpy(out[i] + hd_len, host + at[i], scan[i]);
+        out[i][hd_len + scan[i]] = 0xFF; out[i][hd_len + scan[i] + 1] = 0xD9;
+    }
+    return LWP_OK;
+}
+
+extern "C" int lwp_debug_jpeg_encode_blocks(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights,
+                                            const int* widths, int quality, int subsampling, int16_t* const* coef_out, uint16_t* qtables_out) {
+    if (!coef_out || !qtables_out) return fail(h, LWP_ERR_ARG, "coef_out / qtables_out is null");
+    JpegEncBatch B;
+    int rc = jpeg_enc_prepare(h, N, frames, mem, heights, widths, quality, subsampling, 0, &B);
+    if (rc) return rc;
+    for (int i = 0; i < N; ++i)
+        if (!coef_out[i]) return fail(h, LWP_ERR_ARG, "coef_out holds a null pointer");
+    LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream));
+    size_t b0 = 0;
+    for (int i = 0; i < N; ++i) {
+        HIP_TRY(h, hipMemcpyAsync(coef_out[i], B.e.coef + b0 * 64, (size_t)B.geom[i].total_blocks * 128, hipMemcpyDeviceToHost, h->stream));
+        b0 += (size_t)B.geom[i].total_blocks;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    memset(qtables_out, 0, (size_t)kJpegQuantSlots * 64 * sizeof(uint16_t));
+    jpeg_enc_quant_tables(quality, reinterpret_cast<uint16_t(*)[64]>(qtables_out));
+    return LWP_OK;
+}
+
+extern "C" int lwp_time_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights,
+                                          const int* widths, int quality, int subsampling, int restart_interval, int iters, float* ms_total) {
+    if (iters < 1 || !ms_total) return fail(h, LWP_ERR_ARG, "iters must be at least 1 and ms_total non-null");
+    JpegEncBatch B;
+    int rc = jpeg_enc_prepare(h, N, frames, mem, heights, widths, quality, subsampling, restart_interval, &B);
+    if (rc) return rc;
+    rc = jpeg_enc_enqueue(h, B);                       // every stage has its inputs, whatever order the windows below run in
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream)); return (int)LWP_OK; }, &ms_total[0]);
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_enc_lengths(B.e, h->stream)); return (int)LWP_OK; }, &ms_total[1]);
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_enc_offsets(B.e, h->stream)); return (int)LWP_OK; }, &ms_total[2]);
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() {
+        HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.o_ubytes, 0, B.ubytes_total, h->stream));
+        LAUNCH(h, KC_OTHER, launch_jpeg_enc_write(B.e, h->stream));
+        return (int)LWP_OK;
+    }, &ms_total[3]);
+    if (rc) return rc;
+    rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_enc_stuff_scan(B.e, h->stream)); return (int)LWP_OK; }, &ms_total[4]);
+    if (rc) return rc;
+    return time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_enc_stuff(B.e, h->stream)); return (int)LWP_OK; }, &ms_total[5]);
 }
 
 // ---------------------------------------------------------------------------------------------- training augmentation

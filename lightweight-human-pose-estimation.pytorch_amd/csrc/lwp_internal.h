@@ -494,6 +494,52 @@ struct JpegEntropyLaunch {
     int subseq_bytes;
 };
 hipError_t launch_jpeg_entropy(const JpegEntropyLaunch& e, hipStream_t s);
+// ---- JPEG encode on the device (jpeg_encode_kernels.hip; libjpeg's default compression path: jccolor.c, box
+// down-sampling, jfdctint.c, Annex K's Huffman tables).  Six stages over a whole batch of frames of mixed sizes:
+//   A  colour, down-sampling, edges, forward DCT, quantisation -> the coefficient layout of jpeg_host.h (8 lanes a block)
+//   B  the bit count of every block, in stream (MCU) order (one lane a block)
+//   C  per image, the scan of the counts into bit offsets, every restart interval starting on a byte (one workgroup an image)
+//   D  the codes of every block at its offset, OR-ed into the zeroed un-stuffed scan (one lane a block)
+//   E  per image, the 0xFF bytes in front of every chunk of the un-stuffed scan (one workgroup an image)
+//   F  the stuffed scan: FF 00 for FF, RSTn between the intervals (one lane a chunk)
+constexpr int kJpegEncBlocksPerGroup = 32;    // stage A: 8 lanes a block, 256 threads a workgroup
+constexpr int kJpegEncGroup = 256;            // stages B .. F: threads a workgroup; C and E step over an image in tiles of this many
+constexpr int kJpegEncChunk = 32;             // stages E and F: un-stuffed bytes a lane owns
+struct JpegEncImage {
+    const unsigned char* src;                 // device BGR pixels, width * 3 bytes a row
+    long long ubytes, sbytes;                 // byte offsets in the workspace: the un-stuffed scan (zeroed, 32-byte granular), the stuffed scan
+    int width, height, hs, vs;                // hs, vs: luma sampling (chroma 1 x 1)
+    int mcus_x, mcus_y;
+    int blocks_w[3];                          // MCU-padded grid widths
+    int real_w[3], real_h[3];                 // blocks that hold samples; the others are dummy blocks
+    unsigned block0, n_blocks;                // its blocks in the batch's arrays (coefficients: plane order; bits, offsets: stream order)
+    unsigned plane0[3];                       // first block of each plane, image-relative
+    unsigned per_mcu, ri_blocks;              // blocks an MCU; blocks a restart interval (0: no restarts)
+    unsigned int0, n_int;                     // its restart intervals in the batch's interval array
+    unsigned chunk0, n_chunks;                // its chunks (the bound) in the batch's chunk array
+    unsigned ucap, scap;                      // bytes available at ubytes and at sbytes
+};
+struct JpegEncLaunch {
+    const JpegEncImage* images;               // [n_images]
+    const unsigned* block_start;              // [n_images + 1] block0 of every image, then the total
+    const unsigned* chunk_start;              // [n_images + 1]
+    const uint16_t* qtables;                  // [2][64] natural order
+    const unsigned* huff;                     // JpegEncHuff (jpeg_encode_host.h) as words: dc[2][16], ac[2][256]
+    int16_t* coef;                            // [total_blocks][64]
+    unsigned* bits; unsigned* offs;           // [total_blocks] bit count; bit offset from the image's un-stuffed scan
+    unsigned* istart;                         // [intervals] first un-stuffed byte of every restart interval
+    unsigned* ulen; unsigned* slen;           // [n_images] un-stuffed and stuffed bytes of the scan
+    unsigned* ffbase;                         // [total_chunks] 0xFF bytes of the image in front of the chunk
+    unsigned char* workspace;
+    int n_images;
+    unsigned total_blocks, total_chunks;
+};
+hipError_t launch_jpeg_enc_dct(const JpegEncLaunch& e, hipStream_t s);
+hipError_t launch_jpeg_enc_lengths(const JpegEncLaunch& e, hipStream_t s);
+hipError_t launch_jpeg_enc_offsets(const JpegEncLaunch& e, hipStream_t s);
+hipError_t launch_jpeg_enc_write(const JpegEncLaunch& e, hipStream_t s);
+hipError_t launch_jpeg_enc_stuff_scan(const JpegEncLaunch& e, hipStream_t s);
+hipError_t launch_jpeg_enc_stuff(const JpegEncLaunch& e, hipStream_t s);
 // ---- COCO key-point evaluation (eval_kernels.hip; COCOeval with iouType 'keypoints' and its default parameters): float64
 constexpr int kEvalK = 17;            // key-points of a person
 constexpr int kEvalMaxDets = 20;      // detections of an image that count (maxDets)

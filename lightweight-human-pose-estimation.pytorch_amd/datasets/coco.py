@@ -157,6 +157,22 @@ def imread(path_or_bytes, engine, entropy="host"):
         raise ValueError("%s: %s" % (name, re.sub(r"^image 0: ", "", str(e)))) from None
 
 
+def imwrite(path, img, engine, quality=95, subsampling="4:2:0"):
+    """``cv2.imwrite(path, img)`` for a ``.jpg`` / ``.jpeg`` path: ``img`` (a uint8 (H, W, 3) BGR array or cuda tensor) is
+    encoded by ``Engine.encode_jpeg_batch`` on the GPU and the file written.  The defaults are ``cv2.imwrite``'s for JPEG
+    (quality 95, 4:2:0).  The arithmetic is libjpeg's default compression path, pinned byte for byte against the files Pillow
+    (libjpeg-turbo) writes and NOT against cv2 itself, which is absent here.  Baseline files with Annex K's Huffman
+    tables only: no grey, progressive or optimised output.  Returns True, as ``cv2.imwrite`` does; any other extension is a
+    ValueError, an unwritable path an OSError."""
+    if os.path.splitext(str(path))[1].lower() not in (".jpg", ".jpeg", ".jpe"):
+        raise ValueError("%s: imwrite writes JPEG files (.jpg / .jpeg / .jpe) only" % (path,))
+    engine = getattr(engine, "engine", engine)
+    data = engine.encode_jpeg_batch([img], quality=quality, subsampling=subsampling)[0]
+    with open(path, "wb") as f:
+        f.write(data)
+    return True
+
+
 class _JpegFolder(object):
     """What the two datasets share: the folder, the engine, and the optional ``fallback(path) -> uint8 HxWx3 BGR`` for files
     the decoder refuses (``fallbacks`` counts its calls).  The package imports no decoder of its own accord.  ``entropy``:

@@ -929,6 +929,109 @@ class Engine(object):
             return ms
         return [buf[int(off[i]):int(off[i]) + h * w * 3].view(h, w, 3) for i, (h, w) in enumerate(sizes)]
 
+    # ------------------------------------------------------------------ JPEG files, written (cv2.imwrite's place)
+    @staticmethod
+    def _jpeg_encode_options(quality, subsampling, restart_interval):
+        if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+            raise ValueError("quality must be an integer from 1 to 100, not %r" % (quality,))
+        if subsampling not in _lib.JPEG_SUBSAMPLINGS:
+            raise ValueError("subsampling must be '4:4:4', '4:2:2' or '4:2:0', not %r" % (subsampling,))
+        if (isinstance(restart_interval, bool) or not isinstance(restart_interval, (int, np.integer))
+                or not 0 <= restart_interval <= 65535):
+            raise ValueError("restart_interval must be an integer from 0 to 65535 MCUs, not %r" % (restart_interval,))
+        return int(quality), _lib.JPEG_SUBSAMPLINGS[subsampling], int(restart_interval)
+
+    @staticmethod
+    def jpeg_encode_bound(height, width, subsampling="4:2:0", restart_interval=0):
+        """Bytes that hold the file ``encode_jpeg_batch`` writes of a height x width frame, whatever its pixels.  Needs no GPU."""
+        _, sub, ri = Engine._jpeg_encode_options(75, subsampling, restart_interval)
+        n = C.c_size_t()
+        check(lib().lwp_jpeg_encode_bound(int(height), int(width), sub, ri, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def debug_jpeg_encode_header(height, width, quality=75, subsampling="4:2:0", restart_interval=0):
+        """The header bytes alone (tests; no GPU): SOI up to and including SOS, in Pillow's layout."""
+        q, sub, ri = Engine._jpeg_encode_options(quality, subsampling, restart_interval)
+        out = np.empty(640, dtype=np.uint8)
+        n = C.c_size_t()
+        check(lib().lwp_debug_jpeg_encode_header(int(height), int(width), q, sub, ri, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def _jpeg_frames(self, frames):
+        """(N, frame pointers, MEM_HOST or MEM_DEVICE, heights, widths, the objects behind the pointers) of a list of (H, W, 3)
+        uint8 arrays or cuda tensors, or of one (N, H, W, 3) batch.  Cuda tensors are read in place; a mix of host and device
+        frames, another type or another shape is a ValueError."""
+        if hasattr(frames, "ndim") and not isinstance(frames, (list, tuple)):
+            if frames.ndim != 4:
+                raise ValueError("a batch of frames must be (N, H, W, 3), not %s" % (tuple(frames.shape),))
+            frames = [frames[i] for i in range(frames.shape[0])]
+        frames = list(frames)
+        if not frames:
+            return 0, None, MEM_HOST, None, None, []
+        keep, mems = [], set()
+        for i, f in enumerate(frames):
+            if not hasattr(f, "shape") or len(f.shape) != 3 or f.shape[2] != 3:
+                raise ValueError("frame %d must be (H, W, 3), not %s" % (i, tuple(getattr(f, "shape", ()))))
+            if not hasattr(f, "dtype") or not _is_dtype(f, np.uint8):
+                raise ValueError("frame %d must be uint8, not %s" % (i, f.dtype))
+            if f.shape[0] < 1 or f.shape[1] < 1 or f.shape[0] > 65535 or f.shape[1] > 65535:
+                raise ValueError("frame %d: %d x %d: height and width must be 1..65535" % (i, f.shape[0], f.shape[1]))
+            ptr, mem, a = self._ptr(f, np.uint8, "frames", convert=False)
+            keep.append((ptr, a))
+            mems.add(mem)
+        if len(mems) != 1:
+            raise ValueError("frames must all be host arrays or all be cuda tensors")
+        N = len(keep)
+        ptrs = (C.c_void_p * N)(*[p for p, _ in keep])
+        heights = (C.c_int * N)(*[int(f.shape[0]) for f in frames])
+        widths = (C.c_int * N)(*[int(f.shape[1]) for f in frames])
+        return N, ptrs, mems.pop(), heights, widths, keep
+
+    def encode_jpeg_batch(self, frames, quality=75, subsampling="4:2:0", restart_interval=0, time_iters=0):
+        """``cv2.imencode('.jpg', ..)`` of a batch of BGR frames in ONE device call: colour conversion, down-sampling, forward
+        DCT, quantisation, Huffman coding and byte stuffing all run on the GPU, and only the compressed bytes come back.
+        ``frames``: a list of (H, W, 3) uint8 arrays (uploaded in one copy) or cuda tensors (read in place), sizes mixed, or one
+        (N, H, W, 3) batch.  ``quality`` 1..100, ``subsampling`` '4:4:4' | '4:2:2' | '4:2:0', ``restart_interval`` in MCUs
+        (0: none); anything else is a ValueError.  Returns a list of ``bytes``: baseline JFIF files, byte for byte what Pillow
+        (libjpeg-turbo) writes of the same pixels with these settings; cv2 itself is not pinned.  With ``time_iters`` > 0 each
+        of the six stages is launched that many times back to back and the call returns their milliseconds."""
+        q, sub, ri = self._jpeg_encode_options(quality, subsampling, restart_interval)
+        N, ptrs, mem, heights, widths, keep = self._jpeg_frames(frames)
+        if N == 0:
+            return []
+        self._order()
+        if time_iters:
+            ms = (C.c_float * 6)()
+            self._call("lwp_time_jpeg_encode_batch", N, ptrs, mem, heights, widths, q, sub, ri, int(time_iters), ms)
+            return tuple(ms)
+        bounds = [self.jpeg_encode_bound(heights[i], widths[i], subsampling, ri) for i in range(N)]
+        off = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(bounds, out=off[1:])
+        buf = np.empty(int(off[-1]), dtype=np.uint8)     # untouched pages cost nothing: files take a fraction of the bound
+        outs = (C.c_void_p * N)(*[buf.ctypes.data + int(off[i]) for i in range(N)])
+        caps = (C.c_size_t * N)(*bounds)
+        lens = (C.c_size_t * N)()
+        self._call("lwp_jpeg_encode_batch", N, ptrs, mem, heights, widths, q, sub, ri, outs, caps, lens)
+        del keep
+        return [buf[int(off[i]):int(off[i]) + lens[i]].tobytes() for i in range(N)]
+
+    def debug_jpeg_encode_blocks(self, frames, quality=75, subsampling="4:2:0"):
+        """The first stage alone (tests): ``[(coefficients int16 (total_blocks, 64))]`` per frame in the decoder's layout
+        (natural order, plane order, MCU-padded grids), and the quantisation tables uint16 (4, 64) of the batch."""
+        q, sub, _ = self._jpeg_encode_options(quality, subsampling, 0)
+        N, ptrs, mem, heights, widths, keep = self._jpeg_frames(frames)
+        coefs = []
+        for i in range(N):
+            hd = self.jpeg_info(self.debug_jpeg_encode_header(heights[i], widths[i], q, subsampling))
+            coefs.append(np.zeros((hd["total_blocks"], 64), dtype=np.int16))
+        qt = np.zeros((4, 64), dtype=np.uint16)
+        if N:
+            self._order()
+            cp = (C.c_void_p * N)(*[c.ctypes.data for c in coefs])
+            self._call("lwp_debug_jpeg_encode_blocks", N, ptrs, mem, heights, widths, q, sub, cp, qt.ctypes.data)
+        return coefs, qt
+
     def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
         """train.py:92-97's per-stage sums: ``outs`` is the list net(x) returned (cuda tensors; an entry may be None),
         ``keypoint_maps`` / ``paf_maps`` the targets, ``mask`` one (N, h, w) cuda tensor broadcast over the channels.
