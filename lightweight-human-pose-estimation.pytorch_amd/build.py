@@ -11,8 +11,8 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "liblwpose_hip.so")
-SOURCES = ["net_graph.cpp", "net_kernels.hip", "net_kernels_bf16.hip", "net_kernels_tiled.hip", "post_kernels.hip", "train_kernels.hip", "bwd_kernels.hip", "optim_kernels.hip", "augment_kernels.hip", "crowd_kernels.hip", "eval_kernels.hip", "jpeg_host.cpp", "jpeg_kernels.hip", "jpeg_entropy_kernels.hip", "jpeg_encode_host.cpp", "jpeg_encode_kernels.hip", "capi.cpp"]
-HEADERS = ["lwp_internal.h", "lwp_owners.h", "h16.h", "jpeg_host.h", "jpeg_encode_host.h", os.path.join("..", "..", "include", "lwpose.h")]
+SOURCES = ["net_graph.cpp", "net_kernels.hip", "net_kernels_bf16.hip", "net_kernels_tiled.hip", "post_kernels.hip", "train_kernels.hip", "bwd_kernels.hip", "optim_kernels.hip", "augment_kernels.hip", "crowd_kernels.hip", "eval_kernels.hip", "jpeg_host.cpp", "jpeg_kernels.hip", "jpeg_entropy_kernels.hip", "jpeg_encode_host.cpp", "jpeg_encode_kernels.hip", "jpeg_batch.cpp", "capi.cpp"]
+HEADERS = ["lwp_internal.h", "lwp_owners.h", "h16.h", "jpeg_host.h", "jpeg_encode_host.h", "jpeg_batch.h", os.path.join("..", "..", "include", "lwpose.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-result", "-DNDEBUG"]
 # the post-processing must reproduce NumPy's separately-rounded float32/float64 arithmetic bit for bit:
 # no FMA contraction anywhere in that translation unit (the in-source pragma alone is not honoured for

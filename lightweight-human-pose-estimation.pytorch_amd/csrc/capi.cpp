@@ -12,8 +12,7 @@
 #include <thread>
 #include <vector>
 
-#include "jpeg_encode_host.h"
-#include "jpeg_host.h"
+#include "jpeg_batch.h"
 #include "lwp_internal.h"
 #include "lwp_owners.h"
 
@@ -148,16 +147,14 @@ struct lwp_context {
         std::vector<int64_t> gt_off;                 // host copy: the OKS offsets of an evaluation need G per image
         std::vector<char> added;                     // per image: rows were appended since the last reset
     } coco;
-    // JPEG decode (lwp_jpeg_decode_batch): the device workspace [upload: coefficients | tables | descriptors][component planes],
-    // the pinned staging of the upload and the event behind its last copy (the staging is not rewritten before it)
-    DevBuf d_jpeg;
-    PinBuf jpeg_stage; Event jpeg_ev; bool jpeg_copy_pending = false;
+    // A JPEG batch's device workspace [upload][device-only regions] (jpeg_batch.h lays both out), the pinned staging the upload
+    // is built in, and the event behind the staging's last copy: the staging is not rewritten before it (jpeg_stage_begin)
+    struct JpegMem { DevBuf dev; PinBuf stage; Event ev; bool copy_pending = false; };
+    JpegMem jpeg;                                    // lwp_jpeg_decode_batch, both entropy modes
+    // lwp_jpeg_encode_batch; the scans come back through the staging too.  Every encode call ends synchronised, so neither
+    // buffer outlives it in use and the event is never recorded
+    JpegMem jpeg_enc;
     int jpeg_entropy_mode = LWP_JPEG_ENTROPY_HOST, jpeg_subseq = kJpegSubseqDefault;     // lwp_set_jpeg_entropy
-    // JPEG encode (lwp_jpeg_encode_batch): the device workspace [upload: records | tables | host frames][coefficients | bit
-    // counts | offsets | interval starts | lengths | un-stuffed scans | chunk counts | stuffed scans] and the pinned staging the
-    // upload leaves through and the scans come back through; every call ends synchronised, so neither outlives it in use
-    DevBuf d_jpeg_enc;
-    PinBuf jpeg_enc_stage;
     bool async_pending = false;                      // an lwp_infer_poses_async whose results were not fetched yet
     int tail_first_id = 0;                 // first id of a lane that is created later (lwp_reset_tracking(-1, id))
     int stage_tail_N = 0;                  // frames whose pose rows h_stage holds (0: the last fetch ran without the tail)
@@ -2515,139 +2512,6 @@ extern "C" int lwp_debug_jpeg_blocks(const unsigned char* data, size_t len, int1
     return LWP_OK;
 }
 
-// the plane and image records of a batch whose headers are hd (a file of no components takes none); plane_base: where the
-// component planes start in the workspace
-static void jpeg_fill_records(const std::vector<lwp_jpeg_header>& hd, int N, unsigned char* const* out, size_t plane_base, JpegPlane* planes,
-                              unsigned* pstart, JpegImage* images, unsigned* istart, uint64_t* blocks, uint64_t* units) {
-    uint64_t b0 = 0, u0 = 0;
-    int p = 0;
-    for (int i = 0; i < N; ++i) {
-        const lwp_jpeg_header& f = hd[i];
-        JpegImage& im = images[i];
-        memset(&im, 0, sizeof im);
-        im.unit0 = (unsigned)u0; istart[i] = (unsigned)u0;
-        im.width = f.width; im.height = f.height;
-        im.mode = f.components == 1 ? 0 : f.h_samp[0] == 1 ? 1 : f.v_samp[0] == 1 ? 2 : 3;
-        im.chroma_w = f.components == 1 ? 0 : (f.width + f.h_samp[0] - 1) / f.h_samp[0];
-        im.chroma_h = f.components == 1 ? 0 : (f.height + f.v_samp[0] - 1) / f.v_samp[0];
-        im.out = out ? out[i] : nullptr;
-        for (int c = 0; c < f.components; ++c) {
-            JpegPlane& pl = planes[p];
-            pl.block0 = (unsigned)b0; pstart[p] = (unsigned)b0;
-            pl.blocks_w = f.blocks_w[c];
-            pl.qt = (unsigned)(((size_t)i * kJpegQuantSlots + (size_t)f.quant_table[c]) * 64);
-            pl.pad_ = 0;
-            pl.plane = (long long)(plane_base + b0 * 64);
-            im.plane[c] = pl.plane; im.stride[c] = f.blocks_w[c] * 8;
-            b0 += (uint64_t)f.blocks_w[c] * f.blocks_h[c];
-            ++p;
-        }
-        u0 += (uint64_t)f.height * (uint64_t)((f.width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
-    }
-    pstart[p] = (unsigned)b0; istart[N] = (unsigned)u0;
-    *blocks = b0; *units = u0;
-}
-
-// checks, the host half of every file and the batch's one upload [coefficients | tables | plane records | plane starts | image
-// records | image starts]; the component planes lie behind it in the same allocation.  Nothing is enqueued before every file
-// has been decoded: a refusal leaves the outputs untouched.
-static int jpeg_prepare(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out, JpegLaunch* launch) {
-    char msg[400], why[256];
-    if (!data || !len || !out) return fail(h, LWP_ERR_ARG, "data / len / out is null");
-    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
-    std::vector<lwp_jpeg_header> hd((size_t)N);
-    uint64_t blocks = 0, units = 0;
-    int n_planes = 0;
-    for (int i = 0; i < N; ++i) {
-        if (!data[i] || !out[i]) { snprintf(msg, sizeof msg, "image %d: data / out is null", i); return fail(h, LWP_ERR_ARG, msg); }
-        why[0] = 0;
-        if (jpeg_parse_header(data[i], len[i], &hd[i], why, sizeof why) != JPEG_OK) {
-            snprintf(msg, sizeof msg, "image %d: %s", i, why);
-            return fail(h, LWP_ERR_ARG, msg);
-        }
-        blocks += (uint64_t)hd[i].total_blocks;
-        units += (uint64_t)hd[i].height * (uint64_t)((hd[i].width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
-        n_planes += hd[i].components;
-    }
-    if (blocks > 0x7fffffffu || units > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^31 or more blocks or pixel groups: decode it in parts");
-    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_coef = 0, o_qt = align16((size_t)blocks * 128), o_planes = o_qt + (size_t)N * kJpegQuantSlots * 128;
-    const size_t o_pstart = align16(o_planes + (size_t)n_planes * sizeof(JpegPlane)), o_images = align16(o_pstart + ((size_t)n_planes + 1) * 4);
-    const size_t o_istart = align16(o_images + (size_t)N * sizeof(JpegImage));
-    const size_t upload = (o_istart + ((size_t)N + 1) * 4 + 255) & ~(size_t)255;
-    const size_t total = upload + (size_t)blocks * 64;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->jpeg_copy_pending) {                        // the copy of the call before may still read the staging
-        HIP_TRY(h, hipEventSynchronize(h->jpeg_ev));
-        h->jpeg_copy_pending = false;
-    }
-    HIP_TRY(h, h->jpeg_stage.ensure(upload));
-    unsigned char* host = h->jpeg_stage.as<unsigned char>();
-    JpegPlane* planes = reinterpret_cast<JpegPlane*>(host + o_planes);
-    unsigned* pstart = reinterpret_cast<unsigned*>(host + o_pstart);
-    JpegImage* images = reinterpret_cast<JpegImage*>(host + o_images);
-    unsigned* istart = reinterpret_cast<unsigned*>(host + o_istart);
-    // the entropy decode of the files: independent of each other, each into its own part of the staging, so a large batch is
-    // shared among up to kJpegHostThreads threads (file i goes to thread i mod T; the result does not depend on T).  The
-    // first refused file in index order is the one reported.
-    std::vector<uint64_t> first_block((size_t)N + 1, 0);
-    size_t in_bytes = 0;
-    for (int i = 0; i < N; ++i) { first_block[i + 1] = first_block[i] + (uint64_t)hd[i].total_blocks; in_bytes += len[i]; }
-    std::vector<int> bad((size_t)N, 0);
-    std::vector<std::string> bad_why((size_t)N);
-    auto decode_file = [&](int i) {
-        lwp_jpeg_header now;
-        char w[256] = {0};
-        const int rc = jpeg_decode_blocks(data[i], len[i], &now, reinterpret_cast<int16_t*>(host + o_coef) + first_block[i] * 64,
-                                          (size_t)hd[i].total_blocks * 64, reinterpret_cast<uint16_t*>(host + o_qt) + (size_t)i * kJpegQuantSlots * 64,
-                                          w, sizeof w);
-        if (rc != JPEG_OK || now.total_blocks != hd[i].total_blocks) { bad[i] = 1; bad_why[i] = rc != JPEG_OK ? w : "the file changed during the call"; }
-    };
-    int T = std::min({kJpegHostThreads, N, (int)std::max(1u, std::thread::hardware_concurrency())});
-    if (in_bytes < kJpegThreadedFromBytes) T = 1;
-    if (T > 1) {
-        std::vector<std::thread> pool;
-        int started = 1;                               // this thread is the first
-        try {
-            for (; started < T; ++started) pool.emplace_back([&, t = started]() { for (int i = t; i < N; i += T) decode_file(i); });
-        } catch (const std::system_error&) {}          // no more threads to be had: this one takes the rest below
-        for (int i = 0; i < N; i += T) decode_file(i);
-        for (std::thread& th : pool) th.join();
-        for (int t = started; t < T; ++t)
-            for (int i = t; i < N; i += T) decode_file(i);
-    } else {
-        for (int i = 0; i < N && !(i && bad[i - 1]); ++i) decode_file(i);
-    }
-    for (int i = 0; i < N; ++i)
-        if (bad[i]) {
-            snprintf(msg, sizeof msg, "image %d: %s", i, bad_why[i].c_str());
-            return fail(h, LWP_ERR_ARG, msg);
-        }
-    uint64_t b0 = 0, u0 = 0;
-    jpeg_fill_records(hd, N, out, upload, planes, pstart, images, istart, &b0, &u0);
-    int rc = order_in(h);
-    if (rc) return rc;
-    if (h->d_jpeg.size() < total) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
-        HIP_TRY(h, h->d_jpeg.ensure(total));
-    }
-    unsigned char* dev = h->d_jpeg.as<unsigned char>();
-    HIP_TRY(h, h->jpeg_ev.ensure(hipEventDisableTiming));
-    HIP_TRY(h, hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->jpeg_ev, h->stream));
-    h->jpeg_copy_pending = true;
-    JpegLaunch j{};
-    j.coef = reinterpret_cast<const int16_t*>(dev + o_coef); j.qtables = reinterpret_cast<const uint16_t*>(dev + o_qt);
-    j.planes = reinterpret_cast<const JpegPlane*>(dev + o_planes); j.plane_block0 = reinterpret_cast<const unsigned*>(dev + o_pstart);
-    j.images = reinterpret_cast<const JpegImage*>(dev + o_images); j.image_unit0 = reinterpret_cast<const unsigned*>(dev + o_istart);
-    j.workspace = dev;
-    j.n_planes = n_planes; j.n_images = N;
-    j.total_blocks = (unsigned)b0; j.total_units = (unsigned)u0;
-    *launch = j;
-    return LWP_OK;
-}
-
 // ---- device entropy mode (lwp_set_jpeg_entropy; jpeg_entropy_kernels.hip)
 static bool jpeg_subseq_ok(int v) { return v >= 4 && v <= 1024 && v % 4 == 0; }
 
@@ -2678,7 +2542,12 @@ extern "C" int lwp_debug_jpeg_scan(const unsigned char* data, size_t len, unsign
     return LWP_OK;
 }
 
-// files shared among up to kJpegHostThreads threads, as the host entropy decode shares them
+// ---- batches.  The checks of the files, the layout of the workspace and the records are jpeg_batch.cpp's; here is what needs
+// the handle.  A refusal of jpeg_batch.cpp as the call's error:
+static int jpeg_fail(lwp_handle h, int rc, const char* msg) { return fail(h, rc == JPEG_CAPACITY ? LWP_ERR_CAPACITY : LWP_ERR_ARG, msg); }
+
+// files shared among up to kJpegHostThreads threads (file i goes to thread i mod T; the result does not depend on T): the
+// files are independent of each other, each works into its own part of the staging
 template <class F>
 static void jpeg_share_files(int N, size_t in_bytes, F per_file) {
     int T = std::min({kJpegHostThreads, N, (int)std::max(1u, std::thread::hardware_concurrency())});
@@ -2694,18 +2563,122 @@ static void jpeg_share_files(int N, size_t in_bytes, F per_file) {
         for (int i = t; i < N; i += T) per_file(i);
 }
 
+// begins a staged batch: `bytes` of pinned staging, which the copy of the call before may still read
+static int jpeg_stage_begin(lwp_handle h, lwp_context::JpegMem& m, size_t bytes, unsigned char** host) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (m.copy_pending) {
+        HIP_TRY(h, hipEventSynchronize(m.ev));
+        m.copy_pending = false;
+    }
+    HIP_TRY(h, m.stage.ensure(bytes));
+    *host = m.stage.as<unsigned char>();
+    return LWP_OK;
+}
+
+// sends it: a workspace of `total` bytes at *dev, the staging's first `upload` bytes into its front on the handle's stream and,
+// with `event`, the event behind the copy (a call that ends synchronised needs none).  finish(*dev) runs in front of the copy:
+// the records that hold device addresses
+template <class F>
+static int jpeg_stage_send(lwp_handle h, lwp_context::JpegMem& m, size_t upload, size_t total, bool event, unsigned char** dev, F finish) {
+    int rc = order_in(h);
+    if (rc) return rc;
+    if (m.dev.size() < total) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
+        HIP_TRY(h, m.dev.ensure(total));
+    }
+    *dev = m.dev.as<unsigned char>();
+    finish(*dev);
+    if (event) HIP_TRY(h, m.ev.ensure(hipEventDisableTiming));
+    HIP_TRY(h, hipMemcpyAsync(*dev, m.stage.as<unsigned char>(), upload, hipMemcpyHostToDevice, h->stream));
+    if (event) {
+        HIP_TRY(h, hipEventRecord(m.ev, h->stream));
+        m.copy_pending = true;
+    }
+    return LWP_OK;
+}
+
+static JpegLaunch jpeg_launch(unsigned char* dev, const JpegHeaders& H, const JpegDecodePlan& P) {
+    JpegLaunch j{};
+    j.coef = reinterpret_cast<const int16_t*>(dev + P.coef); j.qtables = reinterpret_cast<const uint16_t*>(dev + P.qt);
+    j.planes = reinterpret_cast<const JpegPlane*>(dev + P.planes); j.plane_block0 = reinterpret_cast<const unsigned*>(dev + P.pstart);
+    j.images = reinterpret_cast<const JpegImage*>(dev + P.images); j.image_unit0 = reinterpret_cast<const unsigned*>(dev + P.istart);
+    j.workspace = dev;
+    j.n_planes = H.n_planes; j.n_images = (int)H.hd.size();
+    j.total_blocks = (unsigned)H.blocks; j.total_units = (unsigned)H.units;
+    return j;
+}
+
+static JpegEntropyLaunch jpeg_entropy_launch(unsigned char* dev, const JpegHeaders& H, const JpegEntropyPlan& P, int subseq) {
+    JpegEntropyLaunch e{};
+    e.words = reinterpret_cast<const unsigned*>(dev + P.bytes); e.n_words = (unsigned)((P.tab - P.bytes) / 4);
+    e.tables = reinterpret_cast<const JpegHuffFlat*>(dev + P.tab);
+    e.files = reinterpret_cast<const JpegEntFile*>(dev + P.files); e.file_wg0 = reinterpret_cast<const unsigned*>(dev + P.fwg);
+    e.segs = reinterpret_cast<const JpegEntSeg*>(dev + P.segs); e.seg_sub0 = reinterpret_cast<const unsigned*>(dev + P.ssub);
+    e.rec = reinterpret_cast<uint2*>(dev + P.rec); e.subpos = reinterpret_cast<unsigned*>(dev + P.subpos);
+    e.wg_entry = reinterpret_cast<uint2*>(dev + P.wg_entry); e.wg_dirty = reinterpret_cast<unsigned*>(dev + P.wg_dirty);
+    e.coef = reinterpret_cast<int16_t*>(dev + P.d.coef); e.status = reinterpret_cast<int*>(dev + P.status);
+    e.n_files = (int)H.hd.size(); e.n_segs = P.n_segs; e.n_subs = P.n_subs; e.n_wgs = P.n_wgs;
+    e.subseq_bytes = subseq;
+    return e;
+}
+
+// the host decoder's verdict on one file, decoded only for that: its message words every refusal, whichever mode met it
+static int jpeg_host_verdict(const unsigned char* data, size_t len, const lwp_jpeg_header& hd, char* why, size_t why_cap) {
+    std::vector<int16_t> coef((size_t)hd.total_blocks * 64);
+    uint16_t qt[kJpegQuantSlots * 64];
+    lwp_jpeg_header now;
+    why[0] = 0;
+    return jpeg_decode_blocks(data, len, &now, coef.data(), coef.size(), qt, why, why_cap);
+}
+
+// host entropy mode: checks, the host half of every file and the batch's one upload.  Nothing is enqueued before every file
+// has been decoded: a refusal leaves the outputs untouched.
+static int jpeg_prepare(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out, JpegLaunch* launch) {
+    char msg[kJpegMsg];
+    if (!data || !len || !out) return fail(h, LWP_ERR_ARG, "data / len / out is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    JpegHeaders H;
+    int rc = jpeg_batch_headers(N, data, len, out, false, &H, msg);
+    if (rc) return jpeg_fail(h, rc, msg);
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    JpegDecodePlan P;
+    jpeg_decode_plan(H, &P);
+    unsigned char *host = nullptr, *dev = nullptr;
+    rc = jpeg_stage_begin(h, h->jpeg, P.upload, &host);
+    if (rc) return rc;
+    // the entropy decode of the files.  The first refused file in index order is the one reported.
+    std::vector<uint64_t> first_block((size_t)N + 1, 0);
+    for (int i = 0; i < N; ++i) first_block[i + 1] = first_block[i] + (uint64_t)H.hd[i].total_blocks;
+    std::vector<std::string> bad((size_t)N);
+    jpeg_share_files(N, H.in_bytes, [&](int i) {
+        lwp_jpeg_header now;
+        char w[256] = {0};
+        const int r = jpeg_decode_blocks(data[i], len[i], &now, reinterpret_cast<int16_t*>(host + P.coef) + first_block[i] * 64,
+                                         (size_t)H.hd[i].total_blocks * 64, reinterpret_cast<uint16_t*>(host + P.qt) + (size_t)i * kJpegQuantSlots * 64,
+                                         w, sizeof w);
+        if (r != JPEG_OK || now.total_blocks != H.hd[i].total_blocks) { H.verdict[i] = JPEG_REFUSED; bad[i] = r != JPEG_OK ? w : "the file changed during the call"; }
+    });
+    for (int i = 0; i < N; ++i)
+        if (H.verdict[i]) {
+            snprintf(msg, sizeof msg, "image %d: %s", i, bad[i].c_str());
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+    jpeg_decode_fill(H, P, out, host);
+    rc = jpeg_stage_send(h, h->jpeg, P.upload, P.total, true, &dev, [](unsigned char*) {});
+    if (rc) return rc;
+    *launch = jpeg_launch(dev, H, P);
+    return LWP_OK;
+}
+
 // the call's error for file i, which the pre-pass (by_kernels false) or the kernels refused: the host decoder's message, so
 // both modes word a refusal alike; a file the host accepts is an internal error, never a silent repair
 static int jpeg_device_refusal(lwp_handle h, int i, const unsigned char* data, size_t len, const lwp_jpeg_header& hd, int verdict, bool by_kernels) {
-    char msg[400], why[256] = {0};
+    char msg[kJpegMsg], why[256];
     if (verdict == JPEG_CAPACITY) {
         snprintf(msg, sizeof msg, "image %d: jpeg: the scan's un-stuffed length is 2^28 bytes or more, which the device entropy mode does not take: decode it in host mode", i);
         return fail(h, LWP_ERR_CAPACITY, msg);
     }
-    std::vector<int16_t> coef((size_t)hd.total_blocks * 64);
-    uint16_t qt[kJpegQuantSlots * 64];
-    lwp_jpeg_header now;
-    if (jpeg_decode_blocks(data, len, &now, coef.data(), coef.size(), qt, why, sizeof why) != JPEG_OK) {
+    if (jpeg_host_verdict(data, len, hd, why, sizeof why) != JPEG_OK) {
         snprintf(msg, sizeof msg, "image %d: %s", i, why);
         return fail(h, LWP_ERR_ARG, msg);
     }
@@ -2714,8 +2687,7 @@ static int jpeg_device_refusal(lwp_handle h, int i, const unsigned char* data, s
 }
 
 struct JpegDeviceBatch {
-    std::vector<lwp_jpeg_header> hd;
-    std::vector<int> verdict;                          // per file: JPEG_OK, or why it takes no part (tolerant calls only)
+    JpegHeaders H;                                     // verdict: per file JPEG_OK, or why it takes no part (tolerant calls only)
     JpegLaunch j{};
     JpegEntropyLaunch e{};
     const uint16_t* qt_host = nullptr;                 // the quantisation tables in the staging
@@ -2723,172 +2695,75 @@ struct JpegDeviceBatch {
     size_t memset_bytes = 0;                           // coefficients and status words, from e.coef on
 };
 
-// Device mode's front half: headers, the pre-pass on the host threads, the one upload [un-stuffed scans | Huffman tables |
-// quantisation tables | records].  `tolerant` (lwp_debug_jpeg_entropy_batch): a refused file takes no part instead of failing
-// the call.  Device layout behind the upload: [coefficients | status][subsequence records][positions][workgroup entries][planes].
+// Device mode's front half: headers, the pre-pass on the host threads, the one upload.  `tolerant`
+// (lwp_debug_jpeg_entropy_batch): a refused file takes no part instead of failing the call.
 static int jpeg_device_prepare(lwp_handle h, int N, const unsigned char* const* data, const size_t* len, unsigned char* const* out,
                                int subseq, bool tolerant, JpegDeviceBatch* B) {
-    char msg[400], why[256];
+    char msg[kJpegMsg], why[256];
     if (!data || !len) return fail(h, LWP_ERR_ARG, "data / len is null");        // out: null where the call writes no pixels
     if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
-    std::vector<lwp_jpeg_header>& hd = B->hd;
-    hd.assign((size_t)N, lwp_jpeg_header{});
-    B->verdict.assign((size_t)N, JPEG_OK);
-    uint64_t blocks = 0, units = 0, n_segs_cap = 0, byte_cap = 0;
-    int n_planes = 0;
-    size_t in_bytes = 0;
-    std::vector<uint64_t> seg_at((size_t)N + 1, 0), byte_at((size_t)N + 1, 0);
-    for (int i = 0; i < N; ++i) {
-        if (!data[i] || (out && !out[i])) { snprintf(msg, sizeof msg, "image %d: data / out is null", i); return fail(h, LWP_ERR_ARG, msg); }
-        why[0] = 0;
-        if (jpeg_parse_header(data[i], len[i], &hd[i], why, sizeof why) != JPEG_OK) {
-            if (!tolerant) { snprintf(msg, sizeof msg, "image %d: %s", i, why); return fail(h, LWP_ERR_ARG, msg); }
-            hd[i] = lwp_jpeg_header{};
-            hd[i].h_samp[0] = hd[i].v_samp[0] = 1;
-            B->verdict[i] = JPEG_REFUSED;
-        }
-        blocks += (uint64_t)hd[i].total_blocks;
-        units += (uint64_t)hd[i].height * (uint64_t)((hd[i].width + kJpegPixelsPerThread - 1) / kJpegPixelsPerThread);
-        n_planes += hd[i].components;
-        seg_at[i + 1] = seg_at[i] + (B->verdict[i] ? 0 : (uint64_t)jpeg_expected_segments(hd[i]));
-        byte_at[i + 1] = byte_at[i] + (B->verdict[i] ? 0 : (((uint64_t)len[i] + 3) & ~(uint64_t)3) + 8);
-        in_bytes += len[i];
-    }
-    n_segs_cap = seg_at[N]; byte_cap = byte_at[N];
-    if (blocks > 0x7fffffffu || units > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^31 or more blocks or pixel groups: decode it in parts");
-    if (byte_cap > 0xfffffff0u || n_segs_cap > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^32 or more bytes or 2^31 or more restart intervals: decode it in parts");
+    JpegHeaders& H = B->H;
+    JpegEntropyPlan P;
+    int rc = jpeg_batch_headers(N, data, len, out, tolerant, &H, msg);
+    if (!rc) rc = jpeg_entropy_plan(H, len, &P, msg);
+    if (rc) return jpeg_fail(h, rc, msg);
     if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_bytes = 0, o_tab = align16((size_t)byte_cap + 8), o_qt = o_tab + (size_t)N * kJpegHuffPerFile * sizeof(JpegHuffFlat);
-    const size_t o_files = o_qt + (size_t)N * kJpegQuantSlots * 128, o_fwg = align16(o_files + (size_t)N * sizeof(JpegEntFile));
-    const size_t o_segs = align16(o_fwg + ((size_t)N + 1) * 4), o_ssub = align16(o_segs + (size_t)n_segs_cap * sizeof(JpegEntSeg));
-    const size_t o_planes = align16(o_ssub + ((size_t)n_segs_cap + 1) * 4);
-    const size_t o_pstart = align16(o_planes + (size_t)n_planes * sizeof(JpegPlane)), o_images = align16(o_pstart + ((size_t)n_planes + 1) * 4);
-    const size_t o_istart = align16(o_images + (size_t)N * sizeof(JpegImage));
-    const size_t upload = (o_istart + ((size_t)N + 1) * 4 + 255) & ~(size_t)255;
-    const size_t stage_bytes = upload + align16(((size_t)N + 2) * 4);     // the status words come back behind the upload
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->jpeg_copy_pending) {                        // the copy of the call before may still read the staging
-        HIP_TRY(h, hipEventSynchronize(h->jpeg_ev));
-        h->jpeg_copy_pending = false;
-    }
-    HIP_TRY(h, h->jpeg_stage.ensure(stage_bytes));
-    unsigned char* host = h->jpeg_stage.as<unsigned char>();
-    JpegHuffFlat* tables = reinterpret_cast<JpegHuffFlat*>(host + o_tab);
-    uint16_t* qt = reinterpret_cast<uint16_t*>(host + o_qt);
-    std::vector<JpegScanSeg> scan((size_t)n_segs_cap + 1);
+    unsigned char *host = nullptr, *dev = nullptr;
+    rc = jpeg_stage_begin(h, h->jpeg, P.stage_bytes, &host);
+    if (rc) return rc;
+    JpegHuffFlat* tables = reinterpret_cast<JpegHuffFlat*>(host + P.tab);
+    uint16_t* qt = reinterpret_cast<uint16_t*>(host + P.d.qt);
+    std::vector<JpegScanSeg> scan((size_t)P.seg_at[N] + 1);
     std::vector<size_t> n_scan((size_t)N, 0);
-    jpeg_share_files(N, in_bytes, [&](int i) {
-        if (B->verdict[i]) {
+    jpeg_share_files(N, H.in_bytes, [&](int i) {
+        if (H.verdict[i]) {
             memset(tables + (size_t)i * kJpegHuffPerFile, 0, kJpegHuffPerFile * sizeof(JpegHuffFlat));
             memset(qt + (size_t)i * kJpegQuantSlots * 64, 0, kJpegQuantSlots * 128);
             return;
         }
         size_t nb = 0;
-        B->verdict[i] = jpeg_scan_segments(data[i], len[i], &hd[i], host + o_bytes + byte_at[i], (size_t)(byte_at[i + 1] - byte_at[i]), &nb,
-                                           scan.data() + seg_at[i], (size_t)(seg_at[i + 1] - seg_at[i]), &n_scan[i],
-                                           tables + (size_t)i * kJpegHuffPerFile, qt + (size_t)i * kJpegQuantSlots * 64);
+        H.verdict[i] = jpeg_scan_segments(data[i], len[i], &H.hd[i], host + P.bytes + P.byte_at[i], (size_t)(P.byte_at[i + 1] - P.byte_at[i]), &nb,
+                                          scan.data() + P.seg_at[i], (size_t)(P.seg_at[i + 1] - P.seg_at[i]), &n_scan[i],
+                                          tables + (size_t)i * kJpegHuffPerFile, qt + (size_t)i * kJpegQuantSlots * 64);
     });
-    memset(host + o_bytes + byte_cap, 0, o_tab - byte_cap);
+    memset(host + P.bytes + P.byte_at[N], 0, P.tab - P.byte_at[N]);
     if (!tolerant)
         for (int i = 0; i < N; ++i)
-            if (B->verdict[i]) {
+            if (H.verdict[i]) {
                 // the call names the LOWEST refused file, and a file in front of this one may be one the kernels would refuse:
                 // nothing has been enqueued yet, so the host decoder gives their verdicts (this path is a failing call's only)
-                for (int j = 0; j < i; ++j) {
-                    std::vector<int16_t> coef((size_t)hd[j].total_blocks * 64);
-                    uint16_t q[kJpegQuantSlots * 64];
-                    lwp_jpeg_header now;
-                    why[0] = 0;
-                    if (jpeg_decode_blocks(data[j], len[j], &now, coef.data(), coef.size(), q, why, sizeof why) != JPEG_OK) {
+                for (int j = 0; j < i; ++j)
+                    if (jpeg_host_verdict(data[j], len[j], H.hd[j], why, sizeof why) != JPEG_OK) {
                         snprintf(msg, sizeof msg, "image %d: %s", j, why);
                         return fail(h, LWP_ERR_ARG, msg);
                     }
-                }
-                return jpeg_device_refusal(h, i, data[i], len[i], hd[i], B->verdict[i], false);
+                return jpeg_device_refusal(h, i, data[i], len[i], H.hd[i], H.verdict[i], false);
             }
-    // the records: files, segments (of the files that take part), their first subsequences and workgroups
-    JpegEntFile* files = reinterpret_cast<JpegEntFile*>(host + o_files);
-    unsigned* fwg = reinterpret_cast<unsigned*>(host + o_fwg);
-    JpegEntSeg* segs = reinterpret_cast<JpegEntSeg*>(host + o_segs);
-    unsigned* ssub = reinterpret_cast<unsigned*>(host + o_ssub);
-    uint64_t n_subs = 0, n_wgs = 0, b0 = 0;
-    size_t n_segs = 0;
-    for (int i = 0; i < N; ++i) {
-        const lwp_jpeg_header& f = hd[i];
-        JpegEntFile& ef = files[i];
-        memset(&ef, 0, sizeof ef);
-        fwg[i] = (unsigned)n_wgs;
-        ef.seg0 = (unsigned)n_segs; ef.sub0 = (unsigned)n_subs; ef.wg0 = (unsigned)n_wgs;
-        ef.block0 = (unsigned)b0; ef.total_blocks = (unsigned)f.total_blocks;
-        ef.components = f.components; ef.mcus_x = std::max(f.mcus_x, 1);
-        ef.h0 = std::max(f.h_samp[0], 1); ef.v0 = std::max(f.v_samp[0], 1);
-        ef.blocks_per_mcu = f.components == 3 ? ef.h0 * ef.v0 + 2 : 1;
-        unsigned pb = 0;
-        for (int c = 0; c < f.components; ++c) { ef.plane_block[c] = pb; ef.blocks_w[c] = f.blocks_w[c]; pb += (unsigned)(f.blocks_w[c] * f.blocks_h[c]); }
-        b0 += (uint64_t)f.total_blocks;
-        if (B->verdict[i]) continue;
-        for (size_t k = 0; k < n_scan[i]; ++k) {
-            const JpegScanSeg& sc = scan[seg_at[i] + k];
-            JpegEntSeg& sg = segs[n_segs];
-            sg.byte0 = (unsigned)(byte_at[i] + sc.byte0); sg.n_bytes = sc.n_bytes;
-            sg.first_block = sc.first_mcu * (unsigned)ef.blocks_per_mcu; sg.n_blocks = sc.n_mcus * (unsigned)ef.blocks_per_mcu;
-            sg.sub0 = (unsigned)n_subs; sg.file = (unsigned)i;
-            ssub[n_segs++] = (unsigned)n_subs;
-            n_subs += std::max<uint64_t>(1, ((uint64_t)sc.n_bytes + (uint64_t)subseq - 1) / (uint64_t)subseq);
-            if (n_subs > 0x7fffffffu) return fail(h, LWP_ERR_CAPACITY, "the batch has 2^31 or more subsequences: decode it in parts or with larger subsequences");
-        }
-        ef.n_segs = (unsigned)(n_segs - ef.seg0); ef.n_subs = (unsigned)(n_subs - ef.sub0);
-        ef.n_wgs = (ef.n_subs + kJpegEntropyGroup - 1) / kJpegEntropyGroup;
-        n_wgs += ef.n_wgs;
-    }
-    fwg[N] = (unsigned)n_wgs; ssub[n_segs] = (unsigned)n_subs;
-    auto align256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t d_coef = upload, coef_status = align256((size_t)blocks * 128 + ((size_t)N + 2) * 4);
-    const size_t d_rec = d_coef + coef_status, d_subpos = d_rec + align256((size_t)n_subs * 8), d_wge = d_subpos + align256((size_t)n_subs * 4);
-    const size_t d_wgd = d_wge + align256((size_t)n_wgs * 8), d_planes = d_wgd + align256((size_t)n_wgs * 4);
-    const size_t total = d_planes + (size_t)blocks * 64;
-    uint64_t fb = 0, fu = 0;
-    jpeg_fill_records(hd, N, out, d_planes, reinterpret_cast<JpegPlane*>(host + o_planes), reinterpret_cast<unsigned*>(host + o_pstart),
-                      reinterpret_cast<JpegImage*>(host + o_images), reinterpret_cast<unsigned*>(host + o_istart), &fb, &fu);
-    int rc = order_in(h);
+    rc = jpeg_entropy_fill(H, &P, scan.data(), n_scan.data(), subseq, host, msg);
+    if (rc) return jpeg_fail(h, rc, msg);
+    jpeg_entropy_place(H, &P);
+    jpeg_decode_fill(H, P.d, out, host);
+    rc = jpeg_stage_send(h, h->jpeg, P.d.upload, P.d.total, true, &dev, [](unsigned char*) {});
     if (rc) return rc;
-    if (h->d_jpeg.size() < total) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
-        HIP_TRY(h, h->d_jpeg.ensure(total));
-    }
-    unsigned char* dev = h->d_jpeg.as<unsigned char>();
-    HIP_TRY(h, h->jpeg_ev.ensure(hipEventDisableTiming));
-    HIP_TRY(h, hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->jpeg_ev, h->stream));
-    h->jpeg_copy_pending = true;
-    JpegLaunch& j = B->j;
-    j.coef = reinterpret_cast<const int16_t*>(dev + d_coef); j.qtables = reinterpret_cast<const uint16_t*>(dev + o_qt);
-    j.planes = reinterpret_cast<const JpegPlane*>(dev + o_planes); j.plane_block0 = reinterpret_cast<const unsigned*>(dev + o_pstart);
-    j.images = reinterpret_cast<const JpegImage*>(dev + o_images); j.image_unit0 = reinterpret_cast<const unsigned*>(dev + o_istart);
-    j.workspace = dev;
-    j.n_planes = n_planes; j.n_images = N;
-    j.total_blocks = (unsigned)fb; j.total_units = (unsigned)fu;
-    JpegEntropyLaunch& e = B->e;
-    e.words = reinterpret_cast<const unsigned*>(dev + o_bytes); e.n_words = (unsigned)(o_tab / 4);
-    e.tables = reinterpret_cast<const JpegHuffFlat*>(dev + o_tab);
-    e.files = reinterpret_cast<const JpegEntFile*>(dev + o_files); e.file_wg0 = reinterpret_cast<const unsigned*>(dev + o_fwg);
-    e.segs = reinterpret_cast<const JpegEntSeg*>(dev + o_segs); e.seg_sub0 = reinterpret_cast<const unsigned*>(dev + o_ssub);
-    e.rec = reinterpret_cast<uint2*>(dev + d_rec); e.subpos = reinterpret_cast<unsigned*>(dev + d_subpos);
-    e.wg_entry = reinterpret_cast<uint2*>(dev + d_wge); e.wg_dirty = reinterpret_cast<unsigned*>(dev + d_wgd);
-    e.coef = reinterpret_cast<int16_t*>(dev + d_coef); e.status = reinterpret_cast<int*>(dev + d_coef + (size_t)blocks * 128);
-    e.n_files = N; e.n_segs = (unsigned)n_segs; e.n_subs = (unsigned)n_subs; e.n_wgs = (unsigned)n_wgs;
-    e.subseq_bytes = subseq;
+    B->j = jpeg_launch(dev, H, P.d);
+    B->e = jpeg_entropy_launch(dev, H, P, subseq);
     B->qt_host = qt;
-    B->status_host = reinterpret_cast<int*>(host + upload);
-    B->memset_bytes = (size_t)blocks * 128 + ((size_t)N + 2) * 4;
+    B->status_host = reinterpret_cast<int*>(host + P.d.upload);
+    B->memset_bytes = P.status + ((size_t)N + 2) * 4 - P.d.coef;
     return LWP_OK;
 }
 
-// the memset, the four entropy kernels, the status words back to the host, and the wait for them
-static int jpeg_device_entropy(lwp_handle h, JpegDeviceBatch& B) {
+// the memset and the four entropy kernels
+static int jpeg_entropy_enqueue(lwp_handle h, const JpegDeviceBatch& B) {
     HIP_TRY(h, hipMemsetAsync(B.e.coef, 0, B.memset_bytes, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_entropy(B.e, h->stream));
+    return LWP_OK;
+}
+
+// ... then the status words back to the host, and the wait for them
+static int jpeg_device_entropy(lwp_handle h, JpegDeviceBatch& B) {
+    int rc = jpeg_entropy_enqueue(h, B);
+    if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(B.status_host, B.e.status, ((size_t)B.e.n_files + 2) * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return LWP_OK;
@@ -2903,7 +2778,7 @@ static int jpeg_prepare_device(lwp_handle h, int N, const unsigned char* const* 
     rc = jpeg_device_entropy(h, B);
     if (rc) return rc;
     for (int i = 0; i < N; ++i)
-        if (B.status_host[i]) return jpeg_device_refusal(h, i, data[i], len[i], B.hd[i], JPEG_REFUSED, true);
+        if (B.status_host[i]) return jpeg_device_refusal(h, i, data[i], len[i], B.H.hd[i], JPEG_REFUSED, true);
     *launch = B.j;
     return LWP_OK;
 }
@@ -2920,8 +2795,8 @@ extern "C" int lwp_debug_jpeg_entropy_batch(lwp_handle h, int N, const unsigned 
     if (rc) return rc;
     size_t b0 = 0;
     for (int i = 0; i < N; ++i) {
-        const size_t n = (size_t)B.hd[i].total_blocks;
-        status_out[i] = B.verdict[i] ? B.verdict[i] : B.status_host[i] ? JPEG_REFUSED : JPEG_OK;
+        const size_t n = (size_t)B.H.hd[i].total_blocks;
+        status_out[i] = B.H.verdict[i] ? B.H.verdict[i] : B.status_host[i] ? JPEG_REFUSED : JPEG_OK;
         if (!status_out[i]) {
             if (!coef_out[i] || !qtables_out[i]) return fail(h, LWP_ERR_ARG, "coef_out[i] / qtables_out[i] is null");
             HIP_TRY(h, hipMemcpyAsync(coef_out[i], B.j.coef + b0 * 64, n * 128, hipMemcpyDeviceToHost, h->stream));
@@ -2941,16 +2816,12 @@ extern "C" int lwp_time_jpeg_entropy_batch(lwp_handle h, int N, const unsigned c
     JpegDeviceBatch B;
     int rc = jpeg_device_prepare(h, N, data, len, nullptr, subseq_bytes ? subseq_bytes : h->jpeg_subseq, false, &B);
     if (rc) return rc;
-    rc = time_on_stream(h, iters, [&]() {
-        HIP_TRY(h, hipMemsetAsync(B.e.coef, 0, B.memset_bytes, h->stream));
-        LAUNCH(h, KC_OTHER, launch_jpeg_entropy(B.e, h->stream));
-        return (int)LWP_OK;
-    }, ms_total);
+    rc = time_on_stream(h, iters, [&]() { return jpeg_entropy_enqueue(h, B); }, ms_total);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(B.status_host, B.e.status, ((size_t)N + 2) * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < N; ++i)
-        if (B.status_host[i]) return jpeg_device_refusal(h, i, data[i], len[i], B.hd[i], JPEG_REFUSED, true);
+        if (B.status_host[i]) return jpeg_device_refusal(h, i, data[i], len[i], B.H.hd[i], JPEG_REFUSED, true);
     rounds[0] = B.status_host[N]; rounds[1] = B.status_host[N + 1];
     return LWP_OK;
 }
@@ -3005,18 +2876,29 @@ extern "C" int lwp_debug_jpeg_encode_header(int height, int width, int quality, 
 }
 
 struct JpegEncBatch {
+    JpegEncPlan P;
     JpegEncLaunch e{};
-    std::vector<JpegEncGeom> geom;
-    size_t o_ubytes = 0, ubytes_total = 0;             // the un-stuffed scans of the batch: one region, zeroed in front of stage D
-    std::vector<size_t> sbytes;                        // where each stuffed scan starts in the workspace
 };
 
-// checks, the per-image records and the batch's one upload [records | block starts | chunk starts | quantisation tables | Huffman
-// codes | host frames]; the arrays the kernels fill lie behind it in the same allocation.  Nothing is enqueued before every
-// image has been checked.
+static JpegEncLaunch jpeg_enc_launch(unsigned char* dev, const JpegEncPlan& P) {
+    JpegEncLaunch e{};
+    e.images = reinterpret_cast<const JpegEncImage*>(dev + P.images);
+    e.block_start = reinterpret_cast<const unsigned*>(dev + P.bstart); e.chunk_start = reinterpret_cast<const unsigned*>(dev + P.cstart);
+    e.qtables = reinterpret_cast<const uint16_t*>(dev + P.qt); e.huff = reinterpret_cast<const unsigned*>(dev + P.huff);
+    e.coef = reinterpret_cast<int16_t*>(dev + P.coef);
+    e.bits = reinterpret_cast<unsigned*>(dev + P.bits); e.offs = reinterpret_cast<unsigned*>(dev + P.offs);
+    e.istart = reinterpret_cast<unsigned*>(dev + P.istart);
+    e.ulen = reinterpret_cast<unsigned*>(dev + P.ulen); e.slen = reinterpret_cast<unsigned*>(dev + P.slen);
+    e.ffbase = reinterpret_cast<unsigned*>(dev + P.ffbase);
+    e.workspace = dev;
+    e.n_images = (int)P.geom.size(); e.total_blocks = (unsigned)P.blocks; e.total_chunks = (unsigned)P.chunks;
+    return e;
+}
+
+// checks, then the batch's one upload.  Nothing is enqueued before every image has been checked.
 static int jpeg_enc_prepare(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights, const int* widths,
                             int quality, int subsampling, int restart_interval, JpegEncBatch* B) {
-    char msg[200];
+    char msg[kJpegMsg];
     if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
     if (!frames || !heights || !widths) return fail(h, LWP_ERR_ARG, "frames / heights / widths is null");
     if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
@@ -3024,106 +2906,16 @@ static int jpeg_enc_prepare(lwp_handle h, int N, const unsigned char* const* fra
     if (quality < 1 || quality > 100) return fail(h, LWP_ERR_ARG, "jpeg encode: quality must be 1..100");
     if (subsampling < 0 || subsampling > 2) return fail(h, LWP_ERR_ARG, "jpeg encode: subsampling must be LWP_JPEG_444, LWP_JPEG_422 or LWP_JPEG_420");
     if (restart_interval < 0 || restart_interval > 65535) return fail(h, LWP_ERR_ARG, "jpeg encode: restart_interval must be 0..65535 MCUs");
-    B->geom.assign((size_t)N, JpegEncGeom{});
-    uint64_t blocks = 0, chunks = 0, intervals = 0, pixels = 0, scan_bytes = 0;
-    for (int i = 0; i < N; ++i) {
-        if (!frames[i]) { snprintf(msg, sizeof msg, "image %d: the frame is null", i); return fail(h, LWP_ERR_ARG, msg); }
-        JpegEncGeom& g = B->geom[i];
-        if (!jpeg_enc_geometry(heights[i], widths[i], subsampling, restart_interval, &g)) {
-            snprintf(msg, sizeof msg, "image %d: jpeg encode: %d x %d: height and width must be 1..65535", i, heights[i], widths[i]);
-            return fail(h, LWP_ERR_ARG, msg);
-        }
-        if ((uint64_t)g.total_blocks * kJpegEncBlockBytes * 8 >= ((uint64_t)1 << 32)) {       // bit offsets are 32-bit
-            snprintf(msg, sizeof msg, "image %d: jpeg encode: %d x %d has too many blocks for one scan: encode it in tiles", i, heights[i], widths[i]);
-            return fail(h, LWP_ERR_CAPACITY, msg);
-        }
-        blocks += (uint64_t)g.total_blocks;
-        intervals += (uint64_t)g.intervals;
-        chunks += (jpeg_enc_unstuffed_bound(g) + kJpegEncChunk - 1) / kJpegEncChunk;
-        pixels += (uint64_t)heights[i] * (uint64_t)widths[i] * 3;
-        scan_bytes += 3 * jpeg_enc_unstuffed_bound(g);
-    }
-    if (blocks > 0x7fffffffu || chunks > 0x7fffffffu || scan_bytes + blocks * 136 + pixels > ((uint64_t)1 << 36))
-        return fail(h, LWP_ERR_CAPACITY, "jpeg encode: the batch needs more than 64 GiB of workspace: encode it in parts");
-    auto align = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
-    const size_t o_images = 0, o_bstart = align((size_t)N * sizeof(JpegEncImage), 16), o_cstart = align(o_bstart + ((size_t)N + 1) * 4, 16);
-    const size_t o_qt = align(o_cstart + ((size_t)N + 1) * 4, 16), o_huff = o_qt + 2 * 64 * sizeof(uint16_t);
-    size_t upload = align(o_huff + sizeof(JpegEncHuff), 256);
-    std::vector<size_t> o_frame((size_t)N, 0);
-    if (mem == LWP_MEM_HOST)
-        for (int i = 0; i < N; ++i) { o_frame[i] = upload; upload = align(upload + (size_t)heights[i] * widths[i] * 3, 256); }
-    const size_t o_coef = upload, o_bits = o_coef + (size_t)blocks * 128, o_offs = o_bits + (size_t)blocks * 4;
-    const size_t o_istart = o_offs + (size_t)blocks * 4, o_ulen = o_istart + (size_t)intervals * 4, o_slen = o_ulen + (size_t)N * 4;
-    const size_t o_ffbase = o_slen + (size_t)N * 4;
-    size_t at = align(o_ffbase + (size_t)chunks * 4, 256);
-    B->o_ubytes = at;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, h->jpeg_enc_stage.ensure(upload));
-    unsigned char* host = h->jpeg_enc_stage.as<unsigned char>();
-    JpegEncImage* images = reinterpret_cast<JpegEncImage*>(host + o_images);
-    unsigned* bstart = reinterpret_cast<unsigned*>(host + o_bstart);
-    unsigned* cstart = reinterpret_cast<unsigned*>(host + o_cstart);
-    uint64_t b0 = 0, c0 = 0, i0 = 0;
-    for (int i = 0; i < N; ++i) {                      // the un-stuffed scans, back to back, whole chunks each
-        const JpegEncGeom& g = B->geom[i];
-        JpegEncImage& im = images[i];
-        memset(&im, 0, sizeof im);
-        const size_t n_chunks = (jpeg_enc_unstuffed_bound(g) + kJpegEncChunk - 1) / kJpegEncChunk;
-        im.ubytes = (long long)at; im.ucap = (unsigned)(n_chunks * kJpegEncChunk);
-        at += n_chunks * kJpegEncChunk;
-        im.width = widths[i]; im.height = heights[i]; im.hs = g.hs; im.vs = g.vs; im.mcus_x = g.mcus_x; im.mcus_y = g.mcus_y;
-        unsigned p0 = 0;
-        for (int c = 0; c < 3; ++c) {
-            im.blocks_w[c] = g.blocks_w[c]; im.real_w[c] = g.real_w[c]; im.real_h[c] = g.real_h[c];
-            im.plane0[c] = p0;
-            p0 += (unsigned)(g.blocks_w[c] * g.blocks_h[c]);
-        }
-        im.block0 = (unsigned)b0; im.n_blocks = (unsigned)g.total_blocks;
-        im.per_mcu = (unsigned)(g.hs * g.vs + 2); im.ri_blocks = im.per_mcu * (unsigned)restart_interval;
-        im.int0 = (unsigned)i0; im.n_int = (unsigned)g.intervals;
-        im.chunk0 = (unsigned)c0; im.n_chunks = (unsigned)n_chunks;
-        bstart[i] = (unsigned)b0; cstart[i] = (unsigned)c0;
-        b0 += (uint64_t)g.total_blocks; c0 += n_chunks; i0 += (uint64_t)g.intervals;
-    }
-    bstart[N] = (unsigned)b0; cstart[N] = (unsigned)c0;
-    B->ubytes_total = at - B->o_ubytes;
-    B->sbytes.assign((size_t)N, 0);
-    for (int i = 0; i < N; ++i) {
-        at = align(at, 16);
-        B->sbytes[i] = at;
-        images[i].sbytes = (long long)at; images[i].scap = (unsigned)jpeg_enc_scan_bound(B->geom[i]);
-        at += images[i].scap;
-    }
-    const size_t total = align(at, 256);
-    jpeg_enc_quant_tables(quality, reinterpret_cast<uint16_t(*)[64]>(host + o_qt));
-    jpeg_enc_huffman(reinterpret_cast<JpegEncHuff*>(host + o_huff));
-    int rc = order_in(h);
+    const JpegEncPlan& P = B->P;
+    int rc = jpeg_enc_plan(N, frames, mem == LWP_MEM_HOST, heights, widths, subsampling, restart_interval, &B->P, msg);
+    if (rc) return jpeg_fail(h, rc, msg);
+    unsigned char *host = nullptr, *dev = nullptr;
+    rc = jpeg_stage_begin(h, h->jpeg_enc, P.upload, &host);
     if (rc) return rc;
-    if (h->d_jpeg_enc.size() < total) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier launch may still read the old buffer
-        HIP_TRY(h, h->d_jpeg_enc.ensure(total));
-    }
-    unsigned char* dev = h->d_jpeg_enc.as<unsigned char>();
-    for (int i = 0; i < N; ++i) {
-        if (mem == LWP_MEM_HOST) {
-            memcpy(host + o_frame[i], frames[i], (size_t)heights[i] * widths[i] * 3);
-            images[i].src = dev + o_frame[i];
-        } else {
-            images[i].src = frames[i];
-        }
-    }
-    HIP_TRY(h, hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, h->stream));
-    JpegEncLaunch& e = B->e;
-    e.images = reinterpret_cast<const JpegEncImage*>(dev + o_images);
-    e.block_start = reinterpret_cast<const unsigned*>(dev + o_bstart); e.chunk_start = reinterpret_cast<const unsigned*>(dev + o_cstart);
-    e.qtables = reinterpret_cast<const uint16_t*>(dev + o_qt); e.huff = reinterpret_cast<const unsigned*>(dev + o_huff);
-    e.coef = reinterpret_cast<int16_t*>(dev + o_coef);
-    e.bits = reinterpret_cast<unsigned*>(dev + o_bits); e.offs = reinterpret_cast<unsigned*>(dev + o_offs);
-    e.istart = reinterpret_cast<unsigned*>(dev + o_istart);
-    e.ulen = reinterpret_cast<unsigned*>(dev + o_ulen); e.slen = reinterpret_cast<unsigned*>(dev + o_slen);
-    e.ffbase = reinterpret_cast<unsigned*>(dev + o_ffbase);
-    e.workspace = dev;
-    e.n_images = N; e.total_blocks = (unsigned)b0; e.total_chunks = (unsigned)c0;
+    rc = jpeg_stage_send(h, h->jpeg_enc, P.upload, P.total, false, &dev,
+                         [&](unsigned char* d) { jpeg_enc_fill(P, frames, mem == LWP_MEM_HOST, heights, widths, quality, d, host); });
+    if (rc) return rc;
+    B->e = jpeg_enc_launch(dev, P);
     return LWP_OK;
 }
 
@@ -3132,7 +2924,7 @@ static int jpeg_enc_enqueue(lwp_handle h, const JpegEncBatch& B) {
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_lengths(B.e, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_offsets(B.e, h->stream));
-    HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.o_ubytes, 0, B.ubytes_total, h->stream));
+    HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.P.ubytes, 0, B.P.ubytes_total, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_write(B.e, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_stuff_scan(B.e, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_stuff(B.e, h->stream));
@@ -3149,7 +2941,7 @@ extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* c
     rc = jpeg_enc_enqueue(h, B);
     if (rc) return rc;
     // the one wait of the call: the N lengths.  The staging's front part is free again: the upload ran in front of the kernels
-    unsigned* lens = h->jpeg_enc_stage.as<unsigned>();
+    unsigned* lens = h->jpeg_enc.stage.as<unsigned>();
     HIP_TRY(h, hipMemcpyAsync(lens, B.e.slen, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     std::vector<size_t> scan((size_t)N), at((size_t)N);
@@ -3158,9 +2950,9 @@ extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* c
     size_t stage = 0;
     for (int i = 0; i < N; ++i) {
         scan[i] = lens[i];
-        if (scan[i] > jpeg_enc_scan_bound(B.geom[i])) {
+        if (scan[i] > jpeg_enc_scan_bound(B.P.geom[i])) {
             char msg[160];
-            snprintf(msg, sizeof msg, "image %d: jpeg encode: a scan of %zu bytes where %zu is the most possible", i, scan[i], jpeg_enc_scan_bound(B.geom[i]));
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: a scan of %zu bytes where %zu is the most possible", i, scan[i], jpeg_enc_scan_bound(B.P.geom[i]));
             return fail(h, LWP_ERR_INTERNAL, msg);
         }
         at[i] = stage;
@@ -3172,10 +2964,10 @@ extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* c
             snprintf(msg, sizeof msg, "image %d: jpeg encode: the file takes %zu bytes, cap is %zu", i, hd_len + scan[i] + 2, cap[i]);
             return fail(h, LWP_ERR_CAPACITY, msg);
         }
-    HIP_TRY(h, h->jpeg_enc_stage.ensure(stage));
-    unsigned char* host = h->jpeg_enc_stage.as<unsigned char>();
+    HIP_TRY(h, h->jpeg_enc.stage.ensure(stage));
+    unsigned char* host = h->jpeg_enc.stage.as<unsigned char>();
     for (int i = 0; i < N; ++i)
-        if (out[i] && scan[i]) HIP_TRY(h, hipMemcpyAsync(host + at[i], B.e.workspace + B.sbytes[i], scan[i], hipMemcpyDeviceToHost, h->stream));
+        if (out[i] && scan[i]) HIP_TRY(h, hipMemcpyAsync(host + at[i], B.e.workspace + B.P.sbytes[i], scan[i], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < N; ++i) {
         len_out[i] = hd_len + scan[i] + 2;
@@ -3198,8 +2990,8 @@ extern "C" int lwp_debug_jpeg_encode_blocks(lwp_handle h, int N, const unsigned 
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream));
     size_t b0 = 0;
     for (int i = 0; i < N; ++i) {
-        HIP_TRY(h, hipMemcpyAsync(coef_out[i], B.e.coef + b0 * 64, (size_t)B.geom[i].total_blocks * 128, hipMemcpyDeviceToHost, h->stream));
-        b0 += (size_t)B.geom[i].total_blocks;
+        HIP_TRY(h, hipMemcpyAsync(coef_out[i], B.e.coef + b0 * 64, (size_t)B.P.geom[i].total_blocks * 128, hipMemcpyDeviceToHost, h->stream));
+        b0 += (size_t)B.P.geom[i].total_blocks;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     memset(qtables_out, 0, (size_t)kJpegQuantSlots * 64 * sizeof(uint16_t));
@@ -3222,7 +3014,7 @@ extern "C" int lwp_time_jpeg_encode_batch(lwp_handle h, int N, const unsigned ch
     rc = time_on_stream(h, iters, [&]() { LAUNCH(h, KC_OTHER, launch_jpeg_enc_offsets(B.e, h->stream)); return (int)LWP_OK; }, &ms_total[2]);
     if (rc) return rc;
     rc = time_on_stream(h, iters, [&]() {
-        HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.o_ubytes, 0, B.ubytes_total, h->stream));
+        HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.P.ubytes, 0, B.P.ubytes_total, h->stream));
         LAUNCH(h, KC_OTHER, launch_jpeg_enc_write(B.e, h->stream));
         return (int)LWP_OK;
     }, &ms_total[3]);
@@ -3445,14 +3237,13 @@ static int coco_eval_match(lwp_handle h, const CocoEvalInput& in, bool with_orde
     CocoEvalParams& p = run->p;
 
     // sections of the allocation, each 16-byte aligned
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    Layout lay;
     const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
-    const size_t i_dt_off = take(nb), i_gt_off = take(nb), i_sel_off = take(nb), i_oks_off = take(nb);
-    const size_t i_dt_kp = take((size_t)ND * kEvalK * 3 * 8), i_dt_score = take((size_t)ND * 8);
-    const size_t i_gt_kp = take((size_t)NG * kEvalK * 3 * 8), i_gt_area = take((size_t)NG * 8), i_gt_bbox = take((size_t)NG * 4 * 8);
-    const size_t i_gt_crowd = take((size_t)NG * 4), i_gt_ignore = take((size_t)NG * 4);
-    const size_t in_bytes = std::max<size_t>(at, 16);
+    const size_t i_dt_off = lay.take<char>(nb), i_gt_off = lay.take<char>(nb), i_sel_off = lay.take<char>(nb), i_oks_off = lay.take<char>(nb);
+    const size_t i_dt_kp = lay.take<char>((size_t)ND * kEvalK * 3 * 8), i_dt_score = lay.take<char>((size_t)ND * 8);
+    const size_t i_gt_kp = lay.take<char>((size_t)NG * kEvalK * 3 * 8), i_gt_area = lay.take<char>((size_t)NG * 8), i_gt_bbox = lay.take<char>((size_t)NG * 4 * 8);
+    const size_t i_gt_crowd = lay.take<char>((size_t)NG * 4), i_gt_ignore = lay.take<char>((size_t)NG * 4);
+    const size_t in_bytes = std::max<size_t>(lay.align(), 16);
     std::vector<unsigned char>& stage = run->stage;
     stage.assign(in_bytes, 0);
     auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(stage.data() + off, src, bytes); };
@@ -3476,22 +3267,21 @@ static int coco_eval_launch(lwp_handle h, bool with_order, CocoEvalRun* run) {
     CocoEvalParams& p = run->p;
     const int n = p.n_images;
     const int64_t NG = p.NG, NS = p.NS, NO = run->oks_off[n];
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-    const size_t s_gt_m = take((size_t)kEvalAT * NG);                       // first: the part that is zeroed
-    const size_t zero_bytes = at;
-    const size_t s_sel_idx = take((size_t)NS * 4), s_sel_score = take((size_t)NS * 8), s_oks = take((size_t)NO * 8);
-    const size_t s_gt_flag = take((size_t)NG), s_dt_m = take((size_t)kEvalAT * NS), s_dt_ig = take((size_t)kEvalAT * NS);
-    const size_t s_npig_img = take((size_t)n * kEvalA * 4);
-    const size_t s_out = take(((size_t)2 * kEvalT * kEvalR * kEvalA + kEvalT * kEvalA) * 8 + kEvalA * 8);
+    Layout lay;
+    const size_t s_gt_m = lay.take<char>((size_t)kEvalAT * NG);                       // first: the part that is zeroed
+    const size_t zero_bytes = lay.align();
+    const size_t s_sel_idx = lay.take<char>((size_t)NS * 4), s_sel_score = lay.take<char>((size_t)NS * 8), s_oks = lay.take<char>((size_t)NO * 8);
+    const size_t s_gt_flag = lay.take<char>((size_t)NG), s_dt_m = lay.take<char>((size_t)kEvalAT * NS), s_dt_ig = lay.take<char>((size_t)kEvalAT * NS);
+    const size_t s_npig_img = lay.take<char>((size_t)n * kEvalA * 4);
+    const size_t s_out = lay.take<char>(((size_t)2 * kEvalT * kEvalR * kEvalA + kEvalT * kEvalA) * 8 + kEvalA * 8);
     size_t s_keys = 0, s_keys_out = 0, s_vals = 0, s_perm = 0, s_tpfp = 0, s_pr = 0, s_tmp = 0;
     if (with_order) {
         HIP_TRY(h, coco_sort_temp_bytes(NS, &run->sort_tmp_bytes));
-        s_keys = take((size_t)NS * 8); s_keys_out = take((size_t)NS * 8); s_vals = take((size_t)NS * 4); s_perm = take((size_t)NS * 4);
-        s_tpfp = take((size_t)kEvalAT * NS * 8); s_pr = take((size_t)kEvalAT * NS * 8);
-        s_tmp = take(run->sort_tmp_bytes);
+        s_keys = lay.take<char>((size_t)NS * 8); s_keys_out = lay.take<char>((size_t)NS * 8); s_vals = lay.take<char>((size_t)NS * 4); s_perm = lay.take<char>((size_t)NS * 4);
+        s_tpfp = lay.take<char>((size_t)kEvalAT * NS * 8); s_pr = lay.take<char>((size_t)kEvalAT * NS * 8);
+        s_tmp = lay.take<char>(run->sort_tmp_bytes);
     }
-    const size_t scratch_bytes = std::max<size_t>(at, 16);
+    const size_t scratch_bytes = std::max<size_t>(lay.align(), 16);
     HIP_TRY(h, run->scratch.ensure(scratch_bytes));
     unsigned char* ds = run->scratch.as<unsigned char>();
     if (zero_bytes) HIP_TRY(h, hipMemsetAsync(ds + s_gt_m, 0, zero_bytes, h->stream));
@@ -3597,13 +3387,12 @@ extern "C" int lwp_coco_open(lwp_handle h, int n_images, const int64_t* gt_off, 
     auto& c = h->coco;
     const int n = n_images;
     const int64_t NG = gt_off[n];
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    Layout lay;
     const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
-    const size_t o_off = take(nb);
-    c.o_kp = take((size_t)NG * kEvalK * 3 * 8); c.o_area = take((size_t)NG * 8); c.o_bbox = take((size_t)NG * 4 * 8);
-    c.o_crowd = take((size_t)NG * 4); c.o_ignore = take((size_t)NG * 4);
-    std::vector<unsigned char> stage(std::max<size_t>(at, 16));
+    const size_t o_off = lay.take<char>(nb);
+    c.o_kp = lay.take<char>((size_t)NG * kEvalK * 3 * 8); c.o_area = lay.take<char>((size_t)NG * 8); c.o_bbox = lay.take<char>((size_t)NG * 4 * 8);
+    c.o_crowd = lay.take<char>((size_t)NG * 4); c.o_ignore = lay.take<char>((size_t)NG * 4);
+    std::vector<unsigned char> stage(std::max<size_t>(lay.align(), 16));
     auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(stage.data() + off, src, bytes); };
     put(o_off, gt_off, nb); put(c.o_kp, gt_kp, (size_t)NG * kEvalK * 3 * 8); put(c.o_area, gt_area, (size_t)NG * 8);
     put(c.o_bbox, gt_bbox, (size_t)NG * 4 * 8); put(c.o_crowd, gt_iscrowd, (size_t)NG * 4); put(c.o_ignore, gt_ignore, (size_t)NG * 4);
@@ -3858,17 +3647,16 @@ static int coco_gather_rows(lwp_context* h, CocoEvalRun* run) {
     const int64_t ND = dt_off[n];
     if (ND > c.st.row_cap) return fail(h, LWP_ERR_STATE, "the detection store's counts exceed its rows");
     coco_eval_offsets(n, dt_off.data(), c.gt_off.data(), run);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    Layout lay;
     const size_t nb = ((size_t)n + 1) * sizeof(int64_t);
-    const size_t i_dt_off = take(nb), i_sel_off = take(nb), i_oks_off = take(nb);
-    const size_t up_bytes = at;
-    const size_t i_dt_kp = take((size_t)ND * kEvalK * 3 * 8), i_dt_score = take((size_t)ND * 8);
+    const size_t i_dt_off = lay.take<char>(nb), i_sel_off = lay.take<char>(nb), i_oks_off = lay.take<char>(nb);
+    const size_t up_bytes = lay.align();
+    const size_t i_dt_kp = lay.take<char>((size_t)ND * kEvalK * 3 * 8), i_dt_score = lay.take<char>((size_t)ND * 8);
     run->stage.assign(up_bytes, 0);
     memcpy(run->stage.data() + i_dt_off, dt_off.data(), nb);
     memcpy(run->stage.data() + i_sel_off, run->sel_off.data(), nb);
     memcpy(run->stage.data() + i_oks_off, run->oks_off.data(), nb);
-    HIP_TRY(h, run->in.ensure(std::max<size_t>(at, 16)));
+    HIP_TRY(h, run->in.ensure(std::max<size_t>(lay.align(), 16)));
     unsigned char* di = run->in.as<unsigned char>();
     HIP_TRY(h, hipMemcpyAsync(di, run->stage.data(), up_bytes, hipMemcpyHostToDevice, h->stream));
     CocoEvalParams& p = run->p;
@@ -3894,11 +3682,10 @@ extern "C" int lwp_coco_rows(lwp_handle h, int* dt_image, double* dt_kp, double*
     auto& c = h->coco;
     const int n = c.st.n_images;
     const size_t cap = (size_t)std::min<int64_t>(row_cap, c.st.row_cap);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-    const size_t s_off = take(((size_t)n + 1) * 8), s_kp = take(cap * kEvalK * 3 * 8), s_score = take(cap * 8), s_image = take(cap * 4);
+    Layout lay;
+    const size_t s_off = lay.take<char>(((size_t)n + 1) * 8), s_kp = lay.take<char>(cap * kEvalK * 3 * 8), s_score = lay.take<char>(cap * 8), s_image = lay.take<char>(cap * 4);
     DevBuf scratch;
-    HIP_TRY(h, scratch.ensure(std::max<size_t>(at, 16)));
+    HIP_TRY(h, scratch.ensure(std::max<size_t>(lay.align(), 16)));
     char* ds = scratch.as<char>();
     LAUNCH(h, KC_OTHER, launch_coco_offsets(c.st, (int64_t*)(ds + s_off), h->stream));
     LAUNCH(h, KC_OTHER, launch_coco_gather(c.st, (const int64_t*)(ds + s_off), (int64_t)cap, (double*)(ds + s_kp), (double*)(ds + s_score),

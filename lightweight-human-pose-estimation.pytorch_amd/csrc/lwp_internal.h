@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/lwpose.h"
+#include "jpeg_batch.h"
 
 namespace lwp {
 
@@ -427,27 +428,8 @@ struct CrowdLaunch {
 };
 hipError_t launch_crowd_masks(const CrowdLaunch& c, hipStream_t s);
 // ---- JPEG decode, device half (jpeg_kernels.hip; libjpeg's default path: jidctint.c, fancy up-sampling, jdcolor.c): stage A
-// turns the coefficient blocks of a batch into block-padded uint8 component planes, stage B up-samples, converts and stores BGR
-constexpr int kJpegBlocksPerGroup = 32;   // stage A: 8 lanes a block, 256 threads a workgroup
-constexpr int kJpegPixelsPerThread = 4;   // stage B: horizontally adjacent output pixels of one thread
-constexpr int kJpegUnitsPerGroup = 256;   // stage B: threads (pixel groups) a workgroup
-struct JpegPlane {                        // one component of one image
-    unsigned block0;                      // its first block in the batch's plane-ordered coefficient array
-    int blocks_w;                         // blocks a block row (the plane is blocks_w * 8 bytes wide)
-    unsigned qt;                          // uint16 offset of its quantisation table (natural order) in the batch's table array
-    unsigned pad_;
-    long long plane;                      // byte offset of the plane in the workspace
-};
-struct JpegImage {
-    unsigned unit0;                       // its first pixel group in the batch (a row holds ceil(width / kJpegPixelsPerThread))
-    int width, height;
-    int mode;                             // 0 grey, 1 4:4:4, 2 4:2:2 (h2v1), 3 4:2:0 (h2v2)
-    int chroma_w, chroma_h;               // TRUE size of the chroma planes: the edges the up-sampling replicates
-    int stride[3];                        // bytes a row of each plane
-    int pad_;
-    long long plane[3];                   // byte offsets of the planes in the workspace
-    unsigned char* out;                   // height * width * 3 bytes, BGR
-};
+// turns the coefficient blocks of a batch into block-padded uint8 component planes, stage B up-samples, converts and stores BGR.
+// The records of this and the next two sections, and the constants their filling needs, are jpeg_batch.h's
 struct JpegLaunch {
     const int16_t* coef; const uint16_t* qtables;
     const JpegPlane* planes; const unsigned* plane_block0;    // [n_planes] records; [n_planes + 1] their block0, then the total
@@ -461,25 +443,6 @@ hipError_t launch_jpeg_color(const JpegLaunch& j, hipStream_t s);
 // ---- JPEG entropy decode on the device (jpeg_entropy_kernels.hip): fills JpegLaunch::coef from the un-stuffed scan
 // bytes, segments and flattened tables that jpeg_scan_segments (jpeg_host.h) left.  One lane owns one subsequence of
 // subseq_bytes bytes of one segment; a workgroup takes kJpegEntropyGroup consecutive subsequences of ONE file.
-struct JpegHuffFlat;                      // jpeg_host.h
-constexpr int kJpegEntropyGroup = 256;
-constexpr int kJpegSubseqDefault = 128;   // bytes; lwp_set_jpeg_entropy's subseq_bytes 0
-struct JpegEntFile {
-    unsigned seg0, n_segs;                // its segments in the batch's segment array
-    unsigned sub0, n_subs;                // its subsequences in the batch's numbering (0: the file is skipped)
-    unsigned wg0, n_wgs;                  // its workgroups of the sync and the write pass
-    unsigned block0, total_blocks;        // its blocks in the batch's plane-ordered coefficient array
-    int components, blocks_per_mcu, mcus_x;
-    int h0, v0;                           // sampling of component 0 (the others are 1x1)
-    unsigned plane_block[3];              // first block of each plane, file-relative
-    int blocks_w[3];
-};
-struct JpegEntSeg {
-    unsigned byte0, n_bytes;              // un-stuffed bytes, byte0 from the start of the batch's byte area
-    unsigned first_block, n_blocks;       // stream index (MCU order, file-relative) of its first block; MCUs times blocks per MCU
-    unsigned sub0;                        // its first subsequence in the batch's numbering
-    unsigned file;
-};
 struct JpegEntropyLaunch {
     const unsigned* words; unsigned n_words;          // the byte area as dwords
     const JpegHuffFlat* tables;                       // [n_files][kJpegHuffPerFile]
@@ -502,23 +465,6 @@ hipError_t launch_jpeg_entropy(const JpegEntropyLaunch& e, hipStream_t s);
 //   D  the codes of every block at its offset, OR-ed into the zeroed un-stuffed scan (one lane a block)
 //   E  per image, the 0xFF bytes in front of every chunk of the un-stuffed scan (one workgroup an image)
 //   F  the stuffed scan: FF 00 for FF, RSTn between the intervals (one lane a chunk)
-constexpr int kJpegEncBlocksPerGroup = 32;    // stage A: 8 lanes a block, 256 threads a workgroup
-constexpr int kJpegEncGroup = 256;            // stages B .. F: threads a workgroup; C and E step over an image in tiles of this many
-constexpr int kJpegEncChunk = 32;             // stages E and F: un-stuffed bytes a lane owns
-struct JpegEncImage {
-    const unsigned char* src;                 // device BGR pixels, width * 3 bytes a row
-    long long ubytes, sbytes;                 // byte offsets in the workspace: the un-stuffed scan (zeroed, 32-byte granular), the stuffed scan
-    int width, height, hs, vs;                // hs, vs: luma sampling (chroma 1 x 1)
-    int mcus_x, mcus_y;
-    int blocks_w[3];                          // MCU-padded grid widths
-    int real_w[3], real_h[3];                 // blocks that hold samples; the others are dummy blocks
-    unsigned block0, n_blocks;                // its blocks in the batch's arrays (coefficients: plane order; bits, offsets: stream order)
-    unsigned plane0[3];                       // first block of each plane, image-relative
-    unsigned per_mcu, ri_blocks;              // blocks an MCU; blocks a restart interval (0: no restarts)
-    unsigned int0, n_int;                     // its restart intervals in the batch's interval array
-    unsigned chunk0, n_chunks;                // its chunks (the bound) in the batch's chunk array
-    unsigned ucap, scap;                      // bytes available at ubytes and at sbytes
-};
 struct JpegEncLaunch {
     const JpegEncImage* images;               // [n_images]
     const unsigned* block_start;              // [n_images + 1] block0 of every image, then the total
