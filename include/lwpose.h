@@ -838,6 +838,15 @@ int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frame
  * (slots 0 and 1). */
 int lwp_debug_jpeg_encode_blocks(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights,
                                  const int* widths, int quality, int subsampling, int16_t* const* coef_out, uint16_t* qtables_out);
+/* the other stages alone, for tests: the entropy code of the CALLER's coefficients.  coef[i]: HOST memory, 64 * total_blocks
+ * int16 in the COEFFICIENT LAYOUT, which is what lwp_debug_jpeg_encode_blocks returns; a DC outside -1024..1023 or an AC term
+ * outside -1023..1023 (no 8-bit picture has more, and the kernels' tables end there) is LWP_ERR_ARG with the image's index
+ * before anything is enqueued.  The call plans and uploads as lwp_jpeg_encode_batch does, copies the coefficients where the
+ * first stage would have left them and runs the memset and the other five launches.  out[i] (cap[i] bytes, or NULL) receives
+ * the stuffed scan alone, RSTn markers included: no header and no EOI; len_out[i] its length.  cap[i] below that is
+ * LWP_ERR_CAPACITY and no out[i] is written. */
+int lwp_debug_jpeg_encode_scan(lwp_handle h, int N, const int16_t* const* coef, const int* heights, const int* widths,
+                               int subsampling, int restart_interval, unsigned char* const* out, const size_t* cap, size_t* len_out);
 /* the header bytes alone, SOI up to and including SOS (at most 640 bytes; LWP_ERR_CAPACITY if cap is below them).  No handle,
  * no GPU. */
 int lwp_debug_jpeg_encode_header(int height, int width, int quality, int subsampling, int restart_interval, unsigned char* out,

@@ -49,7 +49,7 @@ EXPORTS = [
     "lwp_jpeg_info", "lwp_debug_jpeg_blocks", "lwp_jpeg_decode_batch", "lwp_time_jpeg_decode_batch",
     "lwp_set_jpeg_entropy", "lwp_debug_jpeg_entropy_batch", "lwp_debug_jpeg_scan", "lwp_time_jpeg_entropy_batch",
     "lwp_jpeg_encode_bound", "lwp_jpeg_encode_batch", "lwp_debug_jpeg_encode_blocks", "lwp_debug_jpeg_encode_header",
-    "lwp_time_jpeg_encode_batch",
+    "lwp_time_jpeg_encode_batch", "lwp_debug_jpeg_encode_scan",
     "lwp_set_backward_precision", "lwp_get_backward_precision",
     "lwp_stage_losses_log", "lwp_loss_log_read",
 ]
@@ -216,6 +216,8 @@ def lib():
     L.lwp_jpeg_encode_bound.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)]
     L.lwp_jpeg_encode_batch.argtypes = jpeg_frames + [C.c_int] * 3 + [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.lwp_debug_jpeg_encode_blocks.argtypes = jpeg_frames + [C.c_int] * 2 + [C.POINTER(vp), vp]
+    L.lwp_debug_jpeg_encode_scan.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_size_t)]
     L.lwp_debug_jpeg_encode_header.argtypes = [C.c_int] * 5 + [vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lwp_time_jpeg_encode_batch.argtypes = jpeg_frames + [C.c_int] * 4 + [fp]
     L.lwp_set_backward_precision.argtypes = [vp, C.c_int, C.c_double]

@@ -2919,9 +2919,14 @@ static int jpeg_enc_prepare(lwp_handle h, int N, const unsigned char* const* fra
     return LWP_OK;
 }
 
-// the six stages, in order, on the handle's stream
-static int jpeg_enc_enqueue(lwp_handle h, const JpegEncBatch& B) {
+// stage A alone ...
+static int jpeg_enc_enqueue_dct(lwp_handle h, const JpegEncBatch& B) {
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream));
+    return LWP_OK;
+}
+
+// ... and behind it the entropy code of whatever B.e.coef holds: stages B and C, the memset of the un-stuffed scans, D, E, F
+static int jpeg_enc_enqueue_entropy(lwp_handle h, const JpegEncBatch& B) {
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_lengths(B.e, h->stream));
     LAUNCH(h, KC_OTHER, launch_jpeg_enc_offsets(B.e, h->stream));
     HIP_TRY(h, hipMemsetAsync(B.e.workspace + B.P.ubytes, 0, B.P.ubytes_total, h->stream));
@@ -2931,22 +2936,25 @@ static int jpeg_enc_enqueue(lwp_handle h, const JpegEncBatch& B) {
     return LWP_OK;
 }
 
-extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights, const int* widths,
-                                     int quality, int subsampling, int restart_interval, unsigned char* const* out, const size_t* cap,
-                                     size_t* len_out) {
-    if (!out || !cap || !len_out) return fail(h, LWP_ERR_ARG, "out / cap / len_out is null");
-    JpegEncBatch B;
-    int rc = jpeg_enc_prepare(h, N, frames, mem, heights, widths, quality, subsampling, restart_interval, &B);
-    if (rc) return rc;
-    rc = jpeg_enc_enqueue(h, B);
-    if (rc) return rc;
-    // the one wait of the call: the N lengths.  The staging's front part is free again: the upload ran in front of the kernels
+// the six stages, in order, on the handle's stream
+static int jpeg_enc_enqueue(lwp_handle h, const JpegEncBatch& B) {
+    const int rc = jpeg_enc_enqueue_dct(h, B);
+    return rc ? rc : jpeg_enc_enqueue_entropy(h, B);
+}
+
+// Behind the enqueue: the one wait of the call, for the N stuffed lengths, which are checked against the bound and, where
+// out[i] is set, against cap[i] (what the caller writes of image i takes `around` bytes more than its scan); then the scans of
+// those images come to the staging, scan[i] bytes at *host + at[i].  Nothing has been written to any out[i] when this fails.
+static int jpeg_enc_fetch(lwp_handle h, const JpegEncBatch& B, unsigned char* const* out, const size_t* cap, size_t around,
+                          std::vector<size_t>* scan_out, std::vector<size_t>* at_out, unsigned char** host_out) {
+    const int N = (int)B.P.geom.size();
+    // the staging's front part is free again: the upload ran in front of the kernels
     unsigned* lens = h->jpeg_enc.stage.as<unsigned>();
     HIP_TRY(h, hipMemcpyAsync(lens, B.e.slen, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    std::vector<size_t> scan((size_t)N), at((size_t)N);
-    unsigned char hd[kJpegEncHeaderMax];
-    const size_t hd_len = jpeg_enc_header(heights[0], widths[0], quality, subsampling, restart_interval, hd);      // the same for every size
+    std::vector<size_t>& scan = *scan_out;
+    std::vector<size_t>& at = *at_out;
+    scan.assign((size_t)N, 0); at.assign((size_t)N, 0);
     size_t stage = 0;
     for (int i = 0; i < N; ++i) {
         scan[i] = lens[i];
@@ -2959,9 +2967,9 @@ extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* c
         if (out[i]) stage += (scan[i] + 15) & ~(size_t)15;
     }
     for (int i = 0; i < N; ++i)
-        if (out[i] && cap[i] < hd_len + scan[i] + 2) {
+        if (out[i] && cap[i] < around + scan[i]) {
             char msg[160];
-            snprintf(msg, sizeof msg, "image %d: jpeg encode: the file takes %zu bytes, cap is %zu", i, hd_len + scan[i] + 2, cap[i]);
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: the %s takes %zu bytes, cap is %zu", i, around ? "file" : "scan", around + scan[i], cap[i]);
             return fail(h, LWP_ERR_CAPACITY, msg);
         }
     HIP_TRY(h, h->jpeg_enc.stage.ensure(stage));
@@ -2969,6 +2977,25 @@ extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* c
     for (int i = 0; i < N; ++i)
         if (out[i] && scan[i]) HIP_TRY(h, hipMemcpyAsync(host + at[i], B.e.workspace + B.P.sbytes[i], scan[i], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *host_out = host;
+    return LWP_OK;
+}
+
+extern "C" int lwp_jpeg_encode_batch(lwp_handle h, int N, const unsigned char* const* frames, int mem, const int* heights, const int* widths,
+                                     int quality, int subsampling, int restart_interval, unsigned char* const* out, const size_t* cap,
+                                     size_t* len_out) {
+    if (!out || !cap || !len_out) return fail(h, LWP_ERR_ARG, "out / cap / len_out is null");
+    JpegEncBatch B;
+    int rc = jpeg_enc_prepare(h, N, frames, mem, heights, widths, quality, subsampling, restart_interval, &B);
+    if (rc) return rc;
+    rc = jpeg_enc_enqueue(h, B);
+    if (rc) return rc;
+    unsigned char hd[kJpegEncHeaderMax];
+    const size_t hd_len = jpeg_enc_header(heights[0], widths[0], quality, subsampling, restart_interval, hd);      // the same for every size
+    std::vector<size_t> scan, at;
+    unsigned char* host = nullptr;
+    rc = jpeg_enc_fetch(h, B, out, cap, hd_len + 2, &scan, &at, &host);
+    if (rc) return rc;
     for (int i = 0; i < N; ++i) {
         len_out[i] = hd_len + scan[i] + 2;
         if (!out[i]) continue;
@@ -2987,7 +3014,8 @@ extern "C" int lwp_debug_jpeg_encode_blocks(lwp_handle h, int N, const unsigned 
     if (rc) return rc;
     for (int i = 0; i < N; ++i)
         if (!coef_out[i]) return fail(h, LWP_ERR_ARG, "coef_out holds a null pointer");
-    LAUNCH(h, KC_OTHER, launch_jpeg_enc_dct(B.e, h->stream));
+    rc = jpeg_enc_enqueue_dct(h, B);
+    if (rc) return rc;
     size_t b0 = 0;
     for (int i = 0; i < N; ++i) {
         HIP_TRY(h, hipMemcpyAsync(coef_out[i], B.e.coef + b0 * 64, (size_t)B.P.geom[i].total_blocks * 128, hipMemcpyDeviceToHost, h->stream));
@@ -2996,6 +3024,55 @@ extern "C" int lwp_debug_jpeg_encode_blocks(lwp_handle h, int N, const unsigned 
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     memset(qtables_out, 0, (size_t)kJpegQuantSlots * 64 * sizeof(uint16_t));
     jpeg_enc_quant_tables(quality, reinterpret_cast<uint16_t(*)[64]>(qtables_out));
+    return LWP_OK;
+}
+
+// the other stages alone: the caller's coefficients in stage A's place
+extern "C" int lwp_debug_jpeg_encode_scan(lwp_handle h, int N, const int16_t* const* coef, const int* heights, const int* widths,
+                                          int subsampling, int restart_interval, unsigned char* const* out, const size_t* cap,
+                                          size_t* len_out) {
+    if (!h) return fail(h, LWP_ERR_ARG, "handle is null");
+    if (!coef || !heights || !widths || !out || !cap || !len_out) return fail(h, LWP_ERR_ARG, "coef / heights / widths / out / cap / len_out is null");
+    if (N < 1 || N > 65535) return fail(h, LWP_ERR_ARG, "N must be 1..65535");
+    // the kernels' contract, which stage A keeps by construction: a DC of -1024..1023, AC terms of -1023..1023
+    for (int i = 0; i < N; ++i) {
+        char msg[200];
+        JpegEncGeom g;
+        if (!coef[i]) { snprintf(msg, sizeof msg, "image %d: coef is null", i); return fail(h, LWP_ERR_ARG, msg); }
+        if (!jpeg_enc_geometry(heights[i], widths[i], subsampling, restart_interval, &g)) {
+            snprintf(msg, sizeof msg, "image %d: jpeg encode: %d x %d: height and width must be 1..65535, subsampling 0..2, restart_interval 0..65535",
+                     i, heights[i], widths[i]);
+            return fail(h, LWP_ERR_ARG, msg);
+        }
+        for (size_t k = 0; k < (size_t)g.total_blocks * 64; ++k) {
+            const int v = coef[i][k];
+            if (v > 1023 || v < (k & 63 ? -1023 : -1024)) {
+                snprintf(msg, sizeof msg, "image %d: jpeg encode: coefficient %d of block %zu is %d: a DC must be -1024..1023, an AC term -1023..1023",
+                         i, (int)(k & 63), k >> 6, v);
+                return fail(h, LWP_ERR_ARG, msg);
+            }
+        }
+    }
+    JpegEncBatch B;
+    // the records want frame addresses; stage A, the one reader of them, does not run: the coefficients' own stand in
+    int rc = jpeg_enc_prepare(h, N, reinterpret_cast<const unsigned char* const*>(coef), LWP_MEM_DEVICE, heights, widths, 100, subsampling,
+                              restart_interval, &B);
+    if (rc) return rc;
+    size_t b0 = 0;
+    for (int i = 0; i < N; ++i) {
+        HIP_TRY(h, hipMemcpyAsync(B.e.coef + b0 * 64, coef[i], (size_t)B.P.geom[i].total_blocks * 128, hipMemcpyHostToDevice, h->stream));
+        b0 += (size_t)B.P.geom[i].total_blocks;
+    }
+    rc = jpeg_enc_enqueue_entropy(h, B);
+    if (rc) return rc;
+    std::vector<size_t> scan, at;
+    unsigned char* host = nullptr;
+    rc = jpeg_enc_fetch(h, B, out, cap, 0, &scan, &at, &host);
+    if (rc) return rc;
+    for (int i = 0; i < N; ++i) {
+        len_out[i] = scan[i];
+        if (out[i]) memcpy(out[i], host + at[i], scan[i]);
+    }
     return LWP_OK;
 }
 

@@ -1032,6 +1032,54 @@ class Engine(object):
             self._call("lwp_debug_jpeg_encode_blocks", N, ptrs, mem, heights, widths, q, sub, cp, qt.ctypes.data)
         return coefs, qt
 
+    @staticmethod
+    def _jpeg_scan_args(coefs, sizes, subsampling, restart_interval):
+        """The checks of ``debug_jpeg_encode_scan`` that need no device: (contiguous int16 arrays, heights, widths, the
+        library's subsampling number, the restart interval).  A coefficient array of another type than int16 (nothing is
+        converted: a wrapped value would be coded as if it were meant) or another shape than (total_blocks, 64) of its size,
+        or another number of sizes than of arrays, is a ValueError."""
+        _, sub, ri = Engine._jpeg_encode_options(75, subsampling, restart_interval)
+        coefs, sizes = list(coefs), list(sizes)
+        if len(sizes) != len(coefs):
+            raise ValueError("%d sizes for %d coefficient arrays" % (len(sizes), len(coefs)))
+        arrs, heights, widths = [], [], []
+        for i, (c, hw) in enumerate(zip(coefs, sizes)):
+            if len(tuple(hw)) != 2:
+                raise ValueError("size %d must be (H, W), not %r" % (i, hw))
+            H, W = int(hw[0]), int(hw[1])
+            if H < 1 or W < 1 or H > 65535 or W > 65535:
+                raise ValueError("size %d: %d x %d: height and width must be 1..65535" % (i, H, W))
+            if not isinstance(c, np.ndarray) or c.dtype != np.int16:
+                raise ValueError("coefficients %d must be an int16 array, not %s" % (i, getattr(c, "dtype", type(c).__name__)))
+            blocks = Engine.jpeg_info(Engine.debug_jpeg_encode_header(H, W, 75, subsampling))["total_blocks"]
+            if c.shape != (blocks, 64):
+                raise ValueError("coefficients %d must be (%d, 64) for %d x %d at %s, not %s" % (i, blocks, H, W, subsampling, c.shape))
+            arrs.append(np.ascontiguousarray(c))
+            heights.append(H)
+            widths.append(W)
+        return arrs, heights, widths, sub, ri
+
+    def debug_jpeg_encode_scan(self, coefs, sizes, subsampling="4:2:0", restart_interval=0):
+        """The stages behind the first alone (tests): the entropy-coded, stuffed scans (``bytes``, RSTn markers included, no
+        header and no EOI) of the caller's coefficients.  ``coefs``: int16 arrays (total_blocks, 64) in the layout
+        ``debug_jpeg_encode_blocks`` returns; ``sizes``: their (H, W).  A DC outside -1024..1023 or an AC term outside
+        -1023..1023 is a ValueError that names the image."""
+        arrs, heights, widths, sub, ri = self._jpeg_scan_args(coefs, sizes, subsampling, restart_interval)
+        N = len(arrs)
+        if N == 0:
+            return []
+        bounds = [self.jpeg_encode_bound(heights[i], widths[i], subsampling, ri) for i in range(N)]
+        off = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(bounds, out=off[1:])
+        buf = np.zeros(int(off[-1]), dtype=np.uint8)
+        cp = (C.c_void_p * N)(*[a.ctypes.data for a in arrs])
+        outs = (C.c_void_p * N)(*[buf.ctypes.data + int(off[i]) for i in range(N)])
+        caps = (C.c_size_t * N)(*bounds)
+        lens = (C.c_size_t * N)()
+        self._order()
+        self._call("lwp_debug_jpeg_encode_scan", N, cp, (C.c_int * N)(*heights), (C.c_int * N)(*widths), sub, ri, outs, caps, lens)
+        return [buf[int(off[i]):int(off[i]) + lens[i]].tobytes() for i in range(N)]
+
     def stage_losses(self, outs, keypoint_maps, paf_maps, mask, batch_size=None, time_iters=0):
         """train.py:92-97's per-stage sums: ``outs`` is the list net(x) returned (cuda tensors; an entry may be None),
         ``keypoint_maps`` / ``paf_maps`` the targets, ``mask`` one (N, h, w) cuda tensor broadcast over the channels.

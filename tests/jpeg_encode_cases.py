@@ -141,9 +141,293 @@ def forward_blocks(bgr, sampling, quality, mutant=None):
     return g, np.concatenate(out).astype(np.int16), qt
 
 
-def scan_of(coef, g, restart_interval=0):
-    """The entropy-coded scan of such coefficients with Annex K's Huffman tables: jpeg_entropy_cases' coder."""
-    return jec.encode_scan(coef, g, jec.standard_tables(), [0, 1, 1], [0, 1, 1], restart_interval)
+def scan_of(coef, g, restart_interval=0, mutant=None, mutant_arg=None):
+    """The entropy-coded scan of such coefficients with Annex K's Huffman tables: jpeg_entropy_cases' coder (and its mutants)."""
+    return jec.encode_scan(coef, g, jec.standard_tables(), [0, 1, 1], [0, 1, 1], restart_interval, mutant, mutant_arg)
+
+
+# ---------------------------------------------------------------------------------------------- what a set of coefficients reaches
+ALL_AC = frozenset([0x00, 0xF0] + [(r << 4) | s for r in range(16) for s in range(1, 11)])      # Annex K's 162 symbols
+ALL_DC = frozenset(range(12))
+WORST_BLOCK_BITS = 1658        # luma: 9 + 11 bits of a category-11 DC difference, 63 times a 16-bit code and 10 magnitude bits
+
+
+def block_symbols(block, pred):
+    """(DC category, [AC symbols]) of one block (64 ints, natural order) as jchuff.c's encode_one_block emits them."""
+    ac, run = [], 0
+    for k in range(1, 64):
+        v = block[jec.ZZ[k]]
+        if v == 0:
+            run += 1
+            continue
+        ac += [0xF0] * (run >> 4)
+        ac.append(((run & 15) << 4) | abs(v).bit_length())
+        run = 0
+    if run:
+        ac.append(0x00)
+    return abs(block[0] - pred).bit_length(), ac
+
+
+def split_scan(scan):
+    """The un-stuffed bytes of every restart interval of a stuffed scan, and the RSTn numbers between them."""
+    parts, cur, rst, i = [], bytearray(), [], 0
+    while i < len(scan):
+        b = scan[i]
+        if b == 0xFF:
+            nxt = scan[i + 1]
+            if nxt == 0:
+                cur.append(0xFF)
+            else:
+                assert 0xD0 <= nxt <= 0xD7, "marker %02x inside a scan" % nxt
+                parts.append(bytes(cur))
+                cur = bytearray()
+                rst.append(nxt - 0xD0)
+            i += 2
+            continue
+        cur.append(b)
+        i += 1
+    parts.append(bytes(cur))
+    return parts, rst
+
+
+def coverage(coef, g, restart=0):
+    """What the entropy stages see of these coefficients, from the coefficients, Annex K's code LENGTHS and scan_of's bytes alone
+    (never from the library):
+      dc, ac            per table (0 luma, 1 chroma): the DC categories coded and the AC symbols emitted (EOB 0x00, ZRL 0xF0)
+      max_zrl           the most ZRLs in one gap
+      block_bits        the bits of every block, in stream order
+      starts            the stream indices at which a restart interval starts (0 first)
+      start_bytes       their byte offsets in the un-stuffed scan
+      length            the un-stuffed length
+      ff                the un-stuffed offsets of the 0xFF bytes; ff_mod32: those modulo 32
+      ff_ends           the intervals, the last excepted, whose last byte is 0xFF; ff_last: the scan's last byte is 0xFF
+    The two views are held against each other: every interval takes the whole bytes its blocks' bits need."""
+    blocks = np.asarray(coef).astype(np.int64).tolist()
+    order, comp = jec.stream_order(g)
+    per_mcu = len(order) // (g["mcus_x"] * g["mcus_y"])
+    tables = jec.standard_tables()
+    dc_len = [{s: l for s, (_, l) in jec._codes(*tables[(0, t)]).items()} for t in (0, 1)]
+    ac_len = [{s: l for s, (_, l) in jec._codes(*tables[(1, t)]).items()} for t in (0, 1)]
+    out = {"dc": [set(), set()], "ac": [set(), set()], "max_zrl": 0, "block_bits": [], "starts": []}
+    pred = [0, 0, 0]
+    for n, (blk, c) in enumerate(zip(order, comp)):
+        if n == 0 or (restart and n % (per_mcu * restart) == 0):
+            out["starts"].append(n)
+            pred = [0, 0, 0]
+        t = min(c, 1)
+        cat, syms = block_symbols(blocks[blk], pred[c])
+        pred[c] = blocks[blk][0]
+        out["dc"][t].add(cat)
+        out["ac"][t].update(syms)
+        bits, zrl = dc_len[t][cat] + cat, 0
+        for s in syms:
+            bits += ac_len[t][s] + (s & 15)
+            zrl = zrl + 1 if s == 0xF0 else 0
+            out["max_zrl"] = max(out["max_zrl"], zrl)
+        out["block_bits"].append(bits)
+    parts, rst = split_scan(scan_of(coef, g, restart))
+    assert len(parts) == len(out["starts"]) and rst == [k & 7 for k in range(len(parts) - 1)]
+    ends = out["starts"][1:] + [len(order)]
+    for part, a, b in zip(parts, out["starts"], ends):
+        assert len(part) == (sum(out["block_bits"][a:b]) + 7) // 8
+    flat = b"".join(parts)
+    out["start_bytes"] = [0] + np.cumsum([len(p) for p in parts[:-1]]).astype(int).tolist()
+    out["length"] = len(flat)
+    out["ff"] = [i for i, b in enumerate(flat) if b == 0xFF]
+    out["ff_mod32"] = sorted({i % 32 for i in out["ff"]})
+    out["ff_ends"] = [k for k, p in enumerate(parts[:-1]) if p[-1] == 0xFF]
+    out["ff_last"] = flat[-1] == 0xFF
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- coefficient cases for stages B .. F
+def _stream_of(g, c):
+    """The plane-order block indices of component c in the order the scan visits them."""
+    order, comp = jec.stream_order(g)
+    return [b for b, cc in zip(order, comp) if cc == c]
+
+
+def _place_symbols(coef, blocks, symbols):
+    """Writes AC run / size symbols, one behind the other in zig-zag order, into the given (zeroed) blocks; a symbol that no
+    longer fits the block opens the next.  Returns the blocks used."""
+    used, k = 0, 1
+    for sym in sorted(symbols):
+        run, size = sym >> 4, sym & 15
+        if k + run > 63:
+            used, k = used + 1, 1
+        coef[blocks[used], jec.ZZ[k + run]] = (1 << size) - 1 if (sym >> 4) & 1 else -(1 << (size - 1))
+        k += run + 1
+    return used + 1
+
+
+DC_LADDER = [0, 0, 1, -1, 3, -5, 11, -21, 43, -85, 171, -341, 683]      # the differences: categories 0, 1, 2 .. 11 in turn
+
+
+def alphabet_case(sampling, width, height, seeds):
+    """Random coefficients of several densities (DC differences up to category 11), then hand-placed blocks for what the meter
+    says the random part leaves out: every one of Annex K's 160 run / size symbols, EOB and ZRL in both AC tables, and a ladder
+    of DC differences through the categories 0 .. 11 at the end of the luma and of the Cb stream."""
+    g = geometry(width, height, sampling)
+    parts = [jec.random_coefficients(seed, g, density=d, dc=1023) for seed, d in zip(seeds, (1.0, 0.5, 0.2, 0.05, 0.02))]
+    coef = parts[0].copy()
+    for k, p in enumerate(parts):
+        coef[k::len(parts)] = p[k::len(parts)]
+    reserve = 28                                       # 160 symbols take 10 * (1 + 2 + .. + 16) = 1360 of 63 places a block
+    for c in (0, 1):
+        stream = _stream_of(g, c)
+        assert len(stream) >= reserve + len(DC_LADDER)
+        coef[stream[:reserve], 1:] = 0
+    have = coverage(coef, g)
+    for c in (0, 1):
+        stream = _stream_of(g, c)
+        missing = [s for s in ALL_AC - have["ac"][c] if s & 15]
+        assert _place_symbols(coef, stream[:reserve - 1], missing) <= reserve - 1
+        coef[stream[reserve - 1], 63] = 1             # a gap of 62 zeros: three ZRLs in a row
+        coef[stream[-len(DC_LADDER):], 0] = DC_LADDER
+    return coef, g
+
+
+def worst_case(sampling, width, height, restart, all_ones, seed=0):
+    """Every block at the luma maximum of WORST_BLOCK_BITS: 63 AC terms of size 10 at run 0 and a DC that alternates between
+    -1024 and 1023 along each component's stream, restarting at every interval, so that every difference has category 11.
+    ``all_ones``: every magnitude 1023, whose bits are ten ones (the most stuffing); else random magnitudes and signs."""
+    g = geometry(width, height, sampling)
+    rng = np.random.RandomState(seed)
+    n = g["total_blocks"]
+    coef = np.full((n, 64), 1023, dtype=np.int64) if all_ones else rng.randint(512, 1024, (n, 64)) * rng.choice([-1, 1], (n, 64))
+    order, comp = jec.stream_order(g)
+    per_mcu = len(order) // (g["mcus_x"] * g["mcus_y"])
+    pred = [0, 0, 0]
+    for i, (b, c) in enumerate(zip(order, comp)):
+        if restart and i % (per_mcu * restart) == 0:
+            pred = [0, 0, 0]
+        coef[b, 0] = pred[c] = 1023 if pred[c] == -1024 else -1024
+    return coef.astype(np.int16), g
+
+
+def sparse_case(sampling, width, height, seed):
+    """Mixed content at picture-like densities: what the seam cases carry across their tiles."""
+    g = geometry(width, height, sampling)
+    a = jec.random_coefficients(seed, g, density=0.12, sizes=(1, 7), dc=600)
+    b = jec.random_coefficients(seed + 1, g, density=0.6, sizes=(1, 10), dc=1023)
+    a[5::7] = b[5::7]
+    return a, g
+
+
+def _search(what, tries, build, accept):
+    for seed in range(tries):
+        coef, g, restart = build(seed)
+        if accept(coverage(coef, g, restart)):
+            return coef, g, restart
+    raise AssertionError("no %s among %d seeds" % (what, tries))
+
+
+def ends_in_ff_case(width, restart):
+    """A width x 8 4:4:4 image whose scan ends FF 00: the last block (Cr of the last MCU) has a coefficient 63, so it ends in
+    magnitude bits and not in EOB; the search runs over the DCs and that coefficient.  With restart 1 an interior interval must
+    end in 0xFF too."""
+    def build(seed):
+        g = geometry(width, 8, "4:4:4")
+        rng = np.random.RandomState(1000 + seed)
+        coef = np.zeros((g["total_blocks"], 64), dtype=np.int16)
+        coef[:, 0] = rng.randint(-1023, 1024, g["total_blocks"])
+        coef[2 * g["mcus_x"]:, 63] = rng.randint(1, 1024, g["mcus_x"])          # every Cr block
+        return coef, g, restart
+    return _search("scan that ends in 0xFF", 200, build, lambda m: m["ff_last"] and (not restart or m["ff_ends"]))
+
+
+def aligned_start_case():
+    """A 48x8 4:4:4 image with restart 1 in which an interval behind the first starts at an un-stuffed offset that is a
+    multiple of 32: on the first byte of a chunk of the stuffing passes."""
+    def build(seed):
+        g = geometry(48, 8, "4:4:4")
+        return jec.random_coefficients(2000 + seed, g, density=0.3, sizes=(1, 8), dc=800), g, 1
+    return _search("interval start on a chunk boundary", 200, build, lambda m: any(b % 32 == 0 for b in m["start_bytes"][1:]))
+
+
+_COEF_CASES = None
+
+
+def coefficient_cases():
+    """{name: dict(coef, g, size (H, W), sampling, restart)}: what lwp_debug_jpeg_encode_scan is handed.  Built once."""
+    global _COEF_CASES
+    if _COEF_CASES is not None:
+        return _COEF_CASES
+    out = {}
+
+    def add(name, coef, g, sampling, width, height, restart):
+        assert coef.dtype == np.int16 and coef.shape == (g["total_blocks"], 64), name
+        out[name] = {"coef": np.ascontiguousarray(coef), "g": g, "size": (height, width), "sampling": sampling, "restart": restart}
+
+    for sampling, (w, h), seeds in (("4:2:0", (128, 96), (1, 2, 3, 4, 5)), ("4:4:4", (80, 64), (6, 7, 8, 9, 10))):
+        coef, g = alphabet_case(sampling, w, h, seeds)
+        add("alphabet_" + SHORT[sampling], coef, g, sampling, w, h, 0)
+    for sampling, (w, h) in (("4:2:0", (16, 16)), ("4:4:4", (24, 8))):
+        for restart in (0, 1):
+            for kind, all_ones in (("random", False), ("ones", True)):
+                coef, g = worst_case(sampling, w, h, restart, all_ones, seed=restart)
+                add("worst_%s_%s_r%d" % (kind, SHORT[sampling], restart), coef, g, sampling, w, h, restart)
+    def seam(sampling, w, h, restart, at, seed0):
+        """The interval in front of block ``at`` must leave pad bits, or a lost byte alignment there would not show."""
+        def build(seed):
+            return sparse_case(sampling, w, h, seed0 + 100 * seed) + (restart,)
+
+        def accept(m):
+            k = m["starts"].index(at)
+            return sum(m["block_bits"][m["starts"][k - 1]:at]) % 8 != 0
+        coef, g, _ = _search("seam with pad bits", 20, build, accept)
+        add("tile_seam_%s_r%d" % (SHORT[sampling], restart), coef, g, sampling, w, h, restart)
+
+    for restart in (1, 8, 64):                         # 72 MCUs of 4 blocks: intervals of 4, 32 and 256 blocks
+        seam("4:2:2", 144, 64, restart, 256, 40 + restart)
+    seam("4:2:0", 256, 144, 128, 768, 50)              # 144 MCUs of 6 blocks: the second interval starts at block 768 = 3 * 256
+    for name, (coef, g, restart), w in (("ends_in_ff", ends_in_ff_case(8, 0), 8), ("ends_in_ff_r1", ends_in_ff_case(24, 1), 24),
+                                        ("aligned_start_r1", aligned_start_case(), 48)):
+        add(name, coef, g, "4:4:4", w, 8, restart)
+    for sampling, (w, h) in (("4:4:4", (72, 64)), ("4:2:0", (112, 80))):
+        g = geometry(w, h, sampling)
+        add("empty_codes_" + SHORT[sampling], np.zeros((g["total_blocks"], 64), dtype=np.int16), g, sampling, w, h, 0)
+    _COEF_CASES = out
+    return out
+
+
+_COEF_SCANS = {}
+
+
+def coefficient_scan(name):
+    """scan_of of a coefficient case, computed once per process."""
+    if name not in _COEF_SCANS:
+        c = coefficient_cases()[name]
+        _COEF_SCANS[name] = scan_of(c["coef"], c["g"], c["restart"])
+    return _COEF_SCANS[name]
+
+
+MANY_SIZES = ((1, 1), (7, 7), (8, 9), (17, 23))       # (H, W)
+
+
+def many_frames(n=300):
+    """n small BGR frames of sizes cycling through MANY_SIZES: noise, a ramp with a little noise, and flat colour in turn."""
+    rng = np.random.RandomState(77)
+    out = []
+    for i in range(n):
+        h, w = MANY_SIZES[i % len(MANY_SIZES)]
+        kind = (i // len(MANY_SIZES)) % 3
+        if kind == 0:
+            f = rng.randint(0, 256, (h, w, 3))
+        elif kind == 1:
+            y, x = np.mgrid[0:h, 0:w]
+            f = ((3 * x + 2 * y + i) % 200 + 20)[:, :, None] + rng.randint(-4, 5, (h, w, 3))
+        else:
+            f = np.broadcast_to(rng.randint(0, 256, 3), (h, w, 3))
+        out.append(np.ascontiguousarray(f, dtype=np.uint8))
+    return out
+
+
+def limit_frame(height, width):
+    """Smooth content for a frame at the dimension limit: a slow ramp along the long side."""
+    y, x = np.mgrid[0:height, 0:width]
+    v = ((x + y) // 97) % 256
+    return np.ascontiguousarray(np.stack([v, 255 - v, (v * 3) % 256], axis=2), dtype=np.uint8)
 
 
 # ---------------------------------------------------------------------------------------------- fixtures

@@ -88,14 +88,30 @@ def stream_order(g):
     return order, comp
 
 
-def encode_scan(coef, g, tables, td, ta, restart_interval=0):
+SCAN_MUTANTS = ("dc11_as_dc10", "ac_code", "no_align", "final_ff_unstuffed", "zrl_at_15")
+
+
+def encode_scan(coef, g, tables, td, ta, restart_interval=0, mutant=None, mutant_arg=None):
     """The scan of coefficients in the project's layout (int (total_blocks, 64), natural order, plane order, DC prediction
-    undone): stuffed bytes with RSTn markers, each interval padded with one-bits."""
+    undone): stuffed bytes with RSTn markers, each interval padded with one-bits.
+
+    ``mutant`` builds a deliberately wrong coder (test_jpeg_encode_host.py shows that its named case sees each): DC category 11
+    coded as category 10; the last bit of AC symbol ``mutant_arg``'s code flipped; the interval that starts at stream index
+    ``mutant_arg`` not byte-aligned (the bits left over go on behind the marker); a final 0xFF without its stuffing zero; ZRL
+    for a run of 15 already."""
+    assert mutant is None or mutant in SCAN_MUTANTS, mutant
     coef = np.asarray(coef).astype(np.int64).tolist()
     order, comp = stream_order(g)
     per_mcu = len(order) // (g["mcus_x"] * g["mcus_y"])
     dc = [_codes(*tables[(0, td[c])]) for c in range(g["components"])]
     ac = [_codes(*tables[(1, ta[c])]) for c in range(g["components"])]
+    if mutant == "dc11_as_dc10":
+        for d in dc:
+            d[11] = d[10]
+    if mutant == "ac_code":
+        for a in ac:
+            a[mutant_arg] = (a[mutant_arg][0] ^ 1, a[mutant_arg][1])
+    longest_run = 14 if mutant == "zrl_at_15" else 15
     out = bytearray()
     acc, nbits = 0, 0
     pred = [0] * g["components"]
@@ -124,7 +140,11 @@ def encode_scan(coef, g, tables, td, ta, restart_interval=0):
 
     for n, (blk, c) in enumerate(zip(order, comp)):
         if restart_interval and n and n % (per_mcu * restart_interval) == 0:
+            keep = nbits % 8 if mutant == "no_align" and n == mutant_arg else 0
+            left = acc & ((1 << keep) - 1)
+            acc, nbits = acc >> keep, nbits - keep
             flush()
+            acc, nbits = left, keep
             out += bytes([0xFF, 0xD0 + rst])
             rst = (rst + 1) & 7
             pred = [0] * g["components"]
@@ -140,9 +160,9 @@ def encode_scan(coef, g, tables, td, ta, restart_interval=0):
             if v == 0:
                 run += 1
                 continue
-            while run > 15:
+            while run > longest_run:
                 put(*ac[c][0xF0])
-                run -= 16
+                run = max(run - 16, 0)
             s, bits = magnitude(v)
             put(*ac[c][(run << 4) | s])
             put(bits, s)
@@ -150,6 +170,8 @@ def encode_scan(coef, g, tables, td, ta, restart_interval=0):
         if last < 63:
             put(*ac[c][0x00])
     flush()
+    if mutant == "final_ff_unstuffed" and out[-2:] == b"\xff\x00":
+        del out[-1]
     return bytes(out)
 
 

@@ -315,3 +315,209 @@ def test_argument_checks_raise_without_a_gpu(tmp_path):
         demo._overlay_options({"device": True, "colour": (1, 2, 3)})
     assert demo._overlay_options({"device": True, "boxes": False}) == ({"boxes": False}, True)
     assert demo._overlay_options(True) == ({}, False)
+
+
+# ---------------------------------------------------------------------------------------------- the entropy stages' cases
+# Conditions on the INPUTS of test_gpu_jpeg_encode_edges.py, read with the meter (jpeg_encode_cases.coverage) from the
+# coefficients and the reference coder alone.  A case that misses its condition fails here; nothing is skipped.
+CASES = jen.coefficient_cases()
+EDGES = sorted(n for n in NAMES if n.startswith(("tiles_", "seam_")))
+BLOCK_BYTES = 208                                                   # kJpegEncBlockBytes (csrc/jpeg_encode_host.h)
+
+_METERS = {}
+
+
+def meter(name):
+    if name not in _METERS:
+        if name in CASES:
+            c = CASES[name]
+            _METERS[name] = jen.coverage(c["coef"], c["g"], c["restart"])
+        else:
+            g, coef, _ = jen.restated(name)
+            _METERS[name] = jen.coverage(coef, g, FIX[name]["restart"])
+    return _METERS[name]
+
+
+def reached(names):
+    """The union over these cases or fixtures: (DC categories, AC symbols) per table."""
+    dc, ac = [set(), set()], [set(), set()]
+    for n in names:
+        for t in (0, 1):
+            dc[t] |= meter(n)["dc"][t]
+            ac[t] |= meter(n)["ac"][t]
+    return dc, ac
+
+
+def test_the_edge_fixtures_are_the_ones_the_tool_writes():
+    assert EDGES == sorted(["tiles_99x37_%s" % s for s in ("444", "422", "420")] + ["seam_144x64_%s" % s for s in ("444", "422", "420")])
+    for n in EDGES:
+        f = FIX[n]
+        assert (f["quality"], f["restart"]) == ((100, 0) if n.startswith("tiles") else (75, 1)), n
+    for s in ("444", "422", "420"):                                # DC categories 10 and 11 from pixels, in both tables
+        m = meter("tiles_99x37_" + s)
+        assert {10, 11} <= m["dc"][0] and {10, 11} <= m["dc"][1], (s, m["dc"])
+    m = meter("seam_144x64_422")                                    # the tile seam through the whole pixel path
+    assert ENC_GROUP in m["starts"] and len(m["starts"]) == 72
+
+
+def test_what_the_older_fixtures_leave_to_the_coefficient_cases():
+    """The gap the coefficient cases close, measured: without the edge fixtures no DC category above 9 in either table, 107
+    and 94 of the 162 AC symbols (EOB and ZRL among them), no restart interval that starts on a tile seam of the offset scan,
+    and no scan that ends in 0xFF."""
+    old = [n for n in NAMES if n not in EDGES]
+    assert len(old) == 59
+    dc, ac = reached(old)
+    assert max(dc[0]) == 9 and max(dc[1]) == 9
+    assert (len(ac[0]), len(ac[1])) == (107, 94)
+    assert not any(s and s % ENC_GROUP == 0 for n in old for s in meter(n)["starts"])
+    assert not any(meter(n)["ff_last"] for n in old)
+    assert sum(len(meter(n)["ff_ends"]) for n in old) == 14
+    assert sum(b % ENC_CHUNK == 0 for n in old for b in meter(n)["start_bytes"][1:]) == 3
+
+
+def test_alphabet_emits_every_symbol_of_all_four_tables():
+    for name in ("alphabet_420", "alphabet_444"):
+        m = meter(name)
+        for t in (0, 1):
+            assert m["ac"][t] == jen.ALL_AC and len(m["ac"][t]) == 162, (name, t, sorted(jen.ALL_AC - m["ac"][t]))
+            assert m["dc"][t] == jen.ALL_DC, (name, t)
+        assert m["max_zrl"] == 3                                    # a gap of 48 or more zeros
+        assert 200 <= CASES[name]["g"]["total_blocks"] <= 400
+    assert CASES["alphabet_420"]["sampling"] == "4:2:0" and CASES["alphabet_444"]["sampling"] == "4:4:4"
+
+
+WORST = sorted(n for n in CASES if n.startswith("worst_"))
+
+
+def test_worst_drives_every_luma_block_to_the_bound():
+    assert len(WORST) == 8 and {(CASES[n]["sampling"], CASES[n]["size"], CASES[n]["restart"]) for n in WORST} == {
+        ("4:2:0", (16, 16), 0), ("4:2:0", (16, 16), 1), ("4:4:4", (8, 24), 0), ("4:4:4", (8, 24), 1)}
+    assert jen.WORST_BLOCK_BITS == 9 + 11 + 63 * (16 + 10) == 1658 <= 8 * BLOCK_BYTES
+    for name in WORST:
+        c, m = CASES[name], meter(name)
+        _, comp = jen.jec.stream_order(c["g"])
+        luma = [b for b, cc in zip(m["block_bits"], comp) if cc == 0]
+        assert luma and set(luma) == {jen.WORST_BLOCK_BITS}, name
+        assert max(m["block_bits"]) == jen.WORST_BLOCK_BITS, name   # chroma's code of run 0, size 10 is shorter: no block takes more
+        assert m["dc"][0] == {11} and m["dc"][1] == {11} and m["ac"][0] == {0x0A}, name
+        coef = c["coef"]
+        assert coef[:, 0].min() == -1024 and coef[:, 0].max() <= 1023 and np.abs(coef[:, 1:].astype(np.int64)).max() <= 1023
+        assert np.abs(coef[:, 1:].astype(np.int64)).min() >= 512
+        # the un-stuffed scan inside what the planner gives it, the stuffed scan inside the bound of the API
+        H, W = c["size"]
+        intervals = len(m["starts"])
+        assert m["length"] <= c["g"]["total_blocks"] * BLOCK_BYTES + intervals, name
+        assert m["length"] >= c["g"]["total_blocks"] * 176, name    # and near it: 1408 bits is what a chroma block takes here
+        header = Engine.debug_jpeg_encode_header(H, W, 75, c["sampling"], c["restart"])
+        scan = jen.coefficient_scan(name)
+        assert len(header) + len(scan) + 2 <= Engine.jpeg_encode_bound(H, W, c["sampling"], c["restart"]), name
+        assert len(scan) <= Engine.jpeg_encode_bound(H, W, c["sampling"], c["restart"]) - 640 - 2, name
+    ones = meter("worst_ones_444_r1")
+    assert len(ones["ff"]) > ones["length"] // 2                    # all-ones magnitudes: more than every second byte is stuffed
+
+
+def test_tile_seam_starts_an_interval_on_the_first_lane_of_a_later_tile():
+    for restart, blocks in ((1, 4), (8, 32), (64, 256)):
+        c, m = CASES["tile_seam_422_r%d" % restart], meter("tile_seam_422_r%d" % restart)
+        assert (c["sampling"], c["size"], c["g"]["total_blocks"]) == ("4:2:2", (64, 144), 288)
+        assert m["starts"] == list(range(0, 288, blocks)) and ENC_GROUP in m["starts"]
+        assert sum(m["block_bits"][ENC_GROUP - blocks:ENC_GROUP]) % 8          # pad bits in front of the seam: the alignment does something
+    c, m = CASES["tile_seam_420_r128"], meter("tile_seam_420_r128")
+    assert c["sampling"] == "4:2:0" and c["g"]["total_blocks"] > 768 and m["starts"] == [0, 768] and 768 == 3 * ENC_GROUP
+    assert m["length"] > ENC_GROUP * ENC_CHUNK                      # and more than one tile of the stuffing passes
+
+
+def test_ends_in_ff_aligned_start_and_empty_codes():
+    c, m = CASES["ends_in_ff"], meter("ends_in_ff")
+    assert (c["size"], c["sampling"], c["restart"]) == ((8, 8), "4:4:4", 0)
+    assert m["ff_last"] and jen.coefficient_scan("ends_in_ff")[-2:] == b"\xff\x00"
+    m = meter("ends_in_ff_r1")
+    assert CASES["ends_in_ff_r1"]["restart"] == 1 and m["ff_last"] and m["ff_ends"] and len(m["starts"]) == 3
+    scan = jen.coefficient_scan("ends_in_ff_r1")
+    assert scan[-2:] == b"\xff\x00" and (b"\xff\x00\xff\xd0" in scan or b"\xff\x00\xff\xd1" in scan)
+    m = meter("aligned_start_r1")
+    assert any(b % ENC_CHUNK == 0 for b in m["start_bytes"][1:])
+    for name in ("empty_codes_444", "empty_codes_420"):
+        c, m = CASES[name], meter(name)
+        assert not c["coef"].any() and c["g"]["total_blocks"] > 200
+        _, comp = jen.jec.stream_order(c["g"])
+        assert all(b == (6 if cc == 0 else 4) for b, cc in zip(m["block_bits"], comp))      # DC category 0 and EOB
+        offsets = np.cumsum([0] + m["block_bits"][:-1])
+        assert set(int(o) % 8 for o in offsets) == set(range(0, 8, 2)) and not m["ff"]      # every even bit offset; words shared by 5 blocks
+
+
+def test_many_and_the_limit_frames_are_what_the_issue_lists():
+    frames = jen.many_frames()
+    assert len(frames) == 300 and [f.shape[:2] for f in frames[:4]] == [(1, 1), (7, 7), (8, 9), (17, 23)]
+    assert all(f.shape[:2] == jen.MANY_SIZES[i % 4] and f.dtype == np.uint8 for i, f in enumerate(frames))
+    assert len({f.tobytes() for f in frames[3::4]}) == 75           # mixed content: no two of the largest alike
+    assert jen.limit_frame(1, 65535).shape == (1, 65535, 3) and jen.limit_frame(65535, 1).shape == (65535, 1, 3)
+
+
+def only_alphabet_reaches():
+    """The lowest luma AC symbol that the alphabet case emits and no pixel fixture does."""
+    _, ac = reached(NAMES)
+    return min(meter("alphabet_420")["ac"][0] - ac[0])
+
+
+def mutant_scan(name, mutant, arg=None):
+    if name in CASES:
+        c = CASES[name]
+        return jen.scan_of(c["coef"], c["g"], c["restart"], mutant, arg), jen.coefficient_scan(name)
+    g, coef, _ = jen.restated(name)
+    return jen.scan_of(coef, g, FIX[name]["restart"], mutant, arg), jen.jec.scan_bytes(FIX[name]["jpeg"])
+
+
+@pytest.mark.parametrize("mutant,arg,name", [
+    ("dc11_as_dc10", None, "tiles_99x37_444"), ("dc11_as_dc10", None, "tiles_99x37_422"), ("dc11_as_dc10", None, "tiles_99x37_420"),
+    ("dc11_as_dc10", None, "alphabet_420"), ("dc11_as_dc10", None, "alphabet_444"),
+    ("ac_code", "only_alphabet", "alphabet_420"), ("ac_code", "only_alphabet", "alphabet_444"),
+    ("no_align", 256, "tile_seam_422_r1"), ("no_align", 256, "tile_seam_422_r8"), ("no_align", 256, "tile_seam_422_r64"),
+    ("no_align", 768, "tile_seam_420_r128"), ("no_align", 256, "seam_144x64_422"),
+    ("final_ff_unstuffed", None, "ends_in_ff"), ("final_ff_unstuffed", None, "ends_in_ff_r1"),
+    ("zrl_at_15", None, "alphabet_420"), ("zrl_at_15", None, "alphabet_444")])
+def test_a_mutant_of_the_scan_coder_changes_the_bytes_of_its_case(mutant, arg, name):
+    if arg == "only_alphabet":
+        arg = only_alphabet_reaches()
+        assert arg in jen.ALL_AC
+    got, want = mutant_scan(name, mutant, arg)
+    assert jen.scan_of(*((CASES[name]["coef"], CASES[name]["g"], CASES[name]["restart"]) if name in CASES else
+                         (jen.restated(name)[1], jen.restated(name)[0], FIX[name]["restart"]))) == want      # the coder itself is right
+    assert got != want
+
+
+def test_the_older_fixtures_do_not_see_those_mutants():
+    """Why the cases above are needed: the 59 older pixel fixtures pass a coder with a wrong DC category 11 or a wrong code
+    for the symbol only the alphabet case reaches."""
+    sym = only_alphabet_reaches()
+    for n in [n for n in NAMES if n not in EDGES][::6]:
+        assert mutant_scan(n, "dc11_as_dc10")[0] == mutant_scan(n, "ac_code", sym)[0] == jen.jec.scan_bytes(FIX[n]["jpeg"]), n
+
+
+def test_the_debug_scan_checks_its_arguments_without_a_gpu():
+    g = jen.geometry(23, 17, "4:2:0")
+    good = np.zeros((g["total_blocks"], 64), np.int16)
+    arrs, heights, widths, sub, ri = Engine._jpeg_scan_args([good, good[:6]], [(17, 23), (1, 1)], "4:2:0", 5)
+    assert (heights, widths, sub, ri) == ([17, 1], [23, 1], 2, 5) and arrs[0].flags.c_contiguous
+    assert Engine._jpeg_scan_args([], [], "4:4:4", 0)[0] == []
+    with pytest.raises(ValueError, match="2 sizes for 1 coefficient"):
+        Engine._jpeg_scan_args([good], [(17, 23), (17, 23)], "4:2:0", 0)
+    for bad in (good.astype(np.int32), good.astype(np.float32), good.tolist(), None):
+        with pytest.raises(ValueError, match="int16"):
+            Engine._jpeg_scan_args([bad], [(17, 23)], "4:2:0", 0)
+    for bad in (good[:-1], good.reshape(-1), good.reshape(-1, 32), good[:, :63]):
+        with pytest.raises(ValueError, match=r"must be \(%d, 64\)" % g["total_blocks"]):
+            Engine._jpeg_scan_args([bad], [(17, 23)], "4:2:0", 0)
+    with pytest.raises(ValueError, match=r"must be \(27, 64\)"):     # the same blocks at another sampling
+        Engine._jpeg_scan_args([good], [(17, 23)], "4:4:4", 0)
+    with pytest.raises(ValueError, match="1..65535"):
+        Engine._jpeg_scan_args([good], [(0, 23)], "4:2:0", 0)
+    with pytest.raises(ValueError, match=r"\(H, W\)"):
+        Engine._jpeg_scan_args([good], [(17, 23, 3)], "4:2:0", 0)
+    with pytest.raises(ValueError, match="subsampling"):
+        Engine._jpeg_scan_args([good], [(17, 23)], "420", 0)
+    with pytest.raises(ValueError, match="restart_interval"):
+        Engine._jpeg_scan_args([good], [(17, 23)], "4:2:0", -1)
+    # the library's own checks in front of the device: a null handle and null arrays are refused
+    L = _lib.lib()
+    assert L.lwp_debug_jpeg_encode_scan(None, 1, None, None, None, 2, 0, None, None, None) == _lib.LWP_ERR_ARG

@@ -1,9 +1,10 @@
-"""Writes the JPEG ENCODE fixtures of tests/golden/encjpeg_cases.npz: small BGR frames and the file Pillow (libjpeg-turbo's
+"""Writes the JPEG ENCODE fixtures of tests/golden/encjpeg_edges.npz (and, with ``--cases``, of encjpeg_cases.npz and
+encjpeg_tables.npz, which are otherwise left as they are): small BGR frames and the file Pillow (libjpeg-turbo's
 default compression path: 16-bit fixed-point colour conversion, h2v1 / h2v2 box down-sampling, slow-but-accurate integer forward
 DCT, Annex K's Huffman tables) writes of each, which is what the tests hold the restatement (tests/jpeg_encode_cases.py) and the
 library to, byte for byte.  Needs Pillow; the tests do not.
 
-    python tools/make_jpeg_encode_golden.py
+    python tools/make_jpeg_encode_golden.py [--cases]
 
 Every fixture is checked before it is written: the restatement must give the coefficients jpeg_cases.decode_blocks reads from
 Pillow's file, none differing.  The table of all hundred qualities (tests/golden/encjpeg_tables.npz) is read from Pillow's files
@@ -80,9 +81,32 @@ def cases():
     return out
 
 
-def main():
+TILE_COLOURS = [(0, 0, 0), (255, 255, 255), (255, 0, 0), (0, 255, 255), (0, 0, 255), (255, 255, 0)]      # BGR: black, white, blue, yellow, red, cyan
+
+
+def tiles(w, h):
+    """16 x 16 tiles of saturated colours in turn: at quality 100 the DC steps between neighbouring blocks of all three
+    components reach the categories 10 and 11."""
+    y, x = np.mgrid[0:h, 0:w]
+    index = ((y // 16) * -(-w // 16) + x // 16) % len(TILE_COLOURS)
+    return np.array(TILE_COLOURS, dtype=np.uint8)[index]
+
+
+def edge_cases():
+    """What stages B .. F of the encoder see too rarely from the cases above: DC categories 10 and 11 in both tables, and a
+    restart interval that starts on the first lane of the offset scan's second tile (4:2:2, 144 x 64, restart 1: 72 intervals
+    of 4 blocks, one of which starts at block 256).  144 x 64 comes in all three samplings, as every size but the long one does."""
+    out = {}
+    for k, sampling in enumerate(jen.SAMPLINGS):
+        s = jen.SHORT[sampling]
+        out["tiles_99x37_%s" % s] = (tiles(99, 37), 100, sampling, 0)
+        out["seam_144x64_%s" % s] = (noise(144, 64, 400 + k), 75, sampling, 1)
+    return out
+
+
+def write(path, which):
     arrays, coefs, differing = {}, 0, 0
-    for name, (bgr, quality, sampling, restart) in cases().items():
+    for name, (bgr, quality, sampling, restart) in which.items():
         data = pillow_file(bgr, quality, sampling, restart)
         hd, want, qt = jpeg_cases.decode_blocks(data)
         g, got, qt_got = jen.forward_blocks(bgr, sampling, quality)
@@ -95,9 +119,15 @@ def main():
         arrays["jpeg/" + name] = np.frombuffer(data, dtype=np.uint8)
         arrays["bgr/" + name] = bgr
         arrays["opts/" + name] = np.array([quality, jen.PILLOW[sampling], restart], dtype=np.int32)
-    path = os.path.join(jpeg_cases.GOLDEN, "encjpeg_cases.npz")
     np.savez_compressed(path, **arrays)
     print("%s: %d files, %d bytes; %d of %d coefficients differ" % (path, len(arrays) // 3, os.path.getsize(path), differing, coefs))
+
+
+def main():
+    write(os.path.join(jpeg_cases.GOLDEN, "encjpeg_edges.npz"), edge_cases())
+    if "--cases" not in sys.argv[1:]:
+        return
+    write(os.path.join(jpeg_cases.GOLDEN, "encjpeg_cases.npz"), cases())
     tables = np.zeros((100, 2, 64), dtype=np.uint16)
     for q in range(1, 101):
         _, _, qt = jpeg_cases.decode_blocks(pillow_file(noise(8, 8, q), q, "4:4:4", 0))
